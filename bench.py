@@ -6,8 +6,13 @@ forward rollout + backward sweep + weight-gradient GEMMs through libgops_hip.so)
 all-reduce when N > 1, and the Adam update.  Inputs are synthetic and already resident in HBM.
 Metric (BASELINE.json): env-model steps/s = N * B * H * K / wall time, weak scaling (per-GPU batch
 fixed).  N > 1:  python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...  - or plain
-`python bench.py --gpus N`, which starts the N ranks itself.  The default 1-GPU run also times every other
-BASELINE.json workload briefly and reports them in the `workloads` field of the one JSON line.
+`python bench.py --gpus N`, which starts the N ranks itself.
+
+A plain run only sets up, warms up, times the K steps and prints the result line.  `--full` adds everything else: the
+parity stamp against the reference fixtures, the cold-start figure, per-kernel timings and the roofline, the CPU baseline,
+the N > 1 collective figures and - on one GPU - a brief timing of every other BASELINE.json workload and kernel
+configuration in the `workloads` field of the one JSON line.  `--dump-outputs DIR` writes what the last timed step
+computed (loss, trained parameters and their gradients) as DIR/<name>.npy.
 """
 import argparse
 import contextlib
@@ -466,10 +471,45 @@ def parity_stamp(alg, cfg, workload, device, variant_name):
 
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: total size of the .npy files
+DUMP_SAMPLE = 1 << 20       # entries kept of an array larger than this (a fixed, seeded sample)
+
+
+def step_outputs(alg, tb):
+    """What a caller of the timed update holds after its last step: the loss scalars of the returned log dict (float64) and
+    the networks' parameters with the gradients that step applied (float32), as host arrays keyed by file name."""
+    out = {}
+    for key, v in (tb or {}).items():
+        if key.startswith("Loss/"):
+            name = "".join(c if c.isalnum() else "_" for c in key[len("Loss/"):].lower()).strip("_")
+            out["loss." + name] = np.asarray([float(v)], dtype=np.float64)
+    for name, p in alg.networks.named_parameters():
+        out["param." + name] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            out["grad." + name] = p.grad.detach().float().cpu().numpy()
+    for name, a in out.items():
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            out[name] = a.reshape(-1)[idx]
+    return out
+
+
+def dump_outputs(outputs, path):
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run_workload(workload, dtype, steps, warmup, profile_steps, ctx, flags=0, check_parity=False, overlap=True, label=None,
-                 strict_refpoints=False, dp_path=False, cold_start=False):
+                 strict_refpoints=False, dp_path=False, cold_start=False, checks=True, outputs=False):
     """Times `steps` updates of one workload on this rank's GPU (all ranks call it together) and returns the
     measurements; rank 0 turns them into the record.
+    profile_steps: untimed updates behind the timed ones with per-kernel HIP-event timing (0: none, `kern` is None).
+    checks: the weights are checked for finiteness after the run.  outputs: the result carries step_outputs() of the
+    last timed step.
     strict_refpoints: the algorithm is built with `strict_reference_points=True` (the appended reference points of every update's
     batch are evaluated on the host with the reference's own torch CPU ops, env/env_ocp/resources/ref_traj_host.py); the loop then
     rotates over four batches and asks for the next batch's points before it queues the current update - what a trainer that
@@ -495,20 +535,21 @@ def run_workload(workload, dtype, steps, warmup, profile_steps, ctx, flags=0, ch
     if rotation is not None:
         alg.prefetch_reference_points(rotation[0])
 
-    def step(it):
+    def step(it):   # -> the log dict the update returned
         if rotation is not None:   # a fresh batch per update: its points were asked for one update ago, the next one's are asked for now
             cur = rotation[it % len(rotation)]
             alg.prefetch_reference_points(rotation[(it + 1) % len(rotation)])
-            alg.local_update(cur, it)
+            return alg.local_update(cur, it)
         elif world == 1 and not dp_path:
-            alg.local_update(data, it)
+            return alg.local_update(data, it)
         else:
             if getattr(alg, "supports_overlapped_reduce", False):   # the all-reduce of the early gradients overlaps the rest of the backward
-                _, info = alg.get_remote_update_info(data, it, reducer=reducer)
+                tb, info = alg.get_remote_update_info(data, it, reducer=reducer)
             else:
-                _, info = alg.get_remote_update_info(data, it)   # no host sync: the loss stays on the device
+                tb, info = alg.get_remote_update_info(data, it)   # no host sync: the loss stays on the device
             reducer.average_(info, defer_scale=True)         # flat SUM all-reduce (or the wait for the started ones); 1/N applied inside the Adam kernel
             alg.remote_update(info)
+            return tb
 
     def barrier():
         if world > 1:
@@ -547,35 +588,40 @@ def run_workload(workload, dtype, steps, warmup, profile_steps, ctx, flags=0, ch
         step(preheat + it)
     barrier()
     t0 = time.perf_counter()
+    tb = None
     for it in range(steps):
-        step(preheat + warmup + it)
+        tb = step(preheat + warmup + it)
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    # Per-kernel durations (roofline): HIP events around each launch on the launch stream.  Events
-    # cannot be read back from inside a replayed graph, so the same steps are issued once more as
-    # plain launches (same kernels, same batch, same stream) right after the timed region.
-    graph_mode = os.environ.get("GOPS_HIP_GRAPH")
-    os.environ["GOPS_HIP_GRAPH"] = "0"
-    hb.profile_reset()
-    hb.profile_enable(True)
-    for it in range(profile_steps):
-        step(preheat + warmup + steps + it)
-    barrier()
-    hb.profile_enable(False)
-    if graph_mode is None:
-        del os.environ["GOPS_HIP_GRAPH"]
-    else:
-        os.environ["GOPS_HIP_GRAPH"] = graph_mode
+    # (read before any later update: the log dict and the gradient buffers are reused by the next one)
+    last = step_outputs(alg, tb) if outputs and rank == 0 else None
+    kern = None
+    if profile_steps > 0:
+        # Per-kernel durations (roofline): HIP events around each launch on the launch stream.  Events
+        # cannot be read back from inside a replayed graph, so the same steps are issued once more as
+        # plain launches (same kernels, same batch, same stream) right after the timed region.
+        graph_mode = os.environ.get("GOPS_HIP_GRAPH")
+        os.environ["GOPS_HIP_GRAPH"] = "0"
+        hb.profile_reset()
+        hb.profile_enable(True)
+        for it in range(profile_steps):
+            step(preheat + warmup + steps + it)
+        barrier()
+        hb.profile_enable(False)
+        if graph_mode is None:
+            del os.environ["GOPS_HIP_GRAPH"]
+        else:
+            os.environ["GOPS_HIP_GRAPH"] = graph_mode
+        kern = {k: hb.profile_read(k) for k in range(6)}
+        hb.profile_reset()
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
-    kern = {k: hb.profile_read(k) for k in range(6)}
-    hb.profile_reset()
     # the networks after warmup + steps + profile updates on the fixed synthetic batch: still finite?  (outside the timed region; a
     # half-range overflow of the plane-split kernels poisons gradients with NaN on purpose - it must not go unnoticed in a bench run)
-    finite = all(bool(torch.isfinite(p_).all()) for p_ in alg.networks.parameters())
+    finite = all(bool(torch.isfinite(p_).all()) for p_ in alg.networks.parameters()) if checks else None
     variant = 0
     for ro in list(getattr(alg, "_rollouts", {}).values()) + [o for o in getattr(alg, "_cache", {}).values() if hasattr(o, "desc")]:
         variant |= max(0, hb.lib().gops_rollout_variant(ro.desc))
@@ -593,7 +639,7 @@ def run_workload(workload, dtype, steps, warmup, profile_steps, ctx, flags=0, ch
     torch.cuda.empty_cache()
     hb.DEFAULT_VARIANT_FLAGS = saved_flags
     return {"elapsed": elapsed, "kern": kern, "variant": variant, "parity": parity, "allreduce_payload_bytes": payload, "finite": finite,
-            "refpoint_batches_evaluated": evaluated, "preheat": preheat, "cold_elapsed": cold_elapsed}
+            "refpoint_batches_evaluated": evaluated, "preheat": preheat, "cold_elapsed": cold_elapsed, "outputs": last}
 
 
 def record_of(workload, dtype, steps, warmup, world, m):
@@ -602,8 +648,8 @@ def record_of(workload, dtype, steps, warmup, world, m):
     dt = "f16" if dtype == "fp16" else "f32"
     elapsed, kern = m["elapsed"], m["kern"]
     value = world * B * H * steps / elapsed
-    pmc, pmc_src = pmc_profile(workload, dt)
-    roofline, flops = roofline_of(cfg, dt, kern, pmc, pmc_src, workload, m.get("variant", 0))
+    pmc, pmc_src = pmc_profile(workload, dt) if kern is not None else (None, None)
+    roofline, flops = roofline_of(cfg, dt, kern, pmc, pmc_src, workload, m.get("variant", 0)) if kern is not None else (None, None)
     peak_tf = MFMA_PEAK_TFLOPS[dt]
     bps = bytes_per_step(cfg, dt)
     # whole-update fractions of both roofs (SURVEY 8d asks for both next to each other)
@@ -642,9 +688,10 @@ def record_of(workload, dtype, steps, warmup, world, m):
         "update_traffic_bytes": update_bytes,                        # counters, every kernel of one update
         "update_algorithmic_bytes": 1.5 * bps * B * H,               # stash written once, read by the sweep, read by the weight-gradient GEMMs
         "update_traffic_over_algorithmic": (update_bytes / (1.5 * bps * B * H)) if update_bytes else None,
-        "kernels_ms": {KERNEL_NAMES[k]: {"avg_ms": kern[k][0], "launches": kern[k][1],
-                                         "tflops": (flops[k] / (kern[k][0] * 1e-3) / 1e12) if kern[k][0] > 0 else 0.0}
-                       for k in kern if kern[k][1] > 0},
+        "kernels_ms": None if kern is None else {
+            KERNEL_NAMES[k]: {"avg_ms": kern[k][0], "launches": kern[k][1],
+                              "tflops": (flops[k] / (kern[k][0] * 1e-3) / 1e12) if kern[k][0] > 0 else 0.0}
+            for k in kern if kern[k][1] > 0},
         "kernel_variant": variant_label(m.get("variant", 0), dt),
         "weights_finite_after_run": m.get("finite"),
         "host_sync_per_step": os.environ.get("GOPS_EAGER_LOG", "0") not in ("", "0"),
@@ -666,21 +713,27 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default=None,
-                    help="one BASELINE workload (default: the north_star target as the headline, plus a short timing of every "
-                         "other BASELINE workload in the `workloads` field)")
+                    help="one BASELINE workload (default: the north_star target as the headline; with --full, plus a short timing of "
+                         "every other BASELINE workload in the `workloads` field)")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16"],
                     help="arithmetic of the MLP contractions: fp32 (exact, parity path) or fp16 (half-precision MFMA, BASELINE cfg5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure: parity stamp, cold start, per-kernel timings and "
+                         "roofline, CPU baseline, N > 1 collective figures, and (one GPU, no --workload) every other workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters, gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
     ap.add_argument("--dp-path", action="store_true",
                     help="one rank: time the data-parallel update path (get_remote_update_info with the two-phase backward -> average_ -> "
                          "remote_update) without collectives instead of the fused local update")
     ap.add_argument("--strict-refpoints", action="store_true",
                     help="build the algorithm with strict_reference_points=True (host-evaluated appended reference points, one batch ahead)")
-    ap.add_argument("--no-other-workloads", action="store_true")
+    ap.add_argument("--no-other-workloads", action="store_true", help="(--full) leave out the other workloads")
     ap.add_argument("--eager-gpu-baseline", action=argparse.BooleanOptionalAction, default=True,
-                    help="also time the oracle restatement as PyTorch eager ops on the GPU (FHADP workloads; ~1 s; reported "
+                    help="(--full) also time the oracle restatement as PyTorch eager ops on the GPU (FHADP workloads; ~1 s; reported "
                          "inside cpu_baseline as eager_gpu_steps_per_s)")
     args = ap.parse_args()
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_distributed(args))
@@ -717,10 +770,13 @@ def main():
     ctx = {"rank": rank, "world": world, "device": device, "dist": dist}
 
     workload = args.workload or HEADLINE
-    m = run_workload(workload, args.dtype, args.steps, args.warmup, min(args.steps, 100), ctx, check_parity=True,
-                     dp_path=args.dp_path and world == 1, strict_refpoints=args.strict_refpoints, cold_start=True)
+    m = run_workload(workload, args.dtype, args.steps, args.warmup, min(args.steps, 100) if full else 0, ctx, check_parity=full,
+                     dp_path=args.dp_path and world == 1, strict_refpoints=args.strict_refpoints, cold_start=full, checks=full,
+                     outputs=args.dump_outputs is not None)
     out = record_of(workload, args.dtype, args.steps, args.warmup, world, m) if rank == 0 else None
-    if world > 1:
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(m["outputs"], args.dump_outputs)
+    if world > 1 and full:
         # N > 1: say what carried the gradients, time the collective alone, and time the update loop a second time with the
         # all-reduce NOT overlapped (one flat collective behind the whole backward) - so that a scaling shortfall can be
         # attributed: collective latency (allreduce_us), lost overlap (overlap.on vs .off) or something else
@@ -752,7 +808,7 @@ def main():
                               "what": "the same timed loop with GradAllReducer(overlap=True): FHADP starts the all-reduce of the output / upper "
                                       "layers' gradients behind backward phase A while phase B still runs (headline) - and with overlap=False: "
                                       "one flat all-reduce behind the whole backward"}
-    if args.workload is None and world == 1 and not args.no_other_workloads:
+    if full and args.workload is None and world == 1 and not args.no_other_workloads:
         # the other BASELINE workloads, ~1 s each: same timing method, fewer steps
         others = {}
 
@@ -817,7 +873,7 @@ def main():
         out["strict_fp32_value"] = others["exact_fp32_stationary"]["value"]   # every product an fp32 MFMA (workloads.exact_fp32_stationary)
         out["workloads"] = others
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(CONFIGS[workload], 0, workload, args.eager_gpu_baseline)
         print(json.dumps(out))
     if world > 1:

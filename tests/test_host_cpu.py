@@ -460,13 +460,19 @@ def test_sync_trainer_gradient_exchange_world_size_2(tmp_path):
     assert (tmp_path / "ok_0").exists() and (tmp_path / "ok_1").exists()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/gops"), reason="needs the GOPS tree (build container only)")
 def test_overlay_routes_hot_path_modules_only(tmp_path):
-    """`gops.<hot path>` -> gops_amd, the rest of GOPS untouched (run in a subprocess: it edits sys.modules)."""
+    """`gops.<hot path>` -> gops_amd, the rest of GOPS untouched (run in a subprocess: it edits sys.modules).  The GOPS tree
+    is a stand-in written here: the packages the overlaid modules live in, and two modules the overlay must leave alone."""
+    stub = tmp_path / "stub_gops"
+    for pkg in ("gops", "gops/create_pkg", "gops/algorithm", "gops/apprfunc", "gops/trainer", "gops/trainer/buffer",
+                "gops/trainer/sampler", "gops/utils"):
+        (stub / pkg).mkdir(parents=True)
+        (stub / pkg / "__init__.py").write_text("")
+    (stub / "gops/utils/common_utils.py").write_text("ORIGIN = 'gops tree'\n")
+    (stub / "gops/trainer/sampler/off_sampler.py").write_text("ORIGIN = 'gops tree'\n")
     code = r"""
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)
-import _ref_import; _ref_import.install()            # gym / tensorboard stubs + reference on sys.path
 import gops_amd.overlay as ov; ov.install()
 from gops.create_pkg.create_alg import create_alg
 from gops.create_pkg.create_env_model import create_env_model
@@ -475,12 +481,13 @@ assert create_alg.__module__ == "gops_amd.create_pkg.create_alg"
 assert f.FHADP.__module__ == "gops_amd.algorithm.fhadp" and m.StateValue.__module__ == "gops_amd.apprfunc.mlp"
 import gops.trainer.buffer.replay_buffer as rb, gops.utils.common_utils as cu, gops.trainer.sampler.off_sampler as smp
 assert rb.ReplayBuffer.__module__ == "gops_amd.trainer.buffer.replay_buffer"      # device-resident buffer
-assert cu.__file__.startswith("/root/reference") and smp.__file__.startswith("/root/reference")   # the reference's own
+assert cu.__file__.startswith(%r) and smp.__file__.startswith(%r)   # the GOPS tree's own
+assert cu.ORIGIN == smp.ORIGIN == "gops tree"
 import numpy as np
 buf = rb.ReplayBuffer(index=0, obsv_dim=6, action_dim=1, buffer_max_size=64, seed=0, additional_info={},
                       trainer="off_serial_trainer", buffer_device="cpu")
 print("overlay ok")
-""" % (ROOT, os.path.join(ROOT, "tests", "golden"))
+""" % (ROOT, str(stub), str(stub), str(stub))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "overlay ok" in out.stdout, out.stdout + out.stderr
 

@@ -147,7 +147,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                          "--workload", "cfg1_idp_fhadp_b64_h10"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                          "--workload", "cfg1_idp_fhadp_b64_h10", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout

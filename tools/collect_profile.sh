@@ -18,9 +18,9 @@ export GOPS_HIP_GRAPH=0
 # short runs would carry those launches - per-update averages of the DEFAULT kernels are wanted here
 export GOPS_PRECISION_CHECK_INTERVAL=0
 UPDATES=8
-timeout 400 python $root/bench.py --workload $wl --dtype $dt --steps 100 --warmup 20 > $out/bench.json 2> $out/bench.err
+timeout 400 python $root/bench.py --full --workload $wl --dtype $dt --steps 100 --warmup 20 > $out/bench.json 2> $out/bench.err
 rm -rf /tmp/stats
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats -o s -- python $root/bench.py --workload $wl --dtype $dt --steps 40 --warmup 10 --no-cpu-baseline > /tmp/stats.log 2>&1
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats -o s -- python $root/bench.py --full --workload $wl --dtype $dt --steps 40 --warmup 10 --no-cpu-baseline > /tmp/stats.log 2>&1
 cp $(find /tmp/stats -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 echo $UPDATES > $out/updates.txt
 i=0

@@ -2,7 +2,7 @@
 # A/B of library variants on one bench workload:
 #   WL="--workload cfg5_lq_infadp_b65536 [--dtype fp16]" tools/gpu/ab_workload.sh <tag> <variant> [<variant> ...]   ("base" = the product library)
 root=$(pwd); tag=$1; shift; out=$root/gpurun_out/$tag; mkdir -p $out
-B="python bench.py $WL --no-other-workloads --no-cpu-baseline --steps ${STEPS:-20} --warmup 5"
+B="python bench.py --full $WL --no-other-workloads --no-cpu-baseline --steps ${STEPS:-20} --warmup 5"
 i=0
 for v in "$@"; do
     i=$((i + 1)); lib=gops_amd/libgops_hip_$v.so; [ "$v" = base ] && lib=gops_amd/libgops_hip.so
