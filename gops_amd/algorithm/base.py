@@ -144,7 +144,7 @@ class PrecisionGuard:
     """When must a launch leave the plane-split kernels for exact fp32 products?  A measured rule.
 
     The default 256-wide kernels carry every operand of a hidden-layer contraction as two half planes (22 significant bits,
-    csrc/common.h GOPS_SPLIT_F16X2), i.e. they evaluate the network with weights moved by up to 2^-22 relative - the same
+    csrc/common.h split2h / gemm_split), i.e. they evaluate the network with weights moved by up to 2^-22 relative - the same
     perturbed network for every sample, so this part of the error does not average out over the batch.  On every fixture trained
     by the reference (tests/test_trained256_gpu.py) that is at the level of the exact-fp32 kernels (2e-6 .. 3e-5 against the
     reference; the round-3 planes, 2^-20, put an ill-conditioned closed loop - the pyth_lq policy with a saturated tanh head, whose

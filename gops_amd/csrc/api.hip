@@ -27,7 +27,7 @@ hipError_t launch_upload_params(const RolloutParams& p, RolloutParams* dst, hipS
 hipError_t launch_prologue(const RolloutParams& p, RolloutParams* dst, int P, float pdt, hipStream_t s);
 hipError_t launch_dw_gemm(const float* D, int N, const float* X, int Kp, long long S, int splits,
                           int chunks_per_split, float* part, float* part_b, bool big, hipStream_t s, const float* dscale, unsigned vflags);
-bool dw_skinny_ok(int N, int Kp, unsigned vflags);   // aux_kernels.hip
+bool dw_skinny_ok(int N, int Kp);   // aux_kernels.hip
 hipError_t launch_dw_gemm_f16(const void* D, int N, const void* X, int Kp, long long S, int splits,
                               int chunks_per_split, float* part, float* part_b, hipStream_t s);
 hipError_t launch_dw_out(const float* dy, const float* h, bool h_is_half, int K, int A, long long S, int splits,
@@ -124,52 +124,28 @@ struct DwPlan {
     bool big;
 };
 
-// ---- debug override of the variant flags from the process environment ------------------------------------------------
-// Kernel variants are selected by GopsRolloutDesc.variant_flags / GopsMlp.variant_flags (ABI v10).  The environment knobs of
-// ABI v9 survive as a DEBUG override only: read ONCE, when the first call reaches the library, OR-ed into every description.
-struct EnvOverride {
-    unsigned flags = 0;
-    int l2_warmup = 0;      // as GopsRolloutDesc.l2_warmup (GOPS_TOUCH = mode -> mode + 1)
-    int dw_wgs = 0;
-    bool dbg_timing = false;
-};
-const EnvOverride& env_override() {
-    static const EnvOverride o = [] {
-        struct Knob { const char* name; char match; unsigned bit; int kind; };   // kind 0: flag when set (match 0) / when value[0] == match
-        static const Knob knobs[] = {
-            {"GOPS_SPLIT", '0', GOPS_VF_NO_STATIONARY_SPLIT, 0}, {"GOPS_SS", '0', GOPS_VF_NO_STREAMED_SPLIT_FWD, 0},
-            {"GOPS_SSB", '0', GOPS_VF_NO_STREAMED_SPLIT_BWD, 0}, {"GOPS_SS_VALUE", '0', GOPS_VF_NO_STREAMED_SPLIT_VALUE, 0},
-            {"GOPS_SPLIT_STREAM0", '0', GOPS_VF_NO_SPLIT_STREAM0, 0}, {"GOPS_SPLIT_TAIL_MULTI", 0, GOPS_VF_SPLIT_TAIL_MULTI, 0},
-            {"GOPS_DW_EXACT", 0, GOPS_VF_DW_EXACT, 0}, {"GOPS_DW_F32", 0, GOPS_VF_DW_F32, 0}, {"GOPS_DW_NOGUARD", 0, GOPS_VF_DW_NO_GUARD, 0}, {"GOPS_NO_FUSED_DW0", 0, GOPS_VF_NO_FUSED_DW0, 0},
-            {"GOPS_DW_SKINNY", '0', GOPS_VF_DW_NO_SKINNY, 0}, {"GOPS_DW_SPEC", '0', GOPS_VF_DW_NO_SPEC, 0}, {"GOPS_DW_DIRECT", 0, GOPS_VF_DW_DIRECT, 0},
-            {"GOPS_NO_FUSED_DWOUT", 0, GOPS_VF_NO_FUSED_DWOUT, 0}, {"GOPS_H64", '0', GOPS_VF_NO_HALF_TILE64, 0}, {"GOPS_NARROW", '0', GOPS_VF_NO_NARROW_LDS, 0}, {"GOPS_N64", '0', GOPS_VF_NO_NARROW_N64, 0}, {"GOPS_BWD_UPLOAD", 0, GOPS_VF_BWD_UPLOAD, 0},
-            {"GOPS_SK", 0, 0, 1}, {"GOPS_TOUCH", 0, 0, 2}, {"GOPS_DW_WGS", 0, 0, 3}, {"GOPS_DBG_TIMING", 0, 0, 4}};
-        EnvOverride r;
-        for (const Knob& k : knobs) {
-            const char* e = getenv(k.name);
-            if (e == nullptr) continue;
-            if (k.kind == 0) { if (k.match == 0 || e[0] == k.match) r.flags |= k.bit; }
-            else if (k.kind == 1) {   // GOPS_SK="a,b": 0,0 = plain streamed kernels, 0,16 = layer 0 streamed; any value: stationary at any batch
-                int a = -1, b = -1;
-                r.flags |= GOPS_VF_STATIONARY_ANY_BATCH;
-                if (sscanf(e, "%d,%d", &a, &b) == 2) { if (b == 0) r.flags |= GOPS_VF_STREAMED_FP32; else if (a == 0) r.flags |= GOPS_VF_STREAM_LAYER0; }
-                else if (e[0] == '0') r.flags |= GOPS_VF_STREAMED_FP32;
-            }
-            else if (k.kind == 2) r.l2_warmup = atoi(e) + 1;
-            else if (k.kind == 3) r.dw_wgs = atoi(e);
-            else r.dbg_timing = true;
-        }
-        return r;
+// Phase counters of block 0 (make dbg: GOPS_DBG_BUILD; tools/dbg_run.py with GOPS_DBG_TIMING=1): 16 counters per direction
+// (`slot` 0: forward, 1: backward), or null.  The product library reads no environment and allocates nothing here.
+unsigned long long* dbg_timing_buffer(int slot) {
+#ifdef GOPS_DBG_BUILD
+    static unsigned long long* const buf = [] {
+        unsigned long long* b = nullptr;
+        if (getenv("GOPS_DBG_TIMING") != nullptr) (void)hipMalloc(&b, 32 * sizeof(unsigned long long));
+        return b;
     }();
-    return o;
+    return buf != nullptr ? buf + 16 * slot : nullptr;
+#else
+    (void)slot;
+    return nullptr;
+#endif
 }
 
-DwPlan plan_dw(int N, int Kp, long long S, bool f16 = false, unsigned vflags = 0, int wg_target = 512) {
+DwPlan plan_dw(int N, int Kp, long long S, bool f16 = false, int wg_target = 512) {
     DwPlan d;
     d.big = f16 || (N >= 128 && Kp >= 128);   // the half-precision GEMM has one tile size (128) and 64-sample chunks
     const int T = d.big ? 128 : 64;
     int tiles = ((N + T - 1) / T) * ((Kp + T - 1) / T);
-    if (!f16 && dw_skinny_ok(N, Kp, vflags)) tiles = (N + 255) / 256;   // dw_skinny_kernel: one workgroup per 256 features and split
+    if (!f16 && dw_skinny_ok(N, Kp)) tiles = (N + 255) / 256;   // dw_skinny_kernel: one workgroup per 256 features and split
     const int sc = f16 ? 64 : DW_SC_HOST;
     const long long chunks = (S + sc - 1) / sc;
     if (wg_target < 1) wg_target = 512;
@@ -236,6 +212,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     memset(&p, 0, sizeof(p));
     const GopsEnv& e = desc.env;
     if (desc.batch < 1 || desc.horizon < 1 || desc.horizon > GOPS_MAX_HORIZON) return GOPS_ERR_BAD_ARG;
+    if (desc.variant_flags & ~GOPS_VF_ALL) return GOPS_ERR_BAD_ARG;   // a retired or unknown bit is refused, not ignored (ABI v14)
     if (e.kind < GOPS_ENV_NONE || e.kind > GOPS_ENV_MOBILEROBOT) return GOPS_ERR_BAD_ARG;
     if (e.obs_dim < 1 || e.data_env) return GOPS_ERR_BAD_ARG;   // data-env semantics exist for gops_env_step only
     const int pol_out = (e.kind == GOPS_ENV_NONE) ? 1 : e.act_dim;
@@ -285,8 +262,8 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     fill_ref_defaults(p.env);
     p.open_loop = desc.open_loop == 2 ? 2 : (desc.open_loop ? 1 : 0);
     p.f16 = f16 ? 1 : 0;
-    p.vflags = desc.variant_flags | env_override().flags;
-    p.dw_wgs = desc.dw_workgroups > 0 ? desc.dw_workgroups : (env_override().dw_wgs > 0 ? env_override().dw_wgs : 512);
+    p.vflags = desc.variant_flags;
+    p.dw_wgs = desc.dw_workgroups > 0 ? desc.dw_workgroups : 512;
     if (p.open_loop) {
         // The kernels keep their tile / stash bookkeeping in terms of a policy: give them the
         // smallest one (obs -> 16 -> act, weights zeroed in the workspace); its layers are never
@@ -310,7 +287,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     // the next step's stash rows); with more tiles than CUs the co-resident workgroups hide it, and the warm-up lines are
     // evicted before their use - measured at cfg5 (4096 tiles): 3.8 GB fetched per sweep with it, 1.55 GB without, 1.39 -> 1.24 ms
     p.touch_mode = ((p.B + TB - 1) / TB > split_grid_limit()) ? 0 : 2;
-    if (const int lw = desc.l2_warmup > 0 ? desc.l2_warmup : env_override().l2_warmup) p.touch_mode = lw - 1;   // tuning knob
+    if (desc.l2_warmup > 0) p.touch_mode = desc.l2_warmup - 1;   // tuning knob
     p.ldx = kp0 + 4;
     p.ldh = hmax + 4;
     const bool veh = env_has_ref_table(e.kind);
@@ -444,7 +421,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
         // partial sums can be reduced by a single launch at the end
         for (int j = 0; j < p.pol.nl - 1; ++j) {
             const int Kp = f16 ? p.pol.kp32[j] : p.pol.kp[j];
-            const DwPlan d = plan_dw(p.pol.dims[j + 1], Kp, S, f16, p.vflags, p.dw_wgs);
+            const DwPlan d = plan_dw(p.pol.dims[j + 1], Kp, S, f16, p.dw_wgs);
             size_t nw = (size_t)d.splits * p.pol.dims[j + 1] * Kp, nb = (size_t)d.splits * p.pol.dims[j + 1];
             if (j == 0 && h64_fuses_dw0(p)) {   // one slab [256][8] / [256] per workgroup of the 64-row sweep instead (rollout_h64.hip)
                 nw = std::max(nw, (size_t)h64_sweep_grid(p) * 256 * 8);
@@ -460,16 +437,6 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     plan.bytes = c.off + kAlign;
     return GOPS_OK;
 }
-
-#ifdef GOPS_DUMP
-// debug build only (make variant V=dump VFLAGS=-DGOPS_DUMP): per-thread, per-step record buffer of the streamed-split forward
-#define GOPS_DUMP_BYTES ((size_t)320 << 20)
-float* gops_dump_buffer() {
-    static float* buf = nullptr;
-    if (buf == nullptr) { (void)hipMalloc(&buf, GOPS_DUMP_BYTES); (void)hipMemset(buf, 0, GOPS_DUMP_BYTES); }
-    return buf;
-}
-#endif
 
 float pdt_of(const GopsEnv& e) { return (float)((double)e.pre_horizon * 0.1); }
 
@@ -491,13 +458,8 @@ int run_forward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const Gops
         hipError_t me = launch_fill_zero(plan.dummy, plan.dummy_floats, s);
         if (me != hipSuccess) return (int)me;
     }
-    static unsigned long long* dbg_buf = nullptr;   // debug knob only: GOPS_DBG_TIMING=1
-    const bool dbg = env_override().dbg_timing;
-    if (dbg && dbg_buf == nullptr) (void)hipMalloc(&dbg_buf, 16 * sizeof(unsigned long long));
-    p.dbg = dbg ? dbg_buf : nullptr;
-#ifdef GOPS_DUMP
-    p.dbg = reinterpret_cast<unsigned long long*>(gops_dump_buffer());
-#endif
+    p.dbg = dbg_timing_buffer(0);
+    const bool dbg = p.dbg != nullptr;
     // parameter block upload + weight packing + reference table: one launch
     hipError_t ue = launch_prologue(p, plan.dev_params, desc.env.pre_horizon, pdt_of(desc.env), s);
     if (ue != hipSuccess) return (int)ue;
@@ -508,7 +470,7 @@ int run_forward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const Gops
     }
     if (dbg) {
         unsigned long long h[16];
-        (void)hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(h, p.dbg, sizeof(h), hipMemcpyDeviceToHost);
         if (p.h64)
             fprintf(stderr, "[gops dbg] fwd 64-row half cycles/step: top+sync %llu | convert+xstash+sync %llu | L0 gemm %llu epi %llu sync %llu | "
                     "L1 gemm %llu epi %llu sync %llu | head %llu sync %llu | env %llu\n",
@@ -604,15 +566,13 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
             if ((e = launch_fill_zero(p.st.dy, S0 * 4, s)) != hipSuccess) return (int)e;
         }
     }
-    static unsigned long long* dbg_buf = nullptr;   // debug knob only: GOPS_DBG_TIMING=1
-    const bool dbg = env_override().dbg_timing;
-    if (dbg && dbg_buf == nullptr) (void)hipMalloc(&dbg_buf, 16 * sizeof(unsigned long long));
-    p.dbg = dbg ? dbg_buf : nullptr;
+    p.dbg = dbg_timing_buffer(1);
+    const bool dbg = p.dbg != nullptr;
     // Split sweep: the output layer's weight gradient is accumulated inside the sweep (one partial per workgroup) - no dw_out
     // pass.  (GELU: the sweep's act' operand is gelu'(z), so it fetches H_2 next to it.)
     // (the streamed-split sweep does the same for the env kinds whose instantiation has the registers: ssb_fuses_out)
     const bool fused_out = (p.sp.on || ssb_fuses_out(p)) && !p.ext && !p.open_loop && want_params &&
-                           ext_delta == nullptr && !(p.vflags & GOPS_VF_NO_FUSED_DWOUT);
+                           ext_delta == nullptr;
     const int sweep_grid = std::min((p.B + TB - 1) / TB, p.sp.on ? split_grid_limit() : ssb_grid_limit());
     if (fused_out) {
         p.sp.out_part = plan.dw_part[p.pol.nl - 1];
@@ -643,7 +603,6 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
         q.ad_snap = p.gscale + 4;
         q.ad_b1 = tail->beta1; q.ad_b2 = tail->beta2;
     }
-    const bool force_upload = (p.vflags & GOPS_VF_BWD_UPLOAD) != 0;   // measurement knob: the pre-patch launch sequence
     // GOPS_VF_BWD_PHASE_A / _B: the call is one half of a backward (see gops_hip.h); only_b skips the sweep
     const unsigned phase = p.vflags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B);
     const bool only_a = phase == GOPS_VF_BWD_PHASE_A, only_b = phase == GOPS_VF_BWD_PHASE_B;
@@ -655,7 +614,7 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
     // forward's prologue zeroes it, and every backward call leaves it zero behind its last reader: fp32 calls that end with the
     // split-K reduce reset it there (ReduceJobs.reset: no extra launch - round 5; it was a 1-block fill in front of every sweep),
     // the others (half precision: the reduce itself reads it; open loop / no parameter gradients: no reduce) with a fill at their end.
-    if ((p.f16 || force_upload) && (e = launch_upload_params(p, plan.dev_params, s)) != hipSuccess) return (int)e;
+    if (p.f16 && (e = launch_upload_params(p, plan.dev_params, s)) != hipSuccess) return (int)e;
     {
         ProfScope scope(desc.env.kind == GOPS_ENV_NONE ? 4 : 1, s);
         if ((e = launch_rollout_bwd(p, plan.dev_params, q, s)) != hipSuccess) return (int)e;
@@ -663,7 +622,7 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
     }   // !only_b
     if (dbg) {
         unsigned long long h[16];
-        (void)hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(h, p.dbg, sizeof(h), hipMemcpyDeviceToHost);
         if (p.h64)
             fprintf(stderr, "[gops dbg] bwd 64-row half cycles/step: env adjoint %llu sync %llu | head %llu sync %llu | gemm %llu sync %llu epi %llu sync %llu | "
                     "g_x %llu | end sync %llu\n", h[0] / p.H, h[1] / p.H, h[2] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, h[7] / p.H, h[8] / p.H,
@@ -698,7 +657,7 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
     for (int j = 0; j < L; ++j) {   // dW_j = D_{j+1}^T * (j == 0 ? X : H_j)
         if ((only_a && j == 0) || (only_b && j != 0)) continue;   // (two-phase backward: layer 0 is phase B)
         const int N = p.pol.dims[j + 1], Kp = p.f16 ? p.pol.kp32[j] : p.pol.kp[j], K = p.pol.dims[j];
-        const DwPlan d = plan_dw(N, Kp, S, p.f16 != 0, p.vflags, p.dw_wgs);
+        const DwPlan d = plan_dw(N, Kp, S, p.f16 != 0, p.dw_wgs);
         const float* X = (j == 0) ? p.st.x : p.st.h[j];
         if (j == 0 && fuse_dw0) {   // formed inside the 64-row sweep: one slab per workgroup
             reduce_jobs_add(jobs, plan.dw_part[0], h64_sweep_grid(p), N, K, 8, grad.weight[0]);
@@ -807,8 +766,7 @@ int plan_mlp(const GopsMlp& mlp, int batch, void* ws, MlpPlan& m) {
     m.gv = c.take((size_t)batch);
     m.gh = c.take((size_t)m.S * m.K);
     m.gyp = c.take((size_t)m.S * m.Wp);
-    const unsigned vf = mlp.variant_flags | env_override().flags;
-    const DwPlan d = plan_dw(m.Wp, m.K, m.S, false, vf);
+    const DwPlan d = plan_dw(m.Wp, m.K, m.S);
     m.part = c.take((size_t)d.splits * m.Wp * m.K);
     m.part_b = c.take((size_t)d.splits * m.Wp);
     m.bytes = m.inner + c.off + kAlign;
@@ -820,13 +778,6 @@ int plan_mlp(const GopsMlp& mlp, int batch, void* ws, MlpPlan& m) {
 }  // namespace
 
 extern "C" {
-
-#ifdef GOPS_DUMP
-int gops_dbg_dump_read(void* host, size_t bytes) {
-    (void)hipDeviceSynchronize();
-    return (int)hipMemcpy(host, gops_dump_buffer(), bytes < GOPS_DUMP_BYTES ? bytes : GOPS_DUMP_BYTES, hipMemcpyDeviceToHost);
-}
-#endif
 
 size_t gops_mlp_workspace_bytes(const GopsMlp* mlp, int32_t batch) {
     if (!mlp) return 0;
@@ -874,9 +825,9 @@ static int mlp_backward_impl(const GopsMlp* mlp, int32_t batch, const float* x, 
     Plan inner;
     build_plan(m.d, workspace, inner);
     if (grad) {
-        const unsigned vf = mlp->variant_flags | env_override().flags;
-        const DwPlan d = plan_dw(m.Wp, m.K, m.S, false, vf);
-        if ((e = launch_dw_gemm(m.gyp, m.Wp, inner.p.st.h[L], m.K, m.S, d.splits, d.chunks_per_split, m.part, m.part_b, d.big, s, nullptr, vf)) != hipSuccess)
+        const DwPlan d = plan_dw(m.Wp, m.K, m.S);
+        if ((e = launch_dw_gemm(m.gyp, m.Wp, inner.p.st.h[L], m.K, m.S, d.splits, d.chunks_per_split, m.part, m.part_b, d.big, s, nullptr,
+                                mlp->variant_flags)) != hipSuccess)
             return (int)e;
         ReduceJobs jobs;
         memset(&jobs, 0, sizeof(jobs));

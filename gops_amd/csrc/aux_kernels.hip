@@ -60,13 +60,7 @@ __device__ __forceinline__ void pack_element_h(const float* __restrict__ W, int 
 //   forward,  layer j: column = OUTPUT feature 16 nt + col, slot s <-> input feature (j == 0 ? s : split_perm(s))
 //   backward, layer j: column = INPUT feature 16 nt + col,  slot s <-> output feature split_perm(s)
 // element ((c * 64 + lane) * 8 + i) of the tile = (column lane & 15, slot 32 c + 8 (lane >> 4) + i): the B operand of
-// v_mfma_f32_16x16x32_{bf16,f16} for chunk c.  w1 = bf16(w) (round to nearest even), rf = f16((w - w1) * s_r) with the
-// power of two s_r that brings the tile's largest residual into [2^13, 2^14); inv[nt] = 1 / s_r.
-__device__ __forceinline__ float bf16_round(float w) {
-    unsigned u = __float_as_uint(w);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return __uint_as_float(u & 0xffff0000u);
-}
+// v_mfma_f32_16x16x32_f16 for chunk c.  w1 / rf: the hi / lo half planes of w s_w (below); inv[nt] = 1 / s_w.
 __device__ __forceinline__ void pack_split_tile(const float* __restrict__ W, int N, int K, bool transposed, bool perm_slots,
                                                 int kc, int nt, unsigned short* __restrict__ w1, _Float16* __restrict__ rf,
                                                 float* __restrict__ inv) {
@@ -79,7 +73,6 @@ __device__ __forceinline__ void pack_split_tile(const float* __restrict__ W, int
         if (!transposed) return (col < N && f < K) ? W[(size_t)col * K + f] : 0.f;   // W[out = col][in = f]
         return (f < N && col < K) ? W[(size_t)f * K + col] : 0.f;                     // W[out = f][in = col]
     };
-#if GOPS_SPLIT_F16X2
     // two half planes of w s_w: wh = f16(w s_w) (round to nearest), wl = f16((w s_w - wh) 2^11); s_w = the power of two that brings the
     // tile's largest |w| into [2^13, 2^14) - fp32's exponent range for the weights, and small-weight tiles use the half's normal range.
     // The tile's <= 16 elements per thread are loaded ONCE, all loads in flight together (a load - use - load loop costs one L2 round
@@ -118,34 +111,6 @@ __device__ __forceinline__ void pack_split_tile(const float* __restrict__ W, int
     }
     if (tid == 0) inv[nt] = 1.f / s_w;
 }
-#else
-    float mx = 0.f;
-    for (int e = tid; e < total; e += 256) {
-        const float w = wval(e);
-        mx = fmaxf(mx, fabsf(w - bf16_round(w)));
-    }
-    red[tid] = mx;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) red[tid] = fmaxf(red[tid], red[tid + h]);
-        __syncthreads();
-    }
-    mx = red[0];
-    float s_r = 1.f;
-    if (mx > 0.f && mx < 3.0e38f) {
-        int ex;
-        (void)frexpf(mx, &ex);   // mx = f * 2^ex, f in [0.5, 1)
-        s_r = ldexpf(1.f, 14 - ex);
-    }
-    const size_t off = (size_t)nt * total;
-    for (int e = tid; e < total; e += 256) {
-        const float w = wval(e), h = bf16_round(w);
-        w1[off + e] = (unsigned short)(__float_as_uint(h) >> 16);
-        rf[off + e] = (_Float16)((w - h) * s_r);
-    }
-    if (tid == 0) inv[nt] = 1.f / s_r;
-}
-#endif
 // The fp32 MFMA-fragment packings (wp / wpt) of the POLICY are read by the exact-fp32 kernels only.  A veh3dofconti launch on the
 // register-stationary plane-split kernels never reaches one - its sweep is the stationary plane-split sweep, and the calls that
 // would divert a backward to the fp32 kernels after the forward has planned (terminal adjoints / gops_rollout_backward_adj,
@@ -201,28 +166,8 @@ __global__ __launch_bounds__(256) void upload_params_kernel(const RolloutParams 
 // Streams that are read ONCE (stash operands of the weight-gradient GEMMs, split-K partials) are loaded with the non-temporal
 // policy: MI355X_MICROARCH.md measures LDS-DMA fills 18 % earlier with `nt` and 6.5 - 6.8 instead of 6.4 TB/s chip-wide; here the
 // wave-specialised GEMM went from 4.2 to 4.9 TB/s (target: weight-gradient group 140 -> 126 us) - the data does not displace
-// the other kernels' working set in L2 / MALL either.  GOPS_DW_NT=0: default policy (A/B).
-#ifndef GOPS_DW_NT
-#define GOPS_DW_NT 1
-#endif
-#if GOPS_DW_NT
-#define DW_STREAM_LOAD(ptr) __builtin_nontemporal_load(ptr)
-#define DW_NT_SUFFIX " nt"
-#else
-#define DW_STREAM_LOAD(ptr) (*(ptr))
-#define DW_NT_SUFFIX ""
-#endif
-
-// common.h async_copy16_to_lds with the stream policy above (the weight-gradient GEMMs' stash operands)
-__device__ __forceinline__ void dw_async_copy16_to_lds(const float* gsrc, const float* lds_base) {
-    const unsigned m0v = __builtin_amdgcn_readfirstlane(
-        (unsigned)(size_t)(const __attribute__((address_space(3))) void*)lds_base);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off" DW_NT_SUFFIX "\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gptr(gsrc)), "s"(m0v)
-                 : "memory");
-}
+// the other kernels' working set in L2 / MALL either.
+#define DW_STREAM_LOAD(ptr) __builtin_nontemporal_load(ptr)   // (LDS-DMA fills of these streams: async_copy16_to_lds<true>)
 
 hipError_t launch_upload_params(const RolloutParams& p, RolloutParams* dst, hipStream_t s) {
     static_assert(sizeof(RolloutParams) % 4 == 0, "parameter block must be dword sized");
@@ -530,12 +475,6 @@ hipError_t launch_prologue(const RolloutParams& p, RolloutParams* dst, int P, fl
 
 // 8 fp32 samples of one feature -> the three bf16x8 plane fragments
 __device__ __forceinline__ void split_frag(const f32x4& lo, const f32x4& hi, bf16x8 (&pl)[3]) {
-#ifdef GOPS_EXP_NOSPLIT
-    const u32x4 v0 = {__float_as_uint(lo[0]), __float_as_uint(lo[1]), __float_as_uint(lo[2]), __float_as_uint(lo[3])};
-    const u32x4 v1 = {__float_as_uint(hi[0]), __float_as_uint(hi[1]), __float_as_uint(hi[2]), __float_as_uint(hi[3])};
-    pl[0] = __builtin_bit_cast(bf16x8, v0); pl[1] = __builtin_bit_cast(bf16x8, v1); pl[2] = __builtin_bit_cast(bf16x8, v0 ^ v1);
-    return;
-#endif
     unsigned p0[3], p1[3], p2[3], p3[3];
     split3(lo[0], lo[1], p0);
     split3(lo[2], lo[3], p1);
@@ -708,18 +647,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void dw_gemm_fm_kernel(const float* __
 // [16, 32).  Range: |x * s| >= 65504 saturates (round toward zero never produces inf); the converting threads watch for it
 // and a workgroup whose operands saturated repeats ITS blocks with the exact three-plane split before it stores anything -
 // a diverged rollout costs time, never a wrong gradient.
-#ifndef GOPS_DW_H2_MODE
-#define GOPS_DW_H2_MODE 2   // 1: lo planes scaled by 2^11, two accumulators, one workgroup per CU (r03: 251 us at the target, slower than the
-                            // exact split); 2: unscaled lo planes, ONE accumulator, two workgroups per CU (177 us; the matrix core takes
-                            // subnormal half inputs as they are - measured: same 2e-7 distance to the exact GEMM as mode 1)
-#endif
-#if GOPS_DW_H2_MODE == 2
 #define DW_H2_SA 1.0f      // (unscaled lo planes: keep typical magnitudes near 1 so that lo stays a normal half)
 #define DW_H2_LO 1.0f
-#else
-#define DW_H2_SA 0.0625f   // activations / observations: up to 1.05e6 before the main term saturates
-#define DW_H2_LO 2048.f
-#endif
 __device__ __forceinline__ void split2h(const f32x4& lo4, const f32x4& hi4, float s, f16x8& ph, f16x8& pl) {
     const float s2 = s * DW_H2_LO;
     u32x4 uh, ul;
@@ -740,7 +669,6 @@ __device__ __forceinline__ void split2h(const f32x4& lo4, const f32x4& hi4, floa
 // destination) - 4 VALU per element pair instead of the 6 hipcc emits for the expression above (v_mul x 2, v_cvt_pkrtz, v_fma_mix x 2,
 // v_cvt_pkrtz).  Rounding is to nearest here (toward zero there): lo then needs one bit less, the pair carries the same 22 bits;
 // |s x| >= 65520 becomes inf instead of saturating - the callers' range watch (vmax < 65504) is on the fp32 values and unchanged.
-#if GOPS_DW_H2_MODE == 2
 __device__ __forceinline__ void split2h_mix(const f32x4& lo4, const f32x4& hi4, float s, f16x8& ph, f16x8& pl) {
     u32x4 uh, ul;
 #pragma unroll
@@ -757,9 +685,6 @@ __device__ __forceinline__ void split2h_mix(const f32x4& lo4, const f32x4& hi4, 
     ph = __builtin_bit_cast(f16x8, uh);
     pl = __builtin_bit_cast(f16x8, ul);
 }
-#else
-#define split2h_mix split2h
-#endif
 // running maximum of |a|, |b| in one instruction (hipcc spells fmaxf(m, fmaxf(fabsf(a), fabsf(b))) as two canonicalising v_max + v_max3)
 __device__ __forceinline__ void absmax2(float& m, float a, float b) { asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a), "v"(b)); }
 
@@ -782,7 +707,7 @@ __device__ __forceinline__ float dw_delta_yardstick(const float* dscale) {
 // per block, 4 per thread, the same items every block (so the bias column sums accumulate in the converting thread).  The
 // MFMA phase then reads ready-made operands (two ds_read_b128 per fragment) and issues no VALU work at all.
 template <bool H2>
-__global__ __launch_bounds__(NTHREADS, (H2 && GOPS_DW_H2_MODE == 1) ? 1 : 2) void dw_gemm_ring_kernel(const float* __restrict__ D, int N,
+__global__ __launch_bounds__(NTHREADS, 2) void dw_gemm_ring_kernel(const float* __restrict__ D, int N,
                                                                     const float* __restrict__ X, int Kp,
                                                                     long long Q, int splits, int chunks_per_split,
                                                                     float* __restrict__ part,
@@ -815,16 +740,14 @@ __global__ __launch_bounds__(NTHREADS, (H2 && GOPS_DW_H2_MODE == 1) ? 1 : 2) voi
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int feat = u * 16 + (lane >> 2);
-            dw_async_copy16_to_lds(feat < kvalid ? src + u * 256 : src + u * 256 - (size_t)(feat - (feat % kvalid)) * 16, dst + u * 256);
+            async_copy16_to_lds<true>(feat < kvalid ? src + u * 256 : src + u * 256 - (size_t)(feat - (feat % kvalid)) * 16, dst + u * 256);
         }
     };
 
     f32x4 acc[R][R] = {};
-    constexpr bool TWO_ACC = H2 && GOPS_DW_H2_MODE == 1;
-    f32x4 accx[TWO_ACC ? R : 1][TWO_ACC ? R : 1] = {};   // cross terms (dh * al + dl * ah), scaled by 2^11
     float bsum[R] = {0.f, 0.f, 0.f, 0.f};
     float sd = 1.f;
-    if constexpr (H2) sd = f16_grad_scale(dw_delta_yardstick(dscale)) * (GOPS_DW_H2_MODE == 2 ? 16.f : 0.015625f);
+    if constexpr (H2) sd = f16_grad_scale(dw_delta_yardstick(dscale)) * 16.f;
     auto block = [&]<bool LAST_HALF_EMPTY, bool M2>(int stage) {
         const float* st = ring + stage * DWR_STAGE_FLOATS;
         const float* da = st + (wn * 64 + f) * 16 + 4 * g;          // D fragments of row-tile i: + 256 i  (+ 2048: second tile)
@@ -840,26 +763,15 @@ __global__ __launch_bounds__(NTHREADS, (H2 && GOPS_DW_H2_MODE == 1) ? 1 : 2) voi
 #pragma unroll
             for (int i = 0; i < R; ++i) {
                 const f16x8 ah = *reinterpret_cast<const f16x8*>(da + 256 * i), al = *reinterpret_cast<const f16x8*>(da + 256 * i + 2048);
-                if constexpr (TWO_ACC) {
 #pragma unroll
-                    for (int j = 0; j < R; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[j], accx[i][j], 0, 0, 0);
+                for (int j = 0; j < R; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[j], acc[i][j], 0, 0, 0);
 #pragma unroll
-                    for (int j = 0; j < R; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[j], accx[i][j], 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < R; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < R; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[j], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < R; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[j], acc[i][j], 0, 0, 0);
 #pragma unroll
                 for (int j = 0; j < R; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[j], acc[i][j], 0, 0, 0);
             }
             return;
         }
-#ifdef GOPS_EXP_NOMFMA
-        acc[0][0] += *reinterpret_cast<const f32x4*>(xa) + *reinterpret_cast<const f32x4*>(da);
-        return;
-#endif
         bf16x8 b[R][3];
 #pragma unroll
         for (int j = 0; j < R; ++j) {
@@ -962,7 +874,6 @@ __global__ __launch_bounds__(NTHREADS, (H2 && GOPS_DW_H2_MODE == 1) ? 1 : 2) voi
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float v = acc[i][j][r];
-                if constexpr (TWO_ACC) v = fmaf(accx[i][j][r], 1.f / 2048.f, v);
                 if constexpr (H2) v *= unscale;
                 pbase[(size_t)(nb + 16 * i + 4 * g + r) * Kp + k] = v;
             }
@@ -996,19 +907,13 @@ __global__ __launch_bounds__(NTHREADS, (H2 && GOPS_DW_H2_MODE == 1) ? 1 : 2) voi
 // the co-resident workgroup falls into the same rhythm.  Here the two kinds of work run side by side on every SIMD:
 //   * 512 threads, one workgroup per CU, 256 x 128 outputs (every delta element is fetched and converted by ONE workgroup
 //     per K-tile), three 48-KiB stages [D q0][D q0+1][X q0][X q0+1] of 32 samples;
-//   * waves 0-3 CONVERT block c + 1 in place (fp32 -> hi / lo half planes, 6 items per thread) while waves 4-7 MULTIPLY
-//     block c (128 x 64 outputs per wave, 96 MFMAs); all eight waves issue the LDS-DMA copies of block c + 2 (6 KiB each);
-//   * ONE barrier per block: converted block c + 1 is published, block c's stage is free for the copies of block c + 3,
-//     and each wave has waited for its own copies of block c + 2.
+//   * waves 0-3 load the fp32 fragments of later blocks into their registers and CONVERT block c + 2 into a stage (fp32 ->
+//     hi / lo half planes, 6 items per thread) while waves 4-7 MULTIPLY block c (128 x 64 outputs per wave, 96 MFMAs) - the
+//     register-direct feed in the kernel below;
+//   * ONE barrier per block: converted block c + 2 is published, block c's stage is free for the conversion of block c + 3.
 // Saturated half planes (a diverged rollout): the workgroup repeats its blocks with the exact three-plane split on the same
-// four multiplying waves, from unconverted stages.
+// four multiplying waves, from fp32 stages copied again (dw_spec_exact_pass).
 // ---------------------------------------------------------------------------------------------
-#ifndef DW_SPEC_REGDIRECT
-#define DW_SPEC_REGDIRECT 1
-#endif
-#ifndef DW_SPEC_RAW3
-#define DW_SPEC_RAW3 0   // three (1) or two (0) blocks of raw fragments in the converting waves' registers
-#endif
 struct DwSpec {
     static constexpr int NW = 8, NT = 512, TN = 256, T = 128;
     static constexpr int DT = TN * 16;                       // floats of one D sample tile
@@ -1042,59 +947,8 @@ __device__ __forceinline__ void dw_spec_copy(const DwSpecGeo& G, float* ring, in
         if (isx && grp >= G.xgroups) grp %= G.xgroups;
         const size_t bq = (size_t)min(b0 + st_tile, G.Q - 1);
         const float* src = (isx ? G.xbase + bq * ((size_t)G.Kp * 16) : G.dbase + bq * ((size_t)G.N * 16)) + grp * 256 + 4 * lane;
-        dw_async_copy16_to_lds(src, dst + u * 256);
+        async_copy16_to_lds<true>(src, dst + u * 256);
     }
-}
-// The same copies with their address arithmetic taken out of the loop.  A piece is wave-uniform (only the 16 bytes per lane inside
-// it differ), its source moves by a constant number of bytes from block to block: the base lives in an SGPR pair that one
-// s_add_u32 / s_addc_u32 advances, the lane's offset in ONE VGPR, and the copy is `global_load_lds_dwordx4 voff, s[base]`.
-// dw_spec_copy above recomputes every piece's 64-bit address with ~25 VALU / SALU instructions - 150 per wave and block in all
-// eight waves, next to the 96 MFMAs of a multiplying wave and the ~150 VALU of a converting one, and VALU and MFMA issue time ADD
-// on a SIMD.  Not for the last block of a split whose second sample tile does not exist (clamped there: dw_spec_copy).
-struct DwSpecSrc {
-    unsigned long long p[DwSpec::PIECES];   // source of this wave's piece u in the NEXT block to copy (wave-uniform, without the lane offset)
-    unsigned long long stride_d, stride_x;  // bytes from block c to block c + 1 of a split
-};
-__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
-    return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v) |   // (the builtin returns int: no sign extension)
-           ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32);
-}
-__device__ __forceinline__ void dw_spec_src_init(const DwSpecGeo& G, int wave, DwSpecSrc& S) {
-    constexpr int T = DwSpec::T, TN = DwSpec::TN, PC = DwSpec::PIECES;
-    const long long b0 = (long long)G.split * 2;
-#pragma unroll
-    for (int u = 0; u < PC; ++u) {
-        const int pc = wave * PC + u;
-        const bool isx = pc >= 2 * (TN / 16);
-        const int q = isx ? pc - 2 * (TN / 16) : pc, per = isx ? T / 16 : TN / 16;
-        const int st_tile = q / per;
-        int grp = q - st_tile * per;
-        if (isx && grp >= G.xgroups) grp %= G.xgroups;
-        const size_t bq = (size_t)(b0 + st_tile);
-        const float* src = (isx ? G.xbase + bq * ((size_t)G.Kp * 16) : G.dbase + bq * ((size_t)G.N * 16)) + grp * 256;
-        S.p[u] = uniform64((unsigned long long)(size_t)src);
-    }
-    S.stride_d = uniform64((unsigned long long)G.splits * 2ull * (unsigned long long)G.N * 64ull);
-    S.stride_x = uniform64((unsigned long long)G.splits * 2ull * (unsigned long long)G.Kp * 64ull);
-}
-__device__ __forceinline__ void dw_spec_copy_next(DwSpecSrc& S, float* ring, int stage, int wave, int lane) {
-    constexpr int TN = DwSpec::TN, PC = DwSpec::PIECES;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane(
-        (unsigned)(size_t)(const __attribute__((address_space(3))) void*)(ring + stage * DwSpec::STAGE_FLOATS + wave * PC * 256));
-    const unsigned voff = 16u * (unsigned)lane;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0" : "=s"(keep));
-#pragma unroll
-    for (int u = 0; u < PC; ++u) {
-        const unsigned long long src = uniform64(S.p[u]);   // (loop-carried: hipcc may keep it in VGPRs - two v_readfirstlane then)
-        asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" DW_NT_SUFFIX : : "v"(voff), "s"(src), "s"(lds0 + 1024u * u) : "memory");
-        S.p[u] += (wave * PC + u >= 2 * (TN / 16)) ? S.stride_x : S.stride_d;
-    }
-    asm volatile("s_mov_b32 m0, %0" : : "s"(keep));
-}
-__device__ __forceinline__ void dw_spec_skip(DwSpecSrc& S, int wave) {   // a block copied by dw_spec_copy: keep the running sources in step
-#pragma unroll
-    for (int u = 0; u < DwSpec::PIECES; ++u) S.p[u] += (wave * DwSpec::PIECES + u >= 2 * (DwSpec::TN / 16)) ? S.stride_x : S.stride_d;
 }
 __device__ __forceinline__ void dw_spec_store(const DwSpecGeo& G, const f32x4 (&acc)[8][4], int wn, int wk, int f, int g, float unscale) {
     const int nb = G.tile_n * DwSpec::TN + wn * 128, kb = G.tile_k * DwSpec::T + wk * 64;
@@ -1181,80 +1035,16 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_spec_kernel(const float* __res
     G.pbase = part + (size_t)split * N * Kp;
     const int nblk = G.nblk, nfull = G.nfull;
 
-#if !DW_SPEC_REGDIRECT
-    // multiplying waves: 128 x 64 outputs each
-    const int mw = wave & 3, wn = mw >> 1, wk = mw & 1;
-    f32x4 acc[8][4] = {};
-    const float sd = f16_grad_scale(dw_delta_yardstick(dscale)) * 16.f;
-    auto block_h2 = [&](int stage) {
-        const float* st = ring + stage * SF;
-        const float* da = st + (wn * 128 + f) * 16 + 4 * g;            // D fragments of row-tile i: + 256 i  (lo plane: + DT)
-        const float* xa = st + 2 * DT + (wk * 64 + f) * 16 + 4 * g;    // X fragments of column-tile j: + 256 j  (lo plane: + 2048)
-        f16x8 bh[4], bl[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            bh[j] = *reinterpret_cast<const f16x8*>(xa + 256 * j);
-            bl[j] = *reinterpret_cast<const f16x8*>(xa + 256 * j + 2048);
-        }
-        // D fragments double-buffered behind scheduling barriers (left alone, hipcc hoists all sixteen reads: 64 registers, spills)
-        f16x8 ah = *reinterpret_cast<const f16x8*>(da), al = *reinterpret_cast<const f16x8*>(da + DT);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            f16x8 nh = ah, nl = al;
-            if (i + 1 < 8) {
-                nh = *reinterpret_cast<const f16x8*>(da + 256 * (i + 1));
-                nl = *reinterpret_cast<const f16x8*>(da + 256 * (i + 1) + DT);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            ah = nh; al = nl;
-        }
-    };
-
-#else
     const int mw = wave & 3, wn = mw >> 1, wk = mw & 1;
     const float sd = f16_grad_scale(dw_delta_yardstick(dscale)) * 16.f;
-#endif
     // converting waves (threads 0 .. 255): items k < 4: D feature (tid >> 2) + 64 k, k = 4, 5: X feature (tid >> 2) + 64 (k - 4);
     // sample group tid & 3.  The same items every block: the bias column sums accumulate in the converting thread.
     float vmax = 0.f, vmax_d = 0.f, vmax_x = 0.f;   // largest |delta| / |activation| this thread converted (unscaled; folded into vmax at the end)
     float csum[4] = {0.f, 0.f, 0.f, 0.f};
     const bool want_csum = part_b != nullptr && G.tile_k == 0;   // (the bias gradient = column sums of D: once per row of output tiles)
-    auto convert_stage = [&]<bool LAST_HALF_EMPTY>(int stage) {
-        float* st = ring + stage * SF;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const bool isd = k < 4;
-            const int fe = (tid >> 2) + 64 * (isd ? k : k - 4), gg = tid & 3, second = isd ? DT : 2048;
-            float* at = st + (isd ? 0 : 2 * DT) + fe * 16 + 4 * gg;
-            const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(at);
-            const f32x4 v1 = LAST_HALF_EMPTY ? zero4 : *reinterpret_cast<const f32x4*>(at + second);
-            if (isd && want_csum) csum[k & 3] += ((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3]));
-            float& vm = isd ? vmax_d : vmax_x;
-            absmax2(vm, v0[0], v0[1]); absmax2(vm, v0[2], v0[3]);
-            absmax2(vm, v1[0], v1[1]); absmax2(vm, v1[2], v1[3]);
-            f16x8 ph, pl;
-            split2h_mix(v0, v1, isd ? sd : DW_H2_SA, ph, pl);
-            *reinterpret_cast<f16x8*>(at) = ph;
-            *reinterpret_cast<f16x8*>(at + second) = pl;
-        }
-    };
-    auto landed_and_sync = [&]() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    };
-    (void)convert_stage; (void)landed_and_sync;   // (used by the LDS-DMA ring form only: DW_SPEC_REGDIRECT 0)
 
     unsigned* sat = reinterpret_cast<unsigned*>(ring + NST * SF);
     if (tid == 0) *sat = 0u;
-#if DW_SPEC_REGDIRECT
     // Register-direct feed (round 6).  The LDS-DMA ring gave a block's copies ONE iteration to land and kept <= 48 KiB per CU in
     // flight - knock-out builds: without the MFMAs -10 us, without the conversion -1 us, i.e. the copy path set the pace (4.2 TB/s).
     // Here the four converting waves LOAD the fp32 fragments themselves (non-temporal 16-byte loads: a wave's instruction covers
@@ -1340,9 +1130,7 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_spec_kernel(const float* __res
 
         __syncthreads();                                  // blocks 0, 1 converted
         for (int c = 0; c < nblk; ++c) {
-#ifndef DW_KO_MFMA   // (knock-out builds: what does each kind of work cost?)
             block_h2(c % NST);
-#endif
             __syncthreads();
         }
         __syncthreads();                                  // the converting waves' verdict on the half range
@@ -1353,29 +1141,6 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_spec_kernel(const float* __res
         dw_spec_store(G, acc, wn, wk, f, g, 1.f / (sd * DW_H2_SA));   // (powers of two: exact)
         return;
     }
-#if DW_SPEC_RAW3
-    Raw r2;
-    load_block(0, r0);   // blocks 0, 1 converted, blocks 2, 3, 4 in flight
-    if (nblk > 1) load_block(1, r1);
-    if (nblk > 2) load_block(2, r2);
-    convert_block(r0, 0);
-    if (nblk > 3) load_block(3, r0);
-    if (nblk > 1) convert_block(r1, 1);
-    if (nblk > 4) load_block(4, r1);
-    __syncthreads();
-    auto iteration = [&](int c, Raw& r) {   // r holds block c + 2
-        if (c + 2 < nblk) {
-            convert_block(r, (c + 2) % NST);
-            if (c + 5 < nblk) load_block(c + 5, r);
-        }
-        __syncthreads();
-    };
-    for (int c = 0; c < nblk; c += 3) {   // block c + 2 sits in r2, r0, r1, r2, ...
-        iteration(c, r2);
-        if (c + 1 < nblk) iteration(c + 1, r0);
-        if (c + 2 < nblk) iteration(c + 2, r1);
-    }
-#else
     load_block(0, r0);   // blocks 0, 1 converted, blocks 2, 3 in flight
     if (nblk > 1) load_block(1, r1);
     convert_block(r0, 0);
@@ -1385,12 +1150,8 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_spec_kernel(const float* __res
     __syncthreads();
     auto iteration = [&](int c, Raw& r) {   // r holds block c + 2
         if (c + 2 < nblk) {
-#ifndef DW_KO_CONV
             convert_block(r, (c + 2) % NST);   // (stage of block c - 1: its multiplication ended before the last barrier)
-#endif
-#ifndef DW_KO_COPY
             if (c + 4 < nblk) load_block(c + 4, r);
-#endif
         }
         __syncthreads();
     };
@@ -1398,40 +1159,6 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_spec_kernel(const float* __res
         iteration(c, r0);
         if (c + 1 < nblk) iteration(c + 1, r1);
     }
-#endif
-#else
-    DwSpecSrc SRC;
-    const int uwave = __builtin_amdgcn_readfirstlane(wave);   // (the compiler cannot see that tid >> 6 is wave-uniform: keeps the sources in SGPRs)
-    dw_spec_src_init(G, uwave, SRC);
-    auto copy_block = [&](int c) {   // blocks are copied in order 0, 1, 2, ...; only a split's last block may lack its second sample tile
-        if (c < nfull) dw_spec_copy_next(SRC, ring, c % NST, uwave, lane);
-        else { dw_spec_copy(G, ring, c, c % NST, wave, lane); dw_spec_skip(SRC, uwave); }
-    };
-    copy_block(0);
-    if (nblk > 1) copy_block(1);
-    landed_and_sync();
-    if (!mul_wave) {
-        if (0 < nfull) convert_stage.template operator()<false>(0);
-        else convert_stage.template operator()<true>(0);
-    }
-    __syncthreads();
-    for (int c = 0; c < nblk; ++c) {
-#ifndef DW_KO_COPY   // (knock-out builds: tools/gpu/scratch - what does each kind of work cost?)
-        if (c + 2 < nblk) copy_block(c + 2);
-#endif
-        if (mul_wave) {
-#ifndef DW_KO_MFMA
-            block_h2(c % NST);
-#endif
-        } else if (c + 1 < nblk) {
-#ifndef DW_KO_CONV
-            if (c + 1 < nfull) convert_stage.template operator()<false>((c + 1) % NST);
-            else convert_stage.template operator()<true>((c + 1) % NST);
-#endif
-        }
-        landed_and_sync();
-    }
-#endif
     if (!mul_wave) {
         vmax = fmaxf(vmax_d * sd, vmax_x * DW_H2_SA);
         if (!(vmax < 65504.f)) *sat = 1u;
@@ -1450,9 +1177,6 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_spec_kernel(const float* __res
         dw_spec_exact_pass(G, ring);
         return;
     }
-#if !DW_SPEC_REGDIRECT
-    if (mul_wave) dw_spec_store(G, acc, wn, wk, f, g, 1.f / (sd * DW_H2_SA));   // (powers of two: exact)
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1537,15 +1261,11 @@ __global__ __launch_bounds__(NTHREADS, 3) void dw_skinny_kernel(const float* __r
         }
     }
 }
-// GOPS_VF_DW_NO_SKINNY: the 64 x 64-tile kernel for these layers too
-bool dw_skinny_ok(int N, int Kp, unsigned vflags) {
-    return !(vflags & GOPS_VF_DW_NO_SKINNY) && Kp == 16 && (N % 16) == 0;
-}
+// The layers the 16-input kernel takes
+bool dw_skinny_ok(int N, int Kp) { return Kp == 16 && (N % 16) == 0; }
 
-// The layers the wave-specialised kernel takes (GOPS_VF_DW_NO_SPEC: the 4-wave ring kernel)
-static bool dw_spec_ok(int N, int Kp, unsigned vflags) {
-    return !(vflags & GOPS_VF_DW_NO_SPEC) && (N % 256) == 0 && ((Kp % 128) == 0 || (Kp > 128 && (Kp % 16) == 0));
-}
+// The layers the wave-specialised kernel takes (the others of the two-half-plane GEMM: the 4-wave ring kernel)
+static bool dw_spec_ok(int N, int Kp) { return (N % 256) == 0 && ((Kp % 128) == 0 || (Kp > 128 && (Kp % 16) == 0)); }
 
 // dscale: device pointer to max|grad_v| of the launch (the deltas' magnitude reference), or null: with it the large
 // layers run the two-half-plane products (22 significant bits per operand), without it - or with GOPS_DW_EXACT set -
@@ -1558,10 +1278,9 @@ hipError_t launch_dw_gemm(const float* D, int N, const float* X, int Kp, long lo
     const long long Q = (S + TB - 1) / TB;
     const int T = big ? 128 : 64, tiles = ((N + T - 1) / T) * ((Kp + T - 1) / T);
     const dim3 grid(tiles * ((splits + 7) / 8) * 8), block(NTHREADS);
-    const bool no_ring = (vflags & GOPS_VF_DW_DIRECT) != 0;   // A/B knob: register-direct kernel for the large layers too
-    if (big && !force_f32 && !no_ring && (N % 128) == 0 && ((Kp % 128) == 0 || (Kp > 128 && (Kp % 16) == 0))) {
+    if (big && !force_f32 && (N % 128) == 0 && ((Kp % 128) == 0 || (Kp > 128 && (Kp % 16) == 0))) {
         const float* none = nullptr;
-        if (dscale != nullptr && !force_exact && dw_spec_ok(N, Kp, vflags)) {
+        if (dscale != nullptr && !force_exact && dw_spec_ok(N, Kp)) {
             const dim3 grids(((N / 256) * ((Kp + 127) / 128)) * ((splits + 7) / 8) * 8);
             launch_with_lds(dw_gemm_spec_kernel, grids, dim3(512), DwSpec::lds_bytes(), s, D, N, X, Kp, Q, splits, part, part_b, dscale,
                             no_guard ? 0 : 1);
@@ -1573,7 +1292,7 @@ hipError_t launch_dw_gemm(const float* D, int N, const float* X, int Kp, long lo
                             splits, chunks_per_split, part, part_b, none, 1);
         }
     }
-    else if (!force_f32 && dw_skinny_ok(N, Kp, vflags))
+    else if (!force_f32 && dw_skinny_ok(N, Kp))
         hipLaunchKernelGGL(dw_skinny_kernel, dim3(((N + 255) / 256) * ((splits + 7) / 8) * 8), block, 0, s, D, N, X, Q, splits, part, part_b);
     else if (big && !force_f32) hipLaunchKernelGGL((dw_gemm_fm_kernel<4, true>), grid, block, 0, s, D, N, X, Kp, Q, splits, chunks_per_split, part, part_b);
     else if (big) hipLaunchKernelGGL((dw_gemm_fm_kernel<4, false>), grid, block, 0, s, D, N, X, Kp, Q, splits, chunks_per_split, part, part_b);

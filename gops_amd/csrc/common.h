@@ -63,9 +63,8 @@ struct MlpDev {
 // Plane-split contractions of the register-stationary kernels (policy: obs -> 256 -> 256 -> act, fp32 results): every fp32
 // operand of a hidden-layer contraction is carried as two 16-bit planes (2 + 2 bytes, the register footprint of the fp32 value)
 // and the products run on 16-cycle v_mfma_f32_16x16x32_* with fp32 accumulation instead of 8 x 32-cycle v_mfma_f32_16x16x4_f32
-// per 32-deep block.  WHICH planes: the GOPS_SPLIT_F16X2 block below (default: two half planes per operand, 3 MFMAs; the
-// round-3 form - w = bf16(w) + f16 residual, a = three exact bf16 planes + one half plane, 4 MFMAs - stays behind the switch).
-// The member types name the round-3 planes; the F16X2 packing stores half bit patterns in both (gemm_split bit-casts).
+// per 32-deep block.  WHICH planes: the block below (two half planes per operand, 3 MFMAs).
+// The member types name the round-3 planes (bf16 + f16); the packing stores half bit patterns in both (gemm_split bit-casts).
 struct SplitDev {
     int on;                     // 1: the stationary kernels run the plane-split contractions (else fp32 MFMA)
     int kc[2];                  // 32-wide k-chunks of hidden layer j's input
@@ -87,11 +86,9 @@ struct SplitNetDev {
     const float* inv[GOPS_MAX_LAYERS - 1];
 };
 __host__ __device__ inline int ss_kc0(int kp32) { const int c = kp32 >> 5; return c <= 1 ? 1 : (c <= 2 ? 2 : (c <= 4 ? 4 : 8)); }
-#ifndef GOPS_PIN_MODE
-#define GOPS_PIN_MODE 2   // layer-1 bf16 planes of the split kernels pinned to AGPRs (StatQ PIN; modes 1 / 2 / 3 measured within 1 %, r03)
-#endif
+constexpr int SPLIT_PIN_MODE = 2;   // layer-1 bf16 planes of the split kernels pinned to AGPRs (StatQ PIN; modes 1 / 2 / 3 measured within 1 %, r03)
 // ---- which plane split the contractions run on ----------------------------------------------------------------------------
-// GOPS_SPLIT_F16X2 = 1 (round 5, default): BOTH operands as two half planes.
+// Round 5: BOTH operands as two half planes.
 //     w s_w = wh + wl / 2^11   with wh = f16(w s_w) (round to nearest), wl = f16((w s_w - wh) 2^11), s_w the power of two that brings
 //                           the n-tile's largest |w| into [2^13, 2^14) (packing kernel): 22 significant bits - the systematic part
 //                           of the error (the same perturbed network for every sample: it does not average out over the batch)
@@ -102,39 +99,23 @@ __host__ __device__ inline int ss_kc0(int kp32) { const int c = kp32 >> 5; retur
 //   s: a power of two that keeps the planes inside the half range: SPLIT_FWD_SA in the forward (below), per tile and step from
 //   max|delta_y| in the sweep (as before).  Nothing is clamped: a value beyond the range converts to inf, every conversion
 //   records it (split2h's `ovf`) and the kernels poison the tile's results with NaN at tile end - an overflow is LOUD.
-//   Against the bf16x3 + f16 form: 3 instead of 4 matrix instructions, 2 instead of 4 plane images in LDS (half the plane
-//   stores and A-fragment reads), ~5 instead of ~8 VALU instructions per element split.
-// GOPS_SPLIT_F16X2 = 0: the round-3 form (three exact bf16 planes of the activation, bf16 + scaled f16 planes of the weight).
-#ifndef GOPS_SPLIT_F16X2
-#define GOPS_SPLIT_F16X2 1
-#endif
-#if GOPS_SPLIT_F16X2
+//   Against the round-3 form (three exact bf16 planes of the activation, bf16 + scaled f16 planes of the weight): 3 instead of
+//   4 matrix instructions, 2 instead of 4 plane images in LDS (half the plane stores and A-fragment reads), ~5 instead of ~8
+//   VALU instructions per element split.
 // forward scale of the activation planes: 2^-4 puts the top of the half range at |a| = 1.05e6 and keeps 22 bits down to
 // |a| = 1e-3 (below that the two planes still resolve 2^-32 ABSOLUTE: hi and lo both run into half subnormals, lo's at 2^-35 / s).
 // Beyond the range the conversion yields inf and the rollout returns non-finite values - loudly, like the reference's own overflow,
 // only earlier; the algorithm classes' PrecisionGuard treats a non-finite distance as exceeded and moves to the exact-fp32 rollout kernels.
 #define SPLIT_FWD_SA 0.0625f
 #define SPLIT_LO_SCALE 2048.0f   // 2^11: the residual planes of both operands
-#else
-#define SPLIT_FWD_SA 0.015625f  // forward: af = f16(a / 64): the correction term saturates only beyond |a| = 4.2e6; below |a| = 4e-3 af is a
-                                // subnormal half (absolute error 4e-6 * 2^-8 |w| per term: under the fp32 rounding of a unit-sized term)
-#endif
 // forward pre-activation z = a W + b from the two accumulators of a plane-split contraction (activation planes scaled by SPLIT_FWD_SA)
 __device__ __forceinline__ float split_preact(float acc, float accr, float inv, float bias) {
-#if GOPS_SPLIT_F16X2
     return fmaf(fmaf(accr, 1.f / SPLIT_LO_SCALE, acc), inv * (1.f / SPLIT_FWD_SA), bias);   // inv = 1 / (the n-tile's weight scale)
-#else
-    return fmaf(accr, inv * (1.f / SPLIT_FWD_SA), acc) + bias;
-#endif
 }
-// result of a plane-split contraction from its two accumulators: `inv` = 1 / (the n-tile's weight scale; bf16 + f16 form: of its
-// residual plane), `inv_s` = 1 / (scale the caller put on the activation planes)
+// result of a plane-split contraction from its two accumulators: `inv` = 1 / (the n-tile's weight scale), `inv_s` = 1 / (scale
+// the caller put on the activation planes)
 __device__ __forceinline__ float split_combine(float acc, float accr, float inv, float inv_s) {
-#if GOPS_SPLIT_F16X2
     return fmaf(accr, 1.f / SPLIT_LO_SCALE, acc) * (inv * inv_s);   // both planes of both operands carry their scale
-#else
-    return fmaf(accr, inv * inv_s, acc);      // only the half plane of the activation is scaled
-#endif
 }
 // position e of a hidden tile's plane row (the order plane_store writes, = the contraction order of the next GEMM) -> feature
 __host__ __device__ inline int split_perm(int e) { return 64 * (e >> 6) + 16 * (e & 3) + ((e & 63) >> 2); }
@@ -195,7 +176,7 @@ struct RolloutParams {
     SplitNetDev ssp, ssv;             //   planes of the policy / the tail value net
     SplitNetDev sspt, ssvt;           //   streamed-split SWEEP (ssb): transposed planes (n-tiles over a layer's inputs, 8 chunks over its outputs)
     int ssb;
-    unsigned vflags;                  // GOPS_VF_* of the description (| the debug override of the process environment, read once at load)
+    unsigned vflags;                  // GOPS_VF_* of the description
     int dw_wgs;                       // target workgroup count of a weight-gradient GEMM
     int h64;                          // 1: GOPS_DTYPE_F16 launch on the 64-trajectory-tile kernels (rollout_h64.hip): stash rows in 64-row tiles
     int narrow;                       // 1 / 2: plain streamed fp32 kernels with the packed hidden-layer weights of the POLICY resident in LDS (narrow nets;
@@ -421,9 +402,6 @@ __device__ __forceinline__ float act_fwd_t(float z) {
 // case, just above the switch point), the odd series up to x^7 below |x| = 1/8 (truncation 2e-10); branch-free.  libm's
 // tanhf is ~200 instructions with divergent branches and sat on the critical path of every step (head -> action).
 __device__ __forceinline__ float fast_tanh(float x) {
-#ifdef GOPS_EXACT_TANH   // A/B knob (make variant VFLAGS=-DGOPS_EXACT_TANH): libm's tanhf in the plane-split kernels too
-    return tanhf(x);
-#endif
     const float ax = fabsf(x), x2 = x * x;
     const float t = __expf(-2.f * ax);
     const float big = (1.f - t) * __builtin_amdgcn_rcpf(1.f + t);
@@ -589,12 +567,6 @@ __device__ __forceinline__ void split3(float a, float b, unsigned (&pl)[3]) {
     const float sa = ra - __uint_as_float(va & 0xffff0000u), sb = rb - __uint_as_float(vb & 0xffff0000u);
     pl[2] = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
 }
-// (a, b) -> packed half pair, round to nearest (v_cvt_pk_f16_f32), saturating at +-65504 instead of producing inf
-__device__ __forceinline__ unsigned pk_half(float a, float b) {
-    const f16x2 h = {(_Float16)__builtin_amdgcn_fmed3f(a, -65504.f, 65504.f), (_Float16)__builtin_amdgcn_fmed3f(b, -65504.f, 65504.f)};
-    return __builtin_bit_cast(unsigned, h);
-}
-
 // (a, b) * s -> packed half pairs hi, lo with x = hi + lo / 2^11 to 2^-22 |x| (x = a s): hi = f16(x) (round to nearest),
 // lo = f16((x - hi) 2^11) - x - hi is exact in fp32, |lo| <= |x|: lo never overflows before hi does
 // `ovf`: running packed maximum of |hi| as 16-bit patterns (v_pk_max_u16): any half >= 0x7c00 (inf / nan) means a value left the
@@ -632,7 +604,6 @@ __device__ __forceinline__ void plane_store(char* planes, int rowb, int wave, in
     char* base = planes + ((lane >> 4) << 2) * rowb + 128 * wave + 8 * (lane & 15);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-#if GOPS_SPLIT_F16X2
         u32x2 hi, lo;
         unsigned h0, l0, h1, l1;
         split2h(v[0][r], v[1][r], s16, h0, l0, ovf);
@@ -640,18 +611,6 @@ __device__ __forceinline__ void plane_store(char* planes, int rowb, int wave, in
         hi[0] = h0; hi[1] = h1; lo[0] = l0; lo[1] = l1;
         *reinterpret_cast<u32x2*>(base + r * rowb) = hi;
         *reinterpret_cast<u32x2*>(base + r * rowb + pstride) = lo;
-#else
-        unsigned p01[3], p23[3];
-        split3(v[0][r], v[1][r], p01);
-        split3(v[2][r], v[3][r], p23);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            const u32x2 w = {p01[pl], p23[pl]};
-            *reinterpret_cast<u32x2*>(base + r * rowb + pl * pstride) = w;
-        }
-        const u32x2 h = {pk_half(v[0][r] * s16, v[1][r] * s16), pk_half(v[2][r] * s16, v[3][r] * s16)};
-        *reinterpret_cast<u32x2*>(base + r * rowb + 3 * pstride) = h;
-#endif
     }
 }
 
@@ -663,7 +622,6 @@ __device__ __forceinline__ void plane_convert_x(const float* xs, int ldx, int kp
         f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
         if (c < kp) { a = *reinterpret_cast<const f32x4*>(xs + m * ldx + c); b = *reinterpret_cast<const f32x4*>(xs + m * ldx + c + 4); }
         char* dst = planes + m * rowb + 16 * u;
-#if GOPS_SPLIT_F16X2
         u32x4 hi, lo;
         unsigned h, l;
         split2h(a[0], a[1], s16, h, l, ovf); hi[0] = h; lo[0] = l;
@@ -672,17 +630,6 @@ __device__ __forceinline__ void plane_convert_x(const float* xs, int ldx, int kp
         split2h(b[2], b[3], s16, h, l, ovf); hi[3] = h; lo[3] = l;
         *reinterpret_cast<u32x4*>(dst) = hi;
         *reinterpret_cast<u32x4*>(dst + pstride) = lo;
-#else
-        unsigned p0[3], p1[3], p2[3], p3[3];
-        split3(a[0], a[1], p0); split3(a[2], a[3], p1); split3(b[0], b[1], p2); split3(b[2], b[3], p3);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            const u32x4 w = {p0[pl], p1[pl], p2[pl], p3[pl]};
-            *reinterpret_cast<u32x4*>(dst + pl * pstride) = w;
-        }
-        const u32x4 h = {pk_half(a[0] * s16, a[1] * s16), pk_half(a[2] * s16, a[3] * s16), pk_half(b[0] * s16, b[1] * s16), pk_half(b[2] * s16, b[3] * s16)};
-        *reinterpret_cast<u32x4*>(dst + 3 * pstride) = h;
-#endif
     }
 }
 
@@ -801,7 +748,6 @@ __device__ __forceinline__ void gemm_split(const char* planes, int rowb, const S
                                            f32x4 (&acc)[NT], f32x4 (&accr)[NT]) {
     const int pstride = TB * rowb;
     const char* arow = planes + (lane & 15) * rowb + (lane >> 4) * 16;
-#if GOPS_SPLIT_F16X2
     // (the `w` plane of StatQ holds half values in this form: its bf16x8 type is the 16-byte container)
     f16x8 ah = *reinterpret_cast<const f16x8*>(arow), al = *reinterpret_cast<const f16x8*>(arow + pstride);
 #pragma unroll
@@ -829,41 +775,6 @@ __device__ __forceinline__ void gemm_split(const char* planes, int rowb, const S
         __builtin_amdgcn_sched_barrier(0);
         ah = nh; al = nl;
     }
-#else
-    bf16x8 a1 = *reinterpret_cast<const bf16x8*>(arow), a2 = *reinterpret_cast<const bf16x8*>(arow + pstride);
-    bf16x8 a3 = *reinterpret_cast<const bf16x8*>(arow + 2 * pstride);
-    f16x8 af = *reinterpret_cast<const f16x8*>(arow + 3 * pstride);
-#pragma unroll
-    for (int c = 0; c < KCH; ++c) {
-        f16x8 rr[NT];
-        if constexpr (RLDS) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) rr[j] = W.rl[(j * KCH + c) * 64];
-        }
-        bf16x8 n1 = a1, n2 = a2, n3 = a3;
-        f16x8 nf = af;
-        if (c + 1 < KCH) {
-            n3 = *reinterpret_cast<const bf16x8*>(arow + 64 * (c + 1) + 2 * pstride);
-            n2 = *reinterpret_cast<const bf16x8*>(arow + 64 * (c + 1) + pstride);
-            n1 = *reinterpret_cast<const bf16x8*>(arow + 64 * (c + 1));
-            nf = *reinterpret_cast<const f16x8*>(arow + 64 * (c + 1) + 3 * pstride);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, W.w[c * NT + j], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, W.w[c * NT + j], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, W.w[c * NT + j], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            if constexpr (RLDS) accr[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, rr[j], accr[j], 0, 0, 0);
-            else accr[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, W.r[c * NT + j], accr[j], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        a1 = n1; a2 = n2; a3 = n3; af = nf;
-    }
-#endif
 }
 
 // Plane-split weights of a layer that does NOT stay on the CU (layer 0 of policies with more than 128 inputs: its planes
@@ -928,7 +839,6 @@ __device__ __forceinline__ void gemm_split_pair(const char* planes, int rowb, co
     const int pstride = TB * rowb;
     const int o[2] = {W.off(2 * pair), W.off(2 * pair + 1)};
     const char* arow = planes + (lane & 15) * rowb + (lane >> 4) * 16;
-#if GOPS_SPLIT_F16X2
     f16x8 ah = *reinterpret_cast<const f16x8*>(arow), al = *reinterpret_cast<const f16x8*>(arow + pstride);
 #pragma unroll
     for (int c = 0; c < KCH; ++c) {
@@ -955,41 +865,6 @@ __device__ __forceinline__ void gemm_split_pair(const char* planes, int rowb, co
         }
         ah = nh; al = nl;
     }
-#else
-    bf16x8 a1 = *reinterpret_cast<const bf16x8*>(arow), a2 = *reinterpret_cast<const bf16x8*>(arow + pstride);
-    bf16x8 a3 = *reinterpret_cast<const bf16x8*>(arow + 2 * pstride);
-    f16x8 af = *reinterpret_cast<const f16x8*>(arow + 3 * pstride);
-#pragma unroll
-    for (int c = 0; c < KCH; ++c) {
-        const int slot = c % PF;
-        bf16x8 n1 = a1, n2 = a2, n3 = a3;
-        f16x8 nf = af;
-        if (c + 1 < KCH) {
-            n3 = *reinterpret_cast<const bf16x8*>(arow + 64 * (c + 1) + 2 * pstride);
-            n2 = *reinterpret_cast<const bf16x8*>(arow + 64 * (c + 1) + pstride);
-            n1 = *reinterpret_cast<const bf16x8*>(arow + 64 * (c + 1));
-            nf = *reinterpret_cast<const f16x8*>(arow + 64 * (c + 1) + 3 * pstride);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, ring.w[slot][j], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, ring.w[slot][j], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, ring.w[slot][j], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) accr[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, ring.r[slot][j], accr[j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (c + PF < KCH) {   // refill the slot behind the MFMAs that read it: in flight during the next PF - 1 chunks
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                ring.w[slot][j] = W.frag_w(o[j], c + PF);
-                ring.r[slot][j] = W.frag_r(o[j], c + PF);
-            }
-        }
-        a1 = n1; a2 = n2; a3 = n3; af = nf;
-    }
-#endif
 }
 
 // One layer of the streamed-split kernels: this wave's four n-tiles (of nt_tot; surplus tiles recompute tile 0) over KCH
@@ -1040,7 +915,9 @@ __device__ __forceinline__ void split_delta_scale(float mx, float* out) {
 // operand holds the matching B values so that one dwordx4 load per lane feeds four MFMAs.
 // Streamed B operand: PF chunks of fragments are kept in flight ahead of the MFMAs (L2 latency is
 // 500+ cycles under load).  prime() may be called well before run() to hide the first fetch.
-template <int NT>
+// EXACT_REFILL: refill a ring slot only while there is a chunk to fetch (the forward kernels).  Else the refill is clamped to the
+// last chunk, a redundant load (the backward kernels: their register allocation degrades with the exact form).
+template <bool EXACT_REFILL, int NT>
 struct StreamB {
     static constexpr int PF = (NT >= 4) ? 1 : 4;
     f32x4 ring[PF][NT];
@@ -1065,18 +942,18 @@ struct StreamB {
                     f32x4 bcur[NT];
 #pragma unroll
                     for (int j = 0; j < NT; ++j) bcur[j] = ring[d][j];
-#ifdef GOPS_STREAMB_EXACT_REFILL
-                    // refill only while there is a chunk to fetch: a clamped (redundant) load stays pending on its
-                    // registers and makes the next GEMM that re-uses them drain vmcnt(0) in front of its first MFMA
-                    if (c + PF < kchunks) {
+                    if constexpr (EXACT_REFILL) {
+                        // a clamped (redundant) load stays pending on its registers and makes the next GEMM that re-uses
+                        // them drain vmcnt(0) in front of its first MFMA
+                        if (c + PF < kchunks) {
 #pragma unroll
-                        for (int j = 0; j < NT; ++j) ring[d][j] = wbase[((size_t)j * kchunks + c + PF) * 64];
+                            for (int j = 0; j < NT; ++j) ring[d][j] = wbase[((size_t)j * kchunks + c + PF) * 64];
+                        }
+                    } else {
+                        const int cn = (c + PF < kchunks) ? c + PF : kchunks - 1;
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) ring[d][j] = wbase[((size_t)j * kchunks + cn) * 64];
                     }
-#else
-                    const int cn = (c + PF < kchunks) ? c + PF : kchunks - 1;
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) ring[d][j] = wbase[((size_t)j * kchunks + cn) * 64];
-#endif
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -1089,11 +966,11 @@ struct StreamB {
     }
 };
 
-template <int NT>
+template <bool EXACT_REFILL, int NT>
 __device__ __forceinline__ void mfma_gemm(const float* __restrict__ A, int lda, int kchunks,
                                           const f32x4* __restrict__ Wp, int nt0, int lane,
                                           f32x4 (&acc)[NT]) {
-    StreamB<NT> sb;
+    StreamB<EXACT_REFILL, NT> sb;
     sb.prime(Wp, kchunks, nt0, lane, 0);
     sb.run(A, lda, kchunks, lane, acc, 0);
 }
@@ -1101,7 +978,7 @@ __device__ __forceinline__ void mfma_gemm(const float* __restrict__ A, int lda, 
 // One dense layer on the tile: out tiles are dealt to the 4 waves in contiguous groups, each wave
 // walks its group 4 / 2 / 1 MFMA n-tiles at a time and hands the finished 16x16 accumulators
 // (tile nt0+q: rows 4*(lane>>4)+r, column 16*(nt0+q) + (lane&15)) to `epi.operator()<COUNT>(acc, nt0)`.
-template <class Epi>
+template <bool EXACT_REFILL, class Epi>
 __device__ __forceinline__ void gemm_layer(const float* A, int lda, int kch, int nt_tot,
                                            const f32x4* Wp, int tid, Epi&& epi) {
     const int lane = tid & 63, wave = tid >> 6;
@@ -1112,17 +989,17 @@ __device__ __forceinline__ void gemm_layer(const float* A, int lda, int kch, int
         const int left = nt_end - nt;
         if (left >= 4) {
             f32x4 acc[4] = {};
-            mfma_gemm<4>(A, lda, kch, Wp, nt, lane, acc);
+            mfma_gemm<EXACT_REFILL, 4>(A, lda, kch, Wp, nt, lane, acc);
             epi.template operator()<4>(acc, nt);
             nt += 4;
         } else if (left >= 2) {
             f32x4 acc[4] = {};
-            mfma_gemm<2>(A, lda, kch, Wp, nt, lane, reinterpret_cast<f32x4(&)[2]>(acc));
+            mfma_gemm<EXACT_REFILL, 2>(A, lda, kch, Wp, nt, lane, reinterpret_cast<f32x4(&)[2]>(acc));
             epi.template operator()<2>(acc, nt);
             nt += 2;
         } else {
             f32x4 acc[4] = {};
-            mfma_gemm<1>(A, lda, kch, Wp, nt, lane, reinterpret_cast<f32x4(&)[1]>(acc));
+            mfma_gemm<EXACT_REFILL, 1>(A, lda, kch, Wp, nt, lane, reinterpret_cast<f32x4(&)[1]>(acc));
             epi.template operator()<1>(acc, nt);
             nt += 1;
         }
@@ -1188,7 +1065,7 @@ __device__ __forceinline__ void settle_loads() { __builtin_amdgcn_s_waitcnt(0x0F
 
 // K-chunks 0..KCH-1 come from the stationary fragments, chunks KCH..kch_total-1 (if any) are
 // streamed from the packed weights like mfma_gemm does.
-template <int KCH, int NT, class Epi>
+template <bool EXACT_REFILL, int KCH, int NT, class Epi>
 __device__ __forceinline__ void gemm_layer_stat(const float* A, int lda, const StatW<KCH, NT>& W,
                                                 int nt_tot, int tid, Epi&& epi, int kch_total = KCH,
                                                 const f32x4* Wp = nullptr) {
@@ -1196,7 +1073,7 @@ __device__ __forceinline__ void gemm_layer_stat(const float* A, int lda, const S
     if (nt0 >= nt_tot) return;
     const float* arow = A + (lane & 15) * lda + 4 * (lane >> 4);
     f32x4 acc[NT] = {};
-    StreamB<NT> sb;
+    StreamB<EXACT_REFILL, NT> sb;
     if (kch_total > KCH) sb.prime(Wp, kch_total, nt0, lane, KCH);   // fetched behind the stationary MFMAs
     f32x4 a_cur = *reinterpret_cast<const f32x4*>(arow);
 #pragma unroll

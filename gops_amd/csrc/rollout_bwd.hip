@@ -8,13 +8,8 @@
 #include <type_traits>
 
 #include "common.h"
-#ifndef GOPS_SWEEP_STAGE_NT
-#define GOPS_SWEEP_STAGE_NT true   // the stash rows the sweep stages one step ahead are read once by this launch
-#endif
-#ifndef GOPS_IDP_BWD_UNROLL
-#define GOPS_IDP_BWD_UNROLL 1   // the five sub-step adjoints of pyth_idpendulum unrolled: the parking reads of all of them issue up front (cfg2 sweep 197 -> 181 us)
-#endif
 #include "env_models.h"
+constexpr bool SWEEP_STAGE_NT = true;   // the stash rows the sweep stages one step ahead are read once by this launch
 #include "rollout_f16.h"
 
 // LDS floats of the per-tile buffers (everything except the optional staged tiles at the end).
@@ -129,14 +124,14 @@ __device__ __forceinline__ void mlp_backward(const MlpDev& M, const W0T& WT0, co
         auto epi = delta_epi(j, out, stage_h1, false);   // (staged variants: L == 2, so j == 1 only)
         bool done = false;
         if constexpr (!std::is_same<W1T, NoW>::value) {
-            if (j == 1) { gemm_layer_stat(cur, ldh, WT1, nt_tot, tid, epi); done = true; }
+            if (j == 1) { gemm_layer_stat<false>(cur, ldh, WT1, nt_tot, tid, epi); done = true; }
         }
         if (!done) {
             if (narrow != nullptr) {
                 gemm_layer_lds(cur, ldh, kch, nt_tot, narrow, tid, epi);
                 narrow += kch * nt_tot * 64;
             } else {
-                gemm_layer(cur, ldh, kch, nt_tot, M.wpt[j], tid, epi);
+                gemm_layer<false>(cur, ldh, kch, nt_tot, M.wpt[j], tid, epi);
             }
         }
         DBG_TICK(6)
@@ -167,9 +162,9 @@ __device__ __forceinline__ void mlp_backward(const MlpDev& M, const W0T& WT0, co
                 }
             }
         };
-        if constexpr (!std::is_same<W0T, NoW>::value) gemm_layer_stat(cur, ldh, WT0, nt_tot, tid, epi, kch, M.wpt[0]);
+        if constexpr (!std::is_same<W0T, NoW>::value) gemm_layer_stat<false>(cur, ldh, WT0, nt_tot, tid, epi, kch, M.wpt[0]);
         else if (narrow != nullptr) gemm_layer_lds(cur, ldh, kch, nt_tot, narrow, tid, epi);
-        else gemm_layer(cur, ldh, kch, nt_tot, M.wpt[0], tid, epi);
+        else gemm_layer<false>(cur, ldh, kch, nt_tot, M.wpt[0], tid, epi);
         DBG_TICK(9)
     }
 }
@@ -269,7 +264,7 @@ template <int PT0, int AMAX>
 struct SplitSweep {
     float dwo[AMAX][4];          // dW_o[a][64 wave + 16 q + (lane & 15)], partial over rows 4 (lane >> 4) .. +3
     float dbo[AMAX];             // d b_o[a], same partial
-    static constexpr int PIN1 = (AMAX == 2) ? 3 : GOPS_PIN_MODE;   // (rollout_fwd.hip SplitPolicy: both planes pinned for veh3dofconti: sweep 187.0 -> 183.8 us)
+    static constexpr int PIN1 = (AMAX == 2) ? 3 : SPLIT_PIN_MODE;   // (rollout_fwd.hip SplitPolicy: both planes pinned for veh3dofconti: sweep 187.0 -> 183.8 us)
     StatQ<8, 4, false, PIN1> QT1;      // delta_2 -> delta_1 through W_1: both planes in registers
     // delta_1 -> g_x through W_0: bf16 plane in registers, half residual plane in LDS; more than 128 inputs (PT0 > 2 n-tiles
     // per wave): both planes stream from L2 (StreamQ, common.h)
@@ -772,18 +767,18 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
         if constexpr (!SPLIT) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                async_copy16_to_lds<GOPS_SWEEP_STAGE_NT>(src2 + wv * 1024 + q * 256 + 4 * ln, dst + wv * 1024 + q * 256);
-                async_copy16_to_lds<GOPS_SWEEP_STAGE_NT>(src1 + wv * 1024 + q * 256 + 4 * ln, dst + TB * 256 + wv * 1024 + q * 256);
+                async_copy16_to_lds<SWEEP_STAGE_NT>(src2 + wv * 1024 + q * 256 + 4 * ln, dst + wv * 1024 + q * 256);
+                async_copy16_to_lds<SWEEP_STAGE_NT>(src1 + wv * 1024 + q * 256 + 4 * ln, dst + TB * 256 + wv * 1024 + q * 256);
             }
         }
         if (wv == 0)        // env rows: 16 x 64 B, contiguous
-            async_copy16_to_lds<GOPS_SWEEP_STAGE_NT>(hst_env + r0 * ENV_STASH + 4 * ln, dst + STAGE_TILES);
+            async_copy16_to_lds<SWEEP_STAGE_NT>(hst_env + r0 * ENV_STASH + 4 * ln, dst + STAGE_TILES);
         if (wv == 1 && ln < 2 * TB)   // first 8 observation columns: 8 x 64 B, contiguous in the FM tile -> st_x[i * 16 + m]
-            async_copy16_to_lds<GOPS_SWEEP_STAGE_NT>(hst_x + r0 * kp0 + 4 * ln, dst + STAGE_TILES + TB * ENV_STASH);
+            async_copy16_to_lds<SWEEP_STAGE_NT>(hst_x + r0 * kp0 + 4 * ln, dst + STAGE_TILES + TB * ENV_STASH);
         if constexpr (SPLIT && ENV == GOPS_ENV_IDPENDULUM) {   // the forward's sub-step parking of the tile: 16 x 512 B, contiguous
 #pragma unroll
             for (int q2 = 0; q2 < 2; ++q2)
-                async_copy16_to_lds<GOPS_SWEEP_STAGE_NT>(p.st.idp + r0 * IDP_PARK + (wv * 2 + q2) * 256 + 4 * ln, s_idp + (tt & 1) * (TB * IDP_PARK) + (wv * 2 + q2) * 256);
+                async_copy16_to_lds<SWEEP_STAGE_NT>(p.st.idp + r0 * IDP_PARK + (wv * 2 + q2) * 256 + 4 * ln, s_idp + (tt & 1) * (TB * IDP_PARK) + (wv * 2 + q2) * 256);
         }
     };
     // pyth_idpendulum on the kernels that stage nothing else (streamed fp32, EXT, streamed-split): the forward's sub-step parking
@@ -799,7 +794,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 const int ln = tid & 63, wv = tid >> 6;
 #pragma unroll
                 for (int q2 = 0; q2 < 2; ++q2)
-                    async_copy16_to_lds<GOPS_SWEEP_STAGE_NT>(p.st.idp + r0 * IDP_PARK + (wv * 2 + q2) * 256 + 4 * ln, s_idp + (wv * 2 + q2) * 256);
+                    async_copy16_to_lds<SWEEP_STAGE_NT>(p.st.idp + r0 * IDP_PARK + (wv * 2 + q2) * 256 + 4 * ln, s_idp + (wv * 2 + q2) * 256);
             }
         }
     };
@@ -1283,11 +1278,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                     g[4] += g_rm * (-1.f * sc_[4]);
                     g[5] += g_rm * (-2.f * sc_[5]);
                     float gforce = 0.f;
-#if GOPS_IDP_BWD_UNROLL
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
                     for (int k = 4; k >= 0; --k) {
                         const float* pk = park + k * 24;
                         IdpSub w;
@@ -1735,7 +1726,7 @@ int split_grid_limit();   // rollout_fwd.hip: CUs of the device
 int ssb_grid_limit() { return 2 * split_grid_limit(); }   // workgroups of the streamed-split sweep (= slabs of its fused output-layer gradient)
 
 // The sweep of a streamed-split forward launch (p.ss) on the streamed-split sweep as well: same conditions, its LDS image at
-// two workgroups per CU.  GOPS_SSB=0 keeps the fp32-MFMA sweep.
+// two workgroups per CU.  GOPS_VF_NO_STREAMED_SPLIT_BWD keeps the fp32-MFMA sweep.
 bool ssb_eligible(const RolloutParams& p) {
     if (!p.ss) return false;
     if (p.vflags & GOPS_VF_NO_STREAMED_SPLIT_BWD) return false;

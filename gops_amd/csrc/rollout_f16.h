@@ -34,12 +34,9 @@ __device__ __forceinline__ f16x8 zero8h() {
 // at B = 65536 (cfg5): a deeper ring (4) or register-stationary fragments (16 K0 + 128 registers per lane for a
 // 256-256 policy) cost more in occupancy than they save - the step is bound by dependent VALU / LDS / scalar
 // latency, which 4 resident workgroups per CU hide better than 2 or 3.
-#ifndef GOPS_F16_PF
-#define GOPS_F16_PF 2   // chunks of weight fragments in flight per wave (16 registers each)
-#endif
 __device__ __forceinline__ void gemm_quad_h(const _Float16* act, int ld, int kch, const f16x8* Wp, int q,
                                             int lane, f32x4 (&acc)[4]) {
-    constexpr int PF = GOPS_F16_PF;
+    constexpr int PF = 2;   // chunks of weight fragments in flight per wave (16 registers each)
     const GLOBAL_AS f16x8* wb = gptr(Wp) + (size_t)q * 4 * kch * 64 + lane;
     const _Float16* brow = act + (lane & 15) * ld + 8 * (lane >> 4);
     f16x8 ring[PF][4];

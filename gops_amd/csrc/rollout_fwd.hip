@@ -9,11 +9,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#define GOPS_STREAMB_EXACT_REFILL   // (this translation unit only: the backward kernels' register allocation degrades with it)
 #include "common.h"
-#ifndef GOPS_IDP_FWD_UNROLL
-#define GOPS_IDP_FWD_UNROLL 1   // sub-steps 2 .. 5 of pyth_idpendulum unrolled (cfg2 forward 213 -> 208 us)
-#endif
 #include "env_models.h"
 #include "rollout_f16.h"
 
@@ -69,17 +65,17 @@ __device__ __forceinline__ float* mlp_hidden_forward(const MlpDev& M, const W0T&
         };
         bool done = false;
         if constexpr (!std::is_same<W0T, NoW>::value) {
-            if (j == 0) { gemm_layer_stat(cur, ldc, W0, nt_tot, tid, epi, kch, M.wp[0]); done = true; }
+            if (j == 0) { gemm_layer_stat<true>(cur, ldc, W0, nt_tot, tid, epi, kch, M.wp[0]); done = true; }
         }
         if constexpr (!std::is_same<W1T, NoW>::value) {
-            if (j == 1) { gemm_layer_stat(cur, ldc, W1, nt_tot, tid, epi); done = true; }
+            if (j == 1) { gemm_layer_stat<true>(cur, ldc, W1, nt_tot, tid, epi); done = true; }
         }
         if (!done) {
             if (narrow != nullptr) {
                 gemm_layer_lds(cur, ldc, kch, nt_tot, narrow, tid, epi);
                 narrow += kch * nt_tot * 64;
             } else {
-                gemm_layer(cur, ldc, kch, nt_tot, M.wp[j], tid, epi);
+                gemm_layer<true>(cur, ldc, kch, nt_tot, M.wp[j], tid, epi);
             }
         }
         DBG_TICK(8 + 3 * (j & 1))
@@ -226,7 +222,7 @@ struct SplitPolicy {
     // launch-time loads batched (round 5) pinning costs nothing at launch any more, and the 22 unpinned residual fragments that
     // hipcc copied back to VGPRs in front of their MFMAs (88 x v_accvgpr_read per step) are gone: forward 181.7 -> 179.5 us; the
     // idpendulum / lq instantiations measured better with the bf16 plane only (cfg2: 234.9 vs 236.9 us)
-    static constexpr int PIN1 = (AMAX == 2) ? 3 : GOPS_PIN_MODE;
+    static constexpr int PIN1 = (AMAX == 2) ? 3 : SPLIT_PIN_MODE;
     StatQ<8, 4, false, PIN1> Q1;       // layer 1: both planes in registers
     // r0_lds: LDS region for layer 0's residual plane (16 n-tiles x KC0 chunks x 1 KiB); the caller's barrier publishes it
     __device__ __forceinline__ void load(const RolloutParams& p, int tid, f16x8* r0_lds) {
@@ -355,8 +351,7 @@ struct NoSplit {};
 template <int AMAX>
 __device__ __forceinline__ float ss_net_forward(const MlpDev& M, const SplitNetDev& S, const float* xs, int ldx, char* xq, char* hq,
                                                 float* s_part, const float* s_bias, int ldb, const float* s_wo4, const float* s_bo,
-                                                int tid, float* const* stash_h, float* const* stash_z, size_t row0, DbgClock& dbg, unsigned& ovf,
-                                                float* dmp = nullptr) {
+                                                int tid, float* const* stash_h, float* const* stash_z, size_t row0, DbgClock& dbg, unsigned& ovf) {
     const int lane = tid & 63, wave = tid >> 6, m0 = (lane >> 4) << 2;
     constexpr int ROWB1 = 2 * 256 + 16;
     const int L = M.nl - 1, rowb0 = split_rowb(32 * S.kc[0]);
@@ -404,14 +399,6 @@ __device__ __forceinline__ float ss_net_forward(const MlpDev& M, const SplitNetD
                 if (ACT == GOPS_ACT_GELU && zrow != nullptr) __builtin_nontemporal_store(zv, gptr(reinterpret_cast<f32x4*>(zrow + n * 16 + m0)));
             }
         });
-#ifdef GOPS_DUMP
-        if (dmp != nullptr) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gptr(dmp)[32 + 16 * (j > 0 ? 1 : 0) + 4 * q + r] = hv[q][r];
-        }
-#endif
         DBG_TICK(8)
         if (!last) {
             plane_store(hq, ROWB1, wave, lane, hv, SPLIT_FWD_SA, ovf);
@@ -699,19 +686,8 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
             if constexpr (SPLIT) {
                 ya_split = SP.run(sp_hot, xs, ldx, xq, rowb0, hq, s_part, s_bias, ldh, s_wo, s_bo, tid, hng != 0, row0, dbg, !FASTV);
             } else if constexpr (SS) {
-#ifdef GOPS_DUMP
-                float* dmp = (p.dbg != nullptr && VEH) ? reinterpret_cast<float*>(p.dbg) + ((((size_t)tile * p.H + t) * NTHREADS + tid) << 6) : nullptr;
-                if (dmp != nullptr) {
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) gptr(dmp)[28 + k] = xs[(tid >> 4) * ldx + (tid & 15) + 16 * k];
-                }
-                ya_split = ss_net_forward<AMAX>(p.pol, p.ssp, xs, ldx, xq, hq, s_part, s_bias, ldh, s_wo, s_bo, tid,
-                                                p.need_grad ? p.st.h : nullptr, p.need_grad ? p.st.z : nullptr, row0, dbg, ss_ovf, dmp);
-                if (dmp != nullptr) gptr(dmp)[0] = ya_split;
-#else
                 ya_split = ss_net_forward<AMAX>(p.pol, p.ssp, xs, ldx, xq, hq, s_part, s_bias, ldh, s_wo, s_bo, tid,
                                                 p.need_grad ? p.st.h : nullptr, p.need_grad ? p.st.z : nullptr, row0, dbg, ss_ovf);
-#endif
             } else
             if (!p.open_loop) {
                 if constexpr (F16) {
@@ -881,11 +857,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                     IdpSub w;
                     idp_substep<true>(IC, s, u, 0.002f, sn, w);
                     park_store(0, w);
-#if GOPS_IDP_FWD_UNROLL
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
                     for (int k = 1; k < 5; ++k) {
                         idp_advance_trig(s, 0.002f, w, w);   // sin / cos of the new angles from the old ones (rotation by tau * theta_dot)
 #pragma unroll
@@ -893,9 +865,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                         idp_substep<false>(IC, s, u, 0.002f, sn, w);
                         park_store(k, w);
                     }
-#if GOPS_IDP_FAST
                     idp_advance_trig(s, 0.002f, w, w);   // cosines of the new angles for the termination test
-#endif
 #pragma unroll
                     for (int i = 0; i < 6; ++i) s[i] = sn[i];
                     // ([126], [127]: tanh(head) and the done flag the step started with - what the sweep's env adjoint needs of the env row:
@@ -903,11 +873,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                     if (parkg != nullptr) { parkg[30] = f32x4{s[0], s[1], s[2], s[3]}; parkg[31] = f32x4{s[4], s[5], s_th[m * 4], s_done[m]}; }
                     r = idp_reward(s, a);
                     rs = (GEN && !p.env.repeat_last_reward) ? rs + r : r;
-#if GOPS_IDP_FAST
                     done_m = idp_done_trig(IC, s, w.c1, w.c2);
-#else
-                    done_m = idp_done(IC, s);
-#endif
                 }
                 r = rs;
                 if (s_done[m] == 0.f) {
@@ -1063,14 +1029,6 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
             VehStep w;
             w.sphi = veh_s; w.cphi = veh_c;
             veh_f_xu(VC, s, steer, ax, sn, w);
-#ifdef GOPS_DUMP
-            float* dmpe = (SS && p.dbg != nullptr) ? reinterpret_cast<float*>(p.dbg) + ((((size_t)tile * p.H + t) * NTHREADS + tid) << 6) : nullptr;
-            if (dmpe != nullptr) {
-                gptr(dmpe)[1] = steer; gptr(dmpe)[2] = ax; gptr(dmpe)[3] = dflag;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) { gptr(dmpe)[4 + i] = s[i]; gptr(dmpe)[10 + i] = sn[i]; }
-            }
-#endif
             float pen_c = 0.f;   // surrcstr_penalty: constraint of the CURRENT pose
             float err_c0 = 0.f, err_c1 = 0.f;   // errcstr: |delta_y| - tol, |delta_u| - tol of the current observation
             if (part == 0) {
@@ -1110,14 +1068,6 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                 const float ytf = dx * snn + dy * cn;
                 const float ptf = angle_normalize(rp[2] - sn[2]);
                 const float utf = rp[3] - sn[3];
-#ifdef GOPS_DUMP
-                if (dmpe != nullptr && j == part) {
-                    gptr(dmpe)[16] = veh_s; gptr(dmpe)[17] = veh_c;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) gptr(dmpe)[18 + i] = rp[i];
-                    gptr(dmpe)[22] = xtf; gptr(dmpe)[23] = ytf; gptr(dmpe)[24] = ptf; gptr(dmpe)[25] = utf;
-                }
-#endif
                 if (j == 0) {
                     done_m = (fabsf(xtf) > 10.f) || (fabsf(ytf) > 10.f) || (fabsf(ptf) > 3.14159265358979323846f);
                     if (SURR && p.env.surr_penalty) done_m = false;   // judge_done of the penalty model: never (:236-246)
@@ -1198,12 +1148,6 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
             float rr = (d != 0.f) ? 0.f : r;
             if (ENV != GOPS_ENV_NONE && hshaping) rr = (rr + hrshift) * hrscale;
             v_acc += rr * gpow_t;
-#ifdef GOPS_DUMP
-            if (SS && VEH && p.dbg != nullptr) {
-                float* dm = reinterpret_cast<float*>(p.dbg) + ((((size_t)tile * p.H + t) * NTHREADS + tid) << 6);
-                gptr(dm)[26] = rr; gptr(dm)[27] = v_acc;
-            }
-#endif
             if (hrewards != nullptr && tid < nvalid) gptr(hrewards)[(size_t)t * hB + b0 + tid] = rr;
             if (!FASTV && done_m && !hnomask) s_done[tid] = 1.f;
         }
@@ -1370,7 +1314,7 @@ int split_grid_limit() { return device_cus(); }
 // Plane-split contractions (common.h SplitDev) replace the fp32 MFMAs of the register-stationary kernels for a closed-loop
 // obs -> 256 -> 256 -> act policy on the BASELINE env kinds with an input of at most 128 columns (4 chunks of 32: the
 // planes of both layers then fit the register file + LDS).  One workgroup per CU keeps the weights resident and walks
-// the tiles grid-stride, whatever the batch size.  GOPS_SPLIT=0 keeps the fp32-MFMA kernels.
+// the tiles grid-stride, whatever the batch size.  GOPS_VF_NO_STATIONARY_SPLIT keeps the fp32-MFMA kernels.
 // Activations whose derivative jumps at 0 (relu, selu) in a launch with a tail value net that keeps a gradient: the gradient runs
 // through dV/d(obs_H) of a piecewise-linear net, and every pre-activation of THAT net which changes sign under the 22-bit plane
 // representation moves it by a finite amount - measured at cfg3 (relu, 256^3, B = 8192): 2.0e-4 from the reference with a
@@ -1390,12 +1334,12 @@ bool split_eligible(const RolloutParams& p) {
     if (p.env.kind != GOPS_ENV_LQ && p.env.kind != GOPS_ENV_IDPENDULUM && p.env.kind != GOPS_ENV_VEH3DOFCONTI) return false;
     if (M.nl != 3 || M.dims[1] != 256 || M.dims[2] != 256 || p.ldh != 260 || M.kp32[0] > 256 || p.ldx != M.kp[0] + 4) return false;
     // more than 128 inputs (veh3dofconti with P > 30): layer 0's planes stream from L2 - instantiated without the tail value net
-    if (M.kp32[0] > 128 && (p.env.kind != GOPS_ENV_VEH3DOFCONTI || p.tail || (p.vflags & GOPS_VF_NO_SPLIT_STREAM0) != 0)) return false;
+    if (M.kp32[0] > 128 && (p.env.kind != GOPS_ENV_VEH3DOFCONTI || p.tail)) return false;
     // More tiles than CUs AND a tail value net: the tail is evaluated per tile with fp32 weights streamed from L2 by the one
     // resident workgroup, which exposes every L2 round trip (measured at B = 65536: no faster than the streamed kernels with
     // their three workgroups per CU) - those launches stay on the streamed kernels.
     if (p.tail && (p.B + TB - 1) / TB > device_cus() && !(p.vflags & GOPS_VF_SPLIT_TAIL_MULTI)) return false;
-    if (p.vflags & (GOPS_VF_NO_STATIONARY_SPLIT | GOPS_VF_STREAMED_FP32 | GOPS_VF_STREAM_LAYER0)) return false;
+    if (p.vflags & (GOPS_VF_NO_STATIONARY_SPLIT | GOPS_VF_STREAMED_FP32)) return false;
     const int ref_pts = env_has_ref_table(p.env.kind) ? p.env.pre_horizon + 1 + p.H : (p.env.kind == GOPS_ENV_IDPENDULUM ? IDP_POINTS(true) : 0);
     if (rollout_fwd_lds_bytes(p.ldx, p.ldh, env_has_ref_table(p.env.kind) ? ref_pts : 0, false, M.kp32[0]) > 160 * 1024) return false;
     if (rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_pts, false, true) > 160 * 1024) return false;
@@ -1410,7 +1354,7 @@ static bool ss_shape_ok(const RolloutParams& p) {
     if (p.f16 || p.ext || p.open_loop || p.env.repeat_num > 1) return false;
     // (value / MLP batches, GOPS_ENV_NONE: one step - half the MFMA time of the fp32 kernels; GOPS_SS_VALUE=0 keeps those)
     if (p.env.kind == GOPS_ENV_NONE && (p.vflags & GOPS_VF_NO_STREAMED_SPLIT_VALUE)) return false;
-    if (p.vflags & (GOPS_VF_NO_STREAMED_SPLIT_FWD | GOPS_VF_STREAMED_FP32 | GOPS_VF_STREAM_LAYER0)) return false;
+    if (p.vflags & (GOPS_VF_NO_STREAMED_SPLIT_FWD | GOPS_VF_STREAMED_FP32)) return false;
     auto net_ok = [](const MlpDev& M) {
         if (M.nl < 3 || M.kp32[0] > 256) return false;
         for (int j = 1; j < M.nl; ++j)
@@ -1439,7 +1383,7 @@ void rollout_variant(const RolloutParams& p, int sk[2], bool backward) {
     // Register-stationary weights pin one workgroup per CU.  That is the right trade only while there
     // is at most one tile per CU (B <= 16 * #CUs = 4096 on MI355X); with more tiles the streamed
     // kernels win because 2-3 workgroups per CU overlap each other's MFMA and VALU phases.
-    if ((p.B + TB - 1) / TB > device_cus() && !(p.vflags & GOPS_VF_STATIONARY_ANY_BATCH)) return;
+    if ((p.B + TB - 1) / TB > device_cus()) return;
     if (M.nl - 1 < 2 || M.dims[1] != 256 || M.dims[2] != 256 || p.env.kind == GOPS_ENV_NONE || p.ldh != 260) return;
     sk[1] = 16;
     const int k0 = M.kp[0] >> 4;
@@ -1456,9 +1400,7 @@ void rollout_variant(const RolloutParams& p, int sk[2], bool backward) {
     // The backward's stationary variants also stage this step's H_2 / H_1 tiles in LDS: exactly two hidden layers.
     if (backward && M.nl != 3) { sk[0] = sk[1] = 0; return; }
     if (backward) sk[0] = (sk[1] == 16 && M.kp[0] == 128) ? 12 : ((sk[1] == 16 && M.kp[0] == 16) ? 16 : 0);
-    // tuning flags (benchmarks only): the plain streamed kernels, or layer 1 stationary only
-    if (p.vflags & GOPS_VF_STREAM_LAYER0) sk[0] = 0;
-    if (p.vflags & GOPS_VF_STREAMED_FP32) sk[0] = sk[1] = 0;
+    if (p.vflags & GOPS_VF_STREAMED_FP32) sk[0] = sk[1] = 0;   // the plain streamed kernels
 }
 
 #define LAUNCH_FWD(ENV, A, B)                                                                            \

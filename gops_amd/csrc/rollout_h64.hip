@@ -106,24 +106,16 @@ __device__ __forceinline__ void mlp_hidden_forward_h64(const MlpDev& M, const _F
                         const int e = 4 * jj + r;
                         const float z = acc[jj][rg][r] + bv[jj][r];
                         float h, dh = 0.f;
-#ifdef H64_KO_MATH   // (knock-out build: what do the epilogue's transcendentals cost?)
-                        h = z; dh = z;
-#else
                         if (ACT == GOPS_ACT_GELU) {
                             gelu_pair_h(z, h, dh);
                             if (!WANT_DH) dh = 0.f;   // (dead: the compiler drops its two instructions and the conversion below)
                         } else h = act_fwd_t<ACT>(z);
-#endif
                         o[e >> 3][e & 7] = (_Float16)h;
                         if (WANT_DH) gd[e >> 3][e & 7] = (_Float16)dh;
                     }
                 *reinterpret_cast<f16x8*>(hbuf + row * H64_LD + f0) = o[0];
                 *reinterpret_cast<f16x8*>(hbuf + row * H64_LD + f0 + 8) = o[1];
-#ifdef H64_KO_STORE   // (knock-out build: what do the stash stores cost?)
-                if (false) {
-#else
                 if (stash_h != nullptr && row < stash_rows) {
-#endif
                     _Float16* hrow = reinterpret_cast<_Float16*>(stash_h[j + 1]) + (row0 + row) * 256;
                     H64_STORE(o[0], gptr(reinterpret_cast<f16x8*>(hrow + f0)));
                     H64_STORE(o[1], gptr(reinterpret_cast<f16x8*>(hrow + f0 + 8)));
@@ -464,10 +456,7 @@ __device__ __forceinline__ void mlp_backward_h64(const MlpDev& M, WP Wo, int ldw
 // The sweep walks the forward's 64-row stash tiles in tiles of H64_BWD_RG x 16 rows.  Measured at cfg5 (round 4): 64 rows per
 // workgroup (two workgroups = 8 waves per CU, 235 registers) 0.491 ms; 32 rows (three workgroups = 12 waves per CU, 143
 // registers) 0.587 ms - the weight stream per trajectory doubles and costs more than the extra waves hide.
-#ifndef H64_BWD_RG
-#define H64_BWD_RG 4
-#endif
-#define H64_BWD_WGS (H64_BWD_RG == 4 ? 2 : 3)
+constexpr int H64_BWD_RG = 4;
 // (+ the fused first-layer gradient: the policy-input rows of two steps [2][TBW][8] and the workgroup's accumulators [256][9])
 #define H64_W0_COLS 8
 size_t rollout_bwd_h64_lds_bytes(int ldx, int ldh) {
@@ -476,7 +465,7 @@ size_t rollout_bwd_h64_lds_bytes(int ldx, int ldh) {
 }
 
 template <int ENV, bool TAIL, int RG>
-__global__ __launch_bounds__(NTHREADS, H64_BWD_WGS) void rollout_bwd_h64_kernel(const RolloutParams* __restrict__ pp, const BwdPatch q) {
+__global__ __launch_bounds__(NTHREADS, 2) void rollout_bwd_h64_kernel(const RolloutParams* __restrict__ pp, const BwdPatch q) {
     constexpr int TBW = 16 * RG;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const RolloutParams& p = *pp;
@@ -485,12 +474,6 @@ __global__ __launch_bounds__(NTHREADS, H64_BWD_WGS) void rollout_bwd_h64_kernel(
     const int ftile = b0 / TB64, fsub = b0 % TB64;   // the forward's 64-row stash tile this tile is part of
     const int O = p.env.obs_dim, A = p.env.act_dim;
     const int ldx = p.ldx, ldh = p.ldh;
-#ifdef H64_SKEW_US   // experiment: every second wave of workgroups starts late, so that co-resident workgroups run different phases
-    if ((blockIdx.x >> 8) & 1) {
-        const long long t0 = wall_clock64();
-        while (wall_clock64() - t0 < (long long)(H64_SKEW_US) * 100) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
     float* G = smem;                  // [64][ldx] adjoint of obs_{t+1}
     float* s_gy = G + TBW * ldx;      // [TBW][4]
     float* s_wo = s_gy + TBW * 4;     // [4][ldh] head weights
@@ -726,10 +709,9 @@ bool h64_fuses_dw0(const RolloutParams& p) {
            !(p.vflags & GOPS_VF_NO_FUSED_DW0);
 }
 
-// The launches the 64-row half kernels take (api.hip build_plan; GOPS_VF_NO_HALF_TILE64 keeps the 16-row kernels)
+// The launches the 64-row half kernels take (api.hip build_plan)
 bool h64_eligible(const RolloutParams& p) {
     if (!p.f16 || p.open_loop || p.ext || p.env.repeat_num > 1) return false;
-    if (p.vflags & GOPS_VF_NO_HALF_TILE64) return false;
     if (p.env.kind != GOPS_ENV_LQ && p.env.kind != GOPS_ENV_NONE) return false;
     if (p.env.kind == GOPS_ENV_NONE && p.tail) return false;
     auto net_ok = [](const MlpDev& M) {

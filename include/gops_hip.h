@@ -45,7 +45,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GOPS_HIP_ABI_VERSION 13
+#define GOPS_HIP_ABI_VERSION 14
 
 #define GOPS_MAX_LAYERS 5   /* Linear layers per MLP (<= 4 hidden + output) */
 #define GOPS_MAX_ACT 4      /* action dimensions */
@@ -481,29 +481,21 @@ int gops_mean_loss(const float* x, int32_t n, double scale, float* stats, void* 
  * bit 3 (GOPS_VARIANT_HALF_TILE64, ABI v10): GOPS_DTYPE_F16 on the 64-trajectory-tile kernels (rollout_h64.hip);
  * none: the streamed kernels (exact fp32 MFMAs, or half-precision MFMAs for GOPS_DTYPE_F16).
  * Negative: a GOPS_ERR_* code for a description the library rejects. */
-/* GopsRolloutDesc.variant_flags / GopsMlp.variant_flags (ABI v10; replaces the process-environment knobs of v9, which
- * survive only as a debug override read ONCE when the library is loaded - see INTEGRATION.md). */
-#define GOPS_VF_NO_STATIONARY_SPLIT 0x1u     /* not the register-stationary plane-split kernels            (v9: GOPS_SPLIT=0) */
-#define GOPS_VF_NO_STREAMED_SPLIT_FWD 0x2u   /* not the streamed plane-split forward                        (GOPS_SS=0) */
-#define GOPS_VF_NO_STREAMED_SPLIT_BWD 0x4u   /* not the streamed plane-split sweep                          (GOPS_SSB=0) */
-#define GOPS_VF_NO_STREAMED_SPLIT_VALUE 0x8u /* value / MLP batches (GOPS_ENV_NONE) on the fp32-MFMA kernels (GOPS_SS_VALUE=0) */
-#define GOPS_VF_STREAMED_FP32 0x10u          /* the plain streamed exact-fp32 kernels: no stationary weights, no planes (GOPS_SK=0,0) */
-#define GOPS_VF_STREAM_LAYER0 0x20u          /* stationary kernels keep layer 1 only                         (GOPS_SK=0,16) */
-#define GOPS_VF_STATIONARY_ANY_BATCH 0x40u   /* stationary fp32 kernels also with more tiles than CUs        (GOPS_SK set) */
-#define GOPS_VF_NO_SPLIT_STREAM0 0x80u       /* no plane-split kernel for policies with 129 .. 256 inputs    (GOPS_SPLIT_STREAM0=0) */
-#define GOPS_VF_SPLIT_TAIL_MULTI 0x100u      /* stationary plane-split kernels also for tail + more tiles than CUs (GOPS_SPLIT_TAIL_MULTI) */
-#define GOPS_VF_NO_HALF_TILE64 0x200u        /* GOPS_DTYPE_F16: the 16-trajectory-tile kernels instead of the 64-row ones (A/B) */
-#define GOPS_VF_NO_NARROW_LDS 0x400u         /* narrow policies on the streamed fp32 kernels: hidden-layer weights from L2 every step, not LDS-resident (GOPS_NARROW=0; A/B) */
-#define GOPS_VF_NO_NARROW_N64 0x800u         /* obs-64-64-act policies on the generic narrow kernels, not the ones written out for that shape (GOPS_N64=0; A/B, identical results) */
-#define GOPS_VF_DW_EXACT 0x10000u            /* weight-gradient GEMM: exact three-plane bf16 split           (GOPS_DW_EXACT) */
-#define GOPS_VF_DW_F32 0x20000u              /*   fp32-MFMA GEMM                                              (GOPS_DW_F32) */
-#define GOPS_VF_DW_NO_GUARD 0x40000u         /*   test knob: no exact redo of saturated blocks                (GOPS_DW_NOGUARD) */
-#define GOPS_VF_DW_NO_SKINNY 0x80000u        /*   no 16-input-layer kernel                                    (GOPS_DW_SKINNY=0) */
-#define GOPS_VF_DW_NO_SPEC 0x100000u         /*   no wave-specialised kernel                                  (GOPS_DW_SPEC=0) */
-#define GOPS_VF_DW_DIRECT 0x200000u          /*   register-direct kernel for the large layers too             (GOPS_DW_DIRECT) */
-#define GOPS_VF_NO_FUSED_DWOUT 0x400000u     /*   output layer's gradient in its own pass                     (GOPS_NO_FUSED_DWOUT) */
+/* GopsRolloutDesc.variant_flags / GopsMlp.variant_flags (ABI v10; replaces the process-environment knobs of v9).  ABI v14
+ * retired the bits 0x20, 0x40, 0x80, 0x200 and 0x80000 .. 0x800000: a description that carries a bit outside GOPS_VF_ALL is
+ * rejected (GOPS_ERR_BAD_ARG). */
+#define GOPS_VF_NO_STATIONARY_SPLIT 0x1u     /* not the register-stationary plane-split kernels */
+#define GOPS_VF_NO_STREAMED_SPLIT_FWD 0x2u   /* not the streamed plane-split forward */
+#define GOPS_VF_NO_STREAMED_SPLIT_BWD 0x4u   /* not the streamed plane-split sweep */
+#define GOPS_VF_NO_STREAMED_SPLIT_VALUE 0x8u /* value / MLP batches (GOPS_ENV_NONE) on the fp32-MFMA kernels */
+#define GOPS_VF_STREAMED_FP32 0x10u          /* the plain streamed exact-fp32 kernels: no stationary weights, no planes */
+#define GOPS_VF_SPLIT_TAIL_MULTI 0x100u      /* stationary plane-split kernels also for tail + more tiles than CUs */
+#define GOPS_VF_NO_NARROW_LDS 0x400u         /* narrow policies on the streamed fp32 kernels: hidden-layer weights from L2 every step, not LDS-resident (A/B) */
+#define GOPS_VF_NO_NARROW_N64 0x800u         /* obs-64-64-act policies on the generic narrow kernels, not the ones written out for that shape (A/B, identical results) */
+#define GOPS_VF_DW_EXACT 0x10000u            /* weight-gradient GEMM: exact three-plane bf16 split */
+#define GOPS_VF_DW_F32 0x20000u              /*   fp32-MFMA GEMM */
+#define GOPS_VF_DW_NO_GUARD 0x40000u         /*   test knob: no exact redo of saturated blocks */
 #define GOPS_VF_NO_FUSED_DW0 0x4000000u      /*   GOPS_DTYPE_F16, 64-row kernels: the first layer's gradient by its GEMM, not inside the sweep (A/B) */
-#define GOPS_VF_BWD_UPLOAD 0x800000u         /*   measurement: parameter upload launch in front of the sweep  (GOPS_BWD_UPLOAD) */
 /* A backward call in two halves, so that a data-parallel caller can put the all-reduce of the gradients that are ready
  * first on a side stream while the rest is still being formed (gops_amd/trainer/grad_sync.py):
  *   PHASE_A: sweep, output layer's gradient and every hidden layer's EXCEPT the first one's (reduced and final in the caller's
@@ -511,6 +503,10 @@ int gops_mean_loss(const float* x, int32_t n, double scale, float* stats, void* 
  *            hidden layer's weight gradient + bias from the stash PHASE_A left.  Neither / both bits: the whole backward. */
 #define GOPS_VF_BWD_PHASE_A 0x1000000u
 #define GOPS_VF_BWD_PHASE_B 0x2000000u
+#define GOPS_VF_ALL (GOPS_VF_NO_STATIONARY_SPLIT | GOPS_VF_NO_STREAMED_SPLIT_FWD | GOPS_VF_NO_STREAMED_SPLIT_BWD | \
+                     GOPS_VF_NO_STREAMED_SPLIT_VALUE | GOPS_VF_STREAMED_FP32 | GOPS_VF_SPLIT_TAIL_MULTI | GOPS_VF_NO_NARROW_LDS | \
+                     GOPS_VF_NO_NARROW_N64 | GOPS_VF_DW_EXACT | GOPS_VF_DW_F32 | GOPS_VF_DW_NO_GUARD | GOPS_VF_NO_FUSED_DW0 | \
+                     GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B)   /* ABI v14: every bit a description may carry */
 
 #define GOPS_VARIANT_SPLIT 1
 #define GOPS_VARIANT_STATIONARY_F32 2

@@ -182,8 +182,8 @@ def test_update_tail_entry_points_reject_bad_arguments_without_a_gpu():
 
 def test_variant_selection_is_part_of_the_description_not_of_the_process():
     """ABI v10: kernel variants are chosen by GopsRolloutDesc.variant_flags - two callers in one process can choose
-    differently (the library keeps no global state) - and the library source reads the process environment in ONE
-    place only (the debug override, read once at load)."""
+    differently (the library keeps no global state).  The library source reads the process environment in ONE
+    place only, inside GOPS_DBG_BUILD (the phase counters of `make dbg`): the product library reads none."""
     import glob
     from gops_amd import hip_backend as hb
     from gops_amd.create_pkg.create_env_model import create_env_model
@@ -227,7 +227,73 @@ def test_variant_selection_is_part_of_the_description_not_of_the_process():
         d.need_grad = ng
         assert variant(0) == 4, ng
     n_getenv = sum(open(f).read().count("getenv(") for f in glob.glob(os.path.join(ROOT, "gops_amd", "csrc", "*.h*")))
-    assert n_getenv <= 3, n_getenv
+    assert n_getenv <= 1, n_getenv
+    api = open(os.path.join(ROOT, "gops_amd", "csrc", "api.hip")).read()
+    for m in re.finditer(r"getenv\(", api):
+        guard = api[:m.start()].rsplit("#ifdef GOPS_DBG_BUILD", 1)
+        assert len(guard) == 2 and "#endif" not in guard[1], "getenv outside #ifdef GOPS_DBG_BUILD"
+
+
+def test_retired_variant_bits_are_rejected():
+    """ABI v14: a description that carries a GOPS_VF_* bit outside GOPS_VF_ALL (one of the nine retired A/B bits, or an
+    unknown one) is refused - not silently run with the default variant."""
+    from gops_amd import hip_backend as hb
+    from gops_amd.create_pkg.create_env_model import create_env_model
+    d = hb.GopsRolloutDesc()
+    d.batch, d.horizon, d.finite_horizon, d.need_grad, d.gamma = 4096, 30, 1, 1, 1.0
+    d.env = create_env_model("pyth_veh3dofconti", pre_horizon=30).hip_env()
+    m = hb.GopsMlp()
+    m.n_layers = 3
+    for i, s in enumerate([127, 256, 256, 2]):
+        m.sizes[i] = s
+    for j in range(3):
+        m.weight[j] = m.bias[j] = 1
+    m.hidden_act = hb.ACT_IDS["elu"]
+    d.policy = m
+    lib = hb.lib()
+    kept = (hb.VF_NO_STATIONARY_SPLIT | hb.VF_NO_STREAMED_SPLIT_FWD | hb.VF_NO_STREAMED_SPLIT_BWD | hb.VF_NO_STREAMED_SPLIT_VALUE |
+            hb.VF_STREAMED_FP32 | hb.VF_SPLIT_TAIL_MULTI | hb.VF_NO_NARROW_LDS | hb.VF_NO_NARROW_N64 | hb.VF_DW_EXACT | hb.VF_DW_F32 |
+            hb.VF_DW_NO_GUARD | hb.VF_NO_FUSED_DW0 | hb.VF_BWD_PHASE_A | hb.VF_BWD_PHASE_B)
+    header = open(os.path.join(ROOT, "include", "gops_hip.h")).read()
+    in_mask = re.search(r"#define GOPS_VF_ALL \((.*?)\)\s*/\*", header, re.S).group(1)
+    assert sum(getattr(hb, "VF_" + n[len("GOPS_VF_"):]) for n in re.findall(r"GOPS_VF_\w+", in_mask)) == kept
+    d.variant_flags = kept
+    assert lib.gops_rollout_workspace_bytes(ctypes.byref(d)) > 0 and lib.gops_rollout_variant(ctypes.byref(d)) >= 0
+    retired = (0x20, 0x40, 0x80, 0x200, 0x80000, 0x100000, 0x200000, 0x400000, 0x800000)   # STREAM_LAYER0 .. BWD_UPLOAD (v13)
+    for bit in retired + (0x8000, 0x80000000):
+        assert bit & kept == 0
+        d.variant_flags = bit
+        assert lib.gops_rollout_workspace_bytes(ctypes.byref(d)) == 0, hex(bit)
+        assert lib.gops_rollout_variant(ctypes.byref(d)) == -1, hex(bit)   # GOPS_ERR_BAD_ARG
+    d.variant_flags = 0
+    assert lib.gops_rollout_variant(ctypes.byref(d)) == 1
+    assert lib.gops_mlp_workspace_bytes(ctypes.byref(m), 64) > 0
+    m.variant_flags = 0x200000                                # (GopsMlp: the value / MLP entry points)
+    assert lib.gops_mlp_workspace_bytes(ctypes.byref(m), 64) == 0
+
+
+# Preprocessor switches the HIP library may test: instruments and scaffolding, not alternative kernels.
+KEPT_SWITCHES = {"GOPS_DBG_BUILD", "GOPS_ONLY_NARROW", "GOPS_ONLY_TARGET", "GOPS_HIP_H", "__cplusplus", "__GNUC__", "__clang__"}
+
+
+def test_device_code_has_one_configuration():
+    """Every #if / #ifdef / #ifndef / #elif under gops_amd/csrc and include/ names only the kept switches: the debug build
+    (`make dbg`), the single-instantiation builds of tools/kernel_regs.sh and the header's own guards.  Alternative kernels
+    and knock-out builds live in DESIGN_LOG.md and git history, not behind a macro in the product source."""
+    import glob
+    files = glob.glob(os.path.join(ROOT, "gops_amd", "csrc", "*.h*")) + glob.glob(os.path.join(ROOT, "include", "*.h"))
+    assert len(files) >= 8
+    seen = set()
+    for f in files:
+        for n, line in enumerate(open(f), 1):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            cond = re.sub(r"/\*.*?\*/", " ", m.group(2)).split("//")[0]
+            names = set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+            assert names and names <= KEPT_SWITCHES, f"{os.path.relpath(f, ROOT)}:{n}: {line.strip()}"
+            seen |= names
+    assert {"GOPS_DBG_BUILD", "GOPS_ONLY_NARROW", "GOPS_ONLY_TARGET"} <= seen
 
 
 def test_registries_and_error_behaviour():

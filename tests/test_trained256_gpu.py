@@ -12,7 +12,7 @@ What round 5 measured here (MI355X):
   * a weight error is SYSTEMATIC (the same perturbed network for every sample: it does not average out over the batch).  With the
     round-3 planes (bf16 + f16 residual, 2^-20 |w|) five of the six fixtures sat at 3e-6 .. 3e-5 but the reference-trained pyth_lq
     policy with a saturated tanh head (the REFERENCE's own gradient moves 6.6e-5 under 1-ulp weight moves) at 3.5e-4 - outside
-    the bar; with two half planes per operand (2^-22 |w|, csrc/common.h GOPS_SPLIT_F16X2) all six are at the level of the exact-fp32
+    the bar; with two half planes per operand (2^-22 |w|, csrc/common.h split2h) all six are at the level of the exact-fp32
     kernels: 1.8e-6 .. 6e-6, the saturated one 3.1e-5 (exact forward: 3.2e-5).  `NEEDS_EXACT_FORWARD` is empty; the algorithm
     classes' `PrecisionGuard` (algorithm/base.py) stays as the measured safety net, and catches a half-range overflow;
   * veh3dofconti: the appended reference headings (exemption 1: a 1 ms finite difference in fp32 whose last bit
