@@ -17,7 +17,7 @@ from gops_amd.utils.common_utils import make_adam
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import (_INFO_KEYS, AlgorithmBase, ApprBase, PrecisionGuard, batch_to_device, cuda_device_of,
-                                     grad_buffers)
+                                     grad_buffers, is_poly, net_grad_buffers, poly_alg_check, poly_env_check, poly_grad_buffers)
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
@@ -56,6 +56,13 @@ class FHADP(AlgorithmBase):
         # measured rule for leaving the plane-split forward (algorithm/base.py PrecisionGuard); fp16 launches state their own tolerance
         self.precision_guard = PrecisionGuard(kwargs.get("precision_check_interval"), kwargs.get("precision_threshold"))
         self._update_graph, self._grad_graph, self._grad_graph_b = StepGraphCache(), StepGraphCache(), StepGraphCache()
+        # POLY policy (apprfunc/poly.py): the one-lane-per-trajectory rollout (hb.PolyRollout) of the plain algorithm only
+        self._poly = is_poly(self.networks.policy)
+        if self._poly:
+            if type(self)._gradient_kernels is not FHADP._gradient_kernels:
+                raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type POLY: only plain FHADP runs the POLY rollout")
+            poly_env_check(self.envmodel, type(self).__name__)
+            poly_alg_check(self, time_input=True)
 
     @property
     def adjustable_parameters(self) -> Tuple[str]:
@@ -72,6 +79,7 @@ class FHADP(AlgorithmBase):
         # the constrained variants bring their own gradient kernels; the plain ones fold loss mean and Adam step into the backward's
         # last launch (ABI v12, gops_rollout_backward_update: two launches less per update)
         fuse = type(self)._gradient_kernels is FHADP._gradient_kernels and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0"   # (host-side A/B knob)
+        fuse = fuse and not self._poly   # (POLY: gradient, loss mean and Adam step as three launches)
 
         def update(b):
             if fuse:
@@ -103,7 +111,7 @@ class FHADP(AlgorithmBase):
         batch = self._device_batch(data)
         self._precision_check(batch)
         work = batch["obs"].shape[0] * self.pre_horizon
-        grad_buffers(self.networks.policy)   # (allocates the flat gradient buffer on first use)
+        net_grad_buffers(self.networks.policy)   # (allocates the flat gradient buffer on first use)
         grads = [p._grad for p in self.networks.policy.parameters()]
         info = {"grad": grads}
         plain = type(self)._gradient_kernels is FHADP._gradient_kernels   # (the constrained variants bring their own gradient kernels)
@@ -142,8 +150,9 @@ class FHADP(AlgorithmBase):
         mlp = policy.hip_mlp()
         if ro is None:
             env = self.envmodel.hip_env(policy.act_low_lim.cpu().numpy(), policy.act_high_lim.cpu().numpy())
-            ro = hb.Rollout(env, mlp, batch=batch, horizon=self.pre_horizon, gamma=self.gamma,
-                            finite_horizon=True, need_grad=True, device=device, dtype=self.mlp_dtype, variant_flags=flags)
+            cls = hb.PolyRollout if self._poly else hb.Rollout
+            ro = cls(env, mlp, batch=batch, horizon=self.pre_horizon, gamma=self.gamma,
+                     finite_horizon=True, need_grad=True, device=device, dtype=self.mlp_dtype, variant_flags=flags)
             # one live workspace per kernel variant of the current shape (shapes rarely change between updates)
             self._rollouts = {k: r for k, r in self._rollouts.items() if k[:5] == key[:5]}
             self._rollouts[key] = ro
@@ -206,6 +215,14 @@ class FHADP(AlgorithmBase):
         `fused_opt` (the policy's HipAdam, single-process update): loss mean and optimizer step ride on the backward's last launch."""
         B, device = batch["obs"].shape[0], batch["obs"].device
         ro = self._rollout_for(B, device)
+        if self._poly:   # forward, backward, loss mean (+ Adam step): no phases, no fused tail for one or two tensors
+            v_pi = ro.forward(batch)["v_pi"]
+            gw, gb = poly_grad_buffers(self.networks.policy)
+            ro.backward(self._grad_v(B, device), gw, gb)
+            out = self._mean_of(v_pi)
+            if fused_opt is not None:
+                fused_opt.step()
+            return out
         if phase == "b":
             gw, gb = grad_buffers(self.networks.policy)
             ro.backward(self._grad_v(B, device), gw, gb, phase="b")

@@ -17,7 +17,7 @@ from gops_amd.utils.common_utils import make_adam
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import (_INFO_KEYS, AlgorithmBase, ApprBase, PrecisionGuard, batch_to_device, cuda_device_of,
-                                     grad_buffers)
+                                     grad_buffers, is_poly, poly_alg_check, poly_env_check, poly_grad_buffers)
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
@@ -73,6 +73,16 @@ class INFADP(AlgorithmBase):
         # measured rule for leaving the plane-split forward (algorithm/base.py PrecisionGuard), one per trained network
         self.precision_guard = {m: PrecisionGuard(kwargs.get("precision_check_interval"), kwargs.get("precision_threshold")) for m in ("v", "policy")}
         self._bufs = {}     # persistent device scratch: loss gradient, loss scalars (read them before the next update of the same mode)
+        # POLY policy AND value (apprfunc/poly.py): the one-lane-per-trajectory rollout (hb.PolyRollout) and hb.PolyValueNet
+        self._poly = is_poly(self.networks.policy)
+        if self._poly != is_poly(self.networks.v):
+            raise NotImplementedError("INFADP: a POLY policy needs a POLY value and the reverse (the rollout's tail value is "
+                                      "evaluated by the policy's kernel)")
+        if self._poly:
+            if type(self)._gradient_kernels is not INFADP._gradient_kernels:
+                raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type POLY: only plain INFADP runs the POLY rollout")
+            poly_env_check(self.envmodel, type(self).__name__)
+            poly_alg_check(self, time_input=False)
 
     @property
     def adjustable_parameters(self):
@@ -91,6 +101,7 @@ class INFADP(AlgorithmBase):
         # (ABI v12, gops_rollout_backward_update / gops_value_backward_update)
         fuse = (type(self)._gradient_kernels is INFADP._gradient_kernels and type(self)._update is INFADP._update
                 and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0")   # (host-side A/B knob)
+        fuse = fuse and not self._poly   # (POLY: Adam and Polyak steps as launches of their own)
 
         def update(b):
             if fuse:
@@ -165,8 +176,9 @@ class INFADP(AlgorithmBase):
         ro = self._cache.get(key)
         if ro is None:
             env = self.envmodel.hip_env(nets.policy.act_low_lim.cpu().numpy(), nets.policy.act_high_lim.cpu().numpy())
-            ro = hb.Rollout(env, pol, batch=batch, horizon=self.forward_step, gamma=self.gamma,
-                            finite_horizon=False, need_grad=need_grad, value=vt, device=device, dtype=self.mlp_dtype, variant_flags=flags)
+            cls = hb.PolyRollout if self._poly else hb.Rollout
+            ro = cls(env, pol, batch=batch, horizon=self.forward_step, gamma=self.gamma,
+                     finite_horizon=False, need_grad=need_grad, value=vt, device=device, dtype=self.mlp_dtype, variant_flags=flags)
             self._cache[key] = ro
         else:
             ro.set_policy(pol, vt)
@@ -178,7 +190,10 @@ class INFADP(AlgorithmBase):
         mlp = self.networks.v.hip_mlp(self.mlp_dtype, variant_flags=flags)
         vn = self._cache.get(key)
         if vn is None:
-            vn = self._cache[key] = hb.ValueNet(mlp, batch, device=device)
+            vn = self._cache[key] = (hb.PolyValueNet(mlp, batch, self.envmodel.hip_env().obs_dim, device=device) if self._poly
+                                     else hb.ValueNet(mlp, batch, device=device))
+        elif self._poly:
+            vn.set_net(mlp)
         else:
             vn.mlp = mlp
         return vn
@@ -222,7 +237,7 @@ class INFADP(AlgorithmBase):
             # loss_v, mean V and d(loss_v)/dV = (2 / B)(V - backup) in one launch (they were six torch passes)
             gdiff = self._scratch("gdiff", B, device)
             scalars = self._loss_stats("v", device).value_loss(v, backup, gdiff)
-            gw, gb = grad_buffers(self.networks.v)
+            gw, gb = poly_grad_buffers(self.networks.v) if self._poly else grad_buffers(self.networks.v)
             if fused_opt is not None:   # -> (scalars, whether Adam + Polyak were part of the backward call)
                 fa, pk = self._fused_parts("v", fused_opt)
                 if fa is None:
@@ -236,7 +251,7 @@ class INFADP(AlgorithmBase):
         # PIM: loss = -mean(sum_t gamma^t r_t + (~d) gamma^n V_target(o_n)), grads into the policy
         ro = self._rollout_for(B, device, need_grad=True)
         v_pi = ro.forward(batch)["v_pi"]
-        gw, gb = grad_buffers(self.networks.policy)
+        gw, gb = poly_grad_buffers(self.networks.policy) if self._poly else grad_buffers(self.networks.policy)
         if fused_opt is not None:   # -> (scalars, whether Adam + Polyak were part of the backward call)
             fa, pk = self._fused_parts("policy", fused_opt)
             stats = self._loss_stats("policy", device)
@@ -247,6 +262,9 @@ class INFADP(AlgorithmBase):
             fused_opt.end_fused()
             return stats.buf[:1], True
         stats = self._loss_stats("policy", device)   # (the loss mean rides on the backward's reduce launch: it needs no gradient)
+        if self._poly:   # (POLY: the loss mean in a launch of its own)
+            ro.backward(self._grad_v(B, device), gw, gb)
+            return stats.mean_loss(v_pi, -1.0)[:1]
         ro.backward(self._grad_v(B, device), gw, gb, tail=hb.make_update_tail(None, v_pi, -1.0, stats))
         return stats.buf[:1]
 

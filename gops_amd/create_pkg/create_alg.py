@@ -64,6 +64,10 @@ class LocalActor:
 
 def create_alg(**kwargs) -> object:
     registry.lookup(kwargs["algorithm"])          # unknown algorithm: KeyError before anything else
+    poly = [k for k in ("policy", "value") if kwargs.get(k + "_func_type") == "POLY"]
+    if poly and kwargs["algorithm"] not in ("FHADP", "INFADP"):   # (the POLY rollout serves these two; nothing fails later)
+        raise NotImplementedError(f"apprfunc type POLY ({', '.join(poly)}) is supported by FHADP and INFADP only, "
+                                  f"not by {kwargs['algorithm']}")
     trainer = kwargs.get("trainer")
     if trainer is not None and not trainer.startswith(_TRAINER_KINDS):
         raise RuntimeError(f"trainer {trainer} not recognized")

@@ -38,6 +38,14 @@ hipError_t launch_linear_out_bwd(const float* gy, int W, int Wp, const float* Wo
                                  float* gyp, hipStream_t s);
 hipError_t launch_reduce(const ReduceJobs& jobs, hipStream_t s);
 hipError_t launch_fill_zero(float* p, size_t n, hipStream_t s);
+// rollout_poly.hip: POLY approximators, one lane per trajectory
+size_t poly_rollout_workspace_bytes(const GopsRolloutDesc& d);
+int poly_rollout_forward(const GopsRolloutDesc& d, const GopsRolloutIn& in, const GopsRolloutOut& out, void* ws, size_t bytes, hipStream_t s);
+int poly_rollout_backward(const GopsRolloutDesc& d, const float* grad_v, const GopsMlpGrad& g, void* ws, size_t bytes, hipStream_t s);
+size_t poly_value_workspace_bytes(const GopsMlp& v, int B);
+int poly_value_forward(const GopsMlp& v, int B, const float* obs, float* out, hipStream_t s);
+int poly_value_backward(const GopsMlp& v, int B, const float* obs, const float* grad_v, const GopsMlpGrad& g, void* ws, size_t bytes,
+                        hipStream_t s);
 hipError_t launch_env_step(const GopsEnv& env, int B, const GopsStepIO& io, float pdt, hipStream_t s);
 hipError_t launch_env_constraint(const GopsEnv& env, int B, const GopsStepIO& io, hipStream_t s);
 bool ss_eligible(const RolloutParams& p);   // rollout_fwd.hip
@@ -861,6 +869,33 @@ int gops_mlp_backward_x(const GopsMlp* mlp, int32_t batch, const float* x, const
 }
 
 int gops_hip_version(void) { return GOPS_HIP_ABI_VERSION; }
+
+size_t gops_poly_rollout_workspace_bytes(const GopsRolloutDesc* desc) { return desc ? poly_rollout_workspace_bytes(*desc) : 0; }
+
+int gops_poly_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const GopsRolloutOut* out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (!desc || !in || !out) return GOPS_ERR_BAD_ARG;
+    return poly_rollout_forward(*desc, *in, *out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int gops_poly_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v, const GopsMlpGrad* policy_grad,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    if (!desc || !in || !policy_grad) return GOPS_ERR_BAD_ARG;
+    return poly_rollout_backward(*desc, grad_v, *policy_grad, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t gops_poly_value_workspace_bytes(const GopsMlp* value, int32_t batch) { return value ? poly_value_workspace_bytes(*value, batch) : 0; }
+
+int gops_poly_value_forward(const GopsMlp* value, int32_t batch, const float* obs, float* v, void* stream) {
+    if (!value) return GOPS_ERR_BAD_ARG;
+    return poly_value_forward(*value, batch, obs, v, static_cast<hipStream_t>(stream));
+}
+
+int gops_poly_value_backward(const GopsMlp* value, int32_t batch, const float* obs, const float* grad_v, const GopsMlpGrad* grad,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (!value || !grad) return GOPS_ERR_BAD_ARG;
+    return poly_value_backward(*value, batch, obs, grad_v, *grad, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
 
 size_t gops_rollout_workspace_bytes(const GopsRolloutDesc* desc) {
     if (desc == nullptr) return 0;

@@ -22,6 +22,9 @@ MOBILEROBOT_NOISE_STD = (0.03, 0.02)
 MAX_SURR = 4
 MAX_REPEAT = 8   # GOPS_MAX_REPEAT
 ACT_IDS = {"linear": 0, "relu": 1, "elu": 2, "gelu": 3, "selu": 4, "sigmoid": 5, "tanh": 6}
+# GopsMlp.hidden_act of a POLY net (ABI v15): make_features(obs, d) for d = 1, 2, 3 and create_features(obs * norm_matrix, 2)
+POLY_FULL = {1: 16, 2: 17, 3: 18}
+POLY_SYM_2 = 24
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "fp16": 1, "f16": 1, "float16": 1, "half": 1}
 
 
@@ -193,6 +196,21 @@ def lib() -> C.CDLL:
                                                           C.POINTER(GopsRolloutAdjoint), C.c_void_p, C.c_size_t, C.c_void_p]
         l.gops_rollout_variant.restype = C.c_int
         l.gops_rollout_variant.argtypes = [C.POINTER(GopsRolloutDesc)]
+        l.gops_poly_rollout_workspace_bytes.restype = C.c_size_t
+        l.gops_poly_rollout_workspace_bytes.argtypes = [C.POINTER(GopsRolloutDesc)]
+        l.gops_poly_rollout_forward.restype = C.c_int
+        l.gops_poly_rollout_forward.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.POINTER(GopsRolloutOut),
+                                                C.c_void_p, C.c_size_t, C.c_void_p]
+        l.gops_poly_rollout_backward.restype = C.c_int
+        l.gops_poly_rollout_backward.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.c_void_p,
+                                                 C.POINTER(GopsMlpGrad), C.c_void_p, C.c_size_t, C.c_void_p]
+        l.gops_poly_value_workspace_bytes.restype = C.c_size_t
+        l.gops_poly_value_workspace_bytes.argtypes = [C.POINTER(GopsMlp), C.c_int32]
+        l.gops_poly_value_forward.restype = C.c_int
+        l.gops_poly_value_forward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gops_poly_value_backward.restype = C.c_int
+        l.gops_poly_value_backward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsMlpGrad),
+                                               C.c_void_p, C.c_size_t, C.c_void_p]
         l.gops_profile_enable.argtypes = [C.c_int32]
         l.gops_profile_reset.argtypes = []
         l.gops_profile_read.restype = C.c_int
@@ -207,7 +225,9 @@ EXPORTED_SYMBOLS = ("gops_hip_version", "gops_rollout_workspace_bytes", "gops_ro
                     "gops_mlp_backward", "gops_mlp_backward_x", "gops_adam_step", "gops_profile_enable",
                     "gops_profile_reset", "gops_profile_read", "gops_rollout_variant", "gops_rollout_backward_open_loop_adj",
                     "gops_env_constraint", "gops_polyak_update", "gops_value_loss", "gops_mean_loss", "gops_rollout_backward_update",
-                    "gops_value_backward_update")
+                    "gops_value_backward_update", "gops_poly_rollout_workspace_bytes", "gops_poly_rollout_forward",
+                    "gops_poly_rollout_backward", "gops_poly_value_workspace_bytes", "gops_poly_value_forward",
+                    "gops_poly_value_backward")
 
 _ERR = {-1: "GOPS_ERR_BAD_ARG", -2: "GOPS_ERR_UNSUPPORTED", -3: "GOPS_ERR_WORKSPACE"}
 
@@ -543,6 +563,129 @@ class Rollout:
                                                     self.workspace.data_ptr(), self.workspace.numel(), _stream()),
               "gops_rollout_backward_open_loop")
         return g
+
+
+def make_poly(weight: torch.Tensor, bias: Optional[torch.Tensor], feature_code: int,
+              norm_matrix: Optional[torch.Tensor] = None) -> GopsMlp:
+    """`GopsMlp` of a POLY net (ABI v15): n_layers = 1, sizes = (obs_dim, out width, weight columns), hidden_act = a POLY_*
+    feature-map code, weight[0] = the Linear weight [out][F (+1)], bias[0] = its bias or NULL, weight[1] = norm_matrix [obs_dim] or
+    NULL (value).  The library checks the column count against the feature map and the rollout's finite_horizon."""
+    m = GopsMlp()
+    m.n_layers = 1
+    m.hidden_act = int(feature_code)
+    m.weight[0], m.bias[0] = _ptr(weight), _ptr(bias)
+    m.weight[1] = _ptr(norm_matrix)
+    m.sizes[1], m.sizes[2] = weight.shape[0], weight.shape[1]
+    m._keep = (weight, bias, norm_matrix)
+    return m
+
+
+def _poly_grad(grad_w: torch.Tensor, grad_b: Optional[torch.Tensor]) -> GopsMlpGrad:
+    g = GopsMlpGrad()
+    g.weight[0], g.bias[0] = _ptr(grad_w), _ptr(grad_b)
+    return g
+
+
+class PolyRollout:
+    """`Rollout`'s call surface for a POLY policy (and POLY tail value): `gops_poly_rollout_forward / _backward`, one lane per
+    trajectory (csrc/rollout_poly.hip).  `backward(grad_v, [grad_weight], [grad_bias or None])` - the lists hold the one Linear
+    layer's gradient tensors, as `grad_buffers` / `poly_grad_buffers` hand them out.  No phases, no fused update tail: a POLY net
+    has one or two tensors."""
+
+    def __init__(self, env: GopsEnv, policy: GopsMlp, *, batch: int, horizon: int, gamma: float, finite_horizon: bool,
+                 need_grad: bool = True, value: Optional[GopsMlp] = None, device: Optional[torch.device] = None,
+                 tail_unmasked: bool = False, dtype=None, variant_flags: Optional[int] = None):
+        """`dtype` must be fp32 and `variant_flags` empty: the POLY kernels have no other arithmetic and no variants."""
+        if dtype_id(dtype) != 0:
+            raise RuntimeError("PolyRollout: POLY approximators run in fp32 only (mlp_dtype fp16 is an MLP setting)")
+        if variant_flags:
+            raise RuntimeError(f"PolyRollout: no kernel variants on the POLY path (variant_flags {variant_flags:#x})")
+        d = self.desc = GopsRolloutDesc()
+        d.batch, d.horizon, d.finite_horizon = batch, horizon, int(finite_horizon)
+        d.need_grad, d.tail_value, d.gamma = int(need_grad), int(value is not None), float(gamma)
+        d.tail_unmasked = int(bool(tail_unmasked))
+        d.env = env
+        policy.sizes[0] = env.obs_dim
+        d.policy = policy
+        if value is not None:
+            value.sizes[0] = env.obs_dim
+            d.value = value
+        self._mlps = (policy, value)
+        nbytes = lib().gops_poly_rollout_workspace_bytes(C.byref(d))
+        if nbytes == 0:
+            raise RuntimeError("gops_poly_rollout_workspace_bytes: descriptor rejected (POLY net, env model or wrapper outside "
+                               "the HIP POLY path)")
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._in = GopsRolloutIn()
+
+    def set_policy(self, policy: GopsMlp, value: Optional[GopsMlp] = None):
+        if policy is not self._mlps[0]:
+            policy.sizes[0] = self.desc.env.obs_dim
+            self.desc.policy = policy
+        if value is not None and value is not self._mlps[1]:
+            value.sizes[0] = self.desc.env.obs_dim
+            self.desc.value = value
+        self._mlps = (policy, value if value is not None else self._mlps[1])
+
+    def forward(self, data: Dict[str, torch.Tensor], *, want_rewards=False, want_final=False):
+        d = self.desc
+        B, H, O = d.batch, d.horizon, d.env.obs_dim
+        i = self._in
+        i.obs, i.done = _ptr(data["obs"]), _ptr(data.get("done"))
+        self._keep = dict(data)
+        out = GopsRolloutOut()
+        res = {"v_pi": torch.empty(B, dtype=torch.float32, device=self.device)}
+        out.v_pi = _ptr(res["v_pi"])
+        if want_rewards:
+            res["rewards"] = torch.empty(H, B, dtype=torch.float32, device=self.device)
+            out.rewards = _ptr(res["rewards"])
+        if want_final:
+            res["final_obs"] = torch.empty(B, O, dtype=torch.float32, device=self.device)
+            res["final_done"] = torch.empty(B, dtype=torch.float32, device=self.device)
+            out.final_obs, out.final_done = _ptr(res["final_obs"]), _ptr(res["final_done"])
+        check(lib().gops_poly_rollout_forward(C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(),
+                                              self.workspace.numel(), _stream()), "gops_poly_rollout_forward")
+        return res
+
+    def backward(self, grad_v: torch.Tensor, grad_w: List[torch.Tensor], grad_b: List[Optional[torch.Tensor]], **kw):
+        if any(v is not None for v in kw.values()):
+            raise NotImplementedError(f"PolyRollout.backward: {sorted(k for k, v in kw.items() if v is not None)} "
+                                      "do not apply to a POLY rollout")
+        g = _poly_grad(grad_w[0], grad_b[0] if grad_b else None)
+        check(lib().gops_poly_rollout_backward(C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g),
+                                               self.workspace.data_ptr(), self.workspace.numel(), _stream()),
+              "gops_poly_rollout_backward")
+
+
+class PolyValueNet:
+    """`ValueNet`'s call surface for a POLY StateValue (`gops_poly_value_forward / _backward`)."""
+
+    def __init__(self, value: GopsMlp, batch: int, obs_dim: int, device: Optional[torch.device] = None):
+        value.sizes[0] = obs_dim
+        self.mlp, self.batch, self.obs_dim = value, batch, obs_dim
+        nbytes = lib().gops_poly_value_workspace_bytes(C.byref(value), batch)
+        if nbytes == 0:
+            raise RuntimeError("gops_poly_value_workspace_bytes: unsupported POLY value network for the HIP path")
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def set_net(self, value: GopsMlp):
+        value.sizes[0] = self.obs_dim
+        self.mlp = value
+
+    def forward(self, obs: torch.Tensor) -> torch.Tensor:
+        v = torch.empty(self.batch, dtype=torch.float32, device=self.device)
+        check(lib().gops_poly_value_forward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(v), _stream()), "gops_poly_value_forward")
+        return v
+
+    def backward(self, obs: torch.Tensor, grad_v: torch.Tensor, grad_w, grad_b, tail=None):
+        if tail is not None:
+            raise NotImplementedError("PolyValueNet.backward: no fused update tail on the POLY path")
+        g = _poly_grad(grad_w[0], grad_b[0] if grad_b else None)
+        check(lib().gops_poly_value_backward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g),
+                                             self.workspace.data_ptr(), self.workspace.numel(), _stream()),
+              "gops_poly_value_backward")
 
 
 class ValueNet:

@@ -24,18 +24,23 @@ def get_activation_func(key: str):
 
 def get_apprfunc_dict(key: str, **kwargs):
     """Collect the per-network constructor arguments `<key>_func_type`, `<key>_hidden_sizes`, ...
-    out of the flat args dict (only the MLP family exists on this path)."""
+    out of the flat args dict (the MLP and POLY families exist on this path)."""
     var = dict()
     var["apprfunc"] = kwargs[key + "_func_type"]
     var["name"] = kwargs[key + "_func_name"]
     var["obs_dim"] = kwargs["obsv_dim"]
     var["pre_horizon"] = kwargs.get("pre_horizon", None)
     apprfunc_type = kwargs[key + "_func_type"]
-    if apprfunc_type != "MLP":
-        raise NotImplementedError(f"apprfunc type {apprfunc_type} is outside the MI355X ADP path (MLP only)")
-    var["hidden_sizes"] = kwargs[key + "_hidden_sizes"]
-    var["hidden_activation"] = kwargs[key + "_hidden_activation"]
-    var["output_activation"] = kwargs.get(key + "_output_activation", "linear")
+    if apprfunc_type == "MLP":
+        var["hidden_sizes"] = kwargs[key + "_hidden_sizes"]
+        var["hidden_activation"] = kwargs[key + "_hidden_activation"]
+        var["output_activation"] = kwargs.get(key + "_output_activation", "linear")
+    elif apprfunc_type == "POLY":   # gops_amd/apprfunc/poly.py (reference common_utils.py:89-91)
+        var["degree"] = kwargs[key + "_degree"]
+        var["add_bias"] = kwargs[key + "_add_bias"]
+        var["norm_matrix"] = kwargs.get("norm_matrix", None)
+    else:
+        raise NotImplementedError(f"apprfunc type {apprfunc_type} is outside the MI355X ADP path (MLP and POLY only)")
     if kwargs["action_type"] == "continu":
         var["act_high_lim"] = np.array(kwargs["action_high_limit"])
         var["act_low_lim"] = np.array(kwargs["action_low_limit"])

@@ -45,7 +45,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GOPS_HIP_ABI_VERSION 14
+#define GOPS_HIP_ABI_VERSION 15
 
 #define GOPS_MAX_LAYERS 5   /* Linear layers per MLP (<= 4 hidden + output) */
 #define GOPS_MAX_ACT 4      /* action dimensions */
@@ -82,6 +82,11 @@ enum { GOPS_ENV_NONE = 0, GOPS_ENV_LQ = 1, GOPS_ENV_IDPENDULUM = 2, GOPS_ENV_VEH
 /* hidden activations: gops/utils/common_utils.py:26-55 */
 enum { GOPS_ACT_LINEAR = 0, GOPS_ACT_RELU = 1, GOPS_ACT_ELU = 2, GOPS_ACT_GELU = 3,
        GOPS_ACT_SELU = 4, GOPS_ACT_SIGMOID = 5, GOPS_ACT_TANH = 6 };
+/* ABI v15: feature maps of a POLY net (gops/apprfunc/poly.py), in GopsMlp.hidden_act of a description with n_layers = 1.
+ *   GOPS_POLY_FULL_d  make_features(obs, d) (:30-49): for k = 1..d the full k-fold outer product of the observation in n_matmul
+ *                     order, i-major, duplicates included (degree 3: (x_i x_j) x_l): F = n + n^2 + .. + n^d features.
+ *   GOPS_POLY_SYM_2   create_features(obs * norm_matrix, 2) (:61-83): x_i x_j for i <= j, i-major: n (n + 1) / 2 features. */
+enum { GOPS_POLY_FULL_1 = 16, GOPS_POLY_FULL_2 = 17, GOPS_POLY_FULL_3 = 18, GOPS_POLY_SYM_2 = 24 };
 
 /* Arithmetic of the MLP contractions (BASELINE.json configs[4]: "fp16 MFMA MLP path").
  *   GOPS_DTYPE_F32: fp32 results at the 1e-4 parity bar (default).  NOT bit-level fp32 arithmetic where the plane-split
@@ -468,6 +473,32 @@ int gops_polyak_update(const GopsAdamTensors* tensors, double tau, void* stream)
 #define GOPS_LOSS_STATS_FLOATS 260
 int gops_value_loss(const float* v, const float* target, int32_t n, float* grad, float* stats, void* stream);
 int gops_mean_loss(const float* x, int32_t n, double scale, float* stats, void* stream);
+
+/* ABI v15.  POLY approximators (gops/apprfunc/poly.py: DetermPolicy, FiniteHorizonPolicy, StateValue) on the model rollout, one lane per
+ * trajectory (csrc/rollout_poly.hip).  A POLY net is a GopsMlp with n_layers = 1 (which the MLP entry points reject):
+ *   sizes[0] = obs_dim, sizes[1] = out width (act_dim for a policy, 1 for a value), sizes[2] = columns of weight[0] (F, plus 1 for a
+ *   FiniteHorizonPolicy; checked against desc->finite_horizon: GOPS_ERR_BAD_ARG otherwise), hidden_act = GOPS_POLY_*,
+ *   weight[0] = [out][F (+1)] row-major (+1: FiniteHorizonPolicy's virtual_t = step + 1 column AFTER the features; the rollout
+ *   takes it when desc->finite_horizon = 1), bias[0] = [out] or NULL (add_bias), weight[1] = norm_matrix [obs_dim] or NULL (value only);
+ *   GopsMlpGrad.weight[0] / bias[0] likewise.
+ * No tanh squash: the raw linear output goes into ScaleAction / ClipAction.  The rollout is that of gops_rollout_forward / _backward for
+ * GOPS_ENV_LQ (obs_dim <= 6), _IDPENDULUM, _CARTPOLE and _PENDULUM with every wrapper those take (MaskAtDone or none, ClipObservation,
+ * ShapingReward, ScaleObservation, ActionRepeat); policy degree 1 or 2 for every obs_dim, degree 3 for obs_dim <= 3; the tail value
+ * (tail_value, tail_unmasked) must be a GOPS_POLY_SYM_2 net.  fp32 only (GOPS_DTYPE_F16 refused), closed loop only, variant_flags 0.
+ * Anything else - an MLP policy or value in the description, another env kind - returns GOPS_ERR_UNSUPPORTED.
+ * The weight gradient is summed over trajectories in a fixed order (per-block partial rows, then one reduce launch): bitwise
+ * reproducible run to run. */
+size_t gops_poly_rollout_workspace_bytes(const GopsRolloutDesc* desc);
+int gops_poly_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const GopsRolloutOut* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int gops_poly_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v,
+                               const GopsMlpGrad* policy_grad, void* workspace, size_t workspace_bytes, void* stream);
+/* POLY StateValue (GOPS_POLY_SYM_2) over a batch: v [batch] = V(obs [batch, obs_dim]) and its backward into the parameters
+ * (INFADP's policy evaluation; gops_value_loss / gops_adam_step / gops_polyak_update take the tensors as they are). */
+size_t gops_poly_value_workspace_bytes(const GopsMlp* value, int32_t batch);
+int gops_poly_value_forward(const GopsMlp* value, int32_t batch, const float* obs, float* v, void* stream);
+int gops_poly_value_backward(const GopsMlp* value, int32_t batch, const float* obs, const float* grad_v,
+                             const GopsMlpGrad* grad, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,

@@ -1,0 +1,292 @@
+"""GPU: POLY approximators (apprfunc/poly.py) on the one-lane-per-trajectory HIP rollout (csrc/rollout_poly.hip), through
+`create_alg(...)` and `hb.PolyRollout` / `hb.PolyValueNet`, against the reference fixtures of tests/golden/make_golden_poly.py."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import golden_meta, load_golden, rel_l2
+from helpers import data_from_golden
+
+from gops_amd import hip_backend as hb
+from gops_amd.algorithm.base import poly_grad_buffers
+from gops_amd.create_pkg.create_alg import create_alg
+from gops_amd.utils.synthetic import act_dim_of, make_batch, obs_dim_of
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+
+
+def _kwargs(cfg, extra, seed, lim=None):
+    A = act_dim_of(cfg)
+    lo, hi = (-np.ones(A, dtype=np.float32), np.ones(A, dtype=np.float32)) if lim is None else \
+        (np.array(lim[0], dtype=np.float32), np.array(lim[1], dtype=np.float32))
+    kw = dict(algorithm=cfg["alg"], trainer="off_serial_trainer", seed=seed, cnn_shared=False, env_id=cfg["env_id"],
+              obsv_dim=obs_dim_of(cfg), action_dim=A, action_type="continu", action_high_limit=hi, action_low_limit=lo,
+              policy_func_name="FiniteHorizonPolicy" if cfg["alg"] == "FHADP" else "DetermPolicy",
+              policy_act_distribution="default", policy_learning_rate=1e-3, use_gpu=True)
+    if cfg["alg"] == "FHADP":
+        kw["pre_horizon"] = cfg.get("pre_horizon", cfg["horizon"])
+    if "lq_config" in cfg:
+        kw["lq_config"] = cfg["lq_config"]
+    kw.update(extra)
+    return kw
+
+
+def _load_alg(name):
+    g = load_golden(name)
+    meta = golden_meta(g)
+    cfg = meta["cfg"]
+    alg = create_alg(**_kwargs(cfg, meta["extra"], meta["seed"], meta.get("lim")))
+    sd = {k[3:]: torch.from_numpy(np.array(v)) for k, v in g.items() if k.startswith("sd/")}
+    alg.load_state_dict(sd)
+    alg.networks.cuda()
+    alg.gamma = cfg["gamma"]
+    if cfg["alg"] == "INFADP":
+        alg.forward_step = cfg["horizon"]
+    return alg, g, cfg
+
+
+def _close(got, want):
+    return abs(float(got) - float(want)) <= TOL * max(1.0, abs(float(want)))
+
+
+@pytest.mark.parametrize("name", ["fhadp_poly_lqs2a1_h80", "fhadp_poly_lqs6a3_d2_bias_h30", "fhadp_poly_idp_d1_bias_h20",
+                                  "fhadp_poly_lqs3a1_obsscale_repeat2"])
+def test_fhadp_poly_matches_reference(name):
+    alg, g, cfg = _load_alg(name)
+    assert isinstance(next(iter(alg._rollouts.values()), None), (type(None), hb.PolyRollout))
+    tb, info = alg.get_remote_update_info(data_from_golden(g), 0)
+    assert _close(tb["Loss/Actor loss-RL iter"], g["loss"])
+    assert len(info["grad"]) == len(list(alg.networks.policy.parameters()))
+    for i, gr in enumerate(info["grad"]):
+        assert rel_l2(gr.cpu(), g[f"grad/{i}"]) < TOL, i
+    assert all(isinstance(ro, hb.PolyRollout) for ro in alg._rollouts.values())
+
+
+@pytest.mark.parametrize("name", ["infadp_poly_lqs4a2", "infadp_poly_lqs4a2_fs5", "infadp_trained_poly_lqs4a2"])
+def test_infadp_poly_matches_reference(name):
+    alg, g, cfg = _load_alg(name)
+    data = data_from_golden(g)
+    tb, info = alg.get_remote_update_info(data, 0)       # PEV
+    assert _close(tb["Loss/Critic loss-RL iter"], g["pev_loss"])
+    assert _close(tb["Train/Critic avg value-RL iter"], g["pev_vmean"])
+    for i, gr in enumerate(info["v"]):
+        assert rel_l2(gr.cpu(), g[f"pev_grad/{i}"]) < TOL, i
+    tb, info = alg.get_remote_update_info(data, 1)       # PIM
+    assert _close(tb["Loss/Actor loss-RL iter"], g["pim_loss"])
+    for i, gr in enumerate(info["policy"]):
+        assert rel_l2(gr.cpu(), g[f"pim_grad/{i}"]) < TOL, i
+
+
+def test_fhadp_poly_five_updates_match_reference():
+    """Five `local_update` calls (Adam included; eager, then captured / replayed under the default graph policy) land on the
+    reference's weights."""
+    g = load_golden("fhadp_poly_lqs2a1_5updates")
+    meta = golden_meta(g)
+    cfg = meta["cfg"]
+    alg = create_alg(**_kwargs(cfg, meta["extra"], meta["seed"]))
+    alg.load_state_dict({k[4:]: torch.from_numpy(np.array(v)) for k, v in g.items() if k.startswith("sd0/")})
+    alg.networks.cuda()
+    alg.gamma = cfg["gamma"]
+    for k in range(5):
+        tb = alg.local_update(data_from_golden(g, f"in{k}/"), k)
+        assert _close(tb["Loss/Actor loss-RL iter"], g[f"loss{k}"]), k
+    for key, p in alg.networks.state_dict().items():
+        want = g["sd5/" + key]
+        assert rel_l2(p.cpu().double(), want) < TOL, key
+
+
+def _poly_rollout(alg, B, device="cuda"):
+    return alg._rollout_for(B, torch.device(device))
+
+
+@pytest.mark.parametrize("B", [1, 300])
+def test_poly_gradient_is_bitwise_reproducible(B):
+    alg, g, cfg = _load_alg("fhadp_poly_lqs6a3_d2_bias_h30")
+    data = {k: v.cuda() for k, v in make_batch(dict(cfg, batch=B), 11).items()}
+    ro = _poly_rollout(alg, B)
+    gv = torch.full((B,), -1.0 / B, device="cuda")
+    outs = []
+    for _ in range(2):
+        res = ro.forward(data, want_rewards=True, want_final=True)
+        gw = [torch.empty_like(alg.networks.policy.pi.weight)]
+        gb = [torch.empty_like(alg.networks.policy.pi.bias)]
+        ro.backward(gv, gw, gb)
+        torch.cuda.synchronize()
+        outs.append((res["v_pi"].clone(), gw[0].clone(), gb[0].clone()))
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+    assert torch.isfinite(outs[0][1]).all() and outs[0][1].abs().sum() > 0
+
+
+def test_poly_batch_slices_are_independent_and_gradients_add_up():
+    """Large batch (B = 65 536, H = 80, the s2a1 example's net): each trajectory's return is computed by its own lane, so a slice
+    of the batch run on its own gives the same bits; the full gradient is the sum of the slices' gradients."""
+    alg, g, cfg = _load_alg("fhadp_poly_lqs2a1_h80")
+    B = 65536
+    data = {k: v.cuda() for k, v in make_batch(dict(cfg, batch=B), 3).items()}
+    ro = _poly_rollout(alg, B)
+    v_full = ro.forward(data, want_final=True)["v_pi"]
+    W = alg.networks.policy.pi.weight
+    gw = [torch.empty_like(W)]
+    ro.backward(torch.full((B,), 1.0, device="cuda"), gw, [None])
+    S = 4096
+    acc = torch.zeros_like(W, dtype=torch.float64)
+    ro_s = _poly_rollout(alg, S)
+    for s0 in range(0, B, S):
+        sl = {k: v[s0:s0 + S].contiguous() for k, v in data.items()}
+        v_s = ro_s.forward(sl)["v_pi"]
+        assert torch.equal(v_s, v_full[s0:s0 + S])
+        gs = [torch.empty_like(W)]
+        ro_s.backward(torch.full((S,), 1.0, device="cuda"), gs, [None])
+        acc += gs[0].double()
+    assert rel_l2(gw[0].cpu().double(), acc.cpu()) < 1e-5
+    res = ro.forward(data, want_rewards=True, want_final=True)
+    _check_against_f64(alg, data, res, cfg, fh=True)
+
+
+def _lq_f64(alg, data, n_rows, horizon, gamma, fh, value=None):
+    """A float64 restatement of the wrapped pyth_lq rollout with a POLY degree-1 policy on the first n_rows trajectories:
+    ScaleAction / ClipAction, x' = inv_IA (x + dt B u), r = rs (rsh - (Q x^2 + R u^2)), ShapingReward, MaskAtDone, ClipObservation,
+    and the tail (~done_H) gamma^H V(x_H) of a POLY StateValue (degree 2, no norm_matrix).  -> v, rewards [H, n], x_H, done_H."""
+    env = alg.envmodel.hip_env()
+    n, m = env.obs_dim, env.act_dim
+    f = lambda vals, k: torch.tensor(list(vals)[:k], dtype=torch.float64)
+    inv_IA, Bm = f(env.lq_inv_IA, n * n).reshape(n, n), f(env.lq_B, n * m).reshape(n, m)
+    Q, R = f(env.lq_Q, n), f(env.lq_R, m)
+    amin, amax, alo, ahi = f(env.min_action, m), f(env.max_action, m), f(env.act_low, m), f(env.act_high, m)
+    W = alg.networks.policy.pi.weight.detach().cpu().double()
+    x = data["obs"][:n_rows].cpu().double()
+    done = data["done"][:n_rows].cpu() != 0
+    v = torch.zeros(n_rows, dtype=torch.float64)
+    rewards = []
+    for t in range(horizon):
+        a = x @ W[:, :n].T + ((t + 1) * W[:, n] if fh else 0.0)
+        u = torch.minimum(torch.maximum(alo + (ahi - alo) * (torch.minimum(torch.maximum(a, amin), amax) - amin) / (amax - amin), alo), ahi)
+        r = env.lq_reward_scale * (env.lq_reward_shift - ((Q * x * x).sum(1) + (R * u * u).sum(1)))
+        xn = (x + env.lq_dt * u @ Bm.T) @ inv_IA.T
+        if env.clip_obs:
+            xn = torch.minimum(torch.maximum(xn, f(env.obs_low, n)), f(env.obs_high, n))
+        rr = torch.where(done, torch.zeros_like(r), r)
+        if env.shaping:
+            rr = (rr + env.reward_shift) * env.reward_scale
+        rewards.append(rr)
+        v += rr * gamma ** t
+        x = torch.where(done[:, None], x, xn)
+    if value is not None:
+        Wv = value.v.weight.detach().cpu().double().reshape(-1)
+        feats = torch.stack([x[:, i] * x[:, j] for i in range(n) for j in range(i, n)], 1)
+        v += torch.where(done, torch.zeros_like(v), torch.ones_like(v)) * gamma ** horizon * (feats @ Wv)
+    return v, torch.stack(rewards), x, done.double()
+
+
+def _check_against_f64(alg, data, res, cfg, fh, value=None, n_rows=256):
+    """v_pi at the 1e-4 bar, rewards and final_obs at 1e-5, final_done exactly, against the float64 restatement."""
+    v, rewards, x_H, d_H = _lq_f64(alg, data, n_rows, cfg["horizon"], cfg["gamma"], fh, value)
+    assert rel_l2(res["v_pi"][:n_rows].cpu().double(), v) < TOL
+    assert rel_l2(res["rewards"][:, :n_rows].cpu().double(), rewards) < 1e-5
+    assert rel_l2(res["final_obs"][:n_rows].cpu().double(), x_H) < 1e-5
+    assert torch.equal(res["final_done"][:n_rows].cpu().double(), d_H)
+
+
+def test_infadp_poly_large_batch():
+    """INFADP s4a2 (forward_step 5, POLY tail value) at B = 65 536: the policy-improvement rollout against the float64 restatement
+    on a slice, its gradient against the sum of the slices' gradients, and the POLY value kernels against float64 autograd."""
+    alg, g, cfg = _load_alg("infadp_poly_lqs4a2_fs5")
+    B = 65536
+    data = {k: v.cuda() for k, v in make_batch(dict(cfg, batch=B), 5).items()}
+    data["done"][::97] = 1.0
+    ro = alg._rollout_for(B, torch.device("cuda"), need_grad=True)
+    res = ro.forward(data, want_rewards=True, want_final=True)
+    _check_against_f64(alg, data, res, cfg, fh=False, value=alg.networks.v_target)
+    W = alg.networks.policy.pi.weight
+    gw = [torch.empty_like(W)]
+    ro.backward(torch.full((B,), 1.0, device="cuda"), gw, [None])
+    S = 8192
+    ro_s = alg._rollout_for(S, torch.device("cuda"), need_grad=True)
+    acc = torch.zeros_like(W, dtype=torch.float64)
+    for s0 in range(0, B, S):
+        sl = {k: v[s0:s0 + S].contiguous() for k, v in data.items()}
+        assert torch.equal(ro_s.forward(sl)["v_pi"], res["v_pi"][s0:s0 + S])
+        gs = [torch.empty_like(W)]
+        ro_s.backward(torch.full((S,), 1.0, device="cuda"), gs, [None])
+        acc += gs[0].double()
+    assert rel_l2(gw[0].cpu().double(), acc.cpu()) < 1e-5
+    # PEV's value net over the whole batch: forward and weight gradient against float64 autograd
+    vn = alg._value_for(B, torch.device("cuda"))
+    obs = data["obs"]
+    gv = torch.linspace(-1.0, 1.0, B, device="cuda")
+    v = vn.forward(obs)
+    gwv = [torch.empty_like(alg.networks.v.v.weight)]
+    vn.backward(obs, gv, gwv, [None])
+    Wv = alg.networks.v.v.weight.detach().double().clone().requires_grad_(True)
+    o64 = obs.double()
+    n = obs.shape[1]
+    feats = torch.stack([o64[:, i] * o64[:, j] for i in range(n) for j in range(i, n)], 1)
+    v64 = (feats @ Wv.reshape(-1, 1)).squeeze(-1)
+    (v64 * gv.double()).sum().backward()
+    assert rel_l2(v.double().cpu(), v64.detach().cpu()) < 1e-5
+    assert rel_l2(gwv[0].double().cpu(), Wv.grad.cpu()) < 1e-5
+
+
+def test_poly_value_kernels_match_host_module_and_autograd():
+    g = load_golden("poly_features")
+    from gops_amd.apprfunc.poly import StateValue
+    from gops_amd.utils.act_distribution import DiracDistribution
+    for name in ("value_nobias", "value_bias"):
+        sd = {k.split("/sd/")[1]: torch.from_numpy(np.array(v)) for k, v in g.items() if k.startswith(f"{name}/sd/")}
+        net = StateValue(obs_dim=4, degree=2, add_bias="v.bias" in sd, norm_matrix=np.array(g[f"{name}/norm"]).tolist(),
+                         action_distribution_cls=DiracDistribution)
+        net.load_state_dict(sd)
+        net.cuda()
+        obs = torch.from_numpy(np.array(g[f"{name}/obs"])).cuda()
+        B = obs.shape[0]
+        vn = hb.PolyValueNet(net.hip_mlp(), B, 4)
+        v = vn.forward(obs)
+        assert rel_l2(v.cpu(), g[f"{name}/out"]) < 1e-6
+        gv = torch.linspace(-1.0, 1.0, B, device="cuda")
+        gw, gb = poly_grad_buffers(net)
+        vn.backward(obs, gv, gw, gb)
+        got = [p.grad.clone() for p in net.parameters()]
+        net.zero_grad(set_to_none=True)
+        (net(obs) * gv).sum().backward()
+        for a, b in zip(got, [p.grad for p in net.parameters()]):
+            assert rel_l2(a.cpu().double(), b.cpu().double()) < 1e-5
+
+
+@pytest.mark.parametrize("mode", ["fhadp", "infadp"])
+def test_poly_update_paths_agree(mode, monkeypatch):
+    """Eager, captured and replayed updates give identical weights; get_remote_update_info + remote_update == local_update."""
+    name = "fhadp_poly_lqs2a1_h80" if mode == "fhadp" else "infadp_poly_lqs4a2_fs5"
+    algs = []
+    for flag in ("1", "0", "0"):
+        monkeypatch.setenv("GOPS_HIP_GRAPH", flag)
+        algs.append(_load_alg(name)[0])
+    cfg = golden_meta(load_golden(name))["cfg"]
+    for it in range(6):
+        data = {k: v.cuda() for k, v in make_batch(cfg, 70 + it).items()}
+        monkeypatch.setenv("GOPS_HIP_GRAPH", "1")
+        algs[0].local_update(data, it)
+        monkeypatch.setenv("GOPS_HIP_GRAPH", "0")
+        algs[1].local_update(data, it)
+        _, info = algs[2].get_remote_update_info(data, it)
+        algs[2].remote_update(info)
+    torch.cuda.synchronize()
+    for other in algs[1:]:
+        for (k, a), b in zip(algs[0].networks.state_dict().items(), other.networks.state_dict().values()):
+            assert torch.equal(a, b), k
+
+
+def test_poly_rollout_refuses_what_it_does_not_run():
+    alg, g, cfg = _load_alg("fhadp_poly_lqs2a1_h80")
+    env = alg.envmodel.hip_env()
+    pol = alg.networks.policy.hip_mlp()
+    with pytest.raises(RuntimeError):   # the MLP entry points keep rejecting n_layers = 1
+        hb.Rollout(env, pol, batch=8, horizon=4, gamma=1.0, finite_horizon=True)
+    bad = hb.GopsEnv.from_buffer_copy(env)
+    bad.kind = hb.ENV_VEH
+    with pytest.raises(RuntimeError):
+        hb.PolyRollout(bad, pol, batch=8, horizon=4, gamma=1.0, finite_horizon=True)
+    d = hb.PolyRollout(env, pol, batch=8, horizon=4, gamma=1.0, finite_horizon=True).desc
+    d.dtype = 1
+    assert hb.lib().gops_poly_rollout_workspace_bytes(d) == 0
