@@ -167,3 +167,274 @@ def fp32_noise_floor(env, net, data, horizon, gamma, ref64_flat, trials=8):
         flat = torch.cat([x.reshape(-1) for x in grads]).double()
         worst = max(worst, float((flat - ref64_flat).norm() / ref64_flat.norm()))
     return worst
+
+
+# ---- per-trajectory checks (tests/test_per_trajectory_gpu.py): float64 oracle with an explicit step loop ----------------------
+def take_rows(data, rows):
+    """The sub-batch `rows` of a replay batch (every tensor whose first axis is the batch axis)."""
+    B = data["obs"].shape[0]
+    idx = torch.as_tensor(list(rows), dtype=torch.long)
+    return {k: (v[idx] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for k, v in data.items()}
+
+
+class _appended_point:
+    """While active, the oracle's vehicle models append `point` [B, 4] instead of evaluating the reference generator: the
+    oracle then runs on the same appended reference points the kernels are handed (`GopsRolloutIn.ref_appended`), in any dtype."""
+
+    def __init__(self, point):
+        self.point = point
+
+    def __enter__(self):
+        self.saved = orc.ref_point
+        if self.point is not None:
+            orc.ref_point = lambda t, path_num, u_num: self.point.to(t.dtype)
+
+    def __exit__(self, *exc):
+        orc.ref_point = self.saved
+
+
+def appended_points(cfg, data):
+    """The H reference points a veh3dofconti rollout appends, from the oracle's restatement of MultiRefTrajModel: [B, H, 4]."""
+    P, dt = cfg["pre_horizon"], 0.1
+    t = data["ref_time"].clone()
+    pts = []
+    for _ in range(cfg["horizon"]):   # veh_step: nt = ref_time + dt (accumulated in fp32), new point at nt + P dt
+        t = t + dt
+        pts.append(orc.ref_point(t + P * dt, data["path_num"], data["u_num"]))
+    return torch.stack(pts, 1).contiguous()
+
+
+def done_margin(env, nobs):
+    """Relative distance of the quantities that decide `done` (on the observation a step returns) to their bounds, per row:
+    min_k | |q_k| - bound_k | / bound_k; inf for models that never terminate."""
+    kind = env["kind"]
+    if kind == "idp":
+        tip = orc.IDP["l1"] * torch.cos(nobs[:, 1]) + orc.IDP["l2"] * torch.cos(nobs[:, 2])
+        return torch.minimum((tip - 1.0).abs(), (nobs[:, 0].abs() - 15.0).abs() / 15.0)
+    if kind in ("veh", "veh_surr", "veh_err") and not env.get("penalty"):
+        q = nobs[:, :3].abs()
+        bound = torch.tensor([10.0, 10.0, np.pi], dtype=nobs.dtype)
+        return ((q - bound).abs() / bound).min(1).values
+    if kind == "veh2":
+        bound = torch.tensor([2.0, np.pi], dtype=nobs.dtype)
+        return ((nobs[:, :2].abs() - bound).abs() / bound).min(1).values
+    if kind == "cartpole":
+        bound = torch.tensor([2.4, 12 * 2 * np.pi / 360], dtype=nobs.dtype)
+        return ((nobs[:, [0, 2]].abs() - bound).abs() / bound).min(1).values
+    assert kind in ("lq", "pendulum") or env.get("penalty"), kind
+    return torch.full((nobs.shape[0],), float("inf"), dtype=nobs.dtype)
+
+
+def _policy_params(net):
+    return [p for pair in zip(net["w"], net["b"]) for p in pair if p is not None]
+
+
+def rollout_history(env, net, data, horizon, gamma, finite_horizon, value_target=None):
+    """The oracle's rollout (adp_oracle.rollout) as an explicit loop, in the dtype of its arguments, keeping what the loop
+    passes through: per-trajectory return `v` (tail value of `value_target` included, masked at done), `rewards` [H, B],
+    `done_hist` [H, B] (done after each step), `margin` [H, B] (done_margin of each step's observation for rows that entered the
+    step alive, inf otherwise), `final_obs`, `final_done`.  A net dict may carry its own `forward(net, obs, virtual_t)` (POLY)."""
+    obs, done, info = data["obs"], data["done"], data
+    app = data.get("ref_appended")
+    v = 0
+    rewards, done_hist, margin = [], [], []
+    for step in range(horizon):
+        t = step + 1 if finite_horizon else None
+        a = net["forward"](net, obs, t) if "forward" in net else orc.policy_forward(net, obs, t)
+        alive = ~done.bool()
+        with _appended_point(None if app is None else app[:, step]):
+            obs, r, done, info = orc.env_forward(env, obs, a, done, info)
+        v = v + r * (gamma ** step)
+        rewards.append(r)
+        done_hist.append(done)
+        m = done_margin(env, obs.detach())
+        margin.append(torch.where(alive, m, torch.full_like(m, float("inf"))))
+    if value_target is not None:
+        tail = value_target["forward"](value_target, obs) if "forward" in value_target else orc.value_forward(value_target, obs)
+        v = v + (~done) * gamma ** horizon * tail
+    return dict(v=v, rewards=torch.stack(rewards), done_hist=torch.stack(done_hist), margin=torch.stack(margin),
+                final_obs=obs, final_done=done)
+
+
+def _net_f64(net, requires_grad=True):
+    n64 = as_f64(net)
+    n64["w"] = [w.requires_grad_(requires_grad) for w in n64["w"]]
+    n64["b"] = [None if b is None else b.requires_grad_(requires_grad) for b in n64["b"]]
+    return n64
+
+
+def weighted_gradient_f64(env, nets, data, horizon, gamma, finite_horizon, gv, value_target=None):
+    """The oracle's rollout in float64 with loss = (gv * v).sum() (v with INFADP's tail value when `value_target` is given):
+    per-trajectory v, per-step rewards, the per-step done history, final obs / done and the policy's parameter gradients."""
+    n64 = _net_f64(nets)
+    vt = None if value_target is None else _net_f64(value_target, False)
+    out = rollout_history(as_f64(env), n64, as_f64(data), horizon, gamma, finite_horizon, vt)
+    loss = (torch.as_tensor(gv).double() * out["v"]).sum()
+    grads = torch.autograd.grad(loss, _policy_params(n64), allow_unused=True)
+    out = {k: x.detach() for k, x in out.items()}
+    out["grads"] = [torch.zeros_like(p) if g is None else g.detach() for g, p in zip(grads, _policy_params(n64))]
+    return out
+
+
+def one_row_gradients(env, nets, data, horizon, gamma, finite_horizon, rows, value_target=None):
+    """d v[i] / d(policy parameters) for every i of `rows`, in the dtype of the arguments: {row: [gradient per tensor]}.  The
+    trajectories of a batch do not interact, so the graph is built over the selected rows only."""
+    rows = list(rows)
+    out = rollout_history(env, nets, take_rows(data, rows), horizon, gamma, finite_horizon, value_target)
+    params = _policy_params(nets)
+    res = {}
+    for k, i in enumerate(rows):
+        if not out["v"][k].requires_grad:
+            res[i] = [torch.zeros_like(p) for p in params]
+            continue
+        g = torch.autograd.grad(out["v"][k], params, retain_graph=True, allow_unused=True)
+        res[i] = [torch.zeros_like(p) if x is None else x.detach() for x, p in zip(g, params)]
+    return res
+
+
+def one_row_gradients_f64(env, nets, data, horizon, gamma, finite_horizon, rows, value_target=None):
+    """The float64 gradient of ONE trajectory's return, for every row of `rows`."""
+    vt = None if value_target is None else _net_f64(value_target, False)
+    return one_row_gradients(as_f64(env), _net_f64(nets), as_f64(data), horizon, gamma, finite_horizon, rows, vt)
+
+
+def flat_grads(grads):
+    return torch.cat([g.reshape(-1) for g in grads]).double().cpu()
+
+
+def _dist(a, b):
+    den = float(b.norm())
+    return float((a - b).norm()) / (den if den > 0 else 1.0)
+
+
+def fp32_weighted_noise_floor(env, nets, data, horizon, gamma, finite_horizon, gv, ref64, rows=(), rows64=None,
+                              value_target=None, trials=2):
+    """fp32_noise_floor for a weighted loss and for single rows: the fp32 oracle, re-run with every weight moved by at most
+    one ulp, against the float64 results `ref64` (weighted_gradient_f64) / `rows64` (one_row_gradients_f64).  Returns
+    (largest rel-L2 distance of the weighted gradient - flat or any one tensor -, {row: largest distance of that row's gradient})."""
+    gen = torch.Generator().manual_seed(0)
+    worst, worst_rows = 0.0, {i: 0.0 for i in rows}
+    for trial in range(trials):
+        pert = dict(nets)
+        scale = 0.0 if trial == 0 else 1.2e-7   # (the first run is the unperturbed fp32 oracle)
+        pert["w"] = [(w.detach() * (1 + (torch.rand(w.shape, generator=gen) - 0.5) * scale)).requires_grad_(True) for w in nets["w"]]
+        pert["b"] = [None if b is None else b.detach().clone().requires_grad_(True) for b in nets["b"]]
+        out = rollout_history(env, pert, data, horizon, gamma, finite_horizon, value_target)
+        params = _policy_params(pert)
+        g = torch.autograd.grad((torch.as_tensor(gv).float() * out["v"]).sum(), params, allow_unused=True)
+        g = [torch.zeros_like(p) if x is None else x for x, p in zip(g, params)]
+        worst = max([worst, _dist(flat_grads(g), flat_grads(ref64["grads"]))]
+                    + [_dist(a.double(), b) for a, b in zip(g, ref64["grads"])])
+        if rows:
+            for i, gi in one_row_gradients(env, pert, data, horizon, gamma, finite_horizon, rows, value_target).items():
+                worst_rows[i] = max(worst_rows[i], _dist(flat_grads(gi), flat_grads(rows64[i])))
+    return worst, worst_rows
+
+
+def edge_rows(B, tile, n_workgroups):
+    """The rows of a batch of B that a tiled, grid-stride kernel is most likely to get wrong: 0, tile - 1, tile, the last row of the
+    last whole tile, the first and the last valid row of the ragged tile and - with more tiles than workgroups - the rows around the
+    first tile a workgroup takes on its second pass (tile * n_workgroups)."""
+    rows = {0, tile - 1, tile, B - 1}
+    whole = B // tile
+    if whole:
+        rows.add(whole * tile - 1)
+    if B % tile:
+        rows.add(whole * tile)
+    if -(-B // tile) > n_workgroups:
+        t2 = tile * n_workgroups
+        rows |= {t2 - 1, t2, t2 + tile - 1, t2 + tile}
+    return sorted(r for r in rows if 0 <= r < B)
+
+
+def edge_tiles(B, tile, n_workgroups):
+    return sorted({r // tile for r in edge_rows(B, tile, n_workgroups)})
+
+
+def premise_rows(B, tile, n_workgroups):
+    """Where batch_with_done puts its special rows: (rows done on entry, rows to terminate inside the horizon) - each list with a
+    tile-edge row, a row of the ragged (last) tile, a row of the second-pass tile where there is one, and a row in the middle."""
+    nt = -(-B // tile)
+    t2 = tile * n_workgroups
+    mid = (nt // 2) * tile + 5
+    d_cand = [tile - 1, B - 1, t2 if nt > n_workgroups else -1, mid, 5, 9, 13]
+    t_cand = [tile, B - 2, t2 + tile - 1 if nt > n_workgroups else -1, mid + 1, 3, 7, 11]
+    done_rows, term_rows = [], []
+    for r in d_cand:
+        if 0 < r < B and r not in done_rows and (len(done_rows) < 3 or r in d_cand[:4]):
+            done_rows.append(r)
+    for r in t_cand:
+        if 0 < r < B and r not in done_rows and r not in term_rows and (len(term_rows) < 3 or r in t_cand[:4]):
+            term_rows.append(r)
+    return done_rows, term_rows
+
+
+def _push_towards_termination(cfg, env, data, row, lam, sign):
+    """Row `row` of `data` with its initial state moved to `lam` short of a termination bound, heading across it."""
+    kind = env["kind"]
+    if kind == "idp":      # both angles just inside tip_y = l1 cos th1 + l2 cos th2 = 1, rotating outwards
+        crit = float(np.arccos(1.0 / (orc.IDP["l1"] + orc.IDP["l2"])))
+        data["obs"][row, 1:3] = sign * (crit - lam)
+        data["obs"][row, 4:6] = sign * 3.0
+    elif kind == "cartpole":   # cart just inside |x| = 2.4, moving outwards
+        data["obs"][row, 0] = sign * (2.4 - lam)
+        data["obs"][row, 1] = sign * 1.5
+    elif kind == "veh":    # lateral error (ego frame) just inside 10 m, heading 0.5 rad off the reference's: it grows by ~0.24 m a step
+        from gops_amd.utils.synthetic import veh_obs_f32
+        ref0 = data["ref_points"][row, 0].numpy()
+        state = data["state"][row].numpy().copy()
+        ephi = np.float32(ref0[2] - sign * 0.5)
+        d = np.float32(sign * (10.0 - lam))
+        state[0] = ref0[0] + d * np.sin(ephi)
+        state[1] = ref0[1] - d * np.cos(ephi)
+        state[2] = ephi
+        data["state"][row] = torch.from_numpy(state)
+        data["obs"][row] = torch.from_numpy(veh_obs_f32(state[None], data["ref_points"][row:row + 1].numpy())[0])
+    else:
+        raise KeyError(kind)
+
+
+_PUSH_GRID = {"idp": (0.003, 0.4), "cartpole": (0.004, 0.4), "veh": (0.02, 2.8)}
+DONE_MARGIN = 1e-3
+
+
+def batch_with_done(cfg, seed, env, net, tile, n_workgroups, finite_horizon=True):
+    """make_batch plus (a) rows with done = 1 on entry and (b) - for models that terminate - rows whose initial state is moved so
+    that the float64 oracle, under the policy `net`, ends them strictly inside the horizon (step 1 .. H - 1) with the deciding
+    quantity at least 2 * DONE_MARGIN away from its bound at every step up to there; both kinds on premise_rows(...).  veh3dofconti
+    batches carry the oracle's appended reference points (`ref_appended`).  Returns (data, done_rows, term_rows)."""
+    from gops_amd.utils.synthetic import make_batch
+    data = make_batch(cfg, seed)
+    H = cfg["horizon"]
+    if env["kind"] == "veh":
+        data["ref_appended"] = appended_points(cfg, data)
+    done_rows, term_rows = premise_rows(cfg["batch"], tile, n_workgroups)
+    if env["kind"] not in _PUSH_GRID or H < 2:
+        term_rows = []
+    if term_rows:
+        lams = np.geomspace(*_PUSH_GRID[env["kind"]], 40)
+        pool = take_rows(data, [r for r in term_rows for _ in lams])
+        pool = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in pool.items()}
+        for j, r in enumerate(term_rows):
+            for k, lam in enumerate(lams):
+                _push_towards_termination(cfg, env, pool, j * len(lams) + k, float(lam), 1.0 if (j + k) % 2 else -1.0)
+        with torch.no_grad():
+            hist = rollout_history(as_f64(env), as_f64(net), as_f64(pool), H, 1.0, finite_horizon)
+        first = H - hist["done_hist"].sum(0)                     # 0-based step whose result is the first done (H: never)
+        for j, r in enumerate(term_rows):
+            want = 1 + j % (H - 1)                              # spread the terminating steps over 1 .. H - 1
+            best = None
+            for k in range(len(lams)):
+                c = j * len(lams) + k
+                step = int(first[c]) + 1                         # 1-based terminating step
+                if not 1 <= step <= H - 1 or float(hist["margin"][:, c].min()) < 2 * DONE_MARGIN:
+                    continue
+                if best is None or abs(step - want) < abs(best[0] - want):
+                    best = (step, c)
+            assert best is not None, f"no initial state found that terminates row {r} inside the horizon"
+            for key, v in data.items():
+                if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == cfg["batch"]:
+                    v[r] = pool[key][best[1]]
+    data["done"][done_rows] = 1.0
+    data["obs2"] = data["obs"].clone()
+    return data, done_rows, term_rows

@@ -1246,3 +1246,69 @@ def test_precision_guard_decides_for_all_replicas_world_size_2(tmp_path):
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     assert (tmp_path / "ok_0").exists() and (tmp_path / "ok_1").exists()
+
+
+# ---- tests/test_per_trajectory_gpu.py: its helpers, its premises and its dispatch, without a GPU --------------------------------
+def test_edge_rows():
+    from helpers import edge_rows, premise_rows
+    assert edge_rows(1, 16, 256) == [0]
+    assert edge_rows(16, 16, 256) == [0, 15]
+    assert edge_rows(17, 16, 256) == [0, 15, 16]
+    assert edge_rows(40, 16, 256) == [0, 15, 16, 31, 32, 39]
+    assert edge_rows(63, 64, 256) == [0, 62]
+    assert edge_rows(65, 64, 256) == [0, 63, 64]
+    assert edge_rows(4096, 16, 256) == [0, 15, 16, 4095]                       # exactly one tile per workgroup: no second pass
+    assert edge_rows(4096 + 16 * 9 + 3, 16, 256) == [0, 15, 16, 4095, 4096, 4111, 4112, 4239, 4240, 4242]
+    assert edge_rows(4097, 16, 256) == [0, 15, 16, 4095, 4096]                 # the second pass is the ragged tile
+    assert edge_rows(2 * 4096 + 16 * 3 + 9, 16, 512) == [0, 15, 16, 8191, 8192, 8207, 8208, 8239, 8240, 8248]
+    assert edge_rows(64 * 300 + 21, 64, 256) == [0, 63, 64, 16383, 16384, 16447, 16448, 19199, 19200, 19220]
+    for B, tile, wg in ((1, 16, 256), (17, 16, 256), (63, 64, 256), (200, 16, 256), (4800, 16, 256), (19221, 64, 256)):
+        rows = edge_rows(B, tile, wg)
+        assert rows == sorted(set(rows)) and all(0 <= r < B for r in rows)
+        done_rows, term_rows = premise_rows(B, tile, wg)
+        assert not set(done_rows) & set(term_rows) and all(0 < r < B for r in done_rows + term_rows)
+        if B >= 2 * tile + 2:
+            assert any(r // tile == (B - 1) // tile for r in done_rows) and any(r // tile == (B - 1) // tile for r in term_rows)
+            assert any(r % tile in (0, tile - 1) for r in done_rows) and any(r % tile in (0, tile - 1) for r in term_rows)
+
+
+def _per_trajectory_cases():
+    import test_per_trajectory_gpu as pt
+    return pt, list(pt.CASES)
+
+
+@pytest.mark.parametrize("name", _per_trajectory_cases()[1])
+def test_per_trajectory_case_premises(name):
+    """What tests/test_per_trajectory_gpu.py assumes about its own inputs (rows done on entry and terminating inside the horizon
+    where they belong, margins to the termination bounds, the fp32 oracle within TOL / 3 of the float64 one for the weighted and
+    every single-row gradient): `prepare` asserts it; a change of make_batch or of the oracle cannot silently empty it."""
+    pt, _ = _per_trajectory_cases()
+    prep = pt.prepare(name)
+    B = prep["cfg"]["batch"]
+    if B >= 12:
+        assert len(prep["done_rows"]) >= 3
+        if prep["env"]["kind"] in ("idp", "veh", "cartpole") and prep["cfg"]["horizon"] >= 2:
+            assert len(prep["term_rows"]) >= 3
+    if prep["case"]["dtype"] is None:
+        assert prep["floor"] <= pt.TOL / 3 and max(prep["floor_rows"].values()) <= pt.TOL / 3
+
+
+@pytest.mark.parametrize("name", [n for n in _per_trajectory_cases()[1] if not _per_trajectory_cases()[0].CASES[n].get("poly")])
+def test_per_trajectory_case_reaches_its_kernel_family(name):
+    """Every case of the per-trajectory table still takes the kernels it was written for (gops_rollout_variant over the case's
+    description; batches lie clearly on one side of the one-tile-per-CU limit, which is 256 CUs with or without a device)."""
+    from gops_amd import hip_backend as hb
+    pt, _ = _per_trajectory_cases()
+    case = pt.CASES[name]
+    d = pt.rollout_desc(name)
+    variant = hb.lib().gops_rollout_variant(ctypes.byref(d))
+    assert variant >= 0, (name, variant)
+    if case["variant"] is not None:
+        assert variant == case["variant"], (name, variant)
+    nbytes = hb.lib().gops_rollout_workspace_bytes(ctypes.byref(d))
+    assert nbytes > 0
+    if name.startswith("sstream"):   # the sweep too: the streamed plane-split sweep carves transposed planes, the fp32 sweep does not
+        d.variant_flags |= hb.VF_NO_STREAMED_SPLIT_BWD
+        assert hb.lib().gops_rollout_workspace_bytes(ctypes.byref(d)) < nbytes, name
+    tiles = -(-case["batch"] // case["tile"])
+    assert abs(tiles - 256) >= 4 and abs(tiles - 512) >= 3, "a batch this close to the CU count does not pin the grid-stride walk"
