@@ -658,9 +658,11 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
     else jobs.poison = reinterpret_cast<const unsigned*>(p.gscale) + 3;   // (set by a plane-split forward / sweep whose conversions overflowed)
     // Two-half-plane weight-gradient GEMM (launch_dw_gemm): its delta scale is derived from max|grad_v|, which bounds the
     // deltas only when grad_v is the sweep's one gradient source - a terminal observation adjoint or constraint-sum
-    // gradients can be orders of magnitude larger, so those launches keep the exact three-plane product.
-    const float* dw_scale = (adj == nullptr && in.grad_constraint == nullptr && in.grad_constraint_prod == nullptr && in.grad_constraint_step == nullptr &&
-                             ext_delta == nullptr)
+    // gradients can be orders of magnitude larger, so those launches keep the exact three-plane product.  The penalty model's
+    // constraint outputs carry no gradient (gops_hip.h): its seeds are not a gradient source, and must not change the result.
+    const bool cstr_seeds = !(p.env.kind == GOPS_ENV_VEH3DOF_SURR && p.env.surr_penalty) &&
+                            (in.grad_constraint != nullptr || in.grad_constraint_prod != nullptr || in.grad_constraint_step != nullptr);
+    const float* dw_scale = (adj == nullptr && !cstr_seeds && ext_delta == nullptr)
                                 ? p.gscale : nullptr;
     for (int j = 0; j < L; ++j) {   // dW_j = D_{j+1}^T * (j == 0 ? X : H_j)
         if ((only_a && j == 0) || (only_b && j != 0)) continue;   // (two-phase backward: layer 0 is phase B)

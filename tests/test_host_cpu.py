@@ -1312,3 +1312,55 @@ def test_per_trajectory_case_reaches_its_kernel_family(name):
         assert hb.lib().gops_rollout_workspace_bytes(ctypes.byref(d)) < nbytes, name
     tiles = -(-case["batch"] // case["tile"])
     assert abs(tiles - 256) >= 4 and abs(tiles - 512) >= 3, "a batch this close to the CU count does not pin the grid-stride walk"
+
+
+# ---- tests/test_constrained_per_trajectory_gpu.py: the same, for the models with constraint outputs -------------------------------
+def _constrained_cases():
+    import test_constrained_per_trajectory_gpu as ct
+    return ct, list(ct.CASES)
+
+
+def test_seeded_reference_without_seeds_is_the_existing_one():
+    """helpers.seeded_gradients_f64 / one_row_seeded_gradients with `grad_v` as the only source return what weighted_gradient_f64 /
+    one_row_gradients_f64 return (an existing case without constraint outputs), and the appended reference points of a
+    veh2dofconti rollout make the oracle's fp32 and float64 runs append the same points."""
+    import helpers as h
+    pt, _ = _per_trajectory_cases()
+    prep = pt.prepare("plain_veh_256")
+    cfg, env, policy, data, gv, rows = prep["cfg"], prep["env"], prep["policy"], prep["data"], prep["gv"], prep["rows"]
+    hist, grads = h.seeded_gradients_f64(env, policy, data, cfg["horizon"], cfg["gamma"], True, {"gv": dict(gv=gv, gc=None, gp=None, gs=None)})
+    assert "constraints" not in hist and torch.equal(hist["v"], prep["ref"]["v"]) and torch.equal(hist["rewards"], prep["ref"]["rewards"])
+    assert all(torch.equal(a, b) for a, b in zip(grads["gv"], prep["ref"]["grads"]))
+    one_hot = lambda i, k: {"gv": dict(gv=torch.eye(len(rows))[k])}
+    got = h.one_row_seeded_gradients(h.as_f64(env), h._net_f64(policy), h.as_f64(data), cfg["horizon"], cfg["gamma"], True, rows, one_hot)
+    for i in rows:
+        assert all(torch.equal(a, b) for a, b in zip(got[i]["gv"], prep["rows64"][i]))
+
+
+@pytest.mark.parametrize("name", _constrained_cases()[1])
+def test_constrained_per_trajectory_case_premises(name):
+    """What tests/test_constrained_per_trajectory_gpu.py assumes about its inputs: special rows present and placed, the margins
+    and caps of the seeds, the fp32 oracle within TOL / 3 of the float64 one for the weighted gradient of every source and for
+    every selected single row (`prepare` asserts them) - and the kernel family of the case."""
+    from gops_amd import hip_backend as hb
+    ct, _ = _constrained_cases()
+    prep = ct.prepare(name)
+    case, B = ct.CASES[name], prep["cfg"]["batch"]
+    assert not prep["problems"]
+    assert max(prep["floor"].values()) <= ct.TOL / 3 and max(prep["floor_row_worst"].values()) <= ct.TOL / 3
+    assert int(prep["masks"]["log"].sum()) * 2 >= B
+    if prep["masked"]:
+        assert len(prep["done_rows"]) >= 3 and set(prep["done_rows"]) & set(prep["rows"])
+        if not prep["penalty"] and prep["cfg"]["horizon"] >= 2:
+            assert len(prep["term_rows"]) >= 3
+    d = ct.rollout_desc(name)
+    variant = hb.lib().gops_rollout_variant(ctypes.byref(d))
+    assert variant == case["variant"], (name, variant)
+    nbytes = hb.lib().gops_rollout_workspace_bytes(ctypes.byref(d))
+    assert nbytes > 0
+    if name.startswith("ss_"):   # the sweep too: the streamed plane-split sweep carves transposed planes, the fp32 sweep does not
+        d.variant_flags |= hb.VF_NO_STREAMED_SPLIT_BWD
+        assert hb.lib().gops_rollout_workspace_bytes(ctypes.byref(d)) < nbytes, name
+    tiles = -(-B // case["tile"])
+    assert abs(tiles - 256) >= 4 and abs(tiles - 512) >= 3
+    assert prep["walks"] == (name == "ss_mob_walk")

@@ -24,10 +24,10 @@ import torch
 from conftest import golden_meta, load_golden, rel_l2
 from helpers import (DONE_MARGIN, batch_with_done, edge_rows, edge_tiles, flat_grads, fp32_weighted_noise_floor, hip_env_from_oracle,
                      hip_mlp_from_net, one_row_gradients_f64, oracle_env, reference_init_nets, take_rows, to_device,
-                     weighted_gradient_f64, appended_points)
+                     weighted_gradient_f64, padded_batch)
 from oracle import adp_oracle as orc
 
-from gops_amd.utils.synthetic import act_dim_of, make_batch, obs_dim_of
+from gops_amd.utils.synthetic import act_dim_of, obs_dim_of
 
 pytestmark = pytest.mark.gpu
 
@@ -70,7 +70,9 @@ CASES = {
     "sstream_veh_2x256_tail_walk": _c("INFADP", "pyth_veh3dofconti", 4800, 4, W2, "elu", 0.99, SS_FWD, wg=(1, 2), pre_horizon=10, seed=5),
     "sstream_cartpole_3x256_tail": _c("INFADP", "gym_cartpoleconti", 200, 5, W3, "gelu", 0.99, SS_FWD, wg=(1, 2), seed=5),
     # (the sweep walks its tiles grid-stride, two workgroups per CU, only in the pyth_lq / cartpole / pendulum / mobilerobot forms:
-    #  more than 2 * CUs tiles of those reach a workgroup's second pass; the vehicle / idpendulum forms take one tile per workgroup)
+    #  more than 2 * CUs tiles of those reach a workgroup's second pass; the vehicle / idpendulum forms - veh3dofconti, every
+    #  GOPS_ENV_VEH3DOF_SURR form (surrcstr, detour, surrcstr_penalty, errcstr) and veh2dofconti - take one tile per workgroup:
+    #  rollout_bwd.hip ssb_fuse_kind.  tests/test_constrained_per_trajectory_gpu.py has the constrained kinds)
     "sstream_lq_2x256_tail_walk": _c("INFADP", "pyth_lq", 2 * 4096 + 16 * 5 + 7, 4, W2, "gelu", 0.99, SS_FWD, wg=(1, 2), lq_config="s4a2", seed=5),
     "sstream_idp_3x256": _c("FHADP", "pyth_idpendulum", 70, 8, W3, "gelu", 1.0, SS_FWD, wg=(1, 2), seed=5),
     # plain streamed fp32
@@ -320,13 +322,7 @@ def _grad_errors(got, want):
 
 def _padded(prep, extra):
     """The case's batch followed by `extra` rows of another seed, their observations (where the observation is the state) tripled."""
-    cfg, case = prep["cfg"], prep["case"]
-    tail = make_batch(dict(cfg, batch=extra), case["seed"] + 77)
-    if prep["env"]["kind"] == "veh":
-        tail["ref_appended"] = appended_points(cfg, tail)
-    else:
-        tail["obs"] = tail["obs"] * 3.0
-    return {k: torch.cat((v, tail[k])).contiguous() for k, v in prep["data"].items()}
+    return padded_batch(prep["cfg"], prep["case"]["seed"], prep["env"], prep["data"], extra)
 
 
 @pytest.fixture(scope="module")
