@@ -185,7 +185,7 @@ class PrecisionGuard:
     @staticmethod
     def applies_to(*modules, env_kind=None) -> bool:
         """Is there anything to guard?  Plane-split kernels exist for networks whose hidden layers are all 256 wide
-        (csrc/rollout_fwd.hip: split_eligible / ss_shape_ok) - narrower nets run exact fp32 products anyway -, and two gradient
+        (csrc/rollout_fwd.hip: split_ok / streamed_split_ok) - narrower nets run exact fp32 products anyway -, and two gradient
         evaluations of the same batch are only comparable when the model is deterministic (pyth_mobilerobot draws its obstacle
         noise per rollout)."""
         from gops_amd import hip_backend as hb

@@ -10,19 +10,8 @@
 #include <vector>
 
 #include "common.h"
+#include "rollout_choice.h"
 
-hipError_t launch_rollout_fwd(const RolloutParams& p, const RolloutParams* dp, hipStream_t stream);
-hipError_t launch_rollout_bwd(const RolloutParams& p, const RolloutParams* dp, const BwdPatch& q, hipStream_t stream);
-size_t rollout_fwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, int split_k0, bool ss = false);
-size_t rollout_bwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, bool split, bool ssb = false);
-bool split_eligible(const RolloutParams& p);
-bool h64_fuses_dw0(const RolloutParams& p);   // rollout_h64.hip
-int h64_sweep_grid(const RolloutParams& p);
-int split_grid_limit();
-int ssb_grid_limit();     // rollout_bwd.hip
-bool ssb_fuses_out(const RolloutParams& p);
-void rollout_variant(const RolloutParams& p, int sk[2], bool backward);
-bool h64_eligible(const RolloutParams& p);   // rollout_h64.hip
 hipError_t launch_upload_params(const RolloutParams& p, RolloutParams* dst, hipStream_t s);
 hipError_t launch_prologue(const RolloutParams& p, RolloutParams* dst, int P, float pdt, hipStream_t s);
 hipError_t launch_dw_gemm(const float* D, int N, const float* X, int Kp, long long S, int splits,
@@ -48,9 +37,6 @@ int poly_value_backward(const GopsMlp& v, int B, const float* obs, const float* 
                         hipStream_t s);
 hipError_t launch_env_step(const GopsEnv& env, int B, const GopsStepIO& io, float pdt, hipStream_t s);
 hipError_t launch_env_constraint(const GopsEnv& env, int B, const GopsStepIO& io, hipStream_t s);
-bool ss_eligible(const RolloutParams& p);   // rollout_fwd.hip
-bool ss_tail_exact(const RolloutParams& p); // rollout_fwd.hip
-bool ssb_eligible(const RolloutParams& p);  // rollout_bwd.hip
 hipError_t launch_polyak(const GopsAdamTensors& T, float omt, float tau, hipStream_t s);
 hipError_t launch_batch_loss(const float* a, const float* b, int n, float gsc, float sc0, float* grad, float* stats, hipStream_t s);
 hipError_t launch_adam(const GopsAdamTensors& T, GopsAdamState* st, double beta1, double beta2, float eps,
@@ -206,6 +192,7 @@ void carve_packs(Carver& c, MlpDev& d, bool f16) {
 
 struct Plan {
     RolloutParams p;
+    RolloutChoice choice;                  // which kernels run (rollout_choice.h); p's variant fields are copies of it
     RolloutParams* dev_params = nullptr;   // device copy read by the rollout kernels
     float* dw_part[GOPS_MAX_LAYERS] = {};     // split-K partial slabs, one region per Linear layer
     float* dw_part_b[GOPS_MAX_LAYERS] = {};
@@ -291,20 +278,17 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     for (int j = 1; j < p.pol.nl; ++j) hmax = p.pol.dims[j] > hmax ? p.pol.dims[j] : hmax;
     if (p.tail)
         for (int j = 1; j < p.val.nl; ++j) hmax = p.val.dims[j] > hmax ? p.val.dims[j] : hmax;
-    // L2 warm-up of the sweep (rollout_bwd.hip warm_up): pays while a CU holds one tile (nothing else hides the HBM latency of
-    // the next step's stash rows); with more tiles than CUs the co-resident workgroups hide it, and the warm-up lines are
-    // evicted before their use - measured at cfg5 (4096 tiles): 3.8 GB fetched per sweep with it, 1.55 GB without, 1.39 -> 1.24 ms
-    p.touch_mode = ((p.B + TB - 1) / TB > split_grid_limit()) ? 0 : 2;
-    if (desc.l2_warmup > 0) p.touch_mode = desc.l2_warmup - 1;   // tuning knob
     p.ldx = kp0 + 4;
     p.ldh = hmax + 4;
     const bool veh = env_has_ref_table(e.kind);
-    const int ref_pts = veh ? e.pre_horizon + 1 + desc.horizon
-                                                          : (e.kind == GOPS_ENV_IDPENDULUM ? IDP_POINTS(false) : 0);
+    const int ref_pts = ref_points_in_lds(p, false);
     if (rollout_fwd_lds_bytes(p.ldx, p.ldh, ref_pts, f16, 0) > 160 * 1024 || rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_pts, f16, false) > 160 * 1024)
         return GOPS_ERR_UNSUPPORTED;
-    p.sp.on = split_eligible(p) ? 1 : 0;
-    p.h64 = h64_eligible(p) ? 1 : 0;   // half precision: 64-trajectory tiles (stash rows in 64-row tiles)
+    RolloutChoice& ch = plan.choice;
+    if (!choose_forward(p, ch)) return GOPS_ERR_UNSUPPORTED;
+    p.touch_mode = desc.l2_warmup > 0 ? desc.l2_warmup - 1 : ch.touch_mode;   // (tuning knob)
+    p.sp.on = ch.split, p.h64 = ch.h64, p.ss = ch.ss, p.ssb = ch.ssb, p.tail_fp32 = ch.tail_fp32;
+    p.narrow = ch.narrow, p.narrow_floats = ch.narrow_floats, p.narrow_off_fwd = ch.narrow_off_fwd, p.narrow_off_bwd = ch.narrow_off_bwd;
     const int tile_rows = p.h64 ? 64 : TB;
     for (int t = 0; t <= p.H; ++t) p.gpow[t] = (float)pow(desc.gamma, (double)t);
 
@@ -337,8 +321,6 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
         sp.invt[1] = c.take(n1 >> 4);
         sp.invt[0] = c.take(p.pol.kp[0] >> 4);
     }
-    p.ss = (!p.sp.on && ss_eligible(p)) ? 1 : 0;
-    p.tail_fp32 = (p.ss && ss_tail_exact(p)) ? 1 : 0;
     if (p.ss) {   // streamed-split forward: planes of every hidden layer of the policy (and of the tail value net)
         for (int m = 0; m < (p.tail ? 2 : 1); ++m) {
             const MlpDev& d = m ? p.val : p.pol;
@@ -353,7 +335,6 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
         }
     }
     // the sweep of the same launch on the streamed-split kernel too: transposed planes (n-tiles over a layer's inputs)
-    p.ssb = (p.need_grad && ssb_eligible(p)) ? 1 : 0;
     if (p.ssb) {
         for (int m = 0; m < (p.tail ? 2 : 1); ++m) {
             const MlpDev& d = m ? p.val : p.pol;
@@ -366,26 +347,6 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
                 sn.r[j] = reinterpret_cast<const f16x8*>(c.take((elems + 1) / 2));
                 sn.inv[j] = c.take(nin >> 4);
             }
-        }
-    }
-    // narrow nets on the plain streamed fp32 kernels (neither plane-split nor register-stationary nor half): the policy's packed
-    // hidden-layer weights live in LDS for the whole launch (common.h gemm_layer_lds) - the shapes of the reference's example scripts
-    p.narrow = 0;
-    if (!f16 && !p.sp.on && !p.ss && !p.ssb && !p.h64 && !p.open_loop && !(p.vflags & GOPS_VF_NO_NARROW_LDS)) {
-        int skf[2], skb[2], nf = 0;
-        rollout_variant(p, skf, false);
-        rollout_variant(p, skb, true);
-        for (int j = 0; j < p.pol.nl - 1; ++j) nf += p.pol.kp[j] * p.pol.dims[j + 1];
-        const size_t lf = (rollout_fwd_lds_bytes(p.ldx, p.ldh, veh ? ref_pts : 0, false, 0) + 15) & ~(size_t)15;
-        const size_t lb = (rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_pts, false, false) + 15) & ~(size_t)15;
-        if (skf[0] == 0 && skf[1] == 0 && skb[0] == 0 && skb[1] == 0 && nf > 0 && nf <= NARROW_MAX_FLOATS && (nf & 3) == 0 &&
-            std::max(lf, lb) + 4 * (size_t)nf <= 52 * 1024) {   // three workgroups per CU stay resident
-            p.narrow = 1;
-            // obs -> 64 -> 64 -> act (<= 64 padded inputs): the kernels' form with these shapes as compile-time constants
-            if (p.pol.nl == 3 && p.pol.dims[1] == 64 && p.pol.dims[2] == 64 && p.pol.kp[0] <= 64 && !(p.vflags & GOPS_VF_NO_NARROW_N64)) p.narrow = 2;
-            p.narrow_floats = nf;
-            p.narrow_off_fwd = (int)(lf / 4);
-            p.narrow_off_bwd = (int)(lb / 4);
         }
     }
     p.gscale = c.take(8);   // [4 ..]: the fused Adam step's scalar factors (adam_snapshot); [0 .. 1]: max|grad_v| / max|delta_y| of a backward launch (f16 sweep scale; delta scale of the weight-gradient GEMM)
@@ -406,17 +367,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
         }
         p.st.dy = c.take((size_t)S * 4);
         p.st.env = c.take((size_t)S * ENV_STASH);
-        if (e.kind == GOPS_ENV_IDPENDULUM && e.repeat_num <= 1) {
-            // the sub-step parking of the forward: read by the plane-split stationary sweep and by the sweeps that stage nothing
-            // else (streamed fp32 - also its EXT form -, streamed-split); the exact-fp32 stationary sweep and the half kernels recompute
-            bool park = p.sp.on != 0;
-            if (!park && !f16) {
-                int sk[2];
-                rollout_variant(p, sk, true);
-                park = p.ssb || sk[1] == 0;
-            }
-            if (park) p.st.idp = c.take((size_t)S * IDP_PARK);
-        }
+        if (ch.idp_parking) p.st.idp = c.take((size_t)S * IDP_PARK);
         if (p.tail) {
             for (int j = 1; j < p.val.nl; ++j) {
                 const size_t rows = (size_t)((p.B + tile_rows - 1) / tile_rows) * tile_rows;   // whole tiles (FM stash tiles are written whole)
@@ -431,7 +382,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
             const int Kp = f16 ? p.pol.kp32[j] : p.pol.kp[j];
             const DwPlan d = plan_dw(p.pol.dims[j + 1], Kp, S, f16, p.dw_wgs);
             size_t nw = (size_t)d.splits * p.pol.dims[j + 1] * Kp, nb = (size_t)d.splits * p.pol.dims[j + 1];
-            if (j == 0 && h64_fuses_dw0(p)) {   // one slab [256][8] / [256] per workgroup of the 64-row sweep instead (rollout_h64.hip)
+            if (j == 0 && ch.fuse_dw0) {   // one slab [256][8] / [256] per workgroup of the 64-row sweep instead (rollout_h64.hip)
                 nw = std::max(nw, (size_t)h64_sweep_grid(p) * 256 * 8);
                 nb = std::max(nb, (size_t)h64_sweep_grid(p) * 256);
             }
@@ -445,6 +396,58 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     plan.bytes = c.off + kAlign;
     return GOPS_OK;
 }
+
+// The phase-counter tables of `make dbg` (tools/dbg_run.py), one per direction; nothing in the product library.
+#ifdef GOPS_DBG_BUILD
+void dbg_print_forward(const RolloutParams& p) {
+    if (p.dbg == nullptr) return;
+    unsigned long long h[16];
+    (void)hipMemcpy(h, p.dbg, sizeof(h), hipMemcpyDeviceToHost);
+    if (p.h64)
+        fprintf(stderr, "[gops dbg] fwd 64-row half cycles/step: top+sync %llu | convert+xstash+sync %llu | L0 gemm %llu epi %llu sync %llu | "
+                "L1 gemm %llu epi %llu sync %llu | head %llu sync %llu | env %llu\n",
+                h[0] / p.H, h[1] / p.H, h[2] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, h[7] / p.H, h[8] / p.H, h[9] / p.H, h[10] / p.H);
+    else if (p.ss)   // (grid-stride launches: the counters add up over the tiles block 0 walked)
+        fprintf(stderr, "[gops dbg] fwd streamed-split cycles/step (x tiles of block 0): top+sync %llu | planes of X+sync %llu | L0 gemm %llu | "
+                "epilogues %llu | plane store+sync %llu | L1.. gemm %llu sync %llu | head partials+combine %llu | tanh+wrap %llu sync %llu | "
+                "envstash %llu | env %llu\n", h[0] / p.H, h[1] / p.H, h[14] / p.H, h[8] / p.H, h[12] / p.H, h[11] / p.H, h[9] / p.H, h[2] / p.H,
+                h[7] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H);
+    else if (p.sp.on)
+        fprintf(stderr, "[gops dbg] fwd SPLIT cycles/step: top+sync %llu | xstash+convert+sync %llu | gemm0 %llu | epi0+planes %llu | sync %llu | "
+                "gemm1 %llu | epi1+head fma %llu | head reduce %llu | sync+combine %llu | tanh+wrap %llu | sync %llu | envstash %llu | env %llu || sum %llu\n",
+                h[0] / p.H, h[1] / p.H, h[14] / p.H, h[8] / p.H, h[9] / p.H, h[11] / p.H, h[12] / p.H, h[2] / p.H, h[6] / p.H, h[7] / p.H,
+                h[3] / p.H, h[4] / p.H, h[5] / p.H,
+                (h[0] + h[1] + h[14] + h[8] + h[9] + h[11] + h[12] + h[2] + h[6] + h[7] + h[3] + h[4] + h[5]) / p.H);
+    if (p.sp.on) fprintf(stderr, "[gops dbg] fwd SPLIT per launch (cycles of block 0): kernel entry -> first step %llu | behind the last step %llu\n", h[13], h[15]);
+    else
+    fprintf(stderr, "[gops dbg] fwd cycles/step: top+sync %llu | xstash %llu | hidden-rest %llu | head %llu | envstash %llu | env %llu"
+            " || L0 epi %llu sync %llu stash %llu | L1 epi %llu sync %llu stash %llu | gemm(L0+L1) %llu || head: dot %llu tanh+wrap %llu barrier %llu\n",
+            h[0] / p.H, h[1] / p.H, h[2] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[8] / p.H, h[9] / p.H,
+            h[10] / p.H, h[11] / p.H, h[12] / p.H, h[13] / p.H, h[14] / p.H, h[6] / p.H, h[7] / p.H, h[3] / p.H);
+}
+void dbg_print_backward(const RolloutParams& p) {
+    if (p.dbg == nullptr) return;
+    unsigned long long h[16];
+    (void)hipMemcpy(h, p.dbg, sizeof(h), hipMemcpyDeviceToHost);
+    if (p.h64)
+        fprintf(stderr, "[gops dbg] bwd 64-row half cycles/step: env adjoint %llu sync %llu | head %llu sync %llu | gemm %llu sync %llu epi %llu sync %llu | "
+                "g_x %llu | end sync %llu\n", h[0] / p.H, h[1] / p.H, h[2] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, h[7] / p.H, h[8] / p.H,
+                h[9] / p.H);
+    else if (p.sp.on)
+        fprintf(stderr, "[gops dbg] bwd SPLIT cycles/step: top %llu | env points %llu | reduce+sync %llu | env finish+sync %llu | head delta+planes %llu | "
+                "sync %llu | hook %llu | gemm1+epi+planes %llu | sync %llu | gemm0+G %llu | end sync %llu || sum %llu\n",
+                h[0] / p.H, h[10] / p.H, h[11] / p.H, h[1] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, (h[7] + h[8]) / p.H, h[9] / p.H,
+                h[2] / p.H, (h[0] + h[10] + h[11] + h[1] + h[3] + h[4] + h[5] + h[6] + h[7] + h[8] + h[9] + h[2]) / p.H);
+    else
+    fprintf(stderr, "[gops dbg] bwd cycles/step: touch %llu | env(points %llu, reduce+sync %llu, finish %llu) | head-bwd %llu sync %llu stash %llu | "
+            "gemm1+epi %llu sync %llu stash %llu | gemm0+epi %llu | end sync %llu\n",
+            h[0] / p.H, h[10] / p.H, h[11] / p.H, h[1] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, h[7] / p.H,
+            h[8] / p.H, h[9] / p.H, h[2] / p.H);
+}
+#else
+inline void dbg_print_forward(const RolloutParams&) {}
+inline void dbg_print_backward(const RolloutParams&) {}
+#endif
 
 float pdt_of(const GopsEnv& e) { return (float)((double)e.pre_horizon * 0.1); }
 
@@ -467,40 +470,15 @@ int run_forward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const Gops
         if (me != hipSuccess) return (int)me;
     }
     p.dbg = dbg_timing_buffer(0);
-    const bool dbg = p.dbg != nullptr;
     // parameter block upload + weight packing + reference table: one launch
     hipError_t ue = launch_prologue(p, plan.dev_params, desc.env.pre_horizon, pdt_of(desc.env), s);
     if (ue != hipSuccess) return (int)ue;
     int ret;
     {
         ProfScope scope(desc.env.kind == GOPS_ENV_NONE ? 3 : 0, s);
-        ret = (int)launch_rollout_fwd(p, plan.dev_params, s);
+        ret = (int)launch_rollout_fwd(p, plan.choice.fwd, plan.dev_params, s);
     }
-    if (dbg) {
-        unsigned long long h[16];
-        (void)hipMemcpy(h, p.dbg, sizeof(h), hipMemcpyDeviceToHost);
-        if (p.h64)
-            fprintf(stderr, "[gops dbg] fwd 64-row half cycles/step: top+sync %llu | convert+xstash+sync %llu | L0 gemm %llu epi %llu sync %llu | "
-                    "L1 gemm %llu epi %llu sync %llu | head %llu sync %llu | env %llu\n",
-                    h[0] / p.H, h[1] / p.H, h[2] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, h[7] / p.H, h[8] / p.H, h[9] / p.H, h[10] / p.H);
-        else if (p.ss)   // (grid-stride launches: the counters add up over the tiles block 0 walked)
-            fprintf(stderr, "[gops dbg] fwd streamed-split cycles/step (x tiles of block 0): top+sync %llu | planes of X+sync %llu | L0 gemm %llu | "
-                    "epilogues %llu | plane store+sync %llu | L1.. gemm %llu sync %llu | head partials+combine %llu | tanh+wrap %llu sync %llu | "
-                    "envstash %llu | env %llu\n", h[0] / p.H, h[1] / p.H, h[14] / p.H, h[8] / p.H, h[12] / p.H, h[11] / p.H, h[9] / p.H, h[2] / p.H,
-                    h[7] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H);
-        else if (p.sp.on)
-            fprintf(stderr, "[gops dbg] fwd SPLIT cycles/step: top+sync %llu | xstash+convert+sync %llu | gemm0 %llu | epi0+planes %llu | sync %llu | "
-                    "gemm1 %llu | epi1+head fma %llu | head reduce %llu | sync+combine %llu | tanh+wrap %llu | sync %llu | envstash %llu | env %llu || sum %llu\n",
-                    h[0] / p.H, h[1] / p.H, h[14] / p.H, h[8] / p.H, h[9] / p.H, h[11] / p.H, h[12] / p.H, h[2] / p.H, h[6] / p.H, h[7] / p.H,
-                    h[3] / p.H, h[4] / p.H, h[5] / p.H,
-                    (h[0] + h[1] + h[14] + h[8] + h[9] + h[11] + h[12] + h[2] + h[6] + h[7] + h[3] + h[4] + h[5]) / p.H);
-        if (p.sp.on) fprintf(stderr, "[gops dbg] fwd SPLIT per launch (cycles of block 0): kernel entry -> first step %llu | behind the last step %llu\n", h[13], h[15]);
-        else
-        fprintf(stderr, "[gops dbg] fwd cycles/step: top+sync %llu | xstash %llu | hidden-rest %llu | head %llu | envstash %llu | env %llu"
-                " || L0 epi %llu sync %llu stash %llu | L1 epi %llu sync %llu stash %llu | gemm(L0+L1) %llu || head: dot %llu tanh+wrap %llu barrier %llu\n",
-                h[0] / p.H, h[1] / p.H, h[2] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[8] / p.H, h[9] / p.H,
-                h[10] / p.H, h[11] / p.H, h[12] / p.H, h[13] / p.H, h[14] / p.H, h[6] / p.H, h[7] / p.H, h[3] / p.H);
-    }
+    dbg_print_forward(p);
     return ret;
 }
 
@@ -556,32 +534,28 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
         }
     }
     hipError_t e;
-    if (desc.env.repeat_num > 1) p.ext = 1;   // ActionRepeatModel: the general (EXT) instantiations of the sweep
-    if (adj != nullptr) {   // gops_rollout_backward_adj / gops_mlp_backward_x: the EXT kernels
-        const int k = desc.env.kind;
-        if (p.tail || p.f16) return GOPS_ERR_UNSUPPORTED;   // (open loop: gops_rollout_backward_open_loop_adj)
-        if (k != GOPS_ENV_NONE && k != GOPS_ENV_LQ && k != GOPS_ENV_IDPENDULUM && k != GOPS_ENV_CARTPOLE && k != GOPS_ENV_PENDULUM &&
-            k != GOPS_ENV_MOBILEROBOT)
-            return GOPS_ERR_UNSUPPORTED;
-        p.ext = 1;
+    // ActionRepeatModel, gops_rollout_backward_adj / gops_mlp_backward_x: the general (EXT) instantiations of the sweep
+    const SweepCall call{desc.env.repeat_num > 1 || adj != nullptr, ext_delta != nullptr, want_params};
+    if (adj != nullptr && (p.tail || p.f16)) return GOPS_ERR_UNSUPPORTED;   // (open loop: gops_rollout_backward_open_loop_adj)
+    KernelChoice& sweep = plan.choice.bwd;
+    if (!choose_sweep(p, plan.choice, call, sweep)) return GOPS_ERR_UNSUPPORTED;
+    p.ext = call.ext;
+    if (adj != nullptr) {
         p.adj_gfo = adj->grad_final_obs;
         p.adj_gobs = adj->grad_obs;
         p.adj_first_only = (adj->first_step_only != 0 && p.H > 1) ? 1 : 0;
         if (p.adj_first_only && want_params) {   // the sweep writes the step-0 deltas only: the rest of the stash is zero
-            const size_t S0 = (size_t)((p.B + TB - 1) / TB) * TB * p.H;
+            const size_t S0 = (size_t)tiles(p) * TB * p.H;
             for (int j = 1; j < p.pol.nl; ++j)
                 if ((e = launch_fill_zero(p.st.d[j], S0 * p.pol.dims[j], s)) != hipSuccess) return (int)e;
             if ((e = launch_fill_zero(p.st.dy, S0 * 4, s)) != hipSuccess) return (int)e;
         }
     }
     p.dbg = dbg_timing_buffer(1);
-    const bool dbg = p.dbg != nullptr;
     // Split sweep: the output layer's weight gradient is accumulated inside the sweep (one partial per workgroup) - no dw_out
     // pass.  (GELU: the sweep's act' operand is gelu'(z), so it fetches H_2 next to it.)
-    // (the streamed-split sweep does the same for the env kinds whose instantiation has the registers: ssb_fuses_out)
-    const bool fused_out = (p.sp.on || ssb_fuses_out(p)) && !p.ext && !p.open_loop && want_params &&
-                           ext_delta == nullptr;
-    const int sweep_grid = std::min((p.B + TB - 1) / TB, p.sp.on ? split_grid_limit() : ssb_grid_limit());
+    // (the streamed-split sweep does the same for the env kinds whose instantiation has the registers: ssb_fuse_kind)
+    const bool fused_out = sweep_fuses_out(sweep, call);
     if (fused_out) {
         p.sp.out_part = plan.dw_part[p.pol.nl - 1];
         p.sp.out_part_b = plan.dw_part_b[p.pol.nl - 1];
@@ -600,7 +574,7 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
     q.out_part = p.sp.out_part;
     q.out_part_b = p.sp.out_part_b;
     q.dbg = p.dbg;
-    const bool fuse_dw0 = h64_fuses_dw0(p) && want_params && ext_delta == nullptr && adj == nullptr &&
+    const bool fuse_dw0 = plan.choice.fuse_dw0 && want_params && ext_delta == nullptr && adj == nullptr &&
                           !(p.vflags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B));
     if (fuse_dw0) {
         q.w0_part = plan.dw_part[0];
@@ -625,27 +599,10 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
     if (p.f16 && (e = launch_upload_params(p, plan.dev_params, s)) != hipSuccess) return (int)e;
     {
         ProfScope scope(desc.env.kind == GOPS_ENV_NONE ? 4 : 1, s);
-        if ((e = launch_rollout_bwd(p, plan.dev_params, q, s)) != hipSuccess) return (int)e;
+        if ((e = launch_rollout_bwd(p, sweep, plan.dev_params, q, s)) != hipSuccess) return (int)e;
     }
     }   // !only_b
-    if (dbg) {
-        unsigned long long h[16];
-        (void)hipMemcpy(h, p.dbg, sizeof(h), hipMemcpyDeviceToHost);
-        if (p.h64)
-            fprintf(stderr, "[gops dbg] bwd 64-row half cycles/step: env adjoint %llu sync %llu | head %llu sync %llu | gemm %llu sync %llu epi %llu sync %llu | "
-                    "g_x %llu | end sync %llu\n", h[0] / p.H, h[1] / p.H, h[2] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, h[7] / p.H, h[8] / p.H,
-                    h[9] / p.H);
-        else if (p.sp.on)
-            fprintf(stderr, "[gops dbg] bwd SPLIT cycles/step: top %llu | env points %llu | reduce+sync %llu | env finish+sync %llu | head delta+planes %llu | "
-                    "sync %llu | hook %llu | gemm1+epi+planes %llu | sync %llu | gemm0+G %llu | end sync %llu || sum %llu\n",
-                    h[0] / p.H, h[10] / p.H, h[11] / p.H, h[1] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, (h[7] + h[8]) / p.H, h[9] / p.H,
-                    h[2] / p.H, (h[0] + h[10] + h[11] + h[1] + h[3] + h[4] + h[5] + h[6] + h[7] + h[8] + h[9] + h[2]) / p.H);
-        else
-        fprintf(stderr, "[gops dbg] bwd cycles/step: touch %llu | env(points %llu, reduce+sync %llu, finish %llu) | head-bwd %llu sync %llu stash %llu | "
-                "gemm1+epi %llu sync %llu stash %llu | gemm0+epi %llu | end sync %llu\n",
-                h[0] / p.H, h[10] / p.H, h[11] / p.H, h[1] / p.H, h[3] / p.H, h[4] / p.H, h[5] / p.H, h[6] / p.H, h[7] / p.H,
-                h[8] / p.H, h[9] / p.H, h[2] / p.H);
-    }
+    dbg_print_backward(p);
     if (p.open_loop || !want_params)   // no parameters behind the rollout / none wanted: no reduce - gscale is reset here
         return (int)launch_fill_zero(p.gscale, 4, s);
     ProfScope scope(desc.env.kind == GOPS_ENV_NONE ? 5 : 2, s);
@@ -685,7 +642,7 @@ int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const flo
     }
     if (ext_delta == nullptr && !only_b) {
         const int K = p.pol.dims[L], A = p.pol.dims[p.pol.nl];
-        long long splits = fused_out ? sweep_grid : DW_OUT_SPLITS;
+        long long splits = fused_out ? sweep.grid : DW_OUT_SPLITS;   // (one slab per workgroup of the sweep)
         if (splits > S) splits = S;
         if (!fused_out)
         if ((e = launch_dw_out(p.st.dy, p.st.h[L], p.f16 != 0, K, A, S, (int)splits, plan.dw_part[L], plan.dw_part_b[L], s)) != hipSuccess) return (int)e;
@@ -911,12 +868,13 @@ int gops_rollout_variant(const GopsRolloutDesc* desc) {
     Plan plan;
     const int rc = build_plan(*desc, nullptr, plan);
     if (rc != GOPS_OK) return rc;
-    if (plan.p.sp.on) return GOPS_VARIANT_SPLIT;
-    if (plan.p.ss) return GOPS_VARIANT_STREAMED_SPLIT_FWD;
-    if (plan.p.h64) return GOPS_VARIANT_HALF_TILE64;
-    int sk[2];
-    rollout_variant(plan.p, sk, false);
-    return sk[1] > 0 ? GOPS_VARIANT_STATIONARY_F32 : 0;
+    switch (plan.choice.fwd.family) {
+        case Family::Split: return GOPS_VARIANT_SPLIT;
+        case Family::StreamedSplit: return GOPS_VARIANT_STREAMED_SPLIT_FWD;
+        case Family::Half64: return GOPS_VARIANT_HALF_TILE64;
+        case Family::Stationary: return GOPS_VARIANT_STATIONARY_F32;
+        default: return 0;
+    }
 }
 
 int gops_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const GopsRolloutOut* out,

@@ -11,6 +11,7 @@
 #include "env_models.h"
 constexpr bool SWEEP_STAGE_NT = true;   // the stash rows the sweep stages one step ahead are read once by this launch
 #include "rollout_f16.h"
+#include "rollout_choice.h"
 
 // LDS floats of the per-tile buffers (everything except the optional staged tiles at the end).
 // split: the plane-split sweep keeps the plane images of delta_2 / delta_1 where the fp32 delta tiles would be (the
@@ -472,7 +473,6 @@ struct NoSweep {};
 __host__ __device__ constexpr bool ssb_fuse_kind(int env) {
     return env == GOPS_ENV_LQ || env == GOPS_ENV_CARTPOLE || env == GOPS_ENV_PENDULUM || env == GOPS_ENV_MOBILEROBOT;
 }
-bool ssb_fuses_out(const RolloutParams& p) { return p.ssb && ssb_fuse_kind(p.env.kind); }
 // Output-layer weight gradient accumulated inside the streamed-split sweep (as SplitSweep does): lane (f = lane & 15,
 // g = lane >> 4) of wave w holds dW_o[a][64 w + 16 q + f] over the rows 4g .. 4g+3 of every tile and step the workgroup walked.
 struct SsOutGrad {
@@ -1714,176 +1714,121 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
 
 // ref_points: reference-table points per trajectory (veh3dofconti), 30 (= 5 x 24 / 4) for the
 // idpendulum sub-step parking area, else 0
-size_t rollout_bwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, bool split, bool ssb = false) {
+size_t rollout_bwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, bool split, bool ssb) {
     size_t b = sizeof(float) * (size_t)bwd_lds_floats(ldx, ldh, ref_points, f16, split, ssb);
     if (split) b += sizeof(float) * 2 * (TB * ENV_STASH + TB * 8) +
                     (ldx - 4 > 128 ? 0 : (size_t)((ldx - 4) >> 4) * 8 * 1024);   // small staging halves + W_0's residual plane (streamed beyond 128 inputs)
     return b;
 }
-
-void rollout_variant(const RolloutParams& p, int sk[2], bool backward);
-int split_grid_limit();   // rollout_fwd.hip: CUs of the device
-int ssb_grid_limit() { return 2 * split_grid_limit(); }   // workgroups of the streamed-split sweep (= slabs of its fused output-layer gradient)
-
-// The sweep of a streamed-split forward launch (p.ss) on the streamed-split sweep as well: same conditions, its LDS image at
-// two workgroups per CU.  GOPS_VF_NO_STREAMED_SPLIT_BWD keeps the fp32-MFMA sweep.
-bool ssb_eligible(const RolloutParams& p) {
-    if (!p.ss) return false;
-    if (p.vflags & GOPS_VF_NO_STREAMED_SPLIT_BWD) return false;
-    const int ref_pts = env_has_ref_table(p.env.kind) ? p.env.pre_horizon + 1 + p.H : (p.env.kind == GOPS_ENV_IDPENDULUM ? IDP_POINTS(false) : 0);
-    return rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_pts, false, false, true) + (env_in_lds(p.env.kind, true) ? 4 * ENV_LDS_FLOATS : 0) <= 80 * 1024;
+int ssb_grid_limit() { return 2 * device_cus(); }   // workgroups of the streamed-split sweep (= slabs of its fused output-layer gradient)
+size_t split_bwd_lds_bytes(const RolloutParams& p) { return rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_points_in_lds(p, true), false, true); }
+size_t ssb_lds_bytes(const RolloutParams& p) {
+    return rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_points_in_lds(p, false), false, false, true) + (env_in_lds(p.env.kind, true) ? 4 * ENV_LDS_FLOATS : 0);
 }
 
-#define LAUNCH_BWD(ENV, A, B)                                                                            \
-    do {                                                                                                 \
-        if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, A, B, true>, grid, block, lds, stream, dp, q);   \
-        else launch_with_lds(rollout_bwd_kernel<ENV, A, B, false>, grid, block, lds, stream, dp, q);         \
-    } while (0)
-// the plain streamed fp32 sweep, or its obs -> 64 -> 64 -> act form (RolloutParams.narrow == 2: mlp_backward_n64)
-#define LAUNCH_BWD_PLAIN(ENV)                                                                                                                       \
-    do {                                                                                                                                            \
-        if (p.narrow == 2 && q.ext_delta == nullptr) {   /* (gops_mlp_backward with a wide output layer: the generic head) */                       \
-            if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, true, 1, false, false, false, false, false, true>, grid, block, lds, stream, dp, q);  \
-            else launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, false, 1, false, false, false, false, false, true>, grid, block, lds, stream, dp, q);        \
-        } else LAUNCH_BWD(ENV, 0, 0);                                                                                                               \
-    } while (0)
+// Family::Stationary sweep (stationary_shape: rollout_fwd.hip).  The sweep's VALU phases need more than the 128 VGPRs left
+// beside 384 weight registers: it keeps only the 256-register layer-1 fragments (all in AGPRs) and streams layer 0 but for the
+// s0 chunks of kStationaryBwd.  It also stages this step's H_2 / H_1 tiles in LDS: exactly two hidden layers.
+bool stationary_bwd_shape(const RolloutParams& p, int& s0) {
+    if (!stationary_shape(p) || p.pol.nl != 3) return false;
+    s0 = p.pol.kp[0] == 128 ? 12 : (p.pol.kp[0] == 16 ? 16 : 0);
+    return has_inst(kStationaryBwd, p.env.kind, s0, 16, p.tail != 0);
+}
 
-#define LAUNCH_BWD_H(ENV)                                                                                       \
-    do {                                                                                                        \
-        if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, true, 1, true>, grid, block, lds, stream, dp, q); \
-        else launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, false, 1, true>, grid, block, lds, stream, dp, q);       \
-    } while (0)
+bool choose_sweep(const RolloutParams& p, const RolloutChoice& c, const SweepCall& call, KernelChoice& k) {
+    const int kind = p.env.kind, nt = tiles(p);
+    k = {Family::None, kind, 0, 0, p.tail != 0, false, nt,
+         c.narrow ? 4 * ((size_t)c.narrow_off_bwd + c.narrow_floats) : rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_points_in_lds(p, false), p.f16 != 0, false)};
+    int s0 = 0;
+    if (c.h64) {
+        k.family = Family::Half64;
+        k.grid = h64_sweep_grid(p);
+        k.lds = rollout_bwd_h64_lds_bytes(p.ldx, p.ldh);
+    } else if (call.ext) {   // adjoint I/O / ActionRepeat: streamed fp32 kernels of the obs == state kinds
+        k.family = Family::General;
+        return !p.f16 && has_inst(kExtBwd, kind, 0, 0, k.tail);
+    } else if (c.ssb && !p.open_loop && !call.ext_delta) {   // (gops_mlp_backward's hidden-stack deltas: the fp32 sweep)
+        k.family = Family::StreamedSplit;
+        k.multi = ssb_fuse_kind(kind);   // two workgroups per CU walk the tiles grid-stride
+        if (k.multi) k.grid = std::min(nt, ssb_grid_limit());
+        k.lds = ssb_lds_bytes(p);
+    } else if (c.split) {   // one workgroup per CU, grid-stride over the tiles
+        k.family = Family::Split;
+        k.s0 = p.pol.kp32[0] >> 5;
+        k.multi = nt > device_cus();
+        k.grid = std::min(nt, device_cus());
+        k.lds = split_bwd_lds_bytes(p);
+    } else if (p.f16) {
+        k.family = Family::Half16;
+        return has_inst(kHalf16, kind, 0, 0, k.tail);
+    } else if (stationary_bwd_shape(p, s0)) {
+        k.family = Family::Stationary;
+        k.s0 = s0;
+        k.s1 = 16;
+        k.lds += sizeof(float) * 2 * (2 * TB * 256 + TB * ENV_STASH + TB * 8);   // two staging halves
+    } else {   // (gops_mlp_backward with a wide output layer: the generic head)
+        k.family = (c.narrow == 2 && !call.ext_delta) ? Family::PlainN64 : Family::Plain;
+        return has_inst(kPlain, kind, 0, 0, k.tail);
+    }
+    return true;
+}
 
-#define LAUNCH_BWD2(ENV, A, B, PT)                                                                          \
-    do {                                                                                                    \
-        if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, A, B, true, PT>, grid, block, lds, stream, dp, q);  \
-        else launch_with_lds(rollout_bwd_kernel<ENV, A, B, false, PT>, grid, block, lds, stream, dp, q);        \
-    } while (0)
+// rollout_bwd_kernel's template arguments by name
+struct BwdCfg {
+    int env, sk0 = 0, sk1 = 0;
+    bool tail = false;
+    int pt0 = 1;
+    bool f16 = false, ext = false, split = false, multi = false, ssb = false, n64 = false;
+};
+template <BwdCfg C>
+static void launch_bwd(const KernelChoice& k, const RolloutParams* dp, const BwdPatch& q, hipStream_t stream) {
+    launch_with_lds(rollout_bwd_kernel<C.env, C.sk0, C.sk1, C.tail, C.pt0, C.f16, C.ext, C.split, C.multi, C.ssb, C.n64>, dim3(k.grid), dim3(NTHREADS),
+                    k.lds, stream, dp, q);
+}
 
-hipError_t launch_rollout_bwd_h64(const RolloutParams& p, const RolloutParams* dp, const BwdPatch& q, hipStream_t stream);   // rollout_h64.hip
-hipError_t launch_rollout_bwd(const RolloutParams& p, const RolloutParams* dp, const BwdPatch& q, hipStream_t stream) {
-#ifdef GOPS_ONLY_NARROW   // the same for the plain streamed fp32 kernel of pyth_idpendulum (cfg1, the example scripts' shapes): EXTRA=-DGOPS_ONLY_NARROW
-#if GOPS_ONLY_NARROW == 2
-    launch_with_lds(rollout_bwd_kernel<GOPS_ENV_IDPENDULUM, 0, 0, false, 1, false, false, false, false, false, true>, dim3((p.B + TB - 1) / TB), dim3(NTHREADS), 4 * ((size_t)p.narrow_off_bwd + p.narrow_floats), stream, dp, q);
+hipError_t launch_rollout_bwd(const RolloutParams& p, const KernelChoice& k, const RolloutParams* dp, const BwdPatch& q, hipStream_t stream) {
+#ifdef GOPS_ONLY_NARROW   // register / spill studies (EXTRA=-DGOPS_ONLY_NARROW[=2] tools/kernel_regs.sh rollout_bwd.hip): ONE instantiation, seconds to compile - the plain streamed fp32 sweep of pyth_idpendulum (cfg1, the example scripts' shapes)
+    launch_bwd<BwdCfg{.env = GOPS_ENV_IDPENDULUM, .n64 = GOPS_ONLY_NARROW == 2}>(k, dp, q, stream);
+    return hipGetLastError();
+#elif defined(GOPS_ONLY_TARGET)   // ... EXTRA=-DGOPS_ONLY_TARGET: the headline launch's sweep
+    launch_bwd<BwdCfg{.env = GOPS_ENV_VEH3DOFCONTI, .sk0 = 8, .sk1 = 8, .pt0 = 2, .split = true}>(k, dp, q, stream);
+    return hipGetLastError();
 #else
-    launch_with_lds(rollout_bwd_kernel<GOPS_ENV_IDPENDULUM, 0, 0, false>, dim3((p.B + TB - 1) / TB), dim3(NTHREADS), 4 * ((size_t)p.narrow_off_bwd + p.narrow_floats), stream, dp, q);
-#endif
-    return hipGetLastError();
-#elif defined(GOPS_ONLY_TARGET)   // register / spill studies (EXTRA=-DGOPS_ONLY_TARGET tools/kernel_regs.sh rollout_bwd.hip): ONE instantiation, seconds to compile
-    launch_with_lds(rollout_bwd_kernel<GOPS_ENV_VEH3DOFCONTI, 8, 8, false, 2, false, false, true>, dim3(1), dim3(NTHREADS), 0, stream, dp, q);
-    return hipGetLastError();
-#else
-    if (p.h64) return launch_rollout_bwd_h64(p, dp, q, stream);   // half precision, 64-trajectory tiles
-    const dim3 grid((p.B + TB - 1) / TB), block(NTHREADS);
-    const int ref_pts = env_has_ref_table(p.env.kind) ? p.env.pre_horizon + 1 + p.H : (p.env.kind == GOPS_ENV_IDPENDULUM ? IDP_POINTS(false) : 0);
-    size_t lds = rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_pts, p.f16 != 0, false);
-    if (p.narrow) lds = 4 * ((size_t)p.narrow_off_bwd + p.narrow_floats);   // (api.hip: only ever set for the plain streamed fp32 sweeps, EXT included)
-    if (p.ext) {   // adjoint I/O / ActionRepeat: streamed fp32 kernels of the obs == state kinds
-        if (p.f16) return hipErrorInvalidValue;
-#define LAUNCH_BWD_EXT(ENV)                                                                                             \
-    do {                                                                                                                \
-        if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, true, 1, false, true>, grid, block, lds, stream, dp, q);  \
-        else launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, false, 1, false, true>, grid, block, lds, stream, dp, q);        \
-    } while (0)
-        switch (p.env.kind) {
-            case GOPS_ENV_NONE:
-                if (p.tail) return hipErrorInvalidValue;
-                launch_with_lds(rollout_bwd_kernel<GOPS_ENV_NONE, 0, 0, false, 1, false, true>, grid, block, lds, stream, dp, q);
-                break;
-            case GOPS_ENV_LQ: LAUNCH_BWD_EXT(GOPS_ENV_LQ); break;
-            case GOPS_ENV_IDPENDULUM: LAUNCH_BWD_EXT(GOPS_ENV_IDPENDULUM); break;
-            case GOPS_ENV_CARTPOLE: LAUNCH_BWD_EXT(GOPS_ENV_CARTPOLE); break;
-            case GOPS_ENV_PENDULUM: LAUNCH_BWD_EXT(GOPS_ENV_PENDULUM); break;
-            case GOPS_ENV_MOBILEROBOT: LAUNCH_BWD_EXT(GOPS_ENV_MOBILEROBOT); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (p.ssb && !p.ext && !p.open_loop && q.ext_delta == nullptr) {   // streamed-split sweep (gops_mlp_backward's hidden-stack deltas: the fp32 sweep)
-        const size_t lds_ss = rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_pts, false, false, true) + (env_in_lds(p.env.kind, true) ? 4 * ENV_LDS_FLOATS : 0);
-        const dim3 grid_ss(std::min<int>((p.B + TB - 1) / TB, ssb_grid_limit()));   // two workgroups per CU walk the tiles grid-stride
-#define LAUNCH_BWD_SS(ENV)                                                                                                                  \
-    do {                                                                                                                                    \
-        constexpr bool MT = ssb_fuse_kind(ENV);   /* grid-stride walk + fused output-layer gradient */                                        \
-        const dim3 g = MT ? grid_ss : grid;                                                                                                   \
-        if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, true, 1, false, false, false, MT, true>, g, block, lds_ss, stream, dp, q);   \
-        else launch_with_lds(rollout_bwd_kernel<ENV, 0, 0, false, 1, false, false, false, MT, true>, g, block, lds_ss, stream, dp, q);         \
-    } while (0)
-        switch (p.env.kind) {
-            case GOPS_ENV_NONE: LAUNCH_BWD_SS(GOPS_ENV_NONE); break;
-            case GOPS_ENV_LQ: LAUNCH_BWD_SS(GOPS_ENV_LQ); break;
-            case GOPS_ENV_IDPENDULUM: LAUNCH_BWD_SS(GOPS_ENV_IDPENDULUM); break;
-            case GOPS_ENV_VEH3DOFCONTI: LAUNCH_BWD_SS(GOPS_ENV_VEH3DOFCONTI); break;
-            case GOPS_ENV_VEH3DOF_SURR: LAUNCH_BWD_SS(GOPS_ENV_VEH3DOF_SURR); break;
-            case GOPS_ENV_CARTPOLE: LAUNCH_BWD_SS(GOPS_ENV_CARTPOLE); break;
-            case GOPS_ENV_PENDULUM: LAUNCH_BWD_SS(GOPS_ENV_PENDULUM); break;
-            case GOPS_ENV_VEH2DOF: LAUNCH_BWD_SS(GOPS_ENV_VEH2DOF); break;
-            case GOPS_ENV_MOBILEROBOT: LAUNCH_BWD_SS(GOPS_ENV_MOBILEROBOT); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (p.sp.on) {   // plane-split stationary sweep: PT0 = n-tiles of g_x per wave
-        lds = rollout_bwd_lds_bytes(p.ldx, p.ldh, p.env.kind == GOPS_ENV_IDPENDULUM ? IDP_POINTS(true) : ref_pts, false, true);
-#define LAUNCH_BWD_SPLIT(ENV, PT)                                                                                                  \
-    do {                                                                                                                          \
-        if (multi) {                                                                                                              \
-            if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, 8, 8, true, PT, false, false, true, true>, grid, block, lds, stream, dp, q);    \
-            else launch_with_lds(rollout_bwd_kernel<ENV, 8, 8, false, PT, false, false, true, true>, grid, block, lds, stream, dp, q);          \
-        } else if (p.tail) launch_with_lds(rollout_bwd_kernel<ENV, 8, 8, true, PT, false, false, true>, grid, block, lds, stream, dp, q);    \
-        else launch_with_lds(rollout_bwd_kernel<ENV, 8, 8, false, PT, false, false, true>, grid, block, lds, stream, dp, q);          \
-    } while (0)
-        const int pt = (p.pol.kp[0] + 63) >> 6;
-        const dim3 grid(std::min<int>((p.B + TB - 1) / TB, split_grid_limit()));   // one workgroup per CU, grid-stride over the tiles
-        const bool multi = (p.B + TB - 1) / TB > split_grid_limit();
-        if (p.env.kind == GOPS_ENV_LQ && pt == 1) LAUNCH_BWD_SPLIT(GOPS_ENV_LQ, 1);
-        else if (p.env.kind == GOPS_ENV_IDPENDULUM && pt == 1) LAUNCH_BWD_SPLIT(GOPS_ENV_IDPENDULUM, 1);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && pt == 1) LAUNCH_BWD_SPLIT(GOPS_ENV_VEH3DOFCONTI, 1);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && pt == 2) LAUNCH_BWD_SPLIT(GOPS_ENV_VEH3DOFCONTI, 2);
-#define LAUNCH_BWD_SPLIT_NOTAIL(ENV, PT)                                                                                          \
-    do {                                                                                                                          \
-        if (multi) launch_with_lds(rollout_bwd_kernel<ENV, 8, 8, false, PT, false, false, true, true>, grid, block, lds, stream, dp, q);  \
-        else launch_with_lds(rollout_bwd_kernel<ENV, 8, 8, false, PT, false, false, true>, grid, block, lds, stream, dp, q);       \
-    } while (0)
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && pt == 3 && !p.tail) LAUNCH_BWD_SPLIT_NOTAIL(GOPS_ENV_VEH3DOFCONTI, 3);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && pt == 4 && !p.tail) LAUNCH_BWD_SPLIT_NOTAIL(GOPS_ENV_VEH3DOFCONTI, 4);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    int sk[2];
-    rollout_variant(p, sk, true);
-    if (sk[1] > 0) lds += sizeof(float) * 2 * (2 * TB * 256 + TB * ENV_STASH + TB * 8);   // two staging halves
-    const int key = sk[0] * 100 + sk[1];
-    if (p.f16) {
-        switch (p.env.kind) {
-            case GOPS_ENV_NONE: LAUNCH_BWD_H(GOPS_ENV_NONE); break;
-            case GOPS_ENV_LQ: LAUNCH_BWD_H(GOPS_ENV_LQ); break;
-            case GOPS_ENV_IDPENDULUM: LAUNCH_BWD_H(GOPS_ENV_IDPENDULUM); break;
-            case GOPS_ENV_VEH3DOFCONTI: LAUNCH_BWD_H(GOPS_ENV_VEH3DOFCONTI); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (p.env.kind) {
-        case GOPS_ENV_NONE: LAUNCH_BWD_PLAIN(GOPS_ENV_NONE); break;
-        case GOPS_ENV_LQ:
-            if (key == 1616) LAUNCH_BWD(GOPS_ENV_LQ, 16, 16); else LAUNCH_BWD_PLAIN(GOPS_ENV_LQ);
+    bool found = false;
+    switch (k.family) {
+        case Family::Half64: return launch_rollout_bwd_h64(p, k, dp, q, stream);
+        case Family::General:
+            found = dispatch<kExtBwd>(k, [&]<Inst E, bool TAIL>() { launch_bwd<BwdCfg{.env = E.env, .tail = TAIL, .ext = true}>(k, dp, q, stream); });
             break;
-        case GOPS_ENV_IDPENDULUM:
-            if (key == 1616) LAUNCH_BWD(GOPS_ENV_IDPENDULUM, 16, 16); else LAUNCH_BWD_PLAIN(GOPS_ENV_IDPENDULUM);
+        case Family::StreamedSplit:   // (ssb_fuse_kind: grid-stride walk + fused output-layer gradient)
+            found = dispatch<kStreamedSplit>(k, [&]<Inst E, bool TAIL>() {
+                launch_bwd<BwdCfg{.env = E.env, .tail = TAIL, .multi = ssb_fuse_kind(E.env), .ssb = true}>(k, dp, q, stream);
+            });
             break;
-        case GOPS_ENV_VEH3DOFCONTI:
-            if (key == 1216) LAUNCH_BWD2(GOPS_ENV_VEH3DOFCONTI, 12, 16, 2);
-            else if (key == 16) LAUNCH_BWD(GOPS_ENV_VEH3DOFCONTI, 0, 16);
-            else LAUNCH_BWD_PLAIN(GOPS_ENV_VEH3DOFCONTI);
+        case Family::Split:   // PT0 = n-tiles of g_x per wave
+            found = dispatch<kSplit>(k, [&]<Inst E, bool TAIL>() {
+                dispatch_bool(k.multi, [&](auto multi) {
+                    launch_bwd<BwdCfg{.env = E.env, .sk0 = 8, .sk1 = 8, .tail = TAIL, .pt0 = (E.s0 + 1) / 2, .split = true, .multi = decltype(multi)::value}>(
+                        k, dp, q, stream);
+                });
+            });
             break;
-        case GOPS_ENV_VEH3DOF_SURR: LAUNCH_BWD_PLAIN(GOPS_ENV_VEH3DOF_SURR); break;
-        case GOPS_ENV_CARTPOLE: LAUNCH_BWD_PLAIN(GOPS_ENV_CARTPOLE); break;
-        case GOPS_ENV_PENDULUM: LAUNCH_BWD_PLAIN(GOPS_ENV_PENDULUM); break;
-        case GOPS_ENV_VEH2DOF: LAUNCH_BWD_PLAIN(GOPS_ENV_VEH2DOF); break;
-        case GOPS_ENV_MOBILEROBOT: LAUNCH_BWD_PLAIN(GOPS_ENV_MOBILEROBOT); break;
-        default: return hipErrorInvalidValue;
+        case Family::Half16:
+            found = dispatch<kHalf16>(k, [&]<Inst E, bool TAIL>() { launch_bwd<BwdCfg{.env = E.env, .tail = TAIL, .f16 = true}>(k, dp, q, stream); });
+            break;
+        case Family::Stationary:
+            found = dispatch<kStationaryBwd>(k, [&]<Inst E, bool TAIL>() {
+                launch_bwd<BwdCfg{.env = E.env, .sk0 = E.s0, .sk1 = E.s1, .tail = TAIL, .pt0 = E.pt0}>(k, dp, q, stream);
+            });
+            break;
+        case Family::Plain:
+            found = dispatch<kPlain>(k, [&]<Inst E, bool TAIL>() { launch_bwd<BwdCfg{.env = E.env, .tail = TAIL}>(k, dp, q, stream); });
+            break;
+        case Family::PlainN64:
+            found = dispatch<kPlain>(k, [&]<Inst E, bool TAIL>() { launch_bwd<BwdCfg{.env = E.env, .tail = TAIL, .n64 = true}>(k, dp, q, stream); });
+            break;
+        case Family::None: break;
     }
-    return hipGetLastError();
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 #endif
 }

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "env_models.h"
 #include "rollout_f16.h"
+#include "rollout_choice.h"
 
 // Hidden layers of `M` applied to the LDS tile `in` (TB x kp[0], leading dim ld_in).  Returns the
 // LDS buffer that holds the last hidden activation.  When stash_h is non-null the activations
@@ -1286,7 +1287,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
 
 // split_k0: input width (multiple of 32) of hidden layer 0 when the plane-split kernel runs, else 0
 // ss: the streamed-split forward (no residual plane in LDS whatever split_k0 is)
-size_t rollout_fwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, int split_k0, bool ss = false) {
+size_t rollout_fwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, int split_k0, bool ss) {
     size_t b = sizeof(float) * (size_t)(TB * ldx + 2 * hidden_tile_floats(ldh, f16) + TB * (8 + 4 + 4 + 1 + 1 + 2) + (4 + GOPS_MAX_LAYERS - 1) * ldh +
                                         4 * TB * ref_points);
     if (f16) b += sizeof(_Float16) * (size_t)TB * ((((ldx - 4) + 31) & ~31) + 8);   // x16
@@ -1297,9 +1298,7 @@ size_t rollout_fwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, int spl
     }
     return b;
 }
-size_t rollout_bwd_lds_bytes(int ldx, int ldh, int ref_points, bool f16, bool split, bool ssb = false);
-
-static int device_cus() {
+int device_cus() {
     static int n_cu = 0;
     if (n_cu == 0) {
         hipDeviceProp_t prop;
@@ -1309,52 +1308,48 @@ static int device_cus() {
     return n_cu;
 }
 
-int split_grid_limit() { return device_cus(); }
-
-// Plane-split contractions (common.h SplitDev) replace the fp32 MFMAs of the register-stationary kernels for a closed-loop
-// obs -> 256 -> 256 -> act policy on the BASELINE env kinds with an input of at most 128 columns (4 chunks of 32: the
-// planes of both layers then fit the register file + LDS).  One workgroup per CU keeps the weights resident and walks
-// the tiles grid-stride, whatever the batch size.  GOPS_VF_NO_STATIONARY_SPLIT keeps the fp32-MFMA kernels.
 // Activations whose derivative jumps at 0 (relu, selu) in a launch with a tail value net that keeps a gradient: the gradient runs
 // through dV/d(obs_H) of a piecewise-linear net, and every pre-activation of THAT net which changes sign under the 22-bit plane
 // representation moves it by a finite amount - measured at cfg3 (relu, 256^3, B = 8192): 2.0e-4 from the reference with a
 // plane-split tail value net, < 1e-4 with exact fp32 products.  The tail value net of such a launch is therefore evaluated with
 // exact fp32 products (the stationary kernels do that for every tail; the streamed ones on RolloutParams.tail_fp32).  Launches
 // without a gradient are not concerned: the VALUES are continuous in the weights.
+// The step loop (policy net, env model: a relu POLICY alone is indifferent, 7.7e-6 vs 7.4e-6 at the target shape) is plane-split
+// like any other launch; the sweep is linear once the forward has fixed the activation pattern: plane-split.
 static bool kinked_with_tail(const RolloutParams& p) {
     auto kinked = [](int a) { return a == GOPS_ACT_RELU || a == GOPS_ACT_SELU; };
     return p.need_grad && p.tail && (kinked(p.pol.act) || kinked(p.val.act));
 }
 
-bool split_eligible(const RolloutParams& p) {
+static bool closed_loop_fp32(const RolloutParams& p) { return !p.f16 && !p.open_loop && p.env.repeat_num <= 1; }
+
+// Family::Split - plane-split contractions (common.h SplitDev) replace the fp32 MFMAs of the register-stationary kernels for a
+// closed-loop obs -> 256 -> 256 -> act policy on the env kinds and input widths of kSplit (up to 4 chunks of 32 inputs the
+// planes of both layers fit the register file + LDS).  One workgroup per CU keeps the weights resident and walks the tiles
+// grid-stride, whatever the batch size.  GOPS_VF_NO_STATIONARY_SPLIT keeps the fp32-MFMA kernels.
+// (relu / selu nets with a tail value net are fine here: these kernels evaluate every tail value net - forward and input
+// adjoint - with exact fp32 products)
+static bool split_ok(const RolloutParams& p, size_t& lds) {
     const MlpDev& M = p.pol;
-    if (p.f16 || p.ext || p.open_loop || p.env.repeat_num > 1) return false;
-    // (relu / selu nets with a tail value net are fine here: these kernels evaluate every tail value net - forward and input
-    // adjoint - with exact fp32 products)
-    if (p.env.kind != GOPS_ENV_LQ && p.env.kind != GOPS_ENV_IDPENDULUM && p.env.kind != GOPS_ENV_VEH3DOFCONTI) return false;
-    if (M.nl != 3 || M.dims[1] != 256 || M.dims[2] != 256 || p.ldh != 260 || M.kp32[0] > 256 || p.ldx != M.kp[0] + 4) return false;
-    // more than 128 inputs (veh3dofconti with P > 30): layer 0's planes stream from L2 - instantiated without the tail value net
-    if (M.kp32[0] > 128 && (p.env.kind != GOPS_ENV_VEH3DOFCONTI || p.tail)) return false;
+    if (!closed_loop_fp32(p) || (p.vflags & (GOPS_VF_NO_STATIONARY_SPLIT | GOPS_VF_STREAMED_FP32))) return false;
+    if (M.nl != 3 || M.dims[1] != 256 || M.dims[2] != 256 || p.ldh != 260 || p.ldx != M.kp[0] + 4) return false;
+    if (!has_inst(kSplit, p.env.kind, M.kp32[0] >> 5, 0, p.tail != 0)) return false;
     // More tiles than CUs AND a tail value net: the tail is evaluated per tile with fp32 weights streamed from L2 by the one
     // resident workgroup, which exposes every L2 round trip (measured at B = 65536: no faster than the streamed kernels with
     // their three workgroups per CU) - those launches stay on the streamed kernels.
-    if (p.tail && (p.B + TB - 1) / TB > device_cus() && !(p.vflags & GOPS_VF_SPLIT_TAIL_MULTI)) return false;
-    if (p.vflags & (GOPS_VF_NO_STATIONARY_SPLIT | GOPS_VF_STREAMED_FP32)) return false;
-    const int ref_pts = env_has_ref_table(p.env.kind) ? p.env.pre_horizon + 1 + p.H : (p.env.kind == GOPS_ENV_IDPENDULUM ? IDP_POINTS(true) : 0);
-    if (rollout_fwd_lds_bytes(p.ldx, p.ldh, env_has_ref_table(p.env.kind) ? ref_pts : 0, false, M.kp32[0]) > 160 * 1024) return false;
-    if (rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_pts, false, true) > 160 * 1024) return false;
-    return true;
+    if (p.tail && tiles(p) > device_cus() && !(p.vflags & GOPS_VF_SPLIT_TAIL_MULTI)) return false;
+    lds = rollout_fwd_lds_bytes(p.ldx, p.ldh, ref_table_points(p), false, M.kp32[0]);
+    return lds <= 160 * 1024 && split_bwd_lds_bytes(p) <= 160 * 1024;
 }
 
-// Streamed-split forward kernels: every hidden layer of the policy (and of the tail value net) 256 wide, at most 256 padded
-// inputs, fp32, closed loop, every env model - the launches the register-stationary kernels do not take (three
-// hidden layers, a tail value net with more tiles than CUs).  The backward sweep of such a launch: rollout_bwd.hip ssb_eligible
+// Family::StreamedSplit forward - every hidden layer of the policy (and of the tail value net) 256 wide, at most 256 padded
+// inputs, fp32, closed loop, every env model: the launches the register-stationary kernels do not take (three hidden layers,
+// a tail value net with more tiles than CUs).  Its LDS image at two workgroups per CU.  The sweep of such a launch: ssb below
 // (both forward variants write the same feature-major stash).  GOPS_VF_NO_STREAMED_SPLIT_FWD switches it off.
-static bool ss_shape_ok(const RolloutParams& p) {
-    if (p.f16 || p.ext || p.open_loop || p.env.repeat_num > 1) return false;
-    // (value / MLP batches, GOPS_ENV_NONE: one step - half the MFMA time of the fp32 kernels; GOPS_SS_VALUE=0 keeps those)
+static bool streamed_split_ok(const RolloutParams& p, size_t& lds) {
+    if (!closed_loop_fp32(p) || (p.vflags & (GOPS_VF_NO_STREAMED_SPLIT_FWD | GOPS_VF_STREAMED_FP32))) return false;
+    // (value / MLP batches, GOPS_ENV_NONE: one step - half the MFMA time of the fp32 kernels)
     if (p.env.kind == GOPS_ENV_NONE && (p.vflags & GOPS_VF_NO_STREAMED_SPLIT_VALUE)) return false;
-    if (p.vflags & (GOPS_VF_NO_STREAMED_SPLIT_FWD | GOPS_VF_STREAMED_FP32)) return false;
     auto net_ok = [](const MlpDev& M) {
         if (M.nl < 3 || M.kp32[0] > 256) return false;
         for (int j = 1; j < M.nl; ++j)
@@ -1362,186 +1357,154 @@ static bool ss_shape_ok(const RolloutParams& p) {
         return true;
     };
     if (!net_ok(p.pol) || p.ldh != 260 || (p.tail && !net_ok(p.val))) return false;
+    if (!has_inst(kStreamedSplit, p.env.kind, 0, 0, p.tail != 0)) return false;
     const int k0 = 32 * std::max(ss_kc0(p.pol.kp32[0]), p.tail ? ss_kc0(p.val.kp32[0]) : 0);
-    const int ref_pts = env_has_ref_table(p.env.kind) ? p.env.pre_horizon + 1 + p.H : 0;
-    return rollout_fwd_lds_bytes(p.ldx, p.ldh, ref_pts, false, k0, true) + (env_in_lds(p.env.kind, true) ? 4 * ENV_LDS_FLOATS : 0) <= 80 * 1024;   // two workgroups per CU
+    lds = rollout_fwd_lds_bytes(p.ldx, p.ldh, ref_table_points(p), false, k0, true) + (env_in_lds(p.env.kind, true) ? 4 * ENV_LDS_FLOATS : 0);
+    return lds <= 80 * 1024;
 }
-// relu / selu with a tail value net, gradient kept (kinked_with_tail above): the step loop (policy net, env model: a relu POLICY alone is
-// indifferent, 7.7e-6 vs 7.4e-6 at the target shape) is plane-split like any other launch, only the TAIL value net keeps exact fp32
-// products (p.tail_fp32); the sweep is linear once the forward has fixed the activation pattern: plane-split.
-bool ss_eligible(const RolloutParams& p) { return ss_shape_ok(p); }
-bool ss_tail_exact(const RolloutParams& p) { return kinked_with_tail(p); }
 
-// Picks the register-stationary variant when the policy is (kp0 in {16,48,128}) -> 256 -> 256 ...,
-// else the fully streamed kernel.  sk[0] / sk[1] receive the chosen chunk counts (0 = streamed).
-void rollout_variant(const RolloutParams& p, int sk[2], bool backward) {
-    sk[0] = sk[1] = 0;
+// Family::Stationary, either direction: (kp0 in {16,48,128}) -> 256 -> 256 ... on the BASELINE env kinds.
+// Register-stationary weights pin one workgroup per CU.  That is the right trade only while there is at most one tile per CU
+// (B <= 16 * #CUs = 4096 on MI355X); with more tiles the streamed kernels win because 2-3 workgroups per CU overlap each
+// other's MFMA and VALU phases.  GEN / EXT instantiations exist for the streamed kernels only; the half-precision path streams
+// its (half as large) weights from L2.
+bool stationary_shape(const RolloutParams& p) {
     const MlpDev& M = p.pol;
-    if (p.f16) return;   // the half-precision path streams its (half as large) weights from L2
-    if (p.env.repeat_num > 1 || p.ext) return;   // GEN / EXT instantiations exist for the streamed kernels only
-    if (p.env.kind >= GOPS_ENV_VEH3DOF_SURR) return;   // constrained / gym-style models: streamed kernels only
-    // Register-stationary weights pin one workgroup per CU.  That is the right trade only while there
-    // is at most one tile per CU (B <= 16 * #CUs = 4096 on MI355X); with more tiles the streamed
-    // kernels win because 2-3 workgroups per CU overlap each other's MFMA and VALU phases.
-    if ((p.B + TB - 1) / TB > device_cus()) return;
-    if (M.nl - 1 < 2 || M.dims[1] != 256 || M.dims[2] != 256 || p.env.kind == GOPS_ENV_NONE || p.ldh != 260) return;
-    sk[1] = 16;
-    const int k0 = M.kp[0] >> 4;
-    if (p.ldx == M.kp[0] + 4) {
-        // veh3dofconti: 3 chunks (P = 10) fully stationary; from 6 chunks up, the first 6 stay in
-        // registers and the rest streams (P = 30: 6 + 2, P = 50: 6 + 7)
-        if (p.env.kind == GOPS_ENV_VEH3DOFCONTI) sk[0] = (k0 == 3) ? 3 : (k0 >= 6 ? 6 : 0);
-        if ((p.env.kind == GOPS_ENV_LQ || p.env.kind == GOPS_ENV_IDPENDULUM) && k0 == 1) sk[0] = 1;
-    }
-    // The backward sweep's VALU phases need more than the 128 VGPRs left beside 384 weight registers:
-    // it keeps only the 256-register layer-1 fragments (all in AGPRs) and streams layer 0.
-    // Backward: sk[0] counts stationary K-chunks (of 16) of the delta_1 -> g_x GEMM.  kp0 = 128: 12 of
-    // them (2 n-tiles per wave; 14 spills); kp0 = 16 (lq): all 16 (1 tile, wave 0); anything else streams.
-    // The backward's stationary variants also stage this step's H_2 / H_1 tiles in LDS: exactly two hidden layers.
-    if (backward && M.nl != 3) { sk[0] = sk[1] = 0; return; }
-    if (backward) sk[0] = (sk[1] == 16 && M.kp[0] == 128) ? 12 : ((sk[1] == 16 && M.kp[0] == 16) ? 16 : 0);
-    if (p.vflags & GOPS_VF_STREAMED_FP32) sk[0] = sk[1] = 0;   // the plain streamed kernels
+    if (p.f16 || p.env.repeat_num > 1 || (p.vflags & GOPS_VF_STREAMED_FP32)) return false;
+    if (p.env.kind >= GOPS_ENV_VEH3DOF_SURR || p.env.kind == GOPS_ENV_NONE) return false;   // constrained / gym-style models: streamed kernels only
+    return tiles(p) <= device_cus() && M.nl - 1 >= 2 && M.dims[1] == 256 && M.dims[2] == 256 && p.ldh == 260;
+}
+static bool stationary_fwd_ok(const RolloutParams& p, int& s0) {
+    if (!stationary_shape(p)) return false;
+    const int k0 = p.pol.kp[0] >> 4;   // chunks of 16 inputs; pyth_lq / pyth_idpendulum: one
+    s0 = 0;
+    if (p.ldx == p.pol.kp[0] + 4) s0 = p.env.kind == GOPS_ENV_VEH3DOFCONTI ? (k0 == 3 ? 3 : (k0 >= 6 ? 6 : 0)) : (k0 == 1 ? 1 : 0);
+    return has_inst(kStationaryFwd, p.env.kind, s0, 16, p.tail != 0);
 }
 
-#define LAUNCH_FWD(ENV, A, B)                                                                            \
-    do {                                                                                                 \
-        if (p.tail) launch_with_lds(rollout_fwd_kernel<ENV, A, B, true>, grid, block, lds, stream, dp);   \
-        else launch_with_lds(rollout_fwd_kernel<ENV, A, B, false>, grid, block, lds, stream, dp);         \
-    } while (0)
-// the plain streamed fp32 kernel, or its obs -> 64 -> 64 -> act form (RolloutParams.narrow == 2: mlp_hidden_forward_n64)
-#define LAUNCH_FWD_PLAIN(ENV)                                                                                                              \
-    do {                                                                                                                                   \
-        if (p.narrow == 2) {                                                                                                               \
-            if (p.tail) launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, true, false, false, false, false, false, true>, grid, block, lds, stream, dp);  \
-            else launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, false, false, false, false, false, false, true>, grid, block, lds, stream, dp);        \
-        } else LAUNCH_FWD(ENV, 0, 0);                                                                                                      \
-    } while (0)
-#define LAUNCH_FWD_H(ENV)                                                                                          \
-    do {                                                                                                           \
-        if (p.tail) launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, true, true>, grid, block, lds, stream, dp);       \
-        else launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, false, true>, grid, block, lds, stream, dp);             \
-    } while (0)
+bool choose_forward(const RolloutParams& p, RolloutChoice& c) {
+    c = RolloutChoice{};
+    const int kind = p.env.kind, nt = tiles(p);
+    const bool tail = p.tail != 0;
+    // L2 warm-up of the sweep (rollout_bwd.hip warm_up): pays while a CU holds one tile (nothing else hides the HBM latency of
+    // the next step's stash rows); with more tiles than CUs the co-resident workgroups hide it, and the warm-up lines are
+    // evicted before their use - measured at cfg5 (4096 tiles): 3.8 GB fetched per sweep with it, 1.55 GB without, 1.39 -> 1.24 ms
+    c.touch_mode = nt > device_cus() ? 0 : 2;
+    size_t lds_split = 0, lds_ss = 0;
+    c.split = split_ok(p, lds_split);
+    c.h64 = h64_shape_ok(p);   // half precision: 64-trajectory tiles (stash rows in 64-row tiles)
+    c.ss = !c.split && streamed_split_ok(p, lds_ss);
+    c.tail_fp32 = c.ss && kinked_with_tail(p);
+    // the sweep of a streamed-split forward on the streamed-split sweep as well: its LDS image at two workgroups per CU.
+    // GOPS_VF_NO_STREAMED_SPLIT_BWD keeps the fp32-MFMA sweep.
+    c.ssb = c.ss && p.need_grad && !(p.vflags & GOPS_VF_NO_STREAMED_SPLIT_BWD) && ssb_lds_bytes(p) <= 80 * 1024;
+    c.fuse_dw0 = c.h64 && h64_can_fuse_dw0(p);
+    int sf = 0, sb = 0;
+    const bool stationary_fwd = stationary_fwd_ok(p, sf);
+    c.stationary_bwd = stationary_bwd_shape(p, sb);
+    const size_t lds_plain = rollout_fwd_lds_bytes(p.ldx, p.ldh, ref_table_points(p), p.f16 != 0, 0);
+    // narrow nets on the plain streamed fp32 kernels (neither plane-split nor register-stationary nor half): the policy's packed
+    // hidden-layer weights live in LDS for the whole launch (common.h gemm_layer_lds) - the shapes of the reference's example scripts
+    if (!p.f16 && !c.split && !c.ss && !c.h64 && !p.open_loop && !(p.vflags & GOPS_VF_NO_NARROW_LDS) && !stationary_fwd && !c.stationary_bwd) {
+        int nf = 0;
+        for (int j = 0; j < p.pol.nl - 1; ++j) nf += p.pol.kp[j] * p.pol.dims[j + 1];
+        const size_t lf = (lds_plain + 15) & ~(size_t)15;
+        const size_t lb = (rollout_bwd_lds_bytes(p.ldx, p.ldh, ref_points_in_lds(p, false), false, false) + 15) & ~(size_t)15;
+        if (nf > 0 && nf <= NARROW_MAX_FLOATS && (nf & 3) == 0 && std::max(lf, lb) + 4 * (size_t)nf <= 52 * 1024) {   // three workgroups per CU stay resident
+            // obs -> 64 -> 64 -> act (<= 64 padded inputs): the kernels' form with these shapes as compile-time constants
+            const bool n64 = p.pol.nl == 3 && p.pol.dims[1] == 64 && p.pol.dims[2] == 64 && p.pol.kp[0] <= 64 && !(p.vflags & GOPS_VF_NO_NARROW_N64);
+            c.narrow = n64 ? 2 : 1;
+            c.narrow_floats = nf;
+            c.narrow_off_fwd = (int)(lf / 4);
+            c.narrow_off_bwd = (int)(lb / 4);
+        }
+    }
+    // the sub-step parking of the idpendulum forward: read by the plane-split stationary sweep and by the sweeps that stage nothing
+    // else (streamed fp32 - also its EXT form -, streamed-split); the exact-fp32 stationary sweep and the half kernels recompute
+    c.idp_parking = kind == GOPS_ENV_IDPENDULUM && p.env.repeat_num <= 1 && p.need_grad && (c.split || (!p.f16 && (c.ssb || !c.stationary_bwd)));
 
-// `p` is the host copy (for shape dispatch), `dp` the device copy the kernel reads.
-hipError_t launch_rollout_fwd_h64(const RolloutParams& p, const RolloutParams* dp, hipStream_t stream);   // rollout_h64.hip
-hipError_t launch_rollout_fwd(const RolloutParams& p, const RolloutParams* dp, hipStream_t stream) {
-#ifdef GOPS_ONLY_NARROW   // the same for the plain streamed fp32 kernel of pyth_idpendulum (cfg1, the example scripts' shapes): EXTRA=-DGOPS_ONLY_NARROW
-#if GOPS_ONLY_NARROW == 2
-    launch_with_lds(rollout_fwd_kernel<GOPS_ENV_IDPENDULUM, 0, 0, false, false, false, false, false, false, true>, dim3((p.B + TB - 1) / TB), dim3(NTHREADS), 4 * ((size_t)p.narrow_off_fwd + p.narrow_floats), stream, dp);
+    KernelChoice& k = c.fwd;
+    k = {Family::None, kind, 0, 0, tail, false, nt, c.narrow ? 4 * ((size_t)c.narrow_off_fwd + c.narrow_floats) : lds_plain};
+    if (c.h64) {
+        k.family = Family::Half64;
+        k.grid = h64_fwd_grid(p);
+        k.lds = rollout_fwd_h64_lds_bytes(p.ldx, p.ldh);
+    } else if (c.split) {   // one workgroup per CU, grid-stride over the tiles
+        k.family = Family::Split;
+        k.s0 = p.pol.kp32[0] >> 5;
+        k.multi = nt > device_cus();
+        k.grid = std::min(nt, device_cus());
+        k.lds = lds_split;
+    } else if (c.ss) {
+        k.family = Family::StreamedSplit;
+        k.lds = lds_ss;
+    } else if (p.f16) {   // weights streamed from L2, four workgroups per CU
+        k.family = Family::Half16;
+        return has_inst(kHalf16, kind, 0, 0, tail);
+    } else if (p.env.repeat_num > 1) {   // ActionRepeatModel
+        k.family = Family::General;
+        return has_inst(kGenFwd, kind, 0, 0, tail);
+    } else if (stationary_fwd) {
+        k.family = Family::Stationary;
+        k.s0 = sf;
+        k.s1 = 16;
+    } else {
+        k.family = c.narrow == 2 ? Family::PlainN64 : Family::Plain;
+        return has_inst(kPlain, kind, 0, 0, tail);
+    }
+    return true;
+}
+
+// rollout_fwd_kernel's template arguments by name
+struct FwdCfg {
+    int env, sk0 = 0, sk1 = 0;
+    bool tail = false, f16 = false, gen = false, split = false, multi = false, ss = false, n64 = false;
+};
+template <FwdCfg C>
+static void launch_fwd(const KernelChoice& k, const RolloutParams* dp, hipStream_t stream) {
+    launch_with_lds(rollout_fwd_kernel<C.env, C.sk0, C.sk1, C.tail, C.f16, C.gen, C.split, C.multi, C.ss, C.n64>, dim3(k.grid), dim3(NTHREADS), k.lds,
+                    stream, dp);
+}
+
+// `p` is the host copy, `dp` the device copy the kernel reads.
+hipError_t launch_rollout_fwd(const RolloutParams& p, const KernelChoice& k, const RolloutParams* dp, hipStream_t stream) {
+#ifdef GOPS_ONLY_NARROW   // register / ISA studies (EXTRA=-DGOPS_ONLY_NARROW[=2] tools/kernel_regs.sh rollout_fwd.hip): ONE instantiation, seconds to compile - the plain streamed fp32 kernel of pyth_idpendulum (cfg1, the example scripts' shapes)
+    launch_fwd<FwdCfg{.env = GOPS_ENV_IDPENDULUM, .n64 = GOPS_ONLY_NARROW == 2}>(k, dp, stream);
+    return hipGetLastError();
+#elif defined(GOPS_ONLY_TARGET)   // ... EXTRA=-DGOPS_ONLY_TARGET: the headline launch's kernel
+    launch_fwd<FwdCfg{.env = GOPS_ENV_VEH3DOFCONTI, .sk0 = 4, .sk1 = 8, .split = true}>(k, dp, stream);
+    return hipGetLastError();
 #else
-    launch_with_lds(rollout_fwd_kernel<GOPS_ENV_IDPENDULUM, 0, 0, false>, dim3((p.B + TB - 1) / TB), dim3(NTHREADS), 4 * ((size_t)p.narrow_off_fwd + p.narrow_floats), stream, dp);
-#endif
-    return hipGetLastError();
-#elif defined(GOPS_ONLY_TARGET)   // register / ISA studies (EXTRA=-DGOPS_ONLY_TARGET tools/kernel_regs.sh rollout_fwd.hip): ONE instantiation, seconds to compile
-    launch_with_lds(rollout_fwd_kernel<GOPS_ENV_VEH3DOFCONTI, 4, 8, false, false, false, true>, dim3(1), dim3(NTHREADS), 0, stream, dp);
-    return hipGetLastError();
-#else
-    if (p.h64) return launch_rollout_fwd_h64(p, dp, stream);   // half precision, 64-trajectory tiles
-    const dim3 grid((p.B + TB - 1) / TB), block(NTHREADS);
-    size_t lds = rollout_fwd_lds_bytes(p.ldx, p.ldh, env_has_ref_table(p.env.kind) ? p.env.pre_horizon + 1 + p.H : 0, p.f16 != 0,
-                                       p.sp.on ? 32 * p.sp.kc[0] : 0);
-    if (p.narrow) lds = 4 * ((size_t)p.narrow_off_fwd + p.narrow_floats);   // (api.hip: only ever set for the plain streamed fp32 kernels)
-    int sk[2];
-    rollout_variant(p, sk, false);
-    const int key = sk[0] * 100 + sk[1];
-    if (p.sp.on) {   // plane-split stationary kernels: layer 0 in KC0 chunks of 32 inputs
-#define LAUNCH_FWD_SPLIT(ENV, KC0)                                                                                           \
-    do {                                                                                                                     \
-        if (multi) {                                                                                                         \
-            if (p.tail) launch_with_lds(rollout_fwd_kernel<ENV, KC0, 8, true, false, false, true, true>, grid, block, lds, stream, dp);  \
-            else launch_with_lds(rollout_fwd_kernel<ENV, KC0, 8, false, false, false, true, true>, grid, block, lds, stream, dp);        \
-        } else if (p.tail) launch_with_lds(rollout_fwd_kernel<ENV, KC0, 8, true, false, false, true>, grid, block, lds, stream, dp);  \
-        else launch_with_lds(rollout_fwd_kernel<ENV, KC0, 8, false, false, false, true>, grid, block, lds, stream, dp);        \
-    } while (0)
-        const int kc0 = p.sp.kc[0];
-        const dim3 grid(std::min<int>((p.B + TB - 1) / TB, device_cus()));   // one workgroup per CU, grid-stride over the tiles
-        const bool multi = (p.B + TB - 1) / TB > device_cus();
-        if (p.env.kind == GOPS_ENV_LQ && kc0 == 1) LAUNCH_FWD_SPLIT(GOPS_ENV_LQ, 1);
-        else if (p.env.kind == GOPS_ENV_IDPENDULUM && kc0 == 1) LAUNCH_FWD_SPLIT(GOPS_ENV_IDPENDULUM, 1);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && kc0 == 2) LAUNCH_FWD_SPLIT(GOPS_ENV_VEH3DOFCONTI, 2);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && kc0 == 3) LAUNCH_FWD_SPLIT(GOPS_ENV_VEH3DOFCONTI, 3);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && kc0 == 4) LAUNCH_FWD_SPLIT(GOPS_ENV_VEH3DOFCONTI, 4);
-#define LAUNCH_FWD_SPLIT_NOTAIL(ENV, KC0)                                                                                    \
-    do {                                                                                                                     \
-        if (multi) launch_with_lds(rollout_fwd_kernel<ENV, KC0, 8, false, false, false, true, true>, grid, block, lds, stream, dp);  \
-        else launch_with_lds(rollout_fwd_kernel<ENV, KC0, 8, false, false, false, true>, grid, block, lds, stream, dp);       \
-    } while (0)
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && kc0 == 5 && !p.tail) LAUNCH_FWD_SPLIT_NOTAIL(GOPS_ENV_VEH3DOFCONTI, 5);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && kc0 == 6 && !p.tail) LAUNCH_FWD_SPLIT_NOTAIL(GOPS_ENV_VEH3DOFCONTI, 6);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && kc0 == 7 && !p.tail) LAUNCH_FWD_SPLIT_NOTAIL(GOPS_ENV_VEH3DOFCONTI, 7);
-        else if (p.env.kind == GOPS_ENV_VEH3DOFCONTI && kc0 == 8 && !p.tail) LAUNCH_FWD_SPLIT_NOTAIL(GOPS_ENV_VEH3DOFCONTI, 8);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (p.ss) {   // streamed-split forward
-        const int k0 = 32 * std::max(p.ssp.kc[0], p.tail ? p.ssv.kc[0] : 0);
-        const size_t lds_ss = rollout_fwd_lds_bytes(p.ldx, p.ldh, env_has_ref_table(p.env.kind) ? p.env.pre_horizon + 1 + p.H : 0, false, k0, true) +
-                              (env_in_lds(p.env.kind, true) ? 4 * ENV_LDS_FLOATS : 0);
-#define LAUNCH_FWD_SS(ENV)                                                                                                        \
-    do {                                                                                                                          \
-        if (p.tail) launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, true, false, false, false, false, true>, grid, block, lds_ss, stream, dp);   \
-        else launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, false, false, false, false, false, true>, grid, block, lds_ss, stream, dp);         \
-    } while (0)
-        switch (p.env.kind) {
-            case GOPS_ENV_NONE: LAUNCH_FWD_SS(GOPS_ENV_NONE); break;
-            case GOPS_ENV_LQ: LAUNCH_FWD_SS(GOPS_ENV_LQ); break;
-            case GOPS_ENV_IDPENDULUM: LAUNCH_FWD_SS(GOPS_ENV_IDPENDULUM); break;
-            case GOPS_ENV_VEH3DOFCONTI: LAUNCH_FWD_SS(GOPS_ENV_VEH3DOFCONTI); break;
-            case GOPS_ENV_VEH3DOF_SURR: LAUNCH_FWD_SS(GOPS_ENV_VEH3DOF_SURR); break;
-            case GOPS_ENV_CARTPOLE: LAUNCH_FWD_SS(GOPS_ENV_CARTPOLE); break;
-            case GOPS_ENV_PENDULUM: LAUNCH_FWD_SS(GOPS_ENV_PENDULUM); break;
-            case GOPS_ENV_VEH2DOF: LAUNCH_FWD_SS(GOPS_ENV_VEH2DOF); break;
-            case GOPS_ENV_MOBILEROBOT: LAUNCH_FWD_SS(GOPS_ENV_MOBILEROBOT); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (p.f16) {   // half-precision kernels: weights streamed from L2, four workgroups per CU
-        switch (p.env.kind) {
-            case GOPS_ENV_NONE: LAUNCH_FWD_H(GOPS_ENV_NONE); break;
-            case GOPS_ENV_LQ: LAUNCH_FWD_H(GOPS_ENV_LQ); break;
-            case GOPS_ENV_IDPENDULUM: LAUNCH_FWD_H(GOPS_ENV_IDPENDULUM); break;
-            case GOPS_ENV_VEH3DOFCONTI: LAUNCH_FWD_H(GOPS_ENV_VEH3DOFCONTI); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (p.env.repeat_num > 1) {   // ActionRepeatModel: the GEN instantiations (streamed)
-#define LAUNCH_FWD_GEN(ENV)                                                                                        \
-    do {                                                                                                           \
-        if (p.tail) launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, true, false, true>, grid, block, lds, stream, dp);  \
-        else launch_with_lds(rollout_fwd_kernel<ENV, 0, 0, false, false, true>, grid, block, lds, stream, dp);        \
-    } while (0)
-        switch (p.env.kind) {
-            case GOPS_ENV_LQ: LAUNCH_FWD_GEN(GOPS_ENV_LQ); break;
-            case GOPS_ENV_IDPENDULUM: LAUNCH_FWD_GEN(GOPS_ENV_IDPENDULUM); break;
-            case GOPS_ENV_CARTPOLE: LAUNCH_FWD_GEN(GOPS_ENV_CARTPOLE); break;
-            case GOPS_ENV_PENDULUM: LAUNCH_FWD_GEN(GOPS_ENV_PENDULUM); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (p.env.kind) {
-        case GOPS_ENV_NONE: LAUNCH_FWD_PLAIN(GOPS_ENV_NONE); break;
-        case GOPS_ENV_LQ:
-            if (key == 116) LAUNCH_FWD(GOPS_ENV_LQ, 1, 16); else LAUNCH_FWD_PLAIN(GOPS_ENV_LQ);
+    bool found = false;
+    switch (k.family) {
+        case Family::Half64: return launch_rollout_fwd_h64(p, k, dp, stream);
+        case Family::Split:
+            found = dispatch<kSplit>(k, [&]<Inst E, bool TAIL>() {
+                dispatch_bool(k.multi, [&](auto multi) {
+                    launch_fwd<FwdCfg{.env = E.env, .sk0 = E.s0, .sk1 = 8, .tail = TAIL, .split = true, .multi = decltype(multi)::value}>(k, dp, stream);
+                });
+            });
             break;
-        case GOPS_ENV_IDPENDULUM:
-            if (key == 116) LAUNCH_FWD(GOPS_ENV_IDPENDULUM, 1, 16); else LAUNCH_FWD_PLAIN(GOPS_ENV_IDPENDULUM);
+        case Family::StreamedSplit:
+            found = dispatch<kStreamedSplit>(k, [&]<Inst E, bool TAIL>() { launch_fwd<FwdCfg{.env = E.env, .tail = TAIL, .ss = true}>(k, dp, stream); });
             break;
-        case GOPS_ENV_VEH3DOFCONTI:
-            if (key == 616) LAUNCH_FWD(GOPS_ENV_VEH3DOFCONTI, 6, 16);
-            else if (key == 316) LAUNCH_FWD(GOPS_ENV_VEH3DOFCONTI, 3, 16);
-            else if (key == 16) LAUNCH_FWD(GOPS_ENV_VEH3DOFCONTI, 0, 16);
-            else LAUNCH_FWD_PLAIN(GOPS_ENV_VEH3DOFCONTI);
+        case Family::Half16:
+            found = dispatch<kHalf16>(k, [&]<Inst E, bool TAIL>() { launch_fwd<FwdCfg{.env = E.env, .tail = TAIL, .f16 = true}>(k, dp, stream); });
             break;
-        case GOPS_ENV_VEH3DOF_SURR: LAUNCH_FWD_PLAIN(GOPS_ENV_VEH3DOF_SURR); break;
-        case GOPS_ENV_CARTPOLE: LAUNCH_FWD_PLAIN(GOPS_ENV_CARTPOLE); break;
-        case GOPS_ENV_PENDULUM: LAUNCH_FWD_PLAIN(GOPS_ENV_PENDULUM); break;
-        case GOPS_ENV_VEH2DOF: LAUNCH_FWD_PLAIN(GOPS_ENV_VEH2DOF); break;
-        case GOPS_ENV_MOBILEROBOT: LAUNCH_FWD_PLAIN(GOPS_ENV_MOBILEROBOT); break;
-        default: return hipErrorInvalidValue;
+        case Family::General:
+            found = dispatch<kGenFwd>(k, [&]<Inst E, bool TAIL>() { launch_fwd<FwdCfg{.env = E.env, .tail = TAIL, .gen = true}>(k, dp, stream); });
+            break;
+        case Family::Stationary:
+            found = dispatch<kStationaryFwd>(k, [&]<Inst E, bool TAIL>() { launch_fwd<FwdCfg{.env = E.env, .sk0 = E.s0, .sk1 = E.s1, .tail = TAIL}>(k, dp, stream); });
+            break;
+        case Family::Plain:
+            found = dispatch<kPlain>(k, [&]<Inst E, bool TAIL>() { launch_fwd<FwdCfg{.env = E.env, .tail = TAIL}>(k, dp, stream); });
+            break;
+        case Family::PlainN64:
+            found = dispatch<kPlain>(k, [&]<Inst E, bool TAIL>() { launch_fwd<FwdCfg{.env = E.env, .tail = TAIL, .n64 = true}>(k, dp, stream); });
+            break;
+        case Family::None: break;
     }
-    return hipGetLastError();
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 #endif
 }

@@ -13,10 +13,11 @@
 // contiguous window (tile-major: 3.5 % slower, address windows 320 KB apart).  The weight-gradient GEMMs contract over all rows
 // and do not care about their order.
 // Scope: env kinds GOPS_ENV_NONE (value / MLP batches) and GOPS_ENV_LQ, closed loop, every hidden layer 256 wide, at most 64
-// padded inputs; everything else stays on the 16-row kernels (api.hip: h64_eligible).
+// padded inputs; everything else stays on the 16-row kernels (h64_shape_ok below).
 #include "common.h"
 #include "env_models.h"
 #include "rollout_f16.h"
+#include "rollout_choice.h"
 
 #define TB64 64
 // stash stores are non-temporal (measured: plain stores cost the sweep 9 %)
@@ -487,7 +488,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void rollout_bwd_h64_kernel(const Roll
     // stash (a third of the sweep's HBM writes) and the layer's GEMM launch (which read it back: 0.38 GB at cfg5) is gone.  The sums
     // of step t are formed by waves 1 .. 3 during the env phase of step t - 1, which occupies wave 0 only (delta_1 of step t stays in
     // `dbuf` until the network sweep of step t - 1 starts behind that phase's barrier); step 0's by everybody behind the loop.
-    const bool fuse_w0 = q.w0_part != nullptr;   // (pyth_lq rollouts and plain value batches: api.hip h64_fuses_dw0)
+    const bool fuse_w0 = q.w0_part != nullptr;   // (pyth_lq rollouts and plain value batches: h64_can_fuse_dw0 below)
     const int K0 = p.pol.dims[0];
     auto w0_accumulate = [&](int feature, const float* xrows) {
         const _Float16* dcol = dbuf + feature;
@@ -667,53 +668,36 @@ __global__ __launch_bounds__(NTHREADS, 2) void rollout_bwd_h64_kernel(const Roll
     if (q.ad_st != nullptr && blockIdx.x == 0 && threadIdx.x == 0) adam_snapshot(q.ad_st, q.ad_snap, q.ad_b1, q.ad_b2);   // (gops_rollout_backward_update)
 }
 
-hipError_t launch_rollout_fwd_h64(const RolloutParams& p, const RolloutParams* dp, hipStream_t stream) {
-    const dim3 grid((p.B + TB64 - 1) / TB64), block(NTHREADS);
-    size_t lds = rollout_fwd_h64_lds_bytes(p.ldx, p.ldh);
+hipError_t launch_rollout_fwd_h64(const RolloutParams& p, const KernelChoice& k, const RolloutParams* dp, hipStream_t stream) {
+    size_t lds = k.lds;
     if (p.dbg != nullptr) lds = max(lds, (size_t)84 * 1024);   // phase counters: ONE workgroup per CU, so that the phases of thread 0 add up
-    if (p.env.kind == GOPS_ENV_LQ) {
-        if (p.tail) launch_with_lds(rollout_fwd_h64_kernel<GOPS_ENV_LQ, true>, grid, block, lds, stream, dp);
-        else launch_with_lds(rollout_fwd_h64_kernel<GOPS_ENV_LQ, false>, grid, block, lds, stream, dp);
-    } else if (p.env.kind == GOPS_ENV_NONE) {
-        if (p.tail) return hipErrorInvalidValue;
-        launch_with_lds(rollout_fwd_h64_kernel<GOPS_ENV_NONE, false>, grid, block, lds, stream, dp);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool found = dispatch<kHalf64>(k, [&]<Inst E, bool TAIL>() {
+        launch_with_lds(rollout_fwd_h64_kernel<E.env, TAIL>, dim3(k.grid), dim3(NTHREADS), lds, stream, dp);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-hipError_t launch_rollout_bwd_h64(const RolloutParams& p, const RolloutParams* dp, const BwdPatch& q, hipStream_t stream) {
-    constexpr int RG = H64_BWD_RG, TBW = 16 * RG;
-    const dim3 grid((p.B + TBW - 1) / TBW), block(NTHREADS);
-    size_t lds = rollout_bwd_h64_lds_bytes(p.ldx, p.ldh);
+hipError_t launch_rollout_bwd_h64(const RolloutParams& p, const KernelChoice& k, const RolloutParams* dp, const BwdPatch& q, hipStream_t stream) {
+    size_t lds = k.lds;
     if (q.dbg != nullptr) lds = max(lds, (size_t)84 * 1024);   // (as in the forward)
-    if (p.env.kind == GOPS_ENV_LQ) {
-        if (p.tail) launch_with_lds(rollout_bwd_h64_kernel<GOPS_ENV_LQ, true, RG>, grid, block, lds, stream, dp, q);
-        else launch_with_lds(rollout_bwd_h64_kernel<GOPS_ENV_LQ, false, RG>, grid, block, lds, stream, dp, q);
-    } else if (p.env.kind == GOPS_ENV_NONE) {
-        if (p.tail) return hipErrorInvalidValue;
-        launch_with_lds(rollout_bwd_h64_kernel<GOPS_ENV_NONE, false, RG>, grid, block, lds, stream, dp, q);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool found = dispatch<kHalf64>(k, [&]<Inst E, bool TAIL>() {
+        launch_with_lds(rollout_bwd_h64_kernel<E.env, TAIL, H64_BWD_RG>, dim3(k.grid), dim3(NTHREADS), lds, stream, dp, q);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
+int h64_fwd_grid(const RolloutParams& p) { return (p.B + TB64 - 1) / TB64; }
+int h64_sweep_grid(const RolloutParams& p) { return (p.B + 16 * H64_BWD_RG - 1) / (16 * H64_BWD_RG); }
 // Launches whose first-layer weight gradient the sweep forms itself (BwdPatch::w0_part): pyth_lq policies and value nets with <= 8 inputs
 // (GOPS_VF_NO_FUSED_DW0: the GEMM path, for A/B)
-int h64_sweep_grid(const RolloutParams& p) { return (p.B + 16 * H64_BWD_RG - 1) / (16 * H64_BWD_RG); }
-bool h64_fuses_dw0(const RolloutParams& p) {
-    return p.f16 && p.h64 && (p.env.kind == GOPS_ENV_LQ || p.env.kind == GOPS_ENV_NONE) && p.pol.dims[0] <= H64_W0_COLS && p.pol.dims[1] == 256 &&
-           p.need_grad &&
-           !(p.vflags & GOPS_VF_NO_FUSED_DW0);
+bool h64_can_fuse_dw0(const RolloutParams& p) {
+    return p.pol.dims[0] <= H64_W0_COLS && p.pol.dims[1] == 256 && p.need_grad && !(p.vflags & GOPS_VF_NO_FUSED_DW0);
 }
 
-// The launches the 64-row half kernels take (api.hip build_plan)
-bool h64_eligible(const RolloutParams& p) {
-    if (!p.f16 || p.open_loop || p.ext || p.env.repeat_num > 1) return false;
-    if (p.env.kind != GOPS_ENV_LQ && p.env.kind != GOPS_ENV_NONE) return false;
-    if (p.env.kind == GOPS_ENV_NONE && p.tail) return false;
+// The launches the 64-row half kernels take (Family::Half64)
+bool h64_shape_ok(const RolloutParams& p) {
+    if (!p.f16 || p.open_loop || p.env.repeat_num > 1) return false;
+    if (!has_inst(kHalf64, p.env.kind, 0, 0, p.tail != 0)) return false;
     auto net_ok = [](const MlpDev& M) {
         if (M.nl < 2 || M.kp32[0] > 64) return false;
         for (int j = 1; j < M.nl; ++j)

@@ -1364,3 +1364,76 @@ def test_constrained_per_trajectory_case_premises(name):
     tiles = -(-B // case["tile"])
     assert abs(tiles - 256) >= 4 and abs(tiles - 512) >= 3
     assert prep["walks"] == (name == "ss_mob_walk")
+
+
+PLAN_TABLE = os.path.join(ROOT, "tests", "golden", "rollout_plan_table.json")
+PLAN_ENVS = (("none", False), ("pyth_lq", False), ("pyth_idpendulum", False), ("pyth_veh3dofconti", True),
+             ("pyth_veh3dofconti_surrcstr", True), ("gym_cartpoleconti", False), ("gym_pendulum", False), ("pyth_veh2dofconti", True),
+             ("pyth_mobilerobot", False))
+
+
+def plan_grid():
+    """Descriptions of the plan table, in its order: env kind x hidden shape x tail value net x dtype x batch (one tile
+    per CU or fewer / more) x pre_horizon (vehicle kinds) x variant flags (the default, and - at the small batch - each flag
+    that steers the choice of a rollout kernel)."""
+    import itertools
+    for (env_id, veh), hidden, tail, f16, batch in itertools.product(
+            PLAN_ENVS, ((64, 64), (32, 32), (256, 256), (256, 256, 256)), (0, 1), (0, 1), (17, 4112)):
+        for P in ((5, 10, 30, 50) if veh else (None,)):
+            for flags in ((0, 0x1, 0x2, 0x4, 0x10, 0x400, 0x800) if batch == 17 and P in (None, 30) else (0,)):
+                yield env_id, P, hidden, tail, f16, batch, flags
+
+
+def plan_desc(env_id, P, hidden, tail, f16, batch, flags):
+    from gops_amd import hip_backend as hb
+    from gops_amd.create_pkg.create_env_model import create_env_model
+    if env_id == "none":
+        e = hb.GopsEnv()
+        e.kind, e.obs_dim, e.act_dim = 0, 6, 1
+    else:
+        e = create_env_model(env_id, **({"pre_horizon": P} if P else {})).hip_env()
+    fh = 0 if (tail or env_id == "none") else 1
+
+    def mlp(sizes):
+        m = hb.GopsMlp()
+        m.n_layers = len(sizes) - 1
+        for i, s in enumerate(sizes):
+            m.sizes[i] = s
+        for j in range(m.n_layers):
+            m.weight[j] = m.bias[j] = 1
+        m.hidden_act, m.dtype = hb.ACT_IDS["elu"], f16
+        return m
+    d = hb.GopsRolloutDesc()
+    d.batch, d.horizon, d.finite_horizon, d.need_grad, d.gamma = batch, (1 if env_id == "none" else (P or 10)), fh, 1, 0.99
+    d.tail_value, d.dtype, d.variant_flags, d.env = tail, f16, flags, e
+    d.policy = mlp([e.obs_dim + fh] + list(hidden) + [1 if env_id == "none" else e.act_dim])
+    if tail:
+        d.value = mlp([e.obs_dim] + list(hidden) + [1])
+    return d
+
+
+def test_rollout_plan_matches_the_recorded_table():
+    """The workspace carve and the kernel family of every description in plan_grid() equal tests/golden/rollout_plan_table.json,
+    recorded from the commit BEFORE the kernel choice moved into csrc/rollout_choice.h: a later change moves the carve only on
+    purpose (and re-records the table).  Rows carry [workspace bytes, gops_rollout_variant, launchable].  `launchable` is 0
+    for the 3 rows (pyth_veh3dofconti, pre_horizon 5, 256-256 policy, fp32) whose plan at that commit named a plane-split
+    forward kernel that was never instantiated - the workspace query succeeded and gops_rollout_forward returned
+    hipErrorInvalidValue.  Eligibility now is "the instantiation exists", so those descriptions take kernels that do exist:
+    for them the test asserts a plan other than the recorded one, for every other row equality."""
+    import json
+    from gops_amd import hip_backend as hb
+    rows = json.load(open(PLAN_TABLE))["rows"]
+    grid = list(plan_grid())
+    assert len(grid) == len(rows) and len(rows) >= 300
+    lib = hb.lib()
+    bad = []
+    for args, (nbytes, variant, launchable) in zip(grid, rows):
+        d = plan_desc(*args)
+        got = [lib.gops_rollout_workspace_bytes(ctypes.byref(d)), lib.gops_rollout_variant(ctypes.byref(d))]
+        if launchable:
+            if got != [nbytes, variant]:
+                bad.append((args, got, [nbytes, variant]))
+        elif not (got[0] > 0 and got[1] >= 0 and got[1] != variant):
+            bad.append((args, got, "a launchable plan"))
+    assert not bad, bad[:5]
+    assert sum(1 for r in rows if not r[2]) == 3
