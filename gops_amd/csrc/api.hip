@@ -10,37 +10,8 @@
 #include <vector>
 
 #include "common.h"
+#include "launchers.h"
 #include "rollout_choice.h"
-
-hipError_t launch_upload_params(const RolloutParams& p, RolloutParams* dst, hipStream_t s);
-hipError_t launch_prologue(const RolloutParams& p, RolloutParams* dst, int P, float pdt, hipStream_t s);
-hipError_t launch_dw_gemm(const float* D, int N, const float* X, int Kp, long long S, int splits,
-                          int chunks_per_split, float* part, float* part_b, bool big, hipStream_t s, const float* dscale, unsigned vflags);
-bool dw_skinny_ok(int N, int Kp);   // aux_kernels.hip
-hipError_t launch_dw_gemm_f16(const void* D, int N, const void* X, int Kp, long long S, int splits,
-                              int chunks_per_split, float* part, float* part_b, hipStream_t s);
-hipError_t launch_dw_out(const float* dy, const float* h, bool h_is_half, int K, int A, long long S, int splits,
-                         float* part, float* part_b, hipStream_t s);
-void reduce_jobs_add(ReduceJobs& jobs, const float* part, int splits, int rows, int cols, int ld, float* out, int slab_rows = 0);
-hipError_t launch_linear_out_fwd(const float* h, int K, const float* Wo, const float* bo, int W, int B, float* y, hipStream_t s);
-hipError_t launch_linear_out_bwd(const float* gy, int W, int Wp, const float* Wo, int K, int B, long long S, float* gh,
-                                 float* gyp, hipStream_t s);
-hipError_t launch_reduce(const ReduceJobs& jobs, hipStream_t s);
-hipError_t launch_fill_zero(float* p, size_t n, hipStream_t s);
-// rollout_poly.hip: POLY approximators, one lane per trajectory
-size_t poly_rollout_workspace_bytes(const GopsRolloutDesc& d);
-int poly_rollout_forward(const GopsRolloutDesc& d, const GopsRolloutIn& in, const GopsRolloutOut& out, void* ws, size_t bytes, hipStream_t s);
-int poly_rollout_backward(const GopsRolloutDesc& d, const float* grad_v, const GopsMlpGrad& g, void* ws, size_t bytes, hipStream_t s);
-size_t poly_value_workspace_bytes(const GopsMlp& v, int B);
-int poly_value_forward(const GopsMlp& v, int B, const float* obs, float* out, hipStream_t s);
-int poly_value_backward(const GopsMlp& v, int B, const float* obs, const float* grad_v, const GopsMlpGrad& g, void* ws, size_t bytes,
-                        hipStream_t s);
-hipError_t launch_env_step(const GopsEnv& env, int B, const GopsStepIO& io, float pdt, hipStream_t s);
-hipError_t launch_env_constraint(const GopsEnv& env, int B, const GopsStepIO& io, hipStream_t s);
-hipError_t launch_polyak(const GopsAdamTensors& T, float omt, float tau, hipStream_t s);
-hipError_t launch_batch_loss(const float* a, const float* b, int n, float gsc, float sc0, float* grad, float* stats, hipStream_t s);
-hipError_t launch_adam(const GopsAdamTensors& T, GopsAdamState* st, double beta1, double beta2, float eps,
-                       hipStream_t s);
 
 // One hipFuncSetAttribute per kernel (common.h: launch_with_lds).
 bool lds_attr_needed(const void* kernel) {
@@ -113,11 +84,6 @@ struct Carver {
     }
 };
 
-struct DwPlan {
-    int splits, chunks_per_split;
-    bool big;
-};
-
 // Phase counters of block 0 (make dbg: GOPS_DBG_BUILD; tools/dbg_run.py with GOPS_DBG_TIMING=1): 16 counters per direction
 // (`slot` 0: forward, 1: backward), or null.  The product library reads no environment and allocates nothing here.
 unsigned long long* dbg_timing_buffer(int slot) {
@@ -132,23 +98,6 @@ unsigned long long* dbg_timing_buffer(int slot) {
     (void)slot;
     return nullptr;
 #endif
-}
-
-DwPlan plan_dw(int N, int Kp, long long S, bool f16 = false, int wg_target = 512) {
-    DwPlan d;
-    d.big = f16 || (N >= 128 && Kp >= 128);   // the half-precision GEMM has one tile size (128) and 64-sample chunks
-    const int T = d.big ? 128 : 64;
-    int tiles = ((N + T - 1) / T) * ((Kp + T - 1) / T);
-    if (!f16 && dw_skinny_ok(N, Kp)) tiles = (N + 255) / 256;   // dw_skinny_kernel: one workgroup per 256 features and split
-    const int sc = f16 ? 64 : DW_SC_HOST;
-    const long long chunks = (S + sc - 1) / sc;
-    if (wg_target < 1) wg_target = 512;
-    long long splits = (wg_target + tiles - 1) / tiles;
-    if (splits > chunks) splits = chunks;
-    if (splits < 1) splits = 1;
-    d.chunks_per_split = (int)((chunks + splits - 1) / splits);
-    d.splits = (int)((chunks + d.chunks_per_split - 1) / d.chunks_per_split);
-    return d;
 }
 
 int check_mlp(const GopsMlp& m, int in_dim, int out_dim, bool f16) {
@@ -194,6 +143,7 @@ struct Plan {
     RolloutParams p;
     RolloutChoice choice;                  // which kernels run (rollout_choice.h); p's variant fields are copies of it
     RolloutParams* dev_params = nullptr;   // device copy read by the rollout kernels
+    DwLayer dw[GOPS_MAX_LAYERS];              // the weight-gradient stage, one record per Linear layer (dw_plan.h)
     float* dw_part[GOPS_MAX_LAYERS] = {};     // split-K partial slabs, one region per Linear layer
     float* dw_part_b[GOPS_MAX_LAYERS] = {};
     float* dummy = nullptr;                   // open loop: stand-in policy weights
@@ -378,20 +328,18 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
         p.st.tail_done = c.take((size_t)p.B);
         // split-K partial slabs of the weight-gradient GEMMs: one region per layer so that all
         // partial sums can be reduced by a single launch at the end
-        for (int j = 0; j < p.pol.nl - 1; ++j) {
-            const int Kp = f16 ? p.pol.kp32[j] : p.pol.kp[j];
-            const DwPlan d = plan_dw(p.pol.dims[j + 1], Kp, S, f16, p.dw_wgs);
-            size_t nw = (size_t)d.splits * p.pol.dims[j + 1] * Kp, nb = (size_t)d.splits * p.pol.dims[j + 1];
-            if (j == 0 && ch.fuse_dw0) {   // one slab [256][8] / [256] per workgroup of the 64-row sweep instead (rollout_h64.hip)
-                nw = std::max(nw, (size_t)h64_sweep_grid(p) * 256 * 8);
-                nb = std::max(nb, (size_t)h64_sweep_grid(p) * 256);
-            }
-            plan.dw_part[j] = c.take(nw);
-            plan.dw_part_b[j] = c.take(nb);
-        }
         const int Lh = p.pol.nl - 1;
-        plan.dw_part[Lh] = c.take((size_t)DW_OUT_SPLITS * GOPS_MAX_ACT * p.pol.dims[Lh]);
-        plan.dw_part_b[Lh] = c.take((size_t)DW_OUT_SPLITS * GOPS_MAX_ACT);
+        for (int j = 0; j < Lh; ++j) plan.dw[j] = plan_dw(p.pol.dims[j + 1], p.pol.dims[j], f16 ? p.pol.kp32[j] : p.pol.kp[j], S, f16, p.dw_wgs);
+        plan.dw[Lh] = plan_dw_out(p.pol.dims[Lh], p.pol.dims[Lh + 1], S);
+        if (ch.fuse_dw0) {   // ... or one slab [N][H64_W0_COLS] / [N] per workgroup of the 64-row sweep (rollout_h64.hip)
+            DwLayer& d = plan.dw[0];
+            d.slab_w = std::max(d.slab_w, (size_t)h64_sweep_grid(p) * d.N * H64_W0_COLS);
+            d.slab_b = std::max(d.slab_b, (size_t)h64_sweep_grid(p) * d.N);
+        }
+        for (int j = 0; j <= Lh; ++j) {
+            plan.dw_part[j] = c.take(plan.dw[j].slab_w);
+            plan.dw_part_b[j] = c.take(plan.dw[j].slab_b);
+        }
     }
     plan.bytes = c.off + kAlign;
     return GOPS_OK;
@@ -482,196 +430,240 @@ int run_forward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const Gops
     return ret;
 }
 
-int run_backward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const float* grad_v,
-                 const GopsMlpGrad& grad, float* g_head_pre, void* ws, size_t ws_bytes, hipStream_t s,
-                 const float* ext_delta = nullptr, const GopsRolloutAdjoint* adj = nullptr, bool want_params = true,
-                 const GopsUpdateTail* tail = nullptr) {
-    if (!desc.need_grad || grad_v == nullptr) return GOPS_ERR_BAD_ARG;
-    Plan plan;
-    int rc = build_plan(desc, ws, plan);
-    if (rc != GOPS_OK) return rc;
-    if (ws == nullptr || ws_bytes < plan.bytes) return GOPS_ERR_WORKSPACE;
-    RolloutParams& p = plan.p;
-    p.in = in;
-    p.grad_v = grad_v;
-    p.g_head_pre = g_head_pre;
-    if ((p.open_loop != 0) != (g_head_pre != nullptr)) return GOPS_ERR_BAD_ARG;
-    if (p.open_loop && in.head_pre == nullptr) return GOPS_ERR_BAD_ARG;
-    p.ext_delta = ext_delta;   // gops_mlp_backward: the head is a stand-in, its gradient is not formed
-    if (ext_delta != nullptr && desc.env.kind != GOPS_ENV_NONE) return GOPS_ERR_BAD_ARG;
-    if (!p.open_loop && want_params)
-        for (int j = 0; j < p.pol.nl - (ext_delta != nullptr ? 1 : 0); ++j)
-            if (grad.weight[j] == nullptr || grad.bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
-    if (tail != nullptr) {   // gops_rollout_backward_update: checked before anything is launched
-        if (p.open_loop || !want_params || ext_delta != nullptr || adj != nullptr) return GOPS_ERR_BAD_ARG;
-        // half a backward (GOPS_VF_BWD_PHASE_A / _B: a data-parallel update all-reduces between gradient and optimizer step) can carry
-        // the LOSS MEAN on phase A's reduce launch - it needs no gradient - but never an optimizer / Polyak step
-        const unsigned ph = desc.variant_flags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B);
-        if (ph != 0 && (ph != GOPS_VF_BWD_PHASE_A || tail->adam != nullptr || tail->polyak != nullptr)) return GOPS_ERR_BAD_ARG;
-        if (tail->mean_x != nullptr && (tail->mean_stats == nullptr || tail->mean_n < 1)) return GOPS_ERR_BAD_ARG;
-        if (tail->adam != nullptr) {
-            const GopsAdamTensors& T = *tail->adam;
-            if (tail->adam_state == nullptr || T.n != 2 * p.pol.nl) return GOPS_ERR_BAD_ARG;
-            for (int j = 0; j < p.pol.nl; ++j) {   // every gradient tensor of the policy has its parameter / moments in the table
-                const long long nw = (long long)p.pol.dims[j + 1] * p.pol.dims[j], nb = p.pol.dims[j + 1];
-                int fw = -1, fb = -1;
-                for (int k = 0; k < T.n; ++k) {
-                    if (T.grad[k] == grad.weight[j] && T.numel[k] == nw) fw = k;
-                    if (T.grad[k] == grad.bias[j] && T.numel[k] == nb) fb = k;
-                }
-                if (fw < 0 || fb < 0 || !T.param[fw] || !T.exp_avg[fw] || !T.exp_avg_sq[fw] || !T.param[fb] || !T.exp_avg[fb] || !T.exp_avg_sq[fb])
-                    return GOPS_ERR_BAD_ARG;
+// What an extern "C" entry point hands to run_backward beyond the description and the workspace.
+struct BackwardCall {
+    const GopsRolloutIn* in = nullptr;
+    const float* grad_v = nullptr;
+    const GopsMlpGrad* grad = nullptr;         // parameter gradients (read when want_params)
+    bool want_params = true;
+    float* g_head_pre = nullptr;               // open loop: gradient of the raw actions
+    const float* ext_delta = nullptr;          // gops_mlp_backward: the head is a stand-in, its gradient is not formed
+    const GopsRolloutAdjoint* adj = nullptr;   // gops_rollout_backward_adj / gops_mlp_backward_x
+    const GopsUpdateTail* tail = nullptr;      // gops_rollout_backward_update
+};
+
+// GOPS_VF_BWD_PHASE_A / _B: the call is one half of a backward (see gops_hip.h) - phase A: sweep and every layer but 0,
+// phase B: no sweep, layer 0 (both bits: a whole backward)
+struct Phase {
+    bool only_a, only_b;
+    explicit Phase(unsigned vflags)
+        : only_a((vflags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B)) == GOPS_VF_BWD_PHASE_A),
+          only_b((vflags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B)) == GOPS_VF_BWD_PHASE_B) {}
+};
+
+// gops_rollout_backward_update's tail
+int check_update_tail(const GopsRolloutDesc& desc, const RolloutParams& p, const BackwardCall& c) {
+    const GopsUpdateTail* tail = c.tail;
+    if (p.open_loop || !c.want_params || c.ext_delta != nullptr || c.adj != nullptr) return GOPS_ERR_BAD_ARG;
+    // half a backward (GOPS_VF_BWD_PHASE_A / _B: a data-parallel update all-reduces between gradient and optimizer step) can carry
+    // the LOSS MEAN on phase A's reduce launch - it needs no gradient - but never an optimizer / Polyak step
+    const unsigned ph = desc.variant_flags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B);
+    if (ph != 0 && (ph != GOPS_VF_BWD_PHASE_A || tail->adam != nullptr || tail->polyak != nullptr)) return GOPS_ERR_BAD_ARG;
+    if (tail->mean_x != nullptr && (tail->mean_stats == nullptr || tail->mean_n < 1)) return GOPS_ERR_BAD_ARG;
+    if (tail->adam != nullptr) {
+        const GopsAdamTensors& T = *tail->adam;
+        if (tail->adam_state == nullptr || T.n != 2 * p.pol.nl) return GOPS_ERR_BAD_ARG;
+        for (int j = 0; j < p.pol.nl; ++j) {   // every gradient tensor of the policy has its parameter / moments in the table
+            const long long nw = (long long)p.pol.dims[j + 1] * p.pol.dims[j], nb = p.pol.dims[j + 1];
+            int fw = -1, fb = -1;
+            for (int k = 0; k < T.n; ++k) {
+                if (T.grad[k] == c.grad->weight[j] && T.numel[k] == nw) fw = k;
+                if (T.grad[k] == c.grad->bias[j] && T.numel[k] == nb) fb = k;
             }
-        }
-        if (tail->polyak != nullptr) {   // every online tensor of the averaging table is a parameter this call steps
-            if (tail->adam == nullptr || tail->polyak->n != tail->adam->n) return GOPS_ERR_BAD_ARG;
-            for (int k = 0; k < tail->polyak->n; ++k) {
-                bool found = false;
-                for (int i = 0; i < tail->adam->n; ++i)
-                    found = found || (tail->polyak->grad[k] == tail->adam->param[i] && tail->polyak->numel[k] == tail->adam->numel[i]);
-                if (!found || tail->polyak->param[k] == nullptr) return GOPS_ERR_BAD_ARG;
-            }
+            if (fw < 0 || fb < 0 || !T.param[fw] || !T.exp_avg[fw] || !T.exp_avg_sq[fw] || !T.param[fb] || !T.exp_avg[fb] || !T.exp_avg_sq[fb])
+                return GOPS_ERR_BAD_ARG;
         }
     }
-    hipError_t e;
-    // ActionRepeatModel, gops_rollout_backward_adj / gops_mlp_backward_x: the general (EXT) instantiations of the sweep
-    const SweepCall call{desc.env.repeat_num > 1 || adj != nullptr, ext_delta != nullptr, want_params};
-    if (adj != nullptr && (p.tail || p.f16)) return GOPS_ERR_UNSUPPORTED;   // (open loop: gops_rollout_backward_open_loop_adj)
-    KernelChoice& sweep = plan.choice.bwd;
-    if (!choose_sweep(p, plan.choice, call, sweep)) return GOPS_ERR_UNSUPPORTED;
-    p.ext = call.ext;
-    if (adj != nullptr) {
-        p.adj_gfo = adj->grad_final_obs;
-        p.adj_gobs = adj->grad_obs;
-        p.adj_first_only = (adj->first_step_only != 0 && p.H > 1) ? 1 : 0;
-        if (p.adj_first_only && want_params) {   // the sweep writes the step-0 deltas only: the rest of the stash is zero
-            const size_t S0 = (size_t)tiles(p) * TB * p.H;
-            for (int j = 1; j < p.pol.nl; ++j)
-                if ((e = launch_fill_zero(p.st.d[j], S0 * p.pol.dims[j], s)) != hipSuccess) return (int)e;
-            if ((e = launch_fill_zero(p.st.dy, S0 * 4, s)) != hipSuccess) return (int)e;
+    if (tail->polyak != nullptr) {   // every online tensor of the averaging table is a parameter this call steps
+        if (tail->adam == nullptr || tail->polyak->n != tail->adam->n) return GOPS_ERR_BAD_ARG;
+        for (int k = 0; k < tail->polyak->n; ++k) {
+            bool found = false;
+            for (int i = 0; i < tail->adam->n; ++i)
+                found = found || (tail->polyak->grad[k] == tail->adam->param[i] && tail->polyak->numel[k] == tail->adam->numel[i]);
+            if (!found || tail->polyak->param[k] == nullptr) return GOPS_ERR_BAD_ARG;
         }
+    }
+    return GOPS_OK;
+}
+
+// Everything about a call that can be refused without knowing its kernels: checked before anything is launched
+int check_backward_call(const GopsRolloutDesc& desc, const RolloutParams& p, const BackwardCall& c) {
+    if ((p.open_loop != 0) != (c.g_head_pre != nullptr)) return GOPS_ERR_BAD_ARG;
+    if (p.open_loop && c.in->head_pre == nullptr) return GOPS_ERR_BAD_ARG;
+    if (c.ext_delta != nullptr && desc.env.kind != GOPS_ENV_NONE) return GOPS_ERR_BAD_ARG;
+    if (!p.open_loop && c.want_params)
+        for (int j = 0; j < p.pol.nl - (c.ext_delta != nullptr ? 1 : 0); ++j)
+            if (c.grad->weight[j] == nullptr || c.grad->bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
+    int rc = GOPS_OK;
+    if (c.tail != nullptr && (rc = check_update_tail(desc, p, c)) != GOPS_OK) return rc;
+    if (c.adj != nullptr && (p.tail || p.f16)) return GOPS_ERR_UNSUPPORTED;   // (open loop: gops_rollout_backward_open_loop_adj)
+    const Phase ph(p.vflags);
+    if ((ph.only_a || ph.only_b) && (p.open_loop || !c.want_params || c.ext_delta != nullptr || c.adj != nullptr)) return GOPS_ERR_UNSUPPORTED;
+    return GOPS_OK;
+}
+
+// Which kernel forms each layer's weight gradient in this call (plan.dw: dw_plan.h).  false: a sweep would write more slabs
+// than the carve holds.
+bool choose_dw_stage(Plan& plan, const BackwardCall& c, const SweepCall& call) {
+    const RolloutParams& p = plan.p;
+    const KernelChoice& sweep = plan.choice.bwd;
+    if (p.open_loop || !c.want_params) return true;   // no parameters behind the rollout / none wanted: no layer takes part
+    const Phase ph(p.vflags);
+    const int L = p.pol.nl - 1;
+    const bool own_sweep = c.adj == nullptr && c.ext_delta == nullptr;
+    // Two-half-plane weight-gradient GEMM: its delta scale is derived from max|grad_v|, which bounds the deltas only when
+    // grad_v is the sweep's one gradient source - a terminal observation adjoint or constraint-sum gradients can be orders of
+    // magnitude larger, so those launches keep the exact three-plane product.  The penalty model's constraint outputs carry
+    // no gradient (gops_hip.h): its seeds are not a gradient source, and must not change the result.
+    const bool cstr_seeds = !(p.env.kind == GOPS_ENV_VEH3DOF_SURR && p.env.surr_penalty) &&
+                            (c.in->grad_constraint != nullptr || c.in->grad_constraint_prod != nullptr || c.in->grad_constraint_step != nullptr);
+    const bool scaled = own_sweep && !cstr_seeds;
+    for (int j = 0; j < L; ++j) {   // dW_j = D_{j+1}^T * (j == 0 ? X : H_j)
+        if ((ph.only_a && j == 0) || (ph.only_b && j != 0)) continue;   // (two-phase backward: layer 0 is phase B)
+        if (j == 0 && plan.choice.fuse_dw0 && own_sweep && !(p.vflags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B))) {
+            // formed inside the 64-row sweep, one slab [N][H64_W0_COLS] per workgroup (h64_can_fuse_dw0: K <= H64_W0_COLS)
+            if (!choose_dw_in_sweep(plan.dw[0], sweep.grid, H64_W0_COLS)) return false;
+        } else {
+            choose_dw_gemm(plan.dw[j], p.f16 != 0, scaled, p.vflags);
+        }
+    }
+    if (c.ext_delta == nullptr && !ph.only_b) {
+        // Split sweep: the output layer's weight gradient is accumulated inside the sweep (one partial [A][K] per workgroup) - no
+        // dw_out pass.  (GELU: the sweep's act' operand is gelu'(z), so it fetches H_2 next to it.)  The streamed-split sweep does
+        // the same for the env kinds whose instantiation has the registers (ssb_fuse_kind).
+        if (!sweep_fuses_out(sweep, call)) choose_dw_out(plan.dw[L], p.f16 != 0);
+        else if (!choose_dw_in_sweep(plan.dw[L], sweep.grid, plan.dw[L].K)) return false;
+    }
+    return true;
+}
+
+// What this call adds to the forward's device copy of the parameter block travels as a kernel argument (BwdPatch); only the
+// half sweep, which needs max|grad_v| before it starts, still takes the upload launch - so the host copy `p` gets the same.
+void fill_patch(Plan& plan, const BackwardCall& c, const SweepCall& call, BwdPatch& q) {
+    RolloutParams& p = plan.p;
+    const int L = p.pol.nl - 1;
+    p.in = *c.in;
+    p.grad_v = c.grad_v;
+    p.g_head_pre = c.g_head_pre;
+    p.ext_delta = c.ext_delta;
+    p.ext = call.ext;
+    if (c.adj != nullptr) {
+        p.adj_gfo = c.adj->grad_final_obs;
+        p.adj_gobs = c.adj->grad_obs;
+        p.adj_first_only = (c.adj->first_step_only != 0 && p.H > 1) ? 1 : 0;
     }
     p.dbg = dbg_timing_buffer(1);
-    // Split sweep: the output layer's weight gradient is accumulated inside the sweep (one partial per workgroup) - no dw_out
-    // pass.  (GELU: the sweep's act' operand is gelu'(z), so it fetches H_2 next to it.)
-    // (the streamed-split sweep does the same for the env kinds whose instantiation has the registers: ssb_fuse_kind)
-    const bool fused_out = sweep_fuses_out(sweep, call);
-    if (fused_out) {
-        p.sp.out_part = plan.dw_part[p.pol.nl - 1];
-        p.sp.out_part_b = plan.dw_part_b[p.pol.nl - 1];
+    if (sweep_fuses_out(plan.choice.bwd, call)) {
+        p.sp.out_part = plan.dw_part[L];
+        p.sp.out_part_b = plan.dw_part_b[L];
     }
-    // What this call adds to the forward's device copy of the parameter block travels as a kernel argument (BwdPatch);
-    // only the half sweep, which needs max|grad_v| before it starts, still takes the upload launch.
-    BwdPatch q;
     memset(&q, 0, sizeof(q));
-    q.in = in;
-    q.grad_v = grad_v;
-    q.g_head_pre = g_head_pre;
-    q.ext_delta = ext_delta;
+    q.in = *c.in;
+    q.grad_v = c.grad_v;
+    q.g_head_pre = c.g_head_pre;
+    q.ext_delta = c.ext_delta;
     q.adj_gfo = p.adj_gfo;
     q.adj_gobs = p.adj_gobs;
     q.adj_first_only = p.adj_first_only;
     q.out_part = p.sp.out_part;
     q.out_part_b = p.sp.out_part_b;
     q.dbg = p.dbg;
-    const bool fuse_dw0 = plan.choice.fuse_dw0 && want_params && ext_delta == nullptr && adj == nullptr &&
-                          !(p.vflags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B));
-    if (fuse_dw0) {
+    if (plan.dw[0].kernel == DwKernel::InSweep) {
         q.w0_part = plan.dw_part[0];
         q.w0_part_b = plan.dw_part_b[0];
     }
-    if (tail != nullptr && tail->adam != nullptr) {   // the sweep's thread 0 advances the optimizer state and leaves this step's factors
-        q.ad_st = tail->adam_state;
+    if (c.tail != nullptr && c.tail->adam != nullptr) {   // the sweep's thread 0 advances the optimizer state and leaves this step's factors
+        q.ad_st = c.tail->adam_state;
         q.ad_snap = p.gscale + 4;
-        q.ad_b1 = tail->beta1; q.ad_b2 = tail->beta2;
+        q.ad_b1 = c.tail->beta1; q.ad_b2 = c.tail->beta2;
     }
-    // GOPS_VF_BWD_PHASE_A / _B: the call is one half of a backward (see gops_hip.h); only_b skips the sweep
-    const unsigned phase = p.vflags & (GOPS_VF_BWD_PHASE_A | GOPS_VF_BWD_PHASE_B);
-    const bool only_a = phase == GOPS_VF_BWD_PHASE_A, only_b = phase == GOPS_VF_BWD_PHASE_B;
-    if ((only_a || only_b) && (p.open_loop || !want_params || ext_delta != nullptr || adj != nullptr)) return GOPS_ERR_UNSUPPORTED;
-    if (!only_b) {
+}
+
+hipError_t launch_sweep(const GopsRolloutDesc& desc, const Plan& plan, const BackwardCall& c, const BwdPatch& q, hipStream_t s) {
+    const RolloutParams& p = plan.p;
+    hipError_t e;
+    if (p.adj_first_only && c.want_params) {   // the sweep writes the step-0 deltas only: the rest of the stash is zero
+        const size_t S0 = (size_t)tiles(p) * TB * p.H;
+        for (int j = 1; j < p.pol.nl; ++j)
+            if ((e = launch_fill_zero(p.st.d[j], S0 * p.pol.dims[j], s)) != hipSuccess) return e;
+        if ((e = launch_fill_zero(p.st.dy, S0 * 4, s)) != hipSuccess) return e;
+    }
+    if (Phase(p.vflags).only_b) return hipSuccess;   // the sweep ran in phase A
+    if (p.f16 && (e = launch_upload_params(p, plan.dev_params, s)) != hipSuccess) return e;
+    ProfScope scope(desc.env.kind == GOPS_ENV_NONE ? 4 : 1, s);
+    return launch_rollout_bwd(p, plan.choice.bwd, plan.dev_params, q, s);
+}
+
+// One layer of the weight-gradient stage: its GEMM (none when the sweep formed the slabs) and its two reduce jobs
+hipError_t launch_dw_layer(const DwLayer& d, const void* D, const void* X, float* part, float* part_b, const float* dscale, int rows,
+                           float* gw, float* gb, ReduceJobs& jobs, hipStream_t s) {
+    const hipError_t e = launch_dw(d, D, X, part, part_b, dscale, s);
+    if (e == hipSuccess) add_reduce_jobs(jobs, d, part, part_b, rows, gw, gb);
+    return e;
+}
+
+// The update's tail rides on the reduce: Adam per gradient element, the loss mean in one more block
+void attach_update_tail(ReduceJobs& jobs, const GopsUpdateTail& tail, const RolloutParams& p) {
+    if (tail.adam != nullptr) {
+        const GopsAdamTensors& T = *tail.adam;
+        for (int i = 0; i < jobs.n; ++i)
+            for (int k = 0; k < T.n; ++k)
+                if (T.grad[k] == jobs.out[i]) { jobs.ad_p[i] = T.param[k]; jobs.ad_m[i] = T.exp_avg[k]; jobs.ad_v[i] = T.exp_avg_sq[k]; }
+        jobs.ad_snap = p.gscale + 4;
+        jobs.ad_skipped = &tail.adam_state->skipped_nonfinite;
+        jobs.ad_b1 = tail.beta1; jobs.ad_b2 = tail.beta2; jobs.ad_eps = (float)tail.eps;
+        if (tail.polyak != nullptr) {
+            for (int i = 0; i < jobs.n; ++i)
+                for (int k = 0; k < tail.polyak->n; ++k)
+                    if (jobs.ad_p[i] != nullptr && tail.polyak->grad[k] == jobs.ad_p[i]) jobs.pk_t[i] = tail.polyak->param[k];
+            jobs.pk_omt = (float)(1.0 - tail.polyak_tau);
+            jobs.pk_tau = (float)tail.polyak_tau;
+        }
+    }
+    if (tail.mean_x != nullptr) {
+        jobs.mean_x = tail.mean_x; jobs.mean_n = tail.mean_n; jobs.mean_sc = (float)tail.mean_scale; jobs.mean_stats = tail.mean_stats;
+    }
+}
+
+int run_backward(const GopsRolloutDesc& desc, const BackwardCall& c, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (!desc.need_grad || c.grad_v == nullptr) return GOPS_ERR_BAD_ARG;
+    Plan plan;
+    int rc = build_plan(desc, ws, plan);
+    if (rc != GOPS_OK) return rc;
+    if (ws == nullptr || ws_bytes < plan.bytes) return GOPS_ERR_WORKSPACE;
+    const RolloutParams& p = plan.p;
+    if ((rc = check_backward_call(desc, p, c)) != GOPS_OK) return rc;
+    // ActionRepeatModel, gops_rollout_backward_adj / gops_mlp_backward_x: the general (EXT) instantiations of the sweep
+    const SweepCall call{desc.env.repeat_num > 1 || c.adj != nullptr, c.ext_delta != nullptr, c.want_params};
+    if (!choose_sweep(p, plan.choice, call, plan.choice.bwd) || !choose_dw_stage(plan, c, call)) return GOPS_ERR_UNSUPPORTED;
+    BwdPatch q;
+    fill_patch(plan, c, call, q);
+    hipError_t e;
+    if ((e = launch_sweep(desc, plan, c, q, s)) != hipSuccess) return (int)e;
+    dbg_print_backward(p);
     // max|grad_v| belongs to THIS backward call: the sweep (fp32) / the upload kernel (half) only ever raise gscale[0], so a
     // second backward after the same forward with a much smaller grad_v would inherit the larger scale and push its scaled
     // deltas into half subnormals (advisor finding, round 3).  Invariant: gscale[0] is ZERO when a backward call starts - the
     // forward's prologue zeroes it, and every backward call leaves it zero behind its last reader: fp32 calls that end with the
     // split-K reduce reset it there (ReduceJobs.reset: no extra launch - round 5; it was a 1-block fill in front of every sweep),
     // the others (half precision: the reduce itself reads it; open loop / no parameter gradients: no reduce) with a fill at their end.
-    if (p.f16 && (e = launch_upload_params(p, plan.dev_params, s)) != hipSuccess) return (int)e;
-    {
-        ProfScope scope(desc.env.kind == GOPS_ENV_NONE ? 4 : 1, s);
-        if ((e = launch_rollout_bwd(p, sweep, plan.dev_params, q, s)) != hipSuccess) return (int)e;
-    }
-    }   // !only_b
-    dbg_print_backward(p);
-    if (p.open_loop || !want_params)   // no parameters behind the rollout / none wanted: no reduce - gscale is reset here
-        return (int)launch_fill_zero(p.gscale, 4, s);
+    if (p.open_loop || !c.want_params) return (int)launch_fill_zero(p.gscale, 4, s);
     ProfScope scope(desc.env.kind == GOPS_ENV_NONE ? 5 : 2, s);
-    const int tile_rows = p.h64 ? 64 : TB;
-    const long long S = (long long)((p.B + tile_rows - 1) / tile_rows) * tile_rows * p.H;
-    const int L = p.pol.nl - 1;
     ReduceJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     if (p.f16) jobs.unscale = p.gscale;   // the sweep ran on gradients scaled by f16_grad_scale(max|grad_v|)
     else jobs.poison = reinterpret_cast<const unsigned*>(p.gscale) + 3;   // (set by a plane-split forward / sweep whose conversions overflowed)
-    // Two-half-plane weight-gradient GEMM (launch_dw_gemm): its delta scale is derived from max|grad_v|, which bounds the
-    // deltas only when grad_v is the sweep's one gradient source - a terminal observation adjoint or constraint-sum
-    // gradients can be orders of magnitude larger, so those launches keep the exact three-plane product.  The penalty model's
-    // constraint outputs carry no gradient (gops_hip.h): its seeds are not a gradient source, and must not change the result.
-    const bool cstr_seeds = !(p.env.kind == GOPS_ENV_VEH3DOF_SURR && p.env.surr_penalty) &&
-                            (in.grad_constraint != nullptr || in.grad_constraint_prod != nullptr || in.grad_constraint_step != nullptr);
-    const float* dw_scale = (adj == nullptr && !cstr_seeds && ext_delta == nullptr)
-                                ? p.gscale : nullptr;
-    for (int j = 0; j < L; ++j) {   // dW_j = D_{j+1}^T * (j == 0 ? X : H_j)
-        if ((only_a && j == 0) || (only_b && j != 0)) continue;   // (two-phase backward: layer 0 is phase B)
-        const int N = p.pol.dims[j + 1], Kp = p.f16 ? p.pol.kp32[j] : p.pol.kp[j], K = p.pol.dims[j];
-        const DwPlan d = plan_dw(N, Kp, S, p.f16 != 0, p.dw_wgs);
-        const float* X = (j == 0) ? p.st.x : p.st.h[j];
-        if (j == 0 && fuse_dw0) {   // formed inside the 64-row sweep: one slab per workgroup
-            reduce_jobs_add(jobs, plan.dw_part[0], h64_sweep_grid(p), N, K, 8, grad.weight[0]);
-            reduce_jobs_add(jobs, plan.dw_part_b[0], h64_sweep_grid(p), 1, N, N, grad.bias[0]);
-            continue;
-        }
-        if (p.f16) {
-            if ((e = launch_dw_gemm_f16(p.st.d[j + 1], N, X, Kp, S, d.splits, d.chunks_per_split, plan.dw_part[j],
-                                        plan.dw_part_b[j], s)) != hipSuccess) return (int)e;
-        } else
-        if ((e = launch_dw_gemm(p.st.d[j + 1], N, X, Kp, S, d.splits, d.chunks_per_split, plan.dw_part[j],
-                                plan.dw_part_b[j], d.big, s, dw_scale, p.vflags)) != hipSuccess) return (int)e;
-        reduce_jobs_add(jobs, plan.dw_part[j], d.splits, N, K, Kp, grad.weight[j]);
-        reduce_jobs_add(jobs, plan.dw_part_b[j], d.splits, 1, N, N, grad.bias[j]);
-    }
-    if (ext_delta == nullptr && !only_b) {
-        const int K = p.pol.dims[L], A = p.pol.dims[p.pol.nl];
-        long long splits = fused_out ? sweep.grid : DW_OUT_SPLITS;   // (one slab per workgroup of the sweep)
-        if (splits > S) splits = S;
-        if (!fused_out)
-        if ((e = launch_dw_out(p.st.dy, p.st.h[L], p.f16 != 0, K, A, S, (int)splits, plan.dw_part[L], plan.dw_part_b[L], s)) != hipSuccess) return (int)e;
-        reduce_jobs_add(jobs, plan.dw_part[L], (int)splits, A, K, K, grad.weight[L]);
-        reduce_jobs_add(jobs, plan.dw_part_b[L], (int)splits, 1, A, A, grad.bias[L]);
+    const int L = p.pol.nl - 1;
+    for (int j = 0; j <= L; ++j) {
+        const DwLayer& d = plan.dw[j];
+        if (d.kernel == DwKernel::None) continue;
+        if ((e = launch_dw_layer(d, j < L ? p.st.d[j + 1] : p.st.dy, j == 0 ? p.st.x : p.st.h[j], plan.dw_part[j], plan.dw_part_b[j], p.gscale,
+                                 d.N, c.grad->weight[j], c.grad->bias[j], jobs, s)) != hipSuccess) return (int)e;
     }
     // (two-phase backward: phase B's GEMM still reads the scale phase A's sweep left - the reset belongs to the LAST reduce of the call pair)
+    const bool only_a = Phase(p.vflags).only_a;
     if (!p.f16 && !only_a && jobs.n > 0) jobs.reset = p.gscale;
-    if (tail != nullptr) {   // the update's tail rides on the reduce: Adam per gradient element, the loss mean in one more block
-        if (tail->adam != nullptr) {
-            const GopsAdamTensors& T = *tail->adam;
-            for (int i = 0; i < jobs.n; ++i)
-                for (int k = 0; k < T.n; ++k)
-                    if (T.grad[k] == jobs.out[i]) { jobs.ad_p[i] = T.param[k]; jobs.ad_m[i] = T.exp_avg[k]; jobs.ad_v[i] = T.exp_avg_sq[k]; }
-            jobs.ad_snap = p.gscale + 4;
-            jobs.ad_skipped = &tail->adam_state->skipped_nonfinite;
-            jobs.ad_b1 = tail->beta1; jobs.ad_b2 = tail->beta2; jobs.ad_eps = (float)tail->eps;
-            if (tail->polyak != nullptr) {
-                for (int i = 0; i < jobs.n; ++i)
-                    for (int k = 0; k < tail->polyak->n; ++k)
-                        if (jobs.ad_p[i] != nullptr && tail->polyak->grad[k] == jobs.ad_p[i]) jobs.pk_t[i] = tail->polyak->param[k];
-                jobs.pk_omt = (float)(1.0 - tail->polyak_tau);
-                jobs.pk_tau = (float)tail->polyak_tau;
-            }
-        }
-        if (tail->mean_x != nullptr) {
-            jobs.mean_x = tail->mean_x; jobs.mean_n = tail->mean_n; jobs.mean_sc = (float)tail->mean_scale; jobs.mean_stats = tail->mean_stats;
-        }
-    }
+    if (c.tail != nullptr) attach_update_tail(jobs, *c.tail, p);
     if ((e = launch_reduce(jobs, s)) != hipSuccess) return (int)e;
     if ((p.f16 || jobs.n == 0) && !only_a && (e = launch_fill_zero(p.gscale, 4, s)) != hipSuccess) return (int)e;
     return GOPS_OK;
@@ -704,6 +696,7 @@ struct MlpPlan {
     float* gyp = nullptr;     // [S][Wp] zero-padded copy of grad_y (delta operand of the output layer's dW GEMM)
     float* part = nullptr;    // split-K slabs of the output layer [splits][Wp][K]
     float* part_b = nullptr;  // [splits][Wp]
+    DwLayer out;              // the output layer's weight-gradient GEMM (dw_plan.h)
     int K = 0, W = 0, Wp = 0;
     long long S = 0;
     size_t bytes = 0;
@@ -733,9 +726,9 @@ int plan_mlp(const GopsMlp& mlp, int batch, void* ws, MlpPlan& m) {
     m.gv = c.take((size_t)batch);
     m.gh = c.take((size_t)m.S * m.K);
     m.gyp = c.take((size_t)m.S * m.Wp);
-    const DwPlan d = plan_dw(m.Wp, m.K, m.S);
-    m.part = c.take((size_t)d.splits * m.Wp * m.K);
-    m.part_b = c.take((size_t)d.splits * m.Wp);
+    m.out = plan_dw(m.Wp, m.K, m.K, m.S, false, 0);   // (dw_workgroups: the default)
+    m.part = c.take(m.out.slab_w);
+    m.part_b = c.take(m.out.slab_b);
     m.bytes = m.inner + c.off + kAlign;
     m.d.policy.weight[mlp.n_layers - 1] = m.zeros;
     m.d.policy.bias[mlp.n_layers - 1] = m.zeros ? m.zeros + m.K : nullptr;
@@ -792,27 +785,24 @@ static int mlp_backward_impl(const GopsMlp* mlp, int32_t batch, const float* x, 
     Plan inner;
     build_plan(m.d, workspace, inner);
     if (grad) {
-        const DwPlan d = plan_dw(m.Wp, m.K, m.S);
-        if ((e = launch_dw_gemm(m.gyp, m.Wp, inner.p.st.h[L], m.K, m.S, d.splits, d.chunks_per_split, m.part, m.part_b, d.big, s, nullptr,
-                                mlp->variant_flags)) != hipSuccess)
-            return (int)e;
+        choose_dw_gemm(m.out, false, false, mlp->variant_flags);   // (no delta scale: g_y is the caller's)
         ReduceJobs jobs;
         memset(&jobs, 0, sizeof(jobs));
-        reduce_jobs_add(jobs, m.part, d.splits, m.W, m.K, m.K, grad->weight[L], m.Wp);
-        reduce_jobs_add(jobs, m.part_b, d.splits, 1, m.W, m.Wp, grad->bias[L]);
+        if ((e = launch_dw_layer(m.out, m.gyp, inner.p.st.h[L], m.part, m.part_b, nullptr, m.W, grad->weight[L], grad->bias[L], jobs, s)) != hipSuccess)
+            return (int)e;
         if ((e = launch_reduce(jobs, s)) != hipSuccess) return (int)e;
     }
     // hidden stack: the sweep starts from g_h instead of a head
     GopsRolloutIn in;
     memset(&in, 0, sizeof(in));
     in.obs = x;
-    GopsMlpGrad none;
-    memset(&none, 0, sizeof(none));
     GopsRolloutAdjoint adj;
     memset(&adj, 0, sizeof(adj));
     adj.grad_obs = grad_x;
-    return run_backward(m.d, in, m.gv, grad ? *grad : none, nullptr, workspace, m.inner, s, m.gh, grad_x ? &adj : nullptr,
-                        grad != nullptr);
+    BackwardCall call;
+    call.in = &in, call.grad_v = m.gv, call.grad = grad, call.want_params = grad != nullptr;
+    call.ext_delta = m.gh, call.adj = grad_x ? &adj : nullptr;
+    return run_backward(m.d, call, workspace, m.inner, s);
 }
 
 int gops_mlp_backward(const GopsMlp* mlp, int32_t batch, const float* x, const float* grad_y, const GopsMlpGrad* grad,
@@ -887,47 +877,46 @@ int gops_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, 
                           const GopsMlpGrad* policy_grad, void* workspace, size_t workspace_bytes,
                           void* stream) {
     if (!desc || !in || !policy_grad) return GOPS_ERR_BAD_ARG;
-    return run_backward(*desc, *in, grad_v, *policy_grad, nullptr, workspace, workspace_bytes,
-                        static_cast<hipStream_t>(stream));
+    BackwardCall call;
+    call.in = in, call.grad_v = grad_v, call.grad = policy_grad;
+    return run_backward(*desc, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int gops_rollout_backward_update(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v,
                                  const GopsMlpGrad* policy_grad, const GopsUpdateTail* tail, void* workspace,
                                  size_t workspace_bytes, void* stream) {
     if (!desc || !in || !policy_grad || !tail) return GOPS_ERR_BAD_ARG;
-    return run_backward(*desc, *in, grad_v, *policy_grad, nullptr, workspace, workspace_bytes,
-                        static_cast<hipStream_t>(stream), nullptr, nullptr, true, tail);
+    BackwardCall call;
+    call.in = in, call.grad_v = grad_v, call.grad = policy_grad, call.tail = tail;
+    return run_backward(*desc, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int gops_rollout_backward_adj(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v,
                               const GopsMlpGrad* policy_grad, const GopsRolloutAdjoint* adj, void* workspace,
                               size_t workspace_bytes, void* stream) {
     if (!desc || !in || !adj) return GOPS_ERR_BAD_ARG;
-    GopsMlpGrad none;
-    memset(&none, 0, sizeof(none));
-    return run_backward(*desc, *in, grad_v, policy_grad ? *policy_grad : none, nullptr, workspace, workspace_bytes,
-                        static_cast<hipStream_t>(stream), nullptr, adj, policy_grad != nullptr);
+    BackwardCall call;
+    call.in = in, call.grad_v = grad_v, call.grad = policy_grad, call.want_params = policy_grad != nullptr, call.adj = adj;
+    return run_backward(*desc, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int gops_rollout_backward_open_loop(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v,
                                     float* grad_head_pre, void* workspace, size_t workspace_bytes, void* stream) {
     if (!desc || !in || !grad_head_pre || !desc->open_loop) return GOPS_ERR_BAD_ARG;
-    GopsMlpGrad none;
-    memset(&none, 0, sizeof(none));
-    return run_backward(*desc, *in, grad_v, none, grad_head_pre, workspace, workspace_bytes,
-                        static_cast<hipStream_t>(stream));
+    BackwardCall call;   // (want_params stays set: run_backward knows that an open loop has no parameters behind it)
+    call.in = in, call.grad_v = grad_v, call.g_head_pre = grad_head_pre;
+    return run_backward(*desc, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int gops_rollout_backward_open_loop_adj(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v,
                                         float* grad_head_pre, const GopsRolloutAdjoint* adj, void* workspace,
                                         size_t workspace_bytes, void* stream) {
     if (!desc || !in || !grad_head_pre || !adj || !desc->open_loop) return GOPS_ERR_BAD_ARG;
-    GopsMlpGrad none;
-    memset(&none, 0, sizeof(none));
     GopsRolloutAdjoint a = *adj;
     a.first_step_only = 0;
-    return run_backward(*desc, *in, grad_v, none, grad_head_pre, workspace, workspace_bytes, static_cast<hipStream_t>(stream),
-                        nullptr, &a, false);
+    BackwardCall call;
+    call.in = in, call.grad_v = grad_v, call.want_params = false, call.g_head_pre = grad_head_pre, call.adj = &a;
+    return run_backward(*desc, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int gops_env_step(const GopsEnv* env, int32_t batch, const GopsStepIO* io, void* stream) {
@@ -993,7 +982,9 @@ int gops_value_backward(const GopsMlp* value, int32_t batch, const float* obs, c
     GopsRolloutIn in;
     memset(&in, 0, sizeof(in));
     in.obs = obs;
-    return run_backward(d, in, grad_v, *grad, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    BackwardCall call;
+    call.in = &in, call.grad_v = grad_v, call.grad = grad;
+    return run_backward(d, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int gops_value_backward_update(const GopsMlp* value, int32_t batch, const float* obs, const float* grad_v,
@@ -1003,7 +994,9 @@ int gops_value_backward_update(const GopsMlp* value, int32_t batch, const float*
     GopsRolloutIn in;
     memset(&in, 0, sizeof(in));
     in.obs = obs;
-    return run_backward(d, in, grad_v, *grad, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), nullptr, nullptr, true, tail);
+    BackwardCall call;
+    call.in = &in, call.grad_v = grad_v, call.grad = grad, call.tail = tail;
+    return run_backward(d, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int gops_adam_step(const GopsAdamTensors* tensors, GopsAdamState* state_dev, double beta1, double beta2,

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include "common.h"
 #include "env_models.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------------------------------------
 // Weight packing.  For Linear layer W [N][K] (torch layout):
@@ -1261,46 +1262,6 @@ __global__ __launch_bounds__(NTHREADS, 3) void dw_skinny_kernel(const float* __r
         }
     }
 }
-// The layers the 16-input kernel takes
-bool dw_skinny_ok(int N, int Kp) { return Kp == 16 && (N % 16) == 0; }
-
-// The layers the wave-specialised kernel takes (the others of the two-half-plane GEMM: the 4-wave ring kernel)
-static bool dw_spec_ok(int N, int Kp) { return (N % 256) == 0 && ((Kp % 128) == 0 || (Kp > 128 && (Kp % 16) == 0)); }
-
-// dscale: device pointer to max|grad_v| of the launch (the deltas' magnitude reference), or null: with it the large
-// layers run the two-half-plane products (22 significant bits per operand), without it - or with GOPS_DW_EXACT set -
-// the exact three-plane bf16 split.
-hipError_t launch_dw_gemm(const float* D, int N, const float* X, int Kp, long long S, int splits,
-                          int chunks_per_split, float* part, float* part_b, bool big, hipStream_t s, const float* dscale, unsigned vflags) {
-    const bool force_f32 = (vflags & GOPS_VF_DW_F32) != 0;       // A/B knob: fp32 MFMA GEMM
-    const bool force_exact = (vflags & GOPS_VF_DW_EXACT) != 0;
-    const bool no_guard = (vflags & GOPS_VF_DW_NO_GUARD) != 0;   // test knob: skip the exact re-run behind a saturated launch
-    const long long Q = (S + TB - 1) / TB;
-    const int T = big ? 128 : 64, tiles = ((N + T - 1) / T) * ((Kp + T - 1) / T);
-    const dim3 grid(tiles * ((splits + 7) / 8) * 8), block(NTHREADS);
-    if (big && !force_f32 && (N % 128) == 0 && ((Kp % 128) == 0 || (Kp > 128 && (Kp % 16) == 0))) {
-        const float* none = nullptr;
-        if (dscale != nullptr && !force_exact && dw_spec_ok(N, Kp)) {
-            const dim3 grids(((N / 256) * ((Kp + 127) / 128)) * ((splits + 7) / 8) * 8);
-            launch_with_lds(dw_gemm_spec_kernel, grids, dim3(512), DwSpec::lds_bytes(), s, D, N, X, Kp, Q, splits, part, part_b, dscale,
-                            no_guard ? 0 : 1);
-        } else if (dscale != nullptr && !force_exact) {
-            launch_with_lds(dw_gemm_ring_kernel<true>, grid, block, (size_t)DWR_STAGES * DWR_STAGE_FLOATS * sizeof(float) + 16, s, D, N, X, Kp, Q,
-                            splits, chunks_per_split, part, part_b, dscale, no_guard ? 0 : 1);
-        } else {
-            launch_with_lds(dw_gemm_ring_kernel<false>, grid, block, (size_t)DWR_STAGES * DWR_STAGE_FLOATS * sizeof(float), s, D, N, X, Kp, Q,
-                            splits, chunks_per_split, part, part_b, none, 1);
-        }
-    }
-    else if (!force_f32 && dw_skinny_ok(N, Kp))
-        hipLaunchKernelGGL(dw_skinny_kernel, dim3(((N + 255) / 256) * ((splits + 7) / 8) * 8), block, 0, s, D, N, X, Q, splits, part, part_b);
-    else if (big && !force_f32) hipLaunchKernelGGL((dw_gemm_fm_kernel<4, true>), grid, block, 0, s, D, N, X, Kp, Q, splits, chunks_per_split, part, part_b);
-    else if (big) hipLaunchKernelGGL((dw_gemm_fm_kernel<4, false>), grid, block, 0, s, D, N, X, Kp, Q, splits, chunks_per_split, part, part_b);
-    else if (!force_f32) hipLaunchKernelGGL((dw_gemm_fm_kernel<2, true>), grid, block, 0, s, D, N, X, Kp, Q, splits, chunks_per_split, part, part_b);
-    else hipLaunchKernelGGL((dw_gemm_fm_kernel<2, false>), grid, block, 0, s, D, N, X, Kp, Q, splits, chunks_per_split, part, part_b);
-    return hipGetLastError();
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // dW GEMM, half-precision operands (GOPS_DTYPE_F16):  part[split][n][k] = sum_s D[s][n] * X[s][k] with D, X
@@ -1312,7 +1273,6 @@ hipError_t launch_dw_gemm(const float* D, int N, const float* X, int Kp, long lo
 // writes [g = s/8][column][8 samples] fragments (ds_write_b64); a lane's MFMA fragment is one ds_read_b128.
 // 16-byte units are XOR-swizzled (column ^ (column >> 3 & 7)) so that both directions are conflict-free.
 // ---------------------------------------------------------------------------------------------
-#define DWH_SC 64                       // samples per staged chunk
 #define DWH_T 128                       // tile edge
 #define DWH_PLANE (8 * DWH_T * 8)       // halfs per operand: [8 g][128 cols][8 samples]
 
@@ -1435,15 +1395,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void dw_gemm_f16_kernel(const _Float16
     }
 }
 
-hipError_t launch_dw_gemm_f16(const void* D, int N, const void* X, int Kp, long long S, int splits,
-                              int chunks_per_split, float* part, float* part_b, hipStream_t s) {
-    const int tiles = ((N + DWH_T - 1) / DWH_T) * ((Kp + DWH_T - 1) / DWH_T);
-    hipLaunchKernelGGL(dw_gemm_f16_kernel, dim3(tiles * ((splits + 7) / 8) * 8), dim3(NTHREADS), 0, s,
-                       static_cast<const _Float16*>(D), N, static_cast<const _Float16*>(X), Kp, S, splits, chunks_per_split,
-                       part, part_b);
-    return hipGetLastError();
-}
-
 // Output layer (width A <= 4) on the VALU: part[split][a][k] = sum_s dy[s][a] * h[s][k].
 // Row-major half h (GOPS_DTYPE_F16 stash): thread = (8 columns, sample lane): one 16-byte read of h per sample, four samples
 // in flight per thread (a workgroup keeps 16 KiB of the stream in flight; the round-3 form - 8-byte reads, 8 KiB - ran at
@@ -1542,15 +1493,115 @@ __global__ __launch_bounds__(NTHREADS) void dw_out_fm_kernel(const float* __rest
     }
 }
 
-hipError_t launch_dw_out(const float* dy, const float* h, bool h_is_half, int K, int A, long long S, int splits,
-                         float* part, float* part_b, hipStream_t s) {
-    if (h_is_half) {
-        const long long per = (S + splits - 1) / splits;
-        hipLaunchKernelGGL(dw_out_h_kernel, dim3(splits), dim3(NTHREADS), 0, s, dy, reinterpret_cast<const _Float16*>(h), K, A, S, per, part,
-                           part_b);
-    } else {   // splits beyond the tile count produce zero slabs (their loops are empty)
-        const long long Q = (S + TB - 1) / TB, per = (Q + splits - 1) / splits;
-        hipLaunchKernelGGL(dw_out_fm_kernel, dim3(splits), dim3(NTHREADS), 0, s, dy, h, K, A, Q, per, part, part_b);
+// ---------------------------------------------------------------------------------------------
+// The weight-gradient stage's record (dw_plan.h): which of the kernels above forms a layer's partial slabs, on which grid.
+// ---------------------------------------------------------------------------------------------
+static_assert(DW_SC == 2 * TB, "a K-block of the fp32 dW GEMMs is two sample tiles (nblk_all = (Q + 1) >> 1)");
+static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// The layers the 16-input kernel takes
+bool dw_skinny_ok(int N, int Kp) { return Kp == 16 && (N % 16) == 0; }
+
+DwLayer plan_dw(int N, int K, int Kp, long long S, bool f16, int wg_target) {
+    DwLayer L;
+    L.N = N, L.K = K, L.Kp = Kp, L.S = S, L.ld = Kp;
+    L.tile = (f16 || (N >= 128 && Kp >= 128)) ? 128 : 64;   // (the half-precision GEMM has one tile size, DWH_T)
+    // Workgroups per split that the split count is derived from.  This is the launched grid's number but for two cases, kept as
+    // they are because another count would move the split-K summation order (and the benchmark): a layer that choose_dw_gemm
+    // gives to dw_gemm_spec_kernel is counted in 128 x 128 tiles although that kernel's are 256 x 128 (half as many workgroups
+    // as counted), and a 16-input layer is counted as the skinny kernel's even where GOPS_VF_DW_F32 moves it to 64 x 64 tiles.
+    const int counted = (!f16 && dw_skinny_ok(N, Kp)) ? cdiv(N, 256) : cdiv(N, L.tile) * cdiv(Kp, L.tile);
+    const int sc = f16 ? DWH_SC : DW_SC;
+    const long long chunks = (S + sc - 1) / sc;
+    if (wg_target < 1) wg_target = 512;
+    long long splits = (wg_target + counted - 1) / counted;
+    if (splits > chunks) splits = chunks;
+    if (splits < 1) splits = 1;
+    L.chunks_per_split = (int)((chunks + splits - 1) / splits);
+    L.splits = (int)((chunks + L.chunks_per_split - 1) / L.chunks_per_split);
+    L.slab_w = (size_t)L.splits * N * Kp;
+    L.slab_b = (size_t)L.splits * N;
+    return L;
+}
+
+DwLayer plan_dw_out(int K, int A, long long S) {
+    DwLayer L;
+    L.N = A, L.K = L.Kp = L.ld = K, L.S = S;
+    L.splits = (int)std::min<long long>(DW_OUT_SPLITS, S);
+    L.slab_w = (size_t)DW_OUT_SPLITS * GOPS_MAX_ACT * K;
+    L.slab_b = (size_t)DW_OUT_SPLITS * GOPS_MAX_ACT;
+    return L;
+}
+
+// With the delta scale the large layers run the two-half-plane products (22 significant bits per operand); without it - or
+// with GOPS_VF_DW_EXACT in the description's variant flags - the exact three-plane bf16 split.
+void choose_dw_gemm(DwLayer& L, bool f16, bool scaled, unsigned vflags) {
+    const int N = L.N, Kp = L.Kp;
+    const bool f32 = (vflags & GOPS_VF_DW_F32) != 0, big = L.tile == 128;   // (A/B knob: fp32 MFMA GEMM)
+    int tiles = cdiv(N, L.tile) * cdiv(Kp, L.tile);
+    L.block = NTHREADS, L.lds = 0;
+    L.guard = (vflags & GOPS_VF_DW_NO_GUARD) ? 0 : 1;   // (test knob: skip the exact re-run behind a saturated launch)
+    if (f16) {
+        L.kernel = DwKernel::F16;
+    } else if (!f32 && big && (N % 128) == 0 && ((Kp % 128) == 0 || (Kp > 128 && (Kp % 16) == 0))) {   // the ring kernels' shapes
+        const bool h2 = scaled && !(vflags & GOPS_VF_DW_EXACT);
+        L.kernel = !h2 ? DwKernel::RingExact : ((N % 256) == 0 ? DwKernel::Spec : DwKernel::RingH2);   // (DwSpec::TN = 256 features)
+        L.lds = (size_t)DWR_STAGES * DWR_STAGE_FLOATS * sizeof(float) + (h2 ? 16 : 0);
+        if (L.kernel == DwKernel::Spec) tiles = (N / DwSpec::TN) * cdiv(Kp, DwSpec::T), L.block = DwSpec::NT, L.lds = DwSpec::lds_bytes();
+    } else if (!f32 && dw_skinny_ok(N, Kp)) {
+        L.kernel = DwKernel::Skinny;
+        tiles = cdiv(N, 256);
+    } else {
+        L.kernel = big ? (f32 ? DwKernel::Fm4F32 : DwKernel::Fm4Bf3) : (f32 ? DwKernel::Fm2F32 : DwKernel::Fm2Bf3);
+    }
+    L.grid = tiles * cdiv(L.splits, 8) * 8;   // (XCD-aware block order: splits in groups of 8)
+}
+
+void choose_dw_out(DwLayer& L, bool f16) {
+    L.kernel = f16 ? DwKernel::OutH : DwKernel::OutFm;
+    L.grid = L.splits, L.block = NTHREADS, L.lds = 0;
+}
+
+bool choose_dw_in_sweep(DwLayer& L, int slabs, int ld) {
+    if ((size_t)slabs * L.N * ld > L.slab_w || (size_t)slabs * L.N > L.slab_b) return false;
+    L.kernel = DwKernel::InSweep;
+    L.splits = slabs, L.ld = ld;
+    L.grid = L.block = 0, L.lds = 0;
+    return true;
+}
+
+hipError_t launch_dw(const DwLayer& L, const void* Dv, const void* Xv, float* part, float* part_b, const float* dscale, hipStream_t s) {
+    const float* D = static_cast<const float*>(Dv);
+    const float* X = static_cast<const float*>(Xv);
+    const _Float16* Xh = static_cast<const _Float16*>(Xv);
+    const float* none = nullptr;
+    const dim3 grid(L.grid), block(L.block);
+    const long long Q = (L.S + TB - 1) / TB;
+    auto fm = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, D, L.N, X, L.Kp, Q, L.splits, L.chunks_per_split, part, part_b); };
+    auto ring = [&](auto kernel, const float* scale, int guard) {
+        launch_with_lds(kernel, grid, block, L.lds, s, D, L.N, X, L.Kp, Q, L.splits, L.chunks_per_split, part, part_b, scale, guard);
+    };
+    switch (L.kernel) {
+        case DwKernel::None:
+        case DwKernel::InSweep: return hipSuccess;
+        case DwKernel::Spec: launch_with_lds(dw_gemm_spec_kernel, grid, block, L.lds, s, D, L.N, X, L.Kp, Q, L.splits, part, part_b, dscale, L.guard); break;
+        case DwKernel::RingH2: ring(dw_gemm_ring_kernel<true>, dscale, L.guard); break;
+        case DwKernel::RingExact: ring(dw_gemm_ring_kernel<false>, none, 1); break;
+        case DwKernel::Skinny: hipLaunchKernelGGL(dw_skinny_kernel, grid, block, 0, s, D, L.N, X, Q, L.splits, part, part_b); break;
+        case DwKernel::Fm4Bf3: fm(dw_gemm_fm_kernel<4, true>); break;
+        case DwKernel::Fm4F32: fm(dw_gemm_fm_kernel<4, false>); break;
+        case DwKernel::Fm2Bf3: fm(dw_gemm_fm_kernel<2, true>); break;
+        case DwKernel::Fm2F32: fm(dw_gemm_fm_kernel<2, false>); break;
+        case DwKernel::F16:
+            hipLaunchKernelGGL(dw_gemm_f16_kernel, grid, block, 0, s, static_cast<const _Float16*>(Dv), L.N, Xh, L.Kp, L.S, L.splits,
+                               L.chunks_per_split, part, part_b);
+            break;
+        case DwKernel::OutH:
+            hipLaunchKernelGGL(dw_out_h_kernel, grid, block, 0, s, D, Xh, L.K, L.N, L.S, (L.S + L.splits - 1) / L.splits, part, part_b);
+            break;
+        case DwKernel::OutFm:   // splits beyond the tile count produce zero slabs (their loops are empty)
+            hipLaunchKernelGGL(dw_out_fm_kernel, grid, block, 0, s, D, X, L.K, L.N, Q, (Q + L.splits - 1) / L.splits, part, part_b);
+            break;
     }
     return hipGetLastError();
 }
@@ -1692,8 +1743,11 @@ void reduce_jobs_add(ReduceJobs& jobs, const float* part, int splits, int rows, 
     if (i == 0) jobs.block0[0] = 0;
     jobs.block0[i + 1] = jobs.block0[i] + (rows * cols + 63) / 64;
 }
+void add_reduce_jobs(ReduceJobs& jobs, const DwLayer& L, const float* part, const float* part_b, int rows, float* gw, float* gb) {
+    reduce_jobs_add(jobs, part, L.splits, rows, L.K, L.ld, gw, L.N);
+    reduce_jobs_add(jobs, part_b, L.splits, 1, rows, L.N, gb);
+}
 
-hipError_t launch_batch_loss(const float* a, const float* b, int n, float gsc, float sc0, float* grad, float* stats, hipStream_t s);
 hipError_t launch_reduce(const ReduceJobs& jobs_in, hipStream_t s) {
     if (jobs_in.n == 0) return hipSuccess;
     ReduceJobs jobs = jobs_in;

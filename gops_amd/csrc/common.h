@@ -12,8 +12,10 @@
 
 #define TB GOPS_TILE      // trajectories per workgroup tile = MFMA M
 #define NTHREADS 256      // 4 wavefronts of 64
-#define DW_SC_HOST 32     // samples per staged chunk of the dW GEMM (== DW_SC in aux_kernels.hip)
+#define DW_SC 32          // samples per K-block of the fp32 dW GEMMs: the unit split-K is counted in (aux_kernels.hip)
+#define DWH_SC 64         // ... per staged chunk of the half-precision one
 #define DW_OUT_SPLITS 1024  // sample splits of the output-layer weight gradient
+#define H64_W0_COLS 8     // policy inputs up to which the 64-row half sweep forms layer 0's weight gradient itself (rollout_h64.hip)
 #define MOB_OBS 13        // pyth_mobilerobot: observation = state columns
 // LDS "reference points" (x 4 TB floats) of the idpendulum sweeps: one [TB][5][24] parking, or - plane-split stationary sweep -
 // the two parity halves of the staged [TB][IDP_PARK] parking the forward wrote

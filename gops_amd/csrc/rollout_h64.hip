@@ -459,7 +459,6 @@ __device__ __forceinline__ void mlp_backward_h64(const MlpDev& M, WP Wo, int ldw
 // registers) 0.587 ms - the weight stream per trajectory doubles and costs more than the extra waves hide.
 constexpr int H64_BWD_RG = 4;
 // (+ the fused first-layer gradient: the policy-input rows of two steps [2][TBW][8] and the workgroup's accumulators [256][9])
-#define H64_W0_COLS 8
 size_t rollout_bwd_h64_lds_bytes(int ldx, int ldh) {
     return sizeof(float) * (size_t)(16 * H64_BWD_RG * ldx + 16 * H64_BWD_RG * 4 + 4 * ldh + ENV_LDS_FLOATS + 2 * 16 * H64_BWD_RG * H64_W0_COLS + 256 * (H64_W0_COLS + 1)) +
            sizeof(_Float16) * (size_t)(16 * H64_BWD_RG * H64_LD);

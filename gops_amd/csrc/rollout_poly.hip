@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "env_models.h"
+#include "launchers.h"
 
 #define POLY_THREADS 256
 
@@ -579,8 +580,6 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_value_bwd_kernel(const floa
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-void reduce_jobs_add(ReduceJobs& jobs, const float* part, int splits, int rows, int cols, int ld, float* out, int slab_rows = 0);
-hipError_t launch_reduce(const ReduceJobs& jobs, hipStream_t s);
 
 static int poly_blocks(int B) { return (B + POLY_THREADS - 1) / POLY_THREADS; }
 static size_t poly_align(size_t n) { return (n + 255) & ~(size_t)255; }

@@ -1437,3 +1437,46 @@ def test_rollout_plan_matches_the_recorded_table():
             bad.append((args, got, "a launchable plan"))
     assert not bad, bad[:5]
     assert sum(1 for r in rows if not r[2]) == 3
+
+
+DW_PLAN_TABLE = os.path.join(ROOT, "tests", "golden", "dw_plan_table.json")
+DW_PLAN_HIDDEN = ((32, 32), (64, 64), (48, 80), (128, 384), (256, 256), (256, 256, 256), (512, 512))
+
+
+def dw_plan_grid():
+    """Rows of the weight-gradient plan table, in its order: ("rollout", description arguments, dw_workgroups) for
+    gops_rollout_workspace_bytes - env kind x hidden shape (ragged and wide ones included) x dtype x batch x dw_workgroups -
+    then ("mlp", hidden shape, output width, batch) for gops_mlp_workspace_bytes."""
+    import itertools
+    for (env_id, P), hidden, f16, batch, wgs in itertools.product(
+            (("none", None), ("pyth_lq", None), ("pyth_veh3dofconti", 30)), DW_PLAN_HIDDEN, (0, 1), (17, 4112), (0, 64, 2048)):
+        yield "rollout", (env_id, P, hidden, 0, f16, batch, 0), wgs
+    for hidden, width, batch in itertools.product(DW_PLAN_HIDDEN, (1, 17, 256, 4096), (17, 4112)):
+        yield "mlp", hidden, width, batch
+
+
+def dw_plan_bytes(lib, row):
+    if row[0] == "rollout":
+        d = plan_desc(*row[1])
+        d.dw_workgroups = row[2]
+        return lib.gops_rollout_workspace_bytes(ctypes.byref(d))
+    _, hidden, width, batch = row
+    m = plan_desc("none", None, hidden, 0, 0, batch, 0).policy
+    m.sizes[m.n_layers] = width
+    return lib.gops_mlp_workspace_bytes(ctypes.byref(m), batch)
+
+
+def test_weight_gradient_plan_matches_the_recorded_table():
+    """The split-K partial slabs of the weight-gradient stage are part of the workspace carve: the bytes of every row of
+    dw_plan_grid() equal tests/golden/dw_plan_table.json, recorded from the commit BEFORE the stage's decisions moved into one
+    record (csrc/dw_plan.h).  The grid varies what rollout_plan_table.json does not: dw_workgroups, ragged and wide hidden
+    layers, and the output widths of gops_mlp_workspace_bytes.  0 bytes = the description is refused."""
+    import json
+    from gops_amd import hip_backend as hb
+    rows = json.load(open(DW_PLAN_TABLE))["bytes"]
+    grid = list(dw_plan_grid())
+    assert len(grid) == len(rows) == 308
+    lib = hb.lib()
+    bad = [(row, got, want) for row, want in zip(grid, rows) for got in [dw_plan_bytes(lib, row)] if got != want]
+    assert not bad, bad[:5]
+    assert sum(1 for r in rows if r > 0) >= 200
