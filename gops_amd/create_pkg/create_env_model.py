@@ -99,6 +99,65 @@ class WrappedEnvModel:
         return nobs, rew, ndone.bool(), ninfo
 
 
+class GameModelWrapper:
+    """The default wrapper chain around a zero-sum game model (env_model/_contigame.py) as RPI uses it, on the host.  Only
+    `forward` passes through the chain: ScaleAction from [min_action, max_action] onto the model's [lb_action, hb_action] - action
+    and adversary column alike - and ClipAction; ClipObservation and MaskAtDone change nothing RPI reads (it hands in done = False
+    and takes `reward` and `info["delta_state"]`).  `step`, `reset`, `best_act`, `worst_adv` and every other attribute reach the
+    bare model and see raw values, as through the reference's `ModelWrapper.__getattr__`.  An attribute ASSIGNED on this object
+    stays on it (no `__setattr__` forwarding, again as in the reference)."""
+
+    def __init__(self, model, *, action_scale: bool, clip_action: bool, min_action, max_action):
+        self.model = model
+        self.action_scale, self.clip_action = bool(action_scale), bool(clip_action)
+        if self.action_scale:
+            as_t = lambda v: torch.as_tensor(v, dtype=torch.float32, device=model.action_lower_bound.device)  # noqa: E731
+            self.min_action = torch.zeros_like(model.action_lower_bound) + as_t(min_action)
+            self.max_action = torch.zeros_like(model.action_upper_bound) + as_t(max_action)
+            self.action_lower_bound, self.action_upper_bound = self.min_action, self.max_action
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["model"], name)
+
+    @property
+    def unwrapped(self):
+        return self.model.unwrapped
+
+    def action(self, action: torch.Tensor) -> torch.Tensor:
+        low, high = self.model.action_lower_bound, self.model.action_upper_bound
+        if self.action_scale:   # scale_action.py:75-83
+            action = torch.clip(action, self.min_action, self.max_action)
+            action = low + (high - low) * ((action - self.min_action) / (self.max_action - self.min_action))
+            action = torch.clip(action, low, high)
+        if self.clip_action:    # clip_action.py:34-36
+            action = action.clip(low, high)
+        return action
+
+    def forward(self, obs, action, done, info):
+        return self.model.forward(obs, self.action(action), done, info)
+
+    def rpi_constants(self) -> np.ndarray:
+        """The whole `const float*` table of gops_rpi_evaluate except the value net's norm_matrix."""
+        c = self.model.rpi_constants()
+        c[hb.RPI_C_ACTION_SCALE], c[hb.RPI_C_CLIP_ACTION] = float(self.action_scale), float(self.clip_action)
+        if self.action_scale:
+            c[hb.RPI_C_SCALE_ACT_LOW], c[hb.RPI_C_SCALE_ACT_HIGH] = float(self.min_action[0]), float(self.max_action[0])
+            c[hb.RPI_C_SCALE_ADV_LOW], c[hb.RPI_C_SCALE_ADV_HIGH] = float(self.min_action[1]), float(self.max_action[1])
+        return c
+
+
+def _wrap_game_model(env_model, *, action_scale, clip_action, min_action, max_action, repeat_num, obs_shift, obs_scale, reward_shift,
+                     reward_scale):
+    refused = [name for name, v in (("repeat_num", repeat_num), ("obs_shift", obs_shift), ("obs_scale", obs_scale),
+                                    ("reward_shift", reward_shift), ("reward_scale", reward_scale)) if v is not None]
+    if refused:
+        raise NotImplementedError(f"{type(env_model).__name__} (an RPI game model): wrapper option(s) {', '.join(refused)} are not "
+                                  "supported - RPI runs on ScaleAction / ClipAction only")
+    if not env_model.is_adversary:
+        raise NotImplementedError(f"{type(env_model).__name__}: is_adversary=False is not supported (RPI's loss needs the adversary)")
+    return GameModelWrapper(env_model, action_scale=action_scale, clip_action=clip_action, min_action=min_action, max_action=max_action)
+
+
 def create_env_model(
     env_id: str,
     *,
@@ -120,6 +179,10 @@ def create_env_model(
     """Build the model `<env_id>_model` and apply the wrappers selected by the arguments (same
     arguments, defaults and KeyError/RuntimeError behaviour as the reference)."""
     env_model = registry.build(env_id + "_model", **kwargs, device="cuda" if kwargs.get("use_gpu", False) else "cpu")
+    if getattr(env_model, "rpi_kind", 0):   # the zero-sum game models of RPI: a host chain of their own, outside the rollout kernels
+        return _wrap_game_model(env_model, action_scale=action_scale, clip_action=clip_action, min_action=min_action,
+                                max_action=max_action, repeat_num=repeat_num, obs_shift=obs_shift, obs_scale=obs_scale,
+                                reward_shift=reward_shift, reward_scale=reward_scale)
 
     # wrapper options outside the fused kernels' contract are refused, never silently ignored
     if repeat_num is not None:   # ActionRepeatModel: in the kernels of the models whose observation is the state

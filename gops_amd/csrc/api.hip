@@ -846,6 +846,15 @@ int gops_poly_value_backward(const GopsMlp* value, int32_t batch, const float* o
     return poly_value_backward(*value, batch, obs, grad_v, *grad, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_rpi_state_bytes(int32_t env_kind, int32_t batch) { return rpi_state_bytes(env_kind, batch); }
+
+int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const float* consts, float* weights,
+                      const float* target_weights, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
+                      double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream) {
+    return rpi_evaluate(env_kind, batch, max_steps, consts, weights, target_weights, max_step, reset_pool, state, state_bytes, lr,
+                        beta1, beta2, eps, result, trace, static_cast<hipStream_t>(stream));
+}
+
 size_t gops_rollout_workspace_bytes(const GopsRolloutDesc* desc) {
     if (desc == nullptr) return 0;
     Plan plan;

@@ -26,3 +26,9 @@ size_t poly_value_workspace_bytes(const GopsMlp& v, int B);
 int poly_value_forward(const GopsMlp& v, int B, const float* obs, float* out, hipStream_t s);
 int poly_value_backward(const GopsMlp& v, int B, const float* obs, const float* grad_v, const GopsMlpGrad& g, void* ws, size_t bytes,
                         hipStream_t s);
+
+// ---- rollout_rpi.hip: RPI's policy evaluation, one workgroup, one lane per batch row ----
+size_t rpi_state_bytes(int kind, int B);
+int rpi_evaluate(int kind, int B, int max_steps, const float* consts, float* w, const float* wt, const float* max_step,
+                 const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, float* result,
+                 float* trace, hipStream_t s);

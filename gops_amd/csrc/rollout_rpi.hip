@@ -1,0 +1,295 @@
+// RPI (relaxed policy iteration, gops/algorithm/rpi.py): the whole policy evaluation of one local_update in ONE launch.
+//
+// The reference performs up to max_step_update_value gradient steps per Newton iteration, each on a batch of B states with 3 .. 10
+// weights: an env step, two autograd passes, an Adam step, a second Hamiltonian on a held-out set and a host-side test.  Here one
+// workgroup runs that chain: one lane per batch row (B <= 1024), the weights, Adam moments and the lane's state in registers, two
+// batch-wide reductions per step.  More workgroups would only add grid syncs to a chain this short.
+//
+// Reductions have a fixed order - butterfly inside each wave, then the waves in index order through LDS, summed by EVERY thread
+// (as rollout_poly.hip's poly_block_sum) - so every thread holds the same sums bit for bit, takes the same Adam step in its own
+// registers and reaches the same continue/stop decision: no barrier sits under divergent control flow, no float atomics, results
+// are reproducible run to run.  The trip count is bounded by max_steps, never by convergence alone.
+//
+// Per step (rpi.py:183-197, sample() :289-327): action and adversary from the TARGET weights at the lane's state, the bare Euler
+// step with the raw values, done / time-limit flags, the Hamiltonian h = U(x, u', w') + dV/dx . f(x, u', w') at the PRE-step state
+// with the wrapped values (ScaleAction / ClipAction, create_env_model's chain) and the CURRENT weights, loss mean|h|, gradient
+// mean sign(h) d(dV/dx . f)/dw (sign(0) = 0; the bias has none), Adam, the held-out mean|h| with the new weights, the reset select.
+#include "launchers.h"
+
+namespace {
+
+constexpr int RPI_MAX_F = 10;
+constexpr int RPI_MAX_WAVES = GOPS_RPI_MAX_BATCH / 64;
+
+struct RpiParams {
+    float c[GOPS_RPI_CONST_COUNT];
+    int B, max_steps;
+    float* w;                // [F] value weights, stepped in place
+    const float* wt;         // [F] target weights
+    const float* max_step;   // [B] time limit of each lane
+    const float* pool;       // [max_steps + 1][S][B]: held-out set, then one reset draw per step
+    float* state;            // the state block (gops_hip.h)
+    float* result;           // [4]
+    float* trace;            // [max_steps][2] or nullptr
+    double lr, beta1, beta2, eps;
+};
+
+constexpr int rpi_state_dim(int kind) {
+    return kind == GOPS_RPI_ENV_OSCILLATOR ? 2 : kind == GOPS_RPI_ENV_AIRCRAFT ? 3 : kind == GOPS_RPI_ENV_SUSPENSION ? 4 : 0;
+}
+
+// dx/dt at x under action u and adversary w, in the order of operations of the host models (env/env_ocp/env_model/pyth_*conti_model.py)
+template <int KIND>
+__device__ __forceinline__ void rpi_derivative(const float* c, const float* x, float u, float w, float* d) {
+    if constexpr (KIND == GOPS_RPI_ENV_OSCILLATOR) {
+        const float ga = c[GOPS_RPI_C_GAMMA_ATTE];
+        const float a = x[0], b = x[1];
+        d[0] = -0.25f * a;
+        d[1] = 0.5f * ((a * a) * b) - (1.f / (2.f * (ga * ga))) * (b * b * b) - 0.5f * b + a * u + b * w;
+    } else if constexpr (KIND == GOPS_RPI_ENV_AIRCRAFT) {
+        d[0] = (-1.01887f * x[0] + 0.90506f * x[1] + -0.00215f * x[2]) + w;
+        d[1] = 0.82225f * x[0] + -1.07741f * x[1] + -0.17555f * x[2];
+        d[2] = -x[2] + u;
+    } else {
+        constexpr float M_b = 300.f, M_us = 60.f, K_t = 190000.f, K_a = 16000.f, K_n = 1600.f, C_a = 1000.f, gain = 1000.f;
+        const float dp = x[0] - x[2], dvel = x[1] - x[3];
+        const float spring = K_a * dp + K_n * (dp * dp * dp) + C_a * dvel;
+        d[0] = x[1];
+        d[1] = -(spring - gain * u) / M_b;
+        d[2] = x[3];
+        d[3] = (spring - K_t * (x[2] - w) - gain * u) / M_us;
+    }
+}
+
+// g(x)' dv and k(x)' dv (one action column, one adversary column)
+template <int KIND>
+__device__ __forceinline__ void rpi_gk_dot(const float* x, const float* dv, float& gdv, float& kdv) {
+    if constexpr (KIND == GOPS_RPI_ENV_OSCILLATOR) {
+        gdv = x[0] * dv[1];
+        kdv = x[1] * dv[1];
+    } else if constexpr (KIND == GOPS_RPI_ENV_AIRCRAFT) {
+        gdv = dv[2];
+        kdv = dv[0];
+    } else {
+        gdv = (1000.f / 300.f) * dv[1] + (-1000.f / 60.f) * dv[3];
+        kdv = (190000.f / 60.f) * dv[3];
+    }
+}
+
+// dV/dx of V = sum_{i<=j} w_ij y_i y_j, y = x * norm (apprfunc/poly.py StateValue, degree 2)
+template <int S>
+__device__ __forceinline__ void rpi_grad_v(const float* w, const float* norm, const float* x, float* dv) {
+    float y[S];
+#pragma unroll
+    for (int m = 0; m < S; ++m) { y[m] = x[m] * norm[m]; dv[m] = 0.f; }
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < S; ++i)
+#pragma unroll
+        for (int j = i; j < S; ++j, ++k) { dv[i] += w[k] * y[j]; dv[j] += w[k] * y[i]; }
+#pragma unroll
+    for (int m = 0; m < S; ++m) dv[m] *= norm[m];
+}
+
+// ScaleAction from [lo_s, hi_s] onto [lo, hi], then ClipAction (wrapper/scale_action.py:75-83, clip_action.py:34-36)
+__device__ __forceinline__ float rpi_wrap(const float* c, float a, float lo_s, float hi_s, float lo, float hi) {
+    if (c[GOPS_RPI_C_ACTION_SCALE] != 0.f) {
+        a = fminf(fmaxf(a, lo_s), hi_s);
+        a = lo + (hi - lo) * ((a - lo_s) / (hi_s - lo_s));
+        a = fminf(fmaxf(a, lo), hi);
+    }
+    if (c[GOPS_RPI_C_CLIP_ACTION] != 0.f) a = fminf(fmaxf(a, lo), hi);
+    return a;
+}
+
+// raw action / adversary from the weights `w` at x, and their wrapped values
+template <int KIND, int S>
+__device__ __forceinline__ void rpi_policy(const float* c, const float* w, const float* x, float& u, float& a, float& uw, float& aw) {
+    float dv[S], gdv, kdv;
+    rpi_grad_v<S>(w, c + GOPS_RPI_C_NORM, x, dv);
+    rpi_gk_dot<KIND>(x, dv, gdv, kdv);
+    const float ga = c[GOPS_RPI_C_GAMMA_ATTE];
+    u = -0.5f * (1.f / c[GOPS_RPI_C_R]) * gdv;
+    a = 0.5f / (ga * ga) * kdv;
+    uw = rpi_wrap(c, u, c[GOPS_RPI_C_SCALE_ACT_LOW], c[GOPS_RPI_C_SCALE_ACT_HIGH], c[GOPS_RPI_C_ACT_LOW], c[GOPS_RPI_C_ACT_HIGH]);
+    aw = rpi_wrap(c, a, c[GOPS_RPI_C_SCALE_ADV_LOW], c[GOPS_RPI_C_SCALE_ADV_HIGH], c[GOPS_RPI_C_ADV_LOW], c[GOPS_RPI_C_ADV_HIGH]);
+}
+
+template <int S>
+__device__ __forceinline__ float rpi_cost(const float* c, const float* x, float u, float a) {
+    float cost = c[GOPS_RPI_C_Q] * (x[0] * x[0]);
+#pragma unroll
+    for (int m = 1; m < S; ++m) cost += c[GOPS_RPI_C_Q + m] * (x[m] * x[m]);
+    const float ga = c[GOPS_RPI_C_GAMMA_ATTE];
+    return cost + c[GOPS_RPI_C_R] * (u * u) - (ga * ga) * (a * a);
+}
+
+// butterfly inside the wave, lane 0 leaves the wave's sum in red[wave * nslots + slot]
+__device__ __forceinline__ void rpi_wave_sum(float v, float* red, int slot, int nslots) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * nslots + slot] = v;
+}
+// after the barrier: the waves' sums in index order, the same value in every thread
+__device__ __forceinline__ float rpi_block_sum(const float* red, int slot, int nslots, int nwaves) {
+    float s = red[slot];
+    for (int wv = 1; wv < nwaves; ++wv) s += red[wv * nslots + slot];
+    return s;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(GOPS_RPI_MAX_BATCH) void rpi_evaluate_kernel(const RpiParams p) {
+    constexpr int S = rpi_state_dim(KIND);
+    constexpr int F = S * (S + 1) / 2;
+    static_assert(F <= RPI_MAX_F, "feature count");
+    __shared__ float red1[RPI_MAX_WAVES * (F + 1)];
+    __shared__ float red2[RPI_MAX_WAVES];
+    const float* c = p.c;
+    const float* norm = c + GOPS_RPI_C_NORM;
+    const int b = threadIdx.x, B = p.B;
+    const bool valid = b < B;
+    const int nwaves = (int)(blockDim.x >> 6);
+    const float invB_den = (float)B;
+    float* hdr = p.state;
+    float* st_x = p.state + GOPS_RPI_STATE_HEADER;
+    float* st_cnt = st_x + (size_t)S * B;
+    float* st_shown = st_cnt + B;
+
+    float w[F], wt[F], am[F], av[F];
+#pragma unroll
+    for (int k = 0; k < F; ++k) { w[k] = p.w[k]; wt[k] = p.wt[k]; am[k] = hdr[k]; av[k] = hdr[RPI_MAX_F + k]; }
+    // The Adam step count and the lanes' counters are floats in the state block: exact up to 2^24, where they stop advancing.  By
+    // then beta1^t and beta2^t are 0 in double (0.99^t < 1e-300 from t = 68 732), so the bias corrections are exactly 1 either way,
+    // and a lane's counter has long passed any time limit (max_step < 2^24), so its test stays true.
+    float tcount = hdr[2 * RPI_MAX_F];
+    double b1p = pow(p.beta1, (double)tcount), b2p = pow(p.beta2, (double)tcount);
+    const float lerp_w = (float)(1.0 - p.beta1), beta2f = (float)p.beta2, omb2 = (float)(1.0 - p.beta2), epsf = (float)p.eps;
+
+    float x[S], xs[S], ds[S], Us = 0.f, cnt = 0.f, shown = -1.f, maxs = 0.f;
+#pragma unroll
+    for (int m = 0; m < S; ++m) { x[m] = 0.f; xs[m] = 0.f; ds[m] = 0.f; }
+    if (valid) {
+#pragma unroll
+        for (int m = 0; m < S; ++m) { x[m] = st_x[(size_t)m * B + b]; xs[m] = p.pool[(size_t)m * B + b]; }
+        cnt = st_cnt[b], shown = st_shown[b], maxs = p.max_step[b];
+        // held-out set: the target's wrapped action pair is the same at every step, and with it U and f
+        float u, a, uw, aw;
+        rpi_policy<KIND, S>(c, wt, xs, u, a, uw, aw);
+        rpi_derivative<KIND>(c, xs, uw, aw, ds);
+        Us = rpi_cost<S>(c, xs, uw, aw);
+    }
+    auto heldout = [&]() {
+        float dv[S], h = Us;
+        rpi_grad_v<S>(w, norm, xs, dv);
+#pragma unroll
+        for (int m = 0; m < S; ++m) h += dv[m] * ds[m];
+        return valid ? fabsf(h) : 0.f;
+    };
+    rpi_wave_sum(heldout(), red2, 0, 1);
+    __syncthreads();
+    const float before = rpi_block_sum(red2, 0, 1, nwaves) / invB_den;
+    float after = before, loss = 0.f;
+    int steps = 0;
+
+#pragma unroll 1
+    for (int i = 0; i < p.max_steps; ++i) {
+        // sample(): target policy, bare step with the raw pair, flags
+        float u, a, uw, aw, d[S], xn[S];
+        rpi_policy<KIND, S>(c, wt, x, u, a, uw, aw);
+        rpi_derivative<KIND>(c, x, u, a, d);
+        bool reset = false;
+#pragma unroll
+        for (int m = 0; m < S; ++m) {
+            xn[m] = x[m] + d[m] * c[GOPS_RPI_C_DT];
+            reset = reset || fabsf(xn[m]) > c[GOPS_RPI_C_THRESHOLD + m];
+        }
+        cnt += 1.f;
+        reset = reset || cnt > maxs;
+        // Hamiltonian at the pre-step state: wrapped pair, current weights
+        float dv[S], y[S];
+        rpi_derivative<KIND>(c, x, uw, aw, d);
+        rpi_grad_v<S>(w, norm, x, dv);
+        float h = rpi_cost<S>(c, x, uw, aw);
+#pragma unroll
+        for (int m = 0; m < S; ++m) { h += dv[m] * d[m]; y[m] = x[m] * norm[m]; }
+        const float sg = !valid ? 0.f : h > 0.f ? 1.f : h < 0.f ? -1.f : 0.f;
+        rpi_wave_sum(valid ? fabsf(h) : 0.f, red1, F, F + 1);
+        {
+            int k = 0;
+#pragma unroll
+            for (int ii = 0; ii < S; ++ii)
+#pragma unroll
+                for (int jj = ii; jj < S; ++jj, ++k)
+                    rpi_wave_sum(sg * ((norm[ii] * d[ii]) * y[jj] + (norm[jj] * d[jj]) * y[ii]), red1, k, F + 1);
+        }
+        __syncthreads();
+        loss = rpi_block_sum(red1, F, F + 1, nwaves) / invB_den;
+        // Adam (torch.optim.Adam, single-tensor form; bias corrections in double as the host computes them)
+        tcount += 1.f;
+        b1p *= p.beta1;
+        b2p *= p.beta2;
+        const float step_size = (float)(p.lr / (1.0 - b1p)), bc2s = (float)sqrt(1.0 - b2p);
+#pragma unroll
+        for (int k = 0; k < F; ++k) {
+            const float g = rpi_block_sum(red1, k, F + 1, nwaves) / invB_den;
+            am[k] = am[k] + lerp_w * (g - am[k]);
+            av[k] = av[k] * beta2f + omb2 * (g * g);
+            const float denom = sqrtf(av[k]) / bc2s + epsf;
+            w[k] = w[k] - step_size * (am[k] / denom);
+        }
+        // held-out norm with the new weights
+        rpi_wave_sum(heldout(), red2, 0, 1);
+        __syncthreads();
+        after = rpi_block_sum(red2, 0, 1, nwaves) / invB_den;
+        // reset select (rpi.py:315-325): this step's draw for lanes that ended
+        if (valid) {
+            const float prev = shown < 0.f ? cnt : shown;   // the first assignment reads the counter the step has just advanced
+            shown = reset ? 0.f : prev;
+#pragma unroll
+            for (int m = 0; m < S; ++m) x[m] = reset ? p.pool[((size_t)(i + 1) * S + m) * B + b] : xn[m];
+        }
+        steps = i + 1;
+        if (p.trace != nullptr && b == 0) { p.trace[2 * (size_t)i] = loss; p.trace[2 * (size_t)i + 1] = after; }
+        // continue_evaluation (rpi.py:164-168): the same sums in every thread, so the branch is uniform
+        if (!(fabs((double)after) > 0.88 * fabs((double)before))) break;
+    }
+
+    if (valid) {
+#pragma unroll
+        for (int m = 0; m < S; ++m) st_x[(size_t)m * B + b] = x[m];
+        st_cnt[b] = cnt, st_shown[b] = shown;
+    }
+    if (b == 0) {
+#pragma unroll
+        for (int k = 0; k < F; ++k) { p.w[k] = w[k]; hdr[k] = am[k]; hdr[RPI_MAX_F + k] = av[k]; }
+        hdr[2 * RPI_MAX_F] = tcount;
+        p.result[0] = (float)steps, p.result[1] = loss, p.result[2] = before, p.result[3] = after;
+    }
+}
+
+}  // namespace
+
+size_t rpi_state_bytes(int kind, int B) {
+    const int S = rpi_state_dim(kind);
+    if (S == 0 || B < 1 || B > GOPS_RPI_MAX_BATCH) return 0;
+    return sizeof(float) * ((size_t)GOPS_RPI_STATE_HEADER + (size_t)(S + 2) * B);
+}
+
+int rpi_evaluate(int kind, int B, int max_steps, const float* consts, float* w, const float* wt, const float* max_step,
+                 const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, float* result,
+                 float* trace, hipStream_t s) {
+    if (rpi_state_dim(kind) == 0 || B > GOPS_RPI_MAX_BATCH) return GOPS_ERR_UNSUPPORTED;
+    if (B < 1 || max_steps < 1 || max_steps > GOPS_RPI_MAX_STEPS) return GOPS_ERR_BAD_ARG;
+    if (!consts || !w || !wt || !max_step || !pool || !state || !result) return GOPS_ERR_BAD_ARG;
+    if (state_bytes < rpi_state_bytes(kind, B)) return GOPS_ERR_WORKSPACE;
+    RpiParams p;
+    for (int i = 0; i < GOPS_RPI_CONST_COUNT; ++i) p.c[i] = consts[i];
+    p.B = B, p.max_steps = max_steps, p.w = w, p.wt = wt, p.max_step = max_step, p.pool = pool;
+    p.state = static_cast<float*>(state), p.result = result, p.trace = trace;
+    p.lr = lr, p.beta1 = beta1, p.beta2 = beta2, p.eps = eps;
+    const dim3 block((unsigned)((B + 63) / 64 * 64));
+    if (kind == GOPS_RPI_ENV_OSCILLATOR) rpi_evaluate_kernel<GOPS_RPI_ENV_OSCILLATOR><<<1, block, 0, s>>>(p);
+    else if (kind == GOPS_RPI_ENV_AIRCRAFT) rpi_evaluate_kernel<GOPS_RPI_ENV_AIRCRAFT><<<1, block, 0, s>>>(p);
+    else rpi_evaluate_kernel<GOPS_RPI_ENV_SUSPENSION><<<1, block, 0, s>>>(p);
+    return (int)hipGetLastError();
+}

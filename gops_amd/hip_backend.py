@@ -25,6 +25,12 @@ ACT_IDS = {"linear": 0, "relu": 1, "elu": 2, "gelu": 3, "selu": 4, "sigmoid": 5,
 # GopsMlp.hidden_act of a POLY net (ABI v15): make_features(obs, d) for d = 1, 2, 3 and create_features(obs * norm_matrix, 2)
 POLY_FULL = {1: 16, 2: 17, 3: 18}
 POLY_SYM_2 = 24
+# RPI's policy evaluation (gops_rpi_evaluate): env kinds of its own and the layout of its constant table (GOPS_RPI_* of gops_hip.h)
+RPI_ENV_OSCILLATOR, RPI_ENV_AIRCRAFT, RPI_ENV_SUSPENSION = 1, 2, 3
+(RPI_C_GAMMA_ATTE, RPI_C_DT, RPI_C_R, RPI_C_ACT_LOW, RPI_C_ACT_HIGH, RPI_C_ADV_LOW, RPI_C_ADV_HIGH, RPI_C_SCALE_ACT_LOW,
+ RPI_C_SCALE_ACT_HIGH, RPI_C_SCALE_ADV_LOW, RPI_C_SCALE_ADV_HIGH, RPI_C_ACTION_SCALE, RPI_C_CLIP_ACTION) = range(13)
+RPI_C_Q, RPI_C_THRESHOLD, RPI_C_NORM, RPI_CONST_COUNT = 13, 17, 21, 32
+RPI_MAX_BATCH, RPI_MAX_STEPS, RPI_STATE_HEADER = 1024, 1 << 20, 32
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "fp16": 1, "f16": 1, "float16": 1, "half": 1}
 
 
@@ -211,6 +217,12 @@ def lib() -> C.CDLL:
         l.gops_poly_value_backward.restype = C.c_int
         l.gops_poly_value_backward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsMlpGrad),
                                                C.c_void_p, C.c_size_t, C.c_void_p]
+        l.gops_rpi_state_bytes.restype = C.c_size_t
+        l.gops_rpi_state_bytes.argtypes = [C.c_int32, C.c_int32]
+        l.gops_rpi_evaluate.restype = C.c_int
+        l.gops_rpi_evaluate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
         l.gops_profile_enable.argtypes = [C.c_int32]
         l.gops_profile_reset.argtypes = []
         l.gops_profile_read.restype = C.c_int
@@ -227,7 +239,7 @@ EXPORTED_SYMBOLS = ("gops_hip_version", "gops_rollout_workspace_bytes", "gops_ro
                     "gops_env_constraint", "gops_polyak_update", "gops_value_loss", "gops_mean_loss", "gops_rollout_backward_update",
                     "gops_value_backward_update", "gops_poly_rollout_workspace_bytes", "gops_poly_rollout_forward",
                     "gops_poly_rollout_backward", "gops_poly_value_workspace_bytes", "gops_poly_value_forward",
-                    "gops_poly_value_backward")
+                    "gops_poly_value_backward", "gops_rpi_state_bytes", "gops_rpi_evaluate")
 
 _ERR = {-1: "GOPS_ERR_BAD_ARG", -2: "GOPS_ERR_UNSUPPORTED", -3: "GOPS_ERR_WORKSPACE"}
 
@@ -686,6 +698,45 @@ class PolyValueNet:
         check(lib().gops_poly_value_backward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g),
                                              self.workspace.data_ptr(), self.workspace.numel(), _stream()),
               "gops_poly_value_backward")
+
+
+class RpiEvaluator:
+    """RPI's policy evaluation of one `local_update` as ONE launch (`gops_rpi_evaluate`, csrc/rollout_rpi.hip): up to `max_steps`
+    gradient steps on the value weights, each with its env step, Hamiltonian, Adam step, held-out Hamiltonian norm and 0.88 test.
+    Owns the device state block (`state`: Adam moments and step count in the header, then the lanes' states column-major, the
+    time-limit counters and the counters the algorithm assigns), which persists from one call to the next."""
+
+    def __init__(self, env_kind: int, batch: int, state_dim: int, consts, device: Optional[torch.device] = None):
+        self.kind, self.batch, self.state_dim = int(env_kind), int(batch), int(state_dim)
+        self.consts = (C.c_float * RPI_CONST_COUNT)(*[float(v) for v in consts])
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        nbytes = lib().gops_rpi_state_bytes(self.kind, self.batch)
+        if nbytes == 0:
+            raise RuntimeError(f"gops_rpi_state_bytes: GOPS_ERR_UNSUPPORTED (env kind {env_kind}, batch {batch}; at most {RPI_MAX_BATCH} lanes)")
+        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+        self.result = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    # views into the state block
+    def lanes(self) -> torch.Tensor:
+        """[state_dim, B] view of the lanes' states."""
+        return self.state[RPI_STATE_HEADER:RPI_STATE_HEADER + self.state_dim * self.batch].view(self.state_dim, self.batch)
+
+    def counters(self) -> torch.Tensor:
+        """[2, B] view: the time-limit counter of each lane, then the counter the algorithm assigns at a reset."""
+        o = RPI_STATE_HEADER + self.state_dim * self.batch
+        return self.state[o:o + 2 * self.batch].view(2, self.batch)
+
+    def evaluate(self, weight: torch.Tensor, target_weight: torch.Tensor, max_step: torch.Tensor, pool: torch.Tensor, max_steps: int,
+                 lr: float, beta1: float, beta2: float, eps: float, trace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Enqueues the launch; returns the device result [steps taken, last loss, norm_before, norm_after].  `pool` is
+        [max_steps + 1, state_dim, B]: the held-out set, then one reset draw per step."""
+        assert tuple(pool.shape) == (max_steps + 1, self.state_dim, self.batch)
+        assert trace is None or trace.numel() >= 2 * max_steps
+        check(lib().gops_rpi_evaluate(self.kind, self.batch, int(max_steps), self.consts, _ptr(weight), _ptr(target_weight),
+                                      _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr),
+                                      float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),
+              "gops_rpi_evaluate")
+        return self.result
 
 
 class ValueNet:

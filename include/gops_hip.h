@@ -500,6 +500,44 @@ int gops_poly_value_forward(const GopsMlp* value, int32_t batch, const float* ob
 int gops_poly_value_backward(const GopsMlp* value, int32_t batch, const float* obs, const float* grad_v,
                              const GopsMlpGrad* grad, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): RPI's policy evaluation (gops/algorithm/rpi.py local_update) as ONE
+ * launch of one workgroup, one lane per batch row (csrc/rollout_rpi.hip).  Up to `max_steps` gradient steps on the weights of a
+ * POLY StateValue of degree 2 (F = S (S + 1) / 2 weights in create_features order; the bias takes no gradient), each with its env
+ * step under the target weights' action / adversary pair, the Hamiltonian loss mean|h| and its gradient, an Adam step, the held-out
+ * Hamiltonian norm and the reference's continue test |after| > 0.88 |before|.  Sums are formed in a fixed order: results are bitwise
+ * reproducible.
+ * The env kinds are an enum of their own: no rollout entry point accepts these models. */
+enum { GOPS_RPI_ENV_OSCILLATOR = 1, GOPS_RPI_ENV_AIRCRAFT = 2, GOPS_RPI_ENV_SUSPENSION = 3 };   /* state_dim S = 2, 3, 4 */
+#define GOPS_RPI_MAX_BATCH 1024          /* lanes of the one workgroup */
+#define GOPS_RPI_MAX_STEPS (1 << 20)
+/* `consts`: GOPS_RPI_CONST_COUNT floats in HOST memory, read at the call */
+enum {
+    GOPS_RPI_C_GAMMA_ATTE = 0, GOPS_RPI_C_DT = 1, GOPS_RPI_C_R = 2,   /* disturbance attenuation, Euler step, control weight */
+    GOPS_RPI_C_ACT_LOW = 3, GOPS_RPI_C_ACT_HIGH = 4, GOPS_RPI_C_ADV_LOW = 5, GOPS_RPI_C_ADV_HIGH = 6,   /* the model's action / adversary bounds */
+    GOPS_RPI_C_SCALE_ACT_LOW = 7, GOPS_RPI_C_SCALE_ACT_HIGH = 8, GOPS_RPI_C_SCALE_ADV_LOW = 9, GOPS_RPI_C_SCALE_ADV_HIGH = 10,   /* ScaleAction's min_action / max_action per column */
+    GOPS_RPI_C_ACTION_SCALE = 11, GOPS_RPI_C_CLIP_ACTION = 12,   /* wrapper switches, 0 or 1 (they act on the Hamiltonian's pair only) */
+    GOPS_RPI_C_Q = 13,           /* [4] diagonal of the state weight */
+    GOPS_RPI_C_THRESHOLD = 17,   /* [4] |x_i| beyond which a lane is done */
+    GOPS_RPI_C_NORM = 21,        /* [4] the value net's norm_matrix */
+    GOPS_RPI_CONST_COUNT = 32
+};
+/* The state block (device memory, persists from call to call, written by the caller before the first one), in floats:
+ *   [0, 10) Adam exp_avg, [10, 20) exp_avg_sq, [20] Adam step count (a float: exact to 2^24 steps, where it stops advancing -
+ *   the bias corrections it feeds are exactly 1 long before), up to GOPS_RPI_STATE_HEADER reserved (zero);
+ *   then x [S][batch] (lane states, column-major), count [batch] (steps since construction: the counter the time-limit test reads),
+ *   shown [batch] (the counter the algorithm assigns at a reset; -1 = not assigned yet).
+ * gops_rpi_state_bytes: its size; 0 for an unknown env kind or batch outside 1 .. GOPS_RPI_MAX_BATCH. */
+#define GOPS_RPI_STATE_HEADER 32
+size_t gops_rpi_state_bytes(int32_t env_kind, int32_t batch);
+/* weights [F] (device, stepped in place), target_weights [F], max_step [batch] (time limit per lane),
+ * reset_pool [max_steps + 1][S][batch] (entry 0: the held-out set; entry 1 + i: the reset draw of step i),
+ * result [4] (device): steps taken, last loss, norm_before, norm_after; trace [max_steps][2] (loss, norm_after per step) or NULL.
+ * batch > GOPS_RPI_MAX_BATCH or an unknown env kind: GOPS_ERR_UNSUPPORTED, nothing is launched; max_steps outside
+ * 1 .. GOPS_RPI_MAX_STEPS or a NULL pointer: GOPS_ERR_BAD_ARG; state_bytes too small: GOPS_ERR_WORKSPACE. */
+int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const float* consts, float* weights,
+                      const float* target_weights, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
+                      double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
