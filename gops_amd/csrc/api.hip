@@ -855,6 +855,18 @@ int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const 
                         beta1, beta2, eps, result, trace, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps) {
+    return episode_workspace_bytes(env, policy, episodes, max_steps);
+}
+
+int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps, const GopsStepIO* init,
+                         const GopsEpisodeOut* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!env) return GOPS_ERR_BAD_ARG;
+    GopsEnv e = *env;
+    fill_ref_defaults(e);
+    return episode_rollout(&e, policy, episodes, max_steps, init, out, workspace, workspace_bytes, pdt_of(e), static_cast<hipStream_t>(stream));
+}
+
 size_t gops_rollout_workspace_bytes(const GopsRolloutDesc* desc) {
     if (desc == nullptr) return 0;
     Plan plan;

@@ -32,3 +32,8 @@ size_t rpi_state_bytes(int kind, int B);
 int rpi_evaluate(int kind, int B, int max_steps, const float* consts, float* w, const float* wt, const float* max_step,
                  const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, float* result,
                  float* trace, hipStream_t s);
+
+// ---- rollout_episode.hip: closed-loop evaluation episodes, 16 per workgroup, every step in one launch ----
+size_t episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int E, int T);
+int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, const GopsStepIO* init, const GopsEpisodeOut* out, void* ws,
+                    size_t ws_bytes, float pdt, hipStream_t s);

@@ -1,0 +1,335 @@
+// Closed-loop evaluation episodes (gops/trainer/evaluator.py:45-86 run_an_episode): policy, DATA-env step, termination, time limit
+// and return of E episodes over up to T steps in ONE launch, no host sync inside.
+//
+// A workgroup of 256 threads owns a tile of 16 episodes (GOPS_TILE = MFMA M) from the first step to the last:
+//   1. all threads stage the tile's observations [16][K0] in LDS (a FiniteHorizonPolicy gets virtual_t = 1 behind them: the
+//      reference evaluator calls policy(obs) with the default) and record them in trace_obs;
+//   2. all four waves evaluate the hidden layers on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation: evaluation
+//      does not depend on the plane-split precision guard), wave w the 16-feature tiles w, w + 4, ..; activations ping-pong
+//      between two LDS tiles; weights are read in place from the live parameter tensors - staged in LDS once per launch when the
+//      whole network fits next to the tiles, else streamed from L2 every step;
+//   3. 16 lanes per episode form the head's dot products (DPP sum), lane a squashes action a (tanh, act limits) and stores it;
+//   4. one lane per episode takes the data env's step through env_step_one (env_step.h) - the function env_step_kernel calls, so
+//      the trace of an episode is reproduced by gops_env_step step by step - and keeps the episode's books in registers.
+// The per-episode step buffers (obs, state, ref_points ring, ref_time) ping-pong between two sets in the workspace; each
+// workgroup touches its own 16 rows only, which stay in L2.  Episodes that ended take no further step and write no further
+// trace row; the workgroup leaves the loop once all of its episodes have ended (the alive flags in LDS, read by every thread: a uniform decision).
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "env_step.h"
+#include "launchers.h"
+
+namespace {
+
+constexpr int EP_THREADS = 256;
+constexpr size_t EP_LDS_LIMIT = 150 * 1024;   // dynamic LDS of one workgroup (the CU has 160 KiB)
+
+struct EpisodeParams {
+    GopsEnv env;   // padded (lq_pad_env), reference constants filled
+    int E, T, O, A, fh, nl, act, staged;
+    int w16;                      // bit j: weight[j] is 16-byte aligned (the unstaged form may load it four floats at a time)
+    int dims[GOPS_MAX_LAYERS + 1];
+    const float* W[GOPS_MAX_LAYERS];
+    const float* Bv[GOPS_MAX_LAYERS];
+    int ldx;                      // row stride of an activation tile (floats)
+    int ldw[GOPS_MAX_LAYERS];     // row stride of a staged weight image
+    int w_off[GOPS_MAX_LAYERS];   // LDS offsets (floats)
+    int b_off[GOPS_MAX_LAYERS];
+    int state_dim, ref_floats;    // per-episode floats of info["state"] / info["ref_points"] (0: the model has none)
+    float pdt;
+    GopsStepIO init;
+    float* obs[2];
+    float* state[2];
+    float* refp[2];
+    float* reft[2];
+    float *action, *reward, *done;
+    GopsEpisodeOut out;
+};
+
+struct EpisodeLayout {
+    size_t obs, state, refp, reft, action, reward, done, bytes;   // float offsets of the first buffer of each pair
+    size_t obs_n, state_n, refp_n, reft_n;
+};
+
+inline size_t ep_align(size_t nfloats) { return (nfloats + 63) & ~(size_t)63; }   // 256-byte steps
+
+EpisodeLayout episode_layout(const GopsEnv& e, int E) {
+    EpisodeLayout l{};
+    const bool ref = env_has_ref_table(e.kind);
+    const int sd = e.kind == GOPS_ENV_VEH3DOFCONTI ? 6 : e.kind == GOPS_ENV_VEH2DOF ? 4 : 0;
+    const int rf = e.kind == GOPS_ENV_VEH3DOFCONTI ? (e.pre_horizon + 1) * 4 : e.kind == GOPS_ENV_VEH2DOF ? (e.pre_horizon + 1) * 2 : 0;
+    l.obs_n = ep_align((size_t)E * e.obs_dim);
+    l.state_n = ref ? ep_align((size_t)E * sd) : 0;
+    l.refp_n = ref ? ep_align((size_t)E * rf) : 0;
+    l.reft_n = ref ? ep_align((size_t)E) : 0;
+    size_t off = 0;
+    l.obs = off; off += 2 * l.obs_n;
+    l.state = off; off += 2 * l.state_n;
+    l.refp = off; off += 2 * l.refp_n;
+    l.reft = off; off += 2 * l.reft_n;
+    l.action = off; off += ep_align((size_t)E * e.act_dim);
+    l.reward = off; off += ep_align((size_t)E);
+    l.done = off; off += ep_align((size_t)E);
+    l.bytes = off * sizeof(float);
+    return l;
+}
+
+int episode_check(const GopsEnv* env, const GopsMlp* pol, int E, int T) {
+    if (!env || !pol || E < 1 || T < 1) return GOPS_ERR_BAD_ARG;
+    if (!env->data_env) return GOPS_ERR_BAD_ARG;   // evaluation steps the DATA environment
+    const int k = env->kind;
+    if (k != GOPS_ENV_LQ && k != GOPS_ENV_IDPENDULUM && k != GOPS_ENV_CARTPOLE && k != GOPS_ENV_VEH3DOFCONTI && k != GOPS_ENV_VEH2DOF)
+        return GOPS_ERR_UNSUPPORTED;   // mobilerobot (noise drawn per step), the constrained vehicle models, pendulum (no data-env restatement)
+    if (env->cstr_err || env->repeat_num > 1) return GOPS_ERR_UNSUPPORTED;
+    if (pol->n_layers == 1 || pol->dtype != GOPS_DTYPE_F32) return GOPS_ERR_UNSUPPORTED;   // POLY nets, half-precision contractions
+    const int O = env->obs_dim, A = env->act_dim, P = env->pre_horizon;
+    if (A < 1 || A > GOPS_MAX_ACT || O < 1) return GOPS_ERR_BAD_ARG;
+    if (k == GOPS_ENV_LQ && O > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED;
+    if ((k == GOPS_ENV_IDPENDULUM && (O != 6 || A != 1)) || (k == GOPS_ENV_CARTPOLE && (O != 4 || A != 1))) return GOPS_ERR_BAD_ARG;
+    if (k == GOPS_ENV_VEH3DOFCONTI && (P < 1 || O != 6 + 4 * P || A != 2)) return GOPS_ERR_BAD_ARG;
+    if (k == GOPS_ENV_VEH2DOF && (P < 1 || O != 4 + P || A != 1)) return GOPS_ERR_BAD_ARG;
+    if (env->scale_obs && (O > 8 || env_has_ref_table(k))) return GOPS_ERR_UNSUPPORTED;
+    if (pol->n_layers < 2 || pol->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_UNSUPPORTED;
+    if ((pol->sizes[0] != O && pol->sizes[0] != O + 1) || pol->sizes[pol->n_layers] != A) return GOPS_ERR_BAD_ARG;
+    for (int j = 1; j < pol->n_layers; ++j)
+        if (pol->sizes[j] < 16 || (pol->sizes[j] & 15)) return GOPS_ERR_UNSUPPORTED;
+    if (pol->hidden_act < GOPS_ACT_LINEAR || pol->hidden_act > GOPS_ACT_TANH) return GOPS_ERR_BAD_ARG;
+    for (int j = 0; j < pol->n_layers; ++j)
+        if (pol->weight[j] == nullptr || pol->bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
+    return GOPS_OK;
+}
+
+inline int ep_pad16(int x) { return (x + 15) & ~15; }
+
+// LDS plan: two activation tiles, the biases, 16 alive flags, then - when everything fits - the weight images.  Returns the
+// bytes, 0 when even the unstaged form does not fit (hidden widths beyond ~1100).
+size_t episode_lds(const GopsMlp& m, EpisodeParams& p) {
+    int maxd = 0;
+    for (int j = 0; j < m.n_layers; ++j) maxd = std::max(maxd, ep_pad16(m.sizes[j]));
+    p.ldx = maxd + 4;   // 4 mod 16: the 16 rows an MFMA operand read touches start in different banks
+    size_t off = 2 * (size_t)GOPS_TILE * p.ldx;
+    for (int j = 0; j < m.n_layers; ++j) { p.b_off[j] = (int)off; off += (size_t)ep_pad16(m.sizes[j + 1]); }
+    off += GOPS_TILE;   // alive flags
+    const size_t base = off;
+    for (int j = 0; j < m.n_layers; ++j) {
+        p.ldw[j] = ep_pad16(m.sizes[j]) + 4;
+        p.w_off[j] = (int)off;
+        off += (size_t)m.sizes[j + 1] * p.ldw[j];
+    }
+    p.staged = off * sizeof(float) <= EP_LDS_LIMIT;
+    const size_t bytes = (p.staged ? off : base) * sizeof(float);
+    return bytes <= EP_LDS_LIMIT ? bytes : 0;
+}
+
+__global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e0 = blockIdx.x * GOPS_TILE;
+    const int nvalid = min(GOPS_TILE, p.E - e0);
+    const int O = p.O, A = p.A, nl = p.nl, ldx = p.ldx;
+    float* xa = lds;
+    float* xb = lds + GOPS_TILE * ldx;
+    int* s_alive = reinterpret_cast<int*>(lds + p.b_off[nl - 1] + ((p.dims[nl] + 15) & ~15));
+
+    // ---- once per launch: biases (and weights) into LDS, the tile's initial condition into step buffer 0 ----
+    for (int j = 0; j < nl; ++j)
+        for (int n = tid; n < p.dims[j + 1]; n += EP_THREADS) lds[p.b_off[j] + n] = p.Bv[j][n];
+    if (p.staged) {
+        for (int j = 0; j < nl; ++j) {
+            const int K = p.dims[j], N = p.dims[j + 1], ldw = p.ldw[j];
+            for (int idx = tid; idx < N * ldw; idx += EP_THREADS) {
+                const int n = idx / ldw, k = idx - n * ldw;
+                lds[p.w_off[j] + idx] = k < K ? p.W[j][(size_t)n * K + k] : 0.f;
+            }
+        }
+    }
+    if (tid < GOPS_TILE) s_alive[tid] = tid < nvalid ? 1 : 0;
+    for (int idx = tid; idx < nvalid * O; idx += EP_THREADS) p.obs[0][(size_t)e0 * O + idx] = p.init.obs[(size_t)e0 * O + idx];
+    if (p.state_dim > 0) {
+        for (int idx = tid; idx < nvalid * p.state_dim; idx += EP_THREADS)
+            p.state[0][(size_t)e0 * p.state_dim + idx] = p.init.state[(size_t)e0 * p.state_dim + idx];
+        for (int idx = tid; idx < nvalid * p.ref_floats; idx += EP_THREADS)
+            p.refp[0][(size_t)e0 * p.ref_floats + idx] = p.init.ref_points[(size_t)e0 * p.ref_floats + idx];
+        if (tid < nvalid) p.reft[0][e0 + tid] = p.init.ref_time[e0 + tid];
+    }
+    // the episode's books, in the registers of its lane (tid < nvalid)
+    bool alive = tid < nvalid;
+    double ret = 0.0;   // (one add per step in one lane: the return carries no summation error of its own)
+    int length = 0;
+    __syncthreads();
+
+    const int K0 = p.dims[0], K0p = (K0 + 15) & ~15;
+#pragma unroll 1
+    for (int t = 0; t < p.T; ++t) {
+        const int cur = t & 1;
+        // 1. observations of the tile -> xa (zero padded; virtual_t = 1 for a FiniteHorizonPolicy), trace_obs
+        {
+            const float* ob = p.obs[cur];
+            for (int idx = tid; idx < GOPS_TILE * K0p; idx += EP_THREADS) {
+                const int m = idx / K0p, k = idx - m * K0p;
+                float v = 0.f;
+                if (m < nvalid) {
+                    if (k < O) {
+                        v = ob[(size_t)(e0 + m) * O + k];
+                        if (p.out.trace_obs != nullptr && s_alive[m]) p.out.trace_obs[((size_t)(e0 + m) * p.T + t) * O + k] = v;
+                    } else if (k == O && p.fh) {
+                        v = 1.f;
+                    }
+                }
+                xa[m * ldx + k] = v;
+            }
+        }
+        __syncthreads();
+        // 2. hidden layers
+        float* cur_x = xa;
+        float* nxt_x = xb;
+        for (int j = 0; j < nl - 1; ++j) {
+            const int K = p.dims[j], N = p.dims[j + 1], kch = (K + 15) >> 4;
+            const float* arow = cur_x + (lane & 15) * ldx + 4 * (lane >> 4);
+            const int m0 = (lane >> 4) << 2;
+            for (int nt = wave; nt < (N >> 4); nt += 4) {
+                const int n = (nt << 4) + (lane & 15);
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                if (p.staged) {
+                    const float* wrow = lds + p.w_off[j] + n * p.ldw[j] + 4 * (lane >> 4);
+                    for (int c = 0; c < kch; ++c) {
+                        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + 16 * c), b = *reinterpret_cast<const f32x4*>(wrow + 16 * c);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i], acc, 0, 0, 0);
+                    }
+                } else if ((K & 15) == 0 && ((p.w16 >> j) & 1)) {   // rows of 64-byte multiples from a 16-byte aligned base: 16-byte loads
+                    const float* wrow = p.W[j] + (size_t)n * K + 4 * (lane >> 4);
+                    for (int c = 0; c < kch; ++c) {
+                        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + 16 * c), b = *reinterpret_cast<const f32x4*>(wrow + 16 * c);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i], acc, 0, 0, 0);
+                    }
+                } else {   // the input layer of an unstaged net, or a weight view at a 4-byte offset: any width, guarded element loads
+                    const float* wrow = p.W[j] + (size_t)n * K;
+                    for (int c = 0; c < kch; ++c) {
+                        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + 16 * c);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int k = 16 * c + 4 * (lane >> 4) + i;
+                            const float b = k < K ? wrow[k] : 0.f;
+                            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b, acc, 0, 0, 0);
+                        }
+                    }
+                }
+                const float bn = lds[p.b_off[j] + n];
+                act_dispatch(p.act, [&]<int ACT>() {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) nxt_x[(m0 + r) * ldx + n] = act_fwd_t<ACT>(acc[r] + bn);
+                });
+            }
+            __syncthreads();
+            float* sw = cur_x; cur_x = nxt_x; nxt_x = sw;
+        }
+        // 3. head: 16 lanes per episode, lane a squashes and stores action a
+        {
+            const int m = tid >> 4, part = tid & 15, K = p.dims[nl - 1];
+            const float* wo = p.staged ? lds + p.w_off[nl - 1] : p.W[nl - 1];
+            const int ldo = p.staged ? p.ldw[nl - 1] : K;
+            float y[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int a = 0; a < GOPS_MAX_ACT; ++a) {
+                if (a < A) {
+                    float s = 0.f;
+                    for (int k = part; k < K; k += 16) s = fmaf(cur_x[m * ldx + k], wo[a * ldo + k], s);
+                    y[a] = row16_sum(s);
+                }
+            }
+            if (part < A && m < nvalid) {
+                const float ya = (part == 0 ? y[0] : part == 1 ? y[1] : part == 2 ? y[2] : y[3]) + lds[p.b_off[nl - 1] + part];
+                const float sc = (p.env.policy_high[part] - p.env.policy_low[part]) / 2.f;
+                const float of = (p.env.policy_high[part] + p.env.policy_low[part]) / 2.f;
+                const float act = sc * tanhf(ya) + of;
+                p.action[(size_t)(e0 + m) * A + part] = act;
+                if (p.out.trace_act != nullptr && s_alive[m]) p.out.trace_act[((size_t)(e0 + m) * p.T + t) * A + part] = act;
+            }
+        }
+        __syncthreads();   // (also orders the action stores before the env lane's loads: one workgroup, global memory)
+        // 4. one lane per episode: the data env's step, the episode's books
+        if (alive) {
+            const int e = e0 + tid;
+            GopsStepIO io = {};
+            io.obs = p.obs[cur]; io.action = p.action; io.done = nullptr;
+            io.state = p.state[cur]; io.ref_points = p.refp[cur]; io.path_num = p.init.path_num; io.u_num = p.init.u_num;
+            io.ref_time = p.reft[cur];
+            io.next_obs = p.obs[cur ^ 1]; io.reward = p.reward; io.next_done = p.done;
+            io.next_state = p.state[cur ^ 1]; io.next_ref_points = p.refp[cur ^ 1]; io.next_ref_time = p.reft[cur ^ 1];
+            env_step_one(p.env, e, io, p.pdt);
+            const float r = p.reward[e];
+            const bool dn = p.done[e] != 0.f;
+            ret += (double)r;
+            length = t + 1;
+            if (p.out.trace_rew != nullptr) p.out.trace_rew[(size_t)e * p.T + t] = r;
+            if (dn || length == p.T) {
+                alive = false;
+                s_alive[tid] = 0;
+                p.out.ret[e] = (float)ret;
+                p.out.length[e] = length;
+                p.out.terminated[e] = dn ? 1.f : 0.f;
+            }
+        }
+        // The barrier that publishes next_obs / s_alive to the tile, then the same 16 flags read by every thread: a uniform
+        // decision.  (Not __syncthreads_or: it adds static LDS, and hipFuncSetAttribute then refuses the 160-KiB dynamic limit.)
+        __syncthreads();
+        int any = 0;
+#pragma unroll
+        for (int m = 0; m < GOPS_TILE; ++m) any |= s_alive[m];
+        if (!any) break;
+    }
+}
+
+}  // namespace
+
+size_t episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int E, int T) {
+    if (episode_check(env, policy, E, T) != GOPS_OK) return 0;
+    EpisodeParams p;
+    if (episode_lds(*policy, p) == 0) return 0;
+    return episode_layout(*env, E).bytes;
+}
+
+int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, const GopsStepIO* init, const GopsEpisodeOut* out, void* ws,
+                    size_t ws_bytes, float pdt, hipStream_t s) {
+    const int rc = episode_check(env, policy, E, T);
+    if (rc != GOPS_OK) return rc;
+    if (!init || !out || !init->obs || !out->ret || !out->length || !out->terminated) return GOPS_ERR_BAD_ARG;
+    const bool ref = env_has_ref_table(env->kind);
+    if (ref && (!init->state || !init->ref_points || !init->path_num || !init->u_num || !init->ref_time)) return GOPS_ERR_BAD_ARG;
+    EpisodeParams p;
+    memset(&p, 0, sizeof(p));
+    const size_t lds = episode_lds(*policy, p);
+    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
+    const EpisodeLayout l = episode_layout(*env, E);
+    if (!ws || ws_bytes < l.bytes) return GOPS_ERR_WORKSPACE;
+    p.env = *env;   // (the caller - api.hip - has filled the reference constants)
+    lq_pad_env(p.env);
+    p.E = E, p.T = T, p.O = env->obs_dim, p.A = env->act_dim;
+    p.fh = policy->sizes[0] == env->obs_dim + 1;
+    p.nl = policy->n_layers, p.act = policy->hidden_act;
+    for (int j = 0; j <= policy->n_layers; ++j) p.dims[j] = policy->sizes[j];
+    for (int j = 0; j < policy->n_layers; ++j) {
+        p.W[j] = policy->weight[j]; p.Bv[j] = policy->bias[j];
+        if ((reinterpret_cast<uintptr_t>(policy->weight[j]) & 15) == 0) p.w16 |= 1 << j;
+    }
+    p.state_dim = env->kind == GOPS_ENV_VEH3DOFCONTI ? 6 : env->kind == GOPS_ENV_VEH2DOF ? 4 : 0;
+    p.ref_floats = env->kind == GOPS_ENV_VEH3DOFCONTI ? (env->pre_horizon + 1) * 4 : env->kind == GOPS_ENV_VEH2DOF ? (env->pre_horizon + 1) * 2 : 0;
+    p.pdt = pdt;
+    p.init = *init;
+    float* f = static_cast<float*>(ws);
+    for (int i = 0; i < 2; ++i) {
+        p.obs[i] = f + l.obs + i * l.obs_n;
+        p.state[i] = ref ? f + l.state + i * l.state_n : nullptr;
+        p.refp[i] = ref ? f + l.refp + i * l.refp_n : nullptr;
+        p.reft[i] = ref ? f + l.reft + i * l.reft_n : nullptr;
+    }
+    p.action = f + l.action, p.reward = f + l.reward, p.done = f + l.done;
+    p.out = *out;
+    launch_with_lds(episode_kernel, dim3((unsigned)((E + GOPS_TILE - 1) / GOPS_TILE)), dim3(EP_THREADS), lds, s, p);
+    return (int)hipGetLastError();
+}

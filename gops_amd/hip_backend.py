@@ -132,6 +132,10 @@ class GopsStepIO(C.Structure):
                                           "surr_state", "next_surr_state", "constraint", "ref_appended", "noise")]
 
 
+class GopsEpisodeOut(C.Structure):   # gops_episode_rollout
+    _fields_ = [(k, C.c_void_p) for k in ("ret", "length", "terminated", "trace_obs", "trace_act", "trace_rew")]
+
+
 _lib = None
 
 
@@ -223,6 +227,11 @@ def lib() -> C.CDLL:
         l.gops_rpi_evaluate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double,
                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gops_episode_workspace_bytes.restype = C.c_size_t
+        l.gops_episode_workspace_bytes.argtypes = [C.POINTER(GopsEnv), C.POINTER(GopsMlp), C.c_int32, C.c_int32]
+        l.gops_episode_rollout.restype = C.c_int
+        l.gops_episode_rollout.argtypes = [C.POINTER(GopsEnv), C.POINTER(GopsMlp), C.c_int32, C.c_int32, C.POINTER(GopsStepIO),
+                                           C.POINTER(GopsEpisodeOut), C.c_void_p, C.c_size_t, C.c_void_p]
         l.gops_profile_enable.argtypes = [C.c_int32]
         l.gops_profile_reset.argtypes = []
         l.gops_profile_read.restype = C.c_int
@@ -239,7 +248,8 @@ EXPORTED_SYMBOLS = ("gops_hip_version", "gops_rollout_workspace_bytes", "gops_ro
                     "gops_env_constraint", "gops_polyak_update", "gops_value_loss", "gops_mean_loss", "gops_rollout_backward_update",
                     "gops_value_backward_update", "gops_poly_rollout_workspace_bytes", "gops_poly_rollout_forward",
                     "gops_poly_rollout_backward", "gops_poly_value_workspace_bytes", "gops_poly_value_forward",
-                    "gops_poly_value_backward", "gops_rpi_state_bytes", "gops_rpi_evaluate")
+                    "gops_poly_value_backward", "gops_rpi_state_bytes", "gops_rpi_evaluate",
+                    "gops_episode_workspace_bytes", "gops_episode_rollout")
 
 _ERR = {-1: "GOPS_ERR_BAD_ARG", -2: "GOPS_ERR_UNSUPPORTED", -3: "GOPS_ERR_WORKSPACE"}
 
@@ -737,6 +747,52 @@ class RpiEvaluator:
                                       float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),
               "gops_rpi_evaluate")
         return self.result
+
+
+class EpisodeRollout:
+    """Whole closed-loop evaluation episodes in ONE launch (`gops_episode_rollout`, csrc/rollout_episode.hip): policy, DATA-env step,
+    termination, time limit and return of `episodes` episodes over up to `max_steps` steps.  `env` must carry data_env = 1; the policy
+    weights are read in place at every call.  A description the kernel refuses raises (GOPS_ERR_UNSUPPORTED / _BAD_ARG)."""
+
+    def __init__(self, env: GopsEnv, policy: GopsMlp, *, episodes: int, max_steps: int, device: Optional[torch.device] = None,
+                 workspace_bytes: Optional[int] = None):
+        self.env, self.policy, self.episodes, self.max_steps = env, policy, int(episodes), int(max_steps)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        nbytes = lib().gops_episode_workspace_bytes(C.byref(env), C.byref(policy), self.episodes, self.max_steps)
+        if workspace_bytes is None:
+            if nbytes == 0:   # ask the entry point itself for the reason
+                check(lib().gops_episode_rollout(C.byref(env), C.byref(policy), self.episodes, self.max_steps, None, None, None, 0, None),
+                      "gops_episode_rollout")
+                raise RuntimeError("gops_episode_workspace_bytes: description refused")
+            workspace_bytes = nbytes
+        self.workspace = torch.empty(max(int(workspace_bytes), 1), dtype=torch.uint8, device=self.device)
+        self._workspace_bytes = int(workspace_bytes)
+
+    def set_policy(self, policy: GopsMlp):
+        self.policy = policy
+
+    def run(self, init: Dict[str, torch.Tensor], *, trace: bool = False, trace_fill: Optional[float] = None) -> Dict[str, torch.Tensor]:
+        """`init`: obs [E, obs_dim] (+ state / ref_points / path_num / u_num / ref_time for the vehicle families).  Returns device
+        tensors ret [E], length [E] (int32), terminated [E] and - with `trace` - trace_obs [E, T, obs_dim], trace_act [E, T, act_dim],
+        trace_rew [E, T] (rows beyond `length` keep `trace_fill`, or are uninitialised when it is None).  Enqueues only."""
+        E, T, dev = self.episodes, self.max_steps, self.device
+        assert init["obs"].shape[0] == E
+        io, out = GopsStepIO(), GopsEpisodeOut()
+        io.obs = _ptr(init["obs"])
+        for k in ("state", "ref_points", "path_num", "u_num", "ref_time"):
+            if init.get(k) is not None:
+                setattr(io, k, _ptr(init[k]))
+        res = dict(ret=torch.empty(E, dtype=torch.float32, device=dev), length=torch.empty(E, dtype=torch.int32, device=dev),
+                   terminated=torch.empty(E, dtype=torch.float32, device=dev))
+        if trace:
+            mk = (lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)) if trace_fill is None else \
+                 (lambda *sh: torch.full(sh, float(trace_fill), dtype=torch.float32, device=dev))
+            res.update(trace_obs=mk(E, T, self.env.obs_dim), trace_act=mk(E, T, self.env.act_dim), trace_rew=mk(E, T))
+        for k, v in res.items():
+            setattr(out, k, v.data_ptr())
+        check(lib().gops_episode_rollout(C.byref(self.env), C.byref(self.policy), E, T, C.byref(io), C.byref(out),
+                                         self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_episode_rollout")
+        return res
 
 
 class ValueNet:

@@ -120,7 +120,8 @@ class TrainerBase:
         return folder
 
     def _evaluate(self):
-        call_maybe_remote(self.evaluator, "load_state_dict", {k: v.cpu() for k, v in self.networks.state_dict().items()})
+        if not getattr(self.evaluator, "on_device", False):   # (a device evaluator shares self.networks: nothing to copy)
+            call_maybe_remote(self.evaluator, "load_state_dict", {k: v.cpu() for k, v in self.networks.state_dict().items()})
         total_avg_return = call_maybe_remote(self.evaluator, "run_evaluation", self.iteration)
         self.last_eval_iteration = self.iteration
         if total_avg_return >= self.best_tar and self.iteration >= self.max_iteration / 5:

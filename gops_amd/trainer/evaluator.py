@@ -1,0 +1,192 @@
+"""In-process evaluator on the MI355X: the surface of the reference's `Evaluator` (gops/trainer/evaluator.py:18-95 -
+`load_state_dict`, `run_an_episode`, `run_n_episodes`, `run_evaluation`, `num_eval_episode`, `eval_save`) with every episode of an
+evaluation in ONE launch (`gops_episode_rollout`, csrc/rollout_episode.hip): policy, data-env step, termination, time limit and
+return over the whole horizon, no host round trip per step.
+
+The evaluator shares the learner's `networks` container (`on_device = True`: `TrainerBase._evaluate` copies no state_dict); the
+kernel reads the live parameter tensors in place.  Episodes start from the data envs' reset distributions
+(`sampler/reset_pool.py`, seed offset +400 as evaluator.py:28) or from explicit initial conditions (`run_episodes`).  Rewards are
+the data env's own: like the reference (evaluator.py:20-25: reward_scale = None, repeat_num = None) the env description is built
+without ShapingReward and ActionRepeat.
+
+What the kernel refuses (POLY policies, pyth_mobilerobot - its obstacle noise is drawn per step -, fp16) runs the same episodes
+through the per-step device loop (so do `ScaleObservation` on the vehicle families and hidden widths the kernel's LDS plan does
+not hold; `Evaluator.path` names the path the last call took and why): torch `policy(obs)` + `gops_env_step(data_env)` per step, a `finished` mask kept on the device
+and read back once at the end.  Env models whose data env is not restated in the step kernel raise.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from gops_amd import hip_backend as hb
+from gops_amd.algorithm.base import is_poly
+from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, NOT_RESTATED, draw_reset_pool
+
+# TimeLimit of the data envs where create_env registers one (gops/create_pkg/create_env.py:142-148 takes the env's own
+# `max_episode_steps` attribute): pyth_idpendulum.py:51, pyth_veh3dofconti.py:114, pyth_veh2dofconti.py:105,
+# pyth_mobilerobot.py:30; pyth_lq: resources/lq_base.py:161 (the config's max_step).  gym_cartpoleconti registers none.
+_REGISTERED_STEPS = {"pyth_idpendulum": 500, "pyth_veh3dofconti": 200, "pyth_veh2dofconti": 200, "pyth_mobilerobot": 200}
+_DATA_KINDS = (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_VEH, hb.ENV_CARTPOLE, hb.ENV_VEH2DOF, hb.ENV_MOBILEROBOT)
+
+
+def registered_episode_steps(cfg: dict, default: int = 200) -> int:
+    env_id = cfg.get("env_id", "")
+    if env_id == "pyth_lq":
+        from gops_amd.env.env_ocp.resources import lq_configs
+        lqc = cfg.get("lq_config") or "s3a1"
+        return int((lqc if isinstance(lqc, dict) else getattr(lq_configs, "config_" + lqc))["max_step"])
+    return _REGISTERED_STEPS.get(env_id, default)
+
+
+class Evaluator:
+    on_device = True   # trainers: the evaluator shares the learner's networks, no state_dict copy
+
+    def __init__(self, index=0, *, env_model, networks, cfg: dict, num_eval_episode: int, eval_save: bool = True,
+                 save_folder=None, seed: int = 0, max_episode_steps: int = None, device="cuda", fused: bool = True, **kwargs):
+        """cfg: workload dict (env_id, pre_horizon, lq_config) as `DeviceEnvSampler` takes it; env_model: the wrapped model of
+        `create_env_model`; networks: the learner's container (its `policy` is evaluated in place).  `max_episode_steps`: None =
+        the data env's registered limit, else 200.  `fused=False` forces the per-step loop."""
+        self.cfg, self.env_model, self.networks = dict(cfg), env_model, networks
+        base = getattr(env_model, "unwrapped", env_model)
+        if getattr(base, "ref_c", None) is not None:
+            raise RuntimeError("Evaluator draws its initial states from the DEFAULT reference trajectories "
+                               "(gops_amd.utils.synthetic); a model with custom path_para / u_para needs explicit initial conditions")
+        if getattr(base, "hip_kind", None) not in _DATA_KINDS or self.cfg.get("env_id", "").endswith("errcstr"):
+            raise RuntimeError(NOT_RESTATED.format(env_id=self.cfg.get("env_id")))
+        self.num_eval_episode, self.eval_save, self.save_folder = int(num_eval_episode), bool(eval_save), save_folder
+        self.seed = int(seed) + int(index) + 400   # evaluator.py:28
+        self.max_episode_steps = int(registered_episode_steps(self.cfg) if max_episode_steps is None else max_episode_steps)
+        self.device = torch.device(device)
+        if torch.cuda.is_available() and not next(networks.parameters()).is_cuda:   # (built from kwargs: not the learner's container)
+            networks.to(self.device)
+        self.fused = bool(fused)
+        self.render = False
+        self.print_time, self.print_iteration = 0, -1
+        self._evals = 0
+        self._henv, self._rollouts = None, {}
+        self.last = None   # device results of the last run_episodes call
+        self.path = None   # how the last run_episodes call ran: "fused", or "loop: <why the kernel was not used>"
+
+    def load_state_dict(self, state_dict):
+        """The reference's surface; a trainer that knows `on_device` never calls it (the networks are shared)."""
+        self.networks.load_state_dict(state_dict)
+
+    # ---- descriptions ---------------------------------------------------------------------------
+    def _hip_env(self):
+        if self._henv is None:
+            pol = self.networks.policy
+            env = self.env_model.hip_env(pol.act_low_lim.cpu().numpy(), pol.act_high_lim.cpu().numpy(), data_env=True)
+            env = hb.GopsEnv.from_buffer_copy(env)   # (the model caches its description: this one is the evaluator's own)
+            env.shaping, env.reward_scale, env.reward_shift = 0, 1.0, 0.0
+            env.repeat_num, env.repeat_last_reward = 0, 0
+            self._henv = env
+        return self._henv
+
+    def kernel_refuses(self):
+        """None when `gops_episode_rollout` takes this evaluator's env and policy, else the reason."""
+        pol = self.networks.policy
+        if is_poly(pol):
+            return "POLY policy"
+        env = self._hip_env()
+        if env.kind == hb.ENV_MOBILEROBOT:
+            return "pyth_mobilerobot draws its obstacle noise per step"
+        if hb.lib().gops_episode_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), 1, 1) == 0:
+            # gops_hip.h lists them: ScaleObservation on the vehicle families or beyond 8 observations, ActionRepeat, hidden widths
+            # that are no multiple of 16 or beyond the LDS plan (~1100)
+            return "env / policy description outside the episode kernel (scaled vehicle observations, hidden widths)"
+        return None
+
+    def draw_initial_conditions(self, n: int) -> dict:
+        """n initial conditions from the data env's reset distribution; a new draw per evaluation, reproducible for a seed."""
+        pool = draw_reset_pool(self.cfg, self.env_model, self.seed + 7919 * self._evals, n, self.device, True)
+        self._evals += 1
+        return pool
+
+    # ---- episodes -------------------------------------------------------------------------------
+    @torch.no_grad()
+    def run_episodes(self, init: dict, *, trace: bool = False, fused: bool = None, trace_fill: float = None) -> dict:
+        """All episodes of `init` (obs [E, obs_dim] + info tensors, on the device): ret [E], length [E] int32, terminated [E] and
+        - with `trace` - trace_obs / trace_act / trace_rew.  Device tensors; nothing is read back here."""
+        init = {k: v.to(self.device, torch.float32).contiguous() for k, v in init.items() if k == "obs" or k in INFO_KEYS}
+        fused = self.fused if fused is None else fused
+        why = self.kernel_refuses() if fused else "fused=False"
+        self.path = "fused" if why is None else "loop: " + why
+        if why is None:
+            E = init["obs"].shape[0]
+            mlp = self.networks.policy.hip_mlp()
+            key = (E, self.max_episode_steps)
+            ro = self._rollouts.get(key)
+            if ro is None:
+                ro = self._rollouts[key] = hb.EpisodeRollout(self._hip_env(), mlp, episodes=E, max_steps=self.max_episode_steps,
+                                                             device=self.device)
+            ro.set_policy(mlp)
+            self.last = ro.run(init, trace=trace, trace_fill=trace_fill)
+        else:
+            self.last = self.step_loop(init, trace=trace, trace_fill=trace_fill)
+        return self.last
+
+    @torch.no_grad()
+    def step_loop(self, init: dict, *, trace: bool = False, trace_fill: float = None, sync_every_step: bool = False) -> dict:
+        """The same episodes through the per-step device loop (torch policy + one `gops_env_step` launch per step).  The
+        `finished` mask stays on the device; `sync_every_step` adds the host read per step the sampler's bookkeeping has."""
+        env, policy, T = self._hip_env(), self.networks.policy, self.max_episode_steps
+        obs, info = init["obs"], {k: init[k] for k in INFO_KEYS if k in init}
+        E, dev = obs.shape[0], obs.device
+        zeros = torch.zeros(E, device=dev)
+        ret = torch.zeros(E, dtype=torch.float64, device=dev)
+        length = torch.zeros(E, dtype=torch.int32, device=dev)
+        terminated = torch.zeros(E, device=dev)
+        finished = torch.zeros(E, dtype=torch.bool, device=dev)
+        res = {}
+        if trace:
+            mk = (lambda *sh: torch.empty(*sh, device=dev)) if trace_fill is None else (lambda *sh: torch.full(sh, float(trace_fill), device=dev))
+            res.update(trace_obs=mk(E, T, env.obs_dim), trace_act=mk(E, T, env.act_dim), trace_rew=mk(E, T))
+        for t in range(T):
+            act = policy(obs).contiguous()
+            obs2, rew, done, info2 = hb.env_step(env, obs, act, zeros, info)
+            live = ~finished
+            if trace:
+                res["trace_obs"][:, t] = torch.where(live[:, None], obs, res["trace_obs"][:, t])
+                res["trace_act"][:, t] = torch.where(live[:, None], act, res["trace_act"][:, t])
+                res["trace_rew"][:, t] = torch.where(live, rew, res["trace_rew"][:, t])
+            ret += torch.where(live, rew.double(), torch.zeros_like(ret))
+            length += live.to(torch.int32)
+            terminated = torch.where(live & (done != 0), torch.ones_like(terminated), terminated)
+            finished = finished | (done != 0)
+            obs, info = obs2, {k: info2[k] for k in info}
+            if sync_every_step and bool(finished.all().item()):
+                break
+        res.update(ret=ret.float(), length=length, terminated=terminated)
+        return res
+
+    # ---- the reference's surface ----------------------------------------------------------------
+    def _save(self, res, iteration, first_index):
+        folder = os.path.join(self.save_folder, "evaluator")
+        os.makedirs(folder, exist_ok=True)
+        host = {k: v.cpu().numpy() for k, v in res.items()}
+        for e in range(host["ret"].shape[0]):
+            n = int(host["length"][e])
+            np.save(os.path.join(folder, "iter{}_ep{}".format(iteration, first_index + e)),
+                    {"reward_list": list(host["trace_rew"][e, :n]), "action_list": list(host["trace_act"][e, :n]),
+                     "obs_list": list(host["trace_obs"][e, :n])})
+
+    def run_n_episodes(self, n, iteration):
+        if self.print_iteration != iteration:
+            self.print_iteration, self.print_time = iteration, 0
+        save = self.eval_save and self.save_folder is not None
+        res = self.run_episodes(self.draw_initial_conditions(int(n)), trace=save)
+        mean = float(res["ret"].double().mean().item())   # the one sync of an evaluation (best_tar needs a Python float)
+        if save:
+            self._save(res, iteration, self.print_time)
+        self.print_time += int(n)
+        return mean
+
+    def run_an_episode(self, iteration, render=False):
+        if render:
+            raise NotImplementedError("gops_amd's Evaluator does not render")
+        return self.run_n_episodes(1, iteration)
+
+    def run_evaluation(self, iteration):
+        return self.run_n_episodes(self.num_eval_episode, iteration)

@@ -23,14 +23,11 @@ data envs' reset distributions (`gops_amd.utils.synthetic.make_batch`), generate
 """
 import time
 
-import numpy as np
 import torch
 
 from gops_amd import hip_backend as hb
-from gops_amd.utils.synthetic import make_batch
+from gops_amd.trainer.sampler.reset_pool import INFO_KEYS as _INFO, NOT_RESTATED, draw_reset_pool
 from gops_amd.utils.tensorboard_setup import tb_tags
-
-_INFO = ("state", "ref_points", "path_num", "u_num", "ref_time")
 
 
 class DeviceEnvSampler:
@@ -53,9 +50,7 @@ class DeviceEnvSampler:
         kind = getattr(getattr(env_model, "unwrapped", env_model), "hip_kind", None)
         if self.data_env and (kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_VEH, hb.ENV_CARTPOLE, hb.ENV_VEH2DOF, hb.ENV_MOBILEROBOT)
                               or self.cfg.get("env_id", "").endswith("errcstr")):
-            raise RuntimeError(f"the DATA environment of {self.cfg.get('env_id')} is not restated in the step kernel "
-                               "(pyth_lq, pyth_idpendulum, pyth_veh3dofconti, pyth_veh2dofconti, pyth_mobilerobot and "
-                               "gym_cartpoleconti are): pass env_step='model'")
+            raise RuntimeError(NOT_RESTATED.format(env_id=self.cfg.get("env_id")))
         self.networks = None
         self.total = 0
         self._pool, self._pool_pos, self._pools_made = None, 0, 0
@@ -72,27 +67,7 @@ class DeviceEnvSampler:
         """k fresh initial conditions (device tensors) from the pool; refills the pool when it runs dry."""
         size = self.pool_factor * self.n
         if self._pool is None or self._pool_pos + k > size:
-            host = make_batch(self.cfg, self.seed + 7919 * self._pools_made, batch=size)
-            if self.cfg["env_id"] == "pyth_mobilerobot" and self.data_env:
-                # the data env's own reset distribution (pyth_mobilerobot.py:31-54, 95-106: robot and obstacle uniform in the work
-                # space, w = 0, tracking errors of the robot state); make_batch's near-collision starts exist for the parity fixtures
-                rng = np.random.RandomState(self.seed + 7919 * self._pools_made)
-                ego = rng.uniform([0.0, -1.0, -0.6, 0.0, 0.0], [2.7, 1.0, 0.6, 0.3, 0.0], size=(size, 5))
-                obst = rng.uniform([3.5, -3.0, np.pi / 2 - 0.3, 0.0, 0.0], [6.0, 3.0, np.pi / 2 + 0.3, 0.5, 0.0], size=(size, 5))
-                ego, obst = ego.astype(np.float32), obst.astype(np.float32)   # (reset casts the drawn state first, :100-101)
-                track = np.stack((ego[:, 1], ego[:, 2], ego[:, 3] - np.float32(0.3)), axis=1)   # path y = 0, phi = 0, v_desired 0.3
-                host["obs"] = torch.from_numpy(np.concatenate((ego, track, obst), axis=1))
-            if self.cfg["env_id"] == "gym_cartpoleconti" and self.data_env:
-                # the data env's own reset distribution (env_gym/gym_cartpoleconti.py:139-147: uniform +-0.05 in every state);
-                # make_batch's wide cartpole states exist to exercise the done thresholds inside short rollouts
-                rng = np.random.RandomState(self.seed + 7919 * self._pools_made)
-                host["obs"] = torch.from_numpy(rng.uniform(-0.05, 0.05, size=(size, 4)).astype(np.float32))
-            self._pool = {key: v.to(self.device) for key, v in host.items() if key == "obs" or key in _INFO}
-            # ScaleObservationData (scale_observation.py:53-62): the sampler hands out (obs + shift) * scale
-            sc, sh = getattr(self.env_model, "obs_scale", None), getattr(self.env_model, "obs_shift", None)
-            if sc is not None or sh is not None:
-                as_t = lambda v, d: torch.as_tensor(d if v is None else v, dtype=torch.float32, device=self.device)  # noqa: E731
-                self._pool["obs"] = (self._pool["obs"] + as_t(sh, 0.0)) * as_t(sc, 1.0)
+            self._pool = draw_reset_pool(self.cfg, self.env_model, self.seed + 7919 * self._pools_made, size, self.device, self.data_env)
             self._pool_pos, self._pools_made = 0, self._pools_made + 1
         sl = slice(self._pool_pos, self._pool_pos + k)
         self._pool_pos += k

@@ -538,6 +538,36 @@ int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const 
                       const float* target_weights, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
                       double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): whole closed-loop EVALUATION episodes in one launch
+ * (csrc/rollout_episode.hip) - the loop of Evaluator.run_an_episode (gops/trainer/evaluator.py:45-86): a_t = policy(obs_t) (a
+ * FiniteHorizonPolicy - sizes[0] = obs_dim + 1 - always gets virtual_t = 1, the default the reference evaluator calls it with), the
+ * tanh squash / act limits, then one DATA-env step (gops_env_step with GopsEnv.data_env = 1: the same device function), until the
+ * first `done` or `max_steps`.  Rewards are the data env's own; env->shaping is honoured as gops_env_step honours it.
+ * Episodes run in tiles of GOPS_TILE per workgroup; the MLP contractions are exact fp32 (v_mfma_f32_16x16x4_f32) whatever
+ * policy->variant_flags says; weights are read in place from the tensors `policy` points to.  No host sync, no device allocation.
+ *   init:  obs [E, obs_dim] and, for the vehicle families, state / ref_points / path_num / u_num / ref_time as gops_env_step takes
+ *          them: the per-episode initial condition (read only; every other field is ignored).  The appended reference point is
+ *          evaluated in the kernel (strict host points - ref_appended - are out of scope for evaluation).
+ *   out:   ret [E] = sum of the rewards up to and including the step that ends the episode (summed in double, rounded once),
+ *          length [E] = steps taken, terminated [E] = 1 when `done` ended the episode, 0 when it reached max_steps;
+ *          trace_obs [E][max_steps][obs_dim], trace_act [E][max_steps][act_dim] (the policy's output, before ScaleAction /
+ *          ClipAction), trace_rew [E][max_steps]: optional (NULL), rows beyond `length` are left untouched.
+ * Accepted: GOPS_ENV_LQ, _IDPENDULUM, _CARTPOLE, _VEH3DOFCONTI, _VEH2DOF (without cstr_err) with data_env = 1 and repeat_num <= 1;
+ * MLP policies with 2 .. GOPS_MAX_LAYERS layers, hidden widths multiples of 16 (up to ~1100: two activation tiles must fit in LDS),
+ * every GOPS_ACT_*, GOPS_DTYPE_F32; weight tensors at any 4-byte alignment (16-byte loads are taken only where the pointer allows).
+ * GOPS_ERR_UNSUPPORTED: any other env kind (mobilerobot draws noise per step, the constrained
+ * vehicle models, GOPS_ENV_PENDULUM has no data-env restatement), POLY nets (n_layers = 1), GOPS_DTYPE_F16.  GOPS_ERR_BAD_ARG:
+ * data_env = 0, shapes that do not match the env kind, NULL pointers.  GOPS_ERR_WORKSPACE: workspace_bytes too small.
+ * gops_episode_workspace_bytes: 0 for a description gops_episode_rollout rejects. */
+struct GopsEpisodeOut {
+    float* ret; int32_t* length; float* terminated;
+    float* trace_obs; float* trace_act; float* trace_rew;
+};
+typedef struct GopsEpisodeOut GopsEpisodeOut;
+size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps);
+int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps, const GopsStepIO* init,
+                         const GopsEpisodeOut* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
