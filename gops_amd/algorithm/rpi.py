@@ -5,10 +5,14 @@ Each `local_update` is one Newton iteration: the value weights take up to `max_s
 loss mean|U(x, u', w') + dV/dx . f(x, u', w')| of states the target weights' action / adversary pair drives, until the Hamiltonian
 norm on a held-out set has fallen to 0.88 of its value at the start; then the target takes the weights.
 
+The value function is a POLY StateValue of degree 2 or an MLP StateValue (one or two hidden layers, widths multiples of 16 up to 64,
+elu / gelu / tanh / sigmoid, linear output).
+
 Two execution paths with one meaning:
-  * `use_gpu=True`: the whole policy evaluation is ONE launch (`hip_backend.RpiEvaluator`, csrc/rollout_rpi.hip), one host sync per
-    `local_update`;
-  * `use_gpu=False`: the same loop in eager fp32 torch on the host (`_evaluate_host`), with the analytic dV/dx of the degree-2 features.
+  * `use_gpu=True`: the whole policy evaluation is ONE launch (`hip_backend.RpiEvaluator`, csrc/rollout_rpi.hip, for POLY;
+    `hip_backend.RpiMlpEvaluator`, csrc/rollout_rpi_mlp.hip, for an MLP), one host sync per `local_update`;
+  * `use_gpu=False`: the same loop in eager fp32 torch on the host (`_evaluate_host`, with the analytic dV/dx of the degree-2
+    features; `_evaluate_host_mlp`, with autograd for dV/dx and the double backward).
 Both take their reset states from `self.reset_source`.  The default one draws from `np.random` in the reference's order; the device
 path pre-draws a pool for `max_step_update_value + 1` resets (one bulk draw, at most MAX_POOL_BYTES) and, once the launch has reported
 n steps, rewinds the generator and consumes n + 1, so the global stream stays the reference's.
@@ -21,7 +25,10 @@ The reference is the yardstick, quirks included:
     step from then on.  `step_count` is that counter; `step_per_episode` is the one the algorithm assigns (what
     `alg.env_model.step_per_episode` shows in the reference);
   * `max_step_per_episode` is drawn at construction (twice: algorithm and container each build a model) and never again.
-Out of scope (NotImplementedError): MLP / GAUSS value functions, a degree other than 2, `initial_weight`, `is_adversary=False`."""
+Out of scope (NotImplementedError): GAUSS value functions, a POLY degree other than 2, `initial_weight`, `is_adversary=False`, and for
+an MLP: relu / selu (their first derivative jumps, so dV/dx - and the action and adversary derived from it - is discontinuous: two
+fp32 orderings cannot be held to a tolerance across the jump), three or more hidden layers, widths above 64 or no multiple of 16, a
+non-linear output activation."""
 __all__ = ["ApproxContainer", "RPI"]
 
 import time
@@ -42,11 +49,26 @@ CONTINUE_FACTOR = 0.88
 MAX_POOL_BYTES = 1 << 30   # device path: bound on the pre-drawn reset pool (the defaults, 10001 x 2 x 64 floats, take 5 MB)
 
 
+MLP_ACTIVATIONS, MLP_MAX_WIDTH, MLP_WIDTH_STEP = ("elu", "gelu", "tanh", "sigmoid"), 64, 16
+
+
 def _refuse_unsupported(kwargs):
-    if kwargs.get("value_func_type") != "POLY":
-        raise NotImplementedError(f"RPI: value_func_type {kwargs.get('value_func_type')!r} is not supported (POLY only)")
-    if kwargs.get("value_degree") != 2:
+    kind = kwargs.get("value_func_type")
+    if kind not in ("POLY", "MLP"):
+        raise NotImplementedError(f"RPI: value_func_type {kind!r} is not supported (POLY or MLP)")
+    if kind == "POLY" and kwargs.get("value_degree") != 2:
         raise NotImplementedError(f"RPI: value_degree {kwargs.get('value_degree')!r} is not supported (2 only)")
+    if kind == "MLP":   # (value_degree is ignored)
+        sizes, act = list(kwargs.get("value_hidden_sizes") or []), kwargs.get("value_hidden_activation")
+        if act not in MLP_ACTIVATIONS:
+            raise NotImplementedError(f"RPI: value_hidden_activation {act!r} is not supported (one of {', '.join(MLP_ACTIVATIONS)}: "
+                                      "dV/dx must be continuous)")
+        if not 1 <= len(sizes) <= 2:
+            raise NotImplementedError(f"RPI: {len(sizes)} hidden layers are not supported (one or two)")
+        if any(h < MLP_WIDTH_STEP or h > MLP_MAX_WIDTH or h % MLP_WIDTH_STEP for h in sizes):
+            raise NotImplementedError(f"RPI: value_hidden_sizes {sizes} are not supported (multiples of {MLP_WIDTH_STEP} up to {MLP_MAX_WIDTH})")
+        if kwargs.get("value_output_activation", "linear") != "linear":
+            raise NotImplementedError(f"RPI: value_output_activation {kwargs.get('value_output_activation')!r} is not supported (linear only)")
     if kwargs.get("initial_weight", None) is not None:
         raise NotImplementedError("RPI: initial_weight is not supported (the reference itself fails there); load a state_dict instead")
     if not kwargs.get("is_adversary", False):
@@ -63,21 +85,43 @@ def value_gradient(weight: torch.Tensor, norm: torch.Tensor, obs: torch.Tensor) 
     return ((obs * norm) @ sym) * norm
 
 
+def mlp_value_gradient(net, obs: torch.Tensor) -> torch.Tensor:
+    """dV/dx [B, S] of an MLP StateValue at `obs` (autograd; no graph is kept)."""
+    with torch.enable_grad():
+        x = obs.detach().clone().requires_grad_(True)
+        (dv,) = torch.autograd.grad(net(x).sum(), x)
+    return dv
+
+
 class ApproxContainer(ApprBase):
-    """The value function and its target: a POLY StateValue of degree 2, weights zero, bias as nn.Linear initialises it."""
+    """The value function and its target.  POLY StateValue of degree 2: weights zero, bias as nn.Linear initialises it.  MLP
+    StateValue: after the module's own initialisation every Linear layer, in module order, draws its weight from
+    uniform(+-sqrt(6 / (fan_in + fan_out))) and zeroes its bias (reference rpi.py:64-71)."""
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
         _refuse_unsupported(kwargs)
         self.env_model = create_env_model(**kwargs)
         self.value = create_apprfunc(**get_apprfunc_dict("value", **kwargs))
-        self.value.v.weight.data.fill_(0)
+        self.is_mlp = kwargs["value_func_type"] == "MLP"
+        if self.is_mlp:
+            for m in self.value.v:
+                if isinstance(m, torch.nn.Linear):
+                    fan_out, fan_in = m.weight.shape
+                    bound = np.sqrt(6.0 / (fan_in + fan_out))
+                    m.weight.data.uniform_(-bound, bound)
+                    m.bias.data.fill_(0)
+        else:
+            self.value.v.weight.data.fill_(0)
         self.value_target = deepcopy(self.value)
 
     def _pair(self, batch_obs):
         net = self.value_target
         dev = batch_obs.device
-        dv = value_gradient(net.v.weight.detach(), net.norm_matrix.to(dev), batch_obs.detach())
+        if self.is_mlp:
+            dv = mlp_value_gradient(net, batch_obs)
+        else:
+            dv = value_gradient(net.v.weight.detach(), net.norm_matrix.to(dev), batch_obs.detach())
         cpu = batch_obs.detach().cpu(), dv.cpu()   # the game models are host objects
         return self.env_model.best_act(*cpu).to(dev), self.env_model.worst_adv(*cpu).to(dev)
 
@@ -156,7 +200,7 @@ class RPI(AlgorithmBase):
         self.use_gpu = bool(kwargs.get("use_gpu", False))
         self.record_trace = False   # device path: keep (loss, norm_after) of every step in `self.trace` (tests)
         self.trace = None
-        self.weight_trace = None    # host path: the weights after every step of the last local_update
+        self.weight_trace = None    # host path: the weights (MLP: all parameters, flattened in parameters() order) after every step of the last local_update
         self.min_row_ratio = None   # host path: min over its loss rows of |h_i| / mean|h|
 
         self.env_model = create_env_model(**kwargs)
@@ -168,8 +212,9 @@ class RPI(AlgorithmBase):
         self.networks = ApproxContainer(**kwargs)
         self.learning_rate = learning_rate
         self.reset_source = NumpyResetSource(self.env_model.unwrapped)
-        # Adam (betas (0.9, 0.99), no weight decay) on the value weights; the bias takes no gradient and never moves
-        n_feat = self.networks.value.v.weight.numel()
+        # Adam (betas (0.9, 0.99), no weight decay) on the value weights; the (output) bias takes no gradient and never moves
+        self.is_mlp = self.networks.is_mlp
+        n_feat = sum(q.numel() for q in self.networks.value.parameters()) if self.is_mlp else self.networks.value.v.weight.numel()
         self._adam = dict(step=0, exp_avg=torch.zeros(n_feat), exp_avg_sq=torch.zeros(n_feat))
         self._evaluator = None
         if self.use_gpu:
@@ -269,23 +314,92 @@ class RPI(AlgorithmBase):
         self.min_row_ratio = min(ratios)   # smallest |h_i| / mean|h| of a loss row: how far every sign(h_i) is from flipping
         return loss
 
+    def _hamiltonian_mlp(self, obs, pair):
+        """h [B] of the VALUE net at `obs` for the action / adversary `pair` (wrapped inside `forward`), differentiable in the
+        net's parameters: dV/dx by autograd with the graph kept."""
+        with torch.no_grad():
+            _, reward, _, info = self.env_model.forward(obs, pair, torch.zeros(obs.shape[0], dtype=torch.bool), {})
+        x = obs.detach().clone().requires_grad_(True)
+        (dv,) = torch.autograd.grad(self.networks.value(x).sum(), x, create_graph=True)
+        return -reward + (dv * info["delta_state"]).sum(1)
+
+    def _adam_step_mlp(self, params, grads):
+        """torch.optim.Adam's single-tensor step per parameter; a parameter without a gradient (the output bias) is skipped."""
+        st, (beta1, beta2) = self._adam, ADAM_BETAS
+        st["step"] += 1
+        step_size = self.learning_rate / (1 - beta1 ** st["step"])
+        bc2_sqrt = (1 - beta2 ** st["step"]) ** 0.5
+        o = 0
+        for q, grad in zip(params, grads):
+            n = q.numel()
+            if grad is not None:
+                m, v, grad = st["exp_avg"][o:o + n], st["exp_avg_sq"][o:o + n], grad.reshape(-1)
+                m.lerp_(grad, 1 - beta1)
+                v.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+                q.data.view(-1).addcdiv_(m, (v.sqrt() / bc2_sqrt).add_(ADAM_EPS), value=-step_size)
+            o += n
+
+    def _evaluate_host_mlp(self):
+        nets, model = self.networks, self.env_model.unwrapped
+        params = list(nets.value.parameters())
+        self.set_state = self.reset_source.next()
+        set_pair = nets.action_and_adversary(self.set_state)
+        norm = lambda: float(self._hamiltonian_mlp(self.set_state, set_pair).detach().abs().mean())  # noqa: E731
+        self.norm_hamiltonian_before = norm()
+        loss, trace, weights, ratios = 0.0, [], [], []
+        for _ in range(self.max_step_update_value):
+            self.num_update_value += 1
+            # sample(): one bare step under the target's raw pair, then the reset select
+            obs = self._obs
+            pair = nets.action_and_adversary(obs)
+            with torch.no_grad():
+                next_obs, _, self.done, info = model.step(pair)
+                reset = self.done | info["TimeLimit.truncated"]
+                self._obs = torch.where(reset.unsqueeze(-1), self.reset_source.next(), next_obs)
+                model.parallel_state = self._obs.clone()
+                self.env_model.step_per_episode = torch.where(reset, model.initial_step(), self.env_model.step_per_episode)
+            # loss, gradient (the double backward) and Adam step at the pre-step states
+            h = self._hamiltonian_mlp(obs, pair)
+            loss_t = h.abs().mean()
+            grads = torch.autograd.grad(loss_t, params, allow_unused=True)
+            loss = float(loss_t.detach())
+            ratios.append(float(h.detach().abs().min()) / loss)
+            with torch.no_grad():
+                self._adam_step_mlp(params, grads)
+            self.norm_hamiltonian_after = norm()
+            trace.append((loss, self.norm_hamiltonian_after))
+            weights.append(torch.cat([q.detach().reshape(-1) for q in params]))
+            if not self.continue_evaluation():
+                break
+        self.trace, self.weight_trace = torch.tensor(trace, dtype=torch.float32), torch.stack(weights)
+        self.min_row_ratio = min(ratios)
+        return loss
+
     # ---- the device path ------------------------------------------------------------------------------------------------------
     def _device_evaluator(self):
         if self._evaluator is None:
             from gops_amd import hip_backend as hb
             model, dev = self.env_model.unwrapped, next(self.networks.parameters()).device
             consts = self.env_model.rpi_constants()
-            norm = self.networks.value.norm_matrix.cpu().numpy()
-            consts[hb.RPI_C_NORM:hb.RPI_C_NORM + len(norm)] = norm
-            ev = hb.RpiEvaluator(model.rpi_kind, model.sample_batch_size, model.state_dim, consts, dev)
+            if self.is_mlp:
+                ev = hb.RpiMlpEvaluator(model.rpi_kind, model.sample_batch_size, model.state_dim, consts, self.networks.value.hip_mlp(),
+                                        self.networks.value_target.hip_mlp(), dev)
+            else:
+                norm = self.networks.value.norm_matrix.cpu().numpy()
+                consts[hb.RPI_C_NORM:hb.RPI_C_NORM + len(norm)] = norm
+                ev = hb.RpiEvaluator(model.rpi_kind, model.sample_batch_size, model.state_dim, consts, dev)
             ev.lanes().copy_(self._obs.t())
             count = model.step_per_episode.to(dev)
             shown = self.env_model.__dict__.get("step_per_episode")   # assigned on the wrapper yet? (a host-path run before)
             ev.counters().copy_(torch.stack([count, torch.full_like(count, -1.0) if shown is None else shown.to(dev)]))
-            n_feat = self._adam["exp_avg"].numel()
-            ev.state[:n_feat] = self._adam["exp_avg"].to(dev)
-            ev.state[10:10 + n_feat] = self._adam["exp_avg_sq"].to(dev)
-            ev.state[20] = float(self._adam["step"])
+            if self.is_mlp:
+                ev.moments().copy_(torch.stack([self._adam["exp_avg"], self._adam["exp_avg_sq"]]))
+                ev.state[0] = float(self._adam["step"])
+            else:
+                n_feat = self._adam["exp_avg"].numel()
+                ev.state[:n_feat] = self._adam["exp_avg"].to(dev)
+                ev.state[10:10 + n_feat] = self._adam["exp_avg_sq"].to(dev)
+                ev.state[20] = float(self._adam["step"])
             self._max_step_dev = model.max_step_per_episode.to(device=dev, dtype=torch.float32)
             self._evaluator = ev
         return self._evaluator
@@ -297,9 +411,12 @@ class RPI(AlgorithmBase):
         pool_dev = pool.to(ev.device)
         self.set_state = pool[0].t().contiguous()
         trace = torch.zeros(n, 2, dtype=torch.float32, device=ev.device) if self.record_trace else None
-        weight, target = self.networks.value.v.weight.data, self.networks.value_target.v.weight.data
-        result = ev.evaluate(weight.view(-1), target.view(-1), self._max_step_dev, pool_dev, n, self.learning_rate,
-                             ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, trace)
+        if self.is_mlp:   # (the nets' weights travel as the pointers of the evaluator's two GopsMlp records)
+            result = ev.evaluate(self._max_step_dev, pool_dev, n, self.learning_rate, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, trace)
+        else:
+            weight, target = self.networks.value.v.weight.data, self.networks.value_target.v.weight.data
+            result = ev.evaluate(weight.view(-1), target.view(-1), self._max_step_dev, pool_dev, n, self.learning_rate,
+                                 ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, trace)
         steps, loss, before, after = result.tolist()                           # the one host sync of this local_update
         self.num_update_value = int(steps)
         self.norm_hamiltonian_before, self.norm_hamiltonian_after = before, after
@@ -311,7 +428,7 @@ class RPI(AlgorithmBase):
     def local_update(self, data_ignored, iteration):
         self.num_update_value = 0
         start_time = time.time()
-        loss = self._evaluate_device() if self.use_gpu else self._evaluate_host()
+        loss = self._evaluate_device() if self.use_gpu else self._evaluate_host_mlp() if self.is_mlp else self._evaluate_host()
         self.networks.value_target.load_state_dict(self.networks.value.state_dict())
         end_time = time.time()
         grad_info = dict()

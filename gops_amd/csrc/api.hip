@@ -855,6 +855,15 @@ int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const 
                         beta1, beta2, eps, result, trace, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_rpi_mlp_state_bytes(int32_t env_kind, int32_t batch, const GopsMlp* value) { return rpi_mlp_state_bytes(env_kind, batch, value); }
+
+int gops_rpi_mlp_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const float* consts, const GopsMlp* value,
+                          const GopsMlp* target, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
+                          double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream) {
+    return rpi_mlp_evaluate(env_kind, batch, max_steps, consts, value, target, max_step, reset_pool, state, state_bytes, lr, beta1,
+                            beta2, eps, result, trace, static_cast<hipStream_t>(stream));
+}
+
 size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps) {
     return episode_workspace_bytes(env, policy, episodes, max_steps);
 }

@@ -33,6 +33,12 @@ int rpi_evaluate(int kind, int B, int max_steps, const float* consts, float* w, 
                  const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, float* result,
                  float* trace, hipStream_t s);
 
+// ---- rollout_rpi_mlp.hip: the same with an MLP value net, one workgroup, batch rows in tiles of 64 ----
+size_t rpi_mlp_state_bytes(int kind, int B, const GopsMlp* v);
+int rpi_mlp_evaluate(int kind, int B, int max_steps, const float* consts, const GopsMlp* v, const GopsMlp* t, const float* max_step,
+                     const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps,
+                     float* result, float* trace, hipStream_t s);
+
 // ---- rollout_episode.hip: closed-loop evaluation episodes, 16 per workgroup, every step in one launch ----
 size_t episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int E, int T);
 int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, const GopsStepIO* init, const GopsEpisodeOut* out, void* ws,

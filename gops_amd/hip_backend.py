@@ -227,6 +227,12 @@ def lib() -> C.CDLL:
         l.gops_rpi_evaluate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double,
                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        l.gops_rpi_mlp_state_bytes.restype = C.c_size_t
+        l.gops_rpi_mlp_state_bytes.argtypes = [C.c_int32, C.c_int32, C.POINTER(GopsMlp)]
+        l.gops_rpi_mlp_evaluate.restype = C.c_int
+        l.gops_rpi_mlp_evaluate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(GopsMlp), C.POINTER(GopsMlp),
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_double,
+                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         l.gops_episode_workspace_bytes.restype = C.c_size_t
         l.gops_episode_workspace_bytes.argtypes = [C.POINTER(GopsEnv), C.POINTER(GopsMlp), C.c_int32, C.c_int32]
         l.gops_episode_rollout.restype = C.c_int
@@ -249,6 +255,7 @@ EXPORTED_SYMBOLS = ("gops_hip_version", "gops_rollout_workspace_bytes", "gops_ro
                     "gops_value_backward_update", "gops_poly_rollout_workspace_bytes", "gops_poly_rollout_forward",
                     "gops_poly_rollout_backward", "gops_poly_value_workspace_bytes", "gops_poly_value_forward",
                     "gops_poly_value_backward", "gops_rpi_state_bytes", "gops_rpi_evaluate",
+                    "gops_rpi_mlp_state_bytes", "gops_rpi_mlp_evaluate",
                     "gops_episode_workspace_bytes", "gops_episode_rollout")
 
 _ERR = {-1: "GOPS_ERR_BAD_ARG", -2: "GOPS_ERR_UNSUPPORTED", -3: "GOPS_ERR_WORKSPACE"}
@@ -746,6 +753,54 @@ class RpiEvaluator:
                                       _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr),
                                       float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),
               "gops_rpi_evaluate")
+        return self.result
+
+
+class RpiMlpEvaluator:
+    """The same for an MLP value net (`gops_rpi_mlp_evaluate`, csrc/rollout_rpi_mlp.hip): ONE launch per `local_update`; the value
+    net's weights and hidden biases are stepped in place through `value`'s pointers.  The state block holds the Adam step count in
+    the header, the lanes' states, the two counters per lane, the Adam moments of all parameters in `parameters()` order, and the
+    kernel's scratch (include/gops_hip.h)."""
+
+    def __init__(self, env_kind: int, batch: int, state_dim: int, consts, value: GopsMlp, target: GopsMlp,
+                 device: Optional[torch.device] = None):
+        self.kind, self.batch, self.state_dim = int(env_kind), int(batch), int(state_dim)
+        self.consts = (C.c_float * RPI_CONST_COUNT)(*[float(v) for v in consts])
+        self.value, self.target = value, target
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        nbytes = lib().gops_rpi_mlp_state_bytes(self.kind, self.batch, C.byref(value))
+        if nbytes == 0:
+            raise RuntimeError(f"gops_rpi_mlp_state_bytes: GOPS_ERR_UNSUPPORTED (env kind {env_kind}, batch {batch}, layer sizes "
+                               f"{list(value.sizes[:value.n_layers + 1])}, activation id {value.hidden_act}): one or two hidden layers, "
+                               f"widths multiples of 16 up to 64, elu / gelu / tanh / sigmoid, at most {RPI_MAX_BATCH} lanes")
+        self.n_params = sum(value.sizes[j + 1] * (value.sizes[j] + 1) for j in range(value.n_layers))
+        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+        self.result = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def lanes(self) -> torch.Tensor:
+        """[state_dim, B] view of the lanes' states."""
+        return self.state[RPI_STATE_HEADER:RPI_STATE_HEADER + self.state_dim * self.batch].view(self.state_dim, self.batch)
+
+    def counters(self) -> torch.Tensor:
+        """[2, B] view: the time-limit counter of each lane, then the counter the algorithm assigns at a reset."""
+        o = RPI_STATE_HEADER + self.state_dim * self.batch
+        return self.state[o:o + 2 * self.batch].view(2, self.batch)
+
+    def moments(self) -> torch.Tensor:
+        """[2, P] view: Adam's exp_avg and exp_avg_sq of all parameters, flattened in `parameters()` order."""
+        o = RPI_STATE_HEADER + (self.state_dim + 2) * self.batch
+        return self.state[o:o + 2 * self.n_params].view(2, self.n_params)
+
+    def evaluate(self, max_step: torch.Tensor, pool: torch.Tensor, max_steps: int, lr: float, beta1: float, beta2: float, eps: float,
+                 trace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Enqueues the launch; returns the device result [steps taken, last loss, norm_before, norm_after].  `pool` is
+        [max_steps + 1, state_dim, B]: the held-out set, then one reset draw per step."""
+        assert tuple(pool.shape) == (max_steps + 1, self.state_dim, self.batch)
+        assert trace is None or trace.numel() >= 2 * max_steps
+        check(lib().gops_rpi_mlp_evaluate(self.kind, self.batch, int(max_steps), self.consts, C.byref(self.value), C.byref(self.target),
+                                          _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr),
+                                          float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),
+              "gops_rpi_mlp_evaluate")
         return self.result
 
 

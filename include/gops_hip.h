@@ -538,6 +538,30 @@ int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const 
                       const float* target_weights, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
                       double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): the same policy evaluation for an MLP value net
+ * (csrc/rollout_rpi_mlp.hip), again ONE launch of one workgroup; batch rows are processed in tiles of 64.  `value` and `target`
+ * describe nets of the same shape: S -> H1 [-> H2] -> 1 with a linear output, one or two hidden layers, widths multiples of 16 and at
+ * most 64, hidden_act GOPS_ACT_ELU / _GELU / _TANH / _SIGMOID, GOPS_DTYPE_F32, sizes[0] = the model's state dimension.  Per step:
+ * dV/dx of the TARGET net by a reverse pass (action / adversary pair), the value net's forward pass with a tangent along f
+ * (h = U + dV/dx . f), the reverse pass over it seeded with sign(h) / batch, an Adam step on every weight and hidden bias (the
+ * output bias has no gradient), the held-out norm, the 0.88 test.  All products are fp32 fmaf chains; sums have a fixed order:
+ * results are bitwise reproducible.  The weights and hidden biases are stepped IN PLACE through the pointers of `value`.
+ * The state block, in floats (P = parameter count of the net, output bias included):
+ *   [0] Adam step count (a float, as above), up to GOPS_RPI_STATE_HEADER reserved (zero);
+ *   x [S][batch], count [batch], shown [batch] as for gops_rpi_evaluate;
+ *   exp_avg [P], exp_avg_sq [P] in torch's parameters() order (weight then bias of each Linear layer, row-major; the output
+ *   bias's slots stay as they are);
+ *   scratch [S + 1][batch] (the held-out set's f and U, rewritten by every call).
+ * gops_rpi_mlp_state_bytes: its size; 0 for anything unsupported.
+ * consts (GOPS_RPI_C_NORM unused), max_step, reset_pool, result and trace as for gops_rpi_evaluate.
+ * An unsupported net (also: target of another shape), env kind or batch > GOPS_RPI_MAX_BATCH: GOPS_ERR_UNSUPPORTED, nothing is
+ * launched; max_steps outside 1 .. GOPS_RPI_MAX_STEPS, batch < 1 or a NULL pointer: GOPS_ERR_BAD_ARG; state_bytes too small:
+ * GOPS_ERR_WORKSPACE. */
+size_t gops_rpi_mlp_state_bytes(int32_t env_kind, int32_t batch, const GopsMlp* value);
+int gops_rpi_mlp_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const float* consts, const GopsMlp* value,
+                          const GopsMlp* target, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
+                          double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream);
+
 /* ABI v15, additive entry points (the version number stays 15): whole closed-loop EVALUATION episodes in one launch
  * (csrc/rollout_episode.hip) - the loop of Evaluator.run_an_episode (gops/trainer/evaluator.py:45-86): a_t = policy(obs_t) (a
  * FiniteHorizonPolicy - sizes[0] = obs_dim + 1 - always gets virtual_t = 1, the default the reference evaluator calls it with), the
