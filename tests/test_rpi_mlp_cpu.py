@@ -2,6 +2,7 @@
 make_golden_rpi_mlp.py), plus construction, refusals and the C ABI's new symbols.  Tolerance per case: max(1e-4, 4 d), d = the
 fixture's distance between the reference's fp32 results and its float64 shadow; step counts and counters are compared exactly (the
 generator asserted a relative margin >= 1e-3 at every continue/stop decision and on every loss row)."""
+import json
 import os
 import re
 import subprocess
@@ -11,7 +12,8 @@ import pytest
 import torch
 
 from rpi_helpers import alg_kwargs, fixture, sub
-from rpi_mlp_helpers import all_cases, build, check_run, flat_params
+from rpi_mlp_helpers import (TENSOR_NAMES, all_cases, build, case_shape, check_run, flat_params, host_gradient, shadow_flat_grad,
+                             shadow_step, split_params, tensor_deviation, to_double)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = all_cases()
@@ -35,6 +37,41 @@ def test_construction_from_the_seed_alone(case):
     assert np.array_equal(alg.obs.numpy(), case["obs0"])
     assert np.array_equal(alg.env_model.max_step_per_episode.numpy(), case["max_step_alg"])
     assert np.array_equal(alg.networks.env_model.max_step_per_episode.numpy(), case["max_step_container"])
+
+
+def _report(what, sizes, devs, bound):
+    names = TENSOR_NAMES[2 * (len(sizes) - 1)]
+    print(f"{what}: " + ", ".join(f"{n} {d:.2e}" for n, d in zip(names, devs)) + f"  (bound {bound:.1e})")
+
+
+@pytest.mark.parametrize("case", [c for _, c in CASES], ids=[i for i, _ in CASES])
+def test_host_first_step_gradient_equals_grad0(case):
+    """`grad0` is the unmodified reference's gradient of its first step.  The eager fp32 host path's (autograd of mean|h| over
+    `_hamiltonian_mlp`) equals it per parameter tensor within 1e-6 of the tensor's largest element (measured: 0 in nine cases, 4e-8
+    in the tenth); the output bias takes none."""
+    alg = build(case, use_gpu=False)
+    sizes, _ = case_shape(case)
+    devs = tensor_deviation(host_gradient(alg, torch.from_numpy(case["obs0"]).clone()), case["grad0"], sizes)
+    _report("host path against grad0", sizes, devs, 1e-6)
+    assert max(devs) <= 1e-6
+    assert case["grad0"][-1] == 0
+
+
+@pytest.mark.parametrize("case", [c for _, c in CASES], ids=[i for i, _ in CASES])
+def test_shadow_gradient_agrees_with_grad0(case):
+    """The float64 shadow of one step (rpi_mlp_helpers.shadow_step, the yardstick of test_rpi_mlp_grad_gpu.py) at the fixture's
+    `obs0` and `params0` against `grad0`: per tensor within max(1e-5, 4 d) of the tensor's largest |grad0|, d = the case's
+    fp32-to-float64 distance."""
+    alg = build(case, use_gpu=False)
+    sizes, act = case_shape(case)
+    params = split_params(case["params0"], sizes)
+    step = shadow_step(to_double(alg.env_model), act, params, params, case["obs0"])
+    assert step.grads[-1] is None and all(g is not None for g in step.grads[:-1])
+    bound = max(1e-5, 4.0 * json.loads(str(case["meta/conditions"]))["fp64_distance"])
+    devs = tensor_deviation(shadow_flat_grad(step), case["grad0"], sizes)
+    _report("shadow against grad0", sizes, devs, bound)
+    assert max(devs) <= bound
+    assert abs(step.loss - case["loss"][0]) <= bound * max(1.0, abs(case["loss"][0]))
 
 
 def test_policy_takes_the_target_nets_gradient():
