@@ -40,7 +40,10 @@ class ApproxContainer(ApprBase):
         self.policy_target = deepcopy(self.policy)
         for p in list(self.v_target.parameters()) + list(self.policy_target.parameters()):
             p.requires_grad = False
-        self.policy_optimizer = make_adam(self.policy.parameters(), lr=kwargs["policy_learning_rate"])
+        # a LipsNet policy trains its two parameter groups at their own learning rates (reference lipsnet.py:211-221): one HipAdam
+        # with two groups - a launch and a device state block per group
+        self.policy_optimizer = make_adam(self.policy.param_groups() if getattr(self.policy, "is_lipsnet", False)
+                                          else self.policy.parameters(), lr=kwargs["policy_learning_rate"])
         self.v_optimizer = make_adam(self.v.parameters(), lr=kwargs["value_learning_rate"])
         self.net_dict = {"v": self.v, "policy": self.policy}
         self.target_net_dict = {"v": self.v_target, "policy": self.policy_target}
@@ -83,10 +86,33 @@ class INFADP(AlgorithmBase):
                 raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type POLY: only plain INFADP runs the POLY rollout")
             poly_env_check(self.envmodel, type(self).__name__)
             poly_alg_check(self, time_input=False)
+        # LipsNet policy (apprfunc/lipsnet.py): the policy sits OUTSIDE an open-loop one-step rollout (`_lips_return`)
+        self._lips = bool(getattr(self.networks.policy, "is_lipsnet", False))
+        if self._lips:
+            name = type(self).__name__
+            if type(self)._gradient_kernels is not INFADP._gradient_kernels or type(self)._update is not INFADP._update:
+                raise NotImplementedError(f"{name} with a LipsNet policy: only plain INFADP composes the LipsNet kernels with the model rollout")
+            if self._poly or getattr(self.networks.v, "is_lipsnet", False) or not hasattr(self.networks.v, "hip_mlp"):
+                raise NotImplementedError(f"{name} with a LipsNet policy needs an MLP StateValue")
+            if hb.dtype_id(self.mlp_dtype) != 0:
+                raise NotImplementedError(f"{name} with a LipsNet policy: mlp_dtype {self.mlp_dtype!r} - the LipsNet path is fp32 only")
+            kind = getattr(self.envmodel.unwrapped, "hip_kind", None)
+            if kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM):   # (gops_rollout_backward_open_loop_adj's env kinds)
+                raise NotImplementedError(f"{name} with a LipsNet policy: env model {type(self.envmodel.unwrapped).__name__} is outside the "
+                                          "path (models whose observation is the state: pyth_lq, pyth_idpendulum, gym cartpoleconti / pendulum)")
 
     @property
     def adjustable_parameters(self):
         return ("gamma", "tau", "pev_step", "pim_step", "forward_step", "reward_scale")
+
+    LIPS_FORWARD_STEP_ERROR = ("INFADP with a LipsNet policy is defined for forward_step = 1 only: with lips_auto_adjust the reference itself "
+                               "fails on longer rollouts (the second firing of its backward hook calls .backward() on the integer 0), and "
+                               "without it they need the policy's input gradient through the Jacobian norm, which the kernels do not form")
+
+    def set_parameters(self, param_dict):
+        super().set_parameters(param_dict)
+        if getattr(self, "_lips", False) and "forward_step" in param_dict and self.forward_step != 1:
+            raise NotImplementedError(self.LIPS_FORWARD_STEP_ERROR)
 
     def local_update(self, data: dict, iteration: int) -> dict:
         # gradient + Adam + Polyak of the iteration's mode as one HIP graph when the update is launch-bound
@@ -102,6 +128,7 @@ class INFADP(AlgorithmBase):
         fuse = (type(self)._gradient_kernels is INFADP._gradient_kernels and type(self)._update is INFADP._update
                 and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0")   # (host-side A/B knob)
         fuse = fuse and not self._poly   # (POLY: Adam and Polyak steps as launches of their own)
+        fuse = fuse and not self._lips   # (LipsNet: two optimizer groups, more tensors than one fused table)
 
         def update(b):
             if fuse:
@@ -113,6 +140,12 @@ class INFADP(AlgorithmBase):
             return scalars
 
         opt.grad_scale = 1.0   # (a data-parallel remote_update may have left 1/N behind)
+        if self._lips:
+            # No HIP-graph replay on this path: the composition allocates its intermediate tensors (actions, final observation,
+            # adjoints) per call and `LipsPolicy` re-reads the module's training flag on the host at every forward - a replay would
+            # freeze both.
+            self._log(mode, update(batch), start_time)
+            return self.tb_info
         cache = self._graphs.setdefault(mode, StepGraphCache())
         scalars = cache.run(self._signature(mode, batch), batch, update, before_replay=opt.sync_hyper,
                             on_replay=opt.advance, work=batch["obs"].shape[0] * self.forward_step,
@@ -229,9 +262,12 @@ class INFADP(AlgorithmBase):
         """Enqueue one policy-evaluation ("v") or policy-improvement ("policy") gradient; returns the
         device scalars the log needs ([loss_v, mean V] / [loss_policy]) without synchronising."""
         B, device = batch["obs"].shape[0], batch["obs"].device
+        if self._lips and mode == "policy":
+            return self._lips_improvement(batch)
         if mode == "v":
             # PEV: loss_v = mean((V(o) - [sum_t gamma^t r_t + (~d) gamma^n V_target(o_n)])^2)
-            backup = self._rollout_for(B, device, need_grad=False).forward(batch)["v_pi"]
+            backup = (self._lips_return(batch, need_grad=False)[0] if self._lips
+                      else self._rollout_for(B, device, need_grad=False).forward(batch)["v_pi"])
             vn = self._value_for(B, device)
             v = vn.forward(batch["obs"])
             # loss_v, mean V and d(loss_v)/dV = (2 / B)(V - backup) in one launch (they were six torch passes)
@@ -267,6 +303,66 @@ class INFADP(AlgorithmBase):
             return stats.mean_loss(v_pi, -1.0)[:1]
         ro.backward(self._grad_v(B, device), gw, gb, tail=hb.make_update_tail(None, v_pi, -1.0, stats))
         return stats.buf[:1]
+
+    # ---- LipsNet policy: policy -> wrapper chain on the action -> open-loop one-step rollout -> target value -----------------------
+    def _lips_parts(self, B, device, need_grad):
+        key = ("lips", B, str(device), need_grad, float(self.gamma))
+        parts = self._cache.get(key)
+        if parts is None:
+            nets = self.networks
+            env = self.envmodel.hip_env(nets.policy.act_low_lim.cpu().numpy(), nets.policy.act_high_lim.cpu().numpy())
+            ro = hb.Rollout(env, None, batch=B, horizon=1, gamma=self.gamma, finite_horizon=False, need_grad=need_grad,
+                            device=device, raw_actions=True)
+            A = env.act_dim
+            t = lambda v: torch.tensor([float(v[i]) for i in range(A)], dtype=torch.float32, device=device)   # noqa: E731
+            parts = self._cache[key] = dict(ro=ro, lp=hb.LipsPolicy(nets.policy, B, device=device), wrap=tuple(
+                t(v) for v in (env.min_action, env.max_action, env.act_low, env.act_high)))
+        return parts
+
+    def _lips_return(self, batch, need_grad):
+        """r + gamma (1 - done') V_target(obs') of one wrapped model step under the LipsNet policy -> (value [B], what the backward
+        needs).  `open_loop = 2` of the rollout takes the MODEL action: ScaleAction / ClipAction (create_env_model.py:120-126) act on the
+        policy's output here, between the two launches, exactly as `wrap_action` of csrc/common.h does inside a closed-loop rollout;
+        MaskAtDone, ShapingReward and the observation wrappers are the rollout's."""
+        if self.forward_step != 1:
+            raise NotImplementedError(self.LIPS_FORWARD_STEP_ERROR)
+        B, device = batch["obs"].shape[0], batch["obs"].device
+        parts = self._lips_parts(B, device, need_grad)
+        pol = self.networks.policy
+        act, K, _ = parts["lp"].forward(batch["obs"], training=need_grad and pol.training)
+        mn, mx, lo, hi = parts["wrap"]
+        a2 = lo + (hi - lo) * ((act.clamp(mn, mx) - mn) / (mx - mn))
+        u = a2.clamp(lo, hi)
+        res = parts["ro"].forward(batch, head_pre=u.unsqueeze(1).contiguous(), want_final=True)
+        vt = self._lips_vt(B, device, need_grad)
+        v_next = vt.forward(res["final_obs"]).reshape(B)
+        tail = float(self.gamma) * (1.0 - res["final_done"])
+        value = res["v_pi"] + tail * v_next
+        pass_through = ((act >= mn) & (act <= mx) & (a2 >= lo) & (a2 <= hi)).float() * ((hi - lo) / (mx - mn))
+        return value, dict(parts=parts, vt=vt, res=res, tail=tail, pass_through=pass_through, K=K)
+
+    def _lips_vt(self, B, device, need_grad):
+        key = ("lips_vt", B, str(device), need_grad)
+        mlp = self.networks.v_target.hip_mlp()
+        net = self._cache.get(key)
+        if net is None:
+            net = self._cache[key] = hb.MlpNet(mlp, B, device=device)
+        else:
+            net.mlp = mlp
+        return net
+
+    def _lips_improvement(self, batch):
+        """PIM: loss = -mean(value); the adjoint walks back through the target value's input, the model step and the action
+        wrappers into `LipsPolicy.backward`, which adds the regular loss's gradient in training mode (not part of the logged loss,
+        as in the reference)."""
+        B, device = batch["obs"].shape[0], batch["obs"].device
+        value, ctx = self._lips_return(batch, need_grad=True)
+        gv = self._grad_v(B, device)
+        g_obs2 = ctx["vt"].backward_x(ctx["res"]["final_obs"], (gv * ctx["tail"]).unsqueeze(1).contiguous())
+        g_u, _ = ctx["parts"]["ro"].backward_open_loop_adj(gv, g_obs2.contiguous())
+        ctx["parts"]["lp"].backward((g_u.reshape(B, -1) * ctx["pass_through"]).contiguous())
+        self.tb_info["Train/LipsNet K mean"] = scalar(ctx["K"].mean().reshape(1), 0)
+        return self._loss_stats("policy", device).mean_loss(value.contiguous(), -1.0)[:1]
 
     def _fused_parts(self, net_name, opt):
         """(what `HipAdam.begin_fused` returns, the network's one-table PolyakUpdater) for a backward call that carries the update's

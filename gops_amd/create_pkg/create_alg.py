@@ -84,6 +84,15 @@ def create_alg(**kwargs) -> object:
     if poly and kwargs["algorithm"] not in ("FHADP", "INFADP"):   # (the POLY rollout serves these two; nothing fails later)
         raise NotImplementedError(f"apprfunc type POLY ({', '.join(poly)}) is supported by FHADP and INFADP only, "
                                   f"not by {kwargs['algorithm']}")
+    lips = [k for k in ("policy", "value") if kwargs.get(k + "_func_type") == "LipsNet"]
+    if lips:   # INFADP with a LipsNet DetermPolicy and an MLP StateValue is the one combination that runs; refused here, so that nothing fails later
+        reason = ("a LipsNet value function does not exist (the reference has none either)" if "value" in lips else
+                  "a LipsNet policy needs an MLP value, not POLY" if poly or kwargs.get("value_func_type") != "MLP" else
+                  f"{kwargs['algorithm']} does not run a LipsNet policy (INFADP only)" if kwargs["algorithm"] != "INFADP" else
+                  f"policy_func_name {kwargs.get('policy_func_name')!r} (DetermPolicy only)" if kwargs.get("policy_func_name") != "DetermPolicy" else
+                  None)
+        if reason is not None:
+            raise NotImplementedError(f"apprfunc type LipsNet ({', '.join(lips)}): {reason}")
     trainer = kwargs.get("trainer")
     if trainer is not None and not trainer.startswith(_TRAINER_KINDS):
         raise RuntimeError(f"trainer {trainer} not recognized")

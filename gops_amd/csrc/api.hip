@@ -855,6 +855,20 @@ int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const 
                         beta1, beta2, eps, result, trace, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_lips_workspace_bytes(const GopsLipsNet* net, int32_t batch) { return net ? lips_workspace_bytes(*net, batch) : 0; }
+
+int gops_lips_forward(const GopsLipsNet* net, int32_t batch, const float* obs, float* action, float* K, float* N, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (net == nullptr) return GOPS_ERR_BAD_ARG;
+    return lips_forward(*net, batch, obs, action, K, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int gops_lips_backward(const GopsLipsNet* net, int32_t batch, const float* obs, const float* grad_action, const GopsLipsGrad* grad,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (net == nullptr || grad == nullptr) return GOPS_ERR_BAD_ARG;
+    return lips_backward(*net, batch, obs, grad_action, *grad, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 size_t gops_rpi_mlp_state_bytes(int32_t env_kind, int32_t batch, const GopsMlp* value) { return rpi_mlp_state_bytes(env_kind, batch, value); }
 
 int gops_rpi_mlp_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const float* consts, const GopsMlp* value,

@@ -43,3 +43,9 @@ int rpi_mlp_evaluate(int kind, int B, int max_steps, const float* consts, const 
 size_t episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int E, int T);
 int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, const GopsStepIO* init, const GopsEpisodeOut* out, void* ws,
                     size_t ws_bytes, float pdt, hipStream_t s);
+
+// ---- rollout_lips.hip: LipsNet policies - an MLP with its input Jacobian, forward and reverse, a tile of samples per workgroup ----
+size_t lips_workspace_bytes(const GopsLipsNet& d, int B);
+int lips_forward(const GopsLipsNet& d, int B, const float* obs, float* action, float* K, float* N, void* ws, size_t bytes, hipStream_t s);
+int lips_backward(const GopsLipsNet& d, int B, const float* obs, const float* grad_action, const GopsLipsGrad& g, void* ws, size_t bytes,
+                  hipStream_t s);

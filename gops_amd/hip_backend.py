@@ -132,6 +132,15 @@ class GopsStepIO(C.Structure):
                                           "surr_state", "next_surr_state", "constraint", "ref_appended", "noise")]
 
 
+class GopsLipsNet(C.Structure):   # gops_lips_forward / _backward
+    _fields_ = [("mlp", GopsMlp), ("k_net", GopsMlp), ("k_scalar", C.c_void_p), ("eps", C.c_float), ("lam", C.c_float),
+                ("training", C.c_int32), ("squash", C.c_int32), ("act_low", C.c_float * MAX_ACT), ("act_high", C.c_float * MAX_ACT)]
+
+
+class GopsLipsGrad(C.Structure):
+    _fields_ = [("mlp", GopsMlpGrad), ("k_net", GopsMlpGrad), ("k_scalar", C.c_void_p)]
+
+
 class GopsEpisodeOut(C.Structure):   # gops_episode_rollout
     _fields_ = [(k, C.c_void_p) for k in ("ret", "length", "terminated", "trace_obs", "trace_act", "trace_rew")]
 
@@ -238,6 +247,14 @@ def lib() -> C.CDLL:
         l.gops_episode_rollout.restype = C.c_int
         l.gops_episode_rollout.argtypes = [C.POINTER(GopsEnv), C.POINTER(GopsMlp), C.c_int32, C.c_int32, C.POINTER(GopsStepIO),
                                            C.POINTER(GopsEpisodeOut), C.c_void_p, C.c_size_t, C.c_void_p]
+        l.gops_lips_workspace_bytes.restype = C.c_size_t
+        l.gops_lips_workspace_bytes.argtypes = [C.POINTER(GopsLipsNet), C.c_int32]
+        l.gops_lips_forward.restype = C.c_int
+        l.gops_lips_forward.argtypes = [C.POINTER(GopsLipsNet), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]
+        l.gops_lips_backward.restype = C.c_int
+        l.gops_lips_backward.argtypes = [C.POINTER(GopsLipsNet), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsLipsGrad), C.c_void_p,
+                                         C.c_size_t, C.c_void_p]
         l.gops_profile_enable.argtypes = [C.c_int32]
         l.gops_profile_reset.argtypes = []
         l.gops_profile_read.restype = C.c_int
@@ -256,7 +273,8 @@ EXPORTED_SYMBOLS = ("gops_hip_version", "gops_rollout_workspace_bytes", "gops_ro
                     "gops_poly_rollout_backward", "gops_poly_value_workspace_bytes", "gops_poly_value_forward",
                     "gops_poly_value_backward", "gops_rpi_state_bytes", "gops_rpi_evaluate",
                     "gops_rpi_mlp_state_bytes", "gops_rpi_mlp_evaluate",
-                    "gops_episode_workspace_bytes", "gops_episode_rollout")
+                    "gops_episode_workspace_bytes", "gops_episode_rollout",
+                    "gops_lips_workspace_bytes", "gops_lips_forward", "gops_lips_backward")
 
 _ERR = {-1: "GOPS_ERR_BAD_ARG", -2: "GOPS_ERR_UNSUPPORTED", -3: "GOPS_ERR_WORKSPACE"}
 
@@ -715,6 +733,107 @@ class PolyValueNet:
         check(lib().gops_poly_value_backward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g),
                                              self.workspace.data_ptr(), self.workspace.numel(), _stream()),
               "gops_poly_value_backward")
+
+
+def _small_mlp(weights, biases, act: str) -> GopsMlp:
+    m = GopsMlp()
+    m.n_layers = len(weights)
+    if len(weights) > MAX_LAYERS:
+        raise RuntimeError(f"MLP with {len(weights)} Linear layers is outside the HIP path")
+    if weights:
+        m.sizes[0] = weights[0].shape[1]
+    for j, (w, b) in enumerate(zip(weights, biases)):
+        m.sizes[j + 1] = w.shape[0]
+        m.weight[j], m.bias[j] = _ptr(w), _ptr(b)
+    m.hidden_act = ACT_IDS[act]
+    return m
+
+
+class LipsPolicy:
+    """A LipsNet DetermPolicy (gops_amd/apprfunc/lipsnet.py) on the tangent-propagation kernels: `gops_lips_workspace_bytes /
+    _forward / _backward` (csrc/rollout_lips.hip).  The parameters of `module` are read in place; call `refresh()` after they moved
+    (`.to(device)`, `load_state_dict` keeps the storage).  `forward(obs, training)` -> (action [B, m], K [B], N [B]) and keeps the
+    stash; `backward(grad_action)` overwrites the gradient buffers (`grads()`: one tensor per parameter in `parameters()` order -
+    mlp, then K - views into one flat buffer, installed as the parameters' `.grad`)."""
+
+    def __init__(self, module, batch: int, device: Optional[torch.device] = None):
+        self.module, self.batch = module, int(batch)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.refresh()
+        nbytes = lib().gops_lips_workspace_bytes(C.byref(self.net), self.batch)
+        if nbytes == 0:
+            raise RuntimeError("gops_lips_workspace_bytes: descriptor rejected (LipsNet outside the HIP path: obs_dim <= 8, act_dim <= 4, "
+                               "1..3 hidden layers, K net global or 1..2 hidden layers, widths multiples of 16 up to 256)")
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._obs = None
+
+    def refresh(self):
+        pol = self.module
+        lin = pol.pi.linear_layers()
+        klin = pol.pi.K.linear_layers()
+        key = tuple(p.data_ptr() for p in pol.parameters())
+        if getattr(self, "_key", None) == key:
+            return
+        self._key = key
+        d = self.net = GopsLipsNet()
+        d.mlp = _small_mlp([l.weight.data for l in lin], [l.bias.data for l in lin], pol._hidden_activation)
+        d.k_net = _small_mlp([l.weight.data for l in klin], [l.bias.data for l in klin], "tanh")
+        d.k_scalar = None if klin else _ptr(pol.pi.K.K.data)
+        d.eps, d.lam = float(pol.pi.eps), float(pol.pi.loss_lambda)
+        d.squash = int(pol.squash_action)
+        # (more than MAX_ACT actions: the library rejects the description, gops_lips_workspace_bytes = 0)
+        _fill(d.act_low, pol.act_low_lim.detach().float().cpu().reshape(-1).tolist()[:MAX_ACT])
+        _fill(d.act_high, pol.act_high_lim.detach().float().cpu().reshape(-1).tolist()[:MAX_ACT])
+        self._grads = None
+
+    def grads(self) -> List[torch.Tensor]:
+        params = list(self.module.parameters())
+        if self._grads is None or any(p.grad is None or p.grad.data_ptr() != g.data_ptr() for p, g in zip(params, self._grads)):
+            flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=self.device)
+            off, self._grads = 0, []
+            for p in params:
+                p.grad = flat[off:off + p.numel()].view_as(p)
+                self._grads.append(p.grad)
+                off += p.numel()
+            self.module._flat_grad = flat
+            g = self._g = GopsLipsGrad()
+            n_lin = len(self.module.pi.linear_layers())
+            for j in range(n_lin):
+                g.mlp.weight[j], g.mlp.bias[j] = _ptr(self._grads[2 * j]), _ptr(self._grads[2 * j + 1])
+            rest = self._grads[2 * n_lin:]
+            if self.module.pi.K.linear_layers():
+                for j in range(len(rest) // 2):
+                    g.k_net.weight[j], g.k_net.bias[j] = _ptr(rest[2 * j]), _ptr(rest[2 * j + 1])
+            else:
+                g.k_scalar = rest[0].data_ptr()
+        return self._grads
+
+    def forward(self, obs: torch.Tensor, training: bool = False):
+        """`training`: the backward that follows carries the regular loss's gradient (lips_auto_adjust in training mode)."""
+        self.refresh()
+        B, m = self.batch, self.net.mlp.sizes[self.net.mlp.n_layers]
+        if tuple(obs.shape) != (B, self.net.mlp.sizes[0]) or obs.device != self.device:   # (_ptr: fp32, contiguous, on a GPU)
+            raise RuntimeError(f"LipsPolicy.forward: obs {tuple(obs.shape)} on {obs.device}, expected {(B, self.net.mlp.sizes[0])} on {self.device}")
+        self.net.training = int(bool(training) and self.module.pi.lips_auto_adjust)
+        act = torch.empty(B, m, dtype=torch.float32, device=self.device)
+        K = torch.empty(B, dtype=torch.float32, device=self.device)
+        N = torch.empty(B, dtype=torch.float32, device=self.device)
+        check(lib().gops_lips_forward(C.byref(self.net), B, _ptr(obs), _ptr(act), _ptr(K), _ptr(N), self.workspace.data_ptr(),
+                                      self.workspace.numel(), _stream()), "gops_lips_forward")
+        self._obs = obs
+        return act, K, N
+
+    def backward(self, grad_action: torch.Tensor) -> List[torch.Tensor]:
+        if self._obs is None:
+            raise RuntimeError("LipsPolicy.backward before forward")
+        m = self.net.mlp.sizes[self.net.mlp.n_layers]
+        if tuple(grad_action.shape) != (self.batch, m) or grad_action.device != self.device:
+            raise RuntimeError(f"LipsPolicy.backward: grad_action {tuple(grad_action.shape)} on {grad_action.device}, expected "
+                               f"{(self.batch, m)} on {self.device}")
+        grads = self.grads()
+        check(lib().gops_lips_backward(C.byref(self.net), self.batch, _ptr(self._obs), _ptr(grad_action), C.byref(self._g),
+                                       self.workspace.data_ptr(), self.workspace.numel(), _stream()), "gops_lips_backward")
+        return grads
 
 
 class RpiEvaluator:

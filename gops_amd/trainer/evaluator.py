@@ -89,6 +89,8 @@ class Evaluator:
         pol = self.networks.policy
         if is_poly(pol):
             return "POLY policy"
+        if getattr(pol, "is_lipsnet", False):
+            return "LipsNet policy"
         env = self._hip_env()
         if env.kind == hb.ENV_MOBILEROBOT:
             return "pyth_mobilerobot draws its obstacle noise per step"

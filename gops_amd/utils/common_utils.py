@@ -39,8 +39,17 @@ def get_apprfunc_dict(key: str, **kwargs):
         var["degree"] = kwargs[key + "_degree"]
         var["add_bias"] = kwargs[key + "_add_bias"]
         var["norm_matrix"] = kwargs.get("norm_matrix", None)
+    elif apprfunc_type == "LipsNet":   # gops_amd/apprfunc/lipsnet.py (reference common_utils.py:94-106)
+        var["hidden_sizes"] = kwargs[key + "_hidden_sizes"]
+        var["hidden_activation"] = kwargs[key + "_hidden_activation"]
+        var["output_activation"] = kwargs.get(key + "_output_activation", "linear")
+        for name in ("lips_init_value", "lips_auto_adjust", "lips_learning_rate", "lips_hidden_sizes", "eps", "lambda", "local_lips",
+                     "squash_action", "learning_rate"):
+            var[name] = kwargs[key + "_" + name]
+        var["mlp_dtype"] = kwargs.get("mlp_dtype", "fp32")   # (the module refuses fp16 at construction)
     else:
-        raise NotImplementedError(f"apprfunc type {apprfunc_type} is outside the MI355X ADP path (MLP and POLY only)")
+        raise NotImplementedError(f"apprfunc type {apprfunc_type} is outside the MI355X ADP path (MLP and POLY only, "
+                                  "LipsNet for the policy of INFADP)")
     if kwargs["action_type"] == "continu":
         var["act_high_lim"] = np.array(kwargs["action_high_limit"])
         var["act_low_lim"] = np.array(kwargs["action_low_limit"])

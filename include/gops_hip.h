@@ -592,6 +592,45 @@ size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, i
 int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps, const GopsStepIO* init,
                          const GopsEpisodeOut* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): LipsNet policies (gops/apprfunc/lipsnet.py DetermPolicy) - an MLP f
+ * evaluated together with its input Jacobian J = df/dx and differentiated through it (csrc/rollout_lips.hip):
+ *     y = K(x) f(x) / (||J||_F + eps),   action = y   or, with `squash`,   (high - low) / 2 tanh(y) + (high + low) / 2,
+ * K(x) = softplus(*k_scalar) (global: k_net.n_layers = 0) or softplus(k_net(x)) (local: a tanh MLP obs -> 1, hidden_act GOPS_ACT_TANH).
+ * A sample is 1 + obs_dim rows through the layers of f (the primal row and the obs_dim tangent columns); the backward walks them
+ * back with the second derivative of the activation on the primal delta.  fp32 fmaf arithmetic throughout; weight gradients are
+ * per-slab partials summed in a fixed order: results are bitwise reproducible.  softplus has torch's threshold of 20; relu'(0) = 0.
+ * Bounds (GOPS_ERR_UNSUPPORTED outside): obs_dim <= 8, act_dim <= GOPS_MAX_ACT, 1..3 hidden layers in `mlp`, `k_net` global or 1..2
+ * hidden layers, hidden widths multiples of 16 up to 256, hidden_act GOPS_ACT_RELU .. GOPS_ACT_TANH, GOPS_DTYPE_F32, variant_flags 0.
+ * Hidden-layer weight tensors must be 16-byte aligned (GOPS_ERR_BAD_ARG).
+ *   gops_lips_forward:  obs [B, obs_dim] -> action [B, act_dim]; K [B] and N [B] (= ||J||_F) are optional outputs (NULL).  Keeps the
+ *                       stash of the backward in `workspace`.
+ *   gops_lips_backward: grad_action [B, act_dim] -> the gradient of every tensor of `mlp` and of `k_net` / `k_scalar` (overwritten),
+ *                       after a forward call with the same description, batch, obs and workspace.  With `training` = 1 the
+ *                       gradient of the regular loss lambda mean_b K(x_b)^2 (the reference's backward pre-hook in training mode)
+ *                       is part of it: 2 lambda K_b / B on K's adjoint of every row.
+ * gops_lips_workspace_bytes: 0 for a description the entry points reject. */
+struct GopsLipsNet {
+    GopsMlp mlp;                 /* f: sizes = obs_dim, hidden..., act_dim */
+    GopsMlp k_net;               /* local K; n_layers = 0: global K */
+    const float* k_scalar;       /* global K: device pointer to the scalar parameter */
+    float eps, lambda;
+    int32_t training;
+    int32_t squash;
+    float act_low[GOPS_MAX_ACT], act_high[GOPS_MAX_ACT];   /* the squash bounds (act_low_lim / act_high_lim buffers) */
+};
+typedef struct GopsLipsNet GopsLipsNet;
+struct GopsLipsGrad {
+    GopsMlpGrad mlp;
+    GopsMlpGrad k_net;
+    float* k_scalar;
+};
+typedef struct GopsLipsGrad GopsLipsGrad;
+size_t gops_lips_workspace_bytes(const GopsLipsNet* net, int32_t batch);
+int gops_lips_forward(const GopsLipsNet* net, int32_t batch, const float* obs, float* action, float* K, float* N,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int gops_lips_backward(const GopsLipsNet* net, int32_t batch, const float* obs, const float* grad_action, const GopsLipsGrad* grad,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
