@@ -342,6 +342,18 @@ __device__ __forceinline__ T keep_s(T v) {
     if constexpr (ON) asm volatile("" : "+s"(v));
     return v;
 }
+// ---- small shared helpers -------------------------------------------------------------------
+// workspace sections start on 256-byte boundaries
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// Fixed-order block sums, first half: butterfly inside the wave, lane 0 leaves the wave's sum in red[wave * nslots + slot].
+// After a barrier the caller adds the waves' slots in index order.
+__device__ __forceinline__ void wave_sum(float v, float* red, int slot, int nslots) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * nslots + slot] = v;
+}
+
 // ---- activations ---------------------------------------------------------------------------
 #define SELU_SCALE 1.0507009873554804934193349852946f
 #define SELU_ALPHA 1.6732632423543772848170429916717f
@@ -398,6 +410,41 @@ __device__ __forceinline__ float act_fwd_t(float z) {
     if (ACT == GOPS_ACT_SIGMOID) return 1.f / (1.f + expf(-z));
     if (ACT == GOPS_ACT_TANH) return tanhf(z);
     return z;
+}
+
+// act(z), act'(z), act''(z) as torch evaluates them (fp32 libm: erf-form GELU, expm1f for ELU / SELU; relu'(0) = 0, relu'' = 0):
+// the lane-per-sample kernels that differentiate a net twice (rollout_rpi_mlp.hip, rollout_lips.hip)
+template <int ACT>
+__device__ __forceinline__ void act3_t(float z, float& a, float& d1, float& d2) {
+    if constexpr (ACT == GOPS_ACT_RELU) {
+        a = fmaxf(z, 0.f); d1 = z > 0.f ? 1.f : 0.f; d2 = 0.f;
+    } else if constexpr (ACT == GOPS_ACT_ELU) {
+        const float e = expf(fminf(z, 0.f));
+        a = z > 0.f ? z : expm1f(z);
+        d1 = z > 0.f ? 1.f : e;
+        d2 = z > 0.f ? 0.f : e;
+    } else if constexpr (ACT == GOPS_ACT_SELU) {
+        const float e = expf(fminf(z, 0.f));
+        a = SELU_SCALE * (z > 0.f ? z : SELU_ALPHA * expm1f(z));
+        d1 = z > 0.f ? SELU_SCALE : SELU_SCALE * SELU_ALPHA * e;
+        d2 = z > 0.f ? 0.f : SELU_SCALE * SELU_ALPHA * e;
+    } else if constexpr (ACT == GOPS_ACT_GELU) {
+        const float cdf = 0.5f * (1.f + erff(z * 0.70710678118654752440f));
+        const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
+        a = z * cdf;
+        d1 = cdf + z * pdf;
+        d2 = pdf * (2.f - z * z);
+    } else if constexpr (ACT == GOPS_ACT_SIGMOID) {
+        a = 1.f / (1.f + expf(-z));
+        d1 = a * (1.f - a);
+        d2 = d1 * (1.f - 2.f * a);
+    } else if constexpr (ACT == GOPS_ACT_TANH) {
+        a = tanhf(z);
+        d1 = 1.f - a * a;
+        d2 = -2.f * a * d1;
+    } else {
+        a = z; d1 = 1.f; d2 = 0.f;
+    }
 }
 
 // tanh on the hardware exponential: (1 - t) / (1 + t) with t = exp(-2|x|) away from zero (relative error ~5e-7 worst

@@ -275,6 +275,130 @@ __device__ __forceinline__ bool idp_done_trig(const IdpConst& C, const float* s,
     return (tip_y <= 1.0f) || (fabsf(s[0]) >= 15.f);
 }
 
+// ================================ the models whose observation is the state, register form ====
+// pyth_lq, gym_cartpoleconti, gym_pendulum, pyth_idpendulum for ONE trajectory held in registers: the single statement of the
+// arithmetic that env_step_kernel, the episode kernel (env_step.h) and the POLY rollout (rollout_poly.hip) step.  The tile-form
+// env phases of rollout_fwd.hip / rollout_bwd.hip are its twin.
+// State arrays of every model here have GOPS_MAX_LQ_STATE entries (lq_forward's padded width); entries beyond the model's are zero.
+
+// one base-model step xi -> xo: r the model's reward, done_m its done test (left as it is by the models that have none)
+template <int ENV>
+__device__ __forceinline__ void state_model_substep(const GopsEnv& env, const float* xi, const float (&u)[GOPS_MAX_ACT], float* xo,
+                                                    float& r, bool& done_m) {
+    if constexpr (ENV == GOPS_ENV_LQ) {
+        lq_forward(env, xi, u, xo, r);
+    } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
+        cart_forward(cart_const(), xi, u[0], xo, r, done_m);
+    } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
+        PendStep w;
+        pend_forward(xi, u[0], xo, r, w);
+    } else {   // five Euler sub-steps: one sincosf pair, then rotations
+        static_assert(ENV == GOPS_ENV_IDPENDULUM, "env kind");
+        const IdpConst IC = idp_const();
+        float s[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) s[i] = xi[i];
+        IdpSub w;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            if (k == 0) idp_substep<true>(IC, s, 500.f * u[0], 0.002f, xo, w);
+            else idp_substep<false>(IC, s, 500.f * u[0], 0.002f, xo, w);
+            idp_advance_trig(s, 0.002f, w, w);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) s[i] = xo[i];
+        }
+        r = idp_reward(s, u[0]);
+        done_m = idp_done(IC, s);
+    }
+}
+
+// its adjoint at the input state xi: gn adjoint of xo, gr adjoint of r -> gxo adjoint of xi, guo adjoint of u (both overwritten)
+template <int ENV>
+__device__ __forceinline__ void state_model_substep_bwd(const GopsEnv& env, const float* xi, const float (&u)[GOPS_MAX_ACT],
+                                                        const float* gn, float gr, float* gxo, float* guo) {
+#pragma unroll
+    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) gxo[i] = 0.f;
+#pragma unroll
+    for (int a = 0; a < GOPS_MAX_ACT; ++a) guo[a] = 0.f;
+    if constexpr (ENV == GOPS_ENV_LQ) {
+        lq_backward(env, xi, u, gn, gr, gxo, guo);
+    } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
+        cart_backward(cart_const(), xi, u[0], gn, gxo, guo[0]);
+    } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
+        pend_backward(xi, u[0], gn, gr, gxo, guo[0]);
+    } else {
+        // the 5 Euler sub-steps recomputed, every sub-step's input state and intermediates kept in registers
+        const IdpConst IC = idp_const();
+        float sk[5][6];
+        IdpSub wk[5];
+        float sc_[6], sn_[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) sc_[i] = xi[i];
+        const float a = u[0], force = 500.f * a;
+        IdpSub w;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            if (k == 0) idp_substep<true>(IC, sc_, force, 0.002f, sn_, w);
+            else idp_substep<false>(IC, sc_, force, 0.002f, sn_, w);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sk[k][i] = sc_[i];
+            wk[k] = w;
+            idp_advance_trig(sc_, 0.002f, w, w);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sc_[i] = sn_[i];
+        }
+        float g[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) g[i] = gn[i];
+        g[1] += gr * (-10.f * sc_[1]);
+        g[2] += gr * (-20.f * sc_[2]);
+        g[3] += gr * (-1.f * sc_[3]);
+        g[4] += gr * (-1.f * sc_[4]);
+        g[5] += gr * (-2.f * sc_[5]);
+        float gforce = 0.f;
+#pragma unroll
+        for (int k = 4; k >= 0; --k) idp_substep_bwd(IC, sk[k], 0.002f, wk[k], g, gforce);
+        guo[0] = 500.f * gforce + gr * (-2.f * a);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) gxo[i] = g[i];
+    }
+}
+
+// One WRAPPED model step: un-scale (ScaleObservationModel), ActionRepeatModel's sub-steps with the initial done flag, the summed
+// or last reward, re-scale, ClipObservation (pyth_idpendulum has no observation bounds).
+// o: the observation the step starts from; u: the wrapped actions; dn: the step's done flag (MaskAtDoneModel); n <= N: the live
+// entries of o / on (a caller whose width is a run-time value passes arrays of N = GOPS_MAX_LQ_STATE, zero beyond n).
+// -> on: the next observation, r: the model's (summed / last) reward, done_m: the base model's done test of the last sub-step.
+template <int ENV, int N>
+__device__ __forceinline__ void state_model_step(const GopsEnv& env, const float (&o)[N], const float (&u)[GOPS_MAX_ACT], bool dn,
+                                                 float (&on)[N], float& r, bool& done_m, int n = N) {
+    const int nrep = env.repeat_num > 1 ? env.repeat_num : 1;
+    const bool last_only = nrep > 1 && env.repeat_last_reward != 0;
+    float x[GOPS_MAX_LQ_STATE], xn[GOPS_MAX_LQ_STATE];
+#pragma unroll
+    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { x[i] = 0.f; xn[i] = 0.f; }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        if (i < n) x[i] = obs_unscale(env, i, o[i]);
+    float rs = 0.f, rr = 0.f;
+    done_m = false;
+#pragma unroll 1
+    for (int rep = 0; rep < nrep; ++rep) {
+        if (rep > 0 && !dn)
+#pragma unroll
+            for (int i = 0; i < N; ++i)   // (the entries beyond N stay the compile-time zeros they are)
+                if (i < n) x[i] = xn[i];
+        state_model_substep<ENV>(env, x, u, xn, rr, done_m);
+        rs = last_only ? rr : rs + rr;
+    }
+    r = rs;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const float v = obs_rescale(env, i, dn ? x[i] : xn[i]);
+        on[i] = (ENV != GOPS_ENV_IDPENDULUM && env.clip_obs) ? clampf(v, env.obs_low[i], env.obs_high[i]) : v;
+    }
+}
+
 // ================================ pyth_mobilerobot ============================================
 // gops/env/env_ocp/env_model/pyth_mobilerobot_model.py:24-213.  State = observation, 13 columns:
 //   [0..4] ego (x, y, theta, v, w)   [5..7] tracking errors (e_y, e_theta, e_v) of the NEW ego state   [8..12] obstacle (x, y, theta, v, w)

@@ -91,6 +91,42 @@ __device__ __forceinline__ f32x4 ref_point_ids(const float* __restrict__ c, floa
 }
 
 // ---------------------------------------------------------------------------------------------
+// The step of a model whose observation is the state, from and to global memory: the wrapped model step (env_models.h:
+// state_model_step), or - DATA environment, GopsEnv.data_env - ONE base-model step without MaskAtDone / ActionRepeat /
+// ClipObservation, with the data env's own ending: pyth_lq (lq_base.py:224-239) is done when the NEXT state leaves the state
+// bounds (clip_obs: they are finite) and pays -100 for it; gym_cartpoleconti (env_gym/gym_cartpoleconti.py:102-137) rewards 1
+// also for the step that ends the episode; pyth_idpendulum's data env calls the model's Dynamics.
+// ---------------------------------------------------------------------------------------------
+template <int ENV, int N>
+__device__ __forceinline__ void env_step_state_model(const GopsEnv& env, bool data, bool dn, const float* ob,
+                                                     const float (&u)[GOPS_MAX_ACT], float* nob, float& r, bool& done_m) {
+    const int n = ENV == GOPS_ENV_LQ ? env.obs_dim : N;
+    float o[N], on[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = i < n ? ob[i] : 0.f;
+    if (!data) {
+        state_model_step<ENV, N>(env, o, u, dn, on, r, done_m, n);
+    } else {
+        float x[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, xn[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (i < n) x[i] = obs_unscale(env, i, o[i]);
+        state_model_substep<ENV>(env, x, u, xn, r, done_m);
+        r += 0.f;   // the wrapped step's sum over its one sub-step: a reward of -0 leaves as +0
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            on[i] = obs_rescale(env, i, xn[i]);
+            if (ENV == GOPS_ENV_LQ && env.clip_obs && i < n && (xn[i] > env.obs_high[i] || xn[i] < env.obs_low[i])) done_m = true;
+        }
+        if (ENV == GOPS_ENV_LQ && done_m) r -= 100.f;
+        if (ENV == GOPS_ENV_CARTPOLE) r = 1.f;
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        if (i < n) nob[i] = on[i];
+}
+
+// ---------------------------------------------------------------------------------------------
 // Single wrapped env-model step (pyth_base_model.py:59-67 contract) of trajectory `b`.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void env_step_one(const GopsEnv& env, int b, const GopsStepIO& io, float pdt) {
@@ -99,73 +135,18 @@ __device__ __forceinline__ void env_step_one(const GopsEnv& env, int b, const Go
     float u[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
     for (int a = 0; a < A; ++a) u[a] = wrap_action(env, a, io.action[(size_t)b * A + a]);
     const bool dn = !data && !env.no_mask_at_done && io.done != nullptr && io.done[b] != 0.f;   // (no MaskAtDoneModel: done flags ignored)
-    const int nrep = (env.repeat_num > 1 && !data) ? env.repeat_num : 1;
-    const bool last_only = nrep > 1 && env.repeat_last_reward != 0;
     float r = 0.f;
     bool done_m = false;
     const float* ob = io.obs + (size_t)b * O;
     float* nob = io.next_obs + (size_t)b * O;
     if (env.kind == GOPS_ENV_LQ) {
-        float x[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, xn[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int i = 0; i < O; ++i) x[i] = obs_unscale(env, i, ob[i]);
-        float rs = 0.f;
-        for (int rep = 0; rep < nrep; ++rep) {   // ActionRepeatModel: sub-steps with the initial done flag (nrep = 1 otherwise)
-            if (rep > 0 && !dn)
-                for (int i = 0; i < O; ++i) x[i] = xn[i];
-            lq_forward(env, x, u, xn, r);
-            rs = last_only ? r : rs + r;
-        }
-        r = rs;
-        for (int i = 0; i < O; ++i) {
-            const float v = obs_rescale(env, i, dn ? x[i] : xn[i]);
-            nob[i] = (env.clip_obs && !data) ? clampf(v, env.obs_low[i], env.obs_high[i]) : v;
-            // data env (lq_base.py:224-231, 236-239): done when the NEXT state leaves the state bounds
-            if (data && env.clip_obs && (xn[i] > env.obs_high[i] || xn[i] < env.obs_low[i])) done_m = true;   // clip_obs: bounds are finite
-        }
-        if (data && done_m) r -= 100.f;
-    } else if (env.kind == GOPS_ENV_CARTPOLE || env.kind == GOPS_ENV_PENDULUM) {
-        const int NS = env.kind == GOPS_ENV_CARTPOLE ? 4 : 3;
-        float x[4] = {0.f, 0.f, 0.f, 0.f}, xn[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int i = 0; i < NS; ++i) x[i] = obs_unscale(env, i, ob[i]);
-        float rs = 0.f;
-        for (int rep = 0; rep < nrep; ++rep) {
-            if (rep > 0 && !dn)
-                for (int i = 0; i < NS; ++i) x[i] = xn[i];
-            if (env.kind == GOPS_ENV_CARTPOLE) {
-                cart_forward(cart_const(), x, u[0], xn, r, done_m);
-            } else {
-                PendStep w;
-                pend_forward(x, u[0], xn, r, w);
-            }
-            rs = last_only ? r : rs + r;
-        }
-        r = rs;
-        // data env (env_gym/gym_cartpoleconti.py:102-137): the same physics, reward 1 also for the step that ends the
-        // episode, no observation clip
-        if (data && env.kind == GOPS_ENV_CARTPOLE) r = 1.f;
-        for (int i = 0; i < NS; ++i) {
-            const float v = obs_rescale(env, i, dn ? x[i] : xn[i]);
-            nob[i] = (env.clip_obs && !data) ? clampf(v, env.obs_low[i], env.obs_high[i]) : v;
-        }
-    } else if (env.kind == GOPS_ENV_IDPENDULUM) {   // data env == model (pyth_idpendulum.py:71-87 calls the model's Dynamics)
-        const IdpConst IC = idp_const();
-        float s[6], sn[6], s0[6];
-        for (int i = 0; i < 6; ++i) s0[i] = s[i] = obs_unscale(env, i, ob[i]);
-        float rs = 0.f;
-        for (int rep = 0; rep < nrep; ++rep) {
-            IdpSub w;
-            for (int k = 0; k < 5; ++k) {   // same arithmetic as the rollout kernels (one sincosf pair, then rotations)
-                if (k == 0) idp_substep<true>(IC, s, 500.f * u[0], 0.002f, sn, w);
-                else idp_substep<false>(IC, s, 500.f * u[0], 0.002f, sn, w);
-                idp_advance_trig(s, 0.002f, w, w);
-                for (int i = 0; i < 6; ++i) s[i] = sn[i];
-            }
-            r = idp_reward(s, u[0]);
-            rs = last_only ? r : rs + r;
-            done_m = idp_done(IC, s);
-        }
-        r = rs;
-        for (int i = 0; i < 6; ++i) nob[i] = (dn && !env.scale_obs) ? ob[i] : obs_rescale(env, i, dn ? s0[i] : s[i]);
+        env_step_state_model<GOPS_ENV_LQ, GOPS_MAX_LQ_STATE>(env, data, dn, ob, u, nob, r, done_m);
+    } else if (env.kind == GOPS_ENV_CARTPOLE) {
+        env_step_state_model<GOPS_ENV_CARTPOLE, 4>(env, data, dn, ob, u, nob, r, done_m);
+    } else if (env.kind == GOPS_ENV_PENDULUM) {
+        env_step_state_model<GOPS_ENV_PENDULUM, 3>(env, data, dn, ob, u, nob, r, done_m);
+    } else if (env.kind == GOPS_ENV_IDPENDULUM) {
+        env_step_state_model<GOPS_ENV_IDPENDULUM, 6>(env, data, dn, ob, u, nob, r, done_m);
     } else if (env.kind == GOPS_ENV_MOBILEROBOT) {
         const MobConst MC = mob_const();
         float x[MOB_OBS], xn[MOB_OBS], c;

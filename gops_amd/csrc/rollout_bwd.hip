@@ -1053,6 +1053,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                         // (every sub-step's reward carries g_r, or only the last one's)
                         repeated = true;
                         const int nrep = min(p.env.repeat_num, GOPS_MAX_REPEAT);
+                        // (register-form twins: state_model_substep / state_model_substep_bwd, env_models.h)
                         auto fwd1 = [&](const float* xi, float* xo) {
                             float rd = 0.f;
                             if constexpr (ENV == GOPS_ENV_LQ) {

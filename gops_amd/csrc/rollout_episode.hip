@@ -54,11 +54,10 @@ struct EpisodeLayout {
     size_t obs_n, state_n, refp_n, reft_n;
 };
 
-inline size_t ep_align(size_t nfloats) { return (nfloats + 63) & ~(size_t)63; }   // 256-byte steps
-
 EpisodeLayout episode_layout(const GopsEnv& e, int E) {
     EpisodeLayout l{};
     const bool ref = env_has_ref_table(e.kind);
+    auto ep_align = [](size_t nfloats) { return align256(nfloats * sizeof(float)) / sizeof(float); };   // the layout counts floats
     const int sd = e.kind == GOPS_ENV_VEH3DOFCONTI ? 6 : e.kind == GOPS_ENV_VEH2DOF ? 4 : 0;
     const int rf = e.kind == GOPS_ENV_VEH3DOFCONTI ? (e.pre_horizon + 1) * 4 : e.kind == GOPS_ENV_VEH2DOF ? (e.pre_horizon + 1) * 2 : 0;
     l.obs_n = ep_align((size_t)E * e.obs_dim);

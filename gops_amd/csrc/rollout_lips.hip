@@ -55,28 +55,9 @@ struct LipsParams {
     float *kpre, *dkpre, *Kws, *Nws, *y;   // [B], y [B][m]
 };
 
-// act(z), act'(z), act''(z) as torch evaluates them (relu'(0) = 0, relu'' = 0; gelu in erf form)
+// act3_t (common.h) for a run-time activation id
 __device__ __forceinline__ void lips_act3(int act, float z, float& a, float& d1, float& d2) {
-    switch (act) {
-        case GOPS_ACT_RELU: a = fmaxf(z, 0.f); d1 = z > 0.f ? 1.f : 0.f; d2 = 0.f; break;
-        case GOPS_ACT_ELU: { const float e = expf(fminf(z, 0.f)); a = z > 0.f ? z : expm1f(z); d1 = z > 0.f ? 1.f : e; d2 = z > 0.f ? 0.f : e; break; }
-        case GOPS_ACT_SELU: {
-            const float e = expf(fminf(z, 0.f));
-            a = SELU_SCALE * (z > 0.f ? z : SELU_ALPHA * expm1f(z));
-            d1 = z > 0.f ? SELU_SCALE : SELU_SCALE * SELU_ALPHA * e;
-            d2 = z > 0.f ? 0.f : SELU_SCALE * SELU_ALPHA * e;
-            break;
-        }
-        case GOPS_ACT_GELU: {
-            const float cdf = 0.5f * (1.f + erff(z * 0.70710678118654752440f));
-            const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
-            a = z * cdf; d1 = cdf + z * pdf; d2 = pdf * (2.f - z * z);
-            break;
-        }
-        case GOPS_ACT_SIGMOID: a = 1.f / (1.f + expf(-z)); d1 = a * (1.f - a); d2 = d1 * (1.f - 2.f * a); break;
-        case GOPS_ACT_TANH: a = tanhf(z); d1 = 1.f - a * a; d2 = -2.f * a * d1; break;
-        default: a = z; d1 = 1.f; d2 = 0.f; break;
-    }
+    act_dispatch(act, [&]<int ACT>() { act3_t<ACT>(z, a, d1, d2); });
 }
 
 // torch.nn.Softplus (beta 1, threshold 20) and its derivative
@@ -444,7 +425,6 @@ __global__ __launch_bounds__(LIPS_NT) void lips_dw_kernel(const LipsDwParams p) 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-static size_t lips_align(size_t n) { return (n + 255) & ~(size_t)255; }
 static bool lips_width_ok(int w) { return w >= 16 && w <= LIPS_MAX_WIDTH && w % 16 == 0; }
 static bool lips_act_ok(int a) { return a >= GOPS_ACT_RELU && a <= GOPS_ACT_TANH; }
 
@@ -507,7 +487,7 @@ static LipsPlan lips_plan(const GopsLipsNet& d, int B) {
     if (pl.slab_samples < 64) pl.slab_samples = 64;
     pl.slabs = (B + pl.slab_samples - 1) / pl.slab_samples;
     size_t off = 0;
-    auto take = [&](size_t floats) { const size_t o = off; off += lips_align(floats * sizeof(float)); return o; };
+    auto take = [&](size_t floats) { const size_t o = off; off += align256(floats * sizeof(float)); return o; };
     const size_t rows = (size_t)B * NR;
     for (int l = 0; l < pl.L; ++l) { pl.Z[l] = take(rows * f.sizes[l + 1]); pl.D[l] = take(rows * f.sizes[l + 1]); }
     pl.FJ = take(rows * m); pl.DO = take(rows * m);

@@ -165,87 +165,6 @@ __device__ __forceinline__ void poly_policy(const PolyParams& p, const float (&p
     }
 }
 
-// ---- one wrapped model step (env_step_kernel's arithmetic for the four models whose observation is the state) -------------------
-// o: the observation the step starts from (what the policy saw); u: the wrapped actions; dn: done flag (MaskAtDone) of the step.
-// -> on: the next observation, r: the model's (summed / last) reward, done_m: the base model's done test of the last sub-step.
-template <int ENV, int N>
-__device__ __forceinline__ void poly_model_step(const GopsEnv& env, const float (&o)[N], const float (&u)[GOPS_MAX_ACT], bool dn,
-                                                float (&on)[N], float& r, bool& done_m) {
-    const int nrep = env.repeat_num > 1 ? env.repeat_num : 1;
-    const bool last_only = nrep > 1 && env.repeat_last_reward != 0;
-    r = 0.f;
-    done_m = false;
-    if constexpr (ENV == GOPS_ENV_LQ) {
-        float x[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, xn[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < N; ++i) x[i] = obs_unscale(env, i, o[i]);
-        float rs = 0.f, rr = 0.f;
-#pragma unroll 1
-        for (int rep = 0; rep < nrep; ++rep) {
-            if (rep > 0 && !dn)
-#pragma unroll
-                for (int i = 0; i < N; ++i) x[i] = xn[i];
-            lq_forward(env, x, u, xn, rr);
-            rs = last_only ? rr : rs + rr;
-        }
-        r = rs;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const float v = obs_rescale(env, i, dn ? x[i] : xn[i]);
-            on[i] = env.clip_obs ? clampf(v, env.obs_low[i], env.obs_high[i]) : v;
-        }
-    } else if constexpr (ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {   // (N = 4 / 3)
-        float x[4] = {0.f, 0.f, 0.f, 0.f}, xn[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < N; ++i) x[i] = obs_unscale(env, i, o[i]);
-        float rs = 0.f, rr = 0.f;
-#pragma unroll 1
-        for (int rep = 0; rep < nrep; ++rep) {
-            if (rep > 0 && !dn)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[i] = xn[i];
-            if constexpr (ENV == GOPS_ENV_CARTPOLE) {
-                cart_forward(cart_const(), x, u[0], xn, rr, done_m);
-            } else {
-                PendStep w;
-                pend_forward(x, u[0], xn, rr, w);
-            }
-            rs = last_only ? rr : rs + rr;
-        }
-        r = rs;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const float v = obs_rescale(env, i, dn ? x[i] : xn[i]);
-            on[i] = env.clip_obs ? clampf(v, env.obs_low[i], env.obs_high[i]) : v;
-        }
-    } else {   // GOPS_ENV_IDPENDULUM (N = 6)
-        static_assert(ENV == GOPS_ENV_IDPENDULUM && N == 6, "env kind / observation width");
-        const IdpConst IC = idp_const();
-        float s[6], sn[6], s0[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) s0[i] = s[i] = obs_unscale(env, i, o[i]);
-        float rs = 0.f;
-#pragma unroll 1
-        for (int rep = 0; rep < nrep; ++rep) {
-            IdpSub w;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                if (k == 0) idp_substep<true>(IC, s, 500.f * u[0], 0.002f, sn, w);
-                else idp_substep<false>(IC, s, 500.f * u[0], 0.002f, sn, w);
-                idp_advance_trig(s, 0.002f, w, w);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) s[i] = sn[i];
-            }
-            const float rr = idp_reward(s, u[0]);
-            rs = last_only ? rr : rs + rr;
-            done_m = idp_done(IC, s);
-        }
-        r = rs;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) on[i] = (dn && !env.scale_obs) ? o[i] : obs_rescale(env, i, dn ? s0[i] : s[i]);
-    }
-}
-
 // ---- adjoint of one wrapped model step (the per-trajectory env phase of rollout_bwd.hip's streamed sweep, register form) --------
 // Gin: adjoint of the next observation; g_r: adjoint of the (shaped) reward; -> go: adjoint of the observation the step started from
 // (overwritten), gu: adjoint of the wrapped actions (overwritten).
@@ -260,80 +179,8 @@ __device__ __forceinline__ void poly_model_step_bwd(const GopsEnv& env, const fl
     for (int i = 0; i < N; ++i) { Gin[i] = Gin_[i]; x[i] = obs_unscale(env, i, o[i]); }
 #pragma unroll
     for (int a = 0; a < GOPS_MAX_ACT; ++a) gu[a] = 0.f;
-    const IdpConst IC = idp_const();
-    // one base-model sub-step and its adjoint (gxo overwritten, guo overwritten)
-    auto fwd1 = [&](const float* xi, float* xo) {
-        float rd = 0.f;
-        if constexpr (ENV == GOPS_ENV_LQ) {
-            lq_forward(env, xi, u, xo, rd);
-        } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
-            bool dd;
-            cart_forward(cart_const(), xi, u[0], xo, rd, dd);
-        } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
-            PendStep w;
-            pend_forward(xi, u[0], xo, rd, w);
-        } else {
-            float s5[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) s5[i] = xi[i];
-            IdpSub w;
-            idp_substep<true>(IC, s5, 500.f * u[0], 0.002f, xo, w);
-#pragma unroll
-            for (int k = 1; k < 5; ++k) {
-                idp_advance_trig(s5, 0.002f, w, w);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) s5[i] = xo[i];
-                idp_substep<false>(IC, s5, 500.f * u[0], 0.002f, xo, w);
-            }
-        }
-    };
-    auto bwd1 = [&](const float* xi, const float* gn, float gr, float* gxo, float* guo) {
-#pragma unroll
-        for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) gxo[i] = 0.f;
-#pragma unroll
-        for (int a = 0; a < GOPS_MAX_ACT; ++a) guo[a] = 0.f;
-        if constexpr (ENV == GOPS_ENV_LQ) {
-            lq_backward(env, xi, u, gn, gr, gxo, guo);
-        } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
-            cart_backward(cart_const(), xi, u[0], gn, gxo, guo[0]);
-        } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
-            pend_backward(xi, u[0], gn, gr, gxo, guo[0]);
-        } else {
-            // the 5 Euler sub-steps recomputed, every sub-step's input state and intermediates kept in registers
-            float sk[5][6];
-            IdpSub wk[5];
-            float sc_[6], sn_[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) sc_[i] = xi[i];
-            const float a = u[0], force = 500.f * a;
-            IdpSub w;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                if (k == 0) idp_substep<true>(IC, sc_, force, 0.002f, sn_, w);
-                else idp_substep<false>(IC, sc_, force, 0.002f, sn_, w);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) sk[k][i] = sc_[i];
-                wk[k] = w;
-                idp_advance_trig(sc_, 0.002f, w, w);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) sc_[i] = sn_[i];
-            }
-            float g[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g[i] = gn[i];
-            g[1] += gr * (-10.f * sc_[1]);
-            g[2] += gr * (-20.f * sc_[2]);
-            g[3] += gr * (-1.f * sc_[3]);
-            g[4] += gr * (-1.f * sc_[4]);
-            g[5] += gr * (-2.f * sc_[5]);
-            float gforce = 0.f;
-#pragma unroll
-            for (int k = 4; k >= 0; --k) idp_substep_bwd(IC, sk[k], 0.002f, wk[k], g, gforce);
-            guo[0] = 500.f * gforce + gr * (-2.f * a);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) gxo[i] = g[i];
-        }
-    };
+    float rd;   // reward and done test of the recomputed sub-steps: not used here
+    bool dd;
     const int nrep = env.repeat_num > 1 ? min(env.repeat_num, GOPS_MAX_REPEAT) : 1;
     // ClipObservation saw the (rescaled) result of the last sub-step (idpendulum: no observation bounds)
     if (env.clip_obs && ENV != GOPS_ENV_IDPENDULUM) {
@@ -343,7 +190,7 @@ __device__ __forceinline__ void poly_model_step_bwd(const GopsEnv& env, const fl
         if (!dn) {
 #pragma unroll 1
             for (int rep = 0; rep < nrep; ++rep) {
-                fwd1(xl, xfin);
+                state_model_substep<ENV>(env, xl, u, xfin, rd, dd);
 #pragma unroll
                 for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) xl[i] = xfin[i];
             }
@@ -371,13 +218,13 @@ __device__ __forceinline__ void poly_model_step_bwd(const GopsEnv& env, const fl
             for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) xr[i] = x[i];
 #pragma unroll 1
             for (int k = 0; k < rep; ++k) {
-                fwd1(xr, xt);
+                state_model_substep<ENV>(env, xr, u, xt, rd, dd);
 #pragma unroll
                 for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) xr[i] = xt[i];
             }
             const float gr = (!env.repeat_last_reward || rep == nrep - 1 || nrep == 1) ? g_rm : 0.f;
             float gxo[GOPS_MAX_LQ_STATE], guo[GOPS_MAX_ACT];
-            bwd1(xr, g, gr, gxo, guo);
+            state_model_substep_bwd<ENV>(env, xr, u, g, gr, gxo, guo);
 #pragma unroll
             for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) g[i] = gxo[i];
 #pragma unroll
@@ -418,7 +265,7 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_fwd_kernel(const PolyParams
         for (int a = 0; a < GOPS_MAX_ACT; ++a) u[a] = a < p.A ? wrap_action(p.env, a, abar[a]) : 0.f;
         float on[N], r;
         bool done_m;
-        poly_model_step<ENV, N>(p.env, o, u, dn, on, r, done_m);
+        state_model_step<ENV, N>(p.env, o, u, dn, on, r, done_m);
         float rr = dn ? 0.f : r;
         if (p.env.shaping) rr = (rr + p.env.reward_shift) * p.env.reward_scale;
         v += rr * p.gpow[t];
@@ -445,14 +292,6 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_fwd_kernel(const PolyParams
 #pragma unroll
         for (int i = 0; i < N; ++i) p.final_obs[(size_t)b * N + i] = o[i];
     if (p.final_done != nullptr) p.final_done[b] = dH ? 1.f : 0.f;
-}
-
-// sum of v over the block in a fixed order (butterfly inside each wave, then the four waves in order), result valid in thread 0..
-__device__ __forceinline__ float poly_block_sum(float v, float* red, int slot, int nslots) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * nslots + slot] = v;
-    return v;
 }
 
 // ---- backward sweep ------------------------------------------------------------------------------------------------------------
@@ -519,11 +358,11 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_bwd_kernel(const PolyParams
             for (int i = 0; i < N; ++i) go[i] = gx[i];
         }
     }
-    // per-block partial rows, fixed order
+    // per-block partial rows, fixed order: butterfly inside each wave, then the four waves in order
 #pragma unroll
     for (int a = 0; a < GOPS_MAX_ACT; ++a)
 #pragma unroll
-        for (int k = 0; k < FP; ++k) (void)poly_block_sum(gw[a][k], red, a * FP + k, GOPS_MAX_ACT * FP);
+        for (int k = 0; k < FP; ++k) wave_sum(gw[a][k], red, a * FP + k, GOPS_MAX_ACT * FP);
     __syncthreads();
     const int A = p.A, ldw = p.ldw;
     for (int e = threadIdx.x; e < A * FP; e += POLY_THREADS) {
@@ -569,7 +408,7 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_value_bwd_kernel(const floa
         acc[K] = g;
     }
 #pragma unroll
-    for (int k = 0; k <= K; ++k) (void)poly_block_sum(acc[k], red, k, K + 1);
+    for (int k = 0; k <= K; ++k) wave_sum(acc[k], red, k, K + 1);
     __syncthreads();
     const int e = threadIdx.x;
     if (e <= K) {
@@ -582,7 +421,6 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_value_bwd_kernel(const floa
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 
 static int poly_blocks(int B) { return (B + POLY_THREADS - 1) / POLY_THREADS; }
-static size_t poly_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // feature degree of a GopsMlp.hidden_act code, 0 = not a make_features code
 static int poly_full_degree(int code) {
@@ -638,10 +476,10 @@ static PolyPlan poly_plan(const GopsRolloutDesc& d) {
     pl.blocks = poly_blocks(B);
     pl.ldw = poly_feat_dim_rt(n, poly_full_degree(d.policy.hidden_act)) + (d.finite_horizon ? 1 : 0);
     size_t off = 0;
-    pl.obs = off; off += poly_align((size_t)(H + 1) * n * B * sizeof(float));
-    pl.done = off; off += poly_align((size_t)(H + 1) * B * sizeof(float));
-    pl.pw = off; off += poly_align((size_t)pl.blocks * A * pl.ldw * sizeof(float));
-    pl.pb = off; off += poly_align((size_t)pl.blocks * A * sizeof(float));
+    pl.obs = off; off += align256((size_t)(H + 1) * n * B * sizeof(float));
+    pl.done = off; off += align256((size_t)(H + 1) * B * sizeof(float));
+    pl.pw = off; off += align256((size_t)pl.blocks * A * pl.ldw * sizeof(float));
+    pl.pb = off; off += align256((size_t)pl.blocks * A * sizeof(float));
     pl.bytes = off;
     return pl;
 }
@@ -735,7 +573,7 @@ int poly_rollout_backward(const GopsRolloutDesc& d, const float* grad_v, const G
 size_t poly_value_workspace_bytes(const GopsMlp& v, int B) {
     if (B < 1 || poly_check_value(v, v.sizes[0]) != GOPS_OK) return 0;
     const int K = v.sizes[0] * (v.sizes[0] + 1) / 2;
-    return poly_align((size_t)poly_blocks(B) * K * sizeof(float)) + poly_align((size_t)poly_blocks(B) * sizeof(float));
+    return align256((size_t)poly_blocks(B) * K * sizeof(float)) + align256((size_t)poly_blocks(B) * sizeof(float));
 }
 
 int poly_value_forward(const GopsMlp& v, int B, const float* obs, float* out, hipStream_t s) {
@@ -766,7 +604,7 @@ int poly_value_backward(const GopsMlp& v, int B, const float* obs, const float* 
     if (ws == nullptr || bytes < need) return GOPS_ERR_WORKSPACE;
     const int n = v.sizes[0], K = n * (n + 1) / 2, nb = poly_blocks(B);
     float* pw = static_cast<float*>(ws);
-    float* pb = g.bias[0] != nullptr ? reinterpret_cast<float*>(static_cast<char*>(ws) + poly_align((size_t)nb * K * sizeof(float))) : nullptr;
+    float* pb = g.bias[0] != nullptr ? reinterpret_cast<float*>(static_cast<char*>(ws) + align256((size_t)nb * K * sizeof(float))) : nullptr;
     const float* nm = v.weight[1];
     const dim3 gr(nb), t(POLY_THREADS);
     switch (n) {

@@ -6,7 +6,7 @@
 // batch-wide reductions per step.  More workgroups would only add grid syncs to a chain this short.
 //
 // Reductions have a fixed order - butterfly inside each wave, then the waves in index order through LDS, summed by EVERY thread
-// (as rollout_poly.hip's poly_block_sum) - so every thread holds the same sums bit for bit, takes the same Adam step in its own
+// (wave_sum of common.h, as rollout_poly.hip) - so every thread holds the same sums bit for bit, takes the same Adam step in its own
 // registers and reaches the same continue/stop decision: no barrier sits under divergent control flow, no float atomics, results
 // are reproducible run to run.  The trip count is bounded by max_steps, never by convergence alone.
 //
@@ -83,8 +83,7 @@ __global__ __launch_bounds__(GOPS_RPI_MAX_BATCH) void rpi_evaluate_kernel(const 
     // then beta1^t and beta2^t are 0 in double (0.99^t < 1e-300 from t = 68 732), so the bias corrections are exactly 1 either way,
     // and a lane's counter has long passed any time limit (max_step < 2^24), so its test stays true.
     float tcount = hdr[2 * RPI_MAX_F];
-    double b1p = pow(p.beta1, (double)tcount), b2p = pow(p.beta2, (double)tcount);
-    const float lerp_w = (float)(1.0 - p.beta1), beta2f = (float)p.beta2, omb2 = (float)(1.0 - p.beta2), epsf = (float)p.eps;
+    RpiAdam adam(p.lr, p.beta1, p.beta2, p.eps, tcount);
 
     float x[S], xs[S], ds[S], Us = 0.f, cnt = 0.f, shown = -1.f, maxs = 0.f;
 #pragma unroll
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(GOPS_RPI_MAX_BATCH) void rpi_evaluate_kernel(const 
         for (int m = 0; m < S; ++m) h += dv[m] * ds[m];
         return valid ? fabsf(h) : 0.f;
     };
-    rpi_wave_sum(heldout(), red2, 0, 1);
+    wave_sum(heldout(), red2, 0, 1);
     __syncthreads();
     const float before = rpi_block_sum(red2, 0, 1, nwaves) / invB_den;
     float after = before, loss = 0.f;
@@ -134,32 +133,23 @@ __global__ __launch_bounds__(GOPS_RPI_MAX_BATCH) void rpi_evaluate_kernel(const 
 #pragma unroll
         for (int m = 0; m < S; ++m) { h += dv[m] * d[m]; y[m] = x[m] * norm[m]; }
         const float sg = !valid ? 0.f : h > 0.f ? 1.f : h < 0.f ? -1.f : 0.f;
-        rpi_wave_sum(valid ? fabsf(h) : 0.f, red1, F, F + 1);
+        wave_sum(valid ? fabsf(h) : 0.f, red1, F, F + 1);
         {
             int k = 0;
 #pragma unroll
             for (int ii = 0; ii < S; ++ii)
 #pragma unroll
                 for (int jj = ii; jj < S; ++jj, ++k)
-                    rpi_wave_sum(sg * ((norm[ii] * d[ii]) * y[jj] + (norm[jj] * d[jj]) * y[ii]), red1, k, F + 1);
+                    wave_sum(sg * ((norm[ii] * d[ii]) * y[jj] + (norm[jj] * d[jj]) * y[ii]), red1, k, F + 1);
         }
         __syncthreads();
         loss = rpi_block_sum(red1, F, F + 1, nwaves) / invB_den;
-        // Adam (torch.optim.Adam, single-tensor form; bias corrections in double as the host computes them)
         tcount += 1.f;
-        b1p *= p.beta1;
-        b2p *= p.beta2;
-        const float step_size = (float)(p.lr / (1.0 - b1p)), bc2s = (float)sqrt(1.0 - b2p);
+        adam.advance();
 #pragma unroll
-        for (int k = 0; k < F; ++k) {
-            const float g = rpi_block_sum(red1, k, F + 1, nwaves) / invB_den;
-            am[k] = am[k] + lerp_w * (g - am[k]);
-            av[k] = av[k] * beta2f + omb2 * (g * g);
-            const float denom = sqrtf(av[k]) / bc2s + epsf;
-            w[k] = w[k] - step_size * (am[k] / denom);
-        }
+        for (int k = 0; k < F; ++k) adam.update(w[k], am[k], av[k], rpi_block_sum(red1, k, F + 1, nwaves) / invB_den);
         // held-out norm with the new weights
-        rpi_wave_sum(heldout(), red2, 0, 1);
+        wave_sum(heldout(), red2, 0, 1);
         __syncthreads();
         after = rpi_block_sum(red2, 0, 1, nwaves) / invB_den;
         // reset select (rpi.py:315-325): this step's draw for lanes that ended

@@ -13,7 +13,7 @@
 //   value net:   forward with the tangent along f (a'_l = act'(z_l) z'_l), h = U + W_L a'_{L-1}; reverse over that pass with the
 //                seed sign(h) / B: adj z'_l = p_l act'(z_l), adj z_l = p_l act''(z_l) z'_l + q_l act'(z_l),
 //                dW_l += adj z_l a_{l-1}' + adj z'_l a'_{l-1}', db_l += adj z_l (the output bias has no gradient);
-// then Adam on every weight and hidden bias (the formulas of rpi_evaluate_kernel; each parameter has ONE owning thread that keeps
+// then Adam on every weight and hidden bias (RpiAdam of rpi_env.h, as rpi_evaluate_kernel; each parameter has ONE owning thread that keeps
 // its moments in registers and its value in LDS), the held-out mean|h| with the new weights (forward-tangent pass only; the
 // held-out f and U under the target's pair are evaluated once before the loop), and the 0.88 test.  The loss and the norm are
 // summed by thread 0 in tile order and read back by every thread from LDS after a barrier, so all threads take the same decision
@@ -56,31 +56,6 @@ struct RpiMlpParams {
     float* trace;            // [max_steps][2] or nullptr
     double lr, beta1, beta2, eps;
 };
-
-// act(z), act'(z), act''(z) as torch evaluates them and their derivatives (fp32 libm)
-template <int ACT>
-__device__ __forceinline__ void rpi_act3(float z, float& a, float& d1, float& d2) {
-    if constexpr (ACT == GOPS_ACT_ELU) {
-        const float e = expf(fminf(z, 0.f));
-        a = z > 0.f ? z : expm1f(z);
-        d1 = z > 0.f ? 1.f : e;
-        d2 = z > 0.f ? 0.f : e;
-    } else if constexpr (ACT == GOPS_ACT_TANH) {
-        a = tanhf(z);
-        d1 = 1.f - a * a;
-        d2 = -2.f * a * d1;
-    } else if constexpr (ACT == GOPS_ACT_SIGMOID) {
-        a = 1.f / (1.f + expf(-z));
-        d1 = a * (1.f - a);
-        d2 = d1 * (1.f - 2.f * a);
-    } else {   // GELU, erf form
-        const float cdf = 0.5f * (1.f + erff(z * 0.70710678118654752440f));
-        const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
-        a = z * cdf;
-        d1 = cdf + z * pdf;
-        d2 = pdf * (2.f - z * z);
-    }
-}
 
 __device__ __forceinline__ float4 lds4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
@@ -162,8 +137,7 @@ __global__ __launch_bounds__(RM_NT) void rpi_mlp_evaluate_kernel(const RpiMlpPar
     if (ownl) { ml = st_m[oWL + r]; vl = st_v[oWL + r]; }
     // The Adam step count and the lanes' counters are floats in the state block, as in rpi_evaluate_kernel (exact up to 2^24).
     float tcount = hdr[0];
-    double b1p = pow(p.beta1, (double)tcount), b2p = pow(p.beta2, (double)tcount);
-    const float lerp_w = (float)(1.0 - p.beta1), beta2f = (float)p.beta2, omb2 = (float)(1.0 - p.beta2), epsf = (float)p.eps;
+    RpiAdam adam(p.lr, p.beta1, p.beta2, p.eps, tcount);
     __syncthreads();
 
     // ---- stages of one tile ----
@@ -187,7 +161,7 @@ __global__ __launch_bounds__(RM_NT) void rpi_mlp_evaluate_kernel(const RpiMlpPar
                     if (TAN) zp = fmaf(w, f[m], zp);
                 }
                 float a, d1, d2;
-                rpi_act3<ACT>(z, a, d1, d2);
+                act3_t<ACT>(z, a, d1, d2);
                 A1[j * RM_LDA + r] = a;
                 D1[j * RM_LDA + r] = d1;
                 if (TAN) { AP1[j * RM_LDA + r] = d1 * zp; E1[j * RM_LDA + r] = d2 * zp; }
@@ -216,7 +190,7 @@ __global__ __launch_bounds__(RM_NT) void rpi_mlp_evaluate_kernel(const RpiMlpPar
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float a, d1, d2;
-                rpi_act3<ACT>(z[i], a, d1, d2);
+                act3_t<ACT>(z[i], a, d1, d2);
                 d1r[i] = d1; er[i] = d2 * zp[i]; apr[i] = d1 * zp[i];
             }
         }
@@ -479,25 +453,17 @@ __global__ __launch_bounds__(RM_NT) void rpi_mlp_evaluate_kernel(const RpiMlpPar
         }
         if (tid == 0) RED[1] = sum / Bf;
 
-        // Adam (torch.optim.Adam, single-tensor form; bias corrections in double as the host computes them), by the owners
+        // Adam, by the owners
         tcount += 1.f;
-        b1p *= p.beta1;
-        b2p *= p.beta2;
-        const float step_size = (float)(p.lr / (1.0 - b1p)), bc2s = (float)sqrt(1.0 - b2p);
-        auto adam = [&](float gr, float& am, float& av, float* w) {
-            am = am + lerp_w * (gr - am);
-            av = av * beta2f + omb2 * (gr * gr);
-            const float denom = sqrtf(av) / bc2s + epsf;
-            *w = *w - step_size * (am / denom);
-        };
+        adam.advance();
         if (own2) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { adam(acc2[i], m2[i], v2[i], NV + N_W2 + (16 * g + i) * 64 + r); acc2[i] = 0.f; }
+            for (int i = 0; i < 16; ++i) { adam.update(NV[N_W2 + (16 * g + i) * 64 + r], m2[i], v2[i], acc2[i]); acc2[i] = 0.f; }
         }
-        if (own1) adam(acc1, m1, v1, NV + N_W1 + r * 4 + g);
-        if (ownb1) adam(accb1, mb1, vb1, NV + N_B1 + r);
-        if (ownb2) adam(GB2[r], mb2, vb2, NV + N_B2 + r);
-        if (ownl) adam(NH == 2 ? GWL[r] : accl, ml, vl, NV + N_WL + r);
+        if (own1) adam.update(NV[N_W1 + r * 4 + g], m1, v1, acc1);
+        if (ownb1) adam.update(NV[N_B1 + r], mb1, vb1, accb1);
+        if (ownb2) adam.update(NV[N_B2 + r], mb2, vb2, GB2[r]);
+        if (ownl) adam.update(NV[N_WL + r], ml, vl, NH == 2 ? GWL[r] : accl);
         acc1 = 0.f, accb1 = 0.f, accl = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc2[i] = 0.f;

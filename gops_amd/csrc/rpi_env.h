@@ -1,6 +1,6 @@
 // Env arithmetic and block sums shared by RPI's two single-launch policy-evaluation kernels (rollout_rpi.hip: POLY value,
 // rollout_rpi_mlp.hip: MLP value): the three zero-sum game models in the host models' order of operations, the wrapper chain, the
-// utility, and the fixed-order wave / block sums.
+// utility, the Adam step, and the fixed-order block sum.
 #pragma once
 #include "common.h"
 
@@ -78,13 +78,30 @@ __device__ __forceinline__ float rpi_cost(const float* c, const float* x, float 
     return cost + c[GOPS_RPI_C_R] * (u * u) - (ga * ga) * (a * a);
 }
 
-// butterfly inside the wave, lane 0 leaves the wave's sum in red[wave * nslots + slot]
-__device__ __forceinline__ void rpi_wave_sum(float v, float* red, int slot, int nslots) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * nslots + slot] = v;
-}
-// after the barrier: the waves' sums in index order, the same value in every thread
+// torch.optim.Adam, single-tensor form, as both evaluation kernels step it: the bias corrections in double as the host computes
+// them, the element update in fp32.  `tcount`: the steps taken so far.
+struct RpiAdam {
+    float lerp_w, beta2f, omb2, epsf, step_size, bc2s;
+    double lr, beta1, beta2, b1p, b2p;
+    __device__ __forceinline__ RpiAdam(double lr_, double beta1_, double beta2_, double eps, float tcount)
+        : lerp_w((float)(1.0 - beta1_)), beta2f((float)beta2_), omb2((float)(1.0 - beta2_)), epsf((float)eps), step_size(0.f), bc2s(0.f),
+          lr(lr_), beta1(beta1_), beta2(beta2_), b1p(pow(beta1_, (double)tcount)), b2p(pow(beta2_, (double)tcount)) {}
+    // the next step's size and second-moment correction
+    __device__ __forceinline__ void advance() {
+        b1p *= beta1;
+        b2p *= beta2;
+        step_size = (float)(lr / (1.0 - b1p));
+        bc2s = (float)sqrt(1.0 - b2p);
+    }
+    __device__ __forceinline__ void update(float& w, float& m, float& v, float g) const {
+        m = m + lerp_w * (g - m);
+        v = v * beta2f + omb2 * (g * g);
+        const float denom = sqrtf(v) / bc2s + epsf;
+        w = w - step_size * (m / denom);
+    }
+};
+
+// after the barrier that follows wave_sum (common.h): the waves' sums in index order, the same value in every thread
 __device__ __forceinline__ float rpi_block_sum(const float* red, int slot, int nslots, int nwaves) {
     float s = red[slot];
     for (int wv = 1; wv < nwaves; ++wv) s += red[wv * nslots + slot];

@@ -145,6 +145,59 @@ class GopsEpisodeOut(C.Structure):   # gops_episode_rollout
     _fields_ = [(k, C.c_void_p) for k in ("ret", "length", "terminated", "trace_obs", "trace_act", "trace_rew")]
 
 
+def _signatures():
+    """name -> (restype, argtypes) of every symbol of include/gops_hip.h (argtypes None: not declared to ctypes)."""
+    P, vp, i32, sz, f64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_size_t, C.c_double, C.c_int
+    desc, rin, rout, mlp, grad, env, io = (P(t) for t in (GopsRolloutDesc, GopsRolloutIn, GopsRolloutOut, GopsMlp, GopsMlpGrad, GopsEnv,
+                                                          GopsStepIO))
+    tail, adj, tensors, lips = P(GopsUpdateTail), P(GopsRolloutAdjoint), P(GopsAdamTensors), P(GopsLipsNet)
+    return {
+        "gops_hip_version": (rc, None),
+        "gops_rollout_workspace_bytes": (sz, [desc]),
+        "gops_rollout_forward": (rc, [desc, rin, rout, vp, sz, vp]),
+        "gops_rollout_backward": (rc, [desc, rin, vp, grad, vp, sz, vp]),
+        "gops_rollout_backward_open_loop": (rc, [desc, rin, vp, vp, vp, sz, vp]),
+        "gops_rollout_backward_adj": (rc, [desc, rin, vp, grad, adj, vp, sz, vp]),
+        "gops_rollout_backward_open_loop_adj": (rc, [desc, rin, vp, vp, adj, vp, sz, vp]),
+        "gops_rollout_backward_update": (rc, [desc, rin, vp, grad, tail, vp, sz, vp]),
+        "gops_rollout_variant": (rc, [desc]),
+        "gops_env_step": (rc, [env, i32, io, vp]),
+        "gops_env_constraint": (rc, [env, i32, io, vp]),
+        "gops_value_workspace_bytes": (sz, [mlp, i32]),
+        "gops_value_forward": (rc, [mlp, i32, vp, vp, vp, sz, vp]),
+        "gops_value_backward": (rc, [mlp, i32, vp, vp, grad, vp, sz, vp]),
+        "gops_value_backward_update": (rc, [mlp, i32, vp, vp, grad, tail, vp, sz, vp]),
+        "gops_mlp_workspace_bytes": (sz, [mlp, i32]),
+        "gops_mlp_forward": (rc, [mlp, i32, vp, vp, vp, sz, vp]),
+        "gops_mlp_backward": (rc, [mlp, i32, vp, vp, grad, vp, sz, vp]),
+        "gops_mlp_backward_x": (rc, [mlp, i32, vp, vp, grad, vp, vp, sz, vp]),
+        "gops_adam_step": (rc, [tensors, vp, f64, f64, f64, vp]),
+        "gops_polyak_update": (rc, [tensors, f64, vp]),
+        "gops_value_loss": (rc, [vp, vp, i32, vp, vp, vp]),
+        "gops_mean_loss": (rc, [vp, i32, f64, vp, vp]),
+        "gops_poly_rollout_workspace_bytes": (sz, [desc]),
+        "gops_poly_rollout_forward": (rc, [desc, rin, rout, vp, sz, vp]),
+        "gops_poly_rollout_backward": (rc, [desc, rin, vp, grad, vp, sz, vp]),
+        "gops_poly_value_workspace_bytes": (sz, [mlp, i32]),
+        "gops_poly_value_forward": (rc, [mlp, i32, vp, vp, vp]),
+        "gops_poly_value_backward": (rc, [mlp, i32, vp, vp, grad, vp, sz, vp]),
+        "gops_rpi_state_bytes": (sz, [i32, i32]),
+        "gops_rpi_evaluate": (rc, [i32, i32, i32, _fp, vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, vp, vp, vp]),
+        "gops_rpi_mlp_state_bytes": (sz, [i32, i32, mlp]),
+        "gops_rpi_mlp_evaluate": (rc, [i32, i32, i32, _fp, mlp, mlp, vp, vp, vp, sz, f64, f64, f64, f64, vp, vp, vp]),
+        "gops_episode_workspace_bytes": (sz, [env, mlp, i32, i32]),
+        "gops_episode_rollout": (rc, [env, mlp, i32, i32, io, P(GopsEpisodeOut), vp, sz, vp]),
+        "gops_lips_workspace_bytes": (sz, [lips, i32]),
+        "gops_lips_forward": (rc, [lips, i32, vp, vp, vp, vp, vp, sz, vp]),
+        "gops_lips_backward": (rc, [lips, i32, vp, vp, P(GopsLipsGrad), vp, sz, vp]),
+        "gops_profile_enable": (rc, [i32]),
+        "gops_profile_reset": (rc, []),
+        "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
+    }
+
+
+_SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _lib = None
 
 
@@ -157,124 +210,14 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C gops_amd/csrc`). The HIP rollout has no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        l.gops_hip_version.restype = C.c_int
-        l.gops_rollout_workspace_bytes.restype = C.c_size_t
-        l.gops_rollout_workspace_bytes.argtypes = [C.POINTER(GopsRolloutDesc)]
-        l.gops_rollout_forward.restype = C.c_int
-        l.gops_rollout_forward.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn),
-                                           C.POINTER(GopsRolloutOut), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_rollout_backward_open_loop.restype = C.c_int
-        l.gops_rollout_backward_open_loop.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.c_void_p,
-                                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_rollout_backward.restype = C.c_int
-        l.gops_rollout_backward.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.c_void_p,
-                                            C.POINTER(GopsMlpGrad), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_rollout_backward_update.restype = C.c_int
-        l.gops_rollout_backward_update.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.c_void_p,
-                                                   C.POINTER(GopsMlpGrad), C.POINTER(GopsUpdateTail), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_value_backward_update.restype = C.c_int
-        l.gops_value_backward_update.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsMlpGrad),
-                                                 C.POINTER(GopsUpdateTail), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_rollout_backward_adj.restype = C.c_int
-        l.gops_rollout_backward_adj.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.c_void_p,
-                                                C.POINTER(GopsMlpGrad), C.POINTER(GopsRolloutAdjoint), C.c_void_p,
-                                                C.c_size_t, C.c_void_p]
-        l.gops_env_step.restype = C.c_int
-        l.gops_env_step.argtypes = [C.POINTER(GopsEnv), C.c_int32, C.POINTER(GopsStepIO), C.c_void_p]
-        l.gops_env_constraint.restype = C.c_int
-        l.gops_env_constraint.argtypes = [C.POINTER(GopsEnv), C.c_int32, C.POINTER(GopsStepIO), C.c_void_p]
-        l.gops_value_workspace_bytes.restype = C.c_size_t
-        l.gops_value_workspace_bytes.argtypes = [C.POINTER(GopsMlp), C.c_int32]
-        l.gops_value_forward.restype = C.c_int
-        l.gops_value_forward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_size_t, C.c_void_p]
-        l.gops_value_backward.restype = C.c_int
-        l.gops_value_backward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p,
-                                          C.POINTER(GopsMlpGrad), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_mlp_workspace_bytes.restype = C.c_size_t
-        l.gops_mlp_workspace_bytes.argtypes = [C.POINTER(GopsMlp), C.c_int32]
-        l.gops_mlp_forward.restype = C.c_int
-        l.gops_mlp_forward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_mlp_backward.restype = C.c_int
-        l.gops_mlp_backward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsMlpGrad),
-                                        C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_mlp_backward_x.restype = C.c_int
-        l.gops_mlp_backward_x.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsMlpGrad),
-                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_adam_step.restype = C.c_int
-        l.gops_adam_step.argtypes = [C.POINTER(GopsAdamTensors), C.c_void_p, C.c_double, C.c_double, C.c_double,
-                                     C.c_void_p]
-        l.gops_polyak_update.restype = C.c_int
-        l.gops_polyak_update.argtypes = [C.POINTER(GopsAdamTensors), C.c_double, C.c_void_p]
-        l.gops_value_loss.restype = C.c_int
-        l.gops_value_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gops_mean_loss.restype = C.c_int
-        l.gops_mean_loss.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
-        l.gops_rollout_backward_open_loop_adj.restype = C.c_int
-        l.gops_rollout_backward_open_loop_adj.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.c_void_p, C.c_void_p,
-                                                          C.POINTER(GopsRolloutAdjoint), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_rollout_variant.restype = C.c_int
-        l.gops_rollout_variant.argtypes = [C.POINTER(GopsRolloutDesc)]
-        l.gops_poly_rollout_workspace_bytes.restype = C.c_size_t
-        l.gops_poly_rollout_workspace_bytes.argtypes = [C.POINTER(GopsRolloutDesc)]
-        l.gops_poly_rollout_forward.restype = C.c_int
-        l.gops_poly_rollout_forward.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.POINTER(GopsRolloutOut),
-                                                C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_poly_rollout_backward.restype = C.c_int
-        l.gops_poly_rollout_backward.argtypes = [C.POINTER(GopsRolloutDesc), C.POINTER(GopsRolloutIn), C.c_void_p,
-                                                 C.POINTER(GopsMlpGrad), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_poly_value_workspace_bytes.restype = C.c_size_t
-        l.gops_poly_value_workspace_bytes.argtypes = [C.POINTER(GopsMlp), C.c_int32]
-        l.gops_poly_value_forward.restype = C.c_int
-        l.gops_poly_value_forward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gops_poly_value_backward.restype = C.c_int
-        l.gops_poly_value_backward.argtypes = [C.POINTER(GopsMlp), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsMlpGrad),
-                                               C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_rpi_state_bytes.restype = C.c_size_t
-        l.gops_rpi_state_bytes.argtypes = [C.c_int32, C.c_int32]
-        l.gops_rpi_evaluate.restype = C.c_int
-        l.gops_rpi_evaluate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gops_rpi_mlp_state_bytes.restype = C.c_size_t
-        l.gops_rpi_mlp_state_bytes.argtypes = [C.c_int32, C.c_int32, C.POINTER(GopsMlp)]
-        l.gops_rpi_mlp_evaluate.restype = C.c_int
-        l.gops_rpi_mlp_evaluate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(GopsMlp), C.POINTER(GopsMlp),
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_double,
-                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.gops_episode_workspace_bytes.restype = C.c_size_t
-        l.gops_episode_workspace_bytes.argtypes = [C.POINTER(GopsEnv), C.POINTER(GopsMlp), C.c_int32, C.c_int32]
-        l.gops_episode_rollout.restype = C.c_int
-        l.gops_episode_rollout.argtypes = [C.POINTER(GopsEnv), C.POINTER(GopsMlp), C.c_int32, C.c_int32, C.POINTER(GopsStepIO),
-                                           C.POINTER(GopsEpisodeOut), C.c_void_p, C.c_size_t, C.c_void_p]
-        l.gops_lips_workspace_bytes.restype = C.c_size_t
-        l.gops_lips_workspace_bytes.argtypes = [C.POINTER(GopsLipsNet), C.c_int32]
-        l.gops_lips_forward.restype = C.c_int
-        l.gops_lips_forward.argtypes = [C.POINTER(GopsLipsNet), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_size_t, C.c_void_p]
-        l.gops_lips_backward.restype = C.c_int
-        l.gops_lips_backward.argtypes = [C.POINTER(GopsLipsNet), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(GopsLipsGrad), C.c_void_p,
-                                         C.c_size_t, C.c_void_p]
-        l.gops_profile_enable.argtypes = [C.c_int32]
-        l.gops_profile_reset.argtypes = []
-        l.gops_profile_read.restype = C.c_int
-        l.gops_profile_read.argtypes = [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(l, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
         _lib = l
     return _lib
 
-
-EXPORTED_SYMBOLS = ("gops_hip_version", "gops_rollout_workspace_bytes", "gops_rollout_forward",
-                    "gops_rollout_backward", "gops_rollout_backward_open_loop", "gops_rollout_backward_adj", "gops_env_step", "gops_value_workspace_bytes",
-                    "gops_value_forward", "gops_value_backward", "gops_mlp_workspace_bytes", "gops_mlp_forward",
-                    "gops_mlp_backward", "gops_mlp_backward_x", "gops_adam_step", "gops_profile_enable",
-                    "gops_profile_reset", "gops_profile_read", "gops_rollout_variant", "gops_rollout_backward_open_loop_adj",
-                    "gops_env_constraint", "gops_polyak_update", "gops_value_loss", "gops_mean_loss", "gops_rollout_backward_update",
-                    "gops_value_backward_update", "gops_poly_rollout_workspace_bytes", "gops_poly_rollout_forward",
-                    "gops_poly_rollout_backward", "gops_poly_value_workspace_bytes", "gops_poly_value_forward",
-                    "gops_poly_value_backward", "gops_rpi_state_bytes", "gops_rpi_evaluate",
-                    "gops_rpi_mlp_state_bytes", "gops_rpi_mlp_evaluate",
-                    "gops_episode_workspace_bytes", "gops_episode_rollout",
-                    "gops_lips_workspace_bytes", "gops_lips_forward", "gops_lips_backward")
 
 _ERR = {-1: "GOPS_ERR_BAD_ARG", -2: "GOPS_ERR_UNSUPPORTED", -3: "GOPS_ERR_WORKSPACE"}
 
@@ -300,6 +243,17 @@ def _fill(arr, vals):
         arr[i] = float(v)
 
 
+def _fill_mlp(m: GopsMlp, weights, biases, act: str) -> GopsMlp:
+    m.n_layers = len(weights)
+    if weights:
+        m.sizes[0] = weights[0].shape[1]
+    for j, (w, b) in enumerate(zip(weights, biases)):
+        m.sizes[j + 1] = w.shape[0]
+        m.weight[j], m.bias[j] = _ptr(w), _ptr(b)
+    m.hidden_act = ACT_IDS[act]
+    return m
+
+
 def make_mlp(weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], act: str, dtype=None,
              variant_flags: Optional[int] = None) -> GopsMlp:
     """`dtype` ("fp32" / "fp16") and `variant_flags` (VF_*) only matter for `ValueNet` / `Mlp` batches; a `Rollout` takes its
@@ -307,15 +261,9 @@ def make_mlp(weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], ac
     m = GopsMlp()
     m.dtype = dtype_id(dtype)
     m.variant_flags = DEFAULT_VARIANT_FLAGS if variant_flags is None else variant_flags
-    m.n_layers = len(weights)
     if not 2 <= len(weights) <= MAX_LAYERS:
         raise RuntimeError(f"MLP with {len(weights)} Linear layers is outside the HIP path (2..{MAX_LAYERS})")
-    m.sizes[0] = weights[0].shape[1]
-    for j, (w, b) in enumerate(zip(weights, biases)):
-        m.sizes[j + 1] = w.shape[0]
-        m.weight[j] = _ptr(w)
-        m.bias[j] = _ptr(b)
-    m.hidden_act = ACT_IDS[act]
+    _fill_mlp(m, weights, biases, act)
     m._keep = (list(weights), list(biases))   # the struct holds raw pointers: keep the tensors alive
     return m
 
@@ -421,6 +369,54 @@ def mobilerobot_noise(shape, device) -> torch.Tensor:
     return n
 
 
+def _rollout_desc(env: GopsEnv, policy: Optional[GopsMlp], value: Optional[GopsMlp], *, batch, horizon, gamma, finite_horizon,
+                  need_grad, tail_unmasked) -> GopsRolloutDesc:
+    """The fields `Rollout` and `PolyRollout` fill alike."""
+    d = GopsRolloutDesc()
+    d.batch, d.horizon, d.finite_horizon = batch, horizon, int(finite_horizon)
+    d.need_grad, d.tail_value, d.gamma = int(need_grad), int(value is not None), float(gamma)
+    d.tail_unmasked = int(bool(tail_unmasked))   # SPIL's evaluation target: the terminal value is not masked at done
+    d.env = env
+    if policy is not None:
+        d.policy = policy
+    if value is not None:
+        d.value = value
+    return d
+
+
+def _rollout_workspace(ro, bytes_fn, refusal: str, device):
+    """`ro.device` and `ro.workspace`, sized by the library for `ro.desc`; a descriptor it refuses raises `refusal`."""
+    nbytes = bytes_fn(C.byref(ro.desc))
+    if nbytes == 0:
+        raise RuntimeError(refusal)
+    ro.device = device or torch.device("cuda", torch.cuda.current_device())
+    ro.workspace = torch.empty(nbytes, dtype=torch.uint8, device=ro.device)
+
+
+def _rebind_nets(ro, policy: GopsMlp, value: Optional[GopsMlp]):
+    if policy is not ro._mlps[0]:
+        ro.desc.policy = policy
+    if value is not None and value is not ro._mlps[1]:
+        ro.desc.value = value
+    ro._mlps = (policy, value if value is not None else ro._mlps[1])
+
+
+def _rollout_outputs(ro, want_rewards, want_final):
+    """(GopsRolloutOut, result dict) with v_pi and, on request, rewards [H, B] and final_obs [B, O] / final_done [B]."""
+    d, dev = ro.desc, ro.device
+    out = GopsRolloutOut()
+    res = {"v_pi": torch.empty(d.batch, dtype=torch.float32, device=dev)}
+    out.v_pi = _ptr(res["v_pi"])
+    if want_rewards:
+        res["rewards"] = torch.empty(d.horizon, d.batch, dtype=torch.float32, device=dev)
+        out.rewards = _ptr(res["rewards"])
+    if want_final:
+        res["final_obs"] = torch.empty(d.batch, d.env.obs_dim, dtype=torch.float32, device=dev)
+        res["final_done"] = torch.empty(d.batch, dtype=torch.float32, device=dev)
+        out.final_obs, out.final_done = _ptr(res["final_obs"]), _ptr(res["final_done"])
+    return out, res
+
+
 class Rollout:
     """One configured horizon rollout (forward + backward) bound to caller-owned tensors.
 
@@ -436,42 +432,27 @@ class Rollout:
         policy-head outputs of all steps [B, H, act_dim] and `backward_open_loop` returns their gradient.
         `dtype`: "fp32" (default: fp32 results at the 1e-4 bar, plane-split MFMAs where they apply) or "fp16" (half-precision
         MFMA contractions and stash).  `variant_flags`: VF_* bits (GopsRolloutDesc.variant_flags), None = DEFAULT_VARIANT_FLAGS."""
-        self.desc = GopsRolloutDesc()
-        d = self.desc
+        d = self.desc = _rollout_desc(env, policy, value, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
+                                      need_grad=need_grad, tail_unmasked=tail_unmasked)
         d.dtype = dtype_id(dtype)
         d.variant_flags = DEFAULT_VARIANT_FLAGS if variant_flags is None else variant_flags
         d.l2_warmup, d.dw_workgroups = int(l2_warmup), int(dw_workgroups)
-        d.batch, d.horizon, d.finite_horizon = batch, horizon, int(finite_horizon)
-        d.need_grad, d.tail_value, d.gamma = int(need_grad), int(value is not None), float(gamma)
-        d.tail_unmasked = int(bool(tail_unmasked))   # SPIL's evaluation target: the terminal value is not masked at done
-        d.env = env
         # raw_actions (open loop only): `head_pre` holds the model's actions themselves (GopsRolloutDesc.open_loop = 2)
         d.open_loop = (2 if raw_actions else 1) if policy is None else 0
-        if policy is not None:
-            d.policy = policy
-        if value is not None:
-            d.value = value
         self._mlps = (policy, value)
-        nbytes = lib().gops_rollout_workspace_bytes(C.byref(d))
-        if nbytes == 0:
-            raise RuntimeError("gops_rollout_workspace_bytes: descriptor rejected (unsupported shape for the HIP path)")
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _rollout_workspace(self, lib().gops_rollout_workspace_bytes,
+                           "gops_rollout_workspace_bytes: descriptor rejected (unsupported shape for the HIP path)", device)
         self._in = GopsRolloutIn()
         self._keep = None
 
     def set_policy(self, policy: GopsMlp, value: Optional[GopsMlp] = None):
         """Rebind the networks (their storage moved, or a new GopsMlp was built for them)."""
-        if policy is not self._mlps[0]:
-            self.desc.policy = policy
-        if value is not None and value is not self._mlps[1]:
-            self.desc.value = value
-        self._mlps = (policy, value if value is not None else self._mlps[1])
+        _rebind_nets(self, policy, value)
 
     def forward(self, data: Dict[str, torch.Tensor], *, want_rewards=False, want_final=False,
                 head_pre: Optional[torch.Tensor] = None, want_constraints=False):
         d = self.desc
-        B, H, O = d.batch, d.horizon, d.env.obs_dim
+        B, H = d.batch, d.horizon
         i = self._in
         if d.open_loop:
             assert head_pre is not None and tuple(head_pre.shape) == (B, H, d.env.act_dim)
@@ -494,16 +475,8 @@ class Rollout:
             assert tuple(noise.shape) == (H, B, 2) and noise.dtype == torch.float32 and noise.is_contiguous()
             self._keep["noise"] = noise
             i.noise = _ptr(noise)   # the kernels (and a later backward) read these tensors: keep them alive
-        out = GopsRolloutOut()
-        res = {"v_pi": torch.empty(B, dtype=torch.float32, device=self.device)}
-        out.v_pi = _ptr(res["v_pi"])
-        if want_rewards:
-            res["rewards"] = torch.empty(H, B, dtype=torch.float32, device=self.device)
-            out.rewards = _ptr(res["rewards"])
+        out, res = _rollout_outputs(self, want_rewards, want_final)
         if want_final:
-            res["final_obs"] = torch.empty(B, O, dtype=torch.float32, device=self.device)
-            res["final_done"] = torch.empty(B, dtype=torch.float32, device=self.device)
-            out.final_obs, out.final_done = _ptr(res["final_obs"]), _ptr(res["final_done"])
             if d.env.kind in (ENV_VEH, ENV_VEH_SURR, ENV_VEH2DOF):
                 res["final_state"] = torch.empty(B, 4 if d.env.kind == ENV_VEH2DOF else 6, dtype=torch.float32, device=self.device)
                 out.final_state = _ptr(res["final_state"])
@@ -647,50 +620,28 @@ class PolyRollout:
             raise RuntimeError("PolyRollout: POLY approximators run in fp32 only (mlp_dtype fp16 is an MLP setting)")
         if variant_flags:
             raise RuntimeError(f"PolyRollout: no kernel variants on the POLY path (variant_flags {variant_flags:#x})")
-        d = self.desc = GopsRolloutDesc()
-        d.batch, d.horizon, d.finite_horizon = batch, horizon, int(finite_horizon)
-        d.need_grad, d.tail_value, d.gamma = int(need_grad), int(value is not None), float(gamma)
-        d.tail_unmasked = int(bool(tail_unmasked))
-        d.env = env
-        policy.sizes[0] = env.obs_dim
-        d.policy = policy
-        if value is not None:
-            value.sizes[0] = env.obs_dim
-            d.value = value
+        for net in (policy, value):   # a POLY GopsMlp learns its input width here (make_poly has only the weight's shape)
+            if net is not None:
+                net.sizes[0] = env.obs_dim
+        self.desc = _rollout_desc(env, policy, value, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
+                                  need_grad=need_grad, tail_unmasked=tail_unmasked)
         self._mlps = (policy, value)
-        nbytes = lib().gops_poly_rollout_workspace_bytes(C.byref(d))
-        if nbytes == 0:
-            raise RuntimeError("gops_poly_rollout_workspace_bytes: descriptor rejected (POLY net, env model or wrapper outside "
-                               "the HIP POLY path)")
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _rollout_workspace(self, lib().gops_poly_rollout_workspace_bytes,
+                           "gops_poly_rollout_workspace_bytes: descriptor rejected (POLY net, env model or wrapper outside "
+                           "the HIP POLY path)", device)
         self._in = GopsRolloutIn()
 
     def set_policy(self, policy: GopsMlp, value: Optional[GopsMlp] = None):
-        if policy is not self._mlps[0]:
-            policy.sizes[0] = self.desc.env.obs_dim
-            self.desc.policy = policy
-        if value is not None and value is not self._mlps[1]:
-            value.sizes[0] = self.desc.env.obs_dim
-            self.desc.value = value
-        self._mlps = (policy, value if value is not None else self._mlps[1])
+        for net in (policy, value):
+            if net is not None:
+                net.sizes[0] = self.desc.env.obs_dim
+        _rebind_nets(self, policy, value)
 
     def forward(self, data: Dict[str, torch.Tensor], *, want_rewards=False, want_final=False):
-        d = self.desc
-        B, H, O = d.batch, d.horizon, d.env.obs_dim
-        i = self._in
+        d, i = self.desc, self._in
         i.obs, i.done = _ptr(data["obs"]), _ptr(data.get("done"))
         self._keep = dict(data)
-        out = GopsRolloutOut()
-        res = {"v_pi": torch.empty(B, dtype=torch.float32, device=self.device)}
-        out.v_pi = _ptr(res["v_pi"])
-        if want_rewards:
-            res["rewards"] = torch.empty(H, B, dtype=torch.float32, device=self.device)
-            out.rewards = _ptr(res["rewards"])
-        if want_final:
-            res["final_obs"] = torch.empty(B, O, dtype=torch.float32, device=self.device)
-            res["final_done"] = torch.empty(B, dtype=torch.float32, device=self.device)
-            out.final_obs, out.final_done = _ptr(res["final_obs"]), _ptr(res["final_done"])
+        out, res = _rollout_outputs(self, want_rewards, want_final)
         check(lib().gops_poly_rollout_forward(C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(),
                                               self.workspace.numel(), _stream()), "gops_poly_rollout_forward")
         return res
@@ -736,17 +687,10 @@ class PolyValueNet:
 
 
 def _small_mlp(weights, biases, act: str) -> GopsMlp:
-    m = GopsMlp()
-    m.n_layers = len(weights)
+    """A LipsNet's nets: zero Linear layers (the global K) up to MAX_LAYERS; the module keeps the tensors alive."""
     if len(weights) > MAX_LAYERS:
         raise RuntimeError(f"MLP with {len(weights)} Linear layers is outside the HIP path")
-    if weights:
-        m.sizes[0] = weights[0].shape[1]
-    for j, (w, b) in enumerate(zip(weights, biases)):
-        m.sizes[j + 1] = w.shape[0]
-        m.weight[j], m.bias[j] = _ptr(w), _ptr(b)
-    m.hidden_act = ACT_IDS[act]
-    return m
+    return _fill_mlp(GopsMlp(), weights, biases, act)
 
 
 class LipsPolicy:
@@ -836,23 +780,20 @@ class LipsPolicy:
         return grads
 
 
-class RpiEvaluator:
-    """RPI's policy evaluation of one `local_update` as ONE launch (`gops_rpi_evaluate`, csrc/rollout_rpi.hip): up to `max_steps`
-    gradient steps on the value weights, each with its env step, Hamiltonian, Adam step, held-out Hamiltonian norm and 0.88 test.
-    Owns the device state block (`state`: Adam moments and step count in the header, then the lanes' states column-major, the
-    time-limit counters and the counters the algorithm assigns), which persists from one call to the next."""
+class _RpiState:
+    """What both RPI evaluators own: the constant table, the device state block (`state`: a header, then the lanes' states
+    column-major, the time-limit counters and the counters the algorithm assigns; it persists from one call to the next) and the
+    result tensor."""
 
-    def __init__(self, env_kind: int, batch: int, state_dim: int, consts, device: Optional[torch.device] = None):
+    def __init__(self, env_kind: int, batch: int, state_dim: int, consts, device, state_bytes: int, refusal: str):
         self.kind, self.batch, self.state_dim = int(env_kind), int(batch), int(state_dim)
         self.consts = (C.c_float * RPI_CONST_COUNT)(*[float(v) for v in consts])
         self.device = device or torch.device("cuda", torch.cuda.current_device())
-        nbytes = lib().gops_rpi_state_bytes(self.kind, self.batch)
-        if nbytes == 0:
-            raise RuntimeError(f"gops_rpi_state_bytes: GOPS_ERR_UNSUPPORTED (env kind {env_kind}, batch {batch}; at most {RPI_MAX_BATCH} lanes)")
-        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+        if state_bytes == 0:
+            raise RuntimeError(refusal)
+        self.state = torch.zeros(state_bytes // 4, dtype=torch.float32, device=self.device)
         self.result = torch.zeros(4, dtype=torch.float32, device=self.device)
 
-    # views into the state block
     def lanes(self) -> torch.Tensor:
         """[state_dim, B] view of the lanes' states."""
         return self.state[RPI_STATE_HEADER:RPI_STATE_HEADER + self.state_dim * self.batch].view(self.state_dim, self.batch)
@@ -862,12 +803,25 @@ class RpiEvaluator:
         o = RPI_STATE_HEADER + self.state_dim * self.batch
         return self.state[o:o + 2 * self.batch].view(2, self.batch)
 
+    def _check(self, pool, max_steps, trace):
+        assert tuple(pool.shape) == (max_steps + 1, self.state_dim, self.batch)
+        assert trace is None or trace.numel() >= 2 * max_steps
+
+
+class RpiEvaluator(_RpiState):
+    """RPI's policy evaluation of one `local_update` as ONE launch (`gops_rpi_evaluate`, csrc/rollout_rpi.hip): up to `max_steps`
+    gradient steps on the value weights, each with its env step, Hamiltonian, Adam step, held-out Hamiltonian norm and 0.88 test.
+    The header of the state block holds the Adam moments and step count."""
+
+    def __init__(self, env_kind: int, batch: int, state_dim: int, consts, device: Optional[torch.device] = None):
+        super().__init__(env_kind, batch, state_dim, consts, device, lib().gops_rpi_state_bytes(int(env_kind), int(batch)),
+                         f"gops_rpi_state_bytes: GOPS_ERR_UNSUPPORTED (env kind {env_kind}, batch {batch}; at most {RPI_MAX_BATCH} lanes)")
+
     def evaluate(self, weight: torch.Tensor, target_weight: torch.Tensor, max_step: torch.Tensor, pool: torch.Tensor, max_steps: int,
                  lr: float, beta1: float, beta2: float, eps: float, trace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Enqueues the launch; returns the device result [steps taken, last loss, norm_before, norm_after].  `pool` is
         [max_steps + 1, state_dim, B]: the held-out set, then one reset draw per step."""
-        assert tuple(pool.shape) == (max_steps + 1, self.state_dim, self.batch)
-        assert trace is None or trace.numel() >= 2 * max_steps
+        self._check(pool, max_steps, trace)
         check(lib().gops_rpi_evaluate(self.kind, self.batch, int(max_steps), self.consts, _ptr(weight), _ptr(target_weight),
                                       _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr),
                                       float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),
@@ -875,7 +829,7 @@ class RpiEvaluator:
         return self.result
 
 
-class RpiMlpEvaluator:
+class RpiMlpEvaluator(_RpiState):
     """The same for an MLP value net (`gops_rpi_mlp_evaluate`, csrc/rollout_rpi_mlp.hip): ONE launch per `local_update`; the value
     net's weights and hidden biases are stepped in place through `value`'s pointers.  The state block holds the Adam step count in
     the header, the lanes' states, the two counters per lane, the Adam moments of all parameters in `parameters()` order, and the
@@ -883,27 +837,13 @@ class RpiMlpEvaluator:
 
     def __init__(self, env_kind: int, batch: int, state_dim: int, consts, value: GopsMlp, target: GopsMlp,
                  device: Optional[torch.device] = None):
-        self.kind, self.batch, self.state_dim = int(env_kind), int(batch), int(state_dim)
-        self.consts = (C.c_float * RPI_CONST_COUNT)(*[float(v) for v in consts])
         self.value, self.target = value, target
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        nbytes = lib().gops_rpi_mlp_state_bytes(self.kind, self.batch, C.byref(value))
-        if nbytes == 0:
-            raise RuntimeError(f"gops_rpi_mlp_state_bytes: GOPS_ERR_UNSUPPORTED (env kind {env_kind}, batch {batch}, layer sizes "
-                               f"{list(value.sizes[:value.n_layers + 1])}, activation id {value.hidden_act}): one or two hidden layers, "
-                               f"widths multiples of 16 up to 64, elu / gelu / tanh / sigmoid, at most {RPI_MAX_BATCH} lanes")
+        super().__init__(env_kind, batch, state_dim, consts, device,
+                         lib().gops_rpi_mlp_state_bytes(int(env_kind), int(batch), C.byref(value)),
+                         f"gops_rpi_mlp_state_bytes: GOPS_ERR_UNSUPPORTED (env kind {env_kind}, batch {batch}, layer sizes "
+                         f"{list(value.sizes[:value.n_layers + 1])}, activation id {value.hidden_act}): one or two hidden layers, "
+                         f"widths multiples of 16 up to 64, elu / gelu / tanh / sigmoid, at most {RPI_MAX_BATCH} lanes")
         self.n_params = sum(value.sizes[j + 1] * (value.sizes[j] + 1) for j in range(value.n_layers))
-        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self.result = torch.zeros(4, dtype=torch.float32, device=self.device)
-
-    def lanes(self) -> torch.Tensor:
-        """[state_dim, B] view of the lanes' states."""
-        return self.state[RPI_STATE_HEADER:RPI_STATE_HEADER + self.state_dim * self.batch].view(self.state_dim, self.batch)
-
-    def counters(self) -> torch.Tensor:
-        """[2, B] view: the time-limit counter of each lane, then the counter the algorithm assigns at a reset."""
-        o = RPI_STATE_HEADER + self.state_dim * self.batch
-        return self.state[o:o + 2 * self.batch].view(2, self.batch)
 
     def moments(self) -> torch.Tensor:
         """[2, P] view: Adam's exp_avg and exp_avg_sq of all parameters, flattened in `parameters()` order."""
@@ -914,8 +854,7 @@ class RpiMlpEvaluator:
                  trace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Enqueues the launch; returns the device result [steps taken, last loss, norm_before, norm_after].  `pool` is
         [max_steps + 1, state_dim, B]: the held-out set, then one reset draw per step."""
-        assert tuple(pool.shape) == (max_steps + 1, self.state_dim, self.batch)
-        assert trace is None or trace.numel() >= 2 * max_steps
+        self._check(pool, max_steps, trace)
         check(lib().gops_rpi_mlp_evaluate(self.kind, self.batch, int(max_steps), self.consts, C.byref(self.value), C.byref(self.target),
                                           _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr),
                                           float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),

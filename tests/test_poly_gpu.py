@@ -290,3 +290,69 @@ def test_poly_rollout_refuses_what_it_does_not_run():
     d = hb.PolyRollout(env, pol, batch=8, horizon=4, gamma=1.0, finite_horizon=True).desc
     d.dtype = 1
     assert hb.lib().gops_poly_rollout_workspace_bytes(d) == 0
+
+
+# ---- one POLY rollout step against hb.env_step: both inline the same wrapped model step (csrc/env_models.h) --------------------
+def _step_env(case):
+    lq2 = dict(inv_IA=[[1.0, 0.05], [-0.02, 0.97]], B=[[0.0], [1.0]], Q=[2.0, 1.0], R=[0.5], dt=0.05, reward_scale=0.1,
+               reward_shift=1.0)
+    lq3 = dict(inv_IA=[[1.0, 0.05, 0.0], [-0.02, 0.97, 0.04], [0.01, -0.03, 0.95]], B=[[0.0], [0.5], [1.0]], Q=[2.0, 1.0, 0.5],
+               R=[0.5], dt=0.05, reward_scale=0.1, reward_shift=1.0)
+    if case == "lq_s2a1":
+        return hb.make_env(hb.ENV_LQ, 2, 1, act_low=[-2.0], act_high=[2.0], lq=lq2)
+    if case == "lq_s3a1_obsscale_repeat2_bounds":
+        return hb.make_env(hb.ENV_LQ, 3, 1, act_low=[-2.0], act_high=[2.0], lq=lq3, obs_scale=[0.5, 2.0, 1.5],
+                           obs_shift=[0.25, -0.125, 0.0], repeat_num=2, obs_low=[-0.2, -0.4, -0.3], obs_high=[0.2, 0.4, 0.3],
+                           reward_scale=0.5, reward_shift=0.25)
+    kind, n = {"idpendulum": (hb.ENV_IDP, 6), "cartpole": (hb.ENV_CARTPOLE, 4), "pendulum": (hb.ENV_PENDULUM, 3)}[case]
+    return hb.make_env(kind, n, 1, act_low=[-1.0], act_high=[1.0])
+
+
+def _ulp_distance(a, b):
+    """Largest distance in units in the last place between two float32 tensors."""
+    def ordered(x):
+        i = x.contiguous().view(torch.int32).long()
+        return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return int((ordered(a) - ordered(b)).abs().max())
+
+
+# Largest distance of the two kernels' next observation, in units in the last place, measured on an MI355X at the commit before
+# they shared one statement of the step (separate copies then, contracted into fused multiply-adds differently by the compiler).
+# The rewards and every other case's observation were bit-equal there; with the shared statement every case measures 0.
+ONE_STEP_OBS_ULP_BEFORE_SHARING = {"idpendulum": 130}
+
+
+@pytest.mark.parametrize("B", [1, 65, 257])
+@pytest.mark.parametrize("case", ["lq_s2a1", "lq_s3a1_obsscale_repeat2_bounds", "idpendulum", "cartpole", "pendulum"])
+def test_poly_one_step_equals_env_step(case, B):
+    """A PolyRollout of H = 1 and `hb.env_step` fed the policy's own pre-wrapper action give the same bits: rewards, next
+    observation and done flag (one lane, a partial wave, one lane past the 256-thread block; every fifth row done).
+    Observations are multiples of 1/64 and weights multiples of 1/8, so the float32 feature product formed on the host is exact
+    and equals the kernel's in any summation order: the action is identical on both sides by construction.  The bound
+    is what the two kernels measured while they were separate copies: bit-equal, except pyth_idpendulum's next observation
+    (ONE_STEP_OBS_ULP_BEFORE_SHARING); the figures are printed before they are asserted."""
+    env = _step_env(case)
+    n = env.obs_dim
+    gen = torch.Generator().manual_seed(1000 + B)
+    obs = torch.randint(-32, 33, (B, n), generator=gen).float() / 64
+    W = torch.randint(-8, 9, (1, n), generator=gen).float() / 8
+    bias = torch.randint(-8, 9, (1,), generator=gen).float() / 8
+    done = torch.zeros(B)
+    done[::5] = 1.0
+    action = (obs @ W.T + bias).cuda()          # degree 1: the features are the observation
+    obs, done, W, bias = obs.cuda(), done.cuda(), W.cuda(), bias.cuda()
+    ro = hb.PolyRollout(env, hb.make_poly(W, bias, hb.POLY_FULL[1]), batch=B, horizon=1, gamma=1.0, finite_horizon=False,
+                        need_grad=False)
+    res = ro.forward({"obs": obs, "done": done}, want_rewards=True, want_final=True)
+    nobs, rew, ndone, _ = hb.env_step(env, obs, action, done)
+    torch.cuda.synchronize()
+    ulp_r, ulp_o = _ulp_distance(res["rewards"][0], rew), _ulp_distance(res["final_obs"], nobs)
+    print(f"{case} B={B}: rewards {ulp_r} ulp, final_obs {ulp_o} ulp")
+    assert torch.equal(res["final_done"], ndone)
+    assert torch.equal(res["rewards"][0], rew)
+    if case in ONE_STEP_OBS_ULP_BEFORE_SHARING:
+        assert ulp_o <= ONE_STEP_OBS_ULP_BEFORE_SHARING[case]
+    else:
+        assert torch.equal(res["final_obs"], nobs)
+    assert torch.equal(res["v_pi"], res["rewards"][0])        # gamma^0 = 1, no tail
+    assert ndone[::5].all() and torch.isfinite(nobs).all()

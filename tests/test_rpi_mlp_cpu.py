@@ -110,5 +110,7 @@ def test_abi_symbols():
         assert re.search(r"\b" + name + r"\(", header)
         assert name in hb.EXPORTED_SYMBOLS
         assert re.search(r" T " + name + r"\b", exported)
-    src = open(os.path.join(ROOT, "gops_amd", "hip_backend.py")).read()
-    assert "l.gops_rpi_mlp_state_bytes.argtypes" in src and "l.gops_rpi_mlp_evaluate.argtypes" in src
+    # both are declared to ctypes with every argument of the header's prototype
+    loaded = hb.lib()
+    assert len(loaded.gops_rpi_mlp_state_bytes.argtypes) == 3 and loaded.gops_rpi_mlp_state_bytes.restype is hb.C.c_size_t
+    assert len(loaded.gops_rpi_mlp_evaluate.argtypes) == 17
