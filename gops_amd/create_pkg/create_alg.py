@@ -21,10 +21,11 @@ def _entries(stem, module):
     yield name, getattr(module, name), dict(algorithm=name, approx_container_cls=getattr(module, "ApproxContainer"))
 
 
-# RPI is an algorithm like the others; it sits in a registry of its own for one reason only: the key set of `registry` is pinned by
-# tests/test_host_cpu.py (the host contract as it stood before RPI), and that test file stays as it is.  `create_alg` and
-# `create_approx_contrainer` look in both.  Once the pinned set is revisited, `loop_registry` folds back into `registry`.
-_LOOP_ALGORITHMS = ("rpi",)
+# RPI, DDPG and TD3 are algorithms like the others; they sit in a registry of their own for one reason only: the key set of `registry`
+# is pinned by tests/test_host_cpu.py (the host contract as it stood before RPI), and that test file stays as it is.  `create_alg`
+# and `create_approx_contrainer` look in both.  Once the pinned set is revisited, `loop_registry` folds back into `registry`.
+_LOOP_ALGORITHMS = ("rpi", "ddpg", "td3")
+_ACTOR_CRITIC = ("DDPG", "TD3")   # model-free: MLP DetermPolicy + MLP ActionValue, fp32 (algorithm/_actor_critic.py)
 loop_registry = Registry("algorithm")
 registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem not in _LOOP_ALGORITHMS)
 loop_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _LOOP_ALGORITHMS)
@@ -93,6 +94,11 @@ def create_alg(**kwargs) -> object:
                   None)
         if reason is not None:
             raise NotImplementedError(f"apprfunc type LipsNet ({', '.join(lips)}): {reason}")
+    if kwargs["algorithm"] in _ACTOR_CRITIC:   # refused here with the reason, so that nothing fails later
+        from gops_amd.algorithm._actor_critic import refusal
+        reason = refusal(kwargs["algorithm"], kwargs)
+        if reason is not None:
+            raise NotImplementedError(reason)
     trainer = kwargs.get("trainer")
     if trainer is not None and not trainer.startswith(_TRAINER_KINDS):
         raise RuntimeError(f"trainer {trainer} not recognized")

@@ -1,0 +1,376 @@
+// The no-grad half of a DDPG / TD3 update (gops/algorithm/ddpg.py:149-151, td3.py:166-183).
+//
+// ac_backup_kernel: the Bellman backup in ONE launch, forward only, nothing stashed.  A workgroup of 256 threads owns a tile of R
+// batch rows (R = 16, 32 or 64) and evaluates the target policy and the one or two target critics on it, one net after the other:
+//   LDS:  in0 [R][O + A]   the tile's obs2 and, behind it, the smoothed target action (the critics' concatenated input lives here only);
+//         xa, xb [R][ldx]  hidden activations, ping-pong;
+//         wb               one chunk of a layer's weights, TRANSPOSED ([K][NC], so that the four features a thread owns are one
+//                          16-byte read, the same address for all lanes of a row group: a broadcast), its biases behind it.
+//   thread (r = tid % R, g = tid / R): row r, feature quads g, g + 256 / R, ..; every output is eight fp32 fmaf chains (input k
+//   goes to chain k mod 8, k ascending) added pairwise, bias last - the same bits whatever R and the chunk size are.  (One
+//   chain over 256 inputs measured 2.6x the rounding error of the MFMA path's blocked accumulation; eight independent chains
+//   also hide the fmaf latency.)  The output layers (act_dim and one output), the squash, the noise clamps, the minimum and the
+//   backup are the same chains in DOUBLE, rounded once where a value is stored.
+//   Row strides of in0 / xa / xb are odd: the R rows a wave reads at one k sit in different banks.
+// ac_critic_loss_kernel: gradient seeds, losses, mean(q) and |q - backup| of the critic regression in one launch; sums in double
+// in a fixed order (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "launchers.h"
+
+namespace {
+
+constexpr int AC_THREADS = 256;
+constexpr int AC_CHAINS = 8;         // partial sums per output: input k goes to chain k mod 8
+constexpr int AC_MAX_WIDTH = 256;    // hidden width (multiples of 16)
+constexpr int AC_MAX_HIDDEN = 3;     // hidden layers per net
+constexpr int AC_MAX_IN = 64;        // obs_dim + act_dim
+constexpr size_t AC_LDS_TWO = 64 * 1024;     // two workgroups per CU
+constexpr size_t AC_LDS_LIMIT = 150 * 1024;  // one (the CU has 160 KiB)
+constexpr size_t AC_WORKSPACE = 256;
+
+struct AcNet {
+    int nl, act;
+    int dims[GOPS_MAX_LAYERS + 1];
+    int nc[GOPS_MAX_LAYERS];   // output features per staged chunk of layer j (hidden layers)
+    const float* W[GOPS_MAX_LAYERS];
+    const float* Bv[GOPS_MAX_LAYERS];
+};
+
+struct AcParams {
+    AcNet net[3];   // 0: policy, 1 .. n_q: critics
+    int n_q, smooth, B, O, A;
+    int ld0, ldx, xa_off, xb_off, w_off;   // floats
+    float sq_low[GOPS_MAX_ACT], sq_high[GOPS_MAX_ACT], act_low[GOPS_MAX_ACT], act_high[GOPS_MAX_ACT];
+    double sigma, clip, rscale, gamma;
+    const float *obs2, *rew, *done, *xi;
+    float *backup, *a2, *q_targ;
+};
+
+int ac_check_net(const GopsMlp& m, int in, int out) {
+    if (m.n_layers < 2 || m.n_layers > AC_MAX_HIDDEN + 1) return GOPS_ERR_UNSUPPORTED;   // (n_layers = 1: a POLY net)
+    if (m.dtype != GOPS_DTYPE_F32 || m.variant_flags != 0) return GOPS_ERR_UNSUPPORTED;
+    if (m.sizes[0] != in || m.sizes[m.n_layers] != out) return GOPS_ERR_BAD_ARG;
+    for (int j = 1; j < m.n_layers; ++j)
+        if (m.sizes[j] < 16 || (m.sizes[j] & 15) || m.sizes[j] > AC_MAX_WIDTH) return GOPS_ERR_UNSUPPORTED;
+    if (m.hidden_act < GOPS_ACT_LINEAR || m.hidden_act > GOPS_ACT_TANH) return GOPS_ERR_BAD_ARG;
+    for (int j = 0; j < m.n_layers; ++j)
+        if (m.weight[j] == nullptr || m.bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
+    return GOPS_OK;
+}
+
+int ac_check(const GopsAcBackup* d, int B) {
+    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
+    if (d->n_q < 1 || d->n_q > 2) return GOPS_ERR_BAD_ARG;
+    if (d->policy.n_layers < 1 || d->policy.n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
+    const int O = d->policy.sizes[0], A = d->policy.sizes[d->policy.n_layers];
+    if (O < 1 || A < 1 || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (O + A > AC_MAX_IN) return GOPS_ERR_UNSUPPORTED;
+    int rc = ac_check_net(d->policy, O, A);
+    for (int i = 0; i < d->n_q && rc == GOPS_OK; ++i) rc = ac_check_net(d->q[i], O + A, 1);
+    return rc;
+}
+
+inline int ac_up4(int x) { return (x + 3) & ~3; }
+
+// LDS plan for tiles of R rows within `limit` bytes; every hidden layer must get chunks of at least `min_nc` features (or the
+// whole layer).  Fills the offsets and the chunk sizes; returns the dynamic LDS bytes, 0 when it does not fit.
+size_t ac_plan(const GopsAcBackup& d, int R, size_t limit, int min_nc, AcParams& p) {
+    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
+    const int O = d.policy.sizes[0], A = d.policy.sizes[d.policy.n_layers];
+    int maxh = 0;
+    for (int n = 0; n <= d.n_q; ++n)
+        for (int j = 1; j < nets[n]->n_layers; ++j) maxh = std::max(maxh, (int)nets[n]->sizes[j]);
+    p.ld0 = (O + A) | 1;
+    p.ldx = maxh | 1;
+    p.xa_off = ac_up4(R * p.ld0);
+    p.xb_off = p.xa_off + ac_up4(R * p.ldx);
+    p.w_off = p.xb_off + ac_up4(R * p.ldx);   // 16-byte aligned: the weight quads are read as one f32x4
+    const long long wfloats = (long long)(limit / sizeof(float)) - p.w_off;
+    if (wfloats <= 0) return 0;
+    long long used = 0;
+    for (int n = 0; n <= d.n_q; ++n) {
+        const GopsMlp& m = *nets[n];
+        for (int j = 0; j < m.n_layers - 1; ++j) {
+            const int K = m.sizes[j], N = m.sizes[j + 1];
+            int nc = (int)std::min<long long>(N, (wfloats / (K + 1)) & ~15LL);
+            if (nc < std::min(N, min_nc)) return 0;
+            p.net[n].nc[j] = nc;
+            used = std::max(used, (long long)(K + 1) * nc);
+        }
+        const long long head = (long long)(m.sizes[m.n_layers - 1] + 1) * m.sizes[m.n_layers];
+        if (head > wfloats) return 0;
+        used = std::max(used, head);
+    }
+    return ((size_t)p.w_off + (size_t)used) * sizeof(float);
+}
+
+// Tile rows and LDS bytes for a description: large batches take 64-row tiles (a weight chunk is staged once per 64 rows), small
+// ones 16-row tiles (more workgroups); within a tile size, the plan that leaves room for a second workgroup on the CU comes first.
+size_t ac_choose(const GopsAcBackup& d, int B, AcParams& p, int& R) {
+    for (R = B >= 16384 ? 64 : B >= 2048 ? 32 : 16; R >= 16; R >>= 1) {
+        size_t lds = ac_plan(d, R, AC_LDS_TWO, 64, p);
+        if (lds == 0) lds = ac_plan(d, R, AC_LDS_LIMIT, 16, p);
+        if (lds != 0) return lds;
+    }
+    return 0;
+}
+
+template <int R>
+__global__ __launch_bounds__(AC_THREADS) void ac_backup_kernel(const AcParams p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int G = AC_THREADS / R;   // feature quads in flight per row
+    const int tid = threadIdx.x, r = tid % R, g = tid / R;
+    const int b0 = blockIdx.x * R;
+    const int nvalid = min(R, p.B - b0);
+    const int O = p.O, A = p.A, ld0 = p.ld0, ldx = p.ldx;
+    float* in0 = lds;
+    float* xa = lds + p.xa_off;
+    float* xb = lds + p.xb_off;
+    float* wb = lds + p.w_off;
+
+    for (int idx = tid; idx < R * O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
+        const int m = idx / O, k = idx - m * O;
+        in0[m * ld0 + k] = m < nvalid ? p.obs2[(size_t)(b0 + m) * O + k] : 0.f;
+    }
+    double q_min = 0.0;   // of row r, in the threads with g == 0
+#pragma unroll 1
+    for (int n = 0; n <= p.n_q; ++n) {
+        const AcNet& net = p.net[n];
+        const float* cur = in0;
+        int ldc = ld0;
+        float* nxt = xa;
+#pragma unroll 1
+        for (int j = 0; j < net.nl - 1; ++j) {
+            const int K = net.dims[j], N = net.dims[j + 1], NC = net.nc[j];
+            const float* __restrict__ Wg = net.W[j];
+#pragma unroll 1
+            for (int n0 = 0; n0 < N; n0 += NC) {
+                const int nc = min(NC, N - n0);
+                __syncthreads();   // the previous readers of wb are done; what the previous layer (or the staging above) wrote is visible
+                for (int idx = tid; idx < nc * K; idx += AC_THREADS) {
+                    const int k = idx / nc, nn = idx - k * nc;
+                    wb[k * NC + nn] = Wg[(size_t)(n0 + nn) * K + k];
+                }
+                for (int idx = tid; idx < nc; idx += AC_THREADS) wb[K * NC + idx] = net.Bv[j][n0 + idx];
+                __syncthreads();
+                const float* xr = cur + r * ldc;
+                act_dispatch(net.act, [&]<int ACT>() {
+                    for (int fg = g; fg < (nc >> 2); fg += G) {
+                        const float* wq = wb + 4 * fg;
+                        f32x4 c[AC_CHAINS];
+#pragma unroll
+                        for (int i = 0; i < AC_CHAINS; ++i) c[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        const int K8 = K & ~(AC_CHAINS - 1);
+                        for (int k = 0; k < K8; k += AC_CHAINS) {
+#pragma unroll
+                            for (int i = 0; i < AC_CHAINS; ++i) {
+                                const float x = xr[k + i];
+                                const f32x4 w = *reinterpret_cast<const f32x4*>(wq + (k + i) * NC);
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) c[i][e] = fmaf(x, w[e], c[i][e]);
+                            }
+                        }
+#pragma unroll
+                        for (int i = 0; i < AC_CHAINS - 1; ++i) {
+                            if (K8 + i < K) {
+                                const float x = xr[K8 + i];
+                                const f32x4 w = *reinterpret_cast<const f32x4*>(wq + (K8 + i) * NC);
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) c[i][e] = fmaf(x, w[e], c[i][e]);
+                            }
+                        }
+                        const float* bq = wb + K * NC + 4 * fg;
+                        float* yr = nxt + r * ldx + n0 + 4 * fg;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float sum = ((c[0][e] + c[1][e]) + (c[2][e] + c[3][e])) + ((c[4][e] + c[5][e]) + (c[6][e] + c[7][e]));
+                            yr[e] = act_fwd_t<ACT>(sum + bq[e]);
+                        }
+                    }
+                });
+            }
+            cur = nxt;
+            ldc = ldx;
+            nxt = nxt == xa ? xb : xa;
+        }
+        // ---- output layer: row-major [N][K] in wb, one thread per (row, output) ----
+        const int K = net.dims[net.nl - 1], N = net.dims[net.nl];
+        __syncthreads();
+        for (int idx = tid; idx < N * K; idx += AC_THREADS) wb[idx] = net.W[net.nl - 1][idx];
+        for (int idx = tid; idx < N; idx += AC_THREADS) wb[N * K + idx] = net.Bv[net.nl - 1][idx];
+        __syncthreads();
+        if (g < N) {
+            const float* xr = cur + r * ldc;
+            const float* wr = wb + g * K;
+            // The output layer, the squash and the backup are formed in double and rounded once where they are stored: one thread
+            // per (row, output), K <= 256 products - a negligible share of the work, and what is left of the kernel's error is the
+            // fp32 rounding of the hidden layers alone.
+            double c[AC_CHAINS];
+#pragma unroll
+            for (int i = 0; i < AC_CHAINS; ++i) c[i] = 0.0;
+            const int K8 = K & ~(AC_CHAINS - 1);
+            for (int k = 0; k < K8; k += AC_CHAINS) {
+#pragma unroll
+                for (int i = 0; i < AC_CHAINS; ++i) c[i] = fma((double)xr[k + i], (double)wr[k + i], c[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < AC_CHAINS - 1; ++i)
+                if (K8 + i < K) c[i] = fma((double)xr[K8 + i], (double)wr[K8 + i], c[i]);
+            const double y = (((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]))) + (double)wb[N * K + g];
+            if (n == 0) {   // the policy's own squash, then TD3's smoothing (td3.py:168-177)
+                const double lo_s = g == 0 ? p.sq_low[0] : g == 1 ? p.sq_low[1] : g == 2 ? p.sq_low[2] : p.sq_low[3];
+                const double hi_s = g == 0 ? p.sq_high[0] : g == 1 ? p.sq_high[1] : g == 2 ? p.sq_high[2] : p.sq_high[3];
+                double a = (hi_s - lo_s) / 2 * tanh(y) + (hi_s + lo_s) / 2;
+                if (p.smooth) {
+                    const double lo = g == 0 ? p.act_low[0] : g == 1 ? p.act_low[1] : g == 2 ? p.act_low[2] : p.act_low[3];
+                    const double hi = g == 0 ? p.act_high[0] : g == 1 ? p.act_high[1] : g == 2 ? p.act_high[2] : p.act_high[3];
+                    const double xi = r < nvalid ? (double)p.xi[(size_t)(b0 + r) * A + g] : 0.0;
+                    const double eps = fmin(fmax(xi * p.sigma, -p.clip), p.clip);
+                    a = fmin(fmax(a + eps, lo), hi);
+                }
+                const float af = (float)a;
+                in0[r * ld0 + O + g] = af;   // (published by the barrier at the top of the critic's first chunk)
+                if (p.a2 != nullptr && r < nvalid) p.a2[(size_t)(b0 + r) * A + g] = af;
+            } else {        // g == 0
+                if (p.q_targ != nullptr && r < nvalid) p.q_targ[(size_t)(n - 1) * p.B + b0 + r] = (float)y;
+                q_min = n == 1 ? y : fmin(q_min, y);
+            }
+        }
+    }
+    if (g == 0 && r < nvalid)   // backup = r * reward_scale + gamma * (1 - d) * q   (ddpg.py:151, td3.py:183)
+        p.backup[b0 + r] = (float)((double)p.rew[b0 + r] * p.rscale + p.gamma * (1.0 - (double)p.done[b0 + r]) * q_min);
+}
+
+// ---- critic regression: seeds, losses, mean(q), |q - backup| -------------------------------------------------------------------
+constexpr int ACL_BLOCKS = 64;
+constexpr int ACL_ONE_BLOCK_MAX = 8192;
+
+// (s0, s1, s2) summed over the block in a fixed order: butterfly inside each wave, then the four waves in index order
+__device__ __forceinline__ void block_sum3(double& s0, double& s1, double& s2, double (*red)[4]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o);
+        s1 += __shfl_xor(s1, o);
+        s2 += __shfl_xor(s2, o);
+    }
+    __syncthreads();   // (red may still be read by a previous call)
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s0; red[1][threadIdx.x >> 6] = s1; red[2][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    s0 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    s1 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    s2 = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+}
+
+__device__ __forceinline__ void acl_finish(double s0, double s1, double s2, int B, float* __restrict__ stats) {
+    const float l0 = (float)(s0 / (double)B), l1 = (float)(s1 / (double)B);
+    stats[0] = l0;
+    stats[1] = l1;
+    stats[2] = (float)(s2 / (double)B);
+    stats[3] = l0 + l1;
+}
+
+__global__ __launch_bounds__(256) void ac_critic_loss_kernel(const float* __restrict__ q, const float* __restrict__ backup,
+                                                             const float* __restrict__ weight, int nq, int B, float gsc,
+                                                             float* __restrict__ seed, float* __restrict__ abs_err,
+                                                             float* __restrict__ stats) {
+    __shared__ double red[3][4];
+    __shared__ bool last;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;   // sum w d0^2, sum w d1^2, sum q0
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256) {
+        const float bk = backup[i], q0 = q[i];
+        const float d0 = q0 - bk;
+        const float w = weight != nullptr ? weight[i] : 1.f;
+        seed[i] = weight != nullptr ? gsc * (w * d0) : gsc * d0;
+        s0 += (double)(weight != nullptr ? w * (d0 * d0) : d0 * d0);
+        s2 += (double)q0;
+        if (abs_err != nullptr) abs_err[i] = fabsf(d0);
+        if (nq == 2) {
+            const float d1 = q[(size_t)B + i] - bk;
+            seed[(size_t)B + i] = weight != nullptr ? gsc * (w * d1) : gsc * d1;
+            s1 += (double)(weight != nullptr ? w * (d1 * d1) : d1 * d1);
+        }
+    }
+    block_sum3(s0, s1, s2, red);
+    if (gridDim.x == 1) {
+        if (threadIdx.x == 0) acl_finish(s0, s1, s2, B, stats);
+        return;
+    }
+    double* part = reinterpret_cast<double*>(stats + 4);   // [ACL_BLOCKS][3]
+    unsigned* ticket = reinterpret_cast<unsigned*>(stats + 4 + 6 * ACL_BLOCKS);
+    if (threadIdx.x == 0) {
+        part[3 * blockIdx.x] = s0;
+        part[3 * blockIdx.x + 1] = s1;
+        part[3 * blockIdx.x + 2] = s2;
+        __threadfence();
+        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (last) {
+        __threadfence();
+        const volatile double* vp = part;
+        const bool has = threadIdx.x < gridDim.x;
+        s0 = has ? vp[3 * threadIdx.x] : 0.0;
+        s1 = has ? vp[3 * threadIdx.x + 1] : 0.0;
+        s2 = has ? vp[3 * threadIdx.x + 2] : 0.0;
+        block_sum3(s0, s1, s2, red);
+        if (threadIdx.x == 0) {
+            acl_finish(s0, s1, s2, B, stats);
+            *ticket = 0u;
+        }
+    }
+}
+static_assert(4 + 6 * ACL_BLOCKS + 1 <= GOPS_AC_LOSS_STATS_FLOATS, "stats: four results, the blocks' partial sums, the ticket");
+
+}  // namespace
+
+size_t ac_backup_workspace_bytes(const GopsAcBackup* d, int B) {
+    if (ac_check(d, B) != GOPS_OK) return 0;
+    AcParams p;
+    int R;
+    return ac_choose(*d, B, p, R) == 0 ? 0 : AC_WORKSPACE;
+}
+
+int ac_backup(const GopsAcBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* xi, float* backup,
+              float* a2, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int rc = ac_check(d, B);
+    if (rc != GOPS_OK) return rc;
+    if (!obs2 || !rew || !done || !backup || (d->smooth && !xi)) return GOPS_ERR_BAD_ARG;
+    AcParams p;
+    memset(&p, 0, sizeof(p));
+    int R;
+    const size_t lds = ac_choose(*d, B, p, R);
+    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < AC_WORKSPACE) return GOPS_ERR_WORKSPACE;
+    const GopsMlp* nets[3] = {&d->policy, &d->q[0], &d->q[1]};
+    for (int n = 0; n <= d->n_q; ++n) {
+        AcNet& a = p.net[n];
+        a.nl = nets[n]->n_layers, a.act = nets[n]->hidden_act;
+        for (int j = 0; j <= a.nl; ++j) a.dims[j] = nets[n]->sizes[j];
+        for (int j = 0; j < a.nl; ++j) { a.W[j] = nets[n]->weight[j]; a.Bv[j] = nets[n]->bias[j]; }
+    }
+    p.n_q = d->n_q, p.smooth = d->smooth != 0, p.B = B;
+    p.O = d->policy.sizes[0], p.A = d->policy.sizes[d->policy.n_layers];
+    for (int a = 0; a < p.A; ++a) {
+        p.sq_low[a] = d->squash_low[a], p.sq_high[a] = d->squash_high[a];
+        p.act_low[a] = d->act_low[a], p.act_high[a] = d->act_high[a];
+    }
+    p.sigma = d->target_noise, p.clip = d->noise_clip, p.rscale = d->reward_scale, p.gamma = d->gamma;
+    p.obs2 = obs2, p.rew = rew, p.done = done, p.xi = xi;
+    p.backup = backup, p.a2 = a2, p.q_targ = q_targ;
+    const dim3 grid((unsigned)((B + R - 1) / R));
+    if (R == 64) launch_with_lds(ac_backup_kernel<64>, grid, dim3(AC_THREADS), lds, s, p);
+    else if (R == 32) launch_with_lds(ac_backup_kernel<32>, grid, dim3(AC_THREADS), lds, s, p);
+    else launch_with_lds(ac_backup_kernel<16>, grid, dim3(AC_THREADS), lds, s, p);
+    return (int)hipGetLastError();
+}
+
+int ac_critic_loss(const float* q, const float* backup, const float* weight, int nq, int B, float* seed, float* abs_err, float* stats,
+                   hipStream_t s) {
+    hipLaunchKernelGGL(ac_critic_loss_kernel, dim3(B <= ACL_ONE_BLOCK_MAX ? 1 : ACL_BLOCKS), dim3(256), 0, s, q, backup, weight, nq, B,
+                       (float)(2.0 / B), seed, abs_err, stats);
+    return (int)hipGetLastError();
+}

@@ -1069,6 +1069,20 @@ int gops_mean_loss(const float* x, int32_t n, double scale, float* stats, void* 
     return (int)launch_batch_loss(x, nullptr, n, 0.f, (float)scale, nullptr, stats, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_ac_backup_workspace_bytes(const GopsAcBackup* desc, int32_t batch) { return ac_backup_workspace_bytes(desc, batch); }
+
+int gops_ac_backup(const GopsAcBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done, const float* xi,
+                   float* backup, float* a2, float* q_targ, void* workspace, size_t workspace_bytes, void* stream) {
+    return ac_backup(desc, batch, obs2, rew, done, xi, backup, a2, q_targ, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int gops_ac_critic_loss(const float* q, const float* backup, const float* weight, int32_t n_q, int32_t batch, float* seed,
+                        float* abs_err, float* stats, void* stream) {
+    if (!q || !backup || !seed || !stats || batch < 1 || n_q < 1 || n_q > 2) return GOPS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
+    return ac_critic_loss(q, backup, weight, n_q, batch, seed, abs_err, stats, static_cast<hipStream_t>(stream));
+}
+
 void gops_profile_enable(int32_t on) {
     std::lock_guard<std::mutex> lk(g_prof.mu);
     g_prof.on = on != 0;

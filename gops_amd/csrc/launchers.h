@@ -49,3 +49,10 @@ size_t lips_workspace_bytes(const GopsLipsNet& d, int B);
 int lips_forward(const GopsLipsNet& d, int B, const float* obs, float* action, float* K, float* N, void* ws, size_t bytes, hipStream_t s);
 int lips_backward(const GopsLipsNet& d, int B, const float* obs, const float* grad_action, const GopsLipsGrad& g, void* ws, size_t bytes,
                   hipStream_t s);
+
+// ---- actor_critic.hip: the no-grad half of a DDPG / TD3 update - Bellman backup in one launch, critic losses in one launch ----
+size_t ac_backup_workspace_bytes(const GopsAcBackup* d, int B);
+int ac_backup(const GopsAcBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* xi, float* backup,
+              float* a2, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s);
+int ac_critic_loss(const float* q, const float* backup, const float* weight, int nq, int B, float* seed, float* abs_err, float* stats,
+                   hipStream_t s);

@@ -8,6 +8,7 @@ import ctypes as C
 import os
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -145,6 +146,13 @@ class GopsEpisodeOut(C.Structure):   # gops_episode_rollout
     _fields_ = [(k, C.c_void_p) for k in ("ret", "length", "terminated", "trace_obs", "trace_act", "trace_rew")]
 
 
+class GopsAcBackup(C.Structure):   # gops_ac_backup
+    _fields_ = [("policy", GopsMlp), ("q", GopsMlp * 2), ("n_q", C.c_int32), ("smooth", C.c_int32),
+                ("squash_low", C.c_float * MAX_ACT), ("squash_high", C.c_float * MAX_ACT),
+                ("act_low", C.c_float * MAX_ACT), ("act_high", C.c_float * MAX_ACT),
+                ("target_noise", C.c_double), ("noise_clip", C.c_double), ("reward_scale", C.c_double), ("gamma", C.c_double)]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every symbol of include/gops_hip.h (argtypes None: not declared to ctypes)."""
     P, vp, i32, sz, f64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_size_t, C.c_double, C.c_int
@@ -190,6 +198,9 @@ def _signatures():
         "gops_lips_workspace_bytes": (sz, [lips, i32]),
         "gops_lips_forward": (rc, [lips, i32, vp, vp, vp, vp, vp, sz, vp]),
         "gops_lips_backward": (rc, [lips, i32, vp, vp, P(GopsLipsGrad), vp, sz, vp]),
+        "gops_ac_backup_workspace_bytes": (sz, [P(GopsAcBackup), i32]),
+        "gops_ac_backup": (rc, [P(GopsAcBackup), i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "gops_ac_critic_loss": (rc, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -952,8 +963,10 @@ class MlpNet:
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        y = torch.empty(self.batch, self.out_dim, dtype=torch.float32, device=self.device)
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`out`: a contiguous tensor of batch * out_dim floats that receives the result (e.g. one row of a [n, batch] buffer)."""
+        y = torch.empty(self.batch, self.out_dim, dtype=torch.float32, device=self.device) if out is None else out
+        assert y.numel() == self.batch * self.out_dim
         check(lib().gops_mlp_forward(C.byref(self.mlp), self.batch, _ptr(x), _ptr(y), self.workspace.data_ptr(),
                                      self.workspace.numel(), _stream()), "gops_mlp_forward")
         return y
@@ -1203,6 +1216,75 @@ class LossStats:
         """-> [scale * mean(x), mean(x)] (`-v_pi.mean()`: infadp.py:213, fhadp.py:123)."""
         check(lib().gops_mean_loss(_ptr(x), x.numel(), float(scale), self.buf.data_ptr(), _stream()), "gops_mean_loss")
         return self.buf[:2]
+
+
+AC_LOSS_STATS_FLOATS = 392   # include/gops_hip.h: GOPS_AC_LOSS_STATS_FLOATS
+
+
+class AcBackup:
+    """The Bellman backup of a DDPG / TD3 update in ONE launch (`gops_ac_backup`, csrc/actor_critic.hip): target policy with its tanh
+    squash, TD3's clipped target noise, one or two target critics on the concatenated input (which never exists in global memory),
+    minimum, `rew * reward_scale + gamma * (1 - done) * q`.  `policy` / `critics`: `GopsMlp` views of the TARGET networks (read in
+    place at every call).  `supported` is False for a shape the kernel does not hold: the caller then composes the backup from
+    `MlpNet.forward` calls; `run` on such a description raises."""
+
+    def __init__(self, policy: GopsMlp, critics: Sequence[GopsMlp], *, squash_low, squash_high, act_low, act_high, batch: int,
+                 smooth: bool, device: Optional[torch.device] = None, workspace_bytes: Optional[int] = None):
+        d = self.desc = GopsAcBackup()
+        self.batch, self.act_dim, self.n_q = int(batch), int(policy.sizes[policy.n_layers]), len(critics)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        d.n_q, d.smooth = self.n_q, int(bool(smooth))
+        for name, vals in (("squash_low", squash_low), ("squash_high", squash_high), ("act_low", act_low), ("act_high", act_high)):
+            _fill(getattr(d, name), np.asarray(vals, dtype=np.float32).reshape(-1)[:MAX_ACT])
+        self.set_nets(policy, critics)
+        nbytes = lib().gops_ac_backup_workspace_bytes(C.byref(d), self.batch)
+        self.supported = nbytes != 0
+        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
+        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
+
+    def set_nets(self, policy: GopsMlp, critics: Sequence[GopsMlp]):
+        assert len(critics) == self.n_q
+        C.memmove(C.byref(self.desc.policy), C.byref(policy), C.sizeof(GopsMlp))
+        for i, c in enumerate(critics):
+            C.memmove(C.byref(self.desc.q[i]), C.byref(c), C.sizeof(GopsMlp))
+        self._keep = (policy, list(critics))   # the description holds raw pointers
+
+    def run(self, obs2, rew, done, xi=None, *, target_noise=0.0, noise_clip=0.0, reward_scale=1.0, gamma=0.99, want_a2=False,
+            want_q=False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """-> {"backup" [B], "a2" [B, A] (want_a2), "q_targ" [n_q, B] (want_q)}; `out` supplies the output tensors instead of fresh
+        ones.  Enqueues only."""
+        B, d, dev = self.batch, self.desc, self.device
+        assert obs2.shape[0] == B
+        d.target_noise, d.noise_clip, d.reward_scale, d.gamma = float(target_noise), float(noise_clip), float(reward_scale), float(gamma)
+        res = dict(out or {})
+        if "backup" not in res:
+            res["backup"] = torch.empty(B, dtype=torch.float32, device=dev)
+        if want_a2 and "a2" not in res:
+            res["a2"] = torch.empty(B, self.act_dim, dtype=torch.float32, device=dev)
+        if want_q and "q_targ" not in res:
+            res["q_targ"] = torch.empty(self.n_q, B, dtype=torch.float32, device=dev)
+        check(lib().gops_ac_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(xi), res["backup"].data_ptr(),
+                                   res["a2"].data_ptr() if "a2" in res else None, res["q_targ"].data_ptr() if "q_targ" in res else None,
+                                   self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_ac_backup")
+        return res
+
+
+class AcCriticLoss:
+    """Gradient seeds, losses, mean(q) and |q - backup| of the critic regression in one launch (`gops_ac_critic_loss`).  `buf[:4]` =
+    loss_0, loss_1, mean(q_0), loss_0 + loss_1; the rest is the kernel's scratch (zero before the first call, left zero)."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(AC_LOSS_STATS_FLOATS, dtype=torch.float32, device=device)
+
+    def run(self, q: torch.Tensor, backup: torch.Tensor, weight: Optional[torch.Tensor] = None, seed: Optional[torch.Tensor] = None,
+            abs_err: Optional[torch.Tensor] = None):
+        """q [n_q, B] -> (seed [n_q, B], abs_err [B], stats [4])."""
+        n_q, B = q.shape
+        seed = torch.empty_like(q) if seed is None else seed
+        abs_err = torch.empty(B, dtype=torch.float32, device=q.device) if abs_err is None else abs_err
+        check(lib().gops_ac_critic_loss(_ptr(q), _ptr(backup), _ptr(weight), n_q, B, _ptr(seed), _ptr(abs_err), self.buf.data_ptr(),
+                                        _stream()), "gops_ac_critic_loss")
+        return seed, abs_err, self.buf[:4]
 
 
 def make_update_tail(fused_adam=None, mean_of: Optional[torch.Tensor] = None, mean_scale: float = -1.0,

@@ -631,6 +631,53 @@ int gops_lips_forward(const GopsLipsNet* net, int32_t batch, const float* obs, f
 int gops_lips_backward(const GopsLipsNet* net, int32_t batch, const float* obs, const float* grad_action, const GopsLipsGrad* grad,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): the no-grad half of a DDPG / TD3 update (csrc/actor_critic.hip).
+ *
+ * gops_ac_backup: the whole Bellman backup of gops/algorithm/ddpg.py:149-151 and td3.py:166-183 in ONE launch, forward only:
+ *     a2     = (high - low) / 2 tanh(policy(obs2)) + (high + low) / 2          (DetermPolicy.forward, squash_low / squash_high)
+ *     a2     = clamp(a2 + clamp(xi * target_noise, -noise_clip, noise_clip), act_low, act_high)      (`smooth` = 1: TD3)
+ *     q_targ = q[i]([obs2, a2]),  i < n_q;   n_q = 2 takes the minimum                (the concatenation exists in LDS only)
+ *     backup = rew * reward_scale + gamma * (1 - done) * q_targ
+ * `policy` / `q[i]` are the TARGET networks; xi [B, act_dim] are unit-normal draws supplied by the caller (read iff `smooth`).
+ * A workgroup of 256 threads owns a tile of 16, 32 or 64 batch rows (by batch size and LDS plan); the three networks are
+ * evaluated one after the other on that tile, weights staged through LDS in chunks of output features, every output eight fp32 fmaf
+ * chains (input k in chain k mod 8, k ascending) added pairwise with the bias added last; the output layers, the squash, the clamps,
+ * the minimum and the backup are formed in double (the hyper-parameters are doubles, as Python holds them) and rounded to fp32 once,
+ * where a2 - the critics' input -, q_targ and backup are stored: the results are bitwise reproducible and do not depend on
+ * the tile size.  Nothing is stashed; no global scratch beyond the one section below.
+ * Accepted (gops_ac_backup_workspace_bytes returns 0 otherwise, gops_ac_backup GOPS_ERR_UNSUPPORTED): 1 .. 3 hidden layers per
+ * network (n_layers 2 .. 4), hidden widths multiples of 16 up to 256, every GOPS_ACT_*, GOPS_DTYPE_F32, variant_flags 0,
+ * act_dim <= GOPS_MAX_ACT, obs_dim + act_dim <= 64; policy: obs_dim -> .. -> act_dim, q[i]: obs_dim + act_dim -> .. -> 1.
+ * GOPS_ERR_BAD_ARG: n_q outside 1 .. 2, shapes of the three networks that do not fit together, NULL pointers, batch < 1.
+ * The workspace is one 256-byte section (no contents today: the kernel keeps no state in global memory; the argument is part of
+ * the call so that a later kernel may stage there without an ABI change); workspace_bytes below it: GOPS_ERR_WORKSPACE.
+ * Outputs: backup [B]; a2 [B, act_dim] and q_targ [n_q, B] are optional (NULL). */
+struct GopsAcBackup {
+    GopsMlp policy;
+    GopsMlp q[2];
+    int32_t n_q;                 /* 1: DDPG, 2: TD3 (minimum of the two) */
+    int32_t smooth;              /* 1: target-policy smoothing (TD3) */
+    float squash_low[GOPS_MAX_ACT], squash_high[GOPS_MAX_ACT];   /* the policy's act_low_lim / act_high_lim buffers */
+    float act_low[GOPS_MAX_ACT], act_high[GOPS_MAX_ACT];         /* the algorithm's action limits: clamp after the noise */
+    double target_noise, noise_clip, reward_scale, gamma;
+};
+typedef struct GopsAcBackup GopsAcBackup;
+size_t gops_ac_backup_workspace_bytes(const GopsAcBackup* desc, int32_t batch);
+int gops_ac_backup(const GopsAcBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,
+                   const float* xi, float* backup, float* a2, float* q_targ, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* gops_ac_critic_loss: the critic losses of the same update in one launch.  q [n_q, B] (row i: critic i on the batch), backup [B],
+ * weight [B] or NULL (prioritized replay's importance weights; NULL = ones):
+ *     seed [n_q, B] = (2 / B) weight (q_i - backup)        d(loss_i) / d(q_i), loss_i = mean(weight (q_i - backup)^2)
+ *     abs_err [B]   = |q_0 - backup|                       the new priorities (NULL: not wanted)
+ *     stats[0] = loss_0, stats[1] = loss_1 (0 for n_q = 1), stats[2] = mean(q_0), stats[3] = loss_0 + loss_1 (fp32 sum)
+ * `stats`: 8-byte aligned device memory of GOPS_AC_LOSS_STATS_FLOATS floats, ALL ZERO before the first call (behind the four
+ * results: the blocks' partial sums and a ticket the call leaves zero again), as for gops_value_loss; sums in double, in a fixed
+ * order that depends on B only.  A `stats` pointer that is not 8-byte aligned: GOPS_ERR_BAD_ARG. */
+#define GOPS_AC_LOSS_STATS_FLOATS 392
+int gops_ac_critic_loss(const float* q, const float* backup, const float* weight, int32_t n_q, int32_t batch, float* seed,
+                        float* abs_err, float* stats, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
