@@ -277,16 +277,17 @@ __device__ __forceinline__ bool idp_done_trig(const IdpConst& C, const float* s,
 
 // ================================ the models whose observation is the state, register form ====
 // pyth_lq, gym_cartpoleconti, gym_pendulum, pyth_idpendulum for ONE trajectory held in registers: the single statement of the
-// arithmetic that env_step_kernel, the episode kernel (env_step.h) and the POLY rollout (rollout_poly.hip) step.  The tile-form
-// env phases of rollout_fwd.hip / rollout_bwd.hip are its twin.
+// arithmetic that env_step_kernel, the episode kernel (env_step.h), the POLY rollout (rollout_poly.hip) and the tile-form env
+// phases of rollout_fwd.hip / rollout_bwd.hip / rollout_h64.hip (rollout_env.h) step.
 // State arrays of every model here have GOPS_MAX_LQ_STATE entries (lq_forward's padded width); entries beyond the model's are zero.
 
 // one base-model step xi -> xo: r the model's reward, done_m its done test (left as it is by the models that have none)
-template <int ENV>
+// N, M: lq_forward's compile-time loop bounds
+template <int ENV, int N = GOPS_MAX_LQ_STATE, int M = GOPS_MAX_ACT>
 __device__ __forceinline__ void state_model_substep(const GopsEnv& env, const float* xi, const float (&u)[GOPS_MAX_ACT], float* xo,
                                                     float& r, bool& done_m) {
     if constexpr (ENV == GOPS_ENV_LQ) {
-        lq_forward(env, xi, u, xo, r);
+        lq_forward<N, M>(env, xi, u, xo, r);
     } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
         cart_forward(cart_const(), xi, u[0], xo, r, done_m);
     } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
@@ -312,7 +313,23 @@ __device__ __forceinline__ void state_model_substep(const GopsEnv& env, const fl
     }
 }
 
-// its adjoint at the input state xi: gn adjoint of xo, gr adjoint of r -> gxo adjoint of xi, guo adjoint of u (both overwritten)
+// adjoint of the single-step models (pyth_lq, gym_cartpoleconti, gym_pendulum) at the input state xi: gn adjoint of xo, gr adjoint
+// of r -> gx ACCUMULATED (it carries what the caller put there), gu: the entries the model has are overwritten
+template <int ENV, int N = GOPS_MAX_LQ_STATE, int M = GOPS_MAX_ACT>
+__device__ __forceinline__ void state_model_backward(const GopsEnv& env, const float* xi, const float (&u)[GOPS_MAX_ACT],
+                                                     const float* gn, float gr, float* gx, float* gu) {
+    if constexpr (ENV == GOPS_ENV_LQ) {
+        lq_backward<N, M>(env, xi, u, gn, gr, gx, gu);
+    } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
+        cart_backward(cart_const(), xi, u[0], gn, gx, gu[0]);
+    } else {
+        static_assert(ENV == GOPS_ENV_PENDULUM, "env kind");
+        pend_backward(xi, u[0], gn, gr, gx, gu[0]);
+    }
+}
+
+// adjoint of state_model_substep at the input state xi: gn adjoint of xo, gr adjoint of r -> gxo adjoint of xi, guo adjoint of u
+// (both overwritten)
 template <int ENV>
 __device__ __forceinline__ void state_model_substep_bwd(const GopsEnv& env, const float* xi, const float (&u)[GOPS_MAX_ACT],
                                                         const float* gn, float gr, float* gxo, float* guo) {
@@ -320,12 +337,8 @@ __device__ __forceinline__ void state_model_substep_bwd(const GopsEnv& env, cons
     for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) gxo[i] = 0.f;
 #pragma unroll
     for (int a = 0; a < GOPS_MAX_ACT; ++a) guo[a] = 0.f;
-    if constexpr (ENV == GOPS_ENV_LQ) {
-        lq_backward(env, xi, u, gn, gr, gxo, guo);
-    } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
-        cart_backward(cart_const(), xi, u[0], gn, gxo, guo[0]);
-    } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
-        pend_backward(xi, u[0], gn, gr, gxo, guo[0]);
+    if constexpr (ENV != GOPS_ENV_IDPENDULUM) {
+        state_model_backward<ENV>(env, xi, u, gn, gr, gxo, guo);
     } else {
         // the 5 Euler sub-steps recomputed, every sub-step's input state and intermediates kept in registers
         const IdpConst IC = idp_const();

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "env_models.h"
+#include "rollout_env.h"
 
 // ---------------------------------------------------------------------------------------------
 // Reference trajectories of pyth_veh3dofconti (ref_traj_model.py:26-232).  Every operation is
@@ -179,7 +180,7 @@ __device__ __forceinline__ void env_step_one(const GopsEnv& env, int b, const Go
         for (int i = 0; i < P; ++i) { rout[2 * i] = rin[2 * (i + 1)]; rout[2 * i + 1] = rin[2 * (i + 1) + 1]; }
         rout[2 * P] = newp[1]; rout[2 * P + 1] = newp[2];
         const float o0 = sn[0] - rout[0], o1 = sn[1] - rout[1];
-        done_m = (fabsf(o0) > 2.f) || (fabsf(o1) > 3.14159265358979323846f);
+        done_m = VEH2_DONE(o0, o1);
         if (data && done_m) r -= 100.f;   // data env (pyth_veh2dofconti.py:179-219): the model's step, -100 at done
         if (dn) {
             for (int i = 0; i < O; ++i) nob[i] = ob[i];
@@ -221,18 +222,16 @@ __device__ __forceinline__ void env_step_one(const GopsEnv& env, int b, const Go
         for (int j = 0; j <= P; ++j) {
             const f32x4 rp = (j < P) ? rin[j + 1] : newp;
             rout[j] = rp;
-            const float dx = rp[0] - sn[0], dy = rp[1] - sn[1];
-            const float xtf = dx * cn - dy * snn, ytf = dx * snn + dy * cn;
-            const float ptf = angle_normalize(rp[2] - sn[2]), utf = rp[3] - sn[3];
+            const EgoPoint e = ref_point_to_ego(rp, sn, cn, snn);
             if (j == 0) {
                 if (data)   // pyth_veh3dofconti.py:263-271: world-frame offsets to the first reference point, 5 / 2 / pi
-                    done_m = (fabsf(dx) > 5.f) || (fabsf(dy) > 2.f) || (fabsf(ptf) > 3.14159265358979323846f);
+                    done_m = (fabsf(rp[0] - sn[0]) > 5.f) || (fabsf(rp[1] - sn[1]) > 2.f) || (fabsf(e.phi) > 3.14159265358979323846f);
                 else
-                    done_m = (fabsf(xtf) > 10.f) || (fabsf(ytf) > 10.f) || (fabsf(ptf) > 3.14159265358979323846f);
-                if (!dn) { nob[0] = xtf; nob[1] = ytf; nob[2] = ptf; nob[3] = utf; nob[4] = sn[4]; nob[5] = sn[5]; }
+                    done_m = VEH_DONE(e.x, e.y, e.phi);
+                if (!dn) { nob[0] = e.x; nob[1] = e.y; nob[2] = e.phi; nob[3] = e.u; nob[4] = sn[4]; nob[5] = sn[5]; }
             } else if (!dn) {
                 float* d = nob + 6 + 4 * (j - 1);
-                d[0] = xtf; d[1] = ytf; d[2] = ptf; d[3] = utf;
+                d[0] = e.x; d[1] = e.y; d[2] = e.phi; d[3] = e.u;
             }
         }
         if (data && done_m) r -= 100.f;   // :224-226

@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "env_models.h"
+#include "rollout_env.h"
 constexpr bool SWEEP_STAGE_NT = true;   // the stash rows the sweep stages one step ahead are read once by this launch
 #include "rollout_f16.h"
 #include "rollout_choice.h"
@@ -926,7 +927,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 s_gy[tid * 4 + 0] = g_r;
                 s_gy[tid * 4 + 1] = s_gy[tid * 4 + 2] = s_gy[tid * 4 + 3] = 0.f;
             }
-        } else if (ENV == GOPS_ENV_LQ && !EXT) {
+        } else if constexpr (ENV == GOPS_ENV_LQ && !EXT) {
             // pyth_lq without ActionRepeat / adjoint I/O: the arithmetic of the generic block below, as a routine with compile-time
             // loop bounds - (4, 2) for BASELINE configs[4] (lq s4a2), the maxima otherwise.  The generic form (run-time guards on
             // every state / action index, ~100 scalars of the description live at once) took 9.9 k of the 32 k cycles of a
@@ -958,50 +959,18 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                         for (int i = 0; i < NS; ++i)
                             if (EXACT || i < O) x[i] = obs_unscale(env, i, x[i]);   // the stash holds the (scaled) policy input
                     }
-                    float abar[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f}, u[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f}, sc[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f},
-                          gu[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int a = 0; a < NA; ++a) {
-                        sc[a] = (env.policy_high[a] - env.policy_low[a]) / 2.f;
-                        abar[a] = sc[a] * th[a] + (env.policy_high[a] + env.policy_low[a]) / 2.f;
-                        u[a] = (EXACT || a < A) ? (p.open_loop == 2 ? th[a] : wrap_action(env, a, abar[a])) : 0.f;   // open_loop 2: raw actions
-                    }
+                    const HeadAct hu = head_unsquash<NA, EXACT>(env, th, A, p.open_loop == 2);   // open_loop 2: raw actions
                     const bool dn = dflag != 0.f;
-                    const float g_rm = dn ? 0.f : g_r;
-                    float Gin[GOPS_MAX_LQ_STATE], gx[GOPS_MAX_LQ_STATE];
+                    float Gin[GOPS_MAX_LQ_STATE], gx[GOPS_MAX_LQ_STATE], gu[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { Gin[i] = (i < NS && (EXACT || i < O)) ? G[m * ldx + i] : 0.f; gx[i] = 0.f; }
-                    if (env.clip_obs) {
-                        float xn[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, rdummy;
-                        lq_forward<NS, NA>(env, x, u, xn, rdummy);
-#pragma unroll
-                        for (int i = 0; i < NS; ++i) {
-                            const float pre = obs_rescale(env, i, dn ? x[i] : xn[i]);   // what ClipObservation saw
-                            if ((EXACT || i < O) && !(pre >= env.obs_low[i] && pre <= env.obs_high[i])) Gin[i] = 0.f;
-                        }
-                    }
-                    if (env.scale_obs) {   // d(scaled next obs) / d(next obs) = scale
-#pragma unroll
-                        for (int i = 0; i < NS; ++i)
-                            if (EXACT || i < O) Gin[i] *= env.obs_scale[i];
-                    }
-                    float gxn[GOPS_MAX_LQ_STATE];
-#pragma unroll
-                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { gxn[i] = dn ? 0.f : Gin[i]; gx[i] = dn ? Gin[i] : 0.f; }
-                    lq_backward<NS, NA>(env, x, u, gxn, g_rm, gx, gu);
-#pragma unroll
-                    for (int i = 0; i < NS; ++i)
-                        if (EXACT || i < O) G[m * ldx + i] = env.scale_obs ? gx[i] / env.obs_scale[i] : gx[i];   // d(obs / scale - shift) / d(obs)
-#pragma unroll
-                    for (int a = 0; a < GOPS_MAX_ACT; ++a)
-                        s_gy[m * 4 + a] = (a < NA && (EXACT || a < A))
-                                              ? (p.open_loop == 2 ? gu[a] : wrap_action_bwd(env, a, abar[a], gu[a]) * sc[a] * (1.f - th[a] * th[a]))
-                                              : 0.f;
+                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) Gin[i] = (i < NS && (EXACT || i < O)) ? G[m * ldx + i] : 0.f;
+                    obs_state_adjoint<ENV, NS, NA>(env, O, x, hu.u, dn, dn ? 0.f : g_r, Gin, gx, gu);
+                    obs_state_adjoint_store<NS, NA>(env, O, A, gx, gu, hu, th, p.open_loop == 2, G + m * ldx, s_gy + m * 4);
                 };
                 if (O == 4 && A == 2) lq_adjoint.template operator()<4, 2>();
                 else lq_adjoint.template operator()<GOPS_MAX_LQ_STATE, GOPS_MAX_ACT>();
             }
-        } else if (ENV == GOPS_ENV_LQ || ENV == GOPS_ENV_IDPENDULUM || ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {
+        } else if constexpr (ENV == GOPS_ENV_LQ || ENV == GOPS_ENV_IDPENDULUM || ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {
             if (tid < TB) {
                 const int m = tid;
                 float th[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f}, dflag = 1.f;
@@ -1033,13 +1002,15 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                     for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i)
                         if (i < O) x[i] = obs_unscale(p.env, i, x[i]);   // the stash holds the (scaled) policy input
                 }
-                float abar[GOPS_MAX_ACT], u[GOPS_MAX_ACT], sc[GOPS_MAX_ACT], gu[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
+                HeadAct hu;
 #pragma unroll
                 for (int a = 0; a < GOPS_MAX_ACT; ++a) {
-                    sc[a] = (p.env.policy_high[a] - p.env.policy_low[a]) / 2.f;
-                    abar[a] = sc[a] * th[a] + (p.env.policy_high[a] + p.env.policy_low[a]) / 2.f;
-                    u[a] = (a < A) ? (p.open_loop == 2 ? th[a] : wrap_action(p.env, a, abar[a])) : 0.f;   // open_loop 2: raw actions
+                    hu.sc[a] = (p.env.policy_high[a] - p.env.policy_low[a]) / 2.f;
+                    hu.abar[a] = hu.sc[a] * th[a] + (p.env.policy_high[a] + p.env.policy_low[a]) / 2.f;
+                    hu.u[a] = (a < A) ? (p.open_loop == 2 ? th[a] : wrap_action(p.env, a, hu.abar[a])) : 0.f;   // open_loop 2: raw actions
                 }
+                const float (&u)[GOPS_MAX_ACT] = hu.u;
+                float gu[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
                 const bool dn = dflag != 0.f;
                 const float g_rm = dn ? 0.f : g_r;
                 float Gin[GOPS_MAX_LQ_STATE], gx[GOPS_MAX_LQ_STATE];
@@ -1053,92 +1024,8 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                         // (every sub-step's reward carries g_r, or only the last one's)
                         repeated = true;
                         const int nrep = min(p.env.repeat_num, GOPS_MAX_REPEAT);
-                        // (register-form twins: state_model_substep / state_model_substep_bwd, env_models.h)
-                        auto fwd1 = [&](const float* xi, float* xo) {
-                            float rd = 0.f;
-                            if constexpr (ENV == GOPS_ENV_LQ) {
-                                lq_forward(p.env, xi, u, xo, rd);
-                            } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
-                                bool dd;
-                                cart_forward(cart_const(), xi, u[0], xo, rd, dd);
-                            } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
-                                PendStep w;
-                                pend_forward(xi, u[0], xo, rd, w);
-                            } else {
-                                float s5[6];
-#pragma unroll
-                                for (int i = 0; i < 6; ++i) s5[i] = xi[i];
-                                IdpSub w;
-                                idp_substep<true>(IC, s5, 500.f * u[0], 0.002f, xo, w);
-#pragma unroll 1
-                                for (int k = 1; k < 5; ++k) {
-                                    idp_advance_trig(s5, 0.002f, w, w);
-#pragma unroll
-                                    for (int i = 0; i < 6; ++i) s5[i] = xo[i];
-                                    idp_substep<false>(IC, s5, 500.f * u[0], 0.002f, xo, w);
-                                }
-                            }
-                        };
-                        auto bwd1 = [&](const float* xi, const float* gn, float gr, float* gxo, float* guo) {
-#pragma unroll
-                            for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) gxo[i] = 0.f;
-                            if constexpr (ENV == GOPS_ENV_LQ) {
-                                lq_backward(p.env, xi, u, gn, gr, gxo, guo);
-                            } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
-                                cart_backward(cart_const(), xi, u[0], gn, gxo, guo[0]);
-                            } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
-                                pend_backward(xi, u[0], gn, gr, gxo, guo[0]);
-                            } else {
-                                float* park = s_idp + m * (5 * 24);
-                                float sc_[6], sn_[6];
-#pragma unroll
-                                for (int i = 0; i < 6; ++i) sc_[i] = xi[i];
-                                const float a = u[0], force = 500.f * a;
-                                IdpSub w;
-#pragma unroll 1
-                                for (int k = 0; k < 5; ++k) {
-                                    if (k == 0) idp_substep<true>(IC, sc_, force, 0.002f, sn_, w);
-                                    else idp_substep<false>(IC, sc_, force, 0.002f, sn_, w);
-                                    float* pk = park + k * 24;
-#pragma unroll
-                                    for (int i = 0; i < 6; ++i) pk[i] = sc_[i];
-                                    pk[6] = w.s1; pk[7] = w.c1; pk[8] = w.s2; pk[9] = w.c2; pk[10] = w.s12; pk[11] = w.c12;
-#pragma unroll
-                                    for (int i = 0; i < 6; ++i) pk[12 + i] = w.inv[i];
-#pragma unroll
-                                    for (int i = 0; i < 3; ++i) pk[18 + i] = w.qdd[i];
-                                    idp_advance_trig(sc_, 0.002f, w, w);
-#pragma unroll
-                                    for (int i = 0; i < 6; ++i) sc_[i] = sn_[i];
-                                }
-                                float g[6];
-#pragma unroll
-                                for (int i = 0; i < 6; ++i) g[i] = gn[i];
-                                g[1] += gr * (-10.f * sc_[1]);
-                                g[2] += gr * (-20.f * sc_[2]);
-                                g[3] += gr * (-1.f * sc_[3]);
-                                g[4] += gr * (-1.f * sc_[4]);
-                                g[5] += gr * (-2.f * sc_[5]);
-                                float gforce = 0.f;
-#pragma unroll 1
-                                for (int k = 4; k >= 0; --k) {
-                                    const float* pk = park + k * 24;
-                                    IdpSub wk;
-                                    float sk[6];
-#pragma unroll
-                                    for (int i = 0; i < 6; ++i) sk[i] = pk[i];
-                                    wk.s1 = pk[6]; wk.c1 = pk[7]; wk.s2 = pk[8]; wk.c2 = pk[9]; wk.s12 = pk[10]; wk.c12 = pk[11];
-#pragma unroll
-                                    for (int i = 0; i < 6; ++i) wk.inv[i] = pk[12 + i];
-#pragma unroll
-                                    for (int i = 0; i < 3; ++i) wk.qdd[i] = pk[18 + i];
-                                    idp_substep_bwd(IC, sk, 0.002f, wk, g, gforce);
-                                }
-                                guo[0] = 500.f * gforce + gr * (-2.f * a);
-#pragma unroll
-                                for (int i = 0; i < 6; ++i) gxo[i] = g[i];
-                            }
-                        };
+                        float rd;   // (sub-step rewards and done tests: not needed here)
+                        bool dd;
                         float xk[GOPS_MAX_REPEAT][GOPS_MAX_LQ_STATE], xfin[GOPS_MAX_LQ_STATE];
 #pragma unroll
                         for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { xk[0][i] = x[i]; xfin[i] = x[i]; }
@@ -1146,13 +1033,13 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                         for (int rep = 1; rep < GOPS_MAX_REPEAT; ++rep) {
 #pragma unroll
                             for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) xk[rep][i] = 0.f;
-                            if (rep < nrep && !dn) fwd1(xk[rep - 1], xk[rep]);
+                            if (rep < nrep && !dn) state_model_substep<ENV>(p.env, xk[rep - 1], u, xk[rep], rd, dd);
                         }
                         if (p.env.clip_obs && ENV != GOPS_ENV_IDPENDULUM) {   // ClipObservation saw the last sub-step's (rescaled) result
                             if (!dn) {
 #pragma unroll
                                 for (int rep = 0; rep < GOPS_MAX_REPEAT; ++rep)
-                                    if (rep == nrep - 1) fwd1(xk[rep], xfin);
+                                    if (rep == nrep - 1) state_model_substep<ENV>(p.env, xk[rep], u, xfin, rd, dd);
                             }
 #pragma unroll
                             for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) {
@@ -1173,7 +1060,9 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                             if (rep < nrep && !dn) {
                                 const float gr = (!p.env.repeat_last_reward || rep == nrep - 1) ? g_rm : 0.f;
                                 float gxo[GOPS_MAX_LQ_STATE], guo[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
-                                bwd1(xk[rep], g, gr, gxo, guo);
+                                // (pyth_idpendulum: the register form would spill here - its sub-steps are parked in LDS)
+                                if constexpr (ENV == GOPS_ENV_IDPENDULUM) idp_step_bwd_parked(IC, xk[rep], u[0], g, gr, s_idp + m * (5 * IDP_REC), gxo, guo[0]);
+                                else state_model_substep_bwd<ENV>(p.env, xk[rep], u, g, gr, gxo, guo);
 #pragma unroll
                                 for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) g[i] = gxo[i];
 #pragma unroll
@@ -1184,50 +1073,11 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                         for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) gx[i] = dn ? Gin[i] : g[i];
                     }
                 }
-                if (repeated) {
-                } else if (ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {
-                    constexpr int NS = (ENV == GOPS_ENV_CARTPOLE) ? 4 : 3;
-                    if (p.env.clip_obs) {   // ClipObservation on the (rescaled) next observation
-                        float xn[4] = {0.f, 0.f, 0.f, 0.f}, rdummy;
-                        bool ddummy;
-                        PendStep wdummy;
-                        if (ENV == GOPS_ENV_CARTPOLE) cart_forward(cart_const(), x, u[0], xn, rdummy, ddummy);
-                        else pend_forward(x, u[0], xn, rdummy, wdummy);
-#pragma unroll
-                        for (int i = 0; i < NS; ++i) {
-                            const float pre = obs_rescale(p.env, i, dn ? x[i] : xn[i]);
-                            if (!(pre >= p.env.obs_low[i] && pre <= p.env.obs_high[i])) Gin[i] = 0.f;
-                        }
-                    }
-                    if (p.env.scale_obs) {
-#pragma unroll
-                        for (int i = 0; i < NS; ++i) Gin[i] *= p.env.obs_scale[i];
-                    }
-                    float gxn[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < NS; ++i) { gxn[i] = dn ? 0.f : Gin[i]; gx[i] = dn ? Gin[i] : 0.f; }
-                    if (ENV == GOPS_ENV_CARTPOLE) cart_backward(cart_const(), x, u[0], gxn, gx, gu[0]);
-                    else pend_backward(x, u[0], gxn, g_rm, gx, gu[0]);
-                } else if (ENV == GOPS_ENV_LQ) {
-                    if (p.env.clip_obs) {
-                        float xn[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, rdummy;
-                        lq_forward(p.env, x, u, xn, rdummy);
-#pragma unroll
-                        for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) {
-                            const float pre = obs_rescale(p.env, i, dn ? x[i] : xn[i]);   // what ClipObservation saw
-                            if (i < O && !(pre >= p.env.obs_low[i] && pre <= p.env.obs_high[i])) Gin[i] = 0.f;
-                        }
-                    }
-                    if (p.env.scale_obs) {   // d(scaled next obs) / d(next obs) = scale
-#pragma unroll
-                        for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i)
-                            if (i < O) Gin[i] *= p.env.obs_scale[i];
-                    }
-                    float gxn[GOPS_MAX_LQ_STATE];
-#pragma unroll
-                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { gxn[i] = dn ? 0.f : Gin[i]; gx[i] = dn ? Gin[i] : 0.f; }
-                    lq_backward(p.env, x, u, gxn, g_rm, gx, gu);
-                } else {
+                if constexpr (ENV != GOPS_ENV_IDPENDULUM) {
+                    if (!repeated)
+                        obs_state_adjoint<ENV, (ENV == GOPS_ENV_LQ) ? GOPS_MAX_LQ_STATE : ((ENV == GOPS_ENV_CARTPOLE) ? 4 : 3), (ENV == GOPS_ENV_LQ) ? GOPS_MAX_ACT : 1>(
+                            p.env, O, x, u, dn, g_rm, Gin, gx, gu);
+                } else if (!repeated) {
                     // Recompute the 5 Euler sub-steps once, parking each sub-step's input state and
                     // intermediates (M^-1, qdd, sin/cos) in LDS; then walk them backwards from there.
                     if (p.env.scale_obs) {   // d(scaled next obs) / d(next obs) = scale
@@ -1247,7 +1097,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
 #pragma unroll
                         for (int i = 0; i < 6; ++i) sc_[i] = park[120 + i];
                     } else {
-                        float* parkw = s_idp + m * (5 * 24);
+                        float* parkw = s_idp + m * (5 * IDP_REC);
                         park = parkw;
                         float sn_[6];
 #pragma unroll
@@ -1257,14 +1107,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                         for (int k = 0; k < 5; ++k) {
                             if (k == 0) idp_substep<true>(IC, sc_, force, 0.002f, sn_, w);
                             else idp_substep<false>(IC, sc_, force, 0.002f, sn_, w);   // w.s1 .. w.c2 advanced at the end of the last trip
-                            float* pk = parkw + k * 24;
-#pragma unroll
-                            for (int i = 0; i < 6; ++i) pk[i] = sc_[i];
-                            pk[6] = w.s1; pk[7] = w.c1; pk[8] = w.s2; pk[9] = w.c2; pk[10] = w.s12; pk[11] = w.c12;
-#pragma unroll
-                            for (int i = 0; i < 6; ++i) pk[12 + i] = w.inv[i];
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) pk[18 + i] = w.qdd[i];
+                            idp_park_store(parkw + k * IDP_REC, sc_, w);
                             idp_advance_trig(sc_, 0.002f, w, w);
 #pragma unroll
                             for (int i = 0; i < 6; ++i) sc_[i] = sn_[i];
@@ -1273,15 +1116,12 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                     float g[6];
 #pragma unroll
                     for (int i = 0; i < 6; ++i) g[i] = dn ? 0.f : Gin[i];
-                    g[1] += g_rm * (-10.f * sc_[1]);
-                    g[2] += g_rm * (-20.f * sc_[2]);
-                    g[3] += g_rm * (-1.f * sc_[3]);
-                    g[4] += g_rm * (-1.f * sc_[4]);
-                    g[5] += g_rm * (-2.f * sc_[5]);
+                    idp_reward_bwd(sc_, g_rm, g);
                     float gforce = 0.f;
 #pragma unroll
-                    for (int k = 4; k >= 0; --k) {
-                        const float* pk = park + k * 24;
+                    for (int k = 4; k >= 0; --k) {   // (the record unpacked in place, the loops written out: through idp_park_load / idp_park_step hipcc
+                                                     //  schedules the step differently and the gradients move by some ulp)
+                        const float* pk = park + k * IDP_REC;
                         IdpSub w;
                         float sk[6];
 #pragma unroll
@@ -1297,12 +1137,13 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
 #pragma unroll
                     for (int i = 0; i < 6; ++i) gx[i] = g[i] + (dn ? Gin[i] : 0.f);
                 }
+                // (= obs_state_adjoint_store, and head_unsquash above, written out: as calls hipcc schedules the idpendulum step differently)
 #pragma unroll
                 for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i)
                     if (i < O) G[m * ldx + i] = p.env.scale_obs ? gx[i] / p.env.obs_scale[i] : gx[i];   // d(obs / scale - shift) / d(obs)
 #pragma unroll
                 for (int a = 0; a < GOPS_MAX_ACT; ++a)
-                    s_gy[m * 4 + a] = (a < A) ? (p.open_loop == 2 ? gu[a] : wrap_action_bwd(p.env, a, abar[a], gu[a]) * sc[a] * (1.f - th[a] * th[a])) : 0.f;
+                    s_gy[m * 4 + a] = (a < A) ? (p.open_loop == 2 ? gu[a] : wrap_action_bwd(p.env, a, hu.abar[a], gu[a]) * hu.sc[a] * (1.f - th[a] * th[a])) : 0.f;
             }
         } else if (ENV == GOPS_ENV_MOBILEROBOT) {
             if (tid < TB) {
@@ -1323,13 +1164,8 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                         nv = nz[0]; nw = nz[1];
                     }
                 }
-                float abar[2], u[2], sc[2];
-#pragma unroll
-                for (int a = 0; a < 2; ++a) {
-                    sc[a] = (p.env.policy_high[a] - p.env.policy_low[a]) / 2.f;
-                    abar[a] = sc[a] * th[a] + (p.env.policy_high[a] + p.env.policy_low[a]) / 2.f;
-                    u[a] = p.open_loop == 2 ? th[a] : wrap_action(p.env, a, abar[a]);
-                }
+                const HeadAct hu = head_unsquash<2, true>(p.env, th, A, p.open_loop == 2);
+                const float (&u)[GOPS_MAX_ACT] = hu.u;
                 const bool dn = dflag != 0.f;
                 const float g_rm = dn ? 0.f : g_r;
                 float xn[MOB_OBS], rdummy, c;
@@ -1349,13 +1185,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 }
                 float gck = 0.f;               // ... but info["constraint"] still comes from the model's step
                 if (m < nvalid) {
-                    gck = gc_ext * 2.f * fmaxf(c, 0.f) + (c > 0.f ? gc_lin : 0.f);
-                    if (c < 0.f) gck += gc_int * (-1.f / (-c + 1e-8f));
-                    gck *= p.gpow[t];
-                    float dlog;
-                    (void)spil_phi(c, dlog);
-                    gck += gc_mul[0] * dlog;
-                    gck += gc_step(t, m, 0);
+                    gck = constraint_grad(c, gc_ext, gc_lin, gc_int, p.gpow[t], gc_mul[0], gc_step(t, m, 0));
                 }
                 float gu[2];
                 mob_backward(MC, x, u[0], u[1], nv, nw, gxn, g_rm, gck, gx, gu);
@@ -1363,7 +1193,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 for (int i = 0; i < MOB_OBS; ++i) G[m * ldx + i] = gx[i];
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
-                    s_gy[m * 4 + a] = p.open_loop == 2 ? gu[a] : wrap_action_bwd(p.env, a, abar[a], gu[a]) * sc[a] * (1.f - th[a] * th[a]);
+                    s_gy[m * 4 + a] = head_unsquash_bwd(p.env, a, hu.sc[a], hu.abar[a], th[a], gu[a], p.open_loop == 2);
                 s_gy[m * 4 + 2] = s_gy[m * 4 + 3] = 0.f;
             }
         } else if (ENV == GOPS_ENV_VEH2DOF) {
@@ -1404,20 +1234,13 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                     gp[3] += g_rm * (-0.02f * o[3]);
                     if (p.env.cstr_err) {   // errcstr: c = |obs[0]| - tol of THIS observation (unmasked sums / products)
                         const float c = fabsf(o[0]) - p.env.err_tol[0];
-                        float gck = gc_ext * 2.f * fmaxf(c, 0.f) + (c > 0.f ? gc_lin : 0.f);
-                        if (c < 0.f) gck += gc_int * (-1.f / (-c + 1e-8f));
-                        gck *= p.gpow[t];
-                        float dlog;
-                        (void)spil_phi(c, dlog);
-                        gck += gc_mul[0] * dlog;
-                        gck += gc_step(t, m, 0);
+                        const float gck = constraint_grad(c, gc_ext, gc_lin, gc_int, p.gpow[t], gc_mul[0], gc_step(t, m, 0));
                         gp[0] += gck * (o[0] > 0.f ? 1.f : (o[0] < 0.f ? -1.f : 0.f));
                     }
                 }
                 g_steer += g_rm * (-0.02f * steer);
-                const float sc0 = (p.env.policy_high[0] - p.env.policy_low[0]) / 2.f;
-                const float abar0 = sc0 * th0 + (p.env.policy_high[0] + p.env.policy_low[0]) / 2.f;
-                s_gy[m * 4 + 0] = p.open_loop == 2 ? g_steer : wrap_action_bwd(p.env, 0, abar0, g_steer) * sc0 * (1.f - th0 * th0);
+                const HeadAct hu = head_unsquash<1, true>(p.env, &th0, A, p.open_loop == 2);   // (the model action itself: `steer`, from the stash)
+                s_gy[m * 4 + 0] = head_unsquash_bwd(p.env, 0, hu.sc[0], hu.abar[0], th0, g_steer, p.open_loop == 2);
                 s_gy[m * 4 + 1] = s_gy[m * 4 + 2] = s_gy[m * 4 + 3] = 0.f;
             }
         } else {   // GOPS_ENV_VEH3DOFCONTI
@@ -1439,9 +1262,8 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 s[0] = e1[1]; s[1] = e1[2]; s[2] = e1[3]; s[3] = e2[0]; s[4] = e2[1]; s[5] = e2[2];
             }
             const bool dn = dflag != 0.f;
-            const float sc0 = ha0.sc, sc1 = ha1.sc;
-            const float abar0 = sc0 * th0 + ha0.of;
-            const float abar1 = sc1 * th1 + ha1.of;
+            const float abar0 = ha0.sc * th0 + ha0.of;
+            const float abar1 = ha1.sc * th1 + ha1.of;
             const float steer = st_steer, ax = st_ax;   // = wrap_action(abar0 / abar1), stashed by the forward kernel
             float sn[6];
             VehStep w;
@@ -1518,7 +1340,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                                 gck *= p.gpow[t];
                                 float dlog;
                                 (void)spil_phi(c, dlog);
-                                gck += gc_mul[k] * dlog;   // d P_k / d c_tk = P_k Phi'(c_tk) / Phi(c_tk); gc_mul carries dL/dP_k * P_k
+                                gck += gc_mul[k] * dlog;   // (= constraint_grad, rollout_env.h, written out: as a call the plain sweeps' gradients move by some ulp)
                                 gck += gc_step(t, m, k);
                                 lamn[0] += gck * sc.dx[k];
                                 lamn[1] += gck * sc.dy[k];
@@ -1612,8 +1434,8 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 g_steer += g_rm * ((SURR ? -2.f * p.env.reward_w[5] : -0.02f) * steer);
                 g_ax += g_rm * ((SURR ? -2.f * p.env.reward_w[6] : -0.02f) * ax);
                 // (open_loop == 2, the raw-action rollouts of OptController, never reaches a SPLIT kernel)
-                s_gy[m * 4 + 0] = (!SPLIT && p.open_loop == 2) ? g_steer : wrap_action_bwd(ha0, abar0, g_steer) * sc0 * (1.f - th0 * th0);
-                s_gy[m * 4 + 1] = (!SPLIT && p.open_loop == 2) ? g_ax : wrap_action_bwd(ha1, abar1, g_ax) * sc1 * (1.f - th1 * th1);
+                s_gy[m * 4 + 0] = head_unsquash_bwd(ha0, abar0, th0, g_steer, !SPLIT && p.open_loop == 2);
+                s_gy[m * 4 + 1] = head_unsquash_bwd(ha1, abar1, th1, g_ax, !SPLIT && p.open_loop == 2);
                 s_gy[m * 4 + 2] = 0.f;
                 s_gy[m * 4 + 3] = 0.f;
             }

@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "env_models.h"
+#include "rollout_env.h"
 #include "rollout_f16.h"
 #include "rollout_choice.h"
 
@@ -641,8 +642,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
     }
     float v_acc = 0.f;
     unsigned ss_ovf = 0;   // SS: half-range overflow of a plane conversion in this tile (SPLIT keeps it in SP.ovf)
-    float c_ext = 0.f, c_lin = 0.f, c_int = 0.f, c_feas = 1.f;   // SURR: discounted constraint sums of trajectory tid (tid < TB)
-    float c_mul[GOPS_MAX_CONSTRAINT] = {1.f, 1.f, 1.f}, c_safe[GOPS_MAX_CONSTRAINT] = {1.f, 1.f, 1.f};   // SPIL products
+    ConstraintSums csum;   // CSTR: discounted constraint sums and SPIL products of trajectory tid (tid < TB)
     float veh_s = 0.f, veh_c = 1.f;   // sin/cos of the current heading, carried across steps
     __syncthreads();
     if (VEH) sincosf(s_state[(tid & 15) * 8 + 2], &veh_s, &veh_c);
@@ -758,75 +758,14 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
         bool done_m = false;    // done flag from the base model
         if (ENV == GOPS_ENV_NONE) {
             if (tid < TB) r = s_th[tid * 4];
-        } else if (ENV == GOPS_ENV_LQ) {
-            if (tid < TB) {
-                const int m = tid;
-                // NS / NA: compile-time loop bounds - (4, 2) for BASELINE configs[4] (lq s4a2), the maxima otherwise
-                auto lq_step = [&]<int NS, int NA>() {
-                    constexpr bool EXACT = NS < GOPS_MAX_LQ_STATE;   // the dimensions ARE (NS, NA): no run-time guards
-                    float x[GOPS_MAX_LQ_STATE], xn[GOPS_MAX_LQ_STATE], u[GOPS_MAX_ACT];
-#pragma unroll
-                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { x[i] = (i < NS && (EXACT || i < O)) ? obs_unscale(env, i, xs[m * ldx + i]) : 0.f; xn[i] = 0.f; }
-#pragma unroll
-                    for (int j = 0; j < GOPS_MAX_ACT; ++j) u[j] = (j < NA && (EXACT || j < A)) ? s_act[m * 4 + j] : 0.f;
-                    // MaskAtDone freezes the (unscaled) observation; ScaleObservation rescales, ClipObservation clips the result
-                    const bool frozen = s_done[m] != 0.f;
-                    const int nrep = GEN ? env.repeat_num : 1;   // ActionRepeat: sub-steps with the initial done flag
-                    float rs = 0.f;
-                    for (int rep = 0; rep < nrep; ++rep) {
-                        if (rep > 0 && !frozen) {
-#pragma unroll
-                            for (int i = 0; i < NS; ++i) x[i] = xn[i];
-                        }
-                        lq_forward<NS, NA>(env, x, u, xn, r);
-                        rs = (GEN && !env.repeat_last_reward) ? rs + r : r;
-                    }
-                    r = rs;
-                    if (!frozen || env.clip_obs || env.scale_obs) {
-#pragma unroll
-                        for (int i = 0; i < NS; ++i)
-                            if (EXACT || i < O) {
-                                const float v = obs_rescale(env, i, sel_reg(frozen, x[i], xn[i]));
-                                xs[m * ldx + i] = env.clip_obs ? clampf(v, env.obs_low[i], env.obs_high[i]) : v;
-                            }
-                    }
-                };
-                if (O == 4 && A == 2) lq_step.template operator()<4, 2>();
-                else lq_step.template operator()<GOPS_MAX_LQ_STATE, GOPS_MAX_ACT>();
+        } else if constexpr (ENV == GOPS_ENV_LQ) {
+            if (tid < TB) {   // NS / NA: compile-time loop bounds - (4, 2) for BASELINE configs[4] (lq s4a2), the maxima otherwise
+                if (O == 4 && A == 2) obs_state_step<ENV, 4, 2, GEN>(env, O, A, xs + tid * ldx, s_act + tid * 4, s_done[tid] != 0.f, r, done_m);
+                else obs_state_step<ENV, GOPS_MAX_LQ_STATE, GOPS_MAX_ACT, GEN>(env, O, A, xs + tid * ldx, s_act + tid * 4, s_done[tid] != 0.f, r, done_m);
             }
-        } else if (ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {
-            if (tid < TB) {   // gym-style models: obs == state, same wrapper handling as pyth_lq
-                const int m = tid;
-                constexpr int NS = (ENV == GOPS_ENV_CARTPOLE) ? 4 : 3;
-                float x[4] = {0.f, 0.f, 0.f, 0.f}, xn[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < NS; ++i) x[i] = obs_unscale(p.env, i, xs[m * ldx + i]);
-                const float a = s_act[m * 4];
-                const bool frozen = s_done[m] != 0.f;
-                const int nrep = GEN ? p.env.repeat_num : 1;
-                float rs = 0.f;
-                for (int rep = 0; rep < nrep; ++rep) {
-                    if (rep > 0 && !frozen) {
-#pragma unroll
-                        for (int i = 0; i < NS; ++i) x[i] = xn[i];
-                    }
-                    if (ENV == GOPS_ENV_CARTPOLE) {
-                        cart_forward(cart_const(), x, a, xn, r, done_m);
-                    } else {
-                        PendStep w;
-                        pend_forward(x, a, xn, r, w);
-                    }
-                    rs = (GEN && !p.env.repeat_last_reward) ? rs + r : r;
-                }
-                r = rs;
-                if (!frozen || p.env.clip_obs || p.env.scale_obs) {
-#pragma unroll
-                    for (int i = 0; i < NS; ++i) {
-                        const float v = obs_rescale(p.env, i, sel_reg(frozen, x[i], xn[i]));
-                        xs[m * ldx + i] = p.env.clip_obs ? clampf(v, p.env.obs_low[i], p.env.obs_high[i]) : v;
-                    }
-                }
-            }
+        } else if constexpr (ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {
+            if (tid < TB)   // gym-style models: obs == state, same wrapper handling as pyth_lq
+                obs_state_step<ENV, (ENV == GOPS_ENV_CARTPOLE) ? 4 : 3, 1, GEN>(env, O, A, xs + tid * ldx, s_act + tid * 4, s_done[tid] != 0.f, r, done_m);
         } else if (ENV == GOPS_ENV_IDPENDULUM) {
             if (tid < TB) {
                 const int m = tid;
@@ -845,14 +784,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                 // of the sweep's env phase, which is half of a sweep step at cfg2)
                 GLOBAL_AS f32x4* parkg = (p.need_grad && p.st.idp != nullptr) ? gptr(reinterpret_cast<f32x4*>(p.st.idp + (row0 + m) * IDP_PARK)) : nullptr;
                 auto park_store = [&](int k, const IdpSub& w) {
-                    if (parkg == nullptr) return;
-                    GLOBAL_AS f32x4* d = parkg + k * 6;
-                    d[0] = f32x4{s[0], s[1], s[2], s[3]};
-                    d[1] = f32x4{s[4], s[5], w.s1, w.c1};
-                    d[2] = f32x4{w.s2, w.c2, w.s12, w.c12};
-                    d[3] = f32x4{w.inv[0], w.inv[1], w.inv[2], w.inv[3]};
-                    d[4] = f32x4{w.inv[4], w.inv[5], w.qdd[0], w.qdd[1]};
-                    d[5] = f32x4{w.qdd[2], 0.f, 0.f, 0.f};
+                    if (parkg != nullptr) idp_park_store(parkg + k * (IDP_REC / 4), s, w);
                 };
                 for (int rep = 0; rep < nrep; ++rep) {
                     IdpSub w;
@@ -901,14 +833,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                 MobStep w;
                 mob_forward(MC, x, s_act[m * 4 + 0], s_act[m * 4 + 1], nv, nw, xn, r, c, done_m, w);
                 if (m < nvalid) {
-                    const float cp = fmaxf(c, 0.f), cm = fminf(c, 0.f);
-                    c_ext += cp * cp * p.gpow[t];
-                    c_lin += cp * p.gpow[t];
-                    c_int += logf(-cm + 1e-8f) * p.gpow[t];
-                    if (!(c < 0.f)) c_feas = 0.f;
-                    float dlog;
-                    c_mul[0] *= spil_phi(c, dlog);
-                    if (!(c <= 0.f)) c_safe[0] = 0.f;
+                    csum.add(&c, 1, p.gpow[t]);
                     if (p.out.constraints != nullptr) gptr(p.out.constraints)[(size_t)t * p.B + b0 + m] = c;
                 }
                 const bool frozen = s_done[m] != 0.f;
@@ -931,14 +856,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                 r = veh2_reward(o, steer);
                 if (p.env.cstr_err && m < nvalid) {   // pyth_veh2dofconti_errcstr: c = |delta_y| - tol of the CURRENT observation (unmasked)
                     const float c = fabsf(o[0]) - p.env.err_tol[0];
-                    const float cp = fmaxf(c, 0.f), cm = fminf(c, 0.f);
-                    c_ext += cp * cp * p.gpow[t];
-                    c_lin += cp * p.gpow[t];
-                    c_int += logf(-cm + 1e-8f) * p.gpow[t];
-                    if (!(c < 0.f)) c_feas = 0.f;
-                    float dlog;
-                    c_mul[0] *= spil_phi(c, dlog);
-                    if (!(c <= 0.f)) c_safe[0] = 0.f;
+                    csum.add(&c, 1, p.gpow[t]);
                     if (p.out.constraints != nullptr) gptr(p.out.constraints)[(size_t)t * p.B + b0 + m] = c;
                 }
                 float sphi, cphi;
@@ -948,7 +866,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                 for (int i = 0; i < 4; ++i) s_state[m * 8 + i] = sn[i];   // the info state advances whatever `done` says
                 const f32x4* tbl = s_ref + m * TL + (t + 1);              // reference points of the new time: (., y, phi, .)
                 const float o0 = sn[0] - tbl[0][1], o1 = sn[1] - tbl[0][2];
-                done_m = (fabsf(o0) > 2.f) || (fabsf(o1) > 3.14159265358979323846f);
+                done_m = VEH2_DONE(o0, o1);
                 if (s_done[m] == 0.f) {
                     float* xo = xs + m * ldx;
                     xo[0] = o0; xo[1] = o1; xo[2] = sn[2]; xo[3] = sn[3];
@@ -993,13 +911,15 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
             const float cn = veh_c, snn = -veh_s;           // cos(-phi'), sin(-phi')
             const f32x4* tbl = s_ref + m * TL + (t + 1);
             {   // point 0: the base model's done test reads its transform - every part evaluates it (the flag lives in registers)
+                // (= ref_point_to_ego, rollout_env.h, written out here and in the loop below: with the call hipcc issues five
+                //  instructions of this kernel's step in another order; in place the headline kernel is the parent's, instruction for instruction)
                 const f32x4 rp = tbl[0];
                 const float dx = rp[0] - sn[0], dy = rp[1] - sn[1];
                 const float xtf = dx * cn - dy * snn;
                 const float ytf = dx * snn + dy * cn;
                 const float ptf = angle_normalize(rp[2] - sn[2]);
                 const float utf = rp[3] - sn[3];
-                done_m = (fabsf(xtf) > 10.f) || (fabsf(ytf) > 10.f) || (fabsf(ptf) > 3.14159265358979323846f);
+                done_m = VEH_DONE(xtf, ytf, ptf);
                 if (part == 0 && dflag == 0.f) {
                     xs[m * ldx + 0] = xtf; xs[m * ldx + 1] = ytf; xs[m * ldx + 2] = ptf;
                     xs[m * ldx + 3] = utf; xs[m * ldx + 4] = sn[4]; xs[m * ldx + 5] = sn[5];
@@ -1063,23 +983,17 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
             const float cn = veh_c, snn = -veh_s;           // cos(-phi'), sin(-phi')
             const f32x4* tbl = s_ref + m * TL + (t + 1);
             for (int j = part; j <= P; j += 16) {
-                const f32x4 rp = tbl[j];
-                const float dx = rp[0] - sn[0], dy = rp[1] - sn[1];
-                const float xtf = dx * cn - dy * snn;
-                const float ytf = dx * snn + dy * cn;
-                const float ptf = angle_normalize(rp[2] - sn[2]);
-                const float utf = rp[3] - sn[3];
+                const EgoPoint e = ref_point_to_ego(tbl[j], sn, cn, snn);
                 if (j == 0) {
-                    done_m = (fabsf(xtf) > 10.f) || (fabsf(ytf) > 10.f) || (fabsf(ptf) > 3.14159265358979323846f);
+                    done_m = VEH_DONE(e.x, e.y, e.phi);
                     if (SURR && p.env.surr_penalty) done_m = false;   // judge_done of the penalty model: never (:236-246)
                     if (dflag == 0.f) {
-                        xs[m * ldx + 0] = xtf; xs[m * ldx + 1] = ytf; xs[m * ldx + 2] = ptf;
-                        xs[m * ldx + 3] = utf; xs[m * ldx + 4] = sn[4]; xs[m * ldx + 5] = sn[5];
+                        xs[m * ldx + 0] = e.x; xs[m * ldx + 1] = e.y; xs[m * ldx + 2] = e.phi;
+                        xs[m * ldx + 3] = e.u; xs[m * ldx + 4] = sn[4]; xs[m * ldx + 5] = sn[5];
                     }
                 } else if (dflag == 0.f) {
-                    f32x4 ov = {xtf, ytf, ptf, utf};
                     float* dst = xs + m * ldx + 6 + 4 * (j - 1);
-                    dst[0] = ov[0]; dst[1] = ov[1]; dst[2] = ov[2]; dst[3] = ov[3];
+                    dst[0] = e.x; dst[1] = e.y; dst[2] = e.phi; dst[3] = e.u;
                 }
             }
             if (part == 0) {
@@ -1122,25 +1036,12 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                     // the penalty model fills info["constraint"] before its info dict is updated (:131-139): CURRENT pose
                     if (p.env.surr_penalty) sc.c[0] = pen_c;
                     if (p.env.cstr_err) { sc.c[0] = err_c0; sc.c[1] = err_c1; }
-                    float e2 = 0.f, e1 = 0.f, lg = 0.f;
+                    csum.add(sc.c, p.env.n_constraint, p.gpow[t]);
+                    if (p.out.constraints != nullptr) {
 #pragma unroll
-                    for (int k = 0; k < GOPS_MAX_CONSTRAINT; ++k) {
-                        if (k < p.env.n_constraint) {
-                            const float cp = fmaxf(sc.c[k], 0.f), cm = fminf(sc.c[k], 0.f);
-                            e2 += cp * cp;
-                            e1 += cp;
-                            lg += logf(-cm + 1e-8f);
-                            if (!(sc.c[k] < 0.f)) c_feas = 0.f;
-                            float dlog;
-                            c_mul[k] *= spil_phi(sc.c[k], dlog);
-                            if (!(sc.c[k] <= 0.f)) c_safe[k] = 0.f;
-                            if (p.out.constraints != nullptr)
-                                gptr(p.out.constraints)[((size_t)t * p.B + b0 + m) * p.env.n_constraint + k] = sc.c[k];
-                        }
+                        for (int k = 0; k < GOPS_MAX_CONSTRAINT; ++k)
+                            if (k < p.env.n_constraint) gptr(p.out.constraints)[((size_t)t * p.B + b0 + m) * p.env.n_constraint + k] = sc.c[k];
                     }
-                    c_ext += e2 * p.gpow[t];
-                    c_lin += e1 * p.gpow[t];
-                    c_int += lg * p.gpow[t];
                 }
             }
         }
@@ -1169,7 +1070,6 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
         // mask_at_done = False: nothing was frozen or masked on the way; the rollout's done is the base model's test on
         // the LAST next state, which is the final observation (every done test of these models reads the new state only)
         const float* o = xs + tid * ldx;
-        const float pi = 3.14159265358979323846f;
         bool dl = false;
         if (ENV == GOPS_ENV_IDPENDULUM) {
             float s6[6];
@@ -1181,9 +1081,9 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
             const float x0 = obs_unscale(p.env, 0, o[0]), x2 = obs_unscale(p.env, 2, o[2]);
             dl = (x0 < -C.xth) || (x0 > C.xth) || (x2 < -C.thth) || (x2 > C.thth);
         } else if (ENV == GOPS_ENV_VEH3DOFCONTI) {
-            dl = (fabsf(o[0]) > 10.f) || (fabsf(o[1]) > 10.f) || (fabsf(o[2]) > pi);
+            dl = VEH_DONE(o[0], o[1], o[2]);
         } else if (ENV == GOPS_ENV_VEH2DOF) {
-            dl = (fabsf(o[0]) > 2.f) || (fabsf(o[1]) > pi);
+            dl = VEH2_DONE(o[0], o[1]);
         } else if (ENV == GOPS_ENV_MOBILEROBOT) {
             const MobConst MC = mob_const();
             const float dx = o[8] - o[0], dy = o[9] - o[1];
@@ -1239,14 +1139,14 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
 
     if (CSTR && tid < nvalid && p.out.constraint_sums != nullptr) {
         GLOBAL_AS float* cs = gptr(p.out.constraint_sums) + b0 + tid;
-        cs[0] = c_ext; cs[(size_t)p.B] = c_lin; cs[(size_t)2 * p.B] = c_int; cs[(size_t)3 * p.B] = c_feas;
+        cs[0] = csum.ext; cs[(size_t)p.B] = csum.lin; cs[(size_t)2 * p.B] = csum.itr; cs[(size_t)3 * p.B] = csum.feas;
     }
     if (CSTR && tid < nvalid && p.out.constraint_prods != nullptr) {
         GLOBAL_AS float* cp = gptr(p.out.constraint_prods) + b0 + tid;
         const int nc = p.env.n_constraint;
 #pragma unroll
         for (int k = 0; k < GOPS_MAX_CONSTRAINT; ++k)
-            if (k < nc) { cp[(size_t)k * p.B] = c_mul[k]; cp[(size_t)(nc + k) * p.B] = c_safe[k]; }
+            if (k < nc) { cp[(size_t)k * p.B] = csum.mul[k]; cp[(size_t)(nc + k) * p.B] = csum.safe[k]; }
     }
     if constexpr (SPLIT || SS) {
         // A value beyond the half range of the plane images (common.h SPLIT_FWD_SA: |a| >= 1.05e6) made part of this tile's contractions

@@ -16,6 +16,7 @@
 // padded inputs; everything else stays on the 16-row kernels (h64_shape_ok below).
 #include "common.h"
 #include "env_models.h"
+#include "rollout_env.h"
 #include "rollout_f16.h"
 #include "rollout_choice.h"
 
@@ -252,29 +253,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void rollout_fwd_h64_kernel(const Roll
                 er[0] = e0;
                 er[1] = e1;
             }
-            if (ENV == GOPS_ENV_NONE) {
+            if constexpr (ENV == GOPS_ENV_NONE) {
                 r = s_th[m * 4];
-            } else {   // GOPS_ENV_LQ (the arithmetic of rollout_fwd_kernel's LQ block); NS / NA: compile-time loop bounds
-                auto lq_step = [&]<int NS, int NA>() {
-                    constexpr bool EXACT = NS < GOPS_MAX_LQ_STATE;   // the dimensions ARE (NS, NA): no run-time guards
-                    float x[GOPS_MAX_LQ_STATE], xn[GOPS_MAX_LQ_STATE], u[GOPS_MAX_ACT];
-#pragma unroll
-                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { x[i] = (i < NS && (EXACT || i < O)) ? obs_unscale(env, i, xs[m * ldx + i]) : 0.f; xn[i] = 0.f; }
-#pragma unroll
-                    for (int j = 0; j < GOPS_MAX_ACT; ++j) u[j] = (j < NA && (EXACT || j < A)) ? s_act[m * 4 + j] : 0.f;
-                    const bool frozen = s_done[m] != 0.f;
-                    lq_forward<NS, NA>(env, x, u, xn, r);
-                    if (!frozen || env.clip_obs || env.scale_obs) {
-#pragma unroll
-                        for (int i = 0; i < NS; ++i)
-                            if (EXACT || i < O) {
-                                const float v = obs_rescale(env, i, sel_reg(frozen, x[i], xn[i]));
-                                xs[m * ldx + i] = env.clip_obs ? clampf(v, env.obs_low[i], env.obs_high[i]) : v;
-                            }
-                    }
-                };
-                if (O == 4 && A == 2) lq_step.template operator()<4, 2>();   // BASELINE configs[4] (lq s4a2)
-                else lq_step.template operator()<GOPS_MAX_LQ_STATE, GOPS_MAX_ACT>();
+            } else {   // GOPS_ENV_LQ; compile-time loop bounds (4, 2) for BASELINE configs[4] (lq s4a2)
+                bool done_m = false;   // (pyth_lq never terminates)
+                if (O == 4 && A == 2) obs_state_step<ENV, 4, 2, false>(env, O, A, xs + m * ldx, s_act + m * 4, s_done[m] != 0.f, r, done_m);
+                else obs_state_step<ENV, GOPS_MAX_LQ_STATE, GOPS_MAX_ACT, false>(env, O, A, xs + m * ldx, s_act + m * 4, s_done[m] != 0.f, r, done_m);
             }
             const float d = s_done[m];
             float rr = (d != 0.f) ? 0.f : r;
@@ -590,10 +574,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void rollout_bwd_h64_kernel(const Roll
                 *reinterpret_cast<f32x4*>(xr) = xa;
                 *reinterpret_cast<f32x4*>(xr + 4) = xb;
             }
-            if (ENV == GOPS_ENV_NONE) {
+            if constexpr (ENV == GOPS_ENV_NONE) {
                 s_gy[m * 4 + 0] = g_r;
                 s_gy[m * 4 + 1] = s_gy[m * 4 + 2] = s_gy[m * 4 + 3] = 0.f;
-            } else {   // GOPS_ENV_LQ (the arithmetic of rollout_bwd_kernel's LQ block); NS / NA: compile-time loop bounds
+            } else {   // GOPS_ENV_LQ; NS / NA: compile-time loop bounds
                 auto lq_adjoint = [&]<int NS, int NA>() {
                     constexpr bool EXACT = NS < GOPS_MAX_LQ_STATE;   // the dimensions ARE (NS, NA): no run-time guards
                     const float th[GOPS_MAX_ACT] = {cur.e0[0], cur.e0[1], cur.e0[2], cur.e0[3]}, dflag = cur.dflag;
@@ -603,43 +587,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void rollout_bwd_h64_kernel(const Roll
                         for (int i = 0; i < NS; ++i)
                             if (EXACT || i < O) x[i] = obs_unscale(env, i, i < 4 ? cur.xa[i & 3] : cur.xb[i & 3]);   // the stash holds the (scaled) policy input
                     }
-                    float abar[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f}, u[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f}, sc[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f},
-                          gu[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int a = 0; a < NA; ++a) {
-                        sc[a] = (env.policy_high[a] - env.policy_low[a]) / 2.f;
-                        abar[a] = sc[a] * th[a] + (env.policy_high[a] + env.policy_low[a]) / 2.f;
-                        u[a] = (EXACT || a < A) ? wrap_action(env, a, abar[a]) : 0.f;
-                    }
+                    const HeadAct hu = head_unsquash<NA, EXACT>(env, th, A, false);
                     const bool dn = dflag != 0.f;
-                    const float g_rm = dn ? 0.f : g_r;
-                    float Gin[GOPS_MAX_LQ_STATE], gx[GOPS_MAX_LQ_STATE];
+                    float Gin[GOPS_MAX_LQ_STATE], gx[GOPS_MAX_LQ_STATE], gu[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { Gin[i] = (i < NS && (EXACT || i < O)) ? G[m * ldx + i] : 0.f; gx[i] = 0.f; }
-                    if (env.clip_obs) {
-                        float xn[GOPS_MAX_LQ_STATE] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, rdummy;
-                        lq_forward<NS, NA>(env, x, u, xn, rdummy);
-#pragma unroll
-                        for (int i = 0; i < NS; ++i) {
-                            const float pre = obs_rescale(env, i, dn ? x[i] : xn[i]);   // what ClipObservation saw
-                            if ((EXACT || i < O) && !(pre >= env.obs_low[i] && pre <= env.obs_high[i])) Gin[i] = 0.f;
-                        }
-                    }
-                    if (env.scale_obs) {
-#pragma unroll
-                        for (int i = 0; i < NS; ++i)
-                            if (EXACT || i < O) Gin[i] *= env.obs_scale[i];
-                    }
-                    float gxn[GOPS_MAX_LQ_STATE];
-#pragma unroll
-                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { gxn[i] = dn ? 0.f : Gin[i]; gx[i] = dn ? Gin[i] : 0.f; }
-                    lq_backward<NS, NA>(env, x, u, gxn, g_rm, gx, gu);
-#pragma unroll
-                    for (int i = 0; i < NS; ++i)
-                        if (EXACT || i < O) G[m * ldx + i] = env.scale_obs ? gx[i] / env.obs_scale[i] : gx[i];
-#pragma unroll
-                    for (int a = 0; a < GOPS_MAX_ACT; ++a)
-                        s_gy[m * 4 + a] = (a < NA && (EXACT || a < A)) ? wrap_action_bwd(env, a, abar[a], gu[a]) * sc[a] * (1.f - th[a] * th[a]) : 0.f;
+                    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) Gin[i] = (i < NS && (EXACT || i < O)) ? G[m * ldx + i] : 0.f;
+                    obs_state_adjoint<ENV, NS, NA>(env, O, x, hu.u, dn, dn ? 0.f : g_r, Gin, gx, gu);
+                    obs_state_adjoint_store<NS, NA>(env, O, A, gx, gu, hu, th, false, G + m * ldx, s_gy + m * 4);
                 };
                 if (O == 4 && A == 2) lq_adjoint.template operator()<4, 2>();   // BASELINE configs[4] (lq s4a2)
                 else lq_adjoint.template operator()<GOPS_MAX_LQ_STATE, GOPS_MAX_ACT>();

@@ -5,7 +5,8 @@ import pytest
 import torch
 
 from conftest import golden_meta, load_golden, rel_l2
-from helpers import data_from_golden
+from helpers import data_from_golden, hip_env_from_oracle, to_device
+from oracle import adp_oracle as orc
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import poly_grad_buffers
@@ -356,3 +357,73 @@ def test_poly_one_step_equals_env_step(case, B):
         assert torch.equal(res["final_obs"], nobs)
     assert torch.equal(res["v_pi"], res["rewards"][0])        # gamma^0 = 1, no tail
     assert ndone[::5].all() and torch.isfinite(nobs).all()
+
+
+# ---- one open-loop step of the tile-form rollout against hb.env_step: both inline the same env phase (csrc/rollout_env.h) ------
+_OPEN_LOOP_ENVS = {"veh2dof": "pyth_veh2dofconti_errcstr", "veh3dofconti_p10": "pyth_veh3dofconti",
+                   "veh3dof_detour": "pyth_veh3dofconti_detour", "mobilerobot": "pyth_mobilerobot"}
+
+
+def _open_loop_env_and_batch(case, B):
+    """(GopsEnv, CPU batch) of a case.  Every action range is [-1, 1], so that the wrapper chain env_step applies to its action
+    is the identity on the multiples of 1/64 the test hands in: the rollout (raw_actions) and env_step step the same action."""
+    gen = torch.Generator().manual_seed(77 + B)
+    if case == "lq_s4a2_obsscale_clip":
+        lq = dict(inv_IA=[[1.0, 0.05, 0.0, 0.01], [-0.02, 0.97, 0.04, 0.0], [0.01, -0.03, 0.95, 0.02], [0.0, 0.02, -0.01, 0.98]],
+                  B=[[0.0, 0.1], [0.5, 0.0], [1.0, -0.25], [0.0, 1.0]], Q=[2.0, 1.0, 0.5, 0.25], R=[0.5, 0.125], dt=0.05,
+                  reward_scale=0.1, reward_shift=1.0)
+        env = hb.make_env(hb.ENV_LQ, 4, 2, act_low=[-1.0, -1.0], act_high=[1.0, 1.0], lq=lq, obs_scale=[0.5, 2.0, 1.5, 1.0],
+                          obs_shift=[0.25, -0.125, 0.0, 0.5], obs_low=[-0.2, -0.4, -0.3, -0.5], obs_high=[0.2, 0.4, 0.3, 0.5])
+        return env, {"obs": torch.randint(-32, 33, (B, 4), generator=gen).float() / 64}
+    if case in ("cartpole", "pendulum", "idpendulum"):
+        env = _step_env(case)
+        return env, {"obs": torch.randint(-32, 33, (B, env.obs_dim), generator=gen).float() / 64}
+    cfg = dict(alg="INFADP", env_id=_OPEN_LOOP_ENVS[case], batch=B, horizon=1, pre_horizon=10)
+    env = hip_env_from_oracle(orc.make_env(cfg["env_id"], pre_horizon=10))
+    for a in range(env.act_dim):
+        env.act_low[a], env.act_high[a], env.min_action[a], env.max_action[a] = -1.0, 1.0, -1.0, 1.0
+    data = {k: v for k, v in make_batch(cfg, 5).items() if torch.is_tensor(v)}
+    if case == "mobilerobot":
+        data["noise"] = (torch.randn(1, B, 2, generator=gen) * torch.tensor(hb.MOBILEROBOT_NOISE_STD)).contiguous()
+    return env, data
+
+
+# Largest distance, in units in the last place, between the open-loop rollout's step and env_step's, measured on an MI355X at the
+# commit before the tile-form kernels took their env phase from csrc/rollout_env.h: {case: {output: ulp}}; what is not listed was
+# bit-equal there (the forward step of either kernel was contracted into fused multiply-adds in its own way).
+OPEN_LOOP_ONE_STEP_ULP_BEFORE_SHARING = {"lq_s4a2_obsscale_clip": {"final_obs": 3}, "idpendulum": {"final_obs": 8},
+                                         "veh3dofconti_p10": {"final_obs": 12}, "veh3dof_detour": {"final_obs": 12}}
+
+
+@pytest.mark.parametrize("case", ["lq_s4a2_obsscale_clip", "cartpole", "pendulum", "idpendulum", "veh2dof", "veh3dofconti_p10",
+                                  "veh3dof_detour", "mobilerobot"])
+def test_open_loop_rollout_one_step_equals_env_step(case):
+    """An open-loop `hb.Rollout` (raw_actions: the actions are handed in) of H = 1, gamma = 1 and `hb.env_step` fed the same
+    actions: rewards, next observation, done flag and - where the model has them - the step's constraint values.  B = 33: two
+    full 16-row tiles and one row; every fifth row done.  The bound per output is what the two kernels measured before they
+    shared the statement of the env phase (OPEN_LOOP_ONE_STEP_ULP_BEFORE_SHARING, 0 where nothing is listed); the figures are
+    printed before they are asserted."""
+    B = 33
+    env, data = _open_loop_env_and_batch(case, B)
+    gen = torch.Generator().manual_seed(4242)
+    actions = torch.randint(-64, 65, (B, 1, env.act_dim), generator=gen).float() / 64
+    data["done"] = torch.zeros(B)
+    data["done"][::5] = 1.0
+    data = to_device(data, torch.device("cuda", 0))
+    actions = actions.cuda()
+    ro = hb.Rollout(env, None, batch=B, horizon=1, gamma=1.0, finite_horizon=False, need_grad=False, raw_actions=True)
+    res = ro.forward(data, head_pre=actions, want_rewards=True, want_final=True, want_constraints=True)
+    info = dict(data, noise=data["noise"][0]) if "noise" in data else data
+    nobs, rew, ndone, ninfo = hb.env_step(env, data["obs"], actions[:, 0].contiguous(), data["done"], info)
+    torch.cuda.synchronize()
+    pairs = {"rewards": (res["rewards"][0], rew), "final_obs": (res["final_obs"], nobs)}
+    if hb.has_constraints(env):
+        pairs["constraints"] = (res["constraints"][0], ninfo["constraint"])
+    ulp = {k: _ulp_distance(a, b) for k, (a, b) in pairs.items()}
+    print(f"{case}: " + ", ".join(f"{k} {v} ulp" for k, v in ulp.items()))
+    assert torch.equal(res["final_done"], ndone)
+    bound = OPEN_LOOP_ONE_STEP_ULP_BEFORE_SHARING.get(case, {})
+    for k, v in ulp.items():
+        assert v <= bound.get(k, 0), (case, k, v)
+    assert torch.equal(res["v_pi"], res["rewards"][0])        # gamma^0 = 1, no tail
+    assert ndone[::5].all() and torch.isfinite(nobs).all() and all(torch.isfinite(a).all() for a, _ in pairs.values())
