@@ -148,7 +148,10 @@ class ActorCriticBase(AlgorithmBase):
             getattr(nets, f"{n}_optimizer").step()
         if iteration % self.delay_update == 0:
             nets.policy_optimizer.step()
-        polyak = 1 - self.tau
+        self._polyak()
+
+    def _polyak(self):
+        nets, polyak = self.networks, 1 - self.tau
         for n in self._q_names + ("policy",):   # p_targ <- polyak p_targ + (1 - polyak) p   (ddpg.py:182-193, td3.py:234-251)
             online, target = list(getattr(nets, n).parameters()), list(getattr(nets, f"{n}_target").parameters())
             up = self._cache.get(("polyak", n))

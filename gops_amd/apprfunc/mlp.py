@@ -1,5 +1,5 @@
-"""MLP approximate functions of the ADP path: DetermPolicy, FiniteHorizonPolicy,
-FiniteHorizonFullPolicy, StateValue, ActionValue.
+"""MLP approximate functions: DetermPolicy, FiniteHorizonPolicy, FiniteHorizonFullPolicy, StateValue, ActionValue of the
+ADP and DDPG / TD3 paths; StochaPolicy and ActionValueDistri of DSAC-T.
 
 Module structure, parameter names (`pi.0.weight` ... / `v.0.weight` ...), registered buffers and
 `forward` semantics follow the reference (gops/apprfunc/mlp.py:36-41,50-111,309-329) so that its
@@ -7,7 +7,8 @@ Module structure, parameter names (`pi.0.weight` ... / `v.0.weight` ...), regist
 and evaluators for single observations; inside `compute_gradient` the same parameters are read
 in place by the fused HIP rollout (`hip_mlp()`), which never calls `forward`.
 """
-__all__ = ["DetermPolicy", "FiniteHorizonPolicy", "FiniteHorizonFullPolicy", "StateValue", "ActionValue"]
+__all__ = ["DetermPolicy", "FiniteHorizonPolicy", "FiniteHorizonFullPolicy", "StateValue", "ActionValue", "StochaPolicy",
+           "ActionValueDistri"]
 
 import weakref
 
@@ -160,3 +161,52 @@ class ActionValue(nn.Module, Action_Distribution, _HipMlpMixin):
 
     def forward(self, obs, act):
         return torch.squeeze(self.q(torch.cat([obs, act], dim=-1)), -1)
+
+
+class StochaPolicy(nn.Module, Action_Distribution, _HipMlpMixin):
+    """Stochastic policy: obs -> (mean, std) of the action distribution from ONE stack with 2 * act_dim outputs (reference
+    gops/apprfunc/mlp.py:149-221 with std_type "mlp_shared"; parameter names `policy.0.weight` ...).  `hip_mlp()` exports the
+    raw stack - its head is linear; the clamp of log std and the exp belong to the kernels (`gops_soft_backup`,
+    `gops_tanh_gauss_forward`)."""
+
+    _net_attr = "policy"
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        self.std_type = kwargs.get("std_type", "mlp_shared")
+        if self.std_type != "mlp_shared":
+            raise NotImplementedError(f"StochaPolicy: std_type {self.std_type!r} - only 'mlp_shared' (one stack for mean and log std) has "
+                                      "HIP kernels; 'mlp_separated' and 'parameter' keep log std outside the stack the kernels read")
+        self.act_dim = kwargs["act_dim"]
+        self._hidden_activation = kwargs["hidden_activation"]
+        self._output_activation = kwargs.get("output_activation", "linear")
+        self.policy = mlp([kwargs["obs_dim"]] + list(kwargs["hidden_sizes"]) + [2 * self.act_dim],
+                          get_activation_func(self._hidden_activation), get_activation_func(self._output_activation))
+        self.min_log_std = kwargs["min_log_std"]
+        self.max_log_std = kwargs["max_log_std"]
+        self.register_buffer("act_high_lim", torch.from_numpy(kwargs["act_high_lim"]))
+        self.register_buffer("act_low_lim", torch.from_numpy(kwargs["act_low_lim"]))
+        self.action_distribution_cls = kwargs["action_distribution_cls"]
+
+    def forward(self, obs):
+        mean, log_std = torch.chunk(self.policy(obs), chunks=2, dim=-1)
+        return torch.cat((mean, torch.clamp(log_std, self.min_log_std, self.max_log_std).exp()), dim=-1)
+
+
+class ActionValueDistri(nn.Module, _HipMlpMixin):
+    """Distributional action-value function: (obs, act) -> (mean, std) of the return, std = softplus of the second output (reference
+    gops/apprfunc/mlp.py:271-296, parameter names `q.0.weight` ...).  `hip_mlp()` exports the raw stack; the softplus belongs to
+    the kernels (`gops_soft_backup`, `gops_dsact_critic_loss`)."""
+
+    _net_attr = "q"
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        self._hidden_activation = kwargs["hidden_activation"]
+        self._output_activation = kwargs.get("output_activation", "linear")
+        self.q = mlp([kwargs["obs_dim"] + kwargs["act_dim"]] + list(kwargs["hidden_sizes"]) + [2],
+                     get_activation_func(self._hidden_activation), get_activation_func(self._output_activation))
+
+    def forward(self, obs, act):
+        mean, raw = torch.chunk(self.q(torch.cat([obs, act], dim=-1)), chunks=2, dim=-1)
+        return torch.cat((mean, torch.nn.functional.softplus(raw)), dim=-1)

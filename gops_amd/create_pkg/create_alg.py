@@ -27,12 +27,17 @@ def _entries(stem, module):
 _LOOP_ALGORITHMS = ("rpi", "ddpg", "td3")
 _ACTOR_CRITIC = ("DDPG", "TD3")   # model-free: MLP DetermPolicy + MLP ActionValue, fp32 (algorithm/_actor_critic.py)
 loop_registry = Registry("algorithm")
-registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem not in _LOOP_ALGORITHMS)
+# DSACT likewise: the key set of `loop_registry` is pinned by tests/test_td3_cpu.py (as it stood before DSAC-T), and that test file
+# stays as it is.  `create_alg` and `create_approx_contrainer` look in all three; `soft_registry` folds back with `loop_registry`.
+_SOFT_ALGORITHMS = ("dsact",)
+soft_registry = Registry("algorithm")
+registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem not in _LOOP_ALGORITHMS + _SOFT_ALGORITHMS)
 loop_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _LOOP_ALGORITHMS)
+soft_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _SOFT_ALGORITHMS)
 
 
 def _registry_of(algorithm: str) -> Registry:
-    return loop_registry if algorithm in loop_registry else registry
+    return loop_registry if algorithm in loop_registry else soft_registry if algorithm in soft_registry else registry
 
 
 def _defaults(kwargs: dict) -> dict:
@@ -97,6 +102,11 @@ def create_alg(**kwargs) -> object:
     if kwargs["algorithm"] in _ACTOR_CRITIC:   # refused here with the reason, so that nothing fails later
         from gops_amd.algorithm._actor_critic import refusal
         reason = refusal(kwargs["algorithm"], kwargs)
+        if reason is not None:
+            raise NotImplementedError(reason)
+    if kwargs["algorithm"] in soft_registry:
+        from gops_amd.algorithm.dsact import refusal
+        reason = refusal(kwargs)
         if reason is not None:
             raise NotImplementedError(reason)
     trainer = kwargs.get("trainer")

@@ -1,4 +1,4 @@
-// The no-grad half of a DDPG / TD3 update (gops/algorithm/ddpg.py:149-151, td3.py:166-183).
+// The no-grad half of a DDPG / TD3 / DSAC-T update (gops/algorithm/ddpg.py:149-151, td3.py:166-183, dsact.py:237-313).
 //
 // ac_backup_kernel: the Bellman backup in ONE launch, forward only, nothing stashed.  A workgroup of 256 threads owns a tile of R
 // batch rows (R = 16, 32 or 64) and evaluates the target policy and the one or two target critics on it, one net after the other:
@@ -12,6 +12,8 @@
 //   also hide the fmaf latency.)  The output layers (act_dim and one output), the squash, the noise clamps, the minimum and the
 //   backup are the same chains in DOUBLE, rounded once where a value is stored.
 //   Row strides of in0 / xa / xb are odd: the R rows a wave reads at one k sit in different banks.
+// soft_backup_kernel: DSAC-T's distributional soft backup (dsact.py:237-313) on the same tile scheme - a tanh-Gaussian target policy
+// (one thread per (row, action dimension) forms that dimension's mean and log std), two critics with (mean, softplus std) heads.
 // ac_critic_loss_kernel: gradient seeds, losses, mean(q) and |q - backup| of the critic regression in one launch; sums in double
 // in a fixed order (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
 #include <stdint.h>
@@ -43,7 +45,7 @@ struct AcNet {
 struct AcParams {
     AcNet net[3];   // 0: policy, 1 .. n_q: critics
     int n_q, smooth, B, O, A;
-    int ld0, ldx, xa_off, xb_off, w_off;   // floats
+    int ld0, ldx, xa_off, xb_off, e_off, w_off;   // floats
     float sq_low[GOPS_MAX_ACT], sq_high[GOPS_MAX_ACT], act_low[GOPS_MAX_ACT], act_high[GOPS_MAX_ACT];
     double sigma, clip, rscale, gamma;
     const float *obs2, *rew, *done, *xi;
@@ -78,21 +80,22 @@ inline int ac_up4(int x) { return (x + 3) & ~3; }
 
 // LDS plan for tiles of R rows within `limit` bytes; every hidden layer must get chunks of at least `min_nc` features (or the
 // whole layer).  Fills the offsets and the chunk sizes; returns the dynamic LDS bytes, 0 when it does not fit.
-size_t ac_plan(const GopsAcBackup& d, int R, size_t limit, int min_nc, AcParams& p) {
-    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
-    const int O = d.policy.sizes[0], A = d.policy.sizes[d.policy.n_layers];
+// `nets`: the policy and the n_q critics; O / A: observation and action width; `extra`: floats per tile row kept between the
+// networks besides in0 (the soft backup's per-dimension log-probability terms), in front of the weight chunk.
+size_t ac_plan(const GopsMlp* const* nets, int n_q, int O, int A, int extra, int R, size_t limit, int min_nc, AcParams& p) {
     int maxh = 0;
-    for (int n = 0; n <= d.n_q; ++n)
+    for (int n = 0; n <= n_q; ++n)
         for (int j = 1; j < nets[n]->n_layers; ++j) maxh = std::max(maxh, (int)nets[n]->sizes[j]);
     p.ld0 = (O + A) | 1;
     p.ldx = maxh | 1;
     p.xa_off = ac_up4(R * p.ld0);
     p.xb_off = p.xa_off + ac_up4(R * p.ldx);
-    p.w_off = p.xb_off + ac_up4(R * p.ldx);   // 16-byte aligned: the weight quads are read as one f32x4
+    p.e_off = p.xb_off + ac_up4(R * p.ldx);
+    p.w_off = p.e_off + ac_up4(R * extra);   // 16-byte aligned: the weight quads are read as one f32x4
     const long long wfloats = (long long)(limit / sizeof(float)) - p.w_off;
     if (wfloats <= 0) return 0;
     long long used = 0;
-    for (int n = 0; n <= d.n_q; ++n) {
+    for (int n = 0; n <= n_q; ++n) {
         const GopsMlp& m = *nets[n];
         for (int j = 0; j < m.n_layers - 1; ++j) {
             const int K = m.sizes[j], N = m.sizes[j + 1];
@@ -110,19 +113,114 @@ size_t ac_plan(const GopsAcBackup& d, int R, size_t limit, int min_nc, AcParams&
 
 // Tile rows and LDS bytes for a description: large batches take 64-row tiles (a weight chunk is staged once per 64 rows), small
 // ones 16-row tiles (more workgroups); within a tile size, the plan that leaves room for a second workgroup on the CU comes first.
-size_t ac_choose(const GopsAcBackup& d, int B, AcParams& p, int& R) {
+size_t ac_choose(const GopsMlp* const* nets, int n_q, int O, int A, int extra, int B, AcParams& p, int& R) {
     for (R = B >= 16384 ? 64 : B >= 2048 ? 32 : 16; R >= 16; R >>= 1) {
-        size_t lds = ac_plan(d, R, AC_LDS_TWO, 64, p);
-        if (lds == 0) lds = ac_plan(d, R, AC_LDS_LIMIT, 16, p);
+        size_t lds = ac_plan(nets, n_q, O, A, extra, R, AC_LDS_TWO, 64, p);
+        if (lds == 0) lds = ac_plan(nets, n_q, O, A, extra, R, AC_LDS_LIMIT, 16, p);
         if (lds != 0) return lds;
     }
     return 0;
+}
+size_t ac_choose(const GopsAcBackup& d, int B, AcParams& p, int& R) {
+    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
+    return ac_choose(nets, d.n_q, d.policy.sizes[0], d.policy.sizes[d.policy.n_layers], 0, B, p, R);
+}
+
+// The hidden layers of `net` on the tile's rows: input `in0` (row stride ld0), activations ping-pong between xa and xb (row stride
+// ldx), one weight chunk at a time through wb.  Returns where the last hidden activations are (row stride ldx).  Begins with a
+// barrier: what the caller wrote into in0 before the call is visible to every thread of the workgroup.
+template <int R>
+__device__ __forceinline__ const float* ac_hidden(const AcNet& net, const float* in0, int ld0, float* xa, float* xb, int ldx, float* wb) {
+    constexpr int G = AC_THREADS / R;   // feature quads in flight per row
+    const int tid = threadIdx.x, r = tid % R, g = tid / R;
+    const float* cur = in0;
+    int ldc = ld0;
+    float* nxt = xa;
+#pragma unroll 1
+    for (int j = 0; j < net.nl - 1; ++j) {
+        const int K = net.dims[j], N = net.dims[j + 1], NC = net.nc[j];
+        const float* __restrict__ Wg = net.W[j];
+#pragma unroll 1
+        for (int n0 = 0; n0 < N; n0 += NC) {
+            const int nc = min(NC, N - n0);
+            __syncthreads();   // the previous readers of wb are done; what the previous layer (or the staging above) wrote is visible
+            for (int idx = tid; idx < nc * K; idx += AC_THREADS) {
+                const int k = idx / nc, nn = idx - k * nc;
+                wb[k * NC + nn] = Wg[(size_t)(n0 + nn) * K + k];
+            }
+            for (int idx = tid; idx < nc; idx += AC_THREADS) wb[K * NC + idx] = net.Bv[j][n0 + idx];
+            __syncthreads();
+            const float* xr = cur + r * ldc;
+            act_dispatch(net.act, [&]<int ACT>() {
+                for (int fg = g; fg < (nc >> 2); fg += G) {
+                    const float* wq = wb + 4 * fg;
+                    f32x4 c[AC_CHAINS];
+#pragma unroll
+                    for (int i = 0; i < AC_CHAINS; ++i) c[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const int K8 = K & ~(AC_CHAINS - 1);
+                    for (int k = 0; k < K8; k += AC_CHAINS) {
+#pragma unroll
+                        for (int i = 0; i < AC_CHAINS; ++i) {
+                            const float x = xr[k + i];
+                            const f32x4 w = *reinterpret_cast<const f32x4*>(wq + (k + i) * NC);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) c[i][e] = fmaf(x, w[e], c[i][e]);
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < AC_CHAINS - 1; ++i) {
+                        if (K8 + i < K) {
+                            const float x = xr[K8 + i];
+                            const f32x4 w = *reinterpret_cast<const f32x4*>(wq + (K8 + i) * NC);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) c[i][e] = fmaf(x, w[e], c[i][e]);
+                        }
+                    }
+                    const float* bq = wb + K * NC + 4 * fg;
+                    float* yr = nxt + r * ldx + n0 + 4 * fg;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float sum = ((c[0][e] + c[1][e]) + (c[2][e] + c[3][e])) + ((c[4][e] + c[5][e]) + (c[6][e] + c[7][e]));
+                        yr[e] = act_fwd_t<ACT>(sum + bq[e]);
+                    }
+                }
+            });
+        }
+        cur = nxt;
+        ldc = ldx;
+        nxt = nxt == xa ? xb : xa;
+    }
+    return cur;
+}
+
+// One output of a head: eight double fma chains over the K hidden activations (input k in chain k mod 8, k ascending), added pairwise.
+__device__ __forceinline__ double ac_head_dot(const float* xr, const float* wr, int K) {
+    double c[AC_CHAINS];
+#pragma unroll
+    for (int i = 0; i < AC_CHAINS; ++i) c[i] = 0.0;
+    const int K8 = K & ~(AC_CHAINS - 1);
+    for (int k = 0; k < K8; k += AC_CHAINS) {
+#pragma unroll
+        for (int i = 0; i < AC_CHAINS; ++i) c[i] = fma((double)xr[k + i], (double)wr[k + i], c[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < AC_CHAINS - 1; ++i)
+        if (K8 + i < K) c[i] = fma((double)xr[K8 + i], (double)wr[K8 + i], c[i]);
+    return ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
+}
+
+// The output layer's weights, row-major [N][K], and its biases behind them into wb (barriers on both sides).
+__device__ __forceinline__ void ac_stage_head(const AcNet& net, float* wb) {
+    const int K = net.dims[net.nl - 1], N = net.dims[net.nl];
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < N * K; idx += AC_THREADS) wb[idx] = net.W[net.nl - 1][idx];
+    for (int idx = threadIdx.x; idx < N; idx += AC_THREADS) wb[N * K + idx] = net.Bv[net.nl - 1][idx];
+    __syncthreads();
 }
 
 template <int R>
 __global__ __launch_bounds__(AC_THREADS) void ac_backup_kernel(const AcParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int G = AC_THREADS / R;   // feature quads in flight per row
     const int tid = threadIdx.x, r = tid % R, g = tid / R;
     const int b0 = blockIdx.x * R;
     const int nvalid = min(R, p.B - b0);
@@ -140,87 +238,15 @@ __global__ __launch_bounds__(AC_THREADS) void ac_backup_kernel(const AcParams p)
 #pragma unroll 1
     for (int n = 0; n <= p.n_q; ++n) {
         const AcNet& net = p.net[n];
-        const float* cur = in0;
-        int ldc = ld0;
-        float* nxt = xa;
-#pragma unroll 1
-        for (int j = 0; j < net.nl - 1; ++j) {
-            const int K = net.dims[j], N = net.dims[j + 1], NC = net.nc[j];
-            const float* __restrict__ Wg = net.W[j];
-#pragma unroll 1
-            for (int n0 = 0; n0 < N; n0 += NC) {
-                const int nc = min(NC, N - n0);
-                __syncthreads();   // the previous readers of wb are done; what the previous layer (or the staging above) wrote is visible
-                for (int idx = tid; idx < nc * K; idx += AC_THREADS) {
-                    const int k = idx / nc, nn = idx - k * nc;
-                    wb[k * NC + nn] = Wg[(size_t)(n0 + nn) * K + k];
-                }
-                for (int idx = tid; idx < nc; idx += AC_THREADS) wb[K * NC + idx] = net.Bv[j][n0 + idx];
-                __syncthreads();
-                const float* xr = cur + r * ldc;
-                act_dispatch(net.act, [&]<int ACT>() {
-                    for (int fg = g; fg < (nc >> 2); fg += G) {
-                        const float* wq = wb + 4 * fg;
-                        f32x4 c[AC_CHAINS];
-#pragma unroll
-                        for (int i = 0; i < AC_CHAINS; ++i) c[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        const int K8 = K & ~(AC_CHAINS - 1);
-                        for (int k = 0; k < K8; k += AC_CHAINS) {
-#pragma unroll
-                            for (int i = 0; i < AC_CHAINS; ++i) {
-                                const float x = xr[k + i];
-                                const f32x4 w = *reinterpret_cast<const f32x4*>(wq + (k + i) * NC);
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) c[i][e] = fmaf(x, w[e], c[i][e]);
-                            }
-                        }
-#pragma unroll
-                        for (int i = 0; i < AC_CHAINS - 1; ++i) {
-                            if (K8 + i < K) {
-                                const float x = xr[K8 + i];
-                                const f32x4 w = *reinterpret_cast<const f32x4*>(wq + (K8 + i) * NC);
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) c[i][e] = fmaf(x, w[e], c[i][e]);
-                            }
-                        }
-                        const float* bq = wb + K * NC + 4 * fg;
-                        float* yr = nxt + r * ldx + n0 + 4 * fg;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float sum = ((c[0][e] + c[1][e]) + (c[2][e] + c[3][e])) + ((c[4][e] + c[5][e]) + (c[6][e] + c[7][e]));
-                            yr[e] = act_fwd_t<ACT>(sum + bq[e]);
-                        }
-                    }
-                });
-            }
-            cur = nxt;
-            ldc = ldx;
-            nxt = nxt == xa ? xb : xa;
-        }
+        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
         // ---- output layer: row-major [N][K] in wb, one thread per (row, output) ----
         const int K = net.dims[net.nl - 1], N = net.dims[net.nl];
-        __syncthreads();
-        for (int idx = tid; idx < N * K; idx += AC_THREADS) wb[idx] = net.W[net.nl - 1][idx];
-        for (int idx = tid; idx < N; idx += AC_THREADS) wb[N * K + idx] = net.Bv[net.nl - 1][idx];
-        __syncthreads();
+        ac_stage_head(net, wb);
         if (g < N) {
-            const float* xr = cur + r * ldc;
-            const float* wr = wb + g * K;
             // The output layer, the squash and the backup are formed in double and rounded once where they are stored: one thread
             // per (row, output), K <= 256 products - a negligible share of the work, and what is left of the kernel's error is the
             // fp32 rounding of the hidden layers alone.
-            double c[AC_CHAINS];
-#pragma unroll
-            for (int i = 0; i < AC_CHAINS; ++i) c[i] = 0.0;
-            const int K8 = K & ~(AC_CHAINS - 1);
-            for (int k = 0; k < K8; k += AC_CHAINS) {
-#pragma unroll
-                for (int i = 0; i < AC_CHAINS; ++i) c[i] = fma((double)xr[k + i], (double)wr[k + i], c[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < AC_CHAINS - 1; ++i)
-                if (K8 + i < K) c[i] = fma((double)xr[K8 + i], (double)wr[K8 + i], c[i]);
-            const double y = (((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]))) + (double)wb[N * K + g];
+            const double y = ac_head_dot(cur + r * ldx, wb + g * K, K) + (double)wb[N * K + g];
             if (n == 0) {   // the policy's own squash, then TD3's smoothing (td3.py:168-177)
                 const double lo_s = g == 0 ? p.sq_low[0] : g == 1 ? p.sq_low[1] : g == 2 ? p.sq_low[2] : p.sq_low[3];
                 const double hi_s = g == 0 ? p.sq_high[0] : g == 1 ? p.sq_high[1] : g == 2 ? p.sq_high[2] : p.sq_high[3];
@@ -243,6 +269,110 @@ __global__ __launch_bounds__(AC_THREADS) void ac_backup_kernel(const AcParams p)
     }
     if (g == 0 && r < nvalid)   // backup = r * reward_scale + gamma * (1 - d) * q   (ddpg.py:151, td3.py:183)
         p.backup[b0 + r] = (float)((double)p.rew[b0 + r] * p.rscale + p.gamma * (1.0 - (double)p.done[b0 + r]) * q_min);
+}
+
+// ---- DSAC-T: the distributional soft backup (gops/algorithm/dsact.py:237-313, the no-grad part) -----------------------------------
+// Same tile, staging and chains as ac_backup_kernel.  The policy head has 2 A outputs (means, then log stds) but a 64-row tile has only
+// four feature groups per row: thread (r, g < A) forms BOTH outputs of action dimension g, samples, squashes, and leaves that
+// dimension's log-probability term in LDS (lp [A][R], doubles, in the plan's extra section); thread (r, 0) forms both outputs of each
+// critic and, at the end, the row's two targets.
+struct SoftParams {
+    AcParams ac;   // net, B, O, A, the LDS plan, act_low / act_high, gamma, obs2 / rew / done, a2, q_targ ([2, B, 2] here)
+    double min_ls, max_ls, alpha;
+    const float *log_alpha, *eps, *z;
+    float *tq, *tqs, *logp;
+};
+
+__device__ __forceinline__ double softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }   // (torch's threshold)
+
+template <int R>
+__global__ __launch_bounds__(AC_THREADS) void soft_backup_kernel(const SoftParams sp) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const AcParams& p = sp.ac;
+    const int tid = threadIdx.x, r = tid % R, g = tid / R;
+    const int b0 = blockIdx.x * R;
+    const int nvalid = min(R, p.B - b0);
+    const int O = p.O, A = p.A, ld0 = p.ld0, ldx = p.ldx;
+    float* in0 = lds;
+    float* xa = lds + p.xa_off;
+    float* xb = lds + p.xb_off;
+    double* lp = reinterpret_cast<double*>(lds + p.e_off);
+    float* wb = lds + p.w_off;
+
+    for (int idx = tid; idx < R * O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
+        const int m = idx / O, k = idx - m * O;
+        in0[m * ld0 + k] = m < nvalid ? p.obs2[(size_t)(b0 + m) * O + k] : 0.f;
+    }
+    {   // ---- target policy: u = mean + std * eps, a2 = half * tanh(u) + mid, the dimension's share of log pi(a2 | obs2) ----
+        const AcNet& net = p.net[0];
+        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
+        const int K = net.dims[net.nl - 1];
+        ac_stage_head(net, wb);
+        if (g < A) {
+            const float* xr = cur + r * ldx;
+            const double mean = ac_head_dot(xr, wb + g * K, K) + (double)wb[2 * A * K + g];
+            const double ls = ac_head_dot(xr, wb + (A + g) * K, K) + (double)wb[2 * A * K + A + g];
+            const double sd = exp(fmin(fmax(ls, sp.min_ls), sp.max_ls));
+            const double e = r < nvalid ? (double)sp.eps[(size_t)(b0 + r) * A + g] : 0.0;
+            const double u = mean + sd * e, th = tanh(u), du = u - mean;
+            const double lo = g == 0 ? p.act_low[0] : g == 1 ? p.act_low[1] : g == 2 ? p.act_low[2] : p.act_low[3];
+            const double hi = g == 0 ? p.act_high[0] : g == 1 ? p.act_high[1] : g == 2 ? p.act_high[2] : p.act_high[3];
+            const double half = (hi - lo) / 2;
+            const float af = (float)(half * th + (hi + lo) / 2);
+            in0[r * ld0 + O + g] = af;   // (published, like lp, by the barrier at the top of the critic's first chunk)
+            if (p.a2 != nullptr && r < nvalid) p.a2[(size_t)(b0 + r) * A + g] = af;
+            // Normal(mean, std).log_prob(u) - log(1 + 1e-6 - tanh(u)^2) - log(half)      (act_distribution_type.py:41-51)
+            lp[g * R + r] = (-(du * du) / (2 * sd * sd) - log(sd) - 0.91893853320467274178) - log(1.0 + 1e-6 - th * th) - log(half);
+        }
+    }
+    double m1 = 0.0, s1 = 0.0, m2 = 0.0, s2 = 0.0;   // of row r, in the threads with g == 0
+#pragma unroll 1
+    for (int n = 1; n <= 2; ++n) {
+        const AcNet& net = p.net[n];
+        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
+        const int K = net.dims[net.nl - 1];
+        ac_stage_head(net, wb);
+        if (g == 0) {
+            const float* xr = cur + r * ldx;
+            const double m = ac_head_dot(xr, wb, K) + (double)wb[2 * K];
+            const double sd = softplus_d(ac_head_dot(xr, wb + K, K) + (double)wb[2 * K + 1]);
+            if (p.q_targ != nullptr && r < nvalid) {
+                float* qt = p.q_targ + ((size_t)(n - 1) * p.B + b0 + r) * 2;
+                qt[0] = (float)m, qt[1] = (float)sd;
+            }
+            if (n == 1) m1 = m, s1 = sd;
+            else m2 = m, s2 = sd;
+        }
+    }
+    if (g == 0 && r < nvalid) {
+        const int b = b0 + r;
+        double logp = 0.0;
+        for (int a = 0; a < A; ++a) logp += lp[a * R + r];
+        const double alpha = sp.log_alpha != nullptr ? exp((double)*sp.log_alpha) : sp.alpha;
+        const double z1 = fmin(fmax((double)sp.z[b], -3.0), 3.0), z2 = fmin(fmax((double)sp.z[(size_t)p.B + b], -3.0), 3.0);
+        const double q_next = fmin(m1, m2), q_sample = m1 < m2 ? m1 + z1 * s1 : m2 + z2 * s2;
+        const double rew = (double)p.rew[b], live = (1.0 - (double)p.done[b]) * p.gamma;
+        sp.tq[b] = (float)(rew + live * (q_next - alpha * logp));    // dsact.py:304-309
+        sp.tqs[b] = (float)(rew + live * (q_sample - alpha * logp));
+        if (sp.logp != nullptr) sp.logp[b] = (float)logp;
+    }
+}
+
+int soft_check(const GopsSoftBackup* d, int B) {
+    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
+    if (d->policy.n_layers < 1 || d->policy.n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
+    const int O = d->policy.sizes[0], A2 = d->policy.sizes[d->policy.n_layers], A = A2 / 2;
+    if (O < 1 || A < 1 || (A2 & 1) || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (O + A > AC_MAX_IN) return GOPS_ERR_UNSUPPORTED;
+    int rc = ac_check_net(d->policy, O, 2 * A);
+    for (int i = 0; i < 2 && rc == GOPS_OK; ++i) rc = ac_check_net(d->q[i], O + A, 2);
+    return rc;
+}
+
+size_t soft_choose(const GopsSoftBackup& d, int B, AcParams& p, int& R) {
+    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
+    const int A = d.policy.sizes[d.policy.n_layers] / 2;
+    return ac_choose(nets, 2, d.policy.sizes[0], A, 2 * A, B, p, R);   // extra: A doubles per row
 }
 
 // ---- critic regression: seeds, losses, mean(q), |q - backup| -------------------------------------------------------------------
@@ -372,5 +502,44 @@ int ac_critic_loss(const float* q, const float* backup, const float* weight, int
                    hipStream_t s) {
     hipLaunchKernelGGL(ac_critic_loss_kernel, dim3(B <= ACL_ONE_BLOCK_MAX ? 1 : ACL_BLOCKS), dim3(256), 0, s, q, backup, weight, nq, B,
                        (float)(2.0 / B), seed, abs_err, stats);
+    return (int)hipGetLastError();
+}
+
+size_t soft_backup_workspace_bytes(const GopsSoftBackup* d, int B) {
+    if (soft_check(d, B) != GOPS_OK) return 0;
+    AcParams p;
+    int R;
+    return soft_choose(*d, B, p, R) == 0 ? 0 : AC_WORKSPACE;
+}
+
+int soft_backup(const GopsSoftBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
+                float* tq, float* tqs, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int rc = soft_check(d, B);
+    if (rc != GOPS_OK) return rc;
+    if (!obs2 || !rew || !done || !eps || !z || !tq || !tqs) return GOPS_ERR_BAD_ARG;
+    SoftParams sp;
+    memset(&sp, 0, sizeof(sp));
+    AcParams& p = sp.ac;
+    int R;
+    const size_t lds = soft_choose(*d, B, p, R);
+    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < AC_WORKSPACE) return GOPS_ERR_WORKSPACE;
+    const GopsMlp* nets[3] = {&d->policy, &d->q[0], &d->q[1]};
+    for (int n = 0; n < 3; ++n) {
+        AcNet& a = p.net[n];
+        a.nl = nets[n]->n_layers, a.act = nets[n]->hidden_act;
+        for (int j = 0; j <= a.nl; ++j) a.dims[j] = nets[n]->sizes[j];
+        for (int j = 0; j < a.nl; ++j) { a.W[j] = nets[n]->weight[j]; a.Bv[j] = nets[n]->bias[j]; }
+    }
+    p.n_q = 2, p.B = B, p.O = d->policy.sizes[0], p.A = d->policy.sizes[d->policy.n_layers] / 2;
+    for (int a = 0; a < p.A; ++a) p.act_low[a] = d->act_low[a], p.act_high[a] = d->act_high[a];
+    p.gamma = d->gamma;
+    p.obs2 = obs2, p.rew = rew, p.done = done, p.a2 = a2, p.q_targ = q_targ;
+    sp.min_ls = d->min_log_std, sp.max_ls = d->max_log_std, sp.alpha = d->alpha, sp.log_alpha = d->log_alpha;
+    sp.eps = eps, sp.z = z, sp.tq = tq, sp.tqs = tqs, sp.logp = logp;
+    const dim3 grid((unsigned)((B + R - 1) / R));
+    if (R == 64) launch_with_lds(soft_backup_kernel<64>, grid, dim3(AC_THREADS), lds, s, sp);
+    else if (R == 32) launch_with_lds(soft_backup_kernel<32>, grid, dim3(AC_THREADS), lds, s, sp);
+    else launch_with_lds(soft_backup_kernel<16>, grid, dim3(AC_THREADS), lds, s, sp);
     return (int)hipGetLastError();
 }

@@ -1083,6 +1083,39 @@ int gops_ac_critic_loss(const float* q, const float* backup, const float* weight
     return ac_critic_loss(q, backup, weight, n_q, batch, seed, abs_err, stats, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_soft_backup_workspace_bytes(const GopsSoftBackup* desc, int32_t batch) { return soft_backup_workspace_bytes(desc, batch); }
+
+int gops_soft_backup(const GopsSoftBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,
+                     const float* eps_next, const float* z_next, float* target_q, float* target_q_sample, float* a2, float* logp,
+                     float* q_targ, void* workspace, size_t workspace_bytes, void* stream) {
+    return soft_backup(desc, batch, obs2, rew, done, eps_next, z_next, target_q, target_q_sample, a2, logp, q_targ, workspace,
+                       workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int gops_dsact_critic_loss(const float* qraw, const float* target_q, const float* target_q_sample, int32_t batch, double tau_b,
+                           GopsDsactState* state, float* seed, float* stats, void* stream) {
+    if (!qraw || !target_q || !target_q_sample || !state || !seed || !stats || batch < 1) return GOPS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
+    return dsact_critic_loss(qraw, target_q, target_q_sample, batch, tau_b, state, seed, stats, static_cast<hipStream_t>(stream));
+}
+
+static bool tanh_gauss_ok(const GopsTanhGauss* d, int32_t batch) {
+    return d && batch >= 1 && d->act_dim >= 1 && d->act_dim <= GOPS_MAX_ACT;
+}
+
+int gops_tanh_gauss_forward(const GopsTanhGauss* desc, int32_t batch, const float* head, const float* eps, double target_entropy,
+                            float* act, float* logp, float* stats, void* stream) {
+    if (!tanh_gauss_ok(desc, batch) || !head || !eps || !act || !logp || !stats) return GOPS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;
+    return tanh_gauss_forward(*desc, batch, head, eps, target_entropy, act, logp, stats, static_cast<hipStream_t>(stream));
+}
+
+int gops_tanh_gauss_backward(const GopsTanhGauss* desc, int32_t batch, const float* head, const float* eps, const float* g_act,
+                             const float* g_logp, float* g_head, void* stream) {
+    if (!tanh_gauss_ok(desc, batch) || !head || !eps || !g_act || !g_logp || !g_head) return GOPS_ERR_BAD_ARG;
+    return tanh_gauss_backward(*desc, batch, head, eps, g_act, g_logp, g_head, static_cast<hipStream_t>(stream));
+}
+
 void gops_profile_enable(int32_t on) {
     std::lock_guard<std::mutex> lk(g_prof.mu);
     g_prof.on = on != 0;

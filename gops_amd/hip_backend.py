@@ -153,6 +153,17 @@ class GopsAcBackup(C.Structure):   # gops_ac_backup
                 ("target_noise", C.c_double), ("noise_clip", C.c_double), ("reward_scale", C.c_double), ("gamma", C.c_double)]
 
 
+class GopsSoftBackup(C.Structure):   # gops_soft_backup
+    _fields_ = [("policy", GopsMlp), ("q", GopsMlp * 2), ("act_low", C.c_float * MAX_ACT), ("act_high", C.c_float * MAX_ACT),
+                ("min_log_std", C.c_double), ("max_log_std", C.c_double), ("gamma", C.c_double), ("alpha", C.c_double),
+                ("log_alpha", C.c_void_p)]
+
+
+class GopsTanhGauss(C.Structure):   # gops_tanh_gauss_forward / _backward
+    _fields_ = [("act_dim", C.c_int32), ("reserved", C.c_int32), ("act_low", C.c_float * MAX_ACT), ("act_high", C.c_float * MAX_ACT),
+                ("min_log_std", C.c_double), ("max_log_std", C.c_double)]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every symbol of include/gops_hip.h (argtypes None: not declared to ctypes)."""
     P, vp, i32, sz, f64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_size_t, C.c_double, C.c_int
@@ -201,6 +212,11 @@ def _signatures():
         "gops_ac_backup_workspace_bytes": (sz, [P(GopsAcBackup), i32]),
         "gops_ac_backup": (rc, [P(GopsAcBackup), i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gops_ac_critic_loss": (rc, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "gops_soft_backup_workspace_bytes": (sz, [P(GopsSoftBackup), i32]),
+        "gops_soft_backup": (rc, [P(GopsSoftBackup), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "gops_dsact_critic_loss": (rc, [vp, vp, vp, i32, f64, vp, vp, vp, vp]),
+        "gops_tanh_gauss_forward": (rc, [P(GopsTanhGauss), i32, vp, vp, f64, vp, vp, vp, vp]),
+        "gops_tanh_gauss_backward": (rc, [P(GopsTanhGauss), i32, vp, vp, vp, vp, vp, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -1285,6 +1301,110 @@ class AcCriticLoss:
         check(lib().gops_ac_critic_loss(_ptr(q), _ptr(backup), _ptr(weight), n_q, B, _ptr(seed), _ptr(abs_err), self.buf.data_ptr(),
                                         _stream()), "gops_ac_critic_loss")
         return seed, abs_err, self.buf[:4]
+
+
+DSACT_STATS_FLOATS = 800        # include/gops_hip.h: GOPS_DSACT_STATS_FLOATS
+TANH_GAUSS_STATS_FLOATS = 800   # include/gops_hip.h: GOPS_TANH_GAUSS_STATS_FLOATS
+
+
+class SoftBackup:
+    """DSAC-T's distributional soft backup in ONE launch (`gops_soft_backup`, csrc/actor_critic.hip): tanh-Gaussian target policy on
+    obs2, both target critics' (mean, softplus std) on the concatenated input, minimum, the clipped return sample, entropy term.
+    `policy` / `critics`: `GopsMlp` views of the TARGET networks' raw stacks.  `log_alpha`: the device tensor the kernel takes alpha
+    from (`exp` inside the kernel), or None for the fixed `alpha` of `run`.  `supported` is False for a shape the kernel does not
+    hold; `run` on such a description raises."""
+
+    def __init__(self, policy: GopsMlp, critics: Sequence[GopsMlp], *, act_low, act_high, min_log_std: float, max_log_std: float,
+                 batch: int, log_alpha: Optional[torch.Tensor] = None, device: Optional[torch.device] = None,
+                 workspace_bytes: Optional[int] = None):
+        d = self.desc = GopsSoftBackup()
+        self.batch, self.act_dim = int(batch), int(policy.sizes[policy.n_layers]) // 2
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        for name, vals in (("act_low", act_low), ("act_high", act_high)):
+            _fill(getattr(d, name), np.asarray(vals, dtype=np.float32).reshape(-1)[:MAX_ACT])
+        d.min_log_std, d.max_log_std = float(min_log_std), float(max_log_std)
+        self.log_alpha = log_alpha
+        d.log_alpha = _ptr(log_alpha)
+        self.set_nets(policy, critics)
+        nbytes = lib().gops_soft_backup_workspace_bytes(C.byref(d), self.batch)
+        self.supported = nbytes != 0
+        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
+        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
+
+    def set_nets(self, policy: GopsMlp, critics: Sequence[GopsMlp]):
+        assert len(critics) == 2
+        C.memmove(C.byref(self.desc.policy), C.byref(policy), C.sizeof(GopsMlp))
+        for i, c in enumerate(critics):
+            C.memmove(C.byref(self.desc.q[i]), C.byref(c), C.sizeof(GopsMlp))
+        self._keep = (policy, list(critics))   # the description holds raw pointers
+
+    def run(self, obs2, rew, done, eps_next, z_next, *, gamma=0.99, alpha=0.2, want=(), out: Optional[Dict[str, torch.Tensor]] = None):
+        """-> {"target_q" [B], "target_q_sample" [B]} and, named in `want`: "a2" [B, A], "logp" [B], "q_targ" [2, B, 2]; `out` supplies
+        output tensors instead of fresh ones.  Enqueues only."""
+        B, d, dev = self.batch, self.desc, self.device
+        assert obs2.shape[0] == B and tuple(z_next.shape) == (2, B)
+        d.gamma, d.alpha = float(gamma), float(alpha)
+        res = dict(out or {})
+        shapes = dict(target_q=(B,), target_q_sample=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(2, B, 2))
+        for k in ("target_q", "target_q_sample") + tuple(want):
+            if k not in res:
+                res[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
+        check(lib().gops_soft_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["target_q"]),
+                                     _ptr(res["target_q_sample"]), _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")),
+                                     self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_soft_backup")
+        return res
+
+
+class DsactCriticLoss:
+    """DSAC-T's critic losses, gradient seeds and the running `mean_std` (`gops_dsact_critic_loss`).  `state` = GopsDsactState as four
+    32-bit words (mean_std1, mean_std2 as floats, the "initialised" word, a spare one); `buf[:11]` = the statistics, the rest is the
+    kernel's scratch (zero before the first call, left zero)."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(DSACT_STATS_FLOATS, dtype=torch.float32, device=device)
+        self.state = torch.zeros(4, dtype=torch.int32, device=device)
+
+    @property
+    def mean_std(self) -> torch.Tensor:
+        return self.state.view(torch.float32)[:2]
+
+    def run(self, qraw: torch.Tensor, target_q: torch.Tensor, target_q_sample: torch.Tensor, tau_b: float, seed: Optional[torch.Tensor] = None):
+        """qraw [2, B, 2] -> (seed [2, B, 2], stats [11])."""
+        B = qraw.shape[1]
+        assert tuple(qraw.shape) == (2, B, 2)
+        seed = torch.empty_like(qraw) if seed is None else seed
+        check(lib().gops_dsact_critic_loss(_ptr(qraw), _ptr(target_q), _ptr(target_q_sample), B, float(tau_b), self.state.data_ptr(),
+                                           _ptr(seed), self.buf.data_ptr(), _stream()), "gops_dsact_critic_loss")
+        return seed, self.buf[:11]
+
+
+class TanhGaussHead:
+    """StochaPolicy's sampling head and its reverse (`gops_tanh_gauss_forward / _backward`): raw head [B, 2 A] and draws eps [B, A] ->
+    action, log-probability and `buf[:4]` = mean(logp), mean(tanh(mean)), mean(std), -(mean(logp) + target_entropy)."""
+
+    def __init__(self, act_low, act_high, min_log_std: float, max_log_std: float, device):
+        d = self.desc = GopsTanhGauss()
+        low = np.asarray(act_low, dtype=np.float32).reshape(-1)
+        d.act_dim = self.act_dim = len(low)
+        _fill(d.act_low, low[:MAX_ACT])
+        _fill(d.act_high, np.asarray(act_high, dtype=np.float32).reshape(-1)[:MAX_ACT])
+        d.min_log_std, d.max_log_std = float(min_log_std), float(max_log_std)
+        self.buf = torch.zeros(TANH_GAUSS_STATS_FLOATS, dtype=torch.float32, device=device)
+
+    def forward(self, head, eps, target_entropy: float = 0.0, act=None, logp=None):
+        B = head.shape[0]
+        act = torch.empty(B, self.act_dim, dtype=torch.float32, device=head.device) if act is None else act
+        logp = torch.empty(B, dtype=torch.float32, device=head.device) if logp is None else logp
+        check(lib().gops_tanh_gauss_forward(C.byref(self.desc), B, _ptr(head), _ptr(eps), float(target_entropy), _ptr(act), _ptr(logp),
+                                            self.buf.data_ptr(), _stream()), "gops_tanh_gauss_forward")
+        return act, logp, self.buf[:4]
+
+    def backward(self, head, eps, g_act, g_logp, g_head=None):
+        B = head.shape[0]
+        g_head = torch.empty_like(head) if g_head is None else g_head
+        check(lib().gops_tanh_gauss_backward(C.byref(self.desc), B, _ptr(head), _ptr(eps), _ptr(g_act), _ptr(g_logp), _ptr(g_head),
+                                             _stream()), "gops_tanh_gauss_backward")
+        return g_head
 
 
 def make_update_tail(fused_adam=None, mean_of: Optional[torch.Tensor] = None, mean_scale: float = -1.0,

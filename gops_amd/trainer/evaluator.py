@@ -22,6 +22,7 @@ import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import is_poly
+from gops_amd.apprfunc.mlp import StochaPolicy
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, NOT_RESTATED, draw_reset_pool
 
 # TimeLimit of the data envs where create_env registers one (gops/create_pkg/create_env.py:142-148 takes the env's own
@@ -91,6 +92,8 @@ class Evaluator:
             return "POLY policy"
         if getattr(pol, "is_lipsnet", False):
             return "LipsNet policy"
+        if isinstance(pol, StochaPolicy):   # (its stack emits (mean, log std): the episode kernel squashes a deterministic head)
+            return "stochastic policy"
         env = self._hip_env()
         if env.kind == hb.ENV_MOBILEROBOT:
             return "pyth_mobilerobot draws its obstacle noise per step"
@@ -146,7 +149,10 @@ class Evaluator:
             mk = (lambda *sh: torch.empty(*sh, device=dev)) if trace_fill is None else (lambda *sh: torch.full(sh, float(trace_fill), device=dev))
             res.update(trace_obs=mk(E, T, env.obs_dim), trace_act=mk(E, T, env.act_dim), trace_rew=mk(E, T))
         for t in range(T):
-            act = policy(obs).contiguous()
+            act = policy(obs)
+            if isinstance(policy, StochaPolicy):   # evaluation acts with the distribution's mode
+                act = policy.get_act_dist(act).mode()
+            act = act.contiguous()
             obs2, rew, done, info2 = hb.env_step(env, obs, act, zeros, info)
             live = ~finished
             if trace:

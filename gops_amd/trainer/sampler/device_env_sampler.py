@@ -22,9 +22,11 @@ data envs' reset distributions (`gops_amd.utils.synthetic.make_batch`), generate
 `pool_factor x n_envs` and uploaded once per pool.
 """
 import time
+import warnings
 
 import torch
 
+from gops_amd.apprfunc.mlp import StochaPolicy
 from gops_amd import hip_backend as hb
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS as _INFO, NOT_RESTATED, draw_reset_pool
 from gops_amd.utils.tensorboard_setup import tb_tags
@@ -44,6 +46,7 @@ class DeviceEnvSampler:
         self.n, self.steps, self.max_steps = n_envs, steps_per_sample, max_episode_steps
         self.device = torch.device(device)
         self.seed, self.pool_factor, self.noise_std = seed, pool_factor, noise_std
+        self._warned_noise = False
         if env_step not in ("data", "model"):
             raise ValueError("env_step must be 'data' (the data environment's step) or 'model' (the env model's)")
         self.data_env = env_step == "data"
@@ -91,11 +94,16 @@ class DeviceEnvSampler:
         chunks = []
         for _ in range(self.steps):
             obs, info = self.obs, self.info
-            act = policy(obs)
-            if self.noise_std > 0.0:
+            act, logp = policy(obs), zeros
+            if isinstance(policy, StochaPolicy):   # the policy's own distribution explores; its log-probability is stored
+                act, logp = policy.get_act_dist(act).sample(generator=self._gen)
+                if self.noise_std > 0.0 and not self._warned_noise:
+                    self._warned_noise = True
+                    warnings.warn("DeviceEnvSampler: noise_std is ignored with a stochastic policy (it samples its own distribution)")
+            elif self.noise_std > 0.0:
                 act = act + self.noise_std * torch.randn(act.shape, generator=self._gen, device=self.device)
             obs2, rew, done, info2 = hb.env_step(self._hip_env(), obs, act.contiguous(), zeros, info)
-            row = dict(obs=obs, act=act, rew=rew, done=done, obs2=obs2, logp=zeros)
+            row = dict(obs=obs, act=act, rew=rew, done=done, obs2=obs2, logp=logp)
             for k in info:
                 row[k], row["next_" + k] = info[k], info2[k]
             chunks.append(row)

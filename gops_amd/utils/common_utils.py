@@ -8,7 +8,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from gops_amd.utils.act_distribution import DiracDistribution
+from gops_amd.utils import act_distribution
+from gops_amd.utils.act_distribution import DiracDistribution, GaussDistribution
 
 _ACTIVATIONS = {"relu": nn.ReLU, "elu": nn.ELU, "gelu": nn.GELU, "selu": nn.SELU,
                 "sigmoid": nn.Sigmoid, "tanh": nn.Tanh, "linear": nn.Identity}
@@ -30,6 +31,9 @@ def get_apprfunc_dict(key: str, **kwargs):
     var["name"] = kwargs[key + "_func_name"]
     var["obs_dim"] = kwargs["obsv_dim"]
     var["pre_horizon"] = kwargs.get("pre_horizon", None)
+    var["min_log_std"] = kwargs.get(key + "_min_log_std", float("-20"))   # (StochaPolicy; reference common_utils.py:63-65)
+    var["max_log_std"] = kwargs.get(key + "_max_log_std", float("2"))
+    var["std_type"] = kwargs.get(key + "_std_type", "mlp_shared")
     apprfunc_type = kwargs[key + "_func_type"]
     if apprfunc_type == "MLP":
         var["hidden_sizes"] = kwargs[key + "_hidden_sizes"]
@@ -56,9 +60,14 @@ def get_apprfunc_dict(key: str, **kwargs):
         var["act_dim"] = kwargs["action_dim"]
     else:
         raise NotImplementedError("discrete actions are outside the MI355X ADP path")
-    if kwargs.get("policy_act_distribution", "default") != "default":
-        raise NotImplementedError("only the default (Dirac) action distribution exists on the ADP path")
-    var["action_distribution_cls"] = DiracDistribution
+    dist = kwargs.get("policy_act_distribution", "default")   # (reference common_utils.py:118-133)
+    if dist == "default":
+        var["action_distribution_cls"] = GaussDistribution if kwargs.get("policy_func_name") == "StochaPolicy" else DiracDistribution
+    elif dist in ("DiracDistribution", "GaussDistribution", "TanhGaussDistribution"):
+        var["action_distribution_cls"] = getattr(act_distribution, dist)
+    else:
+        raise NotImplementedError(f"policy_act_distribution {dist!r}: DiracDistribution, GaussDistribution and TanhGaussDistribution "
+                                  "exist here (discrete actions are outside this path)")
     return var
 
 

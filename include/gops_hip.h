@@ -678,6 +678,80 @@ int gops_ac_backup(const GopsAcBackup* desc, int32_t batch, const float* obs2, c
 int gops_ac_critic_loss(const float* q, const float* backup, const float* weight, int32_t n_q, int32_t batch, float* seed,
                         float* abs_err, float* stats, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): DSAC-T (gops/algorithm/dsact.py; csrc/actor_critic.hip, csrc/dsact.hip).
+ * All fp32, fixed summation order, bitwise reproducible; no kernel waits on another workgroup.
+ *
+ * gops_soft_backup: the whole no-grad target of dsact.py:237-313 in ONE launch, forward only, nothing stashed.  Per batch row:
+ *     (mean, log_std) = policy(obs2)                      the TARGET StochaPolicy's raw stack, 2 * act_dim linear outputs
+ *     u      = mean + exp(clamp(log_std, min_log_std, max_log_std)) * eps_next
+ *     a2     = half * tanh(u) + mid,   half = (act_high - act_low) / 2,  mid = (act_high + act_low) / 2
+ *     logp   = sum_a [Normal(mean, std).log_prob(u) - log(1 + 1e-6 - tanh(u)^2) - log(half)]
+ *     (m_i, s_i) = (q[i]([obs2, a2])[0], softplus(q[i]([obs2, a2])[1]))    softplus with torch's threshold of 20; i = 1, 2
+ *     q_next = min(m_1, m_2);   q_next_sample = m_1 < m_2 ? m_1 + clamp(z_1, -3, 3) s_1 : m_2 + clamp(z_2, -3, 3) s_2
+ *     target_q        = rew + (1 - done) gamma (q_next - alpha logp)
+ *     target_q_sample = rew + (1 - done) gamma (q_next_sample - alpha logp)
+ * eps_next [B, act_dim] and z_next [2, B] are unit-normal draws supplied by the caller.  alpha: `log_alpha` (a device pointer to one
+ * float; the kernel forms exp itself) when it is not NULL, else the double `alpha`.  Tiles, staging and the eight fmaf chains are
+ * gops_ac_backup's; the heads, the squash, the log-probability, softplus, the minimum and the targets are formed in double and rounded
+ * once where they are stored (a2 - the critics' input - included).  One thread per (row, action dimension) forms that dimension's
+ * mean and log std.  Accepted shapes as for gops_ac_backup, with policy: obs_dim -> .. -> 2 * act_dim, q[i]: obs_dim + act_dim -> .. -> 2;
+ * the same return codes and the same 256-byte workspace section.
+ * Outputs: target_q [B], target_q_sample [B]; optional (NULL): a2 [B, act_dim], logp [B], q_targ [2, B, 2] = (m_i, s_i). */
+struct GopsSoftBackup {
+    GopsMlp policy;
+    GopsMlp q[2];
+    float act_low[GOPS_MAX_ACT], act_high[GOPS_MAX_ACT];   /* the policy's act_low_lim / act_high_lim buffers */
+    double min_log_std, max_log_std, gamma, alpha;
+    const float* log_alpha;                                /* device memory, or NULL: use `alpha` */
+};
+typedef struct GopsSoftBackup GopsSoftBackup;
+size_t gops_soft_backup_workspace_bytes(const GopsSoftBackup* desc, int32_t batch);
+int gops_soft_backup(const GopsSoftBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,
+                     const float* eps_next, const float* z_next, float* target_q, float* target_q_sample, float* a2, float* logp,
+                     float* q_targ, void* workspace, size_t workspace_bytes, void* stream);
+/* gops_dsact_critic_loss: the critic losses of dsact.py:243-251, 284-313 and their gradient seeds.  qraw [2, B, 2]: the ONLINE critics'
+ * raw head outputs (q_i, raw_i) on the data, std_i = softplus(raw_i); target_q, target_q_sample [B] from gops_soft_backup.
+ *     state->mean_std[i] <- mean(std_i)                                            first call (state->initialised == 0)
+ *                           (1 - tau_b) state->mean_std[i] + tau_b mean(std_i)     later calls;   rounded to fp32, then used below
+ *     bound_i = q_i + clamp(target_q_sample - q_i, -3 mean_std_i, 3 mean_std_i)
+ *     loss_i  = (mean_std_i^2 + 0.1) mean(-(target_q - q_i) / (std_i^2 + 0.1) q_i - ((q_i - bound_i)^2 - std_i^2) / (std_i^3 + 0.1) std_i)
+ *     seed [2, B, 2] = d(loss_1 + loss_2) / d(q_i, raw_i): q_i and std_i standing alone are live, every other occurrence is detached
+ *                      (the reference's pattern); the raw column carries softplus' derivative sigmoid(raw_i)
+ *     stats[0] = loss_1 + loss_2 (fp32 sum), [1], [2] = mean(q_i), [3], [4] = mean(std_i), [5], [6] = min(std_i),
+ *     stats[7], [8] = mean_std_i, [9], [10] = loss_i
+ * The seeds need the batch mean of std before they can be formed: up to 8192 rows one workgroup does both phases in ONE launch;
+ * larger batches take TWO launches of 64 workgroups (moments and state, then seeds and losses).
+ * `state`: zero before the first update.  `stats`: 8-byte aligned, GOPS_DSACT_STATS_FLOATS floats, ALL ZERO before the first call
+ * (partial sums and a ticket the call leaves zero again, as for gops_ac_critic_loss); otherwise GOPS_ERR_BAD_ARG. */
+struct GopsDsactState {
+    float mean_std[2];
+    uint32_t initialised;
+    uint32_t reserved;
+};
+typedef struct GopsDsactState GopsDsactState;
+#define GOPS_DSACT_STATS_FLOATS 800
+int gops_dsact_critic_loss(const float* qraw, const float* target_q, const float* target_q_sample, int32_t batch, double tau_b,
+                           GopsDsactState* state, float* seed, float* stats, void* stream);
+/* gops_tanh_gauss_forward / _backward: StochaPolicy's sampling head (TanhGaussDistribution.rsample) and its reverse.
+ * head [B, 2 * act_dim] = (mean, log_std) raw, eps [B, act_dim] unit-normal draws:
+ *     act [B, act_dim], logp [B] as a2 / logp of gops_soft_backup;
+ *     stats[0] = mean(logp), [1] = mean(tanh(mean)), [2] = mean(std), [3] = -(mean(logp) + target_entropy) = d loss_alpha / d log_alpha
+ * backward: g_act [B, act_dim], g_logp [B] -> g_head [B, 2 * act_dim]; the log_std column is zero outside [min_log_std, max_log_std].
+ * `stats`: 8-byte aligned, GOPS_TANH_GAUSS_STATS_FLOATS floats, all zero before the first call.  act_dim outside 1 .. GOPS_MAX_ACT,
+ * NULL pointers, batch < 1: GOPS_ERR_BAD_ARG. */
+struct GopsTanhGauss {
+    int32_t act_dim;
+    int32_t reserved;
+    float act_low[GOPS_MAX_ACT], act_high[GOPS_MAX_ACT];
+    double min_log_std, max_log_std;
+};
+typedef struct GopsTanhGauss GopsTanhGauss;
+#define GOPS_TANH_GAUSS_STATS_FLOATS 800
+int gops_tanh_gauss_forward(const GopsTanhGauss* desc, int32_t batch, const float* head, const float* eps, double target_entropy,
+                            float* act, float* logp, float* stats, void* stream);
+int gops_tanh_gauss_backward(const GopsTanhGauss* desc, int32_t batch, const float* head, const float* eps, const float* g_act,
+                             const float* g_logp, float* g_head, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
