@@ -15,12 +15,13 @@
 // soft_backup_kernel: DSAC-T's distributional soft backup (dsact.py:237-313) on the same tile scheme - a tanh-Gaussian target policy
 // (one thread per (row, action dimension) forms that dimension's mean and log std), two critics with (mean, softplus std) heads.
 // ac_critic_loss_kernel: gradient seeds, losses, mean(q) and |q - backup| of the critic regression in one launch; sums in double
-// in a fixed order (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
+// in the fixed order of block_reduce.h (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
 
+#include "block_reduce.h"
 #include "launchers.h"
 
 namespace {
@@ -379,78 +380,39 @@ size_t soft_choose(const GopsSoftBackup& d, int B, AcParams& p, int& R) {
 constexpr int ACL_BLOCKS = 64;
 constexpr int ACL_ONE_BLOCK_MAX = 8192;
 
-// (s0, s1, s2) summed over the block in a fixed order: butterfly inside each wave, then the four waves in index order
-__device__ __forceinline__ void block_sum3(double& s0, double& s1, double& s2, double (*red)[4]) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s0 += __shfl_xor(s0, o);
-        s1 += __shfl_xor(s1, o);
-        s2 += __shfl_xor(s2, o);
-    }
-    __syncthreads();   // (red may still be read by a previous call)
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s0; red[1][threadIdx.x >> 6] = s1; red[2][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    s0 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    s1 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    s2 = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-}
-
-__device__ __forceinline__ void acl_finish(double s0, double s1, double s2, int B, float* __restrict__ stats) {
-    const float l0 = (float)(s0 / (double)B), l1 = (float)(s1 / (double)B);
-    stats[0] = l0;
-    stats[1] = l1;
-    stats[2] = (float)(s2 / (double)B);
-    stats[3] = l0 + l1;
-}
-
 __global__ __launch_bounds__(256) void ac_critic_loss_kernel(const float* __restrict__ q, const float* __restrict__ backup,
                                                              const float* __restrict__ weight, int nq, int B, float gsc,
                                                              float* __restrict__ seed, float* __restrict__ abs_err,
                                                              float* __restrict__ stats) {
     __shared__ double red[3][4];
     __shared__ bool last;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;   // sum w d0^2, sum w d1^2, sum q0
+    double s[3] = {0.0, 0.0, 0.0};   // sum w d0^2, sum w d1^2, sum q0
     for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256) {
         const float bk = backup[i], q0 = q[i];
         const float d0 = q0 - bk;
         const float w = weight != nullptr ? weight[i] : 1.f;
         seed[i] = weight != nullptr ? gsc * (w * d0) : gsc * d0;
-        s0 += (double)(weight != nullptr ? w * (d0 * d0) : d0 * d0);
-        s2 += (double)q0;
+        s[0] += (double)(weight != nullptr ? w * (d0 * d0) : d0 * d0);
+        s[2] += (double)q0;
         if (abs_err != nullptr) abs_err[i] = fabsf(d0);
         if (nq == 2) {
             const float d1 = q[(size_t)B + i] - bk;
             seed[(size_t)B + i] = weight != nullptr ? gsc * (w * d1) : gsc * d1;
-            s1 += (double)(weight != nullptr ? w * (d1 * d1) : d1 * d1);
+            s[1] += (double)(weight != nullptr ? w * (d1 * d1) : d1 * d1);
         }
     }
-    block_sum3(s0, s1, s2, red);
-    if (gridDim.x == 1) {
-        if (threadIdx.x == 0) acl_finish(s0, s1, s2, B, stats);
-        return;
+    block_fold<3, false>(s, red);
+    bool fin = gridDim.x == 1;
+    if (!fin) {   // the blocks' partial sums [ACL_BLOCKS][3] behind the four results, then the ticket
+        fin = last_block<3>(s, reinterpret_cast<double*>(stats + 4), 3, reinterpret_cast<unsigned*>(stats + 4 + 6 * ACL_BLOCKS), &last);
+        if (fin) block_fold<3, false>(s, red);
     }
-    double* part = reinterpret_cast<double*>(stats + 4);   // [ACL_BLOCKS][3]
-    unsigned* ticket = reinterpret_cast<unsigned*>(stats + 4 + 6 * ACL_BLOCKS);
-    if (threadIdx.x == 0) {
-        part[3 * blockIdx.x] = s0;
-        part[3 * blockIdx.x + 1] = s1;
-        part[3 * blockIdx.x + 2] = s2;
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (last) {
-        __threadfence();
-        const volatile double* vp = part;
-        const bool has = threadIdx.x < gridDim.x;
-        s0 = has ? vp[3 * threadIdx.x] : 0.0;
-        s1 = has ? vp[3 * threadIdx.x + 1] : 0.0;
-        s2 = has ? vp[3 * threadIdx.x + 2] : 0.0;
-        block_sum3(s0, s1, s2, red);
-        if (threadIdx.x == 0) {
-            acl_finish(s0, s1, s2, B, stats);
-            *ticket = 0u;
-        }
+    if (fin && threadIdx.x == 0) {
+        const float l0 = (float)(s[0] / (double)B), l1 = (float)(s[1] / (double)B);
+        stats[0] = l0;
+        stats[1] = l1;
+        stats[2] = (float)(s[2] / (double)B);
+        stats[3] = l0 + l1;
     }
 }
 static_assert(4 + 6 * ACL_BLOCKS + 1 <= GOPS_AC_LOSS_STATS_FLOATS, "stats: four results, the blocks' partial sums, the ticket");

@@ -12,7 +12,7 @@
 
 #define TB GOPS_TILE      // trajectories per workgroup tile = MFMA M
 #define NTHREADS 256      // 4 wavefronts of 64
-#define DW_SC 32          // samples per K-block of the fp32 dW GEMMs: the unit split-K is counted in (aux_kernels.hip)
+#define DW_SC 32          // samples per K-block of the fp32 dW GEMMs: the unit split-K is counted in (dw_gemm.hip)
 #define DWH_SC 64         // ... per staged chunk of the half-precision one
 #define DW_OUT_SPLITS 1024  // sample splits of the output-layer weight gradient
 #define H64_W0_COLS 8     // policy inputs up to which the 64-row half sweep forms layer 0's weight gradient itself (rollout_h64.hip)
@@ -234,6 +234,35 @@ __device__ __forceinline__ void adam_snapshot(GopsAdamState* st, float* snap, do
 // answer a half-range overflow with NaN gradients on purpose (a loud failure instead of a wrong number); without this gate one
 // such update would write NaN into every weight and target before the host - which reads losses lazily - could react.
 __device__ __forceinline__ bool grad_is_finite(float g) { return (__float_as_uint(g) & 0x7f800000u) != 0x7f800000u; }
+
+// One rounding per operation, never fused: HIP's __fmul_rn / __fadd_rn are plain `a * b` / `a + b`, which hipcc's default
+// -ffp-contract=fast-honor-pragmas may contract into an fma with a neighbour - whether it did depended on unrelated codegen
+// (round 4: building without packed-fp32 instructions moved 4 more of the 48 appended headings of the step fixture by ~1e-3).
+// The reference (torch CPU) rounds every product and sum separately.
+__device__ __forceinline__ float rn_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float rn_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float rn_sub(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// One element's Adam step: the fused tail of reduce_partials_kernel (dw_gemm.hip) calls it, adam_kernel (optim.hip) restates it (the
+// call costs that kernel two registers and a wave of occupancy); the tests hold the two bit-equal.  gi = the scaled, finite gradient (the callers gate and count the others); step_size, bc2_sqrt =
+// adam_snapshot's factors, omb1 = 1 - beta1, omb2 = 1 - beta2, b2 = beta2 rounded to fp32.  m, v, p leave as the new values.
+__device__ __forceinline__ void adam_element(float gi, float& m, float& v, float& p, float step_size, float bc2_sqrt, float omb1,
+                                             float omb2, float b2, float eps) {
+    m = m + (gi - m) * omb1;
+    v = v * b2 + omb2 * gi * gi;
+    p = p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
+}
+// One element of the Polyak average t (1 - tau) + tau p, with the roundings of the two torch passes it replaces (polyak_kernel)
+__device__ __forceinline__ float polyak_element(float t, float p, float omt, float tau) { return rn_add(rn_mul(t, omt), rn_mul(tau, p)); }
 
 // upload_params_kernel / prologue_kernel take the block BY VALUE: it has to fit the 4 KiB kernel-argument segment
 static_assert(sizeof(RolloutParams) <= 4000, "RolloutParams outgrew the kernel-argument segment (move gpow[] out)");

@@ -8,10 +8,11 @@
 //   draws the last ticket.  Nothing waits on another workgroup.
 // tanh_gauss_fwd_kernel / tanh_gauss_bwd_kernel: StochaPolicy's sampling head - clamp, exp, u = mean + std eps, tanh squash,
 //   log-probability - and its reverse, one thread per row; the forward reduces mean(logp), mean(tanh(mean)) and mean(std).
-// Every value is formed in double from the fp32 inputs and rounded once where it is stored; sums are doubles in a fixed order
-// (butterfly inside a wave, waves in index order, blocks in index order) that depends on B only.
+// Every value is formed in double from the fp32 inputs and rounded once where it is stored; sums are doubles in the fixed order of
+// block_reduce.h, which depends on B only.
 #include <stdint.h>
 
+#include "block_reduce.h"
 #include "launchers.h"
 
 namespace {
@@ -20,47 +21,6 @@ constexpr int DS_BLOCKS = 64;
 constexpr int DS_ONE_BLOCK_MAX = 8192;
 constexpr int DS_RESULTS = 16;   // floats in front of the partial sums
 constexpr int DS_PART = 6;       // doubles per block
-
-template <int N, bool MIN>
-__device__ __forceinline__ void block_fold(double (&s)[N], double (*red)[4]) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const double t = __shfl_xor(s[i], o);
-            s[i] = MIN ? fmin(s[i], t) : s[i] + t;
-        }
-    }
-    __syncthreads();   // (red may still be read by a previous call)
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) red[i][threadIdx.x >> 6] = s[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        s[i] = MIN ? fmin(fmin(red[i][0], red[i][1]), fmin(red[i][2], red[i][3])) : (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
-}
-
-// Publishes this block's partial values and draws a ticket; true in every thread of the block that drew the last one, which then
-// holds in `v` the blocks' values of slot threadIdx.x (`fill` where there is no such block) and has left the ticket zero.
-template <int N>
-__device__ __forceinline__ bool last_block(double (&v)[N], double fill_from, double* part, unsigned* ticket, bool* last) {
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) part[DS_PART * blockIdx.x + i] = v[i];
-        __threadfence();
-        *last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!*last) return false;
-    __threadfence();
-    const volatile double* vp = part;
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = threadIdx.x < gridDim.x ? vp[DS_PART * threadIdx.x + i] : fill_from;
-    if (threadIdx.x == 0) *ticket = 0u;
-    return true;
-}
 
 __device__ __forceinline__ double softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }   // (torch's threshold)
 __device__ __forceinline__ double softplus_grad_d(double x) { return x > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-x)); }
@@ -88,7 +48,7 @@ __global__ __launch_bounds__(256) void dsact_loss_kernel(const float* __restrict
         bool fin = gridDim.x == 1;
         if (!fin) {
             double v[6] = {s[0], s[1], s[2], s[3], mn[0], mn[1]};
-            fin = last_block<6>(v, 0.0, part, ticket, &last);
+            fin = last_block<6>(v, part, DS_PART, ticket, &last);
             if (fin) {
                 double vs[4] = {v[0], v[1], v[2], v[3]};
                 double vm[2] = {threadIdx.x < gridDim.x ? v[4] : INFINITY, threadIdx.x < gridDim.x ? v[5] : INFINITY};
@@ -136,7 +96,7 @@ __global__ __launch_bounds__(256) void dsact_loss_kernel(const float* __restrict
     block_fold<2, false>(l, red);
     bool fin = gridDim.x == 1;
     if (!fin) {
-        fin = last_block<2>(l, 0.0, part, ticket, &last);
+        fin = last_block<2>(l, part, DS_PART, ticket, &last);
         if (fin) block_fold<2, false>(l, red);
     }
     if (fin && threadIdx.x == 0) {
@@ -178,7 +138,7 @@ __global__ __launch_bounds__(256) void tanh_gauss_fwd_kernel(const TgParams p, c
     bool fin = gridDim.x == 1;
     if (!fin) {
         double* part = reinterpret_cast<double*>(stats + 4);   // [DS_BLOCKS][DS_PART]
-        fin = last_block<3>(s, 0.0, part, reinterpret_cast<unsigned*>(stats + 4 + 2 * DS_PART * DS_BLOCKS), &last);
+        fin = last_block<3>(s, part, DS_PART, reinterpret_cast<unsigned*>(stats + 4 + 2 * DS_PART * DS_BLOCKS), &last);
         if (fin) block_fold<3, false>(s, red);
     }
     if (fin && threadIdx.x == 0) {

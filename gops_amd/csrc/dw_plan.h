@@ -1,7 +1,7 @@
 // The weight-gradient stage of a backward call (host only): per Linear layer ONE record - DwLayer - that says which kernel
 // forms the layer's split-K partial slabs, on which grid, and how the reduce launch reads them.  plan_dw fills what the
 // workspace carve needs (api.hip build_plan / plan_mlp keep the record in their plan), choose_dw_* add what a call decides;
-// launch_dw and add_reduce_jobs read the record and nothing else.  The functions live next to the kernels (aux_kernels.hip).
+// launch_dw and add_reduce_jobs read the record and nothing else.  The functions live next to the kernels (dw_gemm.hip).
 #pragma once
 #include "common.h"
 

@@ -1,5 +1,5 @@
-// The single wrapped env step (one trajectory) and the reference-trajectory generator it evaluates: shared by
-// env_step_kernel (aux_kernels.hip, gops_env_step) and the episode kernel (rollout_episode.hip, gops_episode_rollout), so that
+// The single wrapped env step (one trajectory) and the reference-trajectory generator it evaluates (which the reference table of
+// prologue.hip evaluates too): shared by env_step_kernel (aux_kernels.hip, gops_env_step) and the episode kernel (rollout_episode.hip, gops_episode_rollout), so that
 // both step the SAME arithmetic, statement for statement.
 #pragma once
 #include "common.h"
@@ -16,22 +16,7 @@
 // number of points where a 1-ulp difference in x(t) is amplified ~1e3x by the finite difference.
 #define SINF_CR(x) ((float)sin((double)(x)))
 #define COSF_CR(x) ((float)cos((double)(x)))
-// One rounding per operation, never fused: HIP's __fmul_rn / __fadd_rn are plain `a * b` / `a + b`, which hipcc's default
-// -ffp-contract=fast-honor-pragmas may contract into an fma with a neighbour - whether it did depended on unrelated codegen
-// (round 4: building without packed-fp32 instructions moved 4 more of the 48 appended headings of the step fixture by ~1e-3).
-// The reference (torch CPU) rounds every product and sum separately.
-__device__ __forceinline__ float rn_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float rn_add(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float rn_sub(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
+// One rounding per operation, never fused (common.h rn_mul / rn_add / rn_sub)
 #define RMUL(a, b) rn_mul((a), (b))
 #define RADD(a, b) rn_add((a), (b))
 #define RSUB(a, b) rn_sub((a), (b))

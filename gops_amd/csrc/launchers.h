@@ -1,22 +1,28 @@
-// Host entry points of aux_kernels.hip and rollout_poly.hip as api.hip calls them: included by both sides, so that a
+// Host entry points of every kernel source but the rollout kernels' as api.hip calls them: included by both sides, so that a
 // signature is written once.  (The rollout kernels' launchers: rollout_choice.h.)
 #pragma once
 #include "common.h"
 #include "dw_plan.h"
 
-// ---- aux_kernels.hip ----
+// ---- prologue.hip: parameter upload, weight packing, reference tables ----
 hipError_t launch_upload_params(const RolloutParams& p, RolloutParams* dst, hipStream_t s);
 hipError_t launch_prologue(const RolloutParams& p, RolloutParams* dst, int P, float pdt, hipStream_t s);
-hipError_t launch_linear_out_fwd(const float* h, int K, const float* Wo, const float* bo, int W, int B, float* y, hipStream_t s);
-hipError_t launch_linear_out_bwd(const float* gy, int W, int Wp, const float* Wo, int K, int B, long long S, float* gh,
-                                 float* gyp, hipStream_t s);
+
+// ---- dw_gemm.hip: the weight-gradient stage (its record and launch_dw: dw_plan.h) ----
 hipError_t launch_reduce(const ReduceJobs& jobs, hipStream_t s);
-hipError_t launch_fill_zero(float* p, size_t n, hipStream_t s);
-hipError_t launch_env_step(const GopsEnv& env, int B, const GopsStepIO& io, float pdt, hipStream_t s);
-hipError_t launch_env_constraint(const GopsEnv& env, int B, const GopsStepIO& io, hipStream_t s);
+
+// ---- optim.hip: Adam, Polyak averaging, loss scalars ----
 hipError_t launch_polyak(const GopsAdamTensors& T, float omt, float tau, hipStream_t s);
 hipError_t launch_batch_loss(const float* a, const float* b, int n, float gsc, float sc0, float* grad, float* stats, hipStream_t s);
 hipError_t launch_adam(const GopsAdamTensors& T, GopsAdamState* st, double beta1, double beta2, float eps, hipStream_t s);
+
+// ---- aux_kernels.hip: any-width output layer, zero fill, single env step / constraint ----
+hipError_t launch_linear_out_fwd(const float* h, int K, const float* Wo, const float* bo, int W, int B, float* y, hipStream_t s);
+hipError_t launch_linear_out_bwd(const float* gy, int W, int Wp, const float* Wo, int K, int B, long long S, float* gh,
+                                 float* gyp, hipStream_t s);
+hipError_t launch_fill_zero(float* p, size_t n, hipStream_t s);
+hipError_t launch_env_step(const GopsEnv& env, int B, const GopsStepIO& io, float pdt, hipStream_t s);
+hipError_t launch_env_constraint(const GopsEnv& env, int B, const GopsStepIO& io, hipStream_t s);
 
 // ---- rollout_poly.hip: POLY approximators, one lane per trajectory ----
 size_t poly_rollout_workspace_bytes(const GopsRolloutDesc& d);

@@ -13,7 +13,7 @@
 //   poly_bwd_kernel   the same lane walks the horizon backwards: model adjoints recomputed from the stashed observation (the
 //                     idpendulum sub-steps included), wrap_action_bwd, g_phi = W^T g_a, g_x += (d phi / d x)^T g_phi; dW += g_a phi
 //                     in registers; per-block partial rows in a fixed order (wave butterfly, then the four waves in order).
-//   reduce_partials_kernel (aux_kernels.hip) sums the blocks' rows in a fixed order: the gradient is bitwise reproducible.
+//   reduce_partials_kernel (dw_gemm.hip) sums the blocks' rows in a fixed order: the gradient is bitwise reproducible.
 //
 // Instantiated per (env kind, obs_dim N, degree): each kernel carries only its own model's arithmetic.
 // Bounds (template parameters, everything else is refused by the host code with GOPS_ERR_UNSUPPORTED): obs_dim N <= 6;

@@ -3,7 +3,7 @@ reference paths; state (y, phi, v, omega), action steer, obs = (y - y_ref0, phi 
 y - y_ref_P), info["ref_points"] [P+1, 2] = (y, phi) (reference:
 gops/env/env_ocp/env_model/pyth_veh2dofconti_model.py:24-174, vehicle parameters gops/env/env_ocp/pyth_veh2dofconti.py:24-34
 - the model of fhadp_mlp_veh2dofconti_serial.py / infadp_mlp_veh2dofconti_offserial.py).  Arithmetic in csrc/env_models.h
-(veh2_f_xu, veh2_reward) and csrc/aux_kernels.hip (ref_point)."""
+(veh2_f_xu, veh2_reward) and csrc/env_step.h (ref_point)."""
 from typing import Dict, Optional, Union
 
 import numpy as np

@@ -2,7 +2,7 @@
 of 2 speed profiles; obs = ego-frame errors of P+1 preview points (reference:
 gops/env/env_ocp/env_model/pyth_veh3dofconti_model.py:64-210,
 gops/env/env_ocp/resources/ref_traj_model.py).  Arithmetic in csrc/env_models.h (veh_f_xu,
-veh_reward) and csrc/aux_kernels.hip (ref_point)."""
+veh_reward) and csrc/env_step.h (ref_point)."""
 from typing import Dict, Optional, Union
 
 import numpy as np

@@ -3,7 +3,7 @@
 Why this exists.  Every rollout step of these models appends one reference point (x, y, phi, u)(t) to the preview window
 (gops/env/env_ocp/env_model/pyth_veh3dofconti_model.py:108-129), and its heading is a 1 ms finite difference evaluated in
 fp32 (gops/env/env_ocp/resources/ref_traj_model.py:144-148): `atan2(y(t + 0.001) - y(t), x(t + 0.001) - x(t))`.  The difference
-amplifies the LAST BIT of `torch.sin` / `torch.cos` ~1e3 times.  The kernels (csrc/aux_kernels.hip `ref_point`) round every
+amplifies the LAST BIT of `torch.sin` / `torch.cos` ~1e3 times.  The kernels (csrc/env_step.h `ref_point`) round every
 product and sum like the reference, but evaluate sin / cos correctly rounded; the reference's values come from the vector math
 library behind `torch.sin` on the host (MKL VML in high-accuracy mode for contiguous fp32 tensors: faithfully, not always
 correctly, rounded; closed source), so ~5 % of the sines differ by one ulp and up to 8 of 48 appended headings of a step move

@@ -2,7 +2,7 @@
 
 The reference builds `MultiRefTrajModel(path_para, u_para)` (gops/env/env_ocp/resources/ref_traj_model.py:26-52): the
 caller's dicts update the default parameter set (ref_traj_data.py:18-37) per path / speed profile.  The arithmetic of the
-trajectories lives in csrc/aux_kernels.hip (`ref_point`); what crosses the C ABI is `GopsEnv.ref_c`, the table of
+trajectories lives in csrc/env_step.h (`ref_point`); what crosses the C ABI is `GopsEnv.ref_c`, the table of
 constants this module folds - in double, at exactly the places where the reference multiplies Python scalars before
 they meet an fp32 tensor (e.g. `-self.A / self.omega * torch.cos(...)`, ref_traj_model.py:119-124).
 """

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / spill / LDS / occupancy summary of the gfx950 kernels of one source file (recompiles it with
-# -Rpass-analysis=kernel-resource-usage, device side only):   tools/kernel_regs.sh aux_kernels.hip [name filter]
+# -Rpass-analysis=kernel-resource-usage, device side only):   tools/kernel_regs.sh dw_gemm.hip [name filter]
 src=${1:?source file under gops_amd/csrc}; pat=${2:-.}
 cd "$(dirname "$0")/../gops_amd/csrc" || exit 1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -I../../include -Xclang -target-feature -Xclang -packed-fp32-ops ${EXTRA} --cuda-device-only -c "$src" -o /dev/null \
