@@ -911,6 +911,20 @@ int gops_rollout_variant(const GopsRolloutDesc* desc) {
     }
 }
 
+int gops_dw_plan_query(int32_t N, int32_t K, int32_t Kp, int64_t S, int32_t f16, int32_t scaled, uint32_t vflags,
+                       int32_t dw_workgroups, int32_t out[4]) {
+    static_assert((int)DwKernel::None == GOPS_DW_NONE && (int)DwKernel::Spec == GOPS_DW_SPEC && (int)DwKernel::RingH2 == GOPS_DW_RING_H2 &&
+                  (int)DwKernel::RingExact == GOPS_DW_RING_EXACT && (int)DwKernel::Skinny == GOPS_DW_SKINNY &&
+                  (int)DwKernel::Fm4Bf3 == GOPS_DW_FM4_BF3 && (int)DwKernel::Fm4F32 == GOPS_DW_FM4_F32 &&
+                  (int)DwKernel::Fm2Bf3 == GOPS_DW_FM2_BF3 && (int)DwKernel::Fm2F32 == GOPS_DW_FM2_F32 && (int)DwKernel::F16 == GOPS_DW_F16,
+                  "gops_hip.h GOPS_DW_* are DwKernel's values");
+    if (out == nullptr || N < 1 || K < 1 || Kp < K || (Kp & 15) || S < 1 || (vflags & ~GOPS_VF_ALL)) return GOPS_ERR_BAD_ARG;
+    DwLayer L = plan_dw(N, K, Kp, S, f16 != 0, dw_workgroups);
+    choose_dw_gemm(L, f16 != 0, scaled != 0, vflags);
+    out[0] = (int)L.kernel, out[1] = L.splits, out[2] = L.chunks_per_split, out[3] = L.grid;
+    return GOPS_OK;
+}
+
 int gops_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const GopsRolloutOut* out,
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!desc || !in || !out) return GOPS_ERR_BAD_ARG;

@@ -38,25 +38,34 @@ __global__ __launch_bounds__(256) void linear_out_fwd_kernel(const float* __rest
 }
 
 // g_h stays row-major [S][K] (rollout_bwd reads it as `ext_delta`); g_yp is the FM delta operand [S/16][Wp][16]
+// The 16 rows of g_y are staged LOB_WC columns at a time (64 KiB, the dynamic LDS a launch gets without asking): an output layer
+// of up to LOB_WC padded columns takes one pass - [16][Wp], as before - and a wider one (plan_mlp admits W <= 4096) continues
+// each g_h sum from the value the pass before stored, i.e. in the same order as one long loop (one more read and write of g_h per
+// pass, which has not been timed).
+constexpr int LOB_WC = 1024;
 __global__ __launch_bounds__(256) void linear_out_bwd_kernel(const float* __restrict__ gy, int W, int Wp, const float* __restrict__ Wo,
                                                              int K, int B, long long S, float* __restrict__ gh, float* __restrict__ gyp) {
-    extern __shared__ __attribute__((aligned(16))) float gs[];   // [16][Wp]
+    extern __shared__ __attribute__((aligned(16))) float gs[];   // [16][min(Wp, LOB_WC)]
     const long long s0 = (long long)blockIdx.x * 16;
-    for (int i = threadIdx.x; i < 16 * Wp; i += 256) {
-        const int m = i / Wp, w = i - m * Wp;
-        gs[i] = (s0 + m < B && w < W) ? gy[(size_t)(s0 + m) * W + w] : 0.f;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 16 * Wp; i += 256) {   // i = w * 16 + m: the FM tile in memory order
-        const int w = i >> 4, m = i & 15;
-        gyp[(size_t)blockIdx.x * 16 * Wp + i] = gs[m * Wp + w];
-    }
-    for (int o = threadIdx.x; o < 16 * K; o += 256) {   // o = m * K + k: coalesced reads of Wo rows and writes of g_h
-        const int m = o / K, k = o - m * K;
-        if (s0 + m >= S) continue;
-        float acc = 0.f;
-        for (int w = 0; w < W; ++w) acc += gs[m * Wp + w] * Wo[(size_t)w * K + k];
-        gh[(size_t)(s0 + m) * K + k] = acc;
+    for (int w0 = 0; w0 < Wp; w0 += LOB_WC) {
+        const int wc = min(LOB_WC, Wp - w0), wlive = min(wc, W - w0);   // staged columns (a multiple of 16) / those that exist
+        if (w0 > 0) __syncthreads();
+        for (int i = threadIdx.x; i < 16 * wc; i += 256) {
+            const int m = i / wc, w = i - m * wc;
+            gs[i] = (s0 + m < B && w0 + w < W) ? gy[(size_t)(s0 + m) * W + w0 + w] : 0.f;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 16 * wc; i += 256) {   // i = w * 16 + m: the FM tile in memory order
+            const int w = i >> 4, m = i & 15;
+            gyp[(size_t)blockIdx.x * 16 * Wp + (size_t)w0 * 16 + i] = gs[m * wc + w];
+        }
+        for (int o = threadIdx.x; o < 16 * K; o += 256) {   // o = m * K + k: coalesced reads of Wo rows and writes of g_h
+            const int m = o / K, k = o - m * K;
+            if (s0 + m >= S) continue;
+            float acc = w0 > 0 ? gh[(size_t)(s0 + m) * K + k] : 0.f;
+            for (int w = 0; w < wlive; ++w) acc += gs[m * wc + w] * Wo[(size_t)(w0 + w) * K + k];
+            gh[(size_t)(s0 + m) * K + k] = acc;
+        }
     }
 }
 
@@ -67,7 +76,7 @@ hipError_t launch_linear_out_fwd(const float* h, int K, const float* Wo, const f
 
 hipError_t launch_linear_out_bwd(const float* gy, int W, int Wp, const float* Wo, int K, int B, long long S, float* gh,
                                  float* gyp, hipStream_t s) {
-    hipLaunchKernelGGL(linear_out_bwd_kernel, dim3((unsigned)((S + 15) / 16)), dim3(256), 16 * Wp * sizeof(float), s, gy, W, Wp, Wo,
+    hipLaunchKernelGGL(linear_out_bwd_kernel, dim3((unsigned)((S + 15) / 16)), dim3(256), 16 * (size_t)std::min(Wp, LOB_WC) * sizeof(float), s, gy, W, Wp, Wo,
                        K, B, S, gh, gyp);
     return hipGetLastError();
 }

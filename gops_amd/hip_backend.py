@@ -93,6 +93,9 @@ VF_STREAMED_FP32, VF_SPLIT_TAIL_MULTI, VF_NO_NARROW_LDS, VF_NO_NARROW_N64 = 0x10
 VF_DW_EXACT, VF_DW_F32, VF_DW_NO_GUARD = 0x10000, 0x20000, 0x40000
 VF_BWD_PHASE_A, VF_BWD_PHASE_B, VF_NO_FUSED_DW0 = 0x1000000, 0x2000000, 0x4000000   # a backward in two halves (overlapped gradient all-reduce, trainer/grad_sync.py)
 DEFAULT_VARIANT_FLAGS = 0
+# gops_dw_plan_query's kernel ids (include/gops_hip.h GOPS_DW_*: csrc/dw_plan.h DwKernel)
+(DW_NONE, DW_SPEC, DW_RING_H2, DW_RING_EXACT, DW_SKINNY, DW_FM4_BF3, DW_FM4_F32, DW_FM2_BF3, DW_FM2_F32, DW_F16) = range(10)
+DW_KERNEL_NAMES = ("None", "Spec", "RingH2", "RingExact", "Skinny", "Fm4Bf3", "Fm4F32", "Fm2Bf3", "Fm2F32", "F16")
 
 
 class GopsRolloutIn(C.Structure):
@@ -180,6 +183,7 @@ def _signatures():
         "gops_rollout_backward_open_loop_adj": (rc, [desc, rin, vp, vp, adj, vp, sz, vp]),
         "gops_rollout_backward_update": (rc, [desc, rin, vp, grad, tail, vp, sz, vp]),
         "gops_rollout_variant": (rc, [desc]),
+        "gops_dw_plan_query": (rc, [i32, i32, i32, C.c_int64, i32, i32, C.c_uint32, i32, P(i32)]),
         "gops_env_step": (rc, [env, i32, io, vp]),
         "gops_env_constraint": (rc, [env, i32, io, vp]),
         "gops_value_workspace_bytes": (sz, [mlp, i32]),
@@ -244,6 +248,16 @@ def lib() -> C.CDLL:
                 fn.argtypes = argtypes
         _lib = l
     return _lib
+
+
+def dw_plan_query(N: int, K: int, S: int, *, Kp: Optional[int] = None, f16=False, scaled=False, vflags: int = 0,
+                  dw_workgroups: int = 0) -> Dict[str, int]:
+    """`gops_dw_plan_query` (host only): the kernel (DW_*), split-K slabs, chunks per slab and launched grid of one layer's
+    weight-gradient GEMM dW[N][K] over S stash rows."""
+    out = (C.c_int32 * 4)()
+    kp = (K + 15) // 16 * 16 if Kp is None else Kp
+    check(lib().gops_dw_plan_query(N, K, kp, S, int(bool(f16)), int(bool(scaled)), vflags, dw_workgroups, out), "gops_dw_plan_query")
+    return dict(kernel=out[0], splits=out[1], chunks_per_split=out[2], grid=out[3])
 
 
 _ERR = {-1: "GOPS_ERR_BAD_ARG", -2: "GOPS_ERR_UNSUPPORTED", -3: "GOPS_ERR_WORKSPACE"}

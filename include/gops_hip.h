@@ -797,6 +797,18 @@ int gops_tanh_gauss_backward(const GopsTanhGauss* desc, int32_t batch, const flo
 #define GOPS_VARIANT_HALF_TILE64 8   /* ABI v10: GOPS_DTYPE_F16 on the 64-trajectory-tile kernels (GOPS_ENV_LQ / _NONE, 256-wide nets) */
 int gops_rollout_variant(const GopsRolloutDesc* desc);
 
+/* Which kernel the weight-gradient stage runs for ONE layer (host only: no launch, no device; for tests): dW[N][K] =
+ * delta^T * input over S stash rows (S = samples padded to whole 16-row tiles, times the horizon), Kp = K padded to 16.
+ *   f16: GOPS_DTYPE_F16 stash;  scaled: the launch has a delta scale (grad_v is the backward call's one gradient source - the
+ *   hidden layers of gops_value_backward / gops_rollout_backward; 0 for gops_mlp_backward);  vflags: GOPS_VF_DW_* bits;
+ *   dw_workgroups: GopsRolloutDesc.dw_workgroups (0 = default; gops_mlp_backward's output layer always plans with 0).
+ * out = {kernel (GOPS_DW_*), split-K slabs, 32-sample chunks per slab (64-sample for f16), launched workgroups - the grid
+ * comes in whole groups of 8 slabs, the surplus workgroups return at once}.  GOPS_OK or GOPS_ERR_BAD_ARG. */
+enum { GOPS_DW_NONE = 0, GOPS_DW_SPEC = 1, GOPS_DW_RING_H2 = 2, GOPS_DW_RING_EXACT = 3, GOPS_DW_SKINNY = 4, GOPS_DW_FM4_BF3 = 5,
+       GOPS_DW_FM4_F32 = 6, GOPS_DW_FM2_BF3 = 7, GOPS_DW_FM2_F32 = 8, GOPS_DW_F16 = 9 };
+int gops_dw_plan_query(int32_t N, int32_t K, int32_t Kp, int64_t S, int32_t f16, int32_t scaled, uint32_t vflags,
+                       int32_t dw_workgroups, int32_t out[4]);
+
 /* Timing hook for bench.py: average duration in ms of the named internal kernel over the
  * launches recorded since the last reset (HIP events on the launch stream).  kernel ids:
  * 0 = forward rollout, 1 = backward sweep, 2 = weight-gradient GEMMs (+ reduce) of gops_rollout_*;

@@ -1480,3 +1480,29 @@ def test_weight_gradient_plan_matches_the_recorded_table():
     bad = [(row, got, want) for row, want in zip(grid, rows) for got in [dw_plan_bytes(lib, row)] if got != want]
     assert not bad, bad[:5]
     assert sum(1 for r in rows if r > 0) >= 200
+
+
+def test_dw_exact_case_table_plans():
+    """gops_dw_plan_query (host only: plan_dw + choose_dw_gemm, no device) pins the kernel, split count and chunks per split of
+    every case of the weight-gradient stage's per-element tests (dw_helpers.CASES / test_dw_exact_gpu.py).  A change to the
+    planner is answered here: a case that silently moved to another kernel would no longer test the one it is named after."""
+    import dw_helpers as dh
+    from gops_amd import hip_backend as hb
+    assert len(dh.CASES) == 73
+    for name, c in list(dh.CASES.items()) + list(dh.F16_CASES.items()) + [("saturated", dh.SATURATED)]:
+        plan = dh.layer_plan(c["api"], c["sizes"], c["B"], c["layer"], c["flags"], c.get("f16", False))
+        assert (hb.DW_KERNEL_NAMES[plan["kernel"]], plan["splits"], plan["chunks_per_split"]) == (c["kernel"], c["splits"], c["chunks"]), (name, plan)
+    q = hb.dw_plan_query
+    # the grid comes in whole groups of 8 splits per tile: 7 splits on 32 x 2 tiles launch 512 workgroups, 64 of which return at once
+    assert q(4096, 256, 640) == dict(kernel=hb.DW_RING_EXACT, splits=7, chunks_per_split=3, grid=512)
+    assert q(256, 256, 272, scaled=True) == dict(kernel=hb.DW_SPEC, splits=9, chunks_per_split=1, grid=32)       # 256 x 128 tiles
+    assert q(256, 256, 272, scaled=True, vflags=hb.VF_DW_EXACT)["kernel"] == hb.DW_RING_EXACT
+    assert q(256, 256, 272)["kernel"] == hb.DW_RING_EXACT and q(384, 384, 272, scaled=True)["kernel"] == hb.DW_RING_H2
+    assert q(272, 256, 272)["kernel"] == hb.DW_FM4_BF3 and q(256, 136, 272)["kernel"] == hb.DW_RING_EXACT and q(256, 112, 272)["kernel"] == hb.DW_FM2_BF3
+    assert q(48, 16, 272)["kernel"] == hb.DW_SKINNY and q(48, 16, 272, vflags=hb.VF_DW_F32)["kernel"] == hb.DW_FM2_F32
+    assert q(256, 256, 4096, f16=True) == dict(kernel=hb.DW_F16, splits=64, chunks_per_split=1, grid=256)   # 64-sample chunks
+    assert q(256, 256, 1 << 20, dw_workgroups=64)["splits"] == 16 and q(256, 256, 1 << 20)["splits"] == 128
+    out = (ctypes.c_int32 * 4)()
+    for bad in ((0, 16, 16, 16), (16, 16, 20, 16), (16, 32, 16, 16), (16, 16, 16, 0)):   # N < 1, Kp not padded, Kp < K, no samples
+        assert hb.lib().gops_dw_plan_query(*bad, 0, 0, 0, 0, out) == -1
+    assert hb.lib().gops_dw_plan_query(16, 16, 16, 16, 0, 0, 0x20, 0, out) == -1   # a retired variant bit
