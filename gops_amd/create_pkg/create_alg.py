@@ -31,13 +31,19 @@ loop_registry = Registry("algorithm")
 # stays as it is.  `create_alg` and `create_approx_contrainer` look in all three; `soft_registry` folds back with `loop_registry`.
 _SOFT_ALGORITHMS = ("dsact",)
 soft_registry = Registry("algorithm")
-registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem not in _LOOP_ALGORITHMS + _SOFT_ALGORITHMS)
+# SAC and DSAC likewise: the key set of `soft_registry` is pinned by tests/test_dsact_cpu.py (as it stood before them), and that test
+# file stays as it is.  `create_alg` and `create_approx_contrainer` look in all four; `soft_q_registry` folds back with the others.
+_SOFT_Q_ALGORITHMS = ("sac", "dsac")
+soft_q_registry = Registry("algorithm")
+_ELSEWHERE = _LOOP_ALGORITHMS + _SOFT_ALGORITHMS + _SOFT_Q_ALGORITHMS
+registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem not in _ELSEWHERE)
 loop_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _LOOP_ALGORITHMS)
 soft_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _SOFT_ALGORITHMS)
+soft_q_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _SOFT_Q_ALGORITHMS)
 
 
 def _registry_of(algorithm: str) -> Registry:
-    return loop_registry if algorithm in loop_registry else soft_registry if algorithm in soft_registry else registry
+    return next((r for r in (loop_registry, soft_registry, soft_q_registry) if algorithm in r), registry)
 
 
 def _defaults(kwargs: dict) -> dict:
@@ -81,7 +87,11 @@ class LocalActor:
 
 def create_alg(**kwargs) -> object:
     reg = _registry_of(kwargs["algorithm"])
-    reg.lookup(kwargs["algorithm"])               # unknown algorithm: KeyError before anything else
+    entry = reg.lookup(kwargs["algorithm"])       # unknown algorithm: KeyError before anything else
+    if reg is soft_q_registry:   # the arguments the reference's SAC / DSAC read with kwargs[...]: its KeyError, before any refusal
+        for name in inspect.getmodule(entry.entry_point).MANDATORY:
+            if name not in kwargs:
+                raise KeyError(name)
     if kwargs.get("env_id") in RPI_ONLY_ENVS and kwargs["algorithm"] != "RPI":
         raise NotImplementedError(f"env {kwargs['env_id']} is a zero-sum game model that only RPI supports, not {kwargs['algorithm']}")
     poly = [k for k in ("policy", "value") if kwargs.get(k + "_func_type") == "POLY"]
@@ -107,6 +117,10 @@ def create_alg(**kwargs) -> object:
     if kwargs["algorithm"] in soft_registry:
         from gops_amd.algorithm.dsact import refusal
         reason = refusal(kwargs)
+        if reason is not None:
+            raise NotImplementedError(reason)
+    if reg is soft_q_registry:
+        reason = inspect.getmodule(entry.entry_point).refusal(kwargs)
         if reason is not None:
             raise NotImplementedError(reason)
     trainer = kwargs.get("trainer")

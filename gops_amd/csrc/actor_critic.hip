@@ -1,4 +1,5 @@
-// The no-grad half of a DDPG / TD3 / DSAC-T update (gops/algorithm/ddpg.py:149-151, td3.py:166-183, dsact.py:237-313).
+// The no-grad half of a DDPG / TD3 / DSAC-T / SAC / DSAC update (gops/algorithm/ddpg.py:149-151, td3.py:166-183, dsact.py:237-313,
+// sac.py:214-223, dsac.py:199-252).
 //
 // ac_backup_kernel: the Bellman backup in ONE launch, forward only, nothing stashed.  A workgroup of 256 threads owns a tile of R
 // batch rows (R = 16, 32 or 64) and evaluates the target policy and the one or two target critics on it, one net after the other:
@@ -14,6 +15,8 @@
 //   Row strides of in0 / xa / xb are odd: the R rows a wave reads at one k sit in different banks.
 // soft_backup_kernel: DSAC-T's distributional soft backup (dsact.py:237-313) on the same tile scheme - a tanh-Gaussian target policy
 // (one thread per (row, action dimension) forms that dimension's mean and log std), two critics with (mean, softplus std) heads.
+// soft_q_backup_kernel: SAC's and DSAC's soft Q backup on the same tile and policy head - one or two scalar critics with their minimum,
+// or one critic with a (mean, softplus std) head and a clipped return sample.
 // ac_critic_loss_kernel: gradient seeds, losses, mean(q) and |q - backup| of the critic regression in one launch; sums in double
 // in the fixed order of block_reduce.h (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
 #include <stdint.h>
@@ -376,6 +379,107 @@ size_t soft_choose(const GopsSoftBackup& d, int B, AcParams& p, int& R) {
     return ac_choose(nets, 2, d.policy.sizes[0], A, 2 * A, B, p, R);   // extra: A doubles per row
 }
 
+// ---- SAC / DSAC: the soft Q backup (gops/algorithm/sac.py:214-223, dsac.py:199-252, the no-grad part) ------------------------------
+// soft_backup_kernel's tile, policy head and log-probability (restated here: that kernel stays as it is), then one or two scalar
+// critics with their minimum (distri = 0), or one critic with a (mean, softplus std) head and a clipped return sample (distri = 1).
+struct SoftQParams {
+    SoftParams s;   // ac.n_q: the critics; tq: the backup; z: [B] (distri); ac.q_targ: [n_q, B], or [B, 2] = (m, s) with distri
+    int distri;
+};
+
+template <int R>
+__global__ __launch_bounds__(AC_THREADS) void soft_q_backup_kernel(const SoftQParams qp) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const SoftParams& sp = qp.s;
+    const AcParams& p = sp.ac;
+    const int tid = threadIdx.x, r = tid % R, g = tid / R;
+    const int b0 = blockIdx.x * R;
+    const int nvalid = min(R, p.B - b0);
+    const int O = p.O, A = p.A, ld0 = p.ld0, ldx = p.ldx;
+    float* in0 = lds;
+    float* xa = lds + p.xa_off;
+    float* xb = lds + p.xb_off;
+    double* lp = reinterpret_cast<double*>(lds + p.e_off);
+    float* wb = lds + p.w_off;
+
+    for (int idx = tid; idx < R * O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
+        const int m = idx / O, k = idx - m * O;
+        in0[m * ld0 + k] = m < nvalid ? p.obs2[(size_t)(b0 + m) * O + k] : 0.f;
+    }
+    {   // ---- the policy at obs2: u = mean + std * eps, a2 = half * tanh(u) + mid, the dimension's share of log pi(a2 | obs2) ----
+        const AcNet& net = p.net[0];
+        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
+        const int K = net.dims[net.nl - 1];
+        ac_stage_head(net, wb);
+        if (g < A) {
+            const float* xr = cur + r * ldx;
+            const double mean = ac_head_dot(xr, wb + g * K, K) + (double)wb[2 * A * K + g];
+            const double ls = ac_head_dot(xr, wb + (A + g) * K, K) + (double)wb[2 * A * K + A + g];
+            const double sd = exp(fmin(fmax(ls, sp.min_ls), sp.max_ls));
+            const double e = r < nvalid ? (double)sp.eps[(size_t)(b0 + r) * A + g] : 0.0;
+            const double u = mean + sd * e, th = tanh(u), du = u - mean;
+            const double lo = g == 0 ? p.act_low[0] : g == 1 ? p.act_low[1] : g == 2 ? p.act_low[2] : p.act_low[3];
+            const double hi = g == 0 ? p.act_high[0] : g == 1 ? p.act_high[1] : g == 2 ? p.act_high[2] : p.act_high[3];
+            const double half = (hi - lo) / 2;
+            const float af = (float)(half * th + (hi + lo) / 2);
+            in0[r * ld0 + O + g] = af;   // (published, like lp, by the barrier at the top of the critic's first chunk)
+            if (p.a2 != nullptr && r < nvalid) p.a2[(size_t)(b0 + r) * A + g] = af;
+            lp[g * R + r] = (-(du * du) / (2 * sd * sd) - log(sd) - 0.91893853320467274178) - log(1.0 + 1e-6 - th * th) - log(half);
+        }
+    }
+    double q_next = 0.0, s_next = 0.0;   // of row r, in the threads with g == 0: min_i q_i, or (m, s) of the one distributional critic
+#pragma unroll 1
+    for (int n = 1; n <= p.n_q; ++n) {
+        const AcNet& net = p.net[n];
+        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
+        const int K = net.dims[net.nl - 1];
+        ac_stage_head(net, wb);
+        if (g == 0) {
+            const float* xr = cur + r * ldx;
+            if (qp.distri) {
+                q_next = ac_head_dot(xr, wb, K) + (double)wb[2 * K];
+                s_next = softplus_d(ac_head_dot(xr, wb + K, K) + (double)wb[2 * K + 1]);
+                if (p.q_targ != nullptr && r < nvalid) {
+                    float* qt = p.q_targ + (size_t)(b0 + r) * 2;
+                    qt[0] = (float)q_next, qt[1] = (float)s_next;
+                }
+            } else {
+                const double y = ac_head_dot(xr, wb, K) + (double)wb[K];
+                if (p.q_targ != nullptr && r < nvalid) p.q_targ[(size_t)(n - 1) * p.B + b0 + r] = (float)y;
+                q_next = n == 1 ? y : fmin(q_next, y);
+            }
+        }
+    }
+    if (g == 0 && r < nvalid) {
+        const int b = b0 + r;
+        double logp = 0.0;
+        for (int a = 0; a < A; ++a) logp += lp[a * R + r];
+        const double alpha = sp.log_alpha != nullptr ? exp((double)*sp.log_alpha) : sp.alpha;
+        if (qp.distri) q_next += fmin(fmax((double)sp.z[b], -3.0), 3.0) * s_next;   // dsac.py:206-208
+        sp.tq[b] = (float)((double)p.rew[b] + (1.0 - (double)p.done[b]) * p.gamma * (q_next - alpha * logp));   // sac.py:221, dsac.py:246
+        if (sp.logp != nullptr) sp.logp[b] = (float)logp;
+    }
+}
+
+int soft_q_check(const GopsSoftQBackup* d, int B) {
+    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
+    if (d->n_q < 1 || d->n_q > 2 || d->distri < 0 || d->distri > 1) return GOPS_ERR_BAD_ARG;
+    if (d->distri && d->n_q == 2) return GOPS_ERR_UNSUPPORTED;   // gops_soft_backup's case
+    if (d->policy.n_layers < 1 || d->policy.n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
+    const int O = d->policy.sizes[0], A2 = d->policy.sizes[d->policy.n_layers], A = A2 / 2;
+    if (O < 1 || A < 1 || (A2 & 1) || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (O + A > AC_MAX_IN) return GOPS_ERR_UNSUPPORTED;
+    int rc = ac_check_net(d->policy, O, 2 * A);
+    for (int i = 0; i < d->n_q && rc == GOPS_OK; ++i) rc = ac_check_net(d->q[i], O + A, d->distri ? 2 : 1);
+    return rc;
+}
+
+size_t soft_q_choose(const GopsSoftQBackup& d, int B, AcParams& p, int& R) {
+    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
+    const int A = d.policy.sizes[d.policy.n_layers] / 2;
+    return ac_choose(nets, d.n_q, d.policy.sizes[0], A, 2 * A, B, p, R);   // extra: A doubles per row
+}
+
 // ---- critic regression: seeds, losses, mean(q), |q - backup| -------------------------------------------------------------------
 constexpr int ACL_BLOCKS = 64;
 constexpr int ACL_ONE_BLOCK_MAX = 8192;
@@ -503,5 +607,46 @@ int soft_backup(const GopsSoftBackup* d, int B, const float* obs2, const float* 
     if (R == 64) launch_with_lds(soft_backup_kernel<64>, grid, dim3(AC_THREADS), lds, s, sp);
     else if (R == 32) launch_with_lds(soft_backup_kernel<32>, grid, dim3(AC_THREADS), lds, s, sp);
     else launch_with_lds(soft_backup_kernel<16>, grid, dim3(AC_THREADS), lds, s, sp);
+    return (int)hipGetLastError();
+}
+
+size_t soft_q_backup_workspace_bytes(const GopsSoftQBackup* d, int B) {
+    if (soft_q_check(d, B) != GOPS_OK) return 0;
+    AcParams p;
+    int R;
+    return soft_q_choose(*d, B, p, R) == 0 ? 0 : AC_WORKSPACE;
+}
+
+int soft_q_backup(const GopsSoftQBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
+                  float* backup, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int rc = soft_q_check(d, B);
+    if (rc != GOPS_OK) return rc;
+    if (!obs2 || !rew || !done || !eps || (d->distri && !z) || !backup) return GOPS_ERR_BAD_ARG;
+    SoftQParams qp;
+    memset(&qp, 0, sizeof(qp));
+    SoftParams& sp = qp.s;
+    AcParams& p = sp.ac;
+    int R;
+    const size_t lds = soft_q_choose(*d, B, p, R);
+    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < AC_WORKSPACE) return GOPS_ERR_WORKSPACE;
+    const GopsMlp* nets[3] = {&d->policy, &d->q[0], &d->q[1]};
+    for (int n = 0; n <= d->n_q; ++n) {
+        AcNet& a = p.net[n];
+        a.nl = nets[n]->n_layers, a.act = nets[n]->hidden_act;
+        for (int j = 0; j <= a.nl; ++j) a.dims[j] = nets[n]->sizes[j];
+        for (int j = 0; j < a.nl; ++j) { a.W[j] = nets[n]->weight[j]; a.Bv[j] = nets[n]->bias[j]; }
+    }
+    p.n_q = d->n_q, p.B = B, p.O = d->policy.sizes[0], p.A = d->policy.sizes[d->policy.n_layers] / 2;
+    for (int a = 0; a < p.A; ++a) p.act_low[a] = d->act_low[a], p.act_high[a] = d->act_high[a];
+    p.gamma = d->gamma;
+    p.obs2 = obs2, p.rew = rew, p.done = done, p.a2 = a2, p.q_targ = q_targ;
+    sp.min_ls = d->min_log_std, sp.max_ls = d->max_log_std, sp.alpha = d->alpha, sp.log_alpha = d->log_alpha;
+    sp.eps = eps, sp.z = z, sp.tq = backup, sp.logp = logp;
+    qp.distri = d->distri;
+    const dim3 grid((unsigned)((B + R - 1) / R));
+    if (R == 64) launch_with_lds(soft_q_backup_kernel<64>, grid, dim3(AC_THREADS), lds, s, qp);
+    else if (R == 32) launch_with_lds(soft_q_backup_kernel<32>, grid, dim3(AC_THREADS), lds, s, qp);
+    else launch_with_lds(soft_q_backup_kernel<16>, grid, dim3(AC_THREADS), lds, s, qp);
     return (int)hipGetLastError();
 }

@@ -1113,6 +1113,21 @@ int gops_dsact_critic_loss(const float* qraw, const float* target_q, const float
     return dsact_critic_loss(qraw, target_q, target_q_sample, batch, tau_b, state, seed, stats, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_soft_q_backup_workspace_bytes(const GopsSoftQBackup* desc, int32_t batch) { return soft_q_backup_workspace_bytes(desc, batch); }
+
+int gops_soft_q_backup(const GopsSoftQBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,
+                       const float* eps_next, const float* z_next, float* backup, float* a2, float* logp, float* q_targ, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return soft_q_backup(desc, batch, obs2, rew, done, eps_next, z_next, backup, a2, logp, q_targ, workspace, workspace_bytes,
+                         static_cast<hipStream_t>(stream));
+}
+
+int gops_dsac_critic_loss(const float* qraw, const float* target_q, int32_t batch, int32_t bound, float* seed, float* stats, void* stream) {
+    if (!qraw || !target_q || !seed || !stats || batch < 1) return GOPS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
+    return dsac_critic_loss(qraw, target_q, batch, bound != 0, seed, stats, static_cast<hipStream_t>(stream));
+}
+
 static bool tanh_gauss_ok(const GopsTanhGauss* d, int32_t batch) {
     return d && batch >= 1 && d->act_dim >= 1 && d->act_dim <= GOPS_MAX_ACT;
 }

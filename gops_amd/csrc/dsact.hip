@@ -1,4 +1,4 @@
-// The elementwise stages of a DSAC-T update (gops/algorithm/dsact.py) that sit between the MLP launches.
+// The elementwise stages of a DSAC-T update (gops/algorithm/dsact.py), and of a DSAC update, that sit between the MLP launches.
 //
 // dsact_loss_kernel: the variance-weighted critic losses and their gradient seeds with respect to the critics' RAW head outputs
 //   (dsact.py:243-251, 284-313).  The seeds depend on the batch mean of std through the running mean_std (the 3 mean_std clamp and
@@ -6,6 +6,8 @@
 //   of mean_std in the device state; (2) seeds and losses.  Up to 8192 rows ONE block runs both in one launch; beyond that the
 //   entry point issues TWO launches of 64 blocks (phase 1, then phase 2), each folding its blocks' partial sums in the block that
 //   draws the last ticket.  Nothing waits on another workgroup.
+// dsac_loss_kernel: DSAC's one-critic loss (gops/algorithm/dsac.py:235-252) and its seeds on the same two-phase scheme; the batch
+//   mean of std enters through td_bound = 3 mean(std).
 // tanh_gauss_fwd_kernel / tanh_gauss_bwd_kernel: StochaPolicy's sampling head - clamp, exp, u = mean + std eps, tanh squash,
 //   log-probability - and its reverse, one thread per row; the forward reduces mean(logp), mean(tanh(mean)) and mean(std).
 // Every value is formed in double from the fp32 inputs and rounded once where it is stored; sums are doubles in the fixed order of
@@ -106,6 +108,62 @@ __global__ __launch_bounds__(256) void dsact_loss_kernel(const float* __restrict
 }
 static_assert(DS_RESULTS + 2 * DS_PART * DS_BLOCKS + 1 <= GOPS_DSACT_STATS_FLOATS, "stats: results, the blocks' partial sums, the ticket");
 
+// ---- DSAC: the one-critic loss (gops/algorithm/dsac.py:235-252) ----------------------------------------------------------------------
+// dsact_loss_kernel's scheme: phase 1 - mean q, mean std and td_bound = 3 mean(std), left in stats[1 .. 3] as fp32; phase 2 - seeds
+// and the loss with td_bound read back from stats[3] (the same fp32 value in the one-launch and in the two-launch path).
+constexpr int DC_RESULTS = 4;   // floats in front of the partial sums
+constexpr int DC_PART = 2;      // doubles per block
+
+__global__ __launch_bounds__(256) void dsac_loss_kernel(const float* __restrict__ qraw, const float* __restrict__ tq, int B, int bound,
+                                                        int phases, float* __restrict__ seed, float* __restrict__ stats) {
+    __shared__ double red[DC_PART][4];
+    __shared__ bool last;
+    __shared__ float td_sh;
+    double* part = reinterpret_cast<double*>(stats + DC_RESULTS);   // [DS_BLOCKS][DC_PART]
+    unsigned* ticket = reinterpret_cast<unsigned*>(stats + DC_RESULTS + 2 * DC_PART * DS_BLOCKS);
+    if (phases & 1) {   // ---- batch moments, td_bound (dsac.py:243, 249) ----
+        double s[2] = {0.0, 0.0};   // sum q, sum std
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256)
+            s[0] += (double)qraw[2 * (size_t)i], s[1] += softplus_d((double)qraw[2 * (size_t)i + 1]);
+        block_fold<2, false>(s, red);
+        bool fin = gridDim.x == 1;
+        if (!fin) {
+            fin = last_block<2>(s, part, DC_PART, ticket, &last);
+            if (fin) block_fold<2, false>(s, red);
+        }
+        if (fin && threadIdx.x == 0) {
+            const float td = (float)(3.0 * (s[1] / (double)B));
+            stats[1] = (float)(s[0] / (double)B), stats[2] = (float)(s[1] / (double)B), stats[3] = td;
+            td_sh = td;
+        }
+        if (phases == 1) return;
+        __syncthreads();   // one block ran phase 1: td_sh is visible
+    } else {
+        if (threadIdx.x == 0) td_sh = stats[3];
+        __syncthreads();
+    }
+    // ---- seeds and loss (dsac.py:235-242): with `bound`, the first term is live in q, the second and third in std ----
+    const double td = (double)td_sh;
+    double l[1] = {0.0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256) {
+        const double q = (double)qraw[2 * (size_t)i], raw = (double)qraw[2 * (size_t)i + 1], sd = softplus_d(raw);
+        const double e = (double)tq[i] - q;                            // target_q - q
+        const double eb = bound ? fmin(fmax(e, -td), td) : e;          // target_q_bound - q
+        const double v = sd * sd;
+        seed[2 * (size_t)i] = (float)(-e / v / (double)B);
+        seed[2 * (size_t)i + 1] = (float)((1.0 / sd - eb * eb / (v * sd)) * softplus_grad_d(raw) / (double)B);
+        l[0] += bound ? e * e / (2 * v) + eb * eb / (2 * v) + log(sd) : e * e / (2 * v) + log(sd) + 0.91893853320467274178;
+    }
+    block_fold<1, false>(l, red);
+    bool fin = gridDim.x == 1;
+    if (!fin) {
+        fin = last_block<1>(l, part, DC_PART, ticket, &last);
+        if (fin) block_fold<1, false>(l, red);
+    }
+    if (fin && threadIdx.x == 0) stats[0] = (float)(l[0] / (double)B);
+}
+static_assert(DC_RESULTS + 2 * DC_PART * DS_BLOCKS + 1 <= GOPS_DSAC_STATS_FLOATS, "stats: results, the blocks' partial sums, the ticket");
+
 // ---- the sampling head ----------------------------------------------------------------------------------------------------------
 struct TgParams {
     int B, A;
@@ -189,6 +247,16 @@ int dsact_critic_loss(const float* qraw, const float* tq, const float* tqs, int 
     } else {
         hipLaunchKernelGGL(dsact_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, tqs, B, tau_b, 1, st, seed, stats);
         hipLaunchKernelGGL(dsact_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, tqs, B, tau_b, 2, st, seed, stats);
+    }
+    return (int)hipGetLastError();
+}
+
+int dsac_critic_loss(const float* qraw, const float* tq, int B, int bound, float* seed, float* stats, hipStream_t s) {
+    if (B <= DS_ONE_BLOCK_MAX) {
+        hipLaunchKernelGGL(dsac_loss_kernel, dim3(1), dim3(256), 0, s, qraw, tq, B, bound, 3, seed, stats);
+    } else {
+        hipLaunchKernelGGL(dsac_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, B, bound, 1, seed, stats);
+        hipLaunchKernelGGL(dsac_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, B, bound, 2, seed, stats);
     }
     return (int)hipGetLastError();
 }

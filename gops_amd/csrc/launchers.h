@@ -65,10 +65,14 @@ int ac_critic_loss(const float* q, const float* backup, const float* weight, int
 size_t soft_backup_workspace_bytes(const GopsSoftBackup* d, int B);
 int soft_backup(const GopsSoftBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
                 float* tq, float* tqs, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s);
+size_t soft_q_backup_workspace_bytes(const GopsSoftQBackup* d, int B);
+int soft_q_backup(const GopsSoftQBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
+                  float* backup, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s);
 
-// ---- dsact.hip: DSAC-T's critic losses with their seeds, and the tanh-Gaussian sampling head forward and reverse ----
+// ---- dsact.hip: DSAC-T's and DSAC's critic losses with their seeds, and the tanh-Gaussian sampling head forward and reverse ----
 int dsact_critic_loss(const float* qraw, const float* tq, const float* tqs, int B, double tau_b, GopsDsactState* st, float* seed,
                       float* stats, hipStream_t s);
+int dsac_critic_loss(const float* qraw, const float* tq, int B, int bound, float* seed, float* stats, hipStream_t s);
 int tanh_gauss_forward(const GopsTanhGauss& d, int B, const float* head, const float* eps, double target_entropy, float* act, float* logp,
                        float* stats, hipStream_t s);
 int tanh_gauss_backward(const GopsTanhGauss& d, int B, const float* head, const float* eps, const float* g_act, const float* g_logp,

@@ -162,6 +162,13 @@ class GopsSoftBackup(C.Structure):   # gops_soft_backup
                 ("log_alpha", C.c_void_p)]
 
 
+class GopsSoftQBackup(C.Structure):   # gops_soft_q_backup
+    _fields_ = [("policy", GopsMlp), ("q", GopsMlp * 2), ("n_q", C.c_int32), ("distri", C.c_int32),
+                ("act_low", C.c_float * MAX_ACT), ("act_high", C.c_float * MAX_ACT),
+                ("min_log_std", C.c_double), ("max_log_std", C.c_double), ("gamma", C.c_double), ("alpha", C.c_double),
+                ("log_alpha", C.c_void_p)]
+
+
 class GopsTanhGauss(C.Structure):   # gops_tanh_gauss_forward / _backward
     _fields_ = [("act_dim", C.c_int32), ("reserved", C.c_int32), ("act_low", C.c_float * MAX_ACT), ("act_high", C.c_float * MAX_ACT),
                 ("min_log_std", C.c_double), ("max_log_std", C.c_double)]
@@ -221,6 +228,9 @@ def _signatures():
         "gops_dsact_critic_loss": (rc, [vp, vp, vp, i32, f64, vp, vp, vp, vp]),
         "gops_tanh_gauss_forward": (rc, [P(GopsTanhGauss), i32, vp, vp, f64, vp, vp, vp, vp]),
         "gops_tanh_gauss_backward": (rc, [P(GopsTanhGauss), i32, vp, vp, vp, vp, vp, vp]),
+        "gops_soft_q_backup_workspace_bytes": (sz, [P(GopsSoftQBackup), i32]),
+        "gops_soft_q_backup": (rc, [P(GopsSoftQBackup), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "gops_dsac_critic_loss": (rc, [vp, vp, i32, i32, vp, vp, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -1390,6 +1400,75 @@ class DsactCriticLoss:
         check(lib().gops_dsact_critic_loss(_ptr(qraw), _ptr(target_q), _ptr(target_q_sample), B, float(tau_b), self.state.data_ptr(),
                                            _ptr(seed), self.buf.data_ptr(), _stream()), "gops_dsact_critic_loss")
         return seed, self.buf[:11]
+
+
+DSAC_STATS_FLOATS = 264   # include/gops_hip.h: GOPS_DSAC_STATS_FLOATS
+
+
+class SoftQBackup:
+    """The soft Q backup of a SAC / DSAC update in ONE launch (`gops_soft_q_backup`, csrc/actor_critic.hip): tanh-Gaussian policy on
+    obs2 with its log-probability, then one or two scalar critics and their minimum (`distri=False`: SAC), or one critic with a
+    (mean, softplus std) head and a clipped return sample (`distri=True`: DSAC), entropy term.  `policy` / `critics`: `GopsMlp` views
+    of the networks' raw stacks (read in place at every call).  `log_alpha`: the device tensor the kernel takes alpha from, or None
+    for the fixed `alpha` of `run`.  `supported` is False for a shape the kernel does not hold; `run` on such a description raises."""
+
+    def __init__(self, policy: GopsMlp, critics: Sequence[GopsMlp], *, distri: bool, act_low, act_high, min_log_std: float,
+                 max_log_std: float, batch: int, log_alpha: Optional[torch.Tensor] = None, device: Optional[torch.device] = None,
+                 workspace_bytes: Optional[int] = None):
+        d = self.desc = GopsSoftQBackup()
+        self.batch, self.act_dim, self.n_q, self.distri = int(batch), int(policy.sizes[policy.n_layers]) // 2, len(critics), bool(distri)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        d.n_q, d.distri = self.n_q, int(self.distri)
+        for name, vals in (("act_low", act_low), ("act_high", act_high)):
+            _fill(getattr(d, name), np.asarray(vals, dtype=np.float32).reshape(-1)[:MAX_ACT])
+        d.min_log_std, d.max_log_std = float(min_log_std), float(max_log_std)
+        self.log_alpha = log_alpha
+        d.log_alpha = _ptr(log_alpha)
+        self.set_nets(policy, critics)
+        nbytes = lib().gops_soft_q_backup_workspace_bytes(C.byref(d), self.batch)
+        self.supported = nbytes != 0
+        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
+        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
+
+    def set_nets(self, policy: GopsMlp, critics: Sequence[GopsMlp]):
+        assert len(critics) == self.n_q
+        C.memmove(C.byref(self.desc.policy), C.byref(policy), C.sizeof(GopsMlp))
+        for i, c in enumerate(critics):
+            C.memmove(C.byref(self.desc.q[i]), C.byref(c), C.sizeof(GopsMlp))
+        self._keep = (policy, list(critics))   # the description holds raw pointers
+
+    def run(self, obs2, rew, done, eps_next, z_next=None, *, gamma=0.99, alpha=0.2, want=(), out: Optional[Dict[str, torch.Tensor]] = None):
+        """-> {"backup" [B]} and, named in `want`: "a2" [B, A], "logp" [B], "q_targ" ([n_q, B], or [B, 2] = (m, s) with `distri`);
+        `out` supplies output tensors instead of fresh ones.  Enqueues only."""
+        B, d, dev = self.batch, self.desc, self.device
+        assert obs2.shape[0] == B and (z_next is None or tuple(z_next.shape) == (B,))
+        d.gamma, d.alpha = float(gamma), float(alpha)
+        res = dict(out or {})
+        shapes = dict(backup=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(B, 2) if self.distri else (self.n_q, B))
+        for k in ("backup",) + tuple(want):
+            if k not in res:
+                res[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
+        check(lib().gops_soft_q_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["backup"]),
+                                       _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")), self.workspace.data_ptr(),
+                                       self._workspace_bytes, _stream()), "gops_soft_q_backup")
+        return res
+
+
+class DsacCriticLoss:
+    """DSAC's critic loss and its gradient seeds (`gops_dsac_critic_loss`).  `buf[:4]` = loss, mean(q), mean(std), td_bound; the rest
+    is the kernel's scratch (zero before the first call, left zero)."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(DSAC_STATS_FLOATS, dtype=torch.float32, device=device)
+
+    def run(self, qraw: torch.Tensor, target_q: torch.Tensor, bound: bool, seed: Optional[torch.Tensor] = None):
+        """qraw [B, 2] -> (seed [B, 2], stats [4])."""
+        B = qraw.shape[0]
+        assert tuple(qraw.shape) == (B, 2)
+        seed = torch.empty_like(qraw) if seed is None else seed
+        check(lib().gops_dsac_critic_loss(_ptr(qraw), _ptr(target_q), B, int(bool(bound)), _ptr(seed), self.buf.data_ptr(), _stream()),
+              "gops_dsac_critic_loss")
+        return seed, self.buf[:4]
 
 
 class TanhGaussHead:

@@ -752,6 +752,49 @@ int gops_tanh_gauss_forward(const GopsTanhGauss* desc, int32_t batch, const floa
 int gops_tanh_gauss_backward(const GopsTanhGauss* desc, int32_t batch, const float* head, const float* eps, const float* g_act,
                              const float* g_logp, float* g_head, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): SAC and DSAC (gops/algorithm/sac.py, dsac.py; csrc/actor_critic.hip,
+ * csrc/dsact.hip).
+ *
+ * gops_soft_q_backup: the whole no-grad target of sac.py:214-223 / dsac.py:199-252 in ONE launch, forward only, nothing stashed.
+ * a2 and logp per batch row exactly as in gops_soft_backup (clamp of log_std, u = mean + std eps_next, squash, log-probability), then
+ *     distri = 0:  backup = rew + (1 - done) gamma (min_i q[i]([obs2, a2]) - alpha logp)              n_q = 2: SAC; n_q = 1: no minimum
+ *     distri = 1:  (m, s) = (q[0](..)[0], softplus(q[0](..)[1]))   softplus with torch's threshold of 20;   n_q = 1: DSAC
+ *                  backup = rew + (1 - done) gamma (m + clamp(z_next, -3, 3) s - alpha logp)
+ * distri = 1 with n_q = 2 is gops_soft_backup's case: GOPS_ERR_UNSUPPORTED (and 0 workspace bytes).  z_next [B] is read iff `distri`;
+ * NULL then: GOPS_ERR_BAD_ARG.  `policy` is whichever policy the algorithm evaluates at obs2 (SAC: the online one).
+ * Tiles, staging, chains, doubles and the policy head are gops_soft_backup's; results are bitwise reproducible and do not depend on the
+ * tile size.  Accepted shapes as for gops_soft_backup, with q[i]: obs_dim + act_dim -> .. -> 1 (distri = 0) or 2 (distri = 1); the
+ * same return codes and the same 256-byte workspace section; n_q outside 1 .. 2 or distri outside 0 .. 1: GOPS_ERR_BAD_ARG.
+ * Outputs: backup [B]; optional (NULL): a2 [B, act_dim], logp [B], q_targ - [n_q, B] for distri = 0, [B, 2] = (m, s) for distri = 1. */
+struct GopsSoftQBackup {
+    GopsMlp policy;              /* obs_dim -> .. -> 2 * act_dim, raw (mean, log_std) */
+    GopsMlp q[2];
+    int32_t n_q;                 /* 1 or 2 */
+    int32_t distri;              /* 0: q[i] -> 1 output (ActionValue); 1: q[i] -> 2 outputs (mean, softplus std) */
+    float act_low[GOPS_MAX_ACT], act_high[GOPS_MAX_ACT];
+    double min_log_std, max_log_std, gamma, alpha;
+    const float* log_alpha;      /* device, or NULL: use alpha */
+};
+typedef struct GopsSoftQBackup GopsSoftQBackup;
+size_t gops_soft_q_backup_workspace_bytes(const GopsSoftQBackup* desc, int32_t batch);
+int gops_soft_q_backup(const GopsSoftQBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,
+                       const float* eps_next, const float* z_next, float* backup, float* a2, float* logp, float* q_targ, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* gops_dsac_critic_loss: DSAC's critic loss (dsac.py:235-252) and its gradient seeds.  qraw [B, 2]: the ONLINE critic's raw head on
+ * the data, q = qraw[:, 0], sd = softplus(qraw[:, 1]); target_q [B] from gops_soft_q_backup.
+ *     td_bound = 3 mean(sd) (rounded to fp32, then used);   target_q_bound = q + clamp(target_q - q, -td_bound, td_bound)
+ *     bound != 0:  loss = mean((q - target_q)^2 / (2 sd^2) + (q - target_q_bound)^2 / (2 sd^2) + log sd)
+ *                  the first term live in q (its sd detached), the second and third live in sd (their q detached)
+ *     bound == 0:  loss = mean(-Normal(q, sd).log_prob(target_q)), live in both
+ *     seed [B, 2] = d loss / d(q, raw); the raw column carries softplus' derivative sigmoid(raw)
+ *     stats[0] = loss, [1] = mean(q), [2] = mean(sd), [3] = td_bound
+ * Up to 8192 rows one workgroup in ONE launch; larger batches TWO launches of 64 workgroups (moments, then seeds and loss).
+ * `stats`: 8-byte aligned, GOPS_DSAC_STATS_FLOATS floats, ALL ZERO before the first call (partial sums and a ticket the call leaves
+ * zero again); otherwise, and for NULL pointers or batch < 1, GOPS_ERR_BAD_ARG. */
+#define GOPS_DSAC_STATS_FLOATS 264
+int gops_dsac_critic_loss(const float* qraw, const float* target_q, int32_t batch, int32_t bound, float* seed, float* stats,
+                          void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32

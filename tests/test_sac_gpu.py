@@ -1,0 +1,442 @@
+"""GPU: SAC and DSAC (algorithm/sac.py, dsac.py) and their kernels - `gops_soft_q_backup`, `gops_dsac_critic_loss` - against a float64
+restatement and the reference fixtures of tests/golden/make_golden_sac.py.
+
+Bound of the soft Q backup (the rule of test_td3_gpu.py / test_dsact_gpu.py): the composed path's max error against float64 is
+measured on the same inputs first; the fused kernel may use twice that, but not less than 4 fp32 ulp of the largest |value|.  The
+critic-loss kernel forms every value in double from its fp32 inputs and rounds once: 4 ulp rel-L2 against float64 evaluated on the
+same fp32 inputs.
+"""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import rel_l2
+from sac_helpers import FIVE_UPDATES, ONE_UPDATE, Q_NAMES, TOL, alg_kwargs, batch_of, load_alg
+
+from gops_amd import hip_backend as hb
+from gops_amd.create_pkg.create_alg import create_alg
+
+pytestmark = pytest.mark.gpu
+EPS32 = 2.0 ** -23
+S = -777.0   # sentinel
+OUT = ("backup", "a2", "logp", "q_targ")
+CTOR = {"SAC": dict(gamma=0.97, tau=0.05, auto_alpha=True), "DSAC": dict(gamma=0.97, tau=0.05, auto_alpha=True, bound=True, delay_update=2)}
+LIM4 = ([-1.0, -0.5, -2.0, -1.0], [2.0, 0.5, 2.0, 1.0])
+
+
+def _alg(name, obs, act, hidden, activation, seed=5, **over):
+    """A SAC / DSAC object on the GPU: targets randomised apart, every policy's head with means within +-0.9 and log stds on both
+    sides of the clamp [-3, -0.5] (so |u| <= 0.9 + 3.3 * exp(-0.5) stays where fp32 resolves 1 + 1e-6 - tanh(u)^2), SAC's twin target
+    critics centred on each other.  act 4 (obs 6): eight head outputs."""
+    env = {3: "gym_pendulum", 4: "pyth_lq", 6: "pyth_idpendulum"}[obs]
+    lim = {1: ([-2.0], [2.0]), 2: ([-1.0, -0.5], [2.0, 0.5]), 4: LIM4}[act]
+    meta = dict(cfg=dict(alg=name, env_id=env, hidden=hidden, act=activation), lim=lim, seed=seed, min_log_std=-3.0, max_log_std=-0.5,
+                ctor=CTOR[name])
+    if obs == 4:
+        meta["cfg"]["lq_config"] = "s4a2"
+    torch.manual_seed(seed)
+    a = create_alg(**alg_kwargs(meta, True, **dict(dict(action_dim=act), **over)))
+    g = torch.Generator().manual_seed(seed + 1)
+    nets = a.networks
+    with torch.no_grad():
+        for n, p in nets.named_parameters():
+            if "_target." in n:
+                p.add_(0.3 * (torch.rand(p.shape, generator=g) - 0.5))
+        probe = torch.randn(256, obs, generator=g)
+        for pol in [nets.policy] + ([nets.policy_target] if name == "DSAC" else []):
+            head, y = pol.linear_layers()[-1], pol.policy(probe)
+            scale = torch.cat([0.9 / y[:, :act].abs().max(dim=0).values.clamp_min(0.9), 1.6 / y[:, act:].std(dim=0)])
+            head.weight.mul_(scale[:, None])
+            head.bias.mul_(scale)
+            head.bias[act:].sub_(pol.policy(probe)[:, act:].median(dim=0).values + 1.75)
+        if name == "SAC":
+            a2 = nets.policy.get_act_dist(nets.policy(probe)).mode()
+            nets.q2_target.linear_layers()[-1].bias[0].add_((nets.q1_target(probe, a2) - nets.q2_target(probe, a2)).median())
+    nets.cuda()
+    return a
+
+
+def _data(B, obs, act, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    o = torch.randn(B, obs, generator=g)
+    d = (torch.rand(B, generator=g) < 0.2).float()
+    if B > 1:
+        d[0], d[-1] = 1.0, 0.0
+    return dict(obs=o, act=torch.rand(B, act, generator=g) * 2 - 1, rew=torch.randn(B, generator=g), obs2=o + 0.1 * torch.randn(B, obs, generator=g),
+                done=d, eps_new=torch.randn(B, act, generator=g), eps_next=torch.randn(B, act, generator=g).clamp(-3.3, 3.3),
+                z_next=2 * torch.randn(B, generator=g))
+
+
+def _ref_backup(alg, data):
+    """The backup of whatever `alg._backup_modules()` names, in float64 on the host."""
+    pol, qs = alg._backup_modules()
+    pol, qs = copy.deepcopy(pol).cpu().double(), [copy.deepcopy(q).cpu().double() for q in qs]
+    d = {k: v.detach().cpu().double() for k, v in data.items()}
+    alpha = float(alg.networks.log_alpha.detach().double().exp()) if alg.auto_alpha else float(alg.alpha)
+    with torch.no_grad():
+        a2, logp = pol.get_act_dist(pol(d["obs2"])).rsample(d["eps_next"])
+        if alg._distri:
+            q_targ = qs[0](d["obs2"], a2)
+            q_next = q_targ[:, 0] + torch.clamp(d["z_next"], -3, 3) * q_targ[:, 1]
+        else:
+            q_targ = torch.stack([q(d["obs2"], a2) for q in qs])
+            q_next = q_targ.min(dim=0).values
+        backup = d["rew"] + (1 - d["done"]) * alg.gamma * (q_next - alpha * logp)
+    return dict(backup=backup, a2=a2, logp=logp, q_targ=q_targ)
+
+
+def _fused(alg, batch, want=("a2", "logp", "q_targ"), **kw):
+    sb = alg._soft_q_backup(batch["obs2"].shape[0], batch["obs2"].device)
+    assert sb.supported and sb.n_q == len(alg._q_names) and sb.distri == alg._distri
+    return sb.run(batch["obs2"], batch["rew"], batch["done"], batch["eps_next"], batch.get("z_next"), gamma=alg.gamma, alpha=alg.alpha,
+                  want=want, **kw)
+
+
+def _check_backup(alg, data, label):
+    batch = alg._batch(data)
+    ref = _ref_backup(alg, data)
+    comp = dict(zip(OUT, alg._backup_composed(batch)))
+    got, again = _fused(alg, batch), _fused(alg, batch)
+    for k in OUT:
+        want = ref[k].reshape(got[k].shape)
+        err_c = (comp[k].double().cpu() - want).abs().max().item()
+        err_f = (got[k].double().cpu() - want).abs().max().item()
+        bound = max(2 * err_c, 4 * EPS32 * want.abs().max().item())
+        print(f"{label} {k}: fused {err_f:.3e} composed {err_c:.3e} bound {bound:.3e}")
+        assert err_f <= bound, (label, k, err_f, err_c, bound)
+        assert torch.equal(got[k], again[k]), (label, k)
+    return ref, batch
+
+
+SHAPES = [(3, 1, [32], "relu"), (4, 2, [64, 48], "tanh"), (3, 1, [48, 16], "gelu")]
+KINDS = ["SAC", "DSAC", "SAC one critic"]   # distri 0 / n_q 2, distri 1 / n_q 1, distri 0 / n_q 1
+
+
+def _kind(kind, *args, **kw):
+    alg = _alg(kind.split()[0], *args, **kw)
+    if kind == "SAC one critic":
+        alg._q_names = ("q1",)   # the backup only is asked of this object
+    return alg
+
+
+@pytest.mark.parametrize("B", [1, 22, 70])
+@pytest.mark.parametrize("obs,act,hidden,activation", SHAPES)
+@pytest.mark.parametrize("kind", KINDS)
+def test_soft_q_backup_against_float64(kind, obs, act, hidden, activation, B):
+    alg = _kind(kind, obs, act, hidden, activation)
+    data = _data(B, obs, act)
+    ref, batch = _check_backup(alg, data, f"{kind} {obs}/{act} {hidden} {activation} B={B}")
+    assert ref["q_targ"].shape == ((B, 2) if kind == "DSAC" else (len(alg._q_names), B))
+    if B == 70:   # the branch cases are in the batch
+        pt = alg._backup_modules()[0]
+        ls = pt.policy(batch["obs2"])[:, act:].cpu()
+        assert (ls < -3.0).any() and (ls > -0.5).any() and ((ls > -3.0) & (ls < -0.5)).any()
+        if kind == "SAC":
+            m = ref["q_targ"]
+            assert (m[0] < m[1]).any() and (m[1] < m[0]).any()
+        if kind == "DSAC":
+            z = data["z_next"]
+            assert (z > 3).any() and (z < -3).any() and (z.abs() < 3).any()
+        assert (data["done"] == 1).any() and (data["done"] == 0).any()
+        mean, std = torch.chunk(pt(batch["obs2"]).cpu().double(), 2, dim=-1)
+        assert (mean + std * data["eps_next"].double()).abs().max() <= 3.0
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_soft_q_backup_fixed_alpha(name):
+    alg = _alg(name, 3, 1, [32, 16], "relu", auto_alpha=False, alpha=0.3)
+    _check_backup(alg, _data(70, 3, 1), f"{name} fixed alpha")
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_soft_q_backup_32_row_tiles(name):
+    _check_backup(_alg(name, 4, 2, [64, 64], "elu"), _data(2054, 4, 2, seed=3), f"{name} [64, 64] B=2054")
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_soft_q_backup_64_row_tiles_eight_head_outputs_chunked_weights(name):
+    _check_backup(_alg(name, 6, 4, [256, 256], "elu", seed=7), _data(16390, 6, 4, seed=3), f"{name} [256, 256] act 4 B=16390")
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_soft_q_backup_does_not_depend_on_the_tile_rows(name):
+    """70 rows alone (16-row tiles) and as the first rows of a batch of 2054 (32-row tiles): the same bits."""
+    alg = _alg(name, 4, 2, [64, 48], "tanh")
+    big = _data(2054, 4, 2, seed=2)
+    small = {k: v[:70].clone() for k, v in big.items()}
+    a, b = _fused(alg, alg._batch(small)), _fused(alg, alg._batch(big))
+    for k in OUT:
+        rows = b[k][:, :70] if (k == "q_targ" and name == "SAC") else b[k][:70]
+        assert torch.equal(a[k], rows), k
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_soft_q_backup_saturation(name):
+    """Rows with |u| > 8: every output is finite and a2 is within the limits (no parity asked where fp32 cannot resolve the log)."""
+    alg = _alg(name, 4, 2, [64, 48], "tanh")
+    data = _data(70, 4, 2)
+    pt = alg._backup_modules()[0]
+    mean, std = torch.chunk(pt(data["obs2"].cuda()).cpu(), 2, dim=-1)
+    data["eps_next"][:6] = (torch.tensor([[12.0, -12.0]] * 3 + [[-30.0, 30.0]] * 3) - mean[:6]) / std[:6]   # u = +-12, +-30
+    batch = alg._batch(data)
+    assert ((mean.cuda() + std.cuda() * batch["eps_next"])[:6].abs() > 8).all()
+    got = _fused(alg, batch)
+    for k in OUT:
+        assert torch.isfinite(got[k]).all(), k
+    assert (got["a2"] >= pt.act_low_lim).all() and (got["a2"] <= pt.act_high_lim).all()
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_optional_outputs_and_rows_beyond_the_batch(name):
+    """Outputs padded with a sentinel: rows beyond the batch stay untouched; with the optional outputs NULL the backup keeps its bits."""
+    B, pad = 70, 64
+    alg = _alg(name, 4, 2, [64, 48], "tanh")
+    batch = alg._batch(_data(B, 4, 2))
+    sizes = dict(backup=B, a2=2 * B, logp=B, q_targ=2 * B)
+    bufs = {k: torch.full((n + pad,), S, device="cuda") for k, n in sizes.items()}
+    shapes = dict(backup=(B,), a2=(B, 2), logp=(B,), q_targ=(B, 2) if name == "DSAC" else (2, B))
+    got = _fused(alg, batch, out={k: v[:sizes[k]].view(shapes[k]) for k, v in bufs.items()})
+    torch.cuda.synchronize()
+    for k, t in bufs.items():
+        assert (t[sizes[k]:] == S).all() and (t[:sizes[k]] != S).all(), k
+    alone = _fused(alg, batch, want=())
+    assert set(alone) == {"backup"} and torch.equal(alone["backup"], got["backup"])
+
+
+def test_soft_q_backup_return_codes():
+    """distri = 1 with n_q = 2 (gops_soft_backup's case) and a 272-wide layer: 0 workspace bytes, GOPS_ERR_UNSUPPORTED; a missing
+    z_next, n_q = 3 and critics of the wrong output width: GOPS_ERR_BAD_ARG; a short workspace: GOPS_ERR_WORKSPACE."""
+    data = _data(22, 3, 1)
+    dsac = _alg("DSAC", 3, 1, [32], "relu")
+    b = dsac._batch(data)
+    args = (b["obs2"], b["rew"], b["done"], b["eps_next"])
+    pt, q = dsac.networks.policy_target, dsac.networks.q_target
+    mk = lambda critics, distri, **kw: hb.SoftQBackup(pt.hip_mlp(), critics, distri=distri, act_low=pt.act_low_lim.cpu().numpy(),   # noqa: E731
+                                                      act_high=pt.act_high_lim.cpu().numpy(), min_log_std=-3.0, max_log_std=-0.5, batch=22, **kw)
+    twin = mk([q.hip_mlp(), q.hip_mlp()], True)
+    assert not twin.supported and hb.lib().gops_soft_q_backup_workspace_bytes(hb.C.byref(twin.desc), 22) == 0
+    with pytest.raises(RuntimeError, match="GOPS_ERR_UNSUPPORTED"):
+        twin.run(*args, b["z_next"])
+    ok = mk([q.hip_mlp()], True)
+    assert ok.supported
+    with pytest.raises(RuntimeError, match="GOPS_ERR_BAD_ARG"):
+        ok.run(*args, None)
+    ok.run(*args, b["z_next"])
+    scalar_on_distri = mk([q.hip_mlp()], False)   # a two-output critic where one output is described
+    assert not scalar_on_distri.supported
+    with pytest.raises(RuntimeError, match="GOPS_ERR_BAD_ARG"):
+        scalar_on_distri.run(*args)
+    ok.desc.n_q = 3
+    assert hb.lib().gops_soft_q_backup_workspace_bytes(hb.C.byref(ok.desc), 22) == 0
+    with pytest.raises(RuntimeError, match="GOPS_ERR_BAD_ARG"):
+        ok.run(*args, b["z_next"])
+    small = mk([q.hip_mlp()], True, workspace_bytes=16)
+    assert small.supported
+    with pytest.raises(RuntimeError, match="GOPS_ERR_WORKSPACE"):
+        small.run(*args, b["z_next"])
+    wide = _alg("SAC", 3, 1, [272], "relu")
+    sb = wide._soft_q_backup(22, b["obs"].device)
+    assert not sb.supported and hb.lib().gops_soft_q_backup_workspace_bytes(hb.C.byref(sb.desc), 22) == 0
+    with pytest.raises(RuntimeError, match="GOPS_ERR_UNSUPPORTED"):
+        sb.run(*args)
+    torch.cuda.synchronize()
+
+
+def _critic_inputs(B, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    qraw = torch.randn(B, 2, generator=g)
+    if B > 4:
+        qraw[1, 1], qraw[2, 1] = 25.0, -2.5   # beyond softplus' threshold, and a small std (0.079)
+    return qraw, qraw[:, 0] + 3.0 * torch.randn(B, generator=g)
+
+
+def _critic_ref(qraw, tq, bound):
+    q, raw, tq, B = qraw[:, 0].double(), qraw[:, 1].double(), tq.double(), qraw.shape[0]
+    sd = torch.nn.functional.softplus(raw)
+    sig = torch.where(raw > 20, torch.ones_like(raw), torch.sigmoid(raw))
+    td = (3 * sd.mean()).float().double()   # handed from the moments to the seeds as fp32
+    e = tq - q
+    eb = torch.clamp(e, -td, td) if bound else e
+    terms = [e ** 2 / (2 * sd ** 2), eb ** 2 / (2 * sd ** 2), torch.log(sd)] if bound else [e ** 2 / (2 * sd ** 2), torch.log(sd) + 0.5 * np.log(2 * np.pi)]
+    seed = torch.stack((-e / sd ** 2 / B, (1 / sd - eb ** 2 / sd ** 3) * sig / B), dim=-1)
+    stats = [sum(terms).mean().item(), q.mean().item(), sd.mean().item(), td.item()]
+    scale = [sum(t.abs() for t in terms).mean().item(), q.abs().mean().item(), sd.mean().item(), td.item()]
+    return seed, stats, scale, e.abs() > td
+
+
+@pytest.mark.parametrize("bound", [True, False])
+@pytest.mark.parametrize("B", [1, 70, 9000])
+def test_dsac_critic_loss_against_float64(B, bound):
+    """B = 9000: beyond one block - two launches of 64 blocks.  Called twice on different inputs (the scratch is left reusable), and
+    again on the same: the same bits; rows beyond the batch keep the sentinel; the ticket is left zero."""
+    cl = hb.DsacCriticLoss("cuda")
+    for call in range(2):
+        qraw, tq = _critic_inputs(B, seed=call)
+        want, stats, scale, binds = _critic_ref(qraw, tq, bound)
+        if B > 1:
+            assert binds.any() and (~binds).any()
+        seed = torch.full((2 * B + 64,), S, device="cuda")
+        out, st = cl.run(qraw.cuda(), tq.cuda(), bound, seed=seed[:2 * B].view(B, 2))
+        got_stats = st.cpu().double().tolist()
+        assert (seed[2 * B:] == S).all()
+        err = rel_l2(out.cpu(), want)
+        print(f"B={B} bound={bound} call {call}: seeds rel-L2 {err:.3e}")
+        assert err <= 4 * EPS32
+        for i, (a, b) in enumerate(zip(got_stats, stats)):
+            assert abs(a - b) <= 4 * EPS32 * max(abs(b), scale[i]) + 1e-30, (i, a, b)
+        assert int(cl.buf[4 + 2 * 2 * 64:].view(torch.int32)[0].item()) == 0   # the ticket is left zero
+        out2, st2 = cl.run(qraw.cuda(), tq.cuda(), bound)
+        assert torch.equal(out, out2) and st2.cpu().double().tolist() == got_stats
+    bad = torch.zeros(hb.DSAC_STATS_FLOATS + 1, device="cuda")
+    q = torch.zeros(22, 2, device="cuda")
+    assert hb.lib().gops_dsac_critic_loss(q.data_ptr(), q.data_ptr(), 22, 1, q.clone().data_ptr(), bad.data_ptr() + 4, None) == -1
+
+
+def _loss_q(alg, tb):
+    return float(tb["Loss/Critic loss-RL iter"]) if type(alg).__name__ == "SAC" else float(alg.loss_q)
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("name", ONE_UPDATE)
+def test_one_update_matches_the_reference(name, fused):
+    alg, g, meta = load_alg(name, use_gpu=True, fused_target=fused)
+    names = Q_NAMES[meta["cfg"]["alg"]]
+    data = batch_of(g)
+    tb, info = alg.get_remote_update_info(data, 0)
+    assert alg.backup_path == ("fused" if fused else "composed")
+    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
+    tb_keys = [k for k in g if k.startswith("tb/")]
+    assert {k for k in tb if not k.startswith("Time/")} == {k[3:] for k in tb_keys}   # the reference's keys
+    for k in tb_keys:
+        assert close(tb[k[3:]], g[k]), (k, float(tb[k[3:]]), float(g[k]))
+    assert close(_loss_q(alg, tb), g["loss_q"]) and close(tb["Loss/Actor loss-RL iter"], g["loss_pi"])
+    batch = alg._batch(data)
+    res = _fused(alg, batch) if fused else dict(zip(OUT, alg._backup_composed(batch)))
+    for k, key in (("backup", "backup"), ("a2", "a2"), ("logp", "logp_next"), ("q_targ", "q_targ")):
+        assert rel_l2(res[k].cpu(), g[key]) < TOL, k
+    assert set(info) == {f"{n}_grad" for n in names + ("policy",)} | {"iteration"} | ({"log_alpha_grad"} if alg.auto_alpha else set())
+    for n in names + ("policy",):
+        for i, gr in enumerate(info[f"{n}_grad"]):
+            assert rel_l2(gr.cpu(), g[f"{n}_grad/{i}"]) < TOL, (n, i, rel_l2(gr.cpu(), g[f"{n}_grad/{i}"]))
+    if alg.auto_alpha:
+        assert close(info["log_alpha_grad"], g["log_alpha_grad"])
+    before = {k: v.detach().clone() for k, v in alg.networks.state_dict().items()}
+    alg.remote_update(info)
+    after = alg.networks.state_dict()
+    assert all(torch.isfinite(p).all() for p in after.values())
+    assert all((after[k] - before[k]).abs().max() > 0 for k in before if "lim" not in k and (alg.auto_alpha or k != "log_alpha"))
+
+
+@pytest.mark.parametrize("name", ["sac_pend_relu", "sac_lqs4a2_gelu", "dsac_pend_relu_bound", "dsac_lqs4a2_gelu_nobound"])
+def test_fused_and_composed_updates_agree(name):
+    out = {}
+    for fused in (True, False):
+        alg, g, meta = load_alg(name, use_gpu=True, fused_target=fused)
+        _, info = alg.get_remote_update_info(batch_of(g), 0)
+        out[fused] = {n: [t.clone() for t in v] for n, v in info.items() if n.endswith("_grad") and n != "log_alpha_grad"}
+    _check_backup(alg, batch_of(g), name)
+    for n in out[True]:
+        for a, b in zip(out[True][n], out[False][n]):
+            assert rel_l2(a.cpu(), b.cpu()) <= 1e-5, n
+
+
+@pytest.mark.parametrize("name", FIVE_UPDATES)
+def test_five_updates_match_the_reference(name):
+    """Five `local_update` calls with the reference's own draws handed in: every parameter and log_alpha after each call.  SAC steps
+    everything every time; DSAC (delay_update = 2) keeps the bits of policy, log_alpha and both targets on iterations 1 and 3."""
+    alg, g, meta = load_alg(name, use_gpu=True, prefix="sd0/")
+    dsac = meta["cfg"]["alg"] == "DSAC"
+    assert alg.tau == 0.05 and (not dsac or alg.delay_update == 2)
+    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
+    delayed = lambda key: key == "log_alpha" or key.startswith("policy.") or "_target." in key   # noqa: E731
+    for k in range(5):
+        before = {key: v.detach().clone() for key, v in alg.networks.state_dict().items()}
+        tb = alg.local_update(batch_of(g, f"in{k}/"), k)
+        assert close(tb["Loss/Actor loss-RL iter"], g[f"loss_pi{k}"]), k
+        if not dsac:
+            assert close(tb["Loss/Critic loss-RL iter"], g[f"loss_q{k}"]), k
+        for key, p in alg.networks.state_dict().items():
+            assert rel_l2(p.cpu().double(), g[f"sd{k + 1}/{key}"]) < TOL, (k, key)
+            if "lim" not in key:
+                assert torch.equal(p, before[key]) == (dsac and delayed(key) and k % 2 == 1), (k, key)
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_graph_replay_equals_eager(name, monkeypatch):
+    B = 70
+
+    def run(mode):
+        monkeypatch.setenv("GOPS_HIP_GRAPH", mode)
+        alg = _alg(name, 3, 1, [32, 16], "relu", seed=4)
+        logs = []
+        for it in range(14):
+            data = {k: v for k, v in _data(B, 3, 1, seed=100 + it).items() if not k.startswith(("eps_", "z_"))}   # the algorithm's own draws
+            logs.append(dict(alg.local_update(data, it)))
+        return alg, logs
+
+    eager, log_e = run("0")
+    graph, log_g = run("1")
+    assert all(c.graph is not None for c in graph._graphs.values()) and len(graph._graphs) == (1 if name == "SAC" else 2)
+    assert all(c.graph is None for c in eager._graphs.values())
+    for (ne, pe), (ng, pg) in zip(eager.networks.named_parameters(), graph.networks.named_parameters()):
+        assert ne == ng and torch.equal(pe, pg), ne
+    for a, b in zip(log_e, log_g):
+        for k in a:
+            if not k.startswith("Time/"):
+                assert float(a[k]) == float(b[k]), k
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_default_backup_path_and_shape_refusals(name):
+    """Up to 64-wide: the one-launch backup; 256-wide: composed unless forced; a 272-wide layer falls back to composed."""
+    data = _data(22, 3, 1)
+    for hidden, over, want in (([64, 64], {}, "fused"), ([256, 256], {}, "composed"), ([256, 256], dict(fused_target="force"), "fused"),
+                               ([64, 64], dict(fused_target=False), "composed"), ([272], {}, "composed"), ([272], dict(fused_target="force"), "composed")):
+        alg = _alg(name, 3, 1, hidden, "relu", **over)
+        alg.get_remote_update_info(data, 0)
+        assert alg.backup_path == want, (hidden, over)
+
+
+@pytest.mark.parametrize("name", ["SAC", "DSAC"])
+def test_end_to_end(name, tmp_path):
+    """OffSerialTrainer + replay_buffer + DeviceEnvSampler (the stochastic policy's own samples) on gym_pendulum: finite losses,
+    every online network moved, the targets lag behind."""
+    from gops_amd.create_pkg.create_buffer import create_buffer
+    from gops_amd.create_pkg.create_env_model import create_env_model
+    from gops_amd.create_pkg.create_trainer import create_trainer
+    from gops_amd.trainer.sampler.device_env_sampler import DeviceEnvSampler
+    torch.manual_seed(0)
+    kw = dict(algorithm=name, trainer="off_serial_trainer", seed=0, cnn_shared=False, env_id="gym_pendulum", obsv_dim=3, action_dim=1,
+              action_type="continu", action_low_limit=-2 * np.ones(1, dtype=np.float32), action_high_limit=2 * np.ones(1, dtype=np.float32),
+              policy_func_type="MLP", policy_func_name="StochaPolicy", policy_hidden_sizes=[64, 64], policy_hidden_activation="relu",
+              policy_act_distribution="TanhGaussDistribution", policy_learning_rate=1e-3, policy_min_log_std=-20, policy_max_log_std=0.5,
+              value_func_type="MLP", value_func_name="ActionValue" if name == "SAC" else "ActionValueDistri", value_hidden_sizes=[64, 64],
+              value_hidden_activation="relu", value_learning_rate=1e-3, q_learning_rate=1e-3, alpha_learning_rate=3e-4, gamma=0.99,
+              tau=0.005, auto_alpha=True, bound=True, delay_update=2, use_gpu=True,
+              buffer_name="replay_buffer", buffer_max_size=4096, buffer_warm_size=512, replay_batch_size=64,
+              sample_interval=1, additional_info={}, max_iteration=8, log_save_interval=1000, apprfunc_save_interval=1000,
+              eval_interval=10 ** 9, save_folder=str(tmp_path), ini_network_dir=None)
+    alg = create_alg(**kw)
+    alg.networks.to("cuda")
+    start = {k: v.detach().clone() for k, v in alg.networks.state_dict().items()}
+    model = create_env_model(**kw)
+    smp = DeviceEnvSampler(dict(env_id="gym_pendulum"), model, n_envs=128, steps_per_sample=2, max_episode_steps=50, seed=3,
+                           env_step="model")   # (gym_pendulum's data environment is not restated in the step kernel)
+    smp.networks = alg.networks
+    trainer = create_trainer(alg, smp, create_buffer(**kw), None, **kw)
+    for _ in range(6):
+        trainer.step()
+        trainer.iteration += 1
+    assert alg.backup_path == "fused"
+    assert all(np.isfinite(float(v)) for v in alg.tb_info.values())
+    nets = alg.networks.state_dict()
+    assert all(torch.isfinite(p).all() for p in nets.values())
+    for key, p in nets.items():
+        if "lim" in key:
+            continue
+        assert not torch.equal(p, start[key]), key
+        if "_target." in key:   # moved, but by less than its online twin
+            online = nets[key.replace("_target", "")]
+            assert (p - start[key]).abs().max() < (online - start[key]).abs().max(), key
