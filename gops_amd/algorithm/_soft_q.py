@@ -1,4 +1,4 @@
-"""What SAC and DSAC share on the HIP kernels: one update = soft Q backup (no grad), critic regression, actor gradient through the
+"""What SAC, DSAC and DSAC-T share on the HIP kernels: one update = soft Q backup (no grad), critic regression, actor gradient through the
 live critic(s), temperature gradient, Adam per network, Polyak on the targets.
 
 Where the arithmetic runs:
@@ -11,8 +11,8 @@ Where the arithmetic runs:
 The temperature lives on the device (`log_alpha`; the kernels form exp themselves), so `local_update` replays as a HIP graph.
 
 The draws the result depends on are INPUTS of the update: `data["eps_new"]` [B, A] (the policy sample at obs), `data["eps_next"]`
-[B, A] (the policy sample at obs2) and, for DSAC, `data["z_next"]` [B] (the target critic's return sample); when the batch has none
-they are drawn on the device from a generator this object owns (seed + index), before the graph.
+[B, A] (the policy sample at obs2) and, for DSAC and DSAC-T, `data["z_next"]` (the target critics' return samples: a class's
+`_draws`); when the batch has none they are drawn on the device from a generator this object owns (seed + index), before the graph.
 """
 import time
 from typing import Tuple
@@ -22,7 +22,7 @@ import torch
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm._actor_critic import FUSED_MAX_WIDTH, ActorCriticBase
 from gops_amd.algorithm.base import batch_to_device, cuda_device_of, grad_buffers
-from gops_amd.apprfunc.mlp import StochaPolicy
+from gops_amd.apprfunc.mlp import ActionValueDistri, StochaPolicy
 from gops_amd.utils.act_distribution import TanhGaussDistribution
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
@@ -30,7 +30,7 @@ from gops_amd.utils.tensorboard_setup import tb_tags
 
 
 def refusal(alg: str, value_name: str, value_words: str, kwargs: dict):
-    """Why `create_alg` cannot build SAC / DSAC from these arguments, or None (POLY / LipsNet are refused before this is asked)."""
+    """Why `create_alg` cannot build SAC / DSAC / DSAC-T from these arguments, or None (POLY / LipsNet are refused before this is asked)."""
     if kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
         return f"{alg} runs MLP networks only (policy_func_type {kwargs.get('policy_func_type')!r}, value_func_type {kwargs.get('value_func_type')!r})"
     if kwargs.get("policy_func_name") != "StochaPolicy" or kwargs.get("policy_act_distribution") != "TanhGaussDistribution":
@@ -56,10 +56,12 @@ def refusal(alg: str, value_name: str, value_words: str, kwargs: dict):
 class SoftQBase(ActorCriticBase):
     _q_names: Tuple[str, ...] = ()
     _value_cls = None                  # the critics' module class
-    _distri = False                    # (mean, softplus std) critic heads with a return sample (DSAC)
+    _distri = False                    # the backup samples the return of ONE (mean, softplus std) critic (DSAC: `gops_soft_q_backup`)
     _policy_at_obs2 = "policy"         # the policy the backup samples at obs2
     _polyak_names: Tuple[str, ...] = ()
     _OUT: Tuple[str, ...] = ()         # the update's output vector, in this order
+    _draws = (("eps_new", lambda B, A: (B, A)), ("eps_next", lambda B, A: (B, A)))   # (name, shape): the update's random inputs
+    _signature_terms: Tuple[str, ...] = ()   # further attributes a captured graph depends on
 
     def _init_soft(self, index: int, fused_target, kwargs: dict):
         nets, name = self.networks, type(self).__name__
@@ -129,13 +131,12 @@ class SoftQBase(ActorCriticBase):
         device = cuda_device_of(self.networks)
         batch = batch_to_device(data, device, ("obs", "act", "rew", "obs2", "done"))
         B, A = batch["act"].shape
-        draws = (("eps_new", (B, A)), ("eps_next", (B, A))) + ((("z_next", (B,)),) if self._distri else ())
-        for name, shape in draws:   # the caller's draws, or this object's - before the graph
+        for name, shape in self._draws:   # the caller's draws, or this object's - before the graph
             x = data.get(name)
             if x is None:
                 if self._noise_gen is None or self._noise_gen.device != device:
                     self._noise_gen = torch.Generator(device=device).manual_seed(self._noise_seed)
-                x = torch.randn(shape, generator=self._noise_gen, device=device, dtype=torch.float32)
+                x = torch.randn(shape(B, A), generator=self._noise_gen, device=device, dtype=torch.float32)
             batch[name] = x.to(device=device, dtype=torch.float32).contiguous()
         return batch
 
@@ -149,6 +150,7 @@ class SoftQBase(ActorCriticBase):
         nets = self.networks
         return (step_policy, self.fused_target, tuple((k, tuple(v.shape)) for k, v in batch.items()), float(self.gamma), float(self.tau),
                 bool(self.auto_alpha), float(self.alpha), float(self.target_entropy), bool(getattr(self, "bound", False)),
+                tuple(float(getattr(self, n)) for n in self._signature_terms),
                 tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in nets.parameters()),
                 tuple(o.storage_signature() for o in self._optimizers(True)),
                 tuple(sorted(obj.workspace.data_ptr() for obj in self._cache.values() if hasattr(obj, "workspace"))),
@@ -249,9 +251,11 @@ class SoftQBase(ActorCriticBase):
             share, q_min = [first, 1 - first], torch.min(qs[0], qs[1])
         else:
             share, q_min = [torch.ones_like(qs[0])], qs[0]
+        # (mean, softplus std) critic heads: the std output carries no gradient
+        zero = [torch.zeros_like(qs[0])] if issubclass(self._value_cls, ActionValueDistri) else []
         g_xq = None
         for net, w in zip(pi_nets, share):
-            cols = [w * (-1.0 / B)] + ([torch.zeros_like(w)] if self._distri else [])   # (the std output carries no gradient)
+            cols = [w * (-1.0 / B)] + zero
             g = net.backward_x(xq, torch.stack(cols, dim=-1))
             g_xq = g if g_xq is None else g_xq + g
         alpha = self._alpha_tensor(device)

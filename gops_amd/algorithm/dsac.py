@@ -66,6 +66,7 @@ class DSAC(SoftQBase):
     _q_names = ("q",)
     _value_cls = ActionValueDistri
     _distri = True
+    _draws = SoftQBase._draws + (("z_next", lambda B, A: (B,)),)
     _policy_at_obs2 = "policy_target"
     _polyak_names = ("q", "policy")
     _OUT = ("DSAC/critic_avg_q-RL iter", "DSAC/critic_avg_std-RL iter", tb_tags["loss_actor"], "DSAC/policy_mean-RL iter",

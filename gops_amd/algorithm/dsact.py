@@ -22,54 +22,25 @@ they are drawn on the device from a generator this object owns (seed + index), b
 """
 __all__ = ["ApproxContainer", "DSACT"]
 
-import time
 from copy import deepcopy
-from typing import Tuple
 
 import torch
 import torch.nn as nn
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm._actor_critic import FUSED_MAX_WIDTH, ActorCriticBase
-from gops_amd.algorithm.base import ApprBase, batch_to_device, cuda_device_of, grad_buffers
-from gops_amd.apprfunc.mlp import ActionValueDistri, StochaPolicy
+from gops_amd.algorithm import _soft_q
+from gops_amd.algorithm._actor_critic import FUSED_MAX_WIDTH
+from gops_amd.algorithm._soft_q import SoftQBase
+from gops_amd.algorithm.base import ApprBase, grad_buffers
+from gops_amd.apprfunc.mlp import ActionValueDistri
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
-from gops_amd.utils.act_distribution import TanhGaussDistribution
 from gops_amd.utils.common_utils import get_apprfunc_dict, make_adam
-from gops_amd.utils.hip_graph import StepGraphCache
-from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.utils.tensorboard_setup import tb_tags
-
-_DRAWS = ("eps_new", "eps_next", "z_next")
-# the update's output vector, in this order
-_OUT = ("DSAC2/critic_avg_q1-RL iter", "DSAC2/critic_avg_q2-RL iter", "DSAC2/critic_avg_std1-RL iter", "DSAC2/critic_avg_std2-RL iter",
-        "DSAC2/critic_avg_min_std1-RL iter", "DSAC2/critic_avg_min_std2-RL iter", tb_tags["loss_actor"], tb_tags["loss_critic"],
-        "DSAC2/policy_mean-RL iter", "DSAC2/policy_std-RL iter", "DSAC2/entropy-RL iter", "DSAC2/alpha-RL iter", "DSAC2/mean_std1",
-        "DSAC2/mean_std2")
 
 
 def refusal(kwargs: dict):
     """Why `create_alg` cannot build DSACT from these arguments, or None."""
-    if kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
-        return f"DSACT runs MLP networks only (policy_func_type {kwargs.get('policy_func_type')!r}, value_func_type {kwargs.get('value_func_type')!r})"
-    if kwargs.get("policy_func_name") != "StochaPolicy" or kwargs.get("policy_act_distribution") != "TanhGaussDistribution":
-        return (f"DSACT takes a stochastic policy with a tanh-Gaussian action distribution (policy_func_name 'StochaPolicy', "
-                f"policy_act_distribution 'TanhGaussDistribution'), not {kwargs.get('policy_func_name')!r} with "
-                f"{kwargs.get('policy_act_distribution')!r}: the kernels sample, squash and differentiate that distribution")
-    if kwargs.get("value_func_name") != "ActionValueDistri":
-        return f"DSACT takes a distributional action-value function (value_func_name 'ActionValueDistri'), not {kwargs.get('value_func_name')!r}"
-    for key in ("policy", "value"):
-        if kwargs.get(f"{key}_output_activation", "linear") != "linear":
-            return (f"DSACT takes networks with a linear output layer ({key}_output_activation "
-                    f"{kwargs.get(key + '_output_activation')!r}): the HIP kernels apply no output activation")
-    if hb.dtype_id(kwargs.get("mlp_dtype")) != 0:
-        return f"DSACT is fp32 only (mlp_dtype {kwargs.get('mlp_dtype')!r}): its kernels have no half-precision path"
-    if kwargs.get("buffer_name") == "prioritized_replay_buffer":
-        return "DSACT has no priorities (the reference's DSAC-T returns none): buffer_name 'prioritized_replay_buffer' is not supported"
-    trainer = kwargs.get("trainer")
-    if trainer is not None and trainer.startswith(("off_sync", "off_async")):
-        return f"DSACT runs under off_serial_trainer only: trainer {trainer!r} (data-parallel replicas) has not been run with its update_info"
-    return None
+    return _soft_q.refusal("DSACT", "ActionValueDistri", "a distributional action-value function", kwargs)
 
 
 class ApproxContainer(ApprBase):
@@ -98,22 +69,27 @@ class ApproxContainer(ApprBase):
         return self.policy.get_act_dist(logits)
 
 
-class DSACT(ActorCriticBase):
+class DSACT(SoftQBase):
     """gamma, tau, auto_alpha, alpha, delay_update, tau_b: the reference's arguments (dsact.py:91-102).  fused_target: the soft
     backup as one `gops_soft_backup` launch for networks up to 64 wide ("force": wherever the kernel holds the shape; False: always
-    composed from `gops_mlp_forward` calls and torch elementwise ops)."""
+    composed from `gops_mlp_forward` calls and torch elementwise ops).  Update API, draws, graph replay, the actor's and the
+    temperature's gradients: algorithm/_soft_q.py."""
 
     _q_names = ("q1", "q2")
+    _value_cls = ActionValueDistri
+    _policy_at_obs2 = "policy_target"
+    _polyak_names = ("q1", "q2", "policy")
+    _draws = SoftQBase._draws + (("z_next", lambda B, A: (2, B)),)
+    _signature_terms = ("tau_b",)
+    # the update's output vector, in this order
+    _OUT = ("DSAC2/critic_avg_q1-RL iter", "DSAC2/critic_avg_q2-RL iter", "DSAC2/critic_avg_std1-RL iter",
+            "DSAC2/critic_avg_std2-RL iter", "DSAC2/critic_avg_min_std1-RL iter", "DSAC2/critic_avg_min_std2-RL iter",
+            tb_tags["loss_actor"], tb_tags["loss_critic"], "DSAC2/policy_mean-RL iter", "DSAC2/policy_std-RL iter",
+            "DSAC2/entropy-RL iter", "DSAC2/alpha-RL iter", "DSAC2/mean_std1", "DSAC2/mean_std2")
 
     def __init__(self, index=0, fused_target=True, **kwargs):
         super().__init__(index, **kwargs)
         self.networks = ApproxContainer(**kwargs)
-        nets = self.networks
-        for n in self._q_names:
-            if not isinstance(getattr(nets, n), ActionValueDistri):
-                raise NotImplementedError(f"DSACT: value network {type(getattr(nets, n)).__name__} (MLP ActionValueDistri only)")
-        if type(nets.policy) is not StochaPolicy or nets.policy.action_distribution_cls is not TanhGaussDistribution:
-            raise NotImplementedError(f"DSACT: policy {type(nets.policy).__name__} (MLP StochaPolicy with TanhGaussDistribution only)")
         self.gamma = kwargs.get("gamma", 0.99)
         self.tau = kwargs.get("tau", 0.005)
         self.target_entropy = -kwargs["action_dim"]
@@ -121,13 +97,7 @@ class DSACT(ActorCriticBase):
         self.alpha = kwargs.get("alpha", 0.2)
         self.delay_update = kwargs.get("delay_update", 2)
         self.tau_b = kwargs.get("tau_b", self.tau)
-        self.per_flag = False
-        self.fused_target = "force" if fused_target == "force" else bool(fused_target)
-        self.backup_path = None   # "fused" / "composed": how the last update formed the targets
-        self._noise_seed = int(kwargs.get("seed") or 0) + int(index)
-        self._noise_gen = None
-        self.tb_info = dict()
-        self._cache, self._graphs, self._bufs = {}, {}, {}
+        self._init_soft(index, fused_target, kwargs)
 
     @property
     def adjustable_parameters(self):
@@ -147,96 +117,17 @@ class DSACT(ActorCriticBase):
     def _critic_loss_obj(self):
         return next((v for k, v in self._cache.items() if k[0] == "critic_loss"), None)
 
-    # ---- update API ----------------------------------------------------------------------------
-    def _optimizers(self, step_policy: bool):
-        nets = self.networks
-        opts = [nets.q1_optimizer, nets.q2_optimizer]
+    def _steps_policy(self, iteration):
+        return iteration % self.delay_update == 0
+
+    def _update(self, iteration):   # policy, temperature and all three targets together (dsact.py:335-358)
+        step_policy = self._steps_policy(iteration)
+        for opt in self._optimizers(step_policy):
+            opt.step()
         if step_policy:
-            opts += [nets.policy_optimizer] + ([nets.alpha_optimizer] if self.auto_alpha else [])
-        return opts
-
-    def local_update(self, data: dict, iteration: int):
-        start_time = time.time()
-        batch = self._batch(data)
-        step_policy = iteration % self.delay_update == 0
-        opts = self._optimizers(step_policy)
-
-        def update(b):
-            out = self._gradient_kernels(b)
-            self._update(iteration)
-            return out
-
-        cache = self._graphs.setdefault(step_policy, StepGraphCache())
-        out = cache.run(self._signature(batch, step_policy), batch, update,
-                        before_replay=lambda: [o.sync_hyper() for o in opts], on_replay=lambda: [o.advance() for o in opts],
-                        work=batch["obs"].shape[0], on_capture_fail=lambda: [o.resync_device_state() for o in opts])
-        self._step_schedulers()
-        return self._result(out, data, start_time)
-
-    def get_remote_update_info(self, data: dict, iteration: int) -> Tuple[dict, dict]:
-        start_time = time.time()
-        tb_info = self._result(self._gradient_kernels(self._batch(data)), data, start_time)
-        nets = self.networks
-        update_info = {f"{n}_grad": [p.grad for p in getattr(nets, n).parameters()] for n in self._q_names + ("policy",)}
-        update_info["iteration"] = iteration
-        if self.auto_alpha:
-            update_info["log_alpha_grad"] = nets.log_alpha.grad
-        return tb_info, update_info
-
-    def remote_update(self, update_info: dict):
-        nets = self.networks
-        for n in self._q_names + ("policy",):
-            for p, grad in zip(getattr(nets, n).parameters(), update_info[f"{n}_grad"]):
-                p.grad = grad
-        if self.auto_alpha:
-            nets.log_alpha.grad = update_info["log_alpha_grad"]
-        self._update(update_info["iteration"])
-        self._step_schedulers()
-
-    def _batch(self, data: dict):
-        device = cuda_device_of(self.networks)
-        batch = batch_to_device(data, device, ("obs", "act", "rew", "obs2", "done"))
-        B, A = batch["act"].shape
-        for name, shape in zip(_DRAWS, ((B, A), (B, A), (2, B))):   # the caller's draws, or this object's - before the graph
-            x = data.get(name)
-            if x is None:
-                if self._noise_gen is None or self._noise_gen.device != device:
-                    self._noise_gen = torch.Generator(device=device).manual_seed(self._noise_seed)
-                x = torch.randn(shape, generator=self._noise_gen, device=device, dtype=torch.float32)
-            batch[name] = x.to(device=device, dtype=torch.float32).contiguous()
-        return batch
-
-    def _result(self, out: torch.Tensor, data: dict, start_time: float):
-        tb_info = {key: scalar(out, i) for i, key in enumerate(_OUT)}
-        tb_info[tb_tags["alg_time"]] = (time.time() - start_time) * 1000
-        self.tb_info = tb_info
-        return tb_info
-
-    def _signature(self, batch, step_policy):
-        nets = self.networks
-        return (step_policy, self.fused_target, tuple((k, tuple(v.shape)) for k, v in batch.items()), float(self.gamma), float(self.tau),
-                float(self.tau_b), bool(self.auto_alpha), float(self.alpha), float(self.target_entropy),
-                tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in nets.parameters()),
-                tuple(o.storage_signature() for o in self._optimizers(True)),
-                tuple(sorted(obj.workspace.data_ptr() for obj in self._cache.values() if hasattr(obj, "workspace"))),
-                tuple(sorted(t.data_ptr() for t in self._bufs.values())))
-
-    def _update(self, iteration):
-        nets = self.networks
-        nets.q1_optimizer.step()
-        nets.q2_optimizer.step()
-        if iteration % self.delay_update == 0:   # policy, temperature and all three targets together (dsact.py:335-358)
-            nets.policy_optimizer.step()
-            if self.auto_alpha:
-                nets.alpha_optimizer.step()
             self._polyak()
 
     # ---- kernels -------------------------------------------------------------------------------
-    def _alpha_tensor(self, device) -> torch.Tensor:
-        if self.auto_alpha:
-            return self.networks.log_alpha.detach().exp()
-        return self._buf(f"alpha={float(self.alpha)!r}", (), device, fill=self.alpha)
-
     def _soft_backup(self, B: int, device) -> hb.SoftBackup:
         nets = self.networks
         pol = nets.policy_target.hip_mlp()
@@ -289,7 +180,7 @@ class DSACT(ActorCriticBase):
         """Enqueue one compute_gradient; returns the update's scalars (`_OUT`) as one device tensor, without synchronising."""
         nets = self.networks
         o, a = batch["obs"], batch["act"]
-        B, O, device = o.shape[0], o.shape[1], o.device
+        B, device = o.shape[0], o.device
         target_q, target_q_sample = self._targets(batch)
 
         # ---- critics: variance-weighted regression (dsact.py:284-301) ----------------------------------
@@ -307,32 +198,5 @@ class DSACT(ActorCriticBase):
             gw, gb = grad_buffers(getattr(nets, n))
             net.backward(x, seed[i], gw, gb)
 
-        # ---- actor: mean(alpha logp - min(q1, q2)) through both live critics, their parameters frozen (dsact.py:315-321) ----
-        pol = nets.policy
-        key = ("tanh_gauss", str(device))
-        tg = self._cache.get(key)
-        if tg is None:
-            tg = self._cache[key] = hb.TanhGaussHead(pol.act_low_lim.cpu().numpy(), pol.act_high_lim.cpu().numpy(), pol.min_log_std,
-                                                     pol.max_log_std, device)
-        pol_o = self._net("policy@o", pol, B, device)
-        head = pol_o.forward(o)
-        new_act, _, tstats = tg.forward(head, batch["eps_new"], self.target_entropy, act=self._buf("new_act", a.shape, device),
-                                        logp=self._buf("new_logp", (B,), device))
-        xq = torch.cat([o, new_act], dim=-1)
-        pi_nets = [self._net(f"{n}@pi", getattr(nets, n), B, device) for n in self._q_names]
-        m1, m2 = (net.forward(xq)[:, 0] for net in pi_nets)
-        first = (m1 <= m2).to(torch.float32)   # the row's seed goes to whichever mean is the minimum
-        zero = torch.zeros_like(first)
-        g_xq = (pi_nets[0].backward_x(xq, torch.stack((first * (-1.0 / B), zero), dim=-1))
-                + pi_nets[1].backward_x(xq, torch.stack(((1 - first) * (-1.0 / B), zero), dim=-1)))
-        alpha = self._alpha_tensor(device)
-        g_head = tg.backward(head, batch["eps_new"], g_xq[:, O:].contiguous(), (alpha / B).expand(B).contiguous())
-        gw, gb = grad_buffers(pol)
-        pol_o.backward(o, g_head, gw, gb)
-        if self.auto_alpha:   # loss_alpha = -log_alpha mean(logp + target_entropy)   (dsact.py:323-329)
-            if nets.log_alpha.grad is None:
-                nets.log_alpha.grad = torch.zeros_like(nets.log_alpha)
-            nets.log_alpha.grad.copy_(tstats[3])
-
-        loss_policy = alpha * tstats[0] - torch.min(m1, m2).mean()
+        loss_policy, tstats, alpha, _ = self._actor(batch)
         return torch.cat([stats[1:7], torch.stack([loss_policy, stats[0], tstats[1], tstats[2], -tstats[0], alpha]), stats[7:9]])

@@ -17,6 +17,10 @@
 // (one thread per (row, action dimension) forms that dimension's mean and log std), two critics with (mean, softplus std) heads.
 // soft_q_backup_kernel: SAC's and DSAC's soft Q backup on the same tile and policy head - one or two scalar critics with their minimum,
 // or one critic with a (mean, softplus std) head and a clipped return sample.
+// What the three kernels share is stated once and inlined into each: the tile prologue (ac_tile), the hidden layers and the head
+// staging (ac_hidden, ac_stage_head, ac_head_dot), and for the two soft kernels the policy head (soft_policy_head, its scalar
+// arithmetic in soft_math.h), the distributional critic head (distri_head) and the row's entropy terms (soft_entropy_terms).  The
+// host side likewise: one description of the nets (AcShape), one plan, one fill of AcParams' nets, one row-count dispatch.
 // ac_critic_loss_kernel: gradient seeds, losses, mean(q) and |q - backup| of the critic regression in one launch; sums in double
 // in the fixed order of block_reduce.h (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
 #include <stdint.h>
@@ -26,6 +30,7 @@
 
 #include "block_reduce.h"
 #include "launchers.h"
+#include "soft_math.h"
 
 namespace {
 
@@ -80,27 +85,63 @@ int ac_check(const GopsAcBackup* d, int B) {
     return rc;
 }
 
+// The stochastic-policy descriptions (gops_soft_backup, gops_soft_q_backup): a policy with 2 A outputs (means, then log stds) and
+// n_q critics of `out` outputs on (obs, action).
+int soft_check_nets(const GopsMlp& policy, const GopsMlp* q, int n_q, int out) {
+    if (policy.n_layers < 1 || policy.n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
+    const int O = policy.sizes[0], A2 = policy.sizes[policy.n_layers], A = A2 / 2;
+    if (O < 1 || A < 1 || (A2 & 1) || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (O + A > AC_MAX_IN) return GOPS_ERR_UNSUPPORTED;
+    int rc = ac_check_net(policy, O, 2 * A);
+    for (int i = 0; i < n_q && rc == GOPS_OK; ++i) rc = ac_check_net(q[i], O + A, out);
+    return rc;
+}
+
+int soft_check(const GopsSoftBackup* d, int B) {
+    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
+    return soft_check_nets(d->policy, d->q, 2, 2);
+}
+
+int soft_q_check(const GopsSoftQBackup* d, int B) {
+    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
+    if (d->n_q < 1 || d->n_q > 2 || d->distri < 0 || d->distri > 1) return GOPS_ERR_BAD_ARG;
+    if (d->distri && d->n_q == 2) return GOPS_ERR_UNSUPPORTED;   // gops_soft_backup's case
+    return soft_check_nets(d->policy, d->q, d->n_q, d->distri ? 2 : 1);
+}
+
+// What the LDS plan and the kernels' nets are made from - `nets`: the policy and the n_q critics; O / A: observation and action
+// width; `extra`: floats per tile row kept between the networks besides in0, in front of the weight chunk.
+struct AcShape {
+    const GopsMlp* nets[3];
+    int n_q, O, A, extra;
+};
+AcShape ac_shape(const GopsAcBackup& d) {
+    return {{&d.policy, &d.q[0], &d.q[1]}, d.n_q, d.policy.sizes[0], d.policy.sizes[d.policy.n_layers], 0};
+}
+AcShape soft_shape(const GopsMlp& policy, const GopsMlp* q, int n_q) {
+    const int A = policy.sizes[policy.n_layers] / 2;
+    return {{&policy, &q[0], &q[1]}, n_q, policy.sizes[0], A, 2 * A};   // extra: the log-probability terms, A doubles per row
+}
+
 inline int ac_up4(int x) { return (x + 3) & ~3; }
 
 // LDS plan for tiles of R rows within `limit` bytes; every hidden layer must get chunks of at least `min_nc` features (or the
 // whole layer).  Fills the offsets and the chunk sizes; returns the dynamic LDS bytes, 0 when it does not fit.
-// `nets`: the policy and the n_q critics; O / A: observation and action width; `extra`: floats per tile row kept between the
-// networks besides in0 (the soft backup's per-dimension log-probability terms), in front of the weight chunk.
-size_t ac_plan(const GopsMlp* const* nets, int n_q, int O, int A, int extra, int R, size_t limit, int min_nc, AcParams& p) {
+size_t ac_plan(const AcShape& sh, int R, size_t limit, int min_nc, AcParams& p) {
     int maxh = 0;
-    for (int n = 0; n <= n_q; ++n)
-        for (int j = 1; j < nets[n]->n_layers; ++j) maxh = std::max(maxh, (int)nets[n]->sizes[j]);
-    p.ld0 = (O + A) | 1;
+    for (int n = 0; n <= sh.n_q; ++n)
+        for (int j = 1; j < sh.nets[n]->n_layers; ++j) maxh = std::max(maxh, (int)sh.nets[n]->sizes[j]);
+    p.ld0 = (sh.O + sh.A) | 1;
     p.ldx = maxh | 1;
     p.xa_off = ac_up4(R * p.ld0);
     p.xb_off = p.xa_off + ac_up4(R * p.ldx);
     p.e_off = p.xb_off + ac_up4(R * p.ldx);
-    p.w_off = p.e_off + ac_up4(R * extra);   // 16-byte aligned: the weight quads are read as one f32x4
+    p.w_off = p.e_off + ac_up4(R * sh.extra);   // 16-byte aligned: the weight quads are read as one f32x4
     const long long wfloats = (long long)(limit / sizeof(float)) - p.w_off;
     if (wfloats <= 0) return 0;
     long long used = 0;
-    for (int n = 0; n <= n_q; ++n) {
-        const GopsMlp& m = *nets[n];
+    for (int n = 0; n <= sh.n_q; ++n) {
+        const GopsMlp& m = *sh.nets[n];
         for (int j = 0; j < m.n_layers - 1; ++j) {
             const int K = m.sizes[j], N = m.sizes[j + 1];
             int nc = (int)std::min<long long>(N, (wfloats / (K + 1)) & ~15LL);
@@ -117,17 +158,41 @@ size_t ac_plan(const GopsMlp* const* nets, int n_q, int O, int A, int extra, int
 
 // Tile rows and LDS bytes for a description: large batches take 64-row tiles (a weight chunk is staged once per 64 rows), small
 // ones 16-row tiles (more workgroups); within a tile size, the plan that leaves room for a second workgroup on the CU comes first.
-size_t ac_choose(const GopsMlp* const* nets, int n_q, int O, int A, int extra, int B, AcParams& p, int& R) {
+size_t ac_choose(const AcShape& sh, int B, AcParams& p, int& R) {
     for (R = B >= 16384 ? 64 : B >= 2048 ? 32 : 16; R >= 16; R >>= 1) {
-        size_t lds = ac_plan(nets, n_q, O, A, extra, R, AC_LDS_TWO, 64, p);
-        if (lds == 0) lds = ac_plan(nets, n_q, O, A, extra, R, AC_LDS_LIMIT, 16, p);
+        size_t lds = ac_plan(sh, R, AC_LDS_TWO, 64, p);
+        if (lds == 0) lds = ac_plan(sh, R, AC_LDS_LIMIT, 16, p);
         if (lds != 0) return lds;
     }
     return 0;
 }
-size_t ac_choose(const GopsAcBackup& d, int B, AcParams& p, int& R) {
-    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
-    return ac_choose(nets, d.n_q, d.policy.sizes[0], d.policy.sizes[d.policy.n_layers], 0, B, p, R);
+
+// The workspace a checked description needs at batch B: 0 when no plan fits.
+size_t ac_workspace_bytes(const AcShape& sh, int B) {
+    AcParams p;
+    int R;
+    return ac_choose(sh, B, p, R) == 0 ? 0 : AC_WORKSPACE;
+}
+
+// The nets of a plan as the kernels read them, and what every description carries: batch, widths, action limits.
+void ac_fill(const AcShape& sh, int B, const float* act_low, const float* act_high, AcParams& p) {
+    for (int n = 0; n <= sh.n_q; ++n) {
+        const GopsMlp& m = *sh.nets[n];
+        AcNet& a = p.net[n];
+        a.nl = m.n_layers, a.act = m.hidden_act;
+        for (int j = 0; j <= a.nl; ++j) a.dims[j] = m.sizes[j];
+        for (int j = 0; j < a.nl; ++j) { a.W[j] = m.weight[j]; a.Bv[j] = m.bias[j]; }
+    }
+    p.n_q = sh.n_q, p.B = B, p.O = sh.O, p.A = sh.A;
+    for (int a = 0; a < p.A; ++a) p.act_low[a] = act_low[a], p.act_high[a] = act_high[a];
+}
+
+// kernel<R> for the tile rows a plan chose:   rows_dispatch(R, [&]<int RR>() { launch_with_lds(kernel<RR>, ...); })
+template <typename F>
+void rows_dispatch(int R, F&& launch) {
+    if (R == 64) launch.template operator()<64>();
+    else if (R == 32) launch.template operator()<32>();
+    else launch.template operator()<16>();
 }
 
 // The hidden layers of `net` on the tile's rows: input `in0` (row stride ld0), activations ping-pong between xa and xb (row stride
@@ -222,22 +287,36 @@ __device__ __forceinline__ void ac_stage_head(const AcNet& net, float* wb) {
     __syncthreads();
 }
 
+// A workgroup's tile: the first batch row and how many of the R rows are inside the batch, the widths and row strides, the
+// sections of the LDS plan.
+struct AcTile {
+    int b0, nvalid, O, A, ld0, ldx;
+    float *in0, *xa, *xb, *extra, *wb;
+};
+
+// The tile prologue of every kernel here: carves the plan's sections out of `lds` and stages the tile's obs2 into in0.
+template <int R>
+__device__ __forceinline__ AcTile ac_tile(const AcParams& p, float* lds) {
+    AcTile t;
+    t.b0 = blockIdx.x * R;
+    t.nvalid = min(R, p.B - t.b0);
+    t.O = p.O, t.A = p.A, t.ld0 = p.ld0, t.ldx = p.ldx;
+    t.in0 = lds, t.xa = lds + p.xa_off, t.xb = lds + p.xb_off, t.extra = lds + p.e_off, t.wb = lds + p.w_off;
+    for (int idx = threadIdx.x; idx < R * t.O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
+        const int m = idx / t.O, k = idx - m * t.O;
+        t.in0[m * t.ld0 + k] = m < t.nvalid ? p.obs2[(size_t)(t.b0 + m) * t.O + k] : 0.f;
+    }
+    return t;
+}
+
 template <int R>
 __global__ __launch_bounds__(AC_THREADS) void ac_backup_kernel(const AcParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, r = tid % R, g = tid / R;
-    const int b0 = blockIdx.x * R;
-    const int nvalid = min(R, p.B - b0);
-    const int O = p.O, A = p.A, ld0 = p.ld0, ldx = p.ldx;
-    float* in0 = lds;
-    float* xa = lds + p.xa_off;
-    float* xb = lds + p.xb_off;
-    float* wb = lds + p.w_off;
+    const AcTile t = ac_tile<R>(p, lds);
+    const int b0 = t.b0, nvalid = t.nvalid, O = t.O, A = t.A, ld0 = t.ld0, ldx = t.ldx;
+    float *in0 = t.in0, *xa = t.xa, *xb = t.xb, *wb = t.wb;
 
-    for (int idx = tid; idx < R * O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
-        const int m = idx / O, k = idx - m * O;
-        in0[m * ld0 + k] = m < nvalid ? p.obs2[(size_t)(b0 + m) * O + k] : 0.f;
-    }
     double q_min = 0.0;   // of row r, in the threads with g == 0
 #pragma unroll 1
     for (int n = 0; n <= p.n_q; ++n) {
@@ -287,72 +366,78 @@ struct SoftParams {
     float *tq, *tqs, *logp;
 };
 
-__device__ __forceinline__ double softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }   // (torch's threshold)
+// The tanh-Gaussian policy at the tile's obs2, of both soft kernels: u = mean + std * eps, a2 = half * tanh(u) + mid into in0 behind
+// obs2 (and into p.a2), the dimension's share of log pi(a2 | obs2) into lp[g * R + r] (soft_math.h: tanh_gauss_dim).  Both are
+// published by the barrier at the top of the first critic's first chunk.
+template <int R>
+__device__ __forceinline__ void soft_policy_head(const SoftParams& sp, const AcTile& t, double* lp) {
+    const AcParams& p = sp.ac;
+    const int tid = threadIdx.x, r = tid % R, g = tid / R;
+    const int O = t.O, A = t.A, ld0 = t.ld0, ldx = t.ldx;
+    const AcNet& net = p.net[0];
+    const float* cur = ac_hidden<R>(net, t.in0, ld0, t.xa, t.xb, ldx, t.wb);
+    const int K = net.dims[net.nl - 1];
+    const float* wb = t.wb;
+    ac_stage_head(net, t.wb);
+    if (g < A) {
+        const float* xr = cur + r * ldx;
+        const double mean = ac_head_dot(xr, wb + g * K, K) + (double)wb[2 * A * K + g];
+        const double ls = ac_head_dot(xr, wb + (A + g) * K, K) + (double)wb[2 * A * K + A + g];
+        const double e = r < t.nvalid ? (double)sp.eps[(size_t)(t.b0 + r) * A + g] : 0.0;
+        const double lo = g == 0 ? p.act_low[0] : g == 1 ? p.act_low[1] : g == 2 ? p.act_low[2] : p.act_low[3];
+        const double hi = g == 0 ? p.act_high[0] : g == 1 ? p.act_high[1] : g == 2 ? p.act_high[2] : p.act_high[3];
+        const TanhGaussDim d = tanh_gauss_dim(mean, ls, e, lo, hi, sp.min_ls, sp.max_ls);
+        const float af = (float)d.act;
+        t.in0[r * ld0 + O + g] = af;
+        if (p.a2 != nullptr && r < t.nvalid) p.a2[(size_t)(t.b0 + r) * A + g] = af;
+        lp[g * R + r] = d.logp;
+    }
+}
+
+// (m, softplus s) of a distributional critic's row from its staged head (row-major [2][K], the two biases behind), stored to qt
+// unless that is null.
+__device__ __forceinline__ void distri_head(const float* xr, const float* wb, int K, float* qt, double& m, double& sd) {
+    m = ac_head_dot(xr, wb, K) + (double)wb[2 * K];
+    sd = softplus_d(ac_head_dot(xr, wb + K, K) + (double)wb[2 * K + 1]);
+    if (qt != nullptr) qt[0] = (float)m, qt[1] = (float)sd;
+}
+
+// log pi(a2 | obs2) of row r - its dimensions' terms in ascending order - and the temperature.
+template <int R>
+__device__ __forceinline__ void soft_entropy_terms(const SoftParams& sp, const double* lp, int A, int r, double& logp, double& alpha) {
+    logp = 0.0;
+    for (int a = 0; a < A; ++a) logp += lp[a * R + r];
+    alpha = sp.log_alpha != nullptr ? exp((double)*sp.log_alpha) : sp.alpha;
+}
 
 template <int R>
 __global__ __launch_bounds__(AC_THREADS) void soft_backup_kernel(const SoftParams sp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const AcParams& p = sp.ac;
     const int tid = threadIdx.x, r = tid % R, g = tid / R;
-    const int b0 = blockIdx.x * R;
-    const int nvalid = min(R, p.B - b0);
-    const int O = p.O, A = p.A, ld0 = p.ld0, ldx = p.ldx;
-    float* in0 = lds;
-    float* xa = lds + p.xa_off;
-    float* xb = lds + p.xb_off;
-    double* lp = reinterpret_cast<double*>(lds + p.e_off);
-    float* wb = lds + p.w_off;
-
-    for (int idx = tid; idx < R * O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
-        const int m = idx / O, k = idx - m * O;
-        in0[m * ld0 + k] = m < nvalid ? p.obs2[(size_t)(b0 + m) * O + k] : 0.f;
-    }
-    {   // ---- target policy: u = mean + std * eps, a2 = half * tanh(u) + mid, the dimension's share of log pi(a2 | obs2) ----
-        const AcNet& net = p.net[0];
-        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
-        const int K = net.dims[net.nl - 1];
-        ac_stage_head(net, wb);
-        if (g < A) {
-            const float* xr = cur + r * ldx;
-            const double mean = ac_head_dot(xr, wb + g * K, K) + (double)wb[2 * A * K + g];
-            const double ls = ac_head_dot(xr, wb + (A + g) * K, K) + (double)wb[2 * A * K + A + g];
-            const double sd = exp(fmin(fmax(ls, sp.min_ls), sp.max_ls));
-            const double e = r < nvalid ? (double)sp.eps[(size_t)(b0 + r) * A + g] : 0.0;
-            const double u = mean + sd * e, th = tanh(u), du = u - mean;
-            const double lo = g == 0 ? p.act_low[0] : g == 1 ? p.act_low[1] : g == 2 ? p.act_low[2] : p.act_low[3];
-            const double hi = g == 0 ? p.act_high[0] : g == 1 ? p.act_high[1] : g == 2 ? p.act_high[2] : p.act_high[3];
-            const double half = (hi - lo) / 2;
-            const float af = (float)(half * th + (hi + lo) / 2);
-            in0[r * ld0 + O + g] = af;   // (published, like lp, by the barrier at the top of the critic's first chunk)
-            if (p.a2 != nullptr && r < nvalid) p.a2[(size_t)(b0 + r) * A + g] = af;
-            // Normal(mean, std).log_prob(u) - log(1 + 1e-6 - tanh(u)^2) - log(half)      (act_distribution_type.py:41-51)
-            lp[g * R + r] = (-(du * du) / (2 * sd * sd) - log(sd) - 0.91893853320467274178) - log(1.0 + 1e-6 - th * th) - log(half);
-        }
-    }
+    const AcTile t = ac_tile<R>(p, lds);
+    const int b0 = t.b0, nvalid = t.nvalid;
+    double* lp = reinterpret_cast<double*>(t.extra);
+    soft_policy_head<R>(sp, t, lp);   // the target policy
     double m1 = 0.0, s1 = 0.0, m2 = 0.0, s2 = 0.0;   // of row r, in the threads with g == 0
 #pragma unroll 1
     for (int n = 1; n <= 2; ++n) {
         const AcNet& net = p.net[n];
-        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
+        const float* cur = ac_hidden<R>(net, t.in0, t.ld0, t.xa, t.xb, t.ldx, t.wb);
         const int K = net.dims[net.nl - 1];
-        ac_stage_head(net, wb);
+        ac_stage_head(net, t.wb);
         if (g == 0) {
-            const float* xr = cur + r * ldx;
-            const double m = ac_head_dot(xr, wb, K) + (double)wb[2 * K];
-            const double sd = softplus_d(ac_head_dot(xr, wb + K, K) + (double)wb[2 * K + 1]);
-            if (p.q_targ != nullptr && r < nvalid) {
-                float* qt = p.q_targ + ((size_t)(n - 1) * p.B + b0 + r) * 2;
-                qt[0] = (float)m, qt[1] = (float)sd;
-            }
+            float* qt = p.q_targ != nullptr && r < nvalid ? p.q_targ + ((size_t)(n - 1) * p.B + b0 + r) * 2 : nullptr;
+            double m, sd;
+            distri_head(cur + r * t.ldx, t.wb, K, qt, m, sd);
             if (n == 1) m1 = m, s1 = sd;
             else m2 = m, s2 = sd;
         }
     }
     if (g == 0 && r < nvalid) {
         const int b = b0 + r;
-        double logp = 0.0;
-        for (int a = 0; a < A; ++a) logp += lp[a * R + r];
-        const double alpha = sp.log_alpha != nullptr ? exp((double)*sp.log_alpha) : sp.alpha;
+        double logp, alpha;
+        soft_entropy_terms<R>(sp, lp, t.A, r, logp, alpha);
         const double z1 = fmin(fmax((double)sp.z[b], -3.0), 3.0), z2 = fmin(fmax((double)sp.z[(size_t)p.B + b], -3.0), 3.0);
         const double q_next = fmin(m1, m2), q_sample = m1 < m2 ? m1 + z1 * s1 : m2 + z2 * s2;
         const double rew = (double)p.rew[b], live = (1.0 - (double)p.done[b]) * p.gamma;
@@ -362,26 +447,9 @@ __global__ __launch_bounds__(AC_THREADS) void soft_backup_kernel(const SoftParam
     }
 }
 
-int soft_check(const GopsSoftBackup* d, int B) {
-    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
-    if (d->policy.n_layers < 1 || d->policy.n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
-    const int O = d->policy.sizes[0], A2 = d->policy.sizes[d->policy.n_layers], A = A2 / 2;
-    if (O < 1 || A < 1 || (A2 & 1) || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
-    if (O + A > AC_MAX_IN) return GOPS_ERR_UNSUPPORTED;
-    int rc = ac_check_net(d->policy, O, 2 * A);
-    for (int i = 0; i < 2 && rc == GOPS_OK; ++i) rc = ac_check_net(d->q[i], O + A, 2);
-    return rc;
-}
-
-size_t soft_choose(const GopsSoftBackup& d, int B, AcParams& p, int& R) {
-    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
-    const int A = d.policy.sizes[d.policy.n_layers] / 2;
-    return ac_choose(nets, 2, d.policy.sizes[0], A, 2 * A, B, p, R);   // extra: A doubles per row
-}
-
 // ---- SAC / DSAC: the soft Q backup (gops/algorithm/sac.py:214-223, dsac.py:199-252, the no-grad part) ------------------------------
-// soft_backup_kernel's tile, policy head and log-probability (restated here: that kernel stays as it is), then one or two scalar
-// critics with their minimum (distri = 0), or one critic with a (mean, softplus std) head and a clipped return sample (distri = 1).
+// soft_backup_kernel's tile, policy head and log-probability (the same helpers), then one or two scalar critics with their minimum
+// (distri = 0), or one critic with a (mean, softplus std) head and a clipped return sample (distri = 1).
 struct SoftQParams {
     SoftParams s;   // ac.n_q: the critics; tq: the backup; z: [B] (distri); ac.q_targ: [n_q, B], or [B, 2] = (m, s) with distri
     int distri;
@@ -393,58 +461,23 @@ __global__ __launch_bounds__(AC_THREADS) void soft_q_backup_kernel(const SoftQPa
     const SoftParams& sp = qp.s;
     const AcParams& p = sp.ac;
     const int tid = threadIdx.x, r = tid % R, g = tid / R;
-    const int b0 = blockIdx.x * R;
-    const int nvalid = min(R, p.B - b0);
-    const int O = p.O, A = p.A, ld0 = p.ld0, ldx = p.ldx;
-    float* in0 = lds;
-    float* xa = lds + p.xa_off;
-    float* xb = lds + p.xb_off;
-    double* lp = reinterpret_cast<double*>(lds + p.e_off);
-    float* wb = lds + p.w_off;
-
-    for (int idx = tid; idx < R * O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
-        const int m = idx / O, k = idx - m * O;
-        in0[m * ld0 + k] = m < nvalid ? p.obs2[(size_t)(b0 + m) * O + k] : 0.f;
-    }
-    {   // ---- the policy at obs2: u = mean + std * eps, a2 = half * tanh(u) + mid, the dimension's share of log pi(a2 | obs2) ----
-        const AcNet& net = p.net[0];
-        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
-        const int K = net.dims[net.nl - 1];
-        ac_stage_head(net, wb);
-        if (g < A) {
-            const float* xr = cur + r * ldx;
-            const double mean = ac_head_dot(xr, wb + g * K, K) + (double)wb[2 * A * K + g];
-            const double ls = ac_head_dot(xr, wb + (A + g) * K, K) + (double)wb[2 * A * K + A + g];
-            const double sd = exp(fmin(fmax(ls, sp.min_ls), sp.max_ls));
-            const double e = r < nvalid ? (double)sp.eps[(size_t)(b0 + r) * A + g] : 0.0;
-            const double u = mean + sd * e, th = tanh(u), du = u - mean;
-            const double lo = g == 0 ? p.act_low[0] : g == 1 ? p.act_low[1] : g == 2 ? p.act_low[2] : p.act_low[3];
-            const double hi = g == 0 ? p.act_high[0] : g == 1 ? p.act_high[1] : g == 2 ? p.act_high[2] : p.act_high[3];
-            const double half = (hi - lo) / 2;
-            const float af = (float)(half * th + (hi + lo) / 2);
-            in0[r * ld0 + O + g] = af;   // (published, like lp, by the barrier at the top of the critic's first chunk)
-            if (p.a2 != nullptr && r < nvalid) p.a2[(size_t)(b0 + r) * A + g] = af;
-            lp[g * R + r] = (-(du * du) / (2 * sd * sd) - log(sd) - 0.91893853320467274178) - log(1.0 + 1e-6 - th * th) - log(half);
-        }
-    }
+    const AcTile t = ac_tile<R>(p, lds);
+    const int b0 = t.b0, nvalid = t.nvalid;
+    double* lp = reinterpret_cast<double*>(t.extra);
+    soft_policy_head<R>(sp, t, lp);   // the policy at obs2
     double q_next = 0.0, s_next = 0.0;   // of row r, in the threads with g == 0: min_i q_i, or (m, s) of the one distributional critic
 #pragma unroll 1
     for (int n = 1; n <= p.n_q; ++n) {
         const AcNet& net = p.net[n];
-        const float* cur = ac_hidden<R>(net, in0, ld0, xa, xb, ldx, wb);
+        const float* cur = ac_hidden<R>(net, t.in0, t.ld0, t.xa, t.xb, t.ldx, t.wb);
         const int K = net.dims[net.nl - 1];
-        ac_stage_head(net, wb);
+        ac_stage_head(net, t.wb);
         if (g == 0) {
-            const float* xr = cur + r * ldx;
+            const float* xr = cur + r * t.ldx;
             if (qp.distri) {
-                q_next = ac_head_dot(xr, wb, K) + (double)wb[2 * K];
-                s_next = softplus_d(ac_head_dot(xr, wb + K, K) + (double)wb[2 * K + 1]);
-                if (p.q_targ != nullptr && r < nvalid) {
-                    float* qt = p.q_targ + (size_t)(b0 + r) * 2;
-                    qt[0] = (float)q_next, qt[1] = (float)s_next;
-                }
+                distri_head(xr, t.wb, K, p.q_targ != nullptr && r < nvalid ? p.q_targ + (size_t)(b0 + r) * 2 : nullptr, q_next, s_next);
             } else {
-                const double y = ac_head_dot(xr, wb, K) + (double)wb[K];
+                const double y = ac_head_dot(xr, t.wb, K) + (double)t.wb[K];
                 if (p.q_targ != nullptr && r < nvalid) p.q_targ[(size_t)(n - 1) * p.B + b0 + r] = (float)y;
                 q_next = n == 1 ? y : fmin(q_next, y);
             }
@@ -452,32 +485,12 @@ __global__ __launch_bounds__(AC_THREADS) void soft_q_backup_kernel(const SoftQPa
     }
     if (g == 0 && r < nvalid) {
         const int b = b0 + r;
-        double logp = 0.0;
-        for (int a = 0; a < A; ++a) logp += lp[a * R + r];
-        const double alpha = sp.log_alpha != nullptr ? exp((double)*sp.log_alpha) : sp.alpha;
+        double logp, alpha;
+        soft_entropy_terms<R>(sp, lp, t.A, r, logp, alpha);
         if (qp.distri) q_next += fmin(fmax((double)sp.z[b], -3.0), 3.0) * s_next;   // dsac.py:206-208
         sp.tq[b] = (float)((double)p.rew[b] + (1.0 - (double)p.done[b]) * p.gamma * (q_next - alpha * logp));   // sac.py:221, dsac.py:246
         if (sp.logp != nullptr) sp.logp[b] = (float)logp;
     }
-}
-
-int soft_q_check(const GopsSoftQBackup* d, int B) {
-    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
-    if (d->n_q < 1 || d->n_q > 2 || d->distri < 0 || d->distri > 1) return GOPS_ERR_BAD_ARG;
-    if (d->distri && d->n_q == 2) return GOPS_ERR_UNSUPPORTED;   // gops_soft_backup's case
-    if (d->policy.n_layers < 1 || d->policy.n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
-    const int O = d->policy.sizes[0], A2 = d->policy.sizes[d->policy.n_layers], A = A2 / 2;
-    if (O < 1 || A < 1 || (A2 & 1) || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
-    if (O + A > AC_MAX_IN) return GOPS_ERR_UNSUPPORTED;
-    int rc = ac_check_net(d->policy, O, 2 * A);
-    for (int i = 0; i < d->n_q && rc == GOPS_OK; ++i) rc = ac_check_net(d->q[i], O + A, d->distri ? 2 : 1);
-    return rc;
-}
-
-size_t soft_q_choose(const GopsSoftQBackup& d, int B, AcParams& p, int& R) {
-    const GopsMlp* nets[3] = {&d.policy, &d.q[0], &d.q[1]};
-    const int A = d.policy.sizes[d.policy.n_layers] / 2;
-    return ac_choose(nets, d.n_q, d.policy.sizes[0], A, 2 * A, B, p, R);   // extra: A doubles per row
 }
 
 // ---- critic regression: seeds, losses, mean(q), |q - backup| -------------------------------------------------------------------
@@ -523,44 +536,55 @@ static_assert(4 + 6 * ACL_BLOCKS + 1 <= GOPS_AC_LOSS_STATS_FLOATS, "stats: four 
 
 }  // namespace
 
+namespace {
+
+// What every backup entry point does between its argument checks and its launch: the plan (GOPS_ERR_UNSUPPORTED when none fits),
+// the workspace check, the fill of the plan's nets and widths.
+int ac_prepare(const AcShape& sh, int B, const float* act_low, const float* act_high, const void* ws, size_t ws_bytes, AcParams& p,
+               int& R, size_t& lds) {
+    lds = ac_choose(sh, B, p, R);
+    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < AC_WORKSPACE) return GOPS_ERR_WORKSPACE;
+    ac_fill(sh, B, act_low, act_high, p);
+    return GOPS_OK;
+}
+
+// The fields GopsSoftBackup and GopsSoftQBackup share, and the tensors both kernels take.
+template <typename Desc>
+void soft_fill(const Desc& d, const float* obs2, const float* rew, const float* done, const float* eps, const float* z, float* a2,
+               float* logp, float* q_targ, SoftParams& sp) {
+    AcParams& p = sp.ac;
+    p.gamma = d.gamma;
+    p.obs2 = obs2, p.rew = rew, p.done = done, p.a2 = a2, p.q_targ = q_targ;
+    sp.min_ls = d.min_log_std, sp.max_ls = d.max_log_std, sp.alpha = d.alpha, sp.log_alpha = d.log_alpha;
+    sp.eps = eps, sp.z = z, sp.logp = logp;
+}
+
+inline dim3 ac_grid(int B, int R) { return dim3((unsigned)((B + R - 1) / R)); }
+
+}  // namespace
+
 size_t ac_backup_workspace_bytes(const GopsAcBackup* d, int B) {
-    if (ac_check(d, B) != GOPS_OK) return 0;
-    AcParams p;
-    int R;
-    return ac_choose(*d, B, p, R) == 0 ? 0 : AC_WORKSPACE;
+    return ac_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(ac_shape(*d), B);
 }
 
 int ac_backup(const GopsAcBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* xi, float* backup,
               float* a2, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int rc = ac_check(d, B);
+    int rc = ac_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (!obs2 || !rew || !done || !backup || (d->smooth && !xi)) return GOPS_ERR_BAD_ARG;
     AcParams p;
     memset(&p, 0, sizeof(p));
     int R;
-    const size_t lds = ac_choose(*d, B, p, R);
-    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < AC_WORKSPACE) return GOPS_ERR_WORKSPACE;
-    const GopsMlp* nets[3] = {&d->policy, &d->q[0], &d->q[1]};
-    for (int n = 0; n <= d->n_q; ++n) {
-        AcNet& a = p.net[n];
-        a.nl = nets[n]->n_layers, a.act = nets[n]->hidden_act;
-        for (int j = 0; j <= a.nl; ++j) a.dims[j] = nets[n]->sizes[j];
-        for (int j = 0; j < a.nl; ++j) { a.W[j] = nets[n]->weight[j]; a.Bv[j] = nets[n]->bias[j]; }
-    }
-    p.n_q = d->n_q, p.smooth = d->smooth != 0, p.B = B;
-    p.O = d->policy.sizes[0], p.A = d->policy.sizes[d->policy.n_layers];
-    for (int a = 0; a < p.A; ++a) {
-        p.sq_low[a] = d->squash_low[a], p.sq_high[a] = d->squash_high[a];
-        p.act_low[a] = d->act_low[a], p.act_high[a] = d->act_high[a];
-    }
+    size_t lds;
+    rc = ac_prepare(ac_shape(*d), B, d->act_low, d->act_high, ws, ws_bytes, p, R, lds);
+    if (rc != GOPS_OK) return rc;
+    p.smooth = d->smooth != 0;
+    for (int a = 0; a < p.A; ++a) p.sq_low[a] = d->squash_low[a], p.sq_high[a] = d->squash_high[a];
     p.sigma = d->target_noise, p.clip = d->noise_clip, p.rscale = d->reward_scale, p.gamma = d->gamma;
     p.obs2 = obs2, p.rew = rew, p.done = done, p.xi = xi;
     p.backup = backup, p.a2 = a2, p.q_targ = q_targ;
-    const dim3 grid((unsigned)((B + R - 1) / R));
-    if (R == 64) launch_with_lds(ac_backup_kernel<64>, grid, dim3(AC_THREADS), lds, s, p);
-    else if (R == 32) launch_with_lds(ac_backup_kernel<32>, grid, dim3(AC_THREADS), lds, s, p);
-    else launch_with_lds(ac_backup_kernel<16>, grid, dim3(AC_THREADS), lds, s, p);
+    rows_dispatch(R, [&]<int RR>() { launch_with_lds(ac_backup_kernel<RR>, ac_grid(B, RR), dim3(AC_THREADS), lds, s, p); });
     return (int)hipGetLastError();
 }
 
@@ -572,81 +596,44 @@ int ac_critic_loss(const float* q, const float* backup, const float* weight, int
 }
 
 size_t soft_backup_workspace_bytes(const GopsSoftBackup* d, int B) {
-    if (soft_check(d, B) != GOPS_OK) return 0;
-    AcParams p;
-    int R;
-    return soft_choose(*d, B, p, R) == 0 ? 0 : AC_WORKSPACE;
+    return soft_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(soft_shape(d->policy, d->q, 2), B);
 }
 
 int soft_backup(const GopsSoftBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
                 float* tq, float* tqs, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int rc = soft_check(d, B);
+    int rc = soft_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (!obs2 || !rew || !done || !eps || !z || !tq || !tqs) return GOPS_ERR_BAD_ARG;
     SoftParams sp;
     memset(&sp, 0, sizeof(sp));
-    AcParams& p = sp.ac;
     int R;
-    const size_t lds = soft_choose(*d, B, p, R);
-    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < AC_WORKSPACE) return GOPS_ERR_WORKSPACE;
-    const GopsMlp* nets[3] = {&d->policy, &d->q[0], &d->q[1]};
-    for (int n = 0; n < 3; ++n) {
-        AcNet& a = p.net[n];
-        a.nl = nets[n]->n_layers, a.act = nets[n]->hidden_act;
-        for (int j = 0; j <= a.nl; ++j) a.dims[j] = nets[n]->sizes[j];
-        for (int j = 0; j < a.nl; ++j) { a.W[j] = nets[n]->weight[j]; a.Bv[j] = nets[n]->bias[j]; }
-    }
-    p.n_q = 2, p.B = B, p.O = d->policy.sizes[0], p.A = d->policy.sizes[d->policy.n_layers] / 2;
-    for (int a = 0; a < p.A; ++a) p.act_low[a] = d->act_low[a], p.act_high[a] = d->act_high[a];
-    p.gamma = d->gamma;
-    p.obs2 = obs2, p.rew = rew, p.done = done, p.a2 = a2, p.q_targ = q_targ;
-    sp.min_ls = d->min_log_std, sp.max_ls = d->max_log_std, sp.alpha = d->alpha, sp.log_alpha = d->log_alpha;
-    sp.eps = eps, sp.z = z, sp.tq = tq, sp.tqs = tqs, sp.logp = logp;
-    const dim3 grid((unsigned)((B + R - 1) / R));
-    if (R == 64) launch_with_lds(soft_backup_kernel<64>, grid, dim3(AC_THREADS), lds, s, sp);
-    else if (R == 32) launch_with_lds(soft_backup_kernel<32>, grid, dim3(AC_THREADS), lds, s, sp);
-    else launch_with_lds(soft_backup_kernel<16>, grid, dim3(AC_THREADS), lds, s, sp);
+    size_t lds;
+    rc = ac_prepare(soft_shape(d->policy, d->q, 2), B, d->act_low, d->act_high, ws, ws_bytes, sp.ac, R, lds);
+    if (rc != GOPS_OK) return rc;
+    soft_fill(*d, obs2, rew, done, eps, z, a2, logp, q_targ, sp);
+    sp.tq = tq, sp.tqs = tqs;
+    rows_dispatch(R, [&]<int RR>() { launch_with_lds(soft_backup_kernel<RR>, ac_grid(B, RR), dim3(AC_THREADS), lds, s, sp); });
     return (int)hipGetLastError();
 }
 
 size_t soft_q_backup_workspace_bytes(const GopsSoftQBackup* d, int B) {
-    if (soft_q_check(d, B) != GOPS_OK) return 0;
-    AcParams p;
-    int R;
-    return soft_q_choose(*d, B, p, R) == 0 ? 0 : AC_WORKSPACE;
+    return soft_q_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(soft_shape(d->policy, d->q, d->n_q), B);
 }
 
 int soft_q_backup(const GopsSoftQBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
                   float* backup, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int rc = soft_q_check(d, B);
+    int rc = soft_q_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (!obs2 || !rew || !done || !eps || (d->distri && !z) || !backup) return GOPS_ERR_BAD_ARG;
     SoftQParams qp;
     memset(&qp, 0, sizeof(qp));
-    SoftParams& sp = qp.s;
-    AcParams& p = sp.ac;
     int R;
-    const size_t lds = soft_q_choose(*d, B, p, R);
-    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < AC_WORKSPACE) return GOPS_ERR_WORKSPACE;
-    const GopsMlp* nets[3] = {&d->policy, &d->q[0], &d->q[1]};
-    for (int n = 0; n <= d->n_q; ++n) {
-        AcNet& a = p.net[n];
-        a.nl = nets[n]->n_layers, a.act = nets[n]->hidden_act;
-        for (int j = 0; j <= a.nl; ++j) a.dims[j] = nets[n]->sizes[j];
-        for (int j = 0; j < a.nl; ++j) { a.W[j] = nets[n]->weight[j]; a.Bv[j] = nets[n]->bias[j]; }
-    }
-    p.n_q = d->n_q, p.B = B, p.O = d->policy.sizes[0], p.A = d->policy.sizes[d->policy.n_layers] / 2;
-    for (int a = 0; a < p.A; ++a) p.act_low[a] = d->act_low[a], p.act_high[a] = d->act_high[a];
-    p.gamma = d->gamma;
-    p.obs2 = obs2, p.rew = rew, p.done = done, p.a2 = a2, p.q_targ = q_targ;
-    sp.min_ls = d->min_log_std, sp.max_ls = d->max_log_std, sp.alpha = d->alpha, sp.log_alpha = d->log_alpha;
-    sp.eps = eps, sp.z = z, sp.tq = backup, sp.logp = logp;
+    size_t lds;
+    rc = ac_prepare(soft_shape(d->policy, d->q, d->n_q), B, d->act_low, d->act_high, ws, ws_bytes, qp.s.ac, R, lds);
+    if (rc != GOPS_OK) return rc;
+    soft_fill(*d, obs2, rew, done, eps, z, a2, logp, q_targ, qp.s);
+    qp.s.tq = backup;
     qp.distri = d->distri;
-    const dim3 grid((unsigned)((B + R - 1) / R));
-    if (R == 64) launch_with_lds(soft_q_backup_kernel<64>, grid, dim3(AC_THREADS), lds, s, qp);
-    else if (R == 32) launch_with_lds(soft_q_backup_kernel<32>, grid, dim3(AC_THREADS), lds, s, qp);
-    else launch_with_lds(soft_q_backup_kernel<16>, grid, dim3(AC_THREADS), lds, s, qp);
+    rows_dispatch(R, [&]<int RR>() { launch_with_lds(soft_q_backup_kernel<RR>, ac_grid(B, RR), dim3(AC_THREADS), lds, s, qp); });
     return (int)hipGetLastError();
 }

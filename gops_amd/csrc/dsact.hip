@@ -9,13 +9,15 @@
 // dsac_loss_kernel: DSAC's one-critic loss (gops/algorithm/dsac.py:235-252) and its seeds on the same two-phase scheme; the batch
 //   mean of std enters through td_bound = 3 mean(std).
 // tanh_gauss_fwd_kernel / tanh_gauss_bwd_kernel: StochaPolicy's sampling head - clamp, exp, u = mean + std eps, tanh squash,
-//   log-probability - and its reverse, one thread per row; the forward reduces mean(logp), mean(tanh(mean)) and mean(std).
+//   log-probability - and its reverse, one thread per row; the forward reduces mean(logp), mean(tanh(mean)) and mean(std).  The
+//   forward spells out soft_math.h's tanh_gauss_dim in place: through the helper it took four more registers.
 // Every value is formed in double from the fp32 inputs and rounded once where it is stored; sums are doubles in the fixed order of
 // block_reduce.h, which depends on B only.
 #include <stdint.h>
 
 #include "block_reduce.h"
 #include "launchers.h"
+#include "soft_math.h"
 
 namespace {
 
@@ -23,9 +25,6 @@ constexpr int DS_BLOCKS = 64;
 constexpr int DS_ONE_BLOCK_MAX = 8192;
 constexpr int DS_RESULTS = 16;   // floats in front of the partial sums
 constexpr int DS_PART = 6;       // doubles per block
-
-__device__ __forceinline__ double softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }   // (torch's threshold)
-__device__ __forceinline__ double softplus_grad_d(double x) { return x > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-x)); }
 
 __global__ __launch_bounds__(256) void dsact_loss_kernel(const float* __restrict__ qraw, const float* __restrict__ tq,
                                                          const float* __restrict__ tqs, int B, double tau_b, int phases,
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(256) void dsac_loss_kernel(const float* __restrict_
         const double v = sd * sd;
         seed[2 * (size_t)i] = (float)(-e / v / (double)B);
         seed[2 * (size_t)i + 1] = (float)((1.0 / sd - eb * eb / (v * sd)) * softplus_grad_d(raw) / (double)B);
-        l[0] += bound ? e * e / (2 * v) + eb * eb / (2 * v) + log(sd) : e * e / (2 * v) + log(sd) + 0.91893853320467274178;
+        l[0] += bound ? e * e / (2 * v) + eb * eb / (2 * v) + log(sd) : e * e / (2 * v) + log(sd) + HALF_LOG_2PI;
     }
     block_fold<1, false>(l, red);
     bool fin = gridDim.x == 1;
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(256) void tanh_gauss_fwd_kernel(const TgParams p, c
             const double u = mean + sd * (double)eps[(size_t)i * A + a], th = tanh(u), du = u - mean;
             const double half = ((double)p.high[a] - (double)p.low[a]) / 2;
             act[(size_t)i * A + a] = (float)(half * th + ((double)p.high[a] + (double)p.low[a]) / 2);
-            lp += (-(du * du) / (2 * sd * sd) - log(sd) - 0.91893853320467274178) - log(1.0 + 1e-6 - th * th) - log(half);
+            lp += (-(du * du) / (2 * sd * sd) - log(sd) - HALF_LOG_2PI) - log(1.0 + 1e-6 - th * th) - log(half);   // soft_math.h: tanh_gauss_dim
             s[1] += tanh(mean), s[2] += sd;
         }
         logp[i] = (float)lp;

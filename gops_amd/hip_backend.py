@@ -1261,23 +1261,21 @@ class LossStats:
 AC_LOSS_STATS_FLOATS = 392   # include/gops_hip.h: GOPS_AC_LOSS_STATS_FLOATS
 
 
-class AcBackup:
-    """The Bellman backup of a DDPG / TD3 update in ONE launch (`gops_ac_backup`, csrc/actor_critic.hip): target policy with its tanh
-    squash, TD3's clipped target noise, one or two target critics on the concatenated input (which never exists in global memory),
-    minimum, `rew * reward_scale + gamma * (1 - done) * q`.  `policy` / `critics`: `GopsMlp` views of the TARGET networks (read in
-    place at every call).  `supported` is False for a shape the kernel does not hold: the caller then composes the backup from
-    `MlpNet.forward` calls; `run` on such a description raises."""
+class _BackupBase:
+    """What the one-launch backups share: the description's nets (raw pointers, kept alive here), its action limits, the workspace
+    with `supported`, and the output tensors of a run."""
 
-    def __init__(self, policy: GopsMlp, critics: Sequence[GopsMlp], *, squash_low, squash_high, act_low, act_high, batch: int,
-                 smooth: bool, device: Optional[torch.device] = None, workspace_bytes: Optional[int] = None):
-        d = self.desc = GopsAcBackup()
-        self.batch, self.act_dim, self.n_q = int(batch), int(policy.sizes[policy.n_layers]), len(critics)
+    _workspace_fn = None   # name of the entry point that sizes the workspace (0: the kernel does not hold the shape)
+
+    def _init_backup(self, desc, policy: GopsMlp, critics: Sequence[GopsMlp], limits: Dict[str, object], batch: int, device,
+                     workspace_bytes: Optional[int]):
+        d = self.desc = desc
+        self.batch, self.n_q = int(batch), len(critics)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
-        d.n_q, d.smooth = self.n_q, int(bool(smooth))
-        for name, vals in (("squash_low", squash_low), ("squash_high", squash_high), ("act_low", act_low), ("act_high", act_high)):
+        for name, vals in limits.items():
             _fill(getattr(d, name), np.asarray(vals, dtype=np.float32).reshape(-1)[:MAX_ACT])
         self.set_nets(policy, critics)
-        nbytes = lib().gops_ac_backup_workspace_bytes(C.byref(d), self.batch)
+        nbytes = getattr(lib(), self._workspace_fn)(C.byref(d), self.batch)
         self.supported = nbytes != 0
         self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
         self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
@@ -1289,20 +1287,41 @@ class AcBackup:
             C.memmove(C.byref(self.desc.q[i]), C.byref(c), C.sizeof(GopsMlp))
         self._keep = (policy, list(critics))   # the description holds raw pointers
 
+    def _outputs(self, out: Optional[Dict[str, torch.Tensor]], want, shapes) -> Dict[str, torch.Tensor]:
+        """`out`, and a fresh tensor for every output named in `want` that it does not supply."""
+        res = dict(out or {})
+        for k in want:
+            if k not in res:
+                res[k] = torch.empty(shapes[k], dtype=torch.float32, device=self.device)
+        return res
+
+
+class AcBackup(_BackupBase):
+    """The Bellman backup of a DDPG / TD3 update in ONE launch (`gops_ac_backup`, csrc/actor_critic.hip): target policy with its tanh
+    squash, TD3's clipped target noise, one or two target critics on the concatenated input (which never exists in global memory),
+    minimum, `rew * reward_scale + gamma * (1 - done) * q`.  `policy` / `critics`: `GopsMlp` views of the TARGET networks (read in
+    place at every call).  `supported` is False for a shape the kernel does not hold: the caller then composes the backup from
+    `MlpNet.forward` calls; `run` on such a description raises."""
+
+    _workspace_fn = "gops_ac_backup_workspace_bytes"
+
+    def __init__(self, policy: GopsMlp, critics: Sequence[GopsMlp], *, squash_low, squash_high, act_low, act_high, batch: int,
+                 smooth: bool, device: Optional[torch.device] = None, workspace_bytes: Optional[int] = None):
+        d = GopsAcBackup()
+        d.n_q, d.smooth = len(critics), int(bool(smooth))
+        self.act_dim = int(policy.sizes[policy.n_layers])
+        self._init_backup(d, policy, critics, dict(squash_low=squash_low, squash_high=squash_high, act_low=act_low, act_high=act_high),
+                          batch, device, workspace_bytes)
+
     def run(self, obs2, rew, done, xi=None, *, target_noise=0.0, noise_clip=0.0, reward_scale=1.0, gamma=0.99, want_a2=False,
             want_q=False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """-> {"backup" [B], "a2" [B, A] (want_a2), "q_targ" [n_q, B] (want_q)}; `out` supplies the output tensors instead of fresh
         ones.  Enqueues only."""
-        B, d, dev = self.batch, self.desc, self.device
+        B, d = self.batch, self.desc
         assert obs2.shape[0] == B
         d.target_noise, d.noise_clip, d.reward_scale, d.gamma = float(target_noise), float(noise_clip), float(reward_scale), float(gamma)
-        res = dict(out or {})
-        if "backup" not in res:
-            res["backup"] = torch.empty(B, dtype=torch.float32, device=dev)
-        if want_a2 and "a2" not in res:
-            res["a2"] = torch.empty(B, self.act_dim, dtype=torch.float32, device=dev)
-        if want_q and "q_targ" not in res:
-            res["q_targ"] = torch.empty(self.n_q, B, dtype=torch.float32, device=dev)
+        res = self._outputs(out, ("backup",) + (("a2",) if want_a2 else ()) + (("q_targ",) if want_q else ()),
+                            dict(backup=(B,), a2=(B, self.act_dim), q_targ=(self.n_q, B)))
         check(lib().gops_ac_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(xi), res["backup"].data_ptr(),
                                    res["a2"].data_ptr() if "a2" in res else None, res["q_targ"].data_ptr() if "q_targ" in res else None,
                                    self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_ac_backup")
@@ -1331,48 +1350,39 @@ DSACT_STATS_FLOATS = 800        # include/gops_hip.h: GOPS_DSACT_STATS_FLOATS
 TANH_GAUSS_STATS_FLOATS = 800   # include/gops_hip.h: GOPS_TANH_GAUSS_STATS_FLOATS
 
 
-class SoftBackup:
+class _SoftBackupBase(_BackupBase):
+    def _init_soft(self, desc, policy, critics, act_low, act_high, min_log_std, max_log_std, batch, log_alpha, device, workspace_bytes):
+        desc.min_log_std, desc.max_log_std = float(min_log_std), float(max_log_std)
+        self.log_alpha = log_alpha
+        desc.log_alpha = _ptr(log_alpha)
+        self.act_dim = int(policy.sizes[policy.n_layers]) // 2
+        self._init_backup(desc, policy, critics, dict(act_low=act_low, act_high=act_high), batch, device, workspace_bytes)
+
+
+class SoftBackup(_SoftBackupBase):
     """DSAC-T's distributional soft backup in ONE launch (`gops_soft_backup`, csrc/actor_critic.hip): tanh-Gaussian target policy on
     obs2, both target critics' (mean, softplus std) on the concatenated input, minimum, the clipped return sample, entropy term.
     `policy` / `critics`: `GopsMlp` views of the TARGET networks' raw stacks.  `log_alpha`: the device tensor the kernel takes alpha
     from (`exp` inside the kernel), or None for the fixed `alpha` of `run`.  `supported` is False for a shape the kernel does not
     hold; `run` on such a description raises."""
 
+    _workspace_fn = "gops_soft_backup_workspace_bytes"
+
     def __init__(self, policy: GopsMlp, critics: Sequence[GopsMlp], *, act_low, act_high, min_log_std: float, max_log_std: float,
                  batch: int, log_alpha: Optional[torch.Tensor] = None, device: Optional[torch.device] = None,
                  workspace_bytes: Optional[int] = None):
-        d = self.desc = GopsSoftBackup()
-        self.batch, self.act_dim = int(batch), int(policy.sizes[policy.n_layers]) // 2
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        for name, vals in (("act_low", act_low), ("act_high", act_high)):
-            _fill(getattr(d, name), np.asarray(vals, dtype=np.float32).reshape(-1)[:MAX_ACT])
-        d.min_log_std, d.max_log_std = float(min_log_std), float(max_log_std)
-        self.log_alpha = log_alpha
-        d.log_alpha = _ptr(log_alpha)
-        self.set_nets(policy, critics)
-        nbytes = lib().gops_soft_backup_workspace_bytes(C.byref(d), self.batch)
-        self.supported = nbytes != 0
-        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
-        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
-
-    def set_nets(self, policy: GopsMlp, critics: Sequence[GopsMlp]):
         assert len(critics) == 2
-        C.memmove(C.byref(self.desc.policy), C.byref(policy), C.sizeof(GopsMlp))
-        for i, c in enumerate(critics):
-            C.memmove(C.byref(self.desc.q[i]), C.byref(c), C.sizeof(GopsMlp))
-        self._keep = (policy, list(critics))   # the description holds raw pointers
+        self._init_soft(GopsSoftBackup(), policy, critics, act_low, act_high, min_log_std, max_log_std, batch, log_alpha, device,
+                        workspace_bytes)
 
     def run(self, obs2, rew, done, eps_next, z_next, *, gamma=0.99, alpha=0.2, want=(), out: Optional[Dict[str, torch.Tensor]] = None):
         """-> {"target_q" [B], "target_q_sample" [B]} and, named in `want`: "a2" [B, A], "logp" [B], "q_targ" [2, B, 2]; `out` supplies
         output tensors instead of fresh ones.  Enqueues only."""
-        B, d, dev = self.batch, self.desc, self.device
+        B, d = self.batch, self.desc
         assert obs2.shape[0] == B and tuple(z_next.shape) == (2, B)
         d.gamma, d.alpha = float(gamma), float(alpha)
-        res = dict(out or {})
-        shapes = dict(target_q=(B,), target_q_sample=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(2, B, 2))
-        for k in ("target_q", "target_q_sample") + tuple(want):
-            if k not in res:
-                res[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
+        res = self._outputs(out, ("target_q", "target_q_sample") + tuple(want),
+                            dict(target_q=(B,), target_q_sample=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(2, B, 2)))
         check(lib().gops_soft_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["target_q"]),
                                      _ptr(res["target_q_sample"]), _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")),
                                      self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_soft_backup")
@@ -1405,49 +1415,31 @@ class DsactCriticLoss:
 DSAC_STATS_FLOATS = 264   # include/gops_hip.h: GOPS_DSAC_STATS_FLOATS
 
 
-class SoftQBackup:
+class SoftQBackup(_SoftBackupBase):
     """The soft Q backup of a SAC / DSAC update in ONE launch (`gops_soft_q_backup`, csrc/actor_critic.hip): tanh-Gaussian policy on
     obs2 with its log-probability, then one or two scalar critics and their minimum (`distri=False`: SAC), or one critic with a
     (mean, softplus std) head and a clipped return sample (`distri=True`: DSAC), entropy term.  `policy` / `critics`: `GopsMlp` views
     of the networks' raw stacks (read in place at every call).  `log_alpha`: the device tensor the kernel takes alpha from, or None
     for the fixed `alpha` of `run`.  `supported` is False for a shape the kernel does not hold; `run` on such a description raises."""
 
+    _workspace_fn = "gops_soft_q_backup_workspace_bytes"
+
     def __init__(self, policy: GopsMlp, critics: Sequence[GopsMlp], *, distri: bool, act_low, act_high, min_log_std: float,
                  max_log_std: float, batch: int, log_alpha: Optional[torch.Tensor] = None, device: Optional[torch.device] = None,
                  workspace_bytes: Optional[int] = None):
-        d = self.desc = GopsSoftQBackup()
-        self.batch, self.act_dim, self.n_q, self.distri = int(batch), int(policy.sizes[policy.n_layers]) // 2, len(critics), bool(distri)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        d.n_q, d.distri = self.n_q, int(self.distri)
-        for name, vals in (("act_low", act_low), ("act_high", act_high)):
-            _fill(getattr(d, name), np.asarray(vals, dtype=np.float32).reshape(-1)[:MAX_ACT])
-        d.min_log_std, d.max_log_std = float(min_log_std), float(max_log_std)
-        self.log_alpha = log_alpha
-        d.log_alpha = _ptr(log_alpha)
-        self.set_nets(policy, critics)
-        nbytes = lib().gops_soft_q_backup_workspace_bytes(C.byref(d), self.batch)
-        self.supported = nbytes != 0
-        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
-        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
-
-    def set_nets(self, policy: GopsMlp, critics: Sequence[GopsMlp]):
-        assert len(critics) == self.n_q
-        C.memmove(C.byref(self.desc.policy), C.byref(policy), C.sizeof(GopsMlp))
-        for i, c in enumerate(critics):
-            C.memmove(C.byref(self.desc.q[i]), C.byref(c), C.sizeof(GopsMlp))
-        self._keep = (policy, list(critics))   # the description holds raw pointers
+        d = GopsSoftQBackup()
+        self.distri = bool(distri)
+        d.n_q, d.distri = len(critics), int(self.distri)
+        self._init_soft(d, policy, critics, act_low, act_high, min_log_std, max_log_std, batch, log_alpha, device, workspace_bytes)
 
     def run(self, obs2, rew, done, eps_next, z_next=None, *, gamma=0.99, alpha=0.2, want=(), out: Optional[Dict[str, torch.Tensor]] = None):
         """-> {"backup" [B]} and, named in `want`: "a2" [B, A], "logp" [B], "q_targ" ([n_q, B], or [B, 2] = (m, s) with `distri`);
         `out` supplies output tensors instead of fresh ones.  Enqueues only."""
-        B, d, dev = self.batch, self.desc, self.device
+        B, d = self.batch, self.desc
         assert obs2.shape[0] == B and (z_next is None or tuple(z_next.shape) == (B,))
         d.gamma, d.alpha = float(gamma), float(alpha)
-        res = dict(out or {})
-        shapes = dict(backup=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(B, 2) if self.distri else (self.n_q, B))
-        for k in ("backup",) + tuple(want):
-            if k not in res:
-                res[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
+        res = self._outputs(out, ("backup",) + tuple(want),
+                            dict(backup=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(B, 2) if self.distri else (self.n_q, B)))
         check(lib().gops_soft_q_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["backup"]),
                                        _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")), self.workspace.data_ptr(),
                                        self._workspace_bytes, _stream()), "gops_soft_q_backup")

@@ -139,6 +139,17 @@ def test_soft_backup_64_row_tiles_eight_head_outputs_chunked_weights():
     _check_backup(_wide_act_alg([256, 256]), _data(16390, 6, 4, seed=3), "[256, 256] act 4 B=16390")
 
 
+def test_soft_backup_does_not_depend_on_the_tile_rows():
+    """70 rows alone (16-row tiles) and as the first rows of a batch of 2054 (32-row tiles): the same bits."""
+    alg = _alg(4, 2, [64, 48], "tanh")
+    big = _data(2054, 4, 2, seed=2)
+    small = {k: (v[:, :70] if k == "z_next" else v[:70]).clone() for k, v in big.items()}
+    a, b = _fused(alg, alg._batch(small)), _fused(alg, alg._batch(big))
+    for k in OUT:
+        rows = b[k][:, :70] if k == "q_targ" else b[k][:70]
+        assert torch.equal(a[k], rows), k
+
+
 def test_soft_backup_saturation():
     """Rows with |u| > 8: every output is finite and a2 is within the limits (no parity asked where fp32 cannot resolve the log)."""
     alg = _alg(4, 2, [64, 48], "tanh")

@@ -172,6 +172,24 @@ def test_soft_q_backup_does_not_depend_on_the_tile_rows(name):
         assert torch.equal(a[k], rows), k
 
 
+def test_soft_backup_and_soft_q_backup_share_one_policy_head():
+    """One policy, obs2 and eps_next through `gops_soft_backup` and through `gops_soft_q_backup` (distri, one critic): the same bits of
+    a2 and logp - both kernels run the one policy head of csrc/actor_critic.hip."""
+    alg = _alg("DSAC", 4, 2, [64, 48], "tanh")
+    batch = alg._batch(_data(70, 4, 2))
+    got = _fused(alg, batch)
+    pt, (q,) = alg._backup_modules()
+    twin = hb.SoftBackup(pt.hip_mlp(), [q.hip_mlp(), q.hip_mlp()], act_low=pt.act_low_lim.cpu().numpy(), act_high=pt.act_high_lim.cpu().numpy(),
+                         min_log_std=pt.min_log_std, max_log_std=pt.max_log_std, batch=70, log_alpha=alg.networks.log_alpha.data,
+                         device=batch["obs2"].device)
+    assert twin.supported
+    z2 = torch.stack((batch["z_next"], batch["z_next"]))
+    ref = twin.run(batch["obs2"], batch["rew"], batch["done"], batch["eps_next"], z2, gamma=alg.gamma, alpha=alg.alpha, want=("a2", "logp"))
+    for k in ("a2", "logp"):
+        assert torch.equal(got[k], ref[k]), k
+    assert got["logp"].abs().max() > 0 and got["a2"].std() > 0
+
+
 @pytest.mark.parametrize("name", ["SAC", "DSAC"])
 def test_soft_q_backup_saturation(name):
     """Rows with |u| > 8: every output is finite and a2 is within the limits (no parity asked where fp32 cannot resolve the log)."""
