@@ -9,7 +9,6 @@ wrapped in this process; of the eight draws of one update the fixture stores the
 checked against the losses the reference reported: the draws are attributed correctly.
 """
 import copy
-import json
 import os
 import sys
 import zlib
@@ -21,17 +20,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import make_golden as mg  # noqa: E402  (installs the reference import hook)
+from _make_ac_common import (LIM_A, LIM_B, MAX_LOG_STD, MIN_LOG_STD, SHAPE_A, SHAPE_B, STOCHA, DrawTap, arrays, batch_of, build_reference,  # noqa: E402
+                             close, five_batches, last_linear, meta_entry, state, tanh_gauss_rsample, update_entries)
 
 from gops.algorithm.dsact import DSACT  # noqa: E402
 from gops.utils.act_distribution_type import GaussDistribution, TanhGaussDistribution  # noqa: E402
 
-from gops_amd.utils.synthetic import act_dim_of, make_batch  # noqa: E402
-
-SHAPE_A = dict(env_id="gym_pendulum", batch=70, hidden=(32, 16), act="relu")               # obs 3 / act 1
-SHAPE_B = dict(env_id="pyth_lq", lq_config="s4a2", batch=33, hidden=(64,), act="gelu")      # obs 4 / act 2
-LIM_A = ([-2.0], [2.0])
-LIM_B = ([-1.0, -0.5], [2.0, 0.5])
-MIN_LOG_STD, MAX_LOG_STD = -3.0, -0.5
 # name: (cfg, action limits, constructor arguments)
 CASES = {
     "dsact_pend_relu": (SHAPE_A, LIM_A, dict(gamma=0.97, tau=0.005, auto_alpha=True, delay_update=2)),
@@ -40,64 +34,15 @@ CASES = {
 }
 
 
-class DrawTap:
-    """Records what `_standard_normal` (rsample) and `torch.normal` (Normal.sample) return while the reference runs."""
-
-    def __enter__(self):
-        import torch.distributions.normal as tdn
-        self.rsamples, self.samples, self._tdn = [], [], tdn
-        self._orig_std, self._orig_normal = tdn._standard_normal, torch.normal
-
-        def std(*a, **k):
-            x = self._orig_std(*a, **k)
-            self.rsamples.append(x.detach().clone())
-            return x
-
-        def normal(*a, **k):
-            x = self._orig_normal(*a, **k)
-            self.samples.append(x.detach().clone())
-            return x
-
-        tdn._standard_normal, torch.normal = std, normal
-        return self
-
-    def __exit__(self, *exc):
-        self._tdn._standard_normal, torch.normal = self._orig_std, self._orig_normal
-
-    def draws(self):
-        """The update's order (dsact.py:172, 239, 241-242, 254-260, 317-318): rsample at obs, rsample at obs2; samples for q1, q2 on
-        the data (unused), q1_target, q2_target (z_next), q1, q2 on the new action (unused)."""
-        assert len(self.rsamples) == 2 and len(self.samples) == 6
-        return dict(eps_new=self.rsamples[0], eps_next=self.rsamples[1], z_next=torch.stack([self.samples[2], self.samples[3]]))
-
-
-def last_linear(seq):
-    return [m for m in seq if isinstance(m, torch.nn.Linear)][-1]
+def draws_of(tap):
+    """The update's order (dsact.py:172, 239, 241-242, 254-260, 317-318): rsample at obs, rsample at obs2; samples for q1, q2 on the
+    data (unused), q1_target, q2_target (z_next), q1, q2 on the new action (unused)."""
+    assert len(tap.rsamples) == 2 and len(tap.samples) == 6
+    return dict(eps_new=tap.rsamples[0], eps_next=tap.rsamples[1], z_next=torch.stack([tap.samples[2], tap.samples[3]]))
 
 
 def build(cfg, lim, ctor, seed):
-    torch.manual_seed(seed)
-    kw = mg.alg_kwargs(dict(cfg, alg="INFADP", horizon=1), seed, action_low_limit=np.array(lim[0], dtype=np.float32),
-                       action_high_limit=np.array(lim[1], dtype=np.float32))
-    kw.update(algorithm="DSACT", policy_func_name="StochaPolicy", policy_act_distribution="TanhGaussDistribution",
-              policy_min_log_std=MIN_LOG_STD, policy_max_log_std=MAX_LOG_STD, value_func_name="ActionValueDistri",
-              value_output_activation="linear", alpha_learning_rate=3e-4, buffer_name="replay_buffer", **ctor)
-    alg = DSACT(**kw)
-    g = torch.Generator().manual_seed(seed + 1000)
-    nets = alg.networks
-    with torch.no_grad():   # the targets start as copies: move them apart
-        for n in ("q1_target", "q2_target", "policy_target"):
-            amp = 0.1 if n == "policy_target" else 0.6
-            for p in getattr(nets, n).parameters():
-                p.add_(amp * (torch.rand(p.shape, generator=g) - 0.5))
-    return alg, g
-
-
-def batch_of(cfg, seed, g):
-    B, A = cfg["batch"], act_dim_of(cfg)
-    obs = make_batch(dict(cfg, alg="INFADP", horizon=1), seed)["obs"]
-    return dict(obs=obs, act=torch.rand(B, A, generator=g) * 2 - 1, rew=torch.randn(B, generator=g),
-                obs2=obs + 0.05 * torch.randn(obs.shape, generator=g), done=(torch.rand(B, generator=g) < 0.15).float())
+    return build_reference(DSACT, cfg, lim, seed, value_func_name="ActionValueDistri", **STOCHA, **ctor)
 
 
 def balance(alg, data):
@@ -122,16 +67,7 @@ def recompute(alg, data, dr, mean_std_before):
     """The update's intermediate values from the recorded draws with the reference's own networks (fp32, as the reference computes)."""
     nets = alg.networks
     alpha = float(nets.log_alpha.exp()) if alg.auto_alpha else alg.alpha
-    lo, hi = nets.policy.act_low_lim, nets.policy.act_high_lim
-    half, mid = (hi - lo) / 2, (hi + lo) / 2
-
-    def rsample(logits, eps):
-        mean, std = torch.chunk(logits, 2, dim=-1)
-        u = mean + std * eps
-        logp = (torch.distributions.Normal(mean, std).log_prob(u).sum(-1) - torch.log(1 + 1e-6 - torch.tanh(u) ** 2).sum(-1)
-                - torch.log(half).sum(-1))
-        return half * torch.tanh(u) + mid, logp, u
-
+    rsample = lambda logits, eps: tanh_gauss_rsample(nets.policy, logits, eps)   # noqa: E731
     with torch.no_grad():
         a2, logp2, u2 = rsample(nets.policy_target(data["obs2"]), dr["eps_next"])
         qt = torch.stack([nets.q1_target(data["obs2"], a2), nets.q2_target(data["obs2"], a2)])   # [2, B, 2]
@@ -180,10 +116,6 @@ def assert_cases(name, alg, data, rc):
     assert not missing, (name, missing)
 
 
-def close(a, b, tol=1e-6):
-    return abs(float(a) - float(b)) <= tol * max(1.0, abs(float(b)))
-
-
 def distribution_values(seed):
     """Inputs and outputs of the reference's two continuous distributions, for tests of their restatement."""
     g = torch.Generator().manual_seed(seed)
@@ -208,14 +140,13 @@ def one_update(name):
     alg, g = build(cfg, lim, ctor, seed)
     data = batch_of(cfg, seed, g)
     balance(alg, data)
-    out = {"in/" + k: v.numpy().copy() for k, v in data.items()}
-    out["meta/cfg"] = json.dumps(dict(cfg=dict(cfg, alg="DSACT"), lim=lim, ctor=ctor, seed=seed, min_log_std=MIN_LOG_STD, max_log_std=MAX_LOG_STD))
-    out.update({k: v.copy() for k, v in mg.sd_to_np(alg.networks.state_dict()).items()})
+    out = {**arrays(data, "in/"), **meta_entry(cfg=dict(cfg, alg="DSACT"), lim=lim, ctor=ctor, seed=seed, min_log_std=MIN_LOG_STD,
+                                               max_log_std=MAX_LOG_STD), **state(alg)}
     before = copy.deepcopy(alg.networks)
     with DrawTap() as tap:
         tb, info = alg.get_remote_update_info(dict(data), 0)
-    dr = tap.draws()
-    out.update({"in/" + k: v.numpy().copy() for k, v in dr.items()})
+    dr = draws_of(tap)
+    out.update(arrays(dr, "in/"))
     after, alg.networks = alg.networks, before
     rc = recompute(alg, data, dr, None)
     alg.networks = after
@@ -224,15 +155,7 @@ def one_update(name):
     assert_cases(name, alg, data, rc)
     for k in ("target_q", "target_q_sample", "a2", "logp_next", "q_targ", "new_act", "new_logp", "mean_std"):
         out[k] = rc[k].numpy().copy()
-    for key, grads in info.items():
-        if key.endswith("_grad") and key != "log_alpha_grad":
-            for i, gr in enumerate(grads):
-                out[f"{key}/{i}"] = gr.detach().numpy().copy()
-    if alg.auto_alpha:
-        out["log_alpha_grad"] = info["log_alpha_grad"].detach().numpy().copy()
-    for k, v in tb.items():
-        if not k.startswith("Time/"):
-            out["tb/" + k] = np.float64(v)
+    out.update(update_entries(info, tb, log_alpha=alg.auto_alpha))
     if name == "dsact_lqs4a2_gelu":
         out.update(distribution_values(seed))
     mg.save(name, **out)
@@ -246,24 +169,18 @@ def five_updates():
     ctor = dict(gamma=0.97, tau=0.05, auto_alpha=True, delay_update=2)
     seed = zlib.crc32(name.encode()) % 1000
     alg, g = build(cfg, lim, ctor, seed)
-    nets = alg.networks
-    for opt in (nets.q1_optimizer, nets.q2_optimizer, nets.policy_optimizer, nets.alpha_optimizer):
-        for group in opt.param_groups:
-            group["lr"] = 1e-2
-    out = {"meta/cfg": json.dumps(dict(cfg=dict(cfg, alg="DSACT"), lim=lim, ctor=ctor, seed=seed, lr=1e-2, min_log_std=MIN_LOG_STD,
-                                       max_log_std=MAX_LOG_STD))}
-    batches = [batch_of(cfg, seed + k, g) for k in range(5)]
-    balance(alg, {key: torch.cat([b[key] for b in batches]) for key in batches[0]})
-    out.update({key: v.copy() for key, v in mg.sd_to_np(nets.state_dict(), "sd0/").items()})
+    out = meta_entry(cfg=dict(cfg, alg="DSACT"), lim=lim, ctor=ctor, seed=seed, lr=1e-2, min_log_std=MIN_LOG_STD, max_log_std=MAX_LOG_STD)
+    batches, sd0 = five_batches(alg, cfg, seed, g, lambda data: balance(alg, data))
+    out.update(sd0)
     for k, data in enumerate(batches):
-        out.update({f"in{k}/" + key: v.numpy().copy() for key, v in data.items()})
+        out.update(arrays(data, f"in{k}/"))
         with DrawTap() as tap:
             tb = alg.local_update(dict(data), k)
-        out.update({f"in{k}/" + key: v.numpy().copy() for key, v in tap.draws().items()})
+        out.update(arrays(draws_of(tap), f"in{k}/"))
         out[f"loss_q{k}"] = np.float64(tb["Loss/Critic loss-RL iter"])
         out[f"loss_pi{k}"] = np.float64(tb["Loss/Actor loss-RL iter"])
         out[f"mean_std{k + 1}"] = np.array([float(alg.mean_std1), float(alg.mean_std2)], dtype=np.float32)
-        out.update({key: v.copy() for key, v in mg.sd_to_np(alg.networks.state_dict(), f"sd{k + 1}/").items()})
+        out.update(state(alg, f"sd{k + 1}/"))
         assert float(max(abs(tb["DSAC2/policy_mean-RL iter"]), 0)) <= 1.0
     mg.save(name, **out)
 

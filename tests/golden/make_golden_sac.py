@@ -2,14 +2,13 @@
 
 Run in the build container only (needs /root/reference):  python tests/golden/make_golden_sac.py
 Every array written here is an input, or an output of the reference's own classes (`gops.algorithm.sac.SAC`, `gops.algorithm.dsac.DSAC`)
-built with the helpers of make_golden.py and make_golden_dsact.py.  The reference draws inside the update (see DrawTap there): SAC two
+built with the helpers of make_golden.py and _make_ac_common.py.  The reference draws inside the update (see DrawTap there): SAC two
 policy samples; DSAC two policy samples and three return samples, of which only the target critic's reaches an output.  The fixture
 stores the draws that reach an output - `eps_new`, `eps_next`, DSAC's `z_next` [B] - and the targets, log-probabilities and losses are
 recomputed here from those with the reference's own networks and checked against what the reference reported (DSAC reports no critic
 loss: there the recomputed loss's gradient is checked against the reference's `q_grad`): the draws are attributed correctly.
 """
 import copy
-import json
 import os
 import sys
 import zlib
@@ -21,7 +20,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import make_golden as mg  # noqa: E402  (installs the reference import hook)
-from make_golden_dsact import LIM_A, LIM_B, MAX_LOG_STD, MIN_LOG_STD, SHAPE_A, SHAPE_B, DrawTap, batch_of, close, last_linear  # noqa: E402
+from _make_ac_common import (LIM_A, LIM_B, MAX_LOG_STD, MIN_LOG_STD, SHAPE_A, SHAPE_B, STOCHA, DrawTap, arrays, batch_of, build_reference,  # noqa: E402
+                             close, five_batches, last_linear, meta_entry, state, tanh_gauss_rsample, update_entries)
 
 from gops.algorithm.dsac import DSAC  # noqa: E402
 from gops.algorithm.sac import SAC  # noqa: E402
@@ -52,20 +52,8 @@ def draws_of(name, tap):
 
 
 def build(name, cfg, lim, ctor, seed):
-    torch.manual_seed(seed)
-    kw = mg.alg_kwargs(dict(cfg, alg="INFADP", horizon=1), seed, action_low_limit=np.array(lim[0], dtype=np.float32),
-                       action_high_limit=np.array(lim[1], dtype=np.float32))
-    kw.update(algorithm=name, policy_func_name="StochaPolicy", policy_act_distribution="TanhGaussDistribution",
-              policy_min_log_std=MIN_LOG_STD, policy_max_log_std=MAX_LOG_STD, value_output_activation="linear",
-              value_func_name="ActionValue" if name == "SAC" else "ActionValueDistri", q_learning_rate=1e-3, alpha_learning_rate=3e-4,
-              buffer_name="replay_buffer", **ctor)
-    alg = (SAC if name == "SAC" else DSAC)(**kw)
-    g = torch.Generator().manual_seed(seed + 1000)
-    with torch.no_grad():   # the targets start as copies: move them apart
-        for n, p in alg.networks.named_parameters():
-            if "_target." in n:
-                p.add_((0.1 if n.startswith("policy") else 0.6) * (torch.rand(p.shape, generator=g) - 0.5))
-    return alg, g
+    return build_reference(SAC if name == "SAC" else DSAC, cfg, lim, seed, q_learning_rate=1e-3,
+                           value_func_name="ActionValue" if name == "SAC" else "ActionValueDistri", **STOCHA, **ctor)
 
 
 def balance(name, alg, data):
@@ -92,16 +80,7 @@ def recompute(name, alg, data, dr):
     the critic loss keeps its graph."""
     nets = alg.networks
     alpha = float(nets.log_alpha.exp()) if alg.auto_alpha else alg.alpha
-    lo, hi = nets.policy.act_low_lim, nets.policy.act_high_lim
-    half, mid = (hi - lo) / 2, (hi + lo) / 2
-
-    def rsample(logits, eps):
-        mean, std = torch.chunk(logits, 2, dim=-1)
-        u = mean + std * eps
-        logp = (torch.distributions.Normal(mean, std).log_prob(u).sum(-1) - torch.log(1 + 1e-6 - torch.tanh(u) ** 2).sum(-1)
-                - torch.log(half).sum(-1))
-        return half * torch.tanh(u) + mid, logp, u
-
+    rsample = lambda logits, eps: tanh_gauss_rsample(nets.policy, logits, eps)   # noqa: E731
     out = {}
     with torch.no_grad():
         a2, logp2, u2 = rsample(getattr(nets, POLICY_AT_OBS2[name])(data["obs2"]), dr["eps_next"])
@@ -195,14 +174,13 @@ def one_update_at(tag, seed):
     alg, g = build(name, cfg, lim, ctor, seed)
     data = batch_of(cfg, seed, g)
     balance(name, alg, data)
-    out = {"in/" + k: v.numpy().copy() for k, v in data.items()}
-    out["meta/cfg"] = json.dumps(dict(cfg=dict(cfg, alg=name), lim=lim, ctor=ctor, seed=seed, min_log_std=MIN_LOG_STD, max_log_std=MAX_LOG_STD))
-    out.update({k: v.copy() for k, v in mg.sd_to_np(alg.networks.state_dict()).items()})
+    out = {**arrays(data, "in/"), **meta_entry(cfg=dict(cfg, alg=name), lim=lim, ctor=ctor, seed=seed, min_log_std=MIN_LOG_STD,
+                                               max_log_std=MAX_LOG_STD), **state(alg)}
     before = copy.deepcopy(alg.networks)
     with DrawTap() as tap:
         tb, info = alg.get_remote_update_info(dict(data), 0)
     dr = draws_of(name, tap)
-    out.update({"in/" + k: v.numpy().copy() for k, v in dr.items()})
+    out.update(arrays(dr, "in/"))
     after, alg.networks = alg.networks, before
     rc = recompute(name, alg, data, dr)
     check_reported(tag, name, alg, rc, tb, info)
@@ -210,15 +188,7 @@ def one_update_at(tag, seed):
     alg.networks = after
     for k in ("backup", "a2", "logp_next", "q_targ", "new_act", "new_logp", "loss_q", "loss_pi") + (("td_bound",) if name == "DSAC" else ()):
         out[k] = rc[k].detach().numpy().copy()
-    for key, grads in info.items():
-        if key.endswith("_grad") and key != "log_alpha_grad":
-            for i, gr in enumerate(grads):
-                out[f"{key}/{i}"] = gr.detach().numpy().copy()
-    if alg.auto_alpha:
-        out["log_alpha_grad"] = info["log_alpha_grad"].detach().numpy().copy()
-    for k, v in tb.items():
-        if not k.startswith("Time/"):
-            out["tb/" + k] = np.float64(v)
+    out.update(update_entries(info, tb, log_alpha=alg.auto_alpha))
     mg.save(tag, **out)
 
 
@@ -231,25 +201,20 @@ def five_updates(name):
     seed = zlib.crc32(tag.encode()) % 1000
     alg, g = build(name, cfg, lim, ctor, seed)
     nets = alg.networks
-    for n in Q_NAMES[name] + ("policy", "alpha"):
-        for group in getattr(nets, f"{n}_optimizer").param_groups:
-            group["lr"] = 1e-2
-    out = {"meta/cfg": json.dumps(dict(cfg=dict(cfg, alg=name), lim=lim, ctor=ctor, seed=seed, lr=1e-2, min_log_std=MIN_LOG_STD,
-                                       max_log_std=MAX_LOG_STD))}
-    batches = [batch_of(cfg, seed + k, g) for k in range(5)]
-    balance(name, alg, {key: torch.cat([b[key] for b in batches]) for key in batches[0]})
-    out.update({key: v.copy() for key, v in mg.sd_to_np(nets.state_dict(), "sd0/").items()})
+    out = meta_entry(cfg=dict(cfg, alg=name), lim=lim, ctor=ctor, seed=seed, lr=1e-2, min_log_std=MIN_LOG_STD, max_log_std=MAX_LOG_STD)
+    batches, sd0 = five_batches(alg, cfg, seed, g, lambda data: balance(name, alg, data))
+    out.update(sd0)
     for k, data in enumerate(batches):
-        out.update({f"in{k}/" + key: v.numpy().copy() for key, v in data.items()})
+        out.update(arrays(data, f"in{k}/"))
         if name == "DSAC":
             assert float(nets.q(data["obs"], data["act"])[:, 1].min()) >= MIN_STD, (tag, k)
         with DrawTap() as tap:
             tb = alg.local_update(dict(data), k)
-        out.update({f"in{k}/" + key: v.numpy().copy() for key, v in draws_of(name, tap).items()})
+        out.update(arrays(draws_of(name, tap), f"in{k}/"))
         out[f"loss_pi{k}"] = np.float64(tb["Loss/Actor loss-RL iter"])
         if name == "SAC":
             out[f"loss_q{k}"] = np.float64(tb["Loss/Critic loss-RL iter"])
-        out.update({key: v.copy() for key, v in mg.sd_to_np(alg.networks.state_dict(), f"sd{k + 1}/").items()})
+        out.update(state(alg, f"sd{k + 1}/"))
     mg.save(tag, **out)
 
 

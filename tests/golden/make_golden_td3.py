@@ -7,7 +7,7 @@ inside the update (td3.py:170): the call is wrapped in this process, and the fix
 `backup`, `a2`, `q_targ` and the per-critic losses are not returned by the reference's update: they are evaluated here with the
 reference's own target networks on the recorded draws, and the recorded critic loss is checked against them.
 """
-import json
+import copy
 import os
 import sys
 import zlib
@@ -19,17 +19,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import make_golden as mg  # noqa: E402  (installs the reference import hook)
+import _make_ac_common as common  # noqa: E402
+from _make_ac_common import LIM_A, LIM_B, SHAPE_A, SHAPE_B, DrawTap, arrays, last_linear, meta_entry, state  # noqa: E402
 
 from gops.algorithm.ddpg import DDPG  # noqa: E402
 from gops.algorithm.td3 import TD3  # noqa: E402
 
-from gops_amd.utils.synthetic import act_dim_of, make_batch  # noqa: E402
-
 # name: (cfg, action limits (low, high), attributes set after construction, PER)
-SHAPE_A = dict(env_id="gym_pendulum", batch=70, hidden=(32, 16), act="relu")               # obs 3 / act 1
-SHAPE_B = dict(env_id="pyth_lq", lq_config="s4a2", batch=33, hidden=(64,), act="gelu")      # obs 4 / act 2
-LIM_A = ([-2.0], [2.0])
-LIM_B = ([-1.0, -0.5], [2.0, 0.5])
 CASES = {
     "td3_pend_relu": (dict(SHAPE_A, alg="TD3"), LIM_A, dict(target_noise=0.4, noise_clip=0.5, reward_scale=0.5), False),
     "td3_lqs4a2_gelu": (dict(SHAPE_B, alg="TD3"), LIM_B, dict(target_noise=0.3, noise_clip=0.4, gamma=0.97), False),
@@ -40,53 +36,21 @@ CASES = {
 }
 
 
-class NoiseTap:
-    """Records what `torch.randn_like` returns while the reference runs."""
-
-    def __enter__(self):
-        self.draws, self._orig = [], torch.randn_like
-
-        def tapped(*a, **k):
-            x = self._orig(*a, **k)
-            self.draws.append(x.detach().clone())
-            return x
-
-        torch.randn_like = tapped
-        return self
-
-    def __exit__(self, *exc):
-        torch.randn_like = self._orig
-
-
 def build(cfg, lim, attrs, per, seed):
-    torch.manual_seed(seed)
-    kw = mg.alg_kwargs(dict(cfg, alg="INFADP", horizon=1), seed, action_low_limit=np.array(lim[0], dtype=np.float32),
-                       action_high_limit=np.array(lim[1], dtype=np.float32))
-    kw.update(algorithm=cfg["alg"], value_func_name="ActionValue", value_output_activation="linear",
-              buffer_name="prioritized_replay_buffer" if per else "replay_buffer")
     ctor = {k: attrs[k] for k in ("target_noise", "noise_clip") if k in attrs}
-    alg = (TD3 if cfg["alg"] == "TD3" else DDPG)(**ctor, **kw)
+    alg, g = common.build_reference(TD3 if cfg["alg"] == "TD3" else DDPG, cfg, lim, seed, value_func_name="ActionValue",
+                                    buffer_name="prioritized_replay_buffer" if per else "replay_buffer", **ctor)
     for k, v in attrs.items():
         if k not in ctor:
             setattr(alg, k, v)
-    g = torch.Generator().manual_seed(seed + 1000)
-    nets = alg.networks
-    q_names = ["q1", "q2"] if cfg["alg"] == "TD3" else ["q"]
-    with torch.no_grad():   # the targets start as copies: move them apart; a steep target head saturates the squash on some rows
-        for n in [f"{q}_target" for q in q_names] + ["policy_target"]:
-            amp = 0.1 if n == "policy_target" else 0.6   # (far enough for the twin targets to cross inside the batch)
-            for p in getattr(nets, n).parameters():
-                p.add_(amp * (torch.rand(p.shape, generator=g) - 0.5))
-        head = [m for m in nets.policy_target.pi if isinstance(m, torch.nn.Linear)][-1]
-        head.weight.mul_(12.0)
-    return alg, q_names, g
+    with torch.no_grad():   # a steep target head saturates the squash on some rows
+        last_linear(alg.networks.policy_target.pi).weight.mul_(12.0)
+    return alg, ["q1", "q2"] if cfg["alg"] == "TD3" else ["q"], g
 
 
 def batch_of(cfg, seed, g, per):
-    B, A = cfg["batch"], act_dim_of(cfg)
-    obs = make_batch(dict(cfg, alg="INFADP", horizon=1), seed)["obs"]
-    data = dict(obs=obs, act=torch.rand(B, A, generator=g) * 2 - 1, rew=torch.randn(B, generator=g),
-                obs2=obs + 0.05 * torch.randn(obs.shape, generator=g), done=(torch.rand(B, generator=g) < 0.15).float())
+    B = cfg["batch"]
+    data = common.batch_of(cfg, seed, g)
     if per:
         data["idx"] = torch.randperm(4 * B, generator=g)[:B].to(torch.int32) + (4 * B - 1)
         data["weight"] = 0.2 + 0.8 * torch.rand(B, generator=g)
@@ -97,7 +61,7 @@ def balance(alg, q_names, data, spread=None):
     """Centre the target policy's head and the twin target critics on this batch: rows on both sides of the squash, and of the minimum.
     `spread`: the standard deviation the head's outputs are scaled to first (several batches have to saturate on both sides)."""
     nets, o2 = alg.networks, data["obs2"]
-    last = lambda seq: [m for m in seq if isinstance(m, torch.nn.Linear)][-1]   # noqa: E731
+    last = last_linear
     with torch.no_grad():
         if spread is not None:
             scale = spread / nets.policy_target.pi(o2).std(dim=0)
@@ -148,19 +112,17 @@ def one_update(name):
     alg, q_names, g = build(cfg, lim, attrs, per, seed)
     data = batch_of(cfg, seed, g, per)
     balance(alg, q_names, data)
-    out = {"in/" + k: v.numpy().copy() for k, v in data.items()}
-    out["meta/cfg"] = json.dumps(dict(cfg=cfg, lim=lim, attrs=attrs, per=per, seed=seed))
-    out.update({k: v.copy() for k, v in mg.sd_to_np(alg.networks.state_dict()).items()})
-    with NoiseTap() as tap:
+    out = {**arrays(data, "in/"), **meta_entry(cfg=cfg, lim=lim, attrs=attrs, per=per, seed=seed), **state(alg)}
+    with DrawTap() as tap:
         extra, info = alg.get_remote_update_info(data, 0)
     tb = extra[0] if per else extra
     xi = None
     if cfg["alg"] == "TD3":
-        assert len(tap.draws) == 1
-        xi = tap.draws[0]
+        assert len(tap.noise) == 1
+        xi = tap.noise[0]
         out["in/target_noise"] = xi.numpy().copy()
     else:
-        assert not tap.draws
+        assert not tap.noise
     backup, a2, q_t, losses = backup_of(alg, q_names, data, xi)
     assert abs(float(sum(losses)) - tb["Loss/Critic loss-RL iter"]) <= 1e-6 * max(1.0, abs(tb["Loss/Critic loss-RL iter"])), name
     if cfg["alg"] == "TD3":
@@ -168,13 +130,7 @@ def one_update(name):
     out.update(backup=backup.numpy(), a2=a2.numpy(), q_targ=q_t.numpy())
     for q, l in zip(q_names, losses):
         out[f"loss_{q}"] = np.float64(l)
-    for key, grads in info.items():
-        if key.endswith("_grad"):
-            for i, gr in enumerate(grads):
-                out[f"{key}/{i}"] = gr.detach().numpy().copy()
-    for k, v in tb.items():
-        if not k.startswith("Time/"):
-            out["tb/" + k] = np.float64(v)
+    out.update(common.update_entries(info, tb, log_alpha=False))
     if per:
         assert torch.equal(extra[1], data["idx"])
         out["abs_err"] = extra[2].detach().numpy().copy()
@@ -189,28 +145,23 @@ def five_updates():
     attrs = dict(target_noise=0.4, noise_clip=0.5, delay_update=2, tau=0.05)
     seed = zlib.crc32(name.encode()) % 1000
     alg, q_names, g = build(cfg, lim, attrs, False, seed)
-    for opt in (alg.networks.q1_optimizer, alg.networks.q2_optimizer, alg.networks.policy_optimizer):
-        for group in opt.param_groups:
-            group["lr"] = 1e-2
-    out = {"meta/cfg": json.dumps(dict(cfg=cfg, lim=lim, attrs=attrs, per=False, seed=seed, lr=1e-2))}
-    batches = [batch_of(cfg, seed + k, g, False) for k in range(5)]
-    balance(alg, q_names, {key: torch.cat([b[key] for b in batches]) for key in batches[0]}, spread=3.0)   # centred on all five batches at once
-    out.update({key: v.copy() for key, v in mg.sd_to_np(alg.networks.state_dict(), "sd0/").items()})
+    out = meta_entry(cfg=cfg, lim=lim, attrs=attrs, per=False, seed=seed, lr=1e-2)
+    batches, sd0 = common.five_batches(alg, cfg, seed, g, lambda data: balance(alg, q_names, data, spread=3.0))
+    out.update(sd0)
     for k, data in enumerate(batches):
-        out.update({f"in{k}/" + key: v.numpy().copy() for key, v in data.items()})
-        import copy
+        out.update(arrays(data, f"in{k}/"))
         before = copy.deepcopy(alg.networks)   # the targets this update's backup is formed with
-        with NoiseTap() as tap:
+        with DrawTap() as tap:
             tb = alg.local_update(data, k)
-        assert len(tap.draws) == 1
-        out[f"in{k}/target_noise"] = tap.draws[0].numpy().copy()
+        assert len(tap.noise) == 1
+        out[f"in{k}/target_noise"] = tap.noise[0].numpy().copy()
         after, alg.networks = alg.networks, before
-        _, a2, q_t, _ = backup_of(alg, q_names, data, tap.draws[0])
-        assert_td3_cases(f"{name}[{k}]", alg, data, tap.draws[0], a2, q_t)
+        _, a2, q_t, _ = backup_of(alg, q_names, data, tap.noise[0])
+        assert_td3_cases(f"{name}[{k}]", alg, data, tap.noise[0], a2, q_t)
         alg.networks = after
         out[f"loss_q{k}"] = np.float64(tb["Loss/Critic loss-RL iter"])
         out[f"loss_pi{k}"] = np.float64(tb["Loss/Actor loss-RL iter"])
-        out.update({key: v.copy() for key, v in mg.sd_to_np(alg.networks.state_dict(), f"sd{k + 1}/").items()})
+        out.update(state(alg, f"sd{k + 1}/"))
     mg.save(name, **out)
 
 

@@ -1,16 +1,13 @@
 """DSAC-T without a GPU: registries, construction, the two continuous action distributions, refusals, the C ABI of the new entry
 points, and the update restated on the host against every fixture of tests/golden/make_golden_dsact.py."""
-import ctypes
 import os
-import re
-import subprocess
 
-import numpy as np
 import pytest
 import torch
 
+from ac_helpers import (DSACT_ONE_UPDATE, REFUSALS, SOFT_REFUSALS, alg_kwargs, batch_of, check_abi, check_host_restatement, check_refusals,
+                        check_soft_tb_and_alpha, q_names, restate_update)
 from conftest import ROOT, golden_meta, load_golden, rel_l2
-from dsact_helpers import GRAD_KEYS, ONE_UPDATE, TOL, alg_kwargs, batch_of, load_alg, restate_update
 
 from gops_amd.create_pkg import create_alg as ca
 from gops_amd.create_pkg.create_alg import create_alg, create_approx_contrainer
@@ -29,7 +26,7 @@ def test_registries_and_construction():
     assert {"DDPG", "TD3", "RPI"} == set(ca.loop_registry) and {"DSACT"} == set(ca.soft_registry)
     g = load_golden("dsact_pend_relu")
     alg = create_alg(**_kw())
-    assert type(alg).__name__ == "DSACT"
+    assert type(alg).__name__ == "DSACT" and q_names(alg) == ("q1", "q2")
     kw = _kw()
     kw.pop("algorithm")
     for nets in (alg.networks, create_approx_contrainer("DSACT", **kw)):
@@ -84,52 +81,22 @@ def test_apprfunc_dict_resolves_the_distribution():
             create_apprfunc(**dict(var, std_type=std_type))
 
 
-@pytest.mark.parametrize("name", ONE_UPDATE)
+@pytest.mark.parametrize("name", DSACT_ONE_UPDATE)
 def test_host_restatement_matches_the_reference(name, capsys):
     """The fixture's state dict loaded into the networks create_alg built, one update restated on the host in fp32 with the recorded
     draws: targets, the samples, every gradient, log_alpha's gradient, mean_std and the tb values against the reference's, rel-L2 <=
     1e-4.  This is the TEST's restatement (the oracle of the GPU tests at float64): it shows that the modules and distributions are
     the reference's and that the oracle is faithful."""
-    alg, g, meta = load_alg(name)
-    got = restate_update(alg, batch_of(g), dtype=torch.float32)
-    worst = 0.0
-    for key in ("target_q", "target_q_sample", "a2", "logp_next", "q_targ", "new_act", "new_logp", "mean_std"):
-        worst = max(worst, rel_l2(got[key], g[key]))
-    for n in GRAD_KEYS:
-        for i, gr in enumerate(got["grads"][n]):
-            worst = max(worst, rel_l2(gr, g[f"{n}_grad/{i}"]))
-    with capsys.disabled():
-        print(f"\n{name}: worst rel-L2 of targets / samples / gradients against the reference {worst:.2e}")
-    assert worst <= TOL
-    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
-    for k, v in got["tb"].items():
-        assert close(v, g["tb/" + k]), k
-    if alg.auto_alpha:
-        assert close(got["log_alpha_grad"], g["log_alpha_grad"])
-    else:
-        assert "log_alpha_grad" not in g
+    keys = ("target_q", "target_q_sample", "a2", "logp_next", "q_targ", "new_act", "new_logp", "mean_std")
+    alg, g, meta, got = check_host_restatement(name, keys, "targets / samples", capsys)
+    check_soft_tb_and_alpha(alg, g, got)
     # fp32 still resolves 1 + 1e-6 - tanh(u)^2 on these rows: the fp32 log-probabilities are the float64 ones at 1e-5
     ref64 = restate_update(alg, batch_of(g))
     assert rel_l2(got["logp_next"], ref64["logp_next"]) <= 1e-5 and rel_l2(got["new_logp"], ref64["new_logp"]) <= 1e-5
 
 
 def test_refusals_carry_a_reason():
-    cases = [(dict(policy_func_type="POLY", policy_degree=1, policy_add_bias=False), "POLY"),
-             (dict(value_func_type="POLY", value_degree=2, value_add_bias=False), "POLY"),
-             (dict(policy_func_type="LipsNet"), "LipsNet"),
-             (dict(policy_func_name="DetermPolicy"), "stochastic policy"),
-             (dict(policy_act_distribution="GaussDistribution"), "tanh-Gaussian"),
-             (dict(policy_act_distribution="default"), "tanh-Gaussian"),
-             (dict(value_func_name="ActionValue"), "distributional action-value"),
-             (dict(value_output_activation="tanh"), "linear output"),
-             (dict(policy_output_activation="relu"), "linear output"),
-             (dict(mlp_dtype="fp16"), "fp32 only"),
-             (dict(buffer_name="prioritized_replay_buffer"), "no priorities"),
-             (dict(trainer="off_sync_trainer"), "off_serial"),
-             (dict(trainer="off_async_trainer"), "off_serial")]
-    for over, reason in cases:
-        with pytest.raises(NotImplementedError, match=reason):
-            create_alg(**_kw(**over))
+    check_refusals(_kw, REFUSALS + SOFT_REFUSALS + [(dict(value_func_name="ActionValue"), "distributional action-value")])
     for alg in ("DDPG", "TD3"):   # unchanged: the deterministic algorithms still refuse a stochastic policy
         with pytest.raises(NotImplementedError, match="deterministic policy"):
             create_alg(**_kw(algorithm=alg, value_func_name="ActionValue"))
@@ -138,26 +105,7 @@ def test_refusals_carry_a_reason():
 def test_abi_of_the_dsact_entry_points(tmp_path):
     """Declared in the header (plain C99), mirrored by ctypes field for field, exported by the library; the version stays 15."""
     from gops_amd import hip_backend as hb
-    header = open(os.path.join(ROOT, "include", "gops_hip.h")).read()
-    assert "#define GOPS_HIP_ABI_VERSION 15" in header
-    for name in ("gops_soft_backup_workspace_bytes", "gops_soft_backup", "gops_dsact_critic_loss", "gops_tanh_gauss_forward",
-                 "gops_tanh_gauss_backward"):
-        assert re.search(rf"\b{name}\s*\(", header) and name in hb.EXPORTED_SYMBOLS
-        assert hasattr(ctypes.CDLL(hb.LIB_PATH), name)
-    assert int(re.search(r"#define GOPS_DSACT_STATS_FLOATS (\d+)", header).group(1)) == hb.DSACT_STATS_FLOATS
-    assert int(re.search(r"#define GOPS_TANH_GAUSS_STATS_FLOATS (\d+)", header).group(1)) == hb.TANH_GAUSS_STATS_FLOATS
-    lines = []
-    for st in ("GopsSoftBackup", "GopsTanhGauss"):
-        lines.append(f'    printf(" %zu", sizeof({st}));\n')
-        lines += [f'    printf(" %zu", offsetof({st}, {f[0]}));\n' for f in getattr(hb, st)._fields_]
-    lines.append('    printf(" %zu", sizeof(GopsDsactState));\n')
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gops_hip.h"\nint main(void) {\n' + "".join(lines) + "    return 0;\n}\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    want = []
-    for st in ("GopsSoftBackup", "GopsTanhGauss"):
-        cls = getattr(hb, st)
-        want += [ctypes.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_]
-    assert got == want + [16]
+    check_abi(tmp_path, [("GopsSoftBackup", hb.GopsSoftBackup), ("GopsTanhGauss", hb.GopsTanhGauss), ("GopsDsactState", 16)],
+              ("gops_soft_backup_workspace_bytes", "gops_soft_backup", "gops_dsact_critic_loss", "gops_tanh_gauss_forward", "gops_tanh_gauss_backward"),
+              [("GOPS_DSACT_STATS_FLOATS", hb.DSACT_STATS_FLOATS), ("GOPS_TANH_GAUSS_STATS_FLOATS", hb.TANH_GAUSS_STATS_FLOATS)])
     assert "dsact.hip" in open(os.path.join(ROOT, "gops_amd", "csrc", "Makefile")).read()

@@ -1,62 +1,37 @@
 """GPU: DSAC-T (algorithm/dsact.py) and its kernels - `gops_soft_backup`, `gops_dsact_critic_loss`, `gops_tanh_gauss_forward /
 _backward` - against a float64 restatement and the reference fixtures of tests/golden/make_golden_dsact.py.
 
-Bound of the soft backup (the rule of test_td3_gpu.py): the composed path's max error against float64 is measured on the same inputs
-first; the fused kernel may use twice that, but not less than 4 fp32 ulp of the largest |value|.  2b and 2c form every value in double
-from their fp32 inputs and round once: 4 ulp rel-L2 against float64 evaluated on the same fp32 inputs.
+Bound of the soft backup (ac_helpers.check_backup, the rule of test_td3_gpu.py): the composed path's max error against float64 is
+measured on the same inputs first; the fused kernel may use twice that, but not less than 4 fp32 ulp of the largest |value|.  2b and
+2c form every value in double from their fp32 inputs and round once: 4 ulp rel-L2 against float64 evaluated on the same fp32 inputs.
 """
 import numpy as np
 import pytest
 import torch
 
+import ac_helpers as ac
+from ac_helpers import DSACT_ONE_UPDATE, EPS32, S, TOL, alg_kwargs, load_alg, restate_update
 from conftest import rel_l2
-from dsact_helpers import GRAD_KEYS, ONE_UPDATE, TOL, alg_kwargs, batch_of, load_alg, restate_update
 
 from gops_amd import hip_backend as hb
 from gops_amd.create_pkg.create_alg import create_alg
 
 pytestmark = pytest.mark.gpu
-EPS32 = 2.0 ** -23
-S = -777.0   # sentinel
 OUT = ("target_q", "target_q_sample", "a2", "logp", "q_targ")
+CTOR = dict(gamma=0.97, tau=0.05, auto_alpha=True, delay_update=2)
 
 
 def _alg(obs, act, hidden, activation, seed=5, **over):
-    """A DSACT object on the GPU: targets randomised apart, policy heads with means within +-0.9 and log stds on both sides of the
-    clamp [-3, -0.5] (so |u| <= 0.9 + 3.3 * exp(-0.5) stays where fp32 resolves 1 + 1e-6 - tanh(u)^2), twin critics centred."""
-    meta = dict(cfg=dict(alg="DSACT", env_id="gym_pendulum" if obs == 3 else "pyth_lq", hidden=hidden, act=activation),
-                lim=([-2.0], [2.0]) if act == 1 else ([-1.0, -0.5], [2.0, 0.5]), seed=seed, min_log_std=-3.0, max_log_std=-0.5,
-                ctor=dict(gamma=0.97, tau=0.05, auto_alpha=True, delay_update=2))
-    if obs == 4:
-        meta["cfg"]["lq_config"] = "s4a2"
-    torch.manual_seed(seed)
-    a = create_alg(**alg_kwargs(meta, True, **over))
-    g = torch.Generator().manual_seed(seed + 1)
-    nets = a.networks
-    with torch.no_grad():
-        for n, p in nets.named_parameters():
-            if "_target" in n:
-                p.add_(0.3 * (torch.rand(p.shape, generator=g) - 0.5))
-        probe = torch.randn(256, obs, generator=g)
-        for pol in (nets.policy, nets.policy_target):
-            head, y = pol.linear_layers()[-1], pol.policy(probe)
-            scale = torch.cat([0.9 / y[:, :act].abs().max(dim=0).values.clamp_min(0.9), 1.6 / y[:, act:].std(dim=0)])
-            head.weight.mul_(scale[:, None])
-            head.bias.mul_(scale)
-            head.bias[act:].sub_(pol.policy(probe)[:, act:].median(dim=0).values + 1.75)
-        a2 = nets.policy_target.get_act_dist(nets.policy_target(probe)).mode()
-        nets.q2_target.linear_layers()[-1].bias[0].add_((nets.q1_target(probe, a2)[:, 0] - nets.q2_target(probe, a2)[:, 0]).median())
-    nets.cuda()
-    return a
+    """A DSACT object on the GPU: targets randomised apart, the heads of ac_helpers.shape_soft_heads, twin critics centred."""
+    meta = ac.synthetic_meta("DSACT", obs, act, hidden, activation, seed, min_log_std=-3.0, max_log_std=-0.5, ctor=CTOR)
+    return ac.synthetic_alg(meta, obs, act, ac.shape_soft_heads, **over)
 
 
 def _wide_act_alg(hidden, seed=7):
     """obs 6, act_dim 4: eight head outputs."""
-    lim = ([-1.0, -0.5, -2.0, -1.0], [2.0, 0.5, 2.0, 1.0])
     torch.manual_seed(seed)
-    kw = alg_kwargs(dict(cfg=dict(alg="DSACT", env_id="pyth_idpendulum", hidden=hidden, act="elu"), lim=lim, seed=seed, min_log_std=-3.0,
-                         max_log_std=-0.5, ctor=dict(gamma=0.97, tau=0.05, auto_alpha=True, delay_update=2)), True, action_dim=4)
-    a = create_alg(**kw)
+    meta = ac.synthetic_meta("DSACT", 6, 4, hidden, "elu", seed, min_log_std=-3.0, max_log_std=-0.5, ctor=CTOR)
+    a = create_alg(**alg_kwargs(meta, True, action_dim=4))
     g = torch.Generator().manual_seed(seed + 1)
     with torch.no_grad():
         for n, p in a.networks.named_parameters():
@@ -70,14 +45,7 @@ def _wide_act_alg(hidden, seed=7):
 
 
 def _data(B, obs, act, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    o = torch.randn(B, obs, generator=g)
-    d = (torch.rand(B, generator=g) < 0.2).float()
-    if B > 1:
-        d[0], d[-1] = 1.0, 0.0
-    return dict(obs=o, act=torch.rand(B, act, generator=g) * 2 - 1, rew=torch.randn(B, generator=g), obs2=o + 0.1 * torch.randn(B, obs, generator=g),
-                done=d, eps_new=torch.randn(B, act, generator=g), eps_next=torch.randn(B, act, generator=g).clamp(-3.3, 3.3),
-                z_next=2 * torch.randn(2, B, generator=g))
+    return ac.synthetic_batch(B, obs, act, seed, z_next=(2, B))
 
 
 def _fused(alg, batch, **kw):
@@ -91,16 +59,7 @@ def _check_backup(alg, data, label):
     batch = alg._batch(data)
     ref = restate_update(alg, data)
     ref["logp"] = ref["logp_next"]
-    comp = dict(zip(OUT, alg._targets_composed(batch)))
-    got, again = _fused(alg, batch), _fused(alg, batch)
-    for k in OUT:
-        want = ref[k].reshape(got[k].shape)
-        err_c = (comp[k].double().cpu() - want).abs().max().item()
-        err_f = (got[k].double().cpu() - want).abs().max().item()
-        bound = max(2 * err_c, 4 * EPS32 * want.abs().max().item())
-        print(f"{label} {k}: fused {err_f:.3e} composed {err_c:.3e} bound {bound:.3e}")
-        assert err_f <= bound, (label, k, err_f, err_c, bound)
-        assert torch.equal(got[k], again[k]), (label, k)
+    ac.check_backup(_fused(alg, batch), _fused(alg, batch), dict(zip(OUT, alg._targets_composed(batch))), ref, OUT, label)
     return ref, batch
 
 
@@ -263,132 +222,64 @@ def test_tanh_gauss_head_against_float64(A, B):
 
 
 def test_rows_beyond_the_batch_stay_untouched():
-    B, pad = 70, 64
+    B = 70
     alg = _alg(4, 2, [64, 48], "tanh")
     batch = alg._batch(_data(B, 4, 2))
-    full = lambda n: torch.full((n,), S, device="cuda")   # noqa: E731
-    bufs = dict(target_q=full(B + pad), target_q_sample=full(B + pad), a2=full(2 * B + pad), logp=full(B + pad), q_targ=full(4 * B + pad))
-    sizes = dict(target_q=B, target_q_sample=B, a2=2 * B, logp=B, q_targ=4 * B)
-    _fused(alg, batch, out={k: v[:sizes[k]] for k, v in bufs.items()})
-    torch.cuda.synchronize()
-    for k, t in bufs.items():
-        assert (t[sizes[k]:] == S).all() and (t[:sizes[k]] != S).all(), k
+    ac.check_rows_beyond_the_batch(lambda out: _fused(alg, batch, out=out), dict(target_q=B, target_q_sample=B, a2=2 * B, logp=B, q_targ=4 * B))
+
+
+def _mean_std(alg):
+    return torch.stack([alg.mean_std1, alg.mean_std2]).cpu()
 
 
 @pytest.mark.parametrize("fused", [True, False])
-@pytest.mark.parametrize("name", ONE_UPDATE)
+@pytest.mark.parametrize("name", DSACT_ONE_UPDATE)
 def test_one_update_matches_the_reference(name, fused):
     alg, g, meta = load_alg(name, use_gpu=True, fused_target=fused)
-    tb, info = alg.get_remote_update_info(batch_of(g), 0)
-    assert alg.backup_path == ("fused" if fused else "composed")
-    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
-    for k in [k for k in g if k.startswith("tb/")]:
-        assert close(tb[k[3:]], g[k]), (k, float(tb[k[3:]]), float(g[k]))
-    assert set(info) == {f"{n}_grad" for n in GRAD_KEYS} | {"iteration"} | ({"log_alpha_grad"} if alg.auto_alpha else set())
-    for n in GRAD_KEYS:
-        for i, gr in enumerate(info[f"{n}_grad"]):
-            assert rel_l2(gr.cpu(), g[f"{n}_grad/{i}"]) < TOL, (n, i, rel_l2(gr.cpu(), g[f"{n}_grad/{i}"]))
-    if alg.auto_alpha:
-        assert close(info["log_alpha_grad"], g["log_alpha_grad"])
-    assert rel_l2(torch.stack([alg.mean_std1, alg.mean_std2]).cpu(), g["mean_std"]) < TOL
-    before = {k: v.detach().clone() for k, v in alg.networks.state_dict().items()}
-    alg.remote_update(info)
-    after = alg.networks.state_dict()
-    assert all(torch.isfinite(p).all() for p in after.values())
-    assert all((after[k] - before[k]).abs().max() > 0 for k in before if "lim" not in k and (alg.auto_alpha or k != "log_alpha"))
+    _, _, _, info = ac.check_one_update(alg, g, meta, fused)
+    assert rel_l2(_mean_std(alg), g["mean_std"]) < TOL
+    ac.check_the_step_moves_everything(alg, info)
 
 
 @pytest.mark.parametrize("name", ["dsact_pend_relu", "dsact_lqs4a2_gelu"])
 def test_fused_and_composed_updates_agree(name):
-    out = {}
-    for fused in (True, False):
-        alg, g, meta = load_alg(name, use_gpu=True, fused_target=fused)
-        _, info = alg.get_remote_update_info(batch_of(g), 0)
-        out[fused] = {n: [t.clone() for t in v] for n, v in info.items() if n.endswith("_grad") and n != "log_alpha_grad"}
-    _check_backup(alg, batch_of(g), name)
-    for n in out[True]:
-        for a, b in zip(out[True][n], out[False][n]):
-            assert rel_l2(a.cpu(), b.cpu()) <= 1e-5, n
+    ac.check_fused_and_composed_agree(name, _check_backup)
 
 
 def test_dsact_five_updates_match_the_reference():
     """Five `local_update` calls with delay_update = 2 and the reference's own draws handed in: every parameter, log_alpha and
     mean_std after each call; policy, log_alpha and all three targets keep their bits on iterations 1 and 3."""
-    alg, g, meta = load_alg("dsact_pend_5updates", use_gpu=True, prefix="sd0/")
-    assert alg.delay_update == 2 and alg.tau == 0.05
-    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
-    delayed = lambda key: key == "log_alpha" or key.startswith("policy.") or "_target." in key   # noqa: E731
-    for k in range(5):
-        before = {key: v.detach().clone() for key, v in alg.networks.state_dict().items()}
-        tb = alg.local_update(batch_of(g, f"in{k}/"), k)
-        assert close(tb["Loss/Critic loss-RL iter"], g[f"loss_q{k}"]) and close(tb["Loss/Actor loss-RL iter"], g[f"loss_pi{k}"]), k
+    for alg, g, k, before in ac.five_updates("dsact_pend_5updates"):
+        assert alg.delay_update == 2 and alg.tau == 0.05
         for key, p in alg.networks.state_dict().items():
-            assert rel_l2(p.cpu().double(), g[f"sd{k + 1}/{key}"]) < TOL, (k, key)
-            if delayed(key) and "lim" not in key:
+            if ac.delayed(key) and "lim" not in key:
                 assert torch.equal(p, before[key]) == (k % 2 == 1), (k, key)
-        assert rel_l2(torch.stack([alg.mean_std1, alg.mean_std2]).cpu(), g[f"mean_std{k + 1}"]) < TOL, k
+        assert rel_l2(_mean_std(alg), g[f"mean_std{k + 1}"]) < TOL, k
 
 
 def test_graph_replay_equals_eager(monkeypatch):
-    B = 70
-
-    def run(mode):
-        monkeypatch.setenv("GOPS_HIP_GRAPH", mode)
-        alg = _alg(3, 1, [32, 16], "relu", seed=4)
-        logs = []
-        for it in range(14):
-            data = {k: v for k, v in _data(B, 3, 1, seed=100 + it).items() if not k.startswith(("eps_", "z_"))}   # the algorithm's own draws
-            logs.append(dict(alg.local_update(data, it)))
-        return alg, logs
-
-    eager, log_e = run("0")
-    graph, log_g = run("1")
-    assert all(c.graph is not None for c in graph._graphs.values()) and len(graph._graphs) == 2
-    assert all(c.graph is None for c in eager._graphs.values())
-    for (ne, pe), (ng, pg) in zip(eager.networks.named_parameters(), graph.networks.named_parameters()):
-        assert ne == ng and torch.equal(pe, pg), ne
+    eager, graph = ac.check_graph_replay(lambda: _alg(3, 1, [32, 16], "relu", seed=4), 2, monkeypatch)
     assert torch.equal(eager._critic_loss_obj().state, graph._critic_loss_obj().state)
-    for a, b in zip(log_e, log_g):
-        for k in a:
-            if not k.startswith("Time/"):
-                assert float(a[k]) == float(b[k]), k
 
 
 def test_end_to_end(tmp_path):
     """OffSerialTrainer + replay_buffer + DeviceEnvSampler + evaluator on pyth_idpendulum: the sampler stores the policy's own
     log-probabilities, the evaluator takes the per-step path with the distribution's mode."""
-    from gops_amd.create_pkg.create_buffer import create_buffer
-    from gops_amd.create_pkg.create_env_model import create_env_model
-    from gops_amd.create_pkg.create_evaluator import create_evaluator
-    from gops_amd.create_pkg.create_trainer import create_trainer
     from gops_amd.trainer.sampler.device_env_sampler import DeviceEnvSampler
-    torch.manual_seed(0)
-    kw = dict(algorithm="DSACT", trainer="off_serial_trainer", seed=0, cnn_shared=False, env_id="pyth_idpendulum", obsv_dim=6, action_dim=1,
-              action_type="continu", action_low_limit=-np.ones(1, dtype=np.float32), action_high_limit=np.ones(1, dtype=np.float32),
-              policy_func_type="MLP", policy_func_name="StochaPolicy", policy_hidden_sizes=[64, 64], policy_hidden_activation="relu",
-              policy_act_distribution="TanhGaussDistribution", policy_learning_rate=1e-3, policy_min_log_std=-20, policy_max_log_std=0.5,
-              value_func_type="MLP", value_func_name="ActionValueDistri", value_hidden_sizes=[64, 64], value_hidden_activation="relu",
-              value_learning_rate=1e-3, alpha_learning_rate=3e-4, gamma=0.99, tau=0.005, auto_alpha=True, delay_update=2, use_gpu=True,
-              buffer_name="replay_buffer", buffer_max_size=4096, buffer_warm_size=512, replay_batch_size=64,
-              sample_interval=1, additional_info={}, max_iteration=8, log_save_interval=1000, apprfunc_save_interval=1000,
-              eval_interval=10 ** 9, save_folder=str(tmp_path), ini_network_dir=None)
-    alg = create_alg(**kw)
-    alg.networks.to("cuda")
-    model = create_env_model(**kw)
-    with pytest.warns(UserWarning, match="noise_std is ignored"):
-        smp = DeviceEnvSampler(dict(env_id="pyth_idpendulum"), model, n_envs=128, steps_per_sample=2, max_episode_steps=50, seed=3, noise_std=0.2)
-        smp.networks = alg.networks
-        first, _ = smp.sample()
-    assert (first["logp"] != 0).all() and first["logp"].shape == (256,)
-    buf = create_buffer(**kw)
-    ev = create_evaluator(**dict(kw, env_model=model, networks=alg.networks, num_eval_episode=4, eval_save=False, is_render=False,
-                                 max_episode_steps=40))
-    trainer = create_trainer(alg, smp, buf, ev, **kw)
-    for _ in range(6):
-        trainer.step()
-        trainer.iteration += 1
+
+    def sampler(model, alg):
+        with pytest.warns(UserWarning, match="noise_std is ignored"):
+            smp = DeviceEnvSampler(dict(env_id="pyth_idpendulum"), model, n_envs=128, steps_per_sample=2, max_episode_steps=50, seed=3, noise_std=0.2)
+            smp.networks = alg.networks
+            first, _ = smp.sample()
+        assert (first["logp"] != 0).all() and first["logp"].shape == (256,)
+        return smp
+
+    kw = ac.trainer_kwargs("DSACT", "pyth_idpendulum", 6, 1.0, tmp_path, policy_min_log_std=-20, policy_max_log_std=0.5, gamma=0.99,
+                           tau=0.005, auto_alpha=True, delay_update=2)
+    alg, buf, ev, trainer = ac.build_trainer(kw, sampler, True)
+    ac.run_trainer(trainer, alg)
     assert (buf.buf["logp"][:len(buf)] != 0).any()
-    assert alg.backup_path == "fused"
     assert all(torch.isfinite(p).all() for p in alg.networks.parameters())
     assert np.isfinite(ev.run_evaluation(0))
     assert ev.path == "loop: stochastic policy"

@@ -1,15 +1,11 @@
 """SAC and DSAC without a GPU: registries, construction, mandatory arguments, refusals, the C ABI of the new entry points, and the
 update restated on the host against every fixture of tests/golden/make_golden_sac.py."""
-import ctypes
-import os
-import re
-import subprocess
-
 import pytest
 import torch
 
-from conftest import ROOT, golden_meta, load_golden, rel_l2
-from sac_helpers import ONE_UPDATE, Q_NAMES, TOL, alg_kwargs, batch_of, load_alg, restate_update
+from ac_helpers import (REFUSALS, SAC_ONE_UPDATE, SOFT_REFUSALS, alg_kwargs, check_abi, check_host_restatement, check_refusals,
+                        check_soft_tb_and_alpha, q_names)
+from conftest import golden_meta, load_golden
 
 from gops_amd.create_pkg import create_alg as ca
 from gops_amd.create_pkg.create_alg import create_alg, create_approx_contrainer
@@ -42,12 +38,13 @@ def test_construction_follows_the_reference(name):
     for nets in (alg.networks, create_approx_contrainer(name, **kw)):
         assert [n for n, _ in nets.named_children()] == CHILDREN[name]
         assert list(nets.state_dict()) == [k[3:] for k in g if k.startswith("sd/")]
-    for n in Q_NAMES[name][:1]:   # (the fixture's maker shifted q2's output bias)
+    assert q_names(alg) == {"SAC": ("q1", "q2"), "DSAC": ("q",)}[name]
+    for n in q_names(alg)[:1]:   # (the fixture's maker shifted q2's output bias)
         for k, v in getattr(alg.networks, n).state_dict().items():
             assert torch.equal(v, torch.from_numpy(g[f"sd/{n}.{k}"])), (n, k)
     assert list(alg.networks.state_dict())[0] == "log_alpha" and alg.networks.log_alpha.item() == 1.0
     from gops_amd.hip_backend import HipAdam
-    for n in Q_NAMES[name] + ("policy", "alpha"):
+    for n in q_names(alg) + ("policy", "alpha"):
         assert isinstance(getattr(alg.networks, f"{n}_optimizer"), HipAdam)
     assert all(not p.requires_grad for n, p in alg.networks.named_parameters() if "_target." in n)
     if name == "SAC":
@@ -80,72 +77,30 @@ def test_mandatory_arguments_raise_the_references_key_error():
 
 @pytest.mark.parametrize("name", ["SAC", "DSAC"])
 def test_refusals_carry_a_reason(name):
-    cases = [(dict(policy_func_type="POLY", policy_degree=1, policy_add_bias=False), "POLY"),
-             (dict(value_func_type="POLY", value_degree=2, value_add_bias=False), "POLY"),
-             (dict(policy_func_type="LipsNet"), "LipsNet"),
-             (dict(policy_func_name="DetermPolicy"), "stochastic policy"),
-             (dict(policy_act_distribution="GaussDistribution"), "tanh-Gaussian"),
-             (dict(policy_act_distribution="default"), "tanh-Gaussian"),
-             (dict(value_func_name="ActionValueDistri" if name == "SAC" else "ActionValue"),
-              "an action-value function" if name == "SAC" else "distributional action-value"),
-             (dict(value_func_name="StateValue"), "action-value"),
-             (dict(value_output_activation="tanh"), "linear output"),
-             (dict(policy_output_activation="relu"), "linear output"),
-             (dict(mlp_dtype="fp16"), "fp32 only"),
-             (dict(buffer_name="prioritized_replay_buffer"), "no priorities"),
-             (dict(trainer="off_sync_trainer"), "off_serial"),
-             (dict(trainer="off_async_trainer"), "off_serial")]
-    for over, reason in cases:
-        with pytest.raises(NotImplementedError, match=reason):
-            create_alg(**_kw(name, **over))
+    check_refusals(lambda **over: _kw(name, **over),
+                   REFUSALS + SOFT_REFUSALS + [(dict(value_func_name="ActionValueDistri" if name == "SAC" else "ActionValue"),
+                                                "an action-value function" if name == "SAC" else "distributional action-value"),
+                                               (dict(value_func_name="StateValue"), "action-value")])
 
 
 def test_abi_of_the_soft_q_entry_points(tmp_path):
     """Declared in the header (plain C99), mirrored by ctypes field for field, exported by the library; the version stays 15."""
     from gops_amd import hip_backend as hb
-    header = open(os.path.join(ROOT, "include", "gops_hip.h")).read()
-    assert "#define GOPS_HIP_ABI_VERSION 15" in header
-    for name in ("gops_soft_q_backup_workspace_bytes", "gops_soft_q_backup", "gops_dsac_critic_loss"):
-        assert re.search(rf"\b{name}\s*\(", header) and name in hb.EXPORTED_SYMBOLS
-        assert hasattr(ctypes.CDLL(hb.LIB_PATH), name)
-    assert int(re.search(r"#define GOPS_DSAC_STATS_FLOATS (\d+)", header).group(1)) == hb.DSAC_STATS_FLOATS
-    lines = ['    printf(" %zu", sizeof(GopsSoftQBackup));\n']
-    lines += [f'    printf(" %zu", offsetof(GopsSoftQBackup, {f[0]}));\n' for f in hb.GopsSoftQBackup._fields_]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gops_hip.h"\nint main(void) {\n' + "".join(lines) + "    return 0;\n}\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    cls = hb.GopsSoftQBackup
-    assert got == [ctypes.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_]
-    assert [f[0] for f in cls._fields_] == ["policy", "q", "n_q", "distri", "act_low", "act_high", "min_log_std", "max_log_std", "gamma",
-                                            "alpha", "log_alpha"]
+    check_abi(tmp_path, [("GopsSoftQBackup", hb.GopsSoftQBackup)], ("gops_soft_q_backup_workspace_bytes", "gops_soft_q_backup", "gops_dsac_critic_loss"),
+              [("GOPS_DSAC_STATS_FLOATS", hb.DSAC_STATS_FLOATS)])
+    assert [f[0] for f in hb.GopsSoftQBackup._fields_] == ["policy", "q", "n_q", "distri", "act_low", "act_high", "min_log_std", "max_log_std",
+                                                           "gamma", "alpha", "log_alpha"]
 
 
-@pytest.mark.parametrize("name", ONE_UPDATE)
+@pytest.mark.parametrize("name", SAC_ONE_UPDATE)
 def test_host_restatement_matches_the_reference(name, capsys):
     """The fixture's state dict loaded into the networks create_alg built, one update restated on the host in fp32 with the recorded
     draws: backup, samples, losses, every gradient, log_alpha's gradient and the tb values against the reference's, rel-L2 <= 1e-4.
     This is the TEST's restatement (the oracle of the GPU tests at float64): it shows that the modules and distributions are the
     reference's and that the oracle is faithful."""
-    alg, g, meta = load_alg(name)
-    got = restate_update(alg, batch_of(g), dtype=torch.float32)
-    worst = 0.0
-    for key in ("backup", "a2", "logp_next", "q_targ", "new_act", "new_logp", "loss_q", "loss_pi") + (("td_bound",) if "td_bound" in g else ()):
-        worst = max(worst, rel_l2(got[key], g[key]))
-    for n in Q_NAMES[meta["cfg"]["alg"]] + ("policy",):
-        for i, gr in enumerate(got["grads"][n]):
-            worst = max(worst, rel_l2(gr, g[f"{n}_grad/{i}"]))
-    with capsys.disabled():
-        print(f"\n{name}: worst rel-L2 of backup / samples / losses / gradients against the reference {worst:.2e}")
-    assert worst <= TOL
-    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
-    tb_keys = [k for k in g if k.startswith("tb/")]
-    assert {k[3:] for k in tb_keys} == set(got["tb"])
-    for k in tb_keys:
-        assert close(got["tb"][k[3:]], g[k]), k
-    if alg.auto_alpha:
-        assert close(got["log_alpha_grad"], g["log_alpha_grad"])
-    else:
-        assert "log_alpha_grad" not in g
+    keys = ("backup", "a2", "logp_next", "q_targ", "new_act", "new_logp", "loss_q", "loss_pi") + (("td_bound",) if name.startswith("dsac") else ())
+    alg, g, meta, got = check_host_restatement(name, keys, "backup / samples / losses", capsys)
+    assert ("td_bound" in g) == name.startswith("dsac")
+    check_soft_tb_and_alpha(alg, g, got)
     if "binds" in got:   # DSAC: the td_bound clamp binds on some rows and is idle on others
         assert got["binds"].any() and (~got["binds"]).any()

@@ -1,10 +1,10 @@
 """GPU: SAC and DSAC (algorithm/sac.py, dsac.py) and their kernels - `gops_soft_q_backup`, `gops_dsac_critic_loss` - against a float64
 restatement and the reference fixtures of tests/golden/make_golden_sac.py.
 
-Bound of the soft Q backup (the rule of test_td3_gpu.py / test_dsact_gpu.py): the composed path's max error against float64 is
-measured on the same inputs first; the fused kernel may use twice that, but not less than 4 fp32 ulp of the largest |value|.  The
-critic-loss kernel forms every value in double from its fp32 inputs and rounds once: 4 ulp rel-L2 against float64 evaluated on the
-same fp32 inputs.
+Bound of the soft Q backup (ac_helpers.check_backup, the rule of test_td3_gpu.py / test_dsact_gpu.py): the composed path's max error
+against float64 is measured on the same inputs first; the fused kernel may use twice that, but not less than 4 fp32 ulp of the
+largest |value|.  The critic-loss kernel forms every value in double from its fp32 inputs and rounds once: 4 ulp rel-L2 against
+float64 evaluated on the same fp32 inputs.
 """
 import copy
 
@@ -12,61 +12,26 @@ import numpy as np
 import pytest
 import torch
 
+import ac_helpers as ac
+from ac_helpers import EPS32, S, SAC_FIVE_UPDATES, SAC_ONE_UPDATE, TOL, close, load_alg
 from conftest import rel_l2
-from sac_helpers import FIVE_UPDATES, ONE_UPDATE, Q_NAMES, TOL, alg_kwargs, batch_of, load_alg
 
 from gops_amd import hip_backend as hb
-from gops_amd.create_pkg.create_alg import create_alg
 
 pytestmark = pytest.mark.gpu
-EPS32 = 2.0 ** -23
-S = -777.0   # sentinel
 OUT = ("backup", "a2", "logp", "q_targ")
 CTOR = {"SAC": dict(gamma=0.97, tau=0.05, auto_alpha=True), "DSAC": dict(gamma=0.97, tau=0.05, auto_alpha=True, bound=True, delay_update=2)}
-LIM4 = ([-1.0, -0.5, -2.0, -1.0], [2.0, 0.5, 2.0, 1.0])
 
 
 def _alg(name, obs, act, hidden, activation, seed=5, **over):
-    """A SAC / DSAC object on the GPU: targets randomised apart, every policy's head with means within +-0.9 and log stds on both
-    sides of the clamp [-3, -0.5] (so |u| <= 0.9 + 3.3 * exp(-0.5) stays where fp32 resolves 1 + 1e-6 - tanh(u)^2), SAC's twin target
-    critics centred on each other.  act 4 (obs 6): eight head outputs."""
-    env = {3: "gym_pendulum", 4: "pyth_lq", 6: "pyth_idpendulum"}[obs]
-    lim = {1: ([-2.0], [2.0]), 2: ([-1.0, -0.5], [2.0, 0.5]), 4: LIM4}[act]
-    meta = dict(cfg=dict(alg=name, env_id=env, hidden=hidden, act=activation), lim=lim, seed=seed, min_log_std=-3.0, max_log_std=-0.5,
-                ctor=CTOR[name])
-    if obs == 4:
-        meta["cfg"]["lq_config"] = "s4a2"
-    torch.manual_seed(seed)
-    a = create_alg(**alg_kwargs(meta, True, **dict(dict(action_dim=act), **over)))
-    g = torch.Generator().manual_seed(seed + 1)
-    nets = a.networks
-    with torch.no_grad():
-        for n, p in nets.named_parameters():
-            if "_target." in n:
-                p.add_(0.3 * (torch.rand(p.shape, generator=g) - 0.5))
-        probe = torch.randn(256, obs, generator=g)
-        for pol in [nets.policy] + ([nets.policy_target] if name == "DSAC" else []):
-            head, y = pol.linear_layers()[-1], pol.policy(probe)
-            scale = torch.cat([0.9 / y[:, :act].abs().max(dim=0).values.clamp_min(0.9), 1.6 / y[:, act:].std(dim=0)])
-            head.weight.mul_(scale[:, None])
-            head.bias.mul_(scale)
-            head.bias[act:].sub_(pol.policy(probe)[:, act:].median(dim=0).values + 1.75)
-        if name == "SAC":
-            a2 = nets.policy.get_act_dist(nets.policy(probe)).mode()
-            nets.q2_target.linear_layers()[-1].bias[0].add_((nets.q1_target(probe, a2) - nets.q2_target(probe, a2)).median())
-    nets.cuda()
-    return a
+    """A SAC / DSAC object on the GPU: targets randomised apart, the heads of ac_helpers.shape_soft_heads.  act 4 (obs 6): eight head
+    outputs."""
+    meta = ac.synthetic_meta(name, obs, act, hidden, activation, seed, min_log_std=-3.0, max_log_std=-0.5, ctor=CTOR[name])
+    return ac.synthetic_alg(meta, obs, act, ac.shape_soft_heads, **over)
 
 
 def _data(B, obs, act, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    o = torch.randn(B, obs, generator=g)
-    d = (torch.rand(B, generator=g) < 0.2).float()
-    if B > 1:
-        d[0], d[-1] = 1.0, 0.0
-    return dict(obs=o, act=torch.rand(B, act, generator=g) * 2 - 1, rew=torch.randn(B, generator=g), obs2=o + 0.1 * torch.randn(B, obs, generator=g),
-                done=d, eps_new=torch.randn(B, act, generator=g), eps_next=torch.randn(B, act, generator=g).clamp(-3.3, 3.3),
-                z_next=2 * torch.randn(B, generator=g))
+    return ac.synthetic_batch(B, obs, act, seed, z_next=(B,))
 
 
 def _ref_backup(alg, data):
@@ -97,16 +62,7 @@ def _fused(alg, batch, want=("a2", "logp", "q_targ"), **kw):
 def _check_backup(alg, data, label):
     batch = alg._batch(data)
     ref = _ref_backup(alg, data)
-    comp = dict(zip(OUT, alg._backup_composed(batch)))
-    got, again = _fused(alg, batch), _fused(alg, batch)
-    for k in OUT:
-        want = ref[k].reshape(got[k].shape)
-        err_c = (comp[k].double().cpu() - want).abs().max().item()
-        err_f = (got[k].double().cpu() - want).abs().max().item()
-        bound = max(2 * err_c, 4 * EPS32 * want.abs().max().item())
-        print(f"{label} {k}: fused {err_f:.3e} composed {err_c:.3e} bound {bound:.3e}")
-        assert err_f <= bound, (label, k, err_f, err_c, bound)
-        assert torch.equal(got[k], again[k]), (label, k)
+    ac.check_backup(_fused(alg, batch), _fused(alg, batch), dict(zip(OUT, alg._backup_composed(batch))), ref, OUT, label)
     return ref, batch
 
 
@@ -209,16 +165,10 @@ def test_soft_q_backup_saturation(name):
 @pytest.mark.parametrize("name", ["SAC", "DSAC"])
 def test_optional_outputs_and_rows_beyond_the_batch(name):
     """Outputs padded with a sentinel: rows beyond the batch stay untouched; with the optional outputs NULL the backup keeps its bits."""
-    B, pad = 70, 64
+    B = 70
     alg = _alg(name, 4, 2, [64, 48], "tanh")
     batch = alg._batch(_data(B, 4, 2))
-    sizes = dict(backup=B, a2=2 * B, logp=B, q_targ=2 * B)
-    bufs = {k: torch.full((n + pad,), S, device="cuda") for k, n in sizes.items()}
-    shapes = dict(backup=(B,), a2=(B, 2), logp=(B,), q_targ=(B, 2) if name == "DSAC" else (2, B))
-    got = _fused(alg, batch, out={k: v[:sizes[k]].view(shapes[k]) for k, v in bufs.items()})
-    torch.cuda.synchronize()
-    for k, t in bufs.items():
-        assert (t[sizes[k]:] == S).all() and (t[:sizes[k]] != S).all(), k
+    got = ac.check_rows_beyond_the_batch(lambda out: _fused(alg, batch, out=out), dict(backup=B, a2=2 * B, logp=B, q_targ=2 * B))
     alone = _fused(alg, batch, want=())
     assert set(alone) == {"backup"} and torch.equal(alone["backup"], got["backup"])
 
@@ -317,93 +267,39 @@ def _loss_q(alg, tb):
 
 
 @pytest.mark.parametrize("fused", [True, False])
-@pytest.mark.parametrize("name", ONE_UPDATE)
+@pytest.mark.parametrize("name", SAC_ONE_UPDATE)
 def test_one_update_matches_the_reference(name, fused):
     alg, g, meta = load_alg(name, use_gpu=True, fused_target=fused)
-    names = Q_NAMES[meta["cfg"]["alg"]]
-    data = batch_of(g)
-    tb, info = alg.get_remote_update_info(data, 0)
-    assert alg.backup_path == ("fused" if fused else "composed")
-    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
-    tb_keys = [k for k in g if k.startswith("tb/")]
-    assert {k for k in tb if not k.startswith("Time/")} == {k[3:] for k in tb_keys}   # the reference's keys
-    for k in tb_keys:
-        assert close(tb[k[3:]], g[k]), (k, float(tb[k[3:]]), float(g[k]))
+    data, _, tb, info = ac.check_one_update(alg, g, meta, fused)
+    assert {k for k in tb if not k.startswith("Time/")} == {k[3:] for k in g if k.startswith("tb/")}   # the reference's keys
     assert close(_loss_q(alg, tb), g["loss_q"]) and close(tb["Loss/Actor loss-RL iter"], g["loss_pi"])
     batch = alg._batch(data)
     res = _fused(alg, batch) if fused else dict(zip(OUT, alg._backup_composed(batch)))
     for k, key in (("backup", "backup"), ("a2", "a2"), ("logp", "logp_next"), ("q_targ", "q_targ")):
         assert rel_l2(res[k].cpu(), g[key]) < TOL, k
-    assert set(info) == {f"{n}_grad" for n in names + ("policy",)} | {"iteration"} | ({"log_alpha_grad"} if alg.auto_alpha else set())
-    for n in names + ("policy",):
-        for i, gr in enumerate(info[f"{n}_grad"]):
-            assert rel_l2(gr.cpu(), g[f"{n}_grad/{i}"]) < TOL, (n, i, rel_l2(gr.cpu(), g[f"{n}_grad/{i}"]))
-    if alg.auto_alpha:
-        assert close(info["log_alpha_grad"], g["log_alpha_grad"])
-    before = {k: v.detach().clone() for k, v in alg.networks.state_dict().items()}
-    alg.remote_update(info)
-    after = alg.networks.state_dict()
-    assert all(torch.isfinite(p).all() for p in after.values())
-    assert all((after[k] - before[k]).abs().max() > 0 for k in before if "lim" not in k and (alg.auto_alpha or k != "log_alpha"))
+    ac.check_the_step_moves_everything(alg, info)
 
 
 @pytest.mark.parametrize("name", ["sac_pend_relu", "sac_lqs4a2_gelu", "dsac_pend_relu_bound", "dsac_lqs4a2_gelu_nobound"])
 def test_fused_and_composed_updates_agree(name):
-    out = {}
-    for fused in (True, False):
-        alg, g, meta = load_alg(name, use_gpu=True, fused_target=fused)
-        _, info = alg.get_remote_update_info(batch_of(g), 0)
-        out[fused] = {n: [t.clone() for t in v] for n, v in info.items() if n.endswith("_grad") and n != "log_alpha_grad"}
-    _check_backup(alg, batch_of(g), name)
-    for n in out[True]:
-        for a, b in zip(out[True][n], out[False][n]):
-            assert rel_l2(a.cpu(), b.cpu()) <= 1e-5, n
+    ac.check_fused_and_composed_agree(name, _check_backup)
 
 
-@pytest.mark.parametrize("name", FIVE_UPDATES)
+@pytest.mark.parametrize("name", SAC_FIVE_UPDATES)
 def test_five_updates_match_the_reference(name):
     """Five `local_update` calls with the reference's own draws handed in: every parameter and log_alpha after each call.  SAC steps
     everything every time; DSAC (delay_update = 2) keeps the bits of policy, log_alpha and both targets on iterations 1 and 3."""
-    alg, g, meta = load_alg(name, use_gpu=True, prefix="sd0/")
-    dsac = meta["cfg"]["alg"] == "DSAC"
-    assert alg.tau == 0.05 and (not dsac or alg.delay_update == 2)
-    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
-    delayed = lambda key: key == "log_alpha" or key.startswith("policy.") or "_target." in key   # noqa: E731
-    for k in range(5):
-        before = {key: v.detach().clone() for key, v in alg.networks.state_dict().items()}
-        tb = alg.local_update(batch_of(g, f"in{k}/"), k)
-        assert close(tb["Loss/Actor loss-RL iter"], g[f"loss_pi{k}"]), k
-        if not dsac:
-            assert close(tb["Loss/Critic loss-RL iter"], g[f"loss_q{k}"]), k
+    dsac = name.startswith("dsac")
+    for alg, g, k, before in ac.five_updates(name, critic_loss=not dsac):   # (the reference's DSAC reports no critic loss)
+        assert type(alg).__name__ == ("DSAC" if dsac else "SAC") and alg.tau == 0.05 and (not dsac or alg.delay_update == 2)
         for key, p in alg.networks.state_dict().items():
-            assert rel_l2(p.cpu().double(), g[f"sd{k + 1}/{key}"]) < TOL, (k, key)
             if "lim" not in key:
-                assert torch.equal(p, before[key]) == (dsac and delayed(key) and k % 2 == 1), (k, key)
+                assert torch.equal(p, before[key]) == (dsac and ac.delayed(key) and k % 2 == 1), (k, key)
 
 
 @pytest.mark.parametrize("name", ["SAC", "DSAC"])
 def test_graph_replay_equals_eager(name, monkeypatch):
-    B = 70
-
-    def run(mode):
-        monkeypatch.setenv("GOPS_HIP_GRAPH", mode)
-        alg = _alg(name, 3, 1, [32, 16], "relu", seed=4)
-        logs = []
-        for it in range(14):
-            data = {k: v for k, v in _data(B, 3, 1, seed=100 + it).items() if not k.startswith(("eps_", "z_"))}   # the algorithm's own draws
-            logs.append(dict(alg.local_update(data, it)))
-        return alg, logs
-
-    eager, log_e = run("0")
-    graph, log_g = run("1")
-    assert all(c.graph is not None for c in graph._graphs.values()) and len(graph._graphs) == (1 if name == "SAC" else 2)
-    assert all(c.graph is None for c in eager._graphs.values())
-    for (ne, pe), (ng, pg) in zip(eager.networks.named_parameters(), graph.networks.named_parameters()):
-        assert ne == ng and torch.equal(pe, pg), ne
-    for a, b in zip(log_e, log_g):
-        for k in a:
-            if not k.startswith("Time/"):
-                assert float(a[k]) == float(b[k]), k
+    ac.check_graph_replay(lambda: _alg(name, 3, 1, [32, 16], "relu", seed=4), 1 if name == "SAC" else 2, monkeypatch)
 
 
 @pytest.mark.parametrize("name", ["SAC", "DSAC"])
@@ -421,33 +317,20 @@ def test_default_backup_path_and_shape_refusals(name):
 def test_end_to_end(name, tmp_path):
     """OffSerialTrainer + replay_buffer + DeviceEnvSampler (the stochastic policy's own samples) on gym_pendulum: finite losses,
     every online network moved, the targets lag behind."""
-    from gops_amd.create_pkg.create_buffer import create_buffer
-    from gops_amd.create_pkg.create_env_model import create_env_model
-    from gops_amd.create_pkg.create_trainer import create_trainer
     from gops_amd.trainer.sampler.device_env_sampler import DeviceEnvSampler
-    torch.manual_seed(0)
-    kw = dict(algorithm=name, trainer="off_serial_trainer", seed=0, cnn_shared=False, env_id="gym_pendulum", obsv_dim=3, action_dim=1,
-              action_type="continu", action_low_limit=-2 * np.ones(1, dtype=np.float32), action_high_limit=2 * np.ones(1, dtype=np.float32),
-              policy_func_type="MLP", policy_func_name="StochaPolicy", policy_hidden_sizes=[64, 64], policy_hidden_activation="relu",
-              policy_act_distribution="TanhGaussDistribution", policy_learning_rate=1e-3, policy_min_log_std=-20, policy_max_log_std=0.5,
-              value_func_type="MLP", value_func_name="ActionValue" if name == "SAC" else "ActionValueDistri", value_hidden_sizes=[64, 64],
-              value_hidden_activation="relu", value_learning_rate=1e-3, q_learning_rate=1e-3, alpha_learning_rate=3e-4, gamma=0.99,
-              tau=0.005, auto_alpha=True, bound=True, delay_update=2, use_gpu=True,
-              buffer_name="replay_buffer", buffer_max_size=4096, buffer_warm_size=512, replay_batch_size=64,
-              sample_interval=1, additional_info={}, max_iteration=8, log_save_interval=1000, apprfunc_save_interval=1000,
-              eval_interval=10 ** 9, save_folder=str(tmp_path), ini_network_dir=None)
-    alg = create_alg(**kw)
-    alg.networks.to("cuda")
-    start = {k: v.detach().clone() for k, v in alg.networks.state_dict().items()}
-    model = create_env_model(**kw)
-    smp = DeviceEnvSampler(dict(env_id="gym_pendulum"), model, n_envs=128, steps_per_sample=2, max_episode_steps=50, seed=3,
-                           env_step="model")   # (gym_pendulum's data environment is not restated in the step kernel)
-    smp.networks = alg.networks
-    trainer = create_trainer(alg, smp, create_buffer(**kw), None, **kw)
-    for _ in range(6):
-        trainer.step()
-        trainer.iteration += 1
-    assert alg.backup_path == "fused"
+    start = {}
+
+    def sampler(model, alg):
+        start.update({k: v.detach().clone() for k, v in alg.networks.state_dict().items()})
+        smp = DeviceEnvSampler(dict(env_id="gym_pendulum"), model, n_envs=128, steps_per_sample=2, max_episode_steps=50, seed=3,
+                               env_step="model")   # (gym_pendulum's data environment is not restated in the step kernel)
+        smp.networks = alg.networks
+        return smp
+
+    kw = ac.trainer_kwargs(name, "gym_pendulum", 3, 2.0, tmp_path, policy_min_log_std=-20, policy_max_log_std=0.5, gamma=0.99, tau=0.005,
+                           auto_alpha=True, bound=True, delay_update=2)
+    alg, _, _, trainer = ac.build_trainer(kw, sampler, False)
+    ac.run_trainer(trainer, alg)
     assert all(np.isfinite(float(v)) for v in alg.tb_info.values())
     nets = alg.networks.state_dict()
     assert all(torch.isfinite(p).all() for p in nets.values())

@@ -1,16 +1,14 @@
 """DDPG / TD3 without a GPU: construction and RNG order, the reference's surface, refusals, registries, the C ABI of the new
 entry points, and the update restated on the host against every fixture of tests/golden/make_golden_td3.py."""
-import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from ac_helpers import REFUSALS, TD3_ONE_UPDATE, TOL, alg_kwargs, check_abi, check_host_restatement, check_refusals, close, q_names
 from conftest import ROOT, golden_meta, load_golden, rel_l2
-from td3_helpers import ONE_UPDATE, TOL, alg_kwargs, batch_of, load_alg, q_names_of, restate_update
 
 from gops_amd.create_pkg import create_alg as ca
 from gops_amd.create_pkg.create_alg import create_alg, create_approx_contrainer
@@ -34,7 +32,8 @@ def test_construction_follows_the_reference(name):
     sd = alg.networks.state_dict()
     assert [n for n, _ in alg.networks.named_children()] == (TD3_KEYS if meta["cfg"]["alg"] == "TD3" else DDPG_KEYS)
     assert list(sd) == [k[3:] for k in g if k.startswith("sd/")]
-    for n in q_names_of(meta["cfg"]["alg"]) + ("policy",):
+    assert q_names(alg) == (("q1", "q2") if meta["cfg"]["alg"] == "TD3" else ("q",))
+    for n in q_names(alg) + ("policy",):
         for k, v in getattr(alg.networks, n).state_dict().items():
             assert np.array_equal(v.numpy(), g[f"sd/{n}.{k}"]), (n, k)
             assert torch.equal(v, getattr(alg.networks, f"{n}_target").state_dict()[k])
@@ -65,20 +64,10 @@ def test_surface_follows_the_reference():
 
 @pytest.mark.parametrize("alg", ["DDPG", "TD3"])
 def test_refusals_carry_a_reason(alg):
-    kw = alg_kwargs(golden_meta(load_golden("td3_pend_relu")), False, algorithm=alg)
-    cases = [(dict(policy_func_type="POLY", policy_degree=1, policy_add_bias=False), "POLY"),
-             (dict(value_func_type="POLY", value_degree=2, value_add_bias=False), "POLY"),
-             (dict(policy_func_type="LipsNet"), "LipsNet"),
-             (dict(mlp_dtype="fp16"), "fp32 only"),
-             (dict(policy_func_name="StochaPolicy"), "deterministic policy"),
-             (dict(value_func_name="StateValue"), "action-value"),
-             (dict(value_output_activation="tanh"), "linear output"),
-             (dict(policy_output_activation="relu"), "linear output"),
-             (dict(trainer="off_sync_trainer"), "off_serial"),
-             (dict(trainer="off_async_trainer"), "off_serial")]
-    for over, reason in cases:
-        with pytest.raises(NotImplementedError, match=reason):
-            create_alg(**dict(kw, **over))
+    meta = golden_meta(load_golden("td3_pend_relu"))
+    check_refusals(lambda **over: alg_kwargs(meta, False, **dict(dict(algorithm=alg), **over)),
+                   REFUSALS + [(dict(policy_func_name="StochaPolicy"), "deterministic policy"),
+                               (dict(value_func_name="StateValue"), "action-value")])
 
 
 def test_registries():
@@ -97,26 +86,14 @@ def test_registries():
         create_alg(**alg_kwargs(meta, False, algorithm="SAC"))
 
 
-@pytest.mark.parametrize("name", ONE_UPDATE)
+@pytest.mark.parametrize("name", TD3_ONE_UPDATE)
 def test_host_restatement_matches_the_reference(name, capsys):
     """The fixture's state dict loaded into the networks create_alg built, one update restated on the host in fp32 (autograd over
     the modules' own `forward`): backup, losses and every gradient against the reference's, rel-L2 <= 1e-4.  This is the TEST's
-    restatement (td3_helpers.restate_update, the oracle of the GPU tests at float64): it shows that the modules are the reference's
+    restatement (ac_helpers.restate_td3, the oracle of the GPU tests at float64): it shows that the modules are the reference's
     and that the oracle is faithful; the algorithm's own update has no host path and is held to the fixtures in test_td3_gpu.py."""
-    alg, g, meta = load_alg(name)
-    got = restate_update(alg, batch_of(g), dtype=torch.float32)
-    names = q_names_of(meta["cfg"]["alg"])
-    worst = 0.0
-    for key in ("backup", "a2", "q_targ"):
-        worst = max(worst, rel_l2(got[key], g[key]))
-    for n in names + ("policy",):
-        for i, gr in enumerate(got["grads"][n]):
-            worst = max(worst, rel_l2(gr, g[f"{n}_grad/{i}"]))
-    with capsys.disabled():
-        print(f"\n{name}: worst rel-L2 of backup / a2 / q_targ / gradients against the reference {worst:.2e}")
-    assert worst <= TOL
-    close = lambda a, b: abs(float(a) - float(b)) <= TOL * max(1.0, abs(float(b)))   # noqa: E731
-    for n, l in zip(names, got["loss_q"]):
+    alg, g, meta, got = check_host_restatement(name, ("backup", "a2", "q_targ"), "backup / a2 / q_targ", capsys)
+    for n, l in zip(q_names(alg), got["loss_q"]):
         assert close(l, g[f"loss_{n}"]), n
     assert close(got["loss"], g["tb/Loss/Critic loss-RL iter"]) and close(got["loss_pi"], g["tb/Loss/Actor loss-RL iter"])
     logged = got["loss"] if meta["cfg"]["alg"] == "TD3" else got["q_mean"]   # td3.py:153 logs the mean of the scalar loss
@@ -128,20 +105,8 @@ def test_host_restatement_matches_the_reference(name, capsys):
 def test_abi_of_the_actor_critic_entry_points(tmp_path):
     """Declared in the header (plain C99), mirrored by ctypes field for field, exported by the library; the version stays 15."""
     from gops_amd import hip_backend as hb
-    header = open(os.path.join(ROOT, "include", "gops_hip.h")).read()
-    assert "#define GOPS_HIP_ABI_VERSION 15" in header
-    for name in ("gops_ac_backup_workspace_bytes", "gops_ac_backup", "gops_ac_critic_loss"):
-        assert re.search(rf"\b{name}\s*\(", header) and name in hb.EXPORTED_SYMBOLS
-        assert hasattr(ctypes.CDLL(hb.LIB_PATH), name)
-    assert int(re.search(r"#define GOPS_AC_LOSS_STATS_FLOATS (\d+)", header).group(1)) == hb.AC_LOSS_STATS_FLOATS
-    fields = [f[0] for f in hb.GopsAcBackup._fields_]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gops_hip.h"\nint main(void) {\n'
-                   '    printf("%zu", sizeof(GopsAcBackup));\n'
-                   + "".join(f'    printf(" %zu", offsetof(GopsAcBackup, {f}));\n' for f in fields) + "    return 0;\n}\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(hb.GopsAcBackup)] + [getattr(hb.GopsAcBackup, f).offset for f in fields]
+    check_abi(tmp_path, [("GopsAcBackup", hb.GopsAcBackup)], ("gops_ac_backup_workspace_bytes", "gops_ac_backup", "gops_ac_critic_loss"),
+              [("GOPS_AC_LOSS_STATS_FLOATS", hb.AC_LOSS_STATS_FLOATS)])
     assert "actor_critic.hip" in open(os.path.join(ROOT, "gops_amd", "csrc", "Makefile")).read()
 
 
