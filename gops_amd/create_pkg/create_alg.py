@@ -35,15 +35,20 @@ soft_registry = Registry("algorithm")
 # file stays as it is.  `create_alg` and `create_approx_contrainer` look in all four; `soft_q_registry` folds back with the others.
 _SOFT_Q_ALGORITHMS = ("sac", "dsac")
 soft_q_registry = Registry("algorithm")
-_ELSEWHERE = _LOOP_ALGORITHMS + _SOFT_ALGORITHMS + _SOFT_Q_ALGORITHMS
+# PPO likewise: the key set of `soft_q_registry` is pinned by tests/test_sac_cpu.py (as it stood before PPO), and that test file stays
+# as it is.  `create_alg` and `create_approx_contrainer` look in all five; `on_policy_registry` folds back with the others.
+_ON_POLICY_ALGORITHMS = ("ppo",)
+on_policy_registry = Registry("algorithm")
+_ELSEWHERE = _LOOP_ALGORITHMS + _SOFT_ALGORITHMS + _SOFT_Q_ALGORITHMS + _ON_POLICY_ALGORITHMS
 registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem not in _ELSEWHERE)
 loop_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _LOOP_ALGORITHMS)
 soft_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _SOFT_ALGORITHMS)
 soft_q_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _SOFT_Q_ALGORITHMS)
+on_policy_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _ON_POLICY_ALGORITHMS)
 
 
 def _registry_of(algorithm: str) -> Registry:
-    return next((r for r in (loop_registry, soft_registry, soft_q_registry) if algorithm in r), registry)
+    return next((r for r in (loop_registry, soft_registry, soft_q_registry, on_policy_registry) if algorithm in r), registry)
 
 
 def _defaults(kwargs: dict) -> dict:
@@ -88,7 +93,7 @@ class LocalActor:
 def create_alg(**kwargs) -> object:
     reg = _registry_of(kwargs["algorithm"])
     entry = reg.lookup(kwargs["algorithm"])       # unknown algorithm: KeyError before anything else
-    if reg is soft_q_registry:   # the arguments the reference's SAC / DSAC read with kwargs[...]: its KeyError, before any refusal
+    if reg in (soft_q_registry, on_policy_registry):   # the arguments the reference's SAC / DSAC / PPO read with kwargs[...]: its KeyError, before any refusal
         for name in inspect.getmodule(entry.entry_point).MANDATORY:
             if name not in kwargs:
                 raise KeyError(name)
@@ -119,7 +124,7 @@ def create_alg(**kwargs) -> object:
         reason = refusal(kwargs)
         if reason is not None:
             raise NotImplementedError(reason)
-    if reg is soft_q_registry:
+    if reg in (soft_q_registry, on_policy_registry):
         reason = inspect.getmodule(entry.entry_point).refusal(kwargs)
         if reason is not None:
             raise NotImplementedError(reason)

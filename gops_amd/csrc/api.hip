@@ -1145,6 +1145,30 @@ int gops_tanh_gauss_backward(const GopsTanhGauss* desc, int32_t batch, const flo
     return tanh_gauss_backward(*desc, batch, head, eps, g_act, g_logp, g_head, static_cast<hipStream_t>(stream));
 }
 
+int gops_ppo_loss(const GopsPpoLoss* desc, int32_t batch, const float* head_new, const float* v_new, const float* act, const float* logp_old,
+                  const float* adv, const float* ret, const float* val_old, const float* logits_old, const float* hyper, float* seed_head,
+                  float* seed_v, float* stats, void* stream) {
+    if (!desc || batch < 1 || desc->act_dim < 1 || desc->act_dim > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (!head_new || !v_new || !act || !logp_old || !adv || !ret || !val_old || !logits_old || !hyper || !seed_head || !seed_v || !stats)
+        return GOPS_ERR_BAD_ARG;
+    if (desc->loss_value_norm && batch < 2) return GOPS_ERR_BAD_ARG;       // the unbiased std of one return does not exist
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the norm and the partial sums behind the results are doubles
+    return ppo_loss(*desc, batch, head_new, v_new, act, logp_old, adv, ret, val_old, logits_old, hyper, seed_head, seed_v, stats,
+                    static_cast<hipStream_t>(stream));
+}
+
+int gops_adv_normalize(const float* adv, int32_t n, double eps, float* out, float* stats, void* stream) {
+    if (!adv || !out || !stats || n < 2) return GOPS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;
+    return adv_normalize(adv, n, eps, out, stats, static_cast<hipStream_t>(stream));
+}
+
+int gops_gae(const float* rew, const float* val, const float* val_next, const float* done, const float* end, int32_t steps, int32_t n_envs,
+             double gamma, double gae_lambda, float* ret, float* adv, void* stream) {
+    if (!rew || !val || !val_next || !done || !end || !ret || !adv || steps < 1 || n_envs < 1) return GOPS_ERR_BAD_ARG;
+    return gae(rew, val, val_next, done, end, steps, n_envs, gamma, gae_lambda, ret, adv, static_cast<hipStream_t>(stream));
+}
+
 void gops_profile_enable(int32_t on) {
     std::lock_guard<std::mutex> lk(g_prof.mu);
     g_prof.on = on != 0;

@@ -77,3 +77,11 @@ int tanh_gauss_forward(const GopsTanhGauss& d, int B, const float* head, const f
                        float* stats, hipStream_t s);
 int tanh_gauss_backward(const GopsTanhGauss& d, int B, const float* head, const float* eps, const float* g_act, const float* g_logp,
                         float* g_head, hipStream_t s);
+
+// ---- ppo.hip: PPO's losses with their seeds, the advantage normalisation, GAE over all environments ----
+int ppo_loss(const GopsPpoLoss& d, int M, const float* head_new, const float* v_new, const float* act, const float* logp_old, const float* adv,
+             const float* ret, const float* val_old, const float* logits_old, const float* hyper, float* seed_head, float* seed_v, float* stats,
+             hipStream_t s);
+int adv_normalize(const float* adv, int n, double eps, float* out, float* stats, hipStream_t s);
+int gae(const float* rew, const float* val, const float* val_next, const float* done, const float* end, int T, int N, double gamma,
+        double lambda, float* ret, float* adv, hipStream_t s);

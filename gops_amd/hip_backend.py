@@ -174,6 +174,11 @@ class GopsTanhGauss(C.Structure):   # gops_tanh_gauss_forward / _backward
                 ("min_log_std", C.c_double), ("max_log_std", C.c_double)]
 
 
+class GopsPpoLoss(C.Structure):   # gops_ppo_loss
+    _fields_ = [("act_dim", C.c_int32), ("loss_value_clip", C.c_int32), ("loss_value_norm", C.c_int32), ("reserved", C.c_int32),
+                ("min_log_std", C.c_double), ("max_log_std", C.c_double)]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every symbol of include/gops_hip.h (argtypes None: not declared to ctypes)."""
     P, vp, i32, sz, f64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_size_t, C.c_double, C.c_int
@@ -231,6 +236,9 @@ def _signatures():
         "gops_soft_q_backup_workspace_bytes": (sz, [P(GopsSoftQBackup), i32]),
         "gops_soft_q_backup": (rc, [P(GopsSoftQBackup), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gops_dsac_critic_loss": (rc, [vp, vp, i32, i32, vp, vp, vp]),
+        "gops_ppo_loss": (rc, [P(GopsPpoLoss), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gops_adv_normalize": (rc, [vp, i32, f64, vp, vp, vp]),
+        "gops_gae": (rc, [vp, vp, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -1490,6 +1498,72 @@ class TanhGaussHead:
         check(lib().gops_tanh_gauss_backward(C.byref(self.desc), B, _ptr(head), _ptr(eps), _ptr(g_act), _ptr(g_logp), _ptr(g_head),
                                              _stream()), "gops_tanh_gauss_backward")
         return g_head
+
+
+PPO_STATS_FLOATS = 656   # include/gops_hip.h: GOPS_PPO_STATS_FLOATS
+PPO_HYPER_FLOATS = 8     # include/gops_hip.h: GOPS_PPO_HYPER_FLOATS
+ADV_STATS_FLOATS = 264   # include/gops_hip.h: GOPS_ADV_STATS_FLOATS
+
+
+class PpoLoss:
+    """PPO's losses and their gradient seeds for one minibatch in one launch (`gops_ppo_loss`, csrc/ppo.hip).  `buf[:6]` = loss_total,
+    loss_surrogate, loss_value, mean entropy, mean kl, clip fraction; the rest is the kernel's scratch (zero before the first call,
+    ticket left zero).  `hyper` (device): clip, value_clip, c_kl, c_v, c_ent - the kernel reads them there, so `set_hyper` between
+    two replays of a captured graph takes effect."""
+
+    def __init__(self, act_dim: int, min_log_std: float, max_log_std: float, device, loss_value_clip=True, loss_value_norm=False):
+        d = self.desc = GopsPpoLoss()
+        d.act_dim = self.act_dim = int(act_dim)
+        d.loss_value_clip, d.loss_value_norm = int(bool(loss_value_clip)), int(bool(loss_value_norm))
+        d.min_log_std, d.max_log_std = float(min_log_std), float(max_log_std)
+        self.buf = torch.zeros(PPO_STATS_FLOATS, dtype=torch.float32, device=device)
+        self.hyper = torch.zeros(PPO_HYPER_FLOATS, dtype=torch.float32, device=device)
+        self._hyper = None
+
+    def set_hyper(self, clip: float, value_clip: float, c_kl: float, c_v: float, c_ent: float):
+        vals = (float(clip), float(value_clip), float(c_kl), float(c_v), float(c_ent))
+        if vals != self._hyper:   # (a host-to-device copy: never inside a capture - graph owners call this before the replay)
+            self.hyper[:5].copy_(torch.tensor(vals, dtype=torch.float32))
+            self._hyper = vals
+
+    def run(self, head_new, v_new, act, logp_old, adv, ret, val_old, logits_old, seed_head=None, seed_v=None):
+        """head_new [M, 2A] raw, v_new [M] -> (seed_head [M, 2A], seed_v [M], stats [6])."""
+        M, A = head_new.shape[0], self.act_dim
+        assert tuple(head_new.shape) == (M, 2 * A) and tuple(logits_old.shape) == (M, 2 * A) and act.numel() == M * A
+        assert all(t.numel() == M for t in (v_new, logp_old, adv, ret, val_old))
+        seed_head = torch.empty_like(head_new) if seed_head is None else seed_head
+        seed_v = torch.empty(M, dtype=torch.float32, device=head_new.device) if seed_v is None else seed_v
+        assert seed_head.numel() == 2 * M * A and seed_v.numel() == M
+        check(lib().gops_ppo_loss(C.byref(self.desc), M, _ptr(head_new), _ptr(v_new), _ptr(act), _ptr(logp_old), _ptr(adv), _ptr(ret),
+                                  _ptr(val_old), _ptr(logits_old), self.hyper.data_ptr(), _ptr(seed_head), _ptr(seed_v),
+                                  self.buf.data_ptr(), _stream()), "gops_ppo_loss")
+        return seed_head, seed_v, self.buf[:6]
+
+
+class AdvNormalize:
+    """`(adv - mean) / (std + eps)` with the unbiased std in one launch (`gops_adv_normalize`); `buf[:2]` = mean, std."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(ADV_STATS_FLOATS, dtype=torch.float32, device=device)
+
+    def run(self, adv: torch.Tensor, eps: float = 1e-8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        out = torch.empty_like(adv) if out is None else out
+        assert out.numel() == adv.numel()
+        check(lib().gops_adv_normalize(_ptr(adv), adv.numel(), float(eps), _ptr(out), self.buf.data_ptr(), _stream()), "gops_adv_normalize")
+        return out
+
+
+def gae(rew, val, val_next, done, end, gamma: float = 0.99, gae_lambda: float = 0.95, ret=None, adv=None):
+    """Value targets and generalised advantages of all environments in one launch (`gops_gae`): time-major [T, N] fp32 tensors ->
+    (ret, adv) [T, N]."""
+    T, N = rew.shape
+    assert all(tuple(t.shape) == (T, N) for t in (val, val_next, done, end))
+    ret = torch.empty_like(rew) if ret is None else ret
+    adv = torch.empty_like(rew) if adv is None else adv
+    assert ret.numel() == T * N and adv.numel() == T * N
+    check(lib().gops_gae(_ptr(rew), _ptr(val), _ptr(val_next), _ptr(done), _ptr(end), T, N, float(gamma), float(gae_lambda), _ptr(ret),
+                         _ptr(adv), _stream()), "gops_gae")
+    return ret, adv
 
 
 def make_update_tail(fused_adam=None, mean_of: Optional[torch.Tensor] = None, mean_scale: float = -1.0,

@@ -84,6 +84,38 @@ class DeviceEnvSampler:
         return self._henv
 
     # ---- sampling -----------------------------------------------------------------------------
+    def _step_once(self, policy, zeros):
+        """Advance all N environments one step; -> (the step's row of replay-format columns, the mask of the instances whose episode
+        this step ended - terminated or timed out - and that restart from a fresh reset state)."""
+        obs, info = self.obs, self.info
+        act, logp = policy(obs), zeros
+        if isinstance(policy, StochaPolicy):   # the policy's own distribution explores; its log-probability is stored
+            act, logp = policy.get_act_dist(act).sample(generator=self._gen)
+            if self.noise_std > 0.0 and not self._warned_noise:
+                self._warned_noise = True
+                warnings.warn("DeviceEnvSampler: noise_std is ignored with a stochastic policy (it samples its own distribution)")
+        elif self.noise_std > 0.0:
+            act = act + self.noise_std * torch.randn(act.shape, generator=self._gen, device=self.device)
+        obs2, rew, done, info2 = hb.env_step(self._hip_env(), obs, act.contiguous(), zeros, info)
+        row = dict(obs=obs, act=act, rew=rew, done=done, obs2=obs2, logp=logp)
+        for k in info:
+            row[k], row["next_" + k] = info[k], info2[k]
+        # episode bookkeeping: terminated or timed-out instances restart from a fresh reset state
+        self.t += 1
+        over = (done != 0) | (self.t >= self.max_steps)
+        n_over = int(over.sum().item())
+        # (pyth_mobilerobot's info["constraint"] is a zero-size replay slot in the reference, pyth_mobilerobot.py:86-92:
+        # the step's constraint output is not a stored column)
+        self.obs, self.info = obs2, {k: info2[k] for k in info}
+        if n_over:
+            fresh = self._draw(n_over)
+            idx = over.nonzero(as_tuple=True)[0]
+            self.obs = self.obs.index_copy(0, idx, fresh["obs"])
+            for k in self.info:
+                self.info[k] = self.info[k].index_copy(0, idx, fresh[k])
+            self.t.index_fill_(0, idx, 0)
+        return row, over
+
     @torch.no_grad()
     def sample(self):
         """Advance all N environments `steps_per_sample` steps; returns (dict of [N*steps, ...] device
@@ -91,36 +123,7 @@ class DeviceEnvSampler:
         t0 = time.time()
         policy = self.networks.policy
         zeros = torch.zeros(self.n, device=self.device)
-        chunks = []
-        for _ in range(self.steps):
-            obs, info = self.obs, self.info
-            act, logp = policy(obs), zeros
-            if isinstance(policy, StochaPolicy):   # the policy's own distribution explores; its log-probability is stored
-                act, logp = policy.get_act_dist(act).sample(generator=self._gen)
-                if self.noise_std > 0.0 and not self._warned_noise:
-                    self._warned_noise = True
-                    warnings.warn("DeviceEnvSampler: noise_std is ignored with a stochastic policy (it samples its own distribution)")
-            elif self.noise_std > 0.0:
-                act = act + self.noise_std * torch.randn(act.shape, generator=self._gen, device=self.device)
-            obs2, rew, done, info2 = hb.env_step(self._hip_env(), obs, act.contiguous(), zeros, info)
-            row = dict(obs=obs, act=act, rew=rew, done=done, obs2=obs2, logp=logp)
-            for k in info:
-                row[k], row["next_" + k] = info[k], info2[k]
-            chunks.append(row)
-            # episode bookkeeping: terminated or timed-out instances restart from a fresh reset state
-            self.t += 1
-            over = (done != 0) | (self.t >= self.max_steps)
-            n_over = int(over.sum().item())
-            # (pyth_mobilerobot's info["constraint"] is a zero-size replay slot in the reference, pyth_mobilerobot.py:86-92:
-            # the step's constraint output is not a stored column)
-            self.obs, self.info = obs2, {k: info2[k] for k in info}
-            if n_over:
-                fresh = self._draw(n_over)
-                idx = over.nonzero(as_tuple=True)[0]
-                self.obs = self.obs.index_copy(0, idx, fresh["obs"])
-                for k in self.info:
-                    self.info[k] = self.info[k].index_copy(0, idx, fresh[k])
-                self.t.index_fill_(0, idx, 0)
+        chunks = [self._step_once(policy, zeros)[0] for _ in range(self.steps)]
         batch = {k: torch.cat([c[k] for c in chunks]) for k in chunks[0]} if len(chunks) > 1 else chunks[0]
         self.total += self.n * self.steps
         return batch, {tb_tags["sampler_time"]: (time.time() - t0) * 1000}

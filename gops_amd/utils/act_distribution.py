@@ -45,6 +45,11 @@ class GaussDistribution:
     def entropy(self):
         return (0.5 + 0.5 * math.log(2 * math.pi) + torch.log(self.std)).sum(-1)
 
+    def kl_divergence(self, other: "GaussDistribution") -> torch.Tensor:
+        """KL(self || other) of the two diagonal Gaussians, summed over the action dimensions (act_distribution_type.py:110-113)."""
+        ratio2 = (self.std / other.std) ** 2
+        return (0.5 * (ratio2 + ((self.mean - other.mean) / other.std) ** 2 - 1 - torch.log(ratio2))).sum(-1)
+
     def mode(self):
         return torch.clamp(self.mean, self.act_low_lim, self.act_high_lim)
 

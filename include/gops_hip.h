@@ -795,6 +795,59 @@ int gops_soft_q_backup(const GopsSoftQBackup* desc, int32_t batch, const float* 
 int gops_dsac_critic_loss(const float* qraw, const float* target_q, int32_t batch, int32_t bound, float* seed, float* stats,
                           void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): PPO (gops/algorithm/ppo.py, gops/trainer/sampler/on_sampler.py;
+ * csrc/ppo.hip).  fp32 in and out, arithmetic in double, one rounding per stored value, sums in the fixed order of the batch size.
+ *
+ * gops_ppo_loss: the losses of ppo.py:167-240 and their gradient seeds for one minibatch of `batch` = M rows, A = act_dim.
+ *   head_new [M, 2A]: the ONLINE StochaPolicy's RAW stack output (mean, log_std); ls = clamp(log_std, min_log_std, max_log_std),
+ *   std = exp(ls) are formed here.  v_new [M], act [M, A], logp_old [M], adv [M], ret [M], val_old [M];
+ *   logits_old [M, 2A] = (mean_old, std_old) as policy(obs) returned them before the update.
+ *   hyper (device, 5 floats): clip, value_clip, c_kl, c_v, c_ent - read by the kernel, so a schedule may change them under a graph.
+ *     logp_new = sum_a (-(act - mean)^2 / (2 std^2) - ls - log sqrt(2 pi));   ratio = exp(logp_new - logp_old)
+ *     sur      = min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv)
+ *     l1 = (v_new - ret)^2;  vc = val_old + clamp(v_new - val_old, -value_clip, value_clip);  l2 = (vc - ret)^2
+ *     value_loss = loss_value_clip ? max(l1, l2) : l1
+ *     entropy  = sum_a (0.5 + log sqrt(2 pi) + ls)
+ *     kl       = sum_a (ls - log std_old + (std_old^2 + (mean_old - mean)^2) / (2 std^2) - 0.5)          KL(N(old) || N(new))
+ *     loss_surrogate = -mean(sur);  loss_value = mean(value_loss), divided by 6 std(ret) (unbiased, over the M rows) iff loss_value_norm
+ *     loss_total = loss_surrogate + c_kl mean(kl) + c_v loss_value - c_ent mean(entropy)
+ *   seed_head [M, 2A] = d loss_total / d head_new (the log_std column through the exp; exactly 0 where log_std lies outside the clamp),
+ *   seed_v [M] = d loss_total / d v_new, under torch's tie rules:
+ *     surrogate: -(1/M) adv ratio d logp_new where ratio adv <= clamp(ratio) adv, else 0 (inside the clip both are the same number and
+ *       clamp passes its gradient on the closed interval, so min's half-and-half split adds up to the whole);
+ *     value: (2 c_v / M)(v_new - ret) / norm where l1 >= l2 or |v_new - val_old| <= value_clip, else 0.
+ *   stats[0 .. 5] = loss_total, loss_surrogate, loss_value, mean(entropy), mean(kl), mean(|ratio - 1| > clip); behind them 6 std(ret),
+ *   the blocks' partial sums and a ticket: GOPS_PPO_STATS_FLOATS floats, 8-byte aligned, ALL ZERO before the first call; the call leaves
+ *   the ticket zero.  loss_value_norm: up to 8192 rows one workgroup in ONE launch, larger minibatches TWO launches of 64 workgroups
+ *   (moments of ret, then seeds and sums); without it one launch at every size.
+ *   GOPS_ERR_BAD_ARG: a NULL pointer, batch < 1, act_dim outside 1 .. GOPS_MAX_ACT, a misaligned `stats`, batch < 2 with loss_value_norm. */
+struct GopsPpoLoss {
+    int32_t act_dim;
+    int32_t loss_value_clip;
+    int32_t loss_value_norm;
+    int32_t reserved;
+    double min_log_std, max_log_std;
+};
+typedef struct GopsPpoLoss GopsPpoLoss;
+#define GOPS_PPO_STATS_FLOATS 656
+#define GOPS_PPO_HYPER_FLOATS 8
+int gops_ppo_loss(const GopsPpoLoss* desc, int32_t batch, const float* head_new, const float* v_new, const float* act, const float* logp_old,
+                  const float* adv, const float* ret, const float* val_old, const float* logits_old, const float* hyper, float* seed_head,
+                  float* seed_v, float* stats, void* stream);
+/* gops_adv_normalize: out[i] = (adv[i] - mean(adv)) / (std(adv) + eps), std unbiased (ppo.py:123-125); `out` may be `adv`.
+ * stats[0] = mean, [1] = std; GOPS_ADV_STATS_FLOATS floats, 8-byte aligned, all zero before the first call.  One launch up to 8192
+ * elements, two launches of 64 workgroups beyond.  GOPS_ERR_BAD_ARG: a NULL pointer, n < 2, a misaligned `stats`. */
+#define GOPS_ADV_STATS_FLOATS 264
+int gops_adv_normalize(const float* adv, int32_t n, double eps, float* out, float* stats, void* stream);
+/* gops_gae: value targets and generalised advantages (on_sampler.py:168-187) of n_envs environments over `steps` = T steps, arrays
+ * time-major [T, n_envs]; one lane per environment walks backwards:
+ *     at a step with end != 0 (the last of a segment: terminated, timed out) and at t = T - 1:
+ *         next_v = val_next (1 - done), the carried gae restarts at 0;     elsewhere next_v = val[t + 1]
+ *     delta = rew + gamma next_v - val;   gae = delta + gamma gae_lambda gae;   ret = gae + val;   adv = gae
+ * in double, stored as float.  GOPS_ERR_BAD_ARG: a NULL pointer, steps < 1, n_envs < 1. */
+int gops_gae(const float* rew, const float* val, const float* val_next, const float* done, const float* end, int32_t steps, int32_t n_envs,
+             double gamma, double gae_lambda, float* ret, float* adv, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
