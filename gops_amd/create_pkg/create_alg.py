@@ -39,16 +39,24 @@ soft_q_registry = Registry("algorithm")
 # as it is.  `create_alg` and `create_approx_contrainer` look in all five; `on_policy_registry` folds back with the others.
 _ON_POLICY_ALGORITHMS = ("ppo",)
 on_policy_registry = Registry("algorithm")
-_ELSEWHERE = _LOOP_ALGORITHMS + _SOFT_ALGORITHMS + _SOFT_Q_ALGORITHMS + _ON_POLICY_ALGORITHMS
+# TRPO likewise: the key set of `on_policy_registry` is pinned by tests/test_ppo_cpu.py (as it stood before TRPO), and that test file
+# stays as it is.  `create_alg` and `create_approx_contrainer` look in all six; `trust_region_registry` folds back with the others.
+_TRUST_REGION_ALGORITHMS = ("trpo",)
+trust_region_registry = Registry("algorithm")
+_ELSEWHERE = _LOOP_ALGORITHMS + _SOFT_ALGORITHMS + _SOFT_Q_ALGORITHMS + _ON_POLICY_ALGORITHMS + _TRUST_REGION_ALGORITHMS
 registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem not in _ELSEWHERE)
 loop_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _LOOP_ALGORITHMS)
 soft_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _SOFT_ALGORITHMS)
 soft_q_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _SOFT_Q_ALGORITHMS)
 on_policy_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _ON_POLICY_ALGORITHMS)
+trust_region_registry.scan(algorithm_path, "gops_amd.algorithm", _entries, keep=lambda stem: stem in _TRUST_REGION_ALGORITHMS)
+# the registries beside `registry`, and of them the ones whose modules state `MANDATORY` and `refusal(kwargs)` themselves
+_SIDE_REGISTRIES = (loop_registry, soft_registry, soft_q_registry, on_policy_registry, trust_region_registry)
+_SELF_DESCRIBED = (soft_q_registry, on_policy_registry, trust_region_registry)
 
 
 def _registry_of(algorithm: str) -> Registry:
-    return next((r for r in (loop_registry, soft_registry, soft_q_registry, on_policy_registry) if algorithm in r), registry)
+    return next((r for r in _SIDE_REGISTRIES if algorithm in r), registry)
 
 
 def _defaults(kwargs: dict) -> dict:
@@ -93,7 +101,7 @@ class LocalActor:
 def create_alg(**kwargs) -> object:
     reg = _registry_of(kwargs["algorithm"])
     entry = reg.lookup(kwargs["algorithm"])       # unknown algorithm: KeyError before anything else
-    if reg in (soft_q_registry, on_policy_registry):   # the arguments the reference's SAC / DSAC / PPO read with kwargs[...]: its KeyError, before any refusal
+    if reg in _SELF_DESCRIBED:   # the arguments the reference's SAC / DSAC / PPO / TRPO cannot do without: a KeyError, before any refusal
         for name in inspect.getmodule(entry.entry_point).MANDATORY:
             if name not in kwargs:
                 raise KeyError(name)
@@ -124,7 +132,7 @@ def create_alg(**kwargs) -> object:
         reason = refusal(kwargs)
         if reason is not None:
             raise NotImplementedError(reason)
-    if reg in (soft_q_registry, on_policy_registry):
+    if reg in _SELF_DESCRIBED:
         reason = inspect.getmodule(entry.entry_point).refusal(kwargs)
         if reason is not None:
             raise NotImplementedError(reason)

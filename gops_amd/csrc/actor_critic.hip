@@ -61,7 +61,9 @@ struct AcParams {
     float *backup, *a2, *q_targ;
 };
 
-int ac_check_net(const GopsMlp& m, int in, int out) {
+}  // namespace
+
+int ac_check_net(const GopsMlp& m, int in, int out) {   // (launchers.h: trpo.hip accepts the same nets)
     if (m.n_layers < 2 || m.n_layers > AC_MAX_HIDDEN + 1) return GOPS_ERR_UNSUPPORTED;   // (n_layers = 1: a POLY net)
     if (m.dtype != GOPS_DTYPE_F32 || m.variant_flags != 0) return GOPS_ERR_UNSUPPORTED;
     if (m.sizes[0] != in || m.sizes[m.n_layers] != out) return GOPS_ERR_BAD_ARG;
@@ -72,6 +74,8 @@ int ac_check_net(const GopsMlp& m, int in, int out) {
         if (m.weight[j] == nullptr || m.bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
     return GOPS_OK;
 }
+
+namespace {
 
 int ac_check(const GopsAcBackup* d, int B) {
     if (!d || B < 1) return GOPS_ERR_BAD_ARG;

@@ -1169,6 +1169,39 @@ int gops_gae(const float* rew, const float* val, const float* val_next, const fl
     return gae(rew, val, val_next, done, end, steps, n_envs, gamma, gae_lambda, ret, adv, static_cast<hipStream_t>(stream));
 }
 
+int gops_gauss_fisher_seed(const GopsMlp* policy, const GopsMlpGrad* tangent, int32_t batch, const float* x, double min_log_std,
+                           double max_log_std, float* seed, void* stream) {
+    if (!policy || !tangent || !x || !seed || batch < 1) return GOPS_ERR_BAD_ARG;
+    if (policy->n_layers < 1 || policy->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
+    return gauss_fisher_seed(*policy, *tangent, batch, x, min_log_std, max_log_std, seed, static_cast<hipStream_t>(stream));
+}
+
+int gops_trpo_surrogate(int32_t act_dim, int32_t batch, double min_log_std, double max_log_std, const float* head_new, const float* head_old,
+                        const float* act, const float* adv, const float* hyper, float* seed_head, float* stats, void* stream) {
+    if (batch < 1 || act_dim < 1 || act_dim > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (!head_new || !head_old || !act || !adv || !hyper || !stats) return GOPS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
+    return trpo_surrogate(batch, act_dim, min_log_std, max_log_std, head_new, head_old, act, adv, hyper, seed_head, stats,
+                          static_cast<hipStream_t>(stream));
+}
+
+static bool cg_state_ok(const GopsCgState* st, int32_t n) { return st && n >= 1 && !(reinterpret_cast<uintptr_t>(st) & 7); }
+
+int gops_cg_init(const float* g, float* x, float* r, float* p, int32_t n, double atol, GopsCgState* state, void* stream) {
+    if (!g || !x || !r || !p || !cg_state_ok(state, n)) return GOPS_ERR_BAD_ARG;
+    return cg_init(g, x, r, p, n, atol, state, static_cast<hipStream_t>(stream));
+}
+
+int gops_cg_step(float* p, float* Ap, float* x, float* r, int32_t n, double damping, double atol, GopsCgState* state, void* stream) {
+    if (!p || !Ap || !x || !r || !cg_state_ok(state, n)) return GOPS_ERR_BAD_ARG;
+    return cg_step(p, Ap, x, r, n, damping, atol, state, static_cast<hipStream_t>(stream));
+}
+
+int gops_cg_finish(const float* g, const float* x, float* step, int32_t n, const float* hyper, GopsCgState* state, void* stream) {
+    if (!g || !x || !step || !hyper || !cg_state_ok(state, n)) return GOPS_ERR_BAD_ARG;
+    return cg_finish(g, x, step, n, hyper, state, static_cast<hipStream_t>(stream));
+}
+
 void gops_profile_enable(int32_t on) {
     std::lock_guard<std::mutex> lk(g_prof.mu);
     g_prof.on = on != 0;

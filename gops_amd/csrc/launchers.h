@@ -69,6 +69,18 @@ size_t soft_q_backup_workspace_bytes(const GopsSoftQBackup* d, int B);
 int soft_q_backup(const GopsSoftQBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
                   float* backup, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s);
 
+// (the nets the tile kernels take: fp32, 1 .. 3 hidden layers of widths that are multiples of 16 up to 256; also trpo.hip's)
+int ac_check_net(const GopsMlp& m, int in, int out);
+
+// ---- trpo.hip: the Fisher-vector product's tangent forward, TRPO's surrogate with the line search's verdict, conjugate gradients ----
+int gauss_fisher_seed(const GopsMlp& m, const GopsMlpGrad& tangent, int B, const float* x, double min_ls, double max_ls, float* seed,
+                      hipStream_t s);
+int trpo_surrogate(int M, int A, double min_ls, double max_ls, const float* head_new, const float* head_old, const float* act,
+                   const float* adv, const float* hyper, float* seed, float* stats, hipStream_t s);
+int cg_init(const float* g, float* x, float* r, float* p, int n, double atol, GopsCgState* st, hipStream_t s);
+int cg_step(float* p, float* Ap, float* x, float* r, int n, double damping, double atol, GopsCgState* st, hipStream_t s);
+int cg_finish(const float* g, const float* x, float* step, int n, const float* hyper, GopsCgState* st, hipStream_t s);
+
 // ---- dsact.hip: DSAC-T's and DSAC's critic losses with their seeds, and the tanh-Gaussian sampling head forward and reverse ----
 int dsact_critic_loss(const float* qraw, const float* tq, const float* tqs, int B, double tau_b, GopsDsactState* st, float* seed,
                       float* stats, hipStream_t s);

@@ -1,0 +1,428 @@
+// The stages of a TRPO update (gops/algorithm/trpo.py) that the MLP launches do not cover.
+//
+// fisher_seed_kernel: the Gauss-Newton form of the KL Hessian-vector product needs J v, the directional derivative of the policy's
+//   RAW head (mean, raw log std) along a parameter tangent v = (V_j, c_j).  A workgroup of 256 threads owns a tile of R batch rows
+//   (actor_critic.hip's scheme) and carries, per layer, the primal row h and ONE tangent row t:
+//       z = W h + b,   u = W t + V h + c,   h' = act(z),   t' = act'(z) u,      t_0 = 0
+//   LDS:  in0 [R][O]; xa, xb [R][ldx] primal activations, ping-pong; ta, tb [R][ldx] tangents, ping-pong; wb: one chunk of W,
+//         TRANSPOSED ([K][NC]) with its biases behind it, and the same chunk of V with c behind that.
+//   thread (r = tid % R, g = tid / R): row r, feature quads g, g + 256 / R, ..; z is eight fp32 fmaf chains (input k in chain k mod 8,
+//   k ascending) added pairwise, bias last; u is two such sets of chains, one for W t and one for V h, added, then c -
+//   the same bits whatever R and the chunk size are.  The head (2A outputs and their tangents) is the same chains in DOUBLE, one
+//   thread per (row, action dimension); it scales the tangent by the metric of the Gaussian's KL, M = diag(1 / sigma^2, 2 inside the
+//   clamp | 0 outside), sigma = exp(clamp(raw)) of the primal it has just formed, and by 1 / B.  No atomics, no workgroup waits.
+// trpo_surrogate_kernel: mean(exp(logp_new - logp_old) adv), mean KL(new || old), the seed d surrogate / d head_new and the line
+//   search's verdict, ppo_loss_kernel's style: values in double, rounded once where stored, sums in the fixed order of block_reduce.h.
+// cg_*_kernel: trpo.py:226-267 on flat fp32 vectors with every scalar in a device state block (GopsCgState of gops_hip.h).
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "block_reduce.h"
+#include "launchers.h"
+#include "soft_math.h"
+
+namespace {
+
+constexpr int FS_THREADS = 256;
+constexpr int FS_CHAINS = 8;
+constexpr size_t FS_LDS_TWO = 64 * 1024;     // two workgroups per CU
+constexpr size_t FS_LDS_LIMIT = 150 * 1024;  // one (the CU has 160 KiB)
+
+struct FsParams {
+    int nl, act, B, O, A;
+    int dims[GOPS_MAX_LAYERS + 1];
+    int nc[GOPS_MAX_LAYERS];   // output features per staged chunk of hidden layer j
+    const float* W[GOPS_MAX_LAYERS];
+    const float* Bv[GOPS_MAX_LAYERS];
+    const float* V[GOPS_MAX_LAYERS];    // the tangent's weight slices
+    const float* Cv[GOPS_MAX_LAYERS];   // and its bias slices
+    int ld0, ldx, xa_off, xb_off, ta_off, tb_off, w_off;   // floats
+    double min_ls, max_ls;
+    const float* x;
+    float* seed;
+};
+
+inline int fs_up4(int x) { return (x + 3) & ~3; }
+
+// LDS plan for tiles of R rows within `limit` bytes (actor_critic.hip's ac_plan with four activation planes and two weight chunks).
+size_t fs_plan(const GopsMlp& m, int R, size_t limit, int min_nc, FsParams& p) {
+    int maxh = 0;
+    for (int j = 1; j < m.n_layers; ++j) maxh = std::max(maxh, (int)m.sizes[j]);
+    p.ld0 = m.sizes[0] | 1;
+    p.ldx = maxh | 1;
+    const int plane = fs_up4(R * p.ldx);
+    p.xa_off = fs_up4(R * p.ld0);
+    p.xb_off = p.xa_off + plane;
+    p.ta_off = p.xb_off + plane;
+    p.tb_off = p.ta_off + plane;
+    p.w_off = p.tb_off + plane;   // 16-byte aligned: the weight quads are read as one f32x4
+    const long long wfloats = (long long)(limit / sizeof(float)) - p.w_off;
+    if (wfloats <= 0) return 0;
+    long long used = 0;
+    for (int j = 0; j < m.n_layers - 1; ++j) {
+        const int K = m.sizes[j], N = m.sizes[j + 1];
+        int nc = (int)std::min<long long>(N, (wfloats / (2 * (K + 1))) & ~15LL);
+        if (nc < std::min(N, min_nc)) return 0;
+        p.nc[j] = nc;
+        used = std::max(used, 2LL * (K + 1) * nc);
+    }
+    const long long head = 2LL * (m.sizes[m.n_layers - 1] + 1) * m.sizes[m.n_layers];
+    if (head > wfloats) return 0;
+    used = std::max(used, head);
+    return ((size_t)p.w_off + (size_t)used) * sizeof(float);
+}
+
+size_t fs_choose(const GopsMlp& m, int B, FsParams& p, int& R) {
+    for (R = B >= 16384 ? 64 : B >= 2048 ? 32 : 16; R >= 16; R >>= 1) {
+        size_t lds = fs_plan(m, R, FS_LDS_TWO, 64, p);
+        if (lds == 0) lds = fs_plan(m, R, FS_LDS_LIMIT, 16, p);
+        if (lds != 0) return lds;
+    }
+    return 0;
+}
+
+// h = act(z), d = act'(z) as torch evaluates them (common.h: act3_t, fp32 libm - erf-form GELU, expm1f for ELU / SELU).  The fast
+// forms of the rollout kernels' forward (polynomial Phi, hardware exp: absolute error ~1e-7) would be the largest term of a seed's
+// error; here the product feeds ten conjugate-gradient iterations.
+template <int ACT>
+__device__ __forceinline__ void fs_act(float z, float& h, float& d) {
+    float d2;
+    act3_t<ACT>(z, h, d, d2);
+}
+
+template <int R>
+__global__ __launch_bounds__(FS_THREADS) void fisher_seed_kernel(const FsParams p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int G = FS_THREADS / R;
+    const int tid = threadIdx.x, r = tid % R, g = tid / R;
+    const int b0 = blockIdx.x * R, nvalid = min(R, p.B - b0), O = p.O, A = p.A, ldx = p.ldx;
+    float *in0 = lds, *xa = lds + p.xa_off, *xb = lds + p.xb_off, *ta = lds + p.ta_off, *tb = lds + p.tb_off, *wb = lds + p.w_off;
+    for (int idx = tid; idx < R * O; idx += FS_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
+        const int m = idx / O, k = idx - m * O;
+        in0[m * p.ld0 + k] = m < nvalid ? p.x[(size_t)(b0 + m) * O + k] : 0.f;
+    }
+    const float *cur = in0, *curt = ta;   // (curt is not read in layer 0: t_0 = 0)
+    int ldc = p.ld0;
+    float *nxt = xa, *nxtt = ta;
+#pragma unroll 1
+    for (int j = 0; j < p.nl - 1; ++j) {
+        const int K = p.dims[j], N = p.dims[j + 1], NC = p.nc[j];
+        const float* __restrict__ Wg = p.W[j];
+        const float* __restrict__ Vg = p.V[j];
+        float* vb = wb + (K + 1) * NC;   // the tangent's chunk, behind W's chunk and biases
+        const bool first = j == 0;
+#pragma unroll 1
+        for (int n0 = 0; n0 < N; n0 += NC) {
+            const int nc = min(NC, N - n0);
+            __syncthreads();   // the previous readers of wb are done; what the previous layer (or the staging above) wrote is visible
+            for (int idx = tid; idx < nc * K; idx += FS_THREADS) {
+                const int k = idx / nc, nn = idx - k * nc;
+                wb[k * NC + nn] = Wg[(size_t)(n0 + nn) * K + k];
+                vb[k * NC + nn] = Vg[(size_t)(n0 + nn) * K + k];
+            }
+            for (int idx = tid; idx < nc; idx += FS_THREADS) {
+                wb[K * NC + idx] = p.Bv[j][n0 + idx];
+                vb[K * NC + idx] = p.Cv[j][n0 + idx];
+            }
+            __syncthreads();
+            const float* xr = cur + r * ldc;
+            const float* tr = curt + r * ldx;
+            act_dispatch(p.act, [&]<int ACT>() {
+                for (int fg = g; fg < (nc >> 2); fg += G) {
+                    const float* wq = wb + 4 * fg;
+                    const float* vq = vb + 4 * fg;
+                    f32x4 c[FS_CHAINS], cu[FS_CHAINS], cv[FS_CHAINS];
+#pragma unroll
+                    for (int i = 0; i < FS_CHAINS; ++i) c[i] = cu[i] = cv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const int K8 = K & ~(FS_CHAINS - 1);
+                    auto term = [&](int k, int i) {
+                        const float x = xr[k];
+                        const f32x4 w = *reinterpret_cast<const f32x4*>(wq + k * NC);
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(vq + k * NC);
+                        if (!first) {
+                            const float t = tr[k];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) cu[i][e] = fmaf(t, w[e], cu[i][e]);
+                        }
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            c[i][e] = fmaf(x, w[e], c[i][e]);
+                            cv[i][e] = fmaf(x, v[e], cv[i][e]);
+                        }
+                    };
+                    for (int k = 0; k < K8; k += FS_CHAINS) {
+#pragma unroll
+                        for (int i = 0; i < FS_CHAINS; ++i) term(k + i, i);
+                    }
+#pragma unroll
+                    for (int i = 0; i < FS_CHAINS - 1; ++i)
+                        if (K8 + i < K) term(K8 + i, i);
+                    const float* bq = wb + K * NC + 4 * fg;
+                    const float* cq = vb + K * NC + 4 * fg;
+                    float* yr = nxt + r * ldx + n0 + 4 * fg;
+                    float* ur = nxtt + r * ldx + n0 + 4 * fg;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float z = ((c[0][e] + c[1][e]) + (c[2][e] + c[3][e])) + ((c[4][e] + c[5][e]) + (c[6][e] + c[7][e])) + bq[e];
+                        const float wt = ((cu[0][e] + cu[1][e]) + (cu[2][e] + cu[3][e])) + ((cu[4][e] + cu[5][e]) + (cu[6][e] + cu[7][e]));
+                        const float vh = ((cv[0][e] + cv[1][e]) + (cv[2][e] + cv[3][e])) + ((cv[4][e] + cv[5][e]) + (cv[6][e] + cv[7][e]));
+                        const float u = (wt + vh) + cq[e];
+                        float h, d;
+                        fs_act<ACT>(z, h, d);
+                        yr[e] = h;
+                        ur[e] = d * u;
+                    }
+                }
+            });
+        }
+        cur = nxt, curt = nxtt, ldc = ldx;
+        nxt = nxt == xa ? xb : xa;
+        nxtt = nxtt == ta ? tb : ta;
+    }
+    // ---- head: W_L [2A][K] with b_L behind it, V_L and c_L behind those; one thread per (row, action dimension) ----
+    const int L = p.nl - 1, K = p.dims[L], N = 2 * A;
+    __syncthreads();
+    for (int idx = tid; idx < N * K; idx += FS_THREADS) wb[idx] = p.W[L][idx], wb[N * K + N + idx] = p.V[L][idx];
+    for (int idx = tid; idx < N; idx += FS_THREADS) wb[N * K + idx] = p.Bv[L][idx], wb[2 * N * K + N + idx] = p.Cv[L][idx];
+    __syncthreads();
+    if (g < A && r < nvalid) {
+        const float *xr = cur + r * ldx, *tr = curt + r * ldx, *vb = wb + N * K + N;
+        auto dot = [&](const float* a, const float* w) {   // eight double fma chains, input k in chain k mod 8, added pairwise
+            double c[FS_CHAINS];
+#pragma unroll
+            for (int i = 0; i < FS_CHAINS; ++i) c[i] = 0.0;
+            for (int k = 0; k < K; k += FS_CHAINS) {   // (hidden widths are multiples of 16)
+#pragma unroll
+                for (int i = 0; i < FS_CHAINS; ++i) c[i] = fma((double)a[k + i], (double)w[k + i], c[i]);
+            }
+            return ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
+        };
+        const double raw = dot(xr, wb + (A + g) * K) + (double)wb[N * K + A + g];
+        const double t_mean = (dot(tr, wb + g * K) + dot(xr, vb + g * K)) + (double)vb[N * K + g];
+        const double t_raw = (dot(tr, wb + (A + g) * K) + dot(xr, vb + (A + g) * K)) + (double)vb[N * K + A + g];
+        const bool inside = raw >= p.min_ls && raw <= p.max_ls;   // (the clamp passes its gradient on the closed interval, as torch's)
+        const double sd = exp(fmin(fmax(raw, p.min_ls), p.max_ls)), inv_b = 1.0 / (double)p.B;
+        float* out = p.seed + (size_t)(b0 + r) * N;
+        out[g] = (float)(t_mean / (sd * sd) * inv_b);
+        out[A + g] = inside ? (float)(2.0 * t_raw * inv_b) : 0.f;
+    }
+}
+
+// ---- surrogate advantage, KL and the line search's verdict (trpo.py:133-138, 148, 185-196) ---------------------------------------
+constexpr int TS_BLOCKS = 64;
+constexpr int TS_VERDICT_AT = 2;   // int32 behind the two results, one spare float behind it
+constexpr int TS_PART_AT = 4;      // the blocks' partial sums
+constexpr int TS_PART = 2;
+
+__global__ __launch_bounds__(256) void trpo_surrogate_kernel(int M, int A, double min_ls, double max_ls, const float* head_new,
+                                                             const float* head_old, const float* __restrict__ act,
+                                                             const float* __restrict__ adv, const float* __restrict__ hyper,
+                                                             float* __restrict__ seed, float* __restrict__ stats) {
+    __shared__ double red[TS_PART][4];
+    __shared__ bool last;
+    double* part = reinterpret_cast<double*>(stats + TS_PART_AT);   // [TS_BLOCKS][TS_PART]
+    unsigned* ticket = reinterpret_cast<unsigned*>(stats + TS_PART_AT + 2 * TS_PART * TS_BLOCKS);
+    const double inv_m = 1.0 / (double)M;
+    double s[2] = {0.0, 0.0};   // sum ratio adv, sum kl
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < M; i += gridDim.x * 256) {
+        const float* hn = head_new + (size_t)i * 2 * A;
+        const float* ho = head_old + (size_t)i * 2 * A;
+        double lpn = 0.0, lpo = 0.0, kl = 0.0;
+        for (int a = 0; a < A; ++a) {
+            const double x = (double)act[(size_t)i * A + a];
+            const double mn = (double)hn[a], lsn = fmin(fmax((double)hn[A + a], min_ls), max_ls), sn = exp(lsn), dn = x - mn;
+            const double mo = (double)ho[a], lso = fmin(fmax((double)ho[A + a], min_ls), max_ls), so = exp(lso), dl = x - mo;
+            lpn += -(dn * dn) / (2 * sn * sn) - lsn - HALF_LOG_2PI;
+            lpo += -(dl * dl) / (2 * so * so) - lso - HALF_LOG_2PI;
+            kl += lso - lsn + (sn * sn + (mn - mo) * (mn - mo)) / (2 * so * so) - 0.5;   // KL(N(new) || N(old))
+        }
+        const double ratio = exp(lpn - lpo), ad = (double)adv[i];
+        if (seed != nullptr) {
+            const double g_lp = inv_m * ad * ratio;   // d surrogate / d logp_new of the row
+            for (int a = 0; a < A; ++a) {
+                const double raw = (double)hn[A + a];
+                const bool inside = raw >= min_ls && raw <= max_ls;
+                const double sd = exp(fmin(fmax(raw, min_ls), max_ls)), iv = 1.0 / (sd * sd), d = (double)act[(size_t)i * A + a] - (double)hn[a];
+                seed[(size_t)i * 2 * A + a] = (float)(g_lp * d * iv);
+                seed[(size_t)i * 2 * A + A + a] = inside ? (float)(g_lp * (d * d * iv - 1.0)) : 0.f;
+            }
+        }
+        s[0] += ratio * ad, s[1] += kl;
+    }
+    block_fold<2, false>(s, red);
+    bool fin = gridDim.x == 1;
+    if (!fin) {
+        fin = last_block<2>(s, part, TS_PART, ticket, &last);
+        if (fin) block_fold<2, false>(s, red);
+    }
+    if (fin && threadIdx.x == 0) {
+        const float sur = (float)(s[0] * inv_m), kl = (float)(s[1] * inv_m);   // (the reference compares its fp32 values)
+        stats[0] = sur, stats[1] = kl;
+        reinterpret_cast<int*>(stats)[TS_VERDICT_AT] = sur > 0.f && kl < hyper[0] ? 1 : 0;
+    }
+}
+static_assert(TS_PART_AT + 2 * TS_PART * TS_BLOCKS + 1 <= GOPS_TRPO_STATS_FLOATS, "stats: results, the verdict, the blocks' partial sums, the ticket");
+
+// ---- conjugate gradients (trpo.py:226-267) ---------------------------------------------------------------------------------------
+constexpr int CG_BLOCKS = 64;
+constexpr double CG_EPS = 1e-8;   // trpo.py:35
+static_assert(sizeof(GopsCgState) == GOPS_CG_STATE_FLOATS * sizeof(float) && sizeof(GopsCgState::part) == 2 * CG_BLOCKS * sizeof(double),
+              "GopsCgState: the scalars, the counters, 64 blocks' two partial sums");
+
+// The sums of the block's (or, in the block that draws the last ticket, the grid's) `s`; true where they are final.
+__device__ __forceinline__ bool cg_fold(double (&s)[2], GopsCgState* st, double (*red)[4], bool* last) {
+    block_fold<2, false>(s, red);
+    if (gridDim.x == 1) return true;
+    if (!last_block<2>(s, st->part, 2, reinterpret_cast<unsigned*>(&st->ticket), last)) return false;
+    block_fold<2, false>(s, red);
+    return true;
+}
+
+// x = 0, r = p = g, r_dot = r.r, done = all(|r| <= atol)   (the reference's first Ax(x0) is a product with zero: not formed)
+__global__ __launch_bounds__(256) void cg_init_kernel(const float* __restrict__ gvec, float* __restrict__ x, float* __restrict__ r,
+                                                      float* __restrict__ p, int n, double atol, GopsCgState* st) {
+    __shared__ double red[2][4];
+    __shared__ bool last;
+    double s[2] = {0.0, 0.0};   // r.r, elements with not |r| <= atol
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float v = gvec[i];
+        x[i] = 0.f, r[i] = v, p[i] = v;
+        s[0] += (double)v * (double)v, s[1] += fabs((double)v) <= atol ? 0.0 : 1.0;
+    }
+    if (cg_fold(s, st, red, &last) && threadIdx.x == 0) {
+        st->r_dot = s[0], st->p_ap = 0.0, st->alpha = 0.0, st->beta = 0.0, st->g_x = 0.0, st->scale = 0.0;
+        st->done = s[1] == 0.0 ? 1 : 0, st->calls = 0, st->iterations = 0;
+    }
+}
+
+// One iteration in three phases (bits 1, 2, 4): one workgroup runs all three in one launch; 64 workgroups one phase per launch.
+// Every thread owns the same elements in every phase, so inside one workgroup only the scalars cross threads (through cg_fold).
+__global__ __launch_bounds__(256) void cg_step_kernel(int phases, float* __restrict__ p, float* __restrict__ Ap, float* __restrict__ x,
+                                                      float* __restrict__ r, int n, double damping, double atol, GopsCgState* st) {
+    __shared__ double red[2][4];
+    __shared__ bool last;
+    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    const bool done_in = st->done != 0;   // (phases 1 and 2: as the call found it; phase 4: as phase 2 left it)
+    if (phases & 1) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) st->calls = st->calls + 1;
+    }
+    if (done_in) return;   // nothing changes once the residual is within atol
+    double alpha = 0.0, beta = 0.0;
+    bool done = false;
+    if (phases & 1) {   // Ap += damping p;  alpha = r_dot / (p.Ap + 1e-8)
+        double s[2] = {0.0, 0.0};
+        for (int i = first; i < n; i += stride) {
+            const float pi = p[i], ap = (float)((double)Ap[i] + damping * (double)pi);
+            Ap[i] = ap;
+            s[0] += (double)pi * (double)ap;
+        }
+        const bool fin = cg_fold(s, st, red, &last);
+        alpha = st->r_dot / (s[0] + CG_EPS);   // (final where fin; one workgroup: in every thread)
+        if (fin && threadIdx.x == 0) st->p_ap = s[0], st->alpha = alpha;
+        if (phases == 1) return;
+    } else {
+        alpha = st->alpha;
+    }
+    if (phases & 2) {   // x += alpha p;  r -= alpha Ap;  done = all(|r| <= atol);  beta = r_dot' / (r_dot + 1e-8)
+        double s[2] = {0.0, 0.0};
+        const double r_dot = st->r_dot;
+        for (int i = first; i < n; i += stride) {
+            x[i] = (float)((double)x[i] + alpha * (double)p[i]);
+            const float rn = (float)((double)r[i] - alpha * (double)Ap[i]);
+            r[i] = rn;
+            s[0] += (double)rn * (double)rn, s[1] += fabs((double)rn) <= atol ? 0.0 : 1.0;
+        }
+        __syncthreads();   // (one workgroup: every thread has read st->r_dot before thread 0 replaces it)
+        const bool fin = cg_fold(s, st, red, &last);
+        beta = s[0] / (r_dot + CG_EPS), done = s[1] == 0.0;
+        if (fin && threadIdx.x == 0) {
+            st->r_dot = s[0], st->beta = beta, st->iterations = st->iterations + 1;
+            st->done = done ? 1 : 0;
+        }
+        if (phases == 2) return;
+    } else {
+        beta = st->beta;
+    }
+    if (done) return;
+    for (int i = first; i < n; i += stride) p[i] = (float)((double)r[i] + beta * (double)p[i]);   // p = r + beta p
+}
+
+// step = sqrt(2 delta / (g.x + 1e-8)) x   (trpo.py:175-177); phases 1 (the dot), 2 (the scaling)
+__global__ __launch_bounds__(256) void cg_finish_kernel(int phases, const float* __restrict__ gvec, const float* __restrict__ x,
+                                                        float* __restrict__ step, int n, const float* __restrict__ hyper, GopsCgState* st) {
+    __shared__ double red[2][4];
+    __shared__ bool last;
+    double scale;
+    if (phases & 1) {
+        double s[2] = {0.0, 0.0};
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) s[0] += (double)gvec[i] * (double)x[i];
+        const bool fin = cg_fold(s, st, red, &last);
+        scale = sqrt(2.0 * (double)hyper[0] / (s[0] + CG_EPS));
+        if (fin && threadIdx.x == 0) st->g_x = s[0], st->scale = scale;
+        if (phases == 1) return;
+    } else {
+        scale = st->scale;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) step[i] = (float)(scale * (double)x[i]);
+}
+
+}  // namespace
+
+int gauss_fisher_seed(const GopsMlp& m, const GopsMlpGrad& tangent, int B, const float* x, double min_ls, double max_ls, float* seed,
+                      hipStream_t s) {
+    const int O = m.sizes[0], A2 = m.sizes[m.n_layers], A = A2 / 2;
+    if (O < 1 || A < 1 || (A2 & 1) || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (O > 64) return GOPS_ERR_UNSUPPORTED;
+    const int rc = ac_check_net(m, O, A2);
+    if (rc != GOPS_OK) return rc;
+    for (int j = 0; j < m.n_layers; ++j)
+        if (tangent.weight[j] == nullptr || tangent.bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
+    FsParams p;
+    memset(&p, 0, sizeof(p));
+    int R;
+    const size_t lds = fs_choose(m, B, p, R);
+    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
+    p.nl = m.n_layers, p.act = m.hidden_act, p.B = B, p.O = O, p.A = A;
+    for (int j = 0; j <= p.nl; ++j) p.dims[j] = m.sizes[j];
+    for (int j = 0; j < p.nl; ++j) p.W[j] = m.weight[j], p.Bv[j] = m.bias[j], p.V[j] = tangent.weight[j], p.Cv[j] = tangent.bias[j];
+    p.min_ls = min_ls, p.max_ls = max_ls, p.x = x, p.seed = seed;
+    const dim3 grid((unsigned)((B + R - 1) / R)), threads(FS_THREADS);
+    if (R == 64) launch_with_lds(fisher_seed_kernel<64>, grid, threads, lds, s, p);
+    else if (R == 32) launch_with_lds(fisher_seed_kernel<32>, grid, threads, lds, s, p);
+    else launch_with_lds(fisher_seed_kernel<16>, grid, threads, lds, s, p);
+    return (int)hipGetLastError();
+}
+
+int trpo_surrogate(int M, int A, double min_ls, double max_ls, const float* head_new, const float* head_old, const float* act,
+                   const float* adv, const float* hyper, float* seed, float* stats, hipStream_t s) {
+    hipLaunchKernelGGL(trpo_surrogate_kernel, dim3(M <= LOSS_ONE_BLOCK_MAX ? 1 : TS_BLOCKS), dim3(256), 0, s, M, A, min_ls, max_ls, head_new,
+                       head_old, act, adv, hyper, seed, stats);
+    return (int)hipGetLastError();
+}
+
+int cg_init(const float* g, float* x, float* r, float* p, int n, double atol, GopsCgState* st, hipStream_t s) {
+    hipLaunchKernelGGL(cg_init_kernel, dim3(n <= GOPS_CG_ONE_BLOCK_MAX ? 1 : CG_BLOCKS), dim3(256), 0, s, g, x, r, p, n, atol, st);
+    return (int)hipGetLastError();
+}
+
+int cg_step(float* p, float* Ap, float* x, float* r, int n, double damping, double atol, GopsCgState* st, hipStream_t s) {
+    if (n <= GOPS_CG_ONE_BLOCK_MAX) {
+        hipLaunchKernelGGL(cg_step_kernel, dim3(1), dim3(256), 0, s, 7, p, Ap, x, r, n, damping, atol, st);
+    } else {
+        for (int phase = 1; phase <= 4; phase <<= 1)
+            hipLaunchKernelGGL(cg_step_kernel, dim3(CG_BLOCKS), dim3(256), 0, s, phase, p, Ap, x, r, n, damping, atol, st);
+    }
+    return (int)hipGetLastError();
+}
+
+int cg_finish(const float* g, const float* x, float* step, int n, const float* hyper, GopsCgState* st, hipStream_t s) {
+    if (n <= GOPS_CG_ONE_BLOCK_MAX) {
+        hipLaunchKernelGGL(cg_finish_kernel, dim3(1), dim3(256), 0, s, 3, g, x, step, n, hyper, st);
+    } else {
+        hipLaunchKernelGGL(cg_finish_kernel, dim3(CG_BLOCKS), dim3(256), 0, s, 1, g, x, step, n, hyper, st);
+        hipLaunchKernelGGL(cg_finish_kernel, dim3(CG_BLOCKS), dim3(256), 0, s, 2, g, x, step, n, hyper, st);
+    }
+    return (int)hipGetLastError();
+}

@@ -239,6 +239,11 @@ def _signatures():
         "gops_ppo_loss": (rc, [P(GopsPpoLoss), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gops_adv_normalize": (rc, [vp, i32, f64, vp, vp, vp]),
         "gops_gae": (rc, [vp, vp, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp]),
+        "gops_gauss_fisher_seed": (rc, [mlp, grad, i32, vp, f64, f64, vp, vp]),
+        "gops_trpo_surrogate": (rc, [i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gops_cg_init": (rc, [vp, vp, vp, vp, i32, f64, vp, vp]),
+        "gops_cg_step": (rc, [vp, vp, vp, vp, i32, f64, f64, vp, vp]),
+        "gops_cg_finish": (rc, [vp, vp, vp, i32, vp, vp, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -1564,6 +1569,112 @@ def gae(rew, val, val_next, done, end, gamma: float = 0.99, gae_lambda: float = 
     check(lib().gops_gae(_ptr(rew), _ptr(val), _ptr(val_next), _ptr(done), _ptr(end), T, N, float(gamma), float(gae_lambda), _ptr(ret),
                          _ptr(adv), _stream()), "gops_gae")
     return ret, adv
+
+
+TRPO_STATS_FLOATS = 264   # include/gops_hip.h: GOPS_TRPO_STATS_FLOATS
+TRPO_HYPER_FLOATS = 4     # include/gops_hip.h: GOPS_TRPO_HYPER_FLOATS
+CG_STATE_FLOATS = 272     # include/gops_hip.h: GOPS_CG_STATE_FLOATS (sizeof(GopsCgState) / 4)
+CG_ONE_BLOCK_MAX = 8192   # include/gops_hip.h: GOPS_CG_ONE_BLOCK_MAX
+
+
+class GopsCgState(C.Structure):   # gops_cg_init / _step / _finish
+    _fields_ = [("r_dot", C.c_double), ("p_ap", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("g_x", C.c_double),
+                ("scale", C.c_double), ("done", C.c_int32), ("calls", C.c_int32), ("iterations", C.c_int32), ("ticket", C.c_int32),
+                ("part", C.c_double * 128)]
+
+
+def flat_views(flat: torch.Tensor, shapes) -> List[torch.Tensor]:
+    """Consecutive views of the flat vector `flat` with `shapes`: `parameters_to_vector`'s order when `shapes` are the parameters'."""
+    out, at = [], 0
+    for shape in shapes:
+        n = int(np.prod(shape))
+        out.append(flat[at:at + n].view(*shape))
+        at += n
+    assert at == flat.numel()
+    return out
+
+
+class FisherSeed:
+    """`gops_gauss_fisher_seed` (csrc/trpo.hip): seed [B, 2A] = (1/B) M (J v) of a Gaussian `mlp_shared` policy, v given as per-layer
+    tensors (or views of one flat vector) in the weights' layout.  `MlpNet.backward(x, seed, ...)` then yields the Fisher-vector
+    product.  The policy's weights are read in place at every call."""
+
+    def __init__(self, mlp: GopsMlp, min_log_std: float, max_log_std: float, device):
+        self.mlp, self.device = mlp, device
+        self.out_dim = int(mlp.sizes[mlp.n_layers])
+        self.min_log_std, self.max_log_std = float(min_log_std), float(max_log_std)
+
+    def run(self, x: torch.Tensor, tangent_w, tangent_b, seed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        B = x.shape[0]
+        seed = torch.empty(B, self.out_dim, dtype=torch.float32, device=x.device) if seed is None else seed
+        assert seed.numel() == B * self.out_dim and x.numel() == B * int(self.mlp.sizes[0])
+        assert len(tangent_w) == len(tangent_b) == self.mlp.n_layers
+        for j, (w, b) in enumerate(zip(tangent_w, tangent_b)):
+            assert w.numel() == int(self.mlp.sizes[j]) * int(self.mlp.sizes[j + 1]) and b.numel() == int(self.mlp.sizes[j + 1])
+        t = make_mlp_grad(tangent_w, tangent_b)
+        check(lib().gops_gauss_fisher_seed(C.byref(self.mlp), C.byref(t), B, _ptr(x), self.min_log_std, self.max_log_std, _ptr(seed),
+                                           _stream()), "gops_gauss_fisher_seed")
+        return seed
+
+
+class TrpoSurrogate:
+    """TRPO's surrogate advantage, mean KL(new || old), the surrogate's gradient seed and the line search's verdict in one launch
+    (`gops_trpo_surrogate`).  `buf[:2]` = surrogate, kl; `verdict` (int32 view of `buf[2]`) = surrogate > 0 and kl < delta; `hyper`
+    (device): delta, read by the kernel."""
+
+    def __init__(self, act_dim: int, min_log_std: float, max_log_std: float, device):
+        self.act_dim, self.min_log_std, self.max_log_std = int(act_dim), float(min_log_std), float(max_log_std)
+        self.buf = torch.zeros(TRPO_STATS_FLOATS, dtype=torch.float32, device=device)
+        self.hyper = torch.zeros(TRPO_HYPER_FLOATS, dtype=torch.float32, device=device)
+        self.verdict = self.buf.view(torch.int32)[2:3]
+        self._delta = None
+
+    def set_delta(self, delta: float):
+        if float(delta) != self._delta:   # (a host-to-device copy: never inside a capture)
+            self.hyper[:1].copy_(torch.tensor([float(delta)], dtype=torch.float32))
+            self._delta = float(delta)
+
+    def run(self, head_new, head_old, act, adv, seed_head=None, want_seed=True):
+        """head_new, head_old [M, 2A] raw (may be the same tensor) -> (seed_head [M, 2A] or None, stats [2])."""
+        M, A = head_new.shape[0], self.act_dim
+        assert tuple(head_new.shape) == (M, 2 * A) and head_old.numel() == 2 * M * A and act.numel() == M * A and adv.numel() == M
+        if want_seed and seed_head is None:
+            seed_head = torch.empty_like(head_new)
+        assert seed_head is None or seed_head.numel() == 2 * M * A
+        check(lib().gops_trpo_surrogate(A, M, self.min_log_std, self.max_log_std, _ptr(head_new), _ptr(head_old), _ptr(act), _ptr(adv),
+                                        self.hyper.data_ptr(), _ptr(seed_head) if want_seed else None, self.buf.data_ptr(), _stream()),
+              "gops_trpo_surrogate")
+        return (seed_head if want_seed else None), self.buf[:2]
+
+
+class CgSolver:
+    """`_conjugate_gradient` of the reference's TRPO (trpo.py:226-267) on the device (`gops_cg_init / _step / _finish`): owns the
+    flat fp32 vectors `g, x, r, p, Ap, step` of `n` elements and the state block (`GopsCgState`); the caller writes the undamped
+    product into `Ap` between `init` / `step` calls and reads nothing on the host.  `hyper` (device): delta, for `finish`."""
+
+    def __init__(self, n: int, device, hyper: Optional[torch.Tensor] = None):
+        self.n = int(n)
+        vec = torch.zeros(6, self.n, dtype=torch.float32, device=device)
+        self.g, self.x, self.r, self.p, self.Ap, self.step_vec = vec.unbind(0)
+        self._state = torch.zeros(CG_STATE_FLOATS // 2, dtype=torch.float64, device=device)   # (8-byte aligned)
+        self.hyper = torch.zeros(TRPO_HYPER_FLOATS, dtype=torch.float32, device=device) if hyper is None else hyper
+
+    def init(self, atol: float):
+        check(lib().gops_cg_init(_ptr(self.g), _ptr(self.x), _ptr(self.r), _ptr(self.p), self.n, float(atol), self._state.data_ptr(),
+                                 _stream()), "gops_cg_init")
+
+    def step(self, damping: float, atol: float):
+        check(lib().gops_cg_step(_ptr(self.p), _ptr(self.Ap), _ptr(self.x), _ptr(self.r), self.n, float(damping), float(atol),
+                                 self._state.data_ptr(), _stream()), "gops_cg_step")
+
+    def finish(self):
+        check(lib().gops_cg_finish(_ptr(self.g), _ptr(self.x), _ptr(self.step_vec), self.n, self.hyper.data_ptr(), self._state.data_ptr(),
+                                   _stream()), "gops_cg_finish")
+
+    def state(self) -> Dict[str, float]:
+        """The state block's fields on the host (one synchronisation)."""
+        raw = GopsCgState.from_buffer_copy(self._state.cpu().numpy().tobytes())
+        return {name: getattr(raw, name) for name, _ in GopsCgState._fields_[:9]}
 
 
 def make_update_tail(fused_adam=None, mean_of: Optional[torch.Tensor] = None, mean_scale: float = -1.0,

@@ -848,6 +848,61 @@ int gops_adv_normalize(const float* adv, int32_t n, double eps, float* out, floa
 int gops_gae(const float* rew, const float* val, const float* val_next, const float* done, const float* end, int32_t steps, int32_t n_envs,
              double gamma, double gae_lambda, float* ret, float* adv, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): TRPO (gops/algorithm/trpo.py; csrc/trpo.hip).
+ *
+ * At theta = theta_old the Hessian of mean_i KL(pi_theta(.|o_i) || pi_old(.|o_i)) is its Gauss-Newton term alone (the KL's gradient
+ * with respect to the head vanishes there):   H v = (1/B) sum_i J_i^T M_i J_i v,   J_i the Jacobian of the policy's RAW head
+ * (mean, raw log std) [2A] of row i with respect to the parameters,   M_i = diag(1 / sigma_a^2, m_a),   m_a = 2 where the raw log std
+ * lies in [min_log_std, max_log_std], 0 outside.  One product is gops_gauss_fisher_seed followed by gops_mlp_backward with its
+ * result as grad_y.
+ *
+ * gops_gauss_fisher_seed: seed [B, 2A] = (1/B) M_i (J_i v) for x [B, in] - the parameter-tangent forward fused with the metric.
+ *   `tangent`: v in GopsMlpGrad's layout (read only): weight[j] [out_j, in_j], bias[j] [out_j].  The primal is recomputed here; no
+ *   stash is read or written, and no workspace is needed.  Accepted nets: fp32, 1 .. 3 hidden layers of widths that are multiples of 16
+ *   up to 256, in <= 64, an even output width 2A with A <= GOPS_MAX_ACT, every hidden activation; GOPS_ERR_UNSUPPORTED otherwise.  A
+ *   row's result does not depend on the batch size.
+ * gops_trpo_surrogate: from the RAW heads head_new, head_old [M, 2A] (clamped and exponentiated here; they may be the same array),
+ *   act [M, A], adv [M]:
+ *     stats[0] = mean(exp(logp_new - logp_old) adv),   stats[1] = mean(KL(N(new) || N(old))),
+ *     ((int32_t*)stats)[2] = stats[0] > 0 && stats[1] < hyper[0]   (hyper: device, hyper[0] = delta; the line search's verdict),
+ *     seed_head [M, 2A] = d stats[0] / d head_new (the log-std column exactly 0 outside the clamp), unless seed_head is NULL.
+ *   With head_old == head_new the ratio is exactly 1 and the KL exactly 0.  stats: GOPS_TRPO_STATS_FLOATS floats, 8-byte aligned, all
+ *   zero before the first call (partial sums and a ticket behind the results).  One workgroup up to 8192 rows, 64 beyond.
+ * gops_cg_init / _step / _finish: `_conjugate_gradient` (trpo.py:226-267) for (H + damping I) x = g on flat fp32 vectors of n
+ *   elements, every scalar in the device state block, so that the host reads nothing between two products:
+ *     init:   x = 0, r = p = g, r_dot = r.r, done = all(|r| <= atol)   (allclose against zero: rtol multiplies |0|), counters = 0
+ *     step:   calls += 1; if done: nothing else.  Otherwise, with Ap the UNDAMPED product H p:
+ *             Ap += damping p;  alpha = r_dot / (p.Ap + 1e-8);  x += alpha p;  r -= alpha Ap;  iterations += 1;
+ *             done = all(|r| <= atol);  if not done: beta = r_dot' / (r_dot + 1e-8), p = r + beta p;   r_dot = r_dot'
+ *     finish: g_x = g.x;  scale = sqrt(2 hyper[0] / (g_x + 1e-8));  step = scale x     (hyper[0] = delta, as above)
+ *   Dots are doubles in the fixed order of the element count; elements are formed in double and rounded once.  Up to
+ *   GOPS_CG_ONE_BLOCK_MAX elements one workgroup does a whole call in one launch; beyond, a step is three launches of 64 workgroups
+ *   (init one, finish two).  The state block must be all zero before the first gops_cg_init.
+ *   GOPS_ERR_BAD_ARG: a NULL pointer, n < 1, a state block that is not 8-byte aligned. */
+struct GopsCgState {
+    double r_dot;         /* r.r of the current residual */
+    double p_ap;          /* p.(H + damping I) p of the last step */
+    double alpha, beta;   /* of the last step */
+    double g_x, scale;    /* gops_cg_finish */
+    int32_t done;         /* 1 once all(|r| <= atol) */
+    int32_t calls;        /* gops_cg_step calls since gops_cg_init */
+    int32_t iterations;   /* of them, the ones that updated x and r: where the reference's loop returns */
+    int32_t ticket;       /* scratch: zero between launches */
+    double part[128];     /* scratch: 64 workgroups' two partial sums */
+};
+typedef struct GopsCgState GopsCgState;
+#define GOPS_CG_STATE_FLOATS 272
+#define GOPS_CG_ONE_BLOCK_MAX 8192
+#define GOPS_TRPO_STATS_FLOATS 264
+#define GOPS_TRPO_HYPER_FLOATS 4
+int gops_gauss_fisher_seed(const GopsMlp* policy, const GopsMlpGrad* tangent, int32_t batch, const float* x, double min_log_std,
+                           double max_log_std, float* seed, void* stream);
+int gops_trpo_surrogate(int32_t act_dim, int32_t batch, double min_log_std, double max_log_std, const float* head_new, const float* head_old,
+                        const float* act, const float* adv, const float* hyper, float* seed_head, float* stats, void* stream);
+int gops_cg_init(const float* g, float* x, float* r, float* p, int32_t n, double atol, GopsCgState* state, void* stream);
+int gops_cg_step(float* p, float* Ap, float* x, float* r, int32_t n, double damping, double atol, GopsCgState* state, void* stream);
+int gops_cg_finish(const float* g, const float* x, float* step, int32_t n, const float* hyper, GopsCgState* state, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
