@@ -31,11 +31,10 @@ import numpy as np
 import torch
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import AlgorithmBase, ApprBase, batch_to_device, cuda_device_of, grad_buffers
-from gops_amd.apprfunc.mlp import StateValue, StochaPolicy
-from gops_amd.create_pkg.create_apprfunc import create_apprfunc
-from gops_amd.utils.act_distribution import GaussDistribution
-from gops_amd.utils.common_utils import get_apprfunc_dict, make_adam
+from gops_amd.algorithm import _on_policy
+from gops_amd.algorithm._on_policy import ApproxContainer, OnPolicyBase
+from gops_amd.algorithm.base import batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.utils.common_utils import make_adam
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.utils.tensorboard_setup import tb_tags
@@ -47,44 +46,11 @@ LOSS_TERMS = ("loss_total", "loss_surrogate", "loss_value", "loss_entropy", "app
 
 
 def refusal(kwargs: dict):
-    """Why `create_alg` cannot build PPO from these arguments, or None (POLY / LipsNet are refused before this is asked)."""
-    if kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
-        return f"PPO runs MLP networks only (policy_func_type {kwargs.get('policy_func_type')!r}, value_func_type {kwargs.get('value_func_type')!r})"
-    dist = kwargs.get("policy_act_distribution", "default")
-    if kwargs.get("policy_func_name") != "StochaPolicy" or dist not in ("default", "GaussDistribution"):
-        return (f"PPO takes a stochastic policy with a Gaussian action distribution (policy_func_name 'StochaPolicy', "
-                f"policy_act_distribution 'GaussDistribution' or 'default'), not {kwargs.get('policy_func_name')!r} with {dist!r}: "
-                "the loss kernel evaluates that density")
-    if kwargs.get("policy_std_type", "mlp_shared") != "mlp_shared":
-        return (f"PPO runs the policy with policy_std_type 'mlp_shared' only (one stack for mean and log std), not "
-                f"{kwargs.get('policy_std_type')!r}: 'parameter' and 'mlp_separated' are not yet supported")
-    if kwargs.get("value_func_name") != "StateValue":
-        return f"PPO takes a state-value function (value_func_name 'StateValue'), not {kwargs.get('value_func_name')!r}"
-    for key in ("policy", "value"):
-        if kwargs.get(f"{key}_output_activation", "linear") != "linear":
-            return (f"PPO takes networks with a linear output layer ({key}_output_activation "
-                    f"{kwargs.get(key + '_output_activation')!r}): the HIP kernels apply no output activation")
-    if hb.dtype_id(kwargs.get("mlp_dtype")) != 0:
-        return f"PPO is fp32 only (mlp_dtype {kwargs.get('mlp_dtype')!r}): its kernels have no half-precision path"
-    trainer = kwargs.get("trainer")
-    if trainer is not None and not trainer.startswith("on_serial"):
-        return f"PPO runs under on_serial_trainer only: trainer {trainer!r} has not been run with its on-policy columns"
-    return None
+    """Why `create_alg` cannot build PPO from these arguments, or None."""
+    return _on_policy.refusal("PPO", "the loss kernel evaluates that density", kwargs)
 
 
-class ApproxContainer(ApprBase):
-    """policy, then value: construction order (and with it the RNG draws and the optimizer's parameter order) follows ppo.py:39-45."""
-
-    def __init__(self, **kwargs):
-        super().__init__(**kwargs)
-        self.policy = create_apprfunc(**get_apprfunc_dict("policy", **kwargs))
-        self.value = create_apprfunc(**get_apprfunc_dict("value", **kwargs))
-
-    def create_action_distributions(self, logits):
-        return self.policy.get_act_dist(logits)
-
-
-class PPO(AlgorithmBase):
+class PPO(OnPolicyBase):
     """max_iteration, num_repeat, num_mini_batch, mini_batch_size, sample_batch_size: the reference's arguments (ppo.py:62-79); the
     attributes below its defaults (ppo.py:82-96)."""
 
@@ -114,16 +80,9 @@ class PPO(AlgorithmBase):
         self.value_clip = 10.0
         self.loss_value_norm = False
 
-        self.networks = ApproxContainer(**kwargs)
-        nets = self.networks
-        if type(nets.policy) is not StochaPolicy or nets.policy.action_distribution_cls is not GaussDistribution:
-            raise NotImplementedError(f"PPO: policy {type(nets.policy).__name__} (MLP StochaPolicy with GaussDistribution only)")
-        if not isinstance(nets.value, StateValue):
-            raise NotImplementedError(f"PPO: value network {type(nets.value).__name__} (MLP StateValue only)")
+        self._init_on_policy(kwargs)
         self.learning_rate = kwargs["learning_rate"]
-        self.approximate_optimizer = make_adam(nets.parameters(), lr=self.learning_rate)
-        self.tb_info = dict()
-        self._cache, self._bufs = {}, {}
+        self.approximate_optimizer = make_adam(self.networks.parameters(), lr=self.learning_rate)
         self._graph = StepGraphCache()
         self.graph_replays = 0   # minibatch steps that ran as a graph replay
 
@@ -179,18 +138,7 @@ class PPO(AlgorithmBase):
         M, device = mb["obs"].shape[0], mb["obs"].device
         loss = self._ppo_loss(M, device)
         loss.set_hyper(self.clip_now, self.value_clip, self.loss_coefficient_kl, self.loss_coefficient_value, self.loss_coefficient_entropy)
-
-        def step(b):
-            out = self.minibatch_gradients(b)
-            opt.step()
-            return out
-
-        def replayed():
-            opt.advance()
-            self.graph_replays += 1
-
-        out = self._graph.run(self._signature(mb), mb, step, before_replay=opt.sync_hyper, on_replay=replayed, work=M,
-                              on_capture_fail=opt.resync_device_state)
+        out = self._adam_step(self._graph, self._signature(mb), mb, self.minibatch_gradients, opt, "graph_replays")
         if self.schedule_clip == "linear":   # (after its use: ppo.py:228-231)
             decay_rate = 1 - (iteration / self.max_iteration)
             assert decay_rate >= 0, "decay_rate is less than 0!"
@@ -226,40 +174,14 @@ class PPO(AlgorithmBase):
         nets = self.networks
         return (tuple((k, tuple(v.shape)) for k, v in mb.items()), bool(self.loss_value_clip), bool(self.loss_value_norm),
                 tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in nets.parameters()),
-                self.approximate_optimizer.storage_signature(),
-                tuple(sorted(obj.workspace.data_ptr() for obj in self._cache.values() if hasattr(obj, "workspace"))),
-                tuple(sorted(t.data_ptr() for t in self._bufs.values())))
+                self.approximate_optimizer.storage_signature(), self._storage())
 
     # ---- kernels' objects ------------------------------------------------------------------------
-    def _net(self, role: str, module, B: int, device) -> hb.MlpNet:
-        key = (role, B, str(device))
-        mlp = module.hip_mlp()
-        net = self._cache.get(key)
-        if net is None:
-            net = self._cache[key] = hb.MlpNet(mlp, B, device=device)
-        else:
-            net.mlp = mlp
-        return net
-
-    def _buf(self, name: str, shape, device) -> torch.Tensor:
-        key = (name, tuple(shape), str(device))
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = torch.empty(shape, dtype=torch.float32, device=device)
-        return t
-
     def _ppo_loss(self, M: int, device) -> hb.PpoLoss:
         pol = self.networks.policy
         key = ("ppo_loss", str(device), bool(self.loss_value_clip), bool(self.loss_value_norm))
-        loss = self._cache.get(key)
+        loss = self._cache.get(key)   # (on every step's path: no closure for `_one`)
         if loss is None:
             loss = self._cache[key] = hb.PpoLoss(pol.act_dim, pol.min_log_std, pol.max_log_std, device, loss_value_clip=self.loss_value_clip,
                                                  loss_value_norm=self.loss_value_norm)
         return loss
-
-    def _adv_normalize(self, device) -> hb.AdvNormalize:
-        key = ("adv_normalize", str(device))
-        an = self._cache.get(key)
-        if an is None:
-            an = self._cache[key] = hb.AdvNormalize(device)
-        return an

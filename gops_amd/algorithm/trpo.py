@@ -35,11 +35,10 @@ from typing import Callable, Tuple
 import torch
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import AlgorithmBase, ApprBase, batch_to_device, cuda_device_of, grad_buffers
-from gops_amd.apprfunc.mlp import StateValue, StochaPolicy
-from gops_amd.create_pkg.create_apprfunc import create_apprfunc
-from gops_amd.utils.act_distribution import GaussDistribution
-from gops_amd.utils.common_utils import get_apprfunc_dict, make_adam
+from gops_amd.algorithm import _on_policy
+from gops_amd.algorithm._on_policy import ApproxContainer, OnPolicyBase
+from gops_amd.algorithm.base import batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.utils.common_utils import make_adam
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.utils.tensorboard_setup import tb_tags
@@ -50,44 +49,11 @@ MANDATORY = ("delta", "rtol", "atol", "damping_factor", "max_cg", "alpha", "max_
 
 
 def refusal(kwargs: dict):
-    """Why `create_alg` cannot build TRPO from these arguments, or None (POLY / LipsNet are refused before this is asked)."""
-    if kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
-        return f"TRPO runs MLP networks only (policy_func_type {kwargs.get('policy_func_type')!r}, value_func_type {kwargs.get('value_func_type')!r})"
-    dist = kwargs.get("policy_act_distribution", "default")
-    if kwargs.get("policy_func_name") != "StochaPolicy" or dist not in ("default", "GaussDistribution"):
-        return (f"TRPO takes a stochastic policy with a Gaussian action distribution (policy_func_name 'StochaPolicy', "
-                f"policy_act_distribution 'GaussDistribution' or 'default'), not {kwargs.get('policy_func_name')!r} with {dist!r}: "
-                "the Fisher metric and the surrogate kernel are that density's")
-    if kwargs.get("policy_std_type", "mlp_shared") != "mlp_shared":
-        return (f"TRPO runs the policy with policy_std_type 'mlp_shared' only (one stack for mean and log std), not "
-                f"{kwargs.get('policy_std_type')!r}: 'parameter' and 'mlp_separated' are not yet supported")
-    if kwargs.get("value_func_name") != "StateValue":
-        return f"TRPO takes a state-value function (value_func_name 'StateValue'), not {kwargs.get('value_func_name')!r}"
-    for key in ("policy", "value"):
-        if kwargs.get(f"{key}_output_activation", "linear") != "linear":
-            return (f"TRPO takes networks with a linear output layer ({key}_output_activation "
-                    f"{kwargs.get(key + '_output_activation')!r}): the HIP kernels apply no output activation")
-    if hb.dtype_id(kwargs.get("mlp_dtype")) != 0:
-        return f"TRPO is fp32 only (mlp_dtype {kwargs.get('mlp_dtype')!r}): its kernels have no half-precision path"
-    trainer = kwargs.get("trainer")
-    if trainer is not None and not trainer.startswith("on_serial"):
-        return f"TRPO runs under on_serial_trainer only: trainer {trainer!r} has not been run with its on-policy columns"
-    return None
+    """Why `create_alg` cannot build TRPO from these arguments, or None."""
+    return _on_policy.refusal("TRPO", "the Fisher metric and the surrogate kernel are that density's", kwargs)
 
 
-class ApproxContainer(ApprBase):
-    """policy, then value: construction order (and with it the RNG draws) follows trpo.py:44-50."""
-
-    def __init__(self, **kwargs):
-        super().__init__(**kwargs)
-        self.policy = create_apprfunc(**get_apprfunc_dict("policy", **kwargs))
-        self.value = create_apprfunc(**get_apprfunc_dict("value", **kwargs))
-
-    def create_action_distributions(self, logits):
-        return self.policy.get_act_dist(logits)
-
-
-class TRPO(AlgorithmBase):
+class TRPO(OnPolicyBase):
     """delta: KL constraint; rtol, atol: CG's tolerances (rtol multiplies |0|: it has no effect, as in the reference); damping_factor:
     lambda of H + lambda I; max_cg; alpha, max_search: the backtracking line search; train_v_iters, value_learning_rate: the value
     function's training; norm_adv (trpo.py:60-69)."""
@@ -105,15 +71,8 @@ class TRPO(AlgorithmBase):
         self.max_search = max_search
         self.train_v_iters = train_v_iters
         self.value_learning_rate = value_learning_rate
-        self.networks = ApproxContainer(**kwargs)
-        nets = self.networks
-        if type(nets.policy) is not StochaPolicy or nets.policy.action_distribution_cls is not GaussDistribution:
-            raise NotImplementedError(f"TRPO: policy {type(nets.policy).__name__} (MLP StochaPolicy with GaussDistribution only)")
-        if not isinstance(nets.value, StateValue):
-            raise NotImplementedError(f"TRPO: value network {type(nets.value).__name__} (MLP StateValue only)")
-        self.value_optimizer = make_adam(nets.value.parameters(), lr=value_learning_rate)
-        self.tb_info = dict()
-        self._cache, self._bufs = {}, {}
+        self._init_on_policy(kwargs)
+        self.value_optimizer = make_adam(self.networks.value.parameters(), lr=value_learning_rate)
         self._cg_graph, self._v_graph = StepGraphCache(), StepGraphCache()
         self.cg_graph_replays = 0      # CG loops that ran as a graph replay
         self.value_graph_replays = 0   # value steps that ran as a graph replay
@@ -202,20 +161,8 @@ class TRPO(AlgorithmBase):
 
     def _value_step(self, batch: dict) -> torch.Tensor:
         """One step of trpo.py:201-206, eager or as a graph replay; -> [mse_loss, mean(v)] before the step (device)."""
-        opt = self.value_optimizer
-        B = batch["obs"].shape[0]
-
-        def step(b):
-            out = self.value_gradients(b)
-            opt.step()
-            return out
-
-        def replayed():
-            opt.advance()
-            self.value_graph_replays += 1
-
-        return self._v_graph.run(self._value_signature(batch), batch, step, before_replay=opt.sync_hyper, on_replay=replayed, work=B,
-                                 on_capture_fail=opt.resync_device_state)
+        return self._adam_step(self._v_graph, self._value_signature(batch), batch, self.value_gradients, self.value_optimizer,
+                               "value_graph_replays")
 
     def value_gradients(self, batch: dict) -> torch.Tensor:
         nets = self.networks
@@ -228,10 +175,6 @@ class TRPO(AlgorithmBase):
         gw, gb = grad_buffers(nets.value)
         val.backward(o, seed_v, gw, gb)
         return stats.clone()
-
-    def _storage(self):
-        return (tuple(sorted(obj.workspace.data_ptr() for obj in self._cache.values() if hasattr(obj, "workspace"))),
-                tuple(sorted(t.data_ptr() for t in self._bufs.values())))
 
     def _cg_signature(self, B, obs):
         cg = self._cache.get("cg")
@@ -254,29 +197,6 @@ class TRPO(AlgorithmBase):
         return v[0::2], v[1::2]
 
     # ---- kernels' objects ------------------------------------------------------------------------
-    def _net(self, role: str, module, B: int, device) -> hb.MlpNet:
-        key = (role, B, str(device))
-        mlp = module.hip_mlp()
-        net = self._cache.get(key)
-        if net is None:
-            net = self._cache[key] = hb.MlpNet(mlp, B, device=device)
-        else:
-            net.mlp = mlp
-        return net
-
-    def _buf(self, name: str, shape, device) -> torch.Tensor:
-        key = (name, tuple(shape), str(device))
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = torch.empty(shape, dtype=torch.float32, device=device)
-        return t
-
-    def _one(self, key, make):
-        obj = self._cache.get(key)
-        if obj is None:
-            obj = self._cache[key] = make()
-        return obj
-
     def _surrogate(self, device) -> hb.TrpoSurrogate:
         pol = self.networks.policy
         return self._one("surrogate", lambda: hb.TrpoSurrogate(pol.act_dim, pol.min_log_std, pol.max_log_std, device))
@@ -290,9 +210,6 @@ class TRPO(AlgorithmBase):
     def _cg(self, device) -> hb.CgSolver:
         n = sum(p.numel() for p in self.networks.policy.parameters())
         return self._one("cg", lambda: hb.CgSolver(n, device, hyper=self._surrogate(device).hyper))
-
-    def _adv_normalize(self, device) -> hb.AdvNormalize:
-        return self._one("adv_normalize", lambda: hb.AdvNormalize(device))
 
     def _loss_stats(self, device) -> hb.LossStats:
         return self._one("loss_stats", lambda: hb.LossStats(device))

@@ -18,29 +18,28 @@
 // soft_q_backup_kernel: SAC's and DSAC's soft Q backup on the same tile and policy head - one or two scalar critics with their minimum,
 // or one critic with a (mean, softplus std) head and a clipped return sample.
 // What the three kernels share is stated once and inlined into each: the tile prologue (ac_tile), the hidden layers and the head
-// staging (ac_hidden, ac_stage_head, ac_head_dot), and for the two soft kernels the policy head (soft_policy_head, its scalar
+// staging (ac_hidden, ac_stage_head; ac_tile.h: ac_head_dot, chain_sum8), and for the two soft kernels the policy head (soft_policy_head, its scalar
 // arithmetic in soft_math.h), the distributional critic head (distri_head) and the row's entropy terms (soft_entropy_terms).  The
 // host side likewise: one description of the nets (AcShape), one plan, one fill of AcParams' nets, one row-count dispatch.
+// ac_tile.h holds what trpo.hip's fisher_seed_kernel takes from this scheme as well: the AC_* tile constants, ac_up4, the row-count
+// ladder (ac_choose_rows), rows_dispatch, chain_sum8 and ac_head_dot.
 // ac_critic_loss_kernel: gradient seeds, losses, mean(q) and |q - backup| of the critic regression in one launch; sums in double
-// in the fixed order of block_reduce.h (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
+// in the fixed order of block_reduce.h's grid_fold (gops_value_loss's scheme: one block up to 8192 rows, else 64 blocks' partials folded by the last one).
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
 
+#include "ac_tile.h"
 #include "block_reduce.h"
 #include "launchers.h"
 #include "soft_math.h"
 
 namespace {
 
-constexpr int AC_THREADS = 256;
-constexpr int AC_CHAINS = 8;         // partial sums per output: input k goes to chain k mod 8
 constexpr int AC_MAX_WIDTH = 256;    // hidden width (multiples of 16)
 constexpr int AC_MAX_HIDDEN = 3;     // hidden layers per net
 constexpr int AC_MAX_IN = 64;        // obs_dim + act_dim
-constexpr size_t AC_LDS_TWO = 64 * 1024;     // two workgroups per CU
-constexpr size_t AC_LDS_LIMIT = 150 * 1024;  // one (the CU has 160 KiB)
 constexpr size_t AC_WORKSPACE = 256;
 
 struct AcNet {
@@ -127,8 +126,6 @@ AcShape soft_shape(const GopsMlp& policy, const GopsMlp* q, int n_q) {
     return {{&policy, &q[0], &q[1]}, n_q, policy.sizes[0], A, 2 * A};   // extra: the log-probability terms, A doubles per row
 }
 
-inline int ac_up4(int x) { return (x + 3) & ~3; }
-
 // LDS plan for tiles of R rows within `limit` bytes; every hidden layer must get chunks of at least `min_nc` features (or the
 // whole layer).  Fills the offsets and the chunk sizes; returns the dynamic LDS bytes, 0 when it does not fit.
 size_t ac_plan(const AcShape& sh, int R, size_t limit, int min_nc, AcParams& p) {
@@ -160,15 +157,9 @@ size_t ac_plan(const AcShape& sh, int R, size_t limit, int min_nc, AcParams& p) 
     return ((size_t)p.w_off + (size_t)used) * sizeof(float);
 }
 
-// Tile rows and LDS bytes for a description: large batches take 64-row tiles (a weight chunk is staged once per 64 rows), small
-// ones 16-row tiles (more workgroups); within a tile size, the plan that leaves room for a second workgroup on the CU comes first.
+// Tile rows and LDS bytes for a description (ac_tile.h: the row-count ladder).
 size_t ac_choose(const AcShape& sh, int B, AcParams& p, int& R) {
-    for (R = B >= 16384 ? 64 : B >= 2048 ? 32 : 16; R >= 16; R >>= 1) {
-        size_t lds = ac_plan(sh, R, AC_LDS_TWO, 64, p);
-        if (lds == 0) lds = ac_plan(sh, R, AC_LDS_LIMIT, 16, p);
-        if (lds != 0) return lds;
-    }
-    return 0;
+    return ac_choose_rows(B, R, [&](int rows, size_t limit, int min_nc) { return ac_plan(sh, rows, limit, min_nc, p); });
 }
 
 // The workspace a checked description needs at batch B: 0 when no plan fits.
@@ -189,14 +180,6 @@ void ac_fill(const AcShape& sh, int B, const float* act_low, const float* act_hi
     }
     p.n_q = sh.n_q, p.B = B, p.O = sh.O, p.A = sh.A;
     for (int a = 0; a < p.A; ++a) p.act_low[a] = act_low[a], p.act_high[a] = act_high[a];
-}
-
-// kernel<R> for the tile rows a plan chose:   rows_dispatch(R, [&]<int RR>() { launch_with_lds(kernel<RR>, ...); })
-template <typename F>
-void rows_dispatch(int R, F&& launch) {
-    if (R == 64) launch.template operator()<64>();
-    else if (R == 32) launch.template operator()<32>();
-    else launch.template operator()<16>();
 }
 
 // The hidden layers of `net` on the tile's rows: input `in0` (row stride ld0), activations ping-pong between xa and xb (row stride
@@ -251,11 +234,9 @@ __device__ __forceinline__ const float* ac_hidden(const AcNet& net, const float*
                     }
                     const float* bq = wb + K * NC + 4 * fg;
                     float* yr = nxt + r * ldx + n0 + 4 * fg;
+                    const f32x4 sum = chain_sum8(c);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float sum = ((c[0][e] + c[1][e]) + (c[2][e] + c[3][e])) + ((c[4][e] + c[5][e]) + (c[6][e] + c[7][e]));
-                        yr[e] = act_fwd_t<ACT>(sum + bq[e]);
-                    }
+                    for (int e = 0; e < 4; ++e) yr[e] = act_fwd_t<ACT>(sum[e] + bq[e]);
                 }
             });
         }
@@ -264,22 +245,6 @@ __device__ __forceinline__ const float* ac_hidden(const AcNet& net, const float*
         nxt = nxt == xa ? xb : xa;
     }
     return cur;
-}
-
-// One output of a head: eight double fma chains over the K hidden activations (input k in chain k mod 8, k ascending), added pairwise.
-__device__ __forceinline__ double ac_head_dot(const float* xr, const float* wr, int K) {
-    double c[AC_CHAINS];
-#pragma unroll
-    for (int i = 0; i < AC_CHAINS; ++i) c[i] = 0.0;
-    const int K8 = K & ~(AC_CHAINS - 1);
-    for (int k = 0; k < K8; k += AC_CHAINS) {
-#pragma unroll
-        for (int i = 0; i < AC_CHAINS; ++i) c[i] = fma((double)xr[k + i], (double)wr[k + i], c[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < AC_CHAINS - 1; ++i)
-        if (K8 + i < K) c[i] = fma((double)xr[K8 + i], (double)wr[K8 + i], c[i]);
-    return ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
 }
 
 // The output layer's weights, row-major [N][K], and its biases behind them into wb (barriers on both sides).
@@ -522,13 +487,9 @@ __global__ __launch_bounds__(256) void ac_critic_loss_kernel(const float* __rest
             s[1] += (double)(weight != nullptr ? w * (d1 * d1) : d1 * d1);
         }
     }
-    block_fold<3, false>(s, red);
-    bool fin = gridDim.x == 1;
-    if (!fin) {   // the blocks' partial sums [ACL_BLOCKS][3] behind the four results, then the ticket
-        fin = last_block<3>(s, reinterpret_cast<double*>(stats + 4), 3, reinterpret_cast<unsigned*>(stats + 4 + 6 * ACL_BLOCKS), &last);
-        if (fin) block_fold<3, false>(s, red);
-    }
-    if (fin && threadIdx.x == 0) {
+    // the blocks' partial sums [ACL_BLOCKS][3] behind the four results, then the ticket
+    if (grid_fold<3>(s, red, reinterpret_cast<double*>(stats + 4), 3, reinterpret_cast<unsigned*>(stats + 4 + 6 * ACL_BLOCKS), &last) &&
+        threadIdx.x == 0) {
         const float l0 = (float)(s[0] / (double)B), l1 = (float)(s[1] / (double)B);
         stats[0] = l0;
         stats[1] = l1;

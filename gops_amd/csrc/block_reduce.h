@@ -3,6 +3,8 @@
 // wave with a butterfly (xor 32, 16, ... 1) and then the four waves as (w0 + w1) + (w2 + w3); with more than one block, every
 // block parks its totals in global memory and draws a ticket (last_block), and the block that draws the last one reads the
 // totals - block b in thread b - and folds them with the same block_fold, i.e. in block index order.  No block waits on another.
+// grid_fold is that sequence for sums and what the kernels call; block_fold and last_block stand alone only in dsact.hip's mixed
+// sum-and-minimum fold and in dw_gemm.hip's one-block sum.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,4 +52,18 @@ __device__ __forceinline__ bool last_block(double (&v)[N], double* part, int str
     for (int i = 0; i < N; ++i) v[i] = threadIdx.x < gridDim.x ? vp[stride * threadIdx.x + i] : 0.0;
     if (threadIdx.x == 0) *ticket = 0u;
     return true;
+}
+
+// The whole idiom for sums: s[i] <- the block's sums and, with more than one block, in the block that draws the last ticket the
+// grid's.  True in the threads that hold the final sums: every thread of the one block, or of the last one.  red, part / stride /
+// ticket, last: as block_fold's and last_block's (part and ticket are not touched by a grid of one block).
+template <int N>
+__device__ __forceinline__ bool grid_fold(double (&s)[N], double (*red)[4], double* part, int stride, unsigned* ticket, bool* last) {
+    block_fold<N, false>(s, red);
+    bool fin = gridDim.x == 1;
+    if (!fin) {
+        fin = last_block<N>(s, part, stride, ticket, last);
+        if (fin) block_fold<N, false>(s, red);
+    }
+    return fin;
 }

@@ -94,13 +94,7 @@ __global__ __launch_bounds__(256) void dsact_loss_kernel(const float* __restrict
             l[c] += wq * q + ws * sd;
         }
     }
-    block_fold<2, false>(l, red);
-    bool fin = gridDim.x == 1;
-    if (!fin) {
-        fin = last_block<2>(l, part, DS_PART, ticket, &last);
-        if (fin) block_fold<2, false>(l, red);
-    }
-    if (fin && threadIdx.x == 0) {
+    if (grid_fold<2>(l, red, part, DS_PART, ticket, &last) && threadIdx.x == 0) {
         const float l1 = (float)((ms[0] * ms[0] + 0.1) * l[0] / (double)B), l2 = (float)((ms[1] * ms[1] + 0.1) * l[1] / (double)B);
         stats[0] = l1 + l2, stats[9] = l1, stats[10] = l2;
     }
@@ -124,13 +118,7 @@ __global__ __launch_bounds__(256) void dsac_loss_kernel(const float* __restrict_
         double s[2] = {0.0, 0.0};   // sum q, sum std
         for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256)
             s[0] += (double)qraw[2 * (size_t)i], s[1] += softplus_d((double)qraw[2 * (size_t)i + 1]);
-        block_fold<2, false>(s, red);
-        bool fin = gridDim.x == 1;
-        if (!fin) {
-            fin = last_block<2>(s, part, DC_PART, ticket, &last);
-            if (fin) block_fold<2, false>(s, red);
-        }
-        if (fin && threadIdx.x == 0) {
+        if (grid_fold<2>(s, red, part, DC_PART, ticket, &last) && threadIdx.x == 0) {
             const float td = (float)(3.0 * (s[1] / (double)B));
             stats[1] = (float)(s[0] / (double)B), stats[2] = (float)(s[1] / (double)B), stats[3] = td;
             td_sh = td;
@@ -153,13 +141,7 @@ __global__ __launch_bounds__(256) void dsac_loss_kernel(const float* __restrict_
         seed[2 * (size_t)i + 1] = (float)((1.0 / sd - eb * eb / (v * sd)) * softplus_grad_d(raw) / (double)B);
         l[0] += bound ? e * e / (2 * v) + eb * eb / (2 * v) + log(sd) : e * e / (2 * v) + log(sd) + HALF_LOG_2PI;
     }
-    block_fold<1, false>(l, red);
-    bool fin = gridDim.x == 1;
-    if (!fin) {
-        fin = last_block<1>(l, part, DC_PART, ticket, &last);
-        if (fin) block_fold<1, false>(l, red);
-    }
-    if (fin && threadIdx.x == 0) stats[0] = (float)(l[0] / (double)B);
+    if (grid_fold<1>(l, red, part, DC_PART, ticket, &last) && threadIdx.x == 0) stats[0] = (float)(l[0] / (double)B);
 }
 static_assert(DC_RESULTS + 2 * DC_PART * DS_BLOCKS + 1 <= GOPS_DSAC_STATS_FLOATS, "stats: results, the blocks' partial sums, the ticket");
 
@@ -191,14 +173,8 @@ __global__ __launch_bounds__(256) void tanh_gauss_fwd_kernel(const TgParams p, c
         logp[i] = (float)lp;
         s[0] += lp;
     }
-    block_fold<3, false>(s, red);
-    bool fin = gridDim.x == 1;
-    if (!fin) {
-        double* part = reinterpret_cast<double*>(stats + 4);   // [DS_BLOCKS][DS_PART]
-        fin = last_block<3>(s, part, DS_PART, reinterpret_cast<unsigned*>(stats + 4 + 2 * DS_PART * DS_BLOCKS), &last);
-        if (fin) block_fold<3, false>(s, red);
-    }
-    if (fin && threadIdx.x == 0) {
+    double* part = reinterpret_cast<double*>(stats + 4);   // [DS_BLOCKS][DS_PART]
+    if (grid_fold<3>(s, red, part, DS_PART, reinterpret_cast<unsigned*>(stats + 4 + 2 * DS_PART * DS_BLOCKS), &last) && threadIdx.x == 0) {
         const double mlp = s[0] / (double)p.B, n = (double)p.B * (double)A;
         stats[0] = (float)mlp, stats[1] = (float)(s[1] / n), stats[2] = (float)(s[2] / n);
         stats[3] = (float)(-(mlp + target_entropy));   // d loss_alpha / d log_alpha (dsact.py:323-329)

@@ -121,13 +121,9 @@ __global__ __launch_bounds__(256) void batch_loss_kernel(const float* __restrict
             }
         }
     }
-    block_fold<2, false>(s, red);
-    bool fin = gridDim.x == 1;
-    if (!fin) {   // the blocks' partial sums [LOSS_BLOCKS][2] behind the two results, then the ticket
-        fin = last_block<2>(s, reinterpret_cast<double*>(stats + 2), 2, reinterpret_cast<unsigned*>(stats + 2 + 4 * LOSS_BLOCKS), &last);
-        if (fin) block_fold<2, false>(s, red);
-    }
-    if (fin && threadIdx.x == 0) {
+    // the blocks' partial sums [LOSS_BLOCKS][2] behind the two results, then the ticket
+    if (grid_fold<2>(s, red, reinterpret_cast<double*>(stats + 2), 2, reinterpret_cast<unsigned*>(stats + 2 + 4 * LOSS_BLOCKS), &last) &&
+        threadIdx.x == 0) {
         stats[0] = (float)((b != nullptr ? 1.0 : (double)sc0) * s[0] / (double)n);
         stats[1] = (float)(s[1] / (double)n);
     }

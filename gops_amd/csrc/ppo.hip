@@ -8,8 +8,9 @@
 //   folding its blocks' partial sums in the block that draws the last ticket.  Without loss_value_norm: phase 2 alone, one launch.
 // adv_normalize_kernel: (adv - mean) / (std + eps) with the unbiased std (ppo.py:123-125) on the same scheme.
 // gae_kernel: on_sampler.py:168-187 for every environment at once, one lane per environment walking T steps backwards.
-// Every value is formed in double from the fp32 inputs and rounded once where it is stored; sums are doubles in the fixed order of
-// block_reduce.h, which depends on the row count only.  Nothing waits on another workgroup.
+// Every value is formed in double from the fp32 inputs and rounded once where it is stored - the Gaussian head's terms by
+// gauss_math.h's expressions, which trpo.hip shares; sums are doubles in the fixed order of block_reduce.h's grid_fold, which
+// depends on the row count only.  Nothing waits on another workgroup.
 //
 // Ties (torch's rules, see include/gops_hip.h): min(sur1, sur2) passes the surrogate's gradient where sur1 <= sur2 - inside the clip
 // the two are the same number and clamp passes its gradient on the closed interval; max(l1, l2) passes the value's gradient where
@@ -18,7 +19,7 @@
 
 #include "block_reduce.h"
 #include "launchers.h"
-#include "soft_math.h"
+#include "gauss_math.h"
 
 namespace {
 
@@ -47,6 +48,13 @@ __device__ __forceinline__ double unbiased_std(const double (&s)[2], int n) {
     return sqrt(fmax(s[1] - s[0] * s[0] / (double)n, 0.0) / (double)(n - 1));
 }
 
+// Phase 1 of both two-phase normalisers: the grid's shifted moments of x[0 .. n); true where they are final (block_reduce.h: grid_fold).
+__device__ __forceinline__ bool grid_moments(const float* x, int n, double (&s)[2], double (*red)[4], double* part, int stride,
+                                             unsigned* ticket, bool* last) {
+    shifted_moments(x, n, s);
+    return grid_fold<2>(s, red, part, stride, ticket, last);
+}
+
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const PpoParams p, int phases, const float* __restrict__ head, const float* __restrict__ v_new,
                                                        const float* __restrict__ act, const float* __restrict__ logp_old,
                                                        const float* __restrict__ adv, const float* __restrict__ ret,
@@ -62,14 +70,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const PpoParams p, int ph
     const int M = p.M, A = p.A;
     if (phases & 1) {   // ---- 6 std(ret) over the minibatch (ppo.py:207-209) ----
         double s[2];
-        shifted_moments(ret, M, s);
-        block_fold<2, false>(s, red);
-        bool fin = gridDim.x == 1;
-        if (!fin) {
-            fin = last_block<2>(s, part, PPO_PART, ticket, &last);
-            if (fin) block_fold<2, false>(s, red);
-        }
-        if (fin && threadIdx.x == 0) {
+        if (grid_moments(ret, M, s, red, part, PPO_PART, ticket, &last) && threadIdx.x == 0) {
             const double n6 = 6.0 * unbiased_std(s, M);
             *norm_at = n6, norm_sh = n6;
         }
@@ -89,23 +90,24 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const PpoParams p, int ph
         const float* lo = logits_old + (size_t)i * 2 * A;
         double lp = 0.0, ent = 0.0, kl = 0.0;
         for (int a = 0; a < A; ++a) {
-            const double mean = (double)h[a], ls = fmin(fmax((double)h[A + a], p.min_ls), p.max_ls), sd = exp(ls);
+            const double mean = (double)h[a];
+            const GaussDim n = gauss_dim((double)h[A + a], p.min_ls, p.max_ls);
             const double d = (double)act[(size_t)i * A + a] - mean, mo = (double)lo[a], so = (double)lo[A + a];
-            lp += -(d * d) / (2 * sd * sd) - ls - HALF_LOG_2PI;
-            ent += 0.5 + HALF_LOG_2PI + ls;
-            kl += ls - log(so) + (so * so + (mo - mean) * (mo - mean)) / (2 * sd * sd) - 0.5;
+            lp += gauss_logp_term(d, n.ls, n.sd);
+            ent += 0.5 + HALF_LOG_2PI + n.ls;
+            kl += gauss_kl_term(log(so), so, mo, n.ls, n.sd, mean);   // KL(N(old) || N(new))
         }
         const double ratio = exp(lp - (double)logp_old[i]), ad = (double)adv[i];
         const double sur1 = ratio * ad, sur2 = fmin(fmax(ratio, 1.0 - clip), 1.0 + clip) * ad;
         const double g_lp = sur1 <= sur2 ? -inv_m * ad * ratio : 0.0;   // d loss_total / d logp_new of the row
         for (int a = 0; a < A; ++a) {
-            const double raw = (double)h[A + a];
-            const bool inside = raw >= p.min_ls && raw <= p.max_ls;   // (the clamp passes its gradient on the closed interval, as torch's)
-            const double mean = (double)h[a], sd = exp(fmin(fmax(raw, p.min_ls), p.max_ls)), iv = 1.0 / (sd * sd);
+            const GaussDim n = gauss_dim((double)h[A + a], p.min_ls, p.max_ls);
+            const double mean = (double)h[a], iv = 1.0 / (n.sd * n.sd);
             const double d = (double)act[(size_t)i * A + a] - mean, mo = (double)lo[a], so = (double)lo[A + a];
             const double q = (so * so + (mo - mean) * (mo - mean)) * iv;
-            seed_head[(size_t)i * 2 * A + a] = (float)(g_lp * d * iv + c_kl * inv_m * (mean - mo) * iv);
-            seed_head[(size_t)i * 2 * A + A + a] = inside ? (float)(g_lp * (d * d * iv - 1.0) + c_kl * inv_m * (1.0 - q) - c_ent * inv_m) : 0.f;
+            const GaussSeed g = gauss_logp_seed(g_lp, d, iv, n.inside);
+            seed_head[(size_t)i * 2 * A + a] = (float)(g.mean + c_kl * inv_m * (mean - mo) * iv);
+            seed_head[(size_t)i * 2 * A + A + a] = n.inside ? (float)(g.ls + c_kl * inv_m * (1.0 - q) - c_ent * inv_m) : 0.f;
         }
         const double v = (double)v_new[i], r = (double)ret[i], vo = (double)val_old[i];
         const double l1 = (v - r) * (v - r);
@@ -119,13 +121,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const PpoParams p, int ph
         seed_v[i] = live ? (float)(2.0 * c_v * inv_m * (v - r) / norm) : 0.f;
         s[0] += fmin(sur1, sur2), s[1] += vl, s[2] += ent, s[3] += kl, s[4] += fabs(ratio - 1.0) > clip ? 1.0 : 0.0;
     }
-    block_fold<5, false>(s, red);
-    bool fin = gridDim.x == 1;
-    if (!fin) {
-        fin = last_block<5>(s, part, PPO_PART, ticket, &last);
-        if (fin) block_fold<5, false>(s, red);
-    }
-    if (fin && threadIdx.x == 0) {
+    if (grid_fold<5>(s, red, part, PPO_PART, ticket, &last) && threadIdx.x == 0) {
         const double l_sur = -s[0] * inv_m, l_v = s[1] * inv_m / norm, ent = s[2] * inv_m, kl = s[3] * inv_m;
         stats[0] = (float)(l_sur + c_kl * kl + c_v * l_v - c_ent * ent);
         stats[1] = (float)l_sur, stats[2] = (float)l_v, stats[3] = (float)ent, stats[4] = (float)kl, stats[5] = (float)(s[4] * inv_m);
@@ -150,14 +146,7 @@ __global__ __launch_bounds__(256) void adv_normalize_kernel(const float* x, int 
     if (phases & 1) {
         double s[2];
         const double x0 = (double)x[0];
-        shifted_moments(x, n, s);
-        block_fold<2, false>(s, red);
-        bool fin = gridDim.x == 1;
-        if (!fin) {
-            fin = last_block<2>(s, part, AN_PART, ticket, &last);
-            if (fin) block_fold<2, false>(s, red);
-        }
-        if (fin && threadIdx.x == 0) {
+        if (grid_moments(x, n, s, red, part, AN_PART, ticket, &last) && threadIdx.x == 0) {
             const double mean = x0 + s[0] / (double)n, sd = unbiased_std(s, n);
             mom_at[0] = mean, mom_at[1] = sd, mom_sh[0] = mean, mom_sh[1] = sd;
             stats[0] = (float)mean, stats[1] = (float)sd;

@@ -3,8 +3,7 @@
 // the results go; every value below is formed by the same expression in all of them, so they return the same bits.
 // (dsact.hip's tanh_gauss_fwd_kernel writes tanh_gauss_dim's expressions out in place - see there - and must follow any change here.)
 #pragma once
-
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;   // log(sqrt(2 pi)): the constant of a normal density's logarithm
+#include "gauss_math.h"   // HALF_LOG_2PI
 
 __device__ __forceinline__ double softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }   // (torch's threshold)
 __device__ __forceinline__ double softplus_grad_d(double x) { return x > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-x)); }

@@ -1,5 +1,8 @@
 // The stages of a TRPO update (gops/algorithm/trpo.py) that the MLP launches do not cover.
 //
+// What this file shares with others is stated there: the Gaussian head's double arithmetic in gauss_math.h (with ppo.hip), the tile
+// constants, row-count ladder, rows_dispatch, chain_sum8 and ac_head_dot in ac_tile.h (with actor_critic.hip), the sums in
+// block_reduce.h's grid_fold.
 // fisher_seed_kernel: the Gauss-Newton form of the KL Hessian-vector product needs J v, the directional derivative of the policy's
 //   RAW head (mean, raw log std) along a parameter tangent v = (V_j, c_j).  A workgroup of 256 threads owns a tile of R batch rows
 //   (actor_critic.hip's scheme) and carries, per layer, the primal row h and ONE tangent row t:
@@ -19,16 +22,12 @@
 
 #include <algorithm>
 
+#include "ac_tile.h"
 #include "block_reduce.h"
+#include "gauss_math.h"
 #include "launchers.h"
-#include "soft_math.h"
 
 namespace {
-
-constexpr int FS_THREADS = 256;
-constexpr int FS_CHAINS = 8;
-constexpr size_t FS_LDS_TWO = 64 * 1024;     // two workgroups per CU
-constexpr size_t FS_LDS_LIMIT = 150 * 1024;  // one (the CU has 160 KiB)
 
 struct FsParams {
     int nl, act, B, O, A;
@@ -44,16 +43,14 @@ struct FsParams {
     float* seed;
 };
 
-inline int fs_up4(int x) { return (x + 3) & ~3; }
-
 // LDS plan for tiles of R rows within `limit` bytes (actor_critic.hip's ac_plan with four activation planes and two weight chunks).
 size_t fs_plan(const GopsMlp& m, int R, size_t limit, int min_nc, FsParams& p) {
     int maxh = 0;
     for (int j = 1; j < m.n_layers; ++j) maxh = std::max(maxh, (int)m.sizes[j]);
     p.ld0 = m.sizes[0] | 1;
     p.ldx = maxh | 1;
-    const int plane = fs_up4(R * p.ldx);
-    p.xa_off = fs_up4(R * p.ld0);
+    const int plane = ac_up4(R * p.ldx);
+    p.xa_off = ac_up4(R * p.ld0);
     p.xb_off = p.xa_off + plane;
     p.ta_off = p.xb_off + plane;
     p.tb_off = p.ta_off + plane;
@@ -75,12 +72,7 @@ size_t fs_plan(const GopsMlp& m, int R, size_t limit, int min_nc, FsParams& p) {
 }
 
 size_t fs_choose(const GopsMlp& m, int B, FsParams& p, int& R) {
-    for (R = B >= 16384 ? 64 : B >= 2048 ? 32 : 16; R >= 16; R >>= 1) {
-        size_t lds = fs_plan(m, R, FS_LDS_TWO, 64, p);
-        if (lds == 0) lds = fs_plan(m, R, FS_LDS_LIMIT, 16, p);
-        if (lds != 0) return lds;
-    }
-    return 0;
+    return ac_choose_rows(B, R, [&](int rows, size_t limit, int min_nc) { return fs_plan(m, rows, limit, min_nc, p); });
 }
 
 // h = act(z), d = act'(z) as torch evaluates them (common.h: act3_t, fp32 libm - erf-form GELU, expm1f for ELU / SELU).  The fast
@@ -93,13 +85,13 @@ __device__ __forceinline__ void fs_act(float z, float& h, float& d) {
 }
 
 template <int R>
-__global__ __launch_bounds__(FS_THREADS) void fisher_seed_kernel(const FsParams p) {
+__global__ __launch_bounds__(AC_THREADS) void fisher_seed_kernel(const FsParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int G = FS_THREADS / R;
+    constexpr int G = AC_THREADS / R;
     const int tid = threadIdx.x, r = tid % R, g = tid / R;
     const int b0 = blockIdx.x * R, nvalid = min(R, p.B - b0), O = p.O, A = p.A, ldx = p.ldx;
     float *in0 = lds, *xa = lds + p.xa_off, *xb = lds + p.xb_off, *ta = lds + p.ta_off, *tb = lds + p.tb_off, *wb = lds + p.w_off;
-    for (int idx = tid; idx < R * O; idx += FS_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
+    for (int idx = tid; idx < R * O; idx += AC_THREADS) {   // rows beyond the batch: zeros (evaluated, never stored)
         const int m = idx / O, k = idx - m * O;
         in0[m * p.ld0 + k] = m < nvalid ? p.x[(size_t)(b0 + m) * O + k] : 0.f;
     }
@@ -117,12 +109,12 @@ __global__ __launch_bounds__(FS_THREADS) void fisher_seed_kernel(const FsParams 
         for (int n0 = 0; n0 < N; n0 += NC) {
             const int nc = min(NC, N - n0);
             __syncthreads();   // the previous readers of wb are done; what the previous layer (or the staging above) wrote is visible
-            for (int idx = tid; idx < nc * K; idx += FS_THREADS) {
+            for (int idx = tid; idx < nc * K; idx += AC_THREADS) {
                 const int k = idx / nc, nn = idx - k * nc;
                 wb[k * NC + nn] = Wg[(size_t)(n0 + nn) * K + k];
                 vb[k * NC + nn] = Vg[(size_t)(n0 + nn) * K + k];
             }
-            for (int idx = tid; idx < nc; idx += FS_THREADS) {
+            for (int idx = tid; idx < nc; idx += AC_THREADS) {
                 wb[K * NC + idx] = p.Bv[j][n0 + idx];
                 vb[K * NC + idx] = p.Cv[j][n0 + idx];
             }
@@ -133,10 +125,10 @@ __global__ __launch_bounds__(FS_THREADS) void fisher_seed_kernel(const FsParams 
                 for (int fg = g; fg < (nc >> 2); fg += G) {
                     const float* wq = wb + 4 * fg;
                     const float* vq = vb + 4 * fg;
-                    f32x4 c[FS_CHAINS], cu[FS_CHAINS], cv[FS_CHAINS];
+                    f32x4 c[AC_CHAINS], cu[AC_CHAINS], cv[AC_CHAINS];
 #pragma unroll
-                    for (int i = 0; i < FS_CHAINS; ++i) c[i] = cu[i] = cv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const int K8 = K & ~(FS_CHAINS - 1);
+                    for (int i = 0; i < AC_CHAINS; ++i) c[i] = cu[i] = cv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const int K8 = K & ~(AC_CHAINS - 1);
                     auto term = [&](int k, int i) {
                         const float x = xr[k];
                         const f32x4 w = *reinterpret_cast<const f32x4*>(wq + k * NC);
@@ -152,23 +144,22 @@ __global__ __launch_bounds__(FS_THREADS) void fisher_seed_kernel(const FsParams 
                             cv[i][e] = fmaf(x, v[e], cv[i][e]);
                         }
                     };
-                    for (int k = 0; k < K8; k += FS_CHAINS) {
+                    for (int k = 0; k < K8; k += AC_CHAINS) {
 #pragma unroll
-                        for (int i = 0; i < FS_CHAINS; ++i) term(k + i, i);
+                        for (int i = 0; i < AC_CHAINS; ++i) term(k + i, i);
                     }
 #pragma unroll
-                    for (int i = 0; i < FS_CHAINS - 1; ++i)
+                    for (int i = 0; i < AC_CHAINS - 1; ++i)
                         if (K8 + i < K) term(K8 + i, i);
                     const float* bq = wb + K * NC + 4 * fg;
                     const float* cq = vb + K * NC + 4 * fg;
                     float* yr = nxt + r * ldx + n0 + 4 * fg;
                     float* ur = nxtt + r * ldx + n0 + 4 * fg;
+                    const f32x4 wh = chain_sum8(c), wt = chain_sum8(cu), vh = chain_sum8(cv);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float z = ((c[0][e] + c[1][e]) + (c[2][e] + c[3][e])) + ((c[4][e] + c[5][e]) + (c[6][e] + c[7][e])) + bq[e];
-                        const float wt = ((cu[0][e] + cu[1][e]) + (cu[2][e] + cu[3][e])) + ((cu[4][e] + cu[5][e]) + (cu[6][e] + cu[7][e]));
-                        const float vh = ((cv[0][e] + cv[1][e]) + (cv[2][e] + cv[3][e])) + ((cv[4][e] + cv[5][e]) + (cv[6][e] + cv[7][e]));
-                        const float u = (wt + vh) + cq[e];
+                        const float z = wh[e] + bq[e];
+                        const float u = (wt[e] + vh[e]) + cq[e];
                         float h, d;
                         fs_act<ACT>(z, h, d);
                         yr[e] = h;
@@ -184,29 +175,19 @@ __global__ __launch_bounds__(FS_THREADS) void fisher_seed_kernel(const FsParams 
     // ---- head: W_L [2A][K] with b_L behind it, V_L and c_L behind those; one thread per (row, action dimension) ----
     const int L = p.nl - 1, K = p.dims[L], N = 2 * A;
     __syncthreads();
-    for (int idx = tid; idx < N * K; idx += FS_THREADS) wb[idx] = p.W[L][idx], wb[N * K + N + idx] = p.V[L][idx];
-    for (int idx = tid; idx < N; idx += FS_THREADS) wb[N * K + idx] = p.Bv[L][idx], wb[2 * N * K + N + idx] = p.Cv[L][idx];
+    for (int idx = tid; idx < N * K; idx += AC_THREADS) wb[idx] = p.W[L][idx], wb[N * K + N + idx] = p.V[L][idx];
+    for (int idx = tid; idx < N; idx += AC_THREADS) wb[N * K + idx] = p.Bv[L][idx], wb[2 * N * K + N + idx] = p.Cv[L][idx];
     __syncthreads();
     if (g < A && r < nvalid) {
         const float *xr = cur + r * ldx, *tr = curt + r * ldx, *vb = wb + N * K + N;
-        auto dot = [&](const float* a, const float* w) {   // eight double fma chains, input k in chain k mod 8, added pairwise
-            double c[FS_CHAINS];
-#pragma unroll
-            for (int i = 0; i < FS_CHAINS; ++i) c[i] = 0.0;
-            for (int k = 0; k < K; k += FS_CHAINS) {   // (hidden widths are multiples of 16)
-#pragma unroll
-                for (int i = 0; i < FS_CHAINS; ++i) c[i] = fma((double)a[k + i], (double)w[k + i], c[i]);
-            }
-            return ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7]));
-        };
-        const double raw = dot(xr, wb + (A + g) * K) + (double)wb[N * K + A + g];
-        const double t_mean = (dot(tr, wb + g * K) + dot(xr, vb + g * K)) + (double)vb[N * K + g];
-        const double t_raw = (dot(tr, wb + (A + g) * K) + dot(xr, vb + (A + g) * K)) + (double)vb[N * K + A + g];
-        const bool inside = raw >= p.min_ls && raw <= p.max_ls;   // (the clamp passes its gradient on the closed interval, as torch's)
-        const double sd = exp(fmin(fmax(raw, p.min_ls), p.max_ls)), inv_b = 1.0 / (double)p.B;
+        const double raw = ac_head_dot(xr, wb + (A + g) * K, K) + (double)wb[N * K + A + g];
+        const double t_mean = (ac_head_dot(tr, wb + g * K, K) + ac_head_dot(xr, vb + g * K, K)) + (double)vb[N * K + g];
+        const double t_raw = (ac_head_dot(tr, wb + (A + g) * K, K) + ac_head_dot(xr, vb + (A + g) * K, K)) + (double)vb[N * K + A + g];
+        const GaussDim n = gauss_dim(raw, p.min_ls, p.max_ls);
+        const double inv_b = 1.0 / (double)p.B;
         float* out = p.seed + (size_t)(b0 + r) * N;
-        out[g] = (float)(t_mean / (sd * sd) * inv_b);
-        out[A + g] = inside ? (float)(2.0 * t_raw * inv_b) : 0.f;
+        out[g] = (float)(t_mean / (n.sd * n.sd) * inv_b);
+        out[A + g] = n.inside ? (float)(2.0 * t_raw * inv_b) : 0.f;
     }
 }
 
@@ -232,32 +213,25 @@ __global__ __launch_bounds__(256) void trpo_surrogate_kernel(int M, int A, doubl
         double lpn = 0.0, lpo = 0.0, kl = 0.0;
         for (int a = 0; a < A; ++a) {
             const double x = (double)act[(size_t)i * A + a];
-            const double mn = (double)hn[a], lsn = fmin(fmax((double)hn[A + a], min_ls), max_ls), sn = exp(lsn), dn = x - mn;
-            const double mo = (double)ho[a], lso = fmin(fmax((double)ho[A + a], min_ls), max_ls), so = exp(lso), dl = x - mo;
-            lpn += -(dn * dn) / (2 * sn * sn) - lsn - HALF_LOG_2PI;
-            lpo += -(dl * dl) / (2 * so * so) - lso - HALF_LOG_2PI;
-            kl += lso - lsn + (sn * sn + (mn - mo) * (mn - mo)) / (2 * so * so) - 0.5;   // KL(N(new) || N(old))
+            const double mn = (double)hn[a], mo = (double)ho[a];
+            const GaussDim n = gauss_dim((double)hn[A + a], min_ls, max_ls), o = gauss_dim((double)ho[A + a], min_ls, max_ls);
+            lpn += gauss_logp_term(x - mn, n.ls, n.sd);
+            lpo += gauss_logp_term(x - mo, o.ls, o.sd);
+            kl += gauss_kl_term(n.ls, n.sd, mn, o.ls, o.sd, mo);   // KL(N(new) || N(old))
         }
         const double ratio = exp(lpn - lpo), ad = (double)adv[i];
         if (seed != nullptr) {
             const double g_lp = inv_m * ad * ratio;   // d surrogate / d logp_new of the row
             for (int a = 0; a < A; ++a) {
-                const double raw = (double)hn[A + a];
-                const bool inside = raw >= min_ls && raw <= max_ls;
-                const double sd = exp(fmin(fmax(raw, min_ls), max_ls)), iv = 1.0 / (sd * sd), d = (double)act[(size_t)i * A + a] - (double)hn[a];
-                seed[(size_t)i * 2 * A + a] = (float)(g_lp * d * iv);
-                seed[(size_t)i * 2 * A + A + a] = inside ? (float)(g_lp * (d * d * iv - 1.0)) : 0.f;
+                const GaussDim n = gauss_dim((double)hn[A + a], min_ls, max_ls);
+                const GaussSeed g = gauss_logp_seed(g_lp, (double)act[(size_t)i * A + a] - (double)hn[a], 1.0 / (n.sd * n.sd), n.inside);
+                seed[(size_t)i * 2 * A + a] = (float)g.mean;
+                seed[(size_t)i * 2 * A + A + a] = (float)g.ls;
             }
         }
         s[0] += ratio * ad, s[1] += kl;
     }
-    block_fold<2, false>(s, red);
-    bool fin = gridDim.x == 1;
-    if (!fin) {
-        fin = last_block<2>(s, part, TS_PART, ticket, &last);
-        if (fin) block_fold<2, false>(s, red);
-    }
-    if (fin && threadIdx.x == 0) {
+    if (grid_fold<2>(s, red, part, TS_PART, ticket, &last) && threadIdx.x == 0) {
         const float sur = (float)(s[0] * inv_m), kl = (float)(s[1] * inv_m);   // (the reference compares its fp32 values)
         stats[0] = sur, stats[1] = kl;
         reinterpret_cast<int*>(stats)[TS_VERDICT_AT] = sur > 0.f && kl < hyper[0] ? 1 : 0;
@@ -273,11 +247,7 @@ static_assert(sizeof(GopsCgState) == GOPS_CG_STATE_FLOATS * sizeof(float) && siz
 
 // The sums of the block's (or, in the block that draws the last ticket, the grid's) `s`; true where they are final.
 __device__ __forceinline__ bool cg_fold(double (&s)[2], GopsCgState* st, double (*red)[4], bool* last) {
-    block_fold<2, false>(s, red);
-    if (gridDim.x == 1) return true;
-    if (!last_block<2>(s, st->part, 2, reinterpret_cast<unsigned*>(&st->ticket), last)) return false;
-    block_fold<2, false>(s, red);
-    return true;
+    return grid_fold<2>(s, red, st->part, 2, reinterpret_cast<unsigned*>(&st->ticket), last);
 }
 
 // x = 0, r = p = g, r_dot = r.r, done = all(|r| <= atol)   (the reference's first Ax(x0) is a product with zero: not formed)
@@ -388,10 +358,8 @@ int gauss_fisher_seed(const GopsMlp& m, const GopsMlpGrad& tangent, int B, const
     for (int j = 0; j <= p.nl; ++j) p.dims[j] = m.sizes[j];
     for (int j = 0; j < p.nl; ++j) p.W[j] = m.weight[j], p.Bv[j] = m.bias[j], p.V[j] = tangent.weight[j], p.Cv[j] = tangent.bias[j];
     p.min_ls = min_ls, p.max_ls = max_ls, p.x = x, p.seed = seed;
-    const dim3 grid((unsigned)((B + R - 1) / R)), threads(FS_THREADS);
-    if (R == 64) launch_with_lds(fisher_seed_kernel<64>, grid, threads, lds, s, p);
-    else if (R == 32) launch_with_lds(fisher_seed_kernel<32>, grid, threads, lds, s, p);
-    else launch_with_lds(fisher_seed_kernel<16>, grid, threads, lds, s, p);
+    const dim3 grid((unsigned)((B + R - 1) / R)), threads(AC_THREADS);
+    rows_dispatch(R, [&]<int RR>() { launch_with_lds(fisher_seed_kernel<RR>, grid, threads, lds, s, p); });
     return (int)hipGetLastError();
 }
 

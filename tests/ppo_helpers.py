@@ -6,6 +6,7 @@ import torch
 
 import ac_helpers as ah
 from ac_helpers import _collect, _float_copies
+from gauss_helpers import MAX_LS, MIN_LS, gauss, logits_of, raw_log_std
 
 from gops_amd.utils.act_distribution import GaussDistribution
 
@@ -17,7 +18,6 @@ ONE_STEP = ["ppo_pend_relu", "ppo_lqs4a2_gelu", "ppo_pend_value_norm", "ppo_pend
 LOCAL_UPDATE = "ppo_pend_local_update"
 TERMS = ("loss_total", "loss_surrogate", "loss_value", "loss_entropy", "approximate_kl", "clip_fraction")
 COLUMNS = ("obs", "act", "logp", "adv", "ret", "val", "logits")
-MIN_LS, MAX_LS = -3.0, -0.5
 MIN_ROWS, MARGIN = 4, 1e-3
 
 
@@ -41,9 +41,8 @@ def restate_ppo_loss(head, v, act, logp_old, adv, ret, val_old, logits_old, *, c
                      loss_value_clip, loss_value_norm):
     """ppo.py:178-226 from the policy's RAW head [M, 2A] and the value output [M], in the tensors' dtype on their device.
     -> dict(terms [6 tensors, TERMS' order], ratio, raw log std, v_new - val_old, l1, l2)."""
-    A = act.shape[1]
-    mean, raw = head[:, :A], head[:, A:]
-    new = GaussDistribution(torch.cat((mean, torch.clamp(raw, min_ls, max_ls).exp()), dim=-1))
+    raw = head[:, act.shape[1]:]
+    new = GaussDistribution(logits_of(head, min_ls, max_ls))
     old = GaussDistribution(logits_old)
     ratio = torch.exp(new.log_prob(act) - logp_old)
     sur1, sur2 = ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv
@@ -119,15 +118,12 @@ def synthetic_minibatch(M, A, seed=0):
     g = torch.Generator().manual_seed(1000 * A + seed + M)
     f64 = torch.float64
     mean = 0.5 * torch.randn(M, A, generator=g, dtype=f64)
-    raw = -1.75 + 1.6 * torch.randn(M, A, generator=g, dtype=f64)
-    for b in (MIN_LS, MAX_LS):
-        raw = torch.where((raw - b).abs() < 0.01, raw + 0.03, raw)
-    head = torch.cat((mean, raw), dim=-1).float()
-    std = torch.clamp(head[:, A:].double(), MIN_LS, MAX_LS).exp()
+    head = torch.cat((mean, raw_log_std(M, A, g)), dim=-1).float()
+    std = gauss(head.double())[1]
     act = (head[:, :A].double() + std * torch.randn(M, A, generator=g, dtype=f64)).float()
     logits = torch.cat((head[:, :A].double() + 0.1 * std * torch.randn(M, A, generator=g, dtype=f64),
                         std * torch.exp(0.2 * torch.randn(M, A, generator=g, dtype=f64))), dim=-1).float()
-    logp_new = GaussDistribution(torch.cat((head[:, :A].double(), std), dim=-1)).log_prob(act.double())
+    logp_new = GaussDistribution(logits_of(head.double())).log_prob(act.double())
     cell = torch.arange(M) % 6
     lo, hi = torch.tensor([0.55, 0.85, 1.25], dtype=f64)[cell % 3], torch.tensor([0.75, 1.15, 1.5], dtype=f64)[cell % 3]
     logp = (logp_new - torch.log(lo + (hi - lo) * torch.rand(M, generator=g, dtype=f64))).float()

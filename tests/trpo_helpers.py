@@ -11,6 +11,7 @@ import torch
 
 import ac_helpers as ah
 from conftest import GOLDEN
+from gauss_helpers import MAX_LS, MIN_LS, gauss, kl_new_old, log_prob, raw_log_std   # noqa: F401  (the tests reach them as th.*)
 
 # create_alg's arguments for TRPO beyond ac_helpers' common dictionary (registered next to the other families', for alg_kwargs);
 # the nine mandatory ones travel in a fixture's `ctor`
@@ -19,7 +20,6 @@ ah.FAMILY.setdefault("TRPO", dict(policy_func_name="StochaPolicy", policy_act_di
 CTOR = dict(delta=0.01, rtol=1e-5, atol=1e-8, damping_factor=0.1, max_cg=10, alpha=0.8, max_search=10, train_v_iters=5,
             value_learning_rate=1e-3, trainer="on_serial_trainer")
 FIXTURES = ["trpo_pend_relu", "trpo_lqs4a2_gelu", "trpo_pend_backtrack", "trpo_pend_all_rejected", "trpo_pend_no_norm"]
-MIN_LS, MAX_LS = -3.0, -0.5
 EPS = 1e-8
 QUANTITIES = ("g", "x", "step", "policy")
 
@@ -74,22 +74,6 @@ def head_fn(seq):
     def f(params, obs):
         return torch.func.functional_call(seq, dict(zip(names, params)), (obs,))
     return f
-
-
-def gauss(head, min_ls=MIN_LS, max_ls=MAX_LS):
-    mean, raw = torch.chunk(head, 2, dim=-1)
-    return mean, torch.clamp(raw, min_ls, max_ls).exp()
-
-
-def log_prob(head, act, min_ls=MIN_LS, max_ls=MAX_LS):
-    mean, std = gauss(head, min_ls, max_ls)
-    return torch.distributions.Normal(mean, std).log_prob(act).sum(-1)
-
-
-def kl_new_old(head, head_old, min_ls=MIN_LS, max_ls=MAX_LS):
-    """mean_i KL(pi(head_i) || pi(head_old_i)): `pi.kl_divergence(pi_old).mean()` of trpo.py:148 with torch's kl_normal_normal."""
-    new, old = (torch.distributions.Normal(*gauss(h, min_ls, max_ls)) for h in (head, head_old))
-    return torch.distributions.kl_divergence(new, old).sum(-1).mean()
 
 
 def metric_seed(seq, obs, tangent, min_ls=MIN_LS, max_ls=MAX_LS):
@@ -232,17 +216,10 @@ def synthetic_heads(M, A, seed=0):
     """head_new, head_old (raw, log stds on both sides of the clamp and at least 0.01 away from it), act, adv in fp32 on the host."""
     g = torch.Generator().manual_seed(1000 * A + seed + M)
     f64 = torch.float64
-
-    def raw_of():
-        raw = -1.75 + 1.6 * torch.randn(M, A, generator=g, dtype=f64)
-        for b in (MIN_LS, MAX_LS):
-            raw = torch.where((raw - b).abs() < 0.01, raw + 0.03, raw)
-        return raw
-
     mean = 0.5 * torch.randn(M, A, generator=g, dtype=f64)
-    head_new = torch.cat((mean, raw_of()), dim=-1).float()
-    head_old = torch.cat((mean + 0.05 * torch.randn(M, A, generator=g, dtype=f64), raw_of()), dim=-1).float()
-    std = torch.clamp(head_old[:, A:].double(), MIN_LS, MAX_LS).exp()
+    head_new = torch.cat((mean, raw_log_std(M, A, g)), dim=-1).float()
+    head_old = torch.cat((mean + 0.05 * torch.randn(M, A, generator=g, dtype=f64), raw_log_std(M, A, g)), dim=-1).float()
+    std = gauss(head_old.double())[1]
     act = (head_old[:, :A].double() + std * torch.randn(M, A, generator=g, dtype=f64)).float()
     adv = torch.randn(M, generator=g, dtype=f64).float()
     return dict(head_new=head_new, head_old=head_old, act=act, adv=adv)
