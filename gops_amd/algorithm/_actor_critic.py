@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import AlgorithmBase, batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.algorithm.base import AlgorithmBase, batch_to_device, cuda_device_of, grad_buffers, install_grads
 from gops_amd.apprfunc.mlp import ActionValue, DetermPolicy
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
@@ -104,8 +104,7 @@ class ActorCriticBase(AlgorithmBase):
 
     def remote_update(self, update_info: dict):
         for n in self._q_names + ("policy",):
-            for p, grad in zip(getattr(self.networks, n).parameters(), update_info[f"{n}_grad"]):
-                p.grad = grad
+            install_grads(getattr(self.networks, n), update_info[f"{n}_grad"])
         self._update(update_info["iteration"])
         self._step_schedulers()
 

@@ -1,0 +1,99 @@
+"""What the model-based algorithms share on the host (FHADP and its constrained variants, FHADP2, INFADP / MAC, SPIL, MPG): the
+device batch of a model rollout, the env description, the cache of kernel objects, the -1/B seed of a mean loss, the test for "the
+plain algorithm", the PrecisionGuard's plumbing, torch's Polyak step and what a POLY approximator must refuse.
+"""
+import torch
+
+from gops_amd import hip_backend as hb
+from gops_amd.algorithm.base import _INFO_KEYS, AlgorithmBase, PrecisionGuard, batch_to_device, cuda_device_of
+
+
+def polyak_foreach_(target, online, tau):
+    """p_targ <- (1 - tau) p_targ + tau p over two parameter lists, as two torch foreach launches (INFADP on the device has
+    hb.PolyakUpdater instead: other rounding)."""
+    torch._foreach_mul_(target, 1 - tau)
+    torch._foreach_add_(target, online, alpha=tau)
+
+
+# POLY approximators (apprfunc/poly.py): the POLY rollout steps the env models whose observation is the state (csrc/rollout_poly.hip)
+def poly_env_check(envmodel, alg: str):
+    if getattr(envmodel.unwrapped, "hip_kind", None) not in hb.STATE_OBS_ENV_KINDS:
+        raise NotImplementedError(f"{alg} with an apprfunc of type POLY: env model {type(envmodel.unwrapped).__name__} is outside "
+                                  "the POLY rollout (pyth_lq, pyth_idpendulum, gym cartpoleconti / pendulum only)")
+
+
+def poly_alg_check(alg, time_input: bool):
+    """What an algorithm with a POLY policy must refuse at construction (FHADP: a FiniteHorizonPolicy, whose weight carries the
+    virtual_t column; INFADP: a DetermPolicy; both: fp32 only - the POLY kernels have no half-precision path)."""
+    name = type(alg).__name__
+    if str(getattr(alg, "mlp_dtype", "fp32") or "fp32").lower() not in ("fp32", "f32", "float32"):
+        raise NotImplementedError(f"{name} with an apprfunc of type POLY: mlp_dtype {alg.mlp_dtype!r} - the POLY path is fp32 only")
+    pol = alg.networks.policy
+    if bool(getattr(pol, "_time_input", False)) != time_input:
+        raise NotImplementedError(f"{name} with a POLY {type(pol).__name__}: the POLY rollout of {name} takes a "
+                                  f"{'FiniteHorizonPolicy' if time_input else 'DetermPolicy'}")
+
+
+class ModelBasedBase(AlgorithmBase):
+    def __init__(self, index, **kwargs):
+        super().__init__(index, **kwargs)
+        self.tb_info = dict()
+        self._cache = {}   # key -> kernel object (hb.Rollout, hb.ValueNet, hb.MlpNet ...), see `_cached`
+
+    def _model_batch(self, data: dict) -> dict:
+        """obs, done and the model's info of `data` on the device, with the appended reference points in strict mode."""
+        return self._attach_reference_points(data, batch_to_device(data, cuda_device_of(self.networks), ("obs", "done") + _INFO_KEYS))
+
+    def _hip_env(self):
+        """The kernels' description of the env model, with the policy's action limits."""
+        policy = self.networks.policy
+        return self.envmodel.hip_env(policy.act_low_lim.cpu().numpy(), policy.act_high_lim.cpu().numpy())
+
+    def _cached(self, key, make, rebind=None):
+        """The kernel object under `key`: `make()` on first use, afterwards the same object after `rebind(obj)` (the networks'
+        current tensors: `hip_mlp()` follows a `load_state_dict` / `.to()`)."""
+        obj = self._cache.get(key)
+        if obj is None:
+            obj = self._cache[key] = make()
+        elif rebind is not None:
+            rebind(obj)
+        return obj
+
+    def _grad_v(self, B, device):
+        """d(-mean v_pi)/d v_pi = -1/B for every trajectory (cached: it only depends on B)."""
+        gv = getattr(self, "_gv", None)
+        if gv is None or gv.shape[0] != B or gv.device != device:
+            gv = self._gv = torch.full((B,), -1.0 / B, dtype=torch.float32, device=device)
+        return gv
+
+    def _is_plain(self, cls) -> bool:
+        """Is this `cls` itself as far as the kernels go?  A subclass that brings its own `_gradient_kernels` or `_update` (the
+        constrained FHADP variants) stays off the paths built for the plain algorithm: fused update, POLY, LipsNet, overlap."""
+        mine = type(self)
+        return mine._gradient_kernels is cls._gradient_kernels and getattr(mine, "_update", None) is getattr(cls, "_update", None)
+
+    # ---- PrecisionGuard (algorithm/base.py) -----------------------------------------------------------------------------------
+    _forced_flags = None   # (set for the duration of a precision check)
+
+    def _variant_flags(self, mode=None) -> int:
+        """Variant flags of the launches right now; `mode`: the key of the guard where `precision_guard` is a dict of them."""
+        if self._forced_flags is not None:
+            return self._forced_flags
+        return (self.precision_guard if mode is None else self.precision_guard[mode]).flags()
+
+    def _guard_check(self, guard, modules, gradient, net):
+        """Every `guard.interval` gradients `gradient()` - which fills `net`'s flat gradient - runs with the launch's own kernels and
+        with the exact-fp32 rollout kernels; beyond the threshold the guard's launches stay on those."""
+        if self.mlp_dtype != "fp32" or not PrecisionGuard.applies_to(*modules, env_kind=getattr(self.envmodel.unwrapped, "hip_kind", None)):
+            return
+        if not guard.due():
+            return
+
+        def flat_gradient(flags):
+            self._forced_flags = flags
+            try:
+                gradient()
+            finally:
+                self._forced_flags = None
+            return net._flat_grad.clone()
+        guard.check(flat_gradient)

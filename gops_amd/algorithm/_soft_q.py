@@ -21,7 +21,7 @@ import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm._actor_critic import FUSED_MAX_WIDTH, ActorCriticBase
-from gops_amd.algorithm.base import batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.algorithm.base import batch_to_device, cuda_device_of, grad_buffers, install_grads
 from gops_amd.apprfunc.mlp import ActionValueDistri, StochaPolicy
 from gops_amd.utils.act_distribution import TanhGaussDistribution
 from gops_amd.utils.hip_graph import StepGraphCache
@@ -120,8 +120,7 @@ class SoftQBase(ActorCriticBase):
     def remote_update(self, update_info: dict):
         nets = self.networks
         for n in self._q_names + ("policy",):
-            for p, grad in zip(getattr(nets, n).parameters(), update_info[f"{n}_grad"]):
-                p.grad = grad
+            install_grads(getattr(nets, n), update_info[f"{n}_grad"])
         if self.auto_alpha:
             nets.log_alpha.grad = update_info["log_alpha_grad"]
         self._update(update_info["iteration"])

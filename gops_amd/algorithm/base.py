@@ -84,6 +84,9 @@ class AlgorithmBase(metaclass=ABCMeta):
             if pipe is None:
                 return batch
             pts = pipe.collect(data, self._rollout_horizon(), device)
+        elif tuple(pts.shape) != (batch["obs"].shape[0], self._rollout_horizon(), 4):   # (the kernels index it by these extents)
+            raise ValueError(f"ref_appended has shape {tuple(pts.shape)}; the rollout of this batch reads "
+                             f"{(batch['obs'].shape[0], self._rollout_horizon(), 4)}")
         batch["ref_appended"] = pts.to(device=device, dtype=torch.float32).contiguous()
         return batch
 
@@ -270,29 +273,16 @@ def is_poly(module) -> bool:
     return bool(getattr(module, "is_poly", False))
 
 
-# env models whose observation is the state: the ones the POLY rollout steps (csrc/rollout_poly.hip)
-def poly_env_check(envmodel, alg: str):
-    from gops_amd import hip_backend as hb
-    kind = getattr(envmodel.unwrapped, "hip_kind", None)
-    if kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM):
-        raise NotImplementedError(f"{alg} with an apprfunc of type POLY: env model {type(envmodel.unwrapped).__name__} is outside "
-                                  "the POLY rollout (pyth_lq, pyth_idpendulum, gym cartpoleconti / pendulum only)")
+def install_grads(module, grads):
+    """Gradients from outside (`remote_update`) become the parameters' `.grad`, in `parameters()` order."""
+    for p, grad in zip(module.parameters(), grads):
+        p.grad = grad
 
 
-def poly_alg_check(alg, time_input: bool):
-    """What an algorithm with a POLY policy must refuse at construction (FHADP: a FiniteHorizonPolicy, whose weight carries the
-    virtual_t column; INFADP: a DetermPolicy; both: fp32 only - the POLY kernels have no half-precision path)."""
-    name = type(alg).__name__
-    if str(getattr(alg, "mlp_dtype", "fp32") or "fp32").lower() not in ("fp32", "f32", "float32"):
-        raise NotImplementedError(f"{name} with an apprfunc of type POLY: mlp_dtype {alg.mlp_dtype!r} - the POLY path is fp32 only")
-    pol = alg.networks.policy
-    if bool(getattr(pol, "_time_input", False)) != time_input:
-        raise NotImplementedError(f"{name} with a POLY {type(pol).__name__}: the POLY rollout of {name} takes a "
-                                  f"{'FiniteHorizonPolicy' if time_input else 'DetermPolicy'}")
-
-
-def poly_grad_buffers(module):
-    """`grad_buffers` for a POLY net: ([weight grad], [bias grad or None]), views into ONE flat buffer in `parameters()` order."""
+def _flat_grads(module):
+    """The `.grad` tensors of one network as views into ONE flat buffer (allocated here on first use, in `parameters()` order), so
+    that the data-parallel trainer can all-reduce a network's gradient in place without flattening / copying back
+    (`trainer/grad_sync.py`).  Gradients installed from outside (`remote_update`) are kept as they are."""
     params = list(module.parameters())
     if any(p.grad is None or not p.grad.is_contiguous() for p in params):
         flat = torch.zeros(sum(p.numel() for p in params), dtype=params[0].dtype, device=params[0].device)
@@ -301,6 +291,11 @@ def poly_grad_buffers(module):
             p.grad = flat[off:off + p.numel()].view_as(p)
             off += p.numel()
         module._flat_grad = flat
+
+
+def poly_grad_buffers(module):
+    """`grad_buffers` for a POLY net: ([weight grad], [bias grad or None])."""
+    _flat_grads(module)
     lin = module.linear_layers()[0]
     return [lin.weight.grad], [None if lin.bias is None else lin.bias.grad]
 
@@ -310,20 +305,8 @@ def net_grad_buffers(module):
 
 
 def grad_buffers(module):
-    """Per-Linear-layer (weight grads, bias grads).  The `.grad` tensors of one network are views into
-    ONE flat buffer (allocated here on first use, in `parameters()` order), so that the data-parallel
-    trainer can all-reduce a network's gradient in place without flattening / copying back
-    (`trainer/grad_sync.py`).  Gradients installed from outside (`remote_update`) are kept as they are."""
-    params = list(module.parameters())
-    flat = getattr(module, "_flat_grad", None)
-    if any(p.grad is None or not p.grad.is_contiguous() for p in params):
-        total = sum(p.numel() for p in params)
-        flat = torch.zeros(total, dtype=params[0].dtype, device=params[0].device)
-        off = 0
-        for p in params:
-            p.grad = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        module._flat_grad = flat
+    """Per-Linear-layer (weight grads, bias grads): views into the network's flat gradient buffer (`_flat_grads`)."""
+    _flat_grads(module)
     gw, gb = [], []
     for layer in module.linear_layers():
         gw.append(layer.weight.grad)

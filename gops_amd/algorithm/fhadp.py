@@ -12,12 +12,12 @@ import os
 import time
 from typing import Tuple
 
-import torch
 from gops_amd.utils.common_utils import make_adam
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import (_INFO_KEYS, AlgorithmBase, ApprBase, PrecisionGuard, batch_to_device, cuda_device_of,
-                                     grad_buffers, is_poly, net_grad_buffers, poly_alg_check, poly_env_check, poly_grad_buffers)
+from gops_amd.algorithm._model_based import ModelBasedBase, poly_alg_check, poly_env_check
+from gops_amd.algorithm.base import (ApprBase, PrecisionGuard, grad_buffers, install_grads, is_poly, net_grad_buffers,
+                                     poly_grad_buffers)
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
@@ -27,7 +27,7 @@ from gops_amd.utils.tensorboard_setup import tb_tags
 
 
 class ApproxContainer(ApprBase):
-    """Approximate function container for FHADP: one policy network + Adam (+ lr scheduler)."""
+    """Approximate function container for FHADP and FHADP2: one policy network + Adam (+ lr scheduler)."""
 
     def __init__(self, *, policy_learning_rate: float, **kwargs):
         super().__init__(**kwargs)
@@ -40,7 +40,7 @@ class ApproxContainer(ApprBase):
         return self.policy.get_act_dist(logits)
 
 
-class FHADP(AlgorithmBase):
+class FHADP(ModelBasedBase):
     """:param int pre_horizon: envmodel predict horizon.  :param float gamma: discount factor."""
 
     def __init__(self, *, pre_horizon: int, gamma: float = 1.0, index: int = 0, **kwargs):
@@ -51,15 +51,15 @@ class FHADP(AlgorithmBase):
         self.gamma = gamma
         # arithmetic of the MLP contractions: "fp32" (exact, the 1e-4 parity path) or "fp16" (half-precision MFMA)
         self.mlp_dtype = kwargs.get("mlp_dtype", "fp32")
-        self.tb_info = dict()
-        self._rollouts = {}
+        self._rollouts = self._cache   # (rollout workspaces only: `_signature` reads every value's)
         # measured rule for leaving the plane-split forward (algorithm/base.py PrecisionGuard); fp16 launches state their own tolerance
         self.precision_guard = PrecisionGuard(kwargs.get("precision_check_interval"), kwargs.get("precision_threshold"))
         self._update_graph, self._grad_graph, self._grad_graph_b = StepGraphCache(), StepGraphCache(), StepGraphCache()
         # POLY policy (apprfunc/poly.py): the one-lane-per-trajectory rollout (hb.PolyRollout) of the plain algorithm only
         self._poly = is_poly(self.networks.policy)
+        self._plain = self._is_plain(FHADP)   # (the constrained variants bring their own gradient kernels)
         if self._poly:
-            if type(self)._gradient_kernels is not FHADP._gradient_kernels:
+            if not self._plain:
                 raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type POLY: only plain FHADP runs the POLY rollout")
             poly_env_check(self.envmodel, type(self).__name__)
             poly_alg_check(self, time_input=True)
@@ -78,7 +78,7 @@ class FHADP(AlgorithmBase):
 
         # the constrained variants bring their own gradient kernels; the plain ones fold loss mean and Adam step into the backward's
         # last launch (ABI v12, gops_rollout_backward_update: two launches less per update)
-        fuse = type(self)._gradient_kernels is FHADP._gradient_kernels and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0"   # (host-side A/B knob)
+        fuse = self._plain and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0"   # (host-side A/B knob)
         fuse = fuse and not self._poly   # (POLY: gradient, loss mean and Adam step as three launches)
 
         def update(b):
@@ -114,8 +114,7 @@ class FHADP(AlgorithmBase):
         net_grad_buffers(self.networks.policy)   # (allocates the flat gradient buffer on first use)
         grads = [p._grad for p in self.networks.policy.parameters()]
         info = {"grad": grads}
-        plain = type(self)._gradient_kernels is FHADP._gradient_kernels   # (the constrained variants bring their own gradient kernels)
-        if reducer is not None and reducer.overlap_enabled() and len(grads) >= 4 and plain:
+        if reducer is not None and reducer.overlap_enabled() and len(grads) >= 4 and self._plain:
             sig = self._signature(batch)
             loss = self._grad_graph.run(("a",) + sig, batch, lambda b: self._gradient_kernels(b, phase="a"), work=work)
             try:
@@ -134,8 +133,7 @@ class FHADP(AlgorithmBase):
         return self.tb_info, info
 
     def _remote_update(self, update_info):
-        for p, grad in zip(self.networks.policy.parameters(), update_info["grad"]):
-            p.grad = grad
+        install_grads(self.networks.policy, update_info["grad"])
         opt = self.networks.policy_optimizer
         opt.grad_scale = float(update_info.get("_grad_scale", 1.0))
         opt.step()
@@ -143,43 +141,22 @@ class FHADP(AlgorithmBase):
 
     # ------------------------------------------------------------------------------------------
     def _rollout_for(self, batch: int, device) -> hb.Rollout:
-        policy = self.networks.policy
         flags = self._variant_flags()
         key = (batch, self.pre_horizon, float(self.gamma), str(device), hb.dtype_id(self.mlp_dtype), flags)
-        ro = self._rollouts.get(key)
-        mlp = policy.hip_mlp()
-        if ro is None:
-            env = self.envmodel.hip_env(policy.act_low_lim.cpu().numpy(), policy.act_high_lim.cpu().numpy())
-            cls = hb.PolyRollout if self._poly else hb.Rollout
-            ro = cls(env, mlp, batch=batch, horizon=self.pre_horizon, gamma=self.gamma,
-                     finite_horizon=True, need_grad=True, device=device, dtype=self.mlp_dtype, variant_flags=flags)
-            # one live workspace per kernel variant of the current shape (shapes rarely change between updates)
-            self._rollouts = {k: r for k, r in self._rollouts.items() if k[:5] == key[:5]}
-            self._rollouts[key] = ro
-        else:
-            ro.set_policy(mlp)
-        return ro
+        mlp = self.networks.policy.hip_mlp()
 
-    def _variant_flags(self) -> int:
-        forced = getattr(self, "_forced_flags", None)   # (set for the duration of a precision check)
-        return self.precision_guard.flags() if forced is None else forced
+        def make():
+            # one live workspace per kernel variant of the current shape (shapes rarely change between updates)
+            for k in [k for k in self._cache if k[:5] != key[:5]]:
+                del self._cache[k]
+            return (hb.PolyRollout if self._poly else hb.Rollout)(
+                self._hip_env(), mlp, batch=batch, horizon=self.pre_horizon, gamma=self.gamma, finite_horizon=True,
+                need_grad=True, device=device, dtype=self.mlp_dtype, variant_flags=flags)
+        return self._cached(key, make, lambda ro: ro.set_policy(mlp))
 
     def _precision_check(self, batch):
-        """PrecisionGuard (algorithm/base.py): every `interval` gradients the gradient of `batch` is formed with the launch's own
-        kernels and with the exact-fp32 rollout kernels; beyond the threshold the algorithm stays on those."""
-        if self.mlp_dtype != "fp32" or not PrecisionGuard.applies_to(self.networks.policy, env_kind=getattr(self.envmodel.unwrapped, "hip_kind", None)):
-            return
-        if not self.precision_guard.due():
-            return
-
-        def flat_gradient(flags):
-            self._forced_flags = flags
-            try:
-                self._gradient_kernels(batch)
-            finally:
-                self._forced_flags = None
-            return self.networks.policy._flat_grad.clone()
-        self.precision_guard.check(flat_gradient)
+        policy = self.networks.policy
+        self._guard_check(self.precision_guard, (policy,), lambda: self._gradient_kernels(batch), policy)
 
     def _fill_tb(self, out, lazy=False):
         """`out` is what `_gradient_kernels` returned - here the pair [-mean(v_pi), mean(v_pi)] of `gops_mean_loss`; entry 0 is the
@@ -192,7 +169,7 @@ class FHADP(AlgorithmBase):
         self.tb_info[tb_tags["alg_time"]] = (time.time() - self._t0) * 1000  # ms
 
     def _device_batch(self, data):
-        return self._attach_reference_points(data, batch_to_device(data, cuda_device_of(self.networks), ("obs", "done") + _INFO_KEYS))
+        return self._model_batch(data)
 
     def _extra_signature(self):
         """Host-side values a subclass bakes into the captured kernels' inputs (penalty coefficients ...)."""
@@ -276,10 +253,3 @@ class FHADP(AlgorithmBase):
         if sync:
             self._log(loss_policy)
         return loss_policy
-
-    def _grad_v(self, B, device):
-        """d(-mean v_pi)/d v_pi = -1/B for every trajectory (cached: it only depends on B)."""
-        gv = getattr(self, "_gv", None)
-        if gv is None or gv.shape[0] != B or gv.device != device:
-            gv = self._gv = torch.full((B,), -1.0 / B, dtype=torch.float32, device=device)
-        return gv

@@ -13,33 +13,16 @@ __all__ = ["FHADP2"]
 import time
 from typing import Tuple
 
-import torch
-
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import (_INFO_KEYS, AlgorithmBase, ApprBase, batch_to_device, cuda_device_of,
-                                     grad_buffers)
-from gops_amd.create_pkg.create_apprfunc import create_apprfunc
+from gops_amd.algorithm._model_based import ModelBasedBase
+from gops_amd.algorithm.base import grad_buffers, install_grads
+from gops_amd.algorithm.fhadp import ApproxContainer  # noqa: F401  (same container; create_alg looks it up here)
 from gops_amd.create_pkg.create_env_model import create_env_model
-from gops_amd.utils.common_utils import get_apprfunc_dict, make_adam
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.utils.tensorboard_setup import tb_tags
 
 
-class ApproxContainer(ApprBase):
-    """Approximate function container for FHADP2: one full-horizon policy + Adam (+ lr scheduler)."""
-
-    def __init__(self, *, policy_learning_rate: float, **kwargs):
-        super().__init__(**kwargs)
-        self.policy = create_apprfunc(**get_apprfunc_dict("policy", **kwargs))
-        self.policy_optimizer = make_adam(self.policy.parameters(), lr=policy_learning_rate)
-        self.optimizer_dict = {"policy": self.policy_optimizer}
-        self.init_scheduler(**kwargs)
-
-    def create_action_distributions(self, logits):
-        return self.policy.get_act_dist(logits)
-
-
-class FHADP2(AlgorithmBase):
+class FHADP2(ModelBasedBase):
     """:param int pre_horizon: length of the emitted action sequence = model rollout horizon."""
 
     def __init__(self, *, pre_horizon: int, index: int = 0, **kwargs):
@@ -48,8 +31,7 @@ class FHADP2(AlgorithmBase):
         self.envmodel = create_env_model(**kwargs, pre_horizon=pre_horizon)
         self.forward_step = pre_horizon
         self.gamma = 1.0
-        self.tb_info = dict()
-        self._rollouts = {}
+        self._rollouts = self._cache
 
     @property
     def adjustable_parameters(self) -> Tuple[str]:
@@ -65,38 +47,25 @@ class FHADP2(AlgorithmBase):
         return self.tb_info, {"grad": [p._grad for p in self.networks.policy.parameters()]}
 
     def _remote_update(self, update_info):
-        for p, grad in zip(self.networks.policy.parameters(), update_info["grad"]):
-            p.grad = grad
+        install_grads(self.networks.policy, update_info["grad"])
         self.networks.policy_optimizer.step()
 
     def _rollout_for(self, batch: int, device) -> hb.Rollout:
         policy = self.networks.policy
         if self.forward_step != policy.pre_horizon:
             raise RuntimeError("FHADP2: forward_step must equal the policy's pre_horizon (its output width)")
-        key = (batch, self.forward_step, float(self.gamma), str(device))
-        ro = self._rollouts.get(key)
-        if ro is None:
-            env = self.envmodel.hip_env(policy.act_low_lim.cpu().numpy(), policy.act_high_lim.cpu().numpy())
-            ro = hb.Rollout(env, None, batch=batch, horizon=self.forward_step, gamma=self.gamma,
-                            finite_horizon=False, need_grad=True, device=device)
-            self._rollouts[key] = ro
-        return ro
+        return self._cached((batch, self.forward_step, float(self.gamma), str(device)), lambda: hb.Rollout(
+            self._hip_env(), None, batch=batch, horizon=self.forward_step, gamma=self.gamma, finite_horizon=False, need_grad=True,
+            device=device))
 
     def _mlp_for(self, batch: int, device) -> hb.MlpNet:
         mlp = self.networks.policy.hip_mlp()
-        key = ("mlp", batch, str(device))
-        net = self._rollouts.get(key)
-        if net is None:
-            net = self._rollouts[key] = hb.MlpNet(mlp, batch, device=device)
-        else:
-            net.mlp = mlp
-        return net
+        return self._cached(("mlp", batch, str(device)), lambda: hb.MlpNet(mlp, batch, device=device), lambda net: setattr(net, "mlp", mlp))
 
     def _compute_gradient(self, data):
         t0 = time.time()
-        device = cuda_device_of(self.networks)
-        batch = self._attach_reference_points(data, batch_to_device(data, device, ("obs", "done") + _INFO_KEYS))
-        B = batch["obs"].shape[0]
+        batch = self._model_batch(data)
+        B, device = batch["obs"].shape[0], batch["obs"].device
         policy = self.networks.policy
         # ONE evaluation of the full-horizon policy emits all H actions (fhadp2.py:100-104): hidden stack on the rollout
         # tiles, wide output layer on its own kernels (gops_mlp_forward); no autograd graph, no rocBLAS
@@ -105,8 +74,7 @@ class FHADP2(AlgorithmBase):
         ro = self._rollout_for(B, device)
         v_pi = ro.forward(batch, head_pre=pre)["v_pi"]
         loss_policy = -v_pi.mean()
-        grad_v = torch.full((B,), -1.0 / B, dtype=torch.float32, device=device)
-        g_pre = ro.backward_open_loop(grad_v)                    # d(loss)/d(head outputs) [B, H, A]
+        g_pre = ro.backward_open_loop(self._grad_v(B, device))   # d(loss)/d(head outputs) [B, H, A]
         gw, gb = grad_buffers(policy)
         net.backward(batch["obs"], g_pre.view(B, -1), gw, gb)    # through the MLP into the parameters' .grad
         self.tb_info[tb_tags["loss_actor"]] = scalar(loss_policy)

@@ -16,8 +16,8 @@ import torch
 from gops_amd.utils.common_utils import make_adam
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import (_INFO_KEYS, AlgorithmBase, ApprBase, PrecisionGuard, batch_to_device, cuda_device_of,
-                                     grad_buffers, is_poly, poly_alg_check, poly_env_check, poly_grad_buffers)
+from gops_amd.algorithm._model_based import ModelBasedBase, poly_alg_check, poly_env_check, polyak_foreach_
+from gops_amd.algorithm.base import ApprBase, PrecisionGuard, install_grads, is_poly, net_grad_buffers
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
@@ -53,7 +53,7 @@ class ApproxContainer(ApprBase):
         return self.policy.get_act_dist(logits)
 
 
-class INFADP(AlgorithmBase):
+class INFADP(ModelBasedBase):
     """forward_step: model rollout length; gamma; tau: Polyak factor; pev_step / pim_step:
     alternation period of evaluation and improvement."""
 
@@ -69,8 +69,6 @@ class INFADP(AlgorithmBase):
         # arithmetic of the MLP contractions: "fp32" (exact, the 1e-4 parity path) or "fp16" (half-precision
         # MFMA, BASELINE.json configs[4])
         self.mlp_dtype = kwargs.get("mlp_dtype", "fp32")
-        self.tb_info = dict()
-        self._cache = {}
         self._graphs = {}
         self._polyak = {}   # net name -> hb.PolyakUpdater
         # measured rule for leaving the plane-split forward (algorithm/base.py PrecisionGuard), one per trained network
@@ -78,11 +76,12 @@ class INFADP(AlgorithmBase):
         self._bufs = {}     # persistent device scratch: loss gradient, loss scalars (read them before the next update of the same mode)
         # POLY policy AND value (apprfunc/poly.py): the one-lane-per-trajectory rollout (hb.PolyRollout) and hb.PolyValueNet
         self._poly = is_poly(self.networks.policy)
+        self._plain = self._is_plain(INFADP)   # (a subclass with gradient kernels or an update of its own stays off the paths below)
         if self._poly != is_poly(self.networks.v):
             raise NotImplementedError("INFADP: a POLY policy needs a POLY value and the reverse (the rollout's tail value is "
                                       "evaluated by the policy's kernel)")
         if self._poly:
-            if type(self)._gradient_kernels is not INFADP._gradient_kernels:
+            if not self._plain:
                 raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type POLY: only plain INFADP runs the POLY rollout")
             poly_env_check(self.envmodel, type(self).__name__)
             poly_alg_check(self, time_input=False)
@@ -90,14 +89,13 @@ class INFADP(AlgorithmBase):
         self._lips = bool(getattr(self.networks.policy, "is_lipsnet", False))
         if self._lips:
             name = type(self).__name__
-            if type(self)._gradient_kernels is not INFADP._gradient_kernels or type(self)._update is not INFADP._update:
+            if not self._plain:
                 raise NotImplementedError(f"{name} with a LipsNet policy: only plain INFADP composes the LipsNet kernels with the model rollout")
             if self._poly or getattr(self.networks.v, "is_lipsnet", False) or not hasattr(self.networks.v, "hip_mlp"):
                 raise NotImplementedError(f"{name} with a LipsNet policy needs an MLP StateValue")
             if hb.dtype_id(self.mlp_dtype) != 0:
                 raise NotImplementedError(f"{name} with a LipsNet policy: mlp_dtype {self.mlp_dtype!r} - the LipsNet path is fp32 only")
-            kind = getattr(self.envmodel.unwrapped, "hip_kind", None)
-            if kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM):   # (gops_rollout_backward_open_loop_adj's env kinds)
+            if getattr(self.envmodel.unwrapped, "hip_kind", None) not in hb.STATE_OBS_ENV_KINDS:   # (gops_rollout_backward_open_loop_adj's env kinds)
                 raise NotImplementedError(f"{name} with a LipsNet policy: env model {type(self.envmodel.unwrapped).__name__} is outside the "
                                           "path (models whose observation is the state: pyth_lq, pyth_idpendulum, gym cartpoleconti / pendulum)")
 
@@ -118,15 +116,14 @@ class INFADP(AlgorithmBase):
         # gradient + Adam + Polyak of the iteration's mode as one HIP graph when the update is launch-bound
         # (replay batches of the shipped examples are 64-256 samples); eager kernels otherwise
         start_time = time.time()
-        batch = self._attach_reference_points(data, batch_to_device(data, cuda_device_of(self.networks), ("obs", "done") + _INFO_KEYS))
+        batch = self._model_batch(data)
         mode = self._mode(iteration)
         opt = self.networks.optimizer_dict[mode]
         self._precision_check(mode, batch)
 
         # The plain algorithm: Adam step, Polyak step of the target (and, for PIM, the loss mean) ride on the backward's last launch
         # (ABI v12, gops_rollout_backward_update / gops_value_backward_update)
-        fuse = (type(self)._gradient_kernels is INFADP._gradient_kernels and type(self)._update is INFADP._update
-                and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0")   # (host-side A/B knob)
+        fuse = self._plain and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0"   # (host-side A/B knob)
         fuse = fuse and not self._poly   # (POLY: Adam and Polyak steps as launches of their own)
         fuse = fuse and not self._lips   # (LipsNet: two optimizer groups, more tensors than one fused table)
 
@@ -159,7 +156,7 @@ class INFADP(AlgorithmBase):
         # Data-parallel path: no host sync between the backward sweep and the gradient all-reduce - the loss
         # scalars stay on the device in tb_info and are read at log time.
         start_time = time.time()
-        batch = self._attach_reference_points(data, batch_to_device(data, cuda_device_of(self.networks), ("obs", "done") + _INFO_KEYS))
+        batch = self._model_batch(data)
         mode = self._mode(iteration)
         self._precision_check(mode, batch)
         scalars = self._gradient_kernels(mode, batch)
@@ -174,8 +171,7 @@ class INFADP(AlgorithmBase):
     def remote_update(self, update_info: dict):
         names = [k for k in update_info if not k.startswith("_")]
         for net_name in names:
-            for p, grad in zip(self.networks.net_dict[net_name].parameters(), update_info[net_name]):
-                p.grad = grad
+            install_grads(self.networks.net_dict[net_name], update_info[net_name])
             self.networks.optimizer_dict[net_name].grad_scale = float(update_info.get("_grad_scale", 1.0))
         self._update(names)
         for net_name in names:   # a later local_update on this object must not inherit the 1/N
@@ -192,8 +188,7 @@ class INFADP(AlgorithmBase):
                 online = list(self.networks.net_dict[net_name].parameters())
                 target = list(self.networks.target_net_dict[net_name].parameters())
                 if not online[0].is_cuda:
-                    torch._foreach_mul_(target, 1 - tau)
-                    torch._foreach_add_(target, online, alpha=tau)
+                    polyak_foreach_(target, online, tau)
                     continue
                 pk = self._polyak.get(net_name)
                 if pk is None or not pk.matches(target, online):
@@ -206,54 +201,23 @@ class INFADP(AlgorithmBase):
         flags = self._variant_flags("policy" if need_grad else "v")   # (PEV's gradient-free backup belongs to the value update)
         key = (batch, self.forward_step, float(self.gamma), str(device), need_grad, hb.dtype_id(self.mlp_dtype), flags)
         pol, vt = nets.policy.hip_mlp(), nets.v_target.hip_mlp()
-        ro = self._cache.get(key)
-        if ro is None:
-            env = self.envmodel.hip_env(nets.policy.act_low_lim.cpu().numpy(), nets.policy.act_high_lim.cpu().numpy())
-            cls = hb.PolyRollout if self._poly else hb.Rollout
-            ro = cls(env, pol, batch=batch, horizon=self.forward_step, gamma=self.gamma,
-                     finite_horizon=False, need_grad=need_grad, value=vt, device=device, dtype=self.mlp_dtype, variant_flags=flags)
-            self._cache[key] = ro
-        else:
-            ro.set_policy(pol, vt)
-        return ro
+        return self._cached(key, lambda: (hb.PolyRollout if self._poly else hb.Rollout)(
+            self._hip_env(), pol, batch=batch, horizon=self.forward_step, gamma=self.gamma, finite_horizon=False, need_grad=need_grad,
+            value=vt, device=device, dtype=self.mlp_dtype, variant_flags=flags), lambda ro: ro.set_policy(pol, vt))
 
     def _value_for(self, batch: int, device) -> hb.ValueNet:
         flags = self._variant_flags("v")
         key = ("v", batch, str(device), hb.dtype_id(self.mlp_dtype), flags)
         mlp = self.networks.v.hip_mlp(self.mlp_dtype, variant_flags=flags)
-        vn = self._cache.get(key)
-        if vn is None:
-            vn = self._cache[key] = (hb.PolyValueNet(mlp, batch, self.envmodel.hip_env().obs_dim, device=device) if self._poly
-                                     else hb.ValueNet(mlp, batch, device=device))
-        elif self._poly:
-            vn.set_net(mlp)
-        else:
-            vn.mlp = mlp
-        return vn
-
-    def _variant_flags(self, mode: str) -> int:
-        forced = getattr(self, "_forced_flags", None)   # (set for the duration of a precision check)
-        return self.precision_guard[mode].flags() if forced is None else forced
+        if self._poly:
+            return self._cached(key, lambda: hb.PolyValueNet(mlp, batch, self.envmodel.hip_env().obs_dim, device=device),
+                                lambda vn: vn.set_net(mlp))
+        return self._cached(key, lambda: hb.ValueNet(mlp, batch, device=device), lambda vn: setattr(vn, "mlp", mlp))
 
     def _precision_check(self, mode: str, batch):
-        """PrecisionGuard (algorithm/base.py) of the network this iteration trains: every `interval` of ITS gradients the gradient of
-        `batch` is formed with the launch's own kernels and with the exact-fp32 rollout kernels; beyond the threshold that network's
-        launches stay on those."""
-        guard = self.precision_guard[mode]
-        if self.mlp_dtype != "fp32" or not PrecisionGuard.applies_to(self.networks.policy, self.networks.v,
-                                                                      env_kind=getattr(self.envmodel.unwrapped, "hip_kind", None)):
-            return
-        if not guard.due():
-            return
-
-        def flat_gradient(flags):
-            self._forced_flags = flags
-            try:
-                self._gradient_kernels(mode, batch)
-            finally:
-                self._forced_flags = None
-            return self.networks.net_dict[mode]._flat_grad.clone()
-        guard.check(flat_gradient)
+        """The guard of the network this iteration trains, on ITS gradients."""
+        nets = self.networks
+        self._guard_check(self.precision_guard[mode], (nets.policy, nets.v), lambda: self._gradient_kernels(mode, batch), nets.net_dict[mode])
 
     def _mode(self, iteration) -> str:
         return "v" if iteration % (self.pev_step + self.pim_step) < self.pev_step else "policy"
@@ -273,7 +237,7 @@ class INFADP(AlgorithmBase):
             # loss_v, mean V and d(loss_v)/dV = (2 / B)(V - backup) in one launch (they were six torch passes)
             gdiff = self._scratch("gdiff", B, device)
             scalars = self._loss_stats("v", device).value_loss(v, backup, gdiff)
-            gw, gb = poly_grad_buffers(self.networks.v) if self._poly else grad_buffers(self.networks.v)
+            gw, gb = net_grad_buffers(self.networks.v)
             if fused_opt is not None:   # -> (scalars, whether Adam + Polyak were part of the backward call)
                 fa, pk = self._fused_parts("v", fused_opt)
                 if fa is None:
@@ -287,7 +251,7 @@ class INFADP(AlgorithmBase):
         # PIM: loss = -mean(sum_t gamma^t r_t + (~d) gamma^n V_target(o_n)), grads into the policy
         ro = self._rollout_for(B, device, need_grad=True)
         v_pi = ro.forward(batch)["v_pi"]
-        gw, gb = poly_grad_buffers(self.networks.policy) if self._poly else grad_buffers(self.networks.policy)
+        gw, gb = net_grad_buffers(self.networks.policy)
         if fused_opt is not None:   # -> (scalars, whether Adam + Polyak were part of the backward call)
             fa, pk = self._fused_parts("policy", fused_opt)
             stats = self._loss_stats("policy", device)
@@ -306,18 +270,15 @@ class INFADP(AlgorithmBase):
 
     # ---- LipsNet policy: policy -> wrapper chain on the action -> open-loop one-step rollout -> target value -----------------------
     def _lips_parts(self, B, device, need_grad):
-        key = ("lips", B, str(device), need_grad, float(self.gamma))
-        parts = self._cache.get(key)
-        if parts is None:
-            nets = self.networks
-            env = self.envmodel.hip_env(nets.policy.act_low_lim.cpu().numpy(), nets.policy.act_high_lim.cpu().numpy())
+        def make():
+            env = self._hip_env()
             ro = hb.Rollout(env, None, batch=B, horizon=1, gamma=self.gamma, finite_horizon=False, need_grad=need_grad,
                             device=device, raw_actions=True)
             A = env.act_dim
             t = lambda v: torch.tensor([float(v[i]) for i in range(A)], dtype=torch.float32, device=device)   # noqa: E731
-            parts = self._cache[key] = dict(ro=ro, lp=hb.LipsPolicy(nets.policy, B, device=device), wrap=tuple(
+            return dict(ro=ro, lp=hb.LipsPolicy(self.networks.policy, B, device=device), wrap=tuple(
                 t(v) for v in (env.min_action, env.max_action, env.act_low, env.act_high)))
-        return parts
+        return self._cached(("lips", B, str(device), need_grad, float(self.gamma)), make)
 
     def _lips_return(self, batch, need_grad):
         """r + gamma (1 - done') V_target(obs') of one wrapped model step under the LipsNet policy -> (value [B], what the backward
@@ -342,14 +303,8 @@ class INFADP(AlgorithmBase):
         return value, dict(parts=parts, vt=vt, res=res, tail=tail, pass_through=pass_through, K=K)
 
     def _lips_vt(self, B, device, need_grad):
-        key = ("lips_vt", B, str(device), need_grad)
         mlp = self.networks.v_target.hip_mlp()
-        net = self._cache.get(key)
-        if net is None:
-            net = self._cache[key] = hb.MlpNet(mlp, B, device=device)
-        else:
-            net.mlp = mlp
-        return net
+        return self._cached(("lips_vt", B, str(device), need_grad), lambda: hb.MlpNet(mlp, B, device=device), lambda net: setattr(net, "mlp", mlp))
 
     def _lips_improvement(self, batch):
         """PIM: loss = -mean(value); the adjoint walks back through the target value's input, the model step and the action
@@ -389,12 +344,6 @@ class INFADP(AlgorithmBase):
             st = self._bufs[("stats", mode)] = hb.LossStats(device)
         return st
 
-    def _grad_v(self, B, device):
-        gv = getattr(self, "_gv", None)
-        if gv is None or gv.shape[0] != B or gv.device != device:
-            gv = self._gv = torch.full((B,), -1.0 / B, dtype=torch.float32, device=device)
-        return gv
-
     def _log(self, mode: str, scalars: torch.Tensor, start_time: float):
         # (LazyScalar: read back on first use; GOPS_EAGER_LOG=1: host sync here, as in the reference)
         if mode == "v":
@@ -406,7 +355,7 @@ class INFADP(AlgorithmBase):
 
     def _compute_gradient(self, data, iteration):
         start_time = time.time()
-        batch = self._attach_reference_points(data, batch_to_device(data, cuda_device_of(self.networks), ("obs", "done") + _INFO_KEYS))
+        batch = self._model_batch(data)
         mode = self._mode(iteration)
         self._log(mode, self._gradient_kernels(mode, batch), start_time)
         return [mode]

@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import AlgorithmBase, ApprBase, batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.algorithm._model_based import ModelBasedBase, polyak_foreach_
+from gops_amd.algorithm.base import ApprBase, batch_to_device, cuda_device_of, grad_buffers, install_grads
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
 from gops_amd.create_pkg.create_env_model import create_env_model
 from gops_amd.utils.common_utils import get_apprfunc_dict, make_adam
@@ -71,7 +72,7 @@ class ApproxContainer(ApprBase):
         return self.policy.get_act_dist(logits)
 
 
-class MPG(AlgorithmBase):
+class MPG(ModelBasedBase):
     """pge_method: "mixed_weight" (rule-based weights of the two gradients, eta / terminal_iter) or "mixed_state"
     (per-sample choice by the disagreement of the data and model backups, kappa); gamma; tau: Polyak factor;
     delay_update: policy update period; forward_step: model rollout length."""
@@ -83,7 +84,7 @@ class MPG(AlgorithmBase):
         self.envmodel = create_env_model(**kwargs)
         # the model return's sweep is gops_rollout_backward_adj: built for the models whose observation is the state
         kind = getattr(getattr(self.envmodel, "model", self.envmodel), "hip_kind", None)
-        if kind is not None and kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM):
+        if kind is not None and kind not in hb.STATE_OBS_ENV_KINDS:
             raise RuntimeError(f"MPG on the HIP path supports pyth_lq, pyth_idpendulum, gym_cartpoleconti and gym_pendulum models "
                                f"(adjoint I/O of the rollout sweep); env model '{kwargs.get('env_id')}' is not among them")
         self.pge_method = kwargs["pge_method"]
@@ -99,8 +100,6 @@ class MPG(AlgorithmBase):
         self.reward_scale = 1.0
         self.delay_update = delay_update
         self.forward_step = forward_step
-        self.tb_info = dict()
-        self._cache = {}
         self._tmp = {}
         self._graphs = {}
 
@@ -174,8 +173,7 @@ class MPG(AlgorithmBase):
 
     def remote_update(self, update_info: dict):
         for n in self._q_names() + ["policy"]:
-            for p, grad in zip(getattr(self.networks, n).parameters(), update_info[f"{n}_grad"]):
-                p.grad = grad
+            install_grads(getattr(self.networks, n), update_info[f"{n}_grad"])
         self._update(update_info["iteration"])
         self._step_schedulers()
 
@@ -188,35 +186,19 @@ class MPG(AlgorithmBase):
         with torch.no_grad():
             torch._foreach_copy_(list(nets.policy4rollout.parameters()), list(nets.policy.parameters()))
             for n in self._q_names() + ["policy"]:   # p_targ <- (1 - tau) p_targ + tau p   (mpg.py:383-424)
-                online = list(getattr(nets, n).parameters())
-                target = list(getattr(nets, f"{n}_target").parameters())
-                torch._foreach_mul_(target, 1 - self.tau)
-                torch._foreach_add_(target, online, alpha=self.tau)
+                polyak_foreach_(list(getattr(nets, f"{n}_target").parameters()), list(getattr(nets, n).parameters()), self.tau)
 
     # ---- kernels -----------------------------------------------------------------------------
     def _net(self, role: str, module, B: int, device) -> hb.MlpNet:
         """One MlpNet (own activation stash) per use of a network inside an update: a backward follows ITS forward."""
-        key = (role, B, str(device))
         mlp = module.hip_mlp()
-        net = self._cache.get(key)
-        if net is None:
-            net = self._cache[key] = hb.MlpNet(mlp, B, device=device)
-        else:
-            net.mlp = mlp
-        return net
+        return self._cached((role, B, str(device)), lambda: hb.MlpNet(mlp, B, device=device), lambda net: setattr(net, "mlp", mlp))
 
     def _rollout_for(self, B: int, device) -> hb.Rollout:
-        nets = self.networks
-        key = ("rollout", B, self.forward_step, float(self.gamma), str(device))
-        pol = nets.policy.hip_mlp()
-        ro = self._cache.get(key)
-        if ro is None:
-            env = self.envmodel.hip_env(nets.policy.act_low_lim.cpu().numpy(), nets.policy.act_high_lim.cpu().numpy())
-            ro = self._cache[key] = hb.Rollout(env, pol, batch=B, horizon=self.forward_step, gamma=self.gamma,
-                                               finite_horizon=False, need_grad=True, device=device)
-        else:
-            ro.set_policy(pol)
-        return ro
+        pol = self.networks.policy.hip_mlp()
+        return self._cached(("rollout", B, self.forward_step, float(self.gamma), str(device)), lambda: hb.Rollout(
+            self._hip_env(), pol, batch=B, horizon=self.forward_step, gamma=self.gamma, finite_horizon=False, need_grad=True,
+            device=device), lambda ro: ro.set_policy(pol))
 
     def _scratch_grads(self, module, tag: str):
         bufs = self._tmp.get(tag)

@@ -21,13 +21,14 @@ import numpy as np
 import torch
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import _INFO_KEYS, AlgorithmBase, batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.algorithm._model_based import ModelBasedBase, polyak_foreach_
+from gops_amd.algorithm.base import grad_buffers, install_grads
 from gops_amd.algorithm.infadp import ApproxContainer  # noqa: F401  (same container: v, policy, targets, two Adams)
 from gops_amd.create_pkg.create_env_model import create_env_model
 from gops_amd.utils.tensorboard_setup import tb_tags
 
 
-class SPIL(AlgorithmBase):
+class SPIL(ModelBasedBase):
     """gamma, tau, pev_step, pim_step, forward_step as in the reference (spil.py:80-112)."""
 
     def __init__(self, index: int = 0, gamma: float = 0.99, tau: float = 0.005, pev_step: int = 1, pim_step: int = 1,
@@ -41,10 +42,8 @@ class SPIL(AlgorithmBase):
         self.n_constraint = kwargs["constraint_dim"]
         self.delta_i = np.array([0.0] * kwargs["constraint_dim"])
         self.Kp, self.Ki, self.Kd = 60, 0.02, 0
-        self.tb_info = dict()
         self.safe_prob_pre = np.array([0.0] * kwargs["constraint_dim"])
         self.chance_thre = np.array([0.97] * kwargs["constraint_dim"])
-        self._cache = {}
 
     @property
     def adjustable_parameters(self):
@@ -60,20 +59,16 @@ class SPIL(AlgorithmBase):
 
     def remote_update(self, update_info: dict):
         for net_name, grads in update_info.items():
-            for p, grad in zip(self.networks.net_dict[net_name].parameters(), grads):
-                p.grad = grad
+            install_grads(self.networks.net_dict[net_name], grads)
         self._update(list(update_info.keys()))
 
     def _update(self, update_list: list):
-        tau = self.tau
         for net_name in update_list:
             self.networks.optimizer_dict[net_name].step()
         with torch.no_grad():
             for net_name in update_list:
-                online = list(self.networks.net_dict[net_name].parameters())
-                target = list(self.networks.target_net_dict[net_name].parameters())
-                torch._foreach_mul_(target, 1 - tau)
-                torch._foreach_add_(target, online, alpha=tau)
+                polyak_foreach_(list(self.networks.target_net_dict[net_name].parameters()),
+                                list(self.networks.net_dict[net_name].parameters()), self.tau)
 
     # ------------------------------------------------------------------------------------------
     def _rollout_for(self, batch: int, device, need_grad: bool) -> hb.Rollout:
@@ -81,36 +76,27 @@ class SPIL(AlgorithmBase):
         key = (batch, self.forward_step, float(self.gamma), str(device), need_grad)
         pol = nets.policy.hip_mlp()
         vt = None if need_grad else nets.v_target.hip_mlp()   # PIM has no terminal value (spil.py:233-250)
-        ro = self._cache.get(key)
-        if ro is None:
-            env = self.envmodel.hip_env(nets.policy.act_low_lim.cpu().numpy(), nets.policy.act_high_lim.cpu().numpy())
+
+        def make():
+            env = self._hip_env()
             if not hb.has_constraints(env):
                 raise RuntimeError("SPIL needs a model with constraint outputs (pyth_veh3dofconti_surrcstr / _detour / _errcstr, "
                                    "pyth_veh2dofconti_errcstr, pyth_mobilerobot)")
             if env.n_constraint != self.n_constraint:
                 raise RuntimeError(f"constraint_dim = {self.n_constraint}, but the model has {env.n_constraint} constraints")
-            ro = hb.Rollout(env, pol, batch=batch, horizon=self.forward_step, gamma=self.gamma, finite_horizon=False,
-                            need_grad=need_grad, value=vt, device=device, tail_unmasked=not need_grad)
-            self._cache[key] = ro
-        else:
-            ro.set_policy(pol, vt)
-        return ro
+            return hb.Rollout(env, pol, batch=batch, horizon=self.forward_step, gamma=self.gamma, finite_horizon=False,
+                              need_grad=need_grad, value=vt, device=device, tail_unmasked=not need_grad)
+        return self._cached(key, make, lambda ro: ro.set_policy(pol, vt))
 
     def _value_for(self, batch: int, device) -> hb.ValueNet:
-        key = ("v", batch, str(device))
         mlp = self.networks.v.hip_mlp()
-        vn = self._cache.get(key)
-        if vn is None:
-            vn = self._cache[key] = hb.ValueNet(mlp, batch, device=device)
-        else:
-            vn.mlp = mlp
-        return vn
+        return self._cached(("v", batch, str(device)), lambda: hb.ValueNet(mlp, batch, device=device), lambda vn: setattr(vn, "mlp", mlp))
 
     def _compute_gradient(self, data: dict, iteration: int) -> list:
         start_time = time.time()
         if self.reward_scale != 1.0:
             raise RuntimeError("SPIL.reward_scale != 1 is not supported by the HIP rollout (the terminal value is unscaled)")
-        batch = self._attach_reference_points(data, batch_to_device(data, cuda_device_of(self.networks), ("obs", "done") + _INFO_KEYS))
+        batch = self._model_batch(data)
         B, device, nc = batch["obs"].shape[0], batch["obs"].device, self.n_constraint
         # ---- policy evaluation -----------------------------------------------------------------
         res = self._rollout_for(B, device, need_grad=False).forward(batch)

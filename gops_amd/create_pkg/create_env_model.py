@@ -186,13 +186,13 @@ def create_env_model(
 
     # wrapper options outside the fused kernels' contract are refused, never silently ignored
     if repeat_num is not None:   # ActionRepeatModel: in the kernels of the models whose observation is the state
-        if env_model.hip_kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM):
+        if env_model.hip_kind not in hb.STATE_OBS_ENV_KINDS:
             raise RuntimeError("ActionRepeatModel (repeat_num) is supported for pyth_lq / pyth_idpendulum / gym_* models only "
                                "by the HIP env models (the reference wrapper does not advance `info`)")
         if not 1 <= int(repeat_num) <= hb.MAX_REPEAT:
             raise RuntimeError(f"repeat_num must be 1..{hb.MAX_REPEAT} for the HIP env models")
     scaled = obs_shift is not None or obs_scale is not None
-    if scaled and (env_model.obs_dim > 8 or env_model.hip_kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM)):
+    if scaled and (env_model.obs_dim > 8 or env_model.hip_kind not in hb.STATE_OBS_ENV_KINDS):
         raise RuntimeError("ScaleObservationModel (obs_shift/obs_scale) is supported for pyth_lq / pyth_idpendulum / gym_* models only "
                            "(observation dimension <= 8) by the HIP env models")
     if not mask_at_done and env_model.hip_kind == hb.ENV_VEH_SURR:

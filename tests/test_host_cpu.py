@@ -752,7 +752,7 @@ def test_remote_update_path_has_no_host_sync_before_the_collective(monkeypatch):
               value_hidden_sizes=[64, 64], value_hidden_activation="gelu", value_learning_rate=1e-3)
     kw.pop("pre_horizon", None)
     inf = create_alg(**kw, precision_check_interval=0)
-    import gops_amd.algorithm.infadp as infadp_mod
+    import gops_amd.algorithm._model_based as infadp_mod
     monkeypatch.setattr(infadp_mod, "batch_to_device", lambda d, dev, keys: d)
     monkeypatch.setattr(infadp_mod, "cuda_device_of", lambda nets: torch.device("cpu"))
     monkeypatch.setattr(inf, "_gradient_kernels", lambda mode, b: _SyncTrap())
@@ -760,6 +760,22 @@ def test_remote_update_path_has_no_host_sync_before_the_collective(monkeypatch):
     for it, name in ((0, "v"), (1, "policy")):
         tb, info = inf.get_remote_update_info({"obs": torch.zeros(4, 6)}, it)
         assert list(info) == [name]
+
+
+def test_caller_provided_ref_appended_of_another_shape_is_refused():
+    """ADVICE (low, `_attach_reference_points`): the kernels index a caller's `ref_appended` by [B, H, 4] of the rollout at hand - a
+    table of any other extent is refused on the host instead of being read past its end."""
+    from gops_amd.create_pkg.create_alg import create_alg
+    alg = create_alg(**_fhadp_kwargs(pre_horizon=3))
+    B, H = 4, 3
+    batch = lambda: {"obs": torch.zeros(B, 6), "done": torch.zeros(B)}   # noqa: E731
+    good = torch.arange(B * H * 4, dtype=torch.float64).reshape(B, H, 4)
+    out = alg._attach_reference_points({"ref_appended": good}, batch())
+    assert out["ref_appended"].dtype is torch.float32 and torch.equal(out["ref_appended"], good.float())
+    for shape in ((B, H + 1, 4), (B, H - 1, 4), (B + 1, H, 4), (B, H, 3), (B, H * 4), (H, B, 4)):
+        with pytest.raises(ValueError, match="ref_appended has shape"):
+            alg._attach_reference_points({"ref_appended": torch.zeros(shape)}, batch())
+    assert "ref_appended" not in alg._attach_reference_points({}, batch())   # (mode off, nothing handed in: untouched)
 
 
 def test_networks_with_cached_abi_views_deepcopy():
