@@ -55,7 +55,31 @@ def refusal(alg: str, kwargs: dict):
     return None
 
 
-class ActorCriticBase(AlgorithmBase):
+class NetCache:
+    """The kernel objects and scratch tensors an update keeps between calls (`self._cache`, `self._bufs`); DQN (algorithm/dqn.py) keeps
+    its own the same way."""
+
+    def _net(self, role: str, module, B: int, device) -> hb.MlpNet:
+        """One MlpNet (own activation stash) per use of a network inside an update: a backward follows ITS forward."""
+        key = (role, B, str(device))
+        mlp = module.hip_mlp()
+        net = self._cache.get(key)
+        if net is None:
+            net = self._cache[key] = hb.MlpNet(mlp, B, device=device)
+        else:
+            net.mlp = mlp
+        return net
+
+    def _buf(self, name: str, shape, device, fill=None) -> torch.Tensor:
+        key = (name, tuple(shape), str(device))
+        t = self._bufs.get(key)
+        if t is None:
+            t = self._bufs[key] = (torch.empty(shape, dtype=torch.float32, device=device) if fill is None else
+                                   torch.full(shape, float(fill), dtype=torch.float32, device=device))
+        return t
+
+
+class ActorCriticBase(NetCache, AlgorithmBase):
     _q_names: Tuple[str, ...] = ("q",)   # the critics; the first one carries the actor gradient and PER's priorities
     _smooth = False                      # TD3's target-policy smoothing
 
@@ -159,25 +183,6 @@ class ActorCriticBase(AlgorithmBase):
             up.step(1 - polyak)
 
     # ---- kernels -------------------------------------------------------------------------------
-    def _net(self, role: str, module, B: int, device) -> hb.MlpNet:
-        """One MlpNet (own activation stash) per use of a network inside an update: a backward follows ITS forward."""
-        key = (role, B, str(device))
-        mlp = module.hip_mlp()
-        net = self._cache.get(key)
-        if net is None:
-            net = self._cache[key] = hb.MlpNet(mlp, B, device=device)
-        else:
-            net.mlp = mlp
-        return net
-
-    def _buf(self, name: str, shape, device, fill=None) -> torch.Tensor:
-        key = (name, tuple(shape), str(device))
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = (torch.empty(shape, dtype=torch.float32, device=device) if fill is None else
-                                   torch.full(shape, float(fill), dtype=torch.float32, device=device))
-        return t
-
     @staticmethod
     def _squash(pol, pre):
         """(action, d action / d pre) of DetermPolicy's tanh squash (apprfunc/mlp.py: `_squash`)."""

@@ -1,5 +1,5 @@
 """MLP approximate functions: DetermPolicy, FiniteHorizonPolicy, FiniteHorizonFullPolicy, StateValue, ActionValue of the
-ADP and DDPG / TD3 paths; StochaPolicy and ActionValueDistri of DSAC-T.
+ADP and DDPG / TD3 paths; StochaPolicy and ActionValueDistri of DSAC-T; ActionValueDis of DQN.
 
 Module structure, parameter names (`pi.0.weight` ... / `v.0.weight` ...), registered buffers and
 `forward` semantics follow the reference (gops/apprfunc/mlp.py:36-41,50-111,309-329) so that its
@@ -7,8 +7,8 @@ Module structure, parameter names (`pi.0.weight` ... / `v.0.weight` ...), regist
 and evaluators for single observations; inside `compute_gradient` the same parameters are read
 in place by the fused HIP rollout (`hip_mlp()`), which never calls `forward`.
 """
-__all__ = ["DetermPolicy", "FiniteHorizonPolicy", "FiniteHorizonFullPolicy", "StateValue", "ActionValue", "StochaPolicy",
-           "ActionValueDistri"]
+__all__ = ["DetermPolicy", "FiniteHorizonPolicy", "FiniteHorizonFullPolicy", "StateValue", "ActionValue", "ActionValueDis",
+           "StochaPolicy", "ActionValueDistri"]
 
 import weakref
 
@@ -161,6 +161,26 @@ class ActionValue(nn.Module, Action_Distribution, _HipMlpMixin):
 
     def forward(self, obs, act):
         return torch.squeeze(self.q(torch.cat([obs, act], dim=-1)), -1)
+
+
+class ActionValueDis(nn.Module, Action_Distribution, _HipMlpMixin):
+    """Action-value function of a discrete action space: obs -> the values of all `act_num` actions (reference
+    gops/apprfunc/mlp.py:248-268, parameter names `q.0.weight` ...).  DQN evaluates it through `gops_mlp_forward / _backward` and
+    `gops_dqn_backup` (`hip_mlp()`)."""
+
+    _net_attr = "q"
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        self.act_num = kwargs["act_num"]
+        self._hidden_activation = kwargs["hidden_activation"]
+        self._output_activation = kwargs.get("output_activation", "linear")
+        self.q = mlp([kwargs["obs_dim"]] + list(kwargs["hidden_sizes"]) + [self.act_num],
+                     get_activation_func(self._hidden_activation), get_activation_func(self._output_activation))
+        self.action_distribution_cls = kwargs["action_distribution_cls"]
+
+    def forward(self, obs):
+        return self.q(obs)
 
 
 class StochaPolicy(nn.Module, Action_Distribution, _HipMlpMixin):

@@ -17,6 +17,8 @@
 // (one thread per (row, action dimension) forms that dimension's mean and log std), two critics with (mean, softplus std) heads.
 // soft_q_backup_kernel: SAC's and DSAC's soft Q backup on the same tile and policy head - one or two scalar critics with their minimum,
 // or one critic with a (mean, softplus std) head and a clipped return sample.
+// dqn_backup_kernel: DQN's max-Q backup on the same tile - one network on obs2 alone, its act_num head outputs in double, their maximum
+// and arg-max per row; dqn_loss_kernel: the dense output-layer seed of the taken action's regression, with ac_critic_loss_kernel's sums.
 // What the three kernels share is stated once and inlined into each: the tile prologue (ac_tile), the hidden layers and the head
 // staging (ac_hidden, ac_stage_head; ac_tile.h: ac_head_dot, chain_sum8), and for the two soft kernels the policy head (soft_policy_head, its scalar
 // arithmetic in soft_math.h), the distributional critic head (distri_head) and the row's entropy terms (soft_entropy_terms).  The
@@ -112,6 +114,13 @@ int soft_q_check(const GopsSoftQBackup* d, int B) {
     return soft_check_nets(d->policy, d->q, d->n_q, d->distri ? 2 : 1);
 }
 
+int dqn_check(const GopsDqnBackup* d, int B) {
+    if (!d || B < 1) return GOPS_ERR_BAD_ARG;
+    if (d->q.n_layers < 1 || d->q.n_layers > GOPS_MAX_LAYERS || d->q.sizes[0] < 1 || d->act_num < 1) return GOPS_ERR_BAD_ARG;
+    if (d->act_num < 2 || d->act_num > GOPS_DQN_MAX_ACTIONS || d->q.sizes[0] > AC_MAX_IN) return GOPS_ERR_UNSUPPORTED;
+    return ac_check_net(d->q, d->q.sizes[0], d->act_num);
+}
+
 // What the LDS plan and the kernels' nets are made from - `nets`: the policy and the n_q critics; O / A: observation and action
 // width; `extra`: floats per tile row kept between the networks besides in0, in front of the weight chunk.
 struct AcShape {
@@ -120,6 +129,9 @@ struct AcShape {
 };
 AcShape ac_shape(const GopsAcBackup& d) {
     return {{&d.policy, &d.q[0], &d.q[1]}, d.n_q, d.policy.sizes[0], d.policy.sizes[d.policy.n_layers], 0};
+}
+AcShape dqn_shape(const GopsDqnBackup& d) {   // one net, no action input; extra: the head's outputs, act_num doubles per row
+    return {{&d.q, nullptr, nullptr}, 0, d.q.sizes[0], 0, 2 * d.act_num};
 }
 AcShape soft_shape(const GopsMlp& policy, const GopsMlp* q, int n_q) {
     const int A = policy.sizes[policy.n_layers] / 2;
@@ -462,6 +474,48 @@ __global__ __launch_bounds__(AC_THREADS) void soft_q_backup_kernel(const SoftQPa
     }
 }
 
+// ---- DQN: the max-Q backup (gops/algorithm/dqn.py:138-140) -------------------------------------------------------------------------
+// Same tile, staging and chains as ac_backup_kernel, one network (obs2 alone is its input).  The head has act_num <= 16 outputs but a
+// 64-row tile has only four feature groups per row: thread (r, g) forms outputs g, g + 256 / R, .. in double and parks them in LDS
+// (qv [act_num][R], doubles, in the plan's extra section); thread (r, 0) then takes the row's maximum over the doubles in index
+// order - the lowest index among bit-equal maxima - and forms the backup.
+struct DqnParams {
+    AcParams ac;   // net[0], B, O (A = 0), the LDS plan, rscale, gamma, obs2 / rew / done, backup, q_targ ([B, act_num] here)
+    int* a_star;
+};
+
+template <int R>
+__global__ __launch_bounds__(AC_THREADS) void dqn_backup_kernel(const DqnParams dp) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int G = AC_THREADS / R;
+    const AcParams& p = dp.ac;
+    const int tid = threadIdx.x, r = tid % R, g = tid / R;
+    const AcTile t = ac_tile<R>(p, lds);
+    const int b0 = t.b0, nvalid = t.nvalid;
+    const AcNet& net = p.net[0];
+    const float* cur = ac_hidden<R>(net, t.in0, t.ld0, t.xa, t.xb, t.ldx, t.wb);
+    const int K = net.dims[net.nl - 1], N = net.dims[net.nl];
+    ac_stage_head(net, t.wb);
+    double* qv = reinterpret_cast<double*>(t.extra);
+    for (int a = g; a < N; a += G) {
+        const double y = ac_head_dot(cur + r * t.ldx, t.wb + a * K, K) + (double)t.wb[N * K + a];
+        qv[a * R + r] = y;
+        if (p.q_targ != nullptr && r < nvalid) p.q_targ[(size_t)(b0 + r) * N + a] = (float)y;
+    }
+    __syncthreads();
+    if (g == 0 && r < nvalid) {
+        double q_max = qv[r];
+        int best = 0;
+        for (int a = 1; a < N; ++a) {
+            const double v = qv[a * R + r];
+            if (v > q_max || (v != v && q_max == q_max)) q_max = v, best = a;   // (a NaN is the maximum, as for torch.max)
+        }
+        const int b = b0 + r;   // backup = r * reward_scale + gamma * (1 - d) * max_a q_target(o2)[a]   (dqn.py:104,140)
+        p.backup[b] = (float)((double)p.rew[b] * p.rscale + p.gamma * (1.0 - (double)p.done[b]) * q_max);
+        if (dp.a_star != nullptr) dp.a_star[b] = best;
+    }
+}
+
 // ---- critic regression: seeds, losses, mean(q), |q - backup| -------------------------------------------------------------------
 constexpr int ACL_BLOCKS = 64;
 constexpr int ACL_ONE_BLOCK_MAX = 8192;
@@ -498,6 +552,46 @@ __global__ __launch_bounds__(256) void ac_critic_loss_kernel(const float* __rest
     }
 }
 static_assert(4 + 6 * ACL_BLOCKS + 1 <= GOPS_AC_LOSS_STATS_FLOATS, "stats: four results, the blocks' partial sums, the ticket");
+
+// DQN's regression on the taken action's value (dqn.py:136-141, 146-153): the dense output-layer seed [B, N], |q_sel - backup|, the
+// loss, mean(q_sel) and the count of rows whose index is outside [0, N).  One thread per row; the same fold and `stats` layout as
+// ac_critic_loss_kernel.
+__global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__ q_all, const float* __restrict__ act,
+                                                       const float* __restrict__ backup, const float* __restrict__ weight, int N, int B,
+                                                       float gsc, float* __restrict__ seed, float* __restrict__ abs_err,
+                                                       float* __restrict__ stats) {
+    __shared__ double red[3][4];
+    __shared__ bool last;
+    double s[3] = {0.0, 0.0, 0.0};   // sum w d^2, sum q_sel, rows with an index outside [0, N)
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256) {
+        const float af = act[i];
+        const bool ok = af > -1.f && af < (float)N;   // truncation towards zero lands in [0, N); false for a NaN
+        const int a = ok ? (int)af : -1;
+        float g = 0.f, e = 0.f;
+        if (ok) {
+            const float q = q_all[(size_t)i * N + a];
+            const float d = q - backup[i];
+            const float w = weight != nullptr ? weight[i] : 1.f;
+            g = weight != nullptr ? gsc * (w * d) : gsc * d;
+            e = fabsf(d);
+            s[0] += (double)(weight != nullptr ? w * (d * d) : d * d);
+            s[1] += (double)q;
+        } else {
+            s[2] += 1.0;
+        }
+        float* srow = seed + (size_t)i * N;
+        for (int c = 0; c < N; ++c) srow[c] = c == a ? g : 0.f;
+        if (abs_err != nullptr) abs_err[i] = e;
+    }
+    if (grid_fold<3>(s, red, reinterpret_cast<double*>(stats + 4), 3, reinterpret_cast<unsigned*>(stats + 4 + 6 * ACL_BLOCKS), &last) &&
+        threadIdx.x == 0) {
+        stats[0] = (float)(s[0] / (double)B);
+        stats[1] = (float)(s[1] / (double)B);
+        stats[2] = (float)s[2];
+        stats[3] = 0.f;
+    }
+}
+static_assert(4 + 6 * ACL_BLOCKS + 1 <= GOPS_DQN_LOSS_STATS_FLOATS, "stats: the results, the blocks' partial sums, the ticket");
 
 }  // namespace
 
@@ -556,6 +650,37 @@ int ac_backup(const GopsAcBackup* d, int B, const float* obs2, const float* rew,
 int ac_critic_loss(const float* q, const float* backup, const float* weight, int nq, int B, float* seed, float* abs_err, float* stats,
                    hipStream_t s) {
     hipLaunchKernelGGL(ac_critic_loss_kernel, dim3(B <= ACL_ONE_BLOCK_MAX ? 1 : ACL_BLOCKS), dim3(256), 0, s, q, backup, weight, nq, B,
+                       (float)(2.0 / B), seed, abs_err, stats);
+    return (int)hipGetLastError();
+}
+
+size_t dqn_backup_workspace_bytes(const GopsDqnBackup* d, int B) {
+    return dqn_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(dqn_shape(*d), B);
+}
+
+int dqn_backup(const GopsDqnBackup* d, int B, const float* obs2, const float* rew, const float* done, float* backup, float* q_targ,
+               int* a_star, void* ws, size_t ws_bytes, hipStream_t s) {
+    int rc = dqn_check(d, B);
+    if (rc != GOPS_OK) return rc;
+    if (!obs2 || !rew || !done || !backup) return GOPS_ERR_BAD_ARG;
+    DqnParams dp;
+    memset(&dp, 0, sizeof(dp));
+    AcParams& p = dp.ac;
+    int R;
+    size_t lds;
+    rc = ac_prepare(dqn_shape(*d), B, nullptr, nullptr, ws, ws_bytes, p, R, lds);
+    if (rc != GOPS_OK) return rc;
+    p.rscale = d->reward_scale, p.gamma = d->gamma;
+    p.obs2 = obs2, p.rew = rew, p.done = done;
+    p.backup = backup, p.q_targ = q_targ;
+    dp.a_star = a_star;
+    rows_dispatch(R, [&]<int RR>() { launch_with_lds(dqn_backup_kernel<RR>, ac_grid(B, RR), dim3(AC_THREADS), lds, s, dp); });
+    return (int)hipGetLastError();
+}
+
+int dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int N, int B, float* seed, float* abs_err,
+             float* stats, hipStream_t s) {
+    hipLaunchKernelGGL(dqn_loss_kernel, dim3(B <= ACL_ONE_BLOCK_MAX ? 1 : ACL_BLOCKS), dim3(256), 0, s, q_all, act, backup, weight, N, B,
                        (float)(2.0 / B), seed, abs_err, stats);
     return (int)hipGetLastError();
 }

@@ -1097,6 +1097,20 @@ int gops_ac_critic_loss(const float* q, const float* backup, const float* weight
     return ac_critic_loss(q, backup, weight, n_q, batch, seed, abs_err, stats, static_cast<hipStream_t>(stream));
 }
 
+size_t gops_dqn_backup_workspace_bytes(const GopsDqnBackup* desc, int32_t batch) { return dqn_backup_workspace_bytes(desc, batch); }
+
+int gops_dqn_backup(const GopsDqnBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done, float* backup,
+                    float* q_targ, int32_t* a_star, void* workspace, size_t workspace_bytes, void* stream) {
+    return dqn_backup(desc, batch, obs2, rew, done, backup, q_targ, a_star, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int gops_dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int32_t act_num, int32_t batch,
+                  float* seed, float* abs_err, float* stats, void* stream) {
+    if (!q_all || !act || !backup || !seed || !stats || batch < 1 || act_num < 1) return GOPS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
+    return dqn_loss(q_all, act, backup, weight, act_num, batch, seed, abs_err, stats, static_cast<hipStream_t>(stream));
+}
+
 size_t gops_soft_backup_workspace_bytes(const GopsSoftBackup* desc, int32_t batch) { return soft_backup_workspace_bytes(desc, batch); }
 
 int gops_soft_backup(const GopsSoftBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,

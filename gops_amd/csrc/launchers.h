@@ -68,6 +68,11 @@ int soft_backup(const GopsSoftBackup* d, int B, const float* obs2, const float* 
 size_t soft_q_backup_workspace_bytes(const GopsSoftQBackup* d, int B);
 int soft_q_backup(const GopsSoftQBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
                   float* backup, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s);
+size_t dqn_backup_workspace_bytes(const GopsDqnBackup* d, int B);
+int dqn_backup(const GopsDqnBackup* d, int B, const float* obs2, const float* rew, const float* done, float* backup, float* q_targ,
+               int* a_star, void* ws, size_t ws_bytes, hipStream_t s);
+int dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int N, int B, float* seed, float* abs_err,
+             float* stats, hipStream_t s);
 
 // (the nets the tile kernels take: fp32, 1 .. 3 hidden layers of widths that are multiples of 16 up to 256; also trpo.hip's)
 int ac_check_net(const GopsMlp& m, int in, int out);

@@ -157,6 +157,10 @@ class GopsAcBackup(C.Structure):   # gops_ac_backup
                 ("target_noise", C.c_double), ("noise_clip", C.c_double), ("reward_scale", C.c_double), ("gamma", C.c_double)]
 
 
+class GopsDqnBackup(C.Structure):   # gops_dqn_backup
+    _fields_ = [("q", GopsMlp), ("act_num", C.c_int32), ("reserved", C.c_int32), ("reward_scale", C.c_double), ("gamma", C.c_double)]
+
+
 class GopsSoftBackup(C.Structure):   # gops_soft_backup
     _fields_ = [("policy", GopsMlp), ("q", GopsMlp * 2), ("act_low", C.c_float * MAX_ACT), ("act_high", C.c_float * MAX_ACT),
                 ("min_log_std", C.c_double), ("max_log_std", C.c_double), ("gamma", C.c_double), ("alpha", C.c_double),
@@ -245,6 +249,9 @@ def _signatures():
         "gops_cg_init": (rc, [vp, vp, vp, vp, i32, f64, vp, vp]),
         "gops_cg_step": (rc, [vp, vp, vp, vp, i32, f64, f64, vp, vp]),
         "gops_cg_finish": (rc, [vp, vp, vp, i32, vp, vp, vp]),
+        "gops_dqn_backup_workspace_bytes": (sz, [P(GopsDqnBackup), i32]),
+        "gops_dqn_backup": (rc, [P(GopsDqnBackup), i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "gops_dqn_loss": (rc, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -1358,6 +1365,72 @@ class AcCriticLoss:
         check(lib().gops_ac_critic_loss(_ptr(q), _ptr(backup), _ptr(weight), n_q, B, _ptr(seed), _ptr(abs_err), self.buf.data_ptr(),
                                         _stream()), "gops_ac_critic_loss")
         return seed, abs_err, self.buf[:4]
+
+
+DQN_MAX_ACTIONS = 16           # include/gops_hip.h: GOPS_DQN_MAX_ACTIONS
+DQN_LOSS_STATS_FLOATS = 392    # include/gops_hip.h: GOPS_DQN_LOSS_STATS_FLOATS
+
+
+class DqnBackup:
+    """DQN's max-Q backup in ONE launch (`gops_dqn_backup`, csrc/actor_critic.hip): the target ActionValueDis on obs2, the row's
+    maximum and arg-max over its `act_num` outputs, `rew * reward_scale + gamma * (1 - done) * max`.  `q`: the `GopsMlp` view of the
+    TARGET network (read in place at every call).  `supported` is False for a shape the kernel does not hold: the caller then composes
+    the backup from `MlpNet.forward` and `torch.max`; `run` on such a description raises."""
+
+    def __init__(self, q: GopsMlp, *, batch: int, device: Optional[torch.device] = None, workspace_bytes: Optional[int] = None):
+        d = self.desc = GopsDqnBackup()
+        self.batch = int(batch)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.set_net(q)
+        self.act_num = d.act_num = int(q.sizes[q.n_layers])
+        nbytes = lib().gops_dqn_backup_workspace_bytes(C.byref(d), self.batch)
+        self.supported = nbytes != 0
+        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
+        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
+
+    def set_net(self, q: GopsMlp):
+        C.memmove(C.byref(self.desc.q), C.byref(q), C.sizeof(GopsMlp))
+        self._keep = q   # the description holds raw pointers
+
+    def run(self, obs2, rew, done, *, reward_scale=1.0, gamma=0.99, want_q=False, want_a=False,
+            out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """-> {"backup" [B], "q_targ" [B, act_num] (want_q), "a_star" [B] int32 (want_a)}; `out` supplies the output tensors instead
+        of fresh ones.  Enqueues only."""
+        B, d = self.batch, self.desc
+        assert obs2.shape[0] == B
+        d.reward_scale, d.gamma = float(reward_scale), float(gamma)
+        res = dict(out or {})
+        for k, want, shape, dtype in (("backup", True, (B,), torch.float32), ("q_targ", want_q, (B, self.act_num), torch.float32),
+                                      ("a_star", want_a, (B,), torch.int32)):
+            if want and k not in res:
+                res[k] = torch.empty(shape, dtype=dtype, device=self.device)
+        a_star = res.get("a_star")
+        assert a_star is None or (a_star.is_cuda and a_star.dtype == torch.int32 and a_star.is_contiguous())
+        check(lib().gops_dqn_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(res["backup"]), _ptr(res.get("q_targ")),
+                                    None if a_star is None else a_star.data_ptr(), self.workspace.data_ptr(), self._workspace_bytes,
+                                    _stream()), "gops_dqn_backup")
+        return res
+
+
+class DqnLoss:
+    """The seam between the forward and the backward of DQN's live network in one launch (`gops_dqn_loss`): the dense output-layer
+    seed, |q_sel - backup|, and `buf[:3]` = loss, mean(q_sel), rows whose action index is out of range; the rest of `buf` is the
+    kernel's scratch (zero before the first call, left zero)."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(DQN_LOSS_STATS_FLOATS, dtype=torch.float32, device=device)
+
+    def run(self, q_all: torch.Tensor, act: torch.Tensor, backup: torch.Tensor, weight: Optional[torch.Tensor] = None,
+            seed: Optional[torch.Tensor] = None, abs_err: Optional[torch.Tensor] = None):
+        """q_all [B, act_num], act [B] (float indices) -> (seed [B, act_num], abs_err [B], stats [3])."""
+        B, N = q_all.shape
+        assert act.numel() == B and backup.numel() == B and (weight is None or weight.numel() == B)
+        seed = torch.empty_like(q_all) if seed is None else seed
+        abs_err = torch.empty(B, dtype=torch.float32, device=q_all.device) if abs_err is None else abs_err
+        assert seed.numel() == B * N and abs_err.numel() == B
+        check(lib().gops_dqn_loss(_ptr(q_all), _ptr(act), _ptr(backup), _ptr(weight), N, B, _ptr(seed), _ptr(abs_err),
+                                  self.buf.data_ptr(), _stream()), "gops_dqn_loss")
+        return seed, abs_err, self.buf[:3]
 
 
 DSACT_STATS_FLOATS = 800        # include/gops_hip.h: GOPS_DSACT_STATS_FLOATS

@@ -22,7 +22,7 @@ import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import is_poly
-from gops_amd.apprfunc.mlp import StochaPolicy
+from gops_amd.apprfunc.mlp import ActionValueDis, StochaPolicy
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, NOT_RESTATED, draw_reset_pool
 
 # TimeLimit of the data envs where create_env registers one (gops/create_pkg/create_env.py:142-148 takes the env's own
@@ -50,6 +50,9 @@ class Evaluator:
         `create_env_model`; networks: the learner's container (its `policy` is evaluated in place).  `max_episode_steps`: None =
         the data env's registered limit, else 200.  `fused=False` forces the per-step loop."""
         self.cfg, self.env_model, self.networks = dict(cfg), env_model, networks
+        if isinstance(getattr(networks, "q", None), ActionValueDis):
+            raise NotImplementedError("Evaluator runs closed loops with continuous actions only: an ActionValueDis policy (DQN) emits "
+                                      "action values over a discrete action set, and no action table is part of the evaluator")
         base = getattr(env_model, "unwrapped", env_model)
         if getattr(base, "ref_c", None) is not None:
             raise RuntimeError("Evaluator draws its initial states from the DEFAULT reference trajectories "

@@ -36,9 +36,14 @@ class DeviceEnvSampler:
     on_device = True   # trainers: do not move the networks to the CPU around sample()
 
     def __init__(self, cfg: dict, env_model, *, n_envs: int, steps_per_sample: int = 1, max_episode_steps: int = 200,
-                 seed: int = 0, device="cuda", pool_factor: int = 8, noise_std: float = 0.0, env_step: str = "data"):
+                 seed: int = 0, device="cuda", pool_factor: int = 8, noise_std: float = 0.0, env_step: str = "data",
+                 action_table=None, epsilon: float = 0.0):
         """cfg: workload dict as in `gops_amd.utils.synthetic.CONFIGS` (env_id, pre_horizon, lq_config);
-        env_model: the wrapped model from `create_env_model` (its constants drive the step kernel)."""
+        env_model: the wrapped model from `create_env_model` (its constants drive the step kernel);
+        action_table [act_num, action_dim] (None: continuous actions, the policy output is the action): the policy output is read as
+        action values - the action index is their arg-max, replaced with probability `epsilon` by a uniform index from this sampler's
+        device generator -, the env is stepped with `action_table[index]` and the stored `act` column is the index as a float, [N, 1]
+        (DQN; `gym_cartpoleconti` with the table [[-1.], [1.]] is the two-action cartpole)."""
         self.cfg, self.env_model = dict(cfg), env_model
         if getattr(getattr(env_model, "unwrapped", env_model), "ref_c", None) is not None:
             raise RuntimeError("DeviceEnvSampler draws its reset states from the DEFAULT reference trajectories "
@@ -47,6 +52,10 @@ class DeviceEnvSampler:
         self.device = torch.device(device)
         self.seed, self.pool_factor, self.noise_std = seed, pool_factor, noise_std
         self._warned_noise = False
+        self.action_table = None if action_table is None else torch.as_tensor(action_table, dtype=torch.float32).to(self.device).contiguous()
+        if self.action_table is not None and self.action_table.dim() != 2:
+            raise ValueError("action_table must be [act_num, action_dim]")
+        self.epsilon = float(epsilon)
         if env_step not in ("data", "model"):
             raise ValueError("env_step must be 'data' (the data environment's step) or 'model' (the env model's)")
         self.data_env = env_step == "data"
@@ -78,9 +87,11 @@ class DeviceEnvSampler:
 
     def _hip_env(self):
         if self._henv is None:
-            pol = self.networks.policy
-            self._henv = self.env_model.hip_env(pol.act_low_lim.cpu().numpy(), pol.act_high_lim.cpu().numpy(),
-                                                data_env=self.data_env)
+            if self.action_table is not None:   # no policy module to ask: the squash limits are the table's column extremes
+                low, high = self.action_table.min(dim=0).values, self.action_table.max(dim=0).values
+            else:
+                low, high = self.networks.policy.act_low_lim, self.networks.policy.act_high_lim
+            self._henv = self.env_model.hip_env(low.cpu().numpy(), high.cpu().numpy(), data_env=self.data_env)
         return self._henv
 
     # ---- sampling -----------------------------------------------------------------------------
@@ -89,7 +100,12 @@ class DeviceEnvSampler:
         this step ended - terminated or timed out - and that restart from a fresh reset state)."""
         obs, info = self.obs, self.info
         act, logp = policy(obs), zeros
-        if isinstance(policy, StochaPolicy):   # the policy's own distribution explores; its log-probability is stored
+        stored = None
+        if self.action_table is not None:
+            stored = self.select_index(act)
+            act = self.action_table[stored]
+            stored = stored.to(torch.float32).unsqueeze(-1)
+        elif isinstance(policy, StochaPolicy):   # the policy's own distribution explores; its log-probability is stored
             act, logp = policy.get_act_dist(act).sample(generator=self._gen)
             if self.noise_std > 0.0 and not self._warned_noise:
                 self._warned_noise = True
@@ -97,7 +113,7 @@ class DeviceEnvSampler:
         elif self.noise_std > 0.0:
             act = act + self.noise_std * torch.randn(act.shape, generator=self._gen, device=self.device)
         obs2, rew, done, info2 = hb.env_step(self._hip_env(), obs, act.contiguous(), zeros, info)
-        row = dict(obs=obs, act=act, rew=rew, done=done, obs2=obs2, logp=logp)
+        row = dict(obs=obs, act=act if stored is None else stored, rew=rew, done=done, obs2=obs2, logp=logp)
         for k in info:
             row[k], row["next_" + k] = info[k], info2[k]
         # episode bookkeeping: terminated or timed-out instances restart from a fresh reset state
@@ -115,6 +131,16 @@ class DeviceEnvSampler:
                 self.info[k] = self.info[k].index_copy(0, idx, fresh[k])
             self.t.index_fill_(0, idx, 0)
         return row, over
+
+    def select_index(self, values: torch.Tensor) -> torch.Tensor:
+        """Epsilon-greedy over action values [N, act_num] -> indices [N] (int64): the arg-max, replaced with probability `epsilon` by
+        a uniform index; both draws come from the sampler's generator."""
+        index = torch.argmax(values, dim=-1)
+        if self.epsilon > 0.0:
+            explore = torch.rand(index.shape, generator=self._gen, device=values.device) < self.epsilon
+            uniform = torch.randint(values.shape[-1], index.shape, generator=self._gen, device=values.device)
+            index = torch.where(explore, uniform, index)
+        return index
 
     @torch.no_grad()
     def sample(self):

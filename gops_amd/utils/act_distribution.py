@@ -5,7 +5,8 @@ action; reference gops/utils/act_distribution_type.py:141-150 and the mixin
 gops/utils/act_distribution_cls.py:13-27 that samplers/evaluators call through
 `networks.create_action_distributions(logits)`).  DSAC-T's StochaPolicy emits `cat(mean, std)`: the diagonal Gaussian and its
 tanh-squashed form (act_distribution_type.py:18-113).  Their `sample` / `rsample` take the unit-normal draws as an optional
-argument: wherever a result has to be reproducible the draws are an input of the computation.
+argument: wherever a result has to be reproducible the draws are an input of the computation.  Discrete action spaces (DQN's
+ActionValueDis) have the arg-max over action values, ValueDiracDistribution, and the categorical distribution (:116-160).
 """
 import math
 
@@ -89,6 +90,45 @@ class DiracDistribution:
 
     def mode(self):
         return self.logits
+
+
+class CategoricalDistribution:
+    """Discrete actions with probabilities softmax(logits) (act_distribution_type.py:116-138)."""
+
+    def __init__(self, logits: torch.Tensor):
+        self.logits = logits
+        self.cat = torch.distributions.Categorical(logits=logits)
+
+    def sample(self):
+        action = self.cat.sample()
+        return action, self.log_prob(action)
+
+    def log_prob(self, action: torch.Tensor) -> torch.Tensor:
+        if action.dim() > 1:
+            action = action.squeeze(1)
+        return self.cat.log_prob(action)
+
+    def entropy(self):
+        return self.cat.entropy()
+
+    def mode(self):
+        return torch.argmax(self.logits, dim=-1)
+
+    def kl_divergence(self, other: "CategoricalDistribution"):
+        return torch.distributions.kl.kl_divergence(self.cat, other.cat)
+
+
+class ValueDiracDistribution:
+    """The logits are action values: the action is their arg-max (act_distribution_type.py:152-160)."""
+
+    def __init__(self, logits: torch.Tensor):
+        self.logits = logits
+
+    def sample(self):
+        return torch.argmax(self.logits, dim=-1), torch.tensor([0.0])
+
+    def mode(self):
+        return torch.argmax(self.logits, dim=-1)
 
 
 class Action_Distribution:

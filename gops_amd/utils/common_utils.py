@@ -58,8 +58,16 @@ def get_apprfunc_dict(key: str, **kwargs):
         var["act_high_lim"] = np.array(kwargs["action_high_limit"])
         var["act_low_lim"] = np.array(kwargs["action_low_limit"])
         var["act_dim"] = kwargs["action_dim"]
-    else:
-        raise NotImplementedError("discrete actions are outside the MI355X ADP path")
+    else:   # discrete actions (reference common_utils.py:115-128): the action count, and a distribution over action indices
+        var["act_num"] = kwargs["action_num"]
+        dist = kwargs.get("policy_act_distribution", "default")
+        if dist == "default":
+            dist = "CategoricalDistribution" if kwargs.get("policy_func_name") == "StochaPolicyDis" else "ValueDiracDistribution"
+        if dist not in ("CategoricalDistribution", "ValueDiracDistribution"):
+            raise NotImplementedError(f"policy_act_distribution {dist!r}: discrete actions take CategoricalDistribution or "
+                                      "ValueDiracDistribution")
+        var["action_distribution_cls"] = getattr(act_distribution, dist)
+        return var
     dist = kwargs.get("policy_act_distribution", "default")   # (reference common_utils.py:118-133)
     if dist == "default":
         var["action_distribution_cls"] = GaussDistribution if kwargs.get("policy_func_name") == "StochaPolicy" else DiracDistribution

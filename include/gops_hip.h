@@ -903,6 +903,50 @@ int gops_cg_init(const float* g, float* x, float* r, float* p, int32_t n, double
 int gops_cg_step(float* p, float* Ap, float* x, float* r, int32_t n, double damping, double atol, GopsCgState* state, void* stream);
 int gops_cg_finish(const float* g, const float* x, float* step, int32_t n, const float* hyper, GopsCgState* state, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): DQN (gops/algorithm/dqn.py; csrc/actor_critic.hip).
+ *
+ * gops_dqn_backup: the whole no-grad half of dqn.py:138-140 in ONE launch, forward only, nothing stashed.  Per batch row:
+ *     q_targ [act_num] = q(obs2)                       the TARGET ActionValueDis' stack, act_num linear outputs
+ *     a_star = argmax_a q_targ[a]                      the LOWEST index among bit-equal maxima
+ *     backup = rew * reward_scale + gamma * (1 - done) * q_targ[a_star]
+ * Tiles, staging and the eight fp32 fmaf chains of the hidden layers are gops_ac_backup's; the act_num head outputs are the same
+ * chains in double - thread (row, g) forms outputs g, g + 256 / R, .. and parks them in LDS, thread (row, 0) takes the maximum over
+ * the doubles in index order - and every stored value is rounded once: the results are bitwise reproducible and a row's result
+ * depends neither on the batch size nor on the tile size.  (Rounding is monotone: q_targ[row, a_star] is the row's maximum of the
+ * stored fp32 values as well.)
+ * Accepted (gops_dqn_backup_workspace_bytes returns 0 otherwise, gops_dqn_backup GOPS_ERR_UNSUPPORTED): act_num 2 ..
+ * GOPS_DQN_MAX_ACTIONS, obs_dim <= 64, q: obs_dim -> .. -> act_num as gops_ac_backup accepts a network.  GOPS_ERR_BAD_ARG: NULL
+ * obs2 / rew / done / backup, batch < 1, a network whose output width is not act_num.  The same 256-byte workspace section as
+ * gops_ac_backup; workspace_bytes below it: GOPS_ERR_WORKSPACE.
+ * Outputs: backup [B]; optional (NULL): q_targ [B, act_num], a_star [B] (int32). */
+#define GOPS_DQN_MAX_ACTIONS 16
+struct GopsDqnBackup {
+    GopsMlp q;                   /* the TARGET network: obs_dim -> .. -> act_num */
+    int32_t act_num;
+    int32_t reserved;
+    double reward_scale, gamma;
+};
+typedef struct GopsDqnBackup GopsDqnBackup;
+size_t gops_dqn_backup_workspace_bytes(const GopsDqnBackup* desc, int32_t batch);
+int gops_dqn_backup(const GopsDqnBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done, float* backup,
+                    float* q_targ, int32_t* a_star, void* workspace, size_t workspace_bytes, void* stream);
+/* gops_dqn_loss: the seam between the forward and the backward of the live network in one launch.  q_all [B, act_num]: the ONLINE
+ * network on obs (gops_mlp_forward's output); act [B]: the replay buffer's float column, the index by truncation towards zero (as
+ * `a.to(torch.long)`); backup [B]; weight [B] or NULL (prioritized replay's importance weights; NULL = ones).  q_sel = q_all[b, act[b]]:
+ *     seed [B, act_num] = (2 / B) weight (q_sel - backup) in column act[b], an explicit 0 in every other (the DENSE seed of the output
+ *                         layer, for gops_mlp_backward)
+ *     abs_err [B]       = |q_sel - backup|                                                      (NULL: not wanted)
+ *     stats[0] = mean(weight (q_sel - backup)^2), stats[1] = mean(q_sel), stats[2] = the number of rows whose index lies outside
+ *     [0, act_num) - such a row (a NaN index included) gets an all-zero seed row and abs_err 0, adds nothing to the sums (the means
+ *     still divide by B) and reads and writes nothing outside its own row.
+ * `stats`: 8-byte aligned device memory of GOPS_DQN_LOSS_STATS_FLOATS floats, ALL ZERO before the first call (behind the results:
+ * the blocks' partial sums and a ticket the call leaves zero again), as for gops_ac_critic_loss; sums in double, in a fixed order
+ * that depends on B only (one block up to 8192 rows, else 64 blocks folded by the last one).
+ * GOPS_ERR_BAD_ARG: NULL q_all / act / backup / seed / stats, batch < 1, act_num < 1, a misaligned `stats`. */
+#define GOPS_DQN_LOSS_STATS_FLOATS 392
+int gops_dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int32_t act_num, int32_t batch,
+                  float* seed, float* abs_err, float* stats, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
