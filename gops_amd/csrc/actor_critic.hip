@@ -623,12 +623,15 @@ inline dim3 ac_grid(int B, int R) { return dim3((unsigned)((B + R - 1) / R)); }
 
 }  // namespace
 
-size_t ac_backup_workspace_bytes(const GopsAcBackup* d, int B) {
+extern "C" {
+
+size_t gops_ac_backup_workspace_bytes(const GopsAcBackup* d, int32_t B) {
     return ac_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(ac_shape(*d), B);
 }
 
-int ac_backup(const GopsAcBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* xi, float* backup,
-              float* a2, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
+int gops_ac_backup(const GopsAcBackup* d, int32_t B, const float* obs2, const float* rew, const float* done, const float* xi, float* backup,
+                   float* a2, float* q_targ, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = ac_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (!obs2 || !rew || !done || !backup || (d->smooth && !xi)) return GOPS_ERR_BAD_ARG;
@@ -647,19 +650,23 @@ int ac_backup(const GopsAcBackup* d, int B, const float* obs2, const float* rew,
     return (int)hipGetLastError();
 }
 
-int ac_critic_loss(const float* q, const float* backup, const float* weight, int nq, int B, float* seed, float* abs_err, float* stats,
-                   hipStream_t s) {
+int gops_ac_critic_loss(const float* q, const float* backup, const float* weight, int32_t nq, int32_t B, float* seed, float* abs_err,
+                        float* stats, void* stream) {
+    if (!q || !backup || !seed || !stats || B < 1 || nq < 1 || nq > 2) return GOPS_ERR_BAD_ARG;
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(ac_critic_loss_kernel, dim3(B <= ACL_ONE_BLOCK_MAX ? 1 : ACL_BLOCKS), dim3(256), 0, s, q, backup, weight, nq, B,
                        (float)(2.0 / B), seed, abs_err, stats);
     return (int)hipGetLastError();
 }
 
-size_t dqn_backup_workspace_bytes(const GopsDqnBackup* d, int B) {
+size_t gops_dqn_backup_workspace_bytes(const GopsDqnBackup* d, int32_t B) {
     return dqn_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(dqn_shape(*d), B);
 }
 
-int dqn_backup(const GopsDqnBackup* d, int B, const float* obs2, const float* rew, const float* done, float* backup, float* q_targ,
-               int* a_star, void* ws, size_t ws_bytes, hipStream_t s) {
+int gops_dqn_backup(const GopsDqnBackup* d, int32_t B, const float* obs2, const float* rew, const float* done, float* backup,
+                    float* q_targ, int32_t* a_star, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = dqn_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (!obs2 || !rew || !done || !backup) return GOPS_ERR_BAD_ARG;
@@ -678,19 +685,23 @@ int dqn_backup(const GopsDqnBackup* d, int B, const float* obs2, const float* re
     return (int)hipGetLastError();
 }
 
-int dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int N, int B, float* seed, float* abs_err,
-             float* stats, hipStream_t s) {
+int gops_dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int32_t N, int32_t B, float* seed,
+                  float* abs_err, float* stats, void* stream) {
+    if (!q_all || !act || !backup || !seed || !stats || B < 1 || N < 1) return GOPS_ERR_BAD_ARG;
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(dqn_loss_kernel, dim3(B <= ACL_ONE_BLOCK_MAX ? 1 : ACL_BLOCKS), dim3(256), 0, s, q_all, act, backup, weight, N, B,
                        (float)(2.0 / B), seed, abs_err, stats);
     return (int)hipGetLastError();
 }
 
-size_t soft_backup_workspace_bytes(const GopsSoftBackup* d, int B) {
+size_t gops_soft_backup_workspace_bytes(const GopsSoftBackup* d, int32_t B) {
     return soft_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(soft_shape(d->policy, d->q, 2), B);
 }
 
-int soft_backup(const GopsSoftBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
-                float* tq, float* tqs, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
+int gops_soft_backup(const GopsSoftBackup* d, int32_t B, const float* obs2, const float* rew, const float* done, const float* eps,
+                     const float* z, float* tq, float* tqs, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = soft_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (!obs2 || !rew || !done || !eps || !z || !tq || !tqs) return GOPS_ERR_BAD_ARG;
@@ -706,12 +717,13 @@ int soft_backup(const GopsSoftBackup* d, int B, const float* obs2, const float* 
     return (int)hipGetLastError();
 }
 
-size_t soft_q_backup_workspace_bytes(const GopsSoftQBackup* d, int B) {
+size_t gops_soft_q_backup_workspace_bytes(const GopsSoftQBackup* d, int32_t B) {
     return soft_q_check(d, B) != GOPS_OK ? 0 : ac_workspace_bytes(soft_shape(d->policy, d->q, d->n_q), B);
 }
 
-int soft_q_backup(const GopsSoftQBackup* d, int B, const float* obs2, const float* rew, const float* done, const float* eps, const float* z,
-                  float* backup, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, hipStream_t s) {
+int gops_soft_q_backup(const GopsSoftQBackup* d, int32_t B, const float* obs2, const float* rew, const float* done, const float* eps,
+                       const float* z, float* backup, float* a2, float* logp, float* q_targ, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = soft_q_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (!obs2 || !rew || !done || !eps || (d->distri && !z) || !backup) return GOPS_ERR_BAD_ARG;
@@ -727,3 +739,5 @@ int soft_q_backup(const GopsSoftQBackup* d, int B, const float* obs2, const floa
     rows_dispatch(R, [&]<int RR>() { launch_with_lds(soft_q_backup_kernel<RR>, ac_grid(B, RR), dim3(AC_THREADS), lds, s, qp); });
     return (int)hipGetLastError();
 }
+
+}  // extern "C"

@@ -1,5 +1,7 @@
-// Host side of the C ABI (include/gops_hip.h): argument checking, workspace carving, launch
-// sequencing.  Nothing here allocates device memory or synchronises the stream.
+// Host side of the rollout / value / MLP family of the C ABI (include/gops_hip.h) - gops_rollout_*, gops_value_*, gops_mlp_*,
+// gops_dw_plan_query - with gops_hip_version and gops_profile_*: argument checking, workspace carving, launch sequencing.  Every
+// other entry point is defined, with all of its checks, in the source that holds its kernels (launchers.h names what the sources
+// call in one another).  Nothing here allocates device memory or synchronises the stream.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,20 +60,6 @@ struct ProfScope {
 };
 
 // ---- workspace plan ----------------------------------------------------------------------------
-// GopsEnv.ref_c of the default MultiRefTrajModel parameters (ref_traj_data.py:18-37), folded like the reference folds
-// its Python scalars (double arithmetic, one rounding to fp32)
-void fill_ref_defaults(GopsEnv& e) {
-    if (e.ref_custom) return;
-    const double PI = 3.14159265358979323846, w = 2.0 * PI / 10.0;
-    const double c[24] = {-1.0 / w, w, 0.0, 5.0, 1.0 / w * 1.0, 1.0,                  // sine speed: A = 1, omega = 2 pi / 10, phi = 0, b = 5
-                          5.0,                                                      // constant speed
-                          1.5, w, 0.0,                                              // sine path
-                          5.0, 9.0, 14.0, 18.0, 0.0, 3.5, 3.5 / 4.0, -3.5 / 4.0,    // double lane
-                          10.0, 2.0 * 3.0 / 10.0, -2.0 * 3.0 / 10.0, 10.0 / 2.0,    // triangle: A = 3, T = 10
-                          100.0, 0.0};                                              // circle
-    for (int i = 0; i < 24; ++i) e.ref_c[i] = (float)c[i];
-}
-
 struct Carver {
     char* base;
     size_t off = 0;
@@ -204,7 +192,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     p.tail_unmasked = (desc.tail_value && desc.tail_unmasked) ? 1 : 0;
     p.env = e;
     lq_pad_env(p.env);   // (env_models.h: the LQ matrices with compile-time strides)
-    fill_ref_defaults(p.env);
+    fill_ref_defaults(p.env);   // (common.h, like lq_pad_env)
     p.open_loop = desc.open_loop == 2 ? 2 : (desc.open_loop ? 1 : 0);
     p.f16 = f16 ? 1 : 0;
     p.vflags = desc.variant_flags;
@@ -396,8 +384,6 @@ void dbg_print_backward(const RolloutParams& p) {
 inline void dbg_print_forward(const RolloutParams&) {}
 inline void dbg_print_backward(const RolloutParams&) {}
 #endif
-
-float pdt_of(const GopsEnv& e) { return (float)((double)e.pre_horizon * 0.1); }
 
 int run_forward(const GopsRolloutDesc& desc, const GopsRolloutIn& in, const GopsRolloutOut& out,
                 void* ws, size_t ws_bytes, hipStream_t s) {
@@ -819,77 +805,6 @@ int gops_mlp_backward_x(const GopsMlp* mlp, int32_t batch, const float* x, const
 
 int gops_hip_version(void) { return GOPS_HIP_ABI_VERSION; }
 
-size_t gops_poly_rollout_workspace_bytes(const GopsRolloutDesc* desc) { return desc ? poly_rollout_workspace_bytes(*desc) : 0; }
-
-int gops_poly_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const GopsRolloutOut* out, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    if (!desc || !in || !out) return GOPS_ERR_BAD_ARG;
-    return poly_rollout_forward(*desc, *in, *out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gops_poly_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v, const GopsMlpGrad* policy_grad,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-    if (!desc || !in || !policy_grad) return GOPS_ERR_BAD_ARG;
-    return poly_rollout_backward(*desc, grad_v, *policy_grad, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_poly_value_workspace_bytes(const GopsMlp* value, int32_t batch) { return value ? poly_value_workspace_bytes(*value, batch) : 0; }
-
-int gops_poly_value_forward(const GopsMlp* value, int32_t batch, const float* obs, float* v, void* stream) {
-    if (!value) return GOPS_ERR_BAD_ARG;
-    return poly_value_forward(*value, batch, obs, v, static_cast<hipStream_t>(stream));
-}
-
-int gops_poly_value_backward(const GopsMlp* value, int32_t batch, const float* obs, const float* grad_v, const GopsMlpGrad* grad,
-                             void* workspace, size_t workspace_bytes, void* stream) {
-    if (!value || !grad) return GOPS_ERR_BAD_ARG;
-    return poly_value_backward(*value, batch, obs, grad_v, *grad, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_rpi_state_bytes(int32_t env_kind, int32_t batch) { return rpi_state_bytes(env_kind, batch); }
-
-int gops_rpi_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const float* consts, float* weights,
-                      const float* target_weights, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
-                      double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream) {
-    return rpi_evaluate(env_kind, batch, max_steps, consts, weights, target_weights, max_step, reset_pool, state, state_bytes, lr,
-                        beta1, beta2, eps, result, trace, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_lips_workspace_bytes(const GopsLipsNet* net, int32_t batch) { return net ? lips_workspace_bytes(*net, batch) : 0; }
-
-int gops_lips_forward(const GopsLipsNet* net, int32_t batch, const float* obs, float* action, float* K, float* N, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-    if (net == nullptr) return GOPS_ERR_BAD_ARG;
-    return lips_forward(*net, batch, obs, action, K, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gops_lips_backward(const GopsLipsNet* net, int32_t batch, const float* obs, const float* grad_action, const GopsLipsGrad* grad,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (net == nullptr || grad == nullptr) return GOPS_ERR_BAD_ARG;
-    return lips_backward(*net, batch, obs, grad_action, *grad, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_rpi_mlp_state_bytes(int32_t env_kind, int32_t batch, const GopsMlp* value) { return rpi_mlp_state_bytes(env_kind, batch, value); }
-
-int gops_rpi_mlp_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, const float* consts, const GopsMlp* value,
-                          const GopsMlp* target, const float* max_step, const float* reset_pool, void* state, size_t state_bytes,
-                          double lr, double beta1, double beta2, double eps, float* result, float* trace, void* stream) {
-    return rpi_mlp_evaluate(env_kind, batch, max_steps, consts, value, target, max_step, reset_pool, state, state_bytes, lr, beta1,
-                            beta2, eps, result, trace, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps) {
-    return episode_workspace_bytes(env, policy, episodes, max_steps);
-}
-
-int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps, const GopsStepIO* init,
-                         const GopsEpisodeOut* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!env) return GOPS_ERR_BAD_ARG;
-    GopsEnv e = *env;
-    fill_ref_defaults(e);
-    return episode_rollout(&e, policy, episodes, max_steps, init, out, workspace, workspace_bytes, pdt_of(e), static_cast<hipStream_t>(stream));
-}
-
 size_t gops_rollout_workspace_bytes(const GopsRolloutDesc* desc) {
     if (desc == nullptr) return 0;
     Plan plan;
@@ -977,43 +892,6 @@ int gops_rollout_backward_open_loop_adj(const GopsRolloutDesc* desc, const GopsR
     return run_backward(*desc, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
-int gops_env_step(const GopsEnv* env, int32_t batch, const GopsStepIO* io, void* stream) {
-    if (!env || !io || batch < 1) return GOPS_ERR_BAD_ARG;
-    if (env->kind < GOPS_ENV_LQ || env->kind > GOPS_ENV_MOBILEROBOT) return GOPS_ERR_BAD_ARG;
-    if (env->kind == GOPS_ENV_MOBILEROBOT &&
-        (env->obs_dim != MOB_OBS || env->act_dim != 2 || env->n_constraint != 1 || env->scale_obs || !io->constraint)) return GOPS_ERR_BAD_ARG;
-    if (env->data_env && (env->kind == GOPS_ENV_PENDULUM || (env->kind == GOPS_ENV_VEH2DOF && env->cstr_err)))
-        return GOPS_ERR_UNSUPPORTED;   // these data envs are not restated
-    if (!io->obs || !io->action || !io->next_obs || !io->reward || !io->next_done) return GOPS_ERR_BAD_ARG;
-    if (env->kind == GOPS_ENV_VEH3DOF_SURR &&
-        (env->data_env || env->n_surr < (env->cstr_err ? 0 : 1) || env->n_surr > (env->cstr_err ? 0 : GOPS_MAX_SURR) ||
-         (env->cstr_err ? env->n_constraint != 2 : (env->n_constraint != 1 && env->n_constraint != 3)) ||
-         (env->n_surr > 0 && (!io->surr_state || !io->next_surr_state)) || !io->constraint)) return GOPS_ERR_BAD_ARG;
-    if (env_has_ref_table(env->kind) &&
-        (!io->state || !io->ref_points || !io->path_num || !io->u_num || !io->ref_time ||
-         !io->next_state || !io->next_ref_points || !io->next_ref_time)) return GOPS_ERR_BAD_ARG;
-    if (env->kind == GOPS_ENV_LQ && env->obs_dim > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED;
-    if (env->scale_obs && env->kind != GOPS_ENV_LQ && env->kind != GOPS_ENV_IDPENDULUM && env->kind < GOPS_ENV_CARTPOLE) return GOPS_ERR_UNSUPPORTED;
-    if (env->repeat_num < 0 || env->repeat_num > GOPS_MAX_REPEAT) return GOPS_ERR_BAD_ARG;
-    if (env->repeat_num > 1 && (env->data_env || (env->kind != GOPS_ENV_LQ && env->kind != GOPS_ENV_IDPENDULUM &&
-                                                  env->kind != GOPS_ENV_CARTPOLE && env->kind != GOPS_ENV_PENDULUM)))
-        return GOPS_ERR_UNSUPPORTED;
-    GopsEnv e = *env;
-    fill_ref_defaults(e);
-    return (int)launch_env_step(e, batch, *io, pdt_of(e), static_cast<hipStream_t>(stream));
-}
-
-int gops_env_constraint(const GopsEnv* env, int32_t batch, const GopsStepIO* io, void* stream) {
-    if (!env || !io || batch < 1 || !io->constraint) return GOPS_ERR_BAD_ARG;
-    const bool err = env->cstr_err != 0 && (env->kind == GOPS_ENV_VEH3DOF_SURR || env->kind == GOPS_ENV_VEH2DOF);
-    const bool surr = env->kind == GOPS_ENV_VEH3DOF_SURR && !env->cstr_err;
-    if (!err && !surr) return GOPS_ERR_UNSUPPORTED;   // the model defines no get_constraint
-    if (err && (!io->obs || env->n_constraint != (env->kind == GOPS_ENV_VEH2DOF ? 1 : 2))) return GOPS_ERR_BAD_ARG;
-    if (surr && (!io->state || !io->surr_state || env->n_surr < 1 || env->n_surr > GOPS_MAX_SURR ||
-                 (env->n_constraint != 1 && env->n_constraint != 3))) return GOPS_ERR_BAD_ARG;
-    return (int)launch_env_constraint(*env, batch, *io, static_cast<hipStream_t>(stream));
-}
-
 size_t gops_value_workspace_bytes(const GopsMlp* value, int32_t batch) {
     if (!value) return 0;
     const GopsRolloutDesc d = value_desc(*value, batch);
@@ -1055,165 +933,6 @@ int gops_value_backward_update(const GopsMlp* value, int32_t batch, const float*
     BackwardCall call;
     call.in = &in, call.grad_v = grad_v, call.grad = grad, call.tail = tail;
     return run_backward(d, call, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gops_adam_step(const GopsAdamTensors* tensors, GopsAdamState* state_dev, double beta1, double beta2,
-                   double eps, void* stream) {
-    if (!tensors || !state_dev || tensors->n < 1 || tensors->n > GOPS_ADAM_MAX_TENSORS) return GOPS_ERR_BAD_ARG;
-    for (int i = 0; i < tensors->n; ++i)
-        if (!tensors->param[i] || !tensors->grad[i] || !tensors->exp_avg[i] || !tensors->exp_avg_sq[i] ||
-            tensors->numel[i] < 1) return GOPS_ERR_BAD_ARG;
-    return (int)launch_adam(*tensors, state_dev, beta1, beta2, (float)eps, static_cast<hipStream_t>(stream));
-}
-
-int gops_polyak_update(const GopsAdamTensors* tensors, double tau, void* stream) {
-    if (!tensors || tensors->n < 1 || tensors->n > GOPS_ADAM_MAX_TENSORS) return GOPS_ERR_BAD_ARG;
-    for (int i = 0; i < tensors->n; ++i)
-        if (!tensors->param[i] || !tensors->grad[i] || tensors->numel[i] < 1) return GOPS_ERR_BAD_ARG;
-    return (int)launch_polyak(*tensors, (float)(1.0 - tau), (float)tau, static_cast<hipStream_t>(stream));
-}
-
-int gops_value_loss(const float* v, const float* target, int32_t n, float* grad, float* stats, void* stream) {
-    if (!v || !target || !stats || n < 1) return GOPS_ERR_BAD_ARG;
-    return (int)launch_batch_loss(v, target, n, (float)(2.0 / n), 1.f, grad, stats, static_cast<hipStream_t>(stream));
-}
-
-int gops_mean_loss(const float* x, int32_t n, double scale, float* stats, void* stream) {
-    if (!x || !stats || n < 1) return GOPS_ERR_BAD_ARG;
-    return (int)launch_batch_loss(x, nullptr, n, 0.f, (float)scale, nullptr, stats, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_ac_backup_workspace_bytes(const GopsAcBackup* desc, int32_t batch) { return ac_backup_workspace_bytes(desc, batch); }
-
-int gops_ac_backup(const GopsAcBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done, const float* xi,
-                   float* backup, float* a2, float* q_targ, void* workspace, size_t workspace_bytes, void* stream) {
-    return ac_backup(desc, batch, obs2, rew, done, xi, backup, a2, q_targ, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gops_ac_critic_loss(const float* q, const float* backup, const float* weight, int32_t n_q, int32_t batch, float* seed,
-                        float* abs_err, float* stats, void* stream) {
-    if (!q || !backup || !seed || !stats || batch < 1 || n_q < 1 || n_q > 2) return GOPS_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
-    return ac_critic_loss(q, backup, weight, n_q, batch, seed, abs_err, stats, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_dqn_backup_workspace_bytes(const GopsDqnBackup* desc, int32_t batch) { return dqn_backup_workspace_bytes(desc, batch); }
-
-int gops_dqn_backup(const GopsDqnBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done, float* backup,
-                    float* q_targ, int32_t* a_star, void* workspace, size_t workspace_bytes, void* stream) {
-    return dqn_backup(desc, batch, obs2, rew, done, backup, q_targ, a_star, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gops_dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int32_t act_num, int32_t batch,
-                  float* seed, float* abs_err, float* stats, void* stream) {
-    if (!q_all || !act || !backup || !seed || !stats || batch < 1 || act_num < 1) return GOPS_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
-    return dqn_loss(q_all, act, backup, weight, act_num, batch, seed, abs_err, stats, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_soft_backup_workspace_bytes(const GopsSoftBackup* desc, int32_t batch) { return soft_backup_workspace_bytes(desc, batch); }
-
-int gops_soft_backup(const GopsSoftBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,
-                     const float* eps_next, const float* z_next, float* target_q, float* target_q_sample, float* a2, float* logp,
-                     float* q_targ, void* workspace, size_t workspace_bytes, void* stream) {
-    return soft_backup(desc, batch, obs2, rew, done, eps_next, z_next, target_q, target_q_sample, a2, logp, q_targ, workspace,
-                       workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gops_dsact_critic_loss(const float* qraw, const float* target_q, const float* target_q_sample, int32_t batch, double tau_b,
-                           GopsDsactState* state, float* seed, float* stats, void* stream) {
-    if (!qraw || !target_q || !target_q_sample || !state || !seed || !stats || batch < 1) return GOPS_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
-    return dsact_critic_loss(qraw, target_q, target_q_sample, batch, tau_b, state, seed, stats, static_cast<hipStream_t>(stream));
-}
-
-size_t gops_soft_q_backup_workspace_bytes(const GopsSoftQBackup* desc, int32_t batch) { return soft_q_backup_workspace_bytes(desc, batch); }
-
-int gops_soft_q_backup(const GopsSoftQBackup* desc, int32_t batch, const float* obs2, const float* rew, const float* done,
-                       const float* eps_next, const float* z_next, float* backup, float* a2, float* logp, float* q_targ, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-    return soft_q_backup(desc, batch, obs2, rew, done, eps_next, z_next, backup, a2, logp, q_targ, workspace, workspace_bytes,
-                         static_cast<hipStream_t>(stream));
-}
-
-int gops_dsac_critic_loss(const float* qraw, const float* target_q, int32_t batch, int32_t bound, float* seed, float* stats, void* stream) {
-    if (!qraw || !target_q || !seed || !stats || batch < 1) return GOPS_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
-    return dsac_critic_loss(qraw, target_q, batch, bound != 0, seed, stats, static_cast<hipStream_t>(stream));
-}
-
-static bool tanh_gauss_ok(const GopsTanhGauss* d, int32_t batch) {
-    return d && batch >= 1 && d->act_dim >= 1 && d->act_dim <= GOPS_MAX_ACT;
-}
-
-int gops_tanh_gauss_forward(const GopsTanhGauss* desc, int32_t batch, const float* head, const float* eps, double target_entropy,
-                            float* act, float* logp, float* stats, void* stream) {
-    if (!tanh_gauss_ok(desc, batch) || !head || !eps || !act || !logp || !stats) return GOPS_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;
-    return tanh_gauss_forward(*desc, batch, head, eps, target_entropy, act, logp, stats, static_cast<hipStream_t>(stream));
-}
-
-int gops_tanh_gauss_backward(const GopsTanhGauss* desc, int32_t batch, const float* head, const float* eps, const float* g_act,
-                             const float* g_logp, float* g_head, void* stream) {
-    if (!tanh_gauss_ok(desc, batch) || !head || !eps || !g_act || !g_logp || !g_head) return GOPS_ERR_BAD_ARG;
-    return tanh_gauss_backward(*desc, batch, head, eps, g_act, g_logp, g_head, static_cast<hipStream_t>(stream));
-}
-
-int gops_ppo_loss(const GopsPpoLoss* desc, int32_t batch, const float* head_new, const float* v_new, const float* act, const float* logp_old,
-                  const float* adv, const float* ret, const float* val_old, const float* logits_old, const float* hyper, float* seed_head,
-                  float* seed_v, float* stats, void* stream) {
-    if (!desc || batch < 1 || desc->act_dim < 1 || desc->act_dim > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
-    if (!head_new || !v_new || !act || !logp_old || !adv || !ret || !val_old || !logits_old || !hyper || !seed_head || !seed_v || !stats)
-        return GOPS_ERR_BAD_ARG;
-    if (desc->loss_value_norm && batch < 2) return GOPS_ERR_BAD_ARG;       // the unbiased std of one return does not exist
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the norm and the partial sums behind the results are doubles
-    return ppo_loss(*desc, batch, head_new, v_new, act, logp_old, adv, ret, val_old, logits_old, hyper, seed_head, seed_v, stats,
-                    static_cast<hipStream_t>(stream));
-}
-
-int gops_adv_normalize(const float* adv, int32_t n, double eps, float* out, float* stats, void* stream) {
-    if (!adv || !out || !stats || n < 2) return GOPS_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;
-    return adv_normalize(adv, n, eps, out, stats, static_cast<hipStream_t>(stream));
-}
-
-int gops_gae(const float* rew, const float* val, const float* val_next, const float* done, const float* end, int32_t steps, int32_t n_envs,
-             double gamma, double gae_lambda, float* ret, float* adv, void* stream) {
-    if (!rew || !val || !val_next || !done || !end || !ret || !adv || steps < 1 || n_envs < 1) return GOPS_ERR_BAD_ARG;
-    return gae(rew, val, val_next, done, end, steps, n_envs, gamma, gae_lambda, ret, adv, static_cast<hipStream_t>(stream));
-}
-
-int gops_gauss_fisher_seed(const GopsMlp* policy, const GopsMlpGrad* tangent, int32_t batch, const float* x, double min_log_std,
-                           double max_log_std, float* seed, void* stream) {
-    if (!policy || !tangent || !x || !seed || batch < 1) return GOPS_ERR_BAD_ARG;
-    if (policy->n_layers < 1 || policy->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
-    return gauss_fisher_seed(*policy, *tangent, batch, x, min_log_std, max_log_std, seed, static_cast<hipStream_t>(stream));
-}
-
-int gops_trpo_surrogate(int32_t act_dim, int32_t batch, double min_log_std, double max_log_std, const float* head_new, const float* head_old,
-                        const float* act, const float* adv, const float* hyper, float* seed_head, float* stats, void* stream) {
-    if (batch < 1 || act_dim < 1 || act_dim > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
-    if (!head_new || !head_old || !act || !adv || !hyper || !stats) return GOPS_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(stats) & 7) return GOPS_ERR_BAD_ARG;   // the partial sums behind the results are doubles
-    return trpo_surrogate(batch, act_dim, min_log_std, max_log_std, head_new, head_old, act, adv, hyper, seed_head, stats,
-                          static_cast<hipStream_t>(stream));
-}
-
-static bool cg_state_ok(const GopsCgState* st, int32_t n) { return st && n >= 1 && !(reinterpret_cast<uintptr_t>(st) & 7); }
-
-int gops_cg_init(const float* g, float* x, float* r, float* p, int32_t n, double atol, GopsCgState* state, void* stream) {
-    if (!g || !x || !r || !p || !cg_state_ok(state, n)) return GOPS_ERR_BAD_ARG;
-    return cg_init(g, x, r, p, n, atol, state, static_cast<hipStream_t>(stream));
-}
-
-int gops_cg_step(float* p, float* Ap, float* x, float* r, int32_t n, double damping, double atol, GopsCgState* state, void* stream) {
-    if (!p || !Ap || !x || !r || !cg_state_ok(state, n)) return GOPS_ERR_BAD_ARG;
-    return cg_step(p, Ap, x, r, n, damping, atol, state, static_cast<hipStream_t>(stream));
-}
-
-int gops_cg_finish(const float* g, const float* x, float* step, int32_t n, const float* hyper, GopsCgState* state, void* stream) {
-    if (!g || !x || !step || !hyper || !cg_state_ok(state, n)) return GOPS_ERR_BAD_ARG;
-    return cg_finish(g, x, step, n, hyper, state, static_cast<hipStream_t>(stream));
 }
 
 void gops_profile_enable(int32_t on) {

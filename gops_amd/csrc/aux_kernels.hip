@@ -139,14 +139,46 @@ __global__ void env_constraint_kernel(const GopsEnv env, int B, const GopsStepIO
     for (int k = 0; k < nc; ++k) io.constraint[(size_t)b * nc + k] = sc.c[k];
 }
 
-hipError_t launch_env_constraint(const GopsEnv& env, int B, const GopsStepIO& io, hipStream_t s) {
-    hipLaunchKernelGGL(env_constraint_kernel, dim3((B + 127) / 128), dim3(128), 0, s, env, B, io);
-    return hipGetLastError();
+extern "C" {
+
+int gops_env_constraint(const GopsEnv* env, int32_t B, const GopsStepIO* io, void* stream) {
+    if (!env || !io || B < 1 || !io->constraint) return GOPS_ERR_BAD_ARG;
+    const bool err = env->cstr_err != 0 && (env->kind == GOPS_ENV_VEH3DOF_SURR || env->kind == GOPS_ENV_VEH2DOF);
+    const bool surr = env->kind == GOPS_ENV_VEH3DOF_SURR && !env->cstr_err;
+    if (!err && !surr) return GOPS_ERR_UNSUPPORTED;   // the model defines no get_constraint
+    if (err && (!io->obs || env->n_constraint != (env->kind == GOPS_ENV_VEH2DOF ? 1 : 2))) return GOPS_ERR_BAD_ARG;
+    if (surr && (!io->state || !io->surr_state || env->n_surr < 1 || env->n_surr > GOPS_MAX_SURR ||
+                 (env->n_constraint != 1 && env->n_constraint != 3))) return GOPS_ERR_BAD_ARG;
+    hipLaunchKernelGGL(env_constraint_kernel, dim3((B + 127) / 128), dim3(128), 0, static_cast<hipStream_t>(stream), *env, B, *io);
+    return (int)hipGetLastError();
 }
 
-hipError_t launch_env_step(const GopsEnv& env, int B, const GopsStepIO& io, float pdt, hipStream_t s) {
-    GopsEnv padded = env;
-    lq_pad_env(padded);
-    hipLaunchKernelGGL(env_step_kernel, dim3((B + 127) / 128), dim3(128), 0, s, padded, B, io, pdt);
-    return hipGetLastError();
+int gops_env_step(const GopsEnv* env, int32_t B, const GopsStepIO* io, void* stream) {
+    if (!env || !io || B < 1) return GOPS_ERR_BAD_ARG;
+    if (env->kind < GOPS_ENV_LQ || env->kind > GOPS_ENV_MOBILEROBOT) return GOPS_ERR_BAD_ARG;
+    if (env->kind == GOPS_ENV_MOBILEROBOT &&
+        (env->obs_dim != MOB_OBS || env->act_dim != 2 || env->n_constraint != 1 || env->scale_obs || !io->constraint)) return GOPS_ERR_BAD_ARG;
+    if (env->data_env && (env->kind == GOPS_ENV_PENDULUM || (env->kind == GOPS_ENV_VEH2DOF && env->cstr_err)))
+        return GOPS_ERR_UNSUPPORTED;   // these data envs are not restated
+    if (!io->obs || !io->action || !io->next_obs || !io->reward || !io->next_done) return GOPS_ERR_BAD_ARG;
+    if (env->kind == GOPS_ENV_VEH3DOF_SURR &&
+        (env->data_env || env->n_surr < (env->cstr_err ? 0 : 1) || env->n_surr > (env->cstr_err ? 0 : GOPS_MAX_SURR) ||
+         (env->cstr_err ? env->n_constraint != 2 : (env->n_constraint != 1 && env->n_constraint != 3)) ||
+         (env->n_surr > 0 && (!io->surr_state || !io->next_surr_state)) || !io->constraint)) return GOPS_ERR_BAD_ARG;
+    if (env_has_ref_table(env->kind) &&
+        (!io->state || !io->ref_points || !io->path_num || !io->u_num || !io->ref_time ||
+         !io->next_state || !io->next_ref_points || !io->next_ref_time)) return GOPS_ERR_BAD_ARG;
+    if (env->kind == GOPS_ENV_LQ && env->obs_dim > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED;
+    if (env->scale_obs && env->kind != GOPS_ENV_LQ && env->kind != GOPS_ENV_IDPENDULUM && env->kind < GOPS_ENV_CARTPOLE) return GOPS_ERR_UNSUPPORTED;
+    if (env->repeat_num < 0 || env->repeat_num > GOPS_MAX_REPEAT) return GOPS_ERR_BAD_ARG;
+    if (env->repeat_num > 1 && (env->data_env || (env->kind != GOPS_ENV_LQ && env->kind != GOPS_ENV_IDPENDULUM &&
+                                                  env->kind != GOPS_ENV_CARTPOLE && env->kind != GOPS_ENV_PENDULUM)))
+        return GOPS_ERR_UNSUPPORTED;
+    GopsEnv e = *env;   // the library's own copy: reference constants filled, LQ matrices padded
+    fill_ref_defaults(e);
+    lq_pad_env(e);
+    hipLaunchKernelGGL(env_step_kernel, dim3((B + 127) / 128), dim3(128), 0, static_cast<hipStream_t>(stream), e, B, *io, pdt_of(e));
+    return (int)hipGetLastError();
 }
+
+}  // extern "C"

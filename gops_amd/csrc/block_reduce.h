@@ -6,10 +6,15 @@
 // grid_fold is that sequence for sums and what the kernels call; block_fold and last_block stand alone only in dsact.hip's mixed
 // sum-and-minimum fold and in dw_gemm.hip's one-block sum.
 #pragma once
+#include <stdint.h>
+
 #include <hip/hip_runtime.h>
 
 // Up to here ONE block forms the sums (<= 32 elements per thread, no partials / ticket round); beyond it the kernels launch 64.
 #define LOSS_ONE_BLOCK_MAX 8192
+
+// What an entry point asks of the `stats` / state buffer it hands to these folds: the partial sums behind the results are doubles.
+inline bool stats_aligned(const void* stats) { return (reinterpret_cast<uintptr_t>(stats) & 7) == 0; }
 
 // s[i] <- the block's sum (MIN: minimum) of s[i], in every thread.  red: N rows of 4 doubles of LDS, reusable right after.
 template <int N, bool MIN>

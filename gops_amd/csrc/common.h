@@ -355,6 +355,22 @@ inline void lq_pad_env(GopsEnv& e) {
     for (int j = m; j < GOPS_MAX_ACT; ++j) e.lq_R[j] = 0.f;
 }
 
+// Host side: GopsEnv.ref_c of the default MultiRefTrajModel parameters (ref_traj_data.py:18-37), folded like the reference folds
+// its Python scalars (double arithmetic, one rounding to fp32); in place, on the library's own copy
+inline void fill_ref_defaults(GopsEnv& e) {
+    if (e.ref_custom) return;
+    const double PI = 3.14159265358979323846, w = 2.0 * PI / 10.0;
+    const double c[24] = {-1.0 / w, w, 0.0, 5.0, 1.0 / w * 1.0, 1.0,                  // sine speed: A = 1, omega = 2 pi / 10, phi = 0, b = 5
+                          5.0,                                                      // constant speed
+                          1.5, w, 0.0,                                              // sine path
+                          5.0, 9.0, 14.0, 18.0, 0.0, 3.5, 3.5 / 4.0, -3.5 / 4.0,    // double lane
+                          10.0, 2.0 * 3.0 / 10.0, -2.0 * 3.0 / 10.0, 10.0 / 2.0,    // triangle: A = 3, T = 10
+                          100.0, 0.0};                                              // circle
+    for (int i = 0; i < 24; ++i) e.ref_c[i] = (float)c[i];
+}
+// Host side: the preview length of the reference-table envs in seconds
+inline float pdt_of(const GopsEnv& e) { return (float)((double)e.pre_horizon * 0.1); }
+
 // LDS copy of the env description (kernels whose env phases read ~100 of its scalars per step: read through the parameter
 // pointer they do not fit the SGPR file - hundreds of lane spills per step; from LDS they are broadcast reads with immediate
 // offsets).  Used by the 64-row half kernels and the pyth_lq instantiations of the streamed plane-split kernels.

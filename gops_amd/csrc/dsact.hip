@@ -16,7 +16,7 @@
 #include <stdint.h>
 
 #include "block_reduce.h"
-#include "launchers.h"
+#include "common.h"
 #include "soft_math.h"
 
 namespace {
@@ -213,10 +213,17 @@ TgParams tg_params(const GopsTanhGauss& d, int B) {
     return p;
 }
 
+bool tanh_gauss_ok(const GopsTanhGauss* d, int B) { return d && B >= 1 && d->act_dim >= 1 && d->act_dim <= GOPS_MAX_ACT; }
+
 }  // namespace
 
-int dsact_critic_loss(const float* qraw, const float* tq, const float* tqs, int B, double tau_b, GopsDsactState* st, float* seed,
-                      float* stats, hipStream_t s) {
+extern "C" {
+
+int gops_dsact_critic_loss(const float* qraw, const float* tq, const float* tqs, int32_t B, double tau_b, GopsDsactState* st, float* seed,
+                           float* stats, void* stream) {
+    if (!qraw || !tq || !tqs || !st || !seed || !stats || B < 1) return GOPS_ERR_BAD_ARG;
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (B <= DS_ONE_BLOCK_MAX) {
         hipLaunchKernelGGL(dsact_loss_kernel, dim3(1), dim3(256), 0, s, qraw, tq, tqs, B, tau_b, 3, st, seed, stats);
     } else {
@@ -226,24 +233,34 @@ int dsact_critic_loss(const float* qraw, const float* tq, const float* tqs, int 
     return (int)hipGetLastError();
 }
 
-int dsac_critic_loss(const float* qraw, const float* tq, int B, int bound, float* seed, float* stats, hipStream_t s) {
+int gops_dsac_critic_loss(const float* qraw, const float* tq, int32_t B, int32_t bound, float* seed, float* stats, void* stream) {
+    if (!qraw || !tq || !seed || !stats || B < 1) return GOPS_ERR_BAD_ARG;
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (B <= DS_ONE_BLOCK_MAX) {
-        hipLaunchKernelGGL(dsac_loss_kernel, dim3(1), dim3(256), 0, s, qraw, tq, B, bound, 3, seed, stats);
+        hipLaunchKernelGGL(dsac_loss_kernel, dim3(1), dim3(256), 0, s, qraw, tq, B, bound != 0, 3, seed, stats);
     } else {
-        hipLaunchKernelGGL(dsac_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, B, bound, 1, seed, stats);
-        hipLaunchKernelGGL(dsac_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, B, bound, 2, seed, stats);
+        hipLaunchKernelGGL(dsac_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, B, bound != 0, 1, seed, stats);
+        hipLaunchKernelGGL(dsac_loss_kernel, dim3(DS_BLOCKS), dim3(256), 0, s, qraw, tq, B, bound != 0, 2, seed, stats);
     }
     return (int)hipGetLastError();
 }
 
-int tanh_gauss_forward(const GopsTanhGauss& d, int B, const float* head, const float* eps, double target_entropy, float* act, float* logp,
-                       float* stats, hipStream_t s) {
-    hipLaunchKernelGGL(tanh_gauss_fwd_kernel, dim3(ds_grid(B)), dim3(256), 0, s, tg_params(d, B), head, eps, target_entropy, act, logp, stats);
+int gops_tanh_gauss_forward(const GopsTanhGauss* d, int32_t B, const float* head, const float* eps, double target_entropy, float* act,
+                            float* logp, float* stats, void* stream) {
+    if (!tanh_gauss_ok(d, B) || !head || !eps || !act || !logp || !stats) return GOPS_ERR_BAD_ARG;
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(tanh_gauss_fwd_kernel, dim3(ds_grid(B)), dim3(256), 0, s, tg_params(*d, B), head, eps, target_entropy, act, logp, stats);
     return (int)hipGetLastError();
 }
 
-int tanh_gauss_backward(const GopsTanhGauss& d, int B, const float* head, const float* eps, const float* g_act, const float* g_logp,
-                        float* g_head, hipStream_t s) {
-    hipLaunchKernelGGL(tanh_gauss_bwd_kernel, dim3(ds_grid(B)), dim3(256), 0, s, tg_params(d, B), head, eps, g_act, g_logp, g_head);
+int gops_tanh_gauss_backward(const GopsTanhGauss* d, int32_t B, const float* head, const float* eps, const float* g_act,
+                             const float* g_logp, float* g_head, void* stream) {
+    if (!tanh_gauss_ok(d, B) || !head || !eps || !g_act || !g_logp || !g_head) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(tanh_gauss_bwd_kernel, dim3(ds_grid(B)), dim3(256), 0, s, tg_params(*d, B), head, eps, g_act, g_logp, g_head);
     return (int)hipGetLastError();
 }
+
+}  // extern "C"

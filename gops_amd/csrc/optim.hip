@@ -77,13 +77,6 @@ __global__ __launch_bounds__(256) void polyak_kernel(const GopsAdamTensors T, fl
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         t[i] = polyak_element(t[i], o[i], omt, tau);
 }
-hipError_t launch_polyak(const GopsAdamTensors& T, float omt, float tau, hipStream_t s) {
-    long long nmax = 1;
-    for (int i = 0; i < T.n; ++i) nmax = std::max<long long>(nmax, T.numel[i]);
-    const int bx = (int)std::min<long long>((nmax + 255) / 256, 64);
-    hipLaunchKernelGGL(polyak_kernel, dim3(bx, T.n), dim3(256), 0, s, T, omt, tau);
-    return hipGetLastError();
-}
 
 // Loss scalars of a batch in ONE launch (they were three torch reductions + three elementwise passes per INFADP update pair:
 // ~10 % of a cfg5 fp16 update).  a, b: [n]; grad (nullable) <- gsc * (a - b);  stats[0] <- sum((a - b)^2) / n (b null: sc0 * sum(a) / n),
@@ -133,12 +126,41 @@ hipError_t launch_batch_loss(const float* a, const float* b, int n, float gsc, f
     return hipGetLastError();
 }
 
-hipError_t launch_adam(const GopsAdamTensors& T, GopsAdamState* st, double beta1, double beta2, float eps,
-                       hipStream_t s) {
+extern "C" {
+
+int gops_adam_step(const GopsAdamTensors* tensors, GopsAdamState* st, double beta1, double beta2, double eps, void* stream) {
+    if (!tensors || !st || tensors->n < 1 || tensors->n > GOPS_ADAM_MAX_TENSORS) return GOPS_ERR_BAD_ARG;
+    const GopsAdamTensors& T = *tensors;
+    for (int i = 0; i < T.n; ++i)
+        if (!T.param[i] || !T.grad[i] || !T.exp_avg[i] || !T.exp_avg_sq[i] || T.numel[i] < 1) return GOPS_ERR_BAD_ARG;
     long long nmax = 1;
     for (int i = 0; i < T.n; ++i) nmax = T.numel[i] > nmax ? T.numel[i] : nmax;
     int bx = (int)((nmax + 1023) / 1024);   // >= 4 elements per thread of the largest tensor
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(adam_kernel, dim3(bx, T.n), dim3(256), 0, s, T, st, beta1, beta2, eps);
-    return hipGetLastError();
+    hipLaunchKernelGGL(adam_kernel, dim3(bx, T.n), dim3(256), 0, static_cast<hipStream_t>(stream), T, st, beta1, beta2, (float)eps);
+    return (int)hipGetLastError();
 }
+
+int gops_polyak_update(const GopsAdamTensors* tensors, double tau, void* stream) {
+    if (!tensors || tensors->n < 1 || tensors->n > GOPS_ADAM_MAX_TENSORS) return GOPS_ERR_BAD_ARG;
+    const GopsAdamTensors& T = *tensors;
+    for (int i = 0; i < T.n; ++i)
+        if (!T.param[i] || !T.grad[i] || T.numel[i] < 1) return GOPS_ERR_BAD_ARG;
+    long long nmax = 1;
+    for (int i = 0; i < T.n; ++i) nmax = std::max<long long>(nmax, T.numel[i]);
+    const int bx = (int)std::min<long long>((nmax + 255) / 256, 64);
+    hipLaunchKernelGGL(polyak_kernel, dim3(bx, T.n), dim3(256), 0, static_cast<hipStream_t>(stream), T, (float)(1.0 - tau), (float)tau);
+    return (int)hipGetLastError();
+}
+
+int gops_value_loss(const float* v, const float* target, int32_t n, float* grad, float* stats, void* stream) {
+    if (!v || !target || !stats || n < 1) return GOPS_ERR_BAD_ARG;
+    return (int)launch_batch_loss(v, target, n, (float)(2.0 / n), 1.f, grad, stats, static_cast<hipStream_t>(stream));
+}
+
+int gops_mean_loss(const float* x, int32_t n, double scale, float* stats, void* stream) {
+    if (!x || !stats || n < 1) return GOPS_ERR_BAD_ARG;
+    return (int)launch_batch_loss(x, nullptr, n, 0.f, (float)scale, nullptr, stats, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

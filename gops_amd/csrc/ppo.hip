@@ -18,7 +18,7 @@
 #include <stdint.h>
 
 #include "block_reduce.h"
-#include "launchers.h"
+#include "common.h"
 #include "gauss_math.h"
 
 namespace {
@@ -185,12 +185,20 @@ __global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ rew,
 
 }  // namespace
 
-int ppo_loss(const GopsPpoLoss& d, int M, const float* head_new, const float* v_new, const float* act, const float* logp_old, const float* adv,
-             const float* ret, const float* val_old, const float* logits_old, const float* hyper, float* seed_head, float* seed_v, float* stats,
-             hipStream_t s) {
+extern "C" {
+
+int gops_ppo_loss(const GopsPpoLoss* d, int32_t M, const float* head_new, const float* v_new, const float* act, const float* logp_old,
+                  const float* adv, const float* ret, const float* val_old, const float* logits_old, const float* hyper, float* seed_head,
+                  float* seed_v, float* stats, void* stream) {
+    if (!d || M < 1 || d->act_dim < 1 || d->act_dim > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (!head_new || !v_new || !act || !logp_old || !adv || !ret || !val_old || !logits_old || !hyper || !seed_head || !seed_v || !stats)
+        return GOPS_ERR_BAD_ARG;
+    if (d->loss_value_norm && M < 2) return GOPS_ERR_BAD_ARG;   // the unbiased std of one return does not exist
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;         // (the norm behind the results is a double too)
+    hipStream_t s = static_cast<hipStream_t>(stream);
     PpoParams p;
-    p.M = M, p.A = d.act_dim, p.value_clip = d.loss_value_clip != 0, p.value_norm = d.loss_value_norm != 0;
-    p.min_ls = d.min_log_std, p.max_ls = d.max_log_std;
+    p.M = M, p.A = d->act_dim, p.value_clip = d->loss_value_clip != 0, p.value_norm = d->loss_value_norm != 0;
+    p.min_ls = d->min_log_std, p.max_ls = d->max_log_std;
     const dim3 one(1), many(PPO_BLOCKS), threads(256);
 #define PPO_LAUNCH(grid, phases) \
     hipLaunchKernelGGL(ppo_loss_kernel, grid, threads, 0, s, p, phases, head_new, v_new, act, logp_old, adv, ret, val_old, logits_old, hyper, seed_head, seed_v, stats)
@@ -206,7 +214,10 @@ int ppo_loss(const GopsPpoLoss& d, int M, const float* head_new, const float* v_
     return (int)hipGetLastError();
 }
 
-int adv_normalize(const float* adv, int n, double eps, float* out, float* stats, hipStream_t s) {
+int gops_adv_normalize(const float* adv, int32_t n, double eps, float* out, float* stats, void* stream) {
+    if (!adv || !out || !stats || n < 2) return GOPS_ERR_BAD_ARG;
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (n <= LOSS_ONE_BLOCK_MAX) {
         hipLaunchKernelGGL(adv_normalize_kernel, dim3(1), dim3(256), 0, s, adv, n, eps, 3, out, stats);
     } else {
@@ -216,8 +227,12 @@ int adv_normalize(const float* adv, int n, double eps, float* out, float* stats,
     return (int)hipGetLastError();
 }
 
-int gae(const float* rew, const float* val, const float* val_next, const float* done, const float* end, int T, int N, double gamma,
-        double lambda, float* ret, float* adv, hipStream_t s) {
+int gops_gae(const float* rew, const float* val, const float* val_next, const float* done, const float* end, int32_t T, int32_t N,
+             double gamma, double lambda, float* ret, float* adv, void* stream) {
+    if (!rew || !val || !val_next || !done || !end || !ret || !adv || T < 1 || N < 1) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rew, val, val_next, done, end, T, N, gamma, lambda, ret, adv);
     return (int)hipGetLastError();
 }
+
+}  // extern "C"

@@ -20,7 +20,7 @@
 #include <algorithm>
 
 #include "env_step.h"
-#include "launchers.h"
+#include "common.h"
 
 namespace {
 
@@ -286,15 +286,17 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
 
 }  // namespace
 
-size_t episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int E, int T) {
+extern "C" {
+
+size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T) {
     if (episode_check(env, policy, E, T) != GOPS_OK) return 0;
     EpisodeParams p;
     if (episode_lds(*policy, p) == 0) return 0;
     return episode_layout(*env, E).bytes;
 }
 
-int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, const GopsStepIO* init, const GopsEpisodeOut* out, void* ws,
-                    size_t ws_bytes, float pdt, hipStream_t s) {
+int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T, const GopsStepIO* init, const GopsEpisodeOut* out,
+                         void* ws, size_t ws_bytes, void* stream) {
     const int rc = episode_check(env, policy, E, T);
     if (rc != GOPS_OK) return rc;
     if (!init || !out || !init->obs || !out->ret || !out->length || !out->terminated) return GOPS_ERR_BAD_ARG;
@@ -306,7 +308,8 @@ int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, con
     if (lds == 0) return GOPS_ERR_UNSUPPORTED;
     const EpisodeLayout l = episode_layout(*env, E);
     if (!ws || ws_bytes < l.bytes) return GOPS_ERR_WORKSPACE;
-    p.env = *env;   // (the caller - api.hip - has filled the reference constants)
+    p.env = *env;
+    fill_ref_defaults(p.env);
     lq_pad_env(p.env);
     p.E = E, p.T = T, p.O = env->obs_dim, p.A = env->act_dim;
     p.fh = policy->sizes[0] == env->obs_dim + 1;
@@ -318,7 +321,7 @@ int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, con
     }
     p.state_dim = env->kind == GOPS_ENV_VEH3DOFCONTI ? 6 : env->kind == GOPS_ENV_VEH2DOF ? 4 : 0;
     p.ref_floats = env->kind == GOPS_ENV_VEH3DOFCONTI ? (env->pre_horizon + 1) * 4 : env->kind == GOPS_ENV_VEH2DOF ? (env->pre_horizon + 1) * 2 : 0;
-    p.pdt = pdt;
+    p.pdt = pdt_of(*env);
     p.init = *init;
     float* f = static_cast<float*>(ws);
     for (int i = 0; i < 2; ++i) {
@@ -329,6 +332,8 @@ int episode_rollout(const GopsEnv* env, const GopsMlp* policy, int E, int T, con
     }
     p.action = f + l.action, p.reward = f + l.reward, p.done = f + l.done;
     p.out = *out;
-    launch_with_lds(episode_kernel, dim3((unsigned)((E + GOPS_TILE - 1) / GOPS_TILE)), dim3(EP_THREADS), lds, s, p);
+    launch_with_lds(episode_kernel, dim3((unsigned)((E + GOPS_TILE - 1) / GOPS_TILE)), dim3(EP_THREADS), lds, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
 }
+
+}  // extern "C"

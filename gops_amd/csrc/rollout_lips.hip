@@ -547,12 +547,18 @@ template <int N> static void lips_launch_bwd(const LipsParams& p, int blocks, si
         default: FN<8>(__VA_ARGS__); break;     \
     }
 
-size_t lips_workspace_bytes(const GopsLipsNet& d, int B) {
-    if (lips_check(d, B) != GOPS_OK) return 0;
-    return lips_plan(d, B).bytes;
+extern "C" {
+
+size_t gops_lips_workspace_bytes(const GopsLipsNet* net, int32_t B) {
+    if (!net || lips_check(*net, B) != GOPS_OK) return 0;
+    return lips_plan(*net, B).bytes;
 }
 
-int lips_forward(const GopsLipsNet& d, int B, const float* obs, float* action, float* K, float* N, void* ws, size_t bytes, hipStream_t s) {
+int gops_lips_forward(const GopsLipsNet* net, int32_t B, const float* obs, float* action, float* K, float* N, void* ws, size_t bytes,
+                      void* stream) {
+    if (net == nullptr) return GOPS_ERR_BAD_ARG;
+    const GopsLipsNet& d = *net;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     const int rc = lips_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (obs == nullptr || action == nullptr) return GOPS_ERR_BAD_ARG;
@@ -566,8 +572,12 @@ int lips_forward(const GopsLipsNet& d, int B, const float* obs, float* action, f
     return e == hipSuccess ? GOPS_OK : (int)e;
 }
 
-int lips_backward(const GopsLipsNet& d, int B, const float* obs, const float* grad_action, const GopsLipsGrad& g, void* ws, size_t bytes,
-                  hipStream_t s) {
+int gops_lips_backward(const GopsLipsNet* net, int32_t B, const float* obs, const float* grad_action, const GopsLipsGrad* grad, void* ws,
+                       size_t bytes, void* stream) {
+    if (net == nullptr || grad == nullptr) return GOPS_ERR_BAD_ARG;
+    const GopsLipsNet& d = *net;
+    const GopsLipsGrad& g = *grad;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     const int rc = lips_check(d, B);
     if (rc != GOPS_OK) return rc;
     if (obs == nullptr || grad_action == nullptr) return GOPS_ERR_BAD_ARG;
@@ -639,3 +649,5 @@ int lips_backward(const GopsLipsNet& d, int B, const float* obs, const float* gr
     e = launch_reduce(rj_k, s);
     return e == hipSuccess ? GOPS_OK : (int)e;
 }
+
+}  // extern "C"

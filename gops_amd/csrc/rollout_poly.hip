@@ -484,9 +484,9 @@ static PolyPlan poly_plan(const GopsRolloutDesc& d) {
     return pl;
 }
 
-size_t poly_rollout_workspace_bytes(const GopsRolloutDesc& d) {
-    if (poly_check_desc(d) != GOPS_OK) return 0;
-    return poly_plan(d).bytes;
+extern "C" size_t gops_poly_rollout_workspace_bytes(const GopsRolloutDesc* desc) {
+    if (!desc || poly_check_desc(*desc) != GOPS_OK) return 0;
+    return poly_plan(*desc).bytes;
 }
 
 static PolyParams poly_params(const GopsRolloutDesc& d, const PolyPlan& pl, void* ws) {
@@ -535,8 +535,15 @@ template <int E, int N, int D> struct PolyBwd {
     }
 };
 
-int poly_rollout_forward(const GopsRolloutDesc& d, const GopsRolloutIn& in, const GopsRolloutOut& out, void* ws, size_t bytes,
-                         hipStream_t s) {
+extern "C" {
+
+int gops_poly_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in_p, const GopsRolloutOut* out_p, void* ws, size_t bytes,
+                              void* stream) {
+    if (!desc || !in_p || !out_p) return GOPS_ERR_BAD_ARG;
+    const GopsRolloutDesc& d = *desc;
+    const GopsRolloutIn& in = *in_p;
+    const GopsRolloutOut& out = *out_p;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = poly_check_desc(d);
     if (rc != GOPS_OK) return rc;
     if (in.obs == nullptr || out.v_pi == nullptr) return GOPS_ERR_BAD_ARG;
@@ -549,7 +556,12 @@ int poly_rollout_forward(const GopsRolloutDesc& d, const GopsRolloutIn& in, cons
     return e == hipSuccess ? GOPS_OK : (int)e;
 }
 
-int poly_rollout_backward(const GopsRolloutDesc& d, const float* grad_v, const GopsMlpGrad& g, void* ws, size_t bytes, hipStream_t s) {
+int gops_poly_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v, const GopsMlpGrad* grad,
+                               void* ws, size_t bytes, void* stream) {
+    if (!desc || !in || !grad) return GOPS_ERR_BAD_ARG;   // (`in` is not read: the forward stashed what the sweep needs)
+    const GopsRolloutDesc& d = *desc;
+    const GopsMlpGrad& g = *grad;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = poly_check_desc(d);
     if (rc != GOPS_OK) return rc;
     if (!d.need_grad || grad_v == nullptr || g.weight[0] == nullptr) return GOPS_ERR_BAD_ARG;
@@ -570,13 +582,18 @@ int poly_rollout_backward(const GopsRolloutDesc& d, const float* grad_v, const G
     return e == hipSuccess ? GOPS_OK : (int)e;
 }
 
-size_t poly_value_workspace_bytes(const GopsMlp& v, int B) {
+size_t gops_poly_value_workspace_bytes(const GopsMlp* value, int32_t B) {
+    if (!value) return 0;
+    const GopsMlp& v = *value;
     if (B < 1 || poly_check_value(v, v.sizes[0]) != GOPS_OK) return 0;
     const int K = v.sizes[0] * (v.sizes[0] + 1) / 2;
     return align256((size_t)poly_blocks(B) * K * sizeof(float)) + align256((size_t)poly_blocks(B) * sizeof(float));
 }
 
-int poly_value_forward(const GopsMlp& v, int B, const float* obs, float* out, hipStream_t s) {
+int gops_poly_value_forward(const GopsMlp* value, int32_t B, const float* obs, float* out, void* stream) {
+    if (!value) return GOPS_ERR_BAD_ARG;
+    const GopsMlp& v = *value;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (B < 1 || obs == nullptr || out == nullptr) return GOPS_ERR_BAD_ARG;
     const int rc = poly_check_value(v, v.sizes[0]);
     if (rc != GOPS_OK) return rc;
@@ -594,13 +611,17 @@ int poly_value_forward(const GopsMlp& v, int B, const float* obs, float* out, hi
     return e == hipSuccess ? GOPS_OK : (int)e;
 }
 
-int poly_value_backward(const GopsMlp& v, int B, const float* obs, const float* grad_v, const GopsMlpGrad& g, void* ws, size_t bytes,
-                        hipStream_t s) {
+int gops_poly_value_backward(const GopsMlp* value, int32_t B, const float* obs, const float* grad_v, const GopsMlpGrad* grad, void* ws,
+                             size_t bytes, void* stream) {
+    if (!value || !grad) return GOPS_ERR_BAD_ARG;
+    const GopsMlp& v = *value;
+    const GopsMlpGrad& g = *grad;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (B < 1 || obs == nullptr || grad_v == nullptr || g.weight[0] == nullptr) return GOPS_ERR_BAD_ARG;
     const int rc = poly_check_value(v, v.sizes[0]);
     if (rc != GOPS_OK) return rc;
     if ((v.bias[0] != nullptr) != (g.bias[0] != nullptr)) return GOPS_ERR_BAD_ARG;
-    const size_t need = poly_value_workspace_bytes(v, B);
+    const size_t need = gops_poly_value_workspace_bytes(value, B);
     if (ws == nullptr || bytes < need) return GOPS_ERR_WORKSPACE;
     const int n = v.sizes[0], K = n * (n + 1) / 2, nb = poly_blocks(B);
     float* pw = static_cast<float*>(ws);
@@ -624,3 +645,5 @@ int poly_value_backward(const GopsMlp& v, int B, const float* obs, const float* 
     e = launch_reduce(jobs, s);
     return e == hipSuccess ? GOPS_OK : (int)e;
 }
+
+}  // extern "C"

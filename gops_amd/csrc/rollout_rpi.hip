@@ -14,7 +14,7 @@
 // step with the raw values, done / time-limit flags, the Hamiltonian h = U(x, u', w') + dV/dx . f(x, u', w') at the PRE-step state
 // with the wrapped values (ScaleAction / ClipAction, create_env_model's chain) and the CURRENT weights, loss mean|h|, gradient
 // mean sign(h) d(dV/dx . f)/dw (sign(0) = 0; the bias has none), Adam, the held-out mean|h| with the new weights, the reset select.
-#include "launchers.h"
+#include "common.h"
 #include "rpi_env.h"
 
 namespace {
@@ -180,19 +180,22 @@ __global__ __launch_bounds__(GOPS_RPI_MAX_BATCH) void rpi_evaluate_kernel(const 
 
 }  // namespace
 
-size_t rpi_state_bytes(int kind, int B) {
+extern "C" {
+
+size_t gops_rpi_state_bytes(int32_t kind, int32_t B) {
     const int S = rpi_state_dim(kind);
     if (S == 0 || B < 1 || B > GOPS_RPI_MAX_BATCH) return 0;
     return sizeof(float) * ((size_t)GOPS_RPI_STATE_HEADER + (size_t)(S + 2) * B);
 }
 
-int rpi_evaluate(int kind, int B, int max_steps, const float* consts, float* w, const float* wt, const float* max_step,
-                 const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, float* result,
-                 float* trace, hipStream_t s) {
+int gops_rpi_evaluate(int32_t kind, int32_t B, int32_t max_steps, const float* consts, float* w, const float* wt, const float* max_step,
+                      const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps, float* result,
+                      float* trace, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (rpi_state_dim(kind) == 0 || B > GOPS_RPI_MAX_BATCH) return GOPS_ERR_UNSUPPORTED;
     if (B < 1 || max_steps < 1 || max_steps > GOPS_RPI_MAX_STEPS) return GOPS_ERR_BAD_ARG;
     if (!consts || !w || !wt || !max_step || !pool || !state || !result) return GOPS_ERR_BAD_ARG;
-    if (state_bytes < rpi_state_bytes(kind, B)) return GOPS_ERR_WORKSPACE;
+    if (state_bytes < gops_rpi_state_bytes(kind, B)) return GOPS_ERR_WORKSPACE;
     RpiParams p;
     for (int i = 0; i < GOPS_RPI_CONST_COUNT; ++i) p.c[i] = consts[i];
     p.B = B, p.max_steps = max_steps, p.w = w, p.wt = wt, p.max_step = max_step, p.pool = pool;
@@ -204,3 +207,5 @@ int rpi_evaluate(int kind, int B, int max_steps, const float* consts, float* w, 
     else rpi_evaluate_kernel<GOPS_RPI_ENV_SUSPENSION><<<1, block, 0, s>>>(p);
     return (int)hipGetLastError();
 }
+
+}  // extern "C"

@@ -27,7 +27,7 @@
 //   layer 1 of the tile: a_1, a'_1, act'(z_1), act''(z_1) z'_1, [unit][row] at stride 65   4 x 4 160 floats   66 560 B
 //   layer 2 adjoints adj z_2, adj z'_2, [unit][row] at stride 64                           2 x 4 096 floats   32 768 B
 //   x, f [4][64], U, seed [64], partial sums [4][4][64], db_2, dW_L [64], 4 scalars                 2 052 floats    8 208 B
-#include "launchers.h"
+#include "common.h"
 #include "rpi_env.h"
 
 namespace {
@@ -557,15 +557,18 @@ void rpi_mlp_launch(int nh, int act, const RpiMlpParams& p, hipStream_t s) {
 
 }  // namespace
 
-size_t rpi_mlp_state_bytes(int kind, int B, const GopsMlp* v) {
+extern "C" {
+
+size_t gops_rpi_mlp_state_bytes(int32_t kind, int32_t B, const GopsMlp* v) {
     if (B < 1 || rpi_mlp_hidden_layers(kind, B, v) == 0) return 0;
     const int S = rpi_state_dim(kind);
     return sizeof(float) * ((size_t)GOPS_RPI_STATE_HEADER + (size_t)(S + 2) * B + 2 * rpi_mlp_param_count(*v) + (size_t)(S + 1) * B);
 }
 
-int rpi_mlp_evaluate(int kind, int B, int max_steps, const float* consts, const GopsMlp* v, const GopsMlp* t, const float* max_step,
-                     const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2, double eps,
-                     float* result, float* trace, hipStream_t s) {
+int gops_rpi_mlp_evaluate(int32_t kind, int32_t B, int32_t max_steps, const float* consts, const GopsMlp* v, const GopsMlp* t,
+                          const float* max_step, const float* pool, void* state, size_t state_bytes, double lr, double beta1, double beta2,
+                          double eps, float* result, float* trace, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (!v || !t) return GOPS_ERR_BAD_ARG;
     const int nh = rpi_mlp_hidden_layers(kind, B, v);
     if (nh == 0 || rpi_mlp_hidden_layers(kind, B, t) != nh || v->hidden_act != t->hidden_act) return GOPS_ERR_UNSUPPORTED;
@@ -575,7 +578,7 @@ int rpi_mlp_evaluate(int kind, int B, int max_steps, const float* consts, const 
     if (!consts || !max_step || !pool || !state || !result) return GOPS_ERR_BAD_ARG;
     for (int l = 0; l <= nh; ++l)
         if (!v->weight[l] || !v->bias[l] || !t->weight[l] || !t->bias[l]) return GOPS_ERR_BAD_ARG;
-    if (state_bytes < rpi_mlp_state_bytes(kind, B, v)) return GOPS_ERR_WORKSPACE;
+    if (state_bytes < gops_rpi_mlp_state_bytes(kind, B, v)) return GOPS_ERR_WORKSPACE;
     RpiMlpParams p;
     for (int i = 0; i < GOPS_RPI_CONST_COUNT; ++i) p.c[i] = consts[i];
     p.B = B, p.max_steps = max_steps, p.H1 = v->sizes[1], p.H2 = nh == 2 ? v->sizes[2] : 0;
@@ -593,3 +596,5 @@ int rpi_mlp_evaluate(int kind, int B, int max_steps, const float* consts, const 
     else rpi_mlp_launch<GOPS_RPI_ENV_SUSPENSION>(nh, v->hidden_act, p, s);
     return (int)hipGetLastError();
 }
+
+}  // extern "C"

@@ -338,10 +338,19 @@ __global__ __launch_bounds__(256) void cg_finish_kernel(int phases, const float*
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) step[i] = (float)(scale * (double)x[i]);
 }
 
+bool cg_state_ok(const GopsCgState* st, int n) { return st && n >= 1 && stats_aligned(st); }
+
 }  // namespace
 
-int gauss_fisher_seed(const GopsMlp& m, const GopsMlpGrad& tangent, int B, const float* x, double min_ls, double max_ls, float* seed,
-                      hipStream_t s) {
+extern "C" {
+
+int gops_gauss_fisher_seed(const GopsMlp* policy, const GopsMlpGrad* tangent_in, int32_t B, const float* x, double min_ls, double max_ls,
+                           float* seed, void* stream) {
+    if (!policy || !tangent_in || !x || !seed || B < 1) return GOPS_ERR_BAD_ARG;
+    if (policy->n_layers < 1 || policy->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_BAD_ARG;
+    const GopsMlp& m = *policy;
+    const GopsMlpGrad& tangent = *tangent_in;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     const int O = m.sizes[0], A2 = m.sizes[m.n_layers], A = A2 / 2;
     if (O < 1 || A < 1 || (A2 & 1) || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
     if (O > 64) return GOPS_ERR_UNSUPPORTED;
@@ -363,19 +372,27 @@ int gauss_fisher_seed(const GopsMlp& m, const GopsMlpGrad& tangent, int B, const
     return (int)hipGetLastError();
 }
 
-int trpo_surrogate(int M, int A, double min_ls, double max_ls, const float* head_new, const float* head_old, const float* act,
-                   const float* adv, const float* hyper, float* seed, float* stats, hipStream_t s) {
+int gops_trpo_surrogate(int32_t A, int32_t M, double min_ls, double max_ls, const float* head_new, const float* head_old, const float* act,
+                        const float* adv, const float* hyper, float* seed, float* stats, void* stream) {
+    if (M < 1 || A < 1 || A > GOPS_MAX_ACT) return GOPS_ERR_BAD_ARG;
+    if (!head_new || !head_old || !act || !adv || !hyper || !stats) return GOPS_ERR_BAD_ARG;
+    if (!stats_aligned(stats)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(trpo_surrogate_kernel, dim3(M <= LOSS_ONE_BLOCK_MAX ? 1 : TS_BLOCKS), dim3(256), 0, s, M, A, min_ls, max_ls, head_new,
                        head_old, act, adv, hyper, seed, stats);
     return (int)hipGetLastError();
 }
 
-int cg_init(const float* g, float* x, float* r, float* p, int n, double atol, GopsCgState* st, hipStream_t s) {
+int gops_cg_init(const float* g, float* x, float* r, float* p, int32_t n, double atol, GopsCgState* st, void* stream) {
+    if (!g || !x || !r || !p || !cg_state_ok(st, n)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(cg_init_kernel, dim3(n <= GOPS_CG_ONE_BLOCK_MAX ? 1 : CG_BLOCKS), dim3(256), 0, s, g, x, r, p, n, atol, st);
     return (int)hipGetLastError();
 }
 
-int cg_step(float* p, float* Ap, float* x, float* r, int n, double damping, double atol, GopsCgState* st, hipStream_t s) {
+int gops_cg_step(float* p, float* Ap, float* x, float* r, int32_t n, double damping, double atol, GopsCgState* st, void* stream) {
+    if (!p || !Ap || !x || !r || !cg_state_ok(st, n)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (n <= GOPS_CG_ONE_BLOCK_MAX) {
         hipLaunchKernelGGL(cg_step_kernel, dim3(1), dim3(256), 0, s, 7, p, Ap, x, r, n, damping, atol, st);
     } else {
@@ -385,7 +402,9 @@ int cg_step(float* p, float* Ap, float* x, float* r, int n, double damping, doub
     return (int)hipGetLastError();
 }
 
-int cg_finish(const float* g, const float* x, float* step, int n, const float* hyper, GopsCgState* st, hipStream_t s) {
+int gops_cg_finish(const float* g, const float* x, float* step, int32_t n, const float* hyper, GopsCgState* st, void* stream) {
+    if (!g || !x || !step || !hyper || !cg_state_ok(st, n)) return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (n <= GOPS_CG_ONE_BLOCK_MAX) {
         hipLaunchKernelGGL(cg_finish_kernel, dim3(1), dim3(256), 0, s, 3, g, x, step, n, hyper, st);
     } else {
@@ -394,3 +413,5 @@ int cg_finish(const float* g, const float* x, float* step, int n, const float* h
     }
     return (int)hipGetLastError();
 }
+
+}  // extern "C"
