@@ -1,27 +1,51 @@
-"""What PPO and TRPO share on the HIP kernels: a Gaussian `mlp_shared` StochaPolicy and a StateValue in one container, the refusal
-`create_alg` states for anything else, the per-object caches of kernel objects and buffers, and the captured Adam step.
+"""What PPO and TRPO share on the HIP kernels: a Gaussian `mlp_shared` StochaPolicy (for TRPO also a categorical StochaPolicyDis) and
+a StateValue in one container, the refusal `create_alg` states for anything else, the per-object caches of kernel objects and
+buffers, and the captured Adam step.
 """
 import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import AlgorithmBase, ApprBase
-from gops_amd.apprfunc.mlp import StateValue, StochaPolicy
+from gops_amd.apprfunc.mlp import StateValue, StochaPolicy, StochaPolicyDis
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
-from gops_amd.utils.act_distribution import GaussDistribution
+from gops_amd.utils.act_distribution import CategoricalDistribution, GaussDistribution
 from gops_amd.utils.common_utils import get_apprfunc_dict
 
+MAX_ACTIONS = 16   # include/gops_hip.h: GOPS_DQN_MAX_ACTIONS, the widest head of gops_cat_fisher_seed / gops_cat_trpo_surrogate
 
-def refusal(alg: str, density_words: str, kwargs: dict):
+
+def categorical_refusal(alg: str, kwargs: dict):
+    """Why `create_alg` cannot build `alg` on a categorical StochaPolicyDis from these arguments, or None."""
+    dist = kwargs.get("policy_act_distribution", "default")
+    if kwargs.get("action_type") != "discret":
+        return (f"{alg} takes policy_func_name 'StochaPolicyDis' with action_type 'discret' only, not {kwargs.get('action_type')!r}: its "
+                "outputs are the logits of action indices (continuous actions take 'StochaPolicy')")
+    if dist not in ("default", "CategoricalDistribution"):
+        return (f"{alg} takes policy_func_name 'StochaPolicyDis' with a categorical action distribution (policy_act_distribution "
+                f"'CategoricalDistribution' or 'default'), not {dist!r}: the softmax Fisher metric and the surrogate kernel are that density's")
+    n = kwargs.get("action_num")
+    if not isinstance(n, int) or not 2 <= n <= MAX_ACTIONS:
+        return f"{alg} takes 2 .. {MAX_ACTIONS} discrete actions (action_num {n!r}): the categorical head kernels hold no other width"
+    return None
+
+
+def refusal(alg: str, density_words: str, kwargs: dict, categorical: bool = False):
     """Why `create_alg` cannot build PPO / TRPO from these arguments, or None (POLY / LipsNet are refused before this is asked).
-    `density_words`: what of the algorithm's kernels is the Gaussian density's."""
+    `density_words`: what of the algorithm's kernels is the Gaussian density's; `categorical`: the algorithm also has the kernels
+    of a categorical StochaPolicyDis (for which the `policy_std_type` / log-std arguments mean nothing and are ignored)."""
     if kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
         return f"{alg} runs MLP networks only (policy_func_type {kwargs.get('policy_func_type')!r}, value_func_type {kwargs.get('value_func_type')!r})"
     dist = kwargs.get("policy_act_distribution", "default")
-    if kwargs.get("policy_func_name") != "StochaPolicy" or dist not in ("default", "GaussDistribution"):
+    discrete = categorical and kwargs.get("policy_func_name") == "StochaPolicyDis"
+    if discrete:
+        reason = categorical_refusal(alg, kwargs)
+        if reason is not None:
+            return reason
+    elif kwargs.get("policy_func_name") != "StochaPolicy" or dist not in ("default", "GaussDistribution"):
         return (f"{alg} takes a stochastic policy with a Gaussian action distribution (policy_func_name 'StochaPolicy', "
                 f"policy_act_distribution 'GaussDistribution' or 'default'), not {kwargs.get('policy_func_name')!r} with {dist!r}: "
                 f"{density_words}")
-    if kwargs.get("policy_std_type", "mlp_shared") != "mlp_shared":
+    if not discrete and kwargs.get("policy_std_type", "mlp_shared") != "mlp_shared":
         return (f"{alg} runs the policy with policy_std_type 'mlp_shared' only (one stack for mean and log std), not "
                 f"{kwargs.get('policy_std_type')!r}: 'parameter' and 'mlp_separated' are not yet supported")
     if kwargs.get("value_func_name") != "StateValue":
@@ -52,12 +76,18 @@ class ApproxContainer(ApprBase):
 
 
 class OnPolicyBase(AlgorithmBase):
-    def _init_on_policy(self, kwargs: dict):
-        """`self.networks`, checked, and the empty caches."""
+    def _init_on_policy(self, kwargs: dict, categorical: bool = False):
+        """`self.networks`, checked, and the empty caches.  `categorical`: a StochaPolicyDis with CategoricalDistribution is accepted
+        beside the Gaussian StochaPolicy."""
         name = type(self).__name__
         self.networks = nets = ApproxContainer(**kwargs)
-        if type(nets.policy) is not StochaPolicy or nets.policy.action_distribution_cls is not GaussDistribution:
-            raise NotImplementedError(f"{name}: policy {type(nets.policy).__name__} (MLP StochaPolicy with GaussDistribution only)")
+        gauss = type(nets.policy) is StochaPolicy and nets.policy.action_distribution_cls is GaussDistribution
+        cat = categorical and type(nets.policy) is StochaPolicyDis and nets.policy.action_distribution_cls is CategoricalDistribution
+        if cat and not 2 <= nets.policy.act_num <= MAX_ACTIONS:
+            raise NotImplementedError(f"{name}: {nets.policy.act_num} discrete actions (2 .. {MAX_ACTIONS} only)")
+        if not gauss and not cat:
+            raise NotImplementedError(f"{name}: policy {type(nets.policy).__name__} (MLP StochaPolicy with GaussDistribution"
+                                      f"{' or MLP StochaPolicyDis with CategoricalDistribution' if categorical else ''} only)")
         if not isinstance(nets.value, StateValue):
             raise NotImplementedError(f"{name}: value network {type(nets.value).__name__} (MLP StateValue only)")
         self.tb_info = dict()

@@ -1,7 +1,8 @@
 """TRPO - trust region policy optimisation - on the HIP kernels.
 
-Same class surface as the reference's gops/algorithm/trpo.py (ApproxContainer :38-53, TRPO :56-267): a Gaussian StochaPolicy stepped
-along the natural gradient within a KL ball, and a StateValue under its own Adam, on the on-policy columns `obs, act, adv, ret`.
+Same class surface as the reference's gops/algorithm/trpo.py (ApproxContainer :38-53, TRPO :56-267): a Gaussian StochaPolicy - or,
+on discrete actions, a categorical StochaPolicyDis - stepped along the natural gradient within a KL ball, and a StateValue under its
+own Adam, on the on-policy columns `obs, act, adv, ret`.
 
 The Fisher-vector product.  The reference forms `H v`, H the Hessian of `mean KL(pi || pi_old)` at theta_old, by a double backward
 through autograd, `max_cg + 1` times per update (trpo.py:150-169).  At theta_old `pi` and `pi_old` are the same numbers, the KL's
@@ -25,7 +26,16 @@ value iteration's, computed before that iteration's step; "fail to improve polic
 the policy stays at theta_old.
 
 The policy is the reference's `std_type="mlp_shared"` StochaPolicy with a GaussDistribution; `"parameter"` (the default of the
-reference's TRPO examples) and `"mlp_separated"` are not yet supported - `create_alg` refuses them with that reason.
+reference's continuous TRPO examples) and `"mlp_separated"` are not yet supported - `create_alg` refuses them with that reason.
+
+Discrete actions (`action_type="discret"`, `policy_func_name="StochaPolicyDis"`, 2 .. 16 actions; the reference's
+trpo_mlp_cartpole_onserial.py).  The head is the `act_num` logits, `act` holds the action indices as floats [B, 1], and the metric
+of the Gauss-Newton form is the softmax Fisher metric M_i = diag(p_i) - p_i p_i^T, p_i = softmax(logits_i).  Two kernel objects
+differ - `_fisher` returns `gops_cat_fisher_seed`'s, `_surrogate` `gops_cat_trpo_surrogate`'s, with the Gaussian ones' call
+surfaces - and nothing else does: the launch sequence, the graphs and the line search are the same code.  The categorical surrogate
+also counts the rows whose index lies outside [0, act_num) (the reference raises inside `gather`); the count is read together
+with the first candidate's verdict, and `local_update` raises ValueError - the policy back at theta_old - when it is not zero.
+`policy_std_type` and the log-std bounds mean nothing for this policy and are ignored.
 """
 __all__ = ["ApproxContainer", "TRPO"]
 
@@ -38,6 +48,7 @@ from gops_amd import hip_backend as hb
 from gops_amd.algorithm import _on_policy
 from gops_amd.algorithm._on_policy import ApproxContainer, OnPolicyBase
 from gops_amd.algorithm.base import batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.apprfunc.mlp import StochaPolicyDis
 from gops_amd.utils.common_utils import make_adam
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
@@ -50,7 +61,7 @@ MANDATORY = ("delta", "rtol", "atol", "damping_factor", "max_cg", "alpha", "max_
 
 def refusal(kwargs: dict):
     """Why `create_alg` cannot build TRPO from these arguments, or None."""
-    return _on_policy.refusal("TRPO", "the Fisher metric and the surrogate kernel are that density's", kwargs)
+    return _on_policy.refusal("TRPO", "the Fisher metric and the surrogate kernel are that density's", kwargs, categorical=True)
 
 
 class TRPO(OnPolicyBase):
@@ -71,7 +82,7 @@ class TRPO(OnPolicyBase):
         self.max_search = max_search
         self.train_v_iters = train_v_iters
         self.value_learning_rate = value_learning_rate
-        self._init_on_policy(kwargs)
+        self._init_on_policy(kwargs, categorical=True)
         self.value_optimizer = make_adam(self.networks.value.parameters(), lr=value_learning_rate)
         self._cg_graph, self._v_graph = StepGraphCache(), StepGraphCache()
         self.cg_graph_replays = 0      # CG loops that ran as a graph replay
@@ -119,7 +130,11 @@ class TRPO(OnPolicyBase):
             torch._foreach_copy_(datas, self._views(theta_old.add(cg.step_vec, alpha=self.alpha ** i), params))
             pol.forward(obs, out=head_new)
             sur.run(head_new, head_old, act, adv, want_seed=False)
-            if int(sur.verdict.item()) != 0:   # surrogate > 0 and kl < delta: one synchronisation per candidate, as in the reference
+            accepted, bad_rows = sur.flags()   # surrogate > 0 and kl < delta: one synchronisation per candidate, as in the reference
+            if bad_rows:   # (a categorical policy's rows with an index outside the head: the reference raises inside `gather`)
+                torch._foreach_copy_(datas, self._views(theta_old, params))
+                raise ValueError(f"TRPO: {bad_rows} rows of `act` hold an action index outside [0, {pol.out_dim})")
+            if accepted:
                 self.last_search_index = i
                 break
         else:
@@ -197,13 +212,20 @@ class TRPO(OnPolicyBase):
         return v[0::2], v[1::2]
 
     # ---- kernels' objects ------------------------------------------------------------------------
-    def _surrogate(self, device) -> hb.TrpoSurrogate:
+    def _surrogate(self, device):
+        """hb.TrpoSurrogate, or hb.CatTrpoSurrogate for a StochaPolicyDis: the same call surface."""
         pol = self.networks.policy
+        if isinstance(pol, StochaPolicyDis):
+            return self._one("surrogate", lambda: hb.CatTrpoSurrogate(pol.act_num, device))
         return self._one("surrogate", lambda: hb.TrpoSurrogate(pol.act_dim, pol.min_log_std, pol.max_log_std, device))
 
     def _fisher(self, device) -> hb.FisherSeed:
+        """hb.FisherSeed, or hb.CatFisherSeed for a StochaPolicyDis."""
         pol = self.networks.policy
-        fisher = self._one("fisher", lambda: hb.FisherSeed(pol.hip_mlp(), pol.min_log_std, pol.max_log_std, device))
+        if isinstance(pol, StochaPolicyDis):
+            fisher = self._one("fisher", lambda: hb.CatFisherSeed(pol.hip_mlp(), device))
+        else:
+            fisher = self._one("fisher", lambda: hb.FisherSeed(pol.hip_mlp(), pol.min_log_std, pol.max_log_std, device))
         fisher.mlp = pol.hip_mlp()
         return fisher
 

@@ -1,5 +1,5 @@
 """MLP approximate functions: DetermPolicy, FiniteHorizonPolicy, FiniteHorizonFullPolicy, StateValue, ActionValue of the
-ADP and DDPG / TD3 paths; StochaPolicy and ActionValueDistri of DSAC-T; ActionValueDis of DQN.
+ADP and DDPG / TD3 paths; StochaPolicy and ActionValueDistri of DSAC-T; ActionValueDis of DQN; StochaPolicyDis of discrete TRPO.
 
 Module structure, parameter names (`pi.0.weight` ... / `v.0.weight` ...), registered buffers and
 `forward` semantics follow the reference (gops/apprfunc/mlp.py:36-41,50-111,309-329) so that its
@@ -8,7 +8,7 @@ and evaluators for single observations; inside `compute_gradient` the same param
 in place by the fused HIP rollout (`hip_mlp()`), which never calls `forward`.
 """
 __all__ = ["DetermPolicy", "FiniteHorizonPolicy", "FiniteHorizonFullPolicy", "StateValue", "ActionValue", "ActionValueDis",
-           "StochaPolicy", "ActionValueDistri"]
+           "StochaPolicy", "ActionValueDistri", "StochaPolicyDis"]
 
 import weakref
 
@@ -181,6 +181,12 @@ class ActionValueDis(nn.Module, Action_Distribution, _HipMlpMixin):
 
     def forward(self, obs):
         return self.q(obs)
+
+
+class StochaPolicyDis(ActionValueDis):
+    """Stochastic policy of a discrete action space: obs -> the logits of all `act_num` actions - an ActionValueDis under another
+    name, as in the reference (gops/apprfunc/mlp.py:299-306; parameter names `q.0.weight` ...).  TRPO reads it through
+    `gops_mlp_forward / _backward`, `gops_cat_fisher_seed` and `gops_cat_trpo_surrogate` (`hip_mlp()`)."""
 
 
 class StochaPolicy(nn.Module, Action_Distribution, _HipMlpMixin):

@@ -246,6 +246,8 @@ def _signatures():
         "gops_gae": (rc, [vp, vp, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp]),
         "gops_gauss_fisher_seed": (rc, [mlp, grad, i32, vp, f64, f64, vp, vp]),
         "gops_trpo_surrogate": (rc, [i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gops_cat_fisher_seed": (rc, [mlp, grad, i32, vp, vp, vp]),
+        "gops_cat_trpo_surrogate": (rc, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gops_cg_init": (rc, [vp, vp, vp, vp, i32, f64, vp, vp]),
         "gops_cg_step": (rc, [vp, vp, vp, vp, i32, f64, f64, vp, vp]),
         "gops_cg_finish": (rc, [vp, vp, vp, i32, vp, vp, vp]),
@@ -1685,19 +1687,31 @@ class FisherSeed:
         assert len(tangent_w) == len(tangent_b) == self.mlp.n_layers
         for j, (w, b) in enumerate(zip(tangent_w, tangent_b)):
             assert w.numel() == int(self.mlp.sizes[j]) * int(self.mlp.sizes[j + 1]) and b.numel() == int(self.mlp.sizes[j + 1])
-        t = make_mlp_grad(tangent_w, tangent_b)
-        check(lib().gops_gauss_fisher_seed(C.byref(self.mlp), C.byref(t), B, _ptr(x), self.min_log_std, self.max_log_std, _ptr(seed),
-                                           _stream()), "gops_gauss_fisher_seed")
+        self._launch(make_mlp_grad(tangent_w, tangent_b), B, x, seed)
         return seed
 
+    def _launch(self, t: GopsMlpGrad, B: int, x, seed):
+        check(lib().gops_gauss_fisher_seed(C.byref(self.mlp), C.byref(t), B, _ptr(x), self.min_log_std, self.max_log_std, _ptr(seed),
+                                           _stream()), "gops_gauss_fisher_seed")
 
-class TrpoSurrogate:
-    """TRPO's surrogate advantage, mean KL(new || old), the surrogate's gradient seed and the line search's verdict in one launch
-    (`gops_trpo_surrogate`).  `buf[:2]` = surrogate, kl; `verdict` (int32 view of `buf[2]`) = surrogate > 0 and kl < delta; `hyper`
-    (device): delta, read by the kernel."""
 
-    def __init__(self, act_dim: int, min_log_std: float, max_log_std: float, device):
-        self.act_dim, self.min_log_std, self.max_log_std = int(act_dim), float(min_log_std), float(max_log_std)
+class CatFisherSeed(FisherSeed):
+    """`gops_cat_fisher_seed`: seed [B, n] = (1/B) (diag(p) - p p^T) (J v) of a categorical policy over n action indices,
+    p = softmax(logits) - `FisherSeed`'s call surface."""
+
+    def __init__(self, mlp: GopsMlp, device):
+        self.mlp, self.device = mlp, device
+        self.out_dim = int(mlp.sizes[mlp.n_layers])
+
+    def _launch(self, t: GopsMlpGrad, B: int, x, seed):
+        check(lib().gops_cat_fisher_seed(C.byref(self.mlp), C.byref(t), B, _ptr(x), _ptr(seed), _stream()), "gops_cat_fisher_seed")
+
+
+class _SurrogateState:
+    """What both surrogate kernels keep on the device: `buf` (`buf[:2]` = surrogate, kl; `verdict`, int32 view of `buf[2]` =
+    surrogate > 0 and kl < delta) and `hyper` (delta, read by the kernel)."""
+
+    def __init__(self, device):
         self.buf = torch.zeros(TRPO_STATS_FLOATS, dtype=torch.float32, device=device)
         self.hyper = torch.zeros(TRPO_HYPER_FLOATS, dtype=torch.float32, device=device)
         self.verdict = self.buf.view(torch.int32)[2:3]
@@ -1707,6 +1721,21 @@ class TrpoSurrogate:
         if float(delta) != self._delta:   # (a host-to-device copy: never inside a capture)
             self.hyper[:1].copy_(torch.tensor([float(delta)], dtype=torch.float32))
             self._delta = float(delta)
+
+    def flags(self):
+        """(verdict, rows left out for their action index - always 0 for the Gaussian kernel) of the last call, in ONE read."""
+        verdict, bad = self.buf.view(torch.int32)[2:4].tolist()
+        return verdict != 0, bad
+
+
+class TrpoSurrogate(_SurrogateState):
+    """TRPO's surrogate advantage, mean KL(new || old), the surrogate's gradient seed and the line search's verdict in one launch
+    (`gops_trpo_surrogate`).  `buf[:2]` = surrogate, kl; `verdict` (int32 view of `buf[2]`) = surrogate > 0 and kl < delta; `hyper`
+    (device): delta, read by the kernel."""
+
+    def __init__(self, act_dim: int, min_log_std: float, max_log_std: float, device):
+        super().__init__(device)
+        self.act_dim, self.min_log_std, self.max_log_std = int(act_dim), float(min_log_std), float(max_log_std)
 
     def run(self, head_new, head_old, act, adv, seed_head=None, want_seed=True):
         """head_new, head_old [M, 2A] raw (may be the same tensor) -> (seed_head [M, 2A] or None, stats [2])."""
@@ -1718,6 +1747,30 @@ class TrpoSurrogate:
         check(lib().gops_trpo_surrogate(A, M, self.min_log_std, self.max_log_std, _ptr(head_new), _ptr(head_old), _ptr(act), _ptr(adv),
                                         self.hyper.data_ptr(), _ptr(seed_head) if want_seed else None, self.buf.data_ptr(), _stream()),
               "gops_trpo_surrogate")
+        return (seed_head if want_seed else None), self.buf[:2]
+
+
+class CatTrpoSurrogate(_SurrogateState):
+    """The same for a categorical policy over `act_num` action indices, from the logits (`gops_cat_trpo_surrogate`) -
+    `TrpoSurrogate`'s call surface, and `bad_index` (int32 view of `buf[3]`): the rows of the last call whose index in `act` lies
+    outside [0, act_num); they are left out of both means and get a zero seed row."""
+
+    def __init__(self, act_num: int, device):
+        super().__init__(device)
+        self.act_num = int(act_num)
+        self.bad_index = self.buf.view(torch.int32)[3:4]
+
+    def run(self, head_new, head_old, act, adv, seed_head=None, want_seed=True):
+        """head_new, head_old [M, n] logits (may be the same tensor), act [M] or [M, 1] indices as floats -> (seed_head [M, n] or
+        None, stats [2])."""
+        M, N = head_new.shape[0], self.act_num
+        assert tuple(head_new.shape) == (M, N) and head_old.numel() == M * N and act.numel() == M and adv.numel() == M
+        if want_seed and seed_head is None:
+            seed_head = torch.empty_like(head_new)
+        assert seed_head is None or seed_head.numel() == M * N
+        check(lib().gops_cat_trpo_surrogate(N, M, _ptr(head_new), _ptr(head_old), _ptr(act), _ptr(adv), self.hyper.data_ptr(),
+                                            _ptr(seed_head) if want_seed else None, self.buf.data_ptr(), _stream()),
+              "gops_cat_trpo_surrogate")
         return (seed_head if want_seed else None), self.buf[:2]
 
 

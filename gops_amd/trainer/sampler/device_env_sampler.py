@@ -26,7 +26,7 @@ import warnings
 
 import torch
 
-from gops_amd.apprfunc.mlp import StochaPolicy
+from gops_amd.apprfunc.mlp import StochaPolicy, StochaPolicyDis
 from gops_amd import hip_backend as hb
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS as _INFO, NOT_RESTATED, draw_reset_pool
 from gops_amd.utils.tensorboard_setup import tb_tags
@@ -43,7 +43,9 @@ class DeviceEnvSampler:
         action_table [act_num, action_dim] (None: continuous actions, the policy output is the action): the policy output is read as
         action values - the action index is their arg-max, replaced with probability `epsilon` by a uniform index from this sampler's
         device generator -, the env is stepped with `action_table[index]` and the stored `act` column is the index as a float, [N, 1]
-        (DQN; `gym_cartpoleconti` with the table [[-1.], [1.]] is the two-action cartpole)."""
+        (DQN; `gym_cartpoleconti` with the table [[-1.], [1.]] is the two-action cartpole).  With a StochaPolicyDis (discrete TRPO) the
+        policy output is read as logits instead: the index is drawn from softmax(logits) with the same generator, `logp` is the
+        log-softmax at it, and `epsilon` must be 0 (`sample()` raises ValueError otherwise)."""
         self.cfg, self.env_model = dict(cfg), env_model
         if getattr(getattr(env_model, "unwrapped", env_model), "ref_c", None) is not None:
             raise RuntimeError("DeviceEnvSampler draws its reset states from the DEFAULT reference trajectories "
@@ -102,7 +104,11 @@ class DeviceEnvSampler:
         act, logp = policy(obs), zeros
         stored = None
         if self.action_table is not None:
-            stored = self.select_index(act)
+            if isinstance(policy, StochaPolicyDis):   # the categorical policy explores by itself; its log-probability is stored
+                self._check_categorical()
+                stored, logp = self.sample_index(act)
+            else:
+                stored = self.select_index(act)
             act = self.action_table[stored]
             stored = stored.to(torch.float32).unsqueeze(-1)
         elif isinstance(policy, StochaPolicy):   # the policy's own distribution explores; its log-probability is stored
@@ -141,6 +147,18 @@ class DeviceEnvSampler:
             uniform = torch.randint(values.shape[-1], index.shape, generator=self._gen, device=values.device)
             index = torch.where(explore, uniform, index)
         return index
+
+    def sample_index(self, logits: torch.Tensor):
+        """A categorical policy's logits [N, act_num] -> (indices [N] (int64) drawn from softmax(logits) with the sampler's generator,
+        their log-probabilities [N]: the log-softmax at the index)."""
+        logp_all = torch.log_softmax(logits, dim=-1)
+        index = torch.multinomial(logp_all.exp(), 1, generator=self._gen)
+        return index.squeeze(-1), logp_all.gather(-1, index).squeeze(-1)
+
+    def _check_categorical(self):
+        if self.epsilon > 0.0:
+            raise ValueError("DeviceEnvSampler: epsilon > 0 with a StochaPolicyDis - the policy samples its own categorical "
+                             "distribution, and the stored logp would not be that of an epsilon-greedy index")
 
     @torch.no_grad()
     def sample(self):

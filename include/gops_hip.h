@@ -947,6 +947,37 @@ int gops_dqn_backup(const GopsDqnBackup* desc, int32_t batch, const float* obs2,
 int gops_dqn_loss(const float* q_all, const float* act, const float* backup, const float* weight, int32_t act_num, int32_t batch,
                   float* seed, float* abs_err, float* stats, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): TRPO on discrete actions - a categorical policy (StochaPolicyDis) over
+ * n = act_num action indices, p = softmax(logits) (csrc/trpo.hip).  The Gauss-Newton form of the KL's Hessian above holds with J_i
+ * the Jacobian of the n LOGITS of row i and M_i = diag(p_i) - p_i p_i^T, the softmax Fisher metric.
+ *
+ * gops_cat_fisher_seed: seed [B, n] = (1/B) (diag(p) - p p^T) (J v), n = policy->sizes[n_layers], for x [B, in]; `tangent` as for
+ *   gops_gauss_fisher_seed, and the hidden layers are that kernel's tangent forward (one kernel, the head is its template parameter).
+ *   Head, per row, in double: the logits z_k and their tangents u_k = W t + V h + c are the eight-chain dots of the Gaussian head,
+ *   parked in LDS - thread (row, g) forms k = g, g + 256 / R, .. -; then in index order
+ *       m = max_k z_k,  e_k = exp(z_k - m),  S = sum_k e_k,  p_k = e_k / S,  pu = sum_k p_k u_k,   seed[k] = (float)(p_k (u_k - pu) / B).
+ *   Every stored value is rounded once; a row's bits depend neither on the batch size (beyond the 1 / B) nor on the tile rows; a second
+ *   launch gives the same bits; no atomics.  Accepted: fp32, 1 .. 3 hidden layers of widths that are multiples of 16 up to 256,
+ *   in <= 64, 2 <= n <= GOPS_DQN_MAX_ACTIONS, every hidden activation; GOPS_ERR_UNSUPPORTED otherwise.  GOPS_ERR_BAD_ARG: a NULL
+ *   pointer (a tangent slice included), batch < 1.
+ * gops_cat_trpo_surrogate: logits_new, logits_old [M, n] (they may be the same array), act [M] the float index column (the index by
+ *   truncation towards zero, as in gops_dqn_loss), adv [M].  Per row, in double:
+ *       lse = m + log(sum_k exp(z_k - m)),  logp_k = z_k - lse   (new and old),   p_new,k = exp(z_new,k - m_new) / S_new,
+ *       ratio = exp(logp_new[a] - logp_old[a]),   kl = sum_k p_new,k (logp_new,k - logp_old,k)   in index order: KL(new || old),
+ *       seed_head [M, n]: seed_head[i, k] = (float)((1/M) adv_i ratio_i ((k == a) - p_new,k)), unless seed_head is NULL.
+ *     stats[0] = mean surrogate, stats[1] = mean KL, ((int32_t*)stats)[2] = stats[0] > 0 && stats[1] < hyper[0] on the stored fp32
+ *     values, ((int32_t*)stats)[3] = the number of rows whose index lies outside [0, n), a NaN index included.  Such a row adds nothing
+ *     to either sum (the means still divide by M), gets an all-zero seed row, and reads and writes nothing outside its own row.
+ *   With logits_old == logits_new the ratio is exactly 1 and the KL exactly 0.  The KL has no special case for a zero probability: a
+ *   p_new,k that underflows to 0 contributes 0, and logp_old is finite for finite logits - torch's kl_divergence returns inf where
+ *   q = 0 in fp32; this does not.  stats: gops_trpo_surrogate's layout and size (GOPS_TRPO_STATS_FLOATS floats, 8-byte aligned, all
+ *   zero before the first call: the partial sums, the ticket and the running count of bad rows behind the results, left zero again).
+ *   One workgroup up to 8192 rows, 64 beyond.  GOPS_ERR_BAD_ARG: a NULL pointer (seed_head excepted), batch < 1, act_num < 1, a
+ *   misaligned `stats`; GOPS_ERR_UNSUPPORTED: act_num outside 2 .. GOPS_DQN_MAX_ACTIONS. */
+int gops_cat_fisher_seed(const GopsMlp* policy, const GopsMlpGrad* tangent, int32_t batch, const float* x, float* seed, void* stream);
+int gops_cat_trpo_surrogate(int32_t act_num, int32_t batch, const float* logits_new, const float* logits_old, const float* act,
+                            const float* adv, const float* hyper, float* seed_head, float* stats, void* stream);
+
 /* Which kernels a rollout description runs on this device (ABI v8; for benchmarks / profiles, no launch):
  * bit 0 (GOPS_VARIANT_SPLIT): the register-stationary kernels with plane-split contractions - hidden-layer weights,
  *        activations and deltas as two half planes each (22 bits), 3 f16 MFMAs (16x16x32) per 32-deep block, fp32
