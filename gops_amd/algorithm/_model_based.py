@@ -15,22 +15,23 @@ def polyak_foreach_(target, online, tau):
     torch._foreach_add_(target, online, alpha=tau)
 
 
-# POLY approximators (apprfunc/poly.py): the POLY rollout steps the env models whose observation is the state (csrc/rollout_poly.hip)
-def poly_env_check(envmodel, alg: str):
+# POLY (apprfunc/poly.py) and GAUSS (apprfunc/gauss.py) approximators: their one-lane-per-trajectory rollouts (csrc/rollout_poly.hip,
+# csrc/rollout_rbf.hip) step the env models whose observation is the state.  `family`: "POLY" or "GAUSS", for the messages.
+def lane_env_check(envmodel, alg: str, family: str):
     if getattr(envmodel.unwrapped, "hip_kind", None) not in hb.STATE_OBS_ENV_KINDS:
-        raise NotImplementedError(f"{alg} with an apprfunc of type POLY: env model {type(envmodel.unwrapped).__name__} is outside "
-                                  "the POLY rollout (pyth_lq, pyth_idpendulum, gym cartpoleconti / pendulum only)")
+        raise NotImplementedError(f"{alg} with an apprfunc of type {family}: env model {type(envmodel.unwrapped).__name__} is outside "
+                                  f"the {family} rollout (pyth_lq, pyth_idpendulum, gym cartpoleconti / pendulum only)")
 
 
-def poly_alg_check(alg, time_input: bool):
-    """What an algorithm with a POLY policy must refuse at construction (FHADP: a FiniteHorizonPolicy, whose weight carries the
-    virtual_t column; INFADP: a DetermPolicy; both: fp32 only - the POLY kernels have no half-precision path)."""
+def lane_alg_check(alg, time_input: bool, family: str):
+    """What an algorithm with a POLY / GAUSS policy must refuse at construction (FHADP: a FiniteHorizonPolicy, whose weight / centres
+    carry the virtual_t column; INFADP: a DetermPolicy; both: fp32 only - these kernels have no half-precision path)."""
     name = type(alg).__name__
     if str(getattr(alg, "mlp_dtype", "fp32") or "fp32").lower() not in ("fp32", "f32", "float32"):
-        raise NotImplementedError(f"{name} with an apprfunc of type POLY: mlp_dtype {alg.mlp_dtype!r} - the POLY path is fp32 only")
+        raise NotImplementedError(f"{name} with an apprfunc of type {family}: mlp_dtype {alg.mlp_dtype!r} - the {family} path is fp32 only")
     pol = alg.networks.policy
     if bool(getattr(pol, "_time_input", False)) != time_input:
-        raise NotImplementedError(f"{name} with a POLY {type(pol).__name__}: the POLY rollout of {name} takes a "
+        raise NotImplementedError(f"{name} with a {family} {type(pol).__name__}: the {family} rollout of {name} takes a "
                                   f"{'FiniteHorizonPolicy' if time_input else 'DetermPolicy'}")
 
 

@@ -273,6 +273,11 @@ def is_poly(module) -> bool:
     return bool(getattr(module, "is_poly", False))
 
 
+def is_rbf(module) -> bool:
+    """A GAUSS approximator (gops_amd/apprfunc/gauss.py): radial basis functions, the HIP RBF rollout."""
+    return bool(getattr(module, "is_rbf", False))
+
+
 def install_grads(module, grads):
     """Gradients from outside (`remote_update`) become the parameters' `.grad`, in `parameters()` order."""
     for p, grad in zip(module.parameters(), grads):
@@ -300,7 +305,15 @@ def poly_grad_buffers(module):
     return [lin.weight.grad], [None if lin.bias is None else lin.bias.grad]
 
 
+def rbf_grad_buffers(module):
+    """The four gradient tensors of a GAUSS net in `state_dict` order (C, sigma_square, w, b), as `hb.RbfRollout.backward` takes them."""
+    _flat_grads(module)
+    return [p.grad for p in module.parameters()]
+
+
 def net_grad_buffers(module):
+    if is_rbf(module):
+        return rbf_grad_buffers(module), None
     return poly_grad_buffers(module) if is_poly(module) else grad_buffers(module)
 
 

@@ -15,9 +15,9 @@ from typing import Tuple
 from gops_amd.utils.common_utils import make_adam
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm._model_based import ModelBasedBase, poly_alg_check, poly_env_check
-from gops_amd.algorithm.base import (ApprBase, PrecisionGuard, grad_buffers, install_grads, is_poly, net_grad_buffers,
-                                     poly_grad_buffers)
+from gops_amd.algorithm._model_based import ModelBasedBase, lane_alg_check, lane_env_check
+from gops_amd.algorithm.base import (ApprBase, PrecisionGuard, grad_buffers, install_grads, is_poly, is_rbf, net_grad_buffers,
+                                     poly_grad_buffers, rbf_grad_buffers)
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
@@ -61,8 +61,15 @@ class FHADP(ModelBasedBase):
         if self._poly:
             if not self._plain:
                 raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type POLY: only plain FHADP runs the POLY rollout")
-            poly_env_check(self.envmodel, type(self).__name__)
-            poly_alg_check(self, time_input=True)
+            lane_env_check(self.envmodel, type(self).__name__, "POLY")
+            lane_alg_check(self, time_input=True, family="POLY")
+        # GAUSS policy (apprfunc/gauss.py): the RBF rollout (hb.RbfRollout), likewise of the plain algorithm only
+        self._rbf = is_rbf(self.networks.policy)
+        if self._rbf:
+            if not self._plain:
+                raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type GAUSS: only plain FHADP runs the RBF rollout")
+            lane_env_check(self.envmodel, type(self).__name__, "GAUSS")
+            lane_alg_check(self, time_input=True, family="GAUSS")
 
     @property
     def adjustable_parameters(self) -> Tuple[str]:
@@ -79,7 +86,7 @@ class FHADP(ModelBasedBase):
         # the constrained variants bring their own gradient kernels; the plain ones fold loss mean and Adam step into the backward's
         # last launch (ABI v12, gops_rollout_backward_update: two launches less per update)
         fuse = self._plain and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0"   # (host-side A/B knob)
-        fuse = fuse and not self._poly   # (POLY: gradient, loss mean and Adam step as three launches)
+        fuse = fuse and not self._poly and not self._rbf   # (POLY, GAUSS: gradient, loss mean and Adam step as launches of their own)
 
         def update(b):
             if fuse:
@@ -114,7 +121,8 @@ class FHADP(ModelBasedBase):
         net_grad_buffers(self.networks.policy)   # (allocates the flat gradient buffer on first use)
         grads = [p._grad for p in self.networks.policy.parameters()]
         info = {"grad": grads}
-        if reducer is not None and reducer.overlap_enabled() and len(grads) >= 4 and self._plain:
+        # (POLY / GAUSS: no phases - their backward is one call, and a second one would rewrite gradients already on their way)
+        if reducer is not None and reducer.overlap_enabled() and len(grads) >= 4 and self._plain and not (self._poly or self._rbf):
             sig = self._signature(batch)
             loss = self._grad_graph.run(("a",) + sig, batch, lambda b: self._gradient_kernels(b, phase="a"), work=work)
             try:
@@ -149,7 +157,7 @@ class FHADP(ModelBasedBase):
             # one live workspace per kernel variant of the current shape (shapes rarely change between updates)
             for k in [k for k in self._cache if k[:5] != key[:5]]:
                 del self._cache[k]
-            return (hb.PolyRollout if self._poly else hb.Rollout)(
+            return (hb.RbfRollout if self._rbf else hb.PolyRollout if self._poly else hb.Rollout)(
                 self._hip_env(), mlp, batch=batch, horizon=self.pre_horizon, gamma=self.gamma, finite_horizon=True,
                 need_grad=True, device=device, dtype=self.mlp_dtype, variant_flags=flags)
         return self._cached(key, make, lambda ro: ro.set_policy(mlp))
@@ -192,6 +200,15 @@ class FHADP(ModelBasedBase):
         `fused_opt` (the policy's HipAdam, single-process update): loss mean and optimizer step ride on the backward's last launch."""
         B, device = batch["obs"].shape[0], batch["obs"].device
         ro = self._rollout_for(B, device)
+        if self._rbf and phase is not None:
+            raise RuntimeError("FHADP with a GAUSS policy: the RBF backward has no phases")
+        if self._rbf:    # forward, backward into the four gradient buffers, loss mean (+ Adam step): no phases, no fused tail
+            v_pi = ro.forward(batch)["v_pi"]
+            ro.backward(self._grad_v(B, device), rbf_grad_buffers(self.networks.policy))
+            out = self._mean_of(v_pi)
+            if fused_opt is not None:
+                fused_opt.step()
+            return out
         if self._poly:   # forward, backward, loss mean (+ Adam step): no phases, no fused tail for one or two tensors
             v_pi = ro.forward(batch)["v_pi"]
             gw, gb = poly_grad_buffers(self.networks.policy)

@@ -16,8 +16,8 @@ import torch
 from gops_amd.utils.common_utils import make_adam
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm._model_based import ModelBasedBase, poly_alg_check, poly_env_check, polyak_foreach_
-from gops_amd.algorithm.base import ApprBase, PrecisionGuard, install_grads, is_poly, net_grad_buffers
+from gops_amd.algorithm._model_based import ModelBasedBase, lane_alg_check, lane_env_check, polyak_foreach_
+from gops_amd.algorithm.base import ApprBase, PrecisionGuard, install_grads, is_poly, is_rbf, net_grad_buffers, rbf_grad_buffers
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
@@ -83,8 +83,21 @@ class INFADP(ModelBasedBase):
         if self._poly:
             if not self._plain:
                 raise NotImplementedError(f"{type(self).__name__} with an apprfunc of type POLY: only plain INFADP runs the POLY rollout")
-            poly_env_check(self.envmodel, type(self).__name__)
-            poly_alg_check(self, time_input=False)
+            lane_env_check(self.envmodel, type(self).__name__, "POLY")
+            lane_alg_check(self, time_input=False, family="POLY")
+        # GAUSS policy (apprfunc/gauss.py) with an MLP value: the RBF rollout has no tail, the host composes it (`_rbf_return`)
+        self._rbf = is_rbf(self.networks.policy)
+        if is_rbf(self.networks.v):
+            raise NotImplementedError("INFADP with a GAUSS value function: the reference itself cannot run it (its [B, 1] value does "
+                                      "not broadcast into the in-place backup)")
+        if self._rbf:
+            name = type(self).__name__
+            if not self._plain:
+                raise NotImplementedError(f"{name} with an apprfunc of type GAUSS: only plain INFADP runs the RBF rollout")
+            if self._poly or getattr(self.networks.v, "is_lipsnet", False) or not hasattr(self.networks.v, "hip_mlp"):
+                raise NotImplementedError(f"{name} with a GAUSS policy needs an MLP StateValue")
+            lane_env_check(self.envmodel, name, "GAUSS")
+            lane_alg_check(self, time_input=False, family="GAUSS")
         # LipsNet policy (apprfunc/lipsnet.py): the policy sits OUTSIDE an open-loop one-step rollout (`_lips_return`)
         self._lips = bool(getattr(self.networks.policy, "is_lipsnet", False))
         if self._lips:
@@ -126,6 +139,7 @@ class INFADP(ModelBasedBase):
         fuse = self._plain and os.environ.get("GOPS_FUSED_UPDATE", "1") != "0"   # (host-side A/B knob)
         fuse = fuse and not self._poly   # (POLY: Adam and Polyak steps as launches of their own)
         fuse = fuse and not self._lips   # (LipsNet: two optimizer groups, more tensors than one fused table)
+        fuse = fuse and not self._rbf    # (GAUSS: the return is composed on the host; Adam and Polyak steps as launches of their own)
 
         def update(b):
             if fuse:
@@ -217,6 +231,8 @@ class INFADP(ModelBasedBase):
     def _precision_check(self, mode: str, batch):
         """The guard of the network this iteration trains, on ITS gradients."""
         nets = self.networks
+        if self._rbf and mode == "policy":   # (the RBF rollout has no kernel variants: nothing to compare; the value update keeps its guard)
+            return
         self._guard_check(self.precision_guard[mode], (nets.policy, nets.v), lambda: self._gradient_kernels(mode, batch), nets.net_dict[mode])
 
     def _mode(self, iteration) -> str:
@@ -228,9 +244,12 @@ class INFADP(ModelBasedBase):
         B, device = batch["obs"].shape[0], batch["obs"].device
         if self._lips and mode == "policy":
             return self._lips_improvement(batch)
+        if self._rbf and mode == "policy":
+            return self._rbf_improvement(batch)
         if mode == "v":
             # PEV: loss_v = mean((V(o) - [sum_t gamma^t r_t + (~d) gamma^n V_target(o_n)])^2)
             backup = (self._lips_return(batch, need_grad=False)[0] if self._lips
+                      else self._rbf_return(batch, need_grad=False)[0] if self._rbf
                       else self._rollout_for(B, device, need_grad=False).forward(batch)["v_pi"])
             vn = self._value_for(B, device)
             v = vn.forward(batch["obs"])
@@ -318,6 +337,35 @@ class INFADP(ModelBasedBase):
         ctx["parts"]["lp"].backward((g_u.reshape(B, -1) * ctx["pass_through"]).contiguous())
         self.tb_info["Train/LipsNet K mean"] = scalar(ctx["K"].mean().reshape(1), 0)
         return self._loss_stats("policy", device).mean_loss(value.contiguous(), -1.0)[:1]
+
+    # ---- GAUSS policy: RBF rollout without a tail -> target value on final_obs -> v_pi + (1 - done_H) gamma^H V --------------------------
+    def _rbf_rollout(self, B, device, need_grad):
+        pol = self.networks.policy.hip_mlp()
+        return self._cached(("rbf", B, self.forward_step, float(self.gamma), str(device), need_grad), lambda: hb.RbfRollout(
+            self._hip_env(), pol, batch=B, horizon=self.forward_step, gamma=self.gamma, finite_horizon=False, need_grad=need_grad,
+            device=device), lambda ro: ro.set_policy(pol))
+
+    def _rbf_return(self, batch, need_grad):
+        """sum_t gamma^t r_t + (1 - done_H) gamma^H V_target(obs_H) under the GAUSS policy -> (value [B], what the backward needs):
+        the rollout's v_pi and final observation, the existing `hb.MlpNet` of the target value on it, one fused multiply-add."""
+        B, device = batch["obs"].shape[0], batch["obs"].device
+        ro = self._rbf_rollout(B, device, need_grad)
+        res = ro.forward(batch, want_final=True)
+        vt = self._lips_vt(B, device, need_grad)
+        v_next = vt.forward(res["final_obs"]).reshape(B)
+        tail = float(self.gamma) ** self.forward_step * (1.0 - res["final_done"])
+        value = torch.addcmul(res["v_pi"], tail, v_next)
+        return value, dict(ro=ro, vt=vt, res=res, tail=tail)
+
+    def _rbf_improvement(self, batch):
+        """PIM: loss = -mean(value); grad_final_obs = grad_v (1 - done_H) gamma^H dV/dx through `gops_mlp_backward_x`, then the RBF
+        rollout's backward into the policy's four gradient tensors."""
+        B, device = batch["obs"].shape[0], batch["obs"].device
+        value, ctx = self._rbf_return(batch, need_grad=True)
+        gv = self._grad_v(B, device)
+        g_final = ctx["vt"].backward_x(ctx["res"]["final_obs"], (gv * ctx["tail"]).unsqueeze(1).contiguous())
+        ctx["ro"].backward(gv, rbf_grad_buffers(self.networks.policy), grad_final_obs=g_final.contiguous())
+        return self._loss_stats("policy", device).mean_loss(value, -1.0)[:1]
 
     def _fused_parts(self, net_name, opt):
         """(what `HipAdam.begin_fused` returns, the network's one-table PolyakUpdater) for a backward call that carries the update's

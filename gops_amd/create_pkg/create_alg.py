@@ -119,6 +119,16 @@ def create_alg(**kwargs) -> object:
     if poly and kwargs["algorithm"] not in ("FHADP", "INFADP"):   # (the POLY rollout serves these two; nothing fails later)
         raise NotImplementedError(f"apprfunc type POLY ({', '.join(poly)}) is supported by FHADP and INFADP only, "
                                   f"not by {kwargs['algorithm']}")
+    gauss = [k for k in ("policy", "value") if kwargs.get(k + "_func_type") == "GAUSS" and kwargs["algorithm"] != "RPI"
+             and not (k == "value" and kwargs["algorithm"] == "FHADP")]   # (FHADP has no value net: the key is ignored, as for MLP)
+    if gauss:   # FHADP with a GAUSS FiniteHorizonPolicy, INFADP with a GAUSS DetermPolicy and an MLP StateValue: refused here, so that nothing fails later
+        reason = (f"supported by FHADP and INFADP only, not by {kwargs['algorithm']}" if kwargs["algorithm"] not in ("FHADP", "INFADP") else
+                  "a GAUSS value function is outside this path: the reference itself cannot run INFADP with one (its [B, 1] value does "
+                  "not broadcast into the in-place backup)" if "value" in gauss else
+                  "a GAUSS policy needs an MLP value, not " + str(kwargs.get("value_func_type"))
+                  if kwargs["algorithm"] == "INFADP" and kwargs.get("value_func_type") != "MLP" else None)
+        if reason is not None:
+            raise NotImplementedError(f"apprfunc type GAUSS ({', '.join(gauss)}): {reason}")
     lips = [k for k in ("policy", "value") if kwargs.get(k + "_func_type") == "LipsNet"]
     if lips:   # INFADP with a LipsNet DetermPolicy and an MLP StateValue is the one combination that runs; refused here, so that nothing fails later
         reason = ("a LipsNet value function does not exist (the reference has none either)" if "value" in lips else

@@ -412,6 +412,100 @@ __device__ __forceinline__ void state_model_step(const GopsEnv& env, const float
     }
 }
 
+// Host side: what the one-lane-per-trajectory rollouts (rollout_poly.hip, rollout_rbf.hip) ask of a description before they look at
+// its policy: shape, fp32, closed loop, no kernel variants, a model env whose observation is the state, the bounds of
+// state_model_step / state_model_step_bwd.
+inline int state_model_check_desc(const GopsRolloutDesc& d) {
+    if (d.batch < 1 || d.horizon < 1 || d.horizon > GOPS_MAX_HORIZON) return GOPS_ERR_BAD_ARG;
+    if (d.open_loop != 0 || d.dtype != GOPS_DTYPE_F32) return GOPS_ERR_UNSUPPORTED;
+    if (d.variant_flags != 0) return GOPS_ERR_UNSUPPORTED;
+    const GopsEnv& e = d.env;
+    const int n = e.obs_dim;
+    switch (e.kind) {
+        case GOPS_ENV_LQ: if (n < 1 || n > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED; break;
+        case GOPS_ENV_IDPENDULUM: if (n != 6) return GOPS_ERR_UNSUPPORTED; break;
+        case GOPS_ENV_CARTPOLE: if (n != 4) return GOPS_ERR_UNSUPPORTED; break;
+        case GOPS_ENV_PENDULUM: if (n != 3) return GOPS_ERR_UNSUPPORTED; break;
+        default: return GOPS_ERR_UNSUPPORTED;
+    }
+    if (e.data_env || e.act_dim < 1 || e.act_dim > GOPS_MAX_ACT) return GOPS_ERR_UNSUPPORTED;
+    if ((e.kind != GOPS_ENV_LQ && e.act_dim != 1) || e.repeat_num > GOPS_MAX_REPEAT) return GOPS_ERR_UNSUPPORTED;
+    return GOPS_OK;
+}
+
+// Adjoint of one WRAPPED model step (state_model_step above; the per-trajectory env phase of rollout_bwd.hip's streamed sweep in
+// register form), shared by the one-lane-per-trajectory sweeps (rollout_poly.hip, rollout_rbf.hip).
+// Gin: adjoint of the next observation; g_r: adjoint of the (shaped) reward; -> go: adjoint of the observation the step started from
+// (overwritten), gu: adjoint of the wrapped actions (overwritten).
+template <int ENV, int N>
+__device__ __forceinline__ void state_model_step_bwd(const GopsEnv& env, const float (&o)[N], const float (&u)[GOPS_MAX_ACT], bool dn,
+                                                    float g_r, const float (&Gin_)[N], float (&go)[N], float (&gu)[GOPS_MAX_ACT]) {
+    const float g_rm = dn ? 0.f : g_r;
+    float Gin[GOPS_MAX_LQ_STATE], gx[GOPS_MAX_LQ_STATE], x[GOPS_MAX_LQ_STATE];
+#pragma unroll
+    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { Gin[i] = 0.f; gx[i] = 0.f; x[i] = 0.f; }
+#pragma unroll
+    for (int i = 0; i < N; ++i) { Gin[i] = Gin_[i]; x[i] = obs_unscale(env, i, o[i]); }
+#pragma unroll
+    for (int a = 0; a < GOPS_MAX_ACT; ++a) gu[a] = 0.f;
+    float rd;   // reward and done test of the recomputed sub-steps: not used here
+    bool dd;
+    const int nrep = env.repeat_num > 1 ? min(env.repeat_num, GOPS_MAX_REPEAT) : 1;
+    // ClipObservation saw the (rescaled) result of the last sub-step (idpendulum: no observation bounds)
+    if (env.clip_obs && ENV != GOPS_ENV_IDPENDULUM) {
+        float xl[GOPS_MAX_LQ_STATE], xfin[GOPS_MAX_LQ_STATE];
+#pragma unroll
+        for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) { xl[i] = x[i]; xfin[i] = x[i]; }
+        if (!dn) {
+#pragma unroll 1
+            for (int rep = 0; rep < nrep; ++rep) {
+                state_model_substep<ENV>(env, xl, u, xfin, rd, dd);
+#pragma unroll
+                for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) xl[i] = xfin[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const float pre = obs_rescale(env, i, xfin[i]);
+            if (!(pre >= env.obs_low[i] && pre <= env.obs_high[i])) Gin[i] = 0.f;
+        }
+    }
+    if (env.scale_obs) {   // d(scaled next obs) / d(next obs) = scale
+#pragma unroll
+        for (int i = 0; i < N; ++i) Gin[i] *= env.obs_scale[i];
+    }
+    float g[GOPS_MAX_LQ_STATE];
+#pragma unroll
+    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) g[i] = dn ? 0.f : Gin[i];
+    if (!dn) {
+        // ActionRepeatModel: sub-step rep starts from the state after rep sub-steps - recomputed from x for each (nrep <= 8, and
+        // nrep = 1 without the wrapper): no run-time indexed register arrays
+#pragma unroll 1
+        for (int rep = nrep - 1; rep >= 0; --rep) {
+            float xr[GOPS_MAX_LQ_STATE], xt[GOPS_MAX_LQ_STATE];
+#pragma unroll
+            for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) xr[i] = x[i];
+#pragma unroll 1
+            for (int k = 0; k < rep; ++k) {
+                state_model_substep<ENV>(env, xr, u, xt, rd, dd);
+#pragma unroll
+                for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) xr[i] = xt[i];
+            }
+            const float gr = (!env.repeat_last_reward || rep == nrep - 1 || nrep == 1) ? g_rm : 0.f;
+            float gxo[GOPS_MAX_LQ_STATE], guo[GOPS_MAX_ACT];
+            state_model_substep_bwd<ENV>(env, xr, u, g, gr, gxo, guo);
+#pragma unroll
+            for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) g[i] = gxo[i];
+#pragma unroll
+            for (int a = 0; a < GOPS_MAX_ACT; ++a) gu[a] += guo[a];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < GOPS_MAX_LQ_STATE; ++i) gx[i] = dn ? Gin[i] : g[i];
+#pragma unroll
+    for (int i = 0; i < N; ++i) go[i] = env.scale_obs ? gx[i] / env.obs_scale[i] : gx[i];   // d(obs / scale - shift) / d(obs)
+}
+
 // ================================ pyth_mobilerobot ============================================
 // gops/env/env_ocp/env_model/pyth_mobilerobot_model.py:24-213.  State = observation, 13 columns:
 //   [0..4] ego (x, y, theta, v, w)   [5..7] tracking errors (e_y, e_theta, e_v) of the NEW ego state   [8..12] obstacle (x, y, theta, v, w)

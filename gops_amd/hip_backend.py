@@ -27,6 +27,8 @@ ACT_IDS = {"linear": 0, "relu": 1, "elu": 2, "gelu": 3, "selu": 4, "sigmoid": 5,
 # GopsMlp.hidden_act of a POLY net (ABI v15): make_features(obs, d) for d = 1, 2, 3 and create_features(obs * norm_matrix, 2)
 POLY_FULL = {1: 16, 2: 17, 3: 18}
 POLY_SYM_2 = 24
+# GopsMlp.hidden_act of an RBF net (gops/apprfunc/gauss.py): DetermPolicy's affine head, FiniteHorizonPolicy's tanh head (GOPS_RBF_*)
+RBF_AFFINE, RBF_TANH = 32, 33
 # RPI's policy evaluation (gops_rpi_evaluate): env kinds of its own and the layout of its constant table (GOPS_RPI_* of gops_hip.h)
 RPI_ENV_OSCILLATOR, RPI_ENV_AIRCRAFT, RPI_ENV_SUSPENSION = 1, 2, 3
 (RPI_C_GAMMA_ATTE, RPI_C_DT, RPI_C_R, RPI_C_ACT_LOW, RPI_C_ACT_HIGH, RPI_C_ADV_LOW, RPI_C_ADV_HIGH, RPI_C_SCALE_ACT_LOW,
@@ -221,6 +223,9 @@ def _signatures():
         "gops_poly_value_workspace_bytes": (sz, [mlp, i32]),
         "gops_poly_value_forward": (rc, [mlp, i32, vp, vp, vp]),
         "gops_poly_value_backward": (rc, [mlp, i32, vp, vp, grad, vp, sz, vp]),
+        "gops_rbf_rollout_workspace_bytes": (sz, [desc]),
+        "gops_rbf_rollout_forward": (rc, [desc, rin, rout, vp, sz, vp]),
+        "gops_rbf_rollout_backward": (rc, [desc, rin, vp, grad, adj, vp, sz, vp]),
         "gops_rpi_state_bytes": (sz, [i32, i32]),
         "gops_rpi_evaluate": (rc, [i32, i32, i32, _fp, vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, vp, vp, vp]),
         "gops_rpi_mlp_state_bytes": (sz, [i32, i32, mlp]),
@@ -728,6 +733,76 @@ class PolyRollout:
         check(lib().gops_poly_rollout_backward(C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g),
                                                self.workspace.data_ptr(), self.workspace.numel(), _stream()),
               "gops_poly_rollout_backward")
+
+
+def make_rbf(w: torch.Tensor, b: torch.Tensor, C: torch.Tensor, sigma_square: torch.Tensor, head_code: int) -> GopsMlp:
+    """`GopsMlp` of an RBF net (gops_rbf_rollout_*): n_layers = 1, sizes = (in_dim, out_dim, K), hidden_act = RBF_AFFINE / RBF_TANH,
+    weight[0] = w [1, out, K], bias[0] = b [1, out, 1], weight[1] = C [1, K, in_dim], bias[1] = sigma_square [1, K] (the module's
+    own storage: contiguous, so the leading 1 and the trailing 1 change nothing).  The library checks in_dim and the head against
+    the env's obs_dim and the rollout's finite_horizon."""
+    for t in (w, b, C, sigma_square):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("make_rbf: the four parameter tensors must be contiguous fp32")
+    K, in_dim, out = C.shape[-2], C.shape[-1], w.shape[-2]
+    if w.shape[-1] != K or sigma_square.numel() != K or b.numel() != out:
+        raise RuntimeError(f"make_rbf: shapes w {tuple(w.shape)}, b {tuple(b.shape)}, C {tuple(C.shape)}, sigma_square "
+                           f"{tuple(sigma_square.shape)} do not describe one RBF net")
+    m = GopsMlp()
+    m.n_layers = 1
+    m.hidden_act = int(head_code)
+    m.sizes[0], m.sizes[1], m.sizes[2] = in_dim, out, K
+    m.weight[0], m.bias[0], m.weight[1], m.bias[1] = _ptr(w), _ptr(b), _ptr(C), _ptr(sigma_square)
+    m._keep = (w, b, C, sigma_square)
+    return m
+
+
+class RbfRollout:
+    """`PolyRollout`'s call surface for a GAUSS policy: `gops_rbf_rollout_forward / _backward`, one lane per trajectory
+    (csrc/rollout_rbf.hip).  `backward(grad_v, grads)`: `grads` holds the four gradient tensors in `state_dict` order (C,
+    sigma_square, w, b).  No tail value (a caller composes it from `final_obs` and hands `grad_final_obs` back), no phases, no fused
+    update tail."""
+
+    def __init__(self, env: GopsEnv, policy: GopsMlp, *, batch: int, horizon: int, gamma: float, finite_horizon: bool,
+                 need_grad: bool = True, device: Optional[torch.device] = None, dtype=None, variant_flags: Optional[int] = None):
+        """`dtype` must be fp32 and `variant_flags` empty: the RBF kernels have no other arithmetic and no variants."""
+        if dtype_id(dtype) != 0:
+            raise RuntimeError("RbfRollout: GAUSS approximators run in fp32 only (mlp_dtype fp16 is an MLP setting)")
+        if variant_flags:
+            raise RuntimeError(f"RbfRollout: no kernel variants on the GAUSS path (variant_flags {variant_flags:#x})")
+        self.desc = _rollout_desc(env, policy, None, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
+                                  need_grad=need_grad, tail_unmasked=False)
+        self._mlps = (policy, None)
+        _rollout_workspace(self, lib().gops_rbf_rollout_workspace_bytes,
+                           "gops_rbf_rollout_workspace_bytes: descriptor rejected (RBF net, env model or wrapper outside "
+                           "the HIP GAUSS path)", device)
+        self._in = GopsRolloutIn()
+
+    def set_policy(self, policy: GopsMlp, value=None):
+        if value is not None:
+            raise NotImplementedError("RbfRollout: no tail value inside the RBF rollout")
+        _rebind_nets(self, policy, None)
+
+    def forward(self, data: Dict[str, torch.Tensor], *, want_rewards=False, want_final=False):
+        d, i = self.desc, self._in
+        i.obs, i.done = _ptr(data["obs"]), _ptr(data.get("done"))
+        self._keep = dict(data)
+        out, res = _rollout_outputs(self, want_rewards, want_final)
+        check(lib().gops_rbf_rollout_forward(C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(),
+                                             self.workspace.numel(), _stream()), "gops_rbf_rollout_forward")
+        return res
+
+    def backward(self, grad_v: torch.Tensor, grads: Sequence[torch.Tensor], grad_final_obs: Optional[torch.Tensor] = None,
+                 grad_obs: Optional[torch.Tensor] = None):
+        """`grad_final_obs` [B, obs_dim]: d(loss)/d(final_obs), None = zeros; `grad_obs` [B, obs_dim]: filled with d(loss)/d(obs)."""
+        g_C, g_s, g_w, g_b = grads
+        g = GopsMlpGrad()
+        g.weight[0], g.bias[0], g.weight[1], g.bias[1] = _ptr(g_w), _ptr(g_b), _ptr(g_C), _ptr(g_s)
+        adj = GopsRolloutAdjoint()
+        adj.grad_final_obs, adj.grad_obs, adj.first_step_only = _ptr(grad_final_obs), _ptr(grad_obs), 0
+        self._adj_keep = (grad_final_obs, grad_obs)
+        check(lib().gops_rbf_rollout_backward(C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), C.byref(adj),
+                                              self.workspace.data_ptr(), self.workspace.numel(), _stream()),
+              "gops_rbf_rollout_backward")
 
 
 class PolyValueNet:

@@ -25,7 +25,7 @@ def get_activation_func(key: str):
 
 def get_apprfunc_dict(key: str, **kwargs):
     """Collect the per-network constructor arguments `<key>_func_type`, `<key>_hidden_sizes`, ...
-    out of the flat args dict (the MLP and POLY families exist on this path)."""
+    out of the flat args dict (the MLP, POLY, GAUSS and LipsNet families exist on this path)."""
     var = dict()
     var["apprfunc"] = kwargs[key + "_func_type"]
     var["name"] = kwargs[key + "_func_name"]
@@ -43,6 +43,8 @@ def get_apprfunc_dict(key: str, **kwargs):
         var["degree"] = kwargs[key + "_degree"]
         var["add_bias"] = kwargs[key + "_add_bias"]
         var["norm_matrix"] = kwargs.get("norm_matrix", None)
+    elif apprfunc_type == "GAUSS" and key + "_num_kernel" in kwargs:   # gops_amd/apprfunc/gauss.py (reference common_utils.py:92-93)
+        var["num_kernel"] = kwargs[key + "_num_kernel"]
     elif apprfunc_type == "LipsNet":   # gops_amd/apprfunc/lipsnet.py (reference common_utils.py:94-106)
         var["hidden_sizes"] = kwargs[key + "_hidden_sizes"]
         var["hidden_activation"] = kwargs[key + "_hidden_activation"]
@@ -52,8 +54,10 @@ def get_apprfunc_dict(key: str, **kwargs):
             var[name] = kwargs[key + "_" + name]
         var["mlp_dtype"] = kwargs.get("mlp_dtype", "fp32")   # (the module refuses fp16 at construction)
     else:
-        raise NotImplementedError(f"apprfunc type {apprfunc_type} is outside the MI355X ADP path (MLP and POLY only, "
-                                  "LipsNet for the policy of INFADP)")
+        # (GAUSS lands here without its kernel count: the family has no default for it, in the reference either)
+        raise NotImplementedError(f"apprfunc type {apprfunc_type}{' without ' + key + '_num_kernel' if apprfunc_type == 'GAUSS' else ''} "
+                                  "is outside the MI355X ADP path (MLP and POLY only, GAUSS for the policy of FHADP and INFADP with "
+                                  "<key>_num_kernel, LipsNet for the policy of INFADP)")
     if kwargs["action_type"] == "continu":
         var["act_high_lim"] = np.array(kwargs["action_high_limit"])
         var["act_low_lim"] = np.array(kwargs["action_low_limit"])

@@ -87,6 +87,12 @@ enum { GOPS_ACT_LINEAR = 0, GOPS_ACT_RELU = 1, GOPS_ACT_ELU = 2, GOPS_ACT_GELU =
  *                     order, i-major, duplicates included (degree 3: (x_i x_j) x_l): F = n + n^2 + .. + n^d features.
  *   GOPS_POLY_SYM_2   create_features(obs * norm_matrix, 2) (:61-83): x_i x_j for i <= j, i-major: n (n + 1) / 2 features. */
 enum { GOPS_POLY_FULL_1 = 16, GOPS_POLY_FULL_2 = 17, GOPS_POLY_FULL_3 = 18, GOPS_POLY_SYM_2 = 24 };
+/* Heads of an RBF net (gops/apprfunc/gauss.py), in GopsMlp.hidden_act of a description with n_layers = 1 (additive, the version
+ * number stays 15): y = w phi(x) + b over K Gaussian kernels, then
+ *   GOPS_RBF_AFFINE  DetermPolicy (:61-65): a = half y + mid, x = obs
+ *   GOPS_RBF_TANH    FiniteHorizonPolicy (:85-93): a = half tanh(y) + mid, x = (obs, virtual_t = step + 1)
+ * with half = (policy_high - policy_low) / 2 and mid = (policy_high + policy_low) / 2 of GopsEnv. */
+enum { GOPS_RBF_AFFINE = 32, GOPS_RBF_TANH = 33 };
 
 /* Arithmetic of the MLP contractions (BASELINE.json configs[4]: "fp16 MFMA MLP path").
  *   GOPS_DTYPE_F32: fp32 results at the 1e-4 parity bar (default).  NOT bit-level fp32 arithmetic where the plane-split
@@ -499,6 +505,27 @@ size_t gops_poly_value_workspace_bytes(const GopsMlp* value, int32_t batch);
 int gops_poly_value_forward(const GopsMlp* value, int32_t batch, const float* obs, float* v, void* stream);
 int gops_poly_value_backward(const GopsMlp* value, int32_t batch, const float* obs, const float* grad_v,
                              const GopsMlpGrad* grad, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ABI v15, additive entry points (the version number stays 15).  GAUSS approximators (gops/apprfunc/gauss.py: DetermPolicy,
+ * FiniteHorizonPolicy over radial basis functions) on the model rollout, one lane per trajectory (csrc/rollout_rbf.hip).  An RBF net is
+ * a GopsMlp with n_layers = 1 and hidden_act = GOPS_RBF_* (the MLP and POLY entry points reject it):
+ *   sizes = (in_dim, out_dim, K): in_dim = obs_dim for GOPS_RBF_AFFINE, obs_dim + 1 for GOPS_RBF_TANH (the virtual time is the LAST
+ *   input; checked with the head against desc->finite_horizon: GOPS_ERR_BAD_ARG otherwise), out_dim = act_dim, 1 <= K <= 64;
+ *   weight[0] = w [out][K], bias[0] = b [out], weight[1] = C [K][in_dim], bias[1] = sigma_square [K], all required;
+ *   GopsMlpGrad uses the same four slots, all required.
+ *   phi_k = exp(-|x - C_k|^2 / (2 |sigma_square_k|)), y = w phi + b; the head's limits are GopsEnv.policy_low / policy_high.
+ * Env models, wrappers and the other limits are those of gops_poly_rollout_*: fp32, closed loop, variant_flags 0.  desc->tail_value
+ * must be 0 (GOPS_ERR_UNSUPPORTED): a caller composes a terminal value from GopsRolloutOut.final_obs / final_done and hands its
+ * adjoint back as adj->grad_final_obs.  `adj` may be NULL; grad_final_obs and grad_obs are honoured, first_step_only must be 0
+ * (GOPS_ERR_UNSUPPORTED).  The backward is three launches - the sweep (adjoints of the observations, g_y of every
+ * step), the parameter gradient as a sum over the horizon * batch samples, the fixed-order sum of its per-block rows: bitwise
+ * reproducible run to run. */
+size_t gops_rbf_rollout_workspace_bytes(const GopsRolloutDesc* desc);
+int gops_rbf_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const GopsRolloutOut* out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int gops_rbf_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v,
+                              const GopsMlpGrad* policy_grad, const GopsRolloutAdjoint* adj,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* ABI v15, additive entry points (the version number stays 15): RPI's policy evaluation (gops/algorithm/rpi.py local_update) as ONE
  * launch of one workgroup, one lane per batch row (csrc/rollout_rpi.hip).  Up to `max_steps` gradient steps on the weights of a
