@@ -277,7 +277,7 @@ __device__ __forceinline__ bool idp_done_trig(const IdpConst& C, const float* s,
 
 // ================================ the models whose observation is the state, register form ====
 // pyth_lq, gym_cartpoleconti, gym_pendulum, pyth_idpendulum for ONE trajectory held in registers: the single statement of the
-// arithmetic that env_step_kernel, the episode kernel (env_step.h), the POLY rollout (rollout_poly.hip) and the tile-form env
+// arithmetic that env_step_kernel, the episode kernel (env_step.h), the lane rollouts (lane_rollout.h) and the tile-form env
 // phases of rollout_fwd.hip / rollout_bwd.hip / rollout_h64.hip (rollout_env.h) step.
 // State arrays of every model here have GOPS_MAX_LQ_STATE entries (lq_forward's padded width); entries beyond the model's are zero.
 
@@ -412,29 +412,32 @@ __device__ __forceinline__ void state_model_step(const GopsEnv& env, const float
     }
 }
 
-// Host side: what the one-lane-per-trajectory rollouts (rollout_poly.hip, rollout_rbf.hip) ask of a description before they look at
-// its policy: shape, fp32, closed loop, no kernel variants, a model env whose observation is the state, the bounds of
+// The (env kind, obs_dim) pairs that state_model_step / state_model_step_bwd are instantiated for: the one list behind the check
+// below and the kernel dispatch of the one-lane-per-trajectory rollouts (lane_rollout.h).
+#define STATE_MODEL_CASES(X)                                                                                              \
+    X(GOPS_ENV_LQ, 1) X(GOPS_ENV_LQ, 2) X(GOPS_ENV_LQ, 3) X(GOPS_ENV_LQ, 4) X(GOPS_ENV_LQ, 5) X(GOPS_ENV_LQ, 6) \
+    X(GOPS_ENV_IDPENDULUM, 6) X(GOPS_ENV_CARTPOLE, 4) X(GOPS_ENV_PENDULUM, 3)
+
+// Host side: what the one-lane-per-trajectory rollouts (lane_rollout.h) ask of a description before they look at its policy:
+// shape, fp32, closed loop, no kernel variants, a model env whose observation is the state, the bounds of
 // state_model_step / state_model_step_bwd.
 inline int state_model_check_desc(const GopsRolloutDesc& d) {
     if (d.batch < 1 || d.horizon < 1 || d.horizon > GOPS_MAX_HORIZON) return GOPS_ERR_BAD_ARG;
     if (d.open_loop != 0 || d.dtype != GOPS_DTYPE_F32) return GOPS_ERR_UNSUPPORTED;
     if (d.variant_flags != 0) return GOPS_ERR_UNSUPPORTED;
     const GopsEnv& e = d.env;
-    const int n = e.obs_dim;
-    switch (e.kind) {
-        case GOPS_ENV_LQ: if (n < 1 || n > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED; break;
-        case GOPS_ENV_IDPENDULUM: if (n != 6) return GOPS_ERR_UNSUPPORTED; break;
-        case GOPS_ENV_CARTPOLE: if (n != 4) return GOPS_ERR_UNSUPPORTED; break;
-        case GOPS_ENV_PENDULUM: if (n != 3) return GOPS_ERR_UNSUPPORTED; break;
-        default: return GOPS_ERR_UNSUPPORTED;
-    }
+    bool listed = false;
+#define STATE_MODEL_LISTED(EE, NN) listed = listed || (e.kind == EE && e.obs_dim == NN);
+    STATE_MODEL_CASES(STATE_MODEL_LISTED)
+#undef STATE_MODEL_LISTED
+    if (!listed) return GOPS_ERR_UNSUPPORTED;
     if (e.data_env || e.act_dim < 1 || e.act_dim > GOPS_MAX_ACT) return GOPS_ERR_UNSUPPORTED;
     if ((e.kind != GOPS_ENV_LQ && e.act_dim != 1) || e.repeat_num > GOPS_MAX_REPEAT) return GOPS_ERR_UNSUPPORTED;
     return GOPS_OK;
 }
 
 // Adjoint of one WRAPPED model step (state_model_step above; the per-trajectory env phase of rollout_bwd.hip's streamed sweep in
-// register form), shared by the one-lane-per-trajectory sweeps (rollout_poly.hip, rollout_rbf.hip).
+// register form), called by the one-lane-per-trajectory backward walk (lane_rollout.h: lane_backward).
 // Gin: adjoint of the next observation; g_r: adjoint of the (shaped) reward; -> go: adjoint of the observation the step started from
 // (overwritten), gu: adjoint of the wrapped actions (overwritten).
 template <int ENV, int N>

@@ -10,7 +10,7 @@
 hipError_t launch_upload_params(const RolloutParams& p, RolloutParams* dst, hipStream_t s);
 hipError_t launch_prologue(const RolloutParams& p, RolloutParams* dst, int P, float pdt, hipStream_t s);
 
-// ---- dw_gemm.hip: the fixed-order reduce of split-K slabs (also rollout_poly.hip's and rollout_lips.hip's partials) ----
+// ---- dw_gemm.hip: the fixed-order reduce of split-K slabs (also the partials of rollout_poly.hip, rollout_rbf.hip, rollout_lips.hip) ----
 hipError_t launch_reduce(const ReduceJobs& jobs, hipStream_t s);
 
 // ---- optim.hip: the loss scalars of a batch (dw_gemm.hip: the loss mean that rides on a reduce) ----

@@ -5,12 +5,10 @@
 //   DetermPolicy (GOPS_RBF_AFFINE): x = obs,              a = half y + mid
 //   FiniteHorizonPolicy (GOPS_RBF_TANH): x = (obs, t + 1), a = half tanh(y) + mid      half / mid from GopsEnv.policy_low / _high
 //
-//   rbf_fwd_kernel         a loop over the kernels k with C, s, w as wave-uniform loads (no phi[] array: y is accumulated directly),
-//                          head, wrap_action, the wrapped model step of env_models.h; sum_t gamma^t r_t.  With need_grad the
-//                          observation each step starts from and its done flag are stashed as [t][i][B] / [t][B].
-//   rbf_sweep_kernel       the same lane walks the horizon backwards: y recomputed from the stash, state_model_step_bwd,
-//                          wrap_action_bwd, the head's adjoint -> g_y, stored as [t][a][B]; g_x by one more loop over k.  No
-//                          parameter-gradient registers: at K = 64, n = 7, A = 4 they would be 772 per lane.
+//   rbf_fwd_kernel         the forward walk of lane_rollout.h; its policy is a loop over the kernels k with C, s, w as wave-uniform
+//                          loads (no phi[] array: y is accumulated directly), then the head.
+//   rbf_sweep_kernel       the backward walk: y recomputed from the stash, the head's adjoint -> g_y, stored as [t][a][B]; g_x by
+//                          one more loop over k.  No parameter-gradient registers: at K = 64, n = 7, A = 4 they would be 772 per lane.
 //   rbf_param_grad_kernel  the parameter gradient is a plain sum over the H * B samples (t, b) of a function of
 //                          (stashed obs, t + 1, g_y): grid = (sample blocks, kernel groups of RBF_GROUP), one lane per sample (a
 //                          fixed stride over the samples beyond RBF_MAX_SAMPLE_BLOCKS blocks), n + 1 + A accumulators per kernel
@@ -19,42 +17,26 @@
 //
 // No tail value in these kernels: INFADP composes it on the host from final_obs / grad_final_obs (algorithm/infadp.py).
 // Bounds (everything else is refused by the host code): 1 <= K <= 64, obs_dim <= 6 (input width <= 7), out = act_dim <= GOPS_MAX_ACT.
-#include <math.h>
-#include <string.h>
-
-#include "common.h"
-#include "env_models.h"
+#include "lane_rollout.h"
 #include "launchers.h"
 
-#define RBF_THREADS 256
 #define RBF_MAX_K 64
 #define RBF_GROUP 8                  // kernels per block of the parameter-gradient launch: 8 * (7 + 1 + 4) + 4 accumulators
 #define RBF_MAX_SAMPLE_BLOCKS 1024   // partial rows per gradient tensor at most; beyond it a lane adds several samples, in index order
 
 struct RbfParams {
-    GopsEnv env;                 // padded (lq_pad_env)
-    int B, H, A, K, need_grad, nblk;
+    GopsEnv env;                 // padded (lq_pad_env); the forward and the sweep read its LDS copy (lane_stage_env)
+    LaneParams l;
+    int K, nblk;
     const float* w;              // [A][K]
     const float* b;              // [A]
     const float* C;              // [K][NI], NI = obs_dim (+ 1: the virtual time, last)
     const float* s;              // sigma_square [K]
-    const float* obs;            // [B][N]
-    const float* done;           // [B] or null
-    const float* grad_v;         // backward: [B]
-    const float* grad_final_obs; // backward: [B][N] or null
-    float* grad_obs;             // backward: [B][N] or null
-    float* v_pi;                 // [B]
-    float* rewards;              // [H][B] or null
-    float* final_obs;            // [B][N] or null
-    float* final_done;           // [B] or null
-    float* st_obs;               // [H + 1][N][B]
-    float* st_done;              // [H + 1][B]
     float* st_gy;                // [H][A][B]
     float* part_w;               // [nblk][A * K]
     float* part_b;               // [nblk][A]
     float* part_C;               // [nblk][K * NI]
     float* part_s;               // [nblk][K]
-    float gpow[GOPS_MAX_HORIZON + 1];
 };
 static_assert(sizeof(RbfParams) <= 4000, "RbfParams outgrew the kernel-argument segment");
 
@@ -82,14 +64,14 @@ __device__ __forceinline__ void rbf_input(const float (&o)[N], int t, float (&x)
 template <int NI>
 __device__ __forceinline__ void rbf_net(const RbfParams& p, const float (&x)[NI], float (&y)[GOPS_MAX_ACT]) {
 #pragma unroll
-    for (int a = 0; a < GOPS_MAX_ACT; ++a) y[a] = a < p.A ? p.b[a] : 0.f;
+    for (int a = 0; a < GOPS_MAX_ACT; ++a) y[a] = a < p.l.A ? p.b[a] : 0.f;
 #pragma unroll 1
     for (int k = 0; k < p.K; ++k) {
         float r;
         const float phi = rbf_phi<NI>(p.C + k * NI, p.s[k], x, r);
 #pragma unroll
         for (int a = 0; a < GOPS_MAX_ACT; ++a)
-            if (a < p.A) y[a] += p.w[a * p.K + k] * phi;
+            if (a < p.l.A) y[a] += p.w[a * p.K + k] * phi;
     }
 }
 
@@ -109,144 +91,80 @@ __device__ __forceinline__ float rbf_head_bwd(const GopsEnv& e, int a, float y, 
     return g * half;
 }
 
-// pre-wrapper and wrapped actions of the policy at observation o, step t
+// the policy at observation o, step t: the net's input x and outputs y (a step's State of the walks), the pre-wrapper actions
 template <int N, bool FH>
-__device__ __forceinline__ void rbf_actions(const RbfParams& p, const GopsEnv& env, const float (&x)[N + (FH ? 1 : 0)], float (&y)[GOPS_MAX_ACT],
-                                            float (&abar)[GOPS_MAX_ACT], float (&u)[GOPS_MAX_ACT]) {
-    rbf_net<N + (FH ? 1 : 0)>(p, x, y);
+struct RbfStep {
+    float x[N + (FH ? 1 : 0)], y[GOPS_MAX_ACT];
+};
+template <int N, bool FH>
+__device__ __forceinline__ void rbf_policy(const RbfParams& p, const GopsEnv& env, const float (&o)[N], int t, RbfStep<N, FH>& st,
+                                           float (&abar)[GOPS_MAX_ACT]) {
+    rbf_input<N, FH>(o, t, st.x);
+    rbf_net<N + (FH ? 1 : 0)>(p, st.x, st.y);
 #pragma unroll
-    for (int a = 0; a < GOPS_MAX_ACT; ++a) {
-        abar[a] = a < p.A ? rbf_head<FH>(env, a, y[a]) : 0.f;
-        u[a] = a < p.A ? wrap_action(env, a, abar[a]) : 0.f;
-    }
-}
-
-// The env description in LDS.  Read through the kernel argument its ~150 scalars are wave-uniform loads that the compiler hoists
-// out of the step and kernel loops: more than the SGPR file holds (the pyth_lq kernels sat at its limit with 20 .. 110 scalar
-// spills and a reserved stack frame).  From LDS they are broadcast reads with immediate offsets, as in the 64-row half kernels
-// (common.h ENV_LDS_FLOATS).  Every thread of the block must call this (it holds a barrier).
-__device__ __forceinline__ const GopsEnv& rbf_stage_env(const RbfParams& p, unsigned* s_env) {
-    const unsigned* src = reinterpret_cast<const unsigned*>(&p.env);
-    for (int i = threadIdx.x; i < (int)(sizeof(GopsEnv) / sizeof(unsigned)); i += RBF_THREADS) s_env[i] = src[i];
-    __syncthreads();
-    return *reinterpret_cast<const GopsEnv*>(s_env);
+    for (int a = 0; a < GOPS_MAX_ACT; ++a) abar[a] = a < p.l.A ? rbf_head<FH>(env, a, st.y[a]) : 0.f;
 }
 
 // ---- forward rollout -----------------------------------------------------------------------------------------------------------
 template <int ENV, int N, bool FH>
-__global__ __launch_bounds__(RBF_THREADS) void rbf_fwd_kernel(const RbfParams p) {
-    constexpr int NI = N + (FH ? 1 : 0);
+__global__ __launch_bounds__(LANE_THREADS) void rbf_fwd_kernel(const RbfParams p) {
     __shared__ unsigned s_env[sizeof(GopsEnv) / sizeof(unsigned)];
-    const GopsEnv& env = rbf_stage_env(p, s_env);
-    const int b = blockIdx.x * RBF_THREADS + threadIdx.x;
-    if (b >= p.B) return;   // (no block-wide step after the staging)
-    const size_t B = (size_t)p.B;
-    const bool nomask = env.no_mask_at_done != 0;
-    float o[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) o[i] = p.obs[(size_t)b * N + i];
-    bool dn = !nomask && p.done != nullptr && p.done[b] != 0.f;
-    bool done_last = false;
-    float v = 0.f;
-#pragma unroll 1
-    for (int t = 0; t < p.H; ++t) {
-        if (p.need_grad) {
-#pragma unroll
-            for (int i = 0; i < N; ++i) p.st_obs[((size_t)t * N + i) * B + b] = o[i];
-            p.st_done[(size_t)t * B + b] = dn ? 1.f : 0.f;
-        }
-        float x[NI], y[GOPS_MAX_ACT], abar[GOPS_MAX_ACT], u[GOPS_MAX_ACT];
-        rbf_input<N, FH>(o, t, x);
-        rbf_actions<N, FH>(p, env, x, y, abar, u);
-        float on[N], r;
-        bool done_m;
-        state_model_step<ENV, N>(env, o, u, dn, on, r, done_m);
-        float rr = dn ? 0.f : r;
-        if (env.shaping) rr = (rr + env.reward_shift) * env.reward_scale;
-        v += rr * p.gpow[t];
-        if (p.rewards != nullptr) p.rewards[(size_t)t * B + b] = rr;
-        dn = dn || (done_m && !nomask);
-        done_last = done_m;
-#pragma unroll
-        for (int i = 0; i < N; ++i) o[i] = on[i];
-    }
-    // no MaskAtDoneModel: final_done is the base model's done test on the last state
-    const bool dH = nomask ? done_last : dn;
-    if (p.need_grad) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) p.st_obs[((size_t)p.H * N + i) * B + b] = o[i];
-        p.st_done[(size_t)p.H * B + b] = dH ? 1.f : 0.f;
-    }
-    p.v_pi[b] = v;
-    if (p.final_obs != nullptr)
-#pragma unroll
-        for (int i = 0; i < N; ++i) p.final_obs[(size_t)b * N + i] = o[i];
-    if (p.final_done != nullptr) p.final_done[b] = dH ? 1.f : 0.f;
+    const GopsEnv& env = lane_stage_env(p.env, s_env);
+    const int b = blockIdx.x * LANE_THREADS + threadIdx.x;
+    if (b >= p.l.B) return;   // (no block-wide step after the staging)
+    using Step = RbfStep<N, FH>;
+    LANE_FORWARD_LOOP(env, p.l, Step, (rbf_policy<N, FH>(p, env, o, t, st, abar)))
+    LANE_FORWARD_FINISH(p.l)   // (no tail value in these kernels)
 }
 
 // ---- backward sweep: adjoints of the observations, g_y of every step ---------------------------------------------------------------
 template <int ENV, int N, bool FH>
-__global__ __launch_bounds__(RBF_THREADS) void rbf_sweep_kernel(const RbfParams p) {
+__global__ __launch_bounds__(LANE_THREADS) void rbf_sweep_kernel(const RbfParams p) {
     constexpr int NI = N + (FH ? 1 : 0);
     __shared__ unsigned s_env[sizeof(GopsEnv) / sizeof(unsigned)];
-    const GopsEnv& env = rbf_stage_env(p, s_env);
-    const int b = blockIdx.x * RBF_THREADS + threadIdx.x;
-    if (b >= p.B) return;   // (no block-wide step after the staging)
-    const size_t B = (size_t)p.B;
-    const float gv = p.grad_v[b];
-    float go[N], o[N];
+    const GopsEnv& env = lane_stage_env(p.env, s_env);
+    const int b = blockIdx.x * LANE_THREADS + threadIdx.x;
+    if (b >= p.l.B) return;   // (no block-wide step after the staging)
+    lane_backward<ENV, N, RbfStep<N, FH>>(
+        env, p.l, b,
+        [&](const float (&o)[N], int t, RbfStep<N, FH>& st, float (&abar)[GOPS_MAX_ACT]) { rbf_policy<N, FH>(p, env, o, t, st, abar); },
+        [&](int t, const float (&)[N], const RbfStep<N, FH>& st, const float (&ga)[GOPS_MAX_ACT], float (&gx)[N]) {
+            const float (&x)[NI] = st.x;
+            float gy[GOPS_MAX_ACT];
 #pragma unroll
-    for (int i = 0; i < N; ++i) go[i] = p.grad_final_obs != nullptr ? p.grad_final_obs[(size_t)b * N + i] : 0.f;
+            for (int a = 0; a < GOPS_MAX_ACT; ++a) {
+                gy[a] = a < p.l.A ? rbf_head_bwd<FH>(env, a, st.y[a], ga[a]) : 0.f;
+                // (a row that is done has ga = 0, so g_y = 0: rbf_param_grad_kernel adds exact zeros for it without a test)
+                if (a < p.l.A) p.st_gy[((size_t)t * p.l.A + a) * (size_t)p.l.B + b] = gy[a];
+            }
+            // g_x -= sum_k g_phi_k phi_k (x - C_k) / |s_k|  (observation inputs only: the time column takes no adjoint)
 #pragma unroll 1
-    for (int t = p.H - 1; t >= 0; --t) {
+            for (int k = 0; k < p.K; ++k) {
+                const float* Ck = p.C + k * NI;
+                const float s = p.s[k];
+                float r;
+                const float phi = rbf_phi<NI>(Ck, s, x, r);
+                float gphi = 0.f;
 #pragma unroll
-        for (int i = 0; i < N; ++i) o[i] = p.st_obs[((size_t)t * N + i) * B + b];
-        const bool dn = p.st_done[(size_t)t * B + b] != 0.f;
-        float x[NI], y[GOPS_MAX_ACT], abar[GOPS_MAX_ACT], u[GOPS_MAX_ACT];
-        rbf_input<N, FH>(o, t, x);
-        rbf_actions<N, FH>(p, env, x, y, abar, u);
-        float g_r = gv * p.gpow[t];   // adjoint of the shaped reward
-        if (env.shaping) g_r *= env.reward_scale;
-        float gu[GOPS_MAX_ACT], gx[N], gy[GOPS_MAX_ACT];
-        state_model_step_bwd<ENV, N>(env, o, u, dn, g_r, go, gx, gu);
+                for (int a = 0; a < GOPS_MAX_ACT; ++a)
+                    if (a < p.l.A) gphi += p.w[a * p.K + k] * gy[a];
+                const float c = gphi * phi / fabsf(s);
 #pragma unroll
-        for (int a = 0; a < GOPS_MAX_ACT; ++a) {
-            gy[a] = a < p.A ? rbf_head_bwd<FH>(env, a, y[a], wrap_action_bwd(env, a, abar[a], gu[a])) : 0.f;
-            // (a row that is done has gu = 0, so g_y = 0: rbf_param_grad_kernel adds exact zeros for it without a test)
-            if (a < p.A) p.st_gy[((size_t)t * p.A + a) * B + b] = gy[a];
-        }
-        // g_x -= sum_k g_phi_k phi_k (x - C_k) / |s_k|  (observation inputs only: the time column takes no adjoint)
-#pragma unroll 1
-        for (int k = 0; k < p.K; ++k) {
-            const float* Ck = p.C + k * NI;
-            const float s = p.s[k];
-            float r;
-            const float phi = rbf_phi<NI>(Ck, s, x, r);
-            float gphi = 0.f;
-#pragma unroll
-            for (int a = 0; a < GOPS_MAX_ACT; ++a)
-                if (a < p.A) gphi += p.w[a * p.K + k] * gy[a];
-            const float c = gphi * phi / fabsf(s);
-#pragma unroll
-            for (int i = 0; i < N; ++i) gx[i] -= c * (x[i] - Ck[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < N; ++i) go[i] = gx[i];
-    }
-    if (p.grad_obs != nullptr)
-#pragma unroll
-        for (int i = 0; i < N; ++i) p.grad_obs[(size_t)b * N + i] = go[i];
+                for (int i = 0; i < N; ++i) gx[i] -= c * (x[i] - Ck[i]);
+            }
+        },
+        [](float, float (&)[N]) {});   // (the seed is grad_final_obs alone)
 }
 
 // ---- parameter gradient: a sum over the H * B samples, RBF_GROUP kernels per block --------------------------------------------------
 template <int N, bool FH>
-__global__ __launch_bounds__(RBF_THREADS) void rbf_param_grad_kernel(const RbfParams p) {
+__global__ __launch_bounds__(LANE_THREADS) void rbf_param_grad_kernel(const RbfParams p) {
     constexpr int NI = N + (FH ? 1 : 0);
     constexpr int G = RBF_GROUP;
     constexpr int PER = NI + 1 + GOPS_MAX_ACT;        // per kernel: g_C [NI], g_s, g_w [A]
     constexpr int NS = G * PER + GOPS_MAX_ACT;        // + g_b [A]
     __shared__ float red[4 * NS];
-    const int k0 = blockIdx.y * G, K = p.K, A = p.A;
+    const int k0 = blockIdx.y * G, K = p.K, A = p.l.A;
     float acc[G][PER], gb[GOPS_MAX_ACT];
 #pragma unroll
     for (int j = 0; j < G; ++j)
@@ -254,14 +172,14 @@ __global__ __launch_bounds__(RBF_THREADS) void rbf_param_grad_kernel(const RbfPa
         for (int c = 0; c < PER; ++c) acc[j][c] = 0.f;
 #pragma unroll
     for (int a = 0; a < GOPS_MAX_ACT; ++a) gb[a] = 0.f;
-    const long long B = p.B, S = (long long)p.H * B, stride = (long long)gridDim.x * RBF_THREADS;
+    const long long B = p.l.B, S = (long long)p.l.H * B, stride = (long long)gridDim.x * LANE_THREADS;
 #pragma unroll 1
-    for (long long smp = (long long)blockIdx.x * RBF_THREADS + threadIdx.x; smp < S; smp += stride) {
+    for (long long smp = (long long)blockIdx.x * LANE_THREADS + threadIdx.x; smp < S; smp += stride) {
         const int t = (int)(smp / B);
         const size_t b = (size_t)(smp - (long long)t * B);
         float o[N], x[NI], gy[GOPS_MAX_ACT];
 #pragma unroll
-        for (int i = 0; i < N; ++i) o[i] = p.st_obs[((size_t)t * N + i) * (size_t)B + b];
+        for (int i = 0; i < N; ++i) o[i] = p.l.st_obs[((size_t)t * N + i) * (size_t)B + b];
         rbf_input<N, FH>(o, t, x);
 #pragma unroll
         for (int a = 0; a < GOPS_MAX_ACT; ++a) {
@@ -299,7 +217,7 @@ __global__ __launch_bounds__(RBF_THREADS) void rbf_param_grad_kernel(const RbfPa
     for (int a = 0; a < GOPS_MAX_ACT; ++a) wave_sum(gb[a], red, G * PER + a, NS);
     __syncthreads();
     const size_t blk = blockIdx.x;
-    for (int e = threadIdx.x; e < NS; e += RBF_THREADS) {
+    for (int e = threadIdx.x; e < NS; e += LANE_THREADS) {
         const float sum = (red[e] + red[NS + e]) + (red[2 * NS + e] + red[3 * NS + e]);
         if (e < G * PER) {
             const int j = e / PER, c = e - j * PER, k = k0 + j;
@@ -314,8 +232,6 @@ __global__ __launch_bounds__(RBF_THREADS) void rbf_param_grad_kernel(const RbfPa
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-
-static int rbf_blocks(int B) { return (B + RBF_THREADS - 1) / RBF_THREADS; }
 
 bool rbf_is_net(const GopsMlp& m) { return m.n_layers == 1 && (m.hidden_act == GOPS_RBF_AFFINE || m.hidden_act == GOPS_RBF_TANH); }
 
@@ -336,18 +252,17 @@ int rbf_check_desc(const GopsRolloutDesc& d) {
 }
 
 struct RbfPlan {
-    size_t obs, done, gy, pw, pb, pc, ps, bytes;
+    LaneStash st;
+    size_t gy, pw, pb, pc, ps, bytes;
     int nblk, groups;
 };
 static RbfPlan rbf_plan(const GopsRolloutDesc& d) {
     RbfPlan pl;
-    const int n = d.env.obs_dim, A = d.env.act_dim, B = d.batch, H = d.horizon, K = d.policy.sizes[2], NI = d.policy.sizes[0];
-    const long long sb = ((long long)H * B + RBF_THREADS - 1) / RBF_THREADS;
+    const int A = d.env.act_dim, B = d.batch, H = d.horizon, K = d.policy.sizes[2], NI = d.policy.sizes[0];
+    const long long sb = ((long long)H * B + LANE_THREADS - 1) / LANE_THREADS;
     pl.nblk = (int)(sb < RBF_MAX_SAMPLE_BLOCKS ? sb : RBF_MAX_SAMPLE_BLOCKS);
     pl.groups = (K + RBF_GROUP - 1) / RBF_GROUP;
-    size_t off = 0;
-    pl.obs = off; off += align256((size_t)(H + 1) * n * B * sizeof(float));
-    pl.done = off; off += align256((size_t)(H + 1) * B * sizeof(float));
+    size_t off = lane_stash_plan(d, pl.st);
     pl.gy = off; off += align256((size_t)H * A * B * sizeof(float));
     pl.pw = off; off += align256((size_t)pl.nblk * A * K * sizeof(float));
     pl.pb = off; off += align256((size_t)pl.nblk * A * sizeof(float));
@@ -360,59 +275,26 @@ static RbfPlan rbf_plan(const GopsRolloutDesc& d) {
 static RbfParams rbf_params(const GopsRolloutDesc& d, const RbfPlan& pl, void* ws) {
     RbfParams p;
     memset(&p, 0, sizeof(p));
-    p.env = d.env;
-    lq_pad_env(p.env);
-    p.B = d.batch; p.H = d.horizon; p.A = d.env.act_dim; p.K = d.policy.sizes[2]; p.need_grad = d.need_grad; p.nblk = pl.nblk;
+    lane_fill(d, ws, pl.st, p.env, p.l);
+    p.K = d.policy.sizes[2]; p.nblk = pl.nblk;
     p.w = d.policy.weight[0]; p.b = d.policy.bias[0]; p.C = d.policy.weight[1]; p.s = d.policy.bias[1];
     char* w = static_cast<char*>(ws);
-    p.st_obs = reinterpret_cast<float*>(w + pl.obs);
-    p.st_done = reinterpret_cast<float*>(w + pl.done);
     p.st_gy = reinterpret_cast<float*>(w + pl.gy);
     p.part_w = reinterpret_cast<float*>(w + pl.pw);
     p.part_b = reinterpret_cast<float*>(w + pl.pb);
     p.part_C = reinterpret_cast<float*>(w + pl.pc);
     p.part_s = reinterpret_cast<float*>(w + pl.ps);
-    for (int t = 0; t <= p.H; ++t) p.gpow[t] = (float)pow(d.gamma, (double)t);   // gamma^t formed in double, then rounded
     return p;
 }
 
-template <template <int, int, bool> class Launch>
-static hipError_t rbf_dispatch(int kind, int n, bool fh, const RbfParams& p, hipStream_t s) {
-    // one instantiation per (env kind, observation width, head): the kernels carry only their own model's arithmetic
-#define RBF_CASE(EE, NN) if (kind == EE && n == NN) return fh ? Launch<EE, NN, true>::run(p, s) : Launch<EE, NN, false>::run(p, s);
-    RBF_CASE(GOPS_ENV_LQ, 1) RBF_CASE(GOPS_ENV_LQ, 2) RBF_CASE(GOPS_ENV_LQ, 3)
-    RBF_CASE(GOPS_ENV_LQ, 4) RBF_CASE(GOPS_ENV_LQ, 5) RBF_CASE(GOPS_ENV_LQ, 6)
-    RBF_CASE(GOPS_ENV_IDPENDULUM, 6) RBF_CASE(GOPS_ENV_CARTPOLE, 4) RBF_CASE(GOPS_ENV_PENDULUM, 3)
-#undef RBF_CASE
-    return hipErrorInvalidValue;
-}
-template <int E, int N, bool FH> struct RbfFwd {
-    static hipError_t run(const RbfParams& p, hipStream_t s) {
-        hipLaunchKernelGGL((rbf_fwd_kernel<E, N, FH>), dim3(rbf_blocks(p.B)), dim3(RBF_THREADS), 0, s, p);
-        return hipGetLastError();
-    }
-};
-template <int E, int N, bool FH> struct RbfSweep {
-    static hipError_t run(const RbfParams& p, hipStream_t s) {
-        hipLaunchKernelGGL((rbf_sweep_kernel<E, N, FH>), dim3(rbf_blocks(p.B)), dim3(RBF_THREADS), 0, s, p);
-        return hipGetLastError();
-    }
-};
-template <int N, bool FH>
-static hipError_t rbf_launch_param_grad(const RbfParams& p, int groups, hipStream_t s) {
-    hipLaunchKernelGGL((rbf_param_grad_kernel<N, FH>), dim3(p.nblk, groups), dim3(RBF_THREADS), 0, s, p);
-    return hipGetLastError();
-}
-static hipError_t rbf_param_grad(int n, bool fh, const RbfParams& p, int groups, hipStream_t s) {   // (independent of the env)
-    switch (n) {
-        case 1: return fh ? rbf_launch_param_grad<1, true>(p, groups, s) : rbf_launch_param_grad<1, false>(p, groups, s);
-        case 2: return fh ? rbf_launch_param_grad<2, true>(p, groups, s) : rbf_launch_param_grad<2, false>(p, groups, s);
-        case 3: return fh ? rbf_launch_param_grad<3, true>(p, groups, s) : rbf_launch_param_grad<3, false>(p, groups, s);
-        case 4: return fh ? rbf_launch_param_grad<4, true>(p, groups, s) : rbf_launch_param_grad<4, false>(p, groups, s);
-        case 5: return fh ? rbf_launch_param_grad<5, true>(p, groups, s) : rbf_launch_param_grad<5, false>(p, groups, s);
-        case 6: return fh ? rbf_launch_param_grad<6, true>(p, groups, s) : rbf_launch_param_grad<6, false>(p, groups, s);
-        default: return hipErrorInvalidValue;
-    }
+// the forward (FWD) or sweep kernel of the description's (env kind, obs_dim, head)
+template <bool FWD>
+static hipError_t rbf_launch(const GopsRolloutDesc& d, const RbfParams& p, hipStream_t s) {
+    return lane_dispatch(d.env.kind, d.env.obs_dim, [&]<int E, int N>() {
+        const dim3 grid(lane_blocks(p.l.B));
+        if (d.finite_horizon) return lane_launch(FWD ? rbf_fwd_kernel<E, N, true> : rbf_sweep_kernel<E, N, true>, grid, s, p);
+        return lane_launch(FWD ? rbf_fwd_kernel<E, N, false> : rbf_sweep_kernel<E, N, false>, grid, s, p);
+    });
 }
 
 extern "C" {
@@ -422,23 +304,12 @@ size_t gops_rbf_rollout_workspace_bytes(const GopsRolloutDesc* desc) {
     return rbf_plan(*desc).bytes;
 }
 
-int gops_rbf_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in_p, const GopsRolloutOut* out_p, void* ws, size_t bytes,
+int gops_rbf_rollout_forward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const GopsRolloutOut* out, void* ws, size_t bytes,
                              void* stream) {
-    if (!desc || !in_p || !out_p) return GOPS_ERR_BAD_ARG;
-    const GopsRolloutDesc& d = *desc;
-    const GopsRolloutIn& in = *in_p;
-    const GopsRolloutOut& out = *out_p;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rc = rbf_check_desc(d);
+    RbfParams p;
+    const int rc = lane_forward_args(desc, in, out, ws, bytes, rbf_check_desc, rbf_plan, rbf_params, p);
     if (rc != GOPS_OK) return rc;
-    if (in.obs == nullptr || out.v_pi == nullptr) return GOPS_ERR_BAD_ARG;
-    const RbfPlan pl = rbf_plan(d);
-    if (ws == nullptr || bytes < pl.bytes) return GOPS_ERR_WORKSPACE;
-    RbfParams p = rbf_params(d, pl, ws);
-    p.obs = in.obs; p.done = in.done;
-    p.v_pi = out.v_pi; p.rewards = out.rewards; p.final_obs = out.final_obs; p.final_done = out.final_done;
-    const hipError_t e = rbf_dispatch<RbfFwd>(d.env.kind, d.env.obs_dim, d.finite_horizon != 0, p, s);
-    return e == hipSuccess ? GOPS_OK : (int)e;
+    return lane_rc(rbf_launch<true>(*desc, p, static_cast<hipStream_t>(stream)));
 }
 
 int gops_rbf_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* in, const float* grad_v, const GopsMlpGrad* grad,
@@ -455,16 +326,18 @@ int gops_rbf_rollout_backward(const GopsRolloutDesc* desc, const GopsRolloutIn* 
     const RbfPlan pl = rbf_plan(d);
     if (ws == nullptr || bytes < pl.bytes) return GOPS_ERR_WORKSPACE;
     RbfParams p = rbf_params(d, pl, ws);
-    p.grad_v = grad_v;
-    if (adj != nullptr) { p.grad_final_obs = adj->grad_final_obs; p.grad_obs = adj->grad_obs; }
-    const bool fh = d.finite_horizon != 0;
-    hipError_t e = rbf_dispatch<RbfSweep>(d.env.kind, d.env.obs_dim, fh, p, s);
+    p.l.grad_v = grad_v;
+    if (adj != nullptr) { p.l.grad_final_obs = adj->grad_final_obs; p.l.grad_obs = adj->grad_obs; }
+    hipError_t e = rbf_launch<false>(d, p, s);
     if (e != hipSuccess) return (int)e;
-    e = rbf_param_grad(d.env.obs_dim, fh, p, pl.groups, s);
+    e = lane_dispatch_width(d.env.obs_dim, [&]<int N>() {   // (the parameter gradient is independent of the env)
+        const dim3 grid(p.nblk, pl.groups);
+        return d.finite_horizon ? lane_launch(rbf_param_grad_kernel<N, true>, grid, s, p) : lane_launch(rbf_param_grad_kernel<N, false>, grid, s, p);
+    });
     if (e != hipSuccess) return (int)e;
     ReduceJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
-    const int A = p.A, K = p.K, NI = d.policy.sizes[0];
+    const int A = p.l.A, K = p.K, NI = d.policy.sizes[0];
     reduce_jobs_add(jobs, p.part_w, pl.nblk, 1, A * K, A * K, g.weight[0]);
     reduce_jobs_add(jobs, p.part_b, pl.nblk, 1, A, A, g.bias[0]);
     reduce_jobs_add(jobs, p.part_C, pl.nblk, 1, K * NI, K * NI, g.weight[1]);

@@ -685,54 +685,71 @@ def _poly_grad(grad_w: torch.Tensor, grad_b: Optional[torch.Tensor]) -> GopsMlpG
     return g
 
 
-class PolyRollout:
-    """`Rollout`'s call surface for a POLY policy (and POLY tail value): `gops_poly_rollout_forward / _backward`, one lane per
-    trajectory (csrc/rollout_poly.hip).  `backward(grad_v, [grad_weight], [grad_bias or None])` - the lists hold the one Linear
-    layer's gradient tensors, as `grad_buffers` / `poly_grad_buffers` hand them out.  No phases, no fused update tail: a POLY net
-    has one or two tensors."""
+class _LaneRollout:
+    """What the lane rollouts (csrc/lane_rollout.h) share here: the refusals, the descriptor and workspace set-up, `forward`.  A
+    subclass names its family, net and three library functions (`_fns`), and keeps `_prepare_nets`, `set_policy` and `backward`."""
+    _family = _net = _entry = _fns = None
 
-    def __init__(self, env: GopsEnv, policy: GopsMlp, *, batch: int, horizon: int, gamma: float, finite_horizon: bool,
-                 need_grad: bool = True, value: Optional[GopsMlp] = None, device: Optional[torch.device] = None,
-                 tail_unmasked: bool = False, dtype=None, variant_flags: Optional[int] = None):
-        """`dtype` must be fp32 and `variant_flags` empty: the POLY kernels have no other arithmetic and no variants."""
+    def __init__(self, env: GopsEnv, policy: GopsMlp, value: Optional[GopsMlp], *, batch, horizon, gamma, finite_horizon, need_grad,
+                 tail_unmasked, device, dtype, variant_flags):
+        name, fam = type(self).__name__, self._family
         if dtype_id(dtype) != 0:
-            raise RuntimeError("PolyRollout: POLY approximators run in fp32 only (mlp_dtype fp16 is an MLP setting)")
+            raise RuntimeError(f"{name}: {fam} approximators run in fp32 only (mlp_dtype fp16 is an MLP setting)")
         if variant_flags:
-            raise RuntimeError(f"PolyRollout: no kernel variants on the POLY path (variant_flags {variant_flags:#x})")
-        for net in (policy, value):   # a POLY GopsMlp learns its input width here (make_poly has only the weight's shape)
-            if net is not None:
-                net.sizes[0] = env.obs_dim
+            raise RuntimeError(f"{name}: no kernel variants on the {fam} path (variant_flags {variant_flags:#x})")
+        self._prepare_nets(env, policy, value)
         self.desc = _rollout_desc(env, policy, value, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
                                   need_grad=need_grad, tail_unmasked=tail_unmasked)
         self._mlps = (policy, value)
-        _rollout_workspace(self, lib().gops_poly_rollout_workspace_bytes,
-                           "gops_poly_rollout_workspace_bytes: descriptor rejected (POLY net, env model or wrapper outside "
-                           "the HIP POLY path)", device)
+        _rollout_workspace(self, self._fns(lib())[0], f"{self._entry}_workspace_bytes: descriptor rejected ({self._net} net, env model "
+                           f"or wrapper outside the HIP {fam} path)", device)
         self._in = GopsRolloutIn()
 
-    def set_policy(self, policy: GopsMlp, value: Optional[GopsMlp] = None):
-        for net in (policy, value):
-            if net is not None:
-                net.sizes[0] = self.desc.env.obs_dim
-        _rebind_nets(self, policy, value)
+    def _prepare_nets(self, env, policy, value):
+        """What a family writes into its nets; called after the refusals, so that a refused construction changes nothing."""
 
     def forward(self, data: Dict[str, torch.Tensor], *, want_rewards=False, want_final=False):
         d, i = self.desc, self._in
         i.obs, i.done = _ptr(data["obs"]), _ptr(data.get("done"))
         self._keep = dict(data)
         out, res = _rollout_outputs(self, want_rewards, want_final)
-        check(lib().gops_poly_rollout_forward(C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(),
-                                              self.workspace.numel(), _stream()), "gops_poly_rollout_forward")
+        check(self._fns(lib())[1](C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
+              self._entry + "_forward")
         return res
+
+    def _backward(self, grad_v, g: GopsMlpGrad, *adj):
+        check(self._fns(lib())[2](C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), *adj, self.workspace.data_ptr(),
+                             self.workspace.numel(), _stream()), self._entry + "_backward")
+
+
+class PolyRollout(_LaneRollout):
+    """`Rollout`'s call surface for a POLY policy (and POLY tail value): `gops_poly_rollout_forward / _backward`, one lane per
+    trajectory (csrc/rollout_poly.hip).  `backward(grad_v, [grad_weight], [grad_bias or None])` - the lists hold the one Linear
+    layer's gradient tensors, as `grad_buffers` / `poly_grad_buffers` hand them out.  No phases, no fused update tail: a POLY net
+    has one or two tensors."""
+    _family, _net, _entry = "POLY", "POLY", "gops_poly_rollout"
+    _fns = staticmethod(lambda L: (L.gops_poly_rollout_workspace_bytes, L.gops_poly_rollout_forward, L.gops_poly_rollout_backward))
+
+    def __init__(self, env: GopsEnv, policy: GopsMlp, *, batch: int, horizon: int, gamma: float, finite_horizon: bool,
+                 need_grad: bool = True, value: Optional[GopsMlp] = None, device: Optional[torch.device] = None,
+                 tail_unmasked: bool = False, dtype=None, variant_flags: Optional[int] = None):
+        """`dtype` must be fp32 and `variant_flags` empty: the POLY kernels have no other arithmetic and no variants."""
+        super().__init__(env, policy, value, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
+                         need_grad=need_grad, tail_unmasked=tail_unmasked, device=device, dtype=dtype, variant_flags=variant_flags)
+
+    def _prepare_nets(self, env, policy, value):   # a POLY GopsMlp learns its input width here (make_poly has only the weight's shape)
+        for net in filter(None, (policy, value)):
+            net.sizes[0] = env.obs_dim
+
+    def set_policy(self, policy: GopsMlp, value: Optional[GopsMlp] = None):
+        self._prepare_nets(self.desc.env, policy, value)
+        _rebind_nets(self, policy, value)
 
     def backward(self, grad_v: torch.Tensor, grad_w: List[torch.Tensor], grad_b: List[Optional[torch.Tensor]], **kw):
         if any(v is not None for v in kw.values()):
             raise NotImplementedError(f"PolyRollout.backward: {sorted(k for k, v in kw.items() if v is not None)} "
                                       "do not apply to a POLY rollout")
-        g = _poly_grad(grad_w[0], grad_b[0] if grad_b else None)
-        check(lib().gops_poly_rollout_backward(C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g),
-                                               self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_poly_rollout_backward")
+        self._backward(grad_v, _poly_grad(grad_w[0], grad_b[0] if grad_b else None))
 
 
 def make_rbf(w: torch.Tensor, b: torch.Tensor, C: torch.Tensor, sigma_square: torch.Tensor, head_code: int) -> GopsMlp:
@@ -756,40 +773,24 @@ def make_rbf(w: torch.Tensor, b: torch.Tensor, C: torch.Tensor, sigma_square: to
     return m
 
 
-class RbfRollout:
+class RbfRollout(_LaneRollout):
     """`PolyRollout`'s call surface for a GAUSS policy: `gops_rbf_rollout_forward / _backward`, one lane per trajectory
     (csrc/rollout_rbf.hip).  `backward(grad_v, grads)`: `grads` holds the four gradient tensors in `state_dict` order (C,
     sigma_square, w, b).  No tail value (a caller composes it from `final_obs` and hands `grad_final_obs` back), no phases, no fused
     update tail."""
+    _family, _net, _entry = "GAUSS", "RBF", "gops_rbf_rollout"
+    _fns = staticmethod(lambda L: (L.gops_rbf_rollout_workspace_bytes, L.gops_rbf_rollout_forward, L.gops_rbf_rollout_backward))
 
     def __init__(self, env: GopsEnv, policy: GopsMlp, *, batch: int, horizon: int, gamma: float, finite_horizon: bool,
                  need_grad: bool = True, device: Optional[torch.device] = None, dtype=None, variant_flags: Optional[int] = None):
         """`dtype` must be fp32 and `variant_flags` empty: the RBF kernels have no other arithmetic and no variants."""
-        if dtype_id(dtype) != 0:
-            raise RuntimeError("RbfRollout: GAUSS approximators run in fp32 only (mlp_dtype fp16 is an MLP setting)")
-        if variant_flags:
-            raise RuntimeError(f"RbfRollout: no kernel variants on the GAUSS path (variant_flags {variant_flags:#x})")
-        self.desc = _rollout_desc(env, policy, None, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
-                                  need_grad=need_grad, tail_unmasked=False)
-        self._mlps = (policy, None)
-        _rollout_workspace(self, lib().gops_rbf_rollout_workspace_bytes,
-                           "gops_rbf_rollout_workspace_bytes: descriptor rejected (RBF net, env model or wrapper outside "
-                           "the HIP GAUSS path)", device)
-        self._in = GopsRolloutIn()
+        super().__init__(env, policy, None, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
+                         need_grad=need_grad, tail_unmasked=False, device=device, dtype=dtype, variant_flags=variant_flags)
 
     def set_policy(self, policy: GopsMlp, value=None):
         if value is not None:
             raise NotImplementedError("RbfRollout: no tail value inside the RBF rollout")
         _rebind_nets(self, policy, None)
-
-    def forward(self, data: Dict[str, torch.Tensor], *, want_rewards=False, want_final=False):
-        d, i = self.desc, self._in
-        i.obs, i.done = _ptr(data["obs"]), _ptr(data.get("done"))
-        self._keep = dict(data)
-        out, res = _rollout_outputs(self, want_rewards, want_final)
-        check(lib().gops_rbf_rollout_forward(C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(),
-                                             self.workspace.numel(), _stream()), "gops_rbf_rollout_forward")
-        return res
 
     def backward(self, grad_v: torch.Tensor, grads: Sequence[torch.Tensor], grad_final_obs: Optional[torch.Tensor] = None,
                  grad_obs: Optional[torch.Tensor] = None):
@@ -800,9 +801,7 @@ class RbfRollout:
         adj = GopsRolloutAdjoint()
         adj.grad_final_obs, adj.grad_obs, adj.first_step_only = _ptr(grad_final_obs), _ptr(grad_obs), 0
         self._adj_keep = (grad_final_obs, grad_obs)
-        check(lib().gops_rbf_rollout_backward(C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), C.byref(adj),
-                                              self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_rbf_rollout_backward")
+        self._backward(grad_v, g, C.byref(adj))
 
 
 class PolyValueNet:
