@@ -256,6 +256,10 @@ def _signatures():
         "gops_cg_init": (rc, [vp, vp, vp, vp, i32, f64, vp, vp]),
         "gops_cg_step": (rc, [vp, vp, vp, vp, i32, f64, f64, vp, vp]),
         "gops_cg_finish": (rc, [vp, vp, vp, i32, vp, vp, vp]),
+        "gops_mpc_state_bytes": (sz, [i32, i32, i32]),
+        "gops_mpc_init": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "gops_mpc_step": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "gops_mpc_finish": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gops_dqn_backup_workspace_bytes": (sz, [P(GopsDqnBackup), i32]),
         "gops_dqn_backup": (rc, [P(GopsDqnBackup), i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gops_dqn_loss": (rc, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
@@ -1876,6 +1880,84 @@ class CgSolver:
         """The state block's fields on the host (one synchronisation)."""
         raw = GopsCgState.from_buffer_copy(self._state.cpu().numpy().tobytes())
         return {name: getattr(raw, name) for name, _ in GopsCgState._fields_[:9]}
+
+
+# gops_mpc_* (include/gops_hip.h: GOPS_MPC_*)
+MPC_MAX_DIM, MPC_MAX_HISTORY, MPC_HYPER_FLOATS, MPC_SCALARS, MPC_COUNTERS, MPC_VECTORS = 256, 8, 8, 5, 8, 6
+MPC_RUNNING, MPC_CONVERGED_PG, MPC_CONVERGED_F, MPC_LINE_SEARCH, MPC_NONFINITE = range(5)
+MPC_STATUS_NAMES = ("running", "converged_pg", "converged_f", "line_search", "nonfinite")
+# c1, shrink, max_ls, pgtol, ftol (scipy's L-BFGS-B: pgtol 1e-5, ftol = factr epsmch = 1e7 * 2.22e-16), curv_eps (its epsmch)
+MPC_HYPER_DEFAULTS = dict(c1=1e-4, shrink=0.5, max_ls=20, pgtol=1e-5, ftol=2.220446049250313e-9, curv_eps=2.220446049250313e-16)
+
+
+class MpcSolver:
+    """`batch` box-constrained L-BFGS problems of `n` variables side by side on the device (`gops_mpc_init / _step / _finish`,
+    csrc/mpc_lbfgs.hip): owns the state block, `x_trial [batch, n]` (where the caller evaluates), `f [batch]` and `g [batch, n]`
+    (where the caller leaves cost and gradient before `step`) and `hyper` (device: tolerances, `set_hyper`).  Nothing is read on the
+    host except by `finish` / `state`."""
+
+    def __init__(self, batch: int, n: int, lo, hi, device, history: int = 8):
+        self.batch, self.n, self.m = int(batch), int(n), int(history)
+        nbytes = lib().gops_mpc_state_bytes(self.batch, self.n, self.m)
+        if nbytes == 0:
+            raise RuntimeError(f"MpcSolver: batch {batch}, n {n}, history {history} is outside 1 <= n <= {MPC_MAX_DIM}, "
+                               f"1 <= history <= {MPC_MAX_HISTORY}, batch >= 1")
+        self.state_bytes = nbytes
+        self._state = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=device)   # (8-byte aligned)
+        bound = lambda v: torch.as_tensor(v, dtype=torch.float32).reshape(-1).expand(self.n).contiguous().to(device)
+        self.lo, self.hi = bound(lo), bound(hi)
+        self.x_trial = torch.zeros(self.batch, self.n, dtype=torch.float32, device=device)
+        self.f = torch.zeros(self.batch, dtype=torch.float32, device=device)
+        self.g = torch.zeros(self.batch, self.n, dtype=torch.float32, device=device)
+        self.x = torch.zeros(self.batch, self.n, dtype=torch.float32, device=device)
+        self.f_best = torch.zeros(self.batch, dtype=torch.float32, device=device)
+        self.status = torch.zeros(self.batch, dtype=torch.int32, device=device)
+        self.iterations = torch.zeros(self.batch, dtype=torch.int32, device=device)
+        self.hyper = torch.zeros(MPC_HYPER_FLOATS, dtype=torch.float32, device=device)
+        self.set_hyper()
+
+    def set_hyper(self, **kw):
+        """c1, shrink, max_ls, pgtol, ftol, curv_eps (MPC_HYPER_DEFAULTS for the ones not given): one small host-to-device copy."""
+        unknown = set(kw) - set(MPC_HYPER_DEFAULTS)
+        if unknown:
+            raise RuntimeError(f"MpcSolver.set_hyper: unknown {sorted(unknown)}")
+        h = dict(MPC_HYPER_DEFAULTS, **kw)
+        vals = [h[k] for k in ("c1", "shrink", "max_ls", "pgtol", "ftol", "curv_eps")] + [0.0, 0.0]
+        self.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+
+    def _args(self):
+        return self._state.data_ptr(), self.state_bytes, self.batch, self.n, self.m
+
+    def init(self, x0: torch.Tensor):
+        check(lib().gops_mpc_init(*self._args(), _ptr(x0), _ptr(self.lo), _ptr(self.hi), _ptr(self.x_trial), _stream()), "gops_mpc_init")
+
+    def step(self):
+        check(lib().gops_mpc_step(*self._args(), _ptr(self.f), _ptr(self.g), _ptr(self.x_trial), _ptr(self.hyper), _stream()),
+              "gops_mpc_step")
+
+    def finish(self):
+        """-> (x [batch, n], f [batch], status [batch] int32, iterations [batch] int32): the accepted points, on the device."""
+        check(lib().gops_mpc_finish(*self._args(), _ptr(self.x), _ptr(self.f_best), self.status.data_ptr(), self.iterations.data_ptr(),
+                                    _stream()), "gops_mpc_finish")
+        return self.x, self.f_best, self.status, self.iterations
+
+    def state(self) -> Dict[str, np.ndarray]:
+        """The state block's sections on the host (one synchronisation), named as in include/gops_hip.h."""
+        return mpc_decode_state(self._state.cpu().numpy().tobytes(), self.batch, self.n, self.m)
+
+
+def mpc_decode_state(raw: bytes, B: int, n: int, m: int) -> Dict[str, np.ndarray]:
+    nd, ni, nb = B * (MPC_SCALARS + m), B * MPC_COUNTERS, 2 * ((n + 1) // 2 * 2)
+    sc = np.frombuffer(raw, np.float64, nd).reshape(B, MPC_SCALARS + m)
+    ct = np.frombuffer(raw, np.int32, ni, 8 * nd).reshape(B, MPC_COUNTERS)
+    bounds = np.frombuffer(raw, np.float32, nb, 8 * nd + 4 * ni).reshape(2, nb // 2)[:, :n]
+    vec = np.frombuffer(raw, np.float32, B * (MPC_VECTORS + 2 * m) * n, 8 * nd + 4 * ni + 4 * nb).reshape(B, MPC_VECTORS + 2 * m, n)
+    out = dict(zip(("f", "f_prev", "alpha", "dphi", "gamma"), sc[:, :MPC_SCALARS].T.copy()), rho=sc[:, MPC_SCALARS:].copy())
+    out.update(zip(("status", "iterations", "evaluations", "ls_count", "head", "count"), ct.T.copy()))
+    out.update(lo=bounds[0].copy(), hi=bounds[1].copy())
+    out.update(zip(("x", "g", "x_prev", "g_prev", "d", "x_trial"), vec[:, :MPC_VECTORS].transpose(1, 0, 2).copy()))
+    out.update(s=vec[:, MPC_VECTORS:MPC_VECTORS + m].copy(), y=vec[:, MPC_VECTORS + m:].copy())
+    return out
 
 
 def make_update_tail(fused_adam=None, mean_of: Optional[torch.Tensor] = None, mean_scale: float = -1.0,

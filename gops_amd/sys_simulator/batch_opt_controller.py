@@ -1,0 +1,176 @@
+"""BatchOptController - shooting MPC for MANY states at once, solved on the device.
+
+`OptController` (opt_controller.py) solves one state per call inside scipy's L-BFGS-B: every cost evaluation is a batch-1 rollout
+launch followed by a device-to-host copy of the cost and of the Jacobian.  Here B states are B rows of ONE open-loop rollout, and
+the solver itself lives on the device (`hb.MpcSolver`: `gops_mpc_init / _step / _finish`, csrc/mpc_lbfgs.hip), so one iteration of
+all B problems is four calls and no host read:
+
+    1. Rollout.forward(head_pre = the trial actions)                 cost   = - v_pi (+ gamma^T terminal_cost(state_T))
+    2. backward_open_loop (backward_open_loop_adj with a terminal cost)   d cost / d action [B, T, A]
+    3. the fold of that gradient over each control interval               [B, n],  n = num_ctrl_points * act_dim
+    4. MpcSolver.step                                                     Armijo test, (s, y) pair, convergence tests, next trial
+
+The host reads the B status words once every `check_every` iterations (one synchronisation) and stops when no problem is running
+or after `max_iter` cost evaluations.  Between two reads a row that has finished is still part of the rollout (at its accepted
+point, which the step kernel keeps writing into its trial row) but is no longer moved.  The raw env description is `OptController`'s (identity action scaling, no observation clip,
+`no_mask_at_done`), the box is the model's action bounds, and the warm start across calls is its shift: drop the first control
+point, repeat the last - per row.
+
+Scope: shooting mode, box constraints.  A model with path constraints (`get_constraint`) is refused at construction; collocation,
+fp16 and graph capture of the loop are not provided.  What the solver does differently from scipy's L-BFGS-B - projected Armijo
+backtracking instead of the Cauchy point, subspace minimisation and the More-Thuente search; tolerances held in fp32 - is in
+include/gops_hip.h and DESIGN.md.
+"""
+import warnings
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from gops_amd import hip_backend as hb
+from gops_amd.sys_simulator.opt_controller import _INFO, _STATE_OBS_KINDS
+
+
+class BatchOptController:
+    def __init__(self, model, num_pred_step: int, ctrl_interval: int = 1, gamma: float = 1.0, use_terminal_cost: bool = False,
+                 terminal_cost=None, max_iter: int = 500, pgtol: float = hb.MPC_HYPER_DEFAULTS["pgtol"],
+                 ftol: float = hb.MPC_HYPER_DEFAULTS["ftol"], history: int = hb.MPC_MAX_HISTORY, check_every: int = 8, device=None):
+        """`max_iter`: the largest number of cost EVALUATIONS (rollout forward + backward of all rows) of one solve - every
+        backtracking trial counts, unlike scipy's `maxiter` / OptController's, which count accepted iterations.  `pgtol`, `ftol`:
+        the stopping tolerances of gops_mpc_step (scipy's L-BFGS-B defaults), held in fp32.  `check_every`: cost evaluations between
+        two host reads of the status words."""
+        assert num_pred_step % ctrl_interval == 0, "ctrl_interval should be a factor of num_pred_step."
+        base = model.unwrapped
+        self.model, self.base = model, base
+        self.terminal_cost = None
+        if use_terminal_cost:
+            self.terminal_cost = terminal_cost if terminal_cost is not None else getattr(model, "get_terminal_cost", None)
+            assert self.terminal_cost is not None, "Choose to use terminal cost, but there is no available terminal cost function."
+            if base.hip_kind not in _STATE_OBS_KINDS:
+                raise NotImplementedError("a terminal cost needs the adjoint of the final observation, which the kernels provide for "
+                                          "the models whose observation is the state")
+        elif terminal_cost is not None:
+            warnings.warn("Choose not to use terminal cost, but a terminal cost function is given. This will be ignored.")
+        self.obs_dim, self.action_dim, self.sim_dt = base.obs_dim, base.action_dim, base.dt
+        self.gamma, self.ctrl_interval, self.num_pred_step = gamma, ctrl_interval, num_pred_step
+        self.num_ctrl_points = num_pred_step // ctrl_interval
+        self.n = self.num_ctrl_points * self.action_dim
+        self.max_iter, self.check_every, self.history = int(max_iter), int(check_every), int(history)
+        self.hyper = dict(pgtol=float(pgtol), ftol=float(ftol))
+        # the RAW model, exactly as OptController describes it
+        env = hb.make_env(base.hip_kind, base.obs_dim, base.action_dim, act_low=base.action_lower_bound.cpu(),
+                          act_high=base.action_upper_bound.cpu(), min_action=base.action_lower_bound.cpu(),
+                          max_action=base.action_upper_bound.cpu(), pre_horizon=getattr(base, "pre_horizon", 0),
+                          **base.hip_constants())
+        env.no_mask_at_done = 1
+        if getattr(base, "get_constraint", None) is not None and hb.has_constraints(env):
+            raise NotImplementedError(f"BatchOptController: {type(base).__name__} has path constraints (get_constraint); the batched "
+                                      "solver handles box constraints only - use OptController(mode='shooting') for it")
+        if not 1 <= self.n <= hb.MPC_MAX_DIM:
+            raise NotImplementedError(f"BatchOptController: {self.n} decision variables per state; the device solver takes 1 .. {hb.MPC_MAX_DIM}")
+        self._env = env
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self._lo = base.action_lower_bound.cpu().to(torch.float32).repeat(self.num_ctrl_points)
+        self._hi = base.action_upper_bound.cpu().to(torch.float32).repeat(self.num_ctrl_points)
+        self._per_batch: Dict[int, Dict] = {}
+        self._terminal_vmap = True
+        self._guess: Optional[torch.Tensor] = None
+        self.last_result: Optional[Dict] = None
+
+    def reset(self):
+        """Forget the warm start: the next call starts every row from zero actions."""
+        self._guess = None
+
+    def _objects(self, B: int) -> Dict:
+        o = self._per_batch.get(B)
+        if o is None:
+            T, A, dev = self.num_pred_step, self.action_dim, self.device
+            o = dict(rollout=hb.Rollout(self._env, None, batch=B, horizon=T, gamma=self.gamma, finite_horizon=False, need_grad=True,
+                                        device=dev, raw_actions=True),
+                     solver=hb.MpcSolver(B, self.n, self._lo, self._hi, dev, history=self.history),
+                     actions=torch.zeros(B, T, A, dtype=torch.float32, device=dev),
+                     minus_one=torch.full((B,), -1.0, dtype=torch.float32, device=dev),
+                     done=torch.zeros(B, dtype=torch.float32, device=dev))
+            if self.base.hip_kind == hb.ENV_MOBILEROBOT:   # a deterministic cost: the obstacle follows its expected motion
+                o["noise"] = torch.zeros(T, B, 2, dtype=torch.float32, device=dev)
+            o["solver"].set_hyper(**self.hyper)
+            self._per_batch[B] = o
+        return o
+
+    def _data(self, o: Dict, x, info: Optional[Dict]) -> Dict:
+        as_dev = lambda v: torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v, dtype=torch.float32, device=self.device).contiguous()
+        data = {"obs": as_dev(x), "done": o["done"]}
+        if "noise" in o:
+            data["noise"] = o["noise"]
+        for k in _INFO:
+            if info and k in info:
+                data[k] = as_dev(info[k])
+        return data
+
+    def _terminal(self, final_obs: torch.Tensor):
+        """(gamma^T terminal_cost(state_T) [B], its gradient [B, obs_dim]) with autograd on the device.  The function is written for
+        ONE state (opt_controller.py:312-317; pyth_lq's x'Px): it is mapped over the rows with torch.func.vmap - one host call per
+        cost evaluation whatever B is - and only a function vmap cannot trace (data-dependent branches, .item()) is called row by
+        row, B host calls per evaluation."""
+        xT = final_obs.detach().clone().requires_grad_(True)
+        if self._terminal_vmap:
+            try:
+                tc = torch.func.vmap(self.terminal_cost)(xT)
+            except Exception:   # not traceable: the same values, row by row
+                self._terminal_vmap = False
+        if not self._terminal_vmap:
+            tc = torch.stack([self.terminal_cost(xT[b]) for b in range(xT.shape[0])])
+        tc = tc.reshape(-1) * (self.gamma ** self.num_pred_step)
+        (g,) = torch.autograd.grad(tc.sum(), xT)
+        return tc.detach().to(torch.float32), g.to(torch.float32).contiguous()
+
+    def _evaluate(self, o: Dict, data: Dict):
+        """Cost and gradient of every row at the solver's trial point, left in solver.f / solver.g."""
+        B, n_cp, ci, A = o["actions"].shape[0], self.num_ctrl_points, self.ctrl_interval, self.action_dim
+        solver, ro = o["solver"], o["rollout"]
+        o["actions"].view(B, n_cp, ci, A).copy_(solver.x_trial.view(B, n_cp, 1, A).expand(B, n_cp, ci, A))   # held over each interval
+        res = ro.forward(data, head_pre=o["actions"], want_final=self.terminal_cost is not None)
+        torch.neg(res["v_pi"], out=solver.f)
+        if self.terminal_cost is not None:
+            tc, gfo = self._terminal(res["final_obs"])
+            solver.f.add_(tc)
+            g, _ = ro.backward_open_loop_adj(o["minus_one"], grad_final_obs=gfo)
+        else:
+            g = ro.backward_open_loop(o["minus_one"])
+        g = g.view(B, n_cp, ci, A)
+        out = solver.g.view(B, n_cp, A)
+        out.copy_(g[:, :, 0])
+        for k in range(1, ci):   # the fold, one interval step at a time: element-wise, so a row's bits do not depend on B
+            out.add_(g[:, :, k])
+
+    def solve(self, x, info: Optional[Dict] = None) -> Dict:
+        """-> dict(action [B, act_dim], plan [B, num_ctrl_points, act_dim], cost [B], status [B] (hb.MPC_*), iterations [B],
+        evaluations: cost evaluations made) for the states x [B, obs_dim]; tensors on the device."""
+        x = np.asarray(x) if not torch.is_tensor(x) else x
+        assert x.ndim == 2 and x.shape[1] == self.obs_dim, "x: [B, obs_dim]"
+        B = int(x.shape[0])
+        o = self._objects(B)
+        solver = o["solver"]
+        data = self._data(o, x, info)
+        guess = self._guess if self._guess is not None and self._guess.shape[0] == B else torch.zeros(B, self.n, dtype=torch.float32,
+                                                                                                      device=self.device)
+        solver.init(guess)
+        evals = 0
+        while evals < self.max_iter:
+            for _ in range(min(self.check_every, self.max_iter - evals)):
+                self._evaluate(o, data)
+                solver.step()
+                evals += 1
+            plan, cost, status, iterations = solver.finish()
+            if not bool((status == hb.MPC_RUNNING).any().item()):   # the one synchronisation per check_every iterations
+                break
+        plan, cost, status, iterations = (t.clone() for t in solver.finish())
+        A = self.action_dim
+        self._guess = torch.cat((plan[:, A:], plan[:, -A:]), 1).contiguous()   # drop the first control point, repeat the last
+        plan = plan.view(B, self.num_ctrl_points, A)
+        self.last_result = dict(action=plan[:, 0].clone(), plan=plan, cost=cost, status=status, iterations=iterations, evaluations=evals)
+        return self.last_result
+
+    def __call__(self, x, info: Optional[Dict] = None) -> torch.Tensor:
+        """The first optimal action of every row [B, act_dim]."""
+        return self.solve(x, info)["action"]

@@ -1062,6 +1062,62 @@ enum { GOPS_DW_NONE = 0, GOPS_DW_SPEC = 1, GOPS_DW_RING_H2 = 2, GOPS_DW_RING_EXA
 int gops_dw_plan_query(int32_t N, int32_t K, int32_t Kp, int64_t S, int32_t f16, int32_t scaled, uint32_t vflags,
                        int32_t dw_workgroups, int32_t out[4]);
 
+/* ABI v15, additive entry points (the version number stays 15): batched shooting MPC - `batch` independent box-constrained problems
+ * min f_b(x), lo <= x <= hi, of n = control points x act_dim variables each, solved side by side by a limited-memory BFGS with history
+ * m whose every scalar lives in ONE device state block, so that the host reads nothing between two cost evaluations
+ * (csrc/mpc_lbfgs.hip).  The caller evaluates cost and gradient of all rows at x_trial (one open-loop rollout forward and backward)
+ * and hands them to gops_mpc_step, which writes the next x_trial.
+ *
+ * State block, gops_mpc_state_bytes(batch, n, m) bytes (0 for arguments the entry points refuse), 8-byte aligned:
+ *     double  [batch][GOPS_MPC_SCALARS + m]    f, f_prev, alpha, dphi, gamma, rho[m]
+ *     int32_t [batch][GOPS_MPC_COUNTERS]       status (GOPS_MPC_*), iterations, evaluations, line-search count, ring head, ring count
+ *     float   lo [n'], hi [n']                 n' = n rounded up to even
+ *     float   [batch][GOPS_MPC_VECTORS + 2 m][n]   x, g (accepted), x_prev, g_prev, d, x_trial, s[m], y[m]
+ *   a problem's vectors are consecutive rows of n floats: the lanes that work on it read contiguous memory.
+ * gops_mpc_init: x = x_trial = clamp(x0, lo, hi) (also written to the x_trial argument), everything else of the block cleared
+ *   (gamma = 1), every status GOPS_MPC_RUNNING; lo, hi are copied into the block.
+ * gops_mpc_step: f [batch], g [batch, n] = cost and gradient at the x_trial the previous call (or gops_mpc_init) wrote.  For every
+ *   row whose status is GOPS_MPC_RUNNING (the others are left untouched, their x_trial row rewritten as their accepted x):
+ *     evaluations += 1.  f or any g not finite: status = GOPS_MPC_NONFINITE.
+ *     First call after init: the point is accepted without a test and without a pair.  Otherwise the Armijo test
+ *         f <= f_acc + c1 dphi,   dphi = g_acc . (x_trial - x) the directional derivative along the PROJECTED step.
+ *     Fails: line-search count += 1; when it reaches max_ls: status = GOPS_MPC_LINE_SEARCH; else alpha *= shrink,
+ *         x_trial = clamp(x + alpha d), dphi again.
+ *     Holds: s = x_trial - x, y = g - g_acc (rounded to float); the pair enters the ring (rho = 1 / s.y, gamma = s.y / y.y) unless
+ *         s.y <= curv_eps y.y (the curvature test of scipy's L-BFGS-B).  x_prev, g_prev, f_prev <- the accepted point; the trial point
+ *         becomes the accepted one; iterations += 1, line-search count = 0.
+ *         max |x - clamp(x - g)| <= pgtol: status = GOPS_MPC_CONVERGED_PG;
+ *         else f_prev - f <= ftol max(|f_prev|, |f|, 1): status = GOPS_MPC_CONVERGED_F    (not on the first call).
+ *         Still running: d = - H g by the two-loop recursion over the ring on the FREE variables (free: not on a bound with
+ *         the gradient pointing outward; fixed variables get d = 0; initial matrix gamma I; rho of the unrestricted pairs);
+ *         with an empty ring d = - g on the free variables and alpha = min(1, 1 / |d|), else alpha = 1;
+ *         x_trial = clamp(x + alpha d).
+ *     Whenever a trial point is formed with dphi >= 0 and a non-empty ring, the ring is dropped (count = 0) and the trial point
+ *     is formed again along the projected steepest descent as above.
+ *   hyper: DEVICE memory, GOPS_MPC_HYPER_FLOATS floats read by the kernel - {c1, shrink, max_ls, pgtol, ftol, curv_eps, 0, 0} - so a
+ *   change of tolerances does not invalidate a captured graph.
+ * gops_mpc_finish: x [batch, n], f [batch], status [batch], iterations [batch] <- the accepted point of every row.
+ * One launch per call.  A sub-group of W lanes owns a problem: W = 64 for n > 64, else the smallest of 4, 8, 16, 32 with 2 W >= n.
+ * Every dot product is a fixed-order sum in double (own elements in index order, then an xor butterfly), there are no atomics and
+ * every stored value is rounded once: a repeated call gives the same bits, and a row's bits depend neither on batch nor on its index.
+ * GOPS_ERR_BAD_ARG: a NULL pointer, batch < 1, n < 1, m < 1, m > GOPS_MPC_MAX_HISTORY, a state block that is not 8-byte aligned;
+ * then GOPS_ERR_UNSUPPORTED: n > GOPS_MPC_MAX_DIM; then GOPS_ERR_WORKSPACE: state_bytes < gops_mpc_state_bytes(batch, n, m) - all
+ * before any HIP call. */
+#define GOPS_MPC_MAX_DIM 256
+#define GOPS_MPC_MAX_HISTORY 8
+#define GOPS_MPC_HYPER_FLOATS 8
+#define GOPS_MPC_SCALARS 5
+#define GOPS_MPC_COUNTERS 8
+#define GOPS_MPC_VECTORS 6
+enum { GOPS_MPC_RUNNING = 0, GOPS_MPC_CONVERGED_PG = 1, GOPS_MPC_CONVERGED_F = 2, GOPS_MPC_LINE_SEARCH = 3, GOPS_MPC_NONFINITE = 4 };
+size_t gops_mpc_state_bytes(int32_t batch, int32_t n, int32_t m);
+int gops_mpc_init(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, const float* x0, const float* lo, const float* hi,
+                  float* x_trial, void* stream);
+int gops_mpc_step(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, const float* f, const float* g, float* x_trial,
+                  const float* hyper, void* stream);
+int gops_mpc_finish(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, float* x, float* f, int32_t* status,
+                    int32_t* iterations, void* stream);
+
 /* Timing hook for bench.py: average duration in ms of the named internal kernel over the
  * launches recorded since the last reset (HIP events on the launch stream).  kernel ids:
  * 0 = forward rollout, 1 = backward sweep, 2 = weight-gradient GEMMs (+ reduce) of gops_rollout_*;
