@@ -146,7 +146,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     const GopsEnv& e = desc.env;
     if (desc.batch < 1 || desc.horizon < 1 || desc.horizon > GOPS_MAX_HORIZON) return GOPS_ERR_BAD_ARG;
     if (desc.variant_flags & ~GOPS_VF_ALL) return GOPS_ERR_BAD_ARG;   // a retired or unknown bit is refused, not ignored (ABI v14)
-    if (e.kind < GOPS_ENV_NONE || e.kind > GOPS_ENV_MOBILEROBOT) return GOPS_ERR_BAD_ARG;
+    if (e.kind < GOPS_ENV_NONE || e.kind > GOPS_ENV_MOUNTAINCAR) return GOPS_ERR_BAD_ARG;
     if (e.obs_dim < 1 || e.data_env) return GOPS_ERR_BAD_ARG;   // data-env semantics exist for gops_env_step only
     const int pol_out = (e.kind == GOPS_ENV_NONE) ? 1 : e.act_dim;
     if (desc.dtype != GOPS_DTYPE_F32 && desc.dtype != GOPS_DTYPE_F16) return GOPS_ERR_BAD_ARG;
@@ -162,6 +162,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     if (e.scale_obs && e.kind != GOPS_ENV_LQ && e.kind != GOPS_ENV_IDPENDULUM && e.kind < GOPS_ENV_CARTPOLE) return GOPS_ERR_UNSUPPORTED;   // obs_dim <= 8 only
     if (e.kind == GOPS_ENV_CARTPOLE && (e.obs_dim != 4 || e.act_dim != 1)) return GOPS_ERR_BAD_ARG;
     if (e.kind == GOPS_ENV_PENDULUM && (e.obs_dim != 3 || e.act_dim != 1)) return GOPS_ERR_BAD_ARG;
+    if (e.kind == GOPS_ENV_MOUNTAINCAR && mcar_check_env(e) != GOPS_OK) return GOPS_ERR_BAD_ARG;
     if (e.kind == GOPS_ENV_VEH2DOF && (e.act_dim != 1 || e.pre_horizon < 1 || e.obs_dim != 4 + e.pre_horizon || e.clip_obs ||
                                         (e.cstr_err && e.n_constraint != 1))) return GOPS_ERR_BAD_ARG;
     if (e.kind == GOPS_ENV_MOBILEROBOT && (e.obs_dim != MOB_OBS || e.act_dim != 2 || e.n_constraint != 1 || e.scale_obs)) return GOPS_ERR_BAD_ARG;
@@ -181,7 +182,7 @@ int build_plan(const GopsRolloutDesc& desc, void* ws, Plan& plan) {
     if (e.clip_obs && e.obs_dim > (e.kind == GOPS_ENV_MOBILEROBOT ? GOPS_MAX_CLIP_OBS : 8)) return GOPS_ERR_UNSUPPORTED;
     if (e.repeat_num < 0 || e.repeat_num > GOPS_MAX_REPEAT) return GOPS_ERR_BAD_ARG;
     if (e.repeat_num > 1 && (f16 || (e.kind != GOPS_ENV_LQ && e.kind != GOPS_ENV_IDPENDULUM && e.kind != GOPS_ENV_CARTPOLE &&
-                                     e.kind != GOPS_ENV_PENDULUM)))
+                                     e.kind != GOPS_ENV_PENDULUM && e.kind != GOPS_ENV_MOUNTAINCAR)))
         return GOPS_ERR_UNSUPPORTED;   // ActionRepeatModel: obs == state models, fp32
 
     p.B = desc.batch;

@@ -155,10 +155,11 @@ int gops_env_constraint(const GopsEnv* env, int32_t B, const GopsStepIO* io, voi
 
 int gops_env_step(const GopsEnv* env, int32_t B, const GopsStepIO* io, void* stream) {
     if (!env || !io || B < 1) return GOPS_ERR_BAD_ARG;
-    if (env->kind < GOPS_ENV_LQ || env->kind > GOPS_ENV_MOBILEROBOT) return GOPS_ERR_BAD_ARG;
+    if (env->kind < GOPS_ENV_LQ || env->kind > GOPS_ENV_MOUNTAINCAR) return GOPS_ERR_BAD_ARG;
     if (env->kind == GOPS_ENV_MOBILEROBOT &&
         (env->obs_dim != MOB_OBS || env->act_dim != 2 || env->n_constraint != 1 || env->scale_obs || !io->constraint)) return GOPS_ERR_BAD_ARG;
-    if (env->data_env && (env->kind == GOPS_ENV_PENDULUM || (env->kind == GOPS_ENV_VEH2DOF && env->cstr_err)))
+    if (env->kind == GOPS_ENV_MOUNTAINCAR && mcar_check_env(*env) != GOPS_OK) return GOPS_ERR_BAD_ARG;
+    if (env->data_env && (env->kind == GOPS_ENV_PENDULUM || env->kind == GOPS_ENV_MOUNTAINCAR || (env->kind == GOPS_ENV_VEH2DOF && env->cstr_err)))
         return GOPS_ERR_UNSUPPORTED;   // these data envs are not restated
     if (!io->obs || !io->action || !io->next_obs || !io->reward || !io->next_done) return GOPS_ERR_BAD_ARG;
     if (env->kind == GOPS_ENV_VEH3DOF_SURR &&
@@ -172,7 +173,8 @@ int gops_env_step(const GopsEnv* env, int32_t B, const GopsStepIO* io, void* str
     if (env->scale_obs && env->kind != GOPS_ENV_LQ && env->kind != GOPS_ENV_IDPENDULUM && env->kind < GOPS_ENV_CARTPOLE) return GOPS_ERR_UNSUPPORTED;
     if (env->repeat_num < 0 || env->repeat_num > GOPS_MAX_REPEAT) return GOPS_ERR_BAD_ARG;
     if (env->repeat_num > 1 && (env->data_env || (env->kind != GOPS_ENV_LQ && env->kind != GOPS_ENV_IDPENDULUM &&
-                                                  env->kind != GOPS_ENV_CARTPOLE && env->kind != GOPS_ENV_PENDULUM)))
+                                                  env->kind != GOPS_ENV_CARTPOLE && env->kind != GOPS_ENV_PENDULUM &&
+                                                  env->kind != GOPS_ENV_MOUNTAINCAR)))
         return GOPS_ERR_UNSUPPORTED;
     GopsEnv e = *env;   // the library's own copy: reference constants filled, LQ matrices padded
     fill_ref_defaults(e);

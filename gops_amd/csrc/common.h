@@ -235,6 +235,14 @@ __device__ __forceinline__ void adam_snapshot(GopsAdamState* st, float* snap, do
 // such update would write NaN into every weight and target before the host - which reads losses lazily - could react.
 __device__ __forceinline__ bool grad_is_finite(float g) { return (__float_as_uint(g) & 0x7f800000u) != 0x7f800000u; }
 
+// Host side: a gym_mountaincarconti description is (2, 1) wide and carries a non-empty action range - ScaleAction divides by
+// max_action - min_action, and a NaN action would decide every branch of the step (GOPS_ERR_BAD_ARG otherwise; NaN bounds fail too)
+inline int mcar_check_env(const GopsEnv& e) {
+    if (e.obs_dim != 2 || e.act_dim != 1) return GOPS_ERR_BAD_ARG;
+    if (!(e.min_action[0] < e.max_action[0]) || !(e.act_low[0] <= e.act_high[0])) return GOPS_ERR_BAD_ARG;
+    return GOPS_OK;
+}
+
 // One rounding per operation, never fused: HIP's __fmul_rn / __fadd_rn are plain `a * b` / `a + b`, which hipcc's default
 // -ffp-contract=fast-honor-pragmas may contract into an fma with a neighbour - whether it did depended on unrelated codegen
 // (round 4: building without packed-fp32 instructions moved 4 more of the 48 appended headings of the step fixture by ~1e-3).
@@ -251,6 +259,10 @@ __device__ __forceinline__ float rn_sub(float a, float b) {
 #pragma clang fp contract(off)
     return a - b;
 }
+// Transcendentals evaluated in double and rounded once, i.e. correctly rounded in fp32: the CPU reference (Sleef u10) is correctly
+// rounded for almost every argument (env_step.h: the reference trajectories; env_models.h: gym_mountaincarconti)
+#define SINF_CR(x) ((float)sin((double)(x)))
+#define COSF_CR(x) ((float)cos((double)(x)))
 
 // One element's Adam step: the fused tail of reduce_partials_kernel (dw_gemm.hip) calls it, adam_kernel (optim.hip) restates it (the
 // call costs that kernel two registers and a wave of occupancy); the tests hold the two bit-equal.  gi = the scaled, finite gradient (the callers gate and count the others); step_size, bc2_sqrt =

@@ -143,6 +143,45 @@ __device__ __forceinline__ void pend_backward(const float* x, float a, const flo
     ga = g_raw * (3.f * 0.05f) + gr * (-0.002f * a);
 }
 
+// ================================ gym_mountaincarconti ========================================
+// gops/env/env_gym/env_model/gym_mountaincarconti_model.py:21-99: state = obs = (pos, vel), no dt.
+//   vel' = clamp(vel + 0.0015 a - 0.0025 cos(3 pos), +-0.07);  pos' = clamp(pos + vel', -1.2, 0.6);
+//   vel' = 0 where pos' == -1.2 and vel' < 0 (the wall, AFTER pos' was formed);  done = pos' >= 0.45 and vel' >= 0 on the NEXT
+//   state;  reward = 100 done - 0.1 a^2 (the indicator has no gradient).
+// Every product and sum rounds on its own, in the reference's order (torch CPU fuses nothing), and the cosine is correctly rounded:
+// the clamps, the wall rule (an EXACT compare of a clamped value) and the done test hang on these values.  The adjoint recomputes
+// this very forward, so both take the same branches.  Clamp derivatives as torch.clamp: 1 on the closed interval.
+struct McarStep { float v_raw, v_cl, p_raw; bool wall; };
+__device__ __forceinline__ void mcar_forward(const float* x, float a, float* xn, float& r, bool& done, McarStep& w) {
+    w.v_raw = rn_sub(rn_add(x[1], rn_mul(0.0015f, a)), rn_mul(0.0025f, COSF_CR(rn_mul(3.f, x[0]))));
+    w.v_cl = clampf(w.v_raw, -0.07f, 0.07f);
+    w.p_raw = rn_add(x[0], w.v_cl);
+    xn[0] = clampf(w.p_raw, -1.2f, 0.6f);
+    w.wall = (xn[0] == -1.2f) && (w.v_cl < 0.f);
+    xn[1] = w.wall ? 0.f : w.v_cl;
+    done = (xn[0] >= 0.45f) && (xn[1] >= 0.f);
+    r = rn_sub(done ? 100.f : 0.f, rn_mul(0.1f, rn_mul(a, a)));
+}
+// adjoints: gxn (adjoint of x'), gr (adjoint of r) -> gx (accumulated), ga (overwritten).  The wall cuts the path into the returned
+// vel' only: pos' was formed from the unzeroed value.
+__device__ __forceinline__ void mcar_backward(const float* x, float a, const float* gxn, float gr, float* gx, float& ga) {
+    float xn[2], r;
+    bool done;
+    McarStep w;
+    mcar_forward(x, a, xn, r, done, w);
+    const float g_p = (w.p_raw >= -1.2f && w.p_raw <= 0.6f) ? gxn[0] : 0.f;
+    const float g_vcl = g_p + (w.wall ? 0.f : gxn[1]);
+    const float g_raw = (w.v_raw >= -0.07f && w.v_raw <= 0.07f) ? g_vcl : 0.f;
+    gx[0] += g_p + g_raw * (0.0075f * SINF_CR(rn_mul(3.f, x[0])));
+    gx[1] += g_raw;
+    ga = g_raw * 0.0015f + gr * (-0.2f * a);
+}
+// width of the gym-style models' state (their action is one number)
+__host__ __device__ constexpr int gym_state_dim(int env) { return env == GOPS_ENV_CARTPOLE ? 4 : (env == GOPS_ENV_PENDULUM ? 3 : 2); }
+__host__ __device__ constexpr bool is_gym_kind(int env) {
+    return env == GOPS_ENV_CARTPOLE || env == GOPS_ENV_PENDULUM || env == GOPS_ENV_MOUNTAINCAR;
+}
+
 // ================================ pyth_idpendulum =============================================
 struct IdpConst {   // products of the Python-double constants, rounded once like torch does
     float a, b, e, f, h, k, gb, ge, l1, l2;
@@ -276,7 +315,7 @@ __device__ __forceinline__ bool idp_done_trig(const IdpConst& C, const float* s,
 }
 
 // ================================ the models whose observation is the state, register form ====
-// pyth_lq, gym_cartpoleconti, gym_pendulum, pyth_idpendulum for ONE trajectory held in registers: the single statement of the
+// pyth_lq, gym_cartpoleconti, gym_pendulum, gym_mountaincarconti, pyth_idpendulum for ONE trajectory held in registers: the single statement of the
 // arithmetic that env_step_kernel, the episode kernel (env_step.h), the lane rollouts (lane_rollout.h) and the tile-form env
 // phases of rollout_fwd.hip / rollout_bwd.hip / rollout_h64.hip (rollout_env.h) step.
 // State arrays of every model here have GOPS_MAX_LQ_STATE entries (lq_forward's padded width); entries beyond the model's are zero.
@@ -293,6 +332,9 @@ __device__ __forceinline__ void state_model_substep(const GopsEnv& env, const fl
     } else if constexpr (ENV == GOPS_ENV_PENDULUM) {
         PendStep w;
         pend_forward(xi, u[0], xo, r, w);
+    } else if constexpr (ENV == GOPS_ENV_MOUNTAINCAR) {
+        McarStep w;
+        mcar_forward(xi, u[0], xo, r, done_m, w);
     } else {   // five Euler sub-steps: one sincosf pair, then rotations
         static_assert(ENV == GOPS_ENV_IDPENDULUM, "env kind");
         const IdpConst IC = idp_const();
@@ -313,7 +355,7 @@ __device__ __forceinline__ void state_model_substep(const GopsEnv& env, const fl
     }
 }
 
-// adjoint of the single-step models (pyth_lq, gym_cartpoleconti, gym_pendulum) at the input state xi: gn adjoint of xo, gr adjoint
+// adjoint of the single-step models (pyth_lq, gym_cartpoleconti, gym_pendulum, gym_mountaincarconti) at the input state xi: gn adjoint of xo, gr adjoint
 // of r -> gx ACCUMULATED (it carries what the caller put there), gu: the entries the model has are overwritten
 template <int ENV, int N = GOPS_MAX_LQ_STATE, int M = GOPS_MAX_ACT>
 __device__ __forceinline__ void state_model_backward(const GopsEnv& env, const float* xi, const float (&u)[GOPS_MAX_ACT],
@@ -322,6 +364,8 @@ __device__ __forceinline__ void state_model_backward(const GopsEnv& env, const f
         lq_backward<N, M>(env, xi, u, gn, gr, gx, gu);
     } else if constexpr (ENV == GOPS_ENV_CARTPOLE) {
         cart_backward(cart_const(), xi, u[0], gn, gx, gu[0]);
+    } else if constexpr (ENV == GOPS_ENV_MOUNTAINCAR) {
+        mcar_backward(xi, u[0], gn, gr, gx, gu[0]);
     } else {
         static_assert(ENV == GOPS_ENV_PENDULUM, "env kind");
         pend_backward(xi, u[0], gn, gr, gx, gu[0]);
@@ -416,7 +460,7 @@ __device__ __forceinline__ void state_model_step(const GopsEnv& env, const float
 // below and the kernel dispatch of the one-lane-per-trajectory rollouts (lane_rollout.h).
 #define STATE_MODEL_CASES(X)                                                                                              \
     X(GOPS_ENV_LQ, 1) X(GOPS_ENV_LQ, 2) X(GOPS_ENV_LQ, 3) X(GOPS_ENV_LQ, 4) X(GOPS_ENV_LQ, 5) X(GOPS_ENV_LQ, 6) \
-    X(GOPS_ENV_IDPENDULUM, 6) X(GOPS_ENV_CARTPOLE, 4) X(GOPS_ENV_PENDULUM, 3)
+    X(GOPS_ENV_IDPENDULUM, 6) X(GOPS_ENV_CARTPOLE, 4) X(GOPS_ENV_PENDULUM, 3) X(GOPS_ENV_MOUNTAINCAR, 2)
 
 // Host side: what the one-lane-per-trajectory rollouts (lane_rollout.h) ask of a description before they look at its policy:
 // shape, fp32, closed loop, no kernel variants, a model env whose observation is the state, the bounds of
@@ -431,6 +475,7 @@ inline int state_model_check_desc(const GopsRolloutDesc& d) {
     STATE_MODEL_CASES(STATE_MODEL_LISTED)
 #undef STATE_MODEL_LISTED
     if (!listed) return GOPS_ERR_UNSUPPORTED;
+    if (e.kind == GOPS_ENV_MOUNTAINCAR && mcar_check_env(e) != GOPS_OK) return GOPS_ERR_BAD_ARG;
     if (e.data_env || e.act_dim < 1 || e.act_dim > GOPS_MAX_ACT) return GOPS_ERR_UNSUPPORTED;
     if ((e.kind != GOPS_ENV_LQ && e.act_dim != 1) || e.repeat_num > GOPS_MAX_REPEAT) return GOPS_ERR_UNSUPPORTED;
     return GOPS_OK;

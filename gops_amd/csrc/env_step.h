@@ -11,11 +11,9 @@
 // rounded separately in fp32, in the reference's order (no FMA contraction): the heading is a
 // 1 ms finite difference whose cancellation noise is part of the reference's result.
 // ---------------------------------------------------------------------------------------------
-// Transcendentals are evaluated in double and rounded once, i.e. correctly rounded in fp32: the CPU
+// Transcendentals are evaluated in double and rounded once (common.h SINF_CR / COSF_CR), i.e. correctly rounded in fp32: the CPU
 // reference (Sleef u10) is correctly rounded for almost every argument, so this minimises the
 // number of points where a 1-ulp difference in x(t) is amplified ~1e3x by the finite difference.
-#define SINF_CR(x) ((float)sin((double)(x)))
-#define COSF_CR(x) ((float)cos((double)(x)))
 // One rounding per operation, never fused (common.h rn_mul / rn_add / rn_sub)
 #define RMUL(a, b) rn_mul((a), (b))
 #define RADD(a, b) rn_add((a), (b))
@@ -131,6 +129,8 @@ __device__ __forceinline__ void env_step_one(const GopsEnv& env, int b, const Go
         env_step_state_model<GOPS_ENV_CARTPOLE, 4>(env, data, dn, ob, u, nob, r, done_m);
     } else if (env.kind == GOPS_ENV_PENDULUM) {
         env_step_state_model<GOPS_ENV_PENDULUM, 3>(env, data, dn, ob, u, nob, r, done_m);
+    } else if (env.kind == GOPS_ENV_MOUNTAINCAR) {
+        env_step_state_model<GOPS_ENV_MOUNTAINCAR, 2>(env, data, dn, ob, u, nob, r, done_m);
     } else if (env.kind == GOPS_ENV_IDPENDULUM) {
         env_step_state_model<GOPS_ENV_IDPENDULUM, 6>(env, data, dn, ob, u, nob, r, done_m);
     } else if (env.kind == GOPS_ENV_MOBILEROBOT) {

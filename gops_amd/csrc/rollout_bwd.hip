@@ -472,7 +472,7 @@ struct NoSweep {};
 // Env kinds whose streamed-split sweep has the registers for it (the vehicle / idpendulum instantiations would spill): those
 // instantiations also walk their tiles grid-stride (one partial slab per workgroup).
 __host__ __device__ constexpr bool ssb_fuse_kind(int env) {
-    return env == GOPS_ENV_LQ || env == GOPS_ENV_CARTPOLE || env == GOPS_ENV_PENDULUM || env == GOPS_ENV_MOBILEROBOT;
+    return env == GOPS_ENV_LQ || is_gym_kind(env) || env == GOPS_ENV_MOBILEROBOT;
 }
 // Output-layer weight gradient accumulated inside the streamed-split sweep (as SplitSweep does): lane (f = lane & 15,
 // g = lane >> 4) of wave w holds dW_o[a][64 w + 16 q + f] over the rows 4g .. 4g+3 of every tile and step the workgroup walked.
@@ -970,7 +970,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 if (O == 4 && A == 2) lq_adjoint.template operator()<4, 2>();
                 else lq_adjoint.template operator()<GOPS_MAX_LQ_STATE, GOPS_MAX_ACT>();
             }
-        } else if constexpr (ENV == GOPS_ENV_LQ || ENV == GOPS_ENV_IDPENDULUM || ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {
+        } else if constexpr (ENV == GOPS_ENV_LQ || ENV == GOPS_ENV_IDPENDULUM || is_gym_kind(ENV)) {
             if (tid < TB) {
                 const int m = tid;
                 float th[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f}, dflag = 1.f;
@@ -1075,7 +1075,7 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SSB ? 2 : ((SK0 == 0 && SK1 ==
                 }
                 if constexpr (ENV != GOPS_ENV_IDPENDULUM) {
                     if (!repeated)
-                        obs_state_adjoint<ENV, (ENV == GOPS_ENV_LQ) ? GOPS_MAX_LQ_STATE : ((ENV == GOPS_ENV_CARTPOLE) ? 4 : 3), (ENV == GOPS_ENV_LQ) ? GOPS_MAX_ACT : 1>(
+                        obs_state_adjoint<ENV, (ENV == GOPS_ENV_LQ) ? GOPS_MAX_LQ_STATE : gym_state_dim(ENV), (ENV == GOPS_ENV_LQ) ? GOPS_MAX_ACT : 1>(
                             p.env, O, x, u, dn, g_rm, Gin, gx, gu);
                 } else if (!repeated) {
                     // Recompute the 5 Euler sub-steps once, parking each sub-step's input state and

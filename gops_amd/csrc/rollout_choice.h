@@ -31,7 +31,7 @@ struct Inst {
 };
 
 inline constexpr Inst kEveryEnv[] = {{GOPS_ENV_NONE}, {GOPS_ENV_LQ}, {GOPS_ENV_IDPENDULUM}, {GOPS_ENV_VEH3DOFCONTI}, {GOPS_ENV_VEH3DOF_SURR},
-                                     {GOPS_ENV_CARTPOLE}, {GOPS_ENV_PENDULUM}, {GOPS_ENV_VEH2DOF}, {GOPS_ENV_MOBILEROBOT}};
+                                     {GOPS_ENV_CARTPOLE}, {GOPS_ENV_PENDULUM}, {GOPS_ENV_VEH2DOF}, {GOPS_ENV_MOBILEROBOT}, {GOPS_ENV_MOUNTAINCAR}};
 inline constexpr auto& kPlain = kEveryEnv;           // forward and sweep, Plain and PlainN64
 inline constexpr auto& kStreamedSplit = kEveryEnv;   // forward and sweep
 inline constexpr Inst kHalf64[] = {{GOPS_ENV_NONE, 0, 0, false}, {GOPS_ENV_LQ}};
@@ -41,9 +41,10 @@ inline constexpr Inst kHalf16[] = {{GOPS_ENV_NONE}, {GOPS_ENV_LQ}, {GOPS_ENV_IDP
 inline constexpr Inst kSplit[] = {{GOPS_ENV_LQ, 1},           {GOPS_ENV_IDPENDULUM, 1},      {GOPS_ENV_VEH3DOFCONTI, 2},
                                   {GOPS_ENV_VEH3DOFCONTI, 3}, {GOPS_ENV_VEH3DOFCONTI, 4},    {GOPS_ENV_VEH3DOFCONTI, 5, 0, false},
                                   {GOPS_ENV_VEH3DOFCONTI, 6, 0, false}, {GOPS_ENV_VEH3DOFCONTI, 7, 0, false}, {GOPS_ENV_VEH3DOFCONTI, 8, 0, false}};
-inline constexpr Inst kGenFwd[] = {{GOPS_ENV_LQ}, {GOPS_ENV_IDPENDULUM}, {GOPS_ENV_CARTPOLE}, {GOPS_ENV_PENDULUM}};   // obs == state models
+inline constexpr Inst kGenFwd[] = {{GOPS_ENV_LQ}, {GOPS_ENV_IDPENDULUM}, {GOPS_ENV_CARTPOLE}, {GOPS_ENV_PENDULUM},
+                                   {GOPS_ENV_MOUNTAINCAR}};   // obs == state models
 inline constexpr Inst kExtBwd[] = {{GOPS_ENV_NONE, 0, 0, false}, {GOPS_ENV_LQ}, {GOPS_ENV_IDPENDULUM}, {GOPS_ENV_CARTPOLE}, {GOPS_ENV_PENDULUM},
-                                   {GOPS_ENV_MOBILEROBOT}};
+                                   {GOPS_ENV_MOBILEROBOT}, {GOPS_ENV_MOUNTAINCAR}};
 // veh3dofconti forward: 3 chunks of 16 inputs (P = 10) fully stationary; from 6 chunks up the first 6 stay in registers and
 // the rest streams (P = 30: 6 + 2, P = 50: 6 + 7); else layer 0 streams
 inline constexpr Inst kStationaryFwd[] = {{GOPS_ENV_LQ, 1, 16}, {GOPS_ENV_IDPENDULUM, 1, 16}, {GOPS_ENV_VEH3DOFCONTI, 6, 16},

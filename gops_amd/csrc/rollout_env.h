@@ -30,7 +30,8 @@ __device__ __forceinline__ float head_unsquash_bwd(const ActC& c, float abar, fl
 }
 
 // ================================ models whose observation is the state ========================
-// pyth_lq (NS, NA: compile-time loop bounds, (4, 2) or the maxima), gym_cartpoleconti (4, 1), gym_pendulum (3, 1).
+// pyth_lq (NS, NA: compile-time loop bounds, (4, 2) or the maxima), gym_cartpoleconti (4, 1), gym_pendulum (3, 1),
+// gym_mountaincarconti (2, 1).
 // EXACT (NS below the maximum): the dimensions ARE (NS, NA), no run-time guards against O / A.
 
 // The wrapped forward step of row `xo` of the observation tile: un-scale, ActionRepeat's sub-steps with the initial done flag

@@ -763,9 +763,9 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
                 if (O == 4 && A == 2) obs_state_step<ENV, 4, 2, GEN>(env, O, A, xs + tid * ldx, s_act + tid * 4, s_done[tid] != 0.f, r, done_m);
                 else obs_state_step<ENV, GOPS_MAX_LQ_STATE, GOPS_MAX_ACT, GEN>(env, O, A, xs + tid * ldx, s_act + tid * 4, s_done[tid] != 0.f, r, done_m);
             }
-        } else if constexpr (ENV == GOPS_ENV_CARTPOLE || ENV == GOPS_ENV_PENDULUM) {
+        } else if constexpr (is_gym_kind(ENV)) {
             if (tid < TB)   // gym-style models: obs == state, same wrapper handling as pyth_lq
-                obs_state_step<ENV, (ENV == GOPS_ENV_CARTPOLE) ? 4 : 3, 1, GEN>(env, O, A, xs + tid * ldx, s_act + tid * 4, s_done[tid] != 0.f, r, done_m);
+                obs_state_step<ENV, gym_state_dim(ENV), 1, GEN>(env, O, A, xs + tid * ldx, s_act + tid * 4, s_done[tid] != 0.f, r, done_m);
         } else if (ENV == GOPS_ENV_IDPENDULUM) {
             if (tid < TB) {
                 const int m = tid;
@@ -1080,6 +1080,8 @@ __global__ __launch_bounds__(NTHREADS, F16 ? 4 : (SS ? 2 : ((SK0 == 0 && SK1 == 
             const CartConst C = cart_const();
             const float x0 = obs_unscale(p.env, 0, o[0]), x2 = obs_unscale(p.env, 2, o[2]);
             dl = (x0 < -C.xth) || (x0 > C.xth) || (x2 < -C.thth) || (x2 > C.thth);
+        } else if (ENV == GOPS_ENV_MOUNTAINCAR) {
+            dl = (obs_unscale(p.env, 0, o[0]) >= 0.45f) && (obs_unscale(p.env, 1, o[1]) >= 0.f);
         } else if (ENV == GOPS_ENV_VEH3DOFCONTI) {
             dl = VEH_DONE(o[0], o[1], o[2]);
         } else if (ENV == GOPS_ENV_VEH2DOF) {

@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("GOPS_HIP_LIB") or os.path.join(_HERE, "libgops_hip.so
 
 MAX_LAYERS, MAX_ACT, MAX_LQ, TILE = 5, 4, 6, 16
 ENV_NONE, ENV_LQ, ENV_IDP, ENV_VEH, ENV_VEH_SURR, ENV_CARTPOLE, ENV_PENDULUM, ENV_VEH2DOF, ENV_MOBILEROBOT = 0, 1, 2, 3, 4, 5, 6, 7, 8
-STATE_OBS_ENV_KINDS = (ENV_LQ, ENV_IDP, ENV_CARTPOLE, ENV_PENDULUM)   # the models whose observation is the state
+ENV_MOUNTAINCAR = 9
+STATE_OBS_ENV_KINDS = (ENV_LQ, ENV_IDP, ENV_CARTPOLE, ENV_PENDULUM, ENV_MOUNTAINCAR)   # the models whose observation is the state
 MAX_CLIP_OBS = 16
 # std of the obstacle robot's per-step (v, w) noise draws (pyth_mobilerobot_model.py:141-147, std_type["obs"])
 MOBILEROBOT_NOISE_STD = (0.03, 0.02)

@@ -50,7 +50,7 @@ from gops_amd import hip_backend as hb
 
 _INFO = ("state", "ref_points", "path_num", "u_num", "ref_time", "surr_state")
 # models whose observation is the state: adjoint I/O around the rollout (gops_rollout_backward_open_loop_adj)
-_STATE_OBS_KINDS = (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM, hb.ENV_MOBILEROBOT)
+_STATE_OBS_KINDS = (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_CARTPOLE, hb.ENV_PENDULUM, hb.ENV_MOBILEROBOT, hb.ENV_MOUNTAINCAR)
 
 
 class OptController:
@@ -62,7 +62,7 @@ class OptController:
         base = model.unwrapped
         if mode == "collocation" and base.hip_kind not in _STATE_OBS_KINDS:
             # The batched collocation needs a model whose observation is its state and whose forward takes no info (pyth_lq,
-            # pyth_idpendulum, gym_cartpoleconti, gym_pendulum, pyth_mobilerobot).  For the others the reference itself drops to
+            # pyth_idpendulum, gym_cartpoleconti, gym_pendulum, gym_mountaincarconti, pyth_mobilerobot).  For the others the reference itself drops to
             # its step-by-step rollout (opt_controller.py:292-294); callers that rely on the default mode keep working here
             # through the shooting formulation: the transition equalities are eliminated instead of imposed - the same optimum
             # UNLESS state bounds are active: collocation hands obs_lower_bound / obs_upper_bound to the solver as variable bounds

@@ -109,6 +109,8 @@ def obs_dim_of(cfg: Dict) -> int:
         return 4 + cfg["pre_horizon"]
     if cfg["env_id"] == "gym_pendulum":
         return 3
+    if cfg["env_id"] == "gym_mountaincarconti":
+        return 2
     if cfg["env_id"] == "pyth_mobilerobot":
         return 13
     if cfg["env_id"] in ("pyth_veh3dofconti", "pyth_veh3dofconti_errcstr"):
@@ -126,7 +128,8 @@ def n_surr_of(cfg: Dict) -> int:
 
 
 def act_dim_of(cfg: Dict) -> int:
-    if cfg["env_id"] in ("pyth_idpendulum", "gym_cartpoleconti", "gym_pendulum", "pyth_veh2dofconti", "pyth_veh2dofconti_errcstr"):
+    if cfg["env_id"] in ("pyth_idpendulum", "gym_cartpoleconti", "gym_pendulum", "gym_mountaincarconti", "pyth_veh2dofconti",
+                         "pyth_veh2dofconti_errcstr"):
         return 1
     if cfg["env_id"] in ("pyth_veh3dofconti", "pyth_veh3dofconti_errcstr", "pyth_mobilerobot") or cfg["env_id"] in _SURR_ENVS:
         return 2
@@ -175,6 +178,8 @@ def make_batch(cfg: Dict, seed: int, batch: int = None) -> Dict[str, torch.Tenso
     elif env_id == "gym_pendulum":        # (cos th, sin th, thdot), speeds up to the +-8 clamp
         th = rng.uniform(-np.pi, np.pi, size=B)
         out["obs"] = np.stack((np.cos(th), np.sin(th), rng.uniform(-8.0, 8.0, size=B)), axis=1).astype(np.float32)
+    elif env_id == "gym_mountaincarconti":   # gym's own reset: pos ~ U[-0.6, -0.4], vel = 0
+        out["obs"] = np.stack((rng.uniform(-0.6, -0.4, size=B), np.zeros(B)), axis=1).astype(np.float32)
     elif env_id == "pyth_lq":
         mean, std = (np.array(v, dtype=np.float32) for v in _LQ_INIT[cfg.get("lq_config", "s4a2")])
         out["obs"] = rng.uniform(mean - 3 * std, mean + 3 * std, size=(B, len(mean))).astype(np.float32)

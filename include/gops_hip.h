@@ -73,7 +73,23 @@ enum { GOPS_ENV_NONE = 0, GOPS_ENV_LQ = 1, GOPS_ENV_IDPENDULUM = 2, GOPS_ENV_VEH
           obstacle its own (v, w) plus the noise draws handed in through GopsRolloutIn.noise / GopsStepIO.noise;
           info["constraint"] [B,1] = 0.89 - distance(obstacle', ego') of the NEW state (n_constraint = 1, unmasked);
           done = x' < -2 | |y'| > 4 | constraint > 0.15.  fp32 only; ClipObservation over all 13 columns. */
-       GOPS_ENV_MOBILEROBOT = 8 };
+       GOPS_ENV_MOBILEROBOT = 8,
+       /* gym_mountaincarconti_model.py:21-99 (additive, the version number stays 15): obs == state [B,2] = (pos, vel), one action in
+          [-1, 1], observation bounds [-1.2, 0.6] x [-0.07, 0.07], no dt, no GopsEnv field beyond the common ones.  One step:
+            vel' = clamp(vel + 0.0015 a - 0.0025 cos(3 pos), -0.07, 0.07);  pos' = clamp(pos + vel', -1.2, 0.6);
+            vel' = 0 where pos' == -1.2 and vel' < 0 (behind the position update, which used the unzeroed vel');
+            done = pos' >= 0.45 and vel' >= 0 on the NEXT state;  reward = 100 done - 0.1 a^2.
+          Every operation rounds separately in the reference's order and the cosine is correctly rounded, so the clamps, the exact
+          wall compare and the done test fall as in the reference.  Adjoint: clamps pass on their closed interval, the wall rule cuts
+          the path into the returned vel' only (not vel' -> pos'), the indicator has no gradient, d reward / d a = -0.2 a.
+          Takes every wrapper GOPS_ENV_PENDULUM takes (ScaleAction, ClipAction, ClipObservation, ScaleObservation, ShapingReward,
+          ActionRepeat, MaskAtDone or none); the MLP rollouts (streamed kernels), the adjoint I/O of
+          gops_rollout_backward_open_loop_adj, the POLY / RBF lane rollouts and gops_env_step.  fp32 only: GOPS_DTYPE_F16 is refused
+          with GOPS_ERR_UNSUPPORTED (a half-precision plane cannot hold the 0.07 / 1.2 thresholds the branches compare against
+          exactly); data_env = 1 likewise (no data-env restatement).  GOPS_ERR_BAD_ARG: obs_dim != 2, act_dim != 1, or an empty
+          action range (min_action >= max_action or act_low > act_high, NaN included: ScaleAction would divide by zero and the NaN
+          action would decide every branch). */
+       GOPS_ENV_MOUNTAINCAR = 9 };
 #define GOPS_MAX_SURR 4        /* surrounding vehicles */
 #define GOPS_MAX_CONSTRAINT 3  /* constraint outputs per step */
 #define GOPS_MAX_REPEAT 8      /* ActionRepeatModel: sub-steps per env step */
@@ -185,7 +201,7 @@ typedef struct GopsEnv {
     int32_t data_env;
     /* ScaleObservationModel (gops/env/wrapper/scale_observation.py:74-119; create_env_model.py:115-118 puts it between
      * ShapingReward and ClipObservation): the observations the policy and the caller see are (obs + obs_shift) * obs_scale;
-     * the model steps obs / obs_scale - obs_shift.  GOPS_ENV_LQ / _IDPENDULUM / _CARTPOLE / _PENDULUM only (obs_dim <= 8).  As in the
+     * the model steps obs / obs_scale - obs_shift.  GOPS_ENV_LQ / _IDPENDULUM / _CARTPOLE / _PENDULUM / _MOUNTAINCAR only (obs_dim <= 8).  As in the
      * reference, ClipObservationModel then clips the SCALED observation with the model's own (unscaled) bounds. */
     int32_t scale_obs;
     float obs_scale[8], obs_shift[8];
@@ -210,7 +226,7 @@ typedef struct GopsEnv {
      * action_repeat.py:54-87): repeat_num >= 2 applies the masked base step repeat_num times to the advancing observation
      * with the INITIAL done flags; the rewards are summed (repeat_last_reward = 1: only the last one is returned), done is
      * the last sub-step's.  0 / 1 = no wrapper.  Supported for the models whose observation is the state (GOPS_ENV_LQ,
-     * _IDPENDULUM, _CARTPOLE, _PENDULUM; the reference wrapper does not advance `info`), fp32, repeat_num <= GOPS_MAX_REPEAT. */
+     * _IDPENDULUM, _CARTPOLE, _PENDULUM, _MOUNTAINCAR; the reference wrapper does not advance `info`), fp32, repeat_num <= GOPS_MAX_REPEAT. */
     int32_t repeat_num;
     int32_t repeat_last_reward;
 } GopsEnv;
@@ -328,7 +344,7 @@ int gops_rollout_backward_open_loop(const GopsRolloutDesc* desc, const GopsRollo
  * requires_grad False: gradients still flow through its INPUT).  The terminal term is evaluated by the caller
  * (gops_mlp_forward / gops_mlp_backward_x) and comes back as `grad_final_obs`.
  * Supported for the env kinds whose observation is the model state (GOPS_ENV_NONE, _LQ, _IDPENDULUM, _CARTPOLE,
- * _PENDULUM), fp32, tail_value = 0, closed loop. */
+ * _PENDULUM, _MOUNTAINCAR), fp32, tail_value = 0, closed loop. */
 typedef struct GopsRolloutAdjoint {
     const float* grad_final_obs;  /* [B, obs_dim] d(loss)/d(final_obs) (GopsRolloutOut.final_obs); NULL = zeros */
     float* grad_obs;              /* out [B, obs_dim]: d(loss)/d(obs) of the initial observation; NULL = not wanted */
@@ -488,7 +504,7 @@ int gops_mean_loss(const float* x, int32_t n, double scale, float* stats, void* 
  *   takes it when desc->finite_horizon = 1), bias[0] = [out] or NULL (add_bias), weight[1] = norm_matrix [obs_dim] or NULL (value only);
  *   GopsMlpGrad.weight[0] / bias[0] likewise.
  * No tanh squash: the raw linear output goes into ScaleAction / ClipAction.  The rollout is that of gops_rollout_forward / _backward for
- * GOPS_ENV_LQ (obs_dim <= 6), _IDPENDULUM, _CARTPOLE and _PENDULUM with every wrapper those take (MaskAtDone or none, ClipObservation,
+ * GOPS_ENV_LQ (obs_dim <= 6), _IDPENDULUM, _CARTPOLE, _PENDULUM and _MOUNTAINCAR with every wrapper those take (MaskAtDone or none, ClipObservation,
  * ShapingReward, ScaleObservation, ActionRepeat); policy degree 1 or 2 for every obs_dim, degree 3 for obs_dim <= 3; the tail value
  * (tail_value, tail_unmasked) must be a GOPS_POLY_SYM_2 net.  fp32 only (GOPS_DTYPE_F16 refused), closed loop only, variant_flags 0.
  * Anything else - an MLP policy or value in the description, another env kind - returns GOPS_ERR_UNSUPPORTED.
@@ -607,7 +623,7 @@ int gops_rpi_mlp_evaluate(int32_t env_kind, int32_t batch, int32_t max_steps, co
  * MLP policies with 2 .. GOPS_MAX_LAYERS layers, hidden widths multiples of 16 (up to ~1100: two activation tiles must fit in LDS),
  * every GOPS_ACT_*, GOPS_DTYPE_F32; weight tensors at any 4-byte alignment (16-byte loads are taken only where the pointer allows).
  * GOPS_ERR_UNSUPPORTED: any other env kind (mobilerobot draws noise per step, the constrained
- * vehicle models, GOPS_ENV_PENDULUM has no data-env restatement), POLY nets (n_layers = 1), GOPS_DTYPE_F16.  GOPS_ERR_BAD_ARG:
+ * vehicle models, GOPS_ENV_PENDULUM and _MOUNTAINCAR have no data-env restatement), POLY nets (n_layers = 1), GOPS_DTYPE_F16.  GOPS_ERR_BAD_ARG:
  * data_env = 0, shapes that do not match the env kind, NULL pointers.  GOPS_ERR_WORKSPACE: workspace_bytes too small.
  * gops_episode_workspace_bytes: 0 for a description gops_episode_rollout rejects. */
 struct GopsEpisodeOut {
