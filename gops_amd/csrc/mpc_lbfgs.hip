@@ -1,4 +1,4 @@
-// Batched box-constrained L-BFGS for shooting MPC (gops_mpc_state_bytes / _init / _step / _finish of include/gops_hip.h): B independent
+// Batched box-constrained L-BFGS for shooting MPC (gops_mpc_state_bytes / _init / _step / _finish / _advance of include/gops_hip.h): B independent
 // problems of n variables, each moved by one call of gops_mpc_step per cost-and-gradient evaluation, with no value read on the host.
 //
 // Work assignment: a sub-group of W lanes owns one problem - W = 64 (one wave per problem) for n > 64, else the smallest of
@@ -343,6 +343,51 @@ __global__ __launch_bounds__(MPC_THREADS) void mpc_finish_kernel(void* state, in
     if (p.lane == 0) f[r] = (float)p.sc[SC_F], status[r] = p.ct[CT_STATUS], iterations[r] = p.ct[CT_ITER];
 }
 
+// The receding-horizon hand-over between two solves of a closed loop (gops_mpc_advance): per row what gops_mpc_finish, the shift of
+// the plan by one control point and gops_mpc_init do one after the other.  x0[i] = x[i + A] below n - A and x[i] from there on (drop
+// the first control point, repeat the last); every lane reads the elements it needs - its own and the ones A further, which other
+// lanes of its wave own - and the row's scalars before any lane writes, so the result does not depend on the order of the lanes.
+template <int W>
+__global__ __launch_bounds__(MPC_THREADS) void mpc_advance_kernel(void* state, int B, int n, int m, int A, const float* __restrict__ frozen,
+                                                                  float* __restrict__ action, int32_t* __restrict__ record,
+                                                                  float* __restrict__ x_trial) {
+    constexpr int E = Problem<W>::E;
+    Problem<W> p;
+    size_t r;
+    if (!mpc_problem(p, state, B, n, m, r)) return;
+    const bool fz = frozen[r] != 0.f;
+    float own[E], next[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = p.lane + e * W;
+        own[e] = next[e] = 0.f;
+        if (i < n) {
+            own[e] = p.row(VE_X)[i];
+            next[e] = i + A < n ? p.row(VE_X)[i + A] : own[e];
+        }
+    }
+    const int status = p.ct[CT_STATUS], iterations = p.ct[CT_ITER], evals = p.ct[CT_EVAL];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = p.lane + e * W;
+        if (i < n) {
+            if (i < A) action[r * A + i] = fz ? 0.f : own[e];
+            const float x = (float)clampd((double)next[e], (double)p.lo[i], (double)p.hi[i]);
+            for (int v = 0; v < GOPS_MPC_VECTORS + 2 * m; ++v) p.row(v)[i] = 0.f;
+            p.row(VE_X)[i] = x, p.row(VE_X_TRIAL)[i] = x, x_trial[r * n + i] = x;
+        }
+    }
+    if (p.lane == 0) {
+        int32_t* rec = record + r * 4;
+        rec[0] = fz ? GOPS_MPC_FROZEN : status;
+        if (!fz) rec[1] += iterations, rec[2] += evals, rec[3] += 1;
+        for (int k = 0; k < GOPS_MPC_SCALARS + m; ++k) p.sc[k] = 0.0;
+        p.sc[SC_GAMMA] = 1.0;
+        for (int k = 0; k < GOPS_MPC_COUNTERS; ++k) p.ct[k] = 0;
+        if (fz) p.ct[CT_STATUS] = GOPS_MPC_FROZEN;
+    }
+}
+
 int mpc_width(int n) { return n > 64 ? 64 : n > 32 ? 32 : n > 16 ? 16 : n > 8 ? 8 : 4; }
 
 // calls f.template operator()<W>() for the sub-group width of n
@@ -404,6 +449,18 @@ int gops_mpc_finish(void* state, size_t state_bytes, int32_t B, int32_t n, int32
     if (rc != GOPS_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     mpc_dispatch(n, [&]<int W>() { hipLaunchKernelGGL(mpc_finish_kernel<W>, mpc_grid(B, n), dim3(MPC_THREADS), 0, s, state, B, n, m, x, f, status, iterations); });
+    return (int)hipGetLastError();
+}
+
+int gops_mpc_advance(void* state, size_t state_bytes, int32_t B, int32_t n, int32_t m, int32_t act_dim, const float* frozen, float* action,
+                     int32_t* record, float* x_trial, void* stream) {
+    if (!state || !frozen || !action || !record || !x_trial || B < 1 || n < 1 || n > GOPS_MPC_MAX_DIM || m < 1 || m > GOPS_MPC_MAX_HISTORY ||
+        act_dim < 1 || n % act_dim != 0 || (reinterpret_cast<uintptr_t>(state) & 7) || state_bytes != mpc_bytes(B, n, m))
+        return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    mpc_dispatch(n, [&]<int W>() {
+        hipLaunchKernelGGL(mpc_advance_kernel<W>, mpc_grid(B, n), dim3(MPC_THREADS), 0, s, state, B, n, m, act_dim, frozen, action, record, x_trial);
+    });
     return (int)hipGetLastError();
 }
 

@@ -261,6 +261,7 @@ def _signatures():
         "gops_mpc_init": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gops_mpc_step": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gops_mpc_finish": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "gops_mpc_advance": (rc, [vp, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gops_dqn_backup_workspace_bytes": (sz, [P(GopsDqnBackup), i32]),
         "gops_dqn_backup": (rc, [P(GopsDqnBackup), i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gops_dqn_loss": (rc, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
@@ -1886,7 +1887,8 @@ class CgSolver:
 # gops_mpc_* (include/gops_hip.h: GOPS_MPC_*)
 MPC_MAX_DIM, MPC_MAX_HISTORY, MPC_HYPER_FLOATS, MPC_SCALARS, MPC_COUNTERS, MPC_VECTORS = 256, 8, 8, 5, 8, 6
 MPC_RUNNING, MPC_CONVERGED_PG, MPC_CONVERGED_F, MPC_LINE_SEARCH, MPC_NONFINITE = range(5)
-MPC_STATUS_NAMES = ("running", "converged_pg", "converged_f", "line_search", "nonfinite")
+MPC_FROZEN = 5   # gops_mpc_advance: the row's episode has ended
+MPC_STATUS_NAMES = ("running", "converged_pg", "converged_f", "line_search", "nonfinite", "frozen")
 # c1, shrink, max_ls, pgtol, ftol (scipy's L-BFGS-B: pgtol 1e-5, ftol = factr epsmch = 1e7 * 2.22e-16), curv_eps (its epsmch)
 MPC_HYPER_DEFAULTS = dict(c1=1e-4, shrink=0.5, max_ls=20, pgtol=1e-5, ftol=2.220446049250313e-9, curv_eps=2.220446049250313e-16)
 
@@ -1941,6 +1943,21 @@ class MpcSolver:
         check(lib().gops_mpc_finish(*self._args(), _ptr(self.x), _ptr(self.f_best), self.status.data_ptr(), self.iterations.data_ptr(),
                                     _stream()), "gops_mpc_finish")
         return self.x, self.f_best, self.status, self.iterations
+
+    def advance(self, frozen: torch.Tensor, action_out: torch.Tensor, record: torch.Tensor):
+        """The hand-over between two solves of a closed loop, one launch (gops_mpc_advance): `action_out` [batch, act_dim] <- the
+        first control point of every row's accepted point (0 where `frozen` [batch] float is non-zero), the block re-initialised
+        from the plan shifted by one control point as `init` would (frozen rows: status MPC_FROZEN, never stepped again), `x_trial`
+        ready for the next evaluation; `record` [batch, 4] int32: last status, summed iterations, summed evaluations, solves."""
+        assert frozen.dtype == torch.float32 and frozen.numel() == self.batch and record.dtype == torch.int32 and record.numel() == 4 * self.batch
+        assert action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.numel() % self.batch == 0
+        check(lib().gops_mpc_advance(*self._args(), action_out.numel() // self.batch, _ptr(frozen), _ptr(action_out), record.data_ptr(),
+                                     _ptr(self.x_trial), _stream()), "gops_mpc_advance")
+
+    def status_words(self) -> torch.Tensor:
+        """The status words of the state block as a strided int32 view [batch] (device; written by element-wise torch operations)."""
+        first = 2 * self.batch * (MPC_SCALARS + self.m)
+        return self._state.view(torch.int32)[first:first + self.batch * MPC_COUNTERS].view(self.batch, MPC_COUNTERS)[:, 0]
 
     def state(self) -> Dict[str, np.ndarray]:
         """The state block's sections on the host (one synchronisation), named as in include/gops_hip.h."""

@@ -16,6 +16,10 @@ point, which the step kernel keeps writing into its trial row) but is no longer 
 `no_mask_at_done`), the box is the model's action bounds, and the warm start across calls is its shift: drop the first control
 point, repeat the last - per row.
 
+`run_episodes` drives the controller in closed loop for B episodes at once: between two solves the plan is handed over on the
+device (`MpcSolver.advance`, gops_mpc_advance: first action out, plan shifted, block re-initialised - one launch), the env model is
+stepped with the action held, and rows whose episode has ended are frozen; the status polls stay the only host reads.
+
 Scope: shooting mode, box constraints.  A model with path constraints (`get_constraint`) is refused at construction; collocation,
 fp16 and graph capture of the loop are not provided.  What the solver does differently from scipy's L-BFGS-B - projected Armijo
 backtracking instead of the Cauchy point, subspace minimisation and the More-Thuente search; tolerances held in fp32 - is in
@@ -63,12 +67,8 @@ class BatchOptController:
                           max_action=base.action_upper_bound.cpu(), pre_horizon=getattr(base, "pre_horizon", 0),
                           **base.hip_constants())
         env.no_mask_at_done = 1
-        if getattr(base, "get_constraint", None) is not None and hb.has_constraints(env):
-            raise NotImplementedError(f"BatchOptController: {type(base).__name__} has path constraints (get_constraint); the batched "
-                                      "solver handles box constraints only - use OptController(mode='shooting') for it")
-        if not 1 <= self.n <= hb.MPC_MAX_DIM:
-            raise NotImplementedError(f"BatchOptController: {self.n} decision variables per state; the device solver takes 1 .. {hb.MPC_MAX_DIM}")
         self._env = env
+        self._refuse()
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._lo = base.action_lower_bound.cpu().to(torch.float32).repeat(self.num_ctrl_points)
         self._hi = base.action_upper_bound.cpu().to(torch.float32).repeat(self.num_ctrl_points)
@@ -76,10 +76,22 @@ class BatchOptController:
         self._terminal_vmap = True
         self._guess: Optional[torch.Tensor] = None
         self.last_result: Optional[Dict] = None
+        self.last_episodes: Optional[Dict] = None
+        self._data_env = None
+
+    def _refuse(self):
+        """What the batched solver does not handle, said at construction and again by `run_episodes`."""
+        base = self.base
+        if getattr(base, "get_constraint", None) is not None and hb.has_constraints(self._env):
+            raise NotImplementedError(f"BatchOptController: {type(base).__name__} has path constraints (get_constraint); the batched "
+                                      "solver handles box constraints only - use OptController(mode='shooting') for it")
+        if not 1 <= self.n <= hb.MPC_MAX_DIM:
+            raise NotImplementedError(f"BatchOptController: {self.n} decision variables per state; the device solver takes 1 .. {hb.MPC_MAX_DIM}")
 
     def reset(self):
-        """Forget the warm start: the next call starts every row from zero actions."""
+        """Forget the warm start and the last episodes: the next call starts every row from zero actions."""
         self._guess = None
+        self.last_episodes = None
 
     def _objects(self, B: int) -> Dict:
         o = self._per_batch.get(B)
@@ -143,6 +155,19 @@ class BatchOptController:
         for k in range(1, ci):   # the fold, one interval step at a time: element-wise, so a row's bits do not depend on B
             out.add_(g[:, :, k])
 
+    def _iterate(self, o: Dict, data: Dict) -> int:
+        """Evaluate / step from the initialised block until no row is running or `max_iter`; -> the cost evaluations made."""
+        solver, evals = o["solver"], 0
+        while evals < self.max_iter:
+            for _ in range(min(self.check_every, self.max_iter - evals)):
+                self._evaluate(o, data)
+                solver.step()
+                evals += 1
+            plan, cost, status, iterations = solver.finish()
+            if not bool((status == hb.MPC_RUNNING).any().item()):   # the one synchronisation per check_every iterations
+                break
+        return evals
+
     def solve(self, x, info: Optional[Dict] = None) -> Dict:
         """-> dict(action [B, act_dim], plan [B, num_ctrl_points, act_dim], cost [B], status [B] (hb.MPC_*), iterations [B],
         evaluations: cost evaluations made) for the states x [B, obs_dim]; tensors on the device."""
@@ -155,15 +180,7 @@ class BatchOptController:
         guess = self._guess if self._guess is not None and self._guess.shape[0] == B else torch.zeros(B, self.n, dtype=torch.float32,
                                                                                                       device=self.device)
         solver.init(guess)
-        evals = 0
-        while evals < self.max_iter:
-            for _ in range(min(self.check_every, self.max_iter - evals)):
-                self._evaluate(o, data)
-                solver.step()
-                evals += 1
-            plan, cost, status, iterations = solver.finish()
-            if not bool((status == hb.MPC_RUNNING).any().item()):   # the one synchronisation per check_every iterations
-                break
+        evals = self._iterate(o, data)
         plan, cost, status, iterations = (t.clone() for t in solver.finish())
         A = self.action_dim
         self._guess = torch.cat((plan[:, A:], plan[:, -A:]), 1).contiguous()   # drop the first control point, repeat the last
@@ -174,3 +191,76 @@ class BatchOptController:
     def __call__(self, x, info: Optional[Dict] = None) -> torch.Tensor:
         """The first optimal action of every row [B, act_dim]."""
         return self.solve(x, info)["action"]
+
+    def _step_env(self, env_step: str):
+        """The env constants the closed loop is advanced with: "model" - the raw model the plan is optimised on; "data" - the data
+        environment's step (its termination tests and terminal penalty) where the step kernel has it restated."""
+        if env_step == "model":
+            return self._env
+        if env_step != "data":
+            raise ValueError("env_step must be 'model' (the env model's step) or 'data' (the data environment's)")
+        base = self.base
+        if base.hip_kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_VEH, hb.ENV_CARTPOLE, hb.ENV_VEH2DOF, hb.ENV_MOBILEROBOT):
+            from gops_amd.trainer.sampler.reset_pool import NOT_RESTATED
+            raise NotImplementedError(NOT_RESTATED.format(env_id=type(base).__name__))
+        if self._data_env is None:
+            lo, hi = base.action_lower_bound.cpu(), base.action_upper_bound.cpu()
+            self._data_env = hb.make_env(base.hip_kind, base.obs_dim, base.action_dim, act_low=lo, act_high=hi, min_action=lo, max_action=hi,
+                                         obs_low=base.obs_lower_bound.cpu(), obs_high=base.obs_upper_bound.cpu(),
+                                         pre_horizon=getattr(base, "pre_horizon", 0), data_env=True, ref_c=getattr(base, "ref_c", None),
+                                         **base.hip_constants())
+        return self._data_env
+
+    def run_episodes(self, x0, steps: int, info: Optional[Dict] = None, env_step: str = "model") -> Dict:
+        """B closed-loop episodes of `steps` control steps from the states x0 [B, obs_dim], the plan handed from one solve to the next
+        on the device (`MpcSolver.advance`): per control step the evaluate / step loop of `solve`, one hand-over launch (first action
+        out, plan shifted by one control point, block re-initialised), `ctrl_interval` env steps with the action held, and the books
+        kept by element-wise device operations.  The host reads the status words as `solve` does and nothing else.  A row whose step
+        reports done is frozen: its state is held, its later actions are 0, its return and length stop, its status reads
+        hb.MPC_FROZEN and it is not solved again.  -> dict(return [B], length [B] (env steps), done [B] bool,
+        actions [steps, B, act_dim], obs [steps + 1, B, obs_dim], status [steps, B] int32 (hb.MPC_*), record [B, 4] int32 (last
+        status, summed iterations, summed evaluations, solves), evaluations: cost evaluations made); tensors on the device."""
+        self._refuse()
+        step_env = self._step_env(env_step)
+        x0 = np.asarray(x0) if not torch.is_tensor(x0) else x0
+        assert x0.ndim == 2 and x0.shape[1] == self.obs_dim, "x0: [B, obs_dim]"
+        B, A, dev, steps = int(x0.shape[0]), self.action_dim, self.device, int(steps)
+        o = self._objects(B)
+        solver = o["solver"]
+        data = self._data(o, x0, info)
+        obs = data["obs"].clone()
+        step_info = {k: v for k, v in data.items() if k not in ("obs", "done", "noise")}
+        if self.base.hip_kind == hb.ENV_MOBILEROBOT:   # the obstacle follows its expected motion, as in the plan's rollout
+            step_info["noise"] = torch.zeros(B, 2, dtype=torch.float32, device=dev)
+        zeros = torch.zeros(B, dtype=torch.float32, device=dev)
+        frozen, ret, length = zeros.clone(), zeros.clone(), zeros.clone()
+        record = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        actions = torch.zeros(steps, B, A, dtype=torch.float32, device=dev)
+        obs_out = torch.zeros(steps + 1, B, self.obs_dim, dtype=torch.float32, device=dev)
+        status = torch.zeros(steps, B, dtype=torch.int32, device=dev)
+        obs_out[0].copy_(obs)
+        solver.init(torch.zeros(B, self.n, dtype=torch.float32, device=dev))
+        evals = 0
+        for k in range(steps):
+            data["obs"] = obs
+            data.update({key: v for key, v in step_info.items() if key != "noise"})
+            evals += self._iterate(o, data)
+            solver.advance(frozen, actions[k], record)
+            status[k].copy_(record[:, 0])
+            for _ in range(self.ctrl_interval):
+                obs2, rew, done, info2 = hb.env_step(step_env, obs, actions[k], zeros, step_info)
+                live = 1.0 - frozen
+                ret = ret + rew * live
+                length = length + live
+                held = frozen != 0
+                obs = torch.where(held.unsqueeze(1), obs, obs2)
+                for key, v in info2.items():
+                    if key in step_info and v is not step_info[key]:
+                        step_info[key] = torch.where(held.view(-1, *[1] * (v.dim() - 1)), step_info[key], v)
+                frozen = torch.maximum(frozen, (done != 0).to(torch.float32))
+            solver.status_words().masked_fill_(frozen != 0, hb.MPC_FROZEN)   # the rows this step ended are not solved again
+            obs_out[k + 1].copy_(obs)
+        self._guess = None   # (the block holds the next warm start; solve() starts from its own)
+        self.last_episodes = {"return": ret, "length": length, "done": frozen != 0, "actions": actions, "obs": obs_out, "status": status,
+                              "record": record, "evaluations": evals}
+        return self.last_episodes

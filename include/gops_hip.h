@@ -1134,6 +1134,23 @@ int gops_mpc_step(void* state, size_t state_bytes, int32_t batch, int32_t n, int
 int gops_mpc_finish(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, float* x, float* f, int32_t* status,
                     int32_t* iterations, void* stream);
 
+/* ABI v15, additive entry point (the version number stays 15): the receding-horizon hand-over between two solves of a closed loop,
+ * one launch.  Per row, with x, status, iterations, evaluations the values gops_mpc_finish reports and A = act_dim, n = n_cp A:
+ *     action [batch, A]  <- x[0 : A], the first control point; 0 for a frozen row
+ *     x0                 =  (x[A : n], x[n - A : n]): the first control point dropped, the last repeated (n_cp = 1: x0 = x)
+ *     the row's block    <- what gops_mpc_init leaves for x0: x = x_trial = clamp(x0, lo, hi) with the bounds of the block (also
+ *                           written to the x_trial argument), every other vector, scalar and counter cleared, gamma = 1, status
+ *                           GOPS_MPC_RUNNING - or GOPS_MPC_FROZEN for a frozen row, which gops_mpc_step then leaves untouched
+ *     record [batch][4]  :  [0] <- the status read (GOPS_MPC_FROZEN for a frozen row); for a row that is not frozen
+ *                           [1] += iterations, [2] += evaluations, [3] += 1 (the caller clears the record before an episode)
+ * frozen [batch]: non-zero = the row's episode has ended.  The block must have been initialised by gops_mpc_init (it holds lo, hi).
+ * Same sub-group layout as the other kernels; every source element is read before any is written; copies and a clamp only.
+ * GOPS_ERR_BAD_ARG: a NULL pointer, batch < 1, n outside 1 .. GOPS_MPC_MAX_DIM, m outside 1 .. GOPS_MPC_MAX_HISTORY, act_dim < 1,
+ * n % act_dim != 0, a state block that is not 8-byte aligned, state_bytes != gops_mpc_state_bytes(batch, n, m) - before any HIP call. */
+#define GOPS_MPC_FROZEN 5
+int gops_mpc_advance(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, int32_t act_dim, const float* frozen,
+                     float* action, int32_t* record, float* x_trial, void* stream);
+
 /* Timing hook for bench.py: average duration in ms of the named internal kernel over the
  * launches recorded since the last reset (HIP events on the launch stream).  kernel ids:
  * 0 = forward rollout, 1 = backward sweep, 2 = weight-gradient GEMMs (+ reduce) of gops_rollout_*;
