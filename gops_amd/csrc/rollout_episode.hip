@@ -21,23 +21,16 @@
 
 #include "env_step.h"
 #include "common.h"
+#include "policy_tile.h"
 
 namespace {
 
-constexpr int EP_THREADS = 256;
-constexpr size_t EP_LDS_LIMIT = 150 * 1024;   // dynamic LDS of one workgroup (the CU has 160 KiB)
+constexpr int EP_THREADS = PT_THREADS;
 
 struct EpisodeParams {
     GopsEnv env;   // padded (lq_pad_env), reference constants filled
-    int E, T, O, A, fh, nl, act, staged;
-    int w16;                      // bit j: weight[j] is 16-byte aligned (the unstaged form may load it four floats at a time)
-    int dims[GOPS_MAX_LAYERS + 1];
-    const float* W[GOPS_MAX_LAYERS];
-    const float* Bv[GOPS_MAX_LAYERS];
-    int ldx;                      // row stride of an activation tile (floats)
-    int ldw[GOPS_MAX_LAYERS];     // row stride of a staged weight image
-    int w_off[GOPS_MAX_LAYERS];   // LDS offsets (floats)
-    int b_off[GOPS_MAX_LAYERS];
+    PolicyTile net;
+    int E, T, O, A, fh;
     int state_dim, ref_floats;    // per-episode floats of info["state"] / info["ref_points"] (0: the model has none)
     float pdt;
     GopsStepIO init;
@@ -101,50 +94,18 @@ int episode_check(const GopsEnv* env, const GopsMlp* pol, int E, int T) {
     return GOPS_OK;
 }
 
-inline int ep_pad16(int x) { return (x + 15) & ~15; }
-
-// LDS plan: two activation tiles, the biases, 16 alive flags, then - when everything fits - the weight images.  Returns the
-// bytes, 0 when even the unstaged form does not fit (hidden widths beyond ~1100).
-size_t episode_lds(const GopsMlp& m, EpisodeParams& p) {
-    int maxd = 0;
-    for (int j = 0; j < m.n_layers; ++j) maxd = std::max(maxd, ep_pad16(m.sizes[j]));
-    p.ldx = maxd + 4;   // 4 mod 16: the 16 rows an MFMA operand read touches start in different banks
-    size_t off = 2 * (size_t)GOPS_TILE * p.ldx;
-    for (int j = 0; j < m.n_layers; ++j) { p.b_off[j] = (int)off; off += (size_t)ep_pad16(m.sizes[j + 1]); }
-    off += GOPS_TILE;   // alive flags
-    const size_t base = off;
-    for (int j = 0; j < m.n_layers; ++j) {
-        p.ldw[j] = ep_pad16(m.sizes[j]) + 4;
-        p.w_off[j] = (int)off;
-        off += (size_t)m.sizes[j + 1] * p.ldw[j];
-    }
-    p.staged = off * sizeof(float) <= EP_LDS_LIMIT;
-    const size_t bytes = (p.staged ? off : base) * sizeof(float);
-    return bytes <= EP_LDS_LIMIT ? bytes : 0;
-}
-
 __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int e0 = blockIdx.x * GOPS_TILE;
     const int nvalid = min(GOPS_TILE, p.E - e0);
-    const int O = p.O, A = p.A, nl = p.nl, ldx = p.ldx;
+    const int O = p.O, A = p.A, nl = p.net.nl, ldx = p.net.ldx;
     float* xa = lds;
     float* xb = lds + GOPS_TILE * ldx;
-    int* s_alive = reinterpret_cast<int*>(lds + p.b_off[nl - 1] + ((p.dims[nl] + 15) & ~15));
+    int* s_alive = reinterpret_cast<int*>(lds + p.net.flags_off);
 
     // ---- once per launch: biases (and weights) into LDS, the tile's initial condition into step buffer 0 ----
-    for (int j = 0; j < nl; ++j)
-        for (int n = tid; n < p.dims[j + 1]; n += EP_THREADS) lds[p.b_off[j] + n] = p.Bv[j][n];
-    if (p.staged) {
-        for (int j = 0; j < nl; ++j) {
-            const int K = p.dims[j], N = p.dims[j + 1], ldw = p.ldw[j];
-            for (int idx = tid; idx < N * ldw; idx += EP_THREADS) {
-                const int n = idx / ldw, k = idx - n * ldw;
-                lds[p.w_off[j] + idx] = k < K ? p.W[j][(size_t)n * K + k] : 0.f;
-            }
-        }
-    }
+    policy_tile_load(p.net, lds, tid);
     if (tid < GOPS_TILE) s_alive[tid] = tid < nvalid ? 1 : 0;
     for (int idx = tid; idx < nvalid * O; idx += EP_THREADS) p.obs[0][(size_t)e0 * O + idx] = p.init.obs[(size_t)e0 * O + idx];
     if (p.state_dim > 0) {
@@ -160,7 +121,7 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
     int length = 0;
     __syncthreads();
 
-    const int K0 = p.dims[0], K0p = (K0 + 15) & ~15;
+    const int K0 = p.net.dims[0], K0p = (K0 + 15) & ~15;
 #pragma unroll 1
     for (int t = 0; t < p.T; ++t) {
         const int cur = t & 1;
@@ -183,66 +144,14 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
         }
         __syncthreads();
         // 2. hidden layers
-        float* cur_x = xa;
-        float* nxt_x = xb;
-        for (int j = 0; j < nl - 1; ++j) {
-            const int K = p.dims[j], N = p.dims[j + 1], kch = (K + 15) >> 4;
-            const float* arow = cur_x + (lane & 15) * ldx + 4 * (lane >> 4);
-            const int m0 = (lane >> 4) << 2;
-            for (int nt = wave; nt < (N >> 4); nt += 4) {
-                const int n = (nt << 4) + (lane & 15);
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (p.staged) {
-                    const float* wrow = lds + p.w_off[j] + n * p.ldw[j] + 4 * (lane >> 4);
-                    for (int c = 0; c < kch; ++c) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + 16 * c), b = *reinterpret_cast<const f32x4*>(wrow + 16 * c);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i], acc, 0, 0, 0);
-                    }
-                } else if ((K & 15) == 0 && ((p.w16 >> j) & 1)) {   // rows of 64-byte multiples from a 16-byte aligned base: 16-byte loads
-                    const float* wrow = p.W[j] + (size_t)n * K + 4 * (lane >> 4);
-                    for (int c = 0; c < kch; ++c) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + 16 * c), b = *reinterpret_cast<const f32x4*>(wrow + 16 * c);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i], acc, 0, 0, 0);
-                    }
-                } else {   // the input layer of an unstaged net, or a weight view at a 4-byte offset: any width, guarded element loads
-                    const float* wrow = p.W[j] + (size_t)n * K;
-                    for (int c = 0; c < kch; ++c) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + 16 * c);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int k = 16 * c + 4 * (lane >> 4) + i;
-                            const float b = k < K ? wrow[k] : 0.f;
-                            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b, acc, 0, 0, 0);
-                        }
-                    }
-                }
-                const float bn = lds[p.b_off[j] + n];
-                act_dispatch(p.act, [&]<int ACT>() {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) nxt_x[(m0 + r) * ldx + n] = act_fwd_t<ACT>(acc[r] + bn);
-                });
-            }
-            __syncthreads();
-            float* sw = cur_x; cur_x = nxt_x; nxt_x = sw;
-        }
+        const float* cur_x = policy_tile_hidden(p.net, lds, xa, xb, lane, wave);
         // 3. head: 16 lanes per episode, lane a squashes and stores action a
         {
-            const int m = tid >> 4, part = tid & 15, K = p.dims[nl - 1];
-            const float* wo = p.staged ? lds + p.w_off[nl - 1] : p.W[nl - 1];
-            const int ldo = p.staged ? p.ldw[nl - 1] : K;
-            float y[GOPS_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int a = 0; a < GOPS_MAX_ACT; ++a) {
-                if (a < A) {
-                    float s = 0.f;
-                    for (int k = part; k < K; k += 16) s = fmaf(cur_x[m * ldx + k], wo[a * ldo + k], s);
-                    y[a] = row16_sum(s);
-                }
-            }
+            const int m = tid >> 4, part = tid & 15;
+            float y[GOPS_MAX_ACT];
+            policy_tile_head(p.net, lds, cur_x, m, part, 0, A, y);
             if (part < A && m < nvalid) {
-                const float ya = (part == 0 ? y[0] : part == 1 ? y[1] : part == 2 ? y[2] : y[3]) + lds[p.b_off[nl - 1] + part];
+                const float ya = (part == 0 ? y[0] : part == 1 ? y[1] : part == 2 ? y[2] : y[3]) + lds[p.net.b_off[nl - 1] + part];
                 const float sc = (p.env.policy_high[part] - p.env.policy_low[part]) / 2.f;
                 const float of = (p.env.policy_high[part] + p.env.policy_low[part]) / 2.f;
                 const float act = sc * tanhf(ya) + of;
@@ -290,8 +199,8 @@ extern "C" {
 
 size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T) {
     if (episode_check(env, policy, E, T) != GOPS_OK) return 0;
-    EpisodeParams p;
-    if (episode_lds(*policy, p) == 0) return 0;
+    PolicyTile net;
+    if (policy_tile_plan(*policy, net) == 0) return 0;
     return episode_layout(*env, E).bytes;
 }
 
@@ -304,7 +213,7 @@ int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, i
     if (ref && (!init->state || !init->ref_points || !init->path_num || !init->u_num || !init->ref_time)) return GOPS_ERR_BAD_ARG;
     EpisodeParams p;
     memset(&p, 0, sizeof(p));
-    const size_t lds = episode_lds(*policy, p);
+    const size_t lds = policy_tile_plan(*policy, p.net);
     if (lds == 0) return GOPS_ERR_UNSUPPORTED;
     const EpisodeLayout l = episode_layout(*env, E);
     if (!ws || ws_bytes < l.bytes) return GOPS_ERR_WORKSPACE;
@@ -313,12 +222,7 @@ int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, i
     lq_pad_env(p.env);
     p.E = E, p.T = T, p.O = env->obs_dim, p.A = env->act_dim;
     p.fh = policy->sizes[0] == env->obs_dim + 1;
-    p.nl = policy->n_layers, p.act = policy->hidden_act;
-    for (int j = 0; j <= policy->n_layers; ++j) p.dims[j] = policy->sizes[j];
-    for (int j = 0; j < policy->n_layers; ++j) {
-        p.W[j] = policy->weight[j]; p.Bv[j] = policy->bias[j];
-        if ((reinterpret_cast<uintptr_t>(policy->weight[j]) & 15) == 0) p.w16 |= 1 << j;
-    }
+    policy_tile_bind(*policy, p.net);
     p.state_dim = env->kind == GOPS_ENV_VEH3DOFCONTI ? 6 : env->kind == GOPS_ENV_VEH2DOF ? 4 : 0;
     p.ref_floats = env->kind == GOPS_ENV_VEH3DOFCONTI ? (env->pre_horizon + 1) * 4 : env->kind == GOPS_ENV_VEH2DOF ? (env->pre_horizon + 1) * 2 : 0;
     p.pdt = pdt_of(*env);

@@ -1,0 +1,262 @@
+// A whole sample() of the device samplers (gops_amd/trainer/sampler/device_env_sampler.py: _step_once, T times) in ONE launch:
+// policy, exploration head, env step, the stored transition row, episode bookkeeping and the re-seeding of finished instances.
+//
+// A workgroup of 256 threads owns a tile of 16 environment instances (GOPS_TILE = MFMA M) for all T steps.  Per step t:
+//   1. carry: all threads write the tile's rows of step t - observation and, for the vehicle families, the info tensors - from where
+//      each row continues (the persistent state at t = 0; the previous step's next_* row; or, after a reset, the instance's own
+//      column of the reset pool) into the time-major outputs, contiguous per tile, and the observations into LDS;
+//   2. the hidden layers on v_mfma_f32_16x16x4_f32 and the head's dot products (policy_tile.h, shared with the episode kernel);
+//   3. one lane per instance forms the head in double - DETERM / GAUSS / TANH_GAUSS, gauss_math.h / soft_math.h - from this
+//      step's noise row and stores act and logp, each rounded once;
+//   4. one lane per instance takes the env step through env_step_one (env_step.h: the function gops_env_step calls) with the
+//      step's output rows as its operands - obs2, rew, done and the next_* info ARE the stored row -, then keeps the books:
+//      t += 1, over = done or t >= max_episode_steps, time_limited, end, and where the row continues from (an LDS flag per row).
+// After the last step the same carry writes the persistent state.  A row depends on its own instance only: the pool row is
+// reset_count[i] % R of column i.  No workgroup reads what another wrote; no atomics; every loop is bounded by `steps`.
+#include <stdint.h>
+#include <string.h>
+
+#include "env_step.h"
+#include "common.h"
+#include "policy_tile.h"
+#include "soft_math.h"
+
+namespace {
+
+struct SampleParams {
+    GopsEnv env;   // padded (lq_pad_env), reference constants filled
+    PolicyTile net;
+    int N, T, O, A, head, R, max_steps;
+    int state_dim, ref_floats;   // per-instance floats of info["state"] / info["ref_points"] (0: the model has none)
+    float pdt;
+    double noise_std, min_ls, max_ls;
+    GopsSampleState st;
+    GopsSamplePool pool;
+    const float* noise;
+    GopsSampleOut out;
+};
+static_assert(sizeof(SampleParams) <= 4096, "kernel arguments are passed by value");
+
+int sample_state_dim(const GopsEnv& e) { return e.kind == GOPS_ENV_VEH3DOFCONTI ? 6 : e.kind == GOPS_ENV_VEH2DOF ? 4 : 0; }
+int sample_ref_floats(const GopsEnv& e) {
+    return e.kind == GOPS_ENV_VEH3DOFCONTI ? (e.pre_horizon + 1) * 4 : e.kind == GOPS_ENV_VEH2DOF ? (e.pre_horizon + 1) * 2 : 0;
+}
+
+// The description alone (what gops_sample_workspace_bytes can see): env kind, policy shape, sizes.
+int sample_check(const GopsEnv* env, const GopsMlp* pol, int N, int T) {
+    if (!env || !pol || N < 1 || T < 1) return GOPS_ERR_BAD_ARG;
+    const int k = env->kind;
+    const bool data_kind = k == GOPS_ENV_LQ || k == GOPS_ENV_IDPENDULUM || k == GOPS_ENV_CARTPOLE || k == GOPS_ENV_VEH3DOFCONTI || k == GOPS_ENV_VEH2DOF;
+    const bool model_kind = k == GOPS_ENV_PENDULUM || k == GOPS_ENV_MOUNTAINCAR;   // env models only: no data-env restatement
+    if (!data_kind && !model_kind) return GOPS_ERR_UNSUPPORTED;   // mobilerobot (obstacle noise drawn per step), the constrained vehicle models
+    if (env->data_env ? !data_kind : !model_kind) return GOPS_ERR_UNSUPPORTED;
+    if (env->cstr_err || env->repeat_num > 1) return GOPS_ERR_UNSUPPORTED;
+    if (pol->n_layers == 1 || pol->dtype != GOPS_DTYPE_F32) return GOPS_ERR_UNSUPPORTED;   // POLY nets, half-precision contractions
+    const int O = env->obs_dim, A = env->act_dim, P = env->pre_horizon;
+    if (A < 1 || A > GOPS_MAX_ACT || O < 1) return GOPS_ERR_BAD_ARG;
+    if (k == GOPS_ENV_LQ && O > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED;
+    if ((k == GOPS_ENV_IDPENDULUM && (O != 6 || A != 1)) || (k == GOPS_ENV_CARTPOLE && (O != 4 || A != 1))) return GOPS_ERR_BAD_ARG;
+    if ((k == GOPS_ENV_PENDULUM && (O != 3 || A != 1)) || (k == GOPS_ENV_MOUNTAINCAR && (O != 2 || A != 1))) return GOPS_ERR_BAD_ARG;
+    if (k == GOPS_ENV_VEH3DOFCONTI && (P < 1 || O != 6 + 4 * P || A != 2)) return GOPS_ERR_BAD_ARG;
+    if (k == GOPS_ENV_VEH2DOF && (P < 1 || O != 4 + P || A != 1)) return GOPS_ERR_BAD_ARG;
+    if (env->scale_obs && (O > 8 || env_has_ref_table(k))) return GOPS_ERR_UNSUPPORTED;
+    if (pol->n_layers < 2 || pol->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_UNSUPPORTED;
+    if (pol->sizes[0] == O + 1) return GOPS_ERR_UNSUPPORTED;   // time-augmented policies (FiniteHorizonPolicy)
+    if (pol->sizes[0] != O || (pol->sizes[pol->n_layers] != A && pol->sizes[pol->n_layers] != 2 * A)) return GOPS_ERR_BAD_ARG;
+    for (int j = 1; j < pol->n_layers; ++j)
+        if (pol->sizes[j] < 16 || (pol->sizes[j] & 15)) return GOPS_ERR_UNSUPPORTED;
+    if (pol->hidden_act < GOPS_ACT_LINEAR || pol->hidden_act > GOPS_ACT_TANH) return GOPS_ERR_BAD_ARG;
+    for (int j = 0; j < pol->n_layers; ++j)
+        if (pol->weight[j] == nullptr || pol->bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
+    return GOPS_OK;
+}
+
+// Where row m continues from: src < 0 the persistent state, 0 the previous step's next_* row, k + 1 pool row k of its column.
+__device__ __forceinline__ float carried(int src, const float* st, const float* prev, const float* pool, size_t N, size_t i, int w, int k) {
+    return src < 0 ? st[i * w + k] : src == 0 ? prev[i * w + k] : pool[((size_t)(src - 1) * N + i) * w + k];
+}
+
+// One field of the tile's rows, all threads: dst[e0 .. e0 + nvalid) (contiguous) from where each row continues.
+__device__ __forceinline__ void carry_field(float* dst, const float* st, const float* prev, const float* pool, const int* s_src, int N,
+                                            int e0, int nvalid, int w, int tid) {
+    for (int idx = tid; idx < nvalid * w; idx += PT_THREADS) {
+        const int m = idx / w, k = idx - m * w;
+        dst[(size_t)e0 * w + idx] = carried(s_src[m], st, prev, pool, (size_t)N, (size_t)(e0 + m), w, k);
+    }
+}
+
+__global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e0 = blockIdx.x * GOPS_TILE;
+    const int nvalid = min(GOPS_TILE, p.N - e0);
+    const int N = p.N, T = p.T, O = p.O, A = p.A, nl = p.net.nl, ldx = p.net.ldx;
+    const int sd = p.state_dim, rf = p.ref_floats;
+    float* xa = lds;
+    float* xb = lds + GOPS_TILE * ldx;
+    int* s_src = reinterpret_cast<int*>(lds + p.net.flags_off);
+
+    policy_tile_load(p.net, lds, tid);
+    if (tid < GOPS_TILE) s_src[tid] = -1;   // the first step continues from the persistent state
+    // the instance's books, in the registers of its lane (tid < nvalid)
+    int ti = 0, rc = 0;
+    if (tid < nvalid) { ti = p.st.t[e0 + tid]; rc = p.st.reset_count[e0 + tid]; }
+    __syncthreads();
+
+    const int K0p = (O + 15) & ~15;
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+        const size_t row0 = (size_t)t * N;                    // first row of step t in a [T, N] column
+        const size_t prow0 = t > 0 ? row0 - (size_t)N : 0;    // of step t - 1 (not read at t = 0: every src is < 0)
+        // 1. carry the tile's rows of step t; observations also -> xa (zero padded)
+        for (int idx = tid; idx < GOPS_TILE * K0p; idx += PT_THREADS) {
+            const int m = idx / K0p, k = idx - m * K0p;
+            float v = 0.f;
+            if (m < nvalid && k < O) {
+                v = carried(s_src[m], p.st.obs, p.out.obs2 + prow0 * O, p.pool.obs, (size_t)N, (size_t)(e0 + m), O, k);
+                p.out.obs[(row0 + e0 + m) * O + k] = v;
+            }
+            xa[m * ldx + k] = v;
+        }
+        if (sd > 0) {
+            carry_field(p.out.state + row0 * sd, p.st.state, p.out.next_state + prow0 * sd, p.pool.state, s_src, N, e0, nvalid, sd, tid);
+            carry_field(p.out.ref_points + row0 * rf, p.st.ref_points, p.out.next_ref_points + prow0 * rf, p.pool.ref_points, s_src, N, e0, nvalid, rf, tid);
+            carry_field(p.out.path_num + row0, p.st.path_num, p.out.path_num + prow0, p.pool.path_num, s_src, N, e0, nvalid, 1, tid);
+            carry_field(p.out.u_num + row0, p.st.u_num, p.out.u_num + prow0, p.pool.u_num, s_src, N, e0, nvalid, 1, tid);
+            carry_field(p.out.ref_time + row0, p.st.ref_time, p.out.next_ref_time + prow0, p.pool.ref_time, s_src, N, e0, nvalid, 1, tid);
+        }
+        __syncthreads();
+        // 2. hidden layers
+        const float* cur_x = policy_tile_hidden(p.net, lds, xa, xb, lane, wave);
+        // 3. head: 16 lanes per instance form the dot products, the group's first lane the action and its log-probability
+        {
+            const int m = tid >> 4, part = tid & 15;
+            float ym[GOPS_MAX_ACT], yl[GOPS_MAX_ACT];
+            policy_tile_head(p.net, lds, cur_x, m, part, 0, A, ym);
+            if (p.head != GOPS_SAMPLE_DETERM) policy_tile_head(p.net, lds, cur_x, m, part, A, A, yl);
+            if (part == 0 && m < nvalid) {
+                const size_t row = row0 + e0 + m;
+                const float* bo = lds + p.net.b_off[nl - 1];
+                double lp = 0.0;
+#pragma unroll
+                for (int a = 0; a < GOPS_MAX_ACT; ++a) {
+                    if (a < A) {
+                        const double mean = (double)(ym[a] + bo[a]), e = (double)p.noise[row * A + a];
+                        const double lo = (double)p.env.policy_low[a], hi = (double)p.env.policy_high[a];
+                        double act;
+                        if (p.head == GOPS_SAMPLE_DETERM) {
+                            act = (hi - lo) / 2 * tanh(mean) + (hi + lo) / 2 + p.noise_std * e;
+                        } else if (p.head == GOPS_SAMPLE_GAUSS) {
+                            const GaussDim g = gauss_dim((double)(yl[a] + bo[A + a]), p.min_ls, p.max_ls);
+                            act = mean + g.sd * e;
+                            lp += -(e * e) / 2 - g.ls - HALF_LOG_2PI;
+                        } else {
+                            const TanhGaussDim d = tanh_gauss_dim(mean, (double)(yl[a] + bo[A + a]), e, lo, hi, p.min_ls, p.max_ls);
+                            act = d.act;
+                            lp += d.logp;
+                        }
+                        p.out.act[row * A + a] = (float)act;
+                    }
+                }
+                p.out.logp[row] = (float)lp;
+            }
+        }
+        __syncthreads();   // (also orders the action stores before the env lane's loads: one workgroup, global memory)
+        // 4. one lane per instance: the env step on the stored row, the instance's books
+        if (tid < nvalid) {
+            const int e = e0 + tid;
+            const size_t row = row0 + e;
+            GopsStepIO io = {};
+            io.obs = p.out.obs + row0 * O; io.action = p.out.act + row0 * A; io.done = nullptr;
+            io.next_obs = p.out.obs2 + row0 * O; io.reward = p.out.rew + row0; io.next_done = p.out.done + row0;
+            if (sd > 0) {
+                io.state = p.out.state + row0 * sd; io.ref_points = p.out.ref_points + row0 * rf;
+                io.path_num = p.out.path_num + row0; io.u_num = p.out.u_num + row0; io.ref_time = p.out.ref_time + row0;
+                io.next_state = p.out.next_state + row0 * sd; io.next_ref_points = p.out.next_ref_points + row0 * rf;
+                io.next_ref_time = p.out.next_ref_time + row0;
+            }
+            env_step_one(p.env, e, io, p.pdt);
+            if (sd > 0) {   // the ids do not change within an episode
+                p.out.next_path_num[row] = p.out.path_num[row];
+                p.out.next_u_num[row] = p.out.u_num[row];
+            }
+            const bool dn = p.out.done[row] != 0.f;
+            ti += 1;
+            const bool over = dn || ti >= p.max_steps;
+            p.out.time_limited[row] = (over && !dn) ? 1.f : 0.f;
+            p.out.end[row] = (over || t == T - 1) ? 1.f : 0.f;
+            if (over) {
+                s_src[tid] = rc % p.R + 1;
+                rc += 1;
+                ti = 0;
+            } else {
+                s_src[tid] = 0;
+            }
+        }
+        __syncthreads();   // publishes the step's next_* rows and s_src to the tile
+    }
+    // the persistent state: where step T would have continued from
+    {
+        const size_t prow0 = (size_t)(T - 1) * N;
+        carry_field(p.st.obs, p.st.obs, p.out.obs2 + prow0 * O, p.pool.obs, s_src, N, e0, nvalid, O, tid);
+        if (sd > 0) {
+            carry_field(p.st.state, p.st.state, p.out.next_state + prow0 * sd, p.pool.state, s_src, N, e0, nvalid, sd, tid);
+            carry_field(p.st.ref_points, p.st.ref_points, p.out.next_ref_points + prow0 * rf, p.pool.ref_points, s_src, N, e0, nvalid, rf, tid);
+            carry_field(p.st.path_num, p.st.path_num, p.out.path_num + prow0, p.pool.path_num, s_src, N, e0, nvalid, 1, tid);
+            carry_field(p.st.u_num, p.st.u_num, p.out.u_num + prow0, p.pool.u_num, s_src, N, e0, nvalid, 1, tid);
+            carry_field(p.st.ref_time, p.st.ref_time, p.out.next_ref_time + prow0, p.pool.ref_time, s_src, N, e0, nvalid, 1, tid);
+        }
+        if (tid < nvalid) { p.st.t[e0 + tid] = ti; p.st.reset_count[e0 + tid] = rc; }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gops_sample_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t n_envs, int32_t steps) {
+    if (sample_check(env, policy, n_envs, steps) != GOPS_OK) return 0;
+    PolicyTile net;
+    if (policy_tile_plan(*policy, net) == 0) return 0;
+    return GOPS_SAMPLE_WORKSPACE_BYTES;
+}
+
+int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, int32_t n_envs, int32_t steps,
+                        const GopsSampleState* state, const GopsSamplePool* pool, const float* noise, const GopsSampleOut* out,
+                        void* ws, size_t ws_bytes, void* stream) {
+    if (!env || !policy || !desc || !state || !pool || !noise || !out || steps < 1 || n_envs < 1) return GOPS_ERR_BAD_ARG;
+    if (desc->pool_rows < 1 || desc->max_episode_steps < 1) return GOPS_ERR_BAD_ARG;
+    if (desc->head < GOPS_SAMPLE_DETERM || desc->head > GOPS_SAMPLE_TANH_GAUSS) return GOPS_ERR_BAD_ARG;
+    const int rc = sample_check(env, policy, n_envs, steps);
+    if (rc != GOPS_OK) return rc;
+    const int A = env->act_dim, n_out = policy->sizes[policy->n_layers];
+    if (n_out != (desc->head == GOPS_SAMPLE_DETERM ? A : 2 * A)) return GOPS_ERR_BAD_ARG;   // (an odd width for the Gaussian heads included)
+    if (!state->obs || !state->t || !state->reset_count || !pool->obs) return GOPS_ERR_BAD_ARG;
+    if (!out->obs || !out->act || !out->rew || !out->done || !out->obs2 || !out->logp || !out->time_limited || !out->end) return GOPS_ERR_BAD_ARG;
+    if (env_has_ref_table(env->kind)) {
+        if (!state->state || !state->ref_points || !state->path_num || !state->u_num || !state->ref_time) return GOPS_ERR_BAD_ARG;
+        if (!pool->state || !pool->ref_points || !pool->path_num || !pool->u_num || !pool->ref_time) return GOPS_ERR_BAD_ARG;
+        if (!out->state || !out->next_state || !out->ref_points || !out->next_ref_points || !out->path_num || !out->next_path_num ||
+            !out->u_num || !out->next_u_num || !out->ref_time || !out->next_ref_time)
+            return GOPS_ERR_BAD_ARG;
+    }
+    SampleParams p;
+    memset(&p, 0, sizeof(p));
+    const size_t lds = policy_tile_plan(*policy, p.net);
+    if (lds == 0) return GOPS_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < GOPS_SAMPLE_WORKSPACE_BYTES) return GOPS_ERR_WORKSPACE;
+    p.env = *env;
+    fill_ref_defaults(p.env);
+    lq_pad_env(p.env);
+    policy_tile_bind(*policy, p.net);
+    p.N = n_envs, p.T = steps, p.O = env->obs_dim, p.A = A;
+    p.head = desc->head, p.R = desc->pool_rows, p.max_steps = desc->max_episode_steps;
+    p.noise_std = desc->noise_std, p.min_ls = desc->min_log_std, p.max_ls = desc->max_log_std;
+    p.state_dim = sample_state_dim(*env), p.ref_floats = sample_ref_floats(*env);
+    p.pdt = pdt_of(*env);
+    p.st = *state, p.pool = *pool, p.noise = noise, p.out = *out;
+    launch_with_lds(sample_kernel, dim3((unsigned)((n_envs + GOPS_TILE - 1) / GOPS_TILE)), dim3(PT_THREADS), lds, static_cast<hipStream_t>(stream), p);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

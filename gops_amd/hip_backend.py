@@ -153,6 +153,29 @@ class GopsEpisodeOut(C.Structure):   # gops_episode_rollout
     _fields_ = [(k, C.c_void_p) for k in ("ret", "length", "terminated", "trace_obs", "trace_act", "trace_rew")]
 
 
+SAMPLE_DETERM, SAMPLE_GAUSS, SAMPLE_TANH_GAUSS = 0, 1, 2   # include/gops_hip.h: GOPS_SAMPLE_*
+SAMPLE_WORKSPACE_BYTES = 256                             # include/gops_hip.h: GOPS_SAMPLE_WORKSPACE_BYTES
+SAMPLE_INFO_KEYS = ("state", "ref_points", "path_num", "u_num", "ref_time")
+
+
+class GopsSampleDesc(C.Structure):   # gops_sample_rollout
+    _fields_ = [("head", C.c_int32), ("max_episode_steps", C.c_int32), ("pool_rows", C.c_int32), ("reserved", C.c_int32),
+                ("noise_std", C.c_double), ("min_log_std", C.c_double), ("max_log_std", C.c_double)]
+
+
+class GopsSampleState(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("obs",) + SAMPLE_INFO_KEYS + ("t", "reset_count")]
+
+
+class GopsSamplePool(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("obs",) + SAMPLE_INFO_KEYS]
+
+
+class GopsSampleOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("obs", "act", "rew", "done", "obs2", "logp", "time_limited", "end")
+                + tuple(p + k for k in SAMPLE_INFO_KEYS for p in ("", "next_"))]
+
+
 class GopsAcBackup(C.Structure):   # gops_ac_backup
     _fields_ = [("policy", GopsMlp), ("q", GopsMlp * 2), ("n_q", C.c_int32), ("smooth", C.c_int32),
                 ("squash_low", C.c_float * MAX_ACT), ("squash_high", C.c_float * MAX_ACT),
@@ -233,6 +256,9 @@ def _signatures():
         "gops_rpi_mlp_evaluate": (rc, [i32, i32, i32, _fp, mlp, mlp, vp, vp, vp, sz, f64, f64, f64, f64, vp, vp, vp]),
         "gops_episode_workspace_bytes": (sz, [env, mlp, i32, i32]),
         "gops_episode_rollout": (rc, [env, mlp, i32, i32, io, P(GopsEpisodeOut), vp, sz, vp]),
+        "gops_sample_workspace_bytes": (sz, [env, mlp, i32, i32]),
+        "gops_sample_rollout": (rc, [env, mlp, P(GopsSampleDesc), i32, i32, P(GopsSampleState), P(GopsSamplePool), vp, P(GopsSampleOut),
+                                     vp, sz, vp]),
         "gops_lips_workspace_bytes": (sz, [lips, i32]),
         "gops_lips_forward": (rc, [lips, i32, vp, vp, vp, vp, vp, sz, vp]),
         "gops_lips_backward": (rc, [lips, i32, vp, vp, P(GopsLipsGrad), vp, sz, vp]),
@@ -1060,6 +1086,59 @@ class EpisodeRollout:
         check(lib().gops_episode_rollout(C.byref(self.env), C.byref(self.policy), E, T, C.byref(io), C.byref(out),
                                          self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_episode_rollout")
         return res
+
+
+class SampleRollout:
+    """A whole `sample()` of the device samplers in ONE launch (`gops_sample_rollout`, csrc/rollout_sample.hip): `steps` steps of
+    `n_envs` environment instances - policy, exploration head, env step, stored rows, bookkeeping, resets from the pool.  Holds the
+    workspace and the time-major output buffers, allocated once for (n_envs, steps): `run` returns VIEWS of them, which the next
+    `run` overwrites.  The policy weights are read in place at every call.  A description the kernel refuses raises."""
+
+    def __init__(self, env: GopsEnv, policy: GopsMlp, *, n_envs: int, steps: int, head: int, max_episode_steps: int, pool_rows: int,
+                 noise_std: float = 0.0, min_log_std: float = 0.0, max_log_std: float = 0.0, info_like: Optional[Dict[str, torch.Tensor]] = None,
+                 device: Optional[torch.device] = None):
+        """`info_like`: the info tensors of the persistent state ([n_envs, ...] each; the vehicle families) - their trailing shapes
+        are the output columns'."""
+        self.env, self.policy, self.n_envs, self.steps = env, policy, int(n_envs), int(steps)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.desc = GopsSampleDesc(head=int(head), max_episode_steps=int(max_episode_steps), pool_rows=int(pool_rows), reserved=0,
+                                   noise_std=float(noise_std), min_log_std=float(min_log_std), max_log_std=float(max_log_std))
+        nbytes = lib().gops_sample_workspace_bytes(C.byref(env), C.byref(policy), self.n_envs, self.steps)
+        if nbytes == 0:
+            raise RuntimeError("gops_sample_workspace_bytes: description refused")
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        T, N = self.steps, self.n_envs
+        mk = lambda *sh: torch.empty((T, N) + tuple(sh), dtype=torch.float32, device=self.device)   # noqa: E731
+        self.out = dict(obs=mk(env.obs_dim), act=mk(env.act_dim), rew=mk(), done=mk(), obs2=mk(env.obs_dim), logp=mk(),
+                        time_limited=mk(), end=mk())
+        self.info_keys = tuple(k for k in SAMPLE_INFO_KEYS if info_like and k in info_like)
+        for k in self.info_keys:
+            self.out[k], self.out["next_" + k] = mk(*info_like[k].shape[1:]), mk(*info_like[k].shape[1:])
+        self._out = GopsSampleOut()
+        for k, v in self.out.items():
+            setattr(self._out, k, v.data_ptr())
+
+    def set_policy(self, policy: GopsMlp):
+        self.policy = policy
+
+    def run(self, state: Dict[str, torch.Tensor], pool: Dict[str, torch.Tensor], noise: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """`state`: obs [N, obs_dim], the info tensors, t [N] and reset_count [N] (int32) - advanced IN PLACE; `pool`: obs and the
+        info tensors as [R, N, ...]; `noise` [T, N, act_dim].  Returns the output buffers ([T, N, ...] each).  Enqueues only."""
+        T, N, R = self.steps, self.n_envs, self.desc.pool_rows
+        assert tuple(noise.shape) == (T, N, self.env.act_dim) and state["obs"].shape[0] == N
+        st, pl = GopsSampleState(), GopsSamplePool()
+        for k in ("obs",) + self.info_keys:
+            assert tuple(pool[k].shape) == (R,) + tuple(state[k].shape), k
+            setattr(st, k, _ptr(state[k]))
+            setattr(pl, k, _ptr(pool[k]))
+        for k in ("t", "reset_count"):
+            v = state[k]
+            assert v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.numel() == N, k
+            setattr(st, k, v.data_ptr())
+        check(lib().gops_sample_rollout(C.byref(self.env), C.byref(self.policy), C.byref(self.desc), N, T, C.byref(st), C.byref(pl),
+                                        _ptr(noise), C.byref(self._out), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
+              "gops_sample_rollout")
+        return self.out
 
 
 class ValueNet:

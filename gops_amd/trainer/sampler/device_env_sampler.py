@@ -21,14 +21,16 @@ keys) for `ReplayBuffer.add_tensors`; nothing crosses PCIe in steady state.  Res
 data envs' reset distributions (`gops_amd.utils.synthetic.make_batch`), generated on the host in pools of
 `pool_factor x n_envs` and uploaded once per pool.
 """
+import ctypes
 import time
 import warnings
 
 import torch
 
-from gops_amd.apprfunc.mlp import StochaPolicy, StochaPolicyDis
+from gops_amd.apprfunc.mlp import DetermPolicy, StochaPolicy, StochaPolicyDis
 from gops_amd import hip_backend as hb
-from gops_amd.trainer.sampler.reset_pool import INFO_KEYS as _INFO, NOT_RESTATED, draw_reset_pool
+from gops_amd.trainer.sampler.reset_pool import INFO_KEYS as _INFO, NOT_RESTATED, draw_reset_pool, pool_needs_refresh
+from gops_amd.utils.act_distribution import GaussDistribution, TanhGaussDistribution
 from gops_amd.utils.tensorboard_setup import tb_tags
 
 
@@ -37,7 +39,7 @@ class DeviceEnvSampler:
 
     def __init__(self, cfg: dict, env_model, *, n_envs: int, steps_per_sample: int = 1, max_episode_steps: int = 200,
                  seed: int = 0, device="cuda", pool_factor: int = 8, noise_std: float = 0.0, env_step: str = "data",
-                 action_table=None, epsilon: float = 0.0):
+                 action_table=None, epsilon: float = 0.0, fused: bool = False):
         """cfg: workload dict as in `gops_amd.utils.synthetic.CONFIGS` (env_id, pre_horizon, lq_config);
         env_model: the wrapped model from `create_env_model` (its constants drive the step kernel);
         action_table [act_num, action_dim] (None: continuous actions, the policy output is the action): the policy output is read as
@@ -45,7 +47,12 @@ class DeviceEnvSampler:
         device generator -, the env is stepped with `action_table[index]` and the stored `act` column is the index as a float, [N, 1]
         (DQN; `gym_cartpoleconti` with the table [[-1.], [1.]] is the two-action cartpole).  With a StochaPolicyDis (discrete TRPO) the
         policy output is read as logits instead: the index is drawn from softmax(logits) with the same generator, `logp` is the
-        log-softmax at it, and `epsilon` must be 0 (`sample()` raises ValueError otherwise)."""
+        log-softmax at it, and `epsilon` must be 0 (`sample()` raises ValueError otherwise).
+        `fused=True`: a whole `sample()` in ONE launch (`gops_sample_rollout`, csrc/rollout_sample.hip) - one `torch.randn` of
+        [steps, n_envs, action_dim], the launch, one 4-byte read (the largest reset count, for the pool refresh) - wherever the kernel
+        takes the env and the policy; `path` names the path the last call took and, for the loop, why.  The returned tensors are then
+        views of buffers the next `sample()` overwrites.  Finished instances restart from their OWN column of the pool
+        (`reset_pool.pool_row`), and the noise stream is the fused path's own: a seeded fused run does not reproduce a seeded loop run."""
         self.cfg, self.env_model = dict(cfg), env_model
         if getattr(getattr(env_model, "unwrapped", env_model), "ref_c", None) is not None:
             raise RuntimeError("DeviceEnvSampler draws its reset states from the DEFAULT reference trajectories "
@@ -75,6 +82,9 @@ class DeviceEnvSampler:
         self.obs = first["obs"]
         self.info = {k: first[k] for k in _INFO if k in first}
         self.t = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.fused = bool(fused)
+        self.path = None   # how the last sample() ran: "fused", or "loop: <why the kernel was not used>"
+        self._fstate, self._fpool, self._frollout = None, None, None
 
     # ---- reset pool ---------------------------------------------------------------------------
     def _draw(self, k: int):
@@ -160,12 +170,94 @@ class DeviceEnvSampler:
             raise ValueError("DeviceEnvSampler: epsilon > 0 with a StochaPolicyDis - the policy samples its own categorical "
                              "distribution, and the stored logp would not be that of an epsilon-greedy index")
 
+    # ---- the fused path ------------------------------------------------------------------------
+    def kernel_refuses(self):
+        """None when `gops_sample_rollout` takes this sampler's env and policy, else the reason."""
+        policy = self.networks.policy
+        if self.action_table is not None:
+            return "action table (discrete actions)"
+        if isinstance(policy, StochaPolicyDis):
+            return "categorical policy"
+        for flag, name in (("is_poly", "POLY"), ("is_rbf", "GAUSS (RBF)"), ("is_lipsnet", "LipsNet")):
+            if getattr(policy, flag, False):
+                return name + " policy"
+        if getattr(policy, "_time_input", False):
+            return "time-augmented policy"
+        if not isinstance(policy, (DetermPolicy, StochaPolicy)):
+            return "policy class outside the sample kernel's heads"
+        if isinstance(policy, StochaPolicy) and not issubclass(policy.action_distribution_cls, GaussDistribution):
+            return "action distribution outside the sample kernel's heads"
+        env = self._hip_env()
+        if env.kind == hb.ENV_MOBILEROBOT:
+            return "pyth_mobilerobot draws its obstacle noise per step"
+        if hb.lib().gops_sample_workspace_bytes(ctypes.byref(env), ctypes.byref(policy.hip_mlp()), self.n, self.steps) == 0:
+            # gops_hip.h lists them: the constrained vehicle models, ActionRepeat, scaled vehicle observations, hidden widths that are
+            # no multiple of 16 or beyond the LDS plan, more than GOPS_MAX_ACT actions
+            return "env / policy description outside the sample kernel (constrained model, ActionRepeat, hidden widths)"
+        return None
+
+    def _draw_fused_pool(self):
+        """`pool_factor` reset states per instance, [R, N, ...]: the same draw as the loop's pool, reshaped; the counts start over."""
+        R, N = self.pool_factor, self.n
+        pool = draw_reset_pool(self.cfg, self.env_model, self.seed + 7919 * self._pools_made, R * N, self.device, self.data_env)
+        self._pools_made += 1
+        self._fpool = {k: v.reshape((R, N) + tuple(v.shape[1:])).contiguous() for k, v in pool.items() if k == "obs" or k in self.info}
+        self._fstate["reset_count"].zero_()
+
+    def _sample_fused(self):
+        """One launch for all `steps` steps; -> the kernel's time-major output buffers ([T, N, ...] each)."""
+        policy = self.networks.policy
+        T, N, R = self.steps, self.n, self.pool_factor
+        st = self._fstate
+        if st is None or st["obs"] is not self.obs:   # the first fused call (or the loop ran since): the kernel advances its state in
+            # place, and the loop hands out its state tensors as batch columns - the fused path owns copies
+            st = self._fstate = dict(obs=self.obs.clone().contiguous(), t=self.t.clone(),
+                                     reset_count=torch.zeros(N, dtype=torch.int32, device=self.device),
+                                     **{k: v.clone().contiguous() for k, v in self.info.items()})
+            self.obs, self.info, self.t = st["obs"], {k: st[k] for k in self.info}, st["t"]
+            self._fpool = None
+        if self._fpool is None:
+            self._draw_fused_pool()
+        stochastic = isinstance(policy, StochaPolicy)
+        if stochastic and self.noise_std > 0.0 and not self._warned_noise:
+            self._warned_noise = True
+            warnings.warn("DeviceEnvSampler: noise_std is ignored with a stochastic policy (it samples its own distribution)")
+        if self._frollout is None or (self._frollout.n_envs, self._frollout.steps) != (N, T):
+            head = hb.SAMPLE_DETERM if not stochastic else \
+                hb.SAMPLE_TANH_GAUSS if issubclass(policy.action_distribution_cls, TanhGaussDistribution) else hb.SAMPLE_GAUSS
+            self._frollout = hb.SampleRollout(self._hip_env(), policy.hip_mlp(), n_envs=N, steps=T, head=head,
+                                              max_episode_steps=self.max_steps, pool_rows=R, noise_std=0.0 if stochastic else self.noise_std,
+                                              min_log_std=getattr(policy, "min_log_std", 0.0), max_log_std=getattr(policy, "max_log_std", 0.0),
+                                              info_like=self.info, device=self.device)
+        ro = self._frollout
+        ro.set_policy(policy.hip_mlp())
+        ro.desc.max_episode_steps = int(self.max_steps)
+        noise = torch.randn((T, N, self._hip_env().act_dim), generator=self._gen, device=self.device)
+        out = ro.run(st, self._fpool, noise)
+        if pool_needs_refresh(int(st["reset_count"].max().item()), R):   # the one host read of a fused sample()
+            self._draw_fused_pool()
+        return out
+
+    def _fused_batch(self, out):
+        """The kernel's buffers as the loop's columns: views flattened time-major."""
+        keys = ["obs", "act", "rew", "done", "obs2", "logp"] + [p + k for k in self.info for p in ("", "next_")]
+        return {k: out[k].flatten(0, 1) for k in keys}
+
+    def _choose_path(self) -> bool:
+        why = self.kernel_refuses() if self.fused else "fused=False"
+        self.path = "fused" if why is None else "loop: " + why
+        return why is None
+
     @torch.no_grad()
     def sample(self):
         """Advance all N environments `steps_per_sample` steps; returns (dict of [N*steps, ...] device
         tensors in replay format, tb dict)."""
         t0 = time.time()
         policy = self.networks.policy
+        if self._choose_path():
+            batch = self._fused_batch(self._sample_fused())
+            self.total += self.n * self.steps
+            return batch, {tb_tags["sampler_time"]: (time.time() - t0) * 1000}
         zeros = torch.zeros(self.n, device=self.device)
         chunks = [self._step_once(policy, zeros)[0] for _ in range(self.steps)]
         batch = {k: torch.cat([c[k] for c in chunks]) for k in chunks[0]} if len(chunks) > 1 else chunks[0]

@@ -38,20 +38,26 @@ class OnPolicyDeviceSampler(DeviceEnvSampler):
     def sample(self):
         t0 = time.time()
         policy = self.networks.policy
-        zeros = torch.zeros(self.n, device=self.device)
-        chunks, ends, limited = [], [], []
-        for s in range(self.steps):
-            row, over = self._step_once(policy, zeros)
-            tlim = over & (row["done"] == 0)
-            chunks.append(row)
-            limited.append(tlim)
-            ends.append(torch.ones_like(over) if s == self.steps - 1 else over)
-        batch = {k: torch.cat([c[k] for c in chunks]) for k in chunks[0]}
         T, N = self.steps, self.n
+        if self._choose_path():   # one launch: the kernel keeps the `time_limited` and `end` columns itself
+            out = self._sample_fused()
+            batch = self._fused_batch(out)
+            limited, end = out["time_limited"].flatten() != 0, out["end"]
+        else:
+            zeros = torch.zeros(self.n, device=self.device)
+            chunks, ends, limited = [], [], []
+            for s in range(self.steps):
+                row, over = self._step_once(policy, zeros)
+                tlim = over & (row["done"] == 0)
+                chunks.append(row)
+                limited.append(tlim)
+                ends.append(torch.ones_like(over) if s == self.steps - 1 else over)
+            batch = {k: torch.cat([c[k] for c in chunks]) for k in chunks[0]}
+            limited, end = torch.cat(limited), torch.cat(ends).to(torch.float32).view(T, N)
         val, val_next = self._values(batch["obs"].contiguous()), self._values(batch["obs2"].contiguous())
         ret, adv = hb.gae(batch["rew"].view(T, N), val.view(T, N), val_next.view(T, N), batch["done"].view(T, N),
-                          torch.cat(ends).to(torch.float32).view(T, N), self.gamma, self.gae_lambda)
+                          end, self.gamma, self.gae_lambda)
         del batch["obs2"]
-        batch.update(time_limited=torch.cat(limited), ret=ret.view(-1), adv=adv.view(-1))
+        batch.update(time_limited=limited, ret=ret.view(-1), adv=adv.view(-1))
         self.total += N * T
         return batch, {tb_tags["sampler_time"]: (time.time() - t0) * 1000}

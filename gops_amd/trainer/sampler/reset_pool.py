@@ -12,6 +12,38 @@ NOT_RESTATED = ("the DATA environment of {env_id} is not restated in the step ke
                 "gym_cartpoleconti are): pass env_step='model'")
 
 
+def pool_row(reset_count, pool_rows: int):
+    """The fused sampler's reset rule (csrc/rollout_sample.hip): an instance whose episode ends continues from row
+    `reset_count % pool_rows` of ITS column of the [pool_rows, n_envs, ...] pool - nothing of another instance enters, and an
+    instance that resets more than `pool_rows` times between refreshes revisits its rows."""
+    return reset_count % pool_rows
+
+
+def pool_needs_refresh(max_reset_count: int, pool_rows: int) -> bool:
+    """The pool is redrawn (and the counts zeroed) once any instance has used more than half of its rows."""
+    return 2 * int(max_reset_count) > int(pool_rows)
+
+
+def restate_sample_books(done, t0, reset_count0, max_episode_steps: int, pool_rows: int) -> dict:
+    """The fused sampler's bookkeeping restated on the host from the `done` column [T, N] (numpy), the steps `t0` [N] the
+    instances had taken and their `reset_count0` [N]: time_limited, end [T, N] (0 / 1), src [T, N] - where the row AFTER step t
+    continues from: -1 the step's own next state, else the pool row -, and the final t / reset_count [N]."""
+    done = np.asarray(done)
+    T, N = done.shape
+    t, rc = np.array(t0, dtype=np.int64), np.array(reset_count0, dtype=np.int64)
+    tlim, end, src = np.zeros((T, N), np.float32), np.zeros((T, N), np.float32), np.full((T, N), -1, np.int64)
+    for s in range(T):
+        t += 1
+        dn = done[s] != 0
+        over = dn | (t >= max_episode_steps)
+        tlim[s] = over & ~dn
+        end[s] = over | (s == T - 1)
+        src[s] = np.where(over, pool_row(rc, pool_rows), -1)
+        rc += over
+        t[over] = 0
+    return dict(time_limited=tlim, end=end, src=src, t=t.astype(np.int32), reset_count=rc.astype(np.int32))
+
+
 def draw_reset_pool(cfg: dict, env_model, seed: int, size: int, device, data_env: bool = True) -> dict:
     """`size` initial conditions (device tensors: obs + the info keys the model carries) of `cfg["env_id"]` for `seed`."""
     host = make_batch(cfg, seed, batch=size)

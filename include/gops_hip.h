@@ -635,6 +635,68 @@ size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, i
 int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t episodes, int32_t max_steps, const GopsStepIO* init,
                          const GopsEpisodeOut* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): a whole sample() of the device samplers in one launch
+ * (csrc/rollout_sample.hip) - `steps` = T times the loop body of DeviceEnvSampler._step_once for `n_envs` = N environment
+ * instances: policy, exploration head, one env step (gops_env_step's own device function), the stored transition row, episode
+ * bookkeeping and the re-seeding of finished instances.  Instances run in tiles of GOPS_TILE per workgroup, the MLP contractions
+ * are exact fp32 (v_mfma_f32_16x16x4_f32) as in gops_episode_rollout; weights are read in place.  No host sync, no device
+ * allocation, no atomics; no workgroup reads what another wrote, so a row does not depend on the tiling.
+ *   desc->head, with y the policy's raw output, eps = noise[t][i] and (lo, hi) = env->policy_low / policy_high:
+ *     GOPS_SAMPLE_DETERM      y [A]:   act = (hi - lo) / 2 tanh(y) + (hi + lo) / 2 + noise_std eps, logp = 0;
+ *     GOPS_SAMPLE_GAUSS       y [2A] = (mean, raw log std): ls = clamp(raw, min_log_std, max_log_std), act = mean + exp(ls) eps,
+ *                             logp = sum_a(-eps_a^2 / 2 - ls_a - log sqrt(2 pi));
+ *     GOPS_SAMPLE_TANH_GAUSS  u as for GAUSS, act = (hi - lo) / 2 tanh(u) + (hi + lo) / 2, logp = the Gaussian's at u
+ *                             - sum_a log(1 + 1e-6 - tanh(u_a)^2) - sum_a log((hi_a - lo_a) / 2)  (TanhGaussDistribution).
+ *     Every head is formed in double and rounded once per stored value.
+ *   noise: [T, N, A] standard normals - the kernel draws nothing: a launch is a pure function of its inputs.
+ *   state (read AND written): obs [N, obs_dim]; for the vehicle families state / ref_points / path_num / u_num / ref_time as
+ *     gops_env_step takes them; t [N] int32 steps into the running episode; reset_count [N] int32 resets since the pool was drawn.
+ *   pool: desc->pool_rows = R reset states per instance, [R, N, ...] for obs and each info tensor (read only).
+ *   Per step: the row of (obs_t, info_t) is stored, the head gives act_t / logp_t, the env step gives rew, done, obs2 and the
+ *     next_* info; t_i += 1; over = done != 0 || t_i >= max_episode_steps.  Where `over`, instance i continues from pool row
+ *     [reset_count[i] % R][i], reset_count[i] += 1 and t_i = 0; else from (obs2, next info).  The rule needs nothing from another
+ *     instance; an instance that resets more than R times between refreshes of the pool revisits its rows (defined behaviour).
+ *   out, time-major [T, N, ...], a tile's rows contiguous: obs, act, rew, done, obs2, logp; each info tensor and its next_ twin
+ *     (vehicle families; ignored otherwise); time_limited = over && done == 0; end = over, 1 at t = T - 1.
+ * Accepted: GOPS_ENV_LQ, _IDPENDULUM, _CARTPOLE, _VEH3DOFCONTI, _VEH2DOF (without cstr_err) with data_env = 1; GOPS_ENV_PENDULUM and
+ * _MOUNTAINCAR with data_env = 0 (they have no data-env restatement); repeat_num <= 1; MLP policies as gops_episode_rollout accepts
+ * them, sizes[0] = obs_dim, out_dim = A (DETERM) or 2A (the Gaussian heads), A <= GOPS_MAX_ACT, GOPS_DTYPE_F32.
+ * GOPS_ERR_UNSUPPORTED, nothing launched: any other env kind or data_env value (mobilerobot draws obstacle noise per step, the
+ * constrained vehicle models), POLY nets (n_layers = 1), time-augmented policies (sizes[0] = obs_dim + 1), GOPS_DTYPE_F16, hidden
+ * widths outside the episode kernel's.  GOPS_ERR_BAD_ARG: NULL pointers, steps < 1, n_envs < 1, pool_rows < 1,
+ * max_episode_steps < 1, an unknown head, an output width that is not the head's (an odd one for the Gaussian heads), shapes that
+ * do not match the env kind.  GOPS_ERR_WORKSPACE: workspace_bytes < GOPS_SAMPLE_WORKSPACE_BYTES (the kernel stages nothing there:
+ * the outputs are its step buffers; the section is reserved so that a later kernel may).
+ * gops_sample_workspace_bytes: 0 for a description gops_sample_rollout rejects. */
+#define GOPS_SAMPLE_DETERM 0
+#define GOPS_SAMPLE_GAUSS 1
+#define GOPS_SAMPLE_TANH_GAUSS 2
+#define GOPS_SAMPLE_WORKSPACE_BYTES 256
+struct GopsSampleDesc {
+    int32_t head, max_episode_steps, pool_rows, reserved;
+    double noise_std, min_log_std, max_log_std;
+};
+typedef struct GopsSampleDesc GopsSampleDesc;
+struct GopsSampleState {
+    float* obs; float* state; float* ref_points; float* path_num; float* u_num; float* ref_time;
+    int32_t* t; int32_t* reset_count;
+};
+typedef struct GopsSampleState GopsSampleState;
+struct GopsSamplePool {
+    const float* obs; const float* state; const float* ref_points; const float* path_num; const float* u_num; const float* ref_time;
+};
+typedef struct GopsSamplePool GopsSamplePool;
+struct GopsSampleOut {
+    float* obs; float* act; float* rew; float* done; float* obs2; float* logp; float* time_limited; float* end;
+    float* state; float* next_state; float* ref_points; float* next_ref_points; float* path_num; float* next_path_num;
+    float* u_num; float* next_u_num; float* ref_time; float* next_ref_time;
+};
+typedef struct GopsSampleOut GopsSampleOut;
+size_t gops_sample_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t n_envs, int32_t steps);
+int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, int32_t n_envs, int32_t steps,
+                        const GopsSampleState* state, const GopsSamplePool* pool, const float* noise, const GopsSampleOut* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ABI v15, additive entry points (the version number stays 15): LipsNet policies (gops/apprfunc/lipsnet.py DetermPolicy) - an MLP f
  * evaluated together with its input Jacobian J = df/dx and differentiated through it (csrc/rollout_lips.hip):
  *     y = K(x) f(x) / (||J||_F + eps),   action = y   or, with `squash`,   (high - low) / 2 tanh(y) + (high + low) / 2,

@@ -1,0 +1,57 @@
+"""The fused device sampler without a GPU: the C ABI of `gops_sample_rollout`, the host statement of its reset rule and
+bookkeeping (`gops_amd.trainer.sampler.reset_pool`) on hand-made counts, and the opt-in switch of the samplers."""
+import inspect
+
+import numpy as np
+
+from ac_helpers import check_abi
+
+from gops_amd.trainer.sampler.reset_pool import pool_needs_refresh, pool_row, restate_sample_books
+
+
+def test_abi_of_the_sample_entry_points(tmp_path):
+    from gops_amd import hip_backend as hb
+    check_abi(tmp_path, [("GopsSampleDesc", hb.GopsSampleDesc), ("GopsSampleState", hb.GopsSampleState),
+                         ("GopsSamplePool", hb.GopsSamplePool), ("GopsSampleOut", hb.GopsSampleOut)],
+              ("gops_sample_workspace_bytes", "gops_sample_rollout"),
+              [("GOPS_SAMPLE_DETERM", hb.SAMPLE_DETERM), ("GOPS_SAMPLE_GAUSS", hb.SAMPLE_GAUSS),
+               ("GOPS_SAMPLE_TANH_GAUSS", hb.SAMPLE_TANH_GAUSS), ("GOPS_SAMPLE_WORKSPACE_BYTES", hb.SAMPLE_WORKSPACE_BYTES)])
+    assert [f[0] for f in hb.GopsSampleDesc._fields_] == ["head", "max_episode_steps", "pool_rows", "reserved", "noise_std", "min_log_std",
+                                                          "max_log_std"]
+    assert [f[0] for f in hb.GopsSampleOut._fields_][:8] == ["obs", "act", "rew", "done", "obs2", "logp", "time_limited", "end"]
+
+
+def test_the_pool_row_wraps_around_and_needs_no_other_instance():
+    counts = np.array([0, 1, 2, 3, 4, 5, 7])
+    assert pool_row(counts, 2).tolist() == [0, 1, 0, 1, 0, 1, 1]
+    assert pool_row(counts, 3).tolist() == [0, 1, 2, 0, 1, 2, 1]
+    assert pool_row(counts, 1).tolist() == [0] * 7
+    assert [pool_needs_refresh(k, 8) for k in (0, 4, 5, 9)] == [False, False, True, True]
+    assert [pool_needs_refresh(k, 2) for k in (0, 1, 2)] == [False, False, True]
+
+
+def test_books_restated_on_hand_made_columns():
+    """Five steps, limit 3, R = 2.  Instance 0 never terminates (time limit at its third step, then again not within the call);
+    instance 1 starts two steps into its episode; instance 2 terminates at every step (five resets: wrap-around twice); instance 3
+    terminates exactly at the time limit (done wins: not time_limited) and starts with one reset already counted."""
+    done = np.array([[0, 0, 1, 0],
+                     [0, 0, 1, 0],
+                     [0, 0, 1, 1],
+                     [0, 0, 1, 0],
+                     [0, 1, 1, 0]], np.float32)
+    got = restate_sample_books(done, t0=[0, 2, 0, 0], reset_count0=[0, 0, 0, 1], max_episode_steps=3, pool_rows=2)
+    assert got["time_limited"].T.tolist() == [[0, 0, 1, 0, 0], [1, 0, 0, 1, 0], [0, 0, 0, 0, 0], [0, 0, 0, 0, 0]]
+    assert got["end"].T.tolist() == [[0, 0, 1, 0, 1], [1, 0, 0, 1, 1], [1, 1, 1, 1, 1], [0, 0, 1, 0, 1]]
+    assert got["src"].T.tolist() == [[-1, -1, 0, -1, -1], [0, -1, -1, 1, 0], [0, 1, 0, 1, 0], [-1, -1, 1, -1, -1]]
+    assert got["t"].tolist() == [2, 0, 0, 2] and got["reset_count"].tolist() == [1, 3, 5, 2]
+    one = restate_sample_books(done[:1], t0=[2, 0, 0, 0], reset_count0=[3, 0, 0, 0], max_episode_steps=3, pool_rows=2)
+    assert one["end"].tolist() == [[1, 1, 1, 1]] and one["time_limited"].tolist() == [[1, 0, 0, 0]]   # the horizon ends every segment
+    assert one["src"].tolist() == [[1, -1, 0, -1]] and one["reset_count"].tolist() == [4, 0, 1, 0]
+
+
+def test_the_loop_stays_the_default():
+    from gops_amd.trainer.sampler.device_env_sampler import DeviceEnvSampler
+    from gops_amd.trainer.sampler.on_policy_device_sampler import OnPolicyDeviceSampler
+    assert inspect.signature(DeviceEnvSampler.__init__).parameters["fused"].default is False
+    assert "fused" not in inspect.signature(OnPolicyDeviceSampler.__init__).parameters   # (handed through to the base: one default)
+    assert OnPolicyDeviceSampler.kernel_refuses is DeviceEnvSampler.kernel_refuses
