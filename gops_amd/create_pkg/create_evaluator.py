@@ -29,7 +29,8 @@ def _build_evaluator(**kwargs):
     return Evaluator(index=kwargs.pop("index", 0), env_model=env_model, networks=networks, cfg=cfg,
                      num_eval_episode=kwargs.pop("num_eval_episode"), eval_save=kwargs.pop("eval_save", True),
                      save_folder=kwargs.pop("save_folder", None), seed=kwargs.pop("seed", 0) or 0,
-                     max_episode_steps=kwargs.pop("max_episode_steps", None), fused=kwargs.pop("fused", True))
+                     max_episode_steps=kwargs.pop("max_episode_steps", None), fused=kwargs.pop("fused", True),
+                     action_table=kwargs.pop("action_table", None))
 
 
 register("evaluator", _build_evaluator)

@@ -2,7 +2,8 @@
 // gops_episode_rollout) and the sampler kernel (rollout_sample.hip, gops_sample_rollout): the LDS plan, the once-per-launch staging
 // of biases and weights, the hidden layers on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation) and the head's dot
 // products (16 lanes per row, DPP sum).  A workgroup of PT_THREADS = 256 threads (four waves) owns the tile; the kernels differ in
-// what they do with the head's outputs and in the env phase around it.
+// what they do with the head's outputs and in the env phase around it.  Their discrete heads (gops_*_rollout_dis: an action table)
+// read all outputs of a row through policy_tile_values and share the arg-max rule policy_tile_greedy.
 #pragma once
 #include <algorithm>
 
@@ -139,4 +140,31 @@ __device__ __forceinline__ void policy_tile_head(const PolicyTile& p, const floa
             y[a] = row16_sum(s);
         }
     }
+}
+
+// The discrete heads (gops_sample_rollout_dis, gops_episode_rollout_dis): all n <= GOPS_DQN_MAX_ACTIONS raw outputs of row m WITH
+// the bias (fp32), in every lane of the row's group - policy_tile_head in chunks of GOPS_MAX_ACT; y[a] = 0 for a >= n.  Every index
+// below is a compile-time constant after unrolling: the array stays in registers.
+__device__ __forceinline__ void policy_tile_values(const PolicyTile& p, const float* lds, const float* cur_x, int m, int part, int n,
+                                                   float (&y)[GOPS_DQN_MAX_ACTIONS]) {
+    const float* bo = lds + p.b_off[p.nl - 1];   // (pt_pad16(n) floats: a read below n's padding stays inside the plan)
+#pragma unroll
+    for (int c = 0; c < GOPS_DQN_MAX_ACTIONS; c += GOPS_MAX_ACT) {
+        float yc[GOPS_MAX_ACT];
+        policy_tile_head(p, lds, cur_x, m, part, c, n - c, yc);   // (n - c <= 0: no dot product is formed)
+#pragma unroll
+        for (int a = 0; a < GOPS_MAX_ACT; ++a) y[c + a] = c + a < n ? yc[a] + bo[c + a] : 0.f;
+    }
+}
+
+// gops_dqn_backup's a_star rule: the LOWEST index among equal maxima; a NaN is the maximum (the first one), as for torch.max.
+__device__ __forceinline__ int policy_tile_greedy(const float (&y)[GOPS_DQN_MAX_ACTIONS], int n) {
+    float best = y[0];
+    int idx = 0;
+#pragma unroll
+    for (int a = 1; a < GOPS_DQN_MAX_ACTIONS; ++a) {
+        const float v = y[a];
+        if (a < n && (v > best || (v != v && best == best))) best = v, idx = a;
+    }
+    return idx;
 }

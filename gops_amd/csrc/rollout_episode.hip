@@ -9,6 +9,8 @@
 //      between two LDS tiles; weights are read in place from the live parameter tensors - staged in LDS once per launch when the
 //      whole network fits next to the tiles, else streamed from L2 every step;
 //   3. 16 lanes per episode form the head's dot products (DPP sum), lane a squashes action a (tanh, act limits) and stores it;
+//      with an action table (gops_episode_rollout_dis) the outputs are action values / logits: lane a stores component a of the
+//      table's row at their arg-max, and the trace keeps the index;
 //   4. one lane per episode takes the data env's step through env_step_one (env_step.h) - the function env_step_kernel calls, so
 //      the trace of an episode is reproduced by gops_env_step step by step - and keeps the episode's books in registers.
 // The per-episode step buffers (obs, state, ref_points ring, ref_time) ping-pong between two sets in the workspace; each
@@ -40,6 +42,8 @@ struct EpisodeParams {
     float* reft[2];
     float *action, *reward, *done;
     GopsEpisodeOut out;
+    int act_num;          // the greedy head over an action table (0: none)
+    const float* table;   // [act_num, A], device memory
 };
 
 struct EpisodeLayout {
@@ -69,7 +73,8 @@ EpisodeLayout episode_layout(const GopsEnv& e, int E) {
     return l;
 }
 
-int episode_check(const GopsEnv* env, const GopsMlp* pol, int E, int T) {
+// `act_num` = 0: the continuous head (output width A); else the greedy head's (output width act_num).
+int episode_check(const GopsEnv* env, const GopsMlp* pol, int E, int T, int act_num = 0) {
     if (!env || !pol || E < 1 || T < 1) return GOPS_ERR_BAD_ARG;
     if (!env->data_env) return GOPS_ERR_BAD_ARG;   // evaluation steps the DATA environment
     const int k = env->kind;
@@ -85,7 +90,7 @@ int episode_check(const GopsEnv* env, const GopsMlp* pol, int E, int T) {
     if (k == GOPS_ENV_VEH2DOF && (P < 1 || O != 4 + P || A != 1)) return GOPS_ERR_BAD_ARG;
     if (env->scale_obs && (O > 8 || env_has_ref_table(k))) return GOPS_ERR_UNSUPPORTED;
     if (pol->n_layers < 2 || pol->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_UNSUPPORTED;
-    if ((pol->sizes[0] != O && pol->sizes[0] != O + 1) || pol->sizes[pol->n_layers] != A) return GOPS_ERR_BAD_ARG;
+    if ((pol->sizes[0] != O && pol->sizes[0] != O + 1) || pol->sizes[pol->n_layers] != (act_num > 0 ? act_num : A)) return GOPS_ERR_BAD_ARG;
     for (int j = 1; j < pol->n_layers; ++j)
         if (pol->sizes[j] < 16 || (pol->sizes[j] & 15)) return GOPS_ERR_UNSUPPORTED;
     if (pol->hidden_act < GOPS_ACT_LINEAR || pol->hidden_act > GOPS_ACT_TANH) return GOPS_ERR_BAD_ARG;
@@ -146,7 +151,16 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
         // 2. hidden layers
         const float* cur_x = policy_tile_hidden(p.net, lds, xa, xb, lane, wave);
         // 3. head: 16 lanes per episode, lane a squashes and stores action a
-        {
+        if (p.act_num > 0) {   // the greedy head: every lane of the group holds all values, lane a stores the table row's component a
+            const int m = tid >> 4, part = tid & 15;
+            float y[GOPS_DQN_MAX_ACTIONS];
+            policy_tile_values(p.net, lds, cur_x, m, part, p.act_num, y);
+            const int index = policy_tile_greedy(y, p.act_num);   // 0 <= index < act_num
+            if (part < A && m < nvalid) {
+                p.action[(size_t)(e0 + m) * A + part] = p.table[index * A + part];
+                if (part == 0 && p.out.trace_act != nullptr && s_alive[m]) p.out.trace_act[(size_t)(e0 + m) * p.T + t] = (float)index;
+            }
+        } else {
             const int m = tid >> 4, part = tid & 15;
             float y[GOPS_MAX_ACT];
             policy_tile_head(p.net, lds, cur_x, m, part, 0, A, y);
@@ -193,21 +207,9 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T) {
-    if (episode_check(env, policy, E, T) != GOPS_OK) return 0;
-    PolicyTile net;
-    if (policy_tile_plan(*policy, net) == 0) return 0;
-    return episode_layout(*env, E).bytes;
-}
-
-int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T, const GopsStepIO* init, const GopsEpisodeOut* out,
-                         void* ws, size_t ws_bytes, void* stream) {
-    const int rc = episode_check(env, policy, E, T);
-    if (rc != GOPS_OK) return rc;
+// What both entry points do once the description passed: the pointer checks, the workspace, the launch.
+int episode_launch(const GopsEnv* env, const GopsMlp* policy, const float* table, int act_num, int E, int T, const GopsStepIO* init,
+                   const GopsEpisodeOut* out, void* ws, size_t ws_bytes, void* stream) {
     if (!init || !out || !init->obs || !out->ret || !out->length || !out->terminated) return GOPS_ERR_BAD_ARG;
     const bool ref = env_has_ref_table(env->kind);
     if (ref && (!init->state || !init->ref_points || !init->path_num || !init->u_num || !init->ref_time)) return GOPS_ERR_BAD_ARG;
@@ -236,8 +238,43 @@ int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, i
     }
     p.action = f + l.action, p.reward = f + l.reward, p.done = f + l.done;
     p.out = *out;
+    p.act_num = act_num, p.table = table;
     launch_with_lds(episode_kernel, dim3((unsigned)((E + GOPS_TILE - 1) / GOPS_TILE)), dim3(EP_THREADS), lds, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T) {
+    if (episode_check(env, policy, E, T) != GOPS_OK) return 0;
+    PolicyTile net;
+    if (policy_tile_plan(*policy, net) == 0) return 0;
+    return episode_layout(*env, E).bytes;
+}
+
+size_t gops_episode_dis_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t act_num, int32_t E, int32_t T) {
+    if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS || episode_check(env, policy, E, T, act_num) != GOPS_OK) return 0;
+    PolicyTile net;
+    if (policy_tile_plan(*policy, net) == 0) return 0;
+    return episode_layout(*env, E).bytes;
+}
+
+int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T, const GopsStepIO* init, const GopsEpisodeOut* out,
+                         void* ws, size_t ws_bytes, void* stream) {
+    const int rc = episode_check(env, policy, E, T);
+    if (rc != GOPS_OK) return rc;
+    return episode_launch(env, policy, nullptr, 0, E, T, init, out, ws, ws_bytes, stream);
+}
+
+int gops_episode_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const float* action_table, int32_t act_num, int32_t E, int32_t T,
+                             const GopsStepIO* init, const GopsEpisodeOut* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!action_table) return GOPS_ERR_BAD_ARG;
+    if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS) return GOPS_ERR_UNSUPPORTED;
+    const int rc = episode_check(env, policy, E, T, act_num);   // (BAD_ARG for an output width other than act_num)
+    if (rc != GOPS_OK) return rc;
+    return episode_launch(env, policy, action_table, act_num, E, T, init, out, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

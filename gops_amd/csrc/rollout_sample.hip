@@ -7,7 +7,9 @@
 //      column of the reset pool) into the time-major outputs, contiguous per tile, and the observations into LDS;
 //   2. the hidden layers on v_mfma_f32_16x16x4_f32 and the head's dot products (policy_tile.h, shared with the episode kernel);
 //   3. one lane per instance forms the head in double - DETERM / GAUSS / TANH_GAUSS, gauss_math.h / soft_math.h - from this
-//      step's noise row and stores act and logp, each rounded once;
+//      step's noise row and stores act and logp, each rounded once; with an action table (gops_sample_rollout_dis) the outputs are
+//      action values / logits instead: EPS_GREEDY / CATEGORICAL pick an index from two uniforms, `act` is the index and the env
+//      steps with the table's row (env_act);
 //   4. one lane per instance takes the env step through env_step_one (env_step.h: the function gops_env_step calls) with the
 //      step's output rows as its operands - obs2, rew, done and the next_* info ARE the stored row -, then keeps the books:
 //      t += 1, over = done or t >= max_episode_steps, time_limited, end, and where the row continues from (an LDS flag per row).
@@ -34,6 +36,11 @@ struct SampleParams {
     GopsSamplePool pool;
     const float* noise;
     GopsSampleOut out;
+    // the discrete heads (act_num = 0: none): the table [act_num, A] in device memory, the applied rows [T, N, A]
+    int act_num;
+    double epsilon;
+    const float* table;
+    float* env_act;
 };
 static_assert(sizeof(SampleParams) <= 4096, "kernel arguments are passed by value");
 
@@ -43,7 +50,8 @@ int sample_ref_floats(const GopsEnv& e) {
 }
 
 // The description alone (what gops_sample_workspace_bytes can see): env kind, policy shape, sizes.
-int sample_check(const GopsEnv* env, const GopsMlp* pol, int N, int T) {
+// `act_num` = 0: the continuous heads (output width A or 2A); else the discrete heads' (output width act_num).
+int sample_check(const GopsEnv* env, const GopsMlp* pol, int N, int T, int act_num = 0) {
     if (!env || !pol || N < 1 || T < 1) return GOPS_ERR_BAD_ARG;
     const int k = env->kind;
     const bool data_kind = k == GOPS_ENV_LQ || k == GOPS_ENV_IDPENDULUM || k == GOPS_ENV_CARTPOLE || k == GOPS_ENV_VEH3DOFCONTI || k == GOPS_ENV_VEH2DOF;
@@ -62,7 +70,8 @@ int sample_check(const GopsEnv* env, const GopsMlp* pol, int N, int T) {
     if (env->scale_obs && (O > 8 || env_has_ref_table(k))) return GOPS_ERR_UNSUPPORTED;
     if (pol->n_layers < 2 || pol->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_UNSUPPORTED;
     if (pol->sizes[0] == O + 1) return GOPS_ERR_UNSUPPORTED;   // time-augmented policies (FiniteHorizonPolicy)
-    if (pol->sizes[0] != O || (pol->sizes[pol->n_layers] != A && pol->sizes[pol->n_layers] != 2 * A)) return GOPS_ERR_BAD_ARG;
+    const int n_out = pol->sizes[pol->n_layers];
+    if (pol->sizes[0] != O || (act_num > 0 ? n_out != act_num : (n_out != A && n_out != 2 * A))) return GOPS_ERR_BAD_ARG;
     for (int j = 1; j < pol->n_layers; ++j)
         if (pol->sizes[j] < 16 || (pol->sizes[j] & 15)) return GOPS_ERR_UNSUPPORTED;
     if (pol->hidden_act < GOPS_ACT_LINEAR || pol->hidden_act > GOPS_ACT_TANH) return GOPS_ERR_BAD_ARG;
@@ -129,7 +138,47 @@ __global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p
         // 2. hidden layers
         const float* cur_x = policy_tile_hidden(p.net, lds, xa, xb, lane, wave);
         // 3. head: 16 lanes per instance form the dot products, the group's first lane the action and its log-probability
-        {
+        if (p.act_num > 0) {   // an action table: y = action values (EPS_GREEDY) or logits (CATEGORICAL), two uniforms per row
+            const int m = tid >> 4, part = tid & 15, n = p.act_num;
+            float y[GOPS_DQN_MAX_ACTIONS];
+            policy_tile_values(p.net, lds, cur_x, m, part, n, y);
+            if (part == 0 && m < nvalid) {
+                const size_t row = row0 + e0 + m;
+                const double u0 = (double)p.noise[row * 2], u1 = (double)p.noise[row * 2 + 1];
+                const int greedy = policy_tile_greedy(y, n);
+                int index;
+                double lp = 0.0;
+                if (p.head == GOPS_SAMPLE_EPS_GREEDY) {
+                    const int uniform = max(min((int)(u1 * n), n - 1), 0);
+                    index = u0 < p.epsilon ? uniform : greedy;
+                } else {
+                    double mx = (double)y[0];
+#pragma unroll
+                    for (int a = 1; a < GOPS_DQN_MAX_ACTIONS; ++a) mx = a == greedy ? (double)y[a] : mx;
+                    double z[GOPS_DQN_MAX_ACTIONS], S = 0.0;
+#pragma unroll
+                    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) {
+                        z[a] = a < n ? exp((double)y[a] - mx) : 0.0;
+                        S += z[a];   // (index order; the zeros beyond n change nothing)
+                    }
+                    const double thr = u0 * S;
+                    double cum = 0.0, yi = 0.0;
+                    index = n - 1;
+                    bool found = false;
+#pragma unroll
+                    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) {
+                        cum += z[a];
+                        if (a < n && !found && thr < cum) index = a, found = true;
+                    }
+#pragma unroll
+                    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) yi = a == index ? (double)y[a] : yi;
+                    lp = (yi - mx) - log(S);
+                }
+                p.out.act[row] = (float)index;
+                p.out.logp[row] = (float)lp;
+                for (int a = 0; a < A; ++a) p.env_act[row * A + a] = p.table[index * A + a];   // 0 <= index < act_num on every path
+            }
+        } else {
             const int m = tid >> 4, part = tid & 15;
             float ym[GOPS_MAX_ACT], yl[GOPS_MAX_ACT];
             policy_tile_head(p.net, lds, cur_x, m, part, 0, A, ym);
@@ -167,7 +216,7 @@ __global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p
             const int e = e0 + tid;
             const size_t row = row0 + e;
             GopsStepIO io = {};
-            io.obs = p.out.obs + row0 * O; io.action = p.out.act + row0 * A; io.done = nullptr;
+            io.obs = p.out.obs + row0 * O; io.action = (p.act_num > 0 ? p.env_act : p.out.act) + row0 * A; io.done = nullptr;
             io.next_obs = p.out.obs2 + row0 * O; io.reward = p.out.rew + row0; io.next_done = p.out.done + row0;
             if (sd > 0) {
                 io.state = p.out.state + row0 * sd; io.ref_points = p.out.ref_points + row0 * rf;
@@ -210,27 +259,11 @@ __global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t gops_sample_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t n_envs, int32_t steps) {
-    if (sample_check(env, policy, n_envs, steps) != GOPS_OK) return 0;
-    PolicyTile net;
-    if (policy_tile_plan(*policy, net) == 0) return 0;
-    return GOPS_SAMPLE_WORKSPACE_BYTES;
-}
-
-int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, int32_t n_envs, int32_t steps,
-                        const GopsSampleState* state, const GopsSamplePool* pool, const float* noise, const GopsSampleOut* out,
-                        void* ws, size_t ws_bytes, void* stream) {
-    if (!env || !policy || !desc || !state || !pool || !noise || !out || steps < 1 || n_envs < 1) return GOPS_ERR_BAD_ARG;
-    if (desc->pool_rows < 1 || desc->max_episode_steps < 1) return GOPS_ERR_BAD_ARG;
-    if (desc->head < GOPS_SAMPLE_DETERM || desc->head > GOPS_SAMPLE_TANH_GAUSS) return GOPS_ERR_BAD_ARG;
-    const int rc = sample_check(env, policy, n_envs, steps);
-    if (rc != GOPS_OK) return rc;
-    const int A = env->act_dim, n_out = policy->sizes[policy->n_layers];
-    if (n_out != (desc->head == GOPS_SAMPLE_DETERM ? A : 2 * A)) return GOPS_ERR_BAD_ARG;   // (an odd width for the Gaussian heads included)
+// What both entry points do once their own head checks passed: the pointer checks, the parameters, the launch.
+int sample_launch(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, int head, const GopsSampleDis* dis, int n_envs,
+                  int steps, const GopsSampleState* state, const GopsSamplePool* pool, const float* noise, const GopsSampleOut* out,
+                  void* ws, size_t ws_bytes, void* stream) {
+    const int A = env->act_dim;
     if (!state->obs || !state->t || !state->reset_count || !pool->obs) return GOPS_ERR_BAD_ARG;
     if (!out->obs || !out->act || !out->rew || !out->done || !out->obs2 || !out->logp || !out->time_limited || !out->end) return GOPS_ERR_BAD_ARG;
     if (env_has_ref_table(env->kind)) {
@@ -250,13 +283,61 @@ int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSam
     lq_pad_env(p.env);
     policy_tile_bind(*policy, p.net);
     p.N = n_envs, p.T = steps, p.O = env->obs_dim, p.A = A;
-    p.head = desc->head, p.R = desc->pool_rows, p.max_steps = desc->max_episode_steps;
+    p.head = head, p.R = desc->pool_rows, p.max_steps = desc->max_episode_steps;
     p.noise_std = desc->noise_std, p.min_ls = desc->min_log_std, p.max_ls = desc->max_log_std;
     p.state_dim = sample_state_dim(*env), p.ref_floats = sample_ref_floats(*env);
     p.pdt = pdt_of(*env);
     p.st = *state, p.pool = *pool, p.noise = noise, p.out = *out;
+    if (dis) p.act_num = dis->act_num, p.epsilon = dis->epsilon, p.table = dis->action_table, p.env_act = dis->env_act;
     launch_with_lds(sample_kernel, dim3((unsigned)((n_envs + GOPS_TILE - 1) / GOPS_TILE)), dim3(PT_THREADS), lds, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gops_sample_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t n_envs, int32_t steps) {
+    if (sample_check(env, policy, n_envs, steps) != GOPS_OK) return 0;
+    PolicyTile net;
+    if (policy_tile_plan(*policy, net) == 0) return 0;
+    return GOPS_SAMPLE_WORKSPACE_BYTES;
+}
+
+size_t gops_sample_dis_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t act_num, int32_t n_envs, int32_t steps) {
+    if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS) return 0;
+    if (sample_check(env, policy, n_envs, steps, act_num) != GOPS_OK) return 0;
+    PolicyTile net;
+    if (policy_tile_plan(*policy, net) == 0) return 0;
+    return GOPS_SAMPLE_WORKSPACE_BYTES;
+}
+
+int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, int32_t n_envs, int32_t steps,
+                        const GopsSampleState* state, const GopsSamplePool* pool, const float* noise, const GopsSampleOut* out,
+                        void* ws, size_t ws_bytes, void* stream) {
+    if (!env || !policy || !desc || !state || !pool || !noise || !out || steps < 1 || n_envs < 1) return GOPS_ERR_BAD_ARG;
+    if (desc->pool_rows < 1 || desc->max_episode_steps < 1) return GOPS_ERR_BAD_ARG;
+    if (desc->head < GOPS_SAMPLE_DETERM || desc->head > GOPS_SAMPLE_TANH_GAUSS) return GOPS_ERR_BAD_ARG;
+    const int rc = sample_check(env, policy, n_envs, steps);
+    if (rc != GOPS_OK) return rc;
+    const int A = env->act_dim, n_out = policy->sizes[policy->n_layers];
+    if (n_out != (desc->head == GOPS_SAMPLE_DETERM ? A : 2 * A)) return GOPS_ERR_BAD_ARG;   // (an odd width for the Gaussian heads included)
+    return sample_launch(env, policy, desc, desc->head, nullptr, n_envs, steps, state, pool, noise, out, ws, ws_bytes, stream);
+}
+
+int gops_sample_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, const GopsSampleDis* dis,
+                            int32_t n_envs, int32_t steps, const GopsSampleState* state, const GopsSamplePool* pool, const float* noise,
+                            const GopsSampleOut* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!env || !policy || !desc || !dis || !state || !pool || !noise || !out || steps < 1 || n_envs < 1) return GOPS_ERR_BAD_ARG;
+    if (desc->pool_rows < 1 || desc->max_episode_steps < 1) return GOPS_ERR_BAD_ARG;
+    if (!dis->action_table || !dis->env_act) return GOPS_ERR_BAD_ARG;
+    if (dis->head != GOPS_SAMPLE_EPS_GREEDY && dis->head != GOPS_SAMPLE_CATEGORICAL) return GOPS_ERR_BAD_ARG;
+    if (!(dis->epsilon >= 0.0 && dis->epsilon <= 1.0)) return GOPS_ERR_BAD_ARG;   // (a NaN included)
+    if (dis->head == GOPS_SAMPLE_CATEGORICAL && dis->epsilon != 0.0) return GOPS_ERR_BAD_ARG;
+    if (dis->act_num < 2 || dis->act_num > GOPS_DQN_MAX_ACTIONS) return GOPS_ERR_UNSUPPORTED;
+    const int rc = sample_check(env, policy, n_envs, steps, dis->act_num);   // (BAD_ARG for an output width other than act_num)
+    if (rc != GOPS_OK) return rc;
+    return sample_launch(env, policy, desc, dis->head, dis, n_envs, steps, state, pool, noise, out, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

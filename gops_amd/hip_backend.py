@@ -176,6 +176,14 @@ class GopsSampleOut(C.Structure):
                 + tuple(p + k for k in SAMPLE_INFO_KEYS for p in ("", "next_"))]
 
 
+SAMPLE_EPS_GREEDY, SAMPLE_CATEGORICAL = 3, 4   # include/gops_hip.h: GOPS_SAMPLE_EPS_GREEDY / _CATEGORICAL (gops_sample_rollout_dis)
+
+
+class GopsSampleDis(C.Structure):   # gops_sample_rollout_dis
+    _fields_ = [("action_table", C.c_void_p), ("act_num", C.c_int32), ("head", C.c_int32), ("epsilon", C.c_double),
+                ("env_act", C.c_void_p)]
+
+
 class GopsAcBackup(C.Structure):   # gops_ac_backup
     _fields_ = [("policy", GopsMlp), ("q", GopsMlp * 2), ("n_q", C.c_int32), ("smooth", C.c_int32),
                 ("squash_low", C.c_float * MAX_ACT), ("squash_high", C.c_float * MAX_ACT),
@@ -259,6 +267,11 @@ def _signatures():
         "gops_sample_workspace_bytes": (sz, [env, mlp, i32, i32]),
         "gops_sample_rollout": (rc, [env, mlp, P(GopsSampleDesc), i32, i32, P(GopsSampleState), P(GopsSamplePool), vp, P(GopsSampleOut),
                                      vp, sz, vp]),
+        "gops_sample_dis_workspace_bytes": (sz, [env, mlp, i32, i32, i32]),
+        "gops_sample_rollout_dis": (rc, [env, mlp, P(GopsSampleDesc), P(GopsSampleDis), i32, i32, P(GopsSampleState), P(GopsSamplePool),
+                                         vp, P(GopsSampleOut), vp, sz, vp]),
+        "gops_episode_dis_workspace_bytes": (sz, [env, mlp, i32, i32, i32]),
+        "gops_episode_rollout_dis": (rc, [env, mlp, vp, i32, i32, i32, io, P(GopsEpisodeOut), vp, sz, vp]),
         "gops_lips_workspace_bytes": (sz, [lips, i32]),
         "gops_lips_forward": (rc, [lips, i32, vp, vp, vp, vp, vp, sz, vp]),
         "gops_lips_backward": (rc, [lips, i32, vp, vp, P(GopsLipsGrad), vp, sz, vp]),
@@ -1045,21 +1058,41 @@ class RpiMlpEvaluator(_RpiState):
 class EpisodeRollout:
     """Whole closed-loop evaluation episodes in ONE launch (`gops_episode_rollout`, csrc/rollout_episode.hip): policy, DATA-env step,
     termination, time limit and return of `episodes` episodes over up to `max_steps` steps.  `env` must carry data_env = 1; the policy
-    weights are read in place at every call.  A description the kernel refuses raises (GOPS_ERR_UNSUPPORTED / _BAD_ARG)."""
+    weights are read in place at every call.  A description the kernel refuses raises (GOPS_ERR_UNSUPPORTED / _BAD_ARG).
+    `action_table` [act_num, act_dim] (device tensor): the greedy head over a discrete action set (`gops_episode_rollout_dis`) - the
+    policy's outputs are action values or logits, the env steps with the table's row at their arg-max, trace_act [E, T, 1] is the index."""
 
     def __init__(self, env: GopsEnv, policy: GopsMlp, *, episodes: int, max_steps: int, device: Optional[torch.device] = None,
-                 workspace_bytes: Optional[int] = None):
+                 workspace_bytes: Optional[int] = None, action_table: Optional[torch.Tensor] = None):
         self.env, self.policy, self.episodes, self.max_steps = env, policy, int(episodes), int(max_steps)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
-        nbytes = lib().gops_episode_workspace_bytes(C.byref(env), C.byref(policy), self.episodes, self.max_steps)
+        self.action_table = action_table
+        if action_table is not None:
+            assert action_table.dim() == 2 and action_table.shape[1] == env.act_dim, "action_table must be [act_num, act_dim]"
+            self.act_num = int(action_table.shape[0])
+            nbytes = lib().gops_episode_dis_workspace_bytes(C.byref(env), C.byref(policy), self.act_num, self.episodes, self.max_steps)
+        else:
+            nbytes = lib().gops_episode_workspace_bytes(C.byref(env), C.byref(policy), self.episodes, self.max_steps)
         if workspace_bytes is None:
             if nbytes == 0:   # ask the entry point itself for the reason
-                check(lib().gops_episode_rollout(C.byref(env), C.byref(policy), self.episodes, self.max_steps, None, None, None, 0, None),
-                      "gops_episode_rollout")
-                raise RuntimeError("gops_episode_workspace_bytes: description refused")
+                check(self._call(None, None, None, 0, None), self._name)
+                raise RuntimeError(("gops_episode_workspace_bytes" if action_table is None else "gops_episode_dis_workspace_bytes")
+                                   + ": description refused")
             workspace_bytes = nbytes
         self.workspace = torch.empty(max(int(workspace_bytes), 1), dtype=torch.uint8, device=self.device)
         self._workspace_bytes = int(workspace_bytes)
+
+    @property
+    def _name(self):
+        return "gops_episode_rollout" if self.action_table is None else "gops_episode_rollout_dis"
+
+    def _call(self, io, out, ws, ws_bytes, stream):
+        ref = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        E, T = self.episodes, self.max_steps
+        if self.action_table is None:
+            return lib().gops_episode_rollout(C.byref(self.env), C.byref(self.policy), E, T, ref(io), ref(out), ws, ws_bytes, stream)
+        return lib().gops_episode_rollout_dis(C.byref(self.env), C.byref(self.policy), _ptr(self.action_table), self.act_num, E, T, ref(io),
+                                              ref(out), ws, ws_bytes, stream)
 
     def set_policy(self, policy: GopsMlp):
         self.policy = policy
@@ -1080,11 +1113,11 @@ class EpisodeRollout:
         if trace:
             mk = (lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)) if trace_fill is None else \
                  (lambda *sh: torch.full(sh, float(trace_fill), dtype=torch.float32, device=dev))
-            res.update(trace_obs=mk(E, T, self.env.obs_dim), trace_act=mk(E, T, self.env.act_dim), trace_rew=mk(E, T))
+            res.update(trace_obs=mk(E, T, self.env.obs_dim), trace_act=mk(E, T, self.env.act_dim if self.action_table is None else 1),
+                       trace_rew=mk(E, T))
         for k, v in res.items():
             setattr(out, k, v.data_ptr())
-        check(lib().gops_episode_rollout(C.byref(self.env), C.byref(self.policy), E, T, C.byref(io), C.byref(out),
-                                         self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_episode_rollout")
+        check(self._call(io, out, self.workspace.data_ptr(), self._workspace_bytes, _stream()), self._name)
         return res
 
 
@@ -1092,40 +1125,54 @@ class SampleRollout:
     """A whole `sample()` of the device samplers in ONE launch (`gops_sample_rollout`, csrc/rollout_sample.hip): `steps` steps of
     `n_envs` environment instances - policy, exploration head, env step, stored rows, bookkeeping, resets from the pool.  Holds the
     workspace and the time-major output buffers, allocated once for (n_envs, steps): `run` returns VIEWS of them, which the next
-    `run` overwrites.  The policy weights are read in place at every call.  A description the kernel refuses raises."""
+    `run` overwrites.  The policy weights are read in place at every call.  A description the kernel refuses raises.
+    `action_table` [act_num, act_dim] (device tensor) selects `gops_sample_rollout_dis`: `head` is SAMPLE_EPS_GREEDY or
+    SAMPLE_CATEGORICAL, `noise` is [steps, n_envs, 2] uniforms in [0, 1), `act` is the index [steps, n_envs, 1] and `env_act`
+    [steps, n_envs, act_dim] the table row applied; `dis.epsilon` is read at every `run` (as `desc.max_episode_steps` is)."""
 
     def __init__(self, env: GopsEnv, policy: GopsMlp, *, n_envs: int, steps: int, head: int, max_episode_steps: int, pool_rows: int,
                  noise_std: float = 0.0, min_log_std: float = 0.0, max_log_std: float = 0.0, info_like: Optional[Dict[str, torch.Tensor]] = None,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None, action_table: Optional[torch.Tensor] = None, epsilon: float = 0.0):
         """`info_like`: the info tensors of the persistent state ([n_envs, ...] each; the vehicle families) - their trailing shapes
         are the output columns'."""
         self.env, self.policy, self.n_envs, self.steps = env, policy, int(n_envs), int(steps)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.desc = GopsSampleDesc(head=int(head), max_episode_steps=int(max_episode_steps), pool_rows=int(pool_rows), reserved=0,
                                    noise_std=float(noise_std), min_log_std=float(min_log_std), max_log_std=float(max_log_std))
-        nbytes = lib().gops_sample_workspace_bytes(C.byref(env), C.byref(policy), self.n_envs, self.steps)
+        self.action_table, self.dis = action_table, None
+        if action_table is not None:
+            assert action_table.dim() == 2 and action_table.shape[1] == env.act_dim, "action_table must be [act_num, act_dim]"
+            self.dis = GopsSampleDis(action_table=_ptr(action_table), act_num=int(action_table.shape[0]), head=int(head),
+                                     epsilon=float(epsilon), env_act=None)
+            nbytes = lib().gops_sample_dis_workspace_bytes(C.byref(env), C.byref(policy), self.dis.act_num, self.n_envs, self.steps)
+        else:
+            nbytes = lib().gops_sample_workspace_bytes(C.byref(env), C.byref(policy), self.n_envs, self.steps)
         if nbytes == 0:
-            raise RuntimeError("gops_sample_workspace_bytes: description refused")
+            raise RuntimeError(("gops_sample_workspace_bytes" if self.dis is None else "gops_sample_dis_workspace_bytes") + ": description refused")
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         T, N = self.steps, self.n_envs
         mk = lambda *sh: torch.empty((T, N) + tuple(sh), dtype=torch.float32, device=self.device)   # noqa: E731
-        self.out = dict(obs=mk(env.obs_dim), act=mk(env.act_dim), rew=mk(), done=mk(), obs2=mk(env.obs_dim), logp=mk(),
-                        time_limited=mk(), end=mk())
+        self.noise_width = env.act_dim if self.dis is None else 2
+        self.out = dict(obs=mk(env.obs_dim), act=mk(env.act_dim if self.dis is None else 1), rew=mk(), done=mk(), obs2=mk(env.obs_dim),
+                        logp=mk(), time_limited=mk(), end=mk())
         self.info_keys = tuple(k for k in SAMPLE_INFO_KEYS if info_like and k in info_like)
         for k in self.info_keys:
             self.out[k], self.out["next_" + k] = mk(*info_like[k].shape[1:]), mk(*info_like[k].shape[1:])
         self._out = GopsSampleOut()
         for k, v in self.out.items():
             setattr(self._out, k, v.data_ptr())
+        if self.dis is not None:   # (not a field of GopsSampleOut: the dis struct's own output)
+            self.out["env_act"] = mk(env.act_dim)
+            self.dis.env_act = self.out["env_act"].data_ptr()
 
     def set_policy(self, policy: GopsMlp):
         self.policy = policy
 
     def run(self, state: Dict[str, torch.Tensor], pool: Dict[str, torch.Tensor], noise: torch.Tensor) -> Dict[str, torch.Tensor]:
         """`state`: obs [N, obs_dim], the info tensors, t [N] and reset_count [N] (int32) - advanced IN PLACE; `pool`: obs and the
-        info tensors as [R, N, ...]; `noise` [T, N, act_dim].  Returns the output buffers ([T, N, ...] each).  Enqueues only."""
+        info tensors as [R, N, ...]; `noise` [T, N, act_dim] standard normals ([T, N, 2] uniforms with an action table).  Returns the output buffers ([T, N, ...] each).  Enqueues only."""
         T, N, R = self.steps, self.n_envs, self.desc.pool_rows
-        assert tuple(noise.shape) == (T, N, self.env.act_dim) and state["obs"].shape[0] == N
+        assert tuple(noise.shape) == (T, N, self.noise_width) and state["obs"].shape[0] == N
         st, pl = GopsSampleState(), GopsSamplePool()
         for k in ("obs",) + self.info_keys:
             assert tuple(pool[k].shape) == (R,) + tuple(state[k].shape), k
@@ -1135,6 +1182,11 @@ class SampleRollout:
             v = state[k]
             assert v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.numel() == N, k
             setattr(st, k, v.data_ptr())
+        if self.dis is not None:
+            check(lib().gops_sample_rollout_dis(C.byref(self.env), C.byref(self.policy), C.byref(self.desc), C.byref(self.dis), N, T,
+                                                C.byref(st), C.byref(pl), _ptr(noise), C.byref(self._out), self.workspace.data_ptr(),
+                                                self.workspace.numel(), _stream()), "gops_sample_rollout_dis")
+            return self.out
         check(lib().gops_sample_rollout(C.byref(self.env), C.byref(self.policy), C.byref(self.desc), N, T, C.byref(st), C.byref(pl),
                                         _ptr(noise), C.byref(self._out), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
               "gops_sample_rollout")

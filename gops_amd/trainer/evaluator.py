@@ -13,6 +13,11 @@ What the kernel refuses (POLY policies, pyth_mobilerobot - its obstacle noise is
 through the per-step device loop (so do `ScaleObservation` on the vehicle families and hidden widths the kernel's LDS plan does
 not hold; `Evaluator.path` names the path the last call took and why): torch `policy(obs)` + `gops_env_step(data_env)` per step, a `finished` mask kept on the device
 and read back once at the end.  Env models whose data env is not restated in the step kernel raise.
+
+Discrete action sets: with `action_table` [act_num, action_dim] the evaluated network is an ActionValueDis (DQN's `networks.q`) or a
+StochaPolicyDis (discrete TRPO's `networks.policy`); every step acts with `action_table[argmax(outputs)]` - the `mode()` of both
+ValueDiracDistribution and CategoricalDistribution, the lowest index among equal maxima - through `gops_episode_rollout_dis`, or the
+same arg-max + table gather in the per-step loop; `trace_act` is the index, [E, T, 1].
 """
 import ctypes
 import os
@@ -22,7 +27,7 @@ import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import is_poly
-from gops_amd.apprfunc.mlp import ActionValueDis, StochaPolicy
+from gops_amd.apprfunc.mlp import ActionValueDis, StochaPolicy, StochaPolicyDis
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, NOT_RESTATED, draw_reset_pool
 
 # TimeLimit of the data envs where create_env registers one (gops/create_pkg/create_env.py:142-148 takes the env's own
@@ -45,12 +50,22 @@ class Evaluator:
     on_device = True   # trainers: the evaluator shares the learner's networks, no state_dict copy
 
     def __init__(self, index=0, *, env_model, networks, cfg: dict, num_eval_episode: int, eval_save: bool = True,
-                 save_folder=None, seed: int = 0, max_episode_steps: int = None, device="cuda", fused: bool = True, **kwargs):
+                 save_folder=None, seed: int = 0, max_episode_steps: int = None, device="cuda", fused: bool = True, action_table=None,
+                 **kwargs):
         """cfg: workload dict (env_id, pre_horizon, lq_config) as `DeviceEnvSampler` takes it; env_model: the wrapped model of
         `create_env_model`; networks: the learner's container (its `policy` is evaluated in place).  `max_episode_steps`: None =
-        the data env's registered limit, else 200.  `fused=False` forces the per-step loop."""
+        the data env's registered limit, else 200.  `fused=False` forces the per-step loop.  `action_table` [act_num, action_dim]:
+        evaluate a discrete policy (see the module docstring); without one an ActionValueDis is refused."""
         self.cfg, self.env_model, self.networks = dict(cfg), env_model, networks
-        if isinstance(getattr(networks, "q", None), ActionValueDis):
+        self.device = torch.device(device)
+        self.action_table = None if action_table is None else torch.as_tensor(action_table, dtype=torch.float32).to(self.device).contiguous()
+        if self.action_table is not None:
+            if self.action_table.dim() != 2:
+                raise ValueError("action_table must be [act_num, action_dim]")
+            if not isinstance(self._policy_module(), ActionValueDis) or self._policy_module().act_num != self.action_table.shape[0]:
+                raise ValueError("Evaluator: an action table needs an ActionValueDis `q` or a StochaPolicyDis `policy` with one output per "
+                                 "table row")
+        elif isinstance(getattr(networks, "q", None), ActionValueDis):
             raise NotImplementedError("Evaluator runs closed loops with continuous actions only: an ActionValueDis policy (DQN) emits "
                                       "action values over a discrete action set, and no action table is part of the evaluator")
         base = getattr(env_model, "unwrapped", env_model)
@@ -62,7 +77,6 @@ class Evaluator:
         self.num_eval_episode, self.eval_save, self.save_folder = int(num_eval_episode), bool(eval_save), save_folder
         self.seed = int(seed) + int(index) + 400   # evaluator.py:28
         self.max_episode_steps = int(registered_episode_steps(self.cfg) if max_episode_steps is None else max_episode_steps)
-        self.device = torch.device(device)
         if torch.cuda.is_available() and not next(networks.parameters()).is_cuda:   # (built from kwargs: not the learner's container)
             networks.to(self.device)
         self.fused = bool(fused)
@@ -78,10 +92,18 @@ class Evaluator:
         self.networks.load_state_dict(state_dict)
 
     # ---- descriptions ---------------------------------------------------------------------------
+    def _policy_module(self):
+        """The network that is evaluated: `networks.policy`, or - DQN, whose `policy` is a plain function over it - `networks.q`."""
+        pol = self.networks.policy
+        return pol if isinstance(pol, torch.nn.Module) else getattr(self.networks, "q", pol)
+
     def _hip_env(self):
         if self._henv is None:
-            pol = self.networks.policy
-            env = self.env_model.hip_env(pol.act_low_lim.cpu().numpy(), pol.act_high_lim.cpu().numpy(), data_env=True)
+            if self.action_table is not None:   # no squash: the limits are the table's column extremes, as in DeviceEnvSampler
+                low, high = self.action_table.min(dim=0).values, self.action_table.max(dim=0).values
+            else:
+                low, high = self.networks.policy.act_low_lim, self.networks.policy.act_high_lim
+            env = self.env_model.hip_env(low.cpu().numpy(), high.cpu().numpy(), data_env=True)
             env = hb.GopsEnv.from_buffer_copy(env)   # (the model caches its description: this one is the evaluator's own)
             env.shaping, env.reward_scale, env.reward_shift = 0, 1.0, 0.0
             env.repeat_num, env.repeat_last_reward = 0, 0
@@ -89,8 +111,8 @@ class Evaluator:
         return self._henv
 
     def kernel_refuses(self):
-        """None when `gops_episode_rollout` takes this evaluator's env and policy, else the reason."""
-        pol = self.networks.policy
+        """None when `gops_episode_rollout` (`_dis` with an action table) takes this evaluator's env and policy, else the reason."""
+        pol = self._policy_module()
         if is_poly(pol):
             return "POLY policy"
         if getattr(pol, "is_lipsnet", False):
@@ -100,6 +122,10 @@ class Evaluator:
         env = self._hip_env()
         if env.kind == hb.ENV_MOBILEROBOT:
             return "pyth_mobilerobot draws its obstacle noise per step"
+        if self.action_table is not None:
+            if hb.lib().gops_episode_dis_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), int(self.action_table.shape[0]), 1, 1) == 0:
+                return "env / policy description outside the episode kernel (more than GOPS_DQN_MAX_ACTIONS actions, hidden widths)"
+            return None
         if hb.lib().gops_episode_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), 1, 1) == 0:
             # gops_hip.h lists them: ScaleObservation on the vehicle families or beyond 8 observations, ActionRepeat, hidden widths
             # that are no multiple of 16 or beyond the LDS plan (~1100)
@@ -123,12 +149,12 @@ class Evaluator:
         self.path = "fused" if why is None else "loop: " + why
         if why is None:
             E = init["obs"].shape[0]
-            mlp = self.networks.policy.hip_mlp()
+            mlp = self._policy_module().hip_mlp()
             key = (E, self.max_episode_steps)
             ro = self._rollouts.get(key)
             if ro is None:
                 ro = self._rollouts[key] = hb.EpisodeRollout(self._hip_env(), mlp, episodes=E, max_steps=self.max_episode_steps,
-                                                             device=self.device)
+                                                             device=self.device, action_table=self.action_table)
             ro.set_policy(mlp)
             self.last = ro.run(init, trace=trace, trace_fill=trace_fill)
         else:
@@ -139,7 +165,8 @@ class Evaluator:
     def step_loop(self, init: dict, *, trace: bool = False, trace_fill: float = None, sync_every_step: bool = False) -> dict:
         """The same episodes through the per-step device loop (torch policy + one `gops_env_step` launch per step).  The
         `finished` mask stays on the device; `sync_every_step` adds the host read per step the sampler's bookkeeping has."""
-        env, policy, T = self._hip_env(), self.networks.policy, self.max_episode_steps
+        env, policy, T = self._hip_env(), self._policy_module(), self.max_episode_steps
+        table = self.action_table
         obs, info = init["obs"], {k: init[k] for k in INFO_KEYS if k in init}
         E, dev = obs.shape[0], obs.device
         zeros = torch.zeros(E, device=dev)
@@ -150,17 +177,22 @@ class Evaluator:
         res = {}
         if trace:
             mk = (lambda *sh: torch.empty(*sh, device=dev)) if trace_fill is None else (lambda *sh: torch.full(sh, float(trace_fill), device=dev))
-            res.update(trace_obs=mk(E, T, env.obs_dim), trace_act=mk(E, T, env.act_dim), trace_rew=mk(E, T))
+            res.update(trace_obs=mk(E, T, env.obs_dim), trace_act=mk(E, T, env.act_dim if table is None else 1), trace_rew=mk(E, T))
         for t in range(T):
             act = policy(obs)
-            if isinstance(policy, StochaPolicy):   # evaluation acts with the distribution's mode
+            if table is not None:   # the mode of ValueDirac / Categorical: the arg-max (lowest index among equal maxima), then the table
+                index = torch.argmax(act, dim=-1)
+                act, stored = table[index], index.to(torch.float32).unsqueeze(-1)
+            elif isinstance(policy, StochaPolicy):   # evaluation acts with the distribution's mode
                 act = policy.get_act_dist(act).mode()
             act = act.contiguous()
+            if table is None:
+                stored = act
             obs2, rew, done, info2 = hb.env_step(env, obs, act, zeros, info)
             live = ~finished
             if trace:
                 res["trace_obs"][:, t] = torch.where(live[:, None], obs, res["trace_obs"][:, t])
-                res["trace_act"][:, t] = torch.where(live[:, None], act, res["trace_act"][:, t])
+                res["trace_act"][:, t] = torch.where(live[:, None], stored, res["trace_act"][:, t])
                 res["trace_rew"][:, t] = torch.where(live, rew, res["trace_rew"][:, t])
             ret += torch.where(live, rew.double(), torch.zeros_like(ret))
             length += live.to(torch.int32)

@@ -27,7 +27,7 @@ import warnings
 
 import torch
 
-from gops_amd.apprfunc.mlp import DetermPolicy, StochaPolicy, StochaPolicyDis
+from gops_amd.apprfunc.mlp import ActionValueDis, DetermPolicy, StochaPolicy, StochaPolicyDis
 from gops_amd import hip_backend as hb
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS as _INFO, NOT_RESTATED, draw_reset_pool, pool_needs_refresh
 from gops_amd.utils.act_distribution import GaussDistribution, TanhGaussDistribution
@@ -52,7 +52,12 @@ class DeviceEnvSampler:
         [steps, n_envs, action_dim], the launch, one 4-byte read (the largest reset count, for the pool refresh) - wherever the kernel
         takes the env and the policy; `path` names the path the last call took and, for the loop, why.  The returned tensors are then
         views of buffers the next `sample()` overwrites.  Finished instances restart from their OWN column of the pool
-        (`reset_pool.pool_row`), and the noise stream is the fused path's own: a seeded fused run does not reproduce a seeded loop run."""
+        (`reset_pool.pool_row`), and the noise stream is the fused path's own: a seeded fused run does not reproduce a seeded loop run.
+        With an action table the fused path is `gops_sample_rollout_dis`: head EPS_GREEDY for an ActionValueDis (DQN: the `q` network
+        behind `networks.policy`), with `self.epsilon` read at every call, head CATEGORICAL for a StochaPolicyDis; one `torch.rand` of
+        [steps, n_envs, 2] replaces the loop's argmax / multinomial / rand / randint / where / gather chain, and the index and logp
+        are `reset_pool.restate_discrete_head` of the network's outputs and those uniforms - again a noise stream of its own, so a
+        seeded fused run does not reproduce a seeded loop run.  A table behind any other policy class stays on the loop."""
         self.cfg, self.env_model = dict(cfg), env_model
         if getattr(getattr(env_model, "unwrapped", env_model), "ref_c", None) is not None:
             raise RuntimeError("DeviceEnvSampler draws its reset states from the DEFAULT reference trajectories "
@@ -173,9 +178,19 @@ class DeviceEnvSampler:
     # ---- the fused path ------------------------------------------------------------------------
     def kernel_refuses(self):
         """None when `gops_sample_rollout` takes this sampler's env and policy, else the reason."""
-        policy = self.networks.policy
+        policy = self._policy_module()
         if self.action_table is not None:
-            return "action table (discrete actions)"
+            if not isinstance(policy, ActionValueDis):   # (StochaPolicyDis is one)
+                return "action table (discrete actions) behind a policy that is neither an ActionValueDis nor a StochaPolicyDis"
+            env = self._hip_env()
+            if env.kind == hb.ENV_MOBILEROBOT:
+                return "pyth_mobilerobot draws its obstacle noise per step"
+            if hb.lib().gops_sample_dis_workspace_bytes(ctypes.byref(env), ctypes.byref(policy.hip_mlp()), int(self.action_table.shape[0]),
+                                                        self.n, self.steps) == 0:
+                # gops_hip.h lists them; gym_cartpoleconti with env_step="model" is one: the kernel steps it as a data env only
+                return ("action table: env / policy description outside the sample kernel (an env the kernel steps under the other "
+                        "env_step only, constrained model, ActionRepeat, hidden widths, more than GOPS_DQN_MAX_ACTIONS actions)")
+            return None
         if isinstance(policy, StochaPolicyDis):
             return "categorical policy"
         for flag, name in (("is_poly", "POLY"), ("is_rbf", "GAUSS (RBF)"), ("is_lipsnet", "LipsNet")):
@@ -196,6 +211,11 @@ class DeviceEnvSampler:
             return "env / policy description outside the sample kernel (constrained model, ActionRepeat, hidden widths)"
         return None
 
+    def _policy_module(self):
+        """The network the kernel reads: `networks.policy`, or - DQN, whose `policy` is a plain function over it - `networks.q`."""
+        policy = self.networks.policy
+        return policy if isinstance(policy, torch.nn.Module) else getattr(self.networks, "q", policy)
+
     def _draw_fused_pool(self):
         """`pool_factor` reset states per instance, [R, N, ...]: the same draw as the loop's pool, reshaped; the counts start over."""
         R, N = self.pool_factor, self.n
@@ -206,7 +226,7 @@ class DeviceEnvSampler:
 
     def _sample_fused(self):
         """One launch for all `steps` steps; -> the kernel's time-major output buffers ([T, N, ...] each)."""
-        policy = self.networks.policy
+        policy = self._policy_module()
         T, N, R = self.steps, self.n, self.pool_factor
         st = self._fstate
         if st is None or st["obs"] is not self.obs:   # the first fused call (or the loop ran since): the kernel advances its state in
@@ -218,6 +238,8 @@ class DeviceEnvSampler:
             self._fpool = None
         if self._fpool is None:
             self._draw_fused_pool()
+        if self.action_table is not None:
+            return self._sample_fused_dis(policy, st)
         stochastic = isinstance(policy, StochaPolicy)
         if stochastic and self.noise_std > 0.0 and not self._warned_noise:
             self._warned_noise = True
@@ -233,6 +255,27 @@ class DeviceEnvSampler:
         ro.set_policy(policy.hip_mlp())
         ro.desc.max_episode_steps = int(self.max_steps)
         noise = torch.randn((T, N, self._hip_env().act_dim), generator=self._gen, device=self.device)
+        out = ro.run(st, self._fpool, noise)
+        if pool_needs_refresh(int(st["reset_count"].max().item()), R):   # the one host read of a fused sample()
+            self._draw_fused_pool()
+        return out
+
+    def _sample_fused_dis(self, policy, st):
+        """The discrete heads: one `torch.rand` of [T, N, 2], one `gops_sample_rollout_dis` launch, the 4-byte read."""
+        T, N, R = self.steps, self.n, self.pool_factor
+        categorical = isinstance(policy, StochaPolicyDis)
+        if categorical:
+            self._check_categorical()
+        if self._frollout is None or (self._frollout.n_envs, self._frollout.steps) != (N, T):
+            self._frollout = hb.SampleRollout(self._hip_env(), policy.hip_mlp(), n_envs=N, steps=T,
+                                              head=hb.SAMPLE_CATEGORICAL if categorical else hb.SAMPLE_EPS_GREEDY,
+                                              max_episode_steps=self.max_steps, pool_rows=R, info_like=self.info, device=self.device,
+                                              action_table=self.action_table)
+        ro = self._frollout
+        ro.set_policy(policy.hip_mlp())
+        ro.desc.max_episode_steps = int(self.max_steps)
+        ro.dis.epsilon = float(self.epsilon)
+        noise = torch.rand((T, N, 2), generator=self._gen, device=self.device)
         out = ro.run(st, self._fpool, noise)
         if pool_needs_refresh(int(st["reset_count"].max().item()), R):   # the one host read of a fused sample()
             self._draw_fused_pool()

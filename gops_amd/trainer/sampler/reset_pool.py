@@ -44,6 +44,35 @@ def restate_sample_books(done, t0, reset_count0, max_episode_steps: int, pool_ro
     return dict(time_limited=tlim, end=end, src=src, t=t.astype(np.int32), reset_count=rc.astype(np.int32))
 
 
+HEAD_EPS_GREEDY, HEAD_CATEGORICAL = 3, 4   # include/gops_hip.h: GOPS_SAMPLE_EPS_GREEDY / _CATEGORICAL
+
+
+def restate_discrete_head(values, u, head: int, epsilon: float = 0.0):
+    """The discrete heads of the fused sampler and evaluator (csrc/rollout_sample.hip, gops_sample_rollout_dis) restated on the
+    host in float64: `values` [..., n] the policy's raw outputs, `u` [..., 2] uniforms in [0, 1) -> (index [...] int64, logp [...]).
+    greedy = the LOWEST index attaining max(values).
+      HEAD_EPS_GREEDY:  index = floor(u1 n) (at most n - 1) where u0 < epsilon, else greedy; logp = 0.
+      HEAD_CATEGORICAL: m = max, z_k = exp(values_k - m), S = z_0 + .. + z_{n-1} in index order; index = the smallest k with
+                        u0 S < z_0 + .. + z_k, else n - 1; logp = (values_index - m) - log S: the log-softmax at the index."""
+    y, u = np.asarray(values, dtype=np.float64), np.asarray(u, dtype=np.float64)
+    n = y.shape[-1]
+    greedy = np.argmax(y, axis=-1)   # (numpy: the first occurrence of the maximum)
+    u0, u1 = u[..., 0], u[..., 1]
+    if head == HEAD_EPS_GREEDY:
+        uniform = np.minimum((u1 * n).astype(np.int64), n - 1)
+        return np.where(u0 < epsilon, uniform, greedy).astype(np.int64), np.zeros(greedy.shape)
+    if head != HEAD_CATEGORICAL:
+        raise ValueError("head must be HEAD_EPS_GREEDY or HEAD_CATEGORICAL")
+    if epsilon != 0.0:
+        raise ValueError("the categorical head takes no epsilon")
+    m = np.max(y, axis=-1, keepdims=True)
+    cum = np.cumsum(np.exp(y - m), axis=-1)   # (sequential: index order)
+    S = cum[..., -1]
+    index = np.minimum((~((u0 * S)[..., None] < cum)).sum(axis=-1), n - 1).astype(np.int64)   # cum is non-decreasing
+    logp = (np.take_along_axis(y, index[..., None], axis=-1)[..., 0] - m[..., 0]) - np.log(S)
+    return index, logp
+
+
 def draw_reset_pool(cfg: dict, env_model, seed: int, size: int, device, data_env: bool = True) -> dict:
     """`size` initial conditions (device tensors: obs + the info keys the model carries) of `cfg["env_id"]` for `seed`."""
     host = make_batch(cfg, seed, batch=size)

@@ -697,6 +697,55 @@ int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSam
                         const GopsSampleState* state, const GopsSamplePool* pool, const float* noise, const GopsSampleOut* out,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): the same launch with a DISCRETE action set (DQN, discrete TRPO) -
+ * gops_sample_rollout_dis takes what gops_sample_rollout takes, plus `dis`; state, pool, out, the per-step books and the resets are
+ * gops_sample_rollout's, word for word (one kernel body).  desc->head, noise_std, min_log_std and max_log_std are ignored.
+ *   dis->action_table [act_num, A], device memory, row-major (read only): the action the env is stepped with for each index;
+ *   dis->act_num = n, 2 .. GOPS_DQN_MAX_ACTIONS; the policy's output width must be n;
+ *   dis->env_act [T, N, A] (required output): the table row applied at each step, env_act[t][i] = action_table[index] bit for bit;
+ *   out->act is [T, N, 1] here: the chosen index as a float (what the samplers store for a discrete action);
+ *   noise: [T, N, 2] UNIFORMS in [0, 1), (u0, u1) per row - the kernel still draws nothing: a launch is a pure function of its inputs.
+ *   dis->head, with y [n] the policy's raw outputs (fp32, bias added in fp32) and greedy = the LOWEST index attaining max y - a NaN
+ *   counts as the maximum, the first one wins: gops_dqn_backup's a_star rule, torch.argmax's on finite values:
+ *     GOPS_SAMPLE_EPS_GREEDY   y = action values: explore = (double)u0 < epsilon, uniform = min((int)((double)u1 * n), n - 1),
+ *                              index = explore ? uniform : greedy, logp = 0;
+ *     GOPS_SAMPLE_CATEGORICAL  y = logits, formed in double: m = y[greedy], z_k = exp(y_k - m), S = z_0 + .. + z_{n-1} in index
+ *                              order; index = the smallest k with u0 * S < z_0 + .. + z_k, else n - 1;
+ *                              logp = (y_index - m) - log S, rounded once (the log-softmax at the index); epsilon must be 0.
+ *     No tanh squash, no act limits: the env lane steps with env_act as gops_env_step's `action`.
+ * Accepted: the env kinds and policies of gops_sample_rollout with sizes[n_layers] = n.  GOPS_ERR_UNSUPPORTED, nothing launched:
+ * act_num outside 2 .. GOPS_DQN_MAX_ACTIONS and whatever gops_sample_rollout returns it for.  GOPS_ERR_BAD_ARG, nothing launched: a
+ * NULL action_table or env_act, an unknown head (the continuous heads included), an output width other than act_num, epsilon
+ * outside [0, 1] (a NaN included), a nonzero epsilon with GOPS_SAMPLE_CATEGORICAL, and gops_sample_rollout's own cases.
+ * GOPS_ERR_WORKSPACE as for gops_sample_rollout.  gops_sample_rollout itself keeps rejecting every head above
+ * GOPS_SAMPLE_TANH_GAUSS.  gops_sample_dis_workspace_bytes: 0 for a description gops_sample_rollout_dis rejects. */
+#define GOPS_SAMPLE_EPS_GREEDY 3
+#define GOPS_SAMPLE_CATEGORICAL 4
+struct GopsSampleDis {
+    const float* action_table;
+    int32_t act_num, head;
+    double epsilon;
+    float* env_act;
+};
+typedef struct GopsSampleDis GopsSampleDis;
+size_t gops_sample_dis_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t act_num, int32_t n_envs, int32_t steps);
+int gops_sample_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, const GopsSampleDis* dis,
+                            int32_t n_envs, int32_t steps, const GopsSampleState* state, const GopsSamplePool* pool, const float* noise,
+                            const GopsSampleOut* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The greedy head of the evaluator over a DISCRETE action set: gops_episode_rollout with a_t = action_table[greedy(y)], y [act_num]
+ * the policy's raw outputs and `greedy` as above - the mode() of ValueDiracDistribution (an ActionValueDis' values) and of
+ * CategoricalDistribution (a StochaPolicyDis' logits), which the reference evaluator acts with.  No tanh squash, no act limits.
+ * action_table [act_num, A] in device memory (read only); trace_act is [E][max_steps][1]: the index as a float.  Everything else -
+ * init, out, the env kinds, the policies (sizes[n_layers] = act_num), the workspace - as gops_episode_rollout.
+ * GOPS_ERR_UNSUPPORTED: act_num outside 2 .. GOPS_DQN_MAX_ACTIONS and gops_episode_rollout's cases; GOPS_ERR_BAD_ARG: a NULL
+ * action_table, an output width other than act_num and gops_episode_rollout's cases.  Nothing is launched on a refusal.
+ * gops_episode_dis_workspace_bytes: 0 for a description gops_episode_rollout_dis rejects. */
+size_t gops_episode_dis_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t act_num, int32_t episodes, int32_t max_steps);
+int gops_episode_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const float* action_table, int32_t act_num, int32_t episodes,
+                             int32_t max_steps, const GopsStepIO* init, const GopsEpisodeOut* out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ABI v15, additive entry points (the version number stays 15): LipsNet policies (gops/apprfunc/lipsnet.py DetermPolicy) - an MLP f
  * evaluated together with its input Jacobian J = df/dx and differentiated through it (csrc/rollout_lips.hip):
  *     y = K(x) f(x) / (||J||_F + eps),   action = y   or, with `squash`,   (high - low) / 2 tanh(y) + (high + low) / 2,
