@@ -1,4 +1,5 @@
-// Batched box-constrained L-BFGS for shooting MPC (gops_mpc_state_bytes / _init / _step / _finish / _advance of include/gops_hip.h): B independent
+// Batched box-constrained L-BFGS for shooting MPC (gops_mpc_state_bytes / _init / _step / _finish / _advance and the block-writing halves of the
+// augmented Lagrangian, gops_mpc_al_update / _al_advance, of include/gops_hip.h): B independent
 // problems of n variables, each moved by one call of gops_mpc_step per cost-and-gradient evaluation, with no value read on the host.
 //
 // Work assignment: a sub-group of W lanes owns one problem - W = 64 (one wave per problem) for n > 64, else the smallest of
@@ -388,6 +389,72 @@ __global__ __launch_bounds__(MPC_THREADS) void mpc_advance_kernel(void* state, i
     }
 }
 
+// The outer step of the augmented Lagrangian (gops_mpc_al_update): it writes the solver block (the re-arm), so it sits here with the
+// block's layout.  Term j = t n_c + k of row r: c[(t B + r) n_c + k], lambda[r J + j], J = H n_c; lane l of the row's sub-group
+// owns the terms l, l + W, ..  Every lane reads the row's scalars before lane 0 writes them (one wave, program order).
+enum { AH_RHO0, AH_GROWTH, AH_RHO_MAX, AH_SHRINK_TARGET, AH_CSTR_TOL, AH_MAX_OUTER, AH_LAMBDA_TOL };
+enum { AO_STATUS, AO_ITER, AO_EVAL };
+static_assert(AH_LAMBDA_TOL < GOPS_MPC_AL_HYPER_FLOATS && AO_EVAL < GOPS_MPC_AL_COUNTERS, "the tables of gops_mpc_al_update in gops_hip.h");
+
+template <int W>
+__global__ __launch_bounds__(MPC_THREADS) void mpc_al_update_kernel(void* state, int B, int n, int m, int H, int nc, const float* __restrict__ c,
+                                                                    float* __restrict__ lambda, float* __restrict__ rho,
+                                                                    const float* __restrict__ viol, float* __restrict__ viol_prev,
+                                                                    int32_t* __restrict__ outer, const float* __restrict__ hyper) {
+    Problem<W> p;
+    size_t r;
+    if (!mpc_problem(p, state, B, n, m, r)) return;
+    const int inner = p.ct[CT_STATUS];
+    int32_t* ao = outer + r * GOPS_MPC_AL_COUNTERS;
+    if ((inner != GOPS_MPC_CONVERGED_PG && inner != GOPS_MPC_CONVERGED_F && inner != GOPS_MPC_LINE_SEARCH) || ao[AO_STATUS] != GOPS_MPC_AL_RUNNING)
+        return;
+    const int J = H * nc;
+    const double rh = (double)rho[r], vio = (double)viol[r], vprev = (double)viol_prev[r];
+    const int iters = ao[AO_ITER] + 1, evals = p.ct[CT_EVAL];
+    double change = 0.0;
+    for (int j = p.lane; j < J; j += W) {
+        const int t = j / nc, k = j - t * nc;
+        const float lam = lambda[r * J + j];
+        const float ln = (float)fmax(0.0, (double)lam + rh * (double)c[((size_t)t * B + r) * nc + k]);
+        change = fmax(change, fabs((double)ln - (double)lam));
+        lambda[r * J + j] = ln;
+    }
+    change = sub_max<W>(change);
+    if (p.lane != 0) return;
+    if (!(vio <= (double)hyper[AH_SHRINK_TARGET] * vprev)) rho[r] = (float)fmin(rh * (double)hyper[AH_GROWTH], (double)hyper[AH_RHO_MAX]);
+    viol_prev[r] = (float)vio;
+    ao[AO_ITER] = iters;
+    if (vio <= (double)hyper[AH_CSTR_TOL] && change <= (double)hyper[AH_LAMBDA_TOL] * rh) {
+        ao[AO_STATUS] = GOPS_MPC_AL_CONVERGED;
+    } else if (iters >= (int)hyper[AH_MAX_OUTER]) {
+        ao[AO_STATUS] = GOPS_MPC_AL_MAX_OUTER;
+    } else {   // re-arm: x stays; the pairs and f_prev belong to the old objective; evaluations = 0 makes the next step accept x untested
+        ao[AO_EVAL] += evals;
+        p.sc[SC_F_PREV] = 0.0;
+        p.ct[CT_STATUS] = GOPS_MPC_RUNNING, p.ct[CT_EVAL] = 0, p.ct[CT_LS] = 0, p.ct[CT_HEAD] = 0, p.ct[CT_COUNT] = 0;
+    }
+}
+
+// The multiplier side of the hand-over (gops_mpc_al_advance), launched behind mpc_advance_kernel: out of place, so no lane reads what
+// another has written.  Frozen rows are copied.
+template <int W>
+__global__ __launch_bounds__(MPC_THREADS) void mpc_al_shift_kernel(int B, int n, int J, int S, const float* __restrict__ frozen,
+                                                                   int32_t* __restrict__ record, const float* __restrict__ lambda_in,
+                                                                   float* __restrict__ lambda_out, float* __restrict__ rho,
+                                                                   float* __restrict__ viol_prev, int32_t* __restrict__ outer,
+                                                                   const float* __restrict__ hyper) {
+    const size_t r = (size_t)blockIdx.x * (MPC_THREADS / W) + threadIdx.x / W;
+    if (r >= (size_t)B) return;
+    const int lane = threadIdx.x % W;
+    const bool fz = frozen[r] != 0.f;
+    for (int j = lane; j < J; j += W) lambda_out[r * J + j] = fz ? lambda_in[r * J + j] : (j + S < J ? lambda_in[r * J + j + S] : 0.f);
+    if (lane != 0 || fz) return;
+    int32_t* ao = outer + r * GOPS_MPC_AL_COUNTERS;
+    record[r * 4 + 2] += ao[AO_EVAL];   // the evaluations the re-arms took out of the block's counter
+    for (int k = 0; k < GOPS_MPC_AL_COUNTERS; ++k) ao[k] = 0;
+    rho[r] = hyper[AH_RHO0], viol_prev[r] = INFINITY;
+}
+
 int mpc_width(int n) { return n > 64 ? 64 : n > 32 ? 32 : n > 16 ? 16 : n > 8 ? 8 : 4; }
 
 // calls f.template operator()<W>() for the sub-group width of n
@@ -460,6 +527,37 @@ int gops_mpc_advance(void* state, size_t state_bytes, int32_t B, int32_t n, int3
     hipStream_t s = static_cast<hipStream_t>(stream);
     mpc_dispatch(n, [&]<int W>() {
         hipLaunchKernelGGL(mpc_advance_kernel<W>, mpc_grid(B, n), dim3(MPC_THREADS), 0, s, state, B, n, m, act_dim, frozen, action, record, x_trial);
+    });
+    return (int)hipGetLastError();
+}
+
+int gops_mpc_al_update(void* state, size_t state_bytes, int32_t B, int32_t n, int32_t m, int32_t H, int32_t n_c, const float* c, float* lambda,
+                       float* rho, const float* viol, float* viol_prev, int32_t* outer, const float* al_hyper, void* stream) {
+    if (!state || !c || !lambda || !rho || !viol || !viol_prev || !outer || !al_hyper || B < 1 || n < 1 || n > GOPS_MPC_MAX_DIM || m < 1 ||
+        m > GOPS_MPC_MAX_HISTORY || H < 1 || H > GOPS_MPC_AL_MAX_H || n_c < 1 || n_c > GOPS_MAX_CONSTRAINT || (reinterpret_cast<uintptr_t>(state) & 7) ||
+        state_bytes != mpc_bytes(B, n, m))
+        return GOPS_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    mpc_dispatch(n, [&]<int W>() {
+        hipLaunchKernelGGL(mpc_al_update_kernel<W>, mpc_grid(B, n), dim3(MPC_THREADS), 0, s, state, B, n, m, H, n_c, c, lambda, rho, viol, viol_prev,
+                           outer, al_hyper);
+    });
+    return (int)hipGetLastError();
+}
+
+int gops_mpc_al_advance(void* state, size_t state_bytes, int32_t B, int32_t n, int32_t m, int32_t act_dim, const float* frozen, float* action,
+                        int32_t* record, float* x_trial, int32_t H, int32_t n_c, int32_t shift, const float* lambda_in, float* lambda_out,
+                        float* rho, float* viol_prev, int32_t* outer, const float* al_hyper, void* stream) {
+    if (!lambda_in || !lambda_out || lambda_in == lambda_out || !rho || !viol_prev || !outer || !al_hyper || H < 1 || H > GOPS_MPC_AL_MAX_H || n_c < 1 ||
+        n_c > GOPS_MAX_CONSTRAINT || shift < 1)
+        return GOPS_ERR_BAD_ARG;
+    const int rc = gops_mpc_advance(state, state_bytes, B, n, m, act_dim, frozen, action, record, x_trial, stream);
+    if (rc != GOPS_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int J = H * n_c, S = shift < H ? shift * n_c : J;
+    mpc_dispatch(n, [&]<int W>() {
+        hipLaunchKernelGGL(mpc_al_shift_kernel<W>, mpc_grid(B, n), dim3(MPC_THREADS), 0, s, B, n, J, S, frozen, record, lambda_in, lambda_out, rho,
+                           viol_prev, outer, al_hyper);
     });
     return (int)hipGetLastError();
 }

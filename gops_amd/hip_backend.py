@@ -6,7 +6,7 @@ if the shared library is missing, or a shape is unsupported, the call raises.
 """
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -301,6 +301,9 @@ def _signatures():
         "gops_mpc_step": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gops_mpc_finish": (rc, [vp, sz, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gops_mpc_advance": (rc, [vp, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "gops_mpc_al_eval": (rc, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gops_mpc_al_update": (rc, [vp, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gops_mpc_al_advance": (rc, [vp, sz, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "gops_dqn_backup_workspace_bytes": (sz, [P(GopsDqnBackup), i32]),
         "gops_dqn_backup": (rc, [P(GopsDqnBackup), i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gops_dqn_loss": (rc, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
@@ -2022,15 +2025,24 @@ MPC_FROZEN = 5   # gops_mpc_advance: the row's episode has ended
 MPC_STATUS_NAMES = ("running", "converged_pg", "converged_f", "line_search", "nonfinite", "frozen")
 # c1, shrink, max_ls, pgtol, ftol (scipy's L-BFGS-B: pgtol 1e-5, ftol = factr epsmch = 1e7 * 2.22e-16), curv_eps (its epsmch)
 MPC_HYPER_DEFAULTS = dict(c1=1e-4, shrink=0.5, max_ls=20, pgtol=1e-5, ftol=2.220446049250313e-9, curv_eps=2.220446049250313e-16)
+# gops_mpc_al_* (GOPS_MPC_AL_*): the outer status words and the augmented Lagrangian's hyper-parameters
+MPC_AL_HYPER_FLOATS, MPC_AL_COUNTERS, MPC_AL_MAX_H, MAX_CONSTRAINT = 8, 4, 65536, 3
+MPC_AL_RUNNING, MPC_AL_CONVERGED, MPC_AL_MAX_OUTER = range(3)
+MPC_AL_STATUS_NAMES = ("running", "converged", "max_outer")
+MPC_AL_HYPER_DEFAULTS = dict(rho0=10.0, growth=10.0, rho_max=1e6, shrink_target=0.25, cstr_tol=1e-4, max_outer=30, lambda_tol=1e-4)
 
 
 class MpcSolver:
     """`batch` box-constrained L-BFGS problems of `n` variables side by side on the device (`gops_mpc_init / _step / _finish`,
     csrc/mpc_lbfgs.hip): owns the state block, `x_trial [batch, n]` (where the caller evaluates), `f [batch]` and `g [batch, n]`
     (where the caller leaves cost and gradient before `step`) and `hyper` (device: tolerances, `set_hyper`).  Nothing is read on the
-    host except by `finish` / `state`."""
+    host except by `finish` / `state`.
 
-    def __init__(self, batch: int, n: int, lo, hi, device, history: int = 8):
+    `constraints=(H, n_c)`: the solver also owns the augmented-Lagrangian state of H n_c path constraints per row (`gops_mpc_al_eval /
+    _update / _advance`): `lam [batch, H, n_c]`, `rho`, `viol`, `viol_prev`, `f_al_in [batch]` (where the caller leaves the ROLLOUT
+    cost before `al_eval`, which writes the objective into `f`), `seed [H, batch, n_c]`, `outer [batch, 4]` int32 and `al_hyper`."""
+
+    def __init__(self, batch: int, n: int, lo, hi, device, history: int = 8, constraints: Optional[Tuple[int, int]] = None):
         self.batch, self.n, self.m = int(batch), int(n), int(history)
         nbytes = lib().gops_mpc_state_bytes(self.batch, self.n, self.m)
         if nbytes == 0:
@@ -2049,6 +2061,67 @@ class MpcSolver:
         self.iterations = torch.zeros(self.batch, dtype=torch.int32, device=device)
         self.hyper = torch.zeros(MPC_HYPER_FLOATS, dtype=torch.float32, device=device)
         self.set_hyper()
+        self.constraints = None
+        if constraints is not None:
+            H, nc = (int(v) for v in constraints)
+            if not (1 <= H <= MPC_AL_MAX_H and 1 <= nc <= MAX_CONSTRAINT):
+                raise RuntimeError(f"MpcSolver: constraints {constraints} is outside 1 <= H <= {MPC_AL_MAX_H}, 1 <= n_c <= {MAX_CONSTRAINT}")
+            self.constraints = (H, nc)
+            f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)
+            self.lam, self._lam_next, self.seed = f32(self.batch, H, nc), f32(self.batch, H, nc), f32(H, self.batch, nc)
+            self.rho, self.viol, self.viol_prev, self.f_al_in = (f32(self.batch) for _ in range(4))
+            self.outer = torch.zeros(self.batch, MPC_AL_COUNTERS, dtype=torch.int32, device=device)
+            self.al_hyper = f32(MPC_AL_HYPER_FLOATS)
+            self.al_hyper_host = dict(MPC_AL_HYPER_DEFAULTS)
+            self.set_al_hyper()
+            self.al_reset()
+
+    def set_al_hyper(self, **kw):
+        """rho0, growth, rho_max, shrink_target, cstr_tol, max_outer, lambda_tol (MPC_AL_HYPER_DEFAULTS for the ones not given): one
+        small host-to-device copy.  `al_reset` / `al_advance` put rho back to rho0."""
+        unknown = set(kw) - set(MPC_AL_HYPER_DEFAULTS)
+        if unknown:
+            raise RuntimeError(f"MpcSolver.set_al_hyper: unknown {sorted(unknown)}")
+        h = dict(MPC_AL_HYPER_DEFAULTS, **kw)
+        self.al_hyper_host = h
+        vals = [h[k] for k in ("rho0", "growth", "rho_max", "shrink_target", "cstr_tol", "max_outer", "lambda_tol")] + [0.0]
+        self.al_hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+
+    def al_reset(self):
+        """Multipliers 0, rho = rho0, viol_prev = +inf, outer words cleared: the start of a solve (element-wise fills, no host read)."""
+        self.lam.zero_(), self.viol.zero_(), self.outer.zero_()
+        self.rho.fill_(float(self.al_hyper_host["rho0"])), self.viol_prev.fill_(float("inf"))
+
+    def _al_dims(self):
+        assert self.constraints is not None, "MpcSolver was made without constraints=(H, n_c)"
+        return self.constraints
+
+    def al_eval(self, c: torch.Tensor):
+        """`f`, `seed`, `viol` <- the augmented Lagrangian of the rollout cost in `f_al_in` and the constraint values c [H, batch, n_c]
+        at the trial point (gops_mpc_al_eval): call between the rollout forward and its backward, then `step`."""
+        H, nc = self._al_dims()
+        assert c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == (H, self.batch, nc)
+        check(lib().gops_mpc_al_eval(self.batch, H, nc, _ptr(c), _ptr(self.lam), _ptr(self.rho), _ptr(self.f_al_in), _ptr(self.f),
+                                     _ptr(self.seed), _ptr(self.viol), _stream()), "gops_mpc_al_eval")
+
+    def al_update(self, c: torch.Tensor):
+        """The outer step (gops_mpc_al_update) with c [H, batch, n_c] and `viol` those of the rows' ACCEPTED points: rows whose inner
+        solve has ended get their multipliers and rho updated and are re-armed, converged or out of outer iterations."""
+        H, nc = self._al_dims()
+        assert c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == (H, self.batch, nc)
+        check(lib().gops_mpc_al_update(*self._args(), H, nc, _ptr(c), _ptr(self.lam), _ptr(self.rho), _ptr(self.viol), _ptr(self.viol_prev),
+                                       self.outer.data_ptr(), _ptr(self.al_hyper), _stream()), "gops_mpc_al_update")
+
+    def al_advance(self, frozen: torch.Tensor, action_out: torch.Tensor, record: torch.Tensor, shift: int = 1):
+        """`advance` plus the multipliers' hand-over (gops_mpc_al_advance): shifted by `shift` env steps (one control interval) with
+        zeros entering at the end, rho back to rho0, outer words cleared; frozen rows keep theirs."""
+        H, nc = self._al_dims()
+        assert frozen.dtype == torch.float32 and frozen.numel() == self.batch and record.dtype == torch.int32 and record.numel() == 4 * self.batch
+        assert action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.numel() % self.batch == 0
+        check(lib().gops_mpc_al_advance(*self._args(), action_out.numel() // self.batch, _ptr(frozen), _ptr(action_out), record.data_ptr(),
+                                        _ptr(self.x_trial), H, nc, int(shift), _ptr(self.lam), _ptr(self._lam_next), _ptr(self.rho),
+                                        _ptr(self.viol_prev), self.outer.data_ptr(), _ptr(self.al_hyper), _stream()), "gops_mpc_al_advance")
+        self.lam, self._lam_next = self._lam_next, self.lam
 
     def set_hyper(self, **kw):
         """c1, shrink, max_ls, pgtol, ftol, curv_eps (MPC_HYPER_DEFAULTS for the ones not given): one small host-to-device copy."""
@@ -2070,9 +2143,13 @@ class MpcSolver:
               "gops_mpc_step")
 
     def finish(self):
-        """-> (x [batch, n], f [batch], status [batch] int32, iterations [batch] int32): the accepted points, on the device."""
+        """-> (x [batch, n], f [batch], status [batch] int32, iterations [batch] int32): the accepted points, on the device; with
+        `constraints` additionally (viol [batch], outer status [batch] int32 (MPC_AL_*), outer iterations [batch] int32) - the
+        violation of the last `al_eval`, views of `outer`."""
         check(lib().gops_mpc_finish(*self._args(), _ptr(self.x), _ptr(self.f_best), self.status.data_ptr(), self.iterations.data_ptr(),
                                     _stream()), "gops_mpc_finish")
+        if self.constraints is not None:
+            return self.x, self.f_best, self.status, self.iterations, self.viol, self.outer[:, 0], self.outer[:, 1]
         return self.x, self.f_best, self.status, self.iterations
 
     def advance(self, frozen: torch.Tensor, action_out: torch.Tensor, record: torch.Tensor):

@@ -1262,6 +1262,53 @@ int gops_mpc_finish(void* state, size_t state_bytes, int32_t batch, int32_t n, i
 int gops_mpc_advance(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, int32_t act_dim, const float* frozen,
                      float* action, int32_t* record, float* x_trial, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): path constraints c_tk(x) <= 0 of the batched shooting MPC by an
+ * augmented Lagrangian around gops_mpc_step, per row and with no host read.  With t = 0 .. H - 1 the steps whose constraint value
+ * depends on the plan and k = 0 .. n_c - 1, the inner problem the L-BFGS minimises between two multiplier updates is
+ *     f_al(x) = f(x) + (1 / (2 rho)) sum_{t,k} (max(0, lambda_tk + rho c_tk(x))^2 - lambda_tk^2)        (Rockafellar's form),
+ * whose gradient is that of f plus the constraint Jacobian applied to the seed max(0, lambda_tk + rho c_tk).
+ * Layouts: c and seed [H, batch, n_c] (GopsRolloutOut.constraints / GopsRolloutIn.grad_constraint_step), lambda [batch, H, n_c]
+ * (a row's multipliers contiguous), rho, viol, viol_prev, f, f_al [batch], outer [batch][GOPS_MPC_AL_COUNTERS] int32:
+ * {outer status (GOPS_MPC_AL_*), outer iterations, evaluations of the inner solves already re-armed, 0}.
+ * al_hyper: DEVICE memory, GOPS_MPC_AL_HYPER_FLOATS floats {rho0, growth, rho_max, shrink_target, cstr_tol, max_outer, lambda_tol, 0}.
+ *
+ * gops_mpc_al_eval (csrc/mpc_constraint.hip), one launch: f_al, seed and viol = max_{t,k} max(0, c_tk) of every row from c, lambda,
+ *   rho and the rollout cost f (f_al must not be f).  One wave per row: lane l adds the terms j = t n_c + k = l, l + 64, .. in index
+ *   order in double, then an xor butterfly - a fixed order that depends on neither batch nor the row.  A c that is not finite makes
+ *   f_al NaN (gops_mpc_step then reports GOPS_MPC_NONFINITE); the seed of a NaN c is NaN; viol passes over a NaN.
+ *   GOPS_ERR_BAD_ARG: a NULL pointer, batch < 1, H outside 1 .. GOPS_MPC_AL_MAX_H, n_c outside 1 .. GOPS_MAX_CONSTRAINT - before any
+ *   HIP call.
+ * gops_mpc_al_update (csrc/mpc_lbfgs.hip), one launch: the outer step.  c, viol: those of the row's ACCEPTED point.  Only a row whose
+ *   inner status is GOPS_MPC_CONVERGED_PG, _CONVERGED_F or _LINE_SEARCH and whose outer status is GOPS_MPC_AL_RUNNING is touched
+ *   (GOPS_MPC_RUNNING, _NONFINITE and _FROZEN rows are left alone):
+ *     lambda_tk <- max(0, lambda_tk + rho c_tk) (formed in double, rounded once); change = max_{t,k} |new - old|;
+ *     unless viol <= shrink_target viol_prev: rho <- min(rho growth, rho_max);   viol_prev <- viol;   outer iterations += 1;
+ *     viol <= cstr_tol and change <= lambda_tol rho (rho before its growth; change / rho = max |max(c_tk, - lambda_tk / rho)|, the
+ *       complementarity measure in the units of c): outer status GOPS_MPC_AL_CONVERGED;
+ *     else outer iterations == max_outer: GOPS_MPC_AL_MAX_OUTER;
+ *     else the row's L-BFGS block is re-armed for the new objective: status GOPS_MPC_RUNNING, ring count, ring head, line-search
+ *       count and f_prev cleared (pairs and costs of the old objective are stale), the block's evaluations moved into outer[2] and
+ *       cleared - so the next gops_mpc_step accepts x with its new cost and gradient untested, as after gops_mpc_init; x, iterations kept.
+ *   GOPS_ERR_BAD_ARG: a NULL pointer, batch < 1, n outside 1 .. GOPS_MPC_MAX_DIM, m outside 1 .. GOPS_MPC_MAX_HISTORY, H outside
+ *   1 .. GOPS_MPC_AL_MAX_H, n_c outside 1 .. GOPS_MAX_CONSTRAINT, a state block that is not 8-byte aligned, state_bytes !=
+ *   gops_mpc_state_bytes(batch, n, m) - before any HIP call.
+ * gops_mpc_al_advance (csrc/mpc_lbfgs.hip), two launches: gops_mpc_advance with its arguments and refusals, then per row that is not
+ *   frozen: lambda_out_t = lambda_in_{t + shift} (t + shift < H), 0 from there on (shift = env steps of one control interval);
+ *   record[2] += outer[2]; rho = rho0; viol_prev = +inf; outer cleared.  Frozen rows: lambda_out = lambda_in, nothing else written.
+ *   Out of place: lambda_in != lambda_out.  GOPS_ERR_BAD_ARG additionally: a NULL pointer, lambda_in == lambda_out, H or n_c as
+ *   above, shift < 1 - before any HIP call. */
+#define GOPS_MPC_AL_HYPER_FLOATS 8
+#define GOPS_MPC_AL_COUNTERS 4
+#define GOPS_MPC_AL_MAX_H 65536
+enum { GOPS_MPC_AL_RUNNING = 0, GOPS_MPC_AL_CONVERGED = 1, GOPS_MPC_AL_MAX_OUTER = 2 };
+int gops_mpc_al_eval(int32_t batch, int32_t H, int32_t n_c, const float* c, const float* lambda, const float* rho, const float* f,
+                     float* f_al, float* seed, float* viol, void* stream);
+int gops_mpc_al_update(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, int32_t H, int32_t n_c, const float* c,
+                       float* lambda, float* rho, const float* viol, float* viol_prev, int32_t* outer, const float* al_hyper, void* stream);
+int gops_mpc_al_advance(void* state, size_t state_bytes, int32_t batch, int32_t n, int32_t m, int32_t act_dim, const float* frozen,
+                        float* action, int32_t* record, float* x_trial, int32_t H, int32_t n_c, int32_t shift, const float* lambda_in,
+                        float* lambda_out, float* rho, float* viol_prev, int32_t* outer, const float* al_hyper, void* stream);
+
 /* Timing hook for bench.py: average duration in ms of the named internal kernel over the
  * launches recorded since the last reset (HIP events on the launch stream).  kernel ids:
  * 0 = forward rollout, 1 = backward sweep, 2 = weight-gradient GEMMs (+ reduce) of gops_rollout_*;
