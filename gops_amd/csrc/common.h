@@ -416,7 +416,8 @@ __device__ __forceinline__ void wave_sum(float v, float* red, int slot, int nslo
 #define SELU_ALPHA 1.6732632423543772848170429916717f
 
 // gelu(z) and gelu'(z) from ONE exponential: Phi(-|z|) = erfc(|z| / sqrt 2) / 2 by Abramowitz-Stegun 7.1.26
-// (|error| <= 1.5e-7 on erfc: fp32 round-off class, far inside the 1e-4 parity bar) and
+// (the formula's own |error| <= 1.5e-7 on erfc; evaluated in fp32 as below, measured against float64: 2.7e-7 on Phi, 4.2e-7 on gelu for
+// |z| <= 12, 3.0e-7 on gelu' - DESIGN.md section 2.2e, tests/test_activations_*.py; far inside the 1e-4 parity bar) and
 // phi(z) = exp(-z^2/2) / sqrt(2 pi) with the same exponential.  ~17 branch-free VALU ops for both values (libm's
 // erff + expf are ~100 with divergent branches, and were the largest VALU item of the GELU workloads).  The forward
 // epilogue stashes gelu'(z) in the Z tensor, so the backward sweep evaluates no transcendental at all.
@@ -436,7 +437,7 @@ __device__ __forceinline__ void gelu_pair(float z, float& h, float& dh) {
 
 // The same pair for the HALF-precision kernels (results are rounded to 2^-11 anyway): Phi(-|z|) = exp(-z^2/2) P7(|z|) with P7 the
 // degree-7 least-squares fit of the Mills ratio Phi(-x) / exp(-x^2/2) on [0, 6] under the weight exp(-x^2/2) (|error| <= 1.6e-5
-// on Phi, 1.2e-5 on gelu, evaluated in fp32 Horner form; numpy: chebvander + lstsq, converted to monomials).  No reciprocal:
+// on Phi and on gelu', 1.2e-5 on gelu, evaluated in fp32 Horner form - measured 1.52e-5 / 1.52e-5 / 1.18e-5; numpy: chebvander + lstsq, converted to monomials).  No reciprocal:
 // one v_exp_f32 + 17 full-rate instructions, ~21 issue slots against ~26 - the forward of the 64-row half kernels is bound
 // by exactly this arithmetic.
 __device__ __forceinline__ void gelu_pair_h(float z, float& h, float& dh) {
@@ -456,7 +457,8 @@ __device__ __forceinline__ void gelu_pair_h(float z, float& h, float& dh) {
 }
 
 // ELU / SELU negative branch: exp(min(z,0)) - 1 on the hardware exponential (v_exp_f32, ~1 ulp of a
-// value <= 1, i.e. absolute error <= 1.2e-7 - fp32 round-off class, far inside the 1e-4 parity
+// value <= 1, on an argument rounded once: absolute error <= 1.4e-7 for ELU - 6.4e-8 of it with a correctly rounded
+// exponential -, 3.0e-7 for SELU; DESIGN.md section 2.2e - fp32 round-off class, far inside the 1e-4 parity
 // bar) and written as max(z,0) + (e - 1) so that no lane diverges: for z > 0, e == 1 exactly.
 template <int ACT>
 __device__ __forceinline__ float act_fwd_t(float z) {
@@ -504,8 +506,8 @@ __device__ __forceinline__ void act3_t(float z, float& a, float& d1, float& d2) 
     }
 }
 
-// tanh on the hardware exponential: (1 - t) / (1 + t) with t = exp(-2|x|) away from zero (relative error ~5e-7 worst
-// case, just above the switch point), the odd series up to x^7 below |x| = 1/8 (truncation 2e-10); branch-free.  libm's
+// tanh on the hardware exponential: (1 - t) / (1 + t) with t = exp(-2|x|) away from zero (relative error ~6e-7 worst
+// case, just above the switch point: 2.9e-7 at |x| = 0.132 with a correctly rounded exponential, plus v_exp_f32's ulp - DESIGN.md section 2.2e), the odd series up to x^7 below |x| = 1/8 (truncation 2e-10); branch-free.  libm's
 // tanhf is ~200 instructions with divergent branches and sat on the critical path of every step (head -> action).
 __device__ __forceinline__ float fast_tanh(float x) {
     const float ax = fabsf(x), x2 = x * x;
