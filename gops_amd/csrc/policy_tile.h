@@ -168,3 +168,32 @@ __device__ __forceinline__ int policy_tile_greedy(const float (&y)[GOPS_DQN_MAX_
     }
     return idx;
 }
+
+// The categorical head's draw from softmax(y[0 .. n)) by the inverse CDF of u0 in [0, 1), in double: the maximum (y[greedy]), the
+// exponentials summed in index order, the threshold u0 S, the FIRST index whose cumulative sum exceeds it (n - 1 when rounding leaves
+// none); `logp` = the log-softmax at the index.  As above every index is a compile-time constant after unrolling: y[] and z[] stay in
+// registers.
+__device__ __forceinline__ int policy_tile_categorical(const float (&y)[GOPS_DQN_MAX_ACTIONS], int n, int greedy, double u0, double& logp) {
+    double mx = (double)y[0];
+#pragma unroll
+    for (int a = 1; a < GOPS_DQN_MAX_ACTIONS; ++a) mx = a == greedy ? (double)y[a] : mx;
+    double z[GOPS_DQN_MAX_ACTIONS], S = 0.0;
+#pragma unroll
+    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) {
+        z[a] = a < n ? exp((double)y[a] - mx) : 0.0;
+        S += z[a];   // (index order; the zeros beyond n change nothing)
+    }
+    const double thr = u0 * S;
+    double cum = 0.0, yi = 0.0;
+    int index = n - 1;
+    bool found = false;
+#pragma unroll
+    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) {
+        cum += z[a];
+        if (a < n && !found && thr < cum) index = a, found = true;
+    }
+#pragma unroll
+    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) yi = a == index ? (double)y[a] : yi;
+    logp = (yi - mx) - log(S);
+    return index;
+}

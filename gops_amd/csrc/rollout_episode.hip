@@ -16,6 +16,8 @@
 // The per-episode step buffers (obs, state, ref_points ring, ref_time) ping-pong between two sets in the workspace; each
 // workgroup touches its own 16 rows only, which stay in L2.  Episodes that ended take no further step and write no further
 // trace row; the workgroup leaves the loop once all of its episodes have ended (the alive flags in LDS, read by every thread: a uniform decision).
+// Which descriptions the kernel admits, the widths of the info tensors and the workspace queries' rule: closed_loop.h, shared with
+// the sampler kernel (the rules that differ are EPISODE_RULES below).
 #include <stdint.h>
 #include <string.h>
 
@@ -23,6 +25,7 @@
 
 #include "env_step.h"
 #include "common.h"
+#include "closed_loop.h"
 #include "policy_tile.h"
 
 namespace {
@@ -33,7 +36,7 @@ struct EpisodeParams {
     GopsEnv env;   // padded (lq_pad_env), reference constants filled
     PolicyTile net;
     int E, T, O, A, fh;
-    int state_dim, ref_floats;    // per-episode floats of info["state"] / info["ref_points"] (0: the model has none)
+    InfoWidths info;
     float pdt;
     GopsStepIO init;
     float* obs[2];
@@ -55,11 +58,10 @@ EpisodeLayout episode_layout(const GopsEnv& e, int E) {
     EpisodeLayout l{};
     const bool ref = env_has_ref_table(e.kind);
     auto ep_align = [](size_t nfloats) { return align256(nfloats * sizeof(float)) / sizeof(float); };   // the layout counts floats
-    const int sd = e.kind == GOPS_ENV_VEH3DOFCONTI ? 6 : e.kind == GOPS_ENV_VEH2DOF ? 4 : 0;
-    const int rf = e.kind == GOPS_ENV_VEH3DOFCONTI ? (e.pre_horizon + 1) * 4 : e.kind == GOPS_ENV_VEH2DOF ? (e.pre_horizon + 1) * 2 : 0;
+    const InfoWidths w = info_widths(e);
     l.obs_n = ep_align((size_t)E * e.obs_dim);
-    l.state_n = ref ? ep_align((size_t)E * sd) : 0;
-    l.refp_n = ref ? ep_align((size_t)E * rf) : 0;
+    l.state_n = ref ? ep_align((size_t)E * w.state_dim) : 0;
+    l.refp_n = ref ? ep_align((size_t)E * w.ref_floats) : 0;
     l.reft_n = ref ? ep_align((size_t)E) : 0;
     size_t off = 0;
     l.obs = off; off += 2 * l.obs_n;
@@ -73,31 +75,9 @@ EpisodeLayout episode_layout(const GopsEnv& e, int E) {
     return l;
 }
 
-// `act_num` = 0: the continuous head (output width A); else the greedy head's (output width act_num).
-int episode_check(const GopsEnv* env, const GopsMlp* pol, int E, int T, int act_num = 0) {
-    if (!env || !pol || E < 1 || T < 1) return GOPS_ERR_BAD_ARG;
-    if (!env->data_env) return GOPS_ERR_BAD_ARG;   // evaluation steps the DATA environment
-    const int k = env->kind;
-    if (k != GOPS_ENV_LQ && k != GOPS_ENV_IDPENDULUM && k != GOPS_ENV_CARTPOLE && k != GOPS_ENV_VEH3DOFCONTI && k != GOPS_ENV_VEH2DOF)
-        return GOPS_ERR_UNSUPPORTED;   // mobilerobot (noise drawn per step), the constrained vehicle models, pendulum (no data-env restatement)
-    if (env->cstr_err || env->repeat_num > 1) return GOPS_ERR_UNSUPPORTED;
-    if (pol->n_layers == 1 || pol->dtype != GOPS_DTYPE_F32) return GOPS_ERR_UNSUPPORTED;   // POLY nets, half-precision contractions
-    const int O = env->obs_dim, A = env->act_dim, P = env->pre_horizon;
-    if (A < 1 || A > GOPS_MAX_ACT || O < 1) return GOPS_ERR_BAD_ARG;
-    if (k == GOPS_ENV_LQ && O > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED;
-    if ((k == GOPS_ENV_IDPENDULUM && (O != 6 || A != 1)) || (k == GOPS_ENV_CARTPOLE && (O != 4 || A != 1))) return GOPS_ERR_BAD_ARG;
-    if (k == GOPS_ENV_VEH3DOFCONTI && (P < 1 || O != 6 + 4 * P || A != 2)) return GOPS_ERR_BAD_ARG;
-    if (k == GOPS_ENV_VEH2DOF && (P < 1 || O != 4 + P || A != 1)) return GOPS_ERR_BAD_ARG;
-    if (env->scale_obs && (O > 8 || env_has_ref_table(k))) return GOPS_ERR_UNSUPPORTED;
-    if (pol->n_layers < 2 || pol->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_UNSUPPORTED;
-    if ((pol->sizes[0] != O && pol->sizes[0] != O + 1) || pol->sizes[pol->n_layers] != (act_num > 0 ? act_num : A)) return GOPS_ERR_BAD_ARG;
-    for (int j = 1; j < pol->n_layers; ++j)
-        if (pol->sizes[j] < 16 || (pol->sizes[j] & 15)) return GOPS_ERR_UNSUPPORTED;
-    if (pol->hidden_act < GOPS_ACT_LINEAR || pol->hidden_act > GOPS_ACT_TANH) return GOPS_ERR_BAD_ARG;
-    for (int j = 0; j < pol->n_layers; ++j)
-        if (pol->weight[j] == nullptr || pol->bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
-    return GOPS_OK;
-}
+// Evaluation steps the DATA environment (pendulum, mountaincar: no data-env restatement); a FiniteHorizonPolicy's time input is
+// taken (virtual_t = 1); output width A, the deterministic head's.
+constexpr ClosedLoopRules EPISODE_RULES = {CLOSED_LOOP_DATA_KINDS, 0, true, false};
 
 __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -113,11 +93,11 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
     policy_tile_load(p.net, lds, tid);
     if (tid < GOPS_TILE) s_alive[tid] = tid < nvalid ? 1 : 0;
     for (int idx = tid; idx < nvalid * O; idx += EP_THREADS) p.obs[0][(size_t)e0 * O + idx] = p.init.obs[(size_t)e0 * O + idx];
-    if (p.state_dim > 0) {
-        for (int idx = tid; idx < nvalid * p.state_dim; idx += EP_THREADS)
-            p.state[0][(size_t)e0 * p.state_dim + idx] = p.init.state[(size_t)e0 * p.state_dim + idx];
-        for (int idx = tid; idx < nvalid * p.ref_floats; idx += EP_THREADS)
-            p.refp[0][(size_t)e0 * p.ref_floats + idx] = p.init.ref_points[(size_t)e0 * p.ref_floats + idx];
+    if (p.info.state_dim > 0) {
+        for (int idx = tid; idx < nvalid * p.info.state_dim; idx += EP_THREADS)
+            p.state[0][(size_t)e0 * p.info.state_dim + idx] = p.init.state[(size_t)e0 * p.info.state_dim + idx];
+        for (int idx = tid; idx < nvalid * p.info.ref_floats; idx += EP_THREADS)
+            p.refp[0][(size_t)e0 * p.info.ref_floats + idx] = p.init.ref_points[(size_t)e0 * p.info.ref_floats + idx];
         if (tid < nvalid) p.reft[0][e0 + tid] = p.init.ref_time[e0 + tid];
     }
     // the episode's books, in the registers of its lane (tid < nvalid)
@@ -225,8 +205,7 @@ int episode_launch(const GopsEnv* env, const GopsMlp* policy, const float* table
     p.E = E, p.T = T, p.O = env->obs_dim, p.A = env->act_dim;
     p.fh = policy->sizes[0] == env->obs_dim + 1;
     policy_tile_bind(*policy, p.net);
-    p.state_dim = env->kind == GOPS_ENV_VEH3DOFCONTI ? 6 : env->kind == GOPS_ENV_VEH2DOF ? 4 : 0;
-    p.ref_floats = env->kind == GOPS_ENV_VEH3DOFCONTI ? (env->pre_horizon + 1) * 4 : env->kind == GOPS_ENV_VEH2DOF ? (env->pre_horizon + 1) * 2 : 0;
+    p.info = info_widths(*env);
     p.pdt = pdt_of(*env);
     p.init = *init;
     float* f = static_cast<float*>(ws);
@@ -248,22 +227,17 @@ int episode_launch(const GopsEnv* env, const GopsMlp* policy, const float* table
 extern "C" {
 
 size_t gops_episode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T) {
-    if (episode_check(env, policy, E, T) != GOPS_OK) return 0;
-    PolicyTile net;
-    if (policy_tile_plan(*policy, net) == 0) return 0;
-    return episode_layout(*env, E).bytes;
+    return closed_loop_takes(EPISODE_RULES, env, policy, E, T, 0) ? episode_layout(*env, E).bytes : 0;
 }
 
 size_t gops_episode_dis_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t act_num, int32_t E, int32_t T) {
-    if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS || episode_check(env, policy, E, T, act_num) != GOPS_OK) return 0;
-    PolicyTile net;
-    if (policy_tile_plan(*policy, net) == 0) return 0;
-    return episode_layout(*env, E).bytes;
+    if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS) return 0;
+    return closed_loop_takes(EPISODE_RULES, env, policy, E, T, act_num) ? episode_layout(*env, E).bytes : 0;
 }
 
 int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, int32_t T, const GopsStepIO* init, const GopsEpisodeOut* out,
                          void* ws, size_t ws_bytes, void* stream) {
-    const int rc = episode_check(env, policy, E, T);
+    const int rc = closed_loop_check(EPISODE_RULES, env, policy, E, T, 0);
     if (rc != GOPS_OK) return rc;
     return episode_launch(env, policy, nullptr, 0, E, T, init, out, ws, ws_bytes, stream);
 }
@@ -272,7 +246,7 @@ int gops_episode_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const fl
                              const GopsStepIO* init, const GopsEpisodeOut* out, void* ws, size_t ws_bytes, void* stream) {
     if (!action_table) return GOPS_ERR_BAD_ARG;
     if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS) return GOPS_ERR_UNSUPPORTED;
-    const int rc = episode_check(env, policy, E, T, act_num);   // (BAD_ARG for an output width other than act_num)
+    const int rc = closed_loop_check(EPISODE_RULES, env, policy, E, T, act_num);   // (BAD_ARG for an output width other than act_num)
     if (rc != GOPS_OK) return rc;
     return episode_launch(env, policy, action_table, act_num, E, T, init, out, ws, ws_bytes, stream);
 }

@@ -15,11 +15,14 @@
 //      t += 1, over = done or t >= max_episode_steps, time_limited, end, and where the row continues from (an LDS flag per row).
 // After the last step the same carry writes the persistent state.  A row depends on its own instance only: the pool row is
 // reset_count[i] % R of column i.  No workgroup reads what another wrote; no atomics; every loop is bounded by `steps`.
+// Which descriptions the kernel admits, the widths of the info tensors and the workspace queries' rule: closed_loop.h, shared with
+// the episode kernel (the rules that differ are SAMPLE_RULES below).
 #include <stdint.h>
 #include <string.h>
 
 #include "env_step.h"
 #include "common.h"
+#include "closed_loop.h"
 #include "policy_tile.h"
 #include "soft_math.h"
 
@@ -29,7 +32,7 @@ struct SampleParams {
     GopsEnv env;   // padded (lq_pad_env), reference constants filled
     PolicyTile net;
     int N, T, O, A, head, R, max_steps;
-    int state_dim, ref_floats;   // per-instance floats of info["state"] / info["ref_points"] (0: the model has none)
+    InfoWidths info;
     float pdt;
     double noise_std, min_ls, max_ls;
     GopsSampleState st;
@@ -44,41 +47,9 @@ struct SampleParams {
 };
 static_assert(sizeof(SampleParams) <= 4096, "kernel arguments are passed by value");
 
-int sample_state_dim(const GopsEnv& e) { return e.kind == GOPS_ENV_VEH3DOFCONTI ? 6 : e.kind == GOPS_ENV_VEH2DOF ? 4 : 0; }
-int sample_ref_floats(const GopsEnv& e) {
-    return e.kind == GOPS_ENV_VEH3DOFCONTI ? (e.pre_horizon + 1) * 4 : e.kind == GOPS_ENV_VEH2DOF ? (e.pre_horizon + 1) * 2 : 0;
-}
-
-// The description alone (what gops_sample_workspace_bytes can see): env kind, policy shape, sizes.
-// `act_num` = 0: the continuous heads (output width A or 2A); else the discrete heads' (output width act_num).
-int sample_check(const GopsEnv* env, const GopsMlp* pol, int N, int T, int act_num = 0) {
-    if (!env || !pol || N < 1 || T < 1) return GOPS_ERR_BAD_ARG;
-    const int k = env->kind;
-    const bool data_kind = k == GOPS_ENV_LQ || k == GOPS_ENV_IDPENDULUM || k == GOPS_ENV_CARTPOLE || k == GOPS_ENV_VEH3DOFCONTI || k == GOPS_ENV_VEH2DOF;
-    const bool model_kind = k == GOPS_ENV_PENDULUM || k == GOPS_ENV_MOUNTAINCAR;   // env models only: no data-env restatement
-    if (!data_kind && !model_kind) return GOPS_ERR_UNSUPPORTED;   // mobilerobot (obstacle noise drawn per step), the constrained vehicle models
-    if (env->data_env ? !data_kind : !model_kind) return GOPS_ERR_UNSUPPORTED;
-    if (env->cstr_err || env->repeat_num > 1) return GOPS_ERR_UNSUPPORTED;
-    if (pol->n_layers == 1 || pol->dtype != GOPS_DTYPE_F32) return GOPS_ERR_UNSUPPORTED;   // POLY nets, half-precision contractions
-    const int O = env->obs_dim, A = env->act_dim, P = env->pre_horizon;
-    if (A < 1 || A > GOPS_MAX_ACT || O < 1) return GOPS_ERR_BAD_ARG;
-    if (k == GOPS_ENV_LQ && O > GOPS_MAX_LQ_STATE) return GOPS_ERR_UNSUPPORTED;
-    if ((k == GOPS_ENV_IDPENDULUM && (O != 6 || A != 1)) || (k == GOPS_ENV_CARTPOLE && (O != 4 || A != 1))) return GOPS_ERR_BAD_ARG;
-    if ((k == GOPS_ENV_PENDULUM && (O != 3 || A != 1)) || (k == GOPS_ENV_MOUNTAINCAR && (O != 2 || A != 1))) return GOPS_ERR_BAD_ARG;
-    if (k == GOPS_ENV_VEH3DOFCONTI && (P < 1 || O != 6 + 4 * P || A != 2)) return GOPS_ERR_BAD_ARG;
-    if (k == GOPS_ENV_VEH2DOF && (P < 1 || O != 4 + P || A != 1)) return GOPS_ERR_BAD_ARG;
-    if (env->scale_obs && (O > 8 || env_has_ref_table(k))) return GOPS_ERR_UNSUPPORTED;
-    if (pol->n_layers < 2 || pol->n_layers > GOPS_MAX_LAYERS) return GOPS_ERR_UNSUPPORTED;
-    if (pol->sizes[0] == O + 1) return GOPS_ERR_UNSUPPORTED;   // time-augmented policies (FiniteHorizonPolicy)
-    const int n_out = pol->sizes[pol->n_layers];
-    if (pol->sizes[0] != O || (act_num > 0 ? n_out != act_num : (n_out != A && n_out != 2 * A))) return GOPS_ERR_BAD_ARG;
-    for (int j = 1; j < pol->n_layers; ++j)
-        if (pol->sizes[j] < 16 || (pol->sizes[j] & 15)) return GOPS_ERR_UNSUPPORTED;
-    if (pol->hidden_act < GOPS_ACT_LINEAR || pol->hidden_act > GOPS_ACT_TANH) return GOPS_ERR_BAD_ARG;
-    for (int j = 0; j < pol->n_layers; ++j)
-        if (pol->weight[j] == nullptr || pol->bias[j] == nullptr) return GOPS_ERR_BAD_ARG;
-    return GOPS_OK;
-}
+// Data envs and - pendulum, mountaincar: no data-env restatement - env models; no time-augmented policies (FiniteHorizonPolicy);
+// output width A or 2A (the entry point then holds the width against the head).
+constexpr ClosedLoopRules SAMPLE_RULES = {CLOSED_LOOP_DATA_KINDS, 1u << GOPS_ENV_PENDULUM | 1u << GOPS_ENV_MOUNTAINCAR, false, true};
 
 // Where row m continues from: src < 0 the persistent state, 0 the previous step's next_* row, k + 1 pool row k of its column.
 __device__ __forceinline__ float carried(int src, const float* st, const float* prev, const float* pool, size_t N, size_t i, int w, int k) {
@@ -94,13 +65,24 @@ __device__ __forceinline__ void carry_field(float* dst, const float* st, const f
     }
 }
 
+// The five info tensors of the tile's rows (the vehicle families) into the destinations given: the step's rows of the outputs, or the
+// persistent state itself.  `prow0`: the first row of the previous step - a continuing episode carries its next_* rows (the ids: its own).
+__device__ __forceinline__ void carry_info(const SampleParams& p, float* state, float* ref_points, float* path_num, float* u_num,
+                                           float* ref_time, size_t prow0, const int* s_src, int N, int sd, int rf, int e0, int nvalid, int tid) {
+    carry_field(state, p.st.state, p.out.next_state + prow0 * sd, p.pool.state, s_src, N, e0, nvalid, sd, tid);
+    carry_field(ref_points, p.st.ref_points, p.out.next_ref_points + prow0 * rf, p.pool.ref_points, s_src, N, e0, nvalid, rf, tid);
+    carry_field(path_num, p.st.path_num, p.out.path_num + prow0, p.pool.path_num, s_src, N, e0, nvalid, 1, tid);
+    carry_field(u_num, p.st.u_num, p.out.u_num + prow0, p.pool.u_num, s_src, N, e0, nvalid, 1, tid);
+    carry_field(ref_time, p.st.ref_time, p.out.next_ref_time + prow0, p.pool.ref_time, s_src, N, e0, nvalid, 1, tid);
+}
+
 __global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int e0 = blockIdx.x * GOPS_TILE;
     const int nvalid = min(GOPS_TILE, p.N - e0);
     const int N = p.N, T = p.T, O = p.O, A = p.A, nl = p.net.nl, ldx = p.net.ldx;
-    const int sd = p.state_dim, rf = p.ref_floats;
+    const int sd = p.info.state_dim, rf = p.info.ref_floats;
     float* xa = lds;
     float* xb = lds + GOPS_TILE * ldx;
     int* s_src = reinterpret_cast<int*>(lds + p.net.flags_off);
@@ -127,13 +109,9 @@ __global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p
             }
             xa[m * ldx + k] = v;
         }
-        if (sd > 0) {
-            carry_field(p.out.state + row0 * sd, p.st.state, p.out.next_state + prow0 * sd, p.pool.state, s_src, N, e0, nvalid, sd, tid);
-            carry_field(p.out.ref_points + row0 * rf, p.st.ref_points, p.out.next_ref_points + prow0 * rf, p.pool.ref_points, s_src, N, e0, nvalid, rf, tid);
-            carry_field(p.out.path_num + row0, p.st.path_num, p.out.path_num + prow0, p.pool.path_num, s_src, N, e0, nvalid, 1, tid);
-            carry_field(p.out.u_num + row0, p.st.u_num, p.out.u_num + prow0, p.pool.u_num, s_src, N, e0, nvalid, 1, tid);
-            carry_field(p.out.ref_time + row0, p.st.ref_time, p.out.next_ref_time + prow0, p.pool.ref_time, s_src, N, e0, nvalid, 1, tid);
-        }
+        if (sd > 0)
+            carry_info(p, p.out.state + row0 * sd, p.out.ref_points + row0 * rf, p.out.path_num + row0, p.out.u_num + row0,
+                       p.out.ref_time + row0, prow0, s_src, N, sd, rf, e0, nvalid, tid);
         __syncthreads();
         // 2. hidden layers
         const float* cur_x = policy_tile_hidden(p.net, lds, xa, xb, lane, wave);
@@ -152,27 +130,7 @@ __global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p
                     const int uniform = max(min((int)(u1 * n), n - 1), 0);
                     index = u0 < p.epsilon ? uniform : greedy;
                 } else {
-                    double mx = (double)y[0];
-#pragma unroll
-                    for (int a = 1; a < GOPS_DQN_MAX_ACTIONS; ++a) mx = a == greedy ? (double)y[a] : mx;
-                    double z[GOPS_DQN_MAX_ACTIONS], S = 0.0;
-#pragma unroll
-                    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) {
-                        z[a] = a < n ? exp((double)y[a] - mx) : 0.0;
-                        S += z[a];   // (index order; the zeros beyond n change nothing)
-                    }
-                    const double thr = u0 * S;
-                    double cum = 0.0, yi = 0.0;
-                    index = n - 1;
-                    bool found = false;
-#pragma unroll
-                    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) {
-                        cum += z[a];
-                        if (a < n && !found && thr < cum) index = a, found = true;
-                    }
-#pragma unroll
-                    for (int a = 0; a < GOPS_DQN_MAX_ACTIONS; ++a) yi = a == index ? (double)y[a] : yi;
-                    lp = (yi - mx) - log(S);
+                    index = policy_tile_categorical(y, n, greedy, u0, lp);
                 }
                 p.out.act[row] = (float)index;
                 p.out.logp[row] = (float)lp;
@@ -248,13 +206,7 @@ __global__ __launch_bounds__(PT_THREADS) void sample_kernel(const SampleParams p
     {
         const size_t prow0 = (size_t)(T - 1) * N;
         carry_field(p.st.obs, p.st.obs, p.out.obs2 + prow0 * O, p.pool.obs, s_src, N, e0, nvalid, O, tid);
-        if (sd > 0) {
-            carry_field(p.st.state, p.st.state, p.out.next_state + prow0 * sd, p.pool.state, s_src, N, e0, nvalid, sd, tid);
-            carry_field(p.st.ref_points, p.st.ref_points, p.out.next_ref_points + prow0 * rf, p.pool.ref_points, s_src, N, e0, nvalid, rf, tid);
-            carry_field(p.st.path_num, p.st.path_num, p.out.path_num + prow0, p.pool.path_num, s_src, N, e0, nvalid, 1, tid);
-            carry_field(p.st.u_num, p.st.u_num, p.out.u_num + prow0, p.pool.u_num, s_src, N, e0, nvalid, 1, tid);
-            carry_field(p.st.ref_time, p.st.ref_time, p.out.next_ref_time + prow0, p.pool.ref_time, s_src, N, e0, nvalid, 1, tid);
-        }
+        if (sd > 0) carry_info(p, p.st.state, p.st.ref_points, p.st.path_num, p.st.u_num, p.st.ref_time, prow0, s_src, N, sd, rf, e0, nvalid, tid);
         if (tid < nvalid) { p.st.t[e0 + tid] = ti; p.st.reset_count[e0 + tid] = rc; }
     }
 }
@@ -285,7 +237,7 @@ int sample_launch(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDes
     p.N = n_envs, p.T = steps, p.O = env->obs_dim, p.A = A;
     p.head = head, p.R = desc->pool_rows, p.max_steps = desc->max_episode_steps;
     p.noise_std = desc->noise_std, p.min_ls = desc->min_log_std, p.max_ls = desc->max_log_std;
-    p.state_dim = sample_state_dim(*env), p.ref_floats = sample_ref_floats(*env);
+    p.info = info_widths(*env);
     p.pdt = pdt_of(*env);
     p.st = *state, p.pool = *pool, p.noise = noise, p.out = *out;
     if (dis) p.act_num = dis->act_num, p.epsilon = dis->epsilon, p.table = dis->action_table, p.env_act = dis->env_act;
@@ -298,18 +250,12 @@ int sample_launch(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDes
 extern "C" {
 
 size_t gops_sample_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t n_envs, int32_t steps) {
-    if (sample_check(env, policy, n_envs, steps) != GOPS_OK) return 0;
-    PolicyTile net;
-    if (policy_tile_plan(*policy, net) == 0) return 0;
-    return GOPS_SAMPLE_WORKSPACE_BYTES;
+    return closed_loop_takes(SAMPLE_RULES, env, policy, n_envs, steps, 0) ? GOPS_SAMPLE_WORKSPACE_BYTES : 0;
 }
 
 size_t gops_sample_dis_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t act_num, int32_t n_envs, int32_t steps) {
     if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS) return 0;
-    if (sample_check(env, policy, n_envs, steps, act_num) != GOPS_OK) return 0;
-    PolicyTile net;
-    if (policy_tile_plan(*policy, net) == 0) return 0;
-    return GOPS_SAMPLE_WORKSPACE_BYTES;
+    return closed_loop_takes(SAMPLE_RULES, env, policy, n_envs, steps, act_num) ? GOPS_SAMPLE_WORKSPACE_BYTES : 0;
 }
 
 int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSampleDesc* desc, int32_t n_envs, int32_t steps,
@@ -318,7 +264,7 @@ int gops_sample_rollout(const GopsEnv* env, const GopsMlp* policy, const GopsSam
     if (!env || !policy || !desc || !state || !pool || !noise || !out || steps < 1 || n_envs < 1) return GOPS_ERR_BAD_ARG;
     if (desc->pool_rows < 1 || desc->max_episode_steps < 1) return GOPS_ERR_BAD_ARG;
     if (desc->head < GOPS_SAMPLE_DETERM || desc->head > GOPS_SAMPLE_TANH_GAUSS) return GOPS_ERR_BAD_ARG;
-    const int rc = sample_check(env, policy, n_envs, steps);
+    const int rc = closed_loop_check(SAMPLE_RULES, env, policy, n_envs, steps, 0);
     if (rc != GOPS_OK) return rc;
     const int A = env->act_dim, n_out = policy->sizes[policy->n_layers];
     if (n_out != (desc->head == GOPS_SAMPLE_DETERM ? A : 2 * A)) return GOPS_ERR_BAD_ARG;   // (an odd width for the Gaussian heads included)
@@ -335,7 +281,7 @@ int gops_sample_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const Gop
     if (!(dis->epsilon >= 0.0 && dis->epsilon <= 1.0)) return GOPS_ERR_BAD_ARG;   // (a NaN included)
     if (dis->head == GOPS_SAMPLE_CATEGORICAL && dis->epsilon != 0.0) return GOPS_ERR_BAD_ARG;
     if (dis->act_num < 2 || dis->act_num > GOPS_DQN_MAX_ACTIONS) return GOPS_ERR_UNSUPPORTED;
-    const int rc = sample_check(env, policy, n_envs, steps, dis->act_num);   // (BAD_ARG for an output width other than act_num)
+    const int rc = closed_loop_check(SAMPLE_RULES, env, policy, n_envs, steps, dis->act_num);   // (BAD_ARG for an output width other than act_num)
     if (rc != GOPS_OK) return rc;
     return sample_launch(env, policy, desc, dis->head, dis, n_envs, steps, state, pool, noise, out, ws, ws_bytes, stream);
 }

@@ -19,6 +19,7 @@ MAX_LAYERS, MAX_ACT, MAX_LQ, TILE = 5, 4, 6, 16
 ENV_NONE, ENV_LQ, ENV_IDP, ENV_VEH, ENV_VEH_SURR, ENV_CARTPOLE, ENV_PENDULUM, ENV_VEH2DOF, ENV_MOBILEROBOT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ENV_MOUNTAINCAR = 9
 STATE_OBS_ENV_KINDS = (ENV_LQ, ENV_IDP, ENV_CARTPOLE, ENV_PENDULUM, ENV_MOUNTAINCAR)   # the models whose observation is the state
+DATA_ENV_KINDS = (ENV_LQ, ENV_IDP, ENV_VEH, ENV_CARTPOLE, ENV_VEH2DOF, ENV_MOBILEROBOT)   # the models whose data env gops_env_step restates
 MAX_CLIP_OBS = 16
 # std of the obstacle robot's per-step (v, w) noise draws (pyth_mobilerobot_model.py:141-147, std_type["obs"])
 MOBILEROBOT_NOISE_STD = (0.03, 0.02)
@@ -1070,32 +1071,26 @@ class EpisodeRollout:
         self.env, self.policy, self.episodes, self.max_steps = env, policy, int(episodes), int(max_steps)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.action_table = action_table
+        # the one place that knows which of the two forms this is: the query, the entry point, the arguments only `_dis` takes
+        query, self._name, query_extra, self._extra, self._act_width = "gops_episode_workspace_bytes", "gops_episode_rollout", (), (), env.act_dim
         if action_table is not None:
             assert action_table.dim() == 2 and action_table.shape[1] == env.act_dim, "action_table must be [act_num, act_dim]"
             self.act_num = int(action_table.shape[0])
-            nbytes = lib().gops_episode_dis_workspace_bytes(C.byref(env), C.byref(policy), self.act_num, self.episodes, self.max_steps)
-        else:
-            nbytes = lib().gops_episode_workspace_bytes(C.byref(env), C.byref(policy), self.episodes, self.max_steps)
+            query, self._name, self._act_width = "gops_episode_dis_workspace_bytes", "gops_episode_rollout_dis", 1
+            query_extra, self._extra = (self.act_num,), (_ptr(action_table), self.act_num)
+        nbytes = getattr(lib(), query)(C.byref(env), C.byref(policy), *query_extra, self.episodes, self.max_steps)
         if workspace_bytes is None:
             if nbytes == 0:   # ask the entry point itself for the reason
                 check(self._call(None, None, None, 0, None), self._name)
-                raise RuntimeError(("gops_episode_workspace_bytes" if action_table is None else "gops_episode_dis_workspace_bytes")
-                                   + ": description refused")
+                raise RuntimeError(query + ": description refused")
             workspace_bytes = nbytes
         self.workspace = torch.empty(max(int(workspace_bytes), 1), dtype=torch.uint8, device=self.device)
         self._workspace_bytes = int(workspace_bytes)
 
-    @property
-    def _name(self):
-        return "gops_episode_rollout" if self.action_table is None else "gops_episode_rollout_dis"
-
     def _call(self, io, out, ws, ws_bytes, stream):
         ref = lambda x: None if x is None else C.byref(x)   # noqa: E731
-        E, T = self.episodes, self.max_steps
-        if self.action_table is None:
-            return lib().gops_episode_rollout(C.byref(self.env), C.byref(self.policy), E, T, ref(io), ref(out), ws, ws_bytes, stream)
-        return lib().gops_episode_rollout_dis(C.byref(self.env), C.byref(self.policy), _ptr(self.action_table), self.act_num, E, T, ref(io),
-                                              ref(out), ws, ws_bytes, stream)
+        return getattr(lib(), self._name)(C.byref(self.env), C.byref(self.policy), *self._extra, self.episodes, self.max_steps, ref(io),
+                                          ref(out), ws, ws_bytes, stream)
 
     def set_policy(self, policy: GopsMlp):
         self.policy = policy
@@ -1116,7 +1111,7 @@ class EpisodeRollout:
         if trace:
             mk = (lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)) if trace_fill is None else \
                  (lambda *sh: torch.full(sh, float(trace_fill), dtype=torch.float32, device=dev))
-            res.update(trace_obs=mk(E, T, self.env.obs_dim), trace_act=mk(E, T, self.env.act_dim if self.action_table is None else 1),
+            res.update(trace_obs=mk(E, T, self.env.obs_dim), trace_act=mk(E, T, self._act_width),
                        trace_rew=mk(E, T))
         for k, v in res.items():
             setattr(out, k, v.data_ptr())
@@ -1143,20 +1138,22 @@ class SampleRollout:
         self.desc = GopsSampleDesc(head=int(head), max_episode_steps=int(max_episode_steps), pool_rows=int(pool_rows), reserved=0,
                                    noise_std=float(noise_std), min_log_std=float(min_log_std), max_log_std=float(max_log_std))
         self.action_table, self.dis = action_table, None
+        # the one place that knows which of the two forms this is: the query, the entry point, the arguments only `_dis` takes
+        query, self._name, query_extra, self._extra = "gops_sample_workspace_bytes", "gops_sample_rollout", (), ()
+        self.noise_width = act_width = env.act_dim
         if action_table is not None:
             assert action_table.dim() == 2 and action_table.shape[1] == env.act_dim, "action_table must be [act_num, act_dim]"
             self.dis = GopsSampleDis(action_table=_ptr(action_table), act_num=int(action_table.shape[0]), head=int(head),
                                      epsilon=float(epsilon), env_act=None)
-            nbytes = lib().gops_sample_dis_workspace_bytes(C.byref(env), C.byref(policy), self.dis.act_num, self.n_envs, self.steps)
-        else:
-            nbytes = lib().gops_sample_workspace_bytes(C.byref(env), C.byref(policy), self.n_envs, self.steps)
+            query, self._name, self.noise_width, act_width = "gops_sample_dis_workspace_bytes", "gops_sample_rollout_dis", 2, 1
+            query_extra, self._extra = (self.dis.act_num,), (C.byref(self.dis),)
+        nbytes = getattr(lib(), query)(C.byref(env), C.byref(policy), *query_extra, self.n_envs, self.steps)
         if nbytes == 0:
-            raise RuntimeError(("gops_sample_workspace_bytes" if self.dis is None else "gops_sample_dis_workspace_bytes") + ": description refused")
+            raise RuntimeError(query + ": description refused")
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         T, N = self.steps, self.n_envs
         mk = lambda *sh: torch.empty((T, N) + tuple(sh), dtype=torch.float32, device=self.device)   # noqa: E731
-        self.noise_width = env.act_dim if self.dis is None else 2
-        self.out = dict(obs=mk(env.obs_dim), act=mk(env.act_dim if self.dis is None else 1), rew=mk(), done=mk(), obs2=mk(env.obs_dim),
+        self.out = dict(obs=mk(env.obs_dim), act=mk(act_width), rew=mk(), done=mk(), obs2=mk(env.obs_dim),
                         logp=mk(), time_limited=mk(), end=mk())
         self.info_keys = tuple(k for k in SAMPLE_INFO_KEYS if info_like and k in info_like)
         for k in self.info_keys:
@@ -1185,14 +1182,9 @@ class SampleRollout:
             v = state[k]
             assert v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.numel() == N, k
             setattr(st, k, v.data_ptr())
-        if self.dis is not None:
-            check(lib().gops_sample_rollout_dis(C.byref(self.env), C.byref(self.policy), C.byref(self.desc), C.byref(self.dis), N, T,
-                                                C.byref(st), C.byref(pl), _ptr(noise), C.byref(self._out), self.workspace.data_ptr(),
-                                                self.workspace.numel(), _stream()), "gops_sample_rollout_dis")
-            return self.out
-        check(lib().gops_sample_rollout(C.byref(self.env), C.byref(self.policy), C.byref(self.desc), N, T, C.byref(st), C.byref(pl),
-                                        _ptr(noise), C.byref(self._out), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_sample_rollout")
+        check(getattr(lib(), self._name)(C.byref(self.env), C.byref(self.policy), C.byref(self.desc), *self._extra, N, T, C.byref(st),
+                                         C.byref(pl), _ptr(noise), C.byref(self._out), self.workspace.data_ptr(), self.workspace.numel(),
+                                         _stream()), self._name)
         return self.out
 
 

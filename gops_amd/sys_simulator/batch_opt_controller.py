@@ -299,7 +299,7 @@ class BatchOptController:
         if env_step != "data":
             raise ValueError("env_step must be 'model' (the env model's step) or 'data' (the data environment's)")
         base = self.base
-        if base.hip_kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_VEH, hb.ENV_CARTPOLE, hb.ENV_VEH2DOF, hb.ENV_MOBILEROBOT):
+        if base.hip_kind not in hb.DATA_ENV_KINDS:
             from gops_amd.trainer.sampler.reset_pool import NOT_RESTATED
             raise NotImplementedError(NOT_RESTATED.format(env_id=type(base).__name__))
         if self._data_env is None:

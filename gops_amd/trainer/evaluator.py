@@ -28,13 +28,13 @@ import torch
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import is_poly
 from gops_amd.apprfunc.mlp import ActionValueDis, StochaPolicy, StochaPolicyDis
+from gops_amd.trainer.closed_loop import ClosedLoopDriver
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, NOT_RESTATED, draw_reset_pool
 
 # TimeLimit of the data envs where create_env registers one (gops/create_pkg/create_env.py:142-148 takes the env's own
 # `max_episode_steps` attribute): pyth_idpendulum.py:51, pyth_veh3dofconti.py:114, pyth_veh2dofconti.py:105,
 # pyth_mobilerobot.py:30; pyth_lq: resources/lq_base.py:161 (the config's max_step).  gym_cartpoleconti registers none.
 _REGISTERED_STEPS = {"pyth_idpendulum": 500, "pyth_veh3dofconti": 200, "pyth_veh2dofconti": 200, "pyth_mobilerobot": 200}
-_DATA_KINDS = (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_VEH, hb.ENV_CARTPOLE, hb.ENV_VEH2DOF, hb.ENV_MOBILEROBOT)
 
 
 def registered_episode_steps(cfg: dict, default: int = 200) -> int:
@@ -46,7 +46,7 @@ def registered_episode_steps(cfg: dict, default: int = 200) -> int:
     return _REGISTERED_STEPS.get(env_id, default)
 
 
-class Evaluator:
+class Evaluator(ClosedLoopDriver):
     on_device = True   # trainers: the evaluator shares the learner's networks, no state_dict copy
 
     def __init__(self, index=0, *, env_model, networks, cfg: dict, num_eval_episode: int, eval_save: bool = True,
@@ -58,10 +58,8 @@ class Evaluator:
         evaluate a discrete policy (see the module docstring); without one an ActionValueDis is refused."""
         self.cfg, self.env_model, self.networks = dict(cfg), env_model, networks
         self.device = torch.device(device)
-        self.action_table = None if action_table is None else torch.as_tensor(action_table, dtype=torch.float32).to(self.device).contiguous()
+        self._take_action_table(action_table)
         if self.action_table is not None:
-            if self.action_table.dim() != 2:
-                raise ValueError("action_table must be [act_num, action_dim]")
             if not isinstance(self._policy_module(), ActionValueDis) or self._policy_module().act_num != self.action_table.shape[0]:
                 raise ValueError("Evaluator: an action table needs an ActionValueDis `q` or a StochaPolicyDis `policy` with one output per "
                                  "table row")
@@ -72,7 +70,7 @@ class Evaluator:
         if getattr(base, "ref_c", None) is not None:
             raise RuntimeError("Evaluator draws its initial states from the DEFAULT reference trajectories "
                                "(gops_amd.utils.synthetic); a model with custom path_para / u_para needs explicit initial conditions")
-        if getattr(base, "hip_kind", None) not in _DATA_KINDS or self.cfg.get("env_id", "").endswith("errcstr"):
+        if getattr(base, "hip_kind", None) not in hb.DATA_ENV_KINDS or self.cfg.get("env_id", "").endswith("errcstr"):
             raise RuntimeError(NOT_RESTATED.format(env_id=self.cfg.get("env_id")))
         self.num_eval_episode, self.eval_save, self.save_folder = int(num_eval_episode), bool(eval_save), save_folder
         self.seed = int(seed) + int(index) + 400   # evaluator.py:28
@@ -85,25 +83,15 @@ class Evaluator:
         self._evals = 0
         self._henv, self._rollouts = None, {}
         self.last = None   # device results of the last run_episodes call
-        self.path = None   # how the last run_episodes call ran: "fused", or "loop: <why the kernel was not used>"
 
     def load_state_dict(self, state_dict):
         """The reference's surface; a trainer that knows `on_device` never calls it (the networks are shared)."""
         self.networks.load_state_dict(state_dict)
 
     # ---- descriptions ---------------------------------------------------------------------------
-    def _policy_module(self):
-        """The network that is evaluated: `networks.policy`, or - DQN, whose `policy` is a plain function over it - `networks.q`."""
-        pol = self.networks.policy
-        return pol if isinstance(pol, torch.nn.Module) else getattr(self.networks, "q", pol)
-
     def _hip_env(self):
         if self._henv is None:
-            if self.action_table is not None:   # no squash: the limits are the table's column extremes, as in DeviceEnvSampler
-                low, high = self.action_table.min(dim=0).values, self.action_table.max(dim=0).values
-            else:
-                low, high = self.networks.policy.act_low_lim, self.networks.policy.act_high_lim
-            env = self.env_model.hip_env(low.cpu().numpy(), high.cpu().numpy(), data_env=True)
+            env = self.env_model.hip_env(*self._squash_limits(), data_env=True)
             env = hb.GopsEnv.from_buffer_copy(env)   # (the model caches its description: this one is the evaluator's own)
             env.shaping, env.reward_scale, env.reward_shift = 0, 1.0, 0.0
             env.repeat_num, env.repeat_last_reward = 0, 0
@@ -145,9 +133,7 @@ class Evaluator:
         - with `trace` - trace_obs / trace_act / trace_rew.  Device tensors; nothing is read back here."""
         init = {k: v.to(self.device, torch.float32).contiguous() for k, v in init.items() if k == "obs" or k in INFO_KEYS}
         fused = self.fused if fused is None else fused
-        why = self.kernel_refuses() if fused else "fused=False"
-        self.path = "fused" if why is None else "loop: " + why
-        if why is None:
+        if self._set_path(self.kernel_refuses() if fused else "fused=False"):
             E = init["obs"].shape[0]
             mlp = self._policy_module().hip_mlp()
             key = (E, self.max_episode_steps)

@@ -29,12 +29,13 @@ import torch
 
 from gops_amd.apprfunc.mlp import ActionValueDis, DetermPolicy, StochaPolicy, StochaPolicyDis
 from gops_amd import hip_backend as hb
+from gops_amd.trainer.closed_loop import ClosedLoopDriver
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS as _INFO, NOT_RESTATED, draw_reset_pool, pool_needs_refresh
 from gops_amd.utils.act_distribution import GaussDistribution, TanhGaussDistribution
 from gops_amd.utils.tensorboard_setup import tb_tags
 
 
-class DeviceEnvSampler:
+class DeviceEnvSampler(ClosedLoopDriver):
     on_device = True   # trainers: do not move the networks to the CPU around sample()
 
     def __init__(self, cfg: dict, env_model, *, n_envs: int, steps_per_sample: int = 1, max_episode_steps: int = 200,
@@ -66,16 +67,13 @@ class DeviceEnvSampler:
         self.device = torch.device(device)
         self.seed, self.pool_factor, self.noise_std = seed, pool_factor, noise_std
         self._warned_noise = False
-        self.action_table = None if action_table is None else torch.as_tensor(action_table, dtype=torch.float32).to(self.device).contiguous()
-        if self.action_table is not None and self.action_table.dim() != 2:
-            raise ValueError("action_table must be [act_num, action_dim]")
+        self._take_action_table(action_table)
         self.epsilon = float(epsilon)
         if env_step not in ("data", "model"):
             raise ValueError("env_step must be 'data' (the data environment's step) or 'model' (the env model's)")
         self.data_env = env_step == "data"
         kind = getattr(getattr(env_model, "unwrapped", env_model), "hip_kind", None)
-        if self.data_env and (kind not in (hb.ENV_LQ, hb.ENV_IDP, hb.ENV_VEH, hb.ENV_CARTPOLE, hb.ENV_VEH2DOF, hb.ENV_MOBILEROBOT)
-                              or self.cfg.get("env_id", "").endswith("errcstr")):
+        if self.data_env and (kind not in hb.DATA_ENV_KINDS or self.cfg.get("env_id", "").endswith("errcstr")):
             raise RuntimeError(NOT_RESTATED.format(env_id=self.cfg.get("env_id")))
         self.networks = None
         self.total = 0
@@ -88,7 +86,6 @@ class DeviceEnvSampler:
         self.info = {k: first[k] for k in _INFO if k in first}
         self.t = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self.fused = bool(fused)
-        self.path = None   # how the last sample() ran: "fused", or "loop: <why the kernel was not used>"
         self._fstate, self._fpool, self._frollout = None, None, None
 
     # ---- reset pool ---------------------------------------------------------------------------
@@ -104,11 +101,7 @@ class DeviceEnvSampler:
 
     def _hip_env(self):
         if self._henv is None:
-            if self.action_table is not None:   # no policy module to ask: the squash limits are the table's column extremes
-                low, high = self.action_table.min(dim=0).values, self.action_table.max(dim=0).values
-            else:
-                low, high = self.networks.policy.act_low_lim, self.networks.policy.act_high_lim
-            self._henv = self.env_model.hip_env(low.cpu().numpy(), high.cpu().numpy(), data_env=self.data_env)
+            self._henv = self.env_model.hip_env(*self._squash_limits(), data_env=self.data_env)
         return self._henv
 
     # ---- sampling -----------------------------------------------------------------------------
@@ -182,39 +175,32 @@ class DeviceEnvSampler:
         if self.action_table is not None:
             if not isinstance(policy, ActionValueDis):   # (StochaPolicyDis is one)
                 return "action table (discrete actions) behind a policy that is neither an ActionValueDis nor a StochaPolicyDis"
-            env = self._hip_env()
-            if env.kind == hb.ENV_MOBILEROBOT:
-                return "pyth_mobilerobot draws its obstacle noise per step"
+        else:
+            if isinstance(policy, StochaPolicyDis):
+                return "categorical policy"
+            for flag, name in (("is_poly", "POLY"), ("is_rbf", "GAUSS (RBF)"), ("is_lipsnet", "LipsNet")):
+                if getattr(policy, flag, False):
+                    return name + " policy"
+            if getattr(policy, "_time_input", False):
+                return "time-augmented policy"
+            if not isinstance(policy, (DetermPolicy, StochaPolicy)):
+                return "policy class outside the sample kernel's heads"
+            if isinstance(policy, StochaPolicy) and not issubclass(policy.action_distribution_cls, GaussDistribution):
+                return "action distribution outside the sample kernel's heads"
+        env = self._hip_env()
+        if env.kind == hb.ENV_MOBILEROBOT:
+            return "pyth_mobilerobot draws its obstacle noise per step"
+        if self.action_table is not None:
             if hb.lib().gops_sample_dis_workspace_bytes(ctypes.byref(env), ctypes.byref(policy.hip_mlp()), int(self.action_table.shape[0]),
                                                         self.n, self.steps) == 0:
                 # gops_hip.h lists them; gym_cartpoleconti with env_step="model" is one: the kernel steps it as a data env only
                 return ("action table: env / policy description outside the sample kernel (an env the kernel steps under the other "
                         "env_step only, constrained model, ActionRepeat, hidden widths, more than GOPS_DQN_MAX_ACTIONS actions)")
-            return None
-        if isinstance(policy, StochaPolicyDis):
-            return "categorical policy"
-        for flag, name in (("is_poly", "POLY"), ("is_rbf", "GAUSS (RBF)"), ("is_lipsnet", "LipsNet")):
-            if getattr(policy, flag, False):
-                return name + " policy"
-        if getattr(policy, "_time_input", False):
-            return "time-augmented policy"
-        if not isinstance(policy, (DetermPolicy, StochaPolicy)):
-            return "policy class outside the sample kernel's heads"
-        if isinstance(policy, StochaPolicy) and not issubclass(policy.action_distribution_cls, GaussDistribution):
-            return "action distribution outside the sample kernel's heads"
-        env = self._hip_env()
-        if env.kind == hb.ENV_MOBILEROBOT:
-            return "pyth_mobilerobot draws its obstacle noise per step"
-        if hb.lib().gops_sample_workspace_bytes(ctypes.byref(env), ctypes.byref(policy.hip_mlp()), self.n, self.steps) == 0:
+        elif hb.lib().gops_sample_workspace_bytes(ctypes.byref(env), ctypes.byref(policy.hip_mlp()), self.n, self.steps) == 0:
             # gops_hip.h lists them: the constrained vehicle models, ActionRepeat, scaled vehicle observations, hidden widths that are
             # no multiple of 16 or beyond the LDS plan, more than GOPS_MAX_ACT actions
             return "env / policy description outside the sample kernel (constrained model, ActionRepeat, hidden widths)"
         return None
-
-    def _policy_module(self):
-        """The network the kernel reads: `networks.policy`, or - DQN, whose `policy` is a plain function over it - `networks.q`."""
-        policy = self.networks.policy
-        return policy if isinstance(policy, torch.nn.Module) else getattr(self.networks, "q", policy)
 
     def _draw_fused_pool(self):
         """`pool_factor` reset states per instance, [R, N, ...]: the same draw as the loop's pool, reshaped; the counts start over."""
@@ -224,8 +210,25 @@ class DeviceEnvSampler:
         self._fpool = {k: v.reshape((R, N) + tuple(v.shape[1:])).contiguous() for k, v in pool.items() if k == "obs" or k in self.info}
         self._fstate["reset_count"].zero_()
 
+    def _fused_head(self, policy):
+        """What the fused path takes from the policy's class: (the kernel's head, the draw of a call's noise - standard normals
+        [T, N, action_dim], or [T, N, 2] uniforms for the discrete heads -, `SampleRollout`'s further keywords)."""
+        if self.action_table is not None:
+            categorical = isinstance(policy, StochaPolicyDis)
+            if categorical:
+                self._check_categorical()
+            return hb.SAMPLE_CATEGORICAL if categorical else hb.SAMPLE_EPS_GREEDY, torch.rand, dict(action_table=self.action_table)
+        stochastic = isinstance(policy, StochaPolicy)
+        if stochastic and self.noise_std > 0.0 and not self._warned_noise:
+            self._warned_noise = True
+            warnings.warn("DeviceEnvSampler: noise_std is ignored with a stochastic policy (it samples its own distribution)")
+        head = hb.SAMPLE_DETERM if not stochastic else \
+            hb.SAMPLE_TANH_GAUSS if issubclass(policy.action_distribution_cls, TanhGaussDistribution) else hb.SAMPLE_GAUSS
+        return head, torch.randn, dict(noise_std=0.0 if stochastic else self.noise_std, min_log_std=getattr(policy, "min_log_std", 0.0),
+                                       max_log_std=getattr(policy, "max_log_std", 0.0))
+
     def _sample_fused(self):
-        """One launch for all `steps` steps; -> the kernel's time-major output buffers ([T, N, ...] each)."""
+        """One noise draw, one launch for all `steps` steps, the 4-byte read; -> the kernel's time-major output buffers ([T, N, ...] each)."""
         policy = self._policy_module()
         T, N, R = self.steps, self.n, self.pool_factor
         st = self._fstate
@@ -238,44 +241,16 @@ class DeviceEnvSampler:
             self._fpool = None
         if self._fpool is None:
             self._draw_fused_pool()
-        if self.action_table is not None:
-            return self._sample_fused_dis(policy, st)
-        stochastic = isinstance(policy, StochaPolicy)
-        if stochastic and self.noise_std > 0.0 and not self._warned_noise:
-            self._warned_noise = True
-            warnings.warn("DeviceEnvSampler: noise_std is ignored with a stochastic policy (it samples its own distribution)")
+        head, draw, keywords = self._fused_head(policy)
         if self._frollout is None or (self._frollout.n_envs, self._frollout.steps) != (N, T):
-            head = hb.SAMPLE_DETERM if not stochastic else \
-                hb.SAMPLE_TANH_GAUSS if issubclass(policy.action_distribution_cls, TanhGaussDistribution) else hb.SAMPLE_GAUSS
-            self._frollout = hb.SampleRollout(self._hip_env(), policy.hip_mlp(), n_envs=N, steps=T, head=head,
-                                              max_episode_steps=self.max_steps, pool_rows=R, noise_std=0.0 if stochastic else self.noise_std,
-                                              min_log_std=getattr(policy, "min_log_std", 0.0), max_log_std=getattr(policy, "max_log_std", 0.0),
-                                              info_like=self.info, device=self.device)
+            self._frollout = hb.SampleRollout(self._hip_env(), policy.hip_mlp(), n_envs=N, steps=T, head=head, max_episode_steps=self.max_steps,
+                                              pool_rows=R, info_like=self.info, device=self.device, **keywords)
         ro = self._frollout
         ro.set_policy(policy.hip_mlp())
         ro.desc.max_episode_steps = int(self.max_steps)
-        noise = torch.randn((T, N, self._hip_env().act_dim), generator=self._gen, device=self.device)
-        out = ro.run(st, self._fpool, noise)
-        if pool_needs_refresh(int(st["reset_count"].max().item()), R):   # the one host read of a fused sample()
-            self._draw_fused_pool()
-        return out
-
-    def _sample_fused_dis(self, policy, st):
-        """The discrete heads: one `torch.rand` of [T, N, 2], one `gops_sample_rollout_dis` launch, the 4-byte read."""
-        T, N, R = self.steps, self.n, self.pool_factor
-        categorical = isinstance(policy, StochaPolicyDis)
-        if categorical:
-            self._check_categorical()
-        if self._frollout is None or (self._frollout.n_envs, self._frollout.steps) != (N, T):
-            self._frollout = hb.SampleRollout(self._hip_env(), policy.hip_mlp(), n_envs=N, steps=T,
-                                              head=hb.SAMPLE_CATEGORICAL if categorical else hb.SAMPLE_EPS_GREEDY,
-                                              max_episode_steps=self.max_steps, pool_rows=R, info_like=self.info, device=self.device,
-                                              action_table=self.action_table)
-        ro = self._frollout
-        ro.set_policy(policy.hip_mlp())
-        ro.desc.max_episode_steps = int(self.max_steps)
-        ro.dis.epsilon = float(self.epsilon)
-        noise = torch.rand((T, N, 2), generator=self._gen, device=self.device)
+        if ro.dis is not None:   # (read at every call, as max_episode_steps is: DQN anneals it)
+            ro.dis.epsilon = float(self.epsilon)
+        noise = draw((T, N, ro.noise_width), generator=self._gen, device=self.device)
         out = ro.run(st, self._fpool, noise)
         if pool_needs_refresh(int(st["reset_count"].max().item()), R):   # the one host read of a fused sample()
             self._draw_fused_pool()
@@ -287,9 +262,7 @@ class DeviceEnvSampler:
         return {k: out[k].flatten(0, 1) for k in keys}
 
     def _choose_path(self) -> bool:
-        why = self.kernel_refuses() if self.fused else "fused=False"
-        self.path = "fused" if why is None else "loop: " + why
-        return why is None
+        return self._set_path(self.kernel_refuses() if self.fused else "fused=False")
 
     @torch.no_grad()
     def sample(self):

@@ -5,6 +5,8 @@ are literals (GOPS_ERR_BAD_ARG -1, GOPS_ERR_UNSUPPORTED -2, GOPS_ERR_WORKSPACE -
 recorded from the library as it stood when every one of these entry points was a trampoline in api.hip; the same table passes
 against that library and against the one that defines each entry point beside its kernels."""
 import ctypes as C
+import json
+import os
 
 import pytest
 
@@ -452,3 +454,131 @@ def test_table_covers_every_entry_point_beside_its_kernels():
     for name, ids in rows.items():
         assert any("null" in i for i in ids) or name in ("gops_rpi_state_bytes",), name   # (two integers: no pointer to leave out)
         assert any(k in i for i in ids for k in ("batch0", "-n0", "episodes0", "steps0")), name
+
+
+# ---- the closed-loop pair: rollout_sample.hip and rollout_episode.hip share one admission check ----------------------------------
+# Every single fault that check names, and every pair of a GOPS_ERR_UNSUPPORTED fault with a GOPS_ERR_BAD_ARG fault (the pairs fix the
+# order of the tests), through the four entry points and the four workspace queries.  A fault is a set of knobs over one valid base
+# description (gym_cartpoleconti as a data env, a 4-16-A net); the workspace pointer is null, so a description that passes every
+# check is refused with GOPS_ERR_WORKSPACE before any HIP call.  The codes (the bytes, for a query) were recorded from the library
+# as it stood when each kernel had a check of its own: tests/golden/closed_loop_refusals.json (`PYTHONPATH=. python
+# tests/test_refusals_cpu.py` rewrites it from the library that is loaded).
+CLOSED_LOOP_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "closed_loop_refusals.json")
+CLOSED_LOOP_ENTRIES = {   # entry point: (the entry point whose single-fault codes choose its pairs, takes an action table)
+    "gops_sample_workspace_bytes": ("gops_sample_rollout", False), "gops_sample_dis_workspace_bytes": ("gops_sample_rollout_dis", True),
+    "gops_episode_workspace_bytes": ("gops_episode_rollout", False), "gops_episode_dis_workspace_bytes": ("gops_episode_rollout_dis", True),
+    "gops_sample_rollout": ("gops_sample_rollout", False), "gops_sample_rollout_dis": ("gops_sample_rollout_dis", True),
+    "gops_episode_rollout": ("gops_episode_rollout", False), "gops_episode_rollout_dis": ("gops_episode_rollout_dis", True)}
+_BASE = dict(kind=hb.ENV_CARTPOLE, O=4, A=1, P=0, data_env=1, cstr_err=0, repeat_num=0, scale_obs=0, in_delta=0, hidden=(16,), out="base",
+             n_layers=None, dtype=0, hidden_act=ELU, null_weight=None, null_bias=None, act_num=3, head=None, eps=0.25, table=P, N=4, T=2)
+
+
+def _env_knobs(kind, O, A, P=0, **more):
+    return dict(kind=kind, O=O, A=A, P=P, **more)
+
+
+CLOSED_LOOP_FAULTS = {
+    "none": {},
+    "envs0": dict(N=0), "steps0": dict(T=0),
+    # each kind neither kernel steps; a model kind as a data env and the reverse
+    "kind-none": _env_knobs(hb.ENV_NONE, 4, 1), "kind-veh-surr": _env_knobs(hb.ENV_VEH_SURR, 14, 2, 1),
+    "kind-mobilerobot": _env_knobs(hb.ENV_MOBILEROBOT, 13, 2), "kind-above-max": _env_knobs(hb.ENV_MOUNTAINCAR + 1, 4, 1),
+    "pendulum-data-env": _env_knobs(hb.ENV_PENDULUM, 3, 1), "mountaincar-data-env": _env_knobs(hb.ENV_MOUNTAINCAR, 2, 1),
+    "pendulum-model": _env_knobs(hb.ENV_PENDULUM, 3, 1, data_env=0), "mountaincar-model": _env_knobs(hb.ENV_MOUNTAINCAR, 2, 1, data_env=0),
+    "cartpole-model": dict(data_env=0), "lq-model": _env_knobs(hb.ENV_LQ, 2, 1, data_env=0),
+    "cstr_err": dict(cstr_err=1), "repeat2": dict(repeat_num=2),
+    "one-layer": dict(hidden=()), "fp16": dict(dtype=1),
+    "act_dim0": dict(A=0), "act_dim-above-max": dict(A=hb.MAX_ACT + 1), "obs_dim0": dict(O=0),
+    "lq-wide": _env_knobs(hb.ENV_LQ, hb.MAX_LQ + 1, 1),
+    # the per-kind shape table
+    "idp-obs": _env_knobs(hb.ENV_IDP, 5, 1), "idp-act": _env_knobs(hb.ENV_IDP, 6, 2),
+    "cartpole-obs": dict(O=5), "cartpole-act": dict(A=2),
+    "pendulum-obs": _env_knobs(hb.ENV_PENDULUM, 4, 1, data_env=0), "pendulum-act": _env_knobs(hb.ENV_PENDULUM, 3, 2, data_env=0),
+    "mountaincar-obs": _env_knobs(hb.ENV_MOUNTAINCAR, 3, 1, data_env=0), "mountaincar-act": _env_knobs(hb.ENV_MOUNTAINCAR, 2, 2, data_env=0),
+    "veh-horizon0": _env_knobs(hb.ENV_VEH, 6, 2, 0), "veh-obs": _env_knobs(hb.ENV_VEH, 13, 2, 2), "veh-act": _env_knobs(hb.ENV_VEH, 14, 1, 2),
+    "veh2dof-horizon0": _env_knobs(hb.ENV_VEH2DOF, 4, 1, 0), "veh2dof-obs": _env_knobs(hb.ENV_VEH2DOF, 7, 1, 2),
+    "veh2dof-act": _env_knobs(hb.ENV_VEH2DOF, 6, 2, 2),
+    "scale_obs-veh": _env_knobs(hb.ENV_VEH, 14, 2, 2, scale_obs=1), "scale_obs-veh2dof": _env_knobs(hb.ENV_VEH2DOF, 6, 1, 2, scale_obs=1),
+    "scale_obs-wide": _env_knobs(hb.ENV_LQ, 9, 1, scale_obs=1), "scale_obs-cartpole": dict(scale_obs=1),
+    "layers0": dict(n_layers=0), "layers-above-max": dict(hidden=(16,) * (hb.MAX_LAYERS - 1), n_layers=hb.MAX_LAYERS + 1),
+    "time-input": dict(in_delta=1), "input-width": dict(in_delta=2),
+    # output widths: base is A (act_num with a table); the Gaussian heads want 2A, the deterministic one A
+    "output-plus1": dict(out="plus1"), "output-double": dict(out="double"), "output-3": dict(out=3),
+    "gauss-width-A": dict(head=hb.SAMPLE_GAUSS), "gauss-width-2A": dict(head=hb.SAMPLE_GAUSS, out="double"),
+    "gauss-odd-width": _env_knobs(hb.ENV_VEH, 14, 2, 2, head=hb.SAMPLE_TANH_GAUSS, out=3),
+    "head-above-max": dict(head=7), "head-negative": dict(head=-1),
+    "hidden-24": dict(hidden=(24,)), "hidden-8": dict(hidden=(8,)), "hidden-second-40": dict(hidden=(16, 40)),
+    "activation-above-max": dict(hidden_act=TANH + 1), "activation-negative": dict(hidden_act=-1), "activation-poly": dict(hidden_act=hb.POLY_FULL[2]),
+    "null-weight": dict(null_weight=0), "null-bias": dict(null_bias=1),
+    "act_num1": dict(act_num=1), "act_num-above-max": dict(act_num=hb.DQN_MAX_ACTIONS + 1), "act_num0": dict(act_num=0),
+    "epsilon-nan": dict(eps=float("nan")), "epsilon-negative": dict(eps=-0.01), "epsilon-above-1": dict(eps=1.01),
+    "epsilon-categorical": dict(head=hb.SAMPLE_CATEGORICAL), "categorical": dict(head=hb.SAMPLE_CATEGORICAL, eps=0.0),
+    "null-table": dict(table=None),
+}
+
+
+def _closed_loop_call(name, knobs):
+    k = {**_BASE, **knobs}
+    dis = CLOSED_LOOP_ENTRIES[name][1]
+    env = _env(k["kind"], k["O"], k["A"], pre_horizon=k["P"], data_env=k["data_env"], cstr_err=k["cstr_err"], repeat_num=k["repeat_num"],
+               scale_obs=k["scale_obs"])
+    base_out = k["act_num"] if dis else k["A"]
+    out_w = {"base": base_out, "plus1": base_out + 1, "double": 2 * base_out}.get(k["out"], k["out"])
+    pol = _mlp([k["O"] + k["in_delta"], *k["hidden"], out_w], act=k["hidden_act"], dtype=k["dtype"])
+    if k["n_layers"] is not None:
+        pol.n_layers = k["n_layers"]
+    if k["null_weight"] is not None:
+        pol.weight[k["null_weight"]] = 0
+    if k["null_bias"] is not None:
+        pol.bias[k["null_bias"]] = 0
+    ref, N, T = C.byref, k["N"], k["T"]
+    if name.endswith("workspace_bytes"):
+        return getattr(hb.lib(), name)(ref(env), ref(pol), *((k["act_num"],) if dis else ()), N, T)
+    if "episode" in name:
+        tail = (N, T, ref(_io()), ref(_all_ptrs(hb.GopsEpisodeOut)), None, 0, None)
+        return getattr(hb.lib(), name)(ref(env), ref(pol), *((k["table"], k["act_num"]) if dis else ()), *tail)
+    head = k["head"]
+    desc = hb.GopsSampleDesc(head=0 if dis or head is None else head, max_episode_steps=3, pool_rows=2, min_log_std=-20.0, max_log_std=0.5)
+    d = hb.GopsSampleDis(action_table=k["table"], act_num=k["act_num"], head=hb.SAMPLE_EPS_GREEDY if head is None else head,
+                         epsilon=k["eps"], env_act=P)
+    tail = (N, T, ref(_all_ptrs(hb.GopsSampleState)), ref(_all_ptrs(hb.GopsSamplePool)), P, ref(_all_ptrs(hb.GopsSampleOut)), None, 0, None)
+    return getattr(hb.lib(), name)(ref(env), ref(pol), ref(desc), *((ref(d),) if dis else ()), *tail)
+
+
+def _closed_loop_codes(name, single_of_chooser):
+    """{"single": {fault: code}, "pair": {unsupported fault: {bad-arg fault: code}}} of one entry point.  A pair is taken where the
+    two faults turn different knobs, so that both are present in the description."""
+    single = {f: _closed_loop_call(name, knobs) for f, knobs in CLOSED_LOOP_FAULTS.items()}
+    uns = [f for f, c in single_of_chooser.items() if c == UNS]
+    bad = [f for f, c in single_of_chooser.items() if c == BAD]
+    pair = {}
+    for u in uns:
+        for b in bad:
+            ku, kb = CLOSED_LOOP_FAULTS[u], CLOSED_LOOP_FAULTS[b]
+            if not set(ku) & set(kb):
+                pair.setdefault(u, {})[b] = _closed_loop_call(name, {**ku, **kb})
+    return dict(single=single, pair=pair)
+
+
+@pytest.mark.parametrize("name", sorted(CLOSED_LOOP_ENTRIES))
+def test_closed_loop_refusal_codes_are_those_recorded(name):
+    with open(CLOSED_LOOP_GOLDEN) as f:
+        golden = json.load(f)
+    want = golden[name]
+    assert sorted(want["single"]) == sorted(CLOSED_LOOP_FAULTS)
+    assert sum(len(v) for v in want["pair"].values()) >= 100   # (the pairs are there)
+    if not name.endswith("workspace_bytes"):   # a refusal each: nothing launches
+        assert all(c in (BAD, UNS, WS) for c in want["single"].values())
+        assert all(c in (BAD, UNS) for v in want["pair"].values() for c in v.values())
+    got = _closed_loop_codes(name, golden[CLOSED_LOOP_ENTRIES[name][0]]["single"])
+    diff = {f: (got["single"][f], c) for f, c in want["single"].items() if got["single"][f] != c}
+    diff.update({u + "+" + b: (got["pair"][u][b], c) for u, v in want["pair"].items() for b, c in v.items() if got["pair"][u][b] != c})
+    assert not diff, diff   # fault: (code now, code recorded)
+    assert got == want
+
+
+if __name__ == "__main__":
+    first = {n: {f: _closed_loop_call(n, k) for f, k in CLOSED_LOOP_FAULTS.items()} for n in CLOSED_LOOP_ENTRIES}
+    with open(CLOSED_LOOP_GOLDEN, "w") as f:
+        json.dump({n: _closed_loop_codes(n, first[CLOSED_LOOP_ENTRIES[n][0]]) for n in sorted(CLOSED_LOOP_ENTRIES)}, f, indent=0, sort_keys=True)
+        f.write("\n")
