@@ -1,7 +1,7 @@
 """create_evaluator: evaluators keyed by name (surface of gops/create_pkg/create_evaluator.py:30-61).  "evaluator" builds
 `gops_amd.trainer.evaluator.Evaluator` in-process - no Ray actor - from the reference's kwargs (`num_eval_episode`, `eval_save`,
-`save_folder`, `seed`, `is_render`) plus either `env_model` and `networks` (the learner's own) or the kwargs `create_alg` takes, from
-which both are built."""
+`save_folder`, `seed`, `is_render`; of its own `max_episode_steps`, `fused`, `action_table`, `stochastic_mode`) plus either
+`env_model` and `networks` (the learner's own) or the kwargs `create_alg` takes, from which both are built."""
 from gops_amd.create_pkg._registry import Registry
 
 registry = Registry("evaluator")
@@ -30,7 +30,7 @@ def _build_evaluator(**kwargs):
                      num_eval_episode=kwargs.pop("num_eval_episode"), eval_save=kwargs.pop("eval_save", True),
                      save_folder=kwargs.pop("save_folder", None), seed=kwargs.pop("seed", 0) or 0,
                      max_episode_steps=kwargs.pop("max_episode_steps", None), fused=kwargs.pop("fused", True),
-                     action_table=kwargs.pop("action_table", None))
+                     action_table=kwargs.pop("action_table", None), stochastic_mode=kwargs.pop("stochastic_mode", False))
 
 
 register("evaluator", _build_evaluator)

@@ -9,6 +9,8 @@
 //      between two LDS tiles; weights are read in place from the live parameter tensors - staged in LDS once per launch when the
 //      whole network fits next to the tiles, else streamed from L2 every step;
 //   3. 16 lanes per episode form the head's dot products (DPP sum), lane a squashes action a (tanh, act limits) and stores it;
+//      with a mode head (gops_episode_rollout_mode) the stack is 2A wide - A means, then A log stds - and lane a stores the mode
+//      of the action distribution, formed from mean a alone (the log-std rows take part in no dot product);
 //      with an action table (gops_episode_rollout_dis) the outputs are action values / logits: lane a stores component a of the
 //      table's row at their arg-max, and the trace keeps the index;
 //   4. one lane per episode takes the data env's step through env_step_one (env_step.h) - the function env_step_kernel calls, so
@@ -45,6 +47,7 @@ struct EpisodeParams {
     float* reft[2];
     float *action, *reward, *done;
     GopsEpisodeOut out;
+    int head;             // GOPS_SAMPLE_DETERM, or a mode head over a 2A-wide stack: GOPS_SAMPLE_GAUSS / _TANH_GAUSS
     int act_num;          // the greedy head over an action table (0: none)
     const float* table;   // [act_num, A], device memory
 };
@@ -78,6 +81,8 @@ EpisodeLayout episode_layout(const GopsEnv& e, int E) {
 // Evaluation steps the DATA environment (pendulum, mountaincar: no data-env restatement); a FiniteHorizonPolicy's time input is
 // taken (virtual_t = 1); output width A, the deterministic head's.
 constexpr ClosedLoopRules EPISODE_RULES = {CLOSED_LOOP_DATA_KINDS, 0, true, false};
+// The mode heads: the same, with the sampler's width rule (the entry point then holds the width against 2A).
+constexpr ClosedLoopRules EPISODE_MODE_RULES = {CLOSED_LOOP_DATA_KINDS, 0, true, true};
 
 __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -146,9 +151,16 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
             policy_tile_head(p.net, lds, cur_x, m, part, 0, A, y);
             if (part < A && m < nvalid) {
                 const float ya = (part == 0 ? y[0] : part == 1 ? y[1] : part == 2 ? y[2] : y[3]) + lds[p.net.b_off[nl - 1] + part];
-                const float sc = (p.env.policy_high[part] - p.env.policy_low[part]) / 2.f;
-                const float of = (p.env.policy_high[part] + p.env.policy_low[part]) / 2.f;
-                const float act = sc * tanhf(ya) + of;
+                const float lo = p.env.policy_low[part], hi = p.env.policy_high[part];
+                float act;
+                if (p.head == GOPS_SAMPLE_GAUSS) {   // GaussDistribution.mode: clamp(mean, low, high); a NaN stays one
+                    act = ya < lo ? lo : ya;
+                    act = act > hi ? hi : act;
+                } else {   // the deterministic head, and TanhGaussDistribution.mode: the same squash of the mean
+                    const float sc = (hi - lo) / 2.f;
+                    const float of = (hi + lo) / 2.f;
+                    act = sc * tanhf(ya) + of;
+                }
                 p.action[(size_t)(e0 + m) * A + part] = act;
                 if (p.out.trace_act != nullptr && s_alive[m]) p.out.trace_act[((size_t)(e0 + m) * p.T + t) * A + part] = act;
             }
@@ -187,9 +199,9 @@ __global__ __launch_bounds__(EP_THREADS) void episode_kernel(const EpisodeParams
     }
 }
 
-// What both entry points do once the description passed: the pointer checks, the workspace, the launch.
-int episode_launch(const GopsEnv* env, const GopsMlp* policy, const float* table, int act_num, int E, int T, const GopsStepIO* init,
-                   const GopsEpisodeOut* out, void* ws, size_t ws_bytes, void* stream) {
+// What the entry points do once the description passed: the pointer checks, the workspace, the launch.
+int episode_launch(const GopsEnv* env, const GopsMlp* policy, int head, const float* table, int act_num, int E, int T,
+                   const GopsStepIO* init, const GopsEpisodeOut* out, void* ws, size_t ws_bytes, void* stream) {
     if (!init || !out || !init->obs || !out->ret || !out->length || !out->terminated) return GOPS_ERR_BAD_ARG;
     const bool ref = env_has_ref_table(env->kind);
     if (ref && (!init->state || !init->ref_points || !init->path_num || !init->u_num || !init->ref_time)) return GOPS_ERR_BAD_ARG;
@@ -217,9 +229,17 @@ int episode_launch(const GopsEnv* env, const GopsMlp* policy, const float* table
     }
     p.action = f + l.action, p.reward = f + l.reward, p.done = f + l.done;
     p.out = *out;
-    p.act_num = act_num, p.table = table;
+    p.head = head, p.act_num = act_num, p.table = table;
     launch_with_lds(episode_kernel, dim3((unsigned)((E + GOPS_TILE - 1) / GOPS_TILE)), dim3(EP_THREADS), lds, static_cast<hipStream_t>(stream), p);
     return (int)hipGetLastError();
+}
+
+// gops_episode_rollout_mode's description: a Gaussian head code, the shared check, output width 2A (an odd one is refused here).
+int episode_mode_check(const GopsEnv* env, const GopsMlp* policy, int head, int E, int T) {
+    if (head != GOPS_SAMPLE_GAUSS && head != GOPS_SAMPLE_TANH_GAUSS) return GOPS_ERR_BAD_ARG;
+    const int rc = closed_loop_check(EPISODE_MODE_RULES, env, policy, E, T, 0);
+    if (rc != GOPS_OK) return rc;
+    return policy->sizes[policy->n_layers] == 2 * env->act_dim ? GOPS_OK : GOPS_ERR_BAD_ARG;
 }
 
 }  // namespace
@@ -239,7 +259,7 @@ int gops_episode_rollout(const GopsEnv* env, const GopsMlp* policy, int32_t E, i
                          void* ws, size_t ws_bytes, void* stream) {
     const int rc = closed_loop_check(EPISODE_RULES, env, policy, E, T, 0);
     if (rc != GOPS_OK) return rc;
-    return episode_launch(env, policy, nullptr, 0, E, T, init, out, ws, ws_bytes, stream);
+    return episode_launch(env, policy, GOPS_SAMPLE_DETERM, nullptr, 0, E, T, init, out, ws, ws_bytes, stream);
 }
 
 int gops_episode_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const float* action_table, int32_t act_num, int32_t E, int32_t T,
@@ -248,7 +268,19 @@ int gops_episode_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const fl
     if (act_num < 2 || act_num > GOPS_DQN_MAX_ACTIONS) return GOPS_ERR_UNSUPPORTED;
     const int rc = closed_loop_check(EPISODE_RULES, env, policy, E, T, act_num);   // (BAD_ARG for an output width other than act_num)
     if (rc != GOPS_OK) return rc;
-    return episode_launch(env, policy, action_table, act_num, E, T, init, out, ws, ws_bytes, stream);
+    return episode_launch(env, policy, GOPS_SAMPLE_DETERM, action_table, act_num, E, T, init, out, ws, ws_bytes, stream);
+}
+
+size_t gops_episode_mode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t head, int32_t E, int32_t T) {
+    PolicyTile net;
+    return episode_mode_check(env, policy, head, E, T) == GOPS_OK && policy_tile_plan(*policy, net) != 0 ? episode_layout(*env, E).bytes : 0;
+}
+
+int gops_episode_rollout_mode(const GopsEnv* env, const GopsMlp* policy, int32_t head, int32_t E, int32_t T, const GopsStepIO* init,
+                              const GopsEpisodeOut* out, void* ws, size_t ws_bytes, void* stream) {
+    const int rc = episode_mode_check(env, policy, head, E, T);
+    if (rc != GOPS_OK) return rc;
+    return episode_launch(env, policy, head, nullptr, 0, E, T, init, out, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -273,6 +273,8 @@ def _signatures():
                                          vp, P(GopsSampleOut), vp, sz, vp]),
         "gops_episode_dis_workspace_bytes": (sz, [env, mlp, i32, i32, i32]),
         "gops_episode_rollout_dis": (rc, [env, mlp, vp, i32, i32, i32, io, P(GopsEpisodeOut), vp, sz, vp]),
+        "gops_episode_mode_workspace_bytes": (sz, [env, mlp, i32, i32, i32]),
+        "gops_episode_rollout_mode": (rc, [env, mlp, i32, i32, i32, io, P(GopsEpisodeOut), vp, sz, vp]),
         "gops_lips_workspace_bytes": (sz, [lips, i32]),
         "gops_lips_forward": (rc, [lips, i32, vp, vp, vp, vp, vp, sz, vp]),
         "gops_lips_backward": (rc, [lips, i32, vp, vp, P(GopsLipsGrad), vp, sz, vp]),
@@ -1064,20 +1066,37 @@ class EpisodeRollout:
     termination, time limit and return of `episodes` episodes over up to `max_steps` steps.  `env` must carry data_env = 1; the policy
     weights are read in place at every call.  A description the kernel refuses raises (GOPS_ERR_UNSUPPORTED / _BAD_ARG).
     `action_table` [act_num, act_dim] (device tensor): the greedy head over a discrete action set (`gops_episode_rollout_dis`) - the
-    policy's outputs are action values or logits, the env steps with the table's row at their arg-max, trace_act [E, T, 1] is the index."""
+    policy's outputs are action values or logits, the env steps with the table's row at their arg-max, trace_act [E, T, 1] is the index.
+    `mode_head` SAMPLE_GAUSS / SAMPLE_TANH_GAUSS: a stochastic policy's 2A-wide stack (mean, log std) acts with the mode of its action
+    distribution (`gops_episode_rollout_mode`); `act_low` / `act_high` [act_dim] then replace the limits `env` carries (in a copy)."""
 
     def __init__(self, env: GopsEnv, policy: GopsMlp, *, episodes: int, max_steps: int, device: Optional[torch.device] = None,
-                 workspace_bytes: Optional[int] = None, action_table: Optional[torch.Tensor] = None):
+                 workspace_bytes: Optional[int] = None, action_table: Optional[torch.Tensor] = None, mode_head: Optional[int] = None,
+                 act_low=None, act_high=None):
+        if mode_head is None:
+            assert act_low is None and act_high is None, "act_low / act_high belong to a mode head"
+        else:
+            assert action_table is None, "a mode head acts without an action table"
+            if mode_head not in (SAMPLE_GAUSS, SAMPLE_TANH_GAUSS):
+                raise ValueError(f"EpisodeRollout: mode_head {mode_head!r} is neither SAMPLE_GAUSS nor SAMPLE_TANH_GAUSS")
+            if act_low is not None or act_high is not None:   # the limits travel as the deterministic head's do: in the description
+                env = GopsEnv.from_buffer_copy(env)
+                for field, lim in ((env.policy_low, act_low), (env.policy_high, act_high)):
+                    if lim is not None:
+                        _fill(field, np.broadcast_to(np.asarray(torch.as_tensor(lim).detach().cpu(), dtype=np.float32).reshape(-1), (env.act_dim,)))
         self.env, self.policy, self.episodes, self.max_steps = env, policy, int(episodes), int(max_steps)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.action_table = action_table
-        # the one place that knows which of the two forms this is: the query, the entry point, the arguments only `_dis` takes
+        # the one place that knows which of the three forms this is: the query, the entry point, the arguments only `_dis` / `_mode` take
         query, self._name, query_extra, self._extra, self._act_width = "gops_episode_workspace_bytes", "gops_episode_rollout", (), (), env.act_dim
         if action_table is not None:
             assert action_table.dim() == 2 and action_table.shape[1] == env.act_dim, "action_table must be [act_num, act_dim]"
             self.act_num = int(action_table.shape[0])
             query, self._name, self._act_width = "gops_episode_dis_workspace_bytes", "gops_episode_rollout_dis", 1
             query_extra, self._extra = (self.act_num,), (_ptr(action_table), self.act_num)
+        elif mode_head is not None:
+            query, self._name = "gops_episode_mode_workspace_bytes", "gops_episode_rollout_mode"
+            query_extra = self._extra = (int(mode_head),)
         nbytes = getattr(lib(), query)(C.byref(env), C.byref(policy), *query_extra, self.episodes, self.max_steps)
         if workspace_bytes is None:
             if nbytes == 0:   # ask the entry point itself for the reason

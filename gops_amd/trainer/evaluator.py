@@ -18,6 +18,11 @@ Discrete action sets: with `action_table` [act_num, action_dim] the evaluated ne
 StochaPolicyDis (discrete TRPO's `networks.policy`); every step acts with `action_table[argmax(outputs)]` - the `mode()` of both
 ValueDiracDistribution and CategoricalDistribution, the lowest index among equal maxima - through `gops_episode_rollout_dis`, or the
 same arg-max + table gather in the per-step loop; `trace_act` is the index, [E, T, 1].
+
+Stochastic policies (`StochaPolicy`: SAC, DSAC, DSAC-T, PPO, TRPO) are evaluated with the `mode()` of their action distribution.  By
+default they run the per-step loop (`path` = "loop: stochastic policy"); `stochastic_mode=True` takes them into the kernel through
+`gops_episode_rollout_mode`: the 2A-wide stack's mean half, clamped to the policy's limits (GaussDistribution) or tanh-squashed into
+them (TanhGaussDistribution).  Any other distribution class, or a log std outside the shared stack, stays on the loop.
 """
 import ctypes
 import os
@@ -30,6 +35,7 @@ from gops_amd.algorithm.base import is_poly
 from gops_amd.apprfunc.mlp import ActionValueDis, StochaPolicy, StochaPolicyDis
 from gops_amd.trainer.closed_loop import ClosedLoopDriver
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, NOT_RESTATED, draw_reset_pool
+from gops_amd.utils.act_distribution import GaussDistribution, TanhGaussDistribution
 
 # TimeLimit of the data envs where create_env registers one (gops/create_pkg/create_env.py:142-148 takes the env's own
 # `max_episode_steps` attribute): pyth_idpendulum.py:51, pyth_veh3dofconti.py:114, pyth_veh2dofconti.py:105,
@@ -51,11 +57,12 @@ class Evaluator(ClosedLoopDriver):
 
     def __init__(self, index=0, *, env_model, networks, cfg: dict, num_eval_episode: int, eval_save: bool = True,
                  save_folder=None, seed: int = 0, max_episode_steps: int = None, device="cuda", fused: bool = True, action_table=None,
-                 **kwargs):
+                 stochastic_mode: bool = False, **kwargs):
         """cfg: workload dict (env_id, pre_horizon, lq_config) as `DeviceEnvSampler` takes it; env_model: the wrapped model of
         `create_env_model`; networks: the learner's container (its `policy` is evaluated in place).  `max_episode_steps`: None =
         the data env's registered limit, else 200.  `fused=False` forces the per-step loop.  `action_table` [act_num, action_dim]:
-        evaluate a discrete policy (see the module docstring); without one an ActionValueDis is refused."""
+        evaluate a discrete policy (see the module docstring); without one an ActionValueDis is refused.  `stochastic_mode=True`: a
+        StochaPolicy acts by its distribution's mode inside the kernel instead of on the per-step loop."""
         self.cfg, self.env_model, self.networks = dict(cfg), env_model, networks
         self.device = torch.device(device)
         self._take_action_table(action_table)
@@ -66,6 +73,10 @@ class Evaluator(ClosedLoopDriver):
         elif isinstance(getattr(networks, "q", None), ActionValueDis):
             raise NotImplementedError("Evaluator runs closed loops with continuous actions only: an ActionValueDis policy (DQN) emits "
                                       "action values over a discrete action set, and no action table is part of the evaluator")
+        self.stochastic_mode = bool(stochastic_mode)
+        if self.stochastic_mode and (self.action_table is not None or not isinstance(self._policy_module(), StochaPolicy)):
+            raise ValueError("Evaluator: stochastic_mode=True evaluates a StochaPolicy by the mode of its action distribution; it goes "
+                             "with neither an action table nor a deterministic policy")
         base = getattr(env_model, "unwrapped", env_model)
         if getattr(base, "ref_c", None) is not None:
             raise RuntimeError("Evaluator draws its initial states from the DEFAULT reference trajectories "
@@ -98,15 +109,33 @@ class Evaluator(ClosedLoopDriver):
             self._henv = env
         return self._henv
 
+    def _mode_head(self):
+        """(head code of `gops_episode_rollout_mode`, None) for this evaluator's StochaPolicy, or (None, why it has none)."""
+        pol = self._policy_module()
+        if getattr(pol, "std_type", "mlp_shared") != "mlp_shared":
+            return None, f"stochastic policy whose log std (std_type {pol.std_type!r}) is not the second half of the shared stack"
+        cls = pol.action_distribution_cls   # (`is`: a subclass may state another mode)
+        if cls is TanhGaussDistribution:
+            return hb.SAMPLE_TANH_GAUSS, None
+        if cls is GaussDistribution:
+            return hb.SAMPLE_GAUSS, None
+        return None, f"stochastic policy with a {getattr(cls, '__name__', cls)} (the mode heads: GaussDistribution, TanhGaussDistribution)"
+
     def kernel_refuses(self):
-        """None when `gops_episode_rollout` (`_dis` with an action table) takes this evaluator's env and policy, else the reason."""
+        """None when `gops_episode_rollout` (`_dis` with an action table, `_mode` with `stochastic_mode`) takes this evaluator's env
+        and policy, else the reason."""
         pol = self._policy_module()
         if is_poly(pol):
             return "POLY policy"
         if getattr(pol, "is_lipsnet", False):
             return "LipsNet policy"
-        if isinstance(pol, StochaPolicy):   # (its stack emits (mean, log std): the episode kernel squashes a deterministic head)
-            return "stochastic policy"
+        head = None
+        if isinstance(pol, StochaPolicy):   # (its stack emits (mean, log std): the mode heads read the mean half, on request)
+            if not self.stochastic_mode:
+                return "stochastic policy"
+            head, why = self._mode_head()
+            if why is not None:
+                return why
         env = self._hip_env()
         if env.kind == hb.ENV_MOBILEROBOT:
             return "pyth_mobilerobot draws its obstacle noise per step"
@@ -114,7 +143,9 @@ class Evaluator(ClosedLoopDriver):
             if hb.lib().gops_episode_dis_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), int(self.action_table.shape[0]), 1, 1) == 0:
                 return "env / policy description outside the episode kernel (more than GOPS_DQN_MAX_ACTIONS actions, hidden widths)"
             return None
-        if hb.lib().gops_episode_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), 1, 1) == 0:
+        nbytes = hb.lib().gops_episode_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), 1, 1) if head is None else \
+            hb.lib().gops_episode_mode_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), head, 1, 1)
+        if nbytes == 0:
             # gops_hip.h lists them: ScaleObservation on the vehicle families or beyond 8 observations, ActionRepeat, hidden widths
             # that are no multiple of 16 or beyond the LDS plan (~1100)
             return "env / policy description outside the episode kernel (scaled vehicle observations, hidden widths)"
@@ -136,11 +167,12 @@ class Evaluator(ClosedLoopDriver):
         if self._set_path(self.kernel_refuses() if fused else "fused=False"):
             E = init["obs"].shape[0]
             mlp = self._policy_module().hip_mlp()
-            key = (E, self.max_episode_steps)
+            head = self._mode_head()[0] if self.stochastic_mode else None   # (part of the key: a rollout is built for one head)
+            key = (E, self.max_episode_steps, head)
             ro = self._rollouts.get(key)
             if ro is None:
                 ro = self._rollouts[key] = hb.EpisodeRollout(self._hip_env(), mlp, episodes=E, max_steps=self.max_episode_steps,
-                                                             device=self.device, action_table=self.action_table)
+                                                             device=self.device, action_table=self.action_table, mode_head=head)
             ro.set_policy(mlp)
             self.last = ro.run(init, trace=trace, trace_fill=trace_fill)
         else:

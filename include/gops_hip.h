@@ -746,6 +746,21 @@ int gops_episode_rollout_dis(const GopsEnv* env, const GopsMlp* policy, const fl
                              int32_t max_steps, const GopsStepIO* init, const GopsEpisodeOut* out, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): the evaluator over a STOCHASTIC policy - gops_episode_rollout with
+ * a_t = the mode() of the policy's action distribution.  The policy stack has output width 2A, y = (mean [A], raw log std [A]) as
+ * gops_sample_rollout's Gaussian heads take it; the action is formed from the mean half alone (the log-std rows are part of the
+ * stack and of no dot product), with (lo, hi) = env->policy_low / policy_high as for gops_episode_rollout's squash:
+ *     GOPS_SAMPLE_GAUSS       a = clamp(mean, lo, hi)                          (GaussDistribution.mode; a NaN mean stays a NaN)
+ *     GOPS_SAMPLE_TANH_GAUSS  a = (hi - lo) / 2 tanh(mean) + (hi + lo) / 2     (TanhGaussDistribution.mode)
+ * in fp32.  trace_act is [E][max_steps][A]: that action.  Everything else - init, out, the env kinds, the data-env step, the books,
+ * the workspace, one kernel body - as gops_episode_rollout.  GOPS_ERR_BAD_ARG, nothing launched: any other head, an output width
+ * other than 2A (A and odd widths included) and gops_episode_rollout's cases; GOPS_ERR_UNSUPPORTED and GOPS_ERR_WORKSPACE as for
+ * gops_episode_rollout (the workspace is tested after everything else).  gops_episode_rollout itself keeps refusing a 2A-wide stack.
+ * gops_episode_mode_workspace_bytes: 0 for a description gops_episode_rollout_mode rejects. */
+size_t gops_episode_mode_workspace_bytes(const GopsEnv* env, const GopsMlp* policy, int32_t head, int32_t episodes, int32_t max_steps);
+int gops_episode_rollout_mode(const GopsEnv* env, const GopsMlp* policy, int32_t head, int32_t episodes, int32_t max_steps,
+                              const GopsStepIO* init, const GopsEpisodeOut* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ABI v15, additive entry points (the version number stays 15): LipsNet policies (gops/apprfunc/lipsnet.py DetermPolicy) - an MLP f
  * evaluated together with its input Jacobian J = df/dx and differentiated through it (csrc/rollout_lips.hip):
  *     y = K(x) f(x) / (||J||_F + eps),   action = y   or, with `squash`,   (high - low) / 2 tanh(y) + (high + low) / 2,
