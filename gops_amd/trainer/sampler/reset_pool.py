@@ -3,7 +3,7 @@ distributions `DeviceEnvSampler` re-seeds finished instances from and `Evaluator
 import numpy as np
 import torch
 
-from gops_amd.utils.synthetic import make_batch
+from gops_amd.utils.synthetic import make_batch, n_surr_of
 
 INFO_KEYS = ("state", "ref_points", "path_num", "u_num", "ref_time")
 
@@ -73,6 +73,42 @@ def restate_discrete_head(values, u, head: int, epsilon: float = 0.0):
     return index, logp
 
 
+SURR_ENV_ID = "pyth_veh3dofconti_surrcstr"
+SURR_WHEELBASE, CIRCLE_RADIUS = 3.0, 100.0   # SurrVehicleData.l; the default circle path's radius (utils/synthetic.py: ref_points_f64)
+
+
+def draw_surr_vehicles(host: dict, n_surr: int, rng) -> dict:
+    """The surrounding vehicles of the data env's reset (pyth_veh3dofconti_surrcstr.py:81-116) for the initial conditions `host`
+    (make_batch: state, ref_points, path_num) -> surr_state [B, n_surr, 5] = (x, y, phi, u, delta) and the env's observation (:134-140).
+    Each vehicle sits at (delta_lon, delta_lat) = (10 U(-1, 1), 5 U(-1, 1)) from the first reference point in the path frame, redrawn
+    until it is outside the ego vehicle's box (|delta_lon| > 7 or |delta_lat| > 3), heads along the path - on the circle path: the
+    reference heading, with the steering angle that keeps it on the circle; else heading and steering 0 - and drives at
+    5 + U(-1, 1).  Float64 like the reset, stored in float32.  The rejection is vectorised: the rejected draws of all rows are redrawn
+    together, so the draws come in another order than the env's, from the same distribution."""
+    state, ref, path_num = (host[k].numpy() for k in ("state", "ref_points", "path_num"))
+    B, P = state.shape[0], ref.shape[1] - 1
+    circle = (path_num == 3)[:, None]
+    phi = np.where(circle, ref[:, :1, 2].astype(np.float64), 0.0) * np.ones((1, n_surr))
+    delta = np.where(circle, -np.arctan2(SURR_WHEELBASE, CIRCLE_RADIUS), 0.0) * np.ones((1, n_surr))
+    lon, lat = np.zeros((B, n_surr)), np.zeros((B, n_surr))
+    todo = np.ones((B, n_surr), dtype=bool)
+    while todo.any():
+        k = int(todo.sum())
+        lon[todo], lat[todo] = 10.0 * rng.uniform(-1.0, 1.0, size=k), 5.0 * rng.uniform(-1.0, 1.0, size=k)
+        todo = ~((np.abs(lon) > 7.0) | (np.abs(lat) > 3.0))
+    x = ref[:, :1, 0] + lon * np.cos(phi) - lat * np.sin(phi)
+    y = ref[:, :1, 1] + lon * np.sin(phi) + lat * np.cos(phi)
+    u = 5.0 + rng.uniform(-1.0, 1.0, size=(B, n_surr))
+    surr = np.stack((x, y, phi, u, delta), axis=2).astype(np.float32)
+    # get_obs: the parent's observation, then the vehicles in the ego frame - all x, all y, all phi - and their speeds
+    ex, ey, ephi = (state[:, i:i + 1].astype(np.float64) for i in range(3))
+    c, s = np.cos(-ephi), np.sin(-ephi)
+    dx, dy = surr[..., 0] - ex, surr[..., 1] - ey
+    rel = np.concatenate((dx * c - dy * s, dx * s + dy * c, (surr[..., 2] - ephi + np.pi) % (2 * np.pi) - np.pi, surr[..., 3]), axis=1)
+    obs = np.concatenate((host["obs"].numpy()[:, :6 + 4 * P], rel.astype(np.float32)), axis=1)
+    return dict(obs=torch.from_numpy(np.ascontiguousarray(obs)), surr_state=torch.from_numpy(surr))
+
+
 def draw_reset_pool(cfg: dict, env_model, seed: int, size: int, device, data_env: bool = True) -> dict:
     """`size` initial conditions (device tensors: obs + the info keys the model carries) of `cfg["env_id"]` for `seed`."""
     host = make_batch(cfg, seed, batch=size)
@@ -90,7 +126,12 @@ def draw_reset_pool(cfg: dict, env_model, seed: int, size: int, device, data_env
         # make_batch's wide cartpole states exist to exercise the done thresholds inside short rollouts
         rng = np.random.RandomState(seed)
         host["obs"] = torch.from_numpy(rng.uniform(-0.05, 0.05, size=(size, 4)).astype(np.float32))
-    pool = {key: v.to(device) for key, v in host.items() if key == "obs" or key in INFO_KEYS}
+    keys = INFO_KEYS
+    if cfg["env_id"] == SURR_ENV_ID and data_env:
+        host.update(draw_surr_vehicles(host, n_surr_of(cfg), np.random.RandomState((seed + 0x5EED) % 2 ** 32)))   # (a stream of its own:
+        # make_batch starts from `seed`)
+        keys = INFO_KEYS + ("surr_state",)
+    pool = {key: v.to(device) for key, v in host.items() if key == "obs" or key in keys}
     # ScaleObservationData (scale_observation.py:53-62): the data env hands out (obs + shift) * scale
     sc, sh = getattr(env_model, "obs_scale", None), getattr(env_model, "obs_shift", None)
     if sc is not None or sh is not None:
