@@ -3,16 +3,12 @@
 the restatement of one update of each family in torch at any dtype, and the bodies the three families' tests have in common.  The
 bodies are plain functions: they take the algorithm (or how to make it), the batch and what the family expects, and assert."""
 import copy
-import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, golden_meta, load_golden, rel_l2
+from conftest import golden_meta, load_golden, rel_l2
 from helpers import data_from_golden
 
 from gops_amd.create_pkg.create_alg import create_alg
@@ -313,33 +309,6 @@ def check_refusals(kw_of, cases):
     for over, reason in cases:
         with pytest.raises(NotImplementedError, match=reason):
             create_alg(**kw_of(**over))
-
-
-def check_abi(tmp_path, structs, entry_points, stats):
-    """The entry points are declared in the header (plain C99), exported by the library and listed by hip_backend; the version stays
-    15; `stats`: (macro, hip_backend's value).  `structs`: (C struct name, ctypes class) - a C probe's sizeof / offsetof of every
-    field against the ctypes mirror - or (C struct name, size) for a struct without a mirror."""
-    from gops_amd import hip_backend as hb
-    header = open(os.path.join(ROOT, "include", "gops_hip.h")).read()
-    assert "#define GOPS_HIP_ABI_VERSION 15" in header
-    for name in entry_points:
-        assert re.search(rf"\b{name}\s*\(", header) and name in hb.EXPORTED_SYMBOLS
-        assert hasattr(ctypes.CDLL(hb.LIB_PATH), name)
-    for macro, value in stats:
-        assert int(re.search(rf"#define {macro} (\d+)", header).group(1)) == value
-    lines, want = [], []
-    for st, cls in structs:
-        lines.append(f'    printf(" %zu", sizeof({st}));\n')
-        if isinstance(cls, int):
-            want.append(cls)
-            continue
-        lines += [f'    printf(" %zu", offsetof({st}, {f[0]}));\n' for f in cls._fields_]
-        want += [ctypes.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gops_hip.h"\nint main(void) {\n' + "".join(lines) + "    return 0;\n}\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == want
 
 
 # ------------------------------------------------------------------------------------------

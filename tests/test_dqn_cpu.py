@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from ac_helpers import TOL, check_abi, check_refusals, close
+from abi_helpers import check_abi
+from ac_helpers import TOL, check_refusals, close
 from conftest import ROOT, rel_l2
 from dqn_helpers import DQN_FIVE_UPDATES, DQN_ONE_UPDATE, dqn_kwargs, fresh, load_dqn, restate_dqn
 from helpers import data_from_golden

@@ -5,7 +5,8 @@ import os
 import pytest
 import torch
 
-from ac_helpers import (DSACT_ONE_UPDATE, REFUSALS, SOFT_REFUSALS, alg_kwargs, batch_of, check_abi, check_host_restatement, check_refusals,
+from abi_helpers import check_abi
+from ac_helpers import (DSACT_ONE_UPDATE, REFUSALS, SOFT_REFUSALS, alg_kwargs, batch_of, check_host_restatement, check_refusals,
                         check_soft_tb_and_alpha, q_names, restate_update)
 from conftest import ROOT, golden_meta, load_golden, rel_l2
 

@@ -1,15 +1,14 @@
 """The device evaluator on the host: `create_evaluator` and its refusals, the reset-pool helper `DeviceEnvSampler` and `Evaluator`
 share (the sampler's draws for a seed must not move), `TrainerBase._evaluate` with and without an `on_device` evaluator, and the C
 ABI surface of `gops_episode_rollout`."""
-import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 import torch
 
-from episode_helpers import alg_kwargs
+from abi_helpers import layout_probe
+from closed_loop_helpers import alg_kwargs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -141,14 +140,6 @@ def test_episode_entry_points_are_additive_in_the_abi(tmp_path):
                      r"const GopsStepIO\* init,\s+const GopsEpisodeOut\* out, void\* workspace, size_t workspace_bytes, void\* stream\);", header)
     assert {"gops_episode_workspace_bytes", "gops_episode_rollout"} <= set(hb.EXPORTED_SYMBOLS)
     assert [f[0] for f in hb.GopsEpisodeOut._fields_] == ["ret", "length", "terminated", "trace_obs", "trace_act", "trace_rew"]
-    # the ctypes mirror against the header's layout, as tests/test_host_cpu.py holds the older structs
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    fields = [f[0] for f in hb.GopsEpisodeOut._fields_]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gops_hip.h"\nint main(void) {\n'
-                   '    printf("%zu", sizeof(GopsEpisodeOut));\n'
-                   + "".join(f'    printf(" %zu", offsetof(GopsEpisodeOut, {f}));\n' for f in fields) + "    return 0;\n}\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(hb.GopsEpisodeOut)] + [getattr(hb.GopsEpisodeOut, f).offset for f in fields]
+    layout_probe(tmp_path, [("GopsEpisodeOut", hb.GopsEpisodeOut)])
     makefile = open(os.path.join(ROOT, "gops_amd", "csrc", "Makefile")).read()
     assert "rollout_episode.hip" in makefile

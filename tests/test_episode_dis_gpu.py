@@ -13,52 +13,25 @@ import numpy as np
 import pytest
 import torch
 
-from test_sample_gpu import ATOL, RTOL, doom
+import closed_loop_helpers as cl
+from closed_loop_helpers import ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
-CFGS = {"cartpole": dict(env_id="gym_cartpoleconti"), "lq": dict(env_id="pyth_lq", lq_config="s4a2"), "idp": dict(env_id="pyth_idpendulum")}
+ENVS = ("cartpole", "idp", "lq")
 MAX_T, FILL = 12, -7.0
 SHAPES = [(1, (16,), "tanh", 2), (17, (64, 64), "relu", 5), (40, (16,), "tanh", 5), (40, (64, 64), "relu", 2)]   # E, hidden, act, act_num
 
 
-class Nets(torch.nn.Module):
-    def __init__(self, policy):
-        super().__init__()
-        self.policy = policy
-
-
-def table_of(env, n):
-    from gops_amd.utils.synthetic import act_dim_of
-    col = torch.linspace(-1.0, 1.0, n)
-    return col[:, None] if act_dim_of(CFGS[env]) == 1 else torch.stack((col, -0.5 * col), dim=1)
-
-
 def make_evaluator(env, hidden, act, n, networks=None, **kw):
-    from gops_amd.apprfunc.mlp import StochaPolicyDis
-    from gops_amd.create_pkg.create_env_model import create_env_model
-    from gops_amd.trainer.evaluator import Evaluator
-    from gops_amd.utils.act_distribution import CategoricalDistribution
     from gops_amd.utils.synthetic import obs_dim_of
-    cfg = CFGS[env]
-    if networks is None:
-        torch.manual_seed(0)
-        net = StochaPolicyDis(obs_dim=obs_dim_of(cfg), act_num=n, hidden_sizes=list(hidden), hidden_activation=act,
-                              action_distribution_cls=CategoricalDistribution)
-        with torch.no_grad():   # logits apart from each other: few close calls
-            net.linear_layers()[-1].weight *= 4.0
-            net.linear_layers()[-1].bias *= 4.0
-        networks = Nets(net.to("cuda"))
-    return Evaluator(env_model=create_env_model(**cfg), networks=networks, cfg=cfg, num_eval_episode=4, eval_save=False,
-                     max_episode_steps=MAX_T, action_table=table_of(env, n), **kw)
+    if networks is None:   # a categorical policy, logits apart from each other: few close calls
+        networks = cl.Nets(cl.dis_net("categorical", obs_dim_of(cl.CFGS[env]), n, hidden, act).to("cuda"))
+    return cl.make_evaluator(env, networks, MAX_T, num_eval_episode=4, action_table=cl.table_of(env, n), **kw)
 
 
 def initial_conditions(ev, env, E, seed):
     """Reset states of the data env; with E > 1 the last episode starts where its first step ends it."""
-    from gops_amd.trainer.sampler.reset_pool import draw_reset_pool
-    init = {k: v.contiguous() for k, v in draw_reset_pool(ev.cfg, ev.env_model, seed, E, ev.device, True).items()}
-    if E > 1:
-        doom(env, init, [E - 1])
-    return init
+    return cl.initial_conditions(ev, env, E, seed, doomed=(E - 1,) if E > 1 else ())
 
 
 def close_calls_of(net, obs, index):
@@ -114,7 +87,7 @@ def check_trace(ev, res, init):
     return live, index
 
 
-@pytest.mark.parametrize("env", sorted(CFGS))
+@pytest.mark.parametrize("env", ENVS)
 def test_trace_is_one_step_consistent(env):
     rows, episodes, ended = [], 0, 0
     for E, hidden, act, n in SHAPES:

@@ -21,11 +21,10 @@ import numpy as np
 import pytest
 import torch
 
-from episode_helpers import ENVS, POLICIES, alg_kwargs
+import closed_loop_helpers as cl
+from closed_loop_helpers import ATOL, EPISODE_ENVS as ENVS, INFO, POLICIES, RTOL, alg_kwargs, deviations, initial_conditions
 
 pytestmark = pytest.mark.gpu
-RTOL, ATOL = 1e-5, 2e-5
-INFO = ("state", "ref_points", "path_num", "u_num", "ref_time")
 
 
 @pytest.fixture(scope="module")
@@ -35,33 +34,10 @@ def dev():
 
 def make_evaluator(env, policy, seed=0, T=40, **extra):
     from gops_amd.create_pkg.create_alg import create_alg
-    from gops_amd.trainer.evaluator import Evaluator
     torch.manual_seed(seed + 1)
-    cfg, kw = alg_kwargs(env, policy, seed)
-    alg = create_alg(**kw)
+    alg = create_alg(**alg_kwargs(env, policy, seed)[1])
     alg.networks.to("cuda")
-    return Evaluator(env_model=alg.envmodel, networks=alg.networks, cfg=cfg, num_eval_episode=5, eval_save=False, seed=seed,
-                     max_episode_steps=T, **extra), alg
-
-
-def initial_conditions(ev, env, E, seed=5, doomed=()):
-    """E reset states of the data env; rows of `doomed` are moved to where the first step ends the episode."""
-    from gops_amd.trainer.sampler.reset_pool import draw_reset_pool
-    init = draw_reset_pool(ev.cfg, ev.env_model, seed, E, ev.device)
-    for r in doomed:
-        if env == "lq":
-            init["obs"][r] = torch.tensor([14.9, 9.0, 14.9, 9.0], device=ev.device)   # state bound 15, moving outwards
-        elif env == "idp":
-            init["obs"][r, 1:3] = 1.4   # tip far below the threshold
-        elif env == "cartpole":
-            init["obs"][r, 0], init["obs"][r, 1] = 2.399, 3.0
-        elif env == "veh3dof":   # 4 m beside the first reference point (bound 2 m); the observation follows the state
-            init["state"][r, 1] += 4.0
-            init["obs"][r, 1] -= 4.0 * torch.cos(init["state"][r, 2])
-        elif env == "veh2dof":
-            init["state"][r, 0] += 4.0
-            init["obs"][r, 0] += 4.0
-    return init
+    return cl.make_evaluator(env, alg.networks, T, env_model=alg.envmodel, num_eval_episode=5, seed=seed, **extra), alg
 
 
 def check_trace(ev, init, res, T):
@@ -163,17 +139,6 @@ def fixture_evaluator(g, T):
     alg.networks.policy.load_state_dict({k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd/")})
     alg.networks.to("cuda")
     return Evaluator(env_model=alg.envmodel, networks=alg.networks, cfg=cfg, num_eval_episode=1, eval_save=False, max_episode_steps=T)
-
-
-def deviations(res, obs, rew_ret, length):
-    """Largest deviation of a run from a record: the return against max(1, |return|), the observations of every recorded step
-    against max(1, the record's largest |observation|)."""
-    E, T = obs.shape[:2]
-    inside = (np.arange(T)[None, :] < length[:, None])[:, :, None]
-    got = res["trace_obs"].cpu().numpy()
-    d_obs = float((np.abs(got - obs) * inside).max() / max(1.0, float((np.abs(obs) * inside).max())))
-    d_ret = float((np.abs(res["ret"].double().cpu().numpy() - rew_ret) / np.maximum(1.0, np.abs(rew_ret))).max())
-    return d_ret, d_obs
 
 
 def check_against_record(ev, init, obs, ret, length, terminated, label):

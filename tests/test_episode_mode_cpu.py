@@ -9,39 +9,21 @@ import re
 
 import pytest
 
-from episode_helpers import alg_kwargs
-from episode_mode_helpers import stocha_evaluator
+from closed_loop_helpers import alg_kwargs, stocha_evaluator
+from desc_helpers import BAD, UNS, WS, env_desc, mlp_desc, ptr_struct as _ptrs
 
 from gops_amd import hip_backend as hb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAD, UNS, WS = -1, -2, -3
-P = 0x1000   # a pointer that is never followed
 GAUSS, TANH_GAUSS = hb.SAMPLE_GAUSS, hb.SAMPLE_TANH_GAUSS
 
 
 def _mlp(sizes, dtype=0):
-    m = hb.GopsMlp()
-    m.n_layers = len(sizes) - 1
-    for i, s in enumerate(sizes):
-        m.sizes[i] = s
-    for j in range(m.n_layers):
-        m.weight[j] = m.bias[j] = P
-    m.hidden_act, m.dtype = hb.ACT_IDS["elu"], dtype
-    return m
+    return mlp_desc(sizes, dtype=dtype)
 
 
 def _env(kind=hb.ENV_CARTPOLE, O=4, A=1, data_env=1):
-    e = hb.GopsEnv()
-    e.kind, e.obs_dim, e.act_dim, e.data_env = kind, O, A, data_env
-    return e
-
-
-def _ptrs(cls):
-    s = cls()
-    for k, _ in cls._fields_:
-        setattr(s, k, P)
-    return s
+    return env_desc(kind, O, A, data_env=data_env)
 
 
 def _rollout(env=True, pol=True, head=TANH_GAUSS, E=4, init=True, out_w=2, dtype=0, env_desc=None, in_w=4):

@@ -17,8 +17,8 @@ step.  With the rows scaled by the 50 - 100 that the narrow cartpole reset state
 steps although each step agrees to rounding (measured: first action against float64 0 / 6e-8); cartpole therefore starts from states
 spread over the track, and no row is scaled by more than MAX_GAIN.
 
-Bound of the float comparisons: the one tests/test_episode_gpu.py holds its fused kernel to against its per-step loop - `deviations`
-(restated here: the return against max(1, |return|), the observations against max(1, the largest |observation|)), at most
+Bound of the float comparisons: the one tests/test_episode_gpu.py holds its fused kernel to against its per-step loop - the shared
+`deviations` (the return against max(1, |return|), the observations against max(1, the largest |observation|)), at most
 max(4 x the loop's own deviation from a record, 1e-5).  No record exists for these policies, so the bound is its floor, 1e-5, the
 smallest value that rule can give; actions and rewards are held to the same figure in the same form (against max(1, the loop's
 largest |value|)).  `length` and `terminated` are equal, for every row: none is left out.  Every figure is printed before it is
@@ -31,7 +31,8 @@ import numpy as np
 import pytest
 import torch
 
-from episode_mode_helpers import stocha_evaluator
+import closed_loop_helpers as cl
+from closed_loop_helpers import deviations, rows, stocha_evaluator
 
 from gops_amd.utils.act_distribution import TanhGaussDistribution
 
@@ -70,13 +71,12 @@ def shape_head(nets, probe):
 def initial_conditions(ev, env, E, seed=5):
     """E reset states of the data env.  Cartpole: states spread over the track instead (position within +-1.5 of the +-2.4 bound,
     speed +-1, angle +-0.03 of the 0.21 bound, rate +-0.1); the last row starts where the first step ends the episode."""
-    from gops_amd.trainer.sampler.reset_pool import draw_reset_pool
-    init = draw_reset_pool(ev.cfg, ev.env_model, seed, E, ev.device)
+    init = cl.initial_conditions(ev, env, E, seed)
     if env == "cartpole":
         g = torch.Generator().manual_seed(seed)
         spread = torch.tensor([1.5, 1.0, 0.03, 0.1])
         init["obs"] = ((2 * torch.rand(E, 4, generator=g) - 1) * spread).to(ev.device)
-        init["obs"][E - 1, 0], init["obs"][E - 1, 1] = 2.399, 3.0
+        cl.doom(env, init, [E - 1])
     return init
 
 
@@ -90,22 +90,6 @@ def make_case(env, hidden, dist):
     shape_head(nets, visited["trace_obs"][inside])
     ev, _ = stocha_evaluator(env, hidden, dist, T=T, nets=nets, stochastic_mode=True)
     return ev, nets, init
-
-
-def deviations(res, obs, rew_ret, length):
-    """tests/test_episode_gpu.py's `deviations`, word for word (that file's yardstick; a test module is not imported for it): the
-    largest deviation of a run from a record - the return against max(1, |return|), the observations of every recorded step against
-    max(1, the record's largest |observation|)."""
-    E, T = obs.shape[:2]
-    inside = (np.arange(T)[None, :] < length[:, None])[:, :, None]
-    got = res["trace_obs"].cpu().numpy()
-    d_obs = float((np.abs(got - obs) * inside).max() / max(1.0, float((np.abs(obs) * inside).max())))
-    d_ret = float((np.abs(res["ret"].double().cpu().numpy() - rew_ret) / np.maximum(1.0, np.abs(rew_ret))).max())
-    return d_ret, d_obs
-
-
-def rows(init, idx):
-    return {k: v[idx].contiguous() for k, v in init.items()}
 
 
 def raw_means(nets, res):

@@ -189,28 +189,7 @@ def test_create_alg_builds_infadp_with_a_lipsnet_policy():
 
 def test_lips_entry_points_and_ctypes_mirrors(tmp_path):
     """The three entry points are additive (the ABI version stays 15) and the two ctypes mirrors have the header's layout."""
-    import ctypes
-    import os
-    import re
-    import subprocess
+    from abi_helpers import check_abi, layout_probe
     from gops_amd import hip_backend as hb
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "gops_hip.h")).read()
-    assert "#define GOPS_HIP_ABI_VERSION 15" in header
-    lib = ctypes.CDLL(hb.LIB_PATH)
-    for name in ("gops_lips_workspace_bytes", "gops_lips_forward", "gops_lips_backward"):
-        assert name in hb.EXPORTED_SYMBOLS and hasattr(lib, name) and re.search(r"\b" + name + r"\(", header)
-    c_names = {"lam": "lambda"}
-    lines = []
-    for cls in (hb.GopsLipsNet, hb.GopsLipsGrad):
-        lines.append(f'    printf("%zu ", sizeof({cls.__name__}));')
-        lines += [f'    printf("%zu ", offsetof({cls.__name__}, {c_names.get(f[0], f[0])}));' for f in cls._fields_]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gops_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\n    return 0;\n}\n")
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    want = []
-    for cls in (hb.GopsLipsNet, hb.GopsLipsGrad):
-        want.append(ctypes.sizeof(cls))
-        want += [getattr(cls, f[0]).offset for f in cls._fields_]
-    assert got == want
+    check_abi(tmp_path, [], ("gops_lips_workspace_bytes", "gops_lips_forward", "gops_lips_backward"), [])
+    layout_probe(tmp_path, [("GopsLipsNet", hb.GopsLipsNet), ("GopsLipsGrad", hb.GopsLipsGrad)], c_names={"lam": "lambda"})

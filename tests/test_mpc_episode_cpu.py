@@ -6,16 +6,16 @@ import json
 import numpy as np
 import pytest
 
-import ac_helpers
 import mpc_episode_helpers as eh
 import mpc_helpers as mh
+from abi_helpers import check_abi
 from gops_amd import hip_backend as hb
 
 BAD, P, ODD = -1, 0x1000, 0x1004
 
 
 def test_abi_surface(tmp_path):
-    ac_helpers.check_abi(tmp_path, [], ["gops_mpc_advance"], [("GOPS_MPC_FROZEN", hb.MPC_FROZEN)])
+    check_abi(tmp_path, [], ["gops_mpc_advance"], [("GOPS_MPC_FROZEN", hb.MPC_FROZEN)])
     assert hb.MPC_FROZEN == eh.FROZEN == len(hb.MPC_STATUS_NAMES) - 1 and hb.MPC_FROZEN > hb.MPC_NONFINITE
 
 

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from ac_helpers import REFUSALS, TOL, alg_kwargs, check_abi, check_refusals, close
+from abi_helpers import check_abi
+from ac_helpers import REFUSALS, TOL, alg_kwargs, check_refusals, close
 from conftest import golden_meta, load_golden, rel_l2
 from ppo_helpers import (HYPER, KERNEL_SHAPES, LOCAL_UPDATE, MARGIN, MIN_ROWS, ONE_STEP, TERMS, branches, hyper_of, load_ppo, minibatch_of,
                          restate_gae, restate_loss_with_seeds, restate_ppo_step, synthetic_minibatch, ulps32)

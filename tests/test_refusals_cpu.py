@@ -10,24 +10,11 @@ import os
 
 import pytest
 
+from desc_helpers import BAD, ELU, ODD, UNS, WS, P, env_desc as _env, mlp_desc as _mlp, ptr_struct as _all_ptrs, struct as _struct
+
 from gops_amd import hip_backend as hb
 
-BAD, UNS, WS = -1, -2, -3
-P, ODD = 0x1000, 0x1004   # a pointer that is never followed (16-byte aligned) / one that is not 8-byte aligned
-ELU, TANH = hb.ACT_IDS["elu"], hb.ACT_IDS["tanh"]
-
-
-def _mlp(sizes, act=ELU, ptr=P, **fields):
-    m = hb.GopsMlp()
-    m.n_layers = len(sizes) - 1
-    for i, s in enumerate(sizes):
-        m.sizes[i] = s
-    for j in range(m.n_layers):
-        m.weight[j] = m.bias[j] = ptr
-    m.hidden_act = act
-    for k, v in fields.items():
-        setattr(m, k, v)
-    return m
+TANH = hb.ACT_IDS["tanh"]
 
 
 def _grad(n=hb.MAX_LAYERS, weight0=P):
@@ -36,24 +23,6 @@ def _grad(n=hb.MAX_LAYERS, weight0=P):
         g.weight[j] = g.bias[j] = P
     g.weight[0] = weight0
     return g
-
-
-def _struct(cls, **fields):
-    s = cls()
-    for k, v in fields.items():
-        setattr(s, k, v)
-    return s
-
-
-def _all_ptrs(cls, **null):
-    s = cls()
-    for k, _ in cls._fields_:
-        setattr(s, k, null.get(k, P))
-    return s
-
-
-def _env(kind, obs_dim, act_dim, **fields):
-    return _struct(hb.GopsEnv, kind=kind, obs_dim=obs_dim, act_dim=act_dim, **fields)
 
 
 def _io(**null):

@@ -3,7 +3,8 @@ update restated on the host against every fixture of tests/golden/make_golden_sa
 import pytest
 import torch
 
-from ac_helpers import (REFUSALS, SAC_ONE_UPDATE, SOFT_REFUSALS, alg_kwargs, check_abi, check_host_restatement, check_refusals,
+from abi_helpers import check_abi
+from ac_helpers import (REFUSALS, SAC_ONE_UPDATE, SOFT_REFUSALS, alg_kwargs, check_host_restatement, check_refusals,
                         check_soft_tb_and_alpha, q_names)
 from conftest import golden_meta, load_golden
 

@@ -4,7 +4,7 @@ import inspect
 
 import numpy as np
 
-from ac_helpers import check_abi
+from abi_helpers import check_abi
 
 from gops_amd.trainer.sampler.reset_pool import pool_needs_refresh, pool_row, restate_sample_books
 

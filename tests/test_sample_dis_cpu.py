@@ -8,13 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-from ac_helpers import check_abi
+from abi_helpers import check_abi
+from closed_loop_helpers import Nets as _Nets
+from desc_helpers import BAD, UNS, WS, P, mlp_desc, ptr_struct
 
 from gops_amd import hip_backend as hb
 from gops_amd.trainer.sampler.reset_pool import HEAD_CATEGORICAL, HEAD_EPS_GREEDY, restate_discrete_head
-
-P = 4096   # a non-NULL "device pointer": no refused call follows it
-BAD, UNS, WS = -1, -2, -3
 
 
 def test_abi_of_the_discrete_entry_points(tmp_path):
@@ -38,16 +37,8 @@ def _env(env_id="gym_cartpoleconti", data_env=True, **cfg):
     return hb.GopsEnv.from_buffer_copy(model.hip_env(-np.ones(A, np.float32), np.ones(A, np.float32), data_env=data_env))
 
 
-def _mlp(sizes, n_layers=None, dtype=0):
-    m = hb.GopsMlp()
-    m.n_layers = len(sizes) - 1 if n_layers is None else n_layers
-    for i, s in enumerate(sizes):
-        m.sizes[i] = s
-    for j in range(len(sizes) - 1):
-        m.weight[j] = m.bias[j] = P
-    m.hidden_act = hb.ACT_IDS["relu"]
-    m.dtype = dtype
-    return m
+def _mlp(sizes, **fields):
+    return mlp_desc(sizes, act=hb.ACT_IDS["relu"], **fields)
 
 
 def _sample_call(env=None, mlp=None, n=3, head=None, eps=0.25, table=P, env_act=P, N=4, T=2, pool_rows=2, max_steps=3, noise=P, out_act=P,
@@ -56,11 +47,7 @@ def _sample_call(env=None, mlp=None, n=3, head=None, eps=0.25, table=P, env_act=
     mlp = _mlp([env.obs_dim, 16, n]) if mlp is None else mlp
     desc = hb.GopsSampleDesc(head=0, max_episode_steps=max_steps, pool_rows=pool_rows)
     d = hb.GopsSampleDis(action_table=table, act_num=n, head=hb.SAMPLE_EPS_GREEDY if head is None else head, epsilon=eps, env_act=env_act)
-    st, pl, out = hb.GopsSampleState(), hb.GopsSamplePool(), hb.GopsSampleOut()
-    for s in (st, pl, out):
-        for f in s._fields_:
-            setattr(s, f[0], P)
-    out.act = out_act
+    st, pl, out = ptr_struct(hb.GopsSampleState), ptr_struct(hb.GopsSamplePool), ptr_struct(hb.GopsSampleOut, act=out_act)
     return hb.lib().gops_sample_rollout_dis(C.byref(env), C.byref(mlp), C.byref(desc), C.byref(d) if dis else None, N, T, C.byref(st),
                                             C.byref(pl), noise, C.byref(out), ws, ws_bytes, None)
 
@@ -172,12 +159,6 @@ def test_restated_categorical():
 
 
 # ---- path choice on the host --------------------------------------------------------------------------------------------------
-class _Nets(torch.nn.Module):
-    def __init__(self, policy):
-        super().__init__()
-        self.policy = policy
-
-
 def _cpu_sampler(**kw):
     from gops_amd.create_pkg.create_env_model import create_env_model
     from gops_amd.trainer.sampler.device_env_sampler import DeviceEnvSampler

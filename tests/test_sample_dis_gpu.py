@@ -25,7 +25,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_sample_gpu import ATOL, ENVS, INFO, MAX_STEPS, R, RTOL, check_books, doom
+import closed_loop_helpers as cl
+from closed_loop_helpers import ATOL, INFO, RTOL, SAMPLE_ENVS as ENVS, check_sample_books as check_books, sample_inputs
 
 pytestmark = pytest.mark.gpu
 EPS = 0.25
@@ -35,73 +36,20 @@ GROUPS = [(env, head) for env in ("cartpole", "lq", "mountaincar") for head in H
 T = 5
 
 
-class Nets(torch.nn.Module):
-    def __init__(self, policy):
-        super().__init__()
-        self.policy = policy
-
-
 def shapes_of(env):
     return [(17, (64, 64), "relu", 3)] if env == "veh3dof" else SHAPES   # one veh3dof case: the info tensors carry through
 
 
-def table_of(env, n):
-    """[n, A]: A = 1 a grid over [-1, 1]; A = 2 (lq s4a2, veh3dof) a second column that runs the other way at half the size."""
-    from gops_amd.utils.synthetic import act_dim_of
-    col = torch.linspace(-1.0, 1.0, n)
-    return col[:, None] if act_dim_of(ENVS[env][0]) == 1 else torch.stack((col, -0.5 * col), dim=1)
-
-
-def make_net(head, O, n, hidden, act, seed=0):
-    from gops_amd.apprfunc.mlp import ActionValueDis, StochaPolicyDis
-    from gops_amd.utils.act_distribution import CategoricalDistribution, ValueDiracDistribution
-    torch.manual_seed(seed)
-    kw = dict(obs_dim=O, act_num=n, hidden_sizes=list(hidden), hidden_activation=act)
-    net = ActionValueDis(action_distribution_cls=ValueDiracDistribution, **kw) if head == "eps_greedy" else \
-        StochaPolicyDis(action_distribution_cls=CategoricalDistribution, **kw)
-    with torch.no_grad():   # values apart from each other: few close calls (module docstring)
-        net.linear_layers()[-1].weight *= 4.0
-        net.linear_layers()[-1].bias *= 4.0
-    return net
-
-
 def make_sampler(env, head, hidden, act, n, N, steps=T, cls=None, device="cuda", **kw):
-    from gops_amd.create_pkg.create_env_model import create_env_model
-    from gops_amd.trainer.sampler.device_env_sampler import DeviceEnvSampler
     from gops_amd.utils.synthetic import obs_dim_of
-    cfg, step, _ = ENVS[env]
-    smp = (cls or DeviceEnvSampler)(cfg, create_env_model(**cfg), n_envs=N, steps_per_sample=steps, max_episode_steps=MAX_STEPS, seed=3,
-                                    pool_factor=R, env_step=step, action_table=table_of(env, n), device=device,
-                                    epsilon=EPS if head == "eps_greedy" else 0.0, **kw)
-    smp.networks = Nets(make_net(head, obs_dim_of(cfg), n, hidden, act).to(device))
-    return smp
-
-
-def make_inputs(smp, env, N, steps, seed):
-    """(state, pool, uniforms): as test_sample_gpu.make_inputs - instance N - 1 (N > 1) doomed in the state and in BOTH of its pool
-    rows, instances at different steps into their episodes -, with [T, N, 2] uniforms in [0, 1) for the noise."""
-    from gops_amd.trainer.sampler.reset_pool import draw_reset_pool
-    dev = smp.device
-    keep = lambda d: {k: v.contiguous() for k, v in d.items() if k == "obs" or k in INFO}   # noqa: E731
-    state = keep(draw_reset_pool(smp.cfg, smp.env_model, seed, N, dev, smp.data_env))
-    flat = keep(draw_reset_pool(smp.cfg, smp.env_model, seed + 1, R * N, dev, smp.data_env))
-    if N > 1 and ENVS[env][2]:
-        doom(env, state, [N - 1])
-        doom(env, flat, [r * N + N - 1 for r in range(R)])
-    pool = {k: v.reshape((R, N) + tuple(v.shape[1:])).contiguous() for k, v in flat.items()}
-    state["t"] = (torch.arange(N, device=dev) % MAX_STEPS).to(torch.int32)
-    state["reset_count"] = ((torch.arange(N, device=dev) // 3) % 2).to(torch.int32)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(seed + 2)
-    return state, pool, torch.rand((steps, N, 2), generator=gen, device=dev)
+    return cl.make_sampler(env, lambda smp: cl.dis_net(head, obs_dim_of(smp.cfg), n, hidden, act).to(device), N, steps, cls=cls,
+                           action_table=cl.table_of(env, n), device=device, epsilon=EPS if head == "eps_greedy" else 0.0, **kw)
 
 
 def make_rollout(smp, head, N, steps, state):
     from gops_amd import hip_backend as hb
-    return hb.SampleRollout(smp._hip_env(), smp.networks.policy.hip_mlp(), n_envs=N, steps=steps,
-                            head=hb.SAMPLE_EPS_GREEDY if head == "eps_greedy" else hb.SAMPLE_CATEGORICAL, max_episode_steps=MAX_STEPS,
-                            pool_rows=R, info_like={k: state[k] for k in INFO if k in state}, device=smp.device,
-                            action_table=smp.action_table, epsilon=smp.epsilon)
+    return cl.make_rollout(smp, hb.SAMPLE_EPS_GREEDY if head == "eps_greedy" else hb.SAMPLE_CATEGORICAL, N, steps, state,
+                           action_table=smp.action_table, epsilon=smp.epsilon)
 
 
 def judge(head, y64, y32, u, index, d):
@@ -154,11 +102,7 @@ def cpu_close_call_check(rows=2048):
 
 def run_case(env, head, N, hidden, act, n, seed):
     smp = make_sampler(env, head, hidden, act, n, N)
-    state, pool, noise = make_inputs(smp, env, N, T, seed)
-    before = {k: v.clone() for k, v in state.items()}
-    ro = make_rollout(smp, head, N, T, state)
-    out = {k: v.clone() for k, v in ro.run(state, pool, noise).items()}
-    return smp, before, state, pool, noise, out
+    return (smp,) + cl.run_sample(smp, env, N, T, seed, "uniform", lambda state: make_rollout(smp, head, N, T, state))
 
 
 def check_env_step(smp, out):
@@ -226,7 +170,7 @@ def test_record_is_one_step_consistent_and_the_books_are_exact(env, head):
 def test_launches_repeat_and_rows_do_not_depend_on_the_tiling(env, head, n):
     N = 70
     smp = make_sampler(env, head, (64, 64), "relu", n, N)
-    state, pool, noise = make_inputs(smp, env, N, T, seed=9)
+    state, pool, noise = sample_inputs(smp, env, N, T, 9, "uniform")
     before = {k: v.clone() for k, v in state.items()}
     ro = make_rollout(smp, head, N, T, state)
     out = {k: v.clone() for k, v in ro.run(state, pool, noise).items()}
@@ -319,7 +263,7 @@ def test_on_policy_sampler_fused_with_a_categorical_policy(monkeypatch):
     for fused in (True, False):
         smp = make_sampler("mountaincar", "categorical", (64, 64), "relu", 2, N, steps=steps, cls=OnPolicyDeviceSampler, gamma=0.97,
                            gae_lambda=0.9, fused=fused)
-        assert ENVS["mountaincar"][1] == "model" and smp.action_table.tolist() == [[-1.0], [1.0]]
+        assert ENVS["mountaincar"][0] == "model" and smp.action_table.tolist() == [[-1.0], [1.0]]
         torch.manual_seed(1)
         smp.networks.value = StateValue(obs_dim=2, hidden_sizes=[64, 64], hidden_activation="relu", output_activation="linear",
                                         action_distribution_cls=None).to("cuda")

@@ -15,28 +15,14 @@ import numpy as np
 import pytest
 import torch
 
+import closed_loop_helpers as cl
+from closed_loop_helpers import ATOL, INFO, MAX_STEPS, R, RTOL, SAMPLE_ENVS as ENVS, Nets, check_sample_books as check_books, sample_inputs
+
 pytestmark = pytest.mark.gpu
-RTOL, ATOL = 1e-5, 2e-5
-INFO = ("state", "ref_points", "path_num", "u_num", "ref_time")
-MAX_STEPS, R = 3, 2
 MIN_LS, MAX_LS = -2.0, 0.5
 NOISE_STD = 0.1
-ENVS = {   # name: (workload cfg, env_step, the model can terminate)
-    "lq": (dict(env_id="pyth_lq", lq_config="s4a2"), "data", True),
-    "cartpole": (dict(env_id="gym_cartpoleconti"), "data", True),
-    "idp": (dict(env_id="pyth_idpendulum"), "data", True),
-    "veh3dof": (dict(env_id="pyth_veh3dofconti", pre_horizon=10), "data", True),
-    "pendulum": (dict(env_id="gym_pendulum"), "model", False),
-    "mountaincar": (dict(env_id="gym_mountaincarconti"), "model", True),
-}
 HEADS = ("determ", "gauss", "tanh_gauss")
 SHAPES = [(1, ((16,), "tanh")), (15, ((64, 64), "relu")), (17, ((16,), "tanh")), (70, ((64, 64), "relu"))]   # N = GOPS_TILE -+ 1, ...
-
-
-class Nets(torch.nn.Module):
-    def __init__(self, policy):
-        super().__init__()
-        self.policy = policy
 
 
 def make_policy(head, O, A, hidden, act, seed=0):
@@ -56,76 +42,28 @@ def make_policy(head, O, A, hidden, act, seed=0):
 
 
 def make_sampler(env, head, hidden, act, N, T, cls=None, **kw):
-    from gops_amd.create_pkg.create_env_model import create_env_model
-    from gops_amd.trainer.sampler.device_env_sampler import DeviceEnvSampler
     from gops_amd.utils.synthetic import act_dim_of, obs_dim_of
-    cfg, step, _ = ENVS[env]
-    model = create_env_model(**cfg)
-    smp = (cls or DeviceEnvSampler)(cfg, model, n_envs=N, steps_per_sample=T, max_episode_steps=MAX_STEPS, seed=3, pool_factor=R,
-                                    env_step=step, noise_std=NOISE_STD if head == "determ" else 0.0, **kw)
-    pol = make_policy(head, obs_dim_of(cfg), act_dim_of(cfg), hidden, act)
-    if head != "determ":   # the median raw log std of the env's reset states ON the upper clamp: rows on both sides of it
-        from gops_amd.trainer.sampler.reset_pool import draw_reset_pool
-        A = act_dim_of(cfg)
-        with torch.no_grad():
-            raw = pol.policy(draw_reset_pool(cfg, model, 77, 64, smp.device, smp.data_env)["obs"])[:, A:]
-            pol.linear_layers()[-1].bias[A:] += MAX_LS - raw.median(dim=0).values
-    smp.networks = Nets(pol)
-    return smp
 
+    def policy_of(smp):
+        A = act_dim_of(smp.cfg)
+        pol = make_policy(head, obs_dim_of(smp.cfg), A, hidden, act)
+        if head != "determ":   # the median raw log std of the env's reset states ON the upper clamp: rows on both sides of it
+            from gops_amd.trainer.sampler.reset_pool import draw_reset_pool
+            with torch.no_grad():
+                raw = pol.policy(draw_reset_pool(smp.cfg, smp.env_model, 77, 64, smp.device, smp.data_env)["obs"])[:, A:]
+                pol.linear_layers()[-1].bias[A:] += MAX_LS - raw.median(dim=0).values
+        return pol
 
-def doom(env, flat, rows):
-    """Move rows of a flat [rows, ...] set of initial conditions to where the first step ends the episode."""
-    dev = flat["obs"].device
-    for r in rows:
-        if env == "lq":
-            flat["obs"][r] = torch.tensor([14.9, 9.0, 14.9, 9.0], device=dev)   # state bound 15, moving outwards
-        elif env == "idp":
-            flat["obs"][r, 1:3] = 1.4
-        elif env == "cartpole":
-            flat["obs"][r, 0], flat["obs"][r, 1] = 2.399, 3.0
-        elif env == "veh3dof":   # 4 m beside the first reference point (bound 2 m); the observation follows the state
-            flat["state"][r, 1] += 4.0
-            flat["obs"][r, 1] -= 4.0 * torch.cos(flat["state"][r, 2])
-        elif env == "mountaincar":
-            flat["obs"][r, 0], flat["obs"][r, 1] = 0.44, 0.06   # 0.45 is the goal
-    return flat
-
-
-def make_inputs(smp, env, N, T, seed):
-    """(state, pool, noise): reset states of the env, instance N - 1 (N > 1) doomed in the state and in BOTH of its pool rows - it
-    resets at every step, past the pool's end -, instances at different steps into their episodes."""
-    from gops_amd.trainer.sampler.reset_pool import draw_reset_pool
-    dev = smp.device
-    keep = lambda d: {k: v.contiguous() for k, v in d.items() if k == "obs" or k in INFO}   # noqa: E731
-    state = keep(draw_reset_pool(smp.cfg, smp.env_model, seed, N, dev, smp.data_env))
-    flat = keep(draw_reset_pool(smp.cfg, smp.env_model, seed + 1, R * N, dev, smp.data_env))
-    if N > 1 and ENVS[env][2]:
-        doom(env, state, [N - 1])
-        doom(env, flat, [r * N + N - 1 for r in range(R)])
-    pool = {k: v.reshape((R, N) + tuple(v.shape[1:])).contiguous() for k, v in flat.items()}
-    state["t"] = (torch.arange(N, device=dev) % MAX_STEPS).to(torch.int32)
-    state["reset_count"] = ((torch.arange(N, device=dev) // 3) % 2).to(torch.int32)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(seed + 2)
-    A = smp._hip_env().act_dim
-    return state, pool, torch.randn((T, N, A), generator=gen, device=dev)
+    return cl.make_sampler(env, policy_of, N, T, cls=cls, noise_std=NOISE_STD if head == "determ" else 0.0, **kw)
 
 
 def make_rollout(smp, head, N, T, state):
-    from gops_amd import hip_backend as hb
-    pol = smp.networks.policy
-    return hb.SampleRollout(smp._hip_env(), pol.hip_mlp(), n_envs=N, steps=T, head=HEADS.index(head), max_episode_steps=MAX_STEPS,
-                            pool_rows=R, noise_std=NOISE_STD if head == "determ" else 0.0, min_log_std=MIN_LS, max_log_std=MAX_LS,
-                            info_like={k: state[k] for k in INFO if k in state}, device=smp.device)
+    return cl.make_rollout(smp, HEADS.index(head), N, T, state, noise_std=NOISE_STD if head == "determ" else 0.0, min_log_std=MIN_LS,
+                           max_log_std=MAX_LS)
 
 
 def run(smp, env, head, N, T, seed):
-    state, pool, noise = make_inputs(smp, env, N, T, seed)
-    before = {k: v.clone() for k, v in state.items()}
-    ro = make_rollout(smp, head, N, T, state)
-    out = {k: v.clone() for k, v in ro.run(state, pool, noise).items()}
-    return before, state, pool, noise, out
+    return cl.run_sample(smp, env, N, T, seed, "normal", lambda state: make_rollout(smp, head, N, T, state))
 
 
 def head_of(policy, head, obs, eps):
@@ -167,37 +105,6 @@ def check_one_step(smp, head, noise, out, acc):
             acc["inside"] += int(((ls >= MIN_LS) & (ls <= MAX_LS)).sum())
 
 
-def check_books(before, state, pool, out, acc):
-    """Carry-over, resets, the final state, time_limited and end, bit for bit against the host restatement of `done`."""
-    from gops_amd.trainer.sampler.reset_pool import restate_sample_books
-    T, N = out["rew"].shape
-    done = out["done"].cpu().numpy()
-    want = restate_sample_books(done, before["t"].cpu().numpy(), before["reset_count"].cpu().numpy(), MAX_STEPS, R)
-    assert np.array_equal(out["time_limited"].cpu().numpy(), want["time_limited"])
-    assert np.array_equal(out["end"].cpu().numpy(), want["end"])
-    assert np.array_equal(state["t"].cpu().numpy(), want["t"]) and np.array_equal(state["reset_count"].cpu().numpy(), want["reset_count"])
-    src = torch.from_numpy(want["src"]).to(out["obs"].device)
-    cols = torch.arange(N, device=src.device)
-    nxt = {"obs": "obs2", "state": "next_state", "ref_points": "next_ref_points", "ref_time": "next_ref_time", "path_num": "path_num",
-           "u_num": "u_num"}
-    for k in ["obs"] + [k for k in INFO if k in out]:
-        assert torch.equal(out[k][0], before[k]), k
-        for t in range(T):
-            reset = src[t] >= 0
-            fresh = pool[k][src[t].clamp_min(0), cols]
-            mask = reset.reshape((N,) + (1,) * (fresh.dim() - 1))
-            want_row = torch.where(mask, fresh, out[nxt[k]][t])
-            got_row = out[k][t + 1] if t + 1 < T else state[k]
-            assert torch.equal(got_row, want_row), (k, t)
-        if k in ("path_num", "u_num"):
-            assert torch.equal(out["next_" + k], out[k])
-    over = want["src"] >= 0
-    acc["done_resets"] += int((over & (done != 0)).sum())
-    acc["limit_resets"] += int((over & (done == 0)).sum())
-    acc["continues"] += int((~over).sum())
-    acc["most_resets"] = max(acc["most_resets"], int(over.sum(axis=0).max()))
-
-
 @pytest.mark.parametrize("head", HEADS)
 @pytest.mark.parametrize("env", sorted(ENVS))
 def test_record_is_one_step_consistent_and_the_books_are_exact(env, head):
@@ -211,7 +118,7 @@ def test_record_is_one_step_consistent_and_the_books_are_exact(env, head):
             check_books(before, state, pool, out, acc)
     print(f"\n{env} / {head}: {acc}")
     assert acc["limit_resets"] >= 1 and acc["continues"] >= 1
-    if ENVS[env][2]:
+    if ENVS[env][1]:
         assert acc["done_resets"] >= 1 and acc["most_resets"] >= 3   # (three resets of one instance in one call: past the pool's end)
     else:
         assert acc["done_resets"] == 0   # the pendulum model has no termination rule
@@ -227,7 +134,7 @@ def test_record_is_one_step_consistent_and_the_books_are_exact(env, head):
 def test_rows_do_not_depend_on_the_tiling_and_launches_repeat(env, head):
     N, T = 70, 5
     smp = make_sampler(env, head, (64, 64), "relu", N, T)
-    state, pool, noise = make_inputs(smp, env, N, T, seed=9)
+    state, pool, noise = sample_inputs(smp, env, N, T, 9, "normal")
     before = {k: v.clone() for k, v in state.items()}
     ro = make_rollout(smp, head, N, T, state)
     out = {k: v.clone() for k, v in ro.run(state, pool, noise).items()}
@@ -307,7 +214,7 @@ def test_bad_arguments_launch_nothing():
     from gops_amd import hip_backend as hb
     N, T = 4, 2
     smp = make_sampler("lq", "gauss", (16,), "relu", N, T)
-    state, pool, noise = make_inputs(smp, "lq", N, T, seed=1)
+    state, pool, noise = sample_inputs(smp, "lq", N, T, 1, "normal")
     ro = make_rollout(smp, "gauss", N, T, state)
     for v in ro.out.values():
         v.fill_(-7.0)

@@ -119,7 +119,7 @@ def test_reset_pool_draws_the_surrounding_vehicles(n_surr, P):
 def test_other_envs_keep_their_pools_and_refusals():
     from gops_amd.create_pkg.create_evaluator import create_evaluator
     from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, draw_reset_pool
-    from episode_helpers import alg_kwargs
+    from closed_loop_helpers import alg_kwargs
     assert INFO_KEYS == ("state", "ref_points", "path_num", "u_num", "ref_time")
     assert sorted(draw_reset_pool(dict(env_id="pyth_veh3dofconti", pre_horizon=2), None, 3, 4, "cpu")) == sorted(("obs",) + INFO_KEYS)
     cfg, kw = alg_kwargs("idp", "relu64", use_gpu=False)

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from ac_helpers import REFUSALS, TD3_ONE_UPDATE, TOL, alg_kwargs, check_abi, check_host_restatement, check_refusals, close, q_names
+from abi_helpers import check_abi
+from ac_helpers import REFUSALS, TD3_ONE_UPDATE, TOL, alg_kwargs, check_host_restatement, check_refusals, close, q_names
 from conftest import ROOT, golden_meta, load_golden, rel_l2
 
 from gops_amd.create_pkg import create_alg as ca

@@ -7,7 +7,8 @@ import pytest
 import torch
 
 import trpo_helpers as th
-from ac_helpers import REFUSALS, alg_kwargs, check_abi, check_refusals
+from abi_helpers import check_abi
+from ac_helpers import REFUSALS, alg_kwargs, check_refusals
 from conftest import golden_meta, load_golden
 
 from gops_amd.create_pkg import create_alg as ca

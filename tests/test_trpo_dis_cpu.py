@@ -11,14 +11,13 @@ import torch
 
 import trpo_dis_helpers as td
 import trpo_helpers as th
-from ac_helpers import TOL, check_abi, check_refusals, close
+from abi_helpers import check_abi
+from ac_helpers import TOL, check_refusals, close
 from conftest import rel_l2
+from desc_helpers import BAD, ODD, UNS, P, mlp_desc
 
 from gops_amd import hip_backend as hb
 from gops_amd.create_pkg.create_alg import create_alg
-
-BAD, UNS = -1, -2
-P, ODD = 0x1000, 0x1004   # a pointer that is never followed / one that is not 8-byte aligned
 
 
 def _kw(**over):
@@ -96,15 +95,8 @@ def test_abi_of_the_categorical_entry_points(tmp_path):
     assert hb.CatFisherSeed.run is hb.FisherSeed.run and hb.CatTrpoSurrogate.set_delta is hb.TrpoSurrogate.set_delta
 
 
-def _mlp(sizes, n_layers=None):
-    m = hb.GopsMlp()
-    m.n_layers = len(sizes) - 1 if n_layers is None else n_layers
-    for i, s in enumerate(sizes):
-        m.sizes[i] = s
-    for j in range(len(sizes) - 1):
-        m.weight[j] = m.bias[j] = P
-    m.hidden_act = hb.ACT_IDS["relu"]
-    return m
+def _mlp(sizes, **fields):
+    return mlp_desc(sizes, act=hb.ACT_IDS["relu"], **fields)
 
 
 def _grad(weight0=P, bias1=P):
