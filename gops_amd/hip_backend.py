@@ -19,6 +19,7 @@ MAX_LAYERS, MAX_ACT, MAX_LQ, TILE = 5, 4, 6, 16
 ENV_NONE, ENV_LQ, ENV_IDP, ENV_VEH, ENV_VEH_SURR, ENV_CARTPOLE, ENV_PENDULUM, ENV_VEH2DOF, ENV_MOBILEROBOT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ENV_MOUNTAINCAR = 9
 STATE_OBS_ENV_KINDS = (ENV_LQ, ENV_IDP, ENV_CARTPOLE, ENV_PENDULUM, ENV_MOUNTAINCAR)   # the models whose observation is the state
+REF_TRAJ_ENV_KINDS = (ENV_VEH, ENV_VEH_SURR, ENV_VEH2DOF)   # the vehicle families: their state and reference trajectory travel as INFO_KEYS
 DATA_ENV_KINDS = (ENV_LQ, ENV_IDP, ENV_VEH, ENV_CARTPOLE, ENV_VEH2DOF, ENV_MOBILEROBOT)   # the models whose data env gops_env_step restates
 MAX_CLIP_OBS = 16
 # std of the obstacle robot's per-step (v, w) noise draws (pyth_mobilerobot_model.py:141-147, std_type["obs"])
@@ -156,7 +157,8 @@ class GopsEpisodeOut(C.Structure):   # gops_episode_rollout
 
 SAMPLE_DETERM, SAMPLE_GAUSS, SAMPLE_TANH_GAUSS = 0, 1, 2   # include/gops_hip.h: GOPS_SAMPLE_*
 SAMPLE_WORKSPACE_BYTES = 256                             # include/gops_hip.h: GOPS_SAMPLE_WORKSPACE_BYTES
-SAMPLE_INFO_KEYS = ("state", "ref_points", "path_num", "u_num", "ref_time")
+INFO_KEYS = ("state", "ref_points", "path_num", "u_num", "ref_time")   # the info tensors of REF_TRAJ_ENV_KINDS
+SAMPLE_INFO_KEYS = INFO_KEYS   # (its name when only the sampler used it)
 
 
 class GopsSampleDesc(C.Structure):   # gops_sample_rollout
@@ -165,16 +167,16 @@ class GopsSampleDesc(C.Structure):   # gops_sample_rollout
 
 
 class GopsSampleState(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("obs",) + SAMPLE_INFO_KEYS + ("t", "reset_count")]
+    _fields_ = [(k, C.c_void_p) for k in ("obs",) + INFO_KEYS + ("t", "reset_count")]
 
 
 class GopsSamplePool(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("obs",) + SAMPLE_INFO_KEYS]
+    _fields_ = [(k, C.c_void_p) for k in ("obs",) + INFO_KEYS]
 
 
 class GopsSampleOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("obs", "act", "rew", "done", "obs2", "logp", "time_limited", "end")
-                + tuple(p + k for k in SAMPLE_INFO_KEYS for p in ("", "next_"))]
+                + tuple(p + k for k in INFO_KEYS for p in ("", "next_"))]
 
 
 SAMPLE_EPS_GREEDY, SAMPLE_CATEGORICAL = 3, 4   # include/gops_hip.h: GOPS_SAMPLE_EPS_GREEDY / _CATEGORICAL (gops_sample_rollout_dis)
@@ -345,7 +347,7 @@ def dw_plan_query(N: int, K: int, S: int, *, Kp: Optional[int] = None, f16=False
     weight-gradient GEMM dW[N][K] over S stash rows."""
     out = (C.c_int32 * 4)()
     kp = (K + 15) // 16 * 16 if Kp is None else Kp
-    check(lib().gops_dw_plan_query(N, K, kp, S, int(bool(f16)), int(bool(scaled)), vflags, dw_workgroups, out), "gops_dw_plan_query")
+    _call("gops_dw_plan_query", N, K, kp, S, int(bool(f16)), int(bool(scaled)), vflags, dw_workgroups, out)
     return dict(kernel=out[0], splits=out[1], chunks_per_split=out[2], grid=out[3])
 
 
@@ -357,6 +359,11 @@ def check(rc: int, what: str):
         raise RuntimeError(f"{what} failed: {_ERR.get(rc, 'hipError_t ' + str(rc))}")
 
 
+def _call(name: str, *args):
+    """Call the entry point `name` of the library and raise on its return code: the launch and the name in its error are one."""
+    check(getattr(lib(), name)(*args), name)
+
+
 def _ptr(t: Optional[torch.Tensor]):
     if t is None:
         return None
@@ -366,6 +373,28 @@ def _ptr(t: Optional[torch.Tensor]):
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _default_device(device):
+    return device or torch.device("cuda", torch.cuda.current_device())
+
+
+def _own_workspace(obj, nbytes: int, device, refusal: Optional[str] = None, override: Optional[int] = None):
+    """`obj.device`, `obj.workspace` (one uint8 tensor, reused across calls) and `obj._workspace_bytes` from the byte count a
+    `*_workspace_bytes` / `*_state_bytes` query returned; `obj.supported` = the library holds the description (count != 0).
+    `refusal`: raised for a count of 0.  The optional form - no `refusal`, or `override` (a caller's own `workspace_bytes=`) -
+    never raises here: the entry point then refuses at the call, and the tensor is a placeholder of at least one byte."""
+    obj.supported = nbytes != 0
+    if refusal is not None and override is None and not obj.supported:
+        raise RuntimeError(refusal)
+    obj.device = _default_device(device)
+    obj._workspace_bytes = int(nbytes if override is None else override)
+    obj.workspace = torch.empty(max(obj._workspace_bytes, 1), dtype=torch.uint8, device=obj.device)
+
+
+def _ws(obj):
+    """The tail of every call that takes a workspace: (pointer, bytes, stream)."""
+    return obj.workspace.data_ptr(), obj._workspace_bytes, _stream()
 
 
 def _fill(arr, vals):
@@ -514,15 +543,6 @@ def _rollout_desc(env: GopsEnv, policy: Optional[GopsMlp], value: Optional[GopsM
     return d
 
 
-def _rollout_workspace(ro, bytes_fn, refusal: str, device):
-    """`ro.device` and `ro.workspace`, sized by the library for `ro.desc`; a descriptor it refuses raises `refusal`."""
-    nbytes = bytes_fn(C.byref(ro.desc))
-    if nbytes == 0:
-        raise RuntimeError(refusal)
-    ro.device = device or torch.device("cuda", torch.cuda.current_device())
-    ro.workspace = torch.empty(nbytes, dtype=torch.uint8, device=ro.device)
-
-
 def _rebind_nets(ro, policy: GopsMlp, value: Optional[GopsMlp]):
     if policy is not ro._mlps[0]:
         ro.desc.policy = policy
@@ -570,8 +590,8 @@ class Rollout:
         # raw_actions (open loop only): `head_pre` holds the model's actions themselves (GopsRolloutDesc.open_loop = 2)
         d.open_loop = (2 if raw_actions else 1) if policy is None else 0
         self._mlps = (policy, value)
-        _rollout_workspace(self, lib().gops_rollout_workspace_bytes,
-                           "gops_rollout_workspace_bytes: descriptor rejected (unsupported shape for the HIP path)", device)
+        _own_workspace(self, lib().gops_rollout_workspace_bytes(C.byref(d)), device,
+                       "gops_rollout_workspace_bytes: descriptor rejected (unsupported shape for the HIP path)")
         self._in = GopsRolloutIn()
         self._keep = None
 
@@ -589,8 +609,8 @@ class Rollout:
             i.head_pre = _ptr(head_pre)
             self._head_pre = head_pre
         i.obs, i.done = _ptr(data["obs"]), _ptr(data.get("done"))
-        if d.env.kind in (ENV_VEH, ENV_VEH_SURR, ENV_VEH2DOF):
-            for k in ("state", "ref_points", "path_num", "u_num", "ref_time"):
+        if d.env.kind in REF_TRAJ_ENV_KINDS:
+            for k in INFO_KEYS:
                 setattr(i, k, _ptr(data[k]))
         if d.env.kind == ENV_VEH_SURR:
             i.surr_state = _ptr(data.get("surr_state"))   # (None for the errcstr model: no surrounding vehicles)
@@ -607,7 +627,7 @@ class Rollout:
             i.noise = _ptr(noise)   # the kernels (and a later backward) read these tensors: keep them alive
         out, res = _rollout_outputs(self, want_rewards, want_final)
         if want_final:
-            if d.env.kind in (ENV_VEH, ENV_VEH_SURR, ENV_VEH2DOF):
+            if d.env.kind in REF_TRAJ_ENV_KINDS:
                 res["final_state"] = torch.empty(B, 4 if d.env.kind == ENV_VEH2DOF else 6, dtype=torch.float32, device=self.device)
                 out.final_state = _ptr(res["final_state"])
         if has_constraints(d.env):   # [4, B]: sum c+^2, sum c+, sum log(-c- + eps), feasible  (discounted, unmasked)
@@ -620,8 +640,7 @@ class Rollout:
             if want_constraints:   # [H, B, n_c]: the unmasked info["constraint"] of every step
                 res["constraints"] = torch.empty(H, B, nc, dtype=torch.float32, device=self.device)
                 out.constraints = _ptr(res["constraints"])
-        check(lib().gops_rollout_forward(C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(),
-                                         self.workspace.numel(), _stream()), "gops_rollout_forward")
+        _call("gops_rollout_forward", C.byref(d), C.byref(i), C.byref(out), *_ws(self))
         return res
 
     def backward(self, grad_v: torch.Tensor, grad_w: List[torch.Tensor], grad_b: List[torch.Tensor],
@@ -657,13 +676,10 @@ class Rollout:
         self.desc.variant_flags = flags | phase_bits
         try:
             if tail is not None:
-                check(lib().gops_rollout_backward_update(C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), C.byref(tail),
-                                                         self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-                      "gops_rollout_backward_update")
+                _call("gops_rollout_backward_update", C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), C.byref(tail),
+                      *_ws(self))
             else:
-                check(lib().gops_rollout_backward(C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g),
-                                                  self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-                      "gops_rollout_backward")
+                _call("gops_rollout_backward", C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), *_ws(self))
         finally:
             self.desc.variant_flags = flags
 
@@ -682,9 +698,8 @@ class Rollout:
         adj.grad_obs = _ptr(g_obs)
         adj.first_step_only = int(bool(first_step_only))
         g = make_mlp_grad(grad_w, grad_b) if grad_w is not None else None
-        check(lib().gops_rollout_backward_adj(C.byref(d), C.byref(self._in), _ptr(grad_v), C.byref(g) if g is not None else None,
-                                              C.byref(adj), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_rollout_backward_adj")
+        _call("gops_rollout_backward_adj", C.byref(d), C.byref(self._in), _ptr(grad_v), C.byref(g) if g is not None else None, C.byref(adj),
+              *_ws(self))
         return g_obs
 
     def backward_open_loop_adj(self, grad_v: torch.Tensor, grad_final_obs: Optional[torch.Tensor] = None):
@@ -696,9 +711,7 @@ class Rollout:
         g_obs = torch.empty(d.batch, d.env.obs_dim, dtype=torch.float32, device=self.device)
         adj = GopsRolloutAdjoint()
         adj.grad_final_obs, adj.grad_obs, adj.first_step_only = _ptr(grad_final_obs), _ptr(g_obs), 0
-        check(lib().gops_rollout_backward_open_loop_adj(C.byref(d), C.byref(self._in), _ptr(grad_v), _ptr(g), C.byref(adj),
-                                                        self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_rollout_backward_open_loop_adj")
+        _call("gops_rollout_backward_open_loop_adj", C.byref(d), C.byref(self._in), _ptr(grad_v), _ptr(g), C.byref(adj), *_ws(self))
         return g, g_obs
 
     def backward_open_loop(self, grad_v: torch.Tensor, grad_constraint_step: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -709,9 +722,7 @@ class Rollout:
         self._in.grad_constraint_step = _ptr(grad_constraint_step)
         self._grad_cs = grad_constraint_step
         g = torch.empty(d.batch, d.horizon, d.env.act_dim, dtype=torch.float32, device=self.device)
-        check(lib().gops_rollout_backward_open_loop(C.byref(d), C.byref(self._in), _ptr(grad_v), _ptr(g),
-                                                    self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_rollout_backward_open_loop")
+        _call("gops_rollout_backward_open_loop", C.byref(d), C.byref(self._in), _ptr(grad_v), _ptr(g), *_ws(self))
         return g
 
 
@@ -738,8 +749,9 @@ def _poly_grad(grad_w: torch.Tensor, grad_b: Optional[torch.Tensor]) -> GopsMlpG
 
 class _LaneRollout:
     """What the lane rollouts (csrc/lane_rollout.h) share here: the refusals, the descriptor and workspace set-up, `forward`.  A
-    subclass names its family, net and three library functions (`_fns`), and keeps `_prepare_nets`, `set_policy` and `backward`."""
-    _family = _net = _entry = _fns = None
+    subclass names its family, net and the stem of its three entry points (`_entry` + `_workspace_bytes` / `_forward` /
+    `_backward`), and keeps `_prepare_nets`, `set_policy` and `backward`."""
+    _family = _net = _entry = None
 
     def __init__(self, env: GopsEnv, policy: GopsMlp, value: Optional[GopsMlp], *, batch, horizon, gamma, finite_horizon, need_grad,
                  tail_unmasked, device, dtype, variant_flags):
@@ -752,8 +764,9 @@ class _LaneRollout:
         self.desc = _rollout_desc(env, policy, value, batch=batch, horizon=horizon, gamma=gamma, finite_horizon=finite_horizon,
                                   need_grad=need_grad, tail_unmasked=tail_unmasked)
         self._mlps = (policy, value)
-        _rollout_workspace(self, self._fns(lib())[0], f"{self._entry}_workspace_bytes: descriptor rejected ({self._net} net, env model "
-                           f"or wrapper outside the HIP {fam} path)", device)
+        query = self._entry + "_workspace_bytes"
+        _own_workspace(self, getattr(lib(), query)(C.byref(self.desc)), device,
+                       f"{query}: descriptor rejected ({self._net} net, env model or wrapper outside the HIP {fam} path)")
         self._in = GopsRolloutIn()
 
     def _prepare_nets(self, env, policy, value):
@@ -764,13 +777,11 @@ class _LaneRollout:
         i.obs, i.done = _ptr(data["obs"]), _ptr(data.get("done"))
         self._keep = dict(data)
         out, res = _rollout_outputs(self, want_rewards, want_final)
-        check(self._fns(lib())[1](C.byref(d), C.byref(i), C.byref(out), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              self._entry + "_forward")
+        _call(self._entry + "_forward", C.byref(d), C.byref(i), C.byref(out), *_ws(self))
         return res
 
     def _backward(self, grad_v, g: GopsMlpGrad, *adj):
-        check(self._fns(lib())[2](C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), *adj, self.workspace.data_ptr(),
-                             self.workspace.numel(), _stream()), self._entry + "_backward")
+        _call(self._entry + "_backward", C.byref(self.desc), C.byref(self._in), _ptr(grad_v), C.byref(g), *adj, *_ws(self))
 
 
 class PolyRollout(_LaneRollout):
@@ -779,7 +790,6 @@ class PolyRollout(_LaneRollout):
     layer's gradient tensors, as `grad_buffers` / `poly_grad_buffers` hand them out.  No phases, no fused update tail: a POLY net
     has one or two tensors."""
     _family, _net, _entry = "POLY", "POLY", "gops_poly_rollout"
-    _fns = staticmethod(lambda L: (L.gops_poly_rollout_workspace_bytes, L.gops_poly_rollout_forward, L.gops_poly_rollout_backward))
 
     def __init__(self, env: GopsEnv, policy: GopsMlp, *, batch: int, horizon: int, gamma: float, finite_horizon: bool,
                  need_grad: bool = True, value: Optional[GopsMlp] = None, device: Optional[torch.device] = None,
@@ -830,7 +840,6 @@ class RbfRollout(_LaneRollout):
     sigma_square, w, b).  No tail value (a caller composes it from `final_obs` and hands `grad_final_obs` back), no phases, no fused
     update tail."""
     _family, _net, _entry = "GAUSS", "RBF", "gops_rbf_rollout"
-    _fns = staticmethod(lambda L: (L.gops_rbf_rollout_workspace_bytes, L.gops_rbf_rollout_forward, L.gops_rbf_rollout_backward))
 
     def __init__(self, env: GopsEnv, policy: GopsMlp, *, batch: int, horizon: int, gamma: float, finite_horizon: bool,
                  need_grad: bool = True, device: Optional[torch.device] = None, dtype=None, variant_flags: Optional[int] = None):
@@ -861,11 +870,8 @@ class PolyValueNet:
     def __init__(self, value: GopsMlp, batch: int, obs_dim: int, device: Optional[torch.device] = None):
         value.sizes[0] = obs_dim
         self.mlp, self.batch, self.obs_dim = value, batch, obs_dim
-        nbytes = lib().gops_poly_value_workspace_bytes(C.byref(value), batch)
-        if nbytes == 0:
-            raise RuntimeError("gops_poly_value_workspace_bytes: unsupported POLY value network for the HIP path")
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _own_workspace(self, lib().gops_poly_value_workspace_bytes(C.byref(value), batch), device,
+                       "gops_poly_value_workspace_bytes: unsupported POLY value network for the HIP path")
 
     def set_net(self, value: GopsMlp):
         value.sizes[0] = self.obs_dim
@@ -873,16 +879,14 @@ class PolyValueNet:
 
     def forward(self, obs: torch.Tensor) -> torch.Tensor:
         v = torch.empty(self.batch, dtype=torch.float32, device=self.device)
-        check(lib().gops_poly_value_forward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(v), _stream()), "gops_poly_value_forward")
+        _call("gops_poly_value_forward", C.byref(self.mlp), self.batch, _ptr(obs), _ptr(v), _stream())
         return v
 
     def backward(self, obs: torch.Tensor, grad_v: torch.Tensor, grad_w, grad_b, tail=None):
         if tail is not None:
             raise NotImplementedError("PolyValueNet.backward: no fused update tail on the POLY path")
         g = _poly_grad(grad_w[0], grad_b[0] if grad_b else None)
-        check(lib().gops_poly_value_backward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g),
-                                             self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_poly_value_backward")
+        _call("gops_poly_value_backward", C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g), *_ws(self))
 
 
 def _small_mlp(weights, biases, act: str) -> GopsMlp:
@@ -901,13 +905,10 @@ class LipsPolicy:
 
     def __init__(self, module, batch: int, device: Optional[torch.device] = None):
         self.module, self.batch = module, int(batch)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.refresh()
-        nbytes = lib().gops_lips_workspace_bytes(C.byref(self.net), self.batch)
-        if nbytes == 0:
-            raise RuntimeError("gops_lips_workspace_bytes: descriptor rejected (LipsNet outside the HIP path: obs_dim <= 8, act_dim <= 4, "
-                               "1..3 hidden layers, K net global or 1..2 hidden layers, widths multiples of 16 up to 256)")
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _own_workspace(self, lib().gops_lips_workspace_bytes(C.byref(self.net), self.batch), device,
+                       "gops_lips_workspace_bytes: descriptor rejected (LipsNet outside the HIP path: obs_dim <= 8, act_dim <= 4, "
+                       "1..3 hidden layers, K net global or 1..2 hidden layers, widths multiples of 16 up to 256)")
         self._obs = None
 
     def refresh(self):
@@ -961,8 +962,7 @@ class LipsPolicy:
         act = torch.empty(B, m, dtype=torch.float32, device=self.device)
         K = torch.empty(B, dtype=torch.float32, device=self.device)
         N = torch.empty(B, dtype=torch.float32, device=self.device)
-        check(lib().gops_lips_forward(C.byref(self.net), B, _ptr(obs), _ptr(act), _ptr(K), _ptr(N), self.workspace.data_ptr(),
-                                      self.workspace.numel(), _stream()), "gops_lips_forward")
+        _call("gops_lips_forward", C.byref(self.net), B, _ptr(obs), _ptr(act), _ptr(K), _ptr(N), *_ws(self))
         self._obs = obs
         return act, K, N
 
@@ -974,8 +974,7 @@ class LipsPolicy:
             raise RuntimeError(f"LipsPolicy.backward: grad_action {tuple(grad_action.shape)} on {grad_action.device}, expected "
                                f"{(self.batch, m)} on {self.device}")
         grads = self.grads()
-        check(lib().gops_lips_backward(C.byref(self.net), self.batch, _ptr(self._obs), _ptr(grad_action), C.byref(self._g),
-                                       self.workspace.data_ptr(), self.workspace.numel(), _stream()), "gops_lips_backward")
+        _call("gops_lips_backward", C.byref(self.net), self.batch, _ptr(self._obs), _ptr(grad_action), C.byref(self._g), *_ws(self))
         return grads
 
 
@@ -987,7 +986,7 @@ class _RpiState:
     def __init__(self, env_kind: int, batch: int, state_dim: int, consts, device, state_bytes: int, refusal: str):
         self.kind, self.batch, self.state_dim = int(env_kind), int(batch), int(state_dim)
         self.consts = (C.c_float * RPI_CONST_COUNT)(*[float(v) for v in consts])
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.device = _default_device(device)
         if state_bytes == 0:
             raise RuntimeError(refusal)
         self.state = torch.zeros(state_bytes // 4, dtype=torch.float32, device=self.device)
@@ -1021,10 +1020,9 @@ class RpiEvaluator(_RpiState):
         """Enqueues the launch; returns the device result [steps taken, last loss, norm_before, norm_after].  `pool` is
         [max_steps + 1, state_dim, B]: the held-out set, then one reset draw per step."""
         self._check(pool, max_steps, trace)
-        check(lib().gops_rpi_evaluate(self.kind, self.batch, int(max_steps), self.consts, _ptr(weight), _ptr(target_weight),
-                                      _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr),
-                                      float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),
-              "gops_rpi_evaluate")
+        _call("gops_rpi_evaluate", self.kind, self.batch, int(max_steps), self.consts, _ptr(weight), _ptr(target_weight), _ptr(max_step),
+              _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr), float(beta1), float(beta2), float(eps),
+              _ptr(self.result), _ptr(trace), _stream())
         return self.result
 
 
@@ -1054,10 +1052,9 @@ class RpiMlpEvaluator(_RpiState):
         """Enqueues the launch; returns the device result [steps taken, last loss, norm_before, norm_after].  `pool` is
         [max_steps + 1, state_dim, B]: the held-out set, then one reset draw per step."""
         self._check(pool, max_steps, trace)
-        check(lib().gops_rpi_mlp_evaluate(self.kind, self.batch, int(max_steps), self.consts, C.byref(self.value), C.byref(self.target),
-                                          _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr),
-                                          float(beta1), float(beta2), float(eps), _ptr(self.result), _ptr(trace), _stream()),
-              "gops_rpi_mlp_evaluate")
+        _call("gops_rpi_mlp_evaluate", self.kind, self.batch, int(max_steps), self.consts, C.byref(self.value), C.byref(self.target),
+              _ptr(max_step), _ptr(pool), self.state.data_ptr(), self.state.numel() * 4, float(lr), float(beta1), float(beta2), float(eps),
+              _ptr(self.result), _ptr(trace), _stream())
         return self.result
 
 
@@ -1085,31 +1082,41 @@ class EpisodeRollout:
                     if lim is not None:
                         _fill(field, np.broadcast_to(np.asarray(torch.as_tensor(lim).detach().cpu(), dtype=np.float32).reshape(-1), (env.act_dim,)))
         self.env, self.policy, self.episodes, self.max_steps = env, policy, int(episodes), int(max_steps)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.action_table = action_table
-        # the one place that knows which of the three forms this is: the query, the entry point, the arguments only `_dis` / `_mode` take
-        query, self._name, query_extra, self._extra, self._act_width = "gops_episode_workspace_bytes", "gops_episode_rollout", (), (), env.act_dim
+        rows = None
         if action_table is not None:
             assert action_table.dim() == 2 and action_table.shape[1] == env.act_dim, "action_table must be [act_num, act_dim]"
-            self.act_num = int(action_table.shape[0])
-            query, self._name, self._act_width = "gops_episode_dis_workspace_bytes", "gops_episode_rollout_dis", 1
-            query_extra, self._extra = (self.act_num,), (_ptr(action_table), self.act_num)
-        elif mode_head is not None:
-            query, self._name = "gops_episode_mode_workspace_bytes", "gops_episode_rollout_mode"
-            query_extra = self._extra = (int(mode_head),)
-        nbytes = getattr(lib(), query)(C.byref(env), C.byref(policy), *query_extra, self.episodes, self.max_steps)
-        if workspace_bytes is None:
-            if nbytes == 0:   # ask the entry point itself for the reason
-                check(self._call(None, None, None, 0, None), self._name)
-                raise RuntimeError(query + ": description refused")
-            workspace_bytes = nbytes
-        self.workspace = torch.empty(max(int(workspace_bytes), 1), dtype=torch.uint8, device=self.device)
-        self._workspace_bytes = int(workspace_bytes)
+            rows = self.act_num = int(action_table.shape[0])
+        query, self._name, self._extra = self._form(rows, mode_head)
+        self._act_width = env.act_dim if rows is None else 1
+        if rows is not None:   # (the call also takes the table itself)
+            self._extra = (_ptr(action_table),) + self._extra
+        nbytes = EpisodeRollout.workspace_bytes(env, policy, episodes=episodes, max_steps=max_steps, action_table_rows=rows, mode_head=mode_head)
+        if nbytes == 0 and workspace_bytes is None:   # ask the entry point itself for the reason
+            self._launch(None, None, None, 0, None)
+        _own_workspace(self, nbytes, device, query + ": description refused", override=workspace_bytes)
 
-    def _call(self, io, out, ws, ws_bytes, stream):
+    @staticmethod
+    def _form(action_table_rows: Optional[int], mode_head: Optional[int]):
+        """The one place that knows which of the three forms this is: (the workspace query, the entry point, the arguments only
+        `_dis` / `_mode` take)."""
+        if action_table_rows is not None:
+            return "gops_episode_dis_workspace_bytes", "gops_episode_rollout_dis", (int(action_table_rows),)
+        if mode_head is not None:
+            return "gops_episode_mode_workspace_bytes", "gops_episode_rollout_mode", (int(mode_head),)
+        return "gops_episode_workspace_bytes", "gops_episode_rollout", ()
+
+    @staticmethod
+    def workspace_bytes(env: GopsEnv, policy: GopsMlp, *, episodes: int, max_steps: int, action_table_rows: Optional[int] = None,
+                        mode_head: Optional[int] = None) -> int:
+        """What the library's query answers for this description, in the form `__init__` would choose: 0 = it refuses it."""
+        query, _, extra = EpisodeRollout._form(action_table_rows, mode_head)
+        return getattr(lib(), query)(C.byref(env), C.byref(policy), *extra, int(episodes), int(max_steps))
+
+    def _launch(self, io, out, ws, ws_bytes, stream):
         ref = lambda x: None if x is None else C.byref(x)   # noqa: E731
-        return getattr(lib(), self._name)(C.byref(self.env), C.byref(self.policy), *self._extra, self.episodes, self.max_steps, ref(io),
-                                          ref(out), ws, ws_bytes, stream)
+        _call(self._name, C.byref(self.env), C.byref(self.policy), *self._extra, self.episodes, self.max_steps, ref(io), ref(out), ws,
+              ws_bytes, stream)
 
     def set_policy(self, policy: GopsMlp):
         self.policy = policy
@@ -1122,7 +1129,7 @@ class EpisodeRollout:
         assert init["obs"].shape[0] == E
         io, out = GopsStepIO(), GopsEpisodeOut()
         io.obs = _ptr(init["obs"])
-        for k in ("state", "ref_points", "path_num", "u_num", "ref_time"):
+        for k in INFO_KEYS:
             if init.get(k) is not None:
                 setattr(io, k, _ptr(init[k]))
         res = dict(ret=torch.empty(E, dtype=torch.float32, device=dev), length=torch.empty(E, dtype=torch.int32, device=dev),
@@ -1134,7 +1141,7 @@ class EpisodeRollout:
                        trace_rew=mk(E, T))
         for k, v in res.items():
             setattr(out, k, v.data_ptr())
-        check(self._call(io, out, self.workspace.data_ptr(), self._workspace_bytes, _stream()), self._name)
+        self._launch(io, out, *_ws(self))
         return res
 
 
@@ -1153,28 +1160,24 @@ class SampleRollout:
         """`info_like`: the info tensors of the persistent state ([n_envs, ...] each; the vehicle families) - their trailing shapes
         are the output columns'."""
         self.env, self.policy, self.n_envs, self.steps = env, policy, int(n_envs), int(steps)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.desc = GopsSampleDesc(head=int(head), max_episode_steps=int(max_episode_steps), pool_rows=int(pool_rows), reserved=0,
                                    noise_std=float(noise_std), min_log_std=float(min_log_std), max_log_std=float(max_log_std))
-        self.action_table, self.dis = action_table, None
-        # the one place that knows which of the two forms this is: the query, the entry point, the arguments only `_dis` takes
-        query, self._name, query_extra, self._extra = "gops_sample_workspace_bytes", "gops_sample_rollout", (), ()
+        self.action_table, self.dis, self._extra = action_table, None, ()
         self.noise_width = act_width = env.act_dim
+        rows = None
         if action_table is not None:
             assert action_table.dim() == 2 and action_table.shape[1] == env.act_dim, "action_table must be [act_num, act_dim]"
-            self.dis = GopsSampleDis(action_table=_ptr(action_table), act_num=int(action_table.shape[0]), head=int(head),
-                                     epsilon=float(epsilon), env_act=None)
-            query, self._name, self.noise_width, act_width = "gops_sample_dis_workspace_bytes", "gops_sample_rollout_dis", 2, 1
-            query_extra, self._extra = (self.dis.act_num,), (C.byref(self.dis),)
-        nbytes = getattr(lib(), query)(C.byref(env), C.byref(policy), *query_extra, self.n_envs, self.steps)
-        if nbytes == 0:
-            raise RuntimeError(query + ": description refused")
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            rows = int(action_table.shape[0])
+            self.dis = GopsSampleDis(action_table=_ptr(action_table), act_num=rows, head=int(head), epsilon=float(epsilon), env_act=None)
+            self.noise_width, act_width, self._extra = 2, 1, (C.byref(self.dis),)
+        query, self._name, _ = self._form(rows)
+        _own_workspace(self, SampleRollout.workspace_bytes(env, policy, n_envs=n_envs, steps=steps, action_table_rows=rows), device,
+                       query + ": description refused")
         T, N = self.steps, self.n_envs
         mk = lambda *sh: torch.empty((T, N) + tuple(sh), dtype=torch.float32, device=self.device)   # noqa: E731
         self.out = dict(obs=mk(env.obs_dim), act=mk(act_width), rew=mk(), done=mk(), obs2=mk(env.obs_dim),
                         logp=mk(), time_limited=mk(), end=mk())
-        self.info_keys = tuple(k for k in SAMPLE_INFO_KEYS if info_like and k in info_like)
+        self.info_keys = tuple(k for k in INFO_KEYS if info_like and k in info_like)
         for k in self.info_keys:
             self.out[k], self.out["next_" + k] = mk(*info_like[k].shape[1:]), mk(*info_like[k].shape[1:])
         self._out = GopsSampleOut()
@@ -1183,6 +1186,20 @@ class SampleRollout:
         if self.dis is not None:   # (not a field of GopsSampleOut: the dis struct's own output)
             self.out["env_act"] = mk(env.act_dim)
             self.dis.env_act = self.out["env_act"].data_ptr()
+
+    @staticmethod
+    def _form(action_table_rows: Optional[int]):
+        """The one place that knows which of the two forms this is: (the workspace query, the entry point, the argument only the
+        `_dis` query takes)."""
+        if action_table_rows is not None:
+            return "gops_sample_dis_workspace_bytes", "gops_sample_rollout_dis", (int(action_table_rows),)
+        return "gops_sample_workspace_bytes", "gops_sample_rollout", ()
+
+    @staticmethod
+    def workspace_bytes(env: GopsEnv, policy: GopsMlp, *, n_envs: int, steps: int, action_table_rows: Optional[int] = None) -> int:
+        """What the library's query answers for this description, in the form `__init__` would choose: 0 = it refuses it."""
+        query, _, extra = SampleRollout._form(action_table_rows)
+        return getattr(lib(), query)(C.byref(env), C.byref(policy), *extra, int(n_envs), int(steps))
 
     def set_policy(self, policy: GopsMlp):
         self.policy = policy
@@ -1201,9 +1218,8 @@ class SampleRollout:
             v = state[k]
             assert v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.numel() == N, k
             setattr(st, k, v.data_ptr())
-        check(getattr(lib(), self._name)(C.byref(self.env), C.byref(self.policy), C.byref(self.desc), *self._extra, N, T, C.byref(st),
-                                         C.byref(pl), _ptr(noise), C.byref(self._out), self.workspace.data_ptr(), self.workspace.numel(),
-                                         _stream()), self._name)
+        _call(self._name, C.byref(self.env), C.byref(self.policy), C.byref(self.desc), *self._extra, N, T, C.byref(st), C.byref(pl),
+              _ptr(noise), C.byref(self._out), *_ws(self))
         return self.out
 
 
@@ -1212,30 +1228,22 @@ class ValueNet:
 
     def __init__(self, value: GopsMlp, batch: int, device: Optional[torch.device] = None):
         self.mlp, self.batch = value, batch
-        nbytes = lib().gops_value_workspace_bytes(C.byref(value), batch)
-        if nbytes == 0:
-            raise RuntimeError("gops_value_workspace_bytes: unsupported value network for the HIP path")
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _own_workspace(self, lib().gops_value_workspace_bytes(C.byref(value), batch), device,
+                       "gops_value_workspace_bytes: unsupported value network for the HIP path")
 
     def forward(self, obs: torch.Tensor) -> torch.Tensor:
         v = torch.empty(self.batch, dtype=torch.float32, device=self.device)
-        check(lib().gops_value_forward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(v),
-                                       self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_value_forward")
+        _call("gops_value_forward", C.byref(self.mlp), self.batch, _ptr(obs), _ptr(v), *_ws(self))
         return v
 
     def backward(self, obs: torch.Tensor, grad_v: torch.Tensor, grad_w, grad_b, tail: Optional["GopsUpdateTail"] = None):
         """`tail` (ABI v12, `gops_value_backward_update`): Adam step (+ Polyak step of the target) folded into the launch that forms the gradients."""
         g = make_mlp_grad(grad_w, grad_b)
         if tail is not None:
-            check(lib().gops_value_backward_update(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g), C.byref(tail),
-                                                   self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-                  "gops_value_backward_update")
+            _call("gops_value_backward_update", C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g), C.byref(tail),
+                  *_ws(self))
             return
-        check(lib().gops_value_backward(C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g),
-                                        self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_value_backward")
+        _call("gops_value_backward", C.byref(self.mlp), self.batch, _ptr(obs), _ptr(grad_v), C.byref(g), *_ws(self))
 
 
 class MlpNet:
@@ -1245,32 +1253,26 @@ class MlpNet:
     def __init__(self, mlp: GopsMlp, batch: int, device: Optional[torch.device] = None):
         self.mlp, self.batch = mlp, batch
         self.out_dim = int(mlp.sizes[mlp.n_layers])
-        nbytes = lib().gops_mlp_workspace_bytes(C.byref(mlp), batch)
-        if nbytes == 0:
-            raise RuntimeError("gops_mlp_workspace_bytes: unsupported network for the HIP path")
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _own_workspace(self, lib().gops_mlp_workspace_bytes(C.byref(mlp), batch), device,
+                       "gops_mlp_workspace_bytes: unsupported network for the HIP path")
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`out`: a contiguous tensor of batch * out_dim floats that receives the result (e.g. one row of a [n, batch] buffer)."""
         y = torch.empty(self.batch, self.out_dim, dtype=torch.float32, device=self.device) if out is None else out
         assert y.numel() == self.batch * self.out_dim
-        check(lib().gops_mlp_forward(C.byref(self.mlp), self.batch, _ptr(x), _ptr(y), self.workspace.data_ptr(),
-                                     self.workspace.numel(), _stream()), "gops_mlp_forward")
+        _call("gops_mlp_forward", C.byref(self.mlp), self.batch, _ptr(x), _ptr(y), *_ws(self))
         return y
 
     def backward(self, x: torch.Tensor, grad_y: torch.Tensor, grad_w, grad_b):
         g = make_mlp_grad(grad_w, grad_b)
-        check(lib().gops_mlp_backward(C.byref(self.mlp), self.batch, _ptr(x), _ptr(grad_y), C.byref(g),
-                                      self.workspace.data_ptr(), self.workspace.numel(), _stream()), "gops_mlp_backward")
+        _call("gops_mlp_backward", C.byref(self.mlp), self.batch, _ptr(x), _ptr(grad_y), C.byref(g), *_ws(self))
 
     def backward_x(self, x: torch.Tensor, grad_y: torch.Tensor, grad_w=None, grad_b=None) -> torch.Tensor:
         """`gops_mlp_backward_x`: returns d(loss)/d(x); parameter gradients too when grad_w / grad_b are given."""
         g = make_mlp_grad(grad_w, grad_b) if grad_w is not None else None
         gx = torch.empty(self.batch, int(self.mlp.sizes[0]), dtype=torch.float32, device=self.device)
-        check(lib().gops_mlp_backward_x(C.byref(self.mlp), self.batch, _ptr(x), _ptr(grad_y), C.byref(g) if g is not None else None,
-                                        _ptr(gx), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
-              "gops_mlp_backward_x")
+        _call("gops_mlp_backward_x", C.byref(self.mlp), self.batch, _ptr(x), _ptr(grad_y), C.byref(g) if g is not None else None, _ptr(gx),
+              *_ws(self))
         return gx
 
 
@@ -1283,8 +1285,8 @@ def env_step(env: GopsEnv, obs, action, done, info: Optional[Dict[str, torch.Ten
     io.obs, io.action, io.done = _ptr(obs), _ptr(action), _ptr(done)
     io.next_obs, io.reward, io.next_done = _ptr(nobs), _ptr(rew), _ptr(ndone)
     ninfo = {}
-    if env.kind in (ENV_VEH, ENV_VEH_SURR, ENV_VEH2DOF):
-        for k in ("state", "ref_points", "path_num", "u_num", "ref_time"):
+    if env.kind in REF_TRAJ_ENV_KINDS:
+        for k in INFO_KEYS:
             setattr(io, k, _ptr(info[k]))
         ninfo = dict(state=torch.empty_like(info["state"]), ref_points=torch.empty_like(info["ref_points"]),
                      ref_time=torch.empty_like(info["ref_time"]), path_num=info["path_num"], u_num=info["u_num"])
@@ -1304,7 +1306,7 @@ def env_step(env: GopsEnv, obs, action, done, info: Optional[Dict[str, torch.Ten
         ninfo["constraint"] = torch.empty(B, env.n_constraint, dtype=torch.float32, device=obs.device)
         io.surr_state, io.next_surr_state = _ptr(info["surr_state"]), _ptr(ninfo["surr_state"])
         io.constraint = _ptr(ninfo["constraint"])
-    check(lib().gops_env_step(C.byref(env), B, C.byref(io), _stream()), "gops_env_step")
+    _call("gops_env_step", C.byref(env), B, C.byref(io), _stream())
     return nobs, rew, ndone, ninfo
 
 
@@ -1316,8 +1318,14 @@ def env_constraint(env: GopsEnv, obs, info: Optional[Dict[str, torch.Tensor]] = 
     io.obs, io.constraint = _ptr(obs), _ptr(out)
     if info:
         io.state, io.surr_state = _ptr(info.get("state")), _ptr(info.get("surr_state"))
-    check(lib().gops_env_constraint(C.byref(env), B, C.byref(io), _stream()), "gops_env_constraint")
+    _call("gops_env_constraint", C.byref(env), B, C.byref(io), _stream())
     return out
+
+
+def _adam_entry(t: GopsAdamTensors, i: int, param, grad, exp_avg=None, exp_avg_sq=None):
+    """Tensor `i` of a `GopsAdamTensors` (for `gops_polyak_update`, without moments: param = the target, grad = the online tensor)."""
+    t.numel[i], t.param[i], t.grad[i] = param.numel(), _ptr(param), _ptr(grad)
+    t.exp_avg[i], t.exp_avg_sq[i] = _ptr(exp_avg), _ptr(exp_avg_sq)
 
 
 class HipAdam(torch.optim.Optimizer):
@@ -1441,12 +1449,10 @@ class HipAdam(torch.optim.Optimizer):
         t.n = len(ps)
         keep = []
         for i, p in enumerate(ps):
-            st = self.state[p]
             if not p.grad.is_contiguous():
                 return None
             keep.append(p.grad)
-            t.numel[i], t.param[i], t.grad[i] = p.numel(), _ptr(p.data), _ptr(p.grad)
-            t.exp_avg[i], t.exp_avg_sq[i] = _ptr(st["exp_avg"]), _ptr(st["exp_avg_sq"])
+            _adam_entry(t, i, p.data, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"])
         b1, b2 = group["betas"]
         self._fused = (ps, dev)
         return t, dev["state"][0].data_ptr(), float(b1), float(b2), float(group["eps"]), keep
@@ -1472,13 +1478,10 @@ class HipAdam(torch.optim.Optimizer):
                 t.n = len(chunk)
                 keep = []
                 for i, p in enumerate(chunk):
-                    st = self.state[p]
                     g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                     keep.append(g)
-                    t.numel[i], t.param[i], t.grad[i] = p.numel(), _ptr(p.data), _ptr(g)
-                    t.exp_avg[i], t.exp_avg_sq[i] = _ptr(st["exp_avg"]), _ptr(st["exp_avg_sq"])
-                check(lib().gops_adam_step(C.byref(t), dev["state"][ci].data_ptr(), b1, b2, group["eps"], _stream()),
-                      "gops_adam_step")
+                    _adam_entry(t, i, p.data, g, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"])
+                _call("gops_adam_step", C.byref(t), dev["state"][ci].data_ptr(), b1, b2, group["eps"], _stream())
             for p in ps:
                 self.state[p]["step"] = int(self.state[p]["step"]) + 1
             dev["step"] += 1
@@ -1497,12 +1500,12 @@ class LossStats:
     def value_loss(self, v: torch.Tensor, target: torch.Tensor, grad: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> [mean((v - target)^2), mean(v)]; `grad` <- (2 / n) (v - target) (gops/algorithm/infadp.py:172-173)."""
         n = v.numel()
-        check(lib().gops_value_loss(_ptr(v), _ptr(target), n, _ptr(grad), self.buf.data_ptr(), _stream()), "gops_value_loss")
+        _call("gops_value_loss", _ptr(v), _ptr(target), n, _ptr(grad), self.buf.data_ptr(), _stream())
         return self.buf[:2]
 
     def mean_loss(self, x: torch.Tensor, scale: float = -1.0) -> torch.Tensor:
         """-> [scale * mean(x), mean(x)] (`-v_pi.mean()`: infadp.py:213, fhadp.py:123)."""
-        check(lib().gops_mean_loss(_ptr(x), x.numel(), float(scale), self.buf.data_ptr(), _stream()), "gops_mean_loss")
+        _call("gops_mean_loss", _ptr(x), x.numel(), float(scale), self.buf.data_ptr(), _stream())
         return self.buf[:2]
 
 
@@ -1519,28 +1522,26 @@ class _BackupBase:
                      workspace_bytes: Optional[int]):
         d = self.desc = desc
         self.batch, self.n_q = int(batch), len(critics)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
         for name, vals in limits.items():
             _fill(getattr(d, name), np.asarray(vals, dtype=np.float32).reshape(-1)[:MAX_ACT])
         self.set_nets(policy, critics)
-        nbytes = getattr(lib(), self._workspace_fn)(C.byref(d), self.batch)
-        self.supported = nbytes != 0
-        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
-        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
+        _own_workspace(self, getattr(lib(), self._workspace_fn)(C.byref(d), self.batch), device, override=workspace_bytes)
 
-    def set_nets(self, policy: GopsMlp, critics: Sequence[GopsMlp]):
+    def set_nets(self, policy: Optional[GopsMlp], critics: Sequence[GopsMlp]):
+        """`policy` None: a description without one (DQN), whose `q` is a single net and no array."""
         assert len(critics) == self.n_q
-        C.memmove(C.byref(self.desc.policy), C.byref(policy), C.sizeof(GopsMlp))
-        for i, c in enumerate(critics):
-            C.memmove(C.byref(self.desc.q[i]), C.byref(c), C.sizeof(GopsMlp))
+        q = self.desc.q
+        nets = list(zip(q if isinstance(q, C.Array) else (q,), critics)) + ([] if policy is None else [(self.desc.policy, policy)])
+        for field, net in nets:
+            C.memmove(C.byref(field), C.byref(net), C.sizeof(GopsMlp))
         self._keep = (policy, list(critics))   # the description holds raw pointers
 
-    def _outputs(self, out: Optional[Dict[str, torch.Tensor]], want, shapes) -> Dict[str, torch.Tensor]:
-        """`out`, and a fresh tensor for every output named in `want` that it does not supply."""
+    def _outputs(self, out: Optional[Dict[str, torch.Tensor]], want, shapes, int32=()) -> Dict[str, torch.Tensor]:
+        """`out`, and a fresh tensor for every output named in `want` that it does not supply (fp32; int32 for those named so)."""
         res = dict(out or {})
         for k in want:
             if k not in res:
-                res[k] = torch.empty(shapes[k], dtype=torch.float32, device=self.device)
+                res[k] = torch.empty(shapes[k], dtype=torch.int32 if k in int32 else torch.float32, device=self.device)
         return res
 
 
@@ -1570,9 +1571,8 @@ class AcBackup(_BackupBase):
         d.target_noise, d.noise_clip, d.reward_scale, d.gamma = float(target_noise), float(noise_clip), float(reward_scale), float(gamma)
         res = self._outputs(out, ("backup",) + (("a2",) if want_a2 else ()) + (("q_targ",) if want_q else ()),
                             dict(backup=(B,), a2=(B, self.act_dim), q_targ=(self.n_q, B)))
-        check(lib().gops_ac_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(xi), res["backup"].data_ptr(),
-                                   res["a2"].data_ptr() if "a2" in res else None, res["q_targ"].data_ptr() if "q_targ" in res else None,
-                                   self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_ac_backup")
+        _call("gops_ac_backup", C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(xi), res["backup"].data_ptr(),
+              res["a2"].data_ptr() if "a2" in res else None, res["q_targ"].data_ptr() if "q_targ" in res else None, *_ws(self))
         return res
 
 
@@ -1589,8 +1589,7 @@ class AcCriticLoss:
         n_q, B = q.shape
         seed = torch.empty_like(q) if seed is None else seed
         abs_err = torch.empty(B, dtype=torch.float32, device=q.device) if abs_err is None else abs_err
-        check(lib().gops_ac_critic_loss(_ptr(q), _ptr(backup), _ptr(weight), n_q, B, _ptr(seed), _ptr(abs_err), self.buf.data_ptr(),
-                                        _stream()), "gops_ac_critic_loss")
+        _call("gops_ac_critic_loss", _ptr(q), _ptr(backup), _ptr(weight), n_q, B, _ptr(seed), _ptr(abs_err), self.buf.data_ptr(), _stream())
         return seed, abs_err, self.buf[:4]
 
 
@@ -1598,26 +1597,21 @@ DQN_MAX_ACTIONS = 16           # include/gops_hip.h: GOPS_DQN_MAX_ACTIONS
 DQN_LOSS_STATS_FLOATS = 392    # include/gops_hip.h: GOPS_DQN_LOSS_STATS_FLOATS
 
 
-class DqnBackup:
+class DqnBackup(_BackupBase):
     """DQN's max-Q backup in ONE launch (`gops_dqn_backup`, csrc/actor_critic.hip): the target ActionValueDis on obs2, the row's
     maximum and arg-max over its `act_num` outputs, `rew * reward_scale + gamma * (1 - done) * max`.  `q`: the `GopsMlp` view of the
     TARGET network (read in place at every call).  `supported` is False for a shape the kernel does not hold: the caller then composes
     the backup from `MlpNet.forward` and `torch.max`; `run` on such a description raises."""
 
+    _workspace_fn = "gops_dqn_backup_workspace_bytes"
+
     def __init__(self, q: GopsMlp, *, batch: int, device: Optional[torch.device] = None, workspace_bytes: Optional[int] = None):
-        d = self.desc = GopsDqnBackup()
-        self.batch = int(batch)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.set_net(q)
+        d = GopsDqnBackup()
         self.act_num = d.act_num = int(q.sizes[q.n_layers])
-        nbytes = lib().gops_dqn_backup_workspace_bytes(C.byref(d), self.batch)
-        self.supported = nbytes != 0
-        self._workspace_bytes = int(nbytes if workspace_bytes is None else workspace_bytes)
-        self.workspace = torch.empty(max(self._workspace_bytes, 1), dtype=torch.uint8, device=self.device)
+        self._init_backup(d, None, [q], {}, batch, device, workspace_bytes)
 
     def set_net(self, q: GopsMlp):
-        C.memmove(C.byref(self.desc.q), C.byref(q), C.sizeof(GopsMlp))
-        self._keep = q   # the description holds raw pointers
+        self.set_nets(None, [q])
 
     def run(self, obs2, rew, done, *, reward_scale=1.0, gamma=0.99, want_q=False, want_a=False,
             out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
@@ -1626,16 +1620,12 @@ class DqnBackup:
         B, d = self.batch, self.desc
         assert obs2.shape[0] == B
         d.reward_scale, d.gamma = float(reward_scale), float(gamma)
-        res = dict(out or {})
-        for k, want, shape, dtype in (("backup", True, (B,), torch.float32), ("q_targ", want_q, (B, self.act_num), torch.float32),
-                                      ("a_star", want_a, (B,), torch.int32)):
-            if want and k not in res:
-                res[k] = torch.empty(shape, dtype=dtype, device=self.device)
+        res = self._outputs(out, ("backup",) + (("q_targ",) if want_q else ()) + (("a_star",) if want_a else ()),
+                            dict(backup=(B,), q_targ=(B, self.act_num), a_star=(B,)), int32=("a_star",))
         a_star = res.get("a_star")
         assert a_star is None or (a_star.is_cuda and a_star.dtype == torch.int32 and a_star.is_contiguous())
-        check(lib().gops_dqn_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(res["backup"]), _ptr(res.get("q_targ")),
-                                    None if a_star is None else a_star.data_ptr(), self.workspace.data_ptr(), self._workspace_bytes,
-                                    _stream()), "gops_dqn_backup")
+        _call("gops_dqn_backup", C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(res["backup"]), _ptr(res.get("q_targ")),
+              None if a_star is None else a_star.data_ptr(), *_ws(self))
         return res
 
 
@@ -1655,8 +1645,8 @@ class DqnLoss:
         seed = torch.empty_like(q_all) if seed is None else seed
         abs_err = torch.empty(B, dtype=torch.float32, device=q_all.device) if abs_err is None else abs_err
         assert seed.numel() == B * N and abs_err.numel() == B
-        check(lib().gops_dqn_loss(_ptr(q_all), _ptr(act), _ptr(backup), _ptr(weight), N, B, _ptr(seed), _ptr(abs_err),
-                                  self.buf.data_ptr(), _stream()), "gops_dqn_loss")
+        _call("gops_dqn_loss", _ptr(q_all), _ptr(act), _ptr(backup), _ptr(weight), N, B, _ptr(seed), _ptr(abs_err), self.buf.data_ptr(),
+              _stream())
         return seed, abs_err, self.buf[:3]
 
 
@@ -1697,9 +1687,8 @@ class SoftBackup(_SoftBackupBase):
         d.gamma, d.alpha = float(gamma), float(alpha)
         res = self._outputs(out, ("target_q", "target_q_sample") + tuple(want),
                             dict(target_q=(B,), target_q_sample=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(2, B, 2)))
-        check(lib().gops_soft_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["target_q"]),
-                                     _ptr(res["target_q_sample"]), _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")),
-                                     self.workspace.data_ptr(), self._workspace_bytes, _stream()), "gops_soft_backup")
+        _call("gops_soft_backup", C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["target_q"]),
+              _ptr(res["target_q_sample"]), _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")), *_ws(self))
         return res
 
 
@@ -1721,8 +1710,8 @@ class DsactCriticLoss:
         B = qraw.shape[1]
         assert tuple(qraw.shape) == (2, B, 2)
         seed = torch.empty_like(qraw) if seed is None else seed
-        check(lib().gops_dsact_critic_loss(_ptr(qraw), _ptr(target_q), _ptr(target_q_sample), B, float(tau_b), self.state.data_ptr(),
-                                           _ptr(seed), self.buf.data_ptr(), _stream()), "gops_dsact_critic_loss")
+        _call("gops_dsact_critic_loss", _ptr(qraw), _ptr(target_q), _ptr(target_q_sample), B, float(tau_b), self.state.data_ptr(),
+              _ptr(seed), self.buf.data_ptr(), _stream())
         return seed, self.buf[:11]
 
 
@@ -1754,9 +1743,8 @@ class SoftQBackup(_SoftBackupBase):
         d.gamma, d.alpha = float(gamma), float(alpha)
         res = self._outputs(out, ("backup",) + tuple(want),
                             dict(backup=(B,), a2=(B, self.act_dim), logp=(B,), q_targ=(B, 2) if self.distri else (self.n_q, B)))
-        check(lib().gops_soft_q_backup(C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["backup"]),
-                                       _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")), self.workspace.data_ptr(),
-                                       self._workspace_bytes, _stream()), "gops_soft_q_backup")
+        _call("gops_soft_q_backup", C.byref(d), B, _ptr(obs2), _ptr(rew), _ptr(done), _ptr(eps_next), _ptr(z_next), _ptr(res["backup"]),
+              _ptr(res.get("a2")), _ptr(res.get("logp")), _ptr(res.get("q_targ")), *_ws(self))
         return res
 
 
@@ -1772,8 +1760,7 @@ class DsacCriticLoss:
         B = qraw.shape[0]
         assert tuple(qraw.shape) == (B, 2)
         seed = torch.empty_like(qraw) if seed is None else seed
-        check(lib().gops_dsac_critic_loss(_ptr(qraw), _ptr(target_q), B, int(bool(bound)), _ptr(seed), self.buf.data_ptr(), _stream()),
-              "gops_dsac_critic_loss")
+        _call("gops_dsac_critic_loss", _ptr(qraw), _ptr(target_q), B, int(bool(bound)), _ptr(seed), self.buf.data_ptr(), _stream())
         return seed, self.buf[:4]
 
 
@@ -1794,15 +1781,14 @@ class TanhGaussHead:
         B = head.shape[0]
         act = torch.empty(B, self.act_dim, dtype=torch.float32, device=head.device) if act is None else act
         logp = torch.empty(B, dtype=torch.float32, device=head.device) if logp is None else logp
-        check(lib().gops_tanh_gauss_forward(C.byref(self.desc), B, _ptr(head), _ptr(eps), float(target_entropy), _ptr(act), _ptr(logp),
-                                            self.buf.data_ptr(), _stream()), "gops_tanh_gauss_forward")
+        _call("gops_tanh_gauss_forward", C.byref(self.desc), B, _ptr(head), _ptr(eps), float(target_entropy), _ptr(act), _ptr(logp),
+              self.buf.data_ptr(), _stream())
         return act, logp, self.buf[:4]
 
     def backward(self, head, eps, g_act, g_logp, g_head=None):
         B = head.shape[0]
         g_head = torch.empty_like(head) if g_head is None else g_head
-        check(lib().gops_tanh_gauss_backward(C.byref(self.desc), B, _ptr(head), _ptr(eps), _ptr(g_act), _ptr(g_logp), _ptr(g_head),
-                                             _stream()), "gops_tanh_gauss_backward")
+        _call("gops_tanh_gauss_backward", C.byref(self.desc), B, _ptr(head), _ptr(eps), _ptr(g_act), _ptr(g_logp), _ptr(g_head), _stream())
         return g_head
 
 
@@ -1840,9 +1826,8 @@ class PpoLoss:
         seed_head = torch.empty_like(head_new) if seed_head is None else seed_head
         seed_v = torch.empty(M, dtype=torch.float32, device=head_new.device) if seed_v is None else seed_v
         assert seed_head.numel() == 2 * M * A and seed_v.numel() == M
-        check(lib().gops_ppo_loss(C.byref(self.desc), M, _ptr(head_new), _ptr(v_new), _ptr(act), _ptr(logp_old), _ptr(adv), _ptr(ret),
-                                  _ptr(val_old), _ptr(logits_old), self.hyper.data_ptr(), _ptr(seed_head), _ptr(seed_v),
-                                  self.buf.data_ptr(), _stream()), "gops_ppo_loss")
+        _call("gops_ppo_loss", C.byref(self.desc), M, _ptr(head_new), _ptr(v_new), _ptr(act), _ptr(logp_old), _ptr(adv), _ptr(ret),
+              _ptr(val_old), _ptr(logits_old), self.hyper.data_ptr(), _ptr(seed_head), _ptr(seed_v), self.buf.data_ptr(), _stream())
         return seed_head, seed_v, self.buf[:6]
 
 
@@ -1855,7 +1840,7 @@ class AdvNormalize:
     def run(self, adv: torch.Tensor, eps: float = 1e-8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         out = torch.empty_like(adv) if out is None else out
         assert out.numel() == adv.numel()
-        check(lib().gops_adv_normalize(_ptr(adv), adv.numel(), float(eps), _ptr(out), self.buf.data_ptr(), _stream()), "gops_adv_normalize")
+        _call("gops_adv_normalize", _ptr(adv), adv.numel(), float(eps), _ptr(out), self.buf.data_ptr(), _stream())
         return out
 
 
@@ -1867,8 +1852,8 @@ def gae(rew, val, val_next, done, end, gamma: float = 0.99, gae_lambda: float = 
     ret = torch.empty_like(rew) if ret is None else ret
     adv = torch.empty_like(rew) if adv is None else adv
     assert ret.numel() == T * N and adv.numel() == T * N
-    check(lib().gops_gae(_ptr(rew), _ptr(val), _ptr(val_next), _ptr(done), _ptr(end), T, N, float(gamma), float(gae_lambda), _ptr(ret),
-                         _ptr(adv), _stream()), "gops_gae")
+    _call("gops_gae", _ptr(rew), _ptr(val), _ptr(val_next), _ptr(done), _ptr(end), T, N, float(gamma), float(gae_lambda), _ptr(ret),
+          _ptr(adv), _stream())
     return ret, adv
 
 
@@ -1916,8 +1901,8 @@ class FisherSeed:
         return seed
 
     def _launch(self, t: GopsMlpGrad, B: int, x, seed):
-        check(lib().gops_gauss_fisher_seed(C.byref(self.mlp), C.byref(t), B, _ptr(x), self.min_log_std, self.max_log_std, _ptr(seed),
-                                           _stream()), "gops_gauss_fisher_seed")
+        _call("gops_gauss_fisher_seed", C.byref(self.mlp), C.byref(t), B, _ptr(x), self.min_log_std, self.max_log_std, _ptr(seed),
+              _stream())
 
 
 class CatFisherSeed(FisherSeed):
@@ -1929,7 +1914,7 @@ class CatFisherSeed(FisherSeed):
         self.out_dim = int(mlp.sizes[mlp.n_layers])
 
     def _launch(self, t: GopsMlpGrad, B: int, x, seed):
-        check(lib().gops_cat_fisher_seed(C.byref(self.mlp), C.byref(t), B, _ptr(x), _ptr(seed), _stream()), "gops_cat_fisher_seed")
+        _call("gops_cat_fisher_seed", C.byref(self.mlp), C.byref(t), B, _ptr(x), _ptr(seed), _stream())
 
 
 class _SurrogateState:
@@ -1969,9 +1954,8 @@ class TrpoSurrogate(_SurrogateState):
         if want_seed and seed_head is None:
             seed_head = torch.empty_like(head_new)
         assert seed_head is None or seed_head.numel() == 2 * M * A
-        check(lib().gops_trpo_surrogate(A, M, self.min_log_std, self.max_log_std, _ptr(head_new), _ptr(head_old), _ptr(act), _ptr(adv),
-                                        self.hyper.data_ptr(), _ptr(seed_head) if want_seed else None, self.buf.data_ptr(), _stream()),
-              "gops_trpo_surrogate")
+        _call("gops_trpo_surrogate", A, M, self.min_log_std, self.max_log_std, _ptr(head_new), _ptr(head_old), _ptr(act), _ptr(adv),
+              self.hyper.data_ptr(), _ptr(seed_head) if want_seed else None, self.buf.data_ptr(), _stream())
         return (seed_head if want_seed else None), self.buf[:2]
 
 
@@ -1993,9 +1977,8 @@ class CatTrpoSurrogate(_SurrogateState):
         if want_seed and seed_head is None:
             seed_head = torch.empty_like(head_new)
         assert seed_head is None or seed_head.numel() == M * N
-        check(lib().gops_cat_trpo_surrogate(N, M, _ptr(head_new), _ptr(head_old), _ptr(act), _ptr(adv), self.hyper.data_ptr(),
-                                            _ptr(seed_head) if want_seed else None, self.buf.data_ptr(), _stream()),
-              "gops_cat_trpo_surrogate")
+        _call("gops_cat_trpo_surrogate", N, M, _ptr(head_new), _ptr(head_old), _ptr(act), _ptr(adv), self.hyper.data_ptr(),
+              _ptr(seed_head) if want_seed else None, self.buf.data_ptr(), _stream())
         return (seed_head if want_seed else None), self.buf[:2]
 
 
@@ -2012,16 +1995,16 @@ class CgSolver:
         self.hyper = torch.zeros(TRPO_HYPER_FLOATS, dtype=torch.float32, device=device) if hyper is None else hyper
 
     def init(self, atol: float):
-        check(lib().gops_cg_init(_ptr(self.g), _ptr(self.x), _ptr(self.r), _ptr(self.p), self.n, float(atol), self._state.data_ptr(),
-                                 _stream()), "gops_cg_init")
+        _call("gops_cg_init", _ptr(self.g), _ptr(self.x), _ptr(self.r), _ptr(self.p), self.n, float(atol), self._state.data_ptr(),
+              _stream())
 
     def step(self, damping: float, atol: float):
-        check(lib().gops_cg_step(_ptr(self.p), _ptr(self.Ap), _ptr(self.x), _ptr(self.r), self.n, float(damping), float(atol),
-                                 self._state.data_ptr(), _stream()), "gops_cg_step")
+        _call("gops_cg_step", _ptr(self.p), _ptr(self.Ap), _ptr(self.x), _ptr(self.r), self.n, float(damping), float(atol),
+              self._state.data_ptr(), _stream())
 
     def finish(self):
-        check(lib().gops_cg_finish(_ptr(self.g), _ptr(self.x), _ptr(self.step_vec), self.n, self.hyper.data_ptr(), self._state.data_ptr(),
-                                   _stream()), "gops_cg_finish")
+        _call("gops_cg_finish", _ptr(self.g), _ptr(self.x), _ptr(self.step_vec), self.n, self.hyper.data_ptr(), self._state.data_ptr(),
+              _stream())
 
     def state(self) -> Dict[str, float]:
         """The state block's fields on the host (one synchronisation)."""
@@ -2112,16 +2095,16 @@ class MpcSolver:
         at the trial point (gops_mpc_al_eval): call between the rollout forward and its backward, then `step`."""
         H, nc = self._al_dims()
         assert c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == (H, self.batch, nc)
-        check(lib().gops_mpc_al_eval(self.batch, H, nc, _ptr(c), _ptr(self.lam), _ptr(self.rho), _ptr(self.f_al_in), _ptr(self.f),
-                                     _ptr(self.seed), _ptr(self.viol), _stream()), "gops_mpc_al_eval")
+        _call("gops_mpc_al_eval", self.batch, H, nc, _ptr(c), _ptr(self.lam), _ptr(self.rho), _ptr(self.f_al_in), _ptr(self.f),
+              _ptr(self.seed), _ptr(self.viol), _stream())
 
     def al_update(self, c: torch.Tensor):
         """The outer step (gops_mpc_al_update) with c [H, batch, n_c] and `viol` those of the rows' ACCEPTED points: rows whose inner
         solve has ended get their multipliers and rho updated and are re-armed, converged or out of outer iterations."""
         H, nc = self._al_dims()
         assert c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == (H, self.batch, nc)
-        check(lib().gops_mpc_al_update(*self._args(), H, nc, _ptr(c), _ptr(self.lam), _ptr(self.rho), _ptr(self.viol), _ptr(self.viol_prev),
-                                       self.outer.data_ptr(), _ptr(self.al_hyper), _stream()), "gops_mpc_al_update")
+        _call("gops_mpc_al_update", *self._args(), H, nc, _ptr(c), _ptr(self.lam), _ptr(self.rho), _ptr(self.viol), _ptr(self.viol_prev),
+              self.outer.data_ptr(), _ptr(self.al_hyper), _stream())
 
     def al_advance(self, frozen: torch.Tensor, action_out: torch.Tensor, record: torch.Tensor, shift: int = 1):
         """`advance` plus the multipliers' hand-over (gops_mpc_al_advance): shifted by `shift` env steps (one control interval) with
@@ -2129,9 +2112,9 @@ class MpcSolver:
         H, nc = self._al_dims()
         assert frozen.dtype == torch.float32 and frozen.numel() == self.batch and record.dtype == torch.int32 and record.numel() == 4 * self.batch
         assert action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.numel() % self.batch == 0
-        check(lib().gops_mpc_al_advance(*self._args(), action_out.numel() // self.batch, _ptr(frozen), _ptr(action_out), record.data_ptr(),
-                                        _ptr(self.x_trial), H, nc, int(shift), _ptr(self.lam), _ptr(self._lam_next), _ptr(self.rho),
-                                        _ptr(self.viol_prev), self.outer.data_ptr(), _ptr(self.al_hyper), _stream()), "gops_mpc_al_advance")
+        _call("gops_mpc_al_advance", *self._args(), action_out.numel() // self.batch, _ptr(frozen), _ptr(action_out), record.data_ptr(),
+              _ptr(self.x_trial), H, nc, int(shift), _ptr(self.lam), _ptr(self._lam_next), _ptr(self.rho), _ptr(self.viol_prev),
+              self.outer.data_ptr(), _ptr(self.al_hyper), _stream())
         self.lam, self._lam_next = self._lam_next, self.lam
 
     def set_hyper(self, **kw):
@@ -2147,18 +2130,17 @@ class MpcSolver:
         return self._state.data_ptr(), self.state_bytes, self.batch, self.n, self.m
 
     def init(self, x0: torch.Tensor):
-        check(lib().gops_mpc_init(*self._args(), _ptr(x0), _ptr(self.lo), _ptr(self.hi), _ptr(self.x_trial), _stream()), "gops_mpc_init")
+        _call("gops_mpc_init", *self._args(), _ptr(x0), _ptr(self.lo), _ptr(self.hi), _ptr(self.x_trial), _stream())
 
     def step(self):
-        check(lib().gops_mpc_step(*self._args(), _ptr(self.f), _ptr(self.g), _ptr(self.x_trial), _ptr(self.hyper), _stream()),
-              "gops_mpc_step")
+        _call("gops_mpc_step", *self._args(), _ptr(self.f), _ptr(self.g), _ptr(self.x_trial), _ptr(self.hyper), _stream())
 
     def finish(self):
         """-> (x [batch, n], f [batch], status [batch] int32, iterations [batch] int32): the accepted points, on the device; with
         `constraints` additionally (viol [batch], outer status [batch] int32 (MPC_AL_*), outer iterations [batch] int32) - the
         violation of the last `al_eval`, views of `outer`."""
-        check(lib().gops_mpc_finish(*self._args(), _ptr(self.x), _ptr(self.f_best), self.status.data_ptr(), self.iterations.data_ptr(),
-                                    _stream()), "gops_mpc_finish")
+        _call("gops_mpc_finish", *self._args(), _ptr(self.x), _ptr(self.f_best), self.status.data_ptr(), self.iterations.data_ptr(),
+              _stream())
         if self.constraints is not None:
             return self.x, self.f_best, self.status, self.iterations, self.viol, self.outer[:, 0], self.outer[:, 1]
         return self.x, self.f_best, self.status, self.iterations
@@ -2170,8 +2152,8 @@ class MpcSolver:
         ready for the next evaluation; `record` [batch, 4] int32: last status, summed iterations, summed evaluations, solves."""
         assert frozen.dtype == torch.float32 and frozen.numel() == self.batch and record.dtype == torch.int32 and record.numel() == 4 * self.batch
         assert action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.numel() % self.batch == 0
-        check(lib().gops_mpc_advance(*self._args(), action_out.numel() // self.batch, _ptr(frozen), _ptr(action_out), record.data_ptr(),
-                                     _ptr(self.x_trial), _stream()), "gops_mpc_advance")
+        _call("gops_mpc_advance", *self._args(), action_out.numel() // self.batch, _ptr(frozen), _ptr(action_out), record.data_ptr(),
+              _ptr(self.x_trial), _stream())
 
     def status_words(self) -> torch.Tensor:
         """The status words of the state block as a strided int32 view [batch] (device; written by element-wise torch operations)."""
@@ -2237,8 +2219,7 @@ class PolyakUpdater:
             t.n = len(chunk)
             for i, (a, b) in enumerate(chunk):
                 assert a.shape == b.shape
-                t.numel[i] = a.numel()
-                t.param[i], t.grad[i] = _ptr(a.data), _ptr(b.data)
+                _adam_entry(t, i, a.data, b.data)
             self.tables.append(t)
 
     def matches(self, target_params, online_params) -> bool:
@@ -2246,7 +2227,7 @@ class PolyakUpdater:
 
     def step(self, tau: float):
         for t in self.tables:
-            check(lib().gops_polyak_update(C.byref(t), float(tau), _stream()), "gops_polyak_update")
+            _call("gops_polyak_update", C.byref(t), float(tau), _stream())
 
 
 def profile_enable(on: bool):
@@ -2259,5 +2240,5 @@ def profile_reset():
 
 def profile_read(kernel_id: int):
     ms, n = C.c_double(0.0), C.c_int64(0)
-    check(lib().gops_profile_read(kernel_id, C.byref(ms), C.byref(n)), "gops_profile_read")
+    _call("gops_profile_read", kernel_id, C.byref(ms), C.byref(n))
     return ms.value, n.value

@@ -24,7 +24,6 @@ default they run the per-step loop (`path` = "loop: stochastic policy"); `stocha
 `gops_episode_rollout_mode`: the 2A-wide stack's mean half, clamped to the policy's limits (GaussDistribution) or tanh-squashed into
 them (TanhGaussDistribution).  Any other distribution class, or a log std outside the shared stack, stays on the loop.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -139,13 +138,10 @@ class Evaluator(ClosedLoopDriver):
         env = self._hip_env()
         if env.kind == hb.ENV_MOBILEROBOT:
             return "pyth_mobilerobot draws its obstacle noise per step"
-        if self.action_table is not None:
-            if hb.lib().gops_episode_dis_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), int(self.action_table.shape[0]), 1, 1) == 0:
+        rows = None if self.action_table is None else int(self.action_table.shape[0])
+        if hb.EpisodeRollout.workspace_bytes(env, pol.hip_mlp(), episodes=1, max_steps=1, action_table_rows=rows, mode_head=head) == 0:
+            if rows is not None:
                 return "env / policy description outside the episode kernel (more than GOPS_DQN_MAX_ACTIONS actions, hidden widths)"
-            return None
-        nbytes = hb.lib().gops_episode_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), 1, 1) if head is None else \
-            hb.lib().gops_episode_mode_workspace_bytes(ctypes.byref(env), ctypes.byref(pol.hip_mlp()), head, 1, 1)
-        if nbytes == 0:
             # gops_hip.h lists them: ScaleObservation on the vehicle families or beyond 8 observations, ActionRepeat, hidden widths
             # that are no multiple of 16 or beyond the LDS plan (~1100)
             return "env / policy description outside the episode kernel (scaled vehicle observations, hidden widths)"

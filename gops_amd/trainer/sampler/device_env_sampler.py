@@ -21,7 +21,6 @@ keys) for `ReplayBuffer.add_tensors`; nothing crosses PCIe in steady state.  Res
 data envs' reset distributions (`gops_amd.utils.synthetic.make_batch`), generated on the host in pools of
 `pool_factor x n_envs` and uploaded once per pool.
 """
-import ctypes
 import time
 import warnings
 
@@ -190,13 +189,12 @@ class DeviceEnvSampler(ClosedLoopDriver):
         env = self._hip_env()
         if env.kind == hb.ENV_MOBILEROBOT:
             return "pyth_mobilerobot draws its obstacle noise per step"
-        if self.action_table is not None:
-            if hb.lib().gops_sample_dis_workspace_bytes(ctypes.byref(env), ctypes.byref(policy.hip_mlp()), int(self.action_table.shape[0]),
-                                                        self.n, self.steps) == 0:
+        rows = None if self.action_table is None else int(self.action_table.shape[0])
+        if hb.SampleRollout.workspace_bytes(env, policy.hip_mlp(), n_envs=self.n, steps=self.steps, action_table_rows=rows) == 0:
+            if rows is not None:
                 # gops_hip.h lists them; gym_cartpoleconti with env_step="model" is one: the kernel steps it as a data env only
                 return ("action table: env / policy description outside the sample kernel (an env the kernel steps under the other "
                         "env_step only, constrained model, ActionRepeat, hidden widths, more than GOPS_DQN_MAX_ACTIONS actions)")
-        elif hb.lib().gops_sample_workspace_bytes(ctypes.byref(env), ctypes.byref(policy.hip_mlp()), self.n, self.steps) == 0:
             # gops_hip.h lists them: the constrained vehicle models, ActionRepeat, scaled vehicle observations, hidden widths that are
             # no multiple of 16 or beyond the LDS plan, more than GOPS_MAX_ACT actions
             return "env / policy description outside the sample kernel (constrained model, ActionRepeat, hidden widths)"

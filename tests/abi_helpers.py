@@ -1,5 +1,5 @@
-"""The C side of the ABI tests: the one layout probe that holds ctypes mirrors to include/gops_hip.h, and what every `test_abi_of_*`
-asks of its entry points."""
+"""The C side of the ABI tests: the layout probe and the constants probe that hold hip_backend's ctypes mirrors and integer constants
+to include/gops_hip.h, and what every `test_abi_of_*` asks of its entry points."""
 import ctypes
 import os
 import re
@@ -33,15 +33,37 @@ def layout_probe(tmp_path, structs, c_names=None):
     assert not differ, differ   # (what, the header's value, the mirror's)
 
 
-def check_abi(tmp_path, structs, entry_points, stats):
+def header_constants():
+    """The names of every GOPS_* integer constant include/gops_hip.h defines: the object-like macros that have a value, and the
+    enumerators of its (anonymous) enums."""
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, "gops_hip.h")).read(), flags=re.S)
+    names = re.findall(r"^#define (GOPS_\w+)[ \t]+\S", header, re.M)
+    for body in re.findall(r"\benum\s*\{(.*?)\}", header, re.S):
+        names += re.findall(r"\b(GOPS_\w+)\s*(?:=|,|$)", body.strip())
+    assert len(names) == len(set(names))
+    return set(names)
+
+
+def constants_probe(tmp_path, pairs):
+    """The same for constants: one C99 program against the header prints each macro or enumerator of `pairs` - (C name,
+    hip_backend's value) - as an integer; a mirror that went stale fails here with its name and both values."""
+    lines = [f'    printf(" %lld", (long long)({name}));\n' for name, _ in pairs]
+    src, exe = tmp_path / "constants.c", tmp_path / "constants"
+    src.write_text('#include <stdio.h>\n#include "gops_hip.h"\nint main(void) {\n' + "".join(lines) + "    return 0;\n}\n")
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", INCLUDE, str(src), "-o", str(exe)], check=True)
+    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert len(got) == len(pairs)
+    differ = [(name, g, w) for (name, w), g in zip(pairs, got) if g != w]
+    assert not differ, differ   # (macro, the header's value, the mirror's)
+
+
+def check_abi(tmp_path, structs, entry_points):
     """The entry points are declared in the header (plain C99), exported by the library and listed by hip_backend; the version stays
-    15; `stats`: (macro, hip_backend's value); `structs`: as `layout_probe` takes them."""
+    15; `structs`: as `layout_probe` takes them.  (The constants a family mirrors: test_host_cpu's one `constants_probe`.)"""
     from gops_amd import hip_backend as hb
     header = open(os.path.join(INCLUDE, "gops_hip.h")).read()
     assert "#define GOPS_HIP_ABI_VERSION 15" in header
     for name in entry_points:
         assert re.search(rf"\b{name}\s*\(", header) and name in hb.EXPORTED_SYMBOLS
         assert hasattr(ctypes.CDLL(hb.LIB_PATH), name)
-    for macro, value in stats:
-        assert int(re.search(rf"#define {macro} (\d+)", header).group(1)) == value
     layout_probe(tmp_path, structs)

@@ -75,6 +75,35 @@ def test_ctypes_mirror_matches_the_header_layout(tmp_path):
     layout_probe(tmp_path, list(mirrors.items()) + list(no_mirror.items()), c_names={"lam": "lambda"})   # (`lambda`: a Python keyword)
 
 
+def test_integer_constants_match_the_header(tmp_path):
+    """`gops_amd/hip_backend.py` restates the header's integer macros and enumerators by hand too.  Every GOPS_* constant the header
+    defines is mirrored - under its own name less the prefix, under the name `renamed` gives, or as an entry of ACT_IDS / DTYPE_IDS /
+    POLY_FULL / `_ERR` - or is listed in `not_mirrored`; one C program (abi_helpers.constants_probe) then holds every mirror to the
+    header's value: a stale one would still run and silently pass garbage."""
+    from abi_helpers import constants_probe, header_constants
+    from gops_amd import hip_backend as hb
+    not_mirrored = {"GOPS_HIP_ABI_VERSION",   # read from the library: gops_hip_version()
+                    "GOPS_OK",                # check(): rc != 0
+                    "GOPS_MAX_HORIZON",       # the library's own refusal
+                    "GOPS_VF_ALL",            # test_retired_variant_bits_are_rejected sums it up from its bits
+                    "GOPS_VARIANT_SPLIT", "GOPS_VARIANT_STATIONARY_F32", "GOPS_VARIANT_STREAMED_SPLIT_FWD", "GOPS_VARIANT_HALF_TILE64"}
+    renamed = {"GOPS_MAX_LQ_STATE": "MAX_LQ", "GOPS_ADAM_MAX_TENSORS": "ADAM_MAX", "GOPS_ENV_IDPENDULUM": "ENV_IDP",
+               "GOPS_ENV_VEH3DOFCONTI": "ENV_VEH", "GOPS_ENV_VEH3DOF_SURR": "ENV_VEH_SURR"}
+    pairs = {"GOPS_ACT_" + name.upper(): code for name, code in hb.ACT_IDS.items()}
+    pairs.update({f"GOPS_POLY_FULL_{degree}": code for degree, code in hb.POLY_FULL.items()})
+    pairs.update({name: code for code, name in hb._ERR.items()})
+    pairs.update(GOPS_DTYPE_F32=hb.DTYPE_IDS["fp32"], GOPS_DTYPE_F16=hb.DTYPE_IDS["fp16"])
+    assert all(hb.DTYPE_IDS[k] == hb.DTYPE_IDS["fp32"] for k in ("f32", "float32"))
+    assert all(hb.DTYPE_IDS[k] == hb.DTYPE_IDS["fp16"] for k in ("f16", "float16", "half")) and len(hb.DTYPE_IDS) == 7
+    declared = header_constants()
+    for name in sorted(declared - set(pairs) - not_mirrored):
+        value = getattr(hb, renamed.get(name, name[len("GOPS_"):]), None)
+        assert type(value) is int, f"{name} of the header is neither mirrored by hip_backend nor listed as not mirrored"
+        pairs[name] = value
+    assert set(pairs) == declared - not_mirrored and not_mirrored <= declared and set(renamed) <= declared and len(pairs) >= 120
+    constants_probe(tmp_path, sorted(pairs.items()))
+
+
 def test_integration_md_stub_matches_the_current_abi():
     """INTEGRATION.md section 2 shows the ctypes stub a GOPS maintainer would add: its `GopsMlp` must be the layout of the
     CURRENT header (v10 put `variant_flags` where v9 had padding - a stale copy would still run and silently pass garbage)."""

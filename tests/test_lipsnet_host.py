@@ -191,5 +191,5 @@ def test_lips_entry_points_and_ctypes_mirrors(tmp_path):
     """The three entry points are additive (the ABI version stays 15) and the two ctypes mirrors have the header's layout."""
     from abi_helpers import check_abi, layout_probe
     from gops_amd import hip_backend as hb
-    check_abi(tmp_path, [], ("gops_lips_workspace_bytes", "gops_lips_forward", "gops_lips_backward"), [])
+    check_abi(tmp_path, [], ("gops_lips_workspace_bytes", "gops_lips_forward", "gops_lips_backward"))
     layout_probe(tmp_path, [("GopsLipsNet", hb.GopsLipsNet), ("GopsLipsGrad", hb.GopsLipsGrad)], c_names={"lam": "lambda"})

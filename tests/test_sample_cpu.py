@@ -13,9 +13,7 @@ def test_abi_of_the_sample_entry_points(tmp_path):
     from gops_amd import hip_backend as hb
     check_abi(tmp_path, [("GopsSampleDesc", hb.GopsSampleDesc), ("GopsSampleState", hb.GopsSampleState),
                          ("GopsSamplePool", hb.GopsSamplePool), ("GopsSampleOut", hb.GopsSampleOut)],
-              ("gops_sample_workspace_bytes", "gops_sample_rollout"),
-              [("GOPS_SAMPLE_DETERM", hb.SAMPLE_DETERM), ("GOPS_SAMPLE_GAUSS", hb.SAMPLE_GAUSS),
-               ("GOPS_SAMPLE_TANH_GAUSS", hb.SAMPLE_TANH_GAUSS), ("GOPS_SAMPLE_WORKSPACE_BYTES", hb.SAMPLE_WORKSPACE_BYTES)])
+              ("gops_sample_workspace_bytes", "gops_sample_rollout"))
     assert [f[0] for f in hb.GopsSampleDesc._fields_] == ["head", "max_episode_steps", "pool_rows", "reserved", "noise_std", "min_log_std",
                                                           "max_log_std"]
     assert [f[0] for f in hb.GopsSampleOut._fields_][:8] == ["obs", "act", "rew", "done", "obs2", "logp", "time_limited", "end"]

@@ -19,9 +19,7 @@ from gops_amd.trainer.sampler.reset_pool import HEAD_CATEGORICAL, HEAD_EPS_GREED
 def test_abi_of_the_discrete_entry_points(tmp_path):
     check_abi(tmp_path, [("GopsSampleDis", hb.GopsSampleDis), ("GopsSampleDesc", hb.GopsSampleDesc), ("GopsSampleOut", hb.GopsSampleOut),
                          ("GopsEpisodeOut", hb.GopsEpisodeOut)],
-              ("gops_sample_dis_workspace_bytes", "gops_sample_rollout_dis", "gops_episode_dis_workspace_bytes", "gops_episode_rollout_dis"),
-              [("GOPS_SAMPLE_EPS_GREEDY", hb.SAMPLE_EPS_GREEDY), ("GOPS_SAMPLE_CATEGORICAL", hb.SAMPLE_CATEGORICAL),
-               ("GOPS_SAMPLE_TANH_GAUSS", hb.SAMPLE_TANH_GAUSS), ("GOPS_DQN_MAX_ACTIONS", hb.DQN_MAX_ACTIONS)])
+              ("gops_sample_dis_workspace_bytes", "gops_sample_rollout_dis", "gops_episode_dis_workspace_bytes", "gops_episode_rollout_dis"))
     assert [f[0] for f in hb.GopsSampleDis._fields_] == ["action_table", "act_num", "head", "epsilon", "env_act"]
     assert hb.SAMPLE_EPS_GREEDY > hb.SAMPLE_TANH_GAUSS and hb.SAMPLE_CATEGORICAL > hb.SAMPLE_TANH_GAUSS   # gops_sample_rollout refuses both
     assert (HEAD_EPS_GREEDY, HEAD_CATEGORICAL) == (hb.SAMPLE_EPS_GREEDY, hb.SAMPLE_CATEGORICAL)
