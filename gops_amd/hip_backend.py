@@ -221,6 +221,17 @@ class GopsPpoLoss(C.Structure):   # gops_ppo_loss
                 ("min_log_std", C.c_double), ("max_log_std", C.c_double)]
 
 
+PER_MAX_KEYS, PER_MAX_BATCH = 22, 8192   # include/gops_hip.h: GOPS_PER_MAX_KEYS / GOPS_PER_MAX_BATCH
+
+
+class GopsPerKey(C.Structure):   # gops_per_sample: one key of the gather table
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GopsPerGather(C.Structure):
+    _fields_ = [("n_keys", C.c_int32), ("reserved", C.c_int32), ("key", GopsPerKey * PER_MAX_KEYS)]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every symbol of include/gops_hip.h (argtypes None: not declared to ctypes)."""
     P, vp, i32, sz, f64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_size_t, C.c_double, C.c_int
@@ -312,6 +323,9 @@ def _signatures():
         "gops_dqn_backup_workspace_bytes": (sz, [P(GopsDqnBackup), i32]),
         "gops_dqn_backup": (rc, [P(GopsDqnBackup), i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "gops_dqn_loss": (rc, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "gops_per_sample": (rc, [vp, vp, i32, i32, f64, vp, i32, P(GopsPerGather), vp, vp, vp]),
+        "gops_per_update": (rc, [vp, vp, vp, i32, vp, vp, i32, i32, f64, f64, vp]),
+        "gops_per_fill": (rc, [vp, vp, vp, i32, i32, i32, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -1221,6 +1235,52 @@ class SampleRollout:
         _call(self._name, C.byref(self.env), C.byref(self.policy), C.byref(self.desc), *self._extra, N, T, C.byref(st), C.byref(pl),
               _ptr(noise), C.byref(self._out), *_ws(self))
         return self.out
+
+
+class PerBuffer:
+    """The prioritized replay buffer's three operations in one launch each (csrc/per_buffer.hip) on the buffer's OWN tensors: the
+    float64 sum / min trees of 2 N - 1 nodes, the device scalar `max_priority` (updated in place) and `storage`, the [N, ...] fp32
+    ring buffers by key.  The gather table is built once: the buffers never move."""
+
+    def __init__(self, sum_tree: torch.Tensor, min_tree: torch.Tensor, max_priority: torch.Tensor, storage: Dict[str, torch.Tensor]):
+        for t in (sum_tree, min_tree, max_priority):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous(), "need contiguous float64 device tensors"
+        assert sum_tree.numel() == min_tree.numel() and sum_tree.numel() % 2 == 1 and max_priority.numel() == 1
+        if len(storage) > PER_MAX_KEYS:
+            raise RuntimeError(f"gops_per_sample gathers at most {PER_MAX_KEYS} keys, the buffer has {len(storage)}")
+        self.sum_tree, self.min_tree, self.max_priority, self.storage = sum_tree, min_tree, max_priority, dict(storage)
+        self.capacity = (sum_tree.numel() + 1) // 2
+        self.gather = GopsPerGather(n_keys=len(storage))
+        for key, (name, t) in zip(self.gather.key, storage.items()):
+            assert t.shape[0] == self.capacity, name
+            key.width = t[0].numel()
+            key.src = _ptr(t) if key.width else None
+        self._trees = (sum_tree.data_ptr(), min_tree.data_ptr())
+
+    def fill(self, ptr: int, n: int):
+        """The leaves of the ring range [ptr, ptr + n) mod N take `max_priority`; their ancestors are recomputed."""
+        _call("gops_per_fill", *self._trees, self.max_priority.data_ptr(), self.capacity, int(ptr), int(n), _stream())
+
+    def sample(self, u: torch.Tensor, size: int, beta: float) -> Dict[str, torch.Tensor]:
+        """u [B]: float64 unit draws -> the batch: every key's rows, "idx" (int32 tree indices) and "weight" (fp32)."""
+        assert u.is_cuda and u.dtype == torch.float64 and u.is_contiguous() and u.dim() == 1
+        B, dev = u.numel(), u.device
+        batch = {k: torch.empty((B,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for k, t in self.storage.items()}
+        for key, t in zip(self.gather.key, batch.values()):
+            key.dst = t.data_ptr() if key.width else None
+        batch["idx"] = torch.empty(B, dtype=torch.int32, device=dev)
+        batch["weight"] = torch.empty(B, dtype=torch.float32, device=dev)
+        _call("gops_per_sample", *self._trees, self.capacity, int(size), float(beta), u.data_ptr(), B, C.byref(self.gather),
+              batch["idx"].data_ptr(), batch["weight"].data_ptr(), _stream())
+        return batch
+
+    def update(self, idx: torch.Tensor, priority: torch.Tensor, alpha: float, epsilon: float):
+        """Leaf idx[t] <- (priority[t] + epsilon)^alpha, the last occurrence of an index winning; idx int32, priority fp32 or float64."""
+        assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()
+        assert priority.is_cuda and priority.dtype in (torch.float32, torch.float64) and priority.is_contiguous()
+        assert priority.numel() == idx.numel()
+        _call("gops_per_update", *self._trees, self.max_priority.data_ptr(), self.capacity, idx.data_ptr(), priority.data_ptr(),
+              int(priority.dtype == torch.float64), idx.numel(), float(alpha), float(epsilon), _stream())
 
 
 class ValueNet:

@@ -14,6 +14,9 @@ leaf of slot i at i + N - 1, children of p at 2 p + 1 / 2 p + 2) and every opera
     (deduplicated) parents of the level below - ceil(log2(N)) + 1 rounds.
 Trees are float64 like numpy's.  The tree has the reference's shape for ANY `buffer_max_size` (not only powers of two): leaves
 sit on the last two levels, so a descent stops as soon as the node it reached has no children.
+
+`buffer_fused=True` (GPU only, default False) keeps the trees, the draws and every result as they are and replaces the rounds of
+small torch kernels by one HIP launch per operation (csrc/per_buffer.hip: gops_per_fill / gops_per_sample / gops_per_update).
 """
 import math
 
@@ -34,6 +37,16 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         self.alpha, self.beta, self.beta_increment, self.epsilon = 0.6, 0.4, 0.01, 1e-6
         self.max_priority = torch.ones((), dtype=torch.float64, device=self.device)   # 1.0 ** alpha (device scalar: no sync on update)
         self._depth = int(math.ceil(math.log2(max(2 * n - 1, 2)))) + 1                # rounds that cover every root-to-leaf path
+        # buffer_fused=True: every tree operation and the row gather in ONE HIP launch each (csrc/per_buffer.hip) on the same trees;
+        # `path` names the path taken, "hip" or "torch".  The torch path below is also the CPU path.
+        self._hip = None
+        if kwargs.get("buffer_fused", False):
+            if self.device.type != "cuda":
+                raise RuntimeError(f"buffer_fused=True needs the buffer on the GPU (buffer_device is {self.device}): the fused "
+                                   "prioritized replay has no CPU path")
+            from gops_amd import hip_backend as hb
+            self._hip = hb.PerBuffer(self.sum_tree, self.min_tree, self.max_priority, self.buf)
+        self.path = "hip" if self._hip is not None else "torch"
 
     # ---- tree maintenance -----------------------------------------------------------------------------------------
     def _repair(self, tree_idx: torch.Tensor):
@@ -53,6 +66,12 @@ class PrioritizedReplayBuffer(ReplayBuffer):
             self.min_tree[nodes] = torch.minimum(self.min_tree[left], self.min_tree[right])
 
     def _rows(self, n):
+        if self._hip is not None:
+            ptr = self.ptr
+            rows = super()._rows(n)
+            if n > 0:
+                self._hip.fill(ptr, n)
+            return rows
         rows = super()._rows(n)
         tree_idx = rows + (self.max_size - 1)
         self.sum_tree[tree_idx] = self.max_priority
@@ -78,6 +97,10 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         return node, self.sum_tree[node]
 
     def sample_batch(self, batch_size: int) -> dict:
+        if self._hip is not None:   # the unit draws are an input of the kernel: both paths consume the generator identically
+            self.beta = min(1.0, self.beta + self.beta_increment)
+            u = torch.rand(batch_size, generator=self._gen, device=self.device, dtype=torch.float64)
+            return self._hip.sample(u, self.size, self.beta)
         total = self.sum_tree[0]
         segment = total / batch_size
         self.beta = min(1.0, self.beta + self.beta_increment)
@@ -95,6 +118,13 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         return batch
 
     def update_batch(self, idxes, priorities) -> None:
+        if self._hip is not None:   # device tensors go straight in; lists / numpy arrays are copied once
+            idx = torch.as_tensor(np.asarray(idxes) if not torch.is_tensor(idxes) else idxes).to(self.device, torch.int32).reshape(-1)
+            pr = torch.as_tensor(np.asarray(priorities) if not torch.is_tensor(priorities) else priorities).detach().to(self.device).reshape(-1)
+            if pr.dtype != torch.float64:
+                pr = pr.to(torch.float32)
+            self._hip.update(idx.contiguous(), pr.contiguous(), self.alpha, self.epsilon)
+            return
         idxes = torch.as_tensor(np.asarray(idxes) if not torch.is_tensor(idxes) else idxes).to(self.device).long().reshape(-1)
         pr = torch.as_tensor(np.asarray(priorities) if not torch.is_tensor(priorities) else priorities)
         pr = (pr.detach().to(self.device, torch.float64).reshape(-1) + self.epsilon) ** self.alpha

@@ -1324,6 +1324,51 @@ int gops_mpc_al_advance(void* state, size_t state_bytes, int32_t batch, int32_t 
                         float* action, int32_t* record, float* x_trial, int32_t H, int32_t n_c, int32_t shift, const float* lambda_in,
                         float* lambda_out, float* rho, float* viol_prev, int32_t* outer, const float* al_hyper, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): the prioritized replay buffer in one launch per operation
+ * (csrc/per_buffer.hip; gops/trainer/buffer/prioritized_replay_buffer.py:22-151).  sum_tree / min_tree: float64 device arrays of
+ * 2 N - 1 nodes in array layout (N = capacity; the leaf of slot i at i + N - 1, the children of p at 2 p + 1 and 2 p + 2; leaves on the
+ * last two levels; N = 1: the root alone); max_priority: one float64 in device memory.  Nothing synchronises the host.
+ *
+ * gops_per_sample: B = batch stratified samples from unit draws u [B] (float64), in float64 and operation for operation
+ *       total = sum_tree[0];  segment = total / B;  value = (i + u_i) * segment;
+ *       node = 0; while node has children: left = 2 node + 1; value <= sum_tree[left] ? node = left : (value -= sum_tree[left], node = left + 1);
+ *       idx[i] = node (int32 tree index);  p = sum_tree[node];
+ *       weight[i] = (float)( (p / total * size)^(-beta) / (min_tree[0] / total * size)^(-beta) )
+ *   and for every key k of `gather` with width > 0: dst_k[i, :] = src_k[node - (N - 1), :] (rows of `width` floats; a key of width 0
+ *   is skipped, its pointers are not read).  size, beta: the buffer's fill count and exponent, by value.
+ * gops_per_update: leaf idx[t] <- (priority[t] + epsilon)^alpha in float64 for t < B (priority: float32, or float64 when priority_f64
+ *   is nonzero; no absolute value is taken); for an index that occurs more than once the LAST occurrence wins; max_priority <-
+ *   max(max_priority, every new value, those that lost included); then every ancestor of a written leaf is recomputed from its
+ *   children, deepest level first: sum = left + right, min = minimum(left, right) (a NaN on either side stays one).  An idx[t] that is
+ *   no leaf of the tree (outside N - 1 .. 2 N - 2) writes nothing and adds nothing to max_priority.  A NaN value does not enter
+ *   max_priority (fmax).
+ * gops_per_fill: the leaves of the ring range [ptr, ptr + n) mod N <- max_priority as it stands, then every ancestor as above.
+ * Internal nodes are bit-equal to a recomputation from the final leaves in that order of operations.
+ * GOPS_ERR_BAD_ARG, nothing launched: a NULL pointer (a key's src / dst only where its width > 0), capacity < 1, batch < 1, size
+ * outside 1 .. capacity, n outside 1 .. capacity, ptr outside 0 .. capacity - 1, n_keys < 0, a negative width.
+ * GOPS_ERR_UNSUPPORTED, nothing launched: batch > GOPS_PER_MAX_BATCH, n_keys > GOPS_PER_MAX_KEYS (six base keys and twice the
+ * eight info keys of pyth_veh3dofconti_surrcstr, the largest key set of the data envs), capacity > 2^29. */
+#define GOPS_PER_MAX_KEYS 22
+#define GOPS_PER_MAX_BATCH 8192
+struct GopsPerKey {
+    const float* src;   /* [N, width]: the buffer's storage of this key */
+    float* dst;         /* [B, width]: the batch's tensor */
+    int32_t width;      /* floats per row; 0: nothing to copy */
+    int32_t reserved;
+};
+typedef struct GopsPerKey GopsPerKey;
+struct GopsPerGather {
+    int32_t n_keys;
+    int32_t reserved;
+    GopsPerKey key[GOPS_PER_MAX_KEYS];
+};
+typedef struct GopsPerGather GopsPerGather;
+int gops_per_sample(const double* sum_tree, const double* min_tree, int32_t capacity, int32_t size, double beta, const double* u,
+                    int32_t batch, const GopsPerGather* gather, int32_t* idx, float* weight, void* stream);
+int gops_per_update(double* sum_tree, double* min_tree, double* max_priority, int32_t capacity, const int32_t* idx, const void* priority,
+                    int32_t priority_f64, int32_t batch, double alpha, double epsilon, void* stream);
+int gops_per_fill(double* sum_tree, double* min_tree, const double* max_priority, int32_t capacity, int32_t ptr, int32_t n, void* stream);
+
 /* Timing hook for bench.py: average duration in ms of the named internal kernel over the
  * launches recorded since the last reset (HIP events on the launch stream).  kernel ids:
  * 0 = forward rollout, 1 = backward sweep, 2 = weight-gradient GEMMs (+ reduce) of gops_rollout_*;
