@@ -1,11 +1,13 @@
-"""What PPO and TRPO share on the HIP kernels: a Gaussian `mlp_shared` StochaPolicy (for TRPO also a categorical StochaPolicyDis) and
-a StateValue in one container, the refusal `create_alg` states for anything else, the per-object caches of kernel objects and
-buffers, and the captured Adam step.
+"""What PPO and TRPO share on the HIP kernels: a Gaussian `mlp_shared` StochaPolicy (for TRPO also a categorical StochaPolicyDis; for PPO
+also the recurrent pair of gops_amd/apprfunc/rnn.py) and a StateValue in one container, the refusal `create_alg` states for anything
+else, the per-object caches of kernel objects and buffers, and the captured Adam step.
 """
+import numpy as np
 import torch
 
 from gops_amd import hip_backend as hb
-from gops_amd.algorithm.base import AlgorithmBase, ApprBase
+from gops_amd.algorithm.base import AlgorithmBase, ApprBase, _flat_grads, grad_buffers
+from gops_amd.apprfunc import rnn
 from gops_amd.apprfunc.mlp import StateValue, StochaPolicy, StochaPolicyDis
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
 from gops_amd.utils.act_distribution import CategoricalDistribution, GaussDistribution
@@ -29,11 +31,39 @@ def categorical_refusal(alg: str, kwargs: dict):
     return None
 
 
-def refusal(alg: str, density_words: str, kwargs: dict, categorical: bool = False):
+def rnn_refusal(alg: str, kwargs: dict):
+    """Why `create_alg` cannot build `alg` on the recurrent kernels (`gops_rnn_forward / _backward`) from these arguments, or None."""
+    types = (kwargs.get("policy_func_type"), kwargs.get("value_func_type"))
+    if types != ("RNN", "RNN"):
+        return (f"{alg} takes RNN networks as a pair, both or neither (policy_func_type {types[0]!r}, value_func_type {types[1]!r}): the policy "
+                "and the value read the same columns, and a stack of observations [S, L, O] is no input of an MLP")
+    shape = kwargs.get("obsv_dim")
+    if not (isinstance(shape, (tuple, list)) and len(shape) == 2 and all(isinstance(v, (int, np.integer)) for v in shape)):
+        return f"{alg} with RNN networks takes obsv_dim as the pair (L, O) of a stack of L observations, not {shape!r}"
+    if not 1 <= shape[0] <= hb.RNN_MAX_SEQ or not 1 <= shape[1] <= hb.RNN_MAX_OBS:
+        return (f"{alg} with RNN networks: obsv_dim {tuple(shape)!r} is outside the recurrent kernels' range (L in 1 .. {hb.RNN_MAX_SEQ}, "
+                f"O in 1 .. {hb.RNN_MAX_OBS})")
+    A = kwargs.get("action_dim")
+    if not isinstance(A, (int, np.integer)) or not 1 <= A <= hb.RNN_MAX_OUT:
+        return f"{alg} with RNN networks: action_dim {A!r} - a head of the recurrent kernels has 1 .. {hb.RNN_MAX_OUT} outputs"
+    for key in ("policy", "value"):
+        sizes = list(kwargs.get(key + "_hidden_sizes") or [])
+        if not 1 <= len(sizes) <= hb.MAX_LAYERS or any(w % 16 or not 16 <= w <= hb.RNN_MAX_HIDDEN for w in sizes):
+            return (f"{alg} with RNN networks: {key}_hidden_sizes {sizes!r} - the recurrent kernels hold 1 .. {hb.MAX_LAYERS} widths (the "
+                    f"recurrence's, then the heads' hidden layers), each a multiple of 16 in 16 .. {hb.RNN_MAX_HIDDEN}")
+    return None
+
+
+def refusal(alg: str, density_words: str, kwargs: dict, categorical: bool = False, recurrent: bool = False):
     """Why `create_alg` cannot build PPO / TRPO from these arguments, or None (POLY / LipsNet are refused before this is asked).
     `density_words`: what of the algorithm's kernels is the Gaussian density's; `categorical`: the algorithm also has the kernels
-    of a categorical StochaPolicyDis (for which the `policy_std_type` / log-std arguments mean nothing and are ignored)."""
-    if kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
+    of a categorical StochaPolicyDis (for which the `policy_std_type` / log-std arguments mean nothing and are ignored); `recurrent`:
+    the algorithm also runs the RNN pair."""
+    if recurrent and "RNN" in (kwargs.get("policy_func_type"), kwargs.get("value_func_type")):
+        reason = rnn_refusal(alg, kwargs)
+        if reason is not None:
+            return reason
+    elif kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
         return f"{alg} runs MLP networks only (policy_func_type {kwargs.get('policy_func_type')!r}, value_func_type {kwargs.get('value_func_type')!r})"
     dist = kwargs.get("policy_act_distribution", "default")
     discrete = categorical and kwargs.get("policy_func_name") == "StochaPolicyDis"
@@ -76,20 +106,23 @@ class ApproxContainer(ApprBase):
 
 
 class OnPolicyBase(AlgorithmBase):
-    def _init_on_policy(self, kwargs: dict, categorical: bool = False):
+    def _init_on_policy(self, kwargs: dict, categorical: bool = False, recurrent: bool = False):
         """`self.networks`, checked, and the empty caches.  `categorical`: a StochaPolicyDis with CategoricalDistribution is accepted
-        beside the Gaussian StochaPolicy."""
+        beside the Gaussian StochaPolicy; `recurrent`: the RNN StochaPolicy / StateValue pair is."""
         name = type(self).__name__
         self.networks = nets = ApproxContainer(**kwargs)
-        gauss = type(nets.policy) is StochaPolicy and nets.policy.action_distribution_cls is GaussDistribution
+        policies, values = ((StochaPolicy, rnn.StochaPolicy), (StateValue, rnn.StateValue)) if recurrent else ((StochaPolicy,), (StateValue,))
+        gauss = type(nets.policy) in policies and nets.policy.action_distribution_cls is GaussDistribution
         cat = categorical and type(nets.policy) is StochaPolicyDis and nets.policy.action_distribution_cls is CategoricalDistribution
         if cat and not 2 <= nets.policy.act_num <= MAX_ACTIONS:
             raise NotImplementedError(f"{name}: {nets.policy.act_num} discrete actions (2 .. {MAX_ACTIONS} only)")
         if not gauss and not cat:
             raise NotImplementedError(f"{name}: policy {type(nets.policy).__name__} (MLP StochaPolicy with GaussDistribution"
                                       f"{' or MLP StochaPolicyDis with CategoricalDistribution' if categorical else ''} only)")
-        if not isinstance(nets.value, StateValue):
+        if not isinstance(nets.value, values):
             raise NotImplementedError(f"{name}: value network {type(nets.value).__name__} (MLP StateValue only)")
+        if isinstance(nets.policy, rnn.StochaPolicy) != isinstance(nets.value, rnn.StateValue):
+            raise NotImplementedError(f"{name}: RNN networks come as a pair, policy and value")
         self.tb_info = dict()
         self._cache, self._bufs = {}, {}
 
@@ -114,7 +147,17 @@ class OnPolicyBase(AlgorithmBase):
                 tuple(sorted(t.data_ptr() for t in self._bufs.values())))
 
     # ---- kernels' objects ------------------------------------------------------------------------
-    def _net(self, role: str, module, B: int, device) -> hb.MlpNet:
+    def _net(self, role: str, module, B: int, device, x=None):
+        """The `MlpNet` of `module` for B rows - or, for a recurrent module, the `RnnNet` for inputs of `x`'s stack length."""
+        if getattr(module, "is_rnn", False):
+            key = (role, B, x.shape[1], str(device))
+            desc = module.hip_rnn(x.shape[1])
+            net = self._cache.get(key)
+            if net is None:
+                net = self._cache[key] = hb.RnnNet(desc, B, device=device)
+            else:
+                net.rnn = desc
+            return net
         key = (role, B, str(device))
         mlp = module.hip_mlp()
         net = self._cache.get(key)
@@ -123,6 +166,16 @@ class OnPolicyBase(AlgorithmBase):
         else:
             net.mlp = mlp
         return net
+
+    @staticmethod
+    def _backward(net, module, x, seed):
+        """`net.backward` into `module`'s `.grad` tensors, whichever of the two kinds `_net` handed out."""
+        if isinstance(net, hb.RnnNet):
+            _flat_grads(module)
+            net.backward(x, seed, module.hip_rnn_grad())
+        else:
+            gw, gb = grad_buffers(module)
+            net.backward(x, seed, gw, gb)
 
     def _buf(self, name: str, shape, device) -> torch.Tensor:
         key = (name, tuple(shape), str(device))

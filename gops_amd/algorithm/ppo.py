@@ -20,7 +20,11 @@ Kept as the reference has them:
 The shuffle is `np.random.shuffle(self.indices)` on the persistent index array (ppo.py:79, 131): a run seeded like the reference draws
 the same permutations.  `data["perm"]`, an integer tensor [num_repeat, sample_batch_size], overrides it.
 
-The policy is the reference's `std_type="mlp_shared"` StochaPolicy with a GaussDistribution; `"parameter"` (the default of the
+With `policy_func_type = value_func_type = "RNN"` (gops_amd/apprfunc/rnn.py) the columns' `obs` is a stack [S, L, O] and the four network
+launches of a step are `gops_rnn_forward / _backward`; the loss kernel sees the same raw head [M, 2A] and value [M], and the step is
+captured the same way.  A mixed pair is refused by `create_alg`.
+
+The MLP policy is the reference's `std_type="mlp_shared"` StochaPolicy with a GaussDistribution; `"parameter"` (the default of the
 reference's PPO examples) and `"mlp_separated"` are not yet supported - `create_alg` refuses them with that reason.
 """
 __all__ = ["ApproxContainer", "PPO"]
@@ -33,7 +37,7 @@ import torch
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm import _on_policy
 from gops_amd.algorithm._on_policy import ApproxContainer, OnPolicyBase
-from gops_amd.algorithm.base import batch_to_device, cuda_device_of, grad_buffers
+from gops_amd.algorithm.base import batch_to_device, cuda_device_of
 from gops_amd.utils.common_utils import make_adam
 from gops_amd.utils.hip_graph import StepGraphCache
 from gops_amd.utils.lazy_scalar import scalar
@@ -47,7 +51,7 @@ LOSS_TERMS = ("loss_total", "loss_surrogate", "loss_value", "loss_entropy", "app
 
 def refusal(kwargs: dict):
     """Why `create_alg` cannot build PPO from these arguments, or None."""
-    return _on_policy.refusal("PPO", "the loss kernel evaluates that density", kwargs)
+    return _on_policy.refusal("PPO", "the loss kernel evaluates that density", kwargs, recurrent=True)
 
 
 class PPO(OnPolicyBase):
@@ -80,7 +84,7 @@ class PPO(OnPolicyBase):
         self.value_clip = 10.0
         self.loss_value_norm = False
 
-        self._init_on_policy(kwargs)
+        self._init_on_policy(kwargs, recurrent=True)
         self.learning_rate = kwargs["learning_rate"]
         self.approximate_optimizer = make_adam(self.networks.parameters(), lr=self.learning_rate)
         self._graph = StepGraphCache()
@@ -100,8 +104,8 @@ class PPO(OnPolicyBase):
         S = cols["obs"].shape[0]
         cols["act"] = cols["act"].reshape(S, -1)
         cols["adv"] = self._adv_normalize(device).run(cols["adv"], self.EPS, out=self._buf("adv", (S,), device))
-        cols["val"] = self._net("value@all", nets.value, S, device).forward(cols["obs"], out=self._buf("val", (S,), device)).view(S)
-        head = self._net("policy@all", nets.policy, S, device).forward(cols["obs"])
+        cols["val"] = self._net("value@all", nets.value, S, device, cols["obs"]).forward(cols["obs"], out=self._buf("val", (S,), device)).view(S)
+        head = self._net("policy@all", nets.policy, S, device, cols["obs"]).forward(cols["obs"])
         A = head.shape[1] // 2
         cols["logits"] = torch.cat((head[:, :A], torch.clamp(head[:, A:], nets.policy.min_log_std, nets.policy.max_log_std).exp()), dim=-1)
 
@@ -157,17 +161,15 @@ class PPO(OnPolicyBase):
         nets = self.networks
         o = mb["obs"]
         M, device = o.shape[0], o.device
-        pol, val, loss = self._net("policy@mb", nets.policy, M, device), self._net("value@mb", nets.value, M, device), self._ppo_loss(M, device)
+        pol, val, loss = self._net("policy@mb", nets.policy, M, device, o), self._net("value@mb", nets.value, M, device, o), self._ppo_loss(M, device)
         if loss._hyper is None:
             loss.set_hyper(self.clip_now, self.value_clip, self.loss_coefficient_kl, self.loss_coefficient_value, self.loss_coefficient_entropy)
         head = pol.forward(o, out=self._buf("head", (M, pol.out_dim), device))
         v = val.forward(o, out=self._buf("v", (M, 1), device))
         seed_head, seed_v, stats = loss.run(head, v, mb["act"], mb["logp"], mb["adv"], mb["ret"], mb["val"], mb["logits"],
                                             seed_head=self._buf("seed_head", (M, pol.out_dim), device), seed_v=self._buf("seed_v", (M, 1), device))
-        gw, gb = grad_buffers(nets.policy)
-        pol.backward(o, seed_head, gw, gb)
-        gw, gb = grad_buffers(nets.value)
-        val.backward(o, seed_v, gw, gb)
+        self._backward(pol, nets.policy, o, seed_head)
+        self._backward(val, nets.value, o, seed_v)
         return stats.clone()
 
     def _signature(self, mb):

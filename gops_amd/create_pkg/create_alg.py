@@ -138,6 +138,12 @@ def create_alg(**kwargs) -> object:
                   None)
         if reason is not None:
             raise NotImplementedError(f"apprfunc type LipsNet ({', '.join(lips)}): {reason}")
+    rnn = [k for k in (("value",) if kwargs["algorithm"] == "RPI" else ("policy", "value")) if kwargs.get(k + "_func_type") == "RNN"]
+    if rnn and not (kwargs["algorithm"] in _ACTOR_CRITIC or kwargs["algorithm"] in soft_registry or reg in _SELF_DESCRIBED):
+        # (the model-free families state their own sentence below; PPO's module accepts the pair)
+        raise NotImplementedError(f"apprfunc type RNN ({', '.join(rnn)}) is supported by PPO only, not by {kwargs['algorithm']}: the recurrent "
+                                  "kernels (gops_rnn_forward / _backward) stand in for a network evaluated on its own, and this "
+                                  "algorithm's fused launches take MLP, POLY, GAUSS or LipsNet networks")
     if kwargs["algorithm"] in _ACTOR_CRITIC:   # refused here with the reason, so that nothing fails later
         from gops_amd.algorithm._actor_critic import refusal
         reason = refusal(kwargs["algorithm"], kwargs)

@@ -232,6 +232,20 @@ class GopsPerGather(C.Structure):
     _fields_ = [("n_keys", C.c_int32), ("reserved", C.c_int32), ("key", GopsPerKey * PER_MAX_KEYS)]
 
 
+RNN_MAX_SEQ, RNN_MAX_HEADS, RNN_MAX_OBS, RNN_MAX_HIDDEN, RNN_MAX_OUT = 32, 2, 64, 128, 16   # include/gops_hip.h: GOPS_RNN_*
+
+
+class GopsRnn(C.Structure):   # gops_rnn_forward / _backward
+    _fields_ = [("seq_len", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32), ("n_heads", C.c_int32),
+                ("weight_ih", C.c_void_p), ("weight_hh", C.c_void_p), ("bias_ih", C.c_void_p), ("bias_hh", C.c_void_p),
+                ("head", GopsMlp * RNN_MAX_HEADS)]
+
+
+class GopsRnnGrad(C.Structure):
+    _fields_ = [("weight_ih", C.c_void_p), ("weight_hh", C.c_void_p), ("bias_ih", C.c_void_p), ("bias_hh", C.c_void_p),
+                ("head", GopsMlpGrad * RNN_MAX_HEADS)]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every symbol of include/gops_hip.h (argtypes None: not declared to ctypes)."""
     P, vp, i32, sz, f64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_size_t, C.c_double, C.c_int
@@ -326,6 +340,9 @@ def _signatures():
         "gops_per_sample": (rc, [vp, vp, i32, i32, f64, vp, i32, P(GopsPerGather), vp, vp, vp]),
         "gops_per_update": (rc, [vp, vp, vp, i32, vp, vp, i32, i32, f64, f64, vp]),
         "gops_per_fill": (rc, [vp, vp, vp, i32, i32, i32, vp]),
+        "gops_rnn_workspace_bytes": (sz, [P(GopsRnn), i32]),
+        "gops_rnn_forward": (rc, [P(GopsRnn), i32, vp, vp, vp, sz, vp]),
+        "gops_rnn_backward": (rc, [P(GopsRnn), i32, vp, vp, P(GopsRnnGrad), vp, sz, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -446,6 +463,40 @@ def make_mlp_grad(gw: Sequence[torch.Tensor], gb: Sequence[torch.Tensor]) -> Gop
     for j, (w, b) in enumerate(zip(gw, gb)):
         g.weight[j] = _ptr(w)
         g.bias[j] = _ptr(b)
+    return g
+
+
+RNN_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+
+
+def make_rnn(recurrent: Sequence[torch.Tensor], heads, act: str, seq_len: int, dtype=None) -> GopsRnn:
+    """`recurrent`: nn.RNN's weight_ih_l0 [H, O], weight_hh_l0 [H, H], bias_ih_l0, bias_hh_l0; `heads`: one or two (weights, biases)
+    of Linear stacks over the last hidden state; `act`: the heads' hidden activation; `seq_len`: the stack length L of the input
+    [B, L, O].  The library holds the limits (RNN_MAX_*): an unsupported shape gets 0 workspace bytes and a refusing `RnnNet`."""
+    if not 1 <= len(heads) <= RNN_MAX_HEADS:
+        raise RuntimeError(f"a recurrent net with {len(heads)} heads is outside the HIP path (1..{RNN_MAX_HEADS})")
+    r = GopsRnn()
+    r.seq_len, r.n_heads = int(seq_len), len(heads)
+    r.hidden, r.obs_dim = recurrent[0].shape
+    for name, t in zip(RNN_PARAMS, recurrent):
+        setattr(r, name, _ptr(t))
+    for h, (weights, biases) in enumerate(heads):
+        if not 1 <= len(weights) <= MAX_LAYERS:
+            raise RuntimeError(f"a head with {len(weights)} Linear layers is outside the HIP path (1..{MAX_LAYERS})")
+        r.head[h].dtype = dtype_id(dtype)
+        _fill_mlp(r.head[h], weights, biases, act)
+    r._keep = (list(recurrent), [(list(w), list(b)) for w, b in heads])   # the struct holds raw pointers: keep the tensors alive
+    return r
+
+
+def make_rnn_grad(recurrent: Sequence[torch.Tensor], heads) -> GopsRnnGrad:
+    """The gradient tensors in `make_rnn`'s order: four recurrent ones, then (weight grads, bias grads) per head."""
+    g = GopsRnnGrad()
+    for name, t in zip(RNN_PARAMS, recurrent):
+        setattr(g, name, _ptr(t))
+    for h, (gw, gb) in enumerate(heads):
+        for j, (w, b) in enumerate(zip(gw, gb)):
+            g.head[h].weight[j], g.head[h].bias[j] = _ptr(w), _ptr(b)
     return g
 
 
@@ -1334,6 +1385,29 @@ class MlpNet:
         _call("gops_mlp_backward_x", C.byref(self.mlp), self.batch, _ptr(x), _ptr(grad_y), C.byref(g) if g is not None else None, _ptr(gx),
               *_ws(self))
         return gx
+
+
+class RnnNet:
+    """Batch evaluation of a recurrent net (`make_rnn`) on inputs [batch, L, O] and its backward through time into every parameter
+    (`gops_rnn_forward / _backward`): `MlpNet`'s surface, with the gradient set as one `GopsRnnGrad` (`make_rnn_grad`)."""
+
+    def __init__(self, rnn: GopsRnn, batch: int, device: Optional[torch.device] = None):
+        self.rnn, self.batch = rnn, batch
+        self.out_dim = sum(int(rnn.head[h].sizes[rnn.head[h].n_layers]) for h in range(rnn.n_heads))
+        _own_workspace(self, lib().gops_rnn_workspace_bytes(C.byref(rnn), batch), device,
+                       "gops_rnn_workspace_bytes: unsupported recurrent network for the HIP path")
+
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`out`: a contiguous tensor of batch * out_dim floats that receives the result."""
+        y = torch.empty(self.batch, self.out_dim, dtype=torch.float32, device=self.device) if out is None else out
+        assert y.numel() == self.batch * self.out_dim and x.numel() == self.batch * self.rnn.seq_len * self.rnn.obs_dim
+        _call("gops_rnn_forward", C.byref(self.rnn), self.batch, _ptr(x), _ptr(y), *_ws(self))
+        return y
+
+    def backward(self, x: torch.Tensor, grad_y: torch.Tensor, grads: GopsRnnGrad):
+        """From the stash the last `forward` of this object left: every gradient tensor of `grads` is overwritten."""
+        assert grad_y.numel() == self.batch * self.out_dim
+        _call("gops_rnn_backward", C.byref(self.rnn), self.batch, _ptr(x), _ptr(grad_y), C.byref(grads), *_ws(self))
 
 
 def env_step(env: GopsEnv, obs, action, done, info: Optional[Dict[str, torch.Tensor]] = None):

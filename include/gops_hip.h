@@ -1369,6 +1369,56 @@ int gops_per_update(double* sum_tree, double* min_tree, double* max_priority, in
                     int32_t priority_f64, int32_t batch, double alpha, double epsilon, void* stream);
 int gops_per_fill(double* sum_tree, double* min_tree, const double* max_priority, int32_t capacity, int32_t ptr, int32_t n, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): recurrent networks (gops/apprfunc/rnn.py) - an Elman recurrence
+ * over a stack of observations whose last hidden state feeds one or two MLP heads (csrc/rnn.hip):
+ *     x [B, seq_len, obs_dim] row-major fp32,  h_0 = 0,  h_t = tanh(W_ih x_t + b_ih + W_hh h_{t-1} + b_hh)  for t = 1 .. seq_len,
+ *     y [B, out_0 (+ out_1)] = head_0(h_L) (|| head_1(h_L))
+ * weight_ih [hidden, obs_dim], weight_hh [hidden, hidden], bias_ih / bias_hh [hidden]: torch's nn.RNN layouts (weight_ih_l0, ...).
+ * A head is a GopsMlp whose input width sizes[0] is `hidden`: n_layers - 1 hidden layers with hidden_act, a linear output layer
+ * (n_layers = 1: the output layer alone).  One head: StateValue, DetermPolicy, ActionValueDis; two: StochaPolicy's mean and raw
+ * log std (clamp and exp stay with the caller's loss kernel).
+ *   gops_rnn_forward:  x -> y; stashes every h_t and the heads' hidden activations in the workspace.  One launch: a workgroup owns
+ *     GOPS_TILE samples, W_ih / W_hh stay in registers for all steps, exact fp32 products (v_mfma_f32_16x16x4_f32).
+ *   gops_rnn_backward: grad_y [B, out_0 (+ out_1)] -> the gradient of every tensor (overwritten), from the stash the forward of the
+ *     SAME workspace left.  Two launches: the reverse sweep, which keeps the recurrent weight gradients in registers over all steps
+ *     and leaves one partial per workgroup, and their sum in workgroup order - no float atomics: bitwise reproducible.  Rows of
+ *     grad_y beyond B are never read, rows of y beyond B never written.
+ * GOPS_ERR_BAD_ARG: a NULL pointer, batch < 1, seq_len < 1, n_heads outside 1 .. GOPS_RNN_MAX_HEADS, a head whose input width is
+ *   not `hidden`.  GOPS_ERR_UNSUPPORTED: seq_len > GOPS_RNN_MAX_SEQ, obs_dim outside 1 .. GOPS_RNN_MAX_OBS, `hidden` or a head's hidden
+ *   width that is no multiple of 16 in 16 .. GOPS_RNN_MAX_HIDDEN, a head with more than GOPS_MAX_LAYERS layers, an output width
+ *   outside 1 .. GOPS_RNN_MAX_OUT, a POLY / RBF head (hidden_act no GOPS_ACT_*), a dtype other than GOPS_DTYPE_F32.
+ *   GOPS_ERR_WORKSPACE: a NULL workspace or workspace_bytes below gops_rnn_workspace_bytes (0 for a description the entry points
+ *   reject).  Nothing is launched in any of these cases. */
+#define GOPS_RNN_MAX_SEQ 32
+#define GOPS_RNN_MAX_HEADS 2
+#define GOPS_RNN_MAX_OBS 64
+#define GOPS_RNN_MAX_HIDDEN 128
+#define GOPS_RNN_MAX_OUT 16
+struct GopsRnn {
+    int32_t seq_len;
+    int32_t obs_dim;
+    int32_t hidden;
+    int32_t n_heads;
+    const float* weight_ih;   /* device pointers */
+    const float* weight_hh;
+    const float* bias_ih;
+    const float* bias_hh;
+    GopsMlp head[GOPS_RNN_MAX_HEADS];
+};
+typedef struct GopsRnn GopsRnn;
+struct GopsRnnGrad {
+    float* weight_ih;
+    float* weight_hh;
+    float* bias_ih;
+    float* bias_hh;
+    GopsMlpGrad head[GOPS_RNN_MAX_HEADS];
+};
+typedef struct GopsRnnGrad GopsRnnGrad;
+size_t gops_rnn_workspace_bytes(const GopsRnn* net, int32_t batch);
+int gops_rnn_forward(const GopsRnn* net, int32_t batch, const float* x, float* y, void* workspace, size_t workspace_bytes, void* stream);
+int gops_rnn_backward(const GopsRnn* net, int32_t batch, const float* x, const float* grad_y, const GopsRnnGrad* grad, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* Timing hook for bench.py: average duration in ms of the named internal kernel over the
  * launches recorded since the last reset (HIP events on the launch stream).  kernel ids:
  * 0 = forward rollout, 1 = backward sweep, 2 = weight-gradient GEMMs (+ reduce) of gops_rollout_*;
