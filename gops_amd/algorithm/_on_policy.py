@@ -1,5 +1,5 @@
 """What PPO and TRPO share on the HIP kernels: a Gaussian `mlp_shared` StochaPolicy (for TRPO also a categorical StochaPolicyDis; for PPO
-also the recurrent pair of gops_amd/apprfunc/rnn.py) and a StateValue in one container, the refusal `create_alg` states for anything
+also the recurrent pair of gops_amd/apprfunc/rnn.py and the convolutional pair of gops_amd/apprfunc/cnn.py) and a StateValue in one container, the refusal `create_alg` states for anything
 else, the per-object caches of kernel objects and buffers, and the captured Adam step.
 """
 import numpy as np
@@ -7,7 +7,7 @@ import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import AlgorithmBase, ApprBase, _flat_grads, grad_buffers
-from gops_amd.apprfunc import rnn
+from gops_amd.apprfunc import cnn, rnn
 from gops_amd.apprfunc.mlp import StateValue, StochaPolicy, StochaPolicyDis
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
 from gops_amd.utils.act_distribution import CategoricalDistribution, GaussDistribution
@@ -54,13 +54,47 @@ def rnn_refusal(alg: str, kwargs: dict):
     return None
 
 
-def refusal(alg: str, density_words: str, kwargs: dict, categorical: bool = False, recurrent: bool = False):
+def cnn_refusal(alg: str, kwargs: dict):
+    """Why `create_alg` cannot build `alg` on the convolution kernels (`gops_conv_forward / _backward`) from these arguments, or None."""
+    types = (kwargs.get("policy_func_type"), kwargs.get("value_func_type"))
+    if types != ("CNN", "CNN"):
+        return (f"{alg} takes CNN networks as a pair, both or neither (policy_func_type {types[0]!r}, value_func_type {types[1]!r}): the policy "
+                "and the value read the same columns, and an image [S, C, H, W] is no input of an MLP")
+    if kwargs.get("cnn_shared"):
+        return f"{alg} with CNN networks: cnn_shared feature networks are outside this path (each network has its own convolutions)"
+    shape = kwargs.get("obsv_dim")
+    if not (isinstance(shape, (tuple, list)) and len(shape) == 3 and all(isinstance(v, (int, np.integer)) for v in shape)):
+        return f"{alg} with CNN networks takes obsv_dim as the triple (C, H, W) of an image, not {shape!r}"
+    A = kwargs.get("action_dim")
+    if not isinstance(A, (int, np.integer)) or not 1 <= A <= hb.MAX_ACT:
+        return f"{alg} with CNN networks: action_dim {A!r} - the loss kernel takes 1 .. {hb.MAX_ACT} actions"
+    for key, out, short in (("policy", A, False), ("value", 1, True)):
+        conv_type = kwargs.get(key + "_conv_type")
+        if conv_type not in cnn.CONV_TYPES:
+            return f"{alg} with CNN networks: {key}_conv_type {conv_type!r} ({', '.join(cnn.CONV_TYPES)} only)"
+        C, H, W = cnn.feature_shape(conv_type, shape)
+        if not (1 <= shape[0] <= hb.CONV_MAX_CHANNELS and all(1 <= v <= hb.CONV_MAX_EXTENT for v in shape[1:]) and H >= 1 and W >= 1):
+            return (f"{alg} with CNN networks: obsv_dim {tuple(shape)!r} is outside the convolution kernels' range for {conv_type} (C in 1 .. "
+                    f"{hb.CONV_MAX_CHANNELS}, H and W up to {hb.CONV_MAX_EXTENT} and large enough for every layer)")
+        widths = [C * H * W] + list(cnn.CONV_TYPES[conv_type]["short" if short else "hidden"]) + [out]
+        if not hb.mlp_widths_supported(widths):
+            return (f"{alg} with CNN networks: obsv_dim {tuple(shape)!r} gives {key} heads of widths {widths!r} with {conv_type} - a feature "
+                    f"width of {widths[0]} is more than the head kernels (gops_mlp_forward / gops_mlp_backward_x) hold in their LDS tiles")
+    return None
+
+
+def refusal(alg: str, density_words: str, kwargs: dict, categorical: bool = False, recurrent: bool = False, convolutional: bool = False):
     """Why `create_alg` cannot build PPO / TRPO from these arguments, or None (POLY / LipsNet are refused before this is asked).
     `density_words`: what of the algorithm's kernels is the Gaussian density's; `categorical`: the algorithm also has the kernels
     of a categorical StochaPolicyDis (for which the `policy_std_type` / log-std arguments mean nothing and are ignored); `recurrent`:
-    the algorithm also runs the RNN pair."""
+    the algorithm also runs the RNN pair; `convolutional`: and the CNN pair (asked with a `<key>_conv_type`)."""
     if recurrent and "RNN" in (kwargs.get("policy_func_type"), kwargs.get("value_func_type")):
         reason = rnn_refusal(alg, kwargs)
+        if reason is not None:
+            return reason
+    elif (convolutional and "CNN" in (kwargs.get("policy_func_type"), kwargs.get("value_func_type"))
+          and ("policy_conv_type" in kwargs or "value_conv_type" in kwargs)):
+        reason = cnn_refusal(alg, kwargs)
         if reason is not None:
             return reason
     elif kwargs.get("policy_func_type") != "MLP" or kwargs.get("value_func_type") != "MLP":
@@ -106,12 +140,13 @@ class ApproxContainer(ApprBase):
 
 
 class OnPolicyBase(AlgorithmBase):
-    def _init_on_policy(self, kwargs: dict, categorical: bool = False, recurrent: bool = False):
+    def _init_on_policy(self, kwargs: dict, categorical: bool = False, recurrent: bool = False, convolutional: bool = False):
         """`self.networks`, checked, and the empty caches.  `categorical`: a StochaPolicyDis with CategoricalDistribution is accepted
-        beside the Gaussian StochaPolicy; `recurrent`: the RNN StochaPolicy / StateValue pair is."""
+        beside the Gaussian StochaPolicy; `recurrent`: the RNN StochaPolicy / StateValue pair is; `convolutional`: the CNN pair is."""
         name = type(self).__name__
         self.networks = nets = ApproxContainer(**kwargs)
-        policies, values = ((StochaPolicy, rnn.StochaPolicy), (StateValue, rnn.StateValue)) if recurrent else ((StochaPolicy,), (StateValue,))
+        families = (rnn,) * recurrent + (cnn,) * convolutional
+        policies, values = (StochaPolicy,) + tuple(m.StochaPolicy for m in families), (StateValue,) + tuple(m.StateValue for m in families)
         gauss = type(nets.policy) in policies and nets.policy.action_distribution_cls is GaussDistribution
         cat = categorical and type(nets.policy) is StochaPolicyDis and nets.policy.action_distribution_cls is CategoricalDistribution
         if cat and not 2 <= nets.policy.act_num <= MAX_ACTIONS:
@@ -121,8 +156,9 @@ class OnPolicyBase(AlgorithmBase):
                                       f"{' or MLP StochaPolicyDis with CategoricalDistribution' if categorical else ''} only)")
         if not isinstance(nets.value, values):
             raise NotImplementedError(f"{name}: value network {type(nets.value).__name__} (MLP StateValue only)")
-        if isinstance(nets.policy, rnn.StochaPolicy) != isinstance(nets.value, rnn.StateValue):
-            raise NotImplementedError(f"{name}: RNN networks come as a pair, policy and value")
+        for family, m in (("RNN", rnn), ("CNN", cnn)):
+            if isinstance(nets.policy, m.StochaPolicy) != isinstance(nets.value, m.StateValue):
+                raise NotImplementedError(f"{name}: {family} networks come as a pair, policy and value")
         self.tb_info = dict()
         self._cache, self._bufs = {}, {}
 
@@ -148,7 +184,17 @@ class OnPolicyBase(AlgorithmBase):
 
     # ---- kernels' objects ------------------------------------------------------------------------
     def _net(self, role: str, module, B: int, device, x=None):
-        """The `MlpNet` of `module` for B rows - or, for a recurrent module, the `RnnNet` for inputs of `x`'s stack length."""
+        """The `MlpNet` of `module` for B rows - or, for a recurrent module, the `RnnNet` for inputs of `x`'s stack length, for a
+        convolutional one the `CnnNet`."""
+        if getattr(module, "is_cnn", False):
+            key = (role, B, str(device))
+            conv, heads = module.hip_cnn()
+            net = self._cache.get(key)
+            if net is None:
+                net = self._cache[key] = hb.CnnNet(conv, heads, B, device=device)
+            else:
+                net.set_descriptions(conv, heads)
+            return net
         if getattr(module, "is_rnn", False):
             key = (role, B, x.shape[1], str(device))
             desc = module.hip_rnn(x.shape[1])
@@ -169,10 +215,13 @@ class OnPolicyBase(AlgorithmBase):
 
     @staticmethod
     def _backward(net, module, x, seed):
-        """`net.backward` into `module`'s `.grad` tensors, whichever of the two kinds `_net` handed out."""
+        """`net.backward` into `module`'s `.grad` tensors, whichever of the three kinds `_net` handed out."""
         if isinstance(net, hb.RnnNet):
             _flat_grads(module)
             net.backward(x, seed, module.hip_rnn_grad())
+        elif isinstance(net, hb.CnnNet):
+            _flat_grads(module)
+            net.backward(x, seed, module.hip_cnn_grad())
         else:
             gw, gb = grad_buffers(module)
             net.backward(x, seed, gw, gb)

@@ -22,7 +22,9 @@ the same permutations.  `data["perm"]`, an integer tensor [num_repeat, sample_ba
 
 With `policy_func_type = value_func_type = "RNN"` (gops_amd/apprfunc/rnn.py) the columns' `obs` is a stack [S, L, O] and the four network
 launches of a step are `gops_rnn_forward / _backward`; the loss kernel sees the same raw head [M, 2A] and value [M], and the step is
-captured the same way.  A mixed pair is refused by `create_alg`.
+captured the same way.  With `policy_func_type = value_func_type = "CNN"` and a `<key>_conv_type` (gops_amd/apprfunc/cnn.py) `obs` is an
+image batch [S, C, H, W] and the launches are `gops_conv_forward / _backward` with `gops_mlp_forward / _backward_x` for the heads.  A mixed
+pair is refused by `create_alg`.
 
 The MLP policy is the reference's `std_type="mlp_shared"` StochaPolicy with a GaussDistribution; `"parameter"` (the default of the
 reference's PPO examples) and `"mlp_separated"` are not yet supported - `create_alg` refuses them with that reason.
@@ -51,7 +53,7 @@ LOSS_TERMS = ("loss_total", "loss_surrogate", "loss_value", "loss_entropy", "app
 
 def refusal(kwargs: dict):
     """Why `create_alg` cannot build PPO from these arguments, or None."""
-    return _on_policy.refusal("PPO", "the loss kernel evaluates that density", kwargs, recurrent=True)
+    return _on_policy.refusal("PPO", "the loss kernel evaluates that density", kwargs, recurrent=True, convolutional=True)
 
 
 class PPO(OnPolicyBase):
@@ -84,7 +86,7 @@ class PPO(OnPolicyBase):
         self.value_clip = 10.0
         self.loss_value_norm = False
 
-        self._init_on_policy(kwargs, recurrent=True)
+        self._init_on_policy(kwargs, recurrent=True, convolutional=True)
         self.learning_rate = kwargs["learning_rate"]
         self.approximate_optimizer = make_adam(self.networks.parameters(), lr=self.learning_rate)
         self._graph = StepGraphCache()

@@ -144,6 +144,12 @@ def create_alg(**kwargs) -> object:
         raise NotImplementedError(f"apprfunc type RNN ({', '.join(rnn)}) is supported by PPO only, not by {kwargs['algorithm']}: the recurrent "
                                   "kernels (gops_rnn_forward / _backward) stand in for a network evaluated on its own, and this "
                                   "algorithm's fused launches take MLP, POLY, GAUSS or LipsNet networks")
+    cnn = [k for k in (("value",) if kwargs["algorithm"] == "RPI" else ("policy", "value"))
+           if kwargs.get(k + "_func_type") == "CNN" and k + "_conv_type" in kwargs]   # (without its conv_type: an unknown type, as before)
+    if cnn and kwargs["algorithm"] != "PPO":
+        raise NotImplementedError(f"apprfunc type CNN ({', '.join(cnn)}) is supported by PPO only, not by {kwargs['algorithm']}: the convolution "
+                                  "kernels (gops_conv_forward / _backward) stand in for a network evaluated on its own, and this "
+                                  "algorithm's fused launches take MLP, POLY, GAUSS or LipsNet networks")
     if kwargs["algorithm"] in _ACTOR_CRITIC:   # refused here with the reason, so that nothing fails later
         from gops_amd.algorithm._actor_critic import refusal
         reason = refusal(kwargs["algorithm"], kwargs)

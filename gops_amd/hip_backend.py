@@ -246,6 +246,19 @@ class GopsRnnGrad(C.Structure):
                 ("head", GopsMlpGrad * RNN_MAX_HEADS)]
 
 
+CONV_MAX_LAYERS, CONV_MAX_KERNEL, CONV_MAX_STRIDE, CONV_MAX_CHANNELS, CONV_MAX_EXTENT = 6, 8, 4, 256, 128   # include/gops_hip.h: GOPS_CONV_*
+
+
+class GopsConv(C.Structure):   # gops_conv_forward / _backward
+    _fields_ = [("n_conv", C.c_int32), ("in_channels", C.c_int32), ("in_h", C.c_int32), ("in_w", C.c_int32),
+                ("channels", C.c_int32 * CONV_MAX_LAYERS), ("kernel", C.c_int32 * CONV_MAX_LAYERS), ("stride", C.c_int32 * CONV_MAX_LAYERS),
+                ("weight", C.c_void_p * CONV_MAX_LAYERS), ("bias", C.c_void_p * CONV_MAX_LAYERS)]
+
+
+class GopsConvGrad(C.Structure):
+    _fields_ = [("weight", C.c_void_p * CONV_MAX_LAYERS), ("bias", C.c_void_p * CONV_MAX_LAYERS)]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every symbol of include/gops_hip.h (argtypes None: not declared to ctypes)."""
     P, vp, i32, sz, f64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_size_t, C.c_double, C.c_int
@@ -343,6 +356,9 @@ def _signatures():
         "gops_rnn_workspace_bytes": (sz, [P(GopsRnn), i32]),
         "gops_rnn_forward": (rc, [P(GopsRnn), i32, vp, vp, vp, sz, vp]),
         "gops_rnn_backward": (rc, [P(GopsRnn), i32, vp, vp, P(GopsRnnGrad), vp, sz, vp]),
+        "gops_conv_workspace_bytes": (sz, [P(GopsConv), i32]),
+        "gops_conv_forward": (rc, [P(GopsConv), i32, vp, vp, vp, sz, vp]),
+        "gops_conv_backward": (rc, [P(GopsConv), i32, vp, vp, vp, P(GopsConvGrad), vp, sz, vp]),
         "gops_profile_enable": (rc, [i32]),
         "gops_profile_reset": (rc, []),
         "gops_profile_read": (rc, [i32, P(f64), P(C.c_int64)]),
@@ -458,6 +474,19 @@ def make_mlp(weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], ac
     return m
 
 
+def mlp_widths_supported(sizes: Sequence[int], batch: int = 1) -> bool:
+    """Whether `gops_mlp_forward / _backward` take an fp32 MLP of these layer widths (input first): the size query alone, host only."""
+    if not 2 <= len(sizes) - 1 <= MAX_LAYERS:
+        return False
+    m = GopsMlp()
+    m.n_layers, m.dtype, m.hidden_act, m.variant_flags = len(sizes) - 1, dtype_id(None), ACT_IDS["tanh"], DEFAULT_VARIANT_FLAGS
+    for j, w in enumerate(sizes):
+        m.sizes[j] = int(w)
+    for j in range(m.n_layers):
+        m.weight[j] = m.bias[j] = 0x1000   # (non-null: the query reads no memory)
+    return lib().gops_mlp_workspace_bytes(C.byref(m), batch) != 0
+
+
 def make_mlp_grad(gw: Sequence[torch.Tensor], gb: Sequence[torch.Tensor]) -> GopsMlpGrad:
     g = GopsMlpGrad()
     for j, (w, b) in enumerate(zip(gw, gb)):
@@ -497,6 +526,38 @@ def make_rnn_grad(recurrent: Sequence[torch.Tensor], heads) -> GopsRnnGrad:
     for h, (gw, gb) in enumerate(heads):
         for j, (w, b) in enumerate(zip(gw, gb)):
             g.head[h].weight[j], g.head[h].bias[j] = _ptr(w), _ptr(b)
+    return g
+
+
+def conv_out_shape(shape, channels, kernels, strides):
+    """(C, H, W) after Conv2d(., channels[l], kernels[l], strides[l]) for every l, without padding; an extent below 1 where a
+    layer's input is smaller than its kernel."""
+    C_, H, W = shape
+    for n, k, s in zip(channels, kernels, strides):
+        C_, H, W = n, (H - k) // s + 1 if H >= k else 0, (W - k) // s + 1 if W >= k else 0
+    return C_, H, W
+
+
+def make_conv(weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], strides: Sequence[int], in_hw) -> GopsConv:
+    """`weights[l]`: nn.Conv2d's weight [C_out, C_in, k, k] (square kernels), `biases[l]` [C_out], `strides[l]`; `in_hw`: (H, W) of
+    the input [B, C_in of layer 0, H, W].  The library holds the limits (CONV_MAX_*): an unsupported geometry gets 0 workspace bytes
+    and a refusing `ConvStack`."""
+    if not 1 <= len(weights) <= CONV_MAX_LAYERS:
+        raise RuntimeError(f"a convolution stack of {len(weights)} layers is outside the HIP path (1..{CONV_MAX_LAYERS})")
+    c = GopsConv()
+    c.n_conv, c.in_channels, (c.in_h, c.in_w) = len(weights), weights[0].shape[1], in_hw
+    for l, (w, b, s) in enumerate(zip(weights, biases, strides)):
+        assert w.dim() == 4 and w.shape[2] == w.shape[3], "square kernels only"
+        c.channels[l], c.kernel[l], c.stride[l] = w.shape[0], w.shape[2], int(s)
+        c.weight[l], c.bias[l] = _ptr(w), _ptr(b)
+    c._keep = (list(weights), list(biases))   # the struct holds raw pointers: keep the tensors alive
+    return c
+
+
+def make_conv_grad(gw: Sequence[torch.Tensor], gb: Sequence[torch.Tensor]) -> GopsConvGrad:
+    g = GopsConvGrad()
+    for l, (w, b) in enumerate(zip(gw, gb)):
+        g.weight[l], g.bias[l] = _ptr(w), _ptr(b)
     return g
 
 
@@ -1378,10 +1439,10 @@ class MlpNet:
         g = make_mlp_grad(grad_w, grad_b)
         _call("gops_mlp_backward", C.byref(self.mlp), self.batch, _ptr(x), _ptr(grad_y), C.byref(g), *_ws(self))
 
-    def backward_x(self, x: torch.Tensor, grad_y: torch.Tensor, grad_w=None, grad_b=None) -> torch.Tensor:
-        """`gops_mlp_backward_x`: returns d(loss)/d(x); parameter gradients too when grad_w / grad_b are given."""
+    def backward_x(self, x: torch.Tensor, grad_y: torch.Tensor, grad_w=None, grad_b=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`gops_mlp_backward_x`: returns d(loss)/d(x) (in `out` when given); parameter gradients too when grad_w / grad_b are given."""
         g = make_mlp_grad(grad_w, grad_b) if grad_w is not None else None
-        gx = torch.empty(self.batch, int(self.mlp.sizes[0]), dtype=torch.float32, device=self.device)
+        gx = torch.empty(self.batch, int(self.mlp.sizes[0]), dtype=torch.float32, device=self.device) if out is None else out
         _call("gops_mlp_backward_x", C.byref(self.mlp), self.batch, _ptr(x), _ptr(grad_y), C.byref(g) if g is not None else None, _ptr(gx),
               *_ws(self))
         return gx
@@ -1408,6 +1469,85 @@ class RnnNet:
         """From the stash the last `forward` of this object left: every gradient tensor of `grads` is overwritten."""
         assert grad_y.numel() == self.batch * self.out_dim
         _call("gops_rnn_backward", C.byref(self.rnn), self.batch, _ptr(x), _ptr(grad_y), C.byref(grads), *_ws(self))
+
+
+class ConvStack:
+    """Batch evaluation of a convolution stack (`make_conv`) on inputs [batch, C, H, W] and its backward into every weight and bias
+    (`gops_conv_forward / _backward`); owns the workspace with the stashed activations."""
+
+    def __init__(self, conv: GopsConv, batch: int, device: Optional[torch.device] = None):
+        self.conv, self.batch = conv, batch
+        C_, H, W = conv_out_shape((conv.in_channels, conv.in_h, conv.in_w), *(list(a)[:conv.n_conv] for a in (conv.channels, conv.kernel, conv.stride)))
+        self.features = C_ * H * W
+        _own_workspace(self, lib().gops_conv_workspace_bytes(C.byref(conv), batch), device,
+                       "gops_conv_workspace_bytes: unsupported convolution stack for the HIP path")
+
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> the features [batch, F] in (C, H, W) order of the last layer (`out`: a contiguous tensor of batch * F floats)."""
+        f = torch.empty(self.batch, self.features, dtype=torch.float32, device=self.device) if out is None else out
+        assert f.numel() == self.batch * self.features and x.numel() == self.batch * self.conv.in_channels * self.conv.in_h * self.conv.in_w
+        _call("gops_conv_forward", C.byref(self.conv), self.batch, _ptr(x), _ptr(f), *_ws(self))
+        return f
+
+    def backward(self, x: torch.Tensor, grad_a: torch.Tensor, grad_b: Optional[torch.Tensor], grads: GopsConvGrad):
+        """From the stash the last `forward` of this object left; `grad_a` (+ `grad_b`): d(loss)/d(features) [batch, F].  Every
+        gradient tensor of `grads` is overwritten."""
+        assert grad_a.numel() == self.batch * self.features and (grad_b is None or grad_b.numel() == grad_a.numel())
+        _call("gops_conv_backward", C.byref(self.conv), self.batch, _ptr(x), _ptr(grad_a), _ptr(grad_b), C.byref(grads), *_ws(self))
+
+
+class CnnNet:
+    """A convolution stack and one MLP per head on its features (gops/apprfunc/cnn.py): `RnnNet`'s surface.  `heads`: one `GopsMlp`
+    per head (`make_mlp`, input width F); `forward` returns [batch, sum of the head widths], head by head - for a StochaPolicy the
+    raw (mean, log std).  `grads` of `backward`: (GopsConvGrad, [(weight grads, bias grads) per head])."""
+
+    def __init__(self, conv: GopsConv, heads: Sequence[GopsMlp], batch: int, device: Optional[torch.device] = None):
+        self.batch = batch
+        self.stack = ConvStack(conv, batch, device)
+        self.device, F = self.stack.device, self.stack.features
+        if not 1 <= len(heads) <= 2 or any(int(m.sizes[0]) != F for m in heads):
+            raise RuntimeError(f"CnnNet: one or two heads of input width {F} (the stack's feature width)")
+        if any(lib().gops_mlp_workspace_bytes(C.byref(m), batch) == 0 for m in heads):   # before any launch
+            raise RuntimeError(f"CnnNet: gops_mlp_forward does not take this head (feature width {F}, widths "
+                               f"{[list(m.sizes)[1:m.n_layers + 1] for m in heads]})")
+        self.heads = [MlpNet(m, batch, self.device) for m in heads]
+        self.out_dim = sum(h.out_dim for h in self.heads)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        self._feat, self._gf = new(batch, F), [new(batch, F) for _ in heads]
+        # (one head writes the result and reads grad_y itself; two have their own rows, joined / cut by a strided copy)
+        self._y = [new(batch, h.out_dim) for h in self.heads] if len(heads) > 1 else None
+        self._gy = [new(batch, h.out_dim) for h in self.heads] if len(heads) > 1 else None
+
+    def set_descriptions(self, conv: GopsConv, heads: Sequence[GopsMlp]):
+        """The same net over parameter storage that moved."""
+        self.stack.conv = conv
+        for h, m in zip(self.heads, heads):
+            h.mlp = m
+
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`out`: a contiguous tensor of batch * out_dim floats that receives the result."""
+        y = torch.empty(self.batch, self.out_dim, dtype=torch.float32, device=self.device) if out is None else out
+        assert y.numel() == self.batch * self.out_dim
+        self.stack.forward(x, out=self._feat)
+        if self._y is None:
+            self.heads[0].forward(self._feat, out=y)
+            return y
+        off = 0
+        for h, yh in zip(self.heads, self._y):
+            y.view(self.batch, self.out_dim)[:, off:off + h.out_dim].copy_(h.forward(self._feat, out=yh))
+            off += h.out_dim
+        return y
+
+    def backward(self, x: torch.Tensor, grad_y: torch.Tensor, grads):
+        """From the stash the last `forward` of this object left: every gradient tensor of `grads` is overwritten."""
+        assert grad_y.numel() == self.batch * self.out_dim
+        conv_grad, head_grads = grads
+        off = 0
+        for i, (h, gf, (gw, gb)) in enumerate(zip(self.heads, self._gf, head_grads)):
+            gy = grad_y if self._gy is None else self._gy[i].copy_(grad_y.view(self.batch, self.out_dim)[:, off:off + h.out_dim])
+            h.backward_x(self._feat, gy, gw, gb, out=gf)
+            off += h.out_dim
+        self.stack.backward(x, self._gf[0], self._gf[1] if len(self.heads) > 1 else None, conv_grad)
 
 
 def env_step(env: GopsEnv, obs, action, done, info: Optional[Dict[str, torch.Tensor]] = None):

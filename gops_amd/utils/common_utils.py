@@ -25,7 +25,7 @@ def get_activation_func(key: str):
 
 def get_apprfunc_dict(key: str, **kwargs):
     """Collect the per-network constructor arguments `<key>_func_type`, `<key>_hidden_sizes`, ...
-    out of the flat args dict (the MLP, POLY, GAUSS, LipsNet and RNN families exist on this path)."""
+    out of the flat args dict (the MLP, POLY, GAUSS, LipsNet, RNN and CNN families exist on this path; CNN with `<key>_conv_type`)."""
     var = dict()
     var["apprfunc"] = kwargs[key + "_func_type"]
     var["name"] = kwargs[key + "_func_name"]
@@ -55,6 +55,10 @@ def get_apprfunc_dict(key: str, **kwargs):
         var["mlp_dtype"] = kwargs.get("mlp_dtype", "fp32")   # (the module refuses fp16 at construction)
     elif apprfunc_type == "RNN":   # gops_amd/apprfunc/rnn.py (reference common_utils.py:72-75); obsv_dim is the pair (L, O)
         var["hidden_sizes"] = kwargs[key + "_hidden_sizes"]
+        var["hidden_activation"] = kwargs[key + "_hidden_activation"]
+        var["output_activation"] = kwargs.get(key + "_output_activation", "linear")
+    elif apprfunc_type == "CNN" and key + "_conv_type" in kwargs:   # gops_amd/apprfunc/cnn.py (reference common_utils.py:76-80); obsv_dim is (C, H, W)
+        var["conv_type"] = kwargs[key + "_conv_type"]
         var["hidden_activation"] = kwargs[key + "_hidden_activation"]
         var["output_activation"] = kwargs.get(key + "_output_activation", "linear")
     else:

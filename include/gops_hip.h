@@ -1419,6 +1419,52 @@ int gops_rnn_forward(const GopsRnn* net, int32_t batch, const float* x, float* y
 int gops_rnn_backward(const GopsRnn* net, int32_t batch, const float* x, const float* grad_y, const GopsRnnGrad* grad, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): convolution stacks (gops/apprfunc/cnn.py: `self.conv`) - n_conv layers
+ * Conv2d(C_in, channels[l], kernel[l], stride[l]) without padding or dilation, each followed by ReLU (csrc/conv.hip):
+ *     x [B, in_channels, in_h, in_w] fp32 in torch layout  ->  features [B, F], F = channels[n - 1] x Ho x Wo of the last layer in
+ *     (C, H, W) order, i.e. `self.conv(x).view(B, -1)`
+ * weight[l] [channels[l], C_in, kernel[l], kernel[l]], bias[l] [channels[l]]: torch's nn.Conv2d layouts, read in place.  The heads are
+ * not part of the description: they read `features` through gops_mlp_forward / gops_mlp_backward_x.
+ *   gops_conv_forward:  one implicit-GEMM launch per layer on exact fp32 products (v_mfma_f32_16x16x4_f32); the inner activations are
+ *     stashed channels-last in the workspace, the features go to `features` and to the workspace.
+ *   gops_conv_backward: grad_features_a (+ grad_features_b unless NULL: a policy has two heads) [B, F] -> the gradient of every weight
+ *     and bias (overwritten), from the stash the forward of the SAME workspace left.  A data-gradient launch for each of layers
+ *     2 .. n in gather form, a weight-gradient launch per layer that leaves one partial per slice of the pixels, and their sum in
+ *     slice order - no float atomics: bitwise reproducible.  The input x gets no gradient.
+ * GOPS_ERR_BAD_ARG: a NULL pointer (grad_features_b excepted), batch < 1, n_conv < 1.  GOPS_ERR_UNSUPPORTED: n_conv >
+ *   GOPS_CONV_MAX_LAYERS, a kernel outside 1 .. GOPS_CONV_MAX_KERNEL, a stride outside 1 .. GOPS_CONV_MAX_STRIDE or above its kernel,
+ *   in_channels or channels[l] outside 1 .. GOPS_CONV_MAX_CHANNELS, in_h or in_w outside 1 .. GOPS_CONV_MAX_EXTENT, a layer whose input
+ *   is smaller than its kernel (an output extent of 0), batch x the largest per-sample tensor of 2^30 elements or more.
+ *   GOPS_ERR_WORKSPACE: a NULL workspace or workspace_bytes below gops_conv_workspace_bytes (0 for a description the entry points
+ *   reject).  Nothing is launched in any of these cases. */
+#define GOPS_CONV_MAX_LAYERS 6
+#define GOPS_CONV_MAX_KERNEL 8
+#define GOPS_CONV_MAX_STRIDE 4
+#define GOPS_CONV_MAX_CHANNELS 256
+#define GOPS_CONV_MAX_EXTENT 128
+struct GopsConv {
+    int32_t n_conv;
+    int32_t in_channels;
+    int32_t in_h;
+    int32_t in_w;
+    int32_t channels[GOPS_CONV_MAX_LAYERS];
+    int32_t kernel[GOPS_CONV_MAX_LAYERS];
+    int32_t stride[GOPS_CONV_MAX_LAYERS];
+    const float* weight[GOPS_CONV_MAX_LAYERS];   /* device pointers */
+    const float* bias[GOPS_CONV_MAX_LAYERS];
+};
+typedef struct GopsConv GopsConv;
+struct GopsConvGrad {
+    float* weight[GOPS_CONV_MAX_LAYERS];
+    float* bias[GOPS_CONV_MAX_LAYERS];
+};
+typedef struct GopsConvGrad GopsConvGrad;
+size_t gops_conv_workspace_bytes(const GopsConv* net, int32_t batch);
+int gops_conv_forward(const GopsConv* net, int32_t batch, const float* x, float* features, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int gops_conv_backward(const GopsConv* net, int32_t batch, const float* x, const float* grad_features_a, const float* grad_features_b,
+                       const GopsConvGrad* grad, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Timing hook for bench.py: average duration in ms of the named internal kernel over the
  * launches recorded since the last reset (HIP events on the launch stream).  kernel ids:
  * 0 = forward rollout, 1 = backward sweep, 2 = weight-gradient GEMMs (+ reduce) of gops_rollout_*;
