@@ -80,6 +80,9 @@ class WrappedEnvModel:
 
     def forward(self, obs: torch.Tensor, action: torch.Tensor, done: torch.Tensor, info: Dict
                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict]:
+        if getattr(self.model, "is_stack", False):
+            raise RuntimeError("gym_cartpolecontiwithstack is a data env stepped inside gops_stack_sample_rollout / _episode_rollout "
+                               "only: it has no env model (gops_env_step would step the flat cart-pole)")
         if not obs.is_cuda:
             raise RuntimeError("env_model.forward runs on the MI355X only (tensors must be on 'cuda'); "
                                "there is no CPU fallback in gops_amd")

@@ -72,6 +72,14 @@ __device__ __forceinline__ CartConst cart_const() {
     c.xth = 2.4f; c.thth = (float)(12 * 2 * 3.14159265358979323846 / 360);
     return c;
 }
+// gym_cartpolecontiwithstack (env_gym/gym_cartpolecontiwithstack.py:86-149): the same stepPhysics, thresholds, done rule and reward as
+// gym_cartpoleconti with ONE difference - force_mag = 30, not 10.  Its observation is the last `stack_length` states; the window is
+// kept by the caller (rollout_stack.hip), the step below is cart_forward on the newest one.
+__device__ __forceinline__ CartConst cart_stack_const() {
+    CartConst c = cart_const();
+    c.fmag = 30.f;
+    return c;
+}
 __device__ __forceinline__ void cart_forward(const CartConst& C, const float* x, float a, float* xn, float& r, bool& done) {
     float sth, cth;
     sincosf(x[2], &sth, &cth);

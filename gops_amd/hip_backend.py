@@ -233,6 +233,7 @@ class GopsPerGather(C.Structure):
 
 
 RNN_MAX_SEQ, RNN_MAX_HEADS, RNN_MAX_OBS, RNN_MAX_HIDDEN, RNN_MAX_OUT = 32, 2, 64, 128, 16   # include/gops_hip.h: GOPS_RNN_*
+STACK_MAX_LEN = 8   # include/gops_hip.h: GOPS_STACK_MAX_LEN (the windows of gops_stack_sample_rollout / _episode_rollout)
 
 
 class GopsRnn(C.Structure):   # gops_rnn_forward / _backward
@@ -356,6 +357,11 @@ def _signatures():
         "gops_rnn_workspace_bytes": (sz, [P(GopsRnn), i32]),
         "gops_rnn_forward": (rc, [P(GopsRnn), i32, vp, vp, vp, sz, vp]),
         "gops_rnn_backward": (rc, [P(GopsRnn), i32, vp, vp, P(GopsRnnGrad), vp, sz, vp]),
+        "gops_stack_sample_workspace_bytes": (sz, [env, P(GopsRnn), i32, i32]),
+        "gops_stack_sample_rollout": (rc, [env, P(GopsRnn), P(GopsSampleDesc), i32, i32, P(GopsSampleState), P(GopsSamplePool), vp,
+                                           P(GopsSampleOut), vp, sz, vp]),
+        "gops_stack_episode_workspace_bytes": (sz, [env, P(GopsRnn), i32, i32]),
+        "gops_stack_episode_rollout": (rc, [env, P(GopsRnn), i32, i32, vp, P(GopsEpisodeOut), vp, sz, vp]),
         "gops_conv_workspace_bytes": (sz, [P(GopsConv), i32]),
         "gops_conv_forward": (rc, [P(GopsConv), i32, vp, vp, vp, sz, vp]),
         "gops_conv_backward": (rc, [P(GopsConv), i32, vp, vp, vp, P(GopsConvGrad), vp, sz, vp]),
@@ -1347,6 +1353,89 @@ class SampleRollout:
         _call(self._name, C.byref(self.env), C.byref(self.policy), C.byref(self.desc), *self._extra, N, T, C.byref(st), C.byref(pl),
               _ptr(noise), C.byref(self._out), *_ws(self))
         return self.out
+
+
+STACK_ROW = 4   # floats of one row of gym_cartpolecontiwithstack's window: the cart-pole's state
+
+
+class StackSampleRollout:
+    """A whole `sample()` on gym_cartpolecontiwithstack under a recurrent StochaPolicy in ONE launch (`gops_stack_sample_rollout`,
+    csrc/rollout_stack.hip): `SampleRollout`'s surface with `policy` a two-head `GopsRnn` whose `seq_len` is the stack length L.
+    `env` describes one row of the window (ENV_CARTPOLE, data_env = 1).  `run` returns VIEWS of buffers the next `run` overwrites;
+    obs / obs2 are [steps, n_envs, L, 4].  A description the kernel refuses raises."""
+
+    def __init__(self, env: GopsEnv, policy: GopsRnn, *, n_envs: int, steps: int, max_episode_steps: int, pool_rows: int,
+                 min_log_std: float, max_log_std: float, device: Optional[torch.device] = None):
+        self.env, self.policy, self.n_envs, self.steps = env, policy, int(n_envs), int(steps)
+        self.desc = GopsSampleDesc(head=SAMPLE_GAUSS, max_episode_steps=int(max_episode_steps), pool_rows=int(pool_rows), reserved=0,
+                                   noise_std=0.0, min_log_std=float(min_log_std), max_log_std=float(max_log_std))
+        self.noise_width = 1
+        _own_workspace(self, StackSampleRollout.workspace_bytes(env, policy, n_envs=n_envs, steps=steps), device,
+                       "gops_stack_sample_workspace_bytes: description refused")
+        T, N, L = self.steps, self.n_envs, int(policy.seq_len)
+        mk = lambda *sh: torch.empty((T, N) + tuple(sh), dtype=torch.float32, device=self.device)   # noqa: E731
+        self.out = dict(obs=mk(L, STACK_ROW), act=mk(1), rew=mk(), done=mk(), obs2=mk(L, STACK_ROW), logp=mk(), time_limited=mk(), end=mk())
+        self._out = GopsSampleOut()
+        for k, v in self.out.items():
+            setattr(self._out, k, v.data_ptr())
+
+    @staticmethod
+    def workspace_bytes(env: GopsEnv, policy: GopsRnn, *, n_envs: int, steps: int) -> int:
+        """What the library's query answers for this description: 0 = it refuses it."""
+        return lib().gops_stack_sample_workspace_bytes(C.byref(env), C.byref(policy), int(n_envs), int(steps))
+
+    def set_policy(self, policy: GopsRnn):
+        self.policy = policy
+
+    def run(self, state: Dict[str, torch.Tensor], pool: Dict[str, torch.Tensor], noise: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """`state`: obs [N, L, 4] (the windows), t [N] and reset_count [N] (int32) - advanced IN PLACE; `pool`: obs [R, N, 4] reset
+        states; `noise` [T, N, 1] standard normals.  Returns the output buffers ([T, N, ...] each).  Enqueues only."""
+        T, N, R, L = self.steps, self.n_envs, self.desc.pool_rows, int(self.policy.seq_len)
+        assert tuple(noise.shape) == (T, N, 1) and tuple(state["obs"].shape) == (N, L, STACK_ROW)
+        assert tuple(pool["obs"].shape) == (R, N, STACK_ROW)
+        st, pl = GopsSampleState(obs=_ptr(state["obs"])), GopsSamplePool(obs=_ptr(pool["obs"]))
+        for k in ("t", "reset_count"):
+            v = state[k]
+            assert v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.numel() == N, k
+            setattr(st, k, v.data_ptr())
+        _call("gops_stack_sample_rollout", C.byref(self.env), C.byref(self.policy), C.byref(self.desc), N, T, C.byref(st), C.byref(pl),
+              _ptr(noise), C.byref(self._out), *_ws(self))
+        return self.out
+
+
+class StackEpisodeRollout:
+    """All evaluation episodes on gym_cartpolecontiwithstack under a recurrent StochaPolicy in ONE launch
+    (`gops_stack_episode_rollout`): `EpisodeRollout`'s surface for the mode head of a GaussDistribution, a = clamp(mean, act_low,
+    act_high) with the limits `env` carries (policy_low / policy_high)."""
+
+    def __init__(self, env: GopsEnv, policy: GopsRnn, *, episodes: int, max_steps: int, device: Optional[torch.device] = None):
+        self.env, self.policy, self.episodes, self.max_steps = env, policy, int(episodes), int(max_steps)
+        _own_workspace(self, StackEpisodeRollout.workspace_bytes(env, policy, episodes=episodes, max_steps=max_steps), device,
+                       "gops_stack_episode_workspace_bytes: description refused")
+
+    @staticmethod
+    def workspace_bytes(env: GopsEnv, policy: GopsRnn, *, episodes: int, max_steps: int) -> int:
+        return lib().gops_stack_episode_workspace_bytes(C.byref(env), C.byref(policy), int(episodes), int(max_steps))
+
+    def set_policy(self, policy: GopsRnn):
+        self.policy = policy
+
+    def run(self, init: Dict[str, torch.Tensor], *, trace: bool = False, trace_fill: Optional[float] = None) -> Dict[str, torch.Tensor]:
+        """`init`: obs [E, 4], the state every row of an episode's first window holds.  Returns device tensors ret [E], length [E]
+        (int32), terminated [E] and - with `trace` - trace_obs [E, T, L, 4], trace_act [E, T, 1], trace_rew [E, T].  Enqueues only."""
+        E, T, L, dev = self.episodes, self.max_steps, int(self.policy.seq_len), self.device
+        assert tuple(init["obs"].shape) == (E, STACK_ROW)
+        out = GopsEpisodeOut()
+        res = dict(ret=torch.empty(E, dtype=torch.float32, device=dev), length=torch.empty(E, dtype=torch.int32, device=dev),
+                   terminated=torch.empty(E, dtype=torch.float32, device=dev))
+        if trace:
+            mk = (lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)) if trace_fill is None else \
+                 (lambda *sh: torch.full(sh, float(trace_fill), dtype=torch.float32, device=dev))
+            res.update(trace_obs=mk(E, T, L, STACK_ROW), trace_act=mk(E, T, 1), trace_rew=mk(E, T))
+        for k, v in res.items():
+            setattr(out, k, v.data_ptr())
+        _call("gops_stack_episode_rollout", C.byref(self.env), C.byref(self.policy), E, T, _ptr(init["obs"]), C.byref(out), *_ws(self))
+        return res
 
 
 class PerBuffer:

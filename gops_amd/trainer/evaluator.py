@@ -31,6 +31,7 @@ import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm.base import is_poly
+from gops_amd.apprfunc import rnn as rnn_nets
 from gops_amd.apprfunc.mlp import ActionValueDis, StochaPolicy, StochaPolicyDis
 from gops_amd.trainer.closed_loop import ClosedLoopDriver
 from gops_amd.trainer.sampler.reset_pool import INFO_KEYS, NOT_RESTATED, draw_reset_pool
@@ -73,10 +74,12 @@ class Evaluator(ClosedLoopDriver):
             raise NotImplementedError("Evaluator runs closed loops with continuous actions only: an ActionValueDis policy (DQN) emits "
                                       "action values over a discrete action set, and no action table is part of the evaluator")
         self.stochastic_mode = bool(stochastic_mode)
-        if self.stochastic_mode and (self.action_table is not None or not isinstance(self._policy_module(), StochaPolicy)):
+        if self.stochastic_mode and (self.action_table is not None or not isinstance(self._policy_module(), (StochaPolicy, rnn_nets.StochaPolicy))):
             raise ValueError("Evaluator: stochastic_mode=True evaluates a StochaPolicy by the mode of its action distribution; it goes "
                              "with neither an action table nor a deterministic policy")
         base = getattr(env_model, "unwrapped", env_model)
+        # gym_cartpolecontiwithstack: windows of L states under a recurrent StochaPolicy, in `gops_stack_episode_rollout` only
+        self.stack_length = getattr(base, "stack_length", None)
         if getattr(base, "ref_c", None) is not None:
             raise RuntimeError("Evaluator draws its initial states from the DEFAULT reference trajectories "
                                "(gops_amd.utils.synthetic); a model with custom path_para / u_para needs explicit initial conditions")
@@ -124,6 +127,14 @@ class Evaluator(ClosedLoopDriver):
         """None when `gops_episode_rollout` (`_dis` with an action table, `_mode` with `stochastic_mode`) takes this evaluator's env
         and policy, else the reason."""
         pol = self._policy_module()
+        if self.stack_length:
+            if not isinstance(pol, rnn_nets.StochaPolicy) or pol.action_distribution_cls is not GaussDistribution:
+                return "gym_cartpolecontiwithstack takes a recurrent StochaPolicy (RNN) with a GaussDistribution"
+            if not self.stochastic_mode:
+                return "stochastic policy"
+            if hb.StackEpisodeRollout.workspace_bytes(self._hip_env(), pol.hip_rnn(self.stack_length), episodes=1, max_steps=1) == 0:
+                return "env / policy description outside the stack kernel (widths beyond GOPS_RNN_*, stack_length)"
+            return None
         if is_poly(pol):
             return "POLY policy"
         if getattr(pol, "is_lipsnet", False):
@@ -160,6 +171,19 @@ class Evaluator(ClosedLoopDriver):
         - with `trace` - trace_obs / trace_act / trace_rew.  Device tensors; nothing is read back here."""
         init = {k: v.to(self.device, torch.float32).contiguous() for k, v in init.items() if k == "obs" or k in INFO_KEYS}
         fused = self.fused if fused is None else fused
+        if self.stack_length:   # no per-step loop steps the stacked env: the one-launch path or nothing
+            if not self._set_path(self.kernel_refuses() if fused else "fused=False"):
+                raise RuntimeError("gym_cartpolecontiwithstack is evaluated by the fused path only (" + self.path + ")")
+            self.path = "fused: gops_stack_episode_rollout"
+            E, desc = init["obs"].shape[0], self._policy_module().hip_rnn(self.stack_length)
+            key = (E, self.max_episode_steps, "stack")
+            ro = self._rollouts.get(key)
+            if ro is None:
+                ro = self._rollouts[key] = hb.StackEpisodeRollout(self._hip_env(), desc, episodes=E, max_steps=self.max_episode_steps,
+                                                                  device=self.device)
+            ro.set_policy(desc)
+            self.last = ro.run(init, trace=trace, trace_fill=trace_fill)
+            return self.last
         if self._set_path(self.kernel_refuses() if fused else "fused=False"):
             E = init["obs"].shape[0]
             mlp = self._policy_module().hip_mlp()

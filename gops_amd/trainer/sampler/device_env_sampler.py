@@ -82,6 +82,11 @@ class DeviceEnvSampler(ClosedLoopDriver):
         self._henv = None
         first = self._draw(self.n)
         self.obs = first["obs"]
+        # gym_cartpolecontiwithstack: the observation is the window of the last L states [N, L, 4] - a reset fills every row -, the
+        # pool holds states; only the fused path steps it (`gops_stack_sample_rollout`, under a recurrent StochaPolicy)
+        self.stack_length = getattr(getattr(env_model, "unwrapped", env_model), "stack_length", None)
+        if self.stack_length:
+            self.obs = self.obs.unsqueeze(1).repeat(1, self.stack_length, 1).contiguous()
         self.info = {k: first[k] for k in _INFO if k in first}
         self.t = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self.fused = bool(fused)
@@ -171,6 +176,8 @@ class DeviceEnvSampler(ClosedLoopDriver):
     def kernel_refuses(self):
         """None when `gops_sample_rollout` takes this sampler's env and policy, else the reason."""
         policy = self._policy_module()
+        if self.stack_length:
+            return self._stack_kernel_refuses(policy)
         if self.action_table is not None:
             if not isinstance(policy, ActionValueDis):   # (StochaPolicyDis is one)
                 return "action table (discrete actions) behind a policy that is neither an ActionValueDis nor a StochaPolicyDis"
@@ -198,6 +205,17 @@ class DeviceEnvSampler(ClosedLoopDriver):
             # gops_hip.h lists them: the constrained vehicle models, ActionRepeat, scaled vehicle observations, hidden widths that are
             # no multiple of 16 or beyond the LDS plan, more than GOPS_MAX_ACT actions
             return "env / policy description outside the sample kernel (constrained model, ActionRepeat, hidden widths)"
+        return None
+
+    def _stack_kernel_refuses(self, policy):
+        """The same answer for `gops_stack_sample_rollout`: a recurrent StochaPolicy with a GaussDistribution over windows of
+        `stack_length` states."""
+        if self.action_table is not None or not getattr(policy, "is_rnn", False) or tuple(getattr(policy, "_heads", ())) != ("mean", "log_std"):
+            return "gym_cartpolecontiwithstack takes a recurrent StochaPolicy (RNN) without an action table"
+        if policy.action_distribution_cls is not GaussDistribution:
+            return "action distribution outside the stack kernel's head (GaussDistribution)"
+        if hb.StackSampleRollout.workspace_bytes(self._hip_env(), policy.hip_rnn(self.stack_length), n_envs=self.n, steps=self.steps) == 0:
+            return "env / policy description outside the stack kernel (wrappers, widths beyond GOPS_RNN_*, stack_length)"
         return None
 
     def _draw_fused_pool(self):
@@ -239,14 +257,22 @@ class DeviceEnvSampler(ClosedLoopDriver):
             self._fpool = None
         if self._fpool is None:
             self._draw_fused_pool()
-        head, draw, keywords = self._fused_head(policy)
-        if self._frollout is None or (self._frollout.n_envs, self._frollout.steps) != (N, T):
-            self._frollout = hb.SampleRollout(self._hip_env(), policy.hip_mlp(), n_envs=N, steps=T, head=head, max_episode_steps=self.max_steps,
-                                              pool_rows=R, info_like=self.info, device=self.device, **keywords)
+        rebuild = self._frollout is None or (self._frollout.n_envs, self._frollout.steps) != (N, T)
+        if self.stack_length:
+            desc, draw = policy.hip_rnn(self.stack_length), torch.randn
+            if rebuild:
+                self._frollout = hb.StackSampleRollout(self._hip_env(), desc, n_envs=N, steps=T, max_episode_steps=self.max_steps, pool_rows=R,
+                                                       min_log_std=policy.min_log_std, max_log_std=policy.max_log_std, device=self.device)
+        else:
+            head, draw, keywords = self._fused_head(policy)
+            desc = policy.hip_mlp()
+            if rebuild:
+                self._frollout = hb.SampleRollout(self._hip_env(), desc, n_envs=N, steps=T, head=head, max_episode_steps=self.max_steps,
+                                                  pool_rows=R, info_like=self.info, device=self.device, **keywords)
         ro = self._frollout
-        ro.set_policy(policy.hip_mlp())
+        ro.set_policy(desc)
         ro.desc.max_episode_steps = int(self.max_steps)
-        if ro.dis is not None:   # (read at every call, as max_episode_steps is: DQN anneals it)
+        if getattr(ro, "dis", None) is not None:   # (read at every call, as max_episode_steps is: DQN anneals it)
             ro.dis.epsilon = float(self.epsilon)
         noise = draw((T, N, ro.noise_width), generator=self._gen, device=self.device)
         out = ro.run(st, self._fpool, noise)
@@ -260,7 +286,12 @@ class DeviceEnvSampler(ClosedLoopDriver):
         return {k: out[k].flatten(0, 1) for k in keys}
 
     def _choose_path(self) -> bool:
-        return self._set_path(self.kernel_refuses() if self.fused else "fused=False")
+        fused = self._set_path(self.kernel_refuses() if self.fused else "fused=False")
+        if self.stack_length:   # no per-step loop steps the stacked env: the one-launch path or nothing
+            if not fused:
+                raise RuntimeError("gym_cartpolecontiwithstack is sampled by the fused path only (" + self.path + ")")
+            self.path = "fused: gops_stack_sample_rollout"
+        return fused
 
     @torch.no_grad()
     def sample(self):

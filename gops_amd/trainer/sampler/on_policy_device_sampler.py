@@ -27,7 +27,14 @@ class OnPolicyDeviceSampler(DeviceEnvSampler):
 
     def _values(self, obs: torch.Tensor) -> torch.Tensor:
         """value(obs) [rows] through `gops_mlp_forward` (every call has T N rows)."""
-        mlp = self.networks.value.hip_mlp()
+        value = self.networks.value
+        if getattr(value, "is_rnn", False):   # windows [rows, L, O] through gops_rnn_forward
+            desc = value.hip_rnn(obs.shape[1])
+            if not isinstance(self._value_net, hb.RnnNet) or self._value_net.batch != obs.shape[0]:
+                self._value_net = hb.RnnNet(desc, obs.shape[0], device=self.device)
+            self._value_net.rnn = desc
+            return self._value_net.forward(obs).view(-1)
+        mlp = value.hip_mlp()
         if self._value_net is None or self._value_net.batch != obs.shape[0]:
             self._value_net = hb.MlpNet(mlp, obs.shape[0], device=self.device)
         else:

@@ -9,7 +9,7 @@ INFO_KEYS = ("state", "ref_points", "path_num", "u_num", "ref_time")
 
 NOT_RESTATED = ("the DATA environment of {env_id} is not restated in the step kernel "
                 "(pyth_lq, pyth_idpendulum, pyth_veh3dofconti, pyth_veh2dofconti, pyth_mobilerobot and "
-                "gym_cartpoleconti are): pass env_step='model'")
+                "gym_cartpoleconti are; gym_cartpolecontiwithstack inside the fused stack kernels): pass env_step='model'")
 
 
 def pool_row(reset_count, pool_rows: int):
@@ -74,6 +74,7 @@ def restate_discrete_head(values, u, head: int, epsilon: float = 0.0):
 
 
 SURR_ENV_ID = "pyth_veh3dofconti_surrcstr"
+STACK_ENV_ID, STACK_RESET_HALF_RANGE = "gym_cartpolecontiwithstack", (2.0, 0.05, 0.2, 0.05)
 SURR_WHEELBASE, CIRCLE_RADIUS = 3.0, 100.0   # SurrVehicleData.l; the default circle path's radius (utils/synthetic.py: ref_points_f64)
 
 
@@ -111,6 +112,11 @@ def draw_surr_vehicles(host: dict, n_surr: int, rng) -> dict:
 
 def draw_reset_pool(cfg: dict, env_model, seed: int, size: int, device, data_env: bool = True) -> dict:
     """`size` initial conditions (device tensors: obs + the info keys the model carries) of `cfg["env_id"]` for `seed`."""
+    if cfg["env_id"] == STACK_ENV_ID:
+        # reset() of env_gym/gym_cartpolecontiwithstack.py:151-158: one state, uniform in +-[2, 0.05, 0.2, 0.05]; it fills every row
+        # of the window (the kernels and the sampler repeat it: the pool holds STATES, [size, 4])
+        h = np.array(STACK_RESET_HALF_RANGE)
+        return dict(obs=torch.from_numpy(np.random.RandomState(seed).uniform(-h, h, size=(size, 4)).astype(np.float32)).to(device))
     host = make_batch(cfg, seed, batch=size)
     if cfg["env_id"] == "pyth_mobilerobot" and data_env:
         # the data env's own reset distribution (pyth_mobilerobot.py:31-54, 95-106: robot and obstacle uniform in the work

@@ -1419,6 +1419,40 @@ int gops_rnn_forward(const GopsRnn* net, int32_t batch, const float* x, float* y
 int gops_rnn_backward(const GopsRnn* net, int32_t batch, const float* x, const float* grad_y, const GopsRnnGrad* grad, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): the closed loops of gops_sample_rollout and
+ * gops_episode_rollout_mode on gym_cartpolecontiwithstack (gops/env/env_gym/gym_cartpolecontiwithstack.py) under a RECURRENT
+ * StochaPolicy - a GopsRnn with two heads, mean and raw log std, one output each (csrc/rollout_stack.hip).  The observation is the
+ * window of the last L = policy->seq_len states [L][4], oldest first; a reset fills all L rows with the initial state, a step drops
+ * the oldest row and appends the new state.  `env` describes ONE row: kind GOPS_ENV_CARTPOLE, obs_dim 4, act_dim 1, data_env 1.
+ * Under these entry points the description is stepped as the stacked env: gym_cartpoleconti's data-env step (reward 1 also for the
+ * step that ends the episode, done on the next state) with force_mag = 30 instead of 10 - the one difference between the two envs;
+ * the action passes the description's ScaleAction / ClipAction range as gops_env_step takes it.
+ *   gops_stack_sample_rollout: gops_sample_rollout's conventions - state (read and written: obs [N, L, 4] the windows, t,
+ *     reset_count), pool (obs [R, N, 4]: reset STATES, one row each), noise [T, N, 1], out time-major (obs and obs2 [T, N, L, 4], act,
+ *     rew, done, logp, time_limited, end); the info fields of the three structs are ignored.  desc->head must be GOPS_SAMPLE_GAUSS:
+ *     act = mean + exp(clamp(raw log std)) noise and its log-probability, formed in double and rounded once; noise_std is ignored.
+ *     Per step the books are gops_sample_rollout's, word for word; consecutive calls continue the same episodes.
+ *   gops_stack_episode_rollout: gops_episode_rollout_mode's books with GaussDistribution.mode, a = clamp(mean, env->policy_low,
+ *     env->policy_high) - the mean head alone is evaluated.  init_state [E, 4]: the state every row of an episode's first window
+ *     holds.  trace_obs is [E][max_steps][L][4], trace_act and trace_rew [E][max_steps] (optional).
+ * One launch each: a workgroup owns GOPS_TILE instances for all steps, W_ih / W_hh stay in registers for the whole launch, the input
+ * projection of a state is computed once and kept in LDS while the state is in the window; the floating-point order of the policy is
+ * gops_rnn_forward's, so (mean, raw log std) equal its outputs on the same window bit for bit.  No atomics: equal inputs give equal bits.
+ * GOPS_ERR_BAD_ARG: a NULL pointer, n_envs / episodes / steps < 1, data_env = 0, obs_dim != 4 or act_dim != 1 (env or policy),
+ *   n_heads != 2, a head whose output width is not 1, pool_rows or max_episode_steps < 1, an unknown head, and gops_rnn_forward's
+ *   cases.  GOPS_ERR_UNSUPPORTED: any env kind but GOPS_ENV_CARTPOLE, ActionRepeat / ScaleObservation / ShapingReward, seq_len >
+ *   GOPS_STACK_MAX_LEN, the heads GOPS_SAMPLE_DETERM / _TANH_GAUSS, and gops_rnn_forward's cases (the GOPS_RNN_* limits).
+ *   GOPS_ERR_WORKSPACE: a NULL workspace or workspace_bytes < GOPS_SAMPLE_WORKSPACE_BYTES (reserved, as for gops_sample_rollout).
+ *   Nothing is launched in any of these cases; the workspace queries return 0 for a description the entry points reject. */
+#define GOPS_STACK_MAX_LEN 8
+size_t gops_stack_sample_workspace_bytes(const GopsEnv* env, const GopsRnn* policy, int32_t n_envs, int32_t steps);
+int gops_stack_sample_rollout(const GopsEnv* env, const GopsRnn* policy, const GopsSampleDesc* desc, int32_t n_envs, int32_t steps,
+                              const GopsSampleState* state, const GopsSamplePool* pool, const float* noise, const GopsSampleOut* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t gops_stack_episode_workspace_bytes(const GopsEnv* env, const GopsRnn* policy, int32_t episodes, int32_t max_steps);
+int gops_stack_episode_rollout(const GopsEnv* env, const GopsRnn* policy, int32_t episodes, int32_t max_steps, const float* init_state,
+                               const GopsEpisodeOut* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ABI v15, additive entry points (the version number stays 15): convolution stacks (gops/apprfunc/cnn.py: `self.conv`) - n_conv layers
  * Conv2d(C_in, channels[l], kernel[l], stride[l]) without padding or dilation, each followed by ReLU (csrc/conv.hip):
  *     x [B, in_channels, in_h, in_w] fp32 in torch layout  ->  features [B, F], F = channels[n - 1] x Ho x Wo of the last layer in
