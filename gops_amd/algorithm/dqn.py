@@ -17,6 +17,13 @@ The `act` column is the action index as a float, converted by truncation as the 
 lies outside [0, act_num) would make the reference's `gather` raise; a kernel cannot raise: such a row gets a zero seed and `abs_err` 0,
 adds nothing to the loss, and is counted - `bad_action_rows()` reads the count of the last update.
 
+With `value_func_type="RNN"` (gops_amd/apprfunc/rnn.py: `obsv_dim` is the pair (L, O), the batch's `obs` / `obs2` are stacks [B, L, O])
+the live network is an Elman recurrence with an MLP head, and the step up to the backward is ONE launch of `gops_rnn_dqn_step`
+(csrc/rnn_dqn.hip, `fused_target=True` or "force": wherever the kernel holds the pair): the target recurrence on
+obs2, the online recurrence on obs with `gops_rnn_forward`'s stash, and the seam - maximum, backup, seed, loss, |q_sel - backup| - on
+the 16-row tile both share; `gops_rnn_backward` follows from that stash.  Composed (`fused_target=False`): target
+`gops_rnn_forward`, `torch.max`, online `gops_rnn_forward`, `gops_dqn_loss`, the same backward.  Adam, Polyak and the graph as below.
+
 Prioritized replay: the reference's PER path reads `self.networks.target` (dqn.py:149), an attribute that does not exist - it raises.
 Here the evident intent is implemented: the backup from `q_target`, the importance-weighted loss `mean(w (q_sel - backup)^2)`, and
 `local_update` returns `(tb_info, idx, |q_sel - backup|)` like DDPG / TD3.  This path has no reference fixture: it is pinned by the
@@ -28,11 +35,13 @@ import time
 from copy import deepcopy
 from typing import Tuple
 
+import numpy as np
 import torch
 
 from gops_amd import hip_backend as hb
 from gops_amd.algorithm._actor_critic import FUSED_MAX_WIDTH, NetCache
-from gops_amd.algorithm.base import AlgorithmBase, ApprBase, batch_to_device, cuda_device_of, grad_buffers, install_grads
+from gops_amd.algorithm.base import AlgorithmBase, ApprBase, _flat_grads, batch_to_device, cuda_device_of, grad_buffers, install_grads
+from gops_amd.apprfunc import rnn
 from gops_amd.apprfunc.mlp import ActionValueDis
 from gops_amd.create_pkg.create_apprfunc import create_apprfunc
 from gops_amd.utils.common_utils import get_apprfunc_dict, make_adam
@@ -43,13 +52,37 @@ from gops_amd.utils.tensorboard_setup import tb_tags
 # `fused_target=True` keeps DDPG / TD3's threshold `FUSED_MAX_WIDTH` (64): DQN's own measurement has the same crossover (DESIGN.md
 # 4.17: update, ms fused / composed, graph replay: 64-64 nets 0.082 / 0.097 at B = 256 and 0.271 / 0.293 at B = 65536; 256-256 nets
 # 0.206 / 0.142 and 1.39 / 0.638).
+# Recurrent networks: `fused_target=True` runs `gops_rnn_dqn_step` wherever the kernel holds the pair - no width or batch rule: the
+# fused update was the faster one at every measured shape, from B = 64, H = 64 to B = 4096, L = 32, H = 128.
 MANDATORY = ("value_learning_rate", "buffer_name")   # what the reference indexes (dqn.py:58,80): a KeyError without them
 N_SCALARS = 4   # loss_q, mean(q_sel), rows with an index out of range, (spare): the head of the update's output vector, PER's abs_err behind it
 
 
+def rnn_refusal(kwargs: dict):
+    """Why `create_alg` cannot build DQN on a recurrent ActionValueDis (`gops_rnn_dqn_step`, `gops_rnn_forward / _backward`), or None."""
+    shape = kwargs.get("obsv_dim")
+    if not (isinstance(shape, (tuple, list)) and len(shape) == 2 and all(isinstance(v, (int, np.integer)) for v in shape)):
+        return f"DQN with an RNN value network takes obsv_dim as the pair (L, O) of a stack of L observations, not {shape!r}"
+    if not 1 <= shape[0] <= hb.RNN_MAX_SEQ or not 1 <= shape[1] <= hb.RNN_MAX_OBS:
+        return (f"DQN with an RNN value network: obsv_dim {tuple(shape)!r} is outside the recurrent kernels' range (L in 1 .. "
+                f"{hb.RNN_MAX_SEQ}, O in 1 .. {hb.RNN_MAX_OBS})")
+    sizes = list(kwargs.get("value_hidden_sizes") or [])
+    if not 1 <= len(sizes) <= hb.MAX_LAYERS or any(w % 16 or not 16 <= w <= hb.RNN_MAX_HIDDEN for w in sizes):
+        return (f"DQN with an RNN value network: value_hidden_sizes {sizes!r} - the recurrent kernels hold 1 .. {hb.MAX_LAYERS} widths (the "
+                f"recurrence's, then the head's hidden layers), each a multiple of 16 in 16 .. {hb.RNN_MAX_HIDDEN}")
+    n = kwargs.get("action_num")
+    if not isinstance(n, (int, np.integer)) or not 2 <= n <= hb.DQN_MAX_ACTIONS:
+        return f"DQN with an RNN value network takes 2 .. {hb.DQN_MAX_ACTIONS} discrete actions (action_num {n!r}): the head of its kernels holds no other width"
+    return None
+
+
 def refusal(kwargs: dict):
     """Why `create_alg` cannot build DQN from these arguments, or None."""
-    if kwargs.get("value_func_type") != "MLP":
+    if kwargs.get("value_func_type") == "RNN":
+        reason = rnn_refusal(kwargs)
+        if reason is not None:
+            return reason
+    elif kwargs.get("value_func_type") != "MLP":
         return f"DQN runs an MLP value network only (value_func_type {kwargs.get('value_func_type')!r})"
     if kwargs.get("value_func_name") != "ActionValueDis":
         return (f"DQN takes the action values of a discrete action space (value_func_name 'ActionValueDis'), not "
@@ -102,8 +135,8 @@ class DQN(NetCache, AlgorithmBase):
         self.tau = 0.005
         self.reward_scale = 1
         self.networks = ApproxContainer(**kwargs)
-        if type(self.networks.q) is not ActionValueDis:
-            raise NotImplementedError(f"DQN: value network {type(self.networks.q).__name__} (MLP ActionValueDis only)")
+        if type(self.networks.q) not in (ActionValueDis, rnn.ActionValueDis):
+            raise NotImplementedError(f"DQN: value network {type(self.networks.q).__name__} (MLP or RNN ActionValueDis only)")
         self.per_flag = kwargs["buffer_name"] == "prioritized_replay_buffer"
         self.fused_target = "force" if fused_target == "force" else bool(fused_target)
         self.backup_path = None   # "fused" / "composed": how the last update formed the backup
@@ -165,7 +198,8 @@ class DQN(NetCache, AlgorithmBase):
                 float(self.reward_scale),
                 tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for m in (nets.q, nets.q_target) for p in m.parameters()),
                 nets.q_optimizer.storage_signature(),
-                tuple(sorted(obj.workspace.data_ptr() for obj in self._cache.values() if hasattr(obj, "workspace"))),
+                tuple(sorted(getattr(obj, name).data_ptr() for obj in self._cache.values() for name in ("workspace", "stats")
+                             if hasattr(obj, name))),
                 tuple(sorted(t.data_ptr() for t in self._bufs.values())))
 
     def _update(self):
@@ -212,6 +246,8 @@ class DQN(NetCache, AlgorithmBase):
         """Enqueue one compute_gradient; returns [loss_q, mean(q_sel), rows with an index out of range, 0] (+ abs_err [B] with PER)
         as one device tensor, without synchronising."""
         nets = self.networks
+        if getattr(nets.q, "is_rnn", False):
+            return self._rnn_gradient_kernels(batch)
         o = batch["obs"]
         B, device = o.shape[0], o.device
         N = nets.q.act_num
@@ -226,5 +262,64 @@ class DQN(NetCache, AlgorithmBase):
                                       seed=self._buf("seed", (B, N), device), abs_err=self._buf("abs_err", (B,), device))
         gw, gb = grad_buffers(nets.q)
         net.backward(o, seed, gw, gb)
+        head = torch.cat([stats, stats[:1] * 0])
+        return torch.cat([head, abs_err]) if self.per_flag else head
+
+    # ---- recurrent networks ----------------------------------------------------------------------
+    def _rnn_net(self, role: str, module, x: torch.Tensor) -> hb.RnnNet:
+        """One RnnNet (own stash) per use of a recurrent network inside an update, for stacks of `x`'s shape."""
+        B, L, device = x.shape[0], x.shape[1], x.device
+        key = (role, B, L, str(device))
+        desc = module.hip_rnn(L)
+        net = self._cache.get(key)
+        if net is None:
+            net = self._cache[key] = hb.RnnNet(desc, B, device=device)
+        else:
+            net.rnn = desc
+        return net
+
+    def _rnn_step(self, net: hb.RnnNet, x: torch.Tensor):
+        """The `RnnDqnStep` that stashes into `net`'s workspace, or None where `fused_target` or the kernel leaves the step composed."""
+        nets = self.networks
+        B, L = x.shape[0], x.shape[1]
+        if not self.fused_target:
+            return None
+        q, target = nets.q.hip_rnn(L), nets.q_target.hip_rnn(L)
+        key = ("rnn_dqn_step", B, L, str(x.device))
+        step = self._cache.get(key)
+        if step is None:
+            step = self._cache[key] = hb.RnnDqnStep(q, target, B, device=x.device, net=net)
+        else:
+            step.set_nets(q, target)
+        return step if step.supported else None
+
+    def _rnn_gradient_kernels(self, batch) -> torch.Tensor:
+        """`_gradient_kernels` on recurrent networks: one `gops_rnn_dqn_step` (or its four composed launches), then BPTT."""
+        nets = self.networks
+        o, o2 = batch["obs"], batch["obs2"]
+        B, device, N = o.shape[0], o.device, nets.q.act_num
+        act, weight = batch["act"].reshape(-1), batch.get("weight") if self.per_flag else None
+        net = self._rnn_net("q@data", nets.q, o)
+        q_all, seed, abs_err = self._buf("q_all", (B, N), device), self._buf("seed", (B, N), device), self._buf("abs_err", (B,), device)
+        step = self._rnn_step(net, o)
+        if step is not None:
+            self.backup_path = "fused"
+            a_star = self._bufs.get(("a_star", B, str(device)))
+            if a_star is None:
+                a_star = self._bufs[("a_star", B, str(device))] = torch.empty(B, dtype=torch.int32, device=device)
+            stats = step.run(o, o2, act, batch["rew"], batch["done"], weight, reward_scale=self.reward_scale, gamma=self.gamma,
+                             out=dict(q_all=q_all, seed=seed, abs_err=abs_err, backup=self._buf("backup", (B,), device), a_star=a_star))["stats"]
+        else:
+            self.backup_path = "composed"
+            q_max = torch.max(self._rnn_net("q_target@o2", nets.q_target, o2).forward(o2), dim=1)[0]
+            backup = batch["rew"] * self.reward_scale + self.gamma * (1 - batch["done"]) * q_max
+            net.forward(o, out=q_all)
+            key = ("dqn_loss", str(device))
+            dl = self._cache.get(key)
+            if dl is None:
+                dl = self._cache[key] = hb.DqnLoss(device)
+            stats = dl.run(q_all, act, backup, weight, seed=seed, abs_err=abs_err)[2]
+        _flat_grads(nets.q)
+        net.backward(o, seed, nets.q.hip_rnn_grad())
         head = torch.cat([stats, stats[:1] * 0])
         return torch.cat([head, abs_err]) if self.per_flag else head

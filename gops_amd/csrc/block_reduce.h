@@ -1,8 +1,11 @@
-// The deterministic sum (or minimum) over a batch that the loss kernels share, for workgroups of 256 threads.  The order is fixed
+// The deterministic sum (or minimum) over a batch that the loss kernels share, for workgroups of 256 threads (W = 4 waves; the tile
+// kernel of rnn_dqn.hip runs it on W = 8).  The order is fixed
 // and depends on the batch size only: every thread adds its own elements in index order; block_fold combines the 64 lanes of each
-// wave with a butterfly (xor 32, 16, ... 1) and then the four waves as (w0 + w1) + (w2 + w3); with more than one block, every
+// wave with a butterfly (xor 32, 16, ... 1) and then the four waves as (w0 + w1) + (w2 + w3) (eight: that of waves 0 - 3 plus that of
+// waves 4 - 7); with more than one block, every
 // block parks its totals in global memory and draws a ticket (last_block), and the block that draws the last one reads the
-// totals - block b in thread b - and folds them with the same block_fold, i.e. in block index order.  No block waits on another.
+// totals - block b in thread b (beyond blockDim.x blocks: thread b adds blocks b, b + blockDim.x, .. in that order) - and folds them
+// with the same block_fold, i.e. in block index order.  No block waits on another.
 // grid_fold is that sequence for sums and what the kernels call; block_fold and last_block stand alone only in dsact.hip's mixed
 // sum-and-minimum fold and in dw_gemm.hip's one-block sum.
 #pragma once
@@ -16,9 +19,11 @@
 // What an entry point asks of the `stats` / state buffer it hands to these folds: the partial sums behind the results are doubles.
 inline bool stats_aligned(const void* stats) { return (reinterpret_cast<uintptr_t>(stats) & 7) == 0; }
 
-// s[i] <- the block's sum (MIN: minimum) of s[i], in every thread.  red: N rows of 4 doubles of LDS, reusable right after.
-template <int N, bool MIN>
-__device__ __forceinline__ void block_fold(double (&s)[N], double (*red)[4]) {
+// s[i] <- the block's sum (MIN: minimum) of s[i], in every thread.  red: N rows of W (= waves of the block: 4 or 8) doubles of LDS,
+// reusable right after.
+template <int N, bool MIN, int W>
+__device__ __forceinline__ void block_fold(double (&s)[N], double (*red)[W]) {
+    static_assert(W == 4 || W == 8, "blocks of 256 or 512 threads");
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
@@ -34,13 +39,20 @@ __device__ __forceinline__ void block_fold(double (&s)[N], double (*red)[4]) {
     }
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < N; ++i)
+    for (int i = 0; i < N; ++i) {
         s[i] = MIN ? fmin(fmin(red[i][0], red[i][1]), fmin(red[i][2], red[i][3])) : (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
+        if constexpr (W == 8) {
+            const double hi = MIN ? fmin(fmin(red[i][4], red[i][5]), fmin(red[i][6], red[i][7]))
+                                  : (red[i][4] + red[i][5]) + (red[i][6] + red[i][7]);
+            s[i] = MIN ? fmin(s[i], hi) : s[i] + hi;
+        }
+    }
 }
 
 // Publishes this block's partial values in row blockIdx.x of part[gridDim.x][stride] and draws a ticket; true in every thread of
-// the block that drew the last one, which then holds in `v` the values of block threadIdx.x (zeros where there is no such block)
-// and has left the ticket zero.  The ticket must be zero on entry; gridDim.x <= 256.
+// the block that drew the last one, which then holds in `v` the values of block threadIdx.x (zeros where there is no such block; with
+// more blocks than threads: plus those of blocks threadIdx.x + blockDim.x, + 2 blockDim.x, .. added in that order) and has left the
+// ticket zero.  The ticket must be zero on entry.
 template <int N>
 __device__ __forceinline__ bool last_block(double (&v)[N], double* part, int stride, unsigned* ticket, bool* last) {
     if (threadIdx.x == 0) {
@@ -55,6 +67,10 @@ __device__ __forceinline__ bool last_block(double (&v)[N], double* part, int str
     const volatile double* vp = part;
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = threadIdx.x < gridDim.x ? vp[stride * threadIdx.x + i] : 0.0;
+    for (unsigned b = threadIdx.x + blockDim.x; b < gridDim.x; b += blockDim.x) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] += vp[(size_t)stride * b + i];
+    }
     if (threadIdx.x == 0) *ticket = 0u;
     return true;
 }
@@ -62,8 +78,8 @@ __device__ __forceinline__ bool last_block(double (&v)[N], double* part, int str
 // The whole idiom for sums: s[i] <- the block's sums and, with more than one block, in the block that draws the last ticket the
 // grid's.  True in the threads that hold the final sums: every thread of the one block, or of the last one.  red, part / stride /
 // ticket, last: as block_fold's and last_block's (part and ticket are not touched by a grid of one block).
-template <int N>
-__device__ __forceinline__ bool grid_fold(double (&s)[N], double (*red)[4], double* part, int stride, unsigned* ticket, bool* last) {
+template <int N, int W>
+__device__ __forceinline__ bool grid_fold(double (&s)[N], double (*red)[W], double* part, int stride, unsigned* ticket, bool* last) {
     block_fold<N, false>(s, red);
     bool fin = gridDim.x == 1;
     if (!fin) {

@@ -26,45 +26,16 @@
 #include "common.h"
 #include "rnn_tile.h"
 
-#define RNN_GRID_MAX 256                                      // workgroups (= slots) of the sweep
 #define RNN_MAX_SEGS (3 + 2 * GOPS_MAX_LAYERS * GOPS_RNN_MAX_HEADS)
 #define RNN_MAX_XB (GOPS_RNN_MAX_OBS / 16)                    // 16-column blocks of the padded x tile
 
-struct RnnHeadDev {
-    int nl, act, yoff, pad_;
-    int dims[GOPS_MAX_LAYERS + 1];
-    const float* w[GOPS_MAX_LAYERS];   // torch layout [dims[l + 1]][dims[l]]
-    const float* b[GOPS_MAX_LAYERS];
-    float* sh[GOPS_MAX_LAYERS];        // stash of hidden layer l's activation [Bpad][dims[l + 1]] (l < nl - 1) ...
-    float* sd[GOPS_MAX_LAYERS];        // ... and of act'(z)
-    int off_w[GOPS_MAX_LAYERS], off_b[GOPS_MAX_LAYERS];   // floats from the start of a slot
-};
-struct RnnDev {
-    int B, Bpad, L, O, O16, H, nheads, ny;
-    int ldw, ldx;                      // LDS leading dims of the hidden / x tiles (floats)
-    int off_wih, off_whh, off_b, P;    // slot layout, floats per slot
-    int G, pad_;                       // slots
-    const float *wih, *whh, *bih, *bhh;
-    float* hst;                        // [L][Bpad][H]
-    float* slots;                      // [G][P]
-    RnnHeadDev head[GOPS_RNN_MAX_HEADS];
-};
+// (RnnHeadDev, RnnDev, rnn_stage_x: rnn_tile.h)
 struct RnnSegs {   // the slot layout as (start, destination) pairs for the reduce
     int n, G, P, pad_;
     int start[RNN_MAX_SEGS + 1];
     float* dst[RNN_MAX_SEGS];
     float* dst2[RNN_MAX_SEGS];         // db goes to bias_ih and bias_hh
 };
-
-// x_t of the tile -> xs [TB][ldx], columns O .. O16 - 1 and rows beyond B zero
-__device__ __forceinline__ void rnn_stage_x(const RnnDev& p, const float* x, int row0, int t, float* xs, int tid) {
-    for (int idx = tid; idx < TB * p.O16; idx += NTHREADS) {
-        const int m = idx / p.O16, o = idx - m * p.O16;
-        float v = 0.f;
-        if (row0 + m < p.B && o < p.O) v = gptr(x)[((size_t)(row0 + m) * p.L + t) * p.O + o];
-        xs[m * p.ldx + o] = v;
-    }
-}
 
 // (rnn_dense, the forward orientation of a head's layer: rnn_tile.h)
 // [TB][K] = D [TB][N] (LDS, columns up to the next multiple of 16 zero) W, W [N][K]; blocks of 16 columns k dealt to the waves.
@@ -116,118 +87,31 @@ __device__ __forceinline__ void rnn_dw(const float* D, int ldd, int N, const flo
 template <int NB>
 __global__ __launch_bounds__(NTHREADS) void rnn_fwd_kernel(const RnnDev p, const float* __restrict__ x, float* __restrict__ y) {
     extern __shared__ float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
-    const int H = p.H, nhb = H >> 4, ldw = p.ldw, ldx = p.ldx, L = p.L;
-    const int row0 = blockIdx.x * TB, nk = (p.O + 3) >> 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
+    const int ldw = p.ldw, ldx = p.ldx, L = p.L;
+    const int row0 = blockIdx.x * TB;
     float* const hb = lds;
     float* const xb = lds + 3 * TB * ldw;
 
-    // the wave's blocks of W_hh and W_ih, and the summed bias of its columns: resident for all L steps
-    f32x4 whh[4 * NB][NB];
-    float wih[GOPS_RNN_MAX_OBS / 4][NB], bias[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int nt = wave + 4 * j, n = 16 * nt + l15;
-        const bool ok = nt < nhb;
-        bias[j] = ok ? gptr(p.bih)[n] + gptr(p.bhh)[n] : 0.f;
-#pragma unroll
-        for (int c = 0; c < 4 * NB; ++c) {
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            whh[c][j] = (ok && c < nhb) ? ld4(gptr(p.whh) + (size_t)n * H + 16 * c + 4 * g) : z;
-        }
-#pragma unroll
-        for (int kc = 0; kc < GOPS_RNN_MAX_OBS / 4; ++kc) {
-            const int k = 4 * kc + g;
-            wih[kc][j] = (ok && k < p.O) ? gptr(p.wih)[(size_t)n * p.O + k] : 0.f;
-        }
-    }
+    RnnRegs<NB> w;
+    rnn_load_regs<NB>(p, wave, lane, w);
     rnn_stage_x(p, x, row0, 0, xb, tid);
     __syncthreads();
 
     for (int t = 0; t < L; ++t) {
-        const int cur = t & 1;
-        const float* hr = hb + cur * TB * ldw;          // h_t (t = 0: h_0 = 0, not read)
-        float* hw = hb + (cur ^ 1) * TB * ldw;
-        const float* xs = xb + cur * TB * ldx;
-        if (wave < nhb) {
-            f32x4 acc[NB] = {};
-#pragma unroll
-            for (int kc = 0; kc < GOPS_RNN_MAX_OBS / 4; ++kc)
-                if (kc < nk) {
-                    const float a = xs[l15 * ldx + 4 * kc + g];
-#pragma unroll
-                    for (int j = 0; j < NB; ++j) acc[j] = mfma4(a, wih[kc][j], acc[j]);
-                }
-            if (t > 0) {
-#pragma unroll
-                for (int c = 0; c < 4 * NB; ++c)
-                    if (c < nhb) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(hr + l15 * ldw + 16 * c + 4 * g);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int j = 0; j < NB; ++j) acc[j] = mfma4(a[i], whh[c][j][i], acc[j]);
-                    }
-            }
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const int nt = wave + 4 * j, n = 16 * nt + l15;
-                if (nt < nhb) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = 4 * g + r;
-                        const float v = tanhf(acc[j][r] + bias[j]);
-                        hw[row * ldw + n] = v;
-                        gptr(p.hst)[((size_t)t * p.Bpad + row0 + row) * H + n] = v;
-                    }
-                }
-            }
-        }
+        const int cur = t & 1;   // h_t in hidden tile cur, h_{t+1} into the other
+        rnn_step<NB>(p, w, t, row0, hb + cur * TB * ldw, hb + (cur ^ 1) * TB * ldw, xb + cur * TB * ldx, true, wave, lane);
         if (t + 1 < L) rnn_stage_x(p, x, row0, t + 1, xb + (cur ^ 1) * TB * ldx, tid);
         __syncthreads();
     }
 
-    // the heads on h_L = hidden tile (L & 1); the other two tiles take their hidden layers in turn
-    const float* hL = hb + (L & 1) * TB * ldw;
-    float* const pp[2] = {hb + ((L & 1) ^ 1) * TB * ldw, hb + 2 * TB * ldw};
-    for (int hd = 0; hd < p.nheads; ++hd) {
-        const RnnHeadDev& hp = p.head[hd];
-        const float* in = hL;
-        for (int l = 0; l < hp.nl; ++l) {
-            const int K = hp.dims[l], N = hp.dims[l + 1];
-            const float* bl = hp.b[l];
-            if (l + 1 < hp.nl) {
-                float* out = (l & 1) ? pp[1] : pp[0];
-                float *sh = hp.sh[l], *sd = hp.sd[l];
-                act_dispatch(hp.act, [&]<int ACT>() {
-                    rnn_dense(in, ldw, K, hp.w[l], N, lane, wave, [&](const f32x4& acc, int n, bool) {
-                        const float bn = gptr(bl)[n];
+    rnn_heads(p, hb, row0, true, lane, wave, [&](const RnnHeadDev& hp, const f32x4& acc, float bn, int n) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 4 * g + r;
-                            float h, dh;
-                            rnn_act_pair<ACT>(acc[r] + bn, h, dh);
-                            out[row * ldw + n] = h;
-                            gptr(sh)[(size_t)(row0 + row) * N + n] = h;
-                            gptr(sd)[(size_t)(row0 + row) * N + n] = dh;
-                        }
-                    });
-                });
-                in = out;
-            } else {
-                rnn_dense(in, ldw, K, hp.w[l], N, lane, wave, [&](const f32x4& acc, int n, bool ok) {
-                    if (!ok) return;
-                    const float bn = gptr(bl)[n];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = row0 + 4 * g + r;
-                        if (row < p.B) gptr(y)[(size_t)row * p.ny + hp.yoff + n] = acc[r] + bn;
-                    }
-                });
-            }
-            __syncthreads();
+        for (int r = 0; r < 4; ++r) {
+            const int row = row0 + 4 * g + r;
+            if (row < p.B) gptr(y)[(size_t)row * p.ny + hp.yoff + n] = acc[r] + bn;
         }
-    }
+    });
 }
 
 // ---- backward sweep -------------------------------------------------------------------------------------------------------------------
@@ -418,59 +302,7 @@ __global__ __launch_bounds__(NTHREADS) void rnn_reduce_kernel(const float* __res
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-// (the checks of the description - rnn_check - : rnn_tile.h)
-struct RnnPlan {
-    RnnDev dev;
-    size_t bytes, lds_fwd, lds_bwd;
-    int ntiles;
-};
-
-// the device description of a checked net: slot layout, LDS sizes and - with a workspace - the stash sections
-static RnnPlan rnn_plan(const GopsRnn& d, int B, void* ws) {
-    RnnPlan pl = {};
-    RnnDev& p = pl.dev;
-    p.B = B; p.Bpad = (B + TB - 1) / TB * TB; p.L = d.seq_len; p.O = d.obs_dim; p.O16 = (d.obs_dim + 15) / 16 * 16; p.H = d.hidden;
-    p.nheads = d.n_heads;
-    p.wih = d.weight_ih; p.whh = d.weight_hh; p.bih = d.bias_ih; p.bhh = d.bias_hh;
-    pl.ntiles = p.Bpad / TB;
-    p.G = pl.ntiles < RNN_GRID_MAX ? pl.ntiles : RNN_GRID_MAX;
-    char* base = static_cast<char*>(ws);
-    size_t off = 0;
-    auto section = [&](size_t floats) {
-        float* at = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        off += align256(floats * sizeof(float));
-        return at;
-    };
-    p.hst = section((size_t)p.L * p.Bpad * p.H);
-    int maxw = p.H, slot = 0;
-    p.off_wih = slot; slot += p.H * p.O;
-    p.off_whh = slot; slot += p.H * p.H;
-    p.off_b = slot; slot += p.H;
-    for (int h = 0; h < d.n_heads; ++h) {
-        const GopsMlp& m = d.head[h];
-        RnnHeadDev& hd = p.head[h];
-        hd.nl = m.n_layers; hd.act = m.hidden_act; hd.yoff = p.ny;
-        p.ny += m.sizes[m.n_layers];
-        for (int l = 0; l <= m.n_layers; ++l) hd.dims[l] = m.sizes[l];
-        for (int l = 0; l < m.n_layers; ++l) {
-            hd.w[l] = m.weight[l]; hd.b[l] = m.bias[l];
-            hd.off_w[l] = slot; slot += m.sizes[l + 1] * m.sizes[l];
-            hd.off_b[l] = slot; slot += m.sizes[l + 1];
-            if (l + 1 < m.n_layers) {
-                maxw = m.sizes[l + 1] > maxw ? m.sizes[l + 1] : maxw;
-                hd.sh[l] = section((size_t)p.Bpad * m.sizes[l + 1]);
-                hd.sd[l] = section((size_t)p.Bpad * m.sizes[l + 1]);
-            }
-        }
-    }
-    p.P = slot;
-    p.slots = section((size_t)p.G * p.P);
-    p.ldw = maxw + 4; p.ldx = p.O16 + 4;
-    pl.bytes = off;
-    pl.lds_fwd = (size_t)(3 * TB * p.ldw + 2 * TB * p.ldx) * sizeof(float);
-    pl.lds_bwd = (size_t)(4 * TB * p.ldw + TB * p.ldx) * sizeof(float);
-    return pl;
-}
+// (the checks of the description - rnn_check - and its plan - rnn_plan -: rnn_tile.h)
 
 extern "C" {
 

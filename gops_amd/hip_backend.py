@@ -247,6 +247,10 @@ class GopsRnnGrad(C.Structure):
                 ("head", GopsMlpGrad * RNN_MAX_HEADS)]
 
 
+class GopsRnnDqn(C.Structure):   # gops_rnn_dqn_step
+    _fields_ = [("act_num", C.c_int32), ("reserved", C.c_int32), ("reward_scale", C.c_double), ("gamma", C.c_double)]
+
+
 CONV_MAX_LAYERS, CONV_MAX_KERNEL, CONV_MAX_STRIDE, CONV_MAX_CHANNELS, CONV_MAX_EXTENT = 6, 8, 4, 256, 128   # include/gops_hip.h: GOPS_CONV_*
 
 
@@ -357,6 +361,8 @@ def _signatures():
         "gops_rnn_workspace_bytes": (sz, [P(GopsRnn), i32]),
         "gops_rnn_forward": (rc, [P(GopsRnn), i32, vp, vp, vp, sz, vp]),
         "gops_rnn_backward": (rc, [P(GopsRnn), i32, vp, vp, P(GopsRnnGrad), vp, sz, vp]),
+        "gops_rnn_dqn_step_workspace_bytes": (sz, [P(GopsRnn), P(GopsRnn), P(GopsRnnDqn), i32]),
+        "gops_rnn_dqn_step": (rc, [P(GopsRnn), P(GopsRnn), P(GopsRnnDqn), i32] + [vp] * 13 + [sz, vp, sz, vp]),
         "gops_stack_sample_workspace_bytes": (sz, [env, P(GopsRnn), i32, i32]),
         "gops_stack_sample_rollout": (rc, [env, P(GopsRnn), P(GopsSampleDesc), i32, i32, P(GopsSampleState), P(GopsSamplePool), vp,
                                            P(GopsSampleOut), vp, sz, vp]),
@@ -1558,6 +1564,50 @@ class RnnNet:
         """From the stash the last `forward` of this object left: every gradient tensor of `grads` is overwritten."""
         assert grad_y.numel() == self.batch * self.out_dim
         _call("gops_rnn_backward", C.byref(self.rnn), self.batch, _ptr(x), _ptr(grad_y), C.byref(grads), *_ws(self))
+
+
+class RnnDqnStep:
+    """DQN's step on recurrent ActionValueDis networks up to the backward, in ONE launch (`gops_rnn_dqn_step`, csrc/rnn_dqn.hip): the
+    target net on obs2 with its maximum, arg-max and backup, the online net on obs with `RnnNet.forward`'s stash, the dense seed,
+    |q_sel - backup| and the loss scalars.  `q` / `target`: `GopsRnn` views (`make_rnn`) of the online and the target network, read in
+    place at every call.  `net`: the online network's `RnnNet` - the launch stashes into ITS workspace, so `net.backward(obs, seed,
+    grads)` follows a `run`; this object owns only the launch's own scratch (zero before the first call, left zero).  `supported` is
+    False for a pair the kernel does not hold: the caller then composes the step from `RnnNet.forward`, `torch.max` and `DqnLoss`."""
+
+    def __init__(self, q: GopsRnn, target: GopsRnn, batch: int, device: Optional[torch.device] = None, net: Optional[RnnNet] = None):
+        self.batch = int(batch)
+        self.desc = GopsRnnDqn()
+        self.act_num = self.desc.act_num = int(q.head[0].sizes[q.head[0].n_layers])
+        self.net = RnnNet(q, self.batch, device) if net is None else net
+        self.set_nets(q, target)
+        _own_workspace(self, lib().gops_rnn_dqn_step_workspace_bytes(C.byref(q), C.byref(target), C.byref(self.desc), self.batch), device)
+        self.workspace.zero_()
+        self.stats = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def set_nets(self, q: GopsRnn, target: GopsRnn):
+        self.q, self.target = q, target   # (the descriptions hold raw pointers and keep their tensors alive)
+        self.net.rnn = q
+
+    def run(self, obs, obs2, act, rew, done, weight=None, *, reward_scale=1.0, gamma=0.99,
+            out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """-> {"q_all" [B, act_num], "backup" [B], "a_star" [B] int32, "seed" [B, act_num], "abs_err" [B], "stats" [3]: loss,
+        mean(q_sel), rows whose action index is out of range}; `out` supplies output tensors instead of fresh ones.  Enqueues only."""
+        B, N, d = self.batch, self.act_num, self.desc
+        assert obs.shape[0] == B and obs.numel() == obs2.numel() == B * self.q.seq_len * self.q.obs_dim
+        assert act.numel() == B and rew.numel() == B and done.numel() == B and (weight is None or weight.numel() == B)
+        d.reward_scale, d.gamma = float(reward_scale), float(gamma)
+        res = dict(out or {})
+        for k, shape in dict(q_all=(B, N), backup=(B,), a_star=(B,), seed=(B, N), abs_err=(B,)).items():
+            if k not in res:
+                res[k] = torch.empty(shape, dtype=torch.int32 if k == "a_star" else torch.float32, device=self.device)
+            assert res[k].numel() == int(np.prod(shape)) and res[k].is_contiguous()
+        a_star = res["a_star"]
+        assert a_star.is_cuda and a_star.dtype == torch.int32
+        _call("gops_rnn_dqn_step", C.byref(self.q), C.byref(self.target), C.byref(d), B, _ptr(obs), _ptr(obs2), _ptr(act), _ptr(rew),
+              _ptr(done), _ptr(weight), _ptr(res["q_all"]), _ptr(res["backup"]), a_star.data_ptr(), _ptr(res["seed"]), _ptr(res["abs_err"]),
+              self.stats.data_ptr(), self.net.workspace.data_ptr(), self.net._workspace_bytes, *_ws(self))
+        res["stats"] = self.stats[:3]
+        return res
 
 
 class ConvStack:

@@ -1419,6 +1419,43 @@ int gops_rnn_forward(const GopsRnn* net, int32_t batch, const float* x, float* y
 int gops_rnn_backward(const GopsRnn* net, int32_t batch, const float* x, const float* grad_y, const GopsRnnGrad* grad, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ABI v15, additive entry points (the version number stays 15): DQN on recurrent ActionValueDis networks - the target recurrence, the
+ * online recurrence and the TD seam between them in ONE launch (csrc/rnn_dqn.hip).  `online` and `target`: two GopsRnn with ONE head
+ * each and the same seq_len, obs_dim, hidden and head widths, the head's output width = desc->act_num.  Per batch row b:
+ *     q_targ [act_num] = target(obs2[b])                  nothing of the target net is stashed or stored
+ *     a_star[b] = argmax_a q_targ[a]                      the LOWEST index attaining the maximum; a NaN counts as the maximum
+ *     backup[b] = rew * reward_scale + gamma * (1 - done) * q_targ[a_star]     formed in double, rounded once
+ *     q_all[b, :] = online(obs[b])                        with exactly the stash gops_rnn_forward leaves in `rnn_workspace`
+ *     q_sel = q_all[b, act[b]]                            act [B]: the index as a float, by truncation towards zero
+ *     seed[b, :] = (2 / B) weight (q_sel - backup) in column act[b], an explicit 0 in every other (dense: gops_rnn_backward's grad_y)
+ *     abs_err[b] = |q_sel - backup|
+ *     stats[0] = mean(weight (q_sel - backup)^2), stats[1] = mean(q_sel), stats[2] = the number of rows whose index lies outside
+ *     [0, act_num) - such a row (a NaN index included) gets an all-zero seed row and abs_err 0 and adds nothing to the sums (the means
+ *     still divide by B); stats[3] = 0.  `stats`: four floats.  `weight` [B] or NULL (= ones).
+ * The seam's definitions are gops_dqn_backup's and gops_dqn_loss's.  A workgroup of 512 threads owns GOPS_TILE transitions: four
+ * waves carry the online net and four the target net, each as gops_rnn_forward maps a net to its four waves, so q_all and the stash
+ * are bit-equal to gops_rnn_forward's on the same inputs and gops_rnn_backward(online, .., seed, .., rnn_workspace) follows unchanged.
+ * The sums are doubles: per tile, parked in `workspace`, added in tile order by the workgroup that finishes last - no float atomics,
+ * equal inputs give equal bits.  Rows beyond B are computed on zeros, never stored, and add nothing.
+ * `rnn_workspace`: the ONLINE net's, of gops_rnn_workspace_bytes(online, batch).  `workspace`: 8-byte aligned device memory of
+ * gops_rnn_dqn_step_workspace_bytes, ALL ZERO before the first call (the tiles' partial sums and a ticket the call leaves zero again).
+ * GOPS_ERR_BAD_ARG: a NULL pointer (weight excepted), batch < 1, n_heads != 1 on either net, and gops_rnn_forward's cases.
+ * GOPS_ERR_UNSUPPORTED: nets that differ in seq_len, obs_dim, hidden or a head width; an output width that is not act_num; act_num
+ *   outside 2 .. GOPS_DQN_MAX_ACTIONS; gops_rnn_forward's cases (the GOPS_RNN_* limits, fp32 only).
+ * GOPS_ERR_WORKSPACE: either workspace NULL, misaligned or below its size.  Nothing is launched in any of these cases; the workspace
+ *   query returns 0 for a pair the entry point rejects. */
+struct GopsRnnDqn {
+    int32_t act_num;
+    int32_t reserved;
+    double reward_scale, gamma;
+};
+typedef struct GopsRnnDqn GopsRnnDqn;
+size_t gops_rnn_dqn_step_workspace_bytes(const GopsRnn* online, const GopsRnn* target, const GopsRnnDqn* desc, int32_t batch);
+int gops_rnn_dqn_step(const GopsRnn* online, const GopsRnn* target, const GopsRnnDqn* desc, int32_t batch, const float* obs,
+                      const float* obs2, const float* act, const float* rew, const float* done, const float* weight, float* q_all,
+                      float* backup, int32_t* a_star, float* seed, float* abs_err, float* stats, void* rnn_workspace,
+                      size_t rnn_workspace_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ABI v15, additive entry points (the version number stays 15): the closed loops of gops_sample_rollout and
  * gops_episode_rollout_mode on gym_cartpolecontiwithstack (gops/env/env_gym/gym_cartpolecontiwithstack.py) under a RECURRENT
  * StochaPolicy - a GopsRnn with two heads, mean and raw log std, one output each (csrc/rollout_stack.hip).  The observation is the
